@@ -33,6 +33,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
                   ranks (weak scaling in rows; one all-reduce of the gradients per pass);
                   "concurrent_paths": the headline path on three engines of one GPU at once (per rank).
                   `--no-extra` skips them.
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what its last step returned (`path_outputs`) as
+DIR/<name>.npy in float64, at most 64 MB in all.  The dataset and the path are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -105,6 +109,39 @@ def measured_traffic(n, p, lanes, kernel):
         return t["hbm_bytes_per_launch"], f"PMC passes of commit {on.get('commit', '?')[:12]}, {t.get('source')}"
     except (OSError, KeyError, ValueError) as exc:
         return None, f"profiles/roofline_traffic.json unreadable: {exc!r}"
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def path_outputs(res):
+    """The arrays a caller of the timed path receives (the PathResult of ``Dataset.solve_path``), copied out of the call's
+    result blocks as float64: the solutions, the per-point records and the inverse step at the last point."""
+    out = {"betas": np.array(res.betas, dtype=np.float64)}
+    if res.group_norms is not None:
+        out["group_norms"] = np.array(res.group_norms, dtype=np.float64)
+    for name in ("n_iter", "status", "mode", "resid", "beta_norm", "loss", "kkt", "mu"):
+        out[name] = np.asarray(getattr(res, name), dtype=np.float64)
+    out["L"] = np.array([res.L], dtype=np.float64)
+    return out
+
+
+def write_dump(arrays, directory, limit=DUMP_LIMIT_BYTES):
+    """``directory/<name>.npy`` for every array.  Past ``limit`` bytes in all, the (points x columns) arrays keep a fixed,
+    seeded sample of their columns, the same fraction of each, and ``<name>_columns.npy`` records which ones were kept."""
+    os.makedirs(directory, exist_ok=True)
+    wide = [k for k in ("betas", "group_norms") if k in arrays]
+    narrow = sum(a.nbytes for k, a in arrays.items() if k not in wide)
+    per_column = sum(arrays[k].shape[1] * (arrays[k].shape[0] + 1) * 8 for k in wide)  # (a kept column and its index)
+    if narrow + sum(arrays[k].nbytes for k in wide) > limit:
+        keep = (limit - narrow) / per_column
+        for k in wide:
+            cols = arrays[k].shape[1]
+            idx = np.sort(np.random.default_rng(0).choice(cols, max(1, int(cols * keep)), replace=False))
+            arrays[k] = np.ascontiguousarray(arrays[k][:, idx])
+            arrays[f"{k}_columns"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def make_coef(p, n_informative, seed):
@@ -1063,7 +1100,11 @@ def main():
     ap.add_argument("--extra-timeout", type=float, default=360.0, help="hard limit (s) on the extra legs")
     ap.add_argument("--rowshard-rows", type=int, default=125_000, help="rows per rank of the row-sharded leg")
     ap.add_argument("--rowshard-cols", type=int, default=10_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0's path) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -1156,6 +1197,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert res is not None
+    if args.dump_outputs and rank == 0:
+        write_dump(path_outputs(res), args.dump_outputs)
     info = eng.device_info()
     per_rank = all_gather({"rank": rank, "local_rank": local_rank, "device": device_id, "name": info["name"],
                            "seconds": my_elapsed, "converged": bool(res.converged),

@@ -62,3 +62,44 @@ def test_strong_scaling_object_and_cpu_baseline_layout():
     cb = bench.stock_first(both, 50, 100000, 5000)
     assert cb["kind"] == "stock" and cb["value"] == 18.5 and cb["port"]["kind"] == "port" and cb["port"]["value"] == 2.4
     assert {"value", "unit", "cores", "kind", "sample"} <= set(cb) and {"value", "unit", "cores", "kind", "sample"} <= set(cb["port"])
+
+
+def test_dump_outputs_writes_the_path_result_in_float64(tmp_path):
+    """--dump-outputs: every array of the path's result as DIR/<name>.npy, float64, the same on a second write."""
+    bench = _bench()
+
+    class FakeResult:  # the attributes of sparselm_amd._engine.PathResult that path_outputs reads
+        betas = np.arange(12.0).reshape(3, 4)
+        group_norms = None
+        n_iter = np.array([5, 6, 7])
+        status = np.zeros(3, dtype=np.int64)
+        mode = np.array([1, 1, 0])
+        resid = beta_norm = loss = kkt = mu = np.array([0.5, 0.25, 0.125])
+        L = 3.5
+
+    arrays = bench.path_outputs(FakeResult())
+    assert set(arrays) == {"betas", "n_iter", "status", "mode", "resid", "beta_norm", "loss", "kkt", "mu", "L"}
+    bench.write_dump(arrays, str(tmp_path / "a"))
+    bench.write_dump(bench.path_outputs(FakeResult()), str(tmp_path / "b"))
+    for name in arrays:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "betas.npy"), FakeResult.betas)
+    assert np.load(tmp_path / "a" / "L.npy")[0] == 3.5
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_columns_past_the_limit(tmp_path):
+    bench = _bench()
+    rng = np.random.default_rng(3)
+    arrays = {"betas": rng.standard_normal((10, 1000)), "group_norms": rng.standard_normal((10, 100)), "loss": np.ones(10)}
+    limit = 20_000
+    bench.write_dump(dict(arrays), str(tmp_path / "a"), limit=limit)
+    bench.write_dump(dict(arrays), str(tmp_path / "b"), limit=limit)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["betas.npy", "betas_columns.npy", "group_norms.npy", "group_norms_columns.npy", "loss.npy"]
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= limit
+    for key in ("betas", "group_norms"):
+        cols = np.load(tmp_path / "a" / f"{key}_columns.npy")
+        np.testing.assert_array_equal(cols, np.load(tmp_path / "b" / f"{key}_columns.npy"))
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{key}.npy"), arrays[key][:, cols.astype(np.int64)])
