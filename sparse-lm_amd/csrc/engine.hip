@@ -127,6 +127,7 @@ static const size_t kPoolMinBytes = (size_t)64 << 20;
 // idle blocks kept per process: 24 GB unless SLM_DEVICE_POOL_GB says otherwise (0 turns the pool off) -- a block idle here is
 // memory no other allocator on the GPU can have (another rank sharing the device, torch, RCCL's buffers): enough for the two
 // or three blocks of the largest dataset shape seen lately, not a standing reservation
+// (read where a block is freed, from whichever call frees it: the one knob below the entry points, a single field)
 static size_t pool_idle_cap() {
   const double gb = knobs().device_pool_gb;
   return gb >= 0.0 ? (size_t)(gb * (double)((size_t)1 << 30)) : (size_t)24 << 30;
@@ -164,7 +165,7 @@ void pool_free(void* p) {
   {
     std::lock_guard<std::mutex> lk(g_pool.m);
     // (over the cap: the blocks that have waited longest go back to the driver first)
-    kept = g_pool.book.give_back(p, pool_idle_cap(), knobs().device_pool, &evict);
+    kept = g_pool.book.give_back(p, pool_idle_cap(), true, &evict);
   }
   for (void* q : evict) (void)hipFree(q);
   if (!kept) (void)hipFree(p);
@@ -176,11 +177,12 @@ void pool_free(void* p) {
 extern "C" int slm_abi_version(void) { return SLM_ABI_VERSION; }
 
 // The environment is read HERE and nowhere else: once, when the first caller asks (host_logic.hpp: Knobs), and again when
-// slm_reload_knobs says so (tests and A/B tools that change a variable after the library is loaded).
+// slm_reload_knobs says so (tests and A/B tools that change a variable after the library is loaded).  Callers get a copy
+// made under the lock: a reload while a solve runs on another thread leaves that solve's settings as they were.
 static std::mutex g_knobs_m;
 static slm_host::Knobs g_knobs;
 static bool g_knobs_loaded = false;
-const slm_host::Knobs& knobs() {
+slm_host::Knobs knobs() {
   std::lock_guard<std::mutex> lk(g_knobs_m);
   if (!g_knobs_loaded) {
     g_knobs = slm_host::Knobs::from([](const char* name) -> const char* { return getenv(name); });
@@ -362,7 +364,7 @@ int set_singleton_groups(slm_dataset* ds) {
 }
 
 // Allocates everything that depends only on (n, p): padded X, vectors, work space.
-static int dataset_alloc(slm_engine* eng, int64_t n, int64_t p, slm_dataset** out) {
+static int dataset_alloc(const slm_host::Knobs& kn, slm_engine* eng, int64_t n, int64_t p, slm_dataset** out) {
   if (n <= 0 || p <= 0) return fail(SLM_ERR_BAD_ARG, "n and p must be positive (got %lld x %lld)",
                                     (long long)n, (long long)p);
   if (p > (int64_t)TAIL_THREADS * kMaxTailE)
@@ -378,7 +380,7 @@ static int dataset_alloc(slm_engine* eng, int64_t n, int64_t p, slm_dataset** ou
   const int64_t ld = ds->ld;
   size_t partial_elems = 0, loss_elems = 0;
   for (int B = 1; B <= kMaxLanes; ++B) {
-    const GradKernel* gk = pick_grad_kernel(ld / 2, B);
+    const GradKernel* gk = pick_grad_kernel(kn, ld / 2, B);
     ds->gk[B - 1] = gk;
     if (!gk) continue;
     int occ = 2;
@@ -386,9 +388,7 @@ static int dataset_alloc(slm_engine* eng, int64_t n, int64_t p, slm_dataset** ou
       hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)gk->fn, gk->W * 64, 0);
       if (e != hipSuccess || occ < 1) occ = 1;
     }
-    int per_cu = occ;
-    if (knobs().grad_blocks_per_cu > 0) per_cu = knobs().grad_blocks_per_cu;
-    int64_t nblk = (int64_t)eng->cus * per_cu;
+    int64_t nblk = (int64_t)eng->cus * occ;
     const int64_t steps = (n + gk->R - 1) / gk->R;
     nblk = std::max<int64_t>(1, std::min<int64_t>(nblk, steps));
     ds->nblk[B - 1] = (int)nblk;
@@ -399,7 +399,7 @@ static int dataset_alloc(slm_engine* eng, int64_t n, int64_t p, slm_dataset** ou
     delete ds;
     return fail(SLM_ERR_UNSUPPORTED, "no gradient kernel covers p = %lld", (long long)p);
   }
-  ds->sk = pick_split_kernel(ld / 2);
+  ds->sk = pick_split_kernel(kn, ld / 2);
   if (ds->sk) {
     ds->split_nblk = (int)std::max<int64_t>(1, std::min<int64_t>(eng->cus, n));  // one ring workgroup per CU
     // (xtr_mfma_kernel's row blocks; the residual kernels' split_nblk blocks only write R and loss_partial)
@@ -496,7 +496,7 @@ extern "C" int slm_dataset_create(slm_engine* eng, const double* X, int64_t n, i
     return fail(SLM_ERR_BAD_ARG, "X must be C- or F-contiguous along one axis (strides %lld, %lld)",
                 (long long)row_stride, (long long)col_stride);
   slm_dataset* ds = nullptr;
-  SLM_TRY(dataset_alloc(eng, n, p, &ds));
+  SLM_TRY(dataset_alloc(knobs(), eng, n, p, &ds));
   int rc = SLM_OK;
   hipError_t e = hipSuccess;
   if (c_order) {
@@ -541,7 +541,7 @@ extern "C" int slm_dataset_create_device(slm_engine* eng, const double* dX, int6
   if (ld_in < p) return fail(SLM_ERR_BAD_ARG, "ld (%lld) < p (%lld)", (long long)ld_in, (long long)p);
   HIP_TRY(hipSetDevice(eng->device));
   slm_dataset* ds = nullptr;
-  SLM_TRY(dataset_alloc(eng, n, p, &ds));
+  SLM_TRY(dataset_alloc(knobs(), eng, n, p, &ds));
   hipError_t e = hipMemcpy2DAsync(ds->X, sizeof(double) * ds->ld, dX, sizeof(double) * ld_in,
                                   sizeof(double) * p, n, hipMemcpyDeviceToDevice, eng->stream);
   if (e == hipSuccess)
@@ -613,7 +613,7 @@ extern "C" int slm_dataset_create_synthetic(slm_engine* eng, int64_t n, int64_t 
   *out = nullptr;
   HIP_TRY(hipSetDevice(eng->device));
   slm_dataset* ds = nullptr;
-  SLM_TRY(dataset_alloc(eng, n, p, &ds));
+  SLM_TRY(dataset_alloc(knobs(), eng, n, p, &ds));
   // coef rides in ds->u for the duration of the generation
   hipError_t e = hipMemcpy(ds->u, coef, sizeof(double) * p, hipMemcpyHostToDevice);
   if (e == hipSuccess) {

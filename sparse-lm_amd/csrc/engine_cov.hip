@@ -15,7 +15,7 @@
 // multiples of sixteen rows read in place -- the ring's last prefetch then reads rows that follow in the block and are never
 // multiplied -- but for the last, which is copied behind zero rows (cov_syrk_padded_rows).  SLM_COV_TILE=3/4: the old kernel
 // (tests compare the two).
-static int cov_gram(slm_dataset* ds, const double* A, int64_t rows, double* C) {
+static int cov_gram(const slm_host::Knobs& kn, slm_dataset* ds, const double* A, int64_t rows, double* C) {
   slm_engine* eng = ds->eng;
   hipStream_t s = eng->stream;
   const int64_t ld = ds->ld;
@@ -23,8 +23,8 @@ static int cov_gram(slm_dataset* ds, const double* A, int64_t rows, double* C) {
     HIP_TRY(hipMemsetAsync(C, 0, sizeof(double) * (size_t)ld * ld, s));
     return SLM_OK;
   }
-  if (knobs().cov_tile != 0) {
-    const int side = knobs().cov_tile == 3 ? 3 : 4;  // (96 or 128 columns per workgroup)
+  if (kn.cov_tile != 0) {
+    const int side = kn.cov_tile == 3 ? 3 : 4;  // (96 or 128 columns per workgroup)
     const int nt = (int)((ld + 32 * side - 1) / (32 * side));
     const dim3 grid((unsigned)(nt * (nt + 1) / 2));
     if (side == 3) hipLaunchKernelGGL(cov_syrk_kernel<3>, grid, dim3(256), 0, s, A, rows, ld, C);
@@ -76,7 +76,7 @@ static int cov_gram(slm_dataset* ds, const double* A, int64_t rows, double* C) {
 }
 
 // the Gram of the rows `rows_host[0..count)` of X (gathered into a block of its own), unscaled, into C
-static int cov_gram_of_rows(slm_dataset* ds, const std::vector<int64_t>& rows_host, double* C) {
+static int cov_gram_of_rows(const slm_host::Knobs& kn, slm_dataset* ds, const std::vector<int64_t>& rows_host, double* C) {
   hipStream_t s = ds->eng->stream;
   const int64_t ld = ds->ld;
   if (rows_host.empty()) {
@@ -94,7 +94,7 @@ static int cov_gram_of_rows(slm_dataset* ds, const std::vector<int64_t>& rows_ho
   if (rc == SLM_OK) {
     hipLaunchKernelGGL(cov_rows_kernel, dim3((unsigned)rows_host.size()), dim3(256), 0, s, ds->X, ld, rows, nullptr,
                        (int64_t)rows_host.size(), block);
-    rc = cov_gram(ds, block, (int64_t)rows_host.size(), C);
+    rc = cov_gram(kn, ds, block, (int64_t)rows_host.size(), C);
   }
   (void)hipStreamSynchronize(s);  // (the staging blocks go back below; the index list is host memory of the caller)
   dfree(rows);
@@ -104,7 +104,7 @@ static int cov_gram_of_rows(slm_dataset* ds, const std::vector<int64_t>& rows_ho
 
 // files the entry of a row set whose scaled Gram G is ready: c = X^T W y / n and y^T W y / n from a standard pass at z = 0.
 // Takes G over (it goes back to the pool if anything fails).
-static int cov_file_entry(slm_dataset* ds, const double* wdev, double n_eff, const double fp[2], double* G) {
+static int cov_file_entry(const slm_host::Knobs& kn, slm_dataset* ds, const double* wdev, double n_eff, const double fp[2], double* G) {
   hipStream_t s = ds->eng->stream;
   const int64_t ld = ds->ld;
   slm_dataset::CovEntry e;
@@ -127,7 +127,7 @@ static int cov_file_entry(slm_dataset* ds, const double* wdev, double n_eff, con
   ls.n_eff[0] = n_eff;
   HIP_TRY(hipMemsetAsync(ds->z, 0, sizeof(double) * ld, s));
   if (ds->gk[0]) SLM_TRY(enqueue_gradient(ds, ls, ds->y, nullptr, nullptr, nullptr));
-  else SLM_TRY(enqueue_gradient_split(ds, ls, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr));
+  else SLM_TRY(enqueue_gradient_split(kn, ds, ls, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr));
   hipLaunchKernelGGL(cov_linear_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, ds->g, ld, e.c, ds->cov_fp);
   SLM_TRY(check_launch());
   HIP_TRY(hipMemcpyAsync(&e.yy, ds->cov_fp, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -143,18 +143,18 @@ static int cov_file_entry(slm_dataset* ds, const double* wdev, double n_eff, con
   return SLM_OK;
 }
 
-static int cov_checks(slm_dataset* ds) {
+static int cov_checks(const slm_host::Knobs& kn, slm_dataset* ds) {
   if (!ds) return fail(SLM_ERR_BAD_ARG, "dataset is NULL");
   if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "covariance passes are not built for row-sharded datasets (replicas: slm_dataset_set_replicated)");
-  if (!split_usable(ds)) return fail(SLM_ERR_UNSUPPORTED, "covariance passes ride on the split pass (rows of up to 10 240 columns)");
+  if (!split_usable(kn, ds)) return fail(SLM_ERR_UNSUPPORTED, "covariance passes ride on the split pass (rows of up to 10 240 columns)");
   return SLM_OK;
 }
 
-static int cov_ensure_all(slm_dataset* ds) {
+static int cov_ensure_all(const slm_host::Knobs& kn, slm_dataset* ds) {
   if (ds->cov_all) return SLM_OK;
   double* all = nullptr;
   SLM_TRY(dalloc(&all, (size_t)ds->ld * ds->ld));
-  const int rc = cov_gram(ds, ds->X, ds->n, all);
+  const int rc = cov_gram(kn, ds, ds->X, ds->n, all);
   if (rc != SLM_OK) {  // (published only once the product is under way: a failed one must not stand in as the minuend)
     (void)hipStreamSynchronize(ds->eng->stream);
     dfree(all);
@@ -166,8 +166,8 @@ static int cov_ensure_all(slm_dataset* ds) {
   return SLM_OK;
 }
 
-extern "C" int slm_dataset_covariance(slm_dataset* ds, const double* row_weight, int64_t n_eff_in) {
-  SLM_TRY(cov_checks(ds));
+static int cov_of_rows(const slm_host::Knobs& kn, slm_dataset* ds, const double* row_weight, int64_t n_eff_in) {
+  SLM_TRY(cov_checks(kn, ds));
   slm_engine* eng = ds->eng;
   HIP_TRY(hipSetDevice(eng->device));
   hipStream_t s = eng->stream;
@@ -212,8 +212,8 @@ extern "C" int slm_dataset_covariance(slm_dataset* ds, const double* row_weight,
   const unsigned cgrid = (unsigned)std::min<int64_t>(4096, (ld * ld + 255) / 256);
   int rc = SLM_OK;
   if (!w_host || (binary && (int64_t)zeros.size() * 2 <= n)) {
-    rc = cov_ensure_all(ds);
-    if (rc == SLM_OK && !zeros.empty()) rc = cov_gram_of_rows(ds, zeros, G);
+    rc = cov_ensure_all(kn, ds);
+    if (rc == SLM_OK && !zeros.empty()) rc = cov_gram_of_rows(kn, ds, zeros, G);
     if (rc == SLM_OK)
       hipLaunchKernelGGL(cov_combine_kernel, dim3(cgrid), dim3(256), 0, s, ds->cov_all, zeros.empty() ? nullptr : G, 1.0 / n_eff,
                          ld * ld, G);
@@ -221,7 +221,7 @@ extern "C" int slm_dataset_covariance(slm_dataset* ds, const double* row_weight,
     rc = dalloc(&tmp.b, (size_t)n * (size_t)ld);
     if (rc == SLM_OK) {
       hipLaunchKernelGGL(cov_rows_kernel, dim3((unsigned)n), dim3(256), 0, s, ds->X, ld, nullptr, wdev, n, tmp.b);
-      rc = cov_gram(ds, tmp.b, n, G);
+      rc = cov_gram(kn, ds, tmp.b, n, G);
     }
     if (rc == SLM_OK) hipLaunchKernelGGL(cov_combine_kernel, dim3(cgrid), dim3(256), 0, s, G, nullptr, 1.0 / n_eff, ld * ld, G);
   }
@@ -230,7 +230,11 @@ extern "C" int slm_dataset_covariance(slm_dataset* ds, const double* row_weight,
     dfree(G);
     return rc;
   }
-  return cov_file_entry(ds, wdev, n_eff, fp, G);
+  return cov_file_entry(kn, ds, wdev, n_eff, fp, G);
+}
+
+extern "C" int slm_dataset_covariance(slm_dataset* ds, const double* row_weight, int64_t n_eff_in) {
+  return cov_of_rows(knobs(), ds, row_weight, n_eff_in);
 }
 
 // The folds of a K-fold split at once.  Their test rows are a partition of the rows, so the Gram of ALL rows is the sum of
@@ -296,9 +300,9 @@ static int cov_partition(const slm_dataset* ds, const double* const* row_weights
 // Queues the parts of this rank's rows on the engine's stream and returns without waiting for anything; *started = 0 when
 // the masks are no partition (nothing queued).  Part f, `stride` doubles: the PACKED lower triangle of X_f^T X_f (test rows of
 // fold f among this rank's; cov_syrk_packed_kernel, all folds in one launch), then t_f = X_f^T y_f [ld] and y_f . y_f [16].
-static int cov_folds_begin(slm_dataset* ds, const double* const* row_weights, const int64_t* n_effs, int32_t count, int* started) {
+static int cov_folds_begin(const slm_host::Knobs& kn, slm_dataset* ds, const double* const* row_weights, const int64_t* n_effs, int32_t count, int* started) {
   *started = 0;
-  SLM_TRY(cov_checks(ds));
+  SLM_TRY(cov_checks(kn, ds));
   if (!row_weights || !n_effs || count < 1 || count > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "between 1 and %d row sets", kMaxLanes);
   if (ds->cov_pend) return fail(SLM_ERR_BAD_ARG, "a fold build is already under way on this dataset (finish it first)");
   slm_engine* eng = ds->eng;
@@ -384,7 +388,7 @@ static int cov_folds_begin(slm_dataset* ds, const double* const* row_weights, co
     SplitArgs a;
     memset(&a, 0, sizeof(a));
     a.X = sb.A[f]; a.R = q->R16; a.partial = ds->partial; a.n = m; a.ld = ld; a.p2 = (int)(ld / 2); a.n_lanes = 1;
-    const int xblk = launch_xtr(eng->cus, a, s);
+    const int xblk = launch_xtr(kn, eng->cus, a, s);
     hipLaunchKernelGGL(cov_xty_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, s, ds->partial, xblk, ld, lin);
     hipLaunchKernelGGL(cov_yy_kernel, dim3(1), dim3(1024), 0, s, ds->y, rows, m, lin + ld);
   }
@@ -481,7 +485,7 @@ extern "C" int slm_dataset_covariance_folds_begin(slm_dataset* ds, const double*
                                                   int32_t* started_out) {
   if (!ds) return fail(SLM_ERR_BAD_ARG, "dataset is NULL");
   int started = 0;
-  SLM_TRY(cov_folds_begin(ds, row_weights, n_effs, count, &started));
+  SLM_TRY(cov_folds_begin(knobs(), ds, row_weights, n_effs, count, &started));
   if (started_out) *started_out = started;
   return SLM_OK;
 }
@@ -493,10 +497,11 @@ extern "C" int slm_dataset_covariance_folds_finish(slm_dataset* ds) {
 
 extern "C" int slm_dataset_covariance_folds(slm_dataset* ds, const double* const* row_weights, const int64_t* n_effs, int32_t count) {
   if (!ds) return fail(SLM_ERR_BAD_ARG, "dataset is NULL");
+  const slm_host::Knobs kn = knobs();
   int started = 0;
-  SLM_TRY(cov_folds_begin(ds, row_weights, n_effs, count, &started));
+  SLM_TRY(cov_folds_begin(kn, ds, row_weights, n_effs, count, &started));
   if (started) return cov_folds_finish(ds);
-  for (int f = 0; f < count; ++f) SLM_TRY(slm_dataset_covariance(ds, row_weights[f], n_effs[f]));
+  for (int f = 0; f < count; ++f) SLM_TRY(cov_of_rows(kn, ds, row_weights[f], n_effs[f]));
   return SLM_OK;
 }
 

@@ -41,8 +41,9 @@ using namespace slm;
 // errors (engine.hip)
 // ------------------------------------------------------------------------------------------------
 int fail(int code, const char* fmt, ...);
-// the SLM_* environment knobs, read once per process (engine.hip; slm_reload_knobs reads them again)
-const slm_host::Knobs& knobs();
+// the SLM_* environment knobs, read once per process (engine.hip; slm_reload_knobs reads them again): a copy, taken once
+// by each entry point that needs one and handed down to what it calls
+slm_host::Knobs knobs();
 
 #define HIP_TRY(expr)                                                                       \
   do {                                                                                      \
@@ -101,10 +102,10 @@ struct SplitKernel {
 };
 static const int kMaxTailE = 64;  // the tail kernels cover p <= 1024 * 64
 static const int64_t kMaxChunks = 64 * 8 * 10;  // largest row the fused kernel covers (p <= 10240)
-const SplitKernel* pick_split_kernel(int64_t p2);
+const SplitKernel* pick_split_kernel(const slm_host::Knobs& kn, int64_t p2);
 int xtr_max_row_blocks(int cus, int64_t ld);
-int launch_xtr(int cus, SplitArgs& a, hipStream_t s, bool sample = false);
-const GradKernel* pick_grad_kernel(int64_t p2, int B);
+int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, bool sample = false);
+const GradKernel* pick_grad_kernel(const slm_host::Knobs& kn, int64_t p2, int B);
 
 // ------------------------------------------------------------------------------------------------
 // In-process communicator (slm_comm_init_local): the engines of ONE process on ONE device form the ranks
@@ -352,20 +353,19 @@ struct LaneSetup {
 LaneSetup default_lanes(slm_dataset* ds, int B);
 int enqueue_gradient(slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done, hipEvent_t ev_start, hipEvent_t ev_stop,
                      int64_t n_rows = 0, const int* skip = nullptr);
-int enqueue_gradient_split(slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done, const PathCtl* ctl, const WsArgs* wa,
+int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done, const PathCtl* ctl, const WsArgs* wa,
                            hipEvent_t ev_start, hipEvent_t ev_stop, int64_t n_rows = 0, bool unit_bracket = false, const int* skip = nullptr);
-bool split_usable(slm_dataset* ds);
-int ensure_xt(slm_dataset* ds);
+bool split_usable(const slm_host::Knobs& kn, slm_dataset* ds);
+int ensure_xt(const slm_host::Knobs& kn, slm_dataset* ds);
 int check_launch();
 // (engine_solve.hip, used by the solve loop of engine_path.hip)
-void launch_rowdot(slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s);
+void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s);
 int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int* done, hipEvent_t ev_start, hipEvent_t ev_stop,
                          const PathCtl* ctl = nullptr, const WsArgs* wa = nullptr);
 void launch_tail(const TailArgs& ta, hipStream_t s);
-int sketch_iters();
 int64_t sketch_rows(int64_t n);
-int power_iteration(slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows = 0);
-int estimate_lipschitz(slm_dataset* ds, double* L_out, int iters);
+int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows = 0);
+int estimate_lipschitz(const slm_host::Knobs& kn, slm_dataset* ds, double* L_out, int iters);
 int allow_big_lds(const void* fn, int device);
 static const int kProfStride = 3;  // SLM_FLAG_PROFILE times every 3rd gradient launch (a working-set path has ~5: two of them;
                                    // an event pair costs ~12 us of stream around the launch it brackets)
@@ -376,10 +376,10 @@ void cov_pending_drop(slm_dataset* ds);  // (engine_cov.hip)
 int set_singleton_groups(slm_dataset* ds);
 // model Gram (engine_mg.hip)
 static const int kMgEntries = 8;
-bool mg_possible(const slm_dataset* ds);
+bool mg_possible(const slm_host::Knobs& kn, const slm_dataset* ds);
 // the model Gram of a row set -- w: its row weights on the device (nullptr: the dataset's own), n_eff its scaling, (fp1, fp2) the
 // fingerprint of w (ignored for the dataset's own) -- built if it is not there yet; entry_out: its index in ds->mg
-int mg_ensure(slm_dataset* ds, const double* w, double n_eff, bool own, double fp1, double fp2, int* entry_out);
+int mg_ensure(const slm_host::Knobs& kn, slm_dataset* ds, const double* w, double n_eff, bool own, double fp1, double fp2, int* entry_out);
 void mg_invalidate(slm_dataset* ds);    // X, the row weights or the scaling changed
 void mg_free(slm_dataset* ds);
 // one round: begin, inner_iters x (products, sums, step), finish.  entry_of_set[s]: the entry of the s-th row set of the call,

@@ -6,8 +6,8 @@
 
 // Where the model Gram can exist: rows short enough for its 4 ld^2 bytes (fp32: 1 GB at the 16 384 columns of MG_MAX_LD), all
 // rows on this device (a row-sharded dataset would have to all-reduce 4 ld^2 bytes per row set: not built).
-bool mg_possible(const slm_dataset* ds) {
-  if (knobs().mg == 0) return false;
+bool mg_possible(const slm_host::Knobs& kn, const slm_dataset* ds) {
+  if (kn.mg == 0) return false;
   if (ds->mg_failed) return false;
   if (ds->ld > MG_MAX_LD || ds->n < 64) return false;
   if (row_sharded(ds)) return false;
@@ -28,11 +28,11 @@ void mg_free(slm_dataset* ds) {
 // G~ = X^T W X / n_eff into G.  Queued on the engine's stream: column maxima (one read of X), the fp16 operand with the
 // square roots of the row weights folded in (one read of the column-major copy), the product in chunks of rows, the sum of
 // the chunks.  The operand and the chunks' partial tiles are scratch; the stream is drained before they go back to the pool.
-static int mg_build(slm_dataset* ds, const double* w, double n_eff, float* G) {
+static int mg_build(const slm_host::Knobs& kn, slm_dataset* ds, const double* w, double n_eff, float* G) {
   slm_engine* eng = ds->eng;
   hipStream_t s = eng->stream;
   const int64_t n = ds->n, ld = ds->ld;
-  SLM_TRY(ensure_xt(ds));
+  SLM_TRY(ensure_xt(kn, ds));
   if (!ds->XT || !ds->XT_ready) return fail(SLM_ERR_OOM, "no column-major copy of X: the model Gram is not built");
   const int64_t row_tiles = (n + 31) / 32;
   const int64_t n_pad = (n + MG_BK - 1) / MG_BK * MG_BK;
@@ -57,7 +57,7 @@ static int mg_build(slm_dataset* ds, const double* w, double n_eff, float* G) {
     return rc;
   }
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  bool timed = knobs().trace != 0;
+  bool timed = kn.trace != 0;
   if (timed) {  // (a diagnostic: an event that cannot be made or recorded switches the timing off, nothing else)
     timed = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, s) == hipSuccess;
     if (!timed) {
@@ -81,8 +81,7 @@ static int mg_build(slm_dataset* ds, const double* w, double n_eff, float* G) {
   {
     MgSyrkArgs a;
     a.M = XTh; a.n_pad = n_pad; a.k_chunk = k_chunk; a.n_tiles = n_tiles; a.n_chunks = n_chunks; a.P = P;
-    if (knobs().mg_syrk == 0) hipLaunchKernelGGL  /* (SLM_MG_SYRK=0: the register-staged form, for A/B runs) */(mg_syrk_f16_kernel, dim3((unsigned)((int64_t)n_tiles * n_chunks)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(mg_syrk_f16_dma_kernel, dim3((unsigned)((int64_t)n_tiles * n_chunks)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(mg_syrk_f16_dma_kernel, dim3((unsigned)((int64_t)n_tiles * n_chunks)), dim3(256), 0, s, a);
   }
   {
     MgReduceArgs r;
@@ -110,7 +109,7 @@ static int mg_build(slm_dataset* ds, const double* w, double n_eff, float* G) {
   return rc;
 }
 
-int mg_ensure(slm_dataset* ds, const double* w, double n_eff, bool own, double fp1, double fp2, int* entry_out) {
+int mg_ensure(const slm_host::Knobs& kn, slm_dataset* ds, const double* w, double n_eff, bool own, double fp1, double fp2, int* entry_out) {
   for (size_t i = 0; i < ds->mg.size(); ++i) {
     const slm_dataset::MgEntry& e = ds->mg[i];
     if (e.n_eff == n_eff && (own ? e.own : (!e.own && e.fp1 == fp1 && e.fp2 == fp2))) {
@@ -135,7 +134,7 @@ int mg_ensure(slm_dataset* ds, const double* w, double n_eff, bool own, double f
   }
   slm_dataset::MgEntry ne;
   if (rc == SLM_OK) rc = dalloc(&ne.G, (size_t)ld * (size_t)ld);
-  if (rc == SLM_OK) rc = mg_build(ds, own ? ds->rw : w, n_eff, ne.G);
+  if (rc == SLM_OK) rc = mg_build(kn, ds, own ? ds->rw : w, n_eff, ne.G);
   if (rc != SLM_OK) {  // no memory: the solve goes on as it would have without the model
     dfree(ne.G);
     if (rc == SLM_ERR_OOM) ds->mg_failed = true;
@@ -239,7 +238,7 @@ extern "C" int slm_dataset_model_gram(slm_dataset* ds, double* G_out) {
     return fail(SLM_ERR_UNSUPPORTED, "the model Gram is built for unsharded datasets of 64 rows or more and p <= %d", MG_MAX_LD);
   ds->mg_failed = false;
   int entry = -1;
-  SLM_TRY(mg_ensure(ds, nullptr, (double)ds->n_global, true, 0.0, 0.0, &entry));
+  SLM_TRY(mg_ensure(knobs(), ds, nullptr, (double)ds->n_global, true, 0.0, 0.0, &entry));
   if (G_out) {
     HIP_TRY(hipStreamSynchronize(ds->eng->stream));
     const size_t count = (size_t)ds->ld * (size_t)ds->ld;

@@ -12,24 +12,24 @@
 // point indices on the device and work stealing between lanes.
 // Working-set refinement policy (see solve_core): 0 = never, 1 = when a path point turns out hard
 // (small problems), 2 = from the first pass.
-static int ws_policy(const slm_dataset* ds, uint32_t flags) {
+static int ws_policy(const slm_host::Knobs& kn, const slm_dataset* ds, uint32_t flags) {
   // (a group has to fit the working set with room for others: up to half its capacity.  Until round 6 the bound was 64 -- the
   //  width of a wavefront, not a property of the kernels: the model solver's group sums walk a group's members through LDS
   //  whatever their number, the scores and the selection move groups as blocks -- and ONE larger group switched the working
   //  set off for the whole dataset.)
   if (ds->max_group > WS_KCAP / 2 || ds->n < 4) return 0;
-  if (knobs().ws == 0 || (flags & SLM_FLAG_NO_WORKING_SET)) return 0;
+  if (kn.ws == 0 || (flags & SLM_FLAG_NO_WORKING_SET)) return 0;
   const bool big = (double)ds->n * (double)ds->ld >= 67108864.0;  // 2^26 doubles = 512 MiB
-  return (big || (flags & SLM_FLAG_WORKING_SET) || knobs().ws == 1) ? 2 : 1;
+  return (big || (flags & SLM_FLAG_WORKING_SET) || kn.ws == 1) ? 2 : 1;
 }
 
 // The on-chip solver (small_kernels.hpp) takes a call when the caller allows it (SLM_FLAG_ON_CHIP), the Gram matrix
 // fits the LDS and nothing asks for a particular iteration of the general path.
-static bool small_ok(const slm_dataset* ds, uint32_t flags) {
+static bool small_ok(const slm_host::Knobs& kn, const slm_dataset* ds, uint32_t flags) {
   if (!(flags & SLM_FLAG_ON_CHIP)) return false;
   if (flags & (SLM_FLAG_NO_RESTART | SLM_FLAG_PROFILE | SLM_FLAG_FISTA_ONLY | SLM_FLAG_WORKING_SET | SLM_FLAG_NO_WORKING_SET))
     return false;
-  if (!knobs().on_chip) return false;
+  if (!kn.on_chip) return false;
   return ds->p <= SM_PMAX && (double)ds->n * (double)ds->ld <= 131072.0 && !row_sharded(ds);
 }
 // most lanes one solve can run: the fused kernels' table, or the split pass's sixteen when the working
@@ -39,17 +39,16 @@ static bool small_ok(const slm_dataset* ds, uint32_t flags) {
 static bool split_possible(const slm_dataset* ds) {  // (split_usable without building anything)
   return ds->sk != nullptr && (ds->sk->rowdot != nullptr || !ds->XT_failed);
 }
-static int max_lanes_for(const slm_dataset* ds, uint32_t flags) {
-  if (small_ok(ds, flags)) return ds->lane_cap;  // a workgroup per lane
-  if ((ws_policy(ds, flags) == 2 || (double)ds->n * (double)ds->ld >= 67108864.0) && split_possible(ds)) {
+static int max_lanes_for(const slm_host::Knobs& kn, const slm_dataset* ds, uint32_t flags) {
+  if (small_ok(kn, ds, flags)) return ds->lane_cap;  // a workgroup per lane
+  if ((ws_policy(kn, ds, flags) == 2 || (double)ds->n * (double)ds->ld >= 67108864.0) && split_possible(ds)) {
     // Two halves of sixteen on ONE read of X (xtr32_mfma_kernel, 0.71 ms against 0.57 at 100k x 5k) where the solve is a
     // working-set solve over X on this device: lanes that advance a point per pass -- the units of a grid, the folds of a
     // search -- then cost 0.6 of what they cost on sixteen (config 4 over X: 159 passes / 0.147 s -> 85 / 0.092 s).
     // Covariance passes take thirty-two as well (a launch of the Gram product per half: 13-37 us each against the chain
     // of a whole pass saved).  Row-sharded solves stay at sixteen; so do rows beyond 5120 columns (no ring variant:
     // every residual from X is a read of the column-major copy per half).
-    if (ws_policy(ds, flags) == 2 && !row_sharded(ds) && ds->sk->rowdot != nullptr && knobs().wide_lanes &&
-        !ds->XT_failed)
+    if (ws_policy(kn, ds, flags) == 2 && !row_sharded(ds) && ds->sk->rowdot != nullptr && !ds->XT_failed)
       return kMaxLanes;
     return SPLIT_LANES;
   }
@@ -59,30 +58,30 @@ static int max_lanes_for(const slm_dataset* ds, uint32_t flags) {
 }
 // A lane count beyond sixteen as a solve can really take it: the column-major copy is built here, on the dataset's own
 // device, and a dataset that has no memory for it stays at sixteen (XT_failed: max_lanes_for then says so as well).
-static int lanes_with_copy(slm_dataset* ds, uint32_t flags, int want, int* lanes_out) {
+static int lanes_with_copy(const slm_host::Knobs& kn, slm_dataset* ds, uint32_t flags, int want, int* lanes_out) {
   *lanes_out = want;
-  if (want <= SPLIT_LANES || small_ok(ds, flags)) return SLM_OK;
+  if (want <= SPLIT_LANES || small_ok(kn, ds, flags)) return SLM_OK;
   HIP_TRY(hipSetDevice(ds->eng->device));
-  SLM_TRY(ensure_xt(ds));
+  SLM_TRY(ensure_xt(kn, ds));
   if (ds->XT == nullptr) *lanes_out = SPLIT_LANES;
   return SLM_OK;
 }
 
-static int solve_core(slm_dataset* ds, const slm_lane* lanes, int32_t n_lanes, const slm_solve_opts* opts,
+static int solve_core(const slm_host::Knobs& kn, slm_dataset* ds, const slm_lane* lanes, int32_t n_lanes, const slm_solve_opts* opts,
                       slm_solve_stats* stats, bool shared_path, const slm_reweight* rules = nullptr, int32_t* rounds_out = nullptr);
 
 // A call the on-chip solver was offered, on the general path: in as many calls as that path needs for the lane count
 // (sixteen workgroups take sixteen lanes whatever p; the fused kernels' table stops earlier).
-static int solve_without_chip(slm_dataset* ds, const slm_lane* lanes, int32_t B, const slm_solve_opts& o, slm_solve_stats* stats,
+static int solve_without_chip(const slm_host::Knobs& kn, slm_dataset* ds, const slm_lane* lanes, int32_t B, const slm_solve_opts& o, slm_solve_stats* stats,
                               bool shared_path) {
   slm_solve_opts again = o;
   again.flags &= ~SLM_FLAG_ON_CHIP;
-  const int per_call = shared_path ? B : std::min<int>(B, max_lanes_for(ds, again.flags));
-  if (per_call >= B) return solve_core(ds, lanes, B, &again, stats, shared_path);
+  const int per_call = shared_path ? B : std::min<int>(B, max_lanes_for(kn, ds, again.flags));
+  if (per_call >= B) return solve_core(kn, ds, lanes, B, &again, stats, shared_path);
   slm_solve_stats sum, part;
   memset(&sum, 0, sizeof(sum));
   for (int l0 = 0; l0 < B; l0 += per_call) {
-    SLM_TRY(solve_core(ds, lanes + l0, std::min(per_call, B - l0), &again, &part, false));
+    SLM_TRY(solve_core(kn, ds, lanes + l0, std::min(per_call, B - l0), &again, &part, false));
     sum.grad_launches += part.grad_launches;
     sum.wall_ms += part.wall_ms;
     sum.lipschitz_ms += part.lipschitz_ms;
@@ -108,7 +107,9 @@ static int solve_without_chip(slm_dataset* ds, const slm_lane* lanes, int32_t B,
 //   finish             results, statistics, trace, the state a later carried start finds
 // ------------------------------------------------------------------------------------------------
 struct PathCall {
+  explicit PathCall(const slm_host::Knobs& k) : kn(k) {}
   // ---- arguments
+  const slm_host::Knobs kn;  // the SLM_* knobs as they were when the call began: every phase reads this copy
   slm_dataset* ds = nullptr;
   const slm_lane* lanes = nullptr;
   int B = 0;
@@ -199,12 +200,12 @@ struct PathCall {
   void report(const DevCtl& snap, int64_t passes);
 };
 
-static int solve_core(slm_dataset* ds, const slm_lane* lanes, int32_t n_lanes, const slm_solve_opts* opts,
+static int solve_core(const slm_host::Knobs& kn, slm_dataset* ds, const slm_lane* lanes, int32_t n_lanes, const slm_solve_opts* opts,
                       slm_solve_stats* stats, bool shared_path, const slm_reweight* rules, int32_t* rounds_out) {
   if (!ds || !lanes) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   HIP_TRY(hipSetDevice(ds->eng->device));  // (before anything that may allocate or launch: split_usable / ensure_xt below)
   // (heap, not stack: the call's state carries two kernels' argument blocks and the lanes' tables)
-  std::unique_ptr<PathCall> c(new PathCall());
+  std::unique_ptr<PathCall> c(new PathCall(kn));
   c->ds = ds; c->lanes = lanes; c->B = n_lanes; c->stats = stats; c->shared_path = shared_path; c->rules = rules; c->rounds_out = rounds_out;
   memset(&c->o, 0, sizeof(c->o));
   if (opts) c->o = *opts;
@@ -240,7 +241,7 @@ int PathCall::shape(const slm_solve_opts* opts) {
   if (rules) {
     // re-weighted rounds run inside the on-chip kernel, nowhere else: other problems keep their loop on the caller's side
     if (!rounds_out) return fail(SLM_ERR_BAD_ARG, "rounds_out is NULL");
-    if (shared_path || !small_ok(ds, opts ? opts->flags : 0u))
+    if (shared_path || !small_ok(kn, ds, opts ? opts->flags : 0u))
       return fail(SLM_ERR_UNSUPPORTED, "re-weighted rounds need a problem the on-chip solver takes (p <= %d, n * ld <= 131072)", SM_PMAX);
     for (int l = 0; l < B && l < SLM_MAX_CELLS; ++l) {
       const slm_reweight& r = rules[l];
@@ -256,7 +257,7 @@ int PathCall::shape(const slm_solve_opts* opts) {
   {
     // sixteen lanes; the on-chip solver, a workgroup per lane, takes SLM_MAX_CELLS (what it does not settle comes back here
     // through solve_without_chip in chunks of sixteen)
-    const int cap = small_ok(ds, opts ? opts->flags : 0u) ? ds->lane_cap : kMaxLanes;
+    const int cap = small_ok(kn, ds, opts ? opts->flags : 0u) ? ds->lane_cap : kMaxLanes;
     if (B < 1 || B > cap) return fail(SLM_ERR_BAD_ARG, "n_lanes must be in [1, %d] (got %d)", cap, B);
   }
   // the split pass costs four launches where the fused kernel costs one: take it when X is large (the
@@ -273,10 +274,10 @@ int PathCall::shape(const slm_solve_opts* opts) {
   // (rows beyond 10 240 columns: the fused table has only the two-pass kernels, two reads of X per gradient -- a working-set
   //  solve takes the split pass there whatever the lane count: one read, and the residuals of points on W from the gathered columns)
   const bool two_pass_only = gk_B != nullptr && gk_B->D < 0;
-  const bool want_split = (ws_policy(ds, opts ? opts->flags : 0u) == 2 && (!wide || two_pass_only)) ? (big_x || !gk_B) : (big_x && !gk_B);
+  const bool want_split = (ws_policy(kn, ds, opts ? opts->flags : 0u) == 2 && (!wide || two_pass_only)) ? (big_x || !gk_B) : (big_x && !gk_B);
   // (covariance passes are a form of the split pass: the flag asks for it whatever the size, where Grams exist)
   want_cov = opts && (opts->flags & SLM_FLAG_COVARIANCE) && !ds->cov.empty() && !row_sharded(ds) && B <= kMaxLanes;
-  split = (want_split || want_cov) && split_usable(ds);
+  split = (want_split || want_cov) && split_usable(kn, ds);
   // Shared path with the working set on from the start: the lanes take the points of the path in turn
   // (lane l: l, l + B, ...) instead of contiguous ranges.  Every lane then starts near alpha_max, where
   // the first working set (chosen from the gradient at zero) is enough, and all lanes move down the
@@ -285,14 +286,14 @@ int PathCall::shape(const slm_solve_opts* opts) {
   // (Only for per-feature penalties.  With group penalties the cold starts do not miss -- config 3: no
   // miss either way -- while looking a whole stride ahead pulls noise groups into W: 380 columns and
   // 10.9 ms per path against 250 columns and 10.3 ms with contiguous ranges.)
-  interleave = shared_path && ds->singleton && ws_policy(ds, opts ? opts->flags : 0u) == 2 &&
-                          knobs().interleave;
-  if (!split && !gk_B && !small_ok(ds, opts ? opts->flags : 0u))
+  interleave = shared_path && ds->singleton && ws_policy(kn, ds, opts ? opts->flags : 0u) == 2 &&
+                          kn.interleave;
+  if (!split && !gk_B && !small_ok(kn, ds, opts ? opts->flags : 0u))
     return fail(SLM_ERR_UNSUPPORTED, "no %d-lane gradient kernel covers p = %lld", B, (long long)ds->p);
   // more than sixteen lanes: two halves on one read of X (xtr32_mfma_kernel) -- working-set solves on the split pass, all rows here
-  if (B > SPLIT_LANES && !small_ok(ds, opts ? opts->flags : 0u) && (!split || row_sharded(ds) || ws_policy(ds, opts ? opts->flags : 0u) != 2))
+  if (B > SPLIT_LANES && !small_ok(kn, ds, opts ? opts->flags : 0u) && (!split || row_sharded(ds) || ws_policy(kn, ds, opts ? opts->flags : 0u) != 2))
     return fail(SLM_ERR_UNSUPPORTED, "%d lanes: more than %d need a working-set solve on the split pass of an unsharded dataset", B, SPLIT_LANES);
-  if (split && B > ROWDOT_LANES) SLM_TRY(ensure_xt(ds));  // rowdot_mfma_kernel reads the column-major copy (optional)
+  if (split && B > ROWDOT_LANES) SLM_TRY(ensure_xt(kn, ds));  // rowdot_mfma_kernel reads the column-major copy (optional)
   for (int l = 0; l < B; ++l) {
     const slm_lane& ln = lanes[l];
     if (!ln.points || !ln.betas_out) return fail(SLM_ERR_BAD_ARG, "lane %d: NULL points or betas_out", l);
@@ -371,7 +372,7 @@ int PathCall::stage_row_weights() {
       custom_scale = true;
     }
 
-  small = small_ok(ds, o.flags);
+  small = small_ok(kn, ds, o.flags);
   return SLM_OK;
 }
 
@@ -411,8 +412,8 @@ int PathCall::find_covariance() {
 
 // the sketch's estimate for the dataset's own rows and weights, computed once and kept on the device
 int PathCall::kept_sketch() {
-  if (ds->sketch_valid && !(o.flags & SLM_FLAG_FRESH_L) && knobs().sketch_cache) return SLM_OK;
-  SLM_TRY(power_iteration(ds, default_lanes(ds, 1), nullptr, sketch_iters(), sketch_rows(ds->n)));
+  if (ds->sketch_valid && !(o.flags & SLM_FLAG_FRESH_L)) return SLM_OK;
+  SLM_TRY(power_iteration(kn, ds, default_lanes(ds, 1), nullptr, slm_host::kSketchPowerIters, sketch_rows(ds->n)));
   HIP_TRY(hipMemcpyAsync(ds->lambda + ds->lane_cap, ds->lambda, sizeof(double), hipMemcpyDeviceToDevice, eng->stream));
   ds->sketch_valid = true;
   return SLM_OK;
@@ -428,7 +429,7 @@ int PathCall::seed_lipschitz() {
     bool ran = false;
     // working-set solves barely use L (first candidate, fallback steps): a bound from the first thirty-second
     // of the rows, three power steps, costs a sixth of the two full passes
-    const bool sketch = ws_policy(ds, o.flags) == 2 && n >= 65536 && knobs().l_sketch;
+    const bool sketch = ws_policy(kn, ds, o.flags) == 2 && n >= 65536;
     if (sketch && !(ds->L_valid && !(o.flags & SLM_FLAG_FRESH_L) && !any_rw && !custom_scale)) {
       const bool per_lane = any_rw || custom_scale;
       bool bounded = per_lane && !sharded;
@@ -445,7 +446,7 @@ int PathCall::seed_lipschitz() {
         LaneSetup plain = default_lanes(ds, 1);
         plain.rw = nullptr;
         if (ds->rw) {  // (not the dataset's own operator: not kept)
-          SLM_TRY(power_iteration(ds, plain, nullptr, sketch_iters(), sketch_rows(n)));
+          SLM_TRY(power_iteration(kn, ds, plain, nullptr, slm_host::kSketchPowerIters, sketch_rows(n)));
         } else {
           SLM_TRY(kept_sketch());
           L_kept = true;
@@ -471,24 +472,24 @@ int PathCall::seed_lipschitz() {
         for (int l = 0; l < B; ++l) L[l] = 0.0;
         L_on_device = true;
       } else {
-      SLM_TRY(power_iteration(ds, per_lane ? ls : default_lanes(ds, 1), L, sketch_iters(), sketch_rows(n)));
+      SLM_TRY(power_iteration(kn, ds, per_lane ? ls : default_lanes(ds, 1), L, slm_host::kSketchPowerIters, sketch_rows(n)));
       // A lane whose row weights vanish on the window (scikit-learn's default cv = unshuffled KFold: the first
       // fold's training mask is zero on the first n / k rows) measured nothing there: all rows, then.
       bool blank = false;
       for (int l = 0; l < (per_lane ? B : 1); ++l) blank = blank || !(L[l] > 0.0);
-      if (blank) SLM_TRY(power_iteration(ds, per_lane ? ls : default_lanes(ds, 1), L, kPowerItersSolve));
+      if (blank) SLM_TRY(power_iteration(kn, ds, per_lane ? ls : default_lanes(ds, 1), L, kPowerItersSolve));
       if (!per_lane)
         for (int l = 1; l < B; ++l) L[l] = L[0];
       }
       ran = true;
     } else if (any_rw || custom_scale) {
-      SLM_TRY(power_iteration(ds, ls, L, kPowerItersSolve));  // lane-specific operators: not cached
+      SLM_TRY(power_iteration(kn, ds, ls, L, kPowerItersSolve));  // lane-specific operators: not cached
       ran = true;
     } else {
       if (o.flags & SLM_FLAG_FRESH_L) ds->L_valid = false;
       ran = !ds->L_valid;
       double L1 = 0.0;
-      SLM_TRY(estimate_lipschitz(ds, &L1, kPowerItersSolve));
+      SLM_TRY(estimate_lipschitz(kn, ds, &L1, kPowerItersSolve));
       for (int l = 0; l < B; ++l) L[l] = L1;
     }
     if (ran)
@@ -525,7 +526,7 @@ int PathCall::stage_lanes() {
   // step of converged length away from -- and its first pass over the data is not run: 9 -> 7 passes for BASELINE
   // config 5.  Decided on the host from the caller's arrays alone, so the ranks of a row-sharded solve agree.
   if (ds->carry_valid && !small && !shared_path && B <= ds->carry_lanes && !(o.flags & SLM_FLAG_COLD_START) &&
-      knobs().carry) {
+      kn.carry) {
     carry = true;
     for (int l = 0; l < B && carry; ++l) {
       const slm_dataset::CarryLane& c = ds->carry_lane[l];
@@ -548,8 +549,8 @@ int PathCall::stage_lanes() {
     ws_n_sets = slm_host::row_sets(nl, rwp, nef, ws_set_of, ws_set_lane);
   }
   // a carried start on the same row sets takes over the working set too (ws_ctl_carry_kernel)
-  ws_carry = carry && ds->ws_carry_valid && ws_policy(ds, o.flags) == 2 && ws_n_sets == ds->ws_carry_sets &&
-                  ds->ws_sets >= ws_n_sets && ds->ws_carry_cov == cov_on && knobs().ws_carry;
+  ws_carry = carry && ds->ws_carry_valid && ws_policy(kn, ds, o.flags) == 2 && ws_n_sets == ds->ws_carry_sets &&
+                  ds->ws_sets >= ws_n_sets && ds->ws_carry_cov == cov_on && kn.ws_carry;
   for (int l = 0; l < B && ws_carry; ++l) ws_carry = ws_set_of[l] == ds->ws_carry_set_of[l];
   ds->ws_carry_valid = false;
   if (!ds->h_stage) {  // (page-locked: the set-up kernel reads the control blocks from it)
@@ -638,7 +639,7 @@ int PathCall::stage_lanes() {
       // ones that have just solved their neighbours -- not to the first, which would reach them from sixteen points
       // up the path: there the features of the last decade of alpha cannot be told yet, the first verification
       // misses and a large append follows (0.33 ms on the headline path).  (host_logic.hpp: interleaved_walk)
-      const slm_host::LaneWalk w = slm_host::interleaved_walk(l, B, total_points, knobs().tail_band, knobs().slack_deep);
+      const slm_host::LaneWalk w = slm_host::interleaved_walk(l, B, total_points, kn.tail_band, true);
       h[l].point = w.first;
       h[l].pt_lo = w.first;
       h[l].n_points = w.n_points;
@@ -690,7 +691,7 @@ int PathCall::stage_lanes() {
       for (int l = 0; l < kMaxLanes; ++l) bg.factor[l] = L_factor[l];
     }
     // (the working set's state where it starts with the solve: ws_setup then has nothing left to launch)
-    ws_begun = !small && !ws_carry && ws_policy(ds, o.flags) == 2;
+    ws_begun = !small && !ws_carry && ws_policy(kn, ds, o.flags) == 2;
     if (ws_begun) {
       bg.ws = &ds->dctl->ws;
       bg.max_builds = kWsMaxBuilds;
@@ -779,9 +780,8 @@ int PathCall::run_on_chip() {
   sm.stage_doubles = (int)((lds - fixed - 64) / sizeof(double));
   SLM_TRY(allow_big_lds((const void*)small_solve_kernel, eng->device));
   // The coefficients of a call that fits the dataset's pinned stage are stored there by the kernel itself and moved to
-  // the caller's arrays after the wait: a copy command into pageable memory is 20-40 us behind a 0.25 ms kernel
-  // (SLM_NO_SMALL_STAGE: the copy commands, for comparison).
-  bool staged_out = (size_t)total_points * (size_t)p <= kSmallOutDoubles && !any_gn && knobs().small_stage;
+  // the caller's arrays after the wait: a copy command into pageable memory is 20-40 us behind a 0.25 ms kernel.
+  bool staged_out = (size_t)total_points * (size_t)p <= kSmallOutDoubles && !any_gn;
   if (staged_out && !ds->h_small_out &&
       hipHostMalloc((void**)&ds->h_small_out, sizeof(double) * kSmallOutDoubles, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError();
@@ -838,11 +838,11 @@ int PathCall::run_on_chip() {
       rounds_out[l] = snap.lane[l].rounds;
     }
   }
-  if (unconverged && knobs().on_chip_fallback) {  // (SLM_ON_CHIP_NO_FALLBACK: diagnostics -- the on-chip records as they are)
-    if (knobs().trace == 2) fprintf(stderr, "[slm] on-chip solve gave a point up after %.3f ms (%lld products): the general path takes the call\n", t_small, (long long)sweeps);
+  if (unconverged) {
+    if (kn.trace == 2) fprintf(stderr, "[slm] on-chip solve gave a point up after %.3f ms (%lld products): the general path takes the call\n", t_small, (long long)sweeps);
     // the on-chip iteration did not settle some point within its products (an ill-conditioned face): the general
     // path, with its Newton steps, takes the call over from the start
-    return solve_without_chip(ds, lanes, B, o, stats, shared_path);
+    return solve_without_chip(kn, ds, lanes, B, o, stats, shared_path);
   }
   if (stats) {
     memset(stats, 0, sizeof(*stats));
@@ -850,7 +850,7 @@ int PathCall::run_on_chip() {
     stats->ws_inner_iters = sweeps;
     stats->wall_ms = t_mark();
   }
-  if (knobs().trace == 2) {
+  if (kn.trace == 2) {
       int sl = 0;  // the lane that took longest
       double worst = -1.0;
       for (int l = 0; l < B; ++l) {
@@ -891,7 +891,7 @@ int PathCall::ws_setup(bool late) {
   if (!ds->ws_pos) SLM_TRY(dalloc(&ds->ws_pos, (size_t)ld));
   if (!ds->ws_score) SLM_TRY(dalloc(&ds->ws_score, (size_t)ld));
   if (!ds->ws_XW) SLM_TRY(dalloc(&ds->ws_XW, (size_t)n * WS_KCAP));
-  if (!ds->ws_nt && knobs().direct) SLM_TRY(dalloc(&ds->ws_nt, (size_t)kMaxLanes * NT_SCRATCH));
+  if (!ds->ws_nt) SLM_TRY(dalloc(&ds->ws_nt, (size_t)kMaxLanes * NT_SCRATCH));
   if (ds->ws_sets < n_sets) {
     dfree(ds->ws_part); dfree(ds->ws_G); dfree(ds->ws_Gx);
     ds->ws_sets = 0;
@@ -903,7 +903,7 @@ int PathCall::ws_setup(bool late) {
   // column-major copy of X (a layout of the data like the padded row-major one: depends on nothing
   // but X, kept for the life of the dataset; 2 ms for 4 GB).  Optional: without the memory for it
   // the gathers read the row-major X, one 64-byte sector per element.
-  SLM_TRY(ensure_xt(ds));
+  SLM_TRY(ensure_xt(kn, ds));
   // (initialised on the device: a host-side copy would need the stream drained before its buffer goes away)
   if (late) HIP_TRY(hipMemsetAsync(ds->ws_ctl, 0, sizeof(WsCtl), s));  // (a fresh solve has cleared it already)
   if (ws_carry && !late) hipLaunchKernelGGL(ws_ctl_carry_kernel, dim3(1), dim3(256), 0, s, ds->ws_ctl, kWsMaxBuilds);
@@ -911,7 +911,7 @@ int PathCall::ws_setup(bool late) {
   wa.ws = ds->ws_ctl;
   wa.idx = ds->ws_idx; wa.pos = ds->ws_pos; wa.gs = ds->ws_gs; wa.gl = ds->ws_gl;
   wa.score = ds->ws_score; wa.XW = ds->ws_XW; wa.part = ds->ws_part; wa.Gm = ds->ws_G;
-  wa.nt = knobs().direct ? ds->ws_nt : nullptr;
+  wa.nt = ds->ws_nt;
   if (sharded && !ds->ws_Gx) SLM_TRY(dalloc(&ds->ws_Gx, (size_t)ds->ws_sets * WS_KCAP * WS_KCAP + STOP_WORDS));
   wa.Gx = sharded ? ds->ws_Gx : nullptr;  // row-sharded: Gram parts are summed over ranks before use
   wa.X = ds->X; wa.XT = ds->XT; wa.n = n; wa.ld = ld;
@@ -926,7 +926,7 @@ int PathCall::ws_setup(bool late) {
   wa.nblk = ws_nblk;
   // row blocks on which a set's row weights are all zeros, or all ones like another set's: ws_block_owner_kernel
   wa.owner = nullptr;
-  if (ls.rw != nullptr && !sharded && knobs().gram_owner && ws_nblk <= 512) {
+  if (ls.rw != nullptr && !sharded && kn.gram_owner && ws_nblk <= 512) {
     if (!ds->ws_owner) SLM_TRY(dalloc(&ds->ws_owner, (size_t)kMaxLanes * 512));
     hipLaunchKernelGGL(ws_block_owner_kernel, dim3((unsigned)ws_nblk), dim3(256), 0, s, ls.rw, ls.rw_stride, wa, ds->ws_owner);
     wa.owner = ds->ws_owner;
@@ -934,9 +934,8 @@ int PathCall::ws_setup(bool late) {
   // measured on the headline path (tools/ws_sweep.py, 24 combinations within 8 % of each other):
   // theta 0.85 / look-ahead 2 / 16 newcomers per pass / 112 initial columns was the fastest
   // (append 48: interleaved lanes need the next band of the path at once; elsewhere 16 cost a pass now and then)
-  const slm_host::Knobs& kn = knobs();
   wa.theta = kn.ws_theta;
-  wa.lookahead = kn.ws_lookahead;
+  wa.lookahead = slm_host::kWsLookahead;
   wa.append_max = kn.ws_append;
   // The first selection.  A path that walks down from alpha_max on interleaved lanes starts small: 112 columns (160: the
   // same; 208: 4.0 ms per headline path against 3.65).  Lanes that start cold at an alpha of their own (single fits, the
@@ -950,7 +949,7 @@ int PathCall::ws_setup(bool late) {
   wa.bb_steps = kn.ws_bb;
   wa.one_solver = kn.ws_one_solver;
   wa.hard_call = kn.hard_callwide;
-  wa.power_iters = kn.ws_power_iters;
+  wa.power_iters = slm_host::kWsPowerIters;
   wa.miss_factor = kn.ws_miss_factor;
   wa.miss_div = kn.ws_miss_div;
   // (0.5 left a first working set of 56-112 columns to the luck of the bisection: 65 on one draw of the headline's law, 102 on
@@ -975,7 +974,7 @@ void PathCall::ws_release() {
 
 int PathCall::prepare_working_set() {
   {
-    const int pol = ws_policy(ds, o.flags);
+    const int pol = ws_policy(kn, ds, o.flags);
     use_ws = pol == 2;
     // (row-sharded: the switch would change the collectives of a pass on the strength of one rank's state)
     ws_late = pol == 1 && !sharded;
@@ -1001,7 +1000,7 @@ int PathCall::prepare_working_set() {
 // possible) when the working set runs from the start, the fused kernel otherwise
 int PathCall::enqueue_pass_gradient(hipEvent_t e0, hipEvent_t e1) {
   if (cov_on) return enqueue_gradient_cov(ds, B, cov_entry, done_flag, e0, e1, ds->ctl, use_ws ? &wa : nullptr);
-  if (split) return enqueue_gradient_split(ds, ls, ds->y, done_flag, ds->ctl, &wa, e0, e1, 0, (o.flags & SLM_FLAG_PROFILE_UNIT) != 0, light_skip);
+  if (split) return enqueue_gradient_split(kn, ds, ls, ds->y, done_flag, ds->ctl, &wa, e0, e1, 0, (o.flags & SLM_FLAG_PROFILE_UNIT) != 0, light_skip);
   return enqueue_gradient(ds, ls, ds->y, done_flag, e0, e1, 0, light_skip);
 }
 
@@ -1013,7 +1012,7 @@ void PathCall::enqueue_tail() {
   // (the dense end of an interleaved path: finished lanes take over tail points their owners have not started)
   if (shared_path && interleave && mg_handover) hipLaunchKernelGGL(tail_handover_kernel, dim3(1), dim3(64), 0, s, ta);
   // (the sparse end: a lane that has fallen a pass behind gives its tail point to a lane that has finished)
-  else if (shared_path && interleave && use_ws && !ws_late && !sharded && planned_end > 0 && knobs().lag_handover)
+  else if (shared_path && interleave && use_ws && !ws_late && !sharded && planned_end > 0 && kn.lag_handover)
     hipLaunchKernelGGL(lag_handover_kernel, dim3(1), dim3(64), 0, s, ta, &ds->ws_ctl->builds, &ds->ws_ctl->stale, (int)(planned_end - enq - 1));
   if (sharded) {  // the ranks agree on "finished" before anything acts on it
     if (use_ws && wa.Gx) {
@@ -1128,13 +1127,13 @@ void PathCall::plan_queue() {
   // Paths only: their first band sits at the top of the alpha range, where what enters stands far above the sampling
   // noise.  A single cold point at a small alpha admits features the sample cannot tell from noise -- measured on the
   // headline's data (tools/single_fit_big.py): 1.51 -> 1.01 ms at 0.3 alpha_max, 1.53 -> 1.91 ms at 0.05 (a miss and its
-  // append on top of the sample's launches), 2.33 -> 1.92 ms at 0.005; SLM_SAMPLE_START_ALL=1 takes that gamble.
+  // append on top of the sample's launches), 2.33 -> 1.92 ms at 0.005.
   {
     bool cold = true;
     for (int l = 0; l < B; ++l) cold = cold && lanes[l].beta0 == nullptr;
-    if (cold && (shared_path || knobs().sample_start_all) && use_ws && !ws_late && !sharded && !cov_on && split && !any_rw && !ds->rw &&
-        !custom_scale && expected > 0 && o.max_iter >= 4 && !(o.flags & SLM_FLAG_FISTA_ONLY) && knobs().sample_start) {
-      const int64_t least = knobs().sample_min_rows;  // (65536: below it a pass costs little more than the launches of the sample's; SLM_SAMPLE_START_MIN_ROWS: tests)
+    if (cold && shared_path && use_ws && !ws_late && !sharded && !cov_on && split && !any_rw && !ds->rw &&
+        !custom_scale && expected > 0 && o.max_iter >= 4 && !(o.flags & SLM_FLAG_FISTA_ONLY) && kn.sample_start) {
+      const int64_t least = kn.sample_min_rows;  // (65536: below it a pass costs little more than the launches of the sample's; SLM_SAMPLE_START_MIN_ROWS: tests)
       // A quarter of the rows (round 4: an eighth).  The sample has to rank the features of the first band's DEEPEST point
       // above the noise features: a gradient entry of the sample carries noise sd(y) / sqrt(rows) -- on the headline's law
       // 3.7 from an eighth of the rows, 2.6 from a quarter -- and the largest of 5 000 noise entries is 3.7 sd: from an
@@ -1143,7 +1142,7 @@ void PathCall::plan_queue() {
       // (tools/headline_data_seeds.py): eighteen lanes 34 passes / 4.43 ms per path on an eighth, 30 / 3.75 on a quarter,
       // 27 / 3.39 on a half; sixteen lanes 4.11 / 3.89 / 3.78; the bench's own draw 2.86 either way; the soak law's twelve
       // 91.6 -> 92.8 ms in total (a half: 98.2).  SLM_SAMPLE_DIV sets the divisor.
-      if (n >= least) n_sample = n / knobs().sample_div;
+      if (n >= least) n_sample = n / kn.sample_div;
     }
   }
   // ---- model Gram (mg_kernels.hpp) -----------------------------------------------------------------------------------
@@ -1152,18 +1151,18 @@ void PathCall::plan_queue() {
   // model Gram of the dataset is built -- once, it stays with the dataset -- and every later pass is followed by a round
   // of proximal-gradient steps on it for the lanes the working set does not serve (mg_enqueue_round).  From then on the
   // host looks at every pass's snapshot before it queues the next: a round is sized by what the last one needed.
-  mg_forced = knobs().mg == 2;  // (tests: any size, from the first snapshot on)
+  mg_forced = kn.mg == 2;  // (tests: any size, from the first snapshot on)
   // (the model Grams of a dataset, fp32, are kept within 3 GB: sixteen row sets at p = 5 000, seven at 10 000)
   mg_cap = slm_host::model_gram_cap(ld, 3.0e9, kMgEntries);
   mg_ok = use_ws && split && (big_x || mg_forced) && !sharded && !cov_on && !(o.flags & SLM_FLAG_NO_MODEL_GRAM) &&
-                     (size_t)ds->lane_cap >= (size_t)kMaxLanes && ws_n_sets <= mg_cap && mg_possible(ds);
+                     (size_t)ds->lane_cap >= (size_t)kMaxLanes && ws_n_sets <= mg_cap && mg_possible(kn, ds);
   if (mg_ok && mg_forced) expected = 0;  // (tests: polled from the first chunk on, so that short solves reach the rounds too)
   // A dataset that already holds the model Gram of every row set of this call (an earlier solve outgrew the working set
   // and built them: the same path again, a refit, the next search on the data) will be served by the rounds the moment
   // its selection stops fitting: the working set then stays as it is from the first overflow on, instead of being
   // selected, gathered and multiplied afresh once (2-3 ms at 500 columns) before the host has seen the counter.
   // (lanes on the dataset's own rows only: other row sets are told apart by fingerprints, a kernel and a round trip)
-  if (mg_ok && !mg_forced && !ds->mg.empty() && knobs().mg_keep) {
+  if (mg_ok && !mg_forced && !ds->mg.empty()) {
     bool all = ws_n_sets > 0;
     for (int st = 0; st < ws_n_sets && all; ++st) {
       const int l = ws_set_lane[st];
@@ -1178,8 +1177,8 @@ void PathCall::plan_queue() {
   prof_off = n_sample > 0 ? 1 : 0;  // (the pass on the sample is no launch of the roofline's kernel on X)
   // SLM_TRACE=3: one line per polled snapshot -- where every lane stands, the working set, the model Gram's rounds
   // (with SLM_TRACE_POLL=1 every pass is polled: a diagnostic, the queue then drains between passes)
-  trace3 = knobs().trace == 3;
-  if (trace3 && knobs().trace_poll && expected > 0) expected = n_sample > 0 ? 2 : 1;  // (the sample pass's refinement is never held back)
+  trace3 = kn.trace == 3;
+  if (trace3 && kn.trace_poll && expected > 0) expected = n_sample > 0 ? 2 : 1;  // (the sample pass's refinement is never held back)
 }
 
 // the model Gram of every row set of the call (ws_set_of: lanes with the same row weights and scaling share one), found
@@ -1212,7 +1211,7 @@ int PathCall::mg_sets() {
         for (const auto& e : ds->mg) have = have || (e.n_eff == ne && (own ? e.own : (!e.own && e.fp1 == f1 && e.fp2 == f2)));
         missing += have ? 0 : 1;
       } else {
-        SLM_TRY(mg_ensure(ds, own ? nullptr : ls.rw + (int64_t)l * ls.rw_stride, ne, own, f1, f2, &mg_entry_of_set[st]));
+        SLM_TRY(mg_ensure(kn, ds, own ? nullptr : ls.rw + (int64_t)l * ls.rw_stride, ne, own, f1, f2, &mg_entry_of_set[st]));
       }
     }
   }
@@ -1232,7 +1231,7 @@ int PathCall::mg_consider(const DevCtl& c) {
   const int rc = mg_sets();
   if (rc == SLM_OK) {
     mg_on = true;
-    mg_handover = knobs().handover;
+    mg_handover = kn.handover;
     wa.keep_full = 1;  // (from here on the working set serves what it holds: enqueue_refinement passes wa by value)
     if (mg_built > 0) mg_build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   } else if (rc != SLM_ERR_OOM) {
@@ -1258,7 +1257,7 @@ void PathCall::trace_pass(const DevCtl& now) const {
 // decides whether it stands (then the pass's kernels return at once) or stands down (then they run).  Shared paths over the
 // dataset's own unweighted rows, one device; not beside model-Gram rounds or covariance passes.
 bool PathCall::light_eligible() {
-  if (!knobs().light_pass || !shared_path || !use_ws || ws_late || cov_on || sharded || mg_on) return false;
+  if (!kn.light_pass || !shared_path || !use_ws || ws_late || cov_on || sharded || mg_on) return false;
   if (any_rw || ds->rw || custom_scale || B > kMaxLanes || !(expected > 0 && enq >= expected)) return false;
   return ds->XT != nullptr && ds->XT_ready && ds->colnorm != nullptr && ds->colnorm_ready;
 }
@@ -1321,7 +1320,7 @@ int PathCall::queue_chunk() {
     if (sample_pass) {
       LaneSetup part = ls;
       for (int l = 0; l < kMaxLanes; ++l) part.n_eff[l] = (double)ds->n_global * (double)n_sample / (double)n;
-      SLM_TRY(enqueue_gradient_split(ds, part, ds->y, done_flag, ds->ctl, &wa, nullptr, nullptr, n_sample));
+      SLM_TRY(enqueue_gradient_split(kn, ds, part, ds->y, done_flag, ds->ctl, &wa, nullptr, nullptr, n_sample));
       TailArgs first = ta;
       first.provisional = 1;
       launch_tail(first, s);
@@ -1352,7 +1351,7 @@ int PathCall::pass_loop() {
     // remain to be fetched.  Polling one chunk behind cost a queued pass that returned at once (eighteen launches,
     // 0.09 ms) and four blocking copies (0.2 ms of host round trips) on every 5 ms path.  A solve that overruns
     // gets a few more passes polled this way, then the pipelined polls.
-    const bool at_end = mg_on || (expected > 0 && enq >= expected && (enq < expected + 4 || (trace3 && knobs().trace_poll)));
+    const bool at_end = mg_on || (expected > 0 && enq >= expected && (enq < expected + 4 || (trace3 && kn.trace_poll)));
     HIP_TRY(hipEventRecord(ds->ev[slot], s));
     // behind the pass the solve is expected to end with, the results set off at once: when it does end there they are
     // under way while the host still reads the snapshot (37 us of idle stream per path); when it does not, they are
@@ -1493,7 +1492,7 @@ int PathCall::finish() {
       stats->ws_columns = wc.Kreal;
       stats->ws_inner_iters = wc.inner_iters;
       stats->ws_direct_steps = wc.newton_steps;
-      if (knobs().trace == 2) {
+      if (kn.trace == 2) {
         fprintf(stderr, "[slm] working set: %d model-solver iterations over %d refinements, %d direct steps (%d refused, %d of them not positive definite), K = %d, lambda_max bound of the first Gram %.4g (seed L %.4g)\n",
                 wc.inner_iters, wc.refined, wc.newton_steps, wc.newton_fails, wc.newton_nopd, wc.K, wc.Lw[0], fin[0].L);
         fprintf(stderr, "[slm] model solver, lane 0, ms over the solve: set-up %.3f, lambda_max of a new Gram %.3f, start value %.3f, "
@@ -1533,8 +1532,8 @@ int PathCall::finish() {
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   tr[4] = t_mark();
-  if (knobs().trace != 0)  // 1: slow solves only, 2: every solve (cumulative ms since entry)
-    if (tr[4] > 15.0 || knobs().trace == 2)
+  if (kn.trace != 0)  // 1: slow solves only, 2: every solve (cumulative ms since entry)
+    if (tr[4] > 15.0 || kn.trace == 2)
       fprintf(stderr, "[slm] solve: row weights %.3f L %.3f setup %.3f sync %.3f prequeue %.3f loop %.3f end %.3f ms\n", tr_rw, tr[5], tr[0], tr[1], tr[2], tr[3], tr[4]);
   if (nonfinite) return fail(SLM_ERR_NON_FINITE, "non-finite iterate (diverged or non-finite data)");
   if (!shared_path && !(o.flags & SLM_FLAG_COLD_START) && B <= kMaxLanes) {  // where the solve ended (carried starts, above)
@@ -1562,34 +1561,34 @@ int PathCall::finish() {
 
 extern "C" int slm_dataset_max_lanes(slm_dataset* ds, uint32_t flags, int32_t* max_lanes_out) {
   if (!ds || !max_lanes_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  *max_lanes_out = max_lanes_for(ds, flags);
+  *max_lanes_out = max_lanes_for(knobs(), ds, flags);
   return SLM_OK;
 }
 
 extern "C" int slm_solve_lanes(slm_dataset* ds, const slm_lane* lanes, int32_t n_lanes,
                                const slm_solve_opts* opts, slm_solve_stats* stats) {
-  return solve_core(ds, lanes, n_lanes, opts, stats, false);
+  return solve_core(knobs(), ds, lanes, n_lanes, opts, stats, false);
 }
 
 extern "C" int slm_solve_lanes_reweighted(slm_dataset* ds, const slm_lane* lanes, const slm_reweight* rules, int32_t n_lanes,
                                           const slm_solve_opts* opts, slm_solve_stats* stats, int32_t* rounds_out) {
   if (!rules) return fail(SLM_ERR_BAD_ARG, "rules is NULL");
-  return solve_core(ds, lanes, n_lanes, opts, stats, false, rules, rounds_out);
+  return solve_core(knobs(), ds, lanes, n_lanes, opts, stats, false, rules, rounds_out);
 }
 
 // the engine's choice of lanes for a shared path (n_lanes = 0): the fewest passes over X at the price of sixteen lanes
-static int auto_lanes(const slm_dataset* ds, int32_t n_points, uint32_t fl) {
-  const int cap = max_lanes_for(ds, fl);
-  const bool big = ws_policy(ds, fl) == 2 && (double)ds->n * (double)ds->ld >= 67108864.0 && !small_ok(ds, fl);
-  const bool interleaved = ds->singleton && knobs().interleave;  // (solve_core: per-feature penalties take the points in turn)
+static int auto_lanes(const slm_host::Knobs& kn, const slm_dataset* ds, int32_t n_points, uint32_t fl) {
+  const int cap = max_lanes_for(kn, ds, fl);
+  const bool big = ws_policy(kn, ds, fl) == 2 && (double)ds->n * (double)ds->ld >= 67108864.0 && !small_ok(kn, ds, fl);
+  const bool interleaved = ds->singleton && kn.interleave;  // (solve_core: per-feature penalties take the points in turn)
   int B = slm_host::auto_path_lanes(n_points, cap, big, !interleaved);
-  if (knobs().auto_lanes > 0) B = std::max(1, std::min<int>(std::min(knobs().auto_lanes, cap), n_points));  // (SLM_AUTO_LANES: A/B runs)
+  if (kn.auto_lanes > 0) B = std::max(1, std::min<int>(std::min(kn.auto_lanes, cap), n_points));  // (SLM_AUTO_LANES: A/B runs)
   return B;
 }
 extern "C" int slm_dataset_path_lanes(slm_dataset* ds, int32_t n_points, uint32_t flags, int32_t* lanes_out) {
   if (!ds || !lanes_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   if (n_points <= 0) return fail(SLM_ERR_BAD_ARG, "n_points must be positive");
-  *lanes_out = auto_lanes(ds, n_points, flags);
+  *lanes_out = auto_lanes(knobs(), ds, n_points, flags);
   return SLM_OK;
 }
 
@@ -1600,14 +1599,15 @@ extern "C" int slm_solve_path_lanes(slm_dataset* ds, const slm_penalty* pen, con
   if (!ds || !points || !betas_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   if (n_points <= 0) return fail(SLM_ERR_BAD_ARG, "n_points must be positive");
   const uint32_t fl = opts ? opts->flags : 0u;
+  const slm_host::Knobs kn = knobs();
   int B;
   if (n_lanes == 0) {  // the engine's choice (host_logic.hpp)
-    B = auto_lanes(ds, n_points, fl);
+    B = auto_lanes(kn, ds, n_points, fl);
   } else {
     B = std::max(1, std::min<int>(std::min<int>(n_lanes, kMaxLanes), n_points));
-    B = std::min(B, max_lanes_for(ds, fl));  // no kernel variant for (p, B): fewer lanes
+    B = std::min(B, max_lanes_for(kn, ds, fl));  // no kernel variant for (p, B): fewer lanes
   }
-  SLM_TRY(lanes_with_copy(ds, fl, B, &B));  // (more than sixteen: the column-major copy, or sixteen)
+  SLM_TRY(lanes_with_copy(kn, ds, fl, B, &B));  // (more than sixteen: the column-major copy, or sixteen)
   slm_lane lanes[SLM_MAX_LANES];
   memset(lanes, 0, sizeof(lanes));
   int64_t lo = 0;
@@ -1622,7 +1622,7 @@ extern "C" int slm_solve_path_lanes(slm_dataset* ds, const slm_penalty* pen, con
     lanes[l].infos = infos ? infos + lo : nullptr;
     lo = hi;
   }
-  return solve_core(ds, lanes, B, opts, stats, B > 1);
+  return solve_core(kn, ds, lanes, B, opts, stats, B > 1);
 }
 
 extern "C" int slm_solve_path(slm_dataset* ds, const slm_penalty* pen, const slm_path_point* points,

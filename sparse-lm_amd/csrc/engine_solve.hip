@@ -61,8 +61,8 @@ static const SplitKernel kSplit[] = {SLM_SK(1, 3), SLM_SK(2, 3), SLM_SK(3, 3), S
 // X^T R walks column blocks of 512, the residuals from X contract the column-major copy group by group, the working set's
 // kernels see its <= 512 columns -- so sixteen lanes and the working set serve p = 20 000 or 40 000 like 5 000.
 static const SplitKernel kSplitAnyWidth = {8, 0, SPLIT_LANES, 0, nullptr, resid_ws_kernel<SPLIT_LANES>};
-const SplitKernel* pick_split_kernel(int64_t p2) {
-  if (!knobs().split) return nullptr;
+const SplitKernel* pick_split_kernel(const slm_host::Knobs& kn, int64_t p2) {
+  if (!kn.split) return nullptr;
   for (const auto& k : kSplit)
     if (64LL * k.W * k.C >= p2) return &k;
   return &kSplitAnyWidth;
@@ -77,16 +77,16 @@ int xtr_max_row_blocks(int cus, int64_t ld) {  // (sizes the partial buffer: the
   return slm_host::xtr_row_blocks_most(cus, ld, XTR_CB);
 }
 // sets a.xrows; returns the number of row blocks (= blocks of `partial` to reduce)
-int launch_xtr(int cus, SplitArgs& a, hipStream_t s, bool sample) {
-  double per_cu = knobs().xtr_wgs_per_cu;  // (SLM_XTR_WGS_PER_CU, A/B runs: workgroups per CU, up to 2)
+int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, bool sample) {
+  double per_cu = kn.xtr_wgs_per_cu;  // (SLM_XTR_WGS_PER_CU, A/B runs: workgroups per CU, up to 2)
   const bool wide = a.lane_slots > SPLIT_LANES;  // thirty-two lanes: both planes of R per row of X
   if (wide) per_cu = 1.0;                        // (its partial sums fill the buffer at one workgroup per CU)
   const slm_host::XtrGrid g = slm_host::xtr_grid(a.n, a.ld, XTR_CB, (int64_t)(xtr_max_row_blocks(cus, a.ld) * per_cu / 2.0));
   const int xb = g.xb, yb = g.yb;
   a.xrows = g.rows;
   // seventeen to twenty lanes: the lanes beyond sixteen on the vector units beside the sixteen on the matrix cores
-  // (xtr18 / xtr20_mfma_kernel: the price of sixteen; SLM_XTR_EXTRAS=0: both halves on the matrix cores)
-  const int extra = wide && knobs().xtr_extras ? a.n_lanes - SPLIT_LANES : 0;
+  // (xtr18 / xtr20_mfma_kernel: the price of sixteen)
+  const int extra = wide ? a.n_lanes - SPLIT_LANES : 0;
   if (wide && extra >= 1 && extra <= 2) {
     if (sample) hipLaunchKernelGGL(xtr18_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
     else hipLaunchKernelGGL(xtr18_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
@@ -116,18 +116,18 @@ static int launch_cov_gz(int cus, SplitArgs& a, hipStream_t s, const CovBatch& c
   return yb;
 }
 
-const GradKernel* pick_grad_kernel(int64_t p2, int B) {
+const GradKernel* pick_grad_kernel(const slm_host::Knobs& kn, int64_t p2, int B) {
   if (p2 > kMaxChunks) return B == 1 ? &kGradTwoPass : nullptr;
   // LDS-ring variants: measured flat in B (0.60-0.61 ms for B = 1..4 at p = 5000) where the register
   // variants grow (0.598 / 0.599 / 0.615 / 0.733 ms on the same box), so they take over from B = 3.
   // SLM_GRAD_RING=0 disables them, =1 forces them for every B.
-  const bool ring_off = knobs().grad_ring == 0, ring_all = knobs().grad_ring == 1;
+  const bool ring_off = kn.grad_ring == 0, ring_all = kn.grad_ring == 1;
   if (!ring_off && p2 > 256 && (B >= 3 || ring_all)) {
     for (const auto& k : kGradRing)
       if (k.B == B && 64LL * k.W * k.C >= p2) return &k;
   }
-  if (knobs().grad_cfg[0] > 0) {  // (SLM_GRAD_CONFIG=W,C,R: tuning sweeps)
-    const int W = knobs().grad_cfg[0], C = knobs().grad_cfg[1], R = knobs().grad_cfg[2];
+  if (kn.grad_cfg[0] > 0) {  // (SLM_GRAD_CONFIG=W,C,R: tuning sweeps)
+    const int W = kn.grad_cfg[0], C = kn.grad_cfg[1], R = kn.grad_cfg[2];
     for (const auto& k : kGradDefault)
       if (k.B == B && k.W == W && k.C == C && k.R == R && 64LL * W * C >= p2) return &k;
     for (const auto& k : kGradExtra)
@@ -216,21 +216,21 @@ int enqueue_gradient(slm_dataset* ds, const LaneSetup& ls, const double* y, cons
 // the column-major copy on the matrix cores when that copy exists (working-set solves make it), otherwise
 // the vector kernel, five lanes per read of X (one window per grid row; a window returns at once unless
 // one of its lanes needs X) -- also the choice for calls of up to five lanes.  SLM_ROWDOT_RING=1/0 forces one.
-void launch_rowdot(slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s) {
+void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s) {
   // Measured at n = 100k, p = 5k (tools/rowdot_probe.py): matrix cores 0.75-0.80 ms whatever the lane count;
   // vector kernel 0.62 ms for one lane, 0.81 ms for five, 3.1 ms for sixteen (four reads of X).
   const int halves = (B + SPLIT_LANES - 1) / SPLIT_LANES;
-  const bool ring = sk->rowdot != nullptr && halves == 1 && (knobs().rowdot_ring >= 0 ? knobs().rowdot_ring == 1 : B <= ROWDOT_LANES);
+  const bool ring = sk->rowdot != nullptr && halves == 1 && (kn.rowdot_ring >= 0 ? kn.rowdot_ring == 1 : B <= ROWDOT_LANES);
   a.lane0 = 0;
   if ((!ring || sk->rowdot == nullptr) && ds->XT && ds->XT_ready) {
     a.XT = ds->XT;
-    // (thirty-two lanes: both halves against ONE read of the copy -- rowdot32_mfma_kernel; SLM_ROWDOT32=0: a read per half)
+    // (thirty-two lanes: both halves against ONE read of the copy -- rowdot32_mfma_kernel)
     // (seventeen to twenty lanes: the lanes beyond sixteen on the vector units beside the matrix cores' sixteen -- rowdot18 /
-    //  rowdot20_mfma_kernel, as for X^T R; SLM_XTR_EXTRAS=0: both halves on the matrix cores)
-    const bool extras = halves == 2 && B <= SPLIT_LANES + 4 && knobs().xtr_extras;
+    //  rowdot20_mfma_kernel, as for X^T R)
+    const bool extras = halves == 2 && B <= SPLIT_LANES + 4;
     if (extras && B <= SPLIT_LANES + 2) hipLaunchKernelGGL(rowdot18_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
     else if (extras) hipLaunchKernelGGL(rowdot20_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
-    else if (halves == 2 && knobs().rowdot32) hipLaunchKernelGGL(rowdot32_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
+    else if (halves == 2) hipLaunchKernelGGL(rowdot32_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
     else hipLaunchKernelGGL(rowdot_mfma_kernel, dim3(nblk, halves), dim3(XZ_WAVES * 64), 0, s, a);
   } else if (sk->rowdot != nullptr) {
     hipLaunchKernelGGL(sk->rowdot, dim3(nblk, (B + ROWDOT_LANES - 1) / ROWDOT_LANES), dim3(sk->W * 64), 0, s, a);
@@ -239,14 +239,14 @@ void launch_rowdot(slm_dataset* ds, const SplitKernel* sk, int nblk, int B, Spli
 }
 
 // The split pass needs a kernel for the residuals that come from X: a ring variant, or the column-major copy.
-bool split_usable(slm_dataset* ds) {
+bool split_usable(const slm_host::Knobs& kn, slm_dataset* ds) {
   if (!ds->sk) return false;
   if (ds->sk->rowdot != nullptr) return true;
-  if (ensure_xt(ds) != SLM_OK) return false;
+  if (ensure_xt(kn, ds) != SLM_OK) return false;
   return ds->XT != nullptr;
 }
 
-int enqueue_gradient_split(slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done,
+int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done,
                            const PathCtl* ctl, const WsArgs* wa, hipEvent_t ev_start,
                            hipEvent_t ev_stop, int64_t n_rows, bool unit_bracket, const int* skip) {
   hipStream_t s = ds->eng->stream;
@@ -268,19 +268,19 @@ int enqueue_gradient_split(slm_dataset* ds, const LaneSetup& ls, const double* y
   a.n = nr; a.ld = ds->ld; a.rows_base = nr / nblk; a.rows_rem = nr % nblk;
   a.p2 = (int)(ds->ld / 2);
   a.n_lanes = ls.B;
-  // (SLM_PROFILE_UNIT=1: the bracket of SLM_FLAG_PROFILE opens here -- the whole gradient unit, residuals and X^T R, not the
-  //  stream over X alone: bench.py's roofline.gradient_unit_frac)
-  const bool unit = ev_start != nullptr && (unit_bracket || knobs().profile_unit);
+  // (SLM_FLAG_PROFILE_UNIT: the bracket of SLM_FLAG_PROFILE opens here -- the whole gradient unit, residuals and X^T R, not
+  //  the stream over X alone: bench.py's roofline.gradient_unit_frac)
+  const bool unit = ev_start != nullptr && unit_bracket;
   if (unit) HIP_TRY(hipEventRecord(ev_start, s));
-  launch_rowdot(ds, sk, nblk, ls.B, a, s);
+  launch_rowdot(kn, ds, sk, nblk, ls.B, a, s);
   if (wa && ctl) {  // residuals from the gathered columns: matrix cores (SLM_RESID_VEC=1: a row per thread)
-    if (knobs().resid_vec && halves == 1) hipLaunchKernelGGL(sk->resid, dim3(nblk), dim3(256), 0, s, a);
-    else if (halves == 2 && knobs().resid32) hipLaunchKernelGGL(resid32_mfma_kernel, dim3(nblk, 1), dim3(RM_WAVES * 64), 0, s, a);  // (both halves on one read of the gathered columns)
+    if (kn.resid_vec && halves == 1) hipLaunchKernelGGL(sk->resid, dim3(nblk), dim3(256), 0, s, a);
+    else if (halves == 2) hipLaunchKernelGGL(resid32_mfma_kernel, dim3(nblk, 1), dim3(RM_WAVES * 64), 0, s, a);  // (both halves on one read of the gathered columns)
     else hipLaunchKernelGGL(resid_mfma_kernel, dim3(nblk, halves), dim3(RM_WAVES * 64), 0, s, a);
   }
   // (SLM_FLAG_PROFILE brackets the kernel that streams X, the one the roofline is quoted on)
   if (ev_start && !unit) HIP_TRY(hipEventRecord(ev_start, s));
-  const int xblk = launch_xtr(ds->eng->cus, a, s, n_rows > 0 && ctl != nullptr);  // (rows of a sample start: solve_core)
+  const int xblk = launch_xtr(kn, ds->eng->cus, a, s, n_rows > 0 && ctl != nullptr);  // (rows of a sample start: solve_core)
   if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, s));
   ReduceArgs ra;
   ra.partial = ds->partial;
@@ -348,7 +348,7 @@ int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int*
   a.R = ds->cov_Z; a.partial = partial; a.done = done;
   a.n = ld; a.ld = ld; a.p2 = (int)(ld / 2); a.n_lanes = B;
   // (points the model solver produced are zero outside the working set: only its rows of G are read then)
-  if (ctl && wa && wa->ws && !knobs().cov_all_rows) { a.ctl = ctl; a.ws = wa->ws; a.idx = wa->idx; }
+  if (ctl && wa && wa->ws) { a.ctl = ctl; a.ws = wa->ws; a.idx = wa->idx; }
   // (more than sixteen lanes: both planes of Z against ONE read of every Gram -- cov_gz32_mfma_kernel)
   a.lane0 = 0;
   a.r_plane = halves > 1 ? ld * SPLIT_RSTRIDE : 0;
@@ -416,24 +416,20 @@ int check_launch() {
 // steps' estimate, 80 us cheaper per solve (a launch chain of nine), and these solves only use L for a first candidate
 // and for fallback steps whose curvature guard repairs an under-estimate.  Round 3, same box, alternating: headline
 // 4.17-4.25 ms with three steps, 4.13-4.16 with two, 4.09-4.12 with one; passes of the headline, configs 3 / 4 and the
-// sparse-regime soak paths unchanged, dense-regime soak paths -3 ... +3 passes of 24-60 (SLM_L_SKETCH_ITERS).
-static const int kPowerItersSketchDefault = 1;
-int sketch_iters() {
-  return knobs().l_sketch_iters;  // (SLM_L_SKETCH_ITERS; default kPowerItersSketchDefault)
-}
+// sparse-regime soak paths unchanged, dense-regime soak paths -3 ... +3 passes of 24-60 (slm_host::kSketchPowerIters).
 static const int kPowerItersQuery = 16;
 // (a thirty-second of the rows: the bound is looser than from a sixteenth -- lambda_max of a sketch grows as it
-// shrinks -- and nothing downstream noticed down to a sixty-fourth, SLM_L_SKETCH_DIV; three steps on
+// shrinks -- and nothing downstream noticed down to a sixty-fourth; three steps on
 // 3 125 of 100 000 rows cost 0.10 ms where a sixteenth cost 0.17)
 int64_t sketch_rows(int64_t n) {
-  return std::max<int64_t>(1, n / knobs().l_sketch_div);  // (SLM_L_SKETCH_DIV; 32)
+  return std::max<int64_t>(1, n / slm_host::kSketchRowDiv);
 }
 
 // n_rows > 0: the operator of the first n_rows rows only, X_S^T W X_S / (n_eff n_rows / n).  Its largest
 // eigenvalue is, in expectation, no smaller than that of the full operator (Jensen: lambda_max is
 // convex and E G_S = G for exchangeable rows), so it serves as a cheap step-size bound where the
 // iteration does not depend on a tight one (working-set solves); the curvature guards cover the rest.
-int power_iteration(slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows) {
+int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows) {
   LaneSetup ls = ls_in;
   if (n_rows > 0) {
     for (int l = 0; l < kMaxLanes; ++l) {
@@ -442,14 +438,14 @@ int power_iteration(slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]
     }
   }
   hipStream_t s = ds->eng->stream;
-  if (knobs().power_iters > 0) iters = knobs().power_iters;
+  if (kn.power_iters > 0) iters = kn.power_iters;
   hipLaunchKernelGGL(power_init_kernel, dim3(ls.B), dim3(TAIL_THREADS), 0, s, ds->z, (int)ds->p, ds->ld);
   for (int k = 0; k < iters; ++k) {
     if (ds->gk[ls.B - 1]) {
       SLM_TRY(enqueue_gradient(ds, ls, ds->yzero, nullptr, nullptr, nullptr, n_rows));
     } else {  // more lanes than the fused kernels serve (working-set solves): the split pass has sixteen
-      if (!split_usable(ds)) return fail(SLM_ERR_UNSUPPORTED, "no %d-lane kernel for p = %lld", ls.B, (long long)ds->p);
-      SLM_TRY(enqueue_gradient_split(ds, ls, ds->yzero, nullptr, nullptr, nullptr, nullptr, nullptr, n_rows));
+      if (!split_usable(kn, ds)) return fail(SLM_ERR_UNSUPPORTED, "no %d-lane kernel for p = %lld", ls.B, (long long)ds->p);
+      SLM_TRY(enqueue_gradient_split(kn, ds, ls, ds->yzero, nullptr, nullptr, nullptr, nullptr, nullptr, n_rows));
     }
     PowerArgs pa;
     pa.g = ds->g;
@@ -477,10 +473,10 @@ int power_iteration(slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]
   return SLM_OK;
 }
 
-int estimate_lipschitz(slm_dataset* ds, double* L_out, int iters) {
+int estimate_lipschitz(const slm_host::Knobs& kn, slm_dataset* ds, double* L_out, int iters) {
   if (!ds->L_valid || ds->L_iters < iters) {
     double L[SLM_MAX_LANES];
-    SLM_TRY(power_iteration(ds, default_lanes(ds, 1), L, iters));
+    SLM_TRY(power_iteration(kn, ds, default_lanes(ds, 1), L, iters));
     ds->L = L[0];
     ds->L_iters = iters;
     ds->L_valid = true;
@@ -492,7 +488,7 @@ int estimate_lipschitz(slm_dataset* ds, double* L_out, int iters) {
 extern "C" int slm_dataset_lipschitz(slm_dataset* ds, double* L_out) {
   if (!ds || !L_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   HIP_TRY(hipSetDevice(ds->eng->device));
-  return estimate_lipschitz(ds, L_out, kPowerItersQuery);
+  return estimate_lipschitz(knobs(), ds, L_out, kPowerItersQuery);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -572,12 +568,13 @@ extern "C" int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradi
   if (opts) o = *opts;
   if (o.route < 0 || o.route > 1) return fail(SLM_ERR_BAD_ARG, "route must be 0 (fused) or 1 (split pass), got %d", o.route);
   if (o.n_lanes > kMaxLanes || o.probe_lanes > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "at most %d lanes", kMaxLanes);
+  const slm_host::Knobs kn = knobs();
   HIP_TRY(hipSetDevice(ds->eng->device));
   hipStream_t s = ds->eng->stream;
   HIP_TRY(hipMemsetAsync(ds->z, 0, sizeof(double) * ds->ld, s));
   if (z) HIP_TRY(hipMemcpyAsync(ds->z, z, sizeof(double) * ds->p, hipMemcpyHostToDevice, s));
-  const bool use_split = o.route == 1 && split_usable(ds);
-  if (use_split) SLM_TRY(ensure_xt(ds));  // (so that tests and probes reach rowdot_mfma_kernel; optional copy)
+  const bool use_split = o.route == 1 && split_usable(kn, ds);
+  if (use_split) SLM_TRY(ensure_xt(kn, ds));  // (so that tests and probes reach rowdot_mfma_kernel; optional copy)
   // (the split pass's wider forms: n_lanes lanes all at z, the gradient of lane lane_out returned)
   int lanes_run = 1, lane_out = 0;
   if (use_split && ds->XT && ds->XT_ready && (size_t)ds->lane_cap >= (size_t)kMaxLanes) {
@@ -591,7 +588,7 @@ extern "C" int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradi
   };
   const LaneSetup ls = default_lanes(ds, lanes_run);
   SLM_TRY(spread_z(lanes_run));
-  if (use_split) SLM_TRY(enqueue_gradient_split(ds, ls, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr));
+  if (use_split) SLM_TRY(enqueue_gradient_split(kn, ds, ls, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr));
   else SLM_TRY(enqueue_gradient(ds, ls, ds->y, nullptr, nullptr, nullptr));
   SLM_TRY(check_launch());
   HIP_TRY(hipStreamSynchronize(s));
@@ -606,7 +603,7 @@ extern "C" int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradi
   SLM_TRY(spread_z(B));
   const LaneSetup lb = default_lanes(ds, B);
   if (use_split) {  // residuals from X + X^T R (or X^T R alone)
-    SLM_TRY(enqueue_gradient_split(ds, lb, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr));  // warm; allocates R
+    SLM_TRY(enqueue_gradient_split(kn, ds, lb, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr));  // warm; allocates R
     SplitArgs a;
     memset(&a, 0, sizeof(a));
     a.X = ds->X; a.y = ds->y; a.rw = lb.rw; a.rw_stride = 0; a.z = ds->z; a.R = ds->R;
@@ -615,8 +612,8 @@ extern "C" int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradi
     a.p2 = (int)(ds->ld / 2); a.n_lanes = B;
     a.lane_slots = SPLIT_LANES * ((B + SPLIT_LANES - 1) / SPLIT_LANES); a.r_plane = (int64_t)ds->n * SPLIT_RSTRIDE;
     return timed_launches(s, reps, ms_out, [&]() -> int {
-      if (!o.xtr_only) launch_rowdot(ds, ds->sk, ds->split_nblk, B, a, s);
-      (void)launch_xtr(ds->eng->cus, a, s);
+      if (!o.xtr_only) launch_rowdot(kn, ds, ds->sk, ds->split_nblk, B, a, s);
+      (void)launch_xtr(kn, ds->eng->cus, a, s);
       return SLM_OK;
     });
   }
@@ -708,6 +705,7 @@ extern "C" int slm_eval_sse(slm_dataset* ds, const double* Z, int32_t m, const d
                             double* sse_out) {
   if (!ds || !Z || !sse_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   if (m <= 0) return fail(SLM_ERR_BAD_ARG, "m must be positive");
+  const slm_host::Knobs kn = knobs();
   HIP_TRY(hipSetDevice(ds->eng->device));
   hipStream_t s = ds->eng->stream;
   const int64_t n = ds->n, p = ds->p, ld = ds->ld;
@@ -731,8 +729,8 @@ extern "C" int slm_eval_sse(slm_dataset* ds, const double* Z, int32_t m, const d
   // More vectors than a fused pass takes (four at p = 5 000): the residual half of the split pass forms X z - y for SIXTEEN
   // per read of X and leaves the blocks' sums of w e^2 behind -- all a score needs.  (The dense ends of a grid's paths,
   // whose joint support is beyond slm_eval_sse_sparse: 50 candidates of a fold in 4 reads instead of 13.)
-  if (m > maxB && ds->sk != nullptr && !row_sharded(ds) && split_usable(ds) && !knobs().eval_fused &&
-      (ds->sk->rowdot != nullptr || (ensure_xt(ds) == SLM_OK && ds->XT && ds->XT_ready))) {
+  if (m > maxB && ds->sk != nullptr && !row_sharded(ds) && split_usable(kn, ds) && !kn.eval_fused &&
+      (ds->sk->rowdot != nullptr || (ensure_xt(kn, ds) == SLM_OK && ds->XT && ds->XT_ready))) {
     const int nblk = ds->split_nblk;
     if (!ds->R) {
       SLM_TRY(dalloc(&ds->R, (size_t)n * SPLIT_RSTRIDE * SPLIT_HALVES));
@@ -750,7 +748,7 @@ extern "C" int slm_eval_sse(slm_dataset* ds, const double* Z, int32_t m, const d
       a.p2 = (int)(ld / 2);
       a.n_lanes = B;
       a.lane_slots = SPLIT_LANES; a.r_plane = (int64_t)n * SPLIT_RSTRIDE;
-      launch_rowdot(ds, ds->sk, nblk, B, a, s);
+      launch_rowdot(kn, ds, ds->sk, nblk, B, a, s);
       hipLaunchKernelGGL(sse_from_blocks_kernel, dim3(1), dim3(64), 0, s, ds->loss_partial, nblk, SPLIT_LANES, ds->partial);
       SLM_TRY(check_launch());
       HIP_TRY(hipMemcpyAsync(losses.data(), ds->partial, sizeof(double) * SPLIT_LANES, hipMemcpyDeviceToHost, s));
@@ -778,7 +776,7 @@ extern "C" int slm_eval_sse(slm_dataset* ds, const double* Z, int32_t m, const d
 }
 
 // column-major copy of X for column gathers (see solve_core / ws_setup); optional (no memory: nullptr)
-int ensure_xt(slm_dataset* ds) {
+int ensure_xt(const slm_host::Knobs& kn, slm_dataset* ds) {
   hipStream_t s = ds->eng->stream;
   const int64_t n = ds->n, ld = ds->ld;
   const int64_t row_tiles = (n + 31) / 32;
@@ -797,7 +795,7 @@ int ensure_xt(slm_dataset* ds) {
   }
   // the column norms certified partial passes bound with (light_kernels.hpp): one read of the copy, kept beside it
   // (unweighted own rows of one device: the only datasets such passes serve)
-  if (ds->XT && ds->XT_ready && !ds->colnorm_ready && !ds->rw && !row_sharded(ds) && knobs().light_pass) {
+  if (ds->XT && ds->XT_ready && !ds->colnorm_ready && !ds->rw && !row_sharded(ds) && kn.light_pass) {
     if (!ds->colnorm && pool_malloc((void**)&ds->colnorm, sizeof(double) * (size_t)ld) != hipSuccess) {
       (void)hipGetLastError();
       ds->colnorm = nullptr;
@@ -833,7 +831,7 @@ extern "C" int slm_eval_sse_sparse(slm_dataset* ds, const int32_t* cols, int32_t
   ds->ws_carry_valid = false;  // (this call gathers its own columns into the working set's buffers)
   if (!ds->ws_idx) SLM_TRY(dalloc(&ds->ws_idx, WS_KCAP));
   if (!ds->ws_XW) SLM_TRY(dalloc(&ds->ws_XW, (size_t)n * WS_KCAP));
-  SLM_TRY(ensure_xt(ds));
+  SLM_TRY(ensure_xt(knobs(), ds));
   const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(eng->cus * 4, (n + 255) / 256));
   // scratch of the scoring loop of a grid search, kept with the dataset (it used to be allocated and freed per
   // call): the coefficient block grows on demand, the per-workgroup partial sums have a fixed size
@@ -904,7 +902,8 @@ extern "C" int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, cons
   const int p = (int)ds->p, G = ds->G;
   const int64_t ld = ds->ld;
   const int gm = ds->max_group;
-  if (!knobs().on_chip) return fail(SLM_ERR_UNSUPPORTED, "the on-chip solvers are switched off (SLM_ON_CHIP=0)");
+  const slm_host::Knobs kn = knobs();
+  if (!kn.on_chip) return fail(SLM_ERR_UNSUPPORTED, "the on-chip solvers are switched off (SLM_ON_CHIP=0)");
   if (row_sharded(ds) || ds->rw || p > SM_PMAX || (double)ds->n * (double)ld > 131072.0)
     return fail(SLM_ERR_UNSUPPORTED, "the splitting runs on chip for unweighted, unsharded problems of p <= %d and n * ld <= 131072", SM_PMAX);
   // LDS: Gram matrix, three vectors, the groups' Cholesky factors; what is left stages the rows of the build and
@@ -962,7 +961,7 @@ extern "C" int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, cons
   slm_point_info rec;
   memcpy(&rec, h_out + rec_off, sizeof(rec));
   memcpy(beta_out, h_out + 2 * ld + 4, sizeof(double) * p);
-  if (knobs().trace == 2)
+  if (kn.trace == 2)
       fprintf(stderr, "[slm] standardised sparse-group splitting on chip: %d sweeps, %d products, %d b-steps by a direct solve, %d factorisations, rho %.3e\n",
               rec.n_iter, rec.rejects, (int)h_out[2 * ld + 2], (int)h_out[2 * ld + 3], rec.L);
   if (group_norms_out) memcpy(group_norms_out, h_out + rec_off + (sizeof(slm_point_info) + 7) / 8, sizeof(double) * G);

@@ -34,11 +34,9 @@ namespace slm {
 
 typedef _Float16 mg_h8 __attribute__((ext_vector_type(8)));
 typedef float mg_f16v __attribute__((ext_vector_type(16)));
-typedef unsigned int mg_u4 __attribute__((ext_vector_type(4)));
 
 constexpr int MG_TILE = 128;               // result tile of a workgroup (four wavefronts, 64 x 64 each)
 constexpr int MG_BK = 64;                  // rows of X per step of the product
-constexpr int MG_LDS_STRIDE = MG_BK + 8;   // halves per LDS row: 144 bytes -- sixteen rows fall on sixteen different 16-byte slots
 constexpr int MG_MAX_LD = 16384;           // the Gram is 4 ld^2 bytes (fp32): 1 GB at most; beyond, slm_dataset_model_gram refuses
                                            // (SLM_ERR_UNSUPPORTED) and solves go on with plain steps: tests/test_width_limits_gpu.py
 constexpr int MG_CHUNK_ROWS = 6400;        // rows per fp32 accumulation (chunks are summed in fp64): 100 steps of MG_BK
@@ -165,8 +163,7 @@ static __global__ __launch_bounds__(256) void mg_convert_kernel(MgConvArgs a) {
 // (3) the product: P[chunk][tile] = M_I M_J^T over the rows of one chunk, M = XTh, for the 128 x 128 tiles (I, J <= I) of the
 // lower triangle.  Four wavefronts, each a 64 x 64 corner as 2 x 2 tiles of v_mfma_f32_32x32x16_f16; both operands come
 // through LDS in steps of MG_BK rows (128 bytes of every one of the tile's 128 columns: full lines), the loads of the next
-// step are in flight while the current one is multiplied.  The fragment a lane needs -- 8 consecutive rows of one column --
-// is 16 bytes of an LDS row; rows are 144 bytes apart, so the sixteen lanes of a ds_read_b128 group hit sixteen slots.
+// step are in flight while the current one is multiplied.
 // Work items are numbered chunk-major and dealt to the XCDs in contiguous ranges: the workgroups of an XCD work on one
 // chunk of rows at a time, whose 128-byte pieces of all columns (640 KB at p = 5k) stay in its L2.
 struct MgSyrkArgs {
@@ -177,93 +174,9 @@ struct MgSyrkArgs {
   int n_chunks;
   float* P;           // [n_chunks][n_tiles][128 x 128]
 };
-static __global__ __launch_bounds__(256) void mg_syrk_f16_kernel(MgSyrkArgs a) {
-  __shared__ __attribute__((aligned(16))) _Float16 As[MG_TILE * MG_LDS_STRIDE];
-  __shared__ __attribute__((aligned(16))) _Float16 Bs[MG_TILE * MG_LDS_STRIDE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int64_t m;
-  {
-    const int64_t total = gridDim.x, lin = blockIdx.x;
-    const int64_t xcd = lin & 7, slot = lin >> 3, base = total >> 3, rem = total & 7;
-    m = xcd * base + (xcd < rem ? xcd : rem) + slot;
-  }
-  const int chunk = (int)(m / a.n_tiles), tile = (int)(m - (int64_t)chunk * a.n_tiles);
-  int I, J;
-  slm_host::triangle_tile_fast(tile, &I, &J);  // (host_logic.hpp: tile t = (I, J <= I) of the lower triangle)
-  const int64_t k0 = (int64_t)chunk * a.k_chunk;
-  const int64_t k1 = k0 + a.k_chunk < a.n_pad ? k0 + a.k_chunk : a.n_pad;
-  // staging: thread -> (row (tid >> 3) + 32 u, 16-byte piece tid & 7)
-  const int srow = tid >> 3, spc = tid & 7;
-  const _Float16* Ag = a.M + ((int64_t)I * MG_TILE + srow) * a.n_pad + 8 * spc;
-  const _Float16* Bg = a.M + ((int64_t)J * MG_TILE + srow) * a.n_pad + 8 * spc;
-  mg_u4 ra[4], rb[4];
-  auto gload = [&](int64_t k) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      ra[u] = *reinterpret_cast<const mg_u4*>(Ag + (int64_t)(32 * u) * a.n_pad + k);
-      rb[u] = *reinterpret_cast<const mg_u4*>(Bg + (int64_t)(32 * u) * a.n_pad + k);
-    }
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      *reinterpret_cast<mg_u4*>(As + (srow + 32 * u) * MG_LDS_STRIDE + 8 * spc) = ra[u];
-      *reinterpret_cast<mg_u4*>(Bs + (srow + 32 * u) * MG_LDS_STRIDE + 8 * spc) = rb[u];
-    }
-  };
-  const int wr = wave >> 1, wc = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  mg_f16v acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
-  if (k0 < k1) {
-    gload(k0);
-    lstore();
-    __syncthreads();
-    for (int64_t k = k0; k < k1; k += MG_BK) {
-      const bool more = k + MG_BK < k1;
-      if (more) gload(k + MG_BK);
-#pragma unroll
-      for (int kk = 0; kk < MG_BK / 16; ++kk) {
-        mg_h8 af[2], bf[2];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-          af[mi] = *reinterpret_cast<const mg_h8*>(As + (64 * wr + 32 * mi + r) * MG_LDS_STRIDE + 16 * kk + 8 * h);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          bf[ni] = *reinterpret_cast<const mg_h8*>(Bs + (64 * wc + 32 * ni + r) * MG_LDS_STRIDE + 16 * kk + 8 * h);
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
-      }
-      __syncthreads();
-      if (more) {
-        lstore();
-        __syncthreads();
-      }
-    }
-  }
-  float* out = a.P + ((int64_t)chunk * a.n_tiles + tile) * (MG_TILE * MG_TILE);
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = 64 * wr + 32 * mi + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const int col = 64 * wc + 32 * ni + r;
-        out[row * MG_TILE + col] = acc[mi][ni][e];
-      }
-}
 
-// The same product with the operands brought into LDS by the DMA path (global_load_lds_dwordx4: no staging registers, no
-// ds_write -- the 16-byte LDS stores of the kernel above cost more LDS cycles than its fragment reads), two buffers, the
+// The operands are brought into LDS by the DMA path (global_load_lds_dwordx4: no staging registers, no ds_write -- the
+// 16-byte LDS stores of a register-staged form cost more LDS cycles than its fragment reads), two buffers, the
 // next step's tiles in flight while the current one is multiplied, one barrier per step.  A DMA instruction fills 1 KiB of
 // LDS in lane order, so the tiles are stored unpadded ([128 rows][64 halves]) and the 16-byte pieces of a row are swizzled
 // instead -- piece c of row R sits in slot c ^ ((R >> 1) & 7), applied to the SOURCE address of the load and to the

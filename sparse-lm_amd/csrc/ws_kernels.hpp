@@ -145,7 +145,7 @@ struct WsArgs {
   int32_t miss_factor; // an append after a miss may take up to this many times append_max (4) ...
   int32_t miss_div;    // ... one more append_max for every miss_div coordinates the plain steps moved outside W
   double fill;         // a selection cut down to a cap stops bisecting its threshold once it holds this share of the cap
-  int32_t power_iters; // power steps for lambda_max of a new Gram (SLM_WS_POWER_ITERS)
+  int32_t power_iters; // power steps for lambda_max of a new Gram (slm_host::kWsPowerIters)
   int32_t hard_call;   // SLM_HARD_CALLWIDE=1 (A/B runs): direct steps once needed start every later refinement of the CALL
   int32_t keep_full;   // a selection that does not fit leaves W as it is (`stale`: the lanes it no longer covers are served by
                        // the model-Gram rounds) instead of selecting, gathering and multiplying afresh pass after pass

@@ -243,6 +243,17 @@ static void test_interleaved_sixteen_lanes() {
   }
 }
 
+// what normal use runs with: nothing set
+static void check_defaults(const Knobs& d) {
+  CHECK(d.split && d.on_chip && d.interleave && d.carry && d.ws_carry);
+  CHECK(d.ws == -1 && d.mg == -1 && d.grad_ring == -1 && d.rowdot_ring == -1 && d.auto_lanes == 0 && d.trace == 0);
+  CHECK(d.ws_theta == 0.85 && d.ws_append == 48 && d.ws_kinit == 0 && d.ws_fill == 0.0);
+  CHECK(d.sample_start && d.sample_min_rows == 65536 && d.sample_div == 4);
+  CHECK(d.device_pool_gb < 0.0 && !d.allow_any_arch && d.xtr_wgs_per_cu == 1.0 && d.handover);
+  CHECK(!d.eval_fused && d.power_iters == 0 && d.grad_cfg[0] == 0);
+  CHECK(d.light_pass && d.gram_owner && d.lag_handover && d.ws_miss_factor == 4 && d.ws_miss_div == 8);  // (round 6)
+}
+
 // the SLM_* knobs: read once into a struct (round-5 verdict, item 5) -- defaults, every kind of field, clamping, reload
 static void test_knobs() {
   std::map<std::string, std::string> env;
@@ -250,14 +261,19 @@ static void test_knobs() {
     auto it = env.find(name);
     return it == env.end() ? nullptr : it->second.c_str();
   };
-  const Knobs d = Knobs::from(get);  // nothing set: what normal use runs with
-  CHECK(d.split && d.xtr_extras && d.rowdot32 && d.resid32 && d.on_chip && d.wide_lanes && d.interleave && d.carry && d.ws_carry);
-  CHECK(d.ws == -1 && d.mg == -1 && d.grad_ring == -1 && d.rowdot_ring == -1 && d.auto_lanes == 0 && d.trace == 0);
-  CHECK(d.ws_theta == 0.85 && d.ws_lookahead == 2 && d.ws_append == 48 && d.ws_kinit == 0 && d.ws_fill == 0.0 && d.ws_power_iters == 10);
-  CHECK(d.sample_start && !d.sample_start_all && d.sample_min_rows == 65536 && d.sample_div == 4 && d.l_sketch_div == 32 && d.l_sketch_iters == 1);
-  CHECK(d.device_pool && d.device_pool_gb < 0.0 && !d.allow_any_arch && d.xtr_wgs_per_cu == 1.0 && d.direct && d.mg_keep && d.handover);
-  CHECK(!d.profile_unit && !d.eval_fused && d.power_iters == 0 && d.grad_cfg[0] == 0);
-  CHECK(d.light_pass && d.gram_owner && d.lag_handover && d.ws_miss_factor == 4 && d.ws_miss_div == 8);  // (round 6)
+  check_defaults(Knobs::from(get));
+  // the settings that were knobs once keep the values they defaulted to
+  CHECK(kSketchPowerIters == 1 && kSketchRowDiv == 32 && kWsLookahead == 2 && kWsPowerIters == 10);
+  // the retired variables, each at its former non-default value: read by nothing
+  for (const char* name : {"SLM_XTR_EXTRAS", "SLM_ROWDOT32", "SLM_MG_SYRK"}) env[name] = "0";
+  for (const char* name : {"SLM_NO_RESID32", "SLM_NO_SLACK_DEEP", "SLM_NO_DIRECT", "SLM_NO_L_SKETCH", "SLM_NO_SKETCH_CACHE",
+                           "SLM_NO_MG_KEEP", "SLM_NO_SMALL_STAGE", "SLM_NO_WIDE_LANES", "SLM_SAMPLE_START_ALL", "SLM_COV_ALL_ROWS",
+                           "SLM_ON_CHIP_NO_FALLBACK", "SLM_PROFILE_UNIT", "SLM_NO_DEVICE_POOL"})
+    env[name] = "1";
+  env["SLM_L_SKETCH_ITERS"] = "3"; env["SLM_L_SKETCH_DIV"] = "16"; env["SLM_WS_LOOKAHEAD"] = "4";
+  env["SLM_WS_POWER_ITERS"] = "20"; env["SLM_GRAD_BLOCKS_PER_CU"] = "2";
+  check_defaults(Knobs::from(get));
+  env.clear();
   env["SLM_WS"] = "0"; env["SLM_MG"] = "2"; env["SLM_TRACE"] = "3"; env["SLM_TRACE_POLL"] = "1"; env["SLM_SPLIT"] = "0";
   env["SLM_GRAD_CONFIG"] = "8,5,2"; env["SLM_WS_THETA"] = "0.7"; env["SLM_WS_APPEND"] = "9999"; env["SLM_WS_KINIT"] = "3";
   env["SLM_SAMPLE_DIV"] = "0"; env["SLM_SAMPLE_START_MIN_ROWS"] = "10"; env["SLM_XTR_WGS_PER_CU"] = "7"; env["SLM_NO_CARRY"] = "";

@@ -1,5 +1,5 @@
 """AdaptiveGroupLasso on the on-chip solver, 25 x 30: how many re-weighting rounds each lane takes in one launch (in-launch re-weighting against the loop of calls)."""
-import os, sys, warnings
+import sys, warnings
 import numpy as np
 sys.path.insert(0, "/root/repo/sparse-lm_amd")
 from sklearn.datasets import make_regression
@@ -15,9 +15,7 @@ with eng.dataset(Xc, yc) as ds:
     b = alpha * np.ones(6)
     for rnd in range(3):
         ref = ds.solve_path([(0.0, 1.0, 0.0)], b=b, tol=1e-10, want_group_norms=True)
-        os.environ["SLM_ON_CHIP_NO_FALLBACK"] = "1"
         r = ds.solve_path([(0.0, 1.0, 0.0)], b=b, tol=1e-10, flags=_engine.FLAG_ON_CHIP, want_group_norms=True)
-        del os.environ["SLM_ON_CHIP_NO_FALLBACK"]
         print(f"round {rnd}: b = {np.array2string(b, precision=3)}")
         print(f"   general: conv {ref.converged} passes {ref.grad_launches} gn {np.array2string(ref.group_norms[0], precision=4)}")
         print(f"   on chip: conv {r.converged} products {r.n_iter[0]} kkt {r.kkt[0]:.3e} resid {r.resid[0]:.3e} mu {r.mu[0]:.3e} L {r.L:.3e} "

@@ -1,7 +1,7 @@
 """The kernels of rounds 3-4 that the headline bench does not reach, one after the other, for `rocprofv3` (kernel trace or
 counters; run the program directly after `--`): the folds' Grams of BASELINE config 4 (cov_syrk_packed_kernel, cov_unpack_kernel;
-then one row set on its own: cov_syrk_kernel), config 4's grid from the Grams (cov_gz_mfma_kernel in both of its ways:
-listed rows of the Gram, all rows), the reference's problem sizes on chip (small_solve_kernel, small_stdsgl_kernel), and
+then one row set on its own: cov_syrk_kernel), config 4's grid from the Grams (cov_gz_mfma_kernel on the
+listed rows of the Gram), the reference's problem sizes on chip (small_solve_kernel, small_stdsgl_kernel), and
 BASELINE config 5's per-rank shape (grad_fused_kernel<8,10,1,1> at p = 10 000, the streaming tail kernel).
 usage: python tools/r04_targets.py [grams] [grid] [small] [config5]   (default: all)"""
 import os
@@ -47,11 +47,6 @@ if want & {"grams", "grid"}:
         for rep in range(3):
             sec, passes = c4.run(calls)
             note(f"config 4 from the Grams: {passes} passes, {1e3 * sec:.2f} ms")
-        os.environ["SLM_COV_ALL_ROWS"] = "1"  # every pass reads all rows of its Grams
-        for rep in range(2):
-            sec, passes = c4.run(calls)
-            note(f"... every pass over all rows of the Gram: {passes} passes, {1e3 * sec:.2f} ms")
-        del os.environ["SLM_COV_ALL_ROWS"]
     c4.close()
 
 if "small" in want:
