@@ -731,6 +731,7 @@ int PathCall::stage_lanes() {
   ta.betas_out = ds->betas_out;
   ta.gn_out = any_gn ? ds->gn_out : nullptr;
   ta.infos = d_infos;
+  ta.lt = &ds->dctl->lt;  // (the tail keeps the light passes' per-lane slack / epoch in step with gprev: light_ctl.hpp)
 
   return SLM_OK;
 }
@@ -1249,6 +1250,10 @@ void PathCall::trace_pass(const DevCtl& now) const {
   for (int l = 0; l < B; ++l)
     fprintf(stderr, " %d.%d%s%s%s", now.lane[l].point, now.lane[l].iter, now.lane[l].done ? "d" : "", now.lane[l].zsup ? "w" : "",
             l < SLM_MAX_LANES && now.mg.lane[l].active ? "m" : "");
+  // the light passes' state per lane: candidates rejected so far, and the attempt the base gradient comes from (0: a pass
+  // over X) with its slack -- the id of the last attempt and whether it stood first
+  fprintf(stderr, " | lt id %d ok %d | lanes (rejects/epoch/slack):", now.lt.id, now.lt.ok);
+  for (int l = 0; l < B && l < SLM_MAX_LANES; ++l) fprintf(stderr, " %d/%d/%.3g", now.lane[l].rejects, now.lt.epoch[l], now.lt.slack[l]);
   fprintf(stderr, "\n");
 }
 
@@ -1316,6 +1321,7 @@ int PathCall::queue_chunk() {
     }
     if (light) SLM_TRY(enqueue_light_attempt());
     light_skip = light ? &ds->dctl->lt.ok : nullptr;
+    ta.light = light ? 1 : 0;
     const bool sample_pass = n_sample > 0 && enq == 0;
     if (sample_pass) {
       LaneSetup part = ls;

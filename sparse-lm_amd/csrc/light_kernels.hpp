@@ -14,7 +14,10 @@
 //   * a column outside W with |g_j(z)| + c_j (S + D) < threshold_j CANNOT enter at b whatever its exact gradient is (S: the
 //     slack of g(z) itself, zero when it came from a pass over X): the prox step keeps it at zero either way;
 //   * the BORDERLINE columns -- the others, a few dozen to a few hundred -- get their exact gradient from their own rows of
-//     the column-major copy: X_j^T dR, 0.8 MB per column instead of 4 GB for all.
+//     the column-major copy: X_j^T dR, 0.8 MB per column instead of 4 GB for all.  That increment is exact only where g_j(z)
+//     is: a lane whose base gradient is itself a hybrid one (LightCtl::epoch != 0) is off by up to c_j S on a borderline
+//     column the attempt before did not read, and an increment would carry that error into a column the tail treats as
+//     exact.  Such a lane gets X_j^T R(b) / n instead, R(b) = X_W b_W - y its residual at b: exact whatever g(z) was.
 // The tail kernel then runs on this hybrid gradient -- exact on W and on the borderline set, the base point's elsewhere,
 // where it provably cannot matter -- under its unchanged acceptance test and stopping rule: the proximal-gradient mapping
 // it evaluates is the one the true gradient gives, coordinate for coordinate.  A point accepted this way is a certified
@@ -28,35 +31,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "light_ctl.hpp"
 #include "split_kernels.hpp"
 #include "tail_kernels.hpp"
 #include "ws_kernels.hpp"
 
 namespace slm {
 
-constexpr int LT_CAP = 1024;  // borderline columns one attempt may read (0.8 MB each at n = 100k)
-constexpr int LT_LANES = 8;   // live lanes one attempt serves: their points and their moves share sixteen MFMA columns
 constexpr int LT_WAVES = 8;   // wavefronts of light_resid_kernel
 
-struct LightCtl {
-  int32_t ok;        // the attempt of this pass stands: the kernels of the pass over X behind it return at once
-  int32_t n_cols;    // borderline columns listed (lt_idx)
-  int32_t n_live;    // live lanes of the attempt ...
-  int32_t lane_of[LT_LANES];  // ... and which they are
-  int32_t attempts;  // over the solve
-  int32_t used;      // ... of which stood (passes over X saved)
-  int32_t cols_total;  // borderline columns read by all of them
-  int32_t why;       // why the last attempt stood down: 1 too many live lanes, 2 a live lane off W or without the set,
-                     // 3 too many borderline columns, 4 W holds a column a lane's hybrid gradient is not exact on (SLM_TRACE=3)
-  int32_t id;        // number of the attempt under way (1, 2, ...: `attempts` as light_prepare_kernel counted it)
-  int32_t epoch[SLM_MAX_LANES];  // per LANE: the attempt its base gradient g(z) comes from, 0: from a pass over X.  A hybrid
-                                 // gradient is exact on the columns that attempt stamped (LightArgs::stamp) -- W and the
-                                 // borderline set of its time -- and the working set's model reads g(z) on ALL of W: a lane
-                                 // whose W has since taken in a column outside that set goes back to a pass over X (why 4)
-  double D[LT_LANES];            // ||X_W (b - z)|| / sqrt(n) of live lane s
-  double slack[SLM_MAX_LANES];   // per LANE: what its base gradient g(z) may be off by, in units of c_j, outside the columns
-                                 // it is exact on: 0 after a pass over X, + D after every light pass
-};
+// LT_CAP, LT_LANES and the control block LightCtl: light_ctl.hpp
 
 struct LightArgs {
   LightCtl* lt;
@@ -74,7 +58,7 @@ struct LightArgs {
   const double *z, *zprev, *gprev, *a0, *b0;  // per lane, stride ld
   double* g;             // [lanes][ld + 16]
   double* loss_partial;  // [nblk][slots]
-  double* dR;            // [n][LT_LANES] the moves' residual changes
+  double* dR;            // [n][LT_LANES] the moves' residual changes (the residuals at b of lanes on a hybrid base gradient)
   double* d2_part;       // [nblk][LT_LANES]
   int32_t* cols;         // [LT_CAP] borderline columns
   int32_t* stamp;        // [ld] the attempt that last made column j's gradient exact for its live lanes (0: none this solve)
@@ -180,11 +164,9 @@ static __global__ __launch_bounds__(1024) void light_prepare_kernel(LightArgs a)
     for (int l = 0; l < a.n_lanes && s < LT_LANES; ++l)
       if (live_s[l]) lt->lane_of[s++] = l;
     lt->n_live = why == 0 ? s : 0;
-    if (why != 0)  // the pass over X behind this attempt delivers true gradients again
-      for (int l = 0; l < SLM_MAX_LANES; ++l) {
-        lt->slack[l] = 0.0;
-        lt->epoch[l] = 0;
-      }
+    // (no lane's slack / epoch changes here: the pass over X behind an attempt that stands down delivers true gradients to
+    //  the lanes the tail serves, and the tail resets theirs when it stores one -- a done or idle lane keeps its base
+    //  gradient, hybrid or not, and with it its own)
   }
 }
 
@@ -218,6 +200,8 @@ static __global__ __launch_bounds__(LT_WAVES * 64) void light_resid_kernel(Light
   }
   __syncthreads();
   const int i16 = lane & 15, q = lane >> 4;
+  // dR of live lane s: its move, or -- for a lane whose base gradient is a hybrid one -- its residual at b (see the top)
+  const bool resid_s = (i16 & 7) < n_live && a.lt->epoch[a.lt->lane_of[i16 & 7]] != 0;
   const int ngroups = K >> 4;
   const int ntiles = (int)((nrows + 15) >> 4);
   double acc_sq = 0.0;  // slot i16: sum of squared errors (slots < 8) / of squared residual changes (slots >= 8)
@@ -261,8 +245,9 @@ static __global__ __launch_bounds__(LT_WAVES * 64) void light_resid_kernel(Light
         if (i16 < 8) {
           const double err = acc[r] - yv[r];
           acc_sq = __builtin_fma(err, err, acc_sq);
+          if (resid_s) a.dR[row * LT_LANES + i16] = err;
         } else {
-          a.dR[row * LT_LANES + (i16 - 8)] = acc[r];
+          if (!resid_s) a.dR[row * LT_LANES + (i16 - 8)] = acc[r];
           acc_sq = __builtin_fma(acc[r], acc[r], acc_sq);
         }
       }
@@ -370,18 +355,14 @@ static __global__ __launch_bounds__(1024) void light_select_kernel(LightArgs a) 
         lt->n_cols = gtotal;
         lt->used += 1;
         lt->cols_total += gtotal;
-        for (int sl = 0; sl < n_live; ++sl) {
+        for (int sl = 0; sl < n_live; ++sl) {  // (pending: the tail commits them with the point it accepts)
           lt->D[sl] = Ds[sl] - lt->slack[lane_s[sl]];
-          lt->slack[lane_s[sl]] = Ds[sl];
-          lt->epoch[lane_s[sl]] = lt->id;
+          lt->pend_slack[lane_s[sl]] = Ds[sl];
+          lt->pend_epoch[lane_s[sl]] = lt->id;
         }
       } else {
         lt->ok = 0;
         lt->why = 3;
-        for (int l = 0; l < SLM_MAX_LANES; ++l) {
-          lt->slack[l] = 0.0;
-          lt->epoch[l] = 0;
-        }
       }
     }
     return;
@@ -451,18 +432,14 @@ static __global__ __launch_bounds__(1024) void light_select_kernel(LightArgs a) 
       lt->n_cols = total;
       lt->used += 1;
       lt->cols_total += total;
-      for (int s = 0; s < n_live; ++s) {
+      for (int s = 0; s < n_live; ++s) {  // (pending: the tail commits them with the point it accepts)
         lt->D[s] = Ds[s] - lt->slack[lane_s[s]];
-        lt->slack[lane_s[s]] = Ds[s];
-        lt->epoch[lane_s[s]] = lt->id;
+        lt->pend_slack[lane_s[s]] = Ds[s];
+        lt->pend_epoch[lane_s[s]] = lt->id;
       }
     } else {
       lt->ok = 0;
       lt->why = 3;
-      for (int l = 0; l < SLM_MAX_LANES; ++l) {
-        lt->slack[l] = 0.0;
-        lt->epoch[l] = 0;
-      }
     }
   }
 }
@@ -557,13 +534,16 @@ static __global__ __launch_bounds__(1024) void light_assemble_kernel(LightArgs a
     g[j] = gp[j] + acc;
     a.stamp[j] = id;
   }
-  // on the borderline set: the row blocks' sums in block order
+  // on the borderline set: the row blocks' sums in block order -- the increment X_j^T dR / n on an exact base gradient, the
+  // whole gradient X_j^T R(b) / n on a hybrid one (light_resid_kernel)
+  const bool whole = lt->epoch[l] != 0;
   const int n_cols = lt->n_cols;
   for (int c = tid; c < n_cols; c += 1024) {
     const int j = a.cols[c];
     double s4[4] = {0.0, 0.0, 0.0, 0.0};
     for (int b = 0; b < a.nblk; ++b) s4[b & 3] += a.part[((int64_t)b * LT_CAP + c) * LT_LANES + s];
-    g[j] = gp[j] + ((s4[0] + s4[1]) + (s4[2] + s4[3])) * a.inv_n;
+    const double xr = ((s4[0] + s4[1]) + (s4[2] + s4[3])) * a.inv_n;
+    g[j] = whole ? xr : gp[j] + xr;
     a.stamp[j] = id;
   }
   double ls[1] = {0.0};

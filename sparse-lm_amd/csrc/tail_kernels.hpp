@@ -19,6 +19,7 @@
 
 #include "../../include/slm_engine.h"
 #include "grad_kernel.hpp"  // DPP reductions
+#include "light_ctl.hpp"
 
 namespace slm {
 
@@ -134,7 +135,21 @@ struct TailArgs {
   double* betas_out; // [total points][p]
   double* gn_out;    // [total points][G] or nullptr
   slm_point_info* infos;  // [total points]
+  // certified partial passes (light_kernels.hpp): the control block whose per-lane slack / epoch describe gprev -- the tail
+  // keeps them in step with the base gradient it stores (LightCtl) -- or nullptr; `light`: a light attempt stands in front of
+  // THIS launch's pass (LightCtl::ok then says whether it stood: the gradient is its hybrid one), 0: no attempt (ok is stale)
+  LightCtl* lt = nullptr;
+  int light = 0;
 };
+
+// The base gradient of lane `lane` has just been stored from this launch's gradient: its slack / epoch follow it (see
+// LightCtl).  (One thread.)
+__device__ __forceinline__ void light_commit(const TailArgs& a, int lane) {
+  if (a.lt == nullptr || lane >= SLM_MAX_LANES) return;
+  const bool hybrid = a.light != 0 && a.lt->ok != 0;
+  a.lt->slack[lane] = hybrid ? a.lt->pend_slack[lane] : 0.0;
+  a.lt->epoch[lane] = hybrid ? a.lt->pend_epoch[lane] : 0;
+}
 
 __device__ __forceinline__ double soft(double v, double thr) {
   const double m = fabs(v) - thr;
@@ -391,6 +406,7 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
   double new_loss_base = ctl->loss_base;
   double new_t = t_old, new_L = L, new_ak = ak_old, new_Lhat = Lhat_old, new_pen_z = pen_z;
   bool did_restart = false, l_bad = false;
+  bool stored = true;  // gprev now holds this call's gradient (all but a rejected candidate)
 
   if (mode == 1) {
     // ================= spectral (BB) scheme =====================================================
@@ -474,6 +490,7 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
       new_have_base = 1;
       new_loss_base = loss_z;
     }
+    stored = accept;
     // base point and its gradient after the decision; (zprev, gprev) = (base, its gradient) stays a
     // consistent pair for the FISTA curvature guard should this lane fall back
     const double step = 1.0 / new_ak;
@@ -670,6 +687,7 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
 
   // ---- control block ----------------------------------------------------------------------------
   if (tid == 0) {
+    if (stored) light_commit(a, lane_id);
     ctl->zzero = 0;  // (z was just rewritten)
     ctl->total_iter = total_iter + 1;
     ctl->L = new_L;
@@ -862,6 +880,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
   //   mode 1: base = zprev[j], next = us[j] (the candidate; the base itself on the switch to FISTA: us holds it then)
   //   mode 0: base / next from us[j] (the proximal point) and beta[j], see below
   double mom = 0.0;
+  bool stored = true;  // gprev now holds this call's gradient (all but a rejected candidate)
 
   if (mode == 1) {
     double s[6] = {0, 0, 0, 0, 0, 0};
@@ -935,6 +954,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
       new_have_base = 1;
       new_loss_base = loss_z;
     }
+    stored = accept;
     const double step = 1.0 / new_ak;
     const bool fallback = !nonfinite && (new_rejects >= BB_REJECT_LIMIT || iter + 1 > BB_POINT_LIMIT);
     __syncthreads();  // (the image may still be read by the group sums above)
@@ -1099,6 +1119,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
 
   // ---- control block (as in fista_tail_kernel) ---------------------------------------------------
   if (tid == 0) {
+    if (stored) light_commit(a, lane_id);
     ctl->zzero = 0;
     ctl->total_iter = total_iter + 1;
     ctl->L = new_L;

@@ -463,7 +463,8 @@ class PathResult:
 
     ``n_iter``, ``status`` (SLM_OK or SLM_ERR_NOT_CONVERGED), ``resid``, ``beta_norm``, ``loss``, ``mode`` (1 = spectral
     steps, 0 = FISTA, 2 = the on-chip solver), ``kkt`` (KKT residual at exit), ``mu`` (strong-convexity estimate the point
-    was accepted with): arrays of n_points; ``L``: inverse step at the last point; ``converged``; and the statistics of the
+    was accepted with), ``L_points`` (inverse step of the step that produced the point): arrays of n_points; ``L``: inverse
+    step at the last point; ``converged``; and the statistics of the
     call, shared by its lanes: ``grad_launches``, ``grad_timed``, ``grad_ms_total``, ``wall_ms``, ``lipschitz_ms``,
     ``ws_builds`` (working sets selected from scratch; 0: refinement not used), ``ws_appends``, ``ws_refined``,
     ``ws_misses``, ``ws_columns`` (columns in the working set at the end), ``ws_inner_iters``, ``ws_direct_steps``,
@@ -486,6 +487,7 @@ class PathResult:
     kkt = property(lambda self: self._infos["kkt"].copy())
     mu = property(lambda self: self._infos["mu"].copy())
     L = property(lambda self: float(self._infos["L"][-1]))
+    L_points = property(lambda self: self._infos["L"].copy())  # inverse step of every point at exit (1 / s of its last step)
 
     @property
     def converged(self) -> bool:
