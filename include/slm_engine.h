@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SLM_ABI_VERSION 19
+#define SLM_ABI_VERSION 20
 
 typedef enum slm_status {
   SLM_OK = 0,
@@ -183,6 +183,23 @@ typedef struct slm_gradient_opts {
 } slm_gradient_opts;
 int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradient_opts* opts, double* g_out, double* loss_out,
                     int32_t reps, double* ms_out);
+
+/*
+ * Diagnostic: one gradient pass of n_lanes lanes, each with its OWN point, row weights and n_eff -- how the tests check the
+ * lane index math of every multi-lane gradient kernel.  For lane l, over the rows used (all, or the first n_rows > 0):
+ *   G_out[l] = X^T W_l (X Z[l] - y) / n_eff[l],   loss_out[l] = 1/(2 n_eff[l]) sum_i w_li (x_i . Z[l] - y_i)^2.
+ *   route 0: the fused one-read kernel of n_lanes lanes (1..6 by width; the two-pass pair for one lane beyond 10 240 columns);
+ *   route 1: the split pass (residuals from X, then X^T R for all lane slots); the column-major copy is built first;
+ *   route 2: the covariance route, G_out[l] = G_k z_l - c_k with k = cov_index[l] an entry of slm_dataset_covariance*
+ *            (its own n_eff; row_weights, n_eff and n_rows do not apply).
+ * Z, G_out: [n_lanes][p] (C-order, host); row_weights: [n_lanes][n] (NULL: the dataset's for every lane); n_eff: [n_lanes]
+ * (NULL: the dataset's n).  kernels_out (nullable): the residual and product kernels launched, ';'-separated, e.g.
+ * "rowdot_ring_kernel<8,1,5,3>;xtr_mfma_kernel".  SLM_ERR_UNSUPPORTED where the route has no kernel for this call: there
+ * is no fallback to another route.  No reference counterpart (tests only).
+ */
+int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lanes, const double* Z, const double* row_weights,
+                       const double* n_eff, const int32_t* cov_index, int64_t n_rows, double* G_out, double* loss_out,
+                       char* kernels_out, int32_t kernels_len);
 
 /*
  * Weighted squared error of m coefficient vectors, as many per pass over X as the fused kernel

@@ -94,17 +94,24 @@ struct GradKernel {
   int W, C, R, B;
   int D;  // 0: rows wait in VGPRs (grad_fused_kernel); > 0: LDS ring, D rows in flight (grad_ring_kernel)
   void (*fn)(GradArgs);
+  const char* name;  // the kernels launched (slm_gradient_lanes reports them)
 };
 struct SplitKernel {
   int W, C, B, D;
   void (*rowdot)(SplitArgs);
   void (*resid)(SplitArgs);
+  const char* rowdot_name;
+};
+// the residual and product kernels a gradient launch chose (slm_gradient_lanes; nullptr everywhere else)
+struct GradNames {
+  const char* resid = nullptr;
+  const char* product = nullptr;
 };
 static const int kMaxTailE = 64;  // the tail kernels cover p <= 1024 * 64
 static const int64_t kMaxChunks = 64 * 8 * 10;  // largest row the fused kernel covers (p <= 10240)
 const SplitKernel* pick_split_kernel(const slm_host::Knobs& kn, int64_t p2);
 int xtr_max_row_blocks(int cus, int64_t ld);
-int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, bool sample = false);
+int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, bool sample = false, const char** name = nullptr);
 const GradKernel* pick_grad_kernel(const slm_host::Knobs& kn, int64_t p2, int B);
 
 // ------------------------------------------------------------------------------------------------
@@ -352,16 +359,18 @@ struct LaneSetup {
 };
 LaneSetup default_lanes(slm_dataset* ds, int B);
 int enqueue_gradient(slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done, hipEvent_t ev_start, hipEvent_t ev_stop,
-                     int64_t n_rows = 0, const int* skip = nullptr);
+                     int64_t n_rows = 0, const int* skip = nullptr, GradNames* names = nullptr);
 int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done, const PathCtl* ctl, const WsArgs* wa,
-                           hipEvent_t ev_start, hipEvent_t ev_stop, int64_t n_rows = 0, bool unit_bracket = false, const int* skip = nullptr);
+                           hipEvent_t ev_start, hipEvent_t ev_stop, int64_t n_rows = 0, bool unit_bracket = false, const int* skip = nullptr,
+                           GradNames* names = nullptr);
 bool split_usable(const slm_host::Knobs& kn, slm_dataset* ds);
 int ensure_xt(const slm_host::Knobs& kn, slm_dataset* ds);
 int check_launch();
 // (engine_solve.hip, used by the solve loop of engine_path.hip)
-void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s);
+void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s,
+                  const char** name = nullptr);
 int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int* done, hipEvent_t ev_start, hipEvent_t ev_stop,
-                         const PathCtl* ctl = nullptr, const WsArgs* wa = nullptr);
+                         const PathCtl* ctl = nullptr, const WsArgs* wa = nullptr, GradNames* names = nullptr);
 void launch_tail(const TailArgs& ta, hipStream_t s);
 int64_t sketch_rows(int64_t n);
 int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows = 0);

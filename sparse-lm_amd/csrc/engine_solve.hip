@@ -6,8 +6,8 @@
 // ------------------------------------------------------------------------------------------------
 // gradient kernel table
 // ------------------------------------------------------------------------------------------------
-#define SLM_GK(W, C, R, B) {W, C, R, B, 0, grad_fused_kernel<W, C, R, B>}
-#define SLM_RK(W, C, B, D) {W, C, 1, B, D, grad_ring_kernel<W, C, B, D>}
+#define SLM_GK(W, C, R, B) {W, C, R, B, 0, grad_fused_kernel<W, C, R, B>, "grad_fused_kernel<" #W "," #C "," #R "," #B ">"}
+#define SLM_RK(W, C, B, D) {W, C, 1, B, D, grad_ring_kernel<W, C, B, D>, "grad_ring_kernel<" #W "," #C "," #B "," #D ">"}
 // LDS-ring variants, preferred where they exist (512-thread workgroups, rows of up to 5120 columns);
 // ordered by capacity within each lane count.
 static const GradKernel kGradRing[] = {
@@ -45,8 +45,9 @@ static const GradKernel kGradExtra[] = {
 };
 
 // Rows longer than the fused kernels cover: two-pass fallback (D = -1), one lane, any p.
-static const GradKernel kGradTwoPass = {8, 4, 2, 1, -1, nullptr};
 static const int kTwoPassC = 4;  // column tile of xtr_kernel: 512 * 4 chunks = 4096 columns
+static const GradKernel kGradTwoPass = {8, 4, 2, 1, -1, nullptr, "rowdot_kernel;xtr_kernel<4>"};
+static_assert(kTwoPassC == 4, "the name of kGradTwoPass");
 
 // Split pass (split_kernels.hpp) for working-set solves: sixteen lanes per read of X.  The table is for
 // rowdot_ring_kernel (rows of up to 5120 columns, D rows in flight as for the fused ring kernel); rows of
@@ -54,13 +55,14 @@ static const int kTwoPassC = 4;  // column tile of xtr_kernel: 512 * 4 chunks = 
 // fit -- and take every residual that needs X from rowdot_mfma_kernel, which has no column limit but needs
 // the column-major copy of X (`rowdot == nullptr`: the split pass is then only used when that copy exists).
 #define SLM_SK(C, D)                                                                                   \
-  {8, C, SPLIT_LANES, D, rowdot_ring_kernel<8, C, ROWDOT_LANES, D>, resid_ws_kernel<SPLIT_LANES>}
+  {8, C, SPLIT_LANES, D, rowdot_ring_kernel<8, C, ROWDOT_LANES, D>, resid_ws_kernel<SPLIT_LANES>, "rowdot_ring_kernel<8," #C ",5," #D ">"}
+static_assert(ROWDOT_LANES == 5, "the names of kSplit");
 static const SplitKernel kSplit[] = {SLM_SK(1, 3), SLM_SK(2, 3), SLM_SK(3, 3), SLM_SK(4, 3), SLM_SK(5, 2)};
 // Rows beyond 5120 columns, ANY width (round 6; until then the table stopped at 10 240 columns and wider rows had one lane on
 // the two-pass kernels, at most half of the roofline by construction): nothing in the split pass depends on the row length --
 // X^T R walks column blocks of 512, the residuals from X contract the column-major copy group by group, the working set's
 // kernels see its <= 512 columns -- so sixteen lanes and the working set serve p = 20 000 or 40 000 like 5 000.
-static const SplitKernel kSplitAnyWidth = {8, 0, SPLIT_LANES, 0, nullptr, resid_ws_kernel<SPLIT_LANES>};
+static const SplitKernel kSplitAnyWidth = {8, 0, SPLIT_LANES, 0, nullptr, resid_ws_kernel<SPLIT_LANES>, nullptr};
 const SplitKernel* pick_split_kernel(const slm_host::Knobs& kn, int64_t p2) {
   if (!kn.split) return nullptr;
   for (const auto& k : kSplit)
@@ -77,7 +79,7 @@ int xtr_max_row_blocks(int cus, int64_t ld) {  // (sizes the partial buffer: the
   return slm_host::xtr_row_blocks_most(cus, ld, XTR_CB);
 }
 // sets a.xrows; returns the number of row blocks (= blocks of `partial` to reduce)
-int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, bool sample) {
+int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, bool sample, const char** name) {
   double per_cu = kn.xtr_wgs_per_cu;  // (SLM_XTR_WGS_PER_CU, A/B runs: workgroups per CU, up to 2)
   const bool wide = a.lane_slots > SPLIT_LANES;  // thirty-two lanes: both planes of R per row of X
   if (wide) per_cu = 1.0;                        // (its partial sums fill the buffer at one workgroup per CU)
@@ -87,30 +89,33 @@ int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, 
   // seventeen to twenty lanes: the lanes beyond sixteen on the vector units beside the sixteen on the matrix cores
   // (xtr18 / xtr20_mfma_kernel: the price of sixteen)
   const int extra = wide ? a.n_lanes - SPLIT_LANES : 0;
+  const char* nm;
   if (wide && extra >= 1 && extra <= 2) {
-    if (sample) hipLaunchKernelGGL(xtr18_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL(xtr18_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
+    if (sample) { hipLaunchKernelGGL(xtr18_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr18_sample_kernel"; }
+    else { hipLaunchKernelGGL(xtr18_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr18_mfma_kernel"; }
   } else if (wide && extra >= 3 && extra <= 4) {
-    if (sample) hipLaunchKernelGGL(xtr20_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL(xtr20_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
+    if (sample) { hipLaunchKernelGGL(xtr20_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr20_sample_kernel"; }
+    else { hipLaunchKernelGGL(xtr20_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr20_mfma_kernel"; }
   } else if (wide) {
-    if (sample) hipLaunchKernelGGL(xtr32_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL(xtr32_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
+    if (sample) { hipLaunchKernelGGL(xtr32_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr32_sample_kernel"; }
+    else { hipLaunchKernelGGL(xtr32_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr32_mfma_kernel"; }
   } else {
-    if (sample) hipLaunchKernelGGL(xtr_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL(xtr_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a);
+    if (sample) { hipLaunchKernelGGL(xtr_sample_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr_sample_kernel"; }
+    else { hipLaunchKernelGGL(xtr_mfma_kernel, dim3(xb, yb), dim3(XTR_WAVES * 64), 0, s, a); nm = "xtr_mfma_kernel"; }
   }
+  if (name) *name = nm;
   return yb;
 }
 
 // the product of a covariance pass (cov_gz_mfma_kernel): xtr_mfma_kernel's grid; when only the working set's rows are read a
 // workgroup row takes the next multiple of four of WS_KCAP / row blocks list entries (at most 32: eight steps in registers)
-static int launch_cov_gz(int cus, SplitArgs& a, hipStream_t s, const CovBatch& cb, int n_sets) {
+static int launch_cov_gz(int cus, SplitArgs& a, hipStream_t s, const CovBatch& cb, int n_sets, const char** name) {
   const slm_host::XtrGrid g = slm_host::xtr_grid(a.n, a.ld, XTR_CB, xtr_max_row_blocks(cus, a.ld) / 2);
   const int xb = g.xb, yb = g.yb;
   a.xrows = g.rows;
   const int per = ((WS_KCAP + yb - 1) / yb + 3) / 4 * 4;
   a.xrows_ws = (a.ctl != nullptr && per <= 32) ? per : 0;
+  if (name) *name = a.r_plane != 0 ? "cov_gz32_mfma_kernel" : "cov_gz_mfma_kernel";
   if (a.r_plane != 0) hipLaunchKernelGGL(cov_gz32_mfma_kernel, dim3(xb, yb, (unsigned)n_sets), dim3(XTR_WAVES * 64), 0, s, a, cb);  // (both halves)
   else hipLaunchKernelGGL(cov_gz_mfma_kernel, dim3(xb, yb, (unsigned)n_sets), dim3(XTR_WAVES * 64), 0, s, a, cb);
   return yb;
@@ -153,11 +158,12 @@ LaneSetup default_lanes(slm_dataset* ds, int B) {
 // grad -> reduce (-> all-reduce) for B lanes on ONE pass over X:
 // g_l = X^T W_l (X z_l - y) / n_eff_l in ds->g + l*(ld+16), loss_l in g_l[ld].
 int enqueue_gradient(slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done,
-                     hipEvent_t ev_start, hipEvent_t ev_stop, int64_t n_rows, const int* skip) {
+                     hipEvent_t ev_start, hipEvent_t ev_stop, int64_t n_rows, const int* skip, GradNames* names) {
   hipStream_t s = ds->eng->stream;
   const int B = ls.B;
   const GradKernel* gk = ds->gk[B - 1];
   if (!gk) return fail(SLM_ERR_UNSUPPORTED, "no %d-lane gradient kernel covers p = %lld", B, (long long)ds->p);
+  if (names) names->product = gk->name;
   const int nblk = ds->nblk[B - 1];
   GradArgs a;
   a.X = ds->X;
@@ -216,7 +222,8 @@ int enqueue_gradient(slm_dataset* ds, const LaneSetup& ls, const double* y, cons
 // the column-major copy on the matrix cores when that copy exists (working-set solves make it), otherwise
 // the vector kernel, five lanes per read of X (one window per grid row; a window returns at once unless
 // one of its lanes needs X) -- also the choice for calls of up to five lanes.  SLM_ROWDOT_RING=1/0 forces one.
-void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s) {
+void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s,
+                  const char** name) {
   // Measured at n = 100k, p = 5k (tools/rowdot_probe.py): matrix cores 0.75-0.80 ms whatever the lane count;
   // vector kernel 0.62 ms for one lane, 0.81 ms for five, 3.1 ms for sixteen (four reads of X).
   const int halves = (B + SPLIT_LANES - 1) / SPLIT_LANES;
@@ -228,12 +235,15 @@ void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel
     // (seventeen to twenty lanes: the lanes beyond sixteen on the vector units beside the matrix cores' sixteen -- rowdot18 /
     //  rowdot20_mfma_kernel, as for X^T R)
     const bool extras = halves == 2 && B <= SPLIT_LANES + 4;
-    if (extras && B <= SPLIT_LANES + 2) hipLaunchKernelGGL(rowdot18_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
-    else if (extras) hipLaunchKernelGGL(rowdot20_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
-    else if (halves == 2) hipLaunchKernelGGL(rowdot32_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL(rowdot_mfma_kernel, dim3(nblk, halves), dim3(XZ_WAVES * 64), 0, s, a);
+    const char* nm;
+    if (extras && B <= SPLIT_LANES + 2) { hipLaunchKernelGGL(rowdot18_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a); nm = "rowdot18_mfma_kernel"; }
+    else if (extras) { hipLaunchKernelGGL(rowdot20_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a); nm = "rowdot20_mfma_kernel"; }
+    else if (halves == 2) { hipLaunchKernelGGL(rowdot32_mfma_kernel, dim3(nblk, 1), dim3(XZ_WAVES * 64), 0, s, a); nm = "rowdot32_mfma_kernel"; }
+    else { hipLaunchKernelGGL(rowdot_mfma_kernel, dim3(nblk, halves), dim3(XZ_WAVES * 64), 0, s, a); nm = "rowdot_mfma_kernel"; }
+    if (name) *name = nm;
   } else if (sk->rowdot != nullptr) {
     hipLaunchKernelGGL(sk->rowdot, dim3(nblk, (B + ROWDOT_LANES - 1) / ROWDOT_LANES), dim3(sk->W * 64), 0, s, a);
+    if (name) *name = sk->rowdot_name;
   }
   // (no ring variant and no column-major copy: split_usable() keeps such datasets off the split pass)
 }
@@ -248,7 +258,7 @@ bool split_usable(const slm_host::Knobs& kn, slm_dataset* ds) {
 
 int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls, const double* y, const int* done,
                            const PathCtl* ctl, const WsArgs* wa, hipEvent_t ev_start,
-                           hipEvent_t ev_stop, int64_t n_rows, bool unit_bracket, const int* skip) {
+                           hipEvent_t ev_stop, int64_t n_rows, bool unit_bracket, const int* skip, GradNames* names) {
   hipStream_t s = ds->eng->stream;
   const SplitKernel* sk = ds->sk;
   const int nblk = ds->split_nblk;
@@ -272,7 +282,7 @@ int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const Lan
   //  the stream over X alone: bench.py's roofline.gradient_unit_frac)
   const bool unit = ev_start != nullptr && unit_bracket;
   if (unit) HIP_TRY(hipEventRecord(ev_start, s));
-  launch_rowdot(kn, ds, sk, nblk, ls.B, a, s);
+  launch_rowdot(kn, ds, sk, nblk, ls.B, a, s, names ? &names->resid : nullptr);
   if (wa && ctl) {  // residuals from the gathered columns: matrix cores (SLM_RESID_VEC=1: a row per thread)
     if (kn.resid_vec && halves == 1) hipLaunchKernelGGL(sk->resid, dim3(nblk), dim3(256), 0, s, a);
     else if (halves == 2) hipLaunchKernelGGL(resid32_mfma_kernel, dim3(nblk, 1), dim3(RM_WAVES * 64), 0, s, a);  // (both halves on one read of the gathered columns)
@@ -280,7 +290,8 @@ int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const Lan
   }
   // (SLM_FLAG_PROFILE brackets the kernel that streams X, the one the roofline is quoted on)
   if (ev_start && !unit) HIP_TRY(hipEventRecord(ev_start, s));
-  const int xblk = launch_xtr(kn, ds->eng->cus, a, s, n_rows > 0 && ctl != nullptr);  // (rows of a sample start: solve_core)
+  const int xblk = launch_xtr(kn, ds->eng->cus, a, s, n_rows > 0 && ctl != nullptr,  // (rows of a sample start: solve_core)
+                              names ? &names->product : nullptr);
   if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, s));
   ReduceArgs ra;
   ra.partial = ds->partial;
@@ -306,7 +317,7 @@ int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const Lan
 // The gradient of one pass from the Grams of the lanes' row sets (cov_kernels.hpp): g_l = G_s z_l - c_s, loss in g_l[ld].
 // `entry_of[l]`: the lane's entry of ds->cov.  One read of a 8 ld^2-byte Gram per row set of the call instead of X.
 int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int* done, hipEvent_t ev_start,
-                         hipEvent_t ev_stop, const PathCtl* ctl, const WsArgs* wa) {
+                         hipEvent_t ev_stop, const PathCtl* ctl, const WsArgs* wa, GradNames* names) {
   hipStream_t s = ds->eng->stream;
   const int64_t ld = ds->ld;
   const int halves = (B + SPLIT_LANES - 1) / SPLIT_LANES;  // (more than sixteen lanes: a plane of Z, a block of partial sums and a launch per half)
@@ -352,7 +363,7 @@ int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int*
   // (more than sixteen lanes: both planes of Z against ONE read of every Gram -- cov_gz32_mfma_kernel)
   a.lane0 = 0;
   a.r_plane = halves > 1 ? ld * SPLIT_RSTRIDE : 0;
-  const int xblk = launch_cov_gz(ds->eng->cus, a, s, cb, n_sets);
+  const int xblk = launch_cov_gz(ds->eng->cus, a, s, cb, n_sets, names ? &names->product : nullptr);
   CovFinishArgs f;
   f.partial = partial; f.z = ds->z; f.g = ds->g; f.done = done; f.nblk = xblk; f.ld = ld;
   hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)(ld / 16), (unsigned)B), dim3(256), 0, s, f, cb);
@@ -635,6 +646,80 @@ extern "C" int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradi
 
 extern "C" int slm_gradient(slm_dataset* ds, const double* z, double* g_out, double* loss_out, int32_t reps, double* ms_out) {
   return slm_gradient_ex(ds, z, nullptr, g_out, loss_out, reps, ms_out);
+}
+
+// Diagnostic: one gradient pass of n_lanes lanes, each with its own point, row weights and n_eff, through a NAMED route and
+// nothing else -- where the route has no kernel for this call the answer is SLM_ERR_UNSUPPORTED, never another route.
+extern "C" int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lanes, const double* Z, const double* row_weights,
+                                  const double* n_eff, const int32_t* cov_index, int64_t n_rows, double* G_out, double* loss_out,
+                                  char* kernels_out, int32_t kernels_len) {
+  if (!ds || !Z || !G_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  if (route < 0 || route > 2) return fail(SLM_ERR_BAD_ARG, "route must be 0 (fused), 1 (split pass) or 2 (covariance), got %d", route);
+  if (n_lanes < 1 || n_lanes > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "between 1 and %d lanes, got %d", kMaxLanes, n_lanes);
+  if (n_rows < 0 || n_rows > ds->n) return fail(SLM_ERR_BAD_ARG, "n_rows = %lld outside [0, %lld]", (long long)n_rows, (long long)ds->n);
+  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "slm_gradient_lanes: row-sharded datasets");
+  if (n_lanes > ds->lane_cap) return fail(SLM_ERR_UNSUPPORTED, "%d lanes: the dataset holds %d", n_lanes, ds->lane_cap);
+  const int B = n_lanes;
+  const int64_t n = ds->n, p = ds->p, ld = ds->ld;
+  for (int64_t k = 0; k < (int64_t)B * p; ++k)
+    if (!std::isfinite(Z[k])) return fail(SLM_ERR_BAD_ARG, "Z contains a non-finite value");
+  if (row_weights)
+    for (int64_t k = 0; k < (int64_t)B * n; ++k)
+      if (!(row_weights[k] >= 0.0) || !std::isfinite(row_weights[k]))
+        return fail(SLM_ERR_BAD_ARG, "row_weights[%lld] is negative or not finite", (long long)k);
+  if (n_eff)
+    for (int l = 0; l < B; ++l)
+      if (!(n_eff[l] > 0.0) || !std::isfinite(n_eff[l])) return fail(SLM_ERR_BAD_ARG, "n_eff[%d] must be positive and finite", l);
+  if (route == 2) {
+    if (row_weights || n_rows > 0) return fail(SLM_ERR_UNSUPPORTED, "route 2 takes its rows from the covariance entries: no row_weights or n_rows");
+    if (ds->cov.empty()) return fail(SLM_ERR_UNSUPPORTED, "route 2: the dataset has no covariance entries");
+    if (!cov_index) return fail(SLM_ERR_BAD_ARG, "route 2 needs cov_index");
+    for (int l = 0; l < B; ++l)
+      if (cov_index[l] < 0 || cov_index[l] >= (int32_t)ds->cov.size())
+        return fail(SLM_ERR_BAD_ARG, "cov_index[%d] = %d: the dataset has %d entries", l, cov_index[l], (int)ds->cov.size());
+  }
+  const slm_host::Knobs kn = knobs();
+  HIP_TRY(hipSetDevice(ds->eng->device));
+  hipStream_t s = ds->eng->stream;
+  if (route == 0 && !ds->gk[B - 1]) return fail(SLM_ERR_UNSUPPORTED, "route 0: no %d-lane kernel covers p = %lld", B, (long long)p);
+  if (route == 1) {
+    if (!ds->sk) return fail(SLM_ERR_UNSUPPORTED, "route 1: no split pass for p = %lld", (long long)p);
+    SLM_TRY(ensure_xt(kn, ds));  // (the copy every kernel choice of launch_rowdot may take: what slm_gradient_ex does)
+    if (!split_usable(kn, ds) || (B > SPLIT_LANES && !(ds->XT && ds->XT_ready)))
+      return fail(SLM_ERR_UNSUPPORTED, "route 1: no residual kernel for %d lanes at p = %lld without the column-major copy", B, (long long)p);
+  }
+  // the lanes' points, zero beyond p and in the unused lane slots of the call
+  const int slots = route == 0 ? B : SPLIT_LANES * ((B + SPLIT_LANES - 1) / SPLIT_LANES);
+  HIP_TRY(hipMemsetAsync(ds->z, 0, sizeof(double) * (size_t)slots * ld, s));
+  HIP_TRY(hipMemcpy2DAsync(ds->z, sizeof(double) * ld, Z, sizeof(double) * p, sizeof(double) * p, B, hipMemcpyHostToDevice, s));
+  LaneSetup ls = default_lanes(ds, B);
+  if (row_weights) {
+    if (!ds->rw_lanes) SLM_TRY(dalloc(&ds->rw_lanes, (size_t)ds->lane_cap * n));
+    HIP_TRY(hipMemcpyAsync(ds->rw_lanes, row_weights, sizeof(double) * (size_t)B * n, hipMemcpyHostToDevice, s));
+    ls.rw = ds->rw_lanes;
+    ls.rw_stride = n;
+  }
+  if (n_eff)
+    for (int l = 0; l < B; ++l) ls.n_eff[l] = n_eff[l];
+  GradNames names;
+  if (route == 0) {
+    SLM_TRY(enqueue_gradient(ds, ls, ds->y, nullptr, nullptr, nullptr, n_rows, nullptr, &names));
+  } else if (route == 1) {
+    SLM_TRY(enqueue_gradient_split(kn, ds, ls, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr, n_rows, false, nullptr, &names));
+  } else {
+    if (!ds->cov_Z) SLM_TRY(dalloc(&ds->cov_Z, (size_t)ld * SPLIT_RSTRIDE * SPLIT_HALVES));
+    SLM_TRY(enqueue_gradient_cov(ds, B, cov_index, nullptr, nullptr, nullptr, nullptr, nullptr, &names));
+  }
+  SLM_TRY(check_launch());
+  HIP_TRY(hipStreamSynchronize(s));
+  const size_t lane_bytes = sizeof(double) * (size_t)(ld + 16);
+  HIP_TRY(hipMemcpy2D(G_out, sizeof(double) * p, ds->g, lane_bytes, sizeof(double) * p, B, hipMemcpyDeviceToHost));
+  if (loss_out) HIP_TRY(hipMemcpy2D(loss_out, sizeof(double), ds->g + ld, lane_bytes, sizeof(double), B, hipMemcpyDeviceToHost));
+  if (kernels_out && kernels_len > 0) {
+    if (names.resid && names.product) snprintf(kernels_out, (size_t)kernels_len, "%s;%s", names.resid, names.product);
+    else snprintf(kernels_out, (size_t)kernels_len, "%s", names.resid ? names.resid : names.product ? names.product : "");
+  }
+  return SLM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -45,7 +45,7 @@ FLAG_PROFILE_UNIT = 1024  # with FLAG_PROFILE: the event bracket spans residuals
 FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plain steps, no rounds on the model Gram (csrc/mg_kernels.hpp)
 
 COMM_ID_BYTES = 128
-ABI_VERSION = 19  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
+ABI_VERSION = 20  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -76,6 +76,7 @@ ABI_SYMBOLS = (
     "slm_dataset_path_lanes",
     "slm_gradient",
     "slm_gradient_ex",
+    "slm_gradient_lanes",
     "slm_eval_sse",
     "slm_eval_sse_sparse",
     "slm_dense_spd_solve",
@@ -284,6 +285,7 @@ def load_library():
             "slm_dataset_path_lanes": [vp, i32, C.c_uint32, P(i32)],
             "slm_gradient": [vp, vp, vp, P(dbl), i32, P(dbl)],
             "slm_gradient_ex": [vp, vp, P(_GradientOpts), vp, P(dbl), i32, P(dbl)],
+            "slm_gradient_lanes": [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, C.c_char_p, i32],
             "slm_reload_knobs": [],
             "slm_eval_sse": [vp, vp, i32, vp, vp],
             "slm_eval_sse_sparse": [vp, vp, i32, vp, i32, vp, vp],
@@ -778,6 +780,28 @@ class Dataset:
             _check(self._lib.slm_gradient_ex(self._h, _ptr(zz), C.byref(o), _ptr(g), C.byref(loss), int(reps),
                                              C.byref(ms) if reps > 0 else None))
         return (g, loss.value, ms.value) if reps > 0 else (g, loss.value)
+
+    def gradient_lanes(self, Z, row_weights=None, n_eff=None, route: int = 0, cov_index=None, n_rows: int = 0):
+        """``slm_gradient_lanes``: one gradient pass of ``len(Z)`` lanes through route 0 (fused), 1 (split pass) or 2
+        (covariance entries ``cov_index``), each lane with its own point ``Z[l]``, row weights ``row_weights[l]`` and
+        ``n_eff[l]``; ``n_rows`` > 0: only the first rows.  Returns ``(G, loss, kernels)``: (lanes, p), (lanes,) and the
+        names of the kernels launched.  A route without a kernel for the call raises NotImplementedError."""
+        _sync_knobs()
+        Z = _f64(np.atleast_2d(Z), "Z")
+        B = Z.shape[0]
+        if Z.shape[1] != self.p:
+            raise ValueError(f"Z must have {self.p} columns")
+        rw = None if row_weights is None else _f64(row_weights, "row_weights", (B, self.n))
+        ne = None if n_eff is None else _f64(n_eff, "n_eff", (B,))
+        ci = None if cov_index is None else np.ascontiguousarray(cov_index, dtype=np.int32)
+        if ci is not None and ci.shape != (B,):
+            raise ValueError(f"cov_index has shape {ci.shape}, expected {(B,)}")
+        G = np.empty((B, self.p))
+        loss = np.empty(B)
+        names = C.create_string_buffer(512)
+        _check(self._lib.slm_gradient_lanes(self._h, int(route), B, _ptr(Z), _ptr(rw), _ptr(ne), _ptr(ci), int(n_rows),
+                                            _ptr(G), _ptr(loss), names, len(names)))
+        return G, loss, names.value.decode()
 
     def eval_sse(self, Z, row_weight=None, sparse=None) -> np.ndarray:
         """sum_i w_i (x_i . Z[k] - y_i)^2 for every row Z[k] of ``Z`` (m, p); ``row_weight`` is e.g. the
