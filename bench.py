@@ -22,17 +22,23 @@ of the timings and the per-rank device report.
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline     -- achieved HBM GB/s of the kernel that streams X, from HIP events recorded on the
                   engine's own stream inside the timed region, against the 8 TB/s peak;
+  ranks        -- rank -> device of every rank and the imbalance (slowest rank / mean rank).
+
+A plain run stops there: set-up, warm-up, the timed steps, the dump of `--dump-outputs`, the line.  ``--full`` adds,
+after the timed region and never part of `value`:
+  roofline     -- the whole gradient unit of the split pass (two more paths under one bracket of HIP events per pass,
+                  `gradient_unit_*`, then `frac`) and the read-stream ceiling of the device (`read_stream_ceiling_*`);
   cpu_baseline -- the oracle's C twin (OpenMP, as many threads as the cgroup grants CPUs) timed on a bounded prefix of the same
-                  path on rank 0 at N = 1 (a reported baseline, not the target);
-  ranks        -- rank -> device of every rank and the imbalance (slowest rank / mean rank);
-  extra_legs   -- measured AFTER the timed region, never part of `value`:
+                  path on rank 0 at N = 1 (a reported baseline, not the target; `--cpu-budget 0` skips it);
+  extra_legs   -- the legs below; `strong_scaling`, `value_mean_over_draws` and all of `summary` but its last
+                  figure are drawn from them:
                   "config4_grid": BASELINE config 4 (SparseGroupLasso, 5 folds x 10 l1_ratio x 50 alpha =
                   2500 fits) with its 50 (fold, l1_ratio) units dealt to the ranks (strong scaling);
                   "rowshard": BASELINE config 5's shape (AdaptiveGroupLasso, 3 re-weighting solves,
                   125 000 rows x 10 000 columns PER RANK) through the engine's RCCL communicator over all
                   ranks (weak scaling in rows; one all-reduce of the gradients per pass);
-                  "concurrent_paths": the headline path on three engines of one GPU at once (per rank).
-                  `--no-extra` skips them.
+                  "concurrent_paths": the headline path on three engines of one GPU at once (per rank);
+                  and more (`main` lists them all).  `--no-extra` skips them, `--legs` picks some.
 
 ``--dump-outputs DIR``: after the timed steps, rank 0 writes what its last step returned (`path_outputs`) as
 DIR/<name>.npy in float64, at most 64 MB in all.  The dataset and the path are seeded, so two builds run with the same
@@ -1082,7 +1088,7 @@ def strong_scaling_object(c4_s, c4_cov_s, world):
     }
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -1094,17 +1100,24 @@ def main():
     ap.add_argument("--lanes", type=int, default=0, help="lanes of the path advancing together on one pass over X (0: the engine's choice, "
                     "slm_solve_path_lanes with n_lanes = 0 -- eighteen for 50 points: three passes instead of four)")
     ap.add_argument("--no-ws", action="store_true", help="disable the working-set refinement (A/B runs)")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work (0 = skip)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config-4 grid and row-sharded legs")
-    ap.add_argument("--legs", default="", help="comma-separated names of the extra legs to run (default: all)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the headline does not need: "
+                    "the roofline's gradient unit and read ceiling, the CPU baseline and the extra legs")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="with --full: seconds of CPU baseline work (0 = skip)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra legs")
+    ap.add_argument("--legs", default="", help="with --full: comma-separated names of the extra legs to run (default: all)")
     ap.add_argument("--extra-timeout", type=float, default=360.0, help="hard limit (s) on the extra legs")
     ap.add_argument("--rowshard-rows", type=int, default=125_000, help="rows per rank of the row-sharded leg")
     ap.add_argument("--rowshard-cols", type=int, default=10_000)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (rank 0's path) as DIR/<name>.npy, float64")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -1222,21 +1235,22 @@ def main():
                     "xtr20_mfma_kernel" if lanes_used <= 20 else "xtr32_mfma_kernel")
         t_grad_ms = grad_ms / max(1, grad_timed)
         achieved = bytes_per_grad / (t_grad_ms * 1e-3) / 1e9 if t_grad_ms > 0 else 0.0
-        # after the timed region, same dataset, same run: (i) the whole gradient unit of the split pass under the same HIP
-        # events -- residuals of the sixteen lane slots (resid_mfma_kernel, and rowdot_mfma_kernel's empty launch) + X^T R --
-        # charged ONE W; (ii) the read-only stream ceiling of THIS device on THIS copy of X (plain 16-byte loads, summed up)
+        # --full, after the timed region, same dataset, same run: (i) the whole gradient unit of the split pass under the same
+        # HIP events -- residuals of the sixteen lane slots (resid_mfma_kernel, and rowdot_mfma_kernel's empty launch) + X^T R
+        # -- charged ONE W; (ii) the read-only stream ceiling of THIS device on THIS copy of X (plain 16-byte loads, summed up)
         unit_ms = ceiling_gbs = ceiling_ms = None
-        if split:
+        if split and args.full:
             u_ms, u_n = 0.0, 0
             for _ in range(2):
                 ru = ds.solve_path(points, tol=args.tol, flags=flags | _engine.FLAG_PROFILE_UNIT, lanes=args.lanes)
                 u_ms += ru.grad_ms_total
                 u_n += ru.grad_timed
             unit_ms = u_ms / max(1, u_n)
-        try:
-            ceiling_gbs, ceiling_ms = ds.read_ceiling(reps=5)
-        except Exception:  # noqa: BLE001 -- a measurement beside the line, never its condition
-            pass
+        if args.full:
+            try:
+                ceiling_gbs, ceiling_ms = ds.read_ceiling(reps=5)
+            except Exception:  # noqa: BLE001 -- a measurement beside the line, never its condition
+                pass
         unit_achieved = (bytes_per_grad / (unit_ms * 1e-3) / 1e9) if unit_ms else None
         secs = [r["seconds"] for r in per_rank]
         out = {
@@ -1290,7 +1304,9 @@ def main():
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
                 "frac": (unit_achieved if unit_achieved else achieved) / HBM_PEAK_GBS,
-                "frac_is": "gradient unit (residuals + X^T R)" if unit_achieved else "the kernel that streams X (no split pass: the fused kernel is the whole unit)",
+                "frac_is": ("gradient unit (residuals + X^T R)" if unit_achieved else
+                            "the kernel that streams X (the gradient unit is measured under --full)" if split and not args.full else
+                            "the kernel that streams X (no split pass: the fused kernel is the whole unit)"),
                 "kernel_achieved": achieved,
                 "kernel_frac": achieved / HBM_PEAK_GBS,
                 "traffic": measured_traffic(n, p, lanes_used, xtr_name if split else "grad_fused_kernel")[0],
@@ -1319,14 +1335,14 @@ def main():
                 },
             },
         }
-        if world == 1 and args.cpu_budget > 0:
+        if args.full and world == 1 and args.cpu_budget > 0:
             out["cpu_baseline"] = cpu_baseline(ds, alphas, res.L, args.tol, res.betas, args.cpu_budget)
         else:
             out["cpu_baseline"] = None
     ds.close()
 
-    # ---- extra legs: after the timed region, guarded by a hard limit ------------------------------------
-    if not args.no_extra:
+    # ---- extra legs (--full): after the timed region, guarded by a hard limit ----------------------------
+    if args.full and not args.no_extra:
         legs = {}
         if out is not None:
             out["extra_legs"] = legs

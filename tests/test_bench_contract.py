@@ -1,5 +1,6 @@
 """Host-side pieces of bench.py that need no GPU: the CPU share the CPU legs are sized to, the argument defaults of the
-contract (`python bench.py` alone = one GPU, a few steps), the synthetic coefficient law."""
+contract (`python bench.py` alone = one GPU, a few steps, nothing beside the headline without `--full`), the synthetic
+coefficient law."""
 
 import importlib.util
 import os
@@ -44,6 +45,15 @@ def test_defaults_of_the_contract():
     coef = bench.make_coef(5000, 50, seed=0)
     assert coef.shape == (5000,) and np.count_nonzero(coef) == 50
     np.testing.assert_array_equal(coef, bench.make_coef(5000, 50, seed=0))
+
+
+def test_a_plain_run_leaves_everything_beside_the_headline_to_full():
+    bench = _bench()
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert not plain.full and (plain.gpus, plain.steps, plain.warmup) == (1, 3, 2)
+    assert bench.parse_args([]).full is False
+    full = bench.parse_args(["--full", "--legs", "soak,config3_path", "--cpu-budget", "0"])
+    assert full.full and full.legs == "soak,config3_path" and full.cpu_budget == 0.0
 
 
 def test_strong_scaling_object_and_cpu_baseline_layout():

@@ -2,7 +2,7 @@
 makes two or three engines of this process the ranks of one job, each driven by its own host thread, so the
 multi-rank state machine of csrc/engine.hip -- gradient all-reduce, rank-agreed stop word, Gram exchange of
 the working set, sharded centring -- runs for real where RCCL cannot form a group (it refuses several ranks
-on one device).  The RCCL leg itself is measured by `bench.py --gpus N` (extra_legs.rowshard).
+on one device).  The RCCL leg itself is measured by `bench.py --full --gpus N` (extra_legs.rowshard).
 
 Reference semantics being reproduced: one `_solve` on the whole (X, y) (src/sparselm/model/_base.py:512-519)
 and `_preprocess_data` centring on the whole matrix (:216-222); the reference has no distributed code.

@@ -1,12 +1,13 @@
 #!/bin/bash
-# A/B of environment settings on the bench's other legs: usage legs_ab.sh "SLM_X=1" "SLM_Y=2 SLM_Z=3" ...  ("" = defaults)
+# A/B of environment settings on the bench's other legs: usage legs_ab.sh OUTDIR "SLM_X=1" "SLM_Y=2 SLM_Z=3" ...  ("" = defaults)
+O=$1; shift; mkdir -p $O
 L=soak,config3_path,config4_grid,config4_grid_dense_regime,rowshard,literal_config2
 i=0
 for s in "$@"; do
   i=$((i+1))
-  env $s python bench.py --cpu-budget 0 --legs $L > gpurun_out/legs_$i.log 2>gpurun_out/legs_$i.err
+  env $s python bench.py --full --cpu-budget 0 --legs $L > $O/legs_$i.log 2>$O/legs_$i.err
   echo "== [$s]"
-  python tools/show_legs.py gpurun_out/legs_$i.log | python -c "
+  python tools/show_legs.py $O/legs_$i.log | python -c "
 import sys,json
 for line in sys.stdin:
     k,_,v=line.partition(' ')
