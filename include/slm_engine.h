@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SLM_ABI_VERSION 20
+#define SLM_ABI_VERSION 21
 
 typedef enum slm_status {
   SLM_OK = 0,
@@ -457,6 +457,27 @@ int slm_solve_path_lanes(slm_dataset* ds, const slm_penalty* pen, const slm_path
 int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, const double* b, const slm_solve_opts* opts,
                                double tol_inner, int32_t max_sweeps, const double* beta0, int32_t warm,
                                double* beta_out, double* group_norms_out, slm_point_info* info);
+
+/*
+ * Linear constraints lo <= A b <= hi on the l1 estimators (the reference's add_constraints, src/sparselm/model/_base.py:
+ * 469-510; Lasso, AdaptiveLasso, OrdinaryLeastSquares with a = 0):
+ *   minimise 1/(2n)||X b - y||^2 + sum_j a[j] |b_j|   subject to   lo <= A b <= hi
+ * by an over-relaxed ADMM splitting with ALL sweeps in one launch (small_constrained_kernels.hpp).  A: m x p, row-major,
+ * finite; lo / hi: m entries each, lo <= hi (equalities lo == hi; +-infinity allowed).  The on-chip solver takes
+ * p <= 128, n * ld <= 131072, m <= 512, unweighted and unsharded datasets with singleton groups; anything else is
+ * SLM_ERR_UNSUPPORTED and the caller runs the sweeps itself (sparselm_amd/model/_constrained.py).  A non-finite entry of
+ * A or a row with lo > hi is SLM_ERR_BAD_ARG before anything is launched.  Stops when the primal residual ||A b - s|| and
+ * the dual residual rho ||A^T (s - s_prev)|| are below opts->tol relative to their scales; the b-steps are solved to
+ * tol_inner (<= 0: min(tol, 1e-10)).  max_sweeps <= 0: 500.  warm != 0 continues from the splitting variables (s, u, rho)
+ * of the previous call on this dataset with the same m (the re-weighting rounds of AdaptiveLasso) instead of starting
+ * from beta0.  lambda_out (m entries, may be NULL): the multipliers, 0 in grad f + d penalty + A^T lambda, > 0 only where
+ * hi binds and < 0 only where lo binds.  info->n_iter = sweeps, info->rejects = matrix-vector products, info->kkt /
+ * info->mu = primal / dual residual, info->L = rho at exit, info->loss = 1/(2n)||X b - y||^2, info->status = SLM_OK or
+ * SLM_ERR_NOT_CONVERGED (outputs are the last iterate).
+ */
+int slm_solve_constrained(slm_dataset* ds, const double* a, const double* A, int32_t m, const double* lo, const double* hi,
+                          const slm_solve_opts* opts, double tol_inner, int32_t max_sweeps, const double* beta0, int32_t warm,
+                          double* beta_out, double* lambda_out, slm_point_info* info);
 
 /*
  * The Gram of a row set, for covariance passes (SLM_FLAG_COVARIANCE): G = X^T W X / n_eff, c = X^T W y / n_eff and

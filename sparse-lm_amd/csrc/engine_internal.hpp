@@ -31,6 +31,7 @@
 #include "light_kernels.hpp"
 #include "small_kernels.hpp"
 #include "small_split_kernels.hpp"
+#include "small_constrained_kernels.hpp"
 #include "cov_kernels.hpp"
 #include "mg_kernels.hpp"
 
@@ -257,6 +258,9 @@ struct slm_dataset {
   double* cov_fp = nullptr;   // [2 * kMaxLanes + 2] fingerprints / scalars on their way to the host
   double* split_state = nullptr;  // [3 ld + 2 + record] slm_solve_standardized_sgl: gamma, u, rho, valid; outputs
   double* h_split = nullptr;      // its page-locked staging: a, b, warm start in; coefficients, group norms, record out
+  double* cons_state = nullptr;   // [SC_STATE] slm_solve_constrained: s, u, rho, valid, m -- what a warm call continues from
+  double* cons_buf = nullptr;     // its inputs and outputs: a, beta0, A, A^T, A^T A, lo, hi; beta, lambda, record
+  size_t cons_buf_doubles = 0;
   double* stop_words = nullptr;  // [STOP_WORDS] row-sharded mode: the vector the ranks all-reduce after every pass
   double* XT = nullptr;  // column-major copy of X in tiles of 32 rows (tile_columns_kernel), built on first use
   bool XT_ready = false, XT_failed = false;

@@ -1056,6 +1056,114 @@ extern "C" int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// linear constraints lo <= A b <= hi on the l1 estimators: the splitting on chip (small_constrained_kernels.hpp)
+// ------------------------------------------------------------------------------------------------
+extern "C" int slm_solve_constrained(slm_dataset* ds, const double* a, const double* A, int32_t m, const double* lo,
+                                     const double* hi, const slm_solve_opts* opts, double tol_inner, int32_t max_sweeps,
+                                     const double* beta0, int32_t warm, double* beta_out, double* lambda_out,
+                                     slm_point_info* info) {
+  if (!ds || !a || !A || !lo || !hi || !beta_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  if (m < 1) return fail(SLM_ERR_BAD_ARG, "m must be >= 1 (got %d)", m);
+  const int p = (int)ds->p;
+  const int64_t ld = ds->ld;
+  // the arguments are checked before anything touches the device
+  for (int64_t e = 0; e < (int64_t)m * p; ++e)
+    if (!std::isfinite(A[e])) return fail(SLM_ERR_BAD_ARG, "A contains a non-finite value at (%lld, %lld)", (long long)(e / p), (long long)(e % p));
+  for (int r = 0; r < m; ++r)
+    if (!(lo[r] <= hi[r])) return fail(SLM_ERR_BAD_ARG, "row %d: lo > hi (or NaN)", r);
+  for (int j = 0; j < p; ++j)
+    if (!(a[j] >= 0.0) || !std::isfinite(a[j])) return fail(SLM_ERR_BAD_ARG, "a[%d] must be finite and >= 0", j);
+  const slm_host::Knobs kn = knobs();
+  if (!kn.on_chip) return fail(SLM_ERR_UNSUPPORTED, "the on-chip solvers are switched off (SLM_ON_CHIP=0)");
+  if (m > SC_MMAX) return fail(SLM_ERR_UNSUPPORTED, "the constrained splitting runs on chip for up to %d constraint rows (got %d)", SC_MMAX, m);
+  if (row_sharded(ds) || ds->rw || !ds->singleton || p > SM_PMAX || (double)ds->n * (double)ld > 131072.0)
+    return fail(SLM_ERR_UNSUPPORTED, "the constrained splitting runs on chip for unweighted, unsharded problems with singleton groups, "
+                "p <= %d and n * ld <= 131072", SM_PMAX);
+  // LDS: Gram matrix, three vectors, the staged constraint vector; what is left stages the rows of the build and then
+  // holds the partial products of three wavefronts and the head of the b-step's direct solves
+  const size_t fixed = sizeof(double) * ((size_t)p * p + 3 * (size_t)p + (size_t)SC_MMAX);
+  const size_t lds = (size_t)SM_LDS_BYTES;
+  const int64_t stage = fixed + 64 < lds ? (int64_t)((lds - fixed - 64) / sizeof(double)) : 0;
+  const int ps = 4 * ((p + 4) / 4);
+  if (stage < 3 * (int64_t)p + 640 || stage < 4 * (int64_t)ps)
+    return fail(SLM_ERR_UNSUPPORTED, "no room in LDS at p = %d", p);
+  slm_engine* eng = ds->eng;
+  HIP_TRY(hipSetDevice(eng->device));
+  hipStream_t s = eng->stream;
+  // one block: in  a [p] | beta0 [p] | A [m p] | A^T [p m] | K [p p] | lo [m] | hi [m]
+  //            out beta [p] | lambda [m] | record
+  const size_t rec_doubles = (sizeof(slm_point_info) + 7) / 8;
+  const size_t n_in = 2 * (size_t)p + 2 * (size_t)m * p + (size_t)p * p + 2 * (size_t)m;
+  const size_t n_out = (size_t)p + (size_t)m + rec_doubles;
+  if (ds->cons_buf_doubles < n_in + n_out) {
+    dfree(ds->cons_buf);
+    ds->cons_buf_doubles = 0;
+    SLM_TRY(dalloc(&ds->cons_buf, n_in + n_out));
+    ds->cons_buf_doubles = n_in + n_out;
+  }
+  if (!ds->cons_state) {
+    SLM_TRY(dalloc(&ds->cons_state, (size_t)SC_STATE));
+    HIP_TRY(hipMemsetAsync(ds->cons_state, 0, sizeof(double) * SC_STATE, s));
+  }
+  std::vector<double> h(n_in + n_out, 0.0);
+  double* ha = h.data();
+  double* hb0 = ha + p;
+  double* hA = hb0 + p;
+  double* hAt = hA + (size_t)m * p;
+  double* hK = hAt + (size_t)m * p;
+  double* hlo = hK + (size_t)p * p;
+  double* hhi = hlo + m;
+  memcpy(ha, a, sizeof(double) * p);
+  if (beta0) memcpy(hb0, beta0, sizeof(double) * p);
+  memcpy(hA, A, sizeof(double) * (size_t)m * p);
+  for (int r = 0; r < m; ++r)
+    for (int j = 0; j < p; ++j) hAt[(size_t)j * m + r] = A[(size_t)r * p + j];
+  for (int i = 0; i < p; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double t = 0.0;
+      for (int r = 0; r < m; ++r) t += A[(size_t)r * p + i] * A[(size_t)r * p + j];
+      hK[(size_t)i * p + j] = t;
+      hK[(size_t)j * p + i] = t;
+    }
+  memcpy(hlo, lo, sizeof(double) * m);
+  memcpy(hhi, hi, sizeof(double) * m);
+  double* d = ds->cons_buf;
+  HIP_TRY(hipMemcpyAsync(d, h.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (the staging vector is pageable and goes with any early return below)
+  ConstrainedArgs k;
+  memset(&k, 0, sizeof(k));
+  k.X = ds->X; k.y = ds->y; k.n = ds->n; k.ld = ld; k.p = p; k.m = m; k.order = ds->order;
+  k.a = d; k.beta0 = beta0 ? d + p : nullptr;
+  k.A = d + 2 * p; k.At = k.A + (size_t)m * p; k.K = k.At + (size_t)m * p;
+  k.lo = k.K + (size_t)p * p; k.hi = k.lo + m;
+  k.beta_out = d + n_in; k.lambda_out = k.beta_out + p;
+  k.info = reinterpret_cast<slm_point_info*>(k.lambda_out + m);
+  k.state = ds->cons_state;
+  k.warm = warm ? 1 : 0;
+  k.tol = opts && opts->tol > 0 ? opts->tol : 1e-8;
+  k.tol_inner = tol_inner > 0 ? tol_inner : std::min(k.tol, 1e-10);
+  k.inv_n = 1.0 / (double)ds->n_global;
+  k.max_sweeps = max_sweeps > 0 ? max_sweeps : 500;
+  k.max_iters = opts && opts->max_iter > 0 ? (int)std::min<int64_t>(opts->max_iter, 4000) : 4000;
+  k.stage_doubles = (int)stage;
+  SLM_TRY(allow_big_lds((const void*)small_constrained_kernel, eng->device));
+  hipLaunchKernelGGL(small_constrained_kernel, dim3(1), dim3(SM_THREADS), lds, s, k);
+  SLM_TRY(check_launch());
+  double* h_out = h.data() + n_in;
+  HIP_TRY(hipMemcpyAsync(h_out, d + n_in, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  slm_point_info rec;
+  memcpy(&rec, h_out + p + m, sizeof(rec));
+  memcpy(beta_out, h_out, sizeof(double) * p);
+  if (lambda_out) memcpy(lambda_out, h_out + p, sizeof(double) * m);
+  if (kn.trace == 2)
+    fprintf(stderr, "[slm] constrained splitting on chip: %d sweeps, %d products, rho %.3e\n", rec.n_iter, rec.rejects, rec.L);
+  if (info) *info = rec;
+  if (rec.status == SLM_ERR_NON_FINITE) return fail(SLM_ERR_NON_FINITE, "non-finite iterate (diverged or non-finite data)");
+  return SLM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // diagnostic: the model solver's dense SPD solve on its own
 // ------------------------------------------------------------------------------------------------
 extern "C" int slm_dense_spd_solve(slm_engine* eng, const double* H, int32_t m, const double* rhs, double* x_out,

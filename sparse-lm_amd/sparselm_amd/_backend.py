@@ -264,6 +264,12 @@ class SolveProblem:
             raise RuntimeError("set_targets needs a problem opened with cache=False")
         self.ds.set_targets(y)
 
+    def set_row_weights(self, row_weight):
+        """New row weights on the same design (problems opened with ``cache=False`` only)."""
+        if not self._private:
+            raise RuntimeError("set_row_weights needs a problem opened with cache=False")
+        self.ds.set_row_weights(row_weight)
+
     def close(self):
         if self.ds is not None:
             _dataset_cache.release(self.ds, self.x_mean, self.y_mean, self._key)

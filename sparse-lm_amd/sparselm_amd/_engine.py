@@ -45,7 +45,7 @@ FLAG_PROFILE_UNIT = 1024  # with FLAG_PROFILE: the event bracket spans residuals
 FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plain steps, no rounds on the model Gram (csrc/mg_kernels.hpp)
 
 COMM_ID_BYTES = 128
-ABI_VERSION = 20  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
+ABI_VERSION = 21  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -85,6 +85,7 @@ ABI_SYMBOLS = (
     "slm_solve_lanes_reweighted",
     "slm_solve_path_lanes",
     "slm_solve_standardized_sgl",
+    "slm_solve_constrained",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -308,6 +309,7 @@ def load_library():
                 vp, P(_PenaltyStruct), P(_PathPoint), i32, i32, P(_SolveOpts), vp, vp, vp, P(_PointInfo), P(_SolveStats),
             ],
             "slm_solve_standardized_sgl": [vp, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
+            "slm_solve_constrained": [vp, vp, vp, i32, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1098,6 +1100,31 @@ class Dataset:
             )
         )
         return beta, gn, info[0]
+
+    def solve_constrained(self, a, A, lo, hi, beta0=None, warm=False, tol=1e-8, tol_inner=0.0, max_sweeps=0, max_iter=0):
+        """``slm_solve_constrained``: ``1/(2n)||X b - y||^2 + sum_j a_j |b_j|`` subject to ``lo <= A b <= hi`` with all
+        sweeps of the splitting in one launch.  Returns ``(beta, multipliers, info)``; ``NotImplementedError`` when the
+        problem is not one the on-chip solver takes (the caller then runs the sweeps itself, model/_constrained.py)."""
+        _sync_knobs()
+        a_ = _f64(np.broadcast_to(a, (self.p,)), "a")
+        A_ = np.ascontiguousarray(A, dtype=np.float64)
+        if A_.ndim != 2 or A_.shape[1] != self.p:
+            raise ValueError(f"A must have {self.p} columns")
+        m = A_.shape[0]
+        lo_ = _f64(lo, "lo", (m,))
+        hi_ = _f64(hi, "hi", (m,))
+        b0 = None if beta0 is None else _f64(beta0, "beta0", (self.p,))
+        opts = _SolveOpts(float(tol), int(max_iter), 0, 0.0, 0)
+        beta = np.empty(self.p)
+        lam = np.empty(m)
+        info = np.zeros(1, dtype=_INFO_DTYPE)
+        _check(
+            self._lib.slm_solve_constrained(
+                self._h, _ptr(a_), _ptr(A_), int(m), _ptr(lo_), _ptr(hi_), C.byref(opts), float(tol_inner), int(max_sweeps),
+                _ptr(b0), int(bool(warm)), _ptr(beta), _ptr(lam), _as(info, _PointInfo),
+            )
+        )
+        return beta, lam, info[0]
 
 
 class _HostPool:

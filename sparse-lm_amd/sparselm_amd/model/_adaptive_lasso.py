@@ -76,6 +76,7 @@ class AdaptiveLasso(Lasso):
         warm_start=True,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         Lasso.__init__(
             self,
@@ -85,6 +86,7 @@ class AdaptiveLasso(Lasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self._init_adaptive(max_iter, eps, tol, update_function)
 
@@ -142,7 +144,8 @@ class AdaptiveLasso(Lasso):
         # standardize=True: the loop runs in the per-group QR coordinates, where the engine's group norms
         # are ||X_g b_g|| -- what the reference feeds to the weight update (_adaptive_lasso.py:364-374)
         dz = self._design_transform(X)
-        problem = self._open_problem(dz.X, dz.target(y), gidx, G, solver_options)
+        problem = self._open_problem(dz.X, dz.target(y), gidx, G, solver_options, design=dz,
+                                     columns=getattr(self, "_ext_columns", None))
         beta = None
         warm = dz.warm(self._warm_beta(p)) if hasattr(self, "coef_") else None
         infos = []
@@ -201,6 +204,7 @@ class AdaptiveGroupLasso(AdaptiveLasso, GroupLasso):
         warm_start=True,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         # explicit base initialisers instead of the reference's cooperative **kwargs chain
         # (sklearn >= 1.6 estimator checks reject a **kwargs constructor)
@@ -215,6 +219,7 @@ class AdaptiveGroupLasso(AdaptiveLasso, GroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self._init_adaptive(max_iter, eps, tol, update_function)
 
@@ -257,6 +262,7 @@ class AdaptiveOverlapGroupLasso(AdaptiveGroupLasso, OverlapGroupLasso):
         warm_start=True,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         OverlapGroupLasso.__init__(
             self,
@@ -269,6 +275,7 @@ class AdaptiveOverlapGroupLasso(AdaptiveGroupLasso, OverlapGroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self._init_adaptive(max_iter, eps, tol, update_function)
 
@@ -285,7 +292,11 @@ class AdaptiveOverlapGroupLasso(AdaptiveGroupLasso, OverlapGroupLasso):
         p = X.shape[1]
         bidx, ext, G = self._extended(X)
         self._ext_groups = ext
-        beta_ext = AdaptiveLasso._solve(self, np.ascontiguousarray(X[:, bidx]), y, solver_options)
+        self._ext_columns = bidx  # (constraints on coef_ act on the sums of the copies: A[:, bidx] on the extended design)
+        try:
+            beta_ext = AdaptiveLasso._solve(self, np.ascontiguousarray(X[:, bidx]), y, solver_options)
+        finally:
+            self._ext_columns = None
         return np.bincount(bidx, weights=beta_ext, minlength=p)
 
     def _design_transform(self, X_ext):
@@ -323,6 +334,7 @@ class AdaptiveSparseGroupLasso(AdaptiveLasso, SparseGroupLasso):
         warm_start=True,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         SparseGroupLasso.__init__(
             self,
@@ -336,6 +348,7 @@ class AdaptiveSparseGroupLasso(AdaptiveLasso, SparseGroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self._init_adaptive(max_iter, eps, tol, update_function)
 
@@ -395,6 +408,7 @@ class AdaptiveRidgedGroupLasso(AdaptiveGroupLasso, RidgedGroupLasso):
         warm_start=True,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         RidgedGroupLasso.__init__(
             self,
@@ -408,6 +422,7 @@ class AdaptiveRidgedGroupLasso(AdaptiveGroupLasso, RidgedGroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self._init_adaptive(max_iter, eps, tol, update_function)
 

@@ -3,8 +3,9 @@
 Mirrors ``CVXRegressor`` (reference src/sparselm/model/_base.py:69-519) for everything a user sees:
 constructor arguments (:128-140), ``fit`` flow (:142-205), preprocessing (:207-227), parameter
 validation through sklearn's declarative constraints (:229-245), ``intercept_`` convention.  The
-cvxpy problem objects (``canonicals_``, ``generate_problem``, ``add_constraints``) have no meaning
-for a proximal-gradient engine and are not provided.
+cvxpy problem objects (``canonicals_``, ``generate_problem``) have no meaning for a proximal-gradient
+engine and are not provided; ``add_constraints`` (:469-510) takes linear constraints in scipy's form
+(``constraints=``, model/_constrained.py).
 """
 
 from __future__ import annotations
@@ -41,9 +42,18 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
             ``check_every``, ``device``, ``on_chip`` (False: never the one-workgroup solvers), ``covariance`` (True: passes
             from the Gram of the rows instead of X -- built once per device dataset; "auto", the default, lets a
             ``GridSearchCV`` decide and a single fit decline).
+        constraints (LinearConstraint | Bounds | list | None): linear constraints on ``coef_`` in
+            ``scipy.optimize`` form -- ``LinearConstraint(A, lb, ub)`` asks ``lb <= A @ coef_ <= ub``, ``Bounds(lb, ub)``
+            asks ``lb <= coef_ <= ub``; ``lb == ub`` rows are equalities, rows with both sides infinite are dropped, a
+            scipy-sparse ``A`` is densified.  They act on ``coef_`` only: the intercept stays ``y_offset - x_offset @ coef_``
+            (reference _base.py:469-510, where they act on ``canonicals_.beta``).  See ``add_constraints``.
 
     Attributes:
         coef_ (ndarray of shape (n_features,)), intercept_ (float), solver_info_ (dict).
+        constraint_multipliers_ (list of ndarray): with ``constraints``, one array per constraint object: the
+            multipliers ``lambda`` of ``0 in grad f + d penalty + sum_k A_k^T lambda_k`` -- ``> 0`` only where ``ub``
+            binds, ``< 0`` only where ``lb`` binds.  ``solver_info_`` then also carries ``route`` (``"on_chip"`` or
+            ``"host"``), ``sweeps``, ``primal_residual``, ``dual_residual``, ``rho`` and ``max_violation``.
     """
 
     _parameter_constraints: dict = {
@@ -52,17 +62,30 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
         "warm_start": ["boolean"],
         "solver": [str, None],
         "solver_options": [dict, None],
+        "constraints": "no_validation",  # (checked at fit: model/_constrained.py)
     }
     # constraints on the regularisation hyper-parameters (the reference's
     # ``_cvx_parameter_constraints``, _base.py:126)
     _hyper_parameter_constraints: dict | None = None
 
-    def __init__(self, fit_intercept=False, copy_X=True, warm_start=False, solver=None, solver_options=None):
+    def __init__(self, fit_intercept=False, copy_X=True, warm_start=False, solver=None, solver_options=None,
+                 constraints=None):
         self.fit_intercept = fit_intercept
         self.copy_X = copy_X
         self.warm_start = warm_start
         self.solver = solver
         self.solver_options = solver_options
+        self.constraints = constraints
+
+    def add_constraints(self, constraints):
+        """Append linear constraints (a ``LinearConstraint`` / ``Bounds`` or a list of them) to ``self.constraints``
+        -- the reference's ``add_constraints`` (_base.py:469-510) in scipy's form.  A new list is built: the caller's
+        list is never changed.  Returns the estimator."""
+        from ._constrained import _as_list
+
+        old = [] if self.constraints is None else _as_list(self.constraints)
+        self.constraints = old + _as_list(constraints)
+        return self
 
     @classmethod
     def _get_param_names(cls):
@@ -102,6 +125,13 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
         else:
             X, y, X_offset, y_offset = self._preprocess_data(X, y, sample_weight)
         self._validate_params(X, y)
+        self._constraint_set = None
+        if self.constraints is not None:
+            from ._constrained import check_feasible, stack_constraints
+
+            cs = stack_constraints(self.constraints, X.shape[1])
+            check_feasible(cs)
+            self._constraint_set = cs
 
         solver_options = self.solver_options if self.solver_options is not None else {}
         if not isinstance(solver_options, dict):
@@ -116,8 +146,17 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
             self.coef_ = self._solve(X, y, normalise_options(solver_options), *args, **kwargs)
             if self._native is not None and self._native.get("offsets") is not None:
                 X_offset, y_offset = self._native["offsets"]
+            cs = self._constraint_set
+            if cs is not None:
+                last = self._constrained_problem
+                self.constraint_multipliers_ = cs.split(last.multipliers)
+                self.solver_info_ = dict(self.solver_info_)
+                keys = ("route", "sweeps", "primal_residual", "dual_residual", "rho", "launches")
+                self.solver_info_.update({k: last.info[k] for k in keys})
+                self.solver_info_["max_violation"] = cs.violation(self.coef_)
         finally:
             native, self._native = self._native, None
+            self._constraint_set = self._constrained_problem = None
         del native
         self._set_intercept(X_offset, y_offset)
         return self
@@ -173,11 +212,16 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
 
     def _needs_host_preprocessing(self) -> bool:
         """True when ``_solve`` manipulates the preprocessed design on the host (column duplication,
-        per-group QR) and therefore needs the centred / re-weighted X itself."""
-        return False
+        per-group QR, the rows of linear constraints) and therefore needs the centred / re-weighted X itself."""
+        return self.constraints is not None
 
-    def _open_problem(self, X, y, gidx, G, solver_options):
-        """Upload (X, y) to the backend; in native mode with device-side weights and centring."""
+    def _open_problem(self, X, y, gidx, G, solver_options, design=None, columns=None):
+        """Upload (X, y) to the backend; in native mode with device-side weights and centring.  With constraints: the
+        splitting of model/_constrained.py, the constraints mapped onto the unknowns of ``design`` (whose columns are
+        ``coef[columns]`` when given: the duplicated columns of the overlap classes)."""
+        cs = getattr(self, "_constraint_set", None)
+        if cs is not None:
+            return self._open_constrained(X, y, gidx, G, solver_options, cs, design, columns)
         native = getattr(self, "_native", None)
         if native is None:
             return get_backend().problem(X, y, gidx, G, solver_options)
@@ -187,6 +231,16 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
         )
         if native["center"]:
             native["offsets"] = (problem.x_mean, problem.y_mean)
+        return problem
+
+    def _open_constrained(self, X, y, gidx, G, solver_options, cs, design, columns):
+        from ._constrained import ConstrainedProblem
+
+        A = cs.A if columns is None else cs.A[:, columns]
+        if design is not None:
+            A = design.map_constraints(A)
+        problem = ConstrainedProblem(X, y, gidx, G, A, cs.lo, cs.hi, solver_options)
+        self._constrained_problem = problem  # (`fit` reads the multipliers and the record of its last solve)
         return problem
 
     def _design_transform(self, X):
@@ -207,7 +261,7 @@ class ProxRegressor(RegressorMixin, BaseEstimator):
         a, b, d, gidx, G = self._penalty(X)
         p = X.shape[1]
         dz = self._design_transform(X)
-        problem = self._open_problem(dz.X, dz.target(y), gidx, G, solver_options)
+        problem = self._open_problem(dz.X, dz.target(y), gidx, G, solver_options, design=dz)
         try:
             beta, _, info = problem.solve(
                 np.zeros(p) if a is None else a,

@@ -41,7 +41,8 @@ class Lasso(ProxRegressor):
     _hyper_parameter_constraints: dict = {"alpha": [Interval(type=Real, left=0.0, right=None, closed="left")]}
 
     def __init__(
-        self, alpha=1.0, fit_intercept=False, copy_X=True, warm_start=False, solver=None, solver_options=None
+        self, alpha=1.0, fit_intercept=False, copy_X=True, warm_start=False, solver=None, solver_options=None,
+        constraints=None,
     ):
         ProxRegressor.__init__(
             self,
@@ -50,6 +51,7 @@ class Lasso(ProxRegressor):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self.alpha = alpha
 
@@ -84,6 +86,7 @@ class GroupLasso(Lasso):
         warm_start=False,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         self.groups = groups
         self.standardize = standardize
@@ -96,6 +99,7 @@ class GroupLasso(Lasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
 
     def _validate_params(self, X, y) -> None:
@@ -114,7 +118,7 @@ class GroupLasso(Lasso):
         check_group_weights(self.group_weights, n_groups)
 
     def _needs_host_preprocessing(self) -> bool:
-        return bool(self.standardize)  # the per-group QR works on the centred design
+        return bool(self.standardize) or super()._needs_host_preprocessing()  # the per-group QR works on the centred design
 
     def _design_transform(self, X):
         if not self.standardize:
@@ -157,6 +161,14 @@ class Design:
         if beta is None or self._forward is None:
             return beta if self._back is None else None
         return self._forward(beta)
+
+    def map_constraints(self, A):
+        """Constraint rows on the coefficients -> rows on the engine's unknowns: ``A B`` with ``coef = B gamma``."""
+        if self._back is None:
+            return A
+        p = self.X.shape[1]
+        B = np.column_stack([self._back(e) for e in np.eye(p)])
+        return np.asarray(A, dtype=np.float64) @ B
 
     def target(self, y):
         if not self.extra_rows:
@@ -295,6 +307,7 @@ class OverlapGroupLasso(GroupLasso):
         warm_start=False,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         self.group_list = group_list
         GroupLasso.__init__(
@@ -308,6 +321,7 @@ class OverlapGroupLasso(GroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
 
     @classmethod
@@ -349,7 +363,7 @@ class OverlapGroupLasso(GroupLasso):
         w = np.ones(G) if self.group_weights is None else np.asarray(self.group_weights, dtype=np.float64)
         X_ext = np.ascontiguousarray(X[:, bidx])
         dz = standardize_groups(X_ext, ext, G) if self.standardize else Design(X_ext)
-        problem = self._open_problem(dz.X, dz.target(y), ext, G, solver_options)
+        problem = self._open_problem(dz.X, dz.target(y), ext, G, solver_options, design=dz, columns=bidx)
         try:
             beta_ext, _, info = problem.solve(np.zeros(len(bidx)), self.alpha * w, np.zeros(G))
         finally:
@@ -374,6 +388,7 @@ class SparseGroupLasso(GroupLasso):
         warm_start=False,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         GroupLasso.__init__(
             self,
@@ -386,6 +401,7 @@ class SparseGroupLasso(GroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self.l1_ratio = l1_ratio
 
@@ -403,6 +419,11 @@ class SparseGroupLasso(GroupLasso):
                 "It is more efficient to use Lasso directly than SparseGroupLasso with l1_ratio=1",
                 UserWarning,
             )
+        if self.standardize and self.constraints is not None:
+            raise ValueError(
+                f"{type(self).__name__}(standardize=True) does not take constraints: its penalty is already solved by a "
+                "splitting (model/_split.py), and a second one around it is not provided"
+            )
 
     def _lambdas(self):
         return self.l1_ratio * self.alpha, (1.0 - self.l1_ratio) * self.alpha
@@ -413,9 +434,9 @@ class SparseGroupLasso(GroupLasso):
     def _design_transform(self, X):
         return Design(X)
 
-    def _open_problem(self, X, y, gidx, G, solver_options):
+    def _open_problem(self, X, y, gidx, G, solver_options, design=None, columns=None):
         if not self.standardize:
-            return super()._open_problem(X, y, gidx, G, solver_options)
+            return super()._open_problem(X, y, gidx, G, solver_options, design=design, columns=columns)
         from ._split import StandardizedSparseGroupProblem
 
         return StandardizedSparseGroupProblem(X, y, gidx, G, solver_options)
@@ -459,6 +480,7 @@ class RidgedGroupLasso(GroupLasso):
         warm_start=False,
         solver=None,
         solver_options=None,
+        constraints=None,
     ):
         GroupLasso.__init__(
             self,
@@ -471,6 +493,7 @@ class RidgedGroupLasso(GroupLasso):
             warm_start=warm_start,
             solver=solver,
             solver_options=solver_options,
+            constraints=constraints,
         )
         self.delta = delta
 

@@ -205,8 +205,9 @@ class GridSearchCV(_GridSearchCV):
             return False
         if getattr(_backend.get_backend(), "name", None) != "hip":  # (tests may inject another backend)
             return False
-        # standardize=True and the overlap classes assemble another design matrix on the host per fit
-        if est._needs_host_preprocessing() or fit_params:
+        # standardize=True and the overlap classes assemble another design matrix on the host per fit; constrained
+        # estimators run the splitting of model/_constrained.py through `fit`, cell by cell
+        if est._needs_host_preprocessing() or getattr(est, "constraints", None) is not None or fit_params:
             return False
         if self.scoring not in _FAST_SCORINGS or self.return_train_score:
             return False

@@ -40,6 +40,10 @@ def constrain_coefficients(indices, high=None, low=None):
 
         @constrain_coefficients(idx, high, low)
         def fit_method(X, y, ...): ...
+
+    This is a heuristic.  The exact alternative is a constrained fit: ``est.add_constraints(
+    scipy.optimize.LinearConstraint(np.eye(p)[idx], low, high))`` -- or ``constraints=`` in the estimator's
+    constructor -- minimises the estimator's own objective subject to the bounds (model/_constrained.py).
     """
     idx = np.asarray(indices, dtype=np.intp).ravel()
     hi = _bound_vector(high, idx.size, np.inf)
