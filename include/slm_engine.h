@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SLM_ABI_VERSION 21
+#define SLM_ABI_VERSION 22
 
 typedef enum slm_status {
   SLM_OK = 0,
@@ -200,6 +200,42 @@ int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradient_opts* o
 int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lanes, const double* Z, const double* row_weights,
                        const double* n_eff, const int32_t* cov_index, int64_t n_rows, double* G_out, double* loss_out,
                        char* kernels_out, int32_t kernels_len);
+
+/*
+ * Diagnostic: a working set W built in stages and one gradient pass of n_lanes lanes on it -- how the tests check the kernels
+ * that build W's Gram and gathered columns and the residual kernels that read them, against a reference.
+ *   cols[0 : k_end[0]] is a fresh selection; build b > 0 appends cols[k_end[b-1] : k_end[b]] (distinct feature indices,
+ *   k_end increasing, at most 512 in all).  Each build sets W's control block as the device's selection does (Kreal, K =
+ *   max(16, Kreal rounded up to 16), k_new = the previous Kreal, idx = -1 on the padding) and queues what a solve queues after
+ *   a selection: ws_gather_kernel (from the column-major copy of X, or from X with SLM_WSL_GATHER_X), the ws_xty kernels
+ *   (SLM_WSL_XTY), ws_gram_kernel, ws_gram_reduce_kernel -- or ws_gram_cov_kernel under route 2.
+ *   Lanes with the same row weights and n_eff share a Gram (a row set); set_of_out[l] is lane l's, n_sets_out their number.
+ *   Then one pass: route 1 the split pass (residuals from W for the lanes with on_ws[l] != 0, from X for the others, then X^T R),
+ *   route 2 the covariance route (cov_index[l]: the lane's entry of slm_dataset_covariance*; no row weights, no n_eff).  A lane
+ *   with on_ws must be zero outside W (SLM_ERR_BAD_ARG otherwise).  G_out[l], loss_out[l] as for slm_gradient_lanes.
+ * gram_out: [n_sets][K][K] (nullable); xw_out: [n][K] (nullable; route 1); xty_out: [Kreal + 1] (SLM_WSL_XTY):
+ * -X_W^T y / n, then y^T y / 2n.  kernels_out (nullable): every kernel launched, ';'-separated, in order; the covariance
+ * product is named "+listed" when every row set reads only W's rows of its Gram.  SLM_ERR_UNSUPPORTED where no kernel serves
+ * the call, and for row-sharded datasets.  No reference counterpart (tests only).
+ */
+#define SLM_WSL_GATHER_X 1u  /* gather from the row-major X, not the column-major copy */
+#define SLM_WSL_XTY 2u       /* queue the ws_xty kernels with every build (the refinement after a row-sample pass) */
+typedef struct slm_ws_lanes_opts {
+  int32_t route;             /* 1: split pass, 2: covariance entries */
+  int32_t n_lanes;           /* 1 .. SLM_MAX_LANES */
+  const double* Z;           /* [n_lanes][p] */
+  const int32_t* on_ws;      /* [n_lanes], NULL: no lane */
+  const double* row_weights; /* [n_lanes][n], NULL: the dataset's */
+  const double* n_eff;       /* [n_lanes], NULL: n */
+  const int32_t* cov_index;  /* [n_lanes], route 2 */
+  const int32_t* cols;       /* [k_end[n_builds - 1]] */
+  const int32_t* k_end;      /* [n_builds] */
+  int32_t n_builds;
+  uint32_t flags;            /* SLM_WSL_* */
+} slm_ws_lanes_opts;
+int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* opts, double* G_out, double* loss_out, int32_t* set_of_out,
+                          int32_t* n_sets_out, double* gram_out, double* xw_out, double* xty_out, char* kernels_out,
+                          int32_t kernels_len);
 
 /*
  * Weighted squared error of m coefficient vectors, as many per pass over X as the fused kernel

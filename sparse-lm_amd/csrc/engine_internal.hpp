@@ -106,7 +106,10 @@ struct SplitKernel {
 // the residual and product kernels a gradient launch chose (slm_gradient_lanes; nullptr everywhere else)
 struct GradNames {
   const char* resid = nullptr;
+  const char* ws_resid = nullptr;  // the residuals from the working set's gathered columns (split pass with control blocks)
   const char* product = nullptr;
+  int cov_rows_ws = 0;    // covariance pass: listed rows per workgroup row (SplitArgs::xrows_ws; 0: the listed mode is off) ...
+  int cov_row_blocks = 0; // ... and the workgroup rows of the product
 };
 static const int kMaxTailE = 64;  // the tail kernels cover p <= 1024 * 64
 static const int64_t kMaxChunks = 64 * 8 * 10;  // largest row the fused kernel covers (p <= 10240)

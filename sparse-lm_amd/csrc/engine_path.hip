@@ -872,19 +872,24 @@ int PathCall::run_on_chip() {
 // Small problems start with plain steps (their passes cost less than a model solve) and switch the
 // refinement on when a path point turns out to be hard (ws_late: more than kWsLateIters passes on
 // one point -- ill-conditioned designs, where FISTA needs thousands).
-int PathCall::ws_setup(bool late) {
-  // lanes with the same row weights (same host pointer: the folds of a CV grid) and the same 1/n
-  // scaling share one Gram
-  const int* set_of = ws_set_of;
-  const int* set_lane = ws_set_lane;
-  const int n_sets = ws_n_sets;
-  const int ws_nblk_most = (int)std::max<int64_t>(1, std::min<int64_t>(eng->cus, n / 64));  // (2 MiB of partials each)
+// The working set's buffers, row blocks and arguments: PathCall::ws_setup and slm_working_set_lanes (the diagnostic runs the
+// grids of a solve, not a copy of them).
+struct WsBlocks {
+  int most;  // row blocks the partial Grams are allocated for (depends on n only)
+  int nblk;  // row blocks of this call
+};
+static WsBlocks ws_row_blocks(const slm_dataset* ds, bool share_blocks, int n_sets) {
+  const int cus = ds->eng->cus;
+  const int most = (int)std::max<int64_t>(1, std::min<int64_t>(cus, ds->n / 64));  // (2 MiB of partials each)
   // Row sets that share partial Grams (ws_block_owner_kernel): the row blocks that are worked on are one per block plus the few
   // where a set's weights change (two per contiguous fold) -- a handful more than there are CUs is a second round of workgroups
   // for the stragglers, i.e. the time of two Grams for the work of one.  A few blocks fewer, and everything is one round.
   // (whether or not SLM_NO_GRAM_OWNER switches the sharing off: the same blocks, the same sums, bit for bit)
-  const bool share_blocks = ls.rw != nullptr && !sharded && n_sets > 1;
-  const int ws_nblk = share_blocks ? std::max(1, std::min(ws_nblk_most, eng->cus - 2 * n_sets)) : ws_nblk_most;
+  return {most, share_blocks ? std::max(1, std::min(most, cus - 2 * n_sets)) : most};
+}
+
+static int ws_alloc(const slm_host::Knobs& kn, slm_dataset* ds, int n_sets, int nblk_most, bool sharded) {
+  const int64_t n = ds->n, ld = ds->ld;
   // (each on its own: slm_eval_sse_sparse may already have brought idx and XW in)
   if (!ds->ws_idx) SLM_TRY(dalloc(&ds->ws_idx, WS_KCAP));
   if (!ds->ws_gs) SLM_TRY(dalloc(&ds->ws_gs, WS_KCAP));
@@ -897,25 +902,28 @@ int PathCall::ws_setup(bool late) {
     dfree(ds->ws_part); dfree(ds->ws_G); dfree(ds->ws_Gx);
     ds->ws_sets = 0;
     if (sharded) SLM_TRY(dalloc(&ds->ws_Gx, (size_t)n_sets * WS_KCAP * WS_KCAP + STOP_WORDS));
-    SLM_TRY(dalloc(&ds->ws_part, (size_t)ws_nblk_most * n_sets * WS_KCAP * WS_KCAP));  // (ws_nblk_most depends on n only)
+    SLM_TRY(dalloc(&ds->ws_part, (size_t)nblk_most * n_sets * WS_KCAP * WS_KCAP));  // (nblk_most depends on n only)
     SLM_TRY(dalloc(&ds->ws_G, (size_t)n_sets * WS_KCAP * WS_KCAP));
     ds->ws_sets = n_sets;
   }
   // column-major copy of X (a layout of the data like the padded row-major one: depends on nothing
   // but X, kept for the life of the dataset; 2 ms for 4 GB).  Optional: without the memory for it
   // the gathers read the row-major X, one 64-byte sector per element.
-  SLM_TRY(ensure_xt(kn, ds));
-  // (initialised on the device: a host-side copy would need the stream drained before its buffer goes away)
-  if (late) HIP_TRY(hipMemsetAsync(ds->ws_ctl, 0, sizeof(WsCtl), s));  // (a fresh solve has cleared it already)
-  if (ws_carry && !late) hipLaunchKernelGGL(ws_ctl_carry_kernel, dim3(1), dim3(256), 0, s, ds->ws_ctl, kWsMaxBuilds);
-  else if (late || !ws_begun) hipLaunchKernelGGL(ws_ctl_init_kernel, dim3(1), dim3(64), 0, s, ds->ws_ctl, kWsMaxBuilds);  // (else: solve_begin_kernel has)
+  return ensure_xt(kn, ds);
+}
+
+// the fields of `wa` that describe the buffers, the data and the row sets; and, where row sets share partial Grams, the owners
+// of the row blocks (ws_block_owner_kernel, queued on s)
+static int ws_bind(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls, const int* set_of, const int* set_lane, int n_sets,
+                   int nblk, bool sharded, WsArgs& wa, hipStream_t s) {
+  const int B = ls.B;
   wa.ws = ds->ws_ctl;
   wa.idx = ds->ws_idx; wa.pos = ds->ws_pos; wa.gs = ds->ws_gs; wa.gl = ds->ws_gl;
   wa.score = ds->ws_score; wa.XW = ds->ws_XW; wa.part = ds->ws_part; wa.Gm = ds->ws_G;
   wa.nt = ds->ws_nt;
   if (sharded && !ds->ws_Gx) SLM_TRY(dalloc(&ds->ws_Gx, (size_t)ds->ws_sets * WS_KCAP * WS_KCAP + STOP_WORDS));
   wa.Gx = sharded ? ds->ws_Gx : nullptr;  // row-sharded: Gram parts are summed over ranks before use
-  wa.X = ds->X; wa.XT = ds->XT; wa.n = n; wa.ld = ld;
+  wa.X = ds->X; wa.XT = ds->XT; wa.n = ds->n; wa.ld = ds->ld;
   wa.rw = ls.rw; wa.rw_stride = ls.rw_stride;
   for (int l = 0; l < kMaxLanes; ++l) {
     wa.set_of[l] = l < B ? set_of[l] : 0;
@@ -924,14 +932,28 @@ int PathCall::ws_setup(bool late) {
     wa.inv_n[l] = 1.0 / (ls.n_eff[rep] > 0 ? ls.n_eff[rep] : (double)ds->n_global);
   }
   wa.n_sets = n_sets;
-  wa.nblk = ws_nblk;
+  wa.nblk = nblk;
   // row blocks on which a set's row weights are all zeros, or all ones like another set's: ws_block_owner_kernel
   wa.owner = nullptr;
-  if (ls.rw != nullptr && !sharded && kn.gram_owner && ws_nblk <= 512) {
+  if (ls.rw != nullptr && !sharded && kn.gram_owner && nblk <= 512) {
     if (!ds->ws_owner) SLM_TRY(dalloc(&ds->ws_owner, (size_t)kMaxLanes * 512));
-    hipLaunchKernelGGL(ws_block_owner_kernel, dim3((unsigned)ws_nblk), dim3(256), 0, s, ls.rw, ls.rw_stride, wa, ds->ws_owner);
+    hipLaunchKernelGGL(ws_block_owner_kernel, dim3((unsigned)nblk), dim3(256), 0, s, ls.rw, ls.rw_stride, wa, ds->ws_owner);
     wa.owner = ds->ws_owner;
   }
+  return SLM_OK;
+}
+
+int PathCall::ws_setup(bool late) {
+  // lanes with the same row weights (same host pointer: the folds of a CV grid) and the same 1/n
+  // scaling share one Gram
+  const int n_sets = ws_n_sets;
+  const WsBlocks wb = ws_row_blocks(ds, ls.rw != nullptr && !sharded && n_sets > 1, n_sets);
+  SLM_TRY(ws_alloc(kn, ds, n_sets, wb.most, sharded));
+  // (initialised on the device: a host-side copy would need the stream drained before its buffer goes away)
+  if (late) HIP_TRY(hipMemsetAsync(ds->ws_ctl, 0, sizeof(WsCtl), s));  // (a fresh solve has cleared it already)
+  if (ws_carry && !late) hipLaunchKernelGGL(ws_ctl_carry_kernel, dim3(1), dim3(256), 0, s, ds->ws_ctl, kWsMaxBuilds);
+  else if (late || !ws_begun) hipLaunchKernelGGL(ws_ctl_init_kernel, dim3(1), dim3(64), 0, s, ds->ws_ctl, kWsMaxBuilds);  // (else: solve_begin_kernel has)
+  SLM_TRY(ws_bind(kn, ds, ls, ws_set_of, ws_set_lane, n_sets, wb.nblk, sharded, wa, s));
   // measured on the headline path (tools/ws_sweep.py, 24 combinations within 8 % of each other):
   // theta 0.85 / look-ahead 2 / 16 newcomers per pass / 112 initial columns was the fastest
   // (append 48: interleaved lanes need the next band of the path at once; elsewhere 16 cost a pass now and then)
@@ -1030,6 +1052,48 @@ void PathCall::enqueue_tail() {
   }
 }
 
+// The build of the working set a selection has just published (WsCtl::building): gather the new columns, optionally the exact
+// gradient at zero on W (`xty`: the refinement after the pass on a row sample), the partial Grams and their fixed-order sum --
+// or, under covariance passes (`cs` != nullptr), the sub-matrix of the row sets' Grams.  Every kernel returns at once unless
+// a build is under way.  PathCall::enqueue_refinement and slm_working_set_lanes; `names` (nullable): the kernels launched.
+struct WsNames {
+  const char* k[8];
+  int n = 0;
+  void add(const char* name) { if (n < 8) k[n++] = name; }
+};
+static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* cs, bool xty, const int* done, int n_lanes, hipStream_t s,
+                             WsNames* names = nullptr) {
+  const int64_t n = ds->n;
+  if (cs) {
+    // covariance passes: the working set's Gram is a sub-matrix of the row set's (no gathered columns, no product
+    // over the rows; nothing reads XW in this mode -- the residuals of a pass are not formed at all)
+    hipLaunchKernelGGL(ws_gram_cov_kernel, dim3(WS_TILES * WS_TILES, (unsigned)wa.n_sets), dim3(256), 0, s, wa, *cs);
+    if (names) names->add("ws_gram_cov_kernel");
+    return;
+  }
+  hipLaunchKernelGGL(ws_gather_kernel, dim3((unsigned)std::min<int64_t>((n + 31) / 32, 1024), WS_KCAP / 32), dim3(256), 0, s, wa);
+  if (names) names->add("ws_gather_kernel");
+  if (xty) {  // the exact gradient at zero on W, from the gathered columns (ws_kernels.hpp (ii-b))
+    XtyArgs xa;
+    // (its partial sums, up to 2 CUs x 513 doubles, go where the Gram kernel's go next: that block holds 512 x 512 doubles per row
+    //  block of the Gram kernel, at least half as many blocks as these.  The gradient's `partial` is sized by the gradient
+    //  kernels' grids alone -- 8192 ld doubles from X^T R, less than 512 x 513 for rows of up to 32 columns)
+    xa.ws = wa.ws; xa.idx = wa.idx; xa.XW = wa.XW; xa.y = ds->y; xa.part = wa.part; xa.g = ds->g; xa.gprev = ds->gprev; xa.z = ds->z;
+    xa.ctl = ds->ctl; xa.done = done; xa.n = n; xa.ld = ds->ld; xa.inv_n = 1.0 / (double)ds->n_global; xa.n_lanes = n_lanes;
+    xa.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(2 * ds->eng->cus, n / 64));
+    hipLaunchKernelGGL(ws_xty_partial_kernel, dim3((unsigned)xa.nblk), dim3(512), 0, s, xa);
+    hipLaunchKernelGGL(ws_xty_apply_kernel, dim3(WS_KCAP / 128), dim3(512), 0, s, xa);
+    if (names) { names->add("ws_xty_partial_kernel"); names->add("ws_xty_apply_kernel"); }
+  }
+  hipLaunchKernelGGL(ws_gram_kernel, dim3((unsigned)wa.nblk, (unsigned)wa.n_sets, 1), dim3(WS_GRAM_THREADS), 0, s,
+                     wa);
+  if (wa.Gx)  // (zero where this pass builds nothing, so the unconditional all-reduce below is harmless)
+    (void)hipMemsetAsync(wa.Gx, 0, sizeof(double) * (size_t)wa.n_sets * WS_KCAP * WS_KCAP, s);
+  hipLaunchKernelGGL(ws_gram_reduce_kernel, dim3(WS_TILES * WS_TILES, (unsigned)wa.n_sets), dim3(256),
+                     0, s, wa);
+  if (names) { names->add("ws_gram_kernel"); names->add("ws_gram_reduce_kernel"); }
+}
+
 void PathCall::enqueue_refinement() {
   if (use_ws) {
     {
@@ -1039,27 +1103,11 @@ void PathCall::enqueue_refinement() {
       hipLaunchKernelGGL(ws_select_kernel, dim3(1), dim3(WS_THREADS), 0, s, ta, wa);
     }
     if (cov_on) {
-      // covariance passes: the working set's Gram is a sub-matrix of the row set's (no gathered columns, no product
-      // over the rows; nothing reads XW in this mode -- the residuals of a pass are not formed at all)
       CovSets cs;
       for (int st = 0; st < kMaxLanes; ++st) cs.G[st] = st < wa.n_sets ? ds->cov[(size_t)cov_entry[wa.set_lane[st]]].G : nullptr;
-      hipLaunchKernelGGL(ws_gram_cov_kernel, dim3(WS_TILES * WS_TILES, (unsigned)wa.n_sets), dim3(256), 0, s, wa, cs);
+      ws_enqueue_build(ds, wa, &cs, false, done_flag, B, s);
     } else {
-    hipLaunchKernelGGL(ws_gather_kernel, dim3((unsigned)std::min<int64_t>((n + 31) / 32, 1024), WS_KCAP / 32), dim3(256), 0, s, wa);
-    if (fix_start) {  // the exact gradient at zero on W, from the gathered columns (ws_kernels.hpp (ii-b))
-      XtyArgs xa;
-      xa.ws = wa.ws; xa.idx = wa.idx; xa.XW = wa.XW; xa.y = ds->y; xa.part = ds->partial; xa.g = ds->g; xa.gprev = ds->gprev; xa.z = ds->z;
-      xa.ctl = ds->ctl; xa.done = done_flag; xa.n = n; xa.ld = ld; xa.inv_n = 1.0 / (double)ds->n_global; xa.n_lanes = B;
-      xa.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(2 * eng->cus, n / 64));
-      hipLaunchKernelGGL(ws_xty_partial_kernel, dim3((unsigned)xa.nblk), dim3(512), 0, s, xa);
-      hipLaunchKernelGGL(ws_xty_apply_kernel, dim3(WS_KCAP / 128), dim3(512), 0, s, xa);
-    }
-    hipLaunchKernelGGL(ws_gram_kernel, dim3((unsigned)wa.nblk, (unsigned)wa.n_sets, 1), dim3(WS_GRAM_THREADS), 0, s,
-                       wa);
-    if (wa.Gx)  // (zero where this pass builds nothing, so the unconditional all-reduce below is harmless)
-      (void)hipMemsetAsync(wa.Gx, 0, sizeof(double) * (size_t)wa.n_sets * WS_KCAP * WS_KCAP, s);
-    hipLaunchKernelGGL(ws_gram_reduce_kernel, dim3(WS_TILES * WS_TILES, (unsigned)wa.n_sets), dim3(256),
-                       0, s, wa);
+      ws_enqueue_build(ds, wa, nullptr, fix_start, done_flag, B, s);
     }
     if (wa.Gx) {
       // one collective per pass on every rank whether or not a build is under way: the ranks run the
@@ -1646,4 +1694,229 @@ extern "C" int slm_solve_path(slm_dataset* ds, const slm_penalty* pen, const slm
   lane.group_norms_out = group_norms_out;
   lane.infos = infos;
   return slm_solve_lanes(ds, &lane, 1, opts, stats);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Diagnostic: a working set built in stages and one gradient pass on it (slm_engine.h).  The buffers, row blocks and launches
+// are a solve's own (ws_row_blocks, ws_alloc, ws_bind, ws_enqueue_build, enqueue_gradient_split / _cov); only the selection is
+// the caller's.  No fallback: where no kernel serves the call the answer is SLM_ERR_UNSUPPORTED.
+// ------------------------------------------------------------------------------------------------
+extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o, double* G_out, double* loss_out, int32_t* set_of_out,
+                                     int32_t* n_sets_out, double* gram_out, double* xw_out, double* xty_out, char* kernels_out,
+                                     int32_t kernels_len) {
+  if (!ds || !o || !o->Z || !o->cols || !o->k_end || !G_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  const int route = o->route, B = o->n_lanes, nb = o->n_builds;
+  const bool gather_x = (o->flags & SLM_WSL_GATHER_X) != 0, xty = (o->flags & SLM_WSL_XTY) != 0;
+  if (route != 1 && route != 2) return fail(SLM_ERR_BAD_ARG, "route must be 1 (split pass) or 2 (covariance), got %d", route);
+  if (B < 1 || B > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "between 1 and %d lanes, got %d", kMaxLanes, B);
+  if (o->flags & ~(SLM_WSL_GATHER_X | SLM_WSL_XTY)) return fail(SLM_ERR_BAD_ARG, "unknown flags %#x", o->flags);
+  if (xty != (xty_out != nullptr)) return fail(SLM_ERR_BAD_ARG, "xty_out goes with SLM_WSL_XTY");
+  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "slm_working_set_lanes: row-sharded datasets");
+  if (B > ds->lane_cap) return fail(SLM_ERR_UNSUPPORTED, "%d lanes: the dataset holds %d", B, ds->lane_cap);
+  const int64_t n = ds->n, p = ds->p, ld = ds->ld;
+  // ---- the stages of W
+  if (nb < 1) return fail(SLM_ERR_BAD_ARG, "at least one build");
+  for (int b = 0; b < nb; ++b)
+    if (o->k_end[b] <= (b > 0 ? o->k_end[b - 1] : 0) || o->k_end[b] > WS_KCAP)
+      return fail(SLM_ERR_BAD_ARG, "k_end must increase from above 0 to at most %d (build %d: %d)", WS_KCAP, b, o->k_end[b]);
+  const int kreal = o->k_end[nb - 1];
+  const int K = std::max(16, (kreal + 15) & ~15);
+  std::vector<int32_t> pos((size_t)ld, -1);
+  for (int k = 0; k < kreal; ++k) {
+    const int32_t j = o->cols[k];
+    if (j < 0 || j >= p) return fail(SLM_ERR_BAD_ARG, "cols[%d] = %d outside [0, %lld)", k, j, (long long)p);
+    if (pos[(size_t)j] >= 0) return fail(SLM_ERR_BAD_ARG, "cols[%d] = %d repeats cols[%d]", k, j, pos[(size_t)j]);
+    pos[(size_t)j] = k;
+  }
+  // ---- the lanes
+  std::vector<int32_t> zzero((size_t)B, 1);
+  for (int l = 0; l < B; ++l)
+    for (int64_t j = 0; j < p; ++j) {
+      const double v = o->Z[(size_t)l * p + j];
+      if (!std::isfinite(v)) return fail(SLM_ERR_BAD_ARG, "Z contains a non-finite value");
+      if (v != 0.0) {
+        zzero[(size_t)l] = 0;
+        if (o->on_ws && o->on_ws[l] && pos[(size_t)j] < 0)
+          return fail(SLM_ERR_BAD_ARG, "lane %d is marked on the working set but Z[%d][%lld] != 0 is outside it", l, l, (long long)j);
+      }
+    }
+  if (o->row_weights)
+    for (int64_t k = 0; k < (int64_t)B * n; ++k)
+      if (!(o->row_weights[k] >= 0.0) || !std::isfinite(o->row_weights[k]))
+        return fail(SLM_ERR_BAD_ARG, "row_weights[%lld] is negative or not finite", (long long)k);
+  if (o->n_eff)
+    for (int l = 0; l < B; ++l)
+      if (!(o->n_eff[l] > 0.0) || !std::isfinite(o->n_eff[l])) return fail(SLM_ERR_BAD_ARG, "n_eff[%d] must be positive and finite", l);
+  if (route == 2) {
+    if (o->row_weights || o->n_eff) return fail(SLM_ERR_UNSUPPORTED, "route 2 takes its rows from the covariance entries: no row_weights or n_eff");
+    if (gather_x || xty || xw_out) return fail(SLM_ERR_UNSUPPORTED, "route 2 gathers no columns: no XW, no X_W^T y");
+    if (ds->cov.empty()) return fail(SLM_ERR_UNSUPPORTED, "route 2: the dataset has no covariance entries");
+    if (!o->cov_index) return fail(SLM_ERR_BAD_ARG, "route 2 needs cov_index");
+    for (int l = 0; l < B; ++l)
+      if (o->cov_index[l] < 0 || o->cov_index[l] >= (int32_t)ds->cov.size())
+        return fail(SLM_ERR_BAD_ARG, "cov_index[%d] = %d: the dataset has %d entries", l, o->cov_index[l], (int)ds->cov.size());
+  }
+  const slm_host::Knobs kn = knobs();
+  HIP_TRY(hipSetDevice(ds->eng->device));
+  hipStream_t s = ds->eng->stream;
+  if (route == 1) {
+    if (!ds->sk) return fail(SLM_ERR_UNSUPPORTED, "route 1: no split pass for p = %lld", (long long)p);
+    SLM_TRY(ensure_xt(kn, ds));
+    if (!split_usable(kn, ds) || (B > SPLIT_LANES && !(ds->XT && ds->XT_ready)))
+      return fail(SLM_ERR_UNSUPPORTED, "route 1: no residual kernel for %d lanes at p = %lld without the column-major copy", B, (long long)p);
+    if (!gather_x && !(ds->XT && ds->XT_ready)) return fail(SLM_ERR_UNSUPPORTED, "no column-major copy of X to gather from");
+  }
+  // host copies (and their device image, synchronously: the host buffers are short-lived)
+  auto put = [&](void* dst, const void* src, size_t bytes) -> int {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SLM_OK;
+  };
+  auto get = [&](void* dst, const void* src, size_t bytes) -> int {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SLM_OK;
+  };
+  LaneSetup ls = default_lanes(ds, B);
+  if (o->row_weights) {
+    if (!ds->rw_lanes) SLM_TRY(dalloc(&ds->rw_lanes, (size_t)ds->lane_cap * n));
+    SLM_TRY(put(ds->rw_lanes, o->row_weights, sizeof(double) * (size_t)B * n));
+    ls.rw = ds->rw_lanes;
+    ls.rw_stride = n;
+  }
+  if (o->n_eff)
+    for (int l = 0; l < B; ++l) ls.n_eff[l] = o->n_eff[l];
+  // row sets: lanes with the same row weights and n_eff (route 2: the same covariance entry)
+  int set_of[kMaxLanes], set_lane[kMaxLanes], n_sets = 0;
+  for (int l = 0; l < B; ++l) {
+    int found = -1;
+    for (int m = 0; m < l && found < 0; ++m) {
+      const bool same = route == 2 ? o->cov_index[m] == o->cov_index[l]
+                                   : ls.n_eff[m] == ls.n_eff[l] &&
+                                         (!o->row_weights || memcmp(o->row_weights + (size_t)m * n, o->row_weights + (size_t)l * n,
+                                                                    sizeof(double) * (size_t)n) == 0);
+      if (same) found = set_of[m];
+    }
+    if (found < 0) {
+      found = n_sets;
+      set_lane[n_sets++] = l;
+    }
+    set_of[l] = found;
+  }
+  // ---- buffers and arguments as a solve makes them
+  const WsBlocks wb = ws_row_blocks(ds, ls.rw != nullptr && n_sets > 1, n_sets);
+  SLM_TRY(ws_alloc(kn, ds, n_sets, wb.most, false));
+  WsArgs wa;
+  memset(&wa, 0, sizeof(wa));
+  SLM_TRY(ws_bind(kn, ds, ls, set_of, set_lane, n_sets, wb.nblk, false, wa, s));
+  if (gather_x) wa.XT = nullptr;  // (what a dataset without the memory for the copy gathers from)
+  std::string names;
+  auto named = [&](const char* k) {
+    if (!names.empty()) names += ';';
+    names += k;
+  };
+  if (wa.owner) named("ws_block_owner_kernel");
+  CovSets cs;
+  memset(&cs, 0, sizeof(cs));
+  if (route == 2)
+    for (int st = 0; st < n_sets; ++st) cs.G[st] = ds->cov[(size_t)o->cov_index[set_lane[st]]].G;
+  // NaN in everything the builds are to write (the gathered columns, the Grams, X_W^T y in g): what they leave out shows
+  HIP_TRY(hipMemsetAsync(ds->ws_XW, 0xff, sizeof(double) * (size_t)n * WS_KCAP, s));
+  HIP_TRY(hipMemsetAsync(ds->ws_G, 0xff, sizeof(double) * (size_t)n_sets * WS_KCAP * WS_KCAP, s));
+  HIP_TRY(hipMemsetAsync(ds->g, 0xff, sizeof(double) * (size_t)(ld + 16) * B, s));
+  HIP_TRY(hipMemsetAsync(&ds->gctl->done, 0, sizeof(int32_t), s));
+  // the state of a fresh solve (ws_ctl_init_kernel)
+  WsCtl* h = new WsCtl;
+  std::unique_ptr<WsCtl> h_hold(h);
+  memset(h, 0, sizeof(WsCtl));
+  h->request = 1;
+  h->max_builds = kWsMaxBuilds;
+  for (int l = 0; l < SLM_MAX_LANES; ++l) h->last_point[l] = -1;
+  std::vector<int32_t> h_idx(WS_KCAP), h_gs(WS_KCAP), h_gl(WS_KCAP, 1), h_pos((size_t)ld, -1);
+  for (int k = 0; k < WS_KCAP; ++k) h_gs[(size_t)k] = k;
+  for (int b = 0; b < nb; ++b) {
+    // what ws_select_kernel publishes (ws_kernels.hpp: the positions, then Kreal / K / k_new and the build flags)
+    const int k_old = b > 0 ? o->k_end[b - 1] : 0, kr = o->k_end[b];
+    for (int k = 0; k < WS_KCAP; ++k) h_idx[(size_t)k] = k < kr ? o->cols[k] : -1;
+    for (int k = k_old; k < kr; ++k) h_pos[(size_t)o->cols[k]] = k;
+    h->Kreal = kr;
+    h->K = std::max(16, (kr + 15) & ~15);
+    h->k_new = k_old;
+    h->building = 1;
+    h->valid = 0;
+    h->stale = 0;
+    h->counter = 0;
+    if (b > 0) h->appends += 1;
+    else h->builds += 1;
+    SLM_TRY(put(ds->ws_idx, h_idx.data(), sizeof(int32_t) * WS_KCAP));
+    SLM_TRY(put(ds->ws_gs, h_gs.data(), sizeof(int32_t) * WS_KCAP));
+    SLM_TRY(put(ds->ws_gl, h_gl.data(), sizeof(int32_t) * WS_KCAP));
+    SLM_TRY(put(ds->ws_pos, h_pos.data(), sizeof(int32_t) * (size_t)ld));
+    SLM_TRY(put(ds->ws_ctl, h, sizeof(WsCtl)));
+    WsNames wn;
+    ws_enqueue_build(ds, wa, route == 2 ? &cs : nullptr, xty, &ds->gctl->done, B, s, &wn);
+    for (int u = 0; u < wn.n; ++u) named(wn.k[u]);
+    SLM_TRY(check_launch());
+    SLM_TRY(get(h, ds->ws_ctl, sizeof(WsCtl)));
+    if (h->valid != 1 || h->building != 0 || h->counter != 0)
+      return fail(SLM_ERR_HIP, "build %d: the Gram was not published (valid %d, building %d, counter %d)", b, h->valid, h->building,
+                  h->counter);
+  }
+  // ---- what the builds made
+  if (gram_out)
+    for (int st = 0; st < n_sets; ++st)
+      HIP_TRY(hipMemcpy2DAsync(gram_out + (size_t)st * K * K, sizeof(double) * K, ds->ws_G + (size_t)st * WS_KCAP * WS_KCAP,
+                               sizeof(double) * WS_KCAP, sizeof(double) * K, K, hipMemcpyDeviceToHost, s));
+  if (xw_out)
+    HIP_TRY(hipMemcpy2DAsync(xw_out, sizeof(double) * K, ds->ws_XW, sizeof(double) * WS_KCAP, sizeof(double) * K, n,
+                             hipMemcpyDeviceToHost, s));
+  if (xty) {
+    std::vector<double> g0((size_t)ld + 16);
+    SLM_TRY(get(g0.data(), ds->g, sizeof(double) * (size_t)(ld + 16)));
+    for (int k = 0; k < kreal; ++k) xty_out[k] = g0[(size_t)o->cols[k]];
+    xty_out[kreal] = g0[(size_t)ld];
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  // ---- one pass on W: the lanes' control blocks (live; on W where asked -- PathCtl::zsup; at zero where they are --
+  //      PathCtl::zzero) and points, zero beyond p and in the unused lane slots
+  std::vector<PathCtl> hc((size_t)B);
+  memset(hc.data(), 0, sizeof(PathCtl) * (size_t)B);
+  for (int l = 0; l < B; ++l) {
+    hc[(size_t)l].zsup = (o->on_ws && o->on_ws[l]) ? 1 : 0;
+    hc[(size_t)l].zzero = zzero[(size_t)l];
+    hc[(size_t)l].tail_pt = -1;
+  }
+  SLM_TRY(put(ds->ctl, hc.data(), sizeof(PathCtl) * (size_t)B));
+  const int slots = SPLIT_LANES * ((B + SPLIT_LANES - 1) / SPLIT_LANES);
+  HIP_TRY(hipMemsetAsync(ds->z, 0, sizeof(double) * (size_t)slots * ld, s));
+  HIP_TRY(hipMemcpy2DAsync(ds->z, sizeof(double) * ld, o->Z, sizeof(double) * p, sizeof(double) * p, B, hipMemcpyHostToDevice, s));
+  GradNames gn;
+  if (route == 1) {
+    SLM_TRY(enqueue_gradient_split(kn, ds, ls, ds->y, nullptr, ds->ctl, &wa, nullptr, nullptr, 0, false, nullptr, &gn));
+  } else {
+    if (!ds->cov_Z) SLM_TRY(dalloc(&ds->cov_Z, (size_t)ld * SPLIT_RSTRIDE * SPLIT_HALVES));
+    SLM_TRY(enqueue_gradient_cov(ds, B, o->cov_index, nullptr, nullptr, nullptr, ds->ctl, &wa, &gn));
+  }
+  SLM_TRY(check_launch());
+  HIP_TRY(hipStreamSynchronize(s));
+  const size_t lane_bytes = sizeof(double) * (size_t)(ld + 16);
+  HIP_TRY(hipMemcpy2D(G_out, sizeof(double) * p, ds->g, lane_bytes, sizeof(double) * p, B, hipMemcpyDeviceToHost));
+  if (loss_out) HIP_TRY(hipMemcpy2D(loss_out, sizeof(double), ds->g + ld, lane_bytes, sizeof(double), B, hipMemcpyDeviceToHost));
+  if (set_of_out)
+    for (int l = 0; l < B; ++l) set_of_out[l] = set_of[l];
+  if (n_sets_out) *n_sets_out = n_sets;
+  if (route == 1) {
+    if (gn.resid) named(gn.resid);
+    if (gn.ws_resid) named(gn.ws_resid);
+    if (gn.product) named(gn.product);
+  } else if (gn.product) {
+    // the listed product (cov_kernels.hpp: only W's rows of G) where every lane of a row set is on W and the list fits the grid:
+    // the kernel's own test, on the flags this call set
+    bool listed = gn.cov_rows_ws > 0 && (int64_t)gn.cov_rows_ws * gn.cov_row_blocks >= K;
+    for (int l = 0; l < B; ++l) listed = listed && o->on_ws && o->on_ws[l];
+    named(gn.product);
+    if (listed) names += "+listed";
+  }
+  if (kernels_out && kernels_len > 0) snprintf(kernels_out, (size_t)kernels_len, "%s", names.c_str());
+  return SLM_OK;
 }

@@ -56,7 +56,7 @@ static_assert(kTwoPassC == 4, "the name of kGradTwoPass");
 // the column-major copy of X (`rowdot == nullptr`: the split pass is then only used when that copy exists).
 #define SLM_SK(C, D)                                                                                   \
   {8, C, SPLIT_LANES, D, rowdot_ring_kernel<8, C, ROWDOT_LANES, D>, resid_ws_kernel<SPLIT_LANES>, "rowdot_ring_kernel<8," #C ",5," #D ">"}
-static_assert(ROWDOT_LANES == 5, "the names of kSplit");
+static_assert(ROWDOT_LANES == 5 && SPLIT_LANES == 16, "the names of kSplit and of its residual kernel");
 static const SplitKernel kSplit[] = {SLM_SK(1, 3), SLM_SK(2, 3), SLM_SK(3, 3), SLM_SK(4, 3), SLM_SK(5, 2)};
 // Rows beyond 5120 columns, ANY width (round 6; until then the table stopped at 10 240 columns and wider rows had one lane on
 // the two-pass kernels, at most half of the roofline by construction): nothing in the split pass depends on the row length --
@@ -109,13 +109,17 @@ int launch_xtr(const slm_host::Knobs& kn, int cus, SplitArgs& a, hipStream_t s, 
 
 // the product of a covariance pass (cov_gz_mfma_kernel): xtr_mfma_kernel's grid; when only the working set's rows are read a
 // workgroup row takes the next multiple of four of WS_KCAP / row blocks list entries (at most 32: eight steps in registers)
-static int launch_cov_gz(int cus, SplitArgs& a, hipStream_t s, const CovBatch& cb, int n_sets, const char** name) {
+static int launch_cov_gz(int cus, SplitArgs& a, hipStream_t s, const CovBatch& cb, int n_sets, GradNames* names) {
   const slm_host::XtrGrid g = slm_host::xtr_grid(a.n, a.ld, XTR_CB, xtr_max_row_blocks(cus, a.ld) / 2);
   const int xb = g.xb, yb = g.yb;
   a.xrows = g.rows;
   const int per = ((WS_KCAP + yb - 1) / yb + 3) / 4 * 4;
   a.xrows_ws = (a.ctl != nullptr && per <= 32) ? per : 0;
-  if (name) *name = a.r_plane != 0 ? "cov_gz32_mfma_kernel" : "cov_gz_mfma_kernel";
+  if (names) {
+    names->product = a.r_plane != 0 ? "cov_gz32_mfma_kernel" : "cov_gz_mfma_kernel";
+    names->cov_rows_ws = a.xrows_ws;
+    names->cov_row_blocks = yb;
+  }
   if (a.r_plane != 0) hipLaunchKernelGGL(cov_gz32_mfma_kernel, dim3(xb, yb, (unsigned)n_sets), dim3(XTR_WAVES * 64), 0, s, a, cb);  // (both halves)
   else hipLaunchKernelGGL(cov_gz_mfma_kernel, dim3(xb, yb, (unsigned)n_sets), dim3(XTR_WAVES * 64), 0, s, a, cb);
   return yb;
@@ -284,9 +288,11 @@ int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const Lan
   if (unit) HIP_TRY(hipEventRecord(ev_start, s));
   launch_rowdot(kn, ds, sk, nblk, ls.B, a, s, names ? &names->resid : nullptr);
   if (wa && ctl) {  // residuals from the gathered columns: matrix cores (SLM_RESID_VEC=1: a row per thread)
-    if (kn.resid_vec && halves == 1) hipLaunchKernelGGL(sk->resid, dim3(nblk), dim3(256), 0, s, a);
-    else if (halves == 2) hipLaunchKernelGGL(resid32_mfma_kernel, dim3(nblk, 1), dim3(RM_WAVES * 64), 0, s, a);  // (both halves on one read of the gathered columns)
-    else hipLaunchKernelGGL(resid_mfma_kernel, dim3(nblk, halves), dim3(RM_WAVES * 64), 0, s, a);
+    const char* nm;
+    if (kn.resid_vec && halves == 1) { hipLaunchKernelGGL(sk->resid, dim3(nblk), dim3(256), 0, s, a); nm = "resid_ws_kernel<16>"; }
+    else if (halves == 2) { hipLaunchKernelGGL(resid32_mfma_kernel, dim3(nblk, 1), dim3(RM_WAVES * 64), 0, s, a); nm = "resid32_mfma_kernel"; }  // (both halves on one read of the gathered columns)
+    else { hipLaunchKernelGGL(resid_mfma_kernel, dim3(nblk, halves), dim3(RM_WAVES * 64), 0, s, a); nm = "resid_mfma_kernel"; }
+    if (names) names->ws_resid = nm;
   }
   // (SLM_FLAG_PROFILE brackets the kernel that streams X, the one the roofline is quoted on)
   if (ev_start && !unit) HIP_TRY(hipEventRecord(ev_start, s));
@@ -363,7 +369,7 @@ int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int*
   // (more than sixteen lanes: both planes of Z against ONE read of every Gram -- cov_gz32_mfma_kernel)
   a.lane0 = 0;
   a.r_plane = halves > 1 ? ld * SPLIT_RSTRIDE : 0;
-  const int xblk = launch_cov_gz(ds->eng->cus, a, s, cb, n_sets, names ? &names->product : nullptr);
+  const int xblk = launch_cov_gz(ds->eng->cus, a, s, cb, n_sets, names);
   CovFinishArgs f;
   f.partial = partial; f.z = ds->z; f.g = ds->g; f.done = done; f.nblk = xblk; f.ld = ld;
   hipLaunchKernelGGL(cov_reduce_kernel, dim3((unsigned)(ld / 16), (unsigned)B), dim3(256), 0, s, f, cb);

@@ -45,7 +45,7 @@ FLAG_PROFILE_UNIT = 1024  # with FLAG_PROFILE: the event bracket spans residuals
 FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plain steps, no rounds on the model Gram (csrc/mg_kernels.hpp)
 
 COMM_ID_BYTES = 128
-ABI_VERSION = 21  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
+ABI_VERSION = 22  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -77,6 +77,7 @@ ABI_SYMBOLS = (
     "slm_gradient",
     "slm_gradient_ex",
     "slm_gradient_lanes",
+    "slm_working_set_lanes",
     "slm_eval_sse",
     "slm_eval_sse_sparse",
     "slm_dense_spd_solve",
@@ -122,6 +123,16 @@ class _PenaltyStruct(C.Structure):
 class _GradientOpts(C.Structure):
     _fields_ = [("route", C.c_int32), ("n_lanes", C.c_int32), ("lane_out", C.c_int32), ("probe_lanes", C.c_int32),
                 ("xtr_only", C.c_int32)]
+
+
+WSL_GATHER_X = 1  # slm_working_set_lanes: gather from the row-major X, not the column-major copy
+WSL_XTY = 2       # ... and queue the ws_xty kernels with every build
+
+
+class _WsLanesOpts(C.Structure):
+    _fields_ = [("route", C.c_int32), ("n_lanes", C.c_int32), ("Z", C.c_void_p), ("on_ws", C.c_void_p),
+                ("row_weights", C.c_void_p), ("n_eff", C.c_void_p), ("cov_index", C.c_void_p), ("cols", C.c_void_p),
+                ("k_end", C.c_void_p), ("n_builds", C.c_int32), ("flags", C.c_uint32)]
 
 
 class _PathPoint(C.Structure):
@@ -287,6 +298,7 @@ def load_library():
             "slm_gradient": [vp, vp, vp, P(dbl), i32, P(dbl)],
             "slm_gradient_ex": [vp, vp, P(_GradientOpts), vp, P(dbl), i32, P(dbl)],
             "slm_gradient_lanes": [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, C.c_char_p, i32],
+            "slm_working_set_lanes": [vp, P(_WsLanesOpts), vp, vp, vp, vp, vp, vp, vp, C.c_char_p, i32],
             "slm_reload_knobs": [],
             "slm_eval_sse": [vp, vp, i32, vp, vp],
             "slm_eval_sse_sparse": [vp, vp, i32, vp, i32, vp, vp],
@@ -804,6 +816,49 @@ class Dataset:
         _check(self._lib.slm_gradient_lanes(self._h, int(route), B, _ptr(Z), _ptr(rw), _ptr(ne), _ptr(ci), int(n_rows),
                                             _ptr(G), _ptr(loss), names, len(names)))
         return G, loss, names.value.decode()
+
+    def working_set_lanes(self, Z, cols, k_end, on_ws=None, row_weights=None, n_eff=None, route: int = 1, cov_index=None,
+                          gather_from_x: bool = False, xty: bool = False, want_xw: bool = False):
+        """``slm_working_set_lanes``: W built in stages -- ``cols[:k_end[0]]``, then each ``cols[k_end[b-1]:k_end[b]]``
+        appended -- and one gradient pass of ``len(Z)`` lanes on it through route 1 (split pass; residuals from W for the
+        lanes with ``on_ws``) or 2 (covariance entries ``cov_index``).  Returns a namespace: ``G`` (lanes, p), ``loss``,
+        ``gram`` (row sets, K, K), ``set_of``, ``n_sets``, ``K``, ``XW`` (n, K) with ``want_xw``, ``xty`` (-X_W^T y / n) and
+        ``yy`` (y^T y / 2n) with ``xty``, and ``kernels``.  A call no kernel serves raises NotImplementedError."""
+        import types
+
+        _sync_knobs()
+        Z = _f64(np.atleast_2d(Z), "Z")
+        B = Z.shape[0]
+        if Z.shape[1] != self.p:
+            raise ValueError(f"Z must have {self.p} columns")
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        k_end = np.ascontiguousarray(np.atleast_1d(k_end), dtype=np.int32)
+        if k_end.size == 0 or cols.size < int(k_end[-1]):
+            raise ValueError("cols must hold k_end[-1] feature indices")
+        kreal = int(k_end[-1])
+        K = max(16, (kreal + 15) // 16 * 16)
+        ow = None if on_ws is None else np.ascontiguousarray(np.broadcast_to(np.asarray(on_ws, dtype=np.int32), (B,)))
+        rw = None if row_weights is None else _f64(row_weights, "row_weights", (B, self.n))
+        ne = None if n_eff is None else _f64(n_eff, "n_eff", (B,))
+        ci = None if cov_index is None else np.ascontiguousarray(cov_index, dtype=np.int32)
+        if ci is not None and ci.shape != (B,):
+            raise ValueError(f"cov_index has shape {ci.shape}, expected {(B,)}")
+        opts = _WsLanesOpts(int(route), B, _ptr(Z), _ptr(ow), _ptr(rw), _ptr(ne), _ptr(ci), _ptr(cols), _ptr(k_end),
+                            int(k_end.size), (WSL_GATHER_X if gather_from_x else 0) | (WSL_XTY if xty else 0))
+        G = np.empty((B, self.p))
+        loss = np.empty(B)
+        set_of = np.empty(B, dtype=np.int32)
+        n_sets = C.c_int32(0)
+        gram = np.empty((B, K, K))
+        XW = np.empty((self.n, K)) if want_xw else None
+        xt = np.empty(kreal + 1) if xty else None
+        names = C.create_string_buffer(4096)
+        _check(self._lib.slm_working_set_lanes(self._h, C.byref(opts), _ptr(G), _ptr(loss), _ptr(set_of), C.byref(n_sets),
+                                               _ptr(gram), _ptr(XW), _ptr(xt), names, len(names)))
+        ns = n_sets.value
+        return types.SimpleNamespace(G=G, loss=loss, gram=gram[:ns], set_of=set_of, n_sets=ns, K=K, XW=XW,
+                                     xty=None if xt is None else xt[:kreal], yy=None if xt is None else float(xt[kreal]),
+                                     kernels=names.value.decode())
 
     def eval_sse(self, Z, row_weight=None, sparse=None) -> np.ndarray:
         """sum_i w_i (x_i . Z[k] - y_i)^2 for every row Z[k] of ``Z`` (m, p); ``row_weight`` is e.g. the

@@ -21,6 +21,18 @@ The covariance route computes G_k z - c_k from a Gram of the lane's row set that
 minus that of the rows left out (engine_cov.hip): its rounding is relative to the rows of the minuend, so ``bound_weights``
 (max(w, 1), all rows) stand in for w in A and in the loss term.  ``gram_reference`` checks the same lanes against the Gram the
 engine holds, with a bound that involves no rows at all.
+
+The working set W (positions k < Kreal hold feature cols[k], K = max(16, Kreal rounded up to 16), the rest is padding) has a
+Gram of its own per row set, G = X_W^T diag(w) X_W / n_eff (ws_kernels.hpp), and at a sample start -X_W^T y / n and
+y^T y / 2n.  ``ws_gram_reference`` and ``ws_xty_reference`` give them with the bound of an n-term dot product:
+
+    |G_ij - ref| <= 2 (n + 16) eps * sum_r w_r |x_ri x_rj| / n_eff       (padding rows and columns: exactly 0)
+
+in any order of the row sums (row blocks, interleaved chains, a fixed-order fold of the blocks' partials) and whichever
+factor the weight is applied to.  A row block summed twice or left out, another row set's weights or n_eff, a stale tile
+row, an entry left unmirrored, float32 accumulation or a gathered column one position off are each far outside it
+(``tests/test_working_set_lanes_cpu.py``).  The gradient of a lane whose point is zero outside W is ``lanes_reference``'s
+whichever way the residual is formed (from X or from the gathered columns).
 """
 
 from __future__ import annotations
@@ -155,3 +167,129 @@ def lane_inputs(rng, n, p, B, n_rows=0, offset=0):
         sw = float(np.sum(W[l, :m]))
         ne[l] = (float(m), max(sw, 0.5), 0.73 * m + 1.5)[(l + offset) % 3]
     return Z, W, ne
+
+
+# ---- the working set ----------------------------------------------------------------------------------------------------------
+def ws_K(kreal):
+    """Columns of W in use with the padding: max(16, Kreal rounded up to a multiple of 16) (ws_select_kernel)."""
+    return max(16, (int(kreal) + 15) // 16 * 16)
+
+
+class GramReference:
+    """G (K, K) and its componentwise bound (0 on the padding: those entries must be exactly 0)."""
+
+    def __init__(self, G, bound, exact):
+        self.G, self.bound, self.exact = G, bound, exact
+
+
+def ws_gram_reference(X, cols, w=None, n_eff=None, chunk=8192) -> GramReference:
+    """X_W^T diag(w) X_W / n_eff for W = ``cols`` (w None: ones; n_eff None: n), padded to K; long double while n K <= 2e7."""
+    X = np.asarray(X, dtype=np.float64)
+    n = X.shape[0]
+    cols = np.asarray(cols, dtype=np.int64)
+    kr = cols.size
+    K = ws_K(kr)
+    w = np.ones(n) if w is None else np.asarray(w, dtype=np.float64).reshape(n)
+    ne = float(n) if n_eff is None else float(n_eff)
+    exact = n * K <= LONGDOUBLE_LIMIT
+    dt = np.longdouble if exact else np.float64
+    G = np.zeros((kr, kr), dtype=dt)
+    A = np.zeros((kr, kr))
+    for i0 in range(0, n, chunk):
+        i1 = min(n, i0 + chunk)
+        Xw = X[i0:i1][:, cols]
+        Xd = Xw.astype(dt)
+        G += Xd.T @ (w[i0:i1, None].astype(dt) * Xd)
+        Xa = np.abs(Xw)
+        A += Xa.T @ (w[i0:i1, None] * Xa)
+    k = 2.0 * (n + 16) * EPS * (1.0 if exact else 2.0)
+    Gp = np.zeros((K, K), dtype=dt)
+    Bp = np.zeros((K, K))
+    Gp[:kr, :kr] = G / dt(ne)
+    Bp[:kr, :kr] = k * A / ne
+    return GramReference(Gp, Bp, exact)
+
+
+def ws_xty_reference(X, y, cols):
+    """(c, c_bound, yy, yy_bound): c = -X_W^T y / n and yy = y^T y / 2n (the gradient and the loss at zero on W, as
+    ws_xty_partial / ws_xty_apply_kernel write them), with the same style of bound."""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    n = X.shape[0]
+    Xw = X[:, np.asarray(cols, dtype=np.int64)]
+    exact = n * max(1, Xw.shape[1]) <= LONGDOUBLE_LIMIT
+    dt = np.longdouble if exact else np.float64
+    k = 2.0 * (n + 16) * EPS * (1.0 if exact else 2.0)
+    c = -(Xw.astype(dt).T @ y.astype(dt)) / dt(n)
+    yy = (y.astype(dt) @ y.astype(dt)) / dt(2 * n)
+    return c, k * (np.abs(Xw).T @ np.abs(y)) / n, yy, k * float(y @ y) / (2 * n)
+
+
+def gram_excess(G, ref: GramReference):
+    """The largest |error| / bound over the entries (> 1: outside the bound; a padding entry that is not 0: inf)."""
+    G = np.asarray(G, dtype=np.float64)
+    err = np.abs(G.astype(np.longdouble) - ref.G).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(ref.bound > 0, err / ref.bound, np.where(err > 0, np.inf, 0.0))
+    r = np.where(np.isnan(G), np.inf, r)
+    return float(np.max(r))
+
+
+def assert_gram_within_bound(G, ref: GramReference, what=""):
+    e = gram_excess(G, ref)
+    assert e <= 1.0, f"{what}: the Gram is outside the componentwise bound (largest error / bound {e})"
+
+
+def assert_xty_within_bound(c, yy, ref, what=""):
+    rc, bc, ryy, byy = ref
+    ec = np.abs(np.asarray(c, dtype=np.float64).astype(np.longdouble) - rc).astype(np.float64)
+    assert np.all(ec <= bc), f"{what}: X_W^T y outside the bound at positions {np.flatnonzero(ec > bc).tolist()[:8]}"
+    assert abs(np.longdouble(yy) - ryy) <= byy, f"{what}: y^T y / 2n = {yy!r}, reference {float(ryy)!r}"
+
+
+# ---- which kernels a call of slm_working_set_lanes launches (a mirror of engine_path.hip / engine_solve.hip) ----------------
+SPLIT_RING = [(C, 3 if C < 5 else 2) for C in (1, 2, 3, 4, 5)]  # rowdot_ring_kernel<8, C, 5, D>: rows of up to 512 C columns
+
+
+def ws_build_expected(k_end, route=1, xty=False, owner=False):
+    """The build kernels: ws_block_owner_kernel once (lanes with row weights, unless SLM_NO_GRAM_OWNER), then per build
+    gather (+ xty) + Gram + reduce -- or ws_gram_cov_kernel under covariance passes."""
+    names = ["ws_block_owner_kernel"] if owner and route == 1 else []
+    for _ in k_end:
+        if route == 2:
+            names.append("ws_gram_cov_kernel")
+        else:
+            names += ["ws_gather_kernel"] + (["ws_xty_partial_kernel", "ws_xty_apply_kernel"] if xty else []) + \
+                     ["ws_gram_kernel", "ws_gram_reduce_kernel"]
+    return names
+
+
+def ws_pass_expected(p, B, resid_vec=False, ring=None):
+    """The pass of route 1 with control blocks: the residuals from X (launch_rowdot: the ring kernel for up to five lanes,
+    or SLM_ROWDOT_RING=1, where one covers p; the matrix-core kernels on the column-major copy otherwise), the residuals
+    from W (resid_ws_kernel with SLM_RESID_VEC=1 for up to sixteen lanes, resid_mfma_kernel, resid32_mfma_kernel for
+    more), then X^T R (launch_xtr)."""
+    p2 = (p + 15) // 16 * 16 // 2
+    ring_kernel = next((f"rowdot_ring_kernel<8,{C},5,{D}>" for C, D in SPLIT_RING if 512 * C >= p2), None)
+    halves = 1 if B <= 16 else 2
+    use_ring = ring_kernel is not None and halves == 1 and (ring == "1" if ring in ("0", "1") else B <= 5)
+    if use_ring:
+        rowdot = ring_kernel
+    elif halves == 1:
+        rowdot = "rowdot_mfma_kernel"
+    else:
+        rowdot = "rowdot18_mfma_kernel" if B <= 18 else "rowdot20_mfma_kernel" if B <= 20 else "rowdot32_mfma_kernel"
+    if halves == 2:
+        resid = "resid32_mfma_kernel"
+    else:
+        resid = "resid_ws_kernel<16>" if resid_vec else "resid_mfma_kernel"
+    product = "xtr_mfma_kernel" if halves == 1 else \
+        "xtr18_mfma_kernel" if B <= 18 else "xtr20_mfma_kernel" if B <= 20 else "xtr32_mfma_kernel"
+    return [rowdot, resid, product]
+
+
+def ws_gram_mapping(k_new, K):
+    """ws_gram_kernel's mapping for a build: "row-split" (a fresh selection of up to 8 tiles, or an append, when the new
+    tile rows are at most 16) or "generic"."""
+    tile_lo, tiles = int(k_new) >> 4, int(K) >> 4
+    return "row-split" if (tile_lo > 0 or tiles <= 8) and tiles - tile_lo <= 16 else "generic"

@@ -39,6 +39,7 @@ _STRUCTS = {
     "slm_point_info": "_PointInfo",
     "slm_solve_stats": "_SolveStats",
     "slm_lane": "_Lane",
+    "slm_ws_lanes_opts": "_WsLanesOpts",
 }
 
 
