@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SLM_ABI_VERSION 22
+#define SLM_ABI_VERSION 23
 
 typedef enum slm_status {
   SLM_OK = 0,
@@ -236,6 +236,71 @@ typedef struct slm_ws_lanes_opts {
 int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* opts, double* G_out, double* loss_out, int32_t* set_of_out,
                           int32_t* n_sets_out, double* gram_out, double* xw_out, double* xty_out, char* kernels_out,
                           int32_t kernels_len);
+
+/*
+ * Diagnostic: the working-set MODEL SOLVER alone, on a model the caller supplies -- how the tests check that it minimises
+ *   m(x) = gprev_W . (x - zprev)_W + 1/2 (x - zprev)_W^T G (x - zprev)_W + pen(x)
+ * on W and writes its point back as documented.  No X is read: the dataset carries p, ld, the groups and nothing else.
+ *   cols[0 : kreal] are W's feature indices (distinct, kreal <= 512; on a dataset with groups: whole groups, each contiguous).
+ *   gram is [n_sets][K][K], K = max(16, kreal rounded up to 16), zero on the padding; lane l uses gram[set_of[l]].
+ *   Per lane: the expansion point zprev, its gradient gprev, the start z, the penalty vectors a0 [p], b0 / d0 [G] (G = p without
+ *   groups), ONE path point (sa, sb, sd), tol and mode (0: accelerated lane, 1: spectral lane).  Lane l's path point has
+ *   number l (what last_point is compared with).
+ * The control blocks are set as ws_select_kernel and a solve leave them (valid, K, Kreal, idx = -1 on the padding, pos, gs, gl);
+ * beta and everything else the solver is to write is filled with NaN; then exactly the launches of a pass's refinement are
+ * queued (ws_solve_kernel<GROUPED, 0>, then <GROUPED, 1> with SLM_WMS_DIRECT; SLM_WS_ONE_SOLVER / SLM_WS_BB as in a solve).
+ * Inputs must be finite, except gram and gprev under SLM_WMS_NONFINITE.  SLM_ERR_BAD_ARG for anything else,
+ * SLM_ERR_UNSUPPORTED for row-sharded datasets.  No reference counterpart (tests only).
+ */
+#define SLM_WMS_DIRECT 1u     /* direct steps allowed (WsArgs::nt set: the second launch) */
+#define SLM_WMS_HARD 2u       /* "start hard": WsCtl::hard_lane (and hard) preset */
+#define SLM_WMS_INVALID 4u    /* WsCtl::valid = 0 */
+#define SLM_WMS_BUILDING 8u   /* WsCtl::building = 1 */
+#define SLM_WMS_DISABLED 16u  /* WsCtl::disabled = 1 */
+#define SLM_WMS_STALE 32u     /* WsCtl::stale = 1 */
+#define SLM_WMS_NONFINITE 64u /* gram and gprev may hold NaN / infinity */
+typedef struct slm_ws_model_opts {
+  int32_t n_lanes;           /* 1 .. SLM_MAX_LANES */
+  int32_t kreal;             /* 1 .. 512 */
+  const int32_t* cols;       /* [kreal] */
+  int32_t n_sets;            /* 1 .. n_lanes */
+  uint32_t flags;            /* SLM_WMS_* */
+  const double* gram;        /* [n_sets][K][K] */
+  const int32_t* set_of;     /* [n_lanes], NULL: all 0 */
+  const double* zprev;       /* [n_lanes][p] */
+  const double* gprev;       /* [n_lanes][p] */
+  const double* z;           /* [n_lanes][p] */
+  const double* a0;          /* [n_lanes][p] */
+  const double* b0;          /* [n_lanes][G] */
+  const double* d0;          /* [n_lanes][G] */
+  const double* points;      /* [n_lanes][3]: sa, sb, sd */
+  const double* tol;         /* [n_lanes] */
+  const int32_t* mode;       /* [n_lanes] */
+  const double* Lw;          /* [n_sets] WsCtl::Lw preset, NULL: 0 (the power iteration runs) */
+  const int32_t* repeats;    /* [n_lanes] WsCtl::repeats preset, NULL: 0 */
+  const int32_t* last_point; /* [n_lanes] WsCtl::last_point preset, NULL: -1 */
+  const int32_t* last_cols;  /* [n_lanes] WsCtl::last_cols preset, NULL: 0 */
+} slm_ws_model_opts;
+typedef struct slm_ws_model_out {
+  double* z;              /* [n_lanes][p] */
+  double* beta;           /* [n_lanes][p] */
+  int32_t* served;        /* [n_lanes] WsCtl::served */
+  double* mu;             /* [n_lanes] PathCtl::mu (preset -1) */
+  int32_t* zsup;          /* [n_lanes] PathCtl::zsup (preset -1) */
+  double* t;              /* [n_lanes] PathCtl::t (preset 7) */
+  int32_t* have_base;     /* [n_lanes] PathCtl::have_base (preset 1) */
+  int32_t* zzero;         /* [n_lanes] PathCtl::zzero (preset 1) */
+  int32_t* want_full;     /* [n_lanes] WsCtl::want_full as left behind */
+  int32_t* repeats;       /* [n_lanes] */
+  int32_t* hard_lane;     /* [n_lanes] */
+  int32_t* last_point;    /* [n_lanes] */
+  double* Lw;             /* [n_sets] */
+  int32_t* counters;      /* [8]: refined, inner_iters, newton_steps, newton_fails, newton_nopd, newton_factors, newton_unknowns,
+                             hard_next */
+  char* kernels;          /* every kernel launched, ';'-separated, in order (nullable) */
+  int32_t kernels_len;
+} slm_ws_model_out;
+int slm_working_set_model_solve(slm_dataset* ds, const slm_ws_model_opts* opts, slm_ws_model_out* out);
 
 /*
  * Weighted squared error of m coefficient vectors, as many per pass over X as the fused kernel

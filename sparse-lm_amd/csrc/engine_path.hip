@@ -1094,6 +1094,24 @@ static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* c
   if (names) { names->add("ws_gram_kernel"); names->add("ws_gram_reduce_kernel"); }
 }
 
+// The model solvers of a pass: the iteration alone, then -- for the lanes it left -- the solver with direct steps
+// (ws_refine_lane).  PathCall::enqueue_refinement and slm_working_set_model_solve; `names` (nullable): the kernels launched.
+static void ws_enqueue_solvers(const slm_dataset* ds, const TailArgs& ta, const WsArgs& wa, int B, hipStream_t s, WsNames* names = nullptr) {
+  if (wa.one_solver && wa.nt) {
+  } else if (ds->singleton) {
+    hipLaunchKernelGGL((ws_solve_kernel<false, 0>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
+    if (names) names->add("ws_solve_kernel<false,0>");
+  } else {
+    hipLaunchKernelGGL((ws_solve_kernel<true, 0>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
+    if (names) names->add("ws_solve_kernel<true,0>");
+  }
+  if (wa.nt) {
+    if (ds->singleton) hipLaunchKernelGGL((ws_solve_kernel<false, 1>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
+    else hipLaunchKernelGGL((ws_solve_kernel<true, 1>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
+    if (names) names->add(ds->singleton ? "ws_solve_kernel<false,1>" : "ws_solve_kernel<true,1>");
+  }
+}
+
 void PathCall::enqueue_refinement() {
   if (use_ws) {
     {
@@ -1117,16 +1135,7 @@ void PathCall::enqueue_refinement() {
       hipLaunchKernelGGL(ws_publish_kernel, dim3(WS_PUBLISH_BLOCKS, (unsigned)wa.n_sets), dim3(256), 0, s, wa);
       hipLaunchKernelGGL(stop_apply_kernel, dim3(1), dim3(64), 0, s, ta.gdone, wa.Gx + gram_words);
     }
-    // the iteration alone, then -- for the lanes it left -- the solver with direct steps (ws_refine_lane)
-    {
-      if (wa.one_solver && wa.nt) {
-      } else if (ds->singleton) hipLaunchKernelGGL((ws_solve_kernel<false, 0>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
-      else hipLaunchKernelGGL((ws_solve_kernel<true, 0>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
-      if (wa.nt) {
-        if (ds->singleton) hipLaunchKernelGGL((ws_solve_kernel<false, 1>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
-        else hipLaunchKernelGGL((ws_solve_kernel<true, 1>), dim3(B), dim3(WS_THREADS), 0, s, ta, wa);
-      }
-    }
+    ws_enqueue_solvers(ds, ta, wa, B, s);
   }
 }
 
@@ -1918,5 +1927,219 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
     if (listed) names += "+listed";
   }
   if (kernels_out && kernels_len > 0) snprintf(kernels_out, (size_t)kernels_len, "%s", names.c_str());
+  return SLM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Diagnostic: the working-set model solver alone, on a model the caller supplies (slm_engine.h).  The state is what
+// ws_select_kernel and a solve leave behind, the launches are a pass's own (ws_enqueue_solvers); no X is read.
+// ------------------------------------------------------------------------------------------------
+extern "C" int slm_working_set_model_solve(slm_dataset* ds, const slm_ws_model_opts* o, slm_ws_model_out* out) {
+  if (!ds || !o || !out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  if (!o->cols || !o->gram || !o->zprev || !o->gprev || !o->z || !o->a0 || !o->b0 || !o->d0 || !o->points || !o->tol || !o->mode)
+    return fail(SLM_ERR_BAD_ARG, "NULL input");
+  if (!out->z || !out->beta || !out->served || !out->mu || !out->zsup || !out->t || !out->have_base || !out->zzero ||
+      !out->want_full || !out->repeats || !out->hard_lane || !out->last_point || !out->Lw || !out->counters)
+    return fail(SLM_ERR_BAD_ARG, "NULL output");
+  const uint32_t known = SLM_WMS_DIRECT | SLM_WMS_HARD | SLM_WMS_INVALID | SLM_WMS_BUILDING | SLM_WMS_DISABLED | SLM_WMS_STALE |
+                         SLM_WMS_NONFINITE;
+  if (o->flags & ~known) return fail(SLM_ERR_BAD_ARG, "unknown flags %#x", o->flags);
+  const int B = o->n_lanes, kreal = o->kreal, n_sets = o->n_sets;
+  if (B < 1 || B > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "between 1 and %d lanes, got %d", kMaxLanes, B);
+  if (kreal < 1 || kreal > WS_KCAP) return fail(SLM_ERR_BAD_ARG, "between 1 and %d columns, got %d", WS_KCAP, kreal);
+  if (n_sets < 1 || n_sets > B) return fail(SLM_ERR_BAD_ARG, "between 1 and n_lanes Grams, got %d", n_sets);
+  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "slm_working_set_model_solve: row-sharded datasets");
+  if (B > ds->lane_cap) return fail(SLM_ERR_UNSUPPORTED, "%d lanes: the dataset holds %d", B, ds->lane_cap);
+  const int64_t p = ds->p, ld = ds->ld;
+  const int G = ds->singleton ? (int)p : ds->G;
+  const int K = std::max(16, (kreal + 15) & ~15);
+  const bool loose = (o->flags & SLM_WMS_NONFINITE) != 0;
+  // ---- W: distinct features; with real groups whole groups, each contiguous
+  std::vector<int32_t> h_pos((size_t)ld, -1), h_idx(WS_KCAP, -1), h_gs(WS_KCAP), h_gl(WS_KCAP, 1);
+  for (int k = 0; k < WS_KCAP; ++k) h_gs[(size_t)k] = k;
+  for (int k = 0; k < kreal; ++k) {
+    const int32_t j = o->cols[k];
+    if (j < 0 || j >= p) return fail(SLM_ERR_BAD_ARG, "cols[%d] = %d outside [0, %lld)", k, j, (long long)p);
+    if (h_pos[(size_t)j] >= 0) return fail(SLM_ERR_BAD_ARG, "cols[%d] = %d repeats cols[%d]", k, j, h_pos[(size_t)j]);
+    h_pos[(size_t)j] = k;
+    h_idx[(size_t)k] = j;
+  }
+  if (!ds->singleton) {
+    std::vector<int> size((size_t)G, 0);
+    for (int64_t j = 0; j < p; ++j) size[(size_t)ds->h_gid[(size_t)j]] += 1;
+    for (int k = 0; k < kreal;) {
+      const int g = ds->h_gid[(size_t)o->cols[k]], len = size[(size_t)g];
+      if (k + len > kreal) return fail(SLM_ERR_BAD_ARG, "cols: group %d (%d members) is split at position %d", g, len, k);
+      for (int m = 0; m < len; ++m) {
+        if (ds->h_gid[(size_t)o->cols[k + m]] != g) return fail(SLM_ERR_BAD_ARG, "cols: group %d (%d members) is split at position %d", g, len, k + m);
+        h_gs[(size_t)(k + m)] = k;
+        h_gl[(size_t)(k + m)] = len;
+      }
+      k += len;
+    }
+  }
+  // ---- the model and the lanes
+  auto finite = [](const double* v, size_t count) {
+    for (size_t e = 0; e < count; ++e)
+      if (!std::isfinite(v[e])) return false;
+    return true;
+  };
+  if (!loose && (!finite(o->gram, (size_t)n_sets * K * K) || !finite(o->gprev, (size_t)B * p)))
+    return fail(SLM_ERR_BAD_ARG, "gram / gprev contain a non-finite value");
+  if (!finite(o->zprev, (size_t)B * p) || !finite(o->z, (size_t)B * p) || !finite(o->a0, (size_t)B * p) ||
+      !finite(o->b0, (size_t)B * G) || !finite(o->d0, (size_t)B * G) || !finite(o->points, (size_t)B * 3) || !finite(o->tol, (size_t)B))
+    return fail(SLM_ERR_BAD_ARG, "zprev / z / a0 / b0 / d0 / points / tol contain a non-finite value");
+  if (o->Lw && !finite(o->Lw, (size_t)n_sets)) return fail(SLM_ERR_BAD_ARG, "Lw contains a non-finite value");
+  for (int st = 0; st < n_sets; ++st)
+    for (int r = 0; r < K; ++r)
+      for (int c = 0; c < K; ++c)
+        if ((r >= kreal || c >= kreal) && o->gram[((size_t)st * K + r) * K + c] != 0.0)
+          return fail(SLM_ERR_BAD_ARG, "gram[%d][%d][%d] on the padding is not zero", st, r, c);
+  for (int l = 0; l < B; ++l) {
+    if (o->set_of && (o->set_of[l] < 0 || o->set_of[l] >= n_sets)) return fail(SLM_ERR_BAD_ARG, "set_of[%d] = %d: %d Grams", l, o->set_of[l], n_sets);
+    if (o->mode[l] != 0 && o->mode[l] != 1) return fail(SLM_ERR_BAD_ARG, "mode[%d] = %d must be 0 or 1", l, o->mode[l]);
+    if (o->tol[l] < 0.0) return fail(SLM_ERR_BAD_ARG, "tol[%d] is negative", l);
+    for (int c = 0; c < 3; ++c)
+      if (o->points[3 * l + c] < 0.0) return fail(SLM_ERR_BAD_ARG, "points[%d][%d] is negative", l, c);
+  }
+  for (size_t e = 0; e < (size_t)B * p; ++e)
+    if (o->a0[e] < 0.0) return fail(SLM_ERR_BAD_ARG, "a0 is negative");
+  for (size_t e = 0; e < (size_t)B * G; ++e)
+    if (o->b0[e] < 0.0 || o->d0[e] < 0.0) return fail(SLM_ERR_BAD_ARG, "b0 / d0 is negative");
+  const slm_host::Knobs kn = knobs();
+  HIP_TRY(hipSetDevice(ds->eng->device));
+  hipStream_t s = ds->eng->stream;
+  HIP_TRY(hipStreamSynchronize(s));
+  // (what an earlier solve left on the device no longer describes it)
+  ds->carry_valid = false;
+  ds->ws_carry_valid = false;
+  // ---- buffers and arguments as a solve makes them
+  LaneSetup ls = default_lanes(ds, B);
+  int set_of[kMaxLanes], set_lane[kMaxLanes];
+  for (int st = 0; st < kMaxLanes; ++st) set_lane[st] = 0;
+  for (int l = B - 1; l >= 0; --l) {
+    set_of[l] = o->set_of ? o->set_of[l] : 0;
+    set_lane[set_of[l]] = l;
+  }
+  const WsBlocks wb = ws_row_blocks(ds, false, n_sets);
+  SLM_TRY(ws_alloc(kn, ds, n_sets, wb.most, false));
+  if (B > ds->cap_points) {
+    dfree(ds->pts); dfree(ds->betas_out); dfree(ds->infos);
+    ds->cap_points = 0;
+    SLM_TRY(dalloc(&ds->pts, (size_t)B));
+    SLM_TRY(dalloc(&ds->betas_out, (size_t)B * p));
+    SLM_TRY(dalloc(&ds->infos, (size_t)B));
+    ds->cap_points = B;
+  }
+  WsArgs wa;
+  memset(&wa, 0, sizeof(wa));
+  SLM_TRY(ws_bind(kn, ds, ls, set_of, set_lane, n_sets, wb.nblk, false, wa, s));
+  if (!(o->flags & SLM_WMS_DIRECT)) wa.nt = nullptr;
+  wa.bb_steps = kn.ws_bb;
+  wa.one_solver = kn.ws_one_solver;
+  wa.hard_call = kn.hard_callwide;
+  wa.power_iters = slm_host::kWsPowerIters;
+  TailArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  ta.ctl = ds->ctl;
+  ta.gdone = reinterpret_cast<int*>(ds->gctl);
+  ta.n_lanes = B;
+  ta.pts = ds->pts;
+  ta.p = (int)p;
+  ta.G = G;
+  ta.singleton = ds->singleton;
+  ta.team = ds->team;
+  ta.beta = ds->beta; ta.z = ds->z; ta.g = ds->g; ta.ld = ld; ta.zprev = ds->zprev; ta.gprev = ds->gprev;
+  ta.gscale = ds->gscale; ta.uscratch = ds->u;
+  ta.a0 = ds->a0; ta.b0 = ds->b0; ta.d0 = ds->d0;
+  ta.order = ds->order; ta.gid = ds->gid; ta.gstart = ds->gstart;
+  ta.betas_out = ds->betas_out; ta.infos = ds->infos;
+  // ---- device state: NaN in everything the inputs do not cover, then the inputs
+  const size_t lanes_ld = sizeof(double) * (size_t)B * ld, row = sizeof(double) * (size_t)p;
+  for (double* v : {ds->z, ds->beta, ds->zprev, ds->gprev, ds->a0, ds->b0, ds->d0}) HIP_TRY(hipMemsetAsync(v, 0xff, lanes_ld, s));
+  HIP_TRY(hipMemsetAsync(ds->ws_G, 0xff, sizeof(double) * (size_t)n_sets * WS_KCAP * WS_KCAP, s));
+  HIP_TRY(hipMemsetAsync(ds->gctl, 0, sizeof(GlobalCtl), s));
+  auto up2 = [&](double* dst, const double* src, size_t width) -> int {
+    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * ld, src, sizeof(double) * width, sizeof(double) * width, B, hipMemcpyHostToDevice, s));
+    return SLM_OK;
+  };
+  SLM_TRY(up2(ds->z, o->z, (size_t)p));
+  SLM_TRY(up2(ds->zprev, o->zprev, (size_t)p));
+  SLM_TRY(up2(ds->gprev, o->gprev, (size_t)p));
+  SLM_TRY(up2(ds->a0, o->a0, (size_t)p));
+  SLM_TRY(up2(ds->b0, o->b0, (size_t)G));
+  SLM_TRY(up2(ds->d0, o->d0, (size_t)G));
+  for (int st = 0; st < n_sets; ++st)
+    HIP_TRY(hipMemcpy2DAsync(ds->ws_G + (size_t)st * WS_KCAP * WS_KCAP, sizeof(double) * WS_KCAP, o->gram + (size_t)st * K * K,
+                             sizeof(double) * K, sizeof(double) * K, K, hipMemcpyHostToDevice, s));
+  std::vector<slm_path_point> h_pts((size_t)B);
+  std::vector<PathCtl> hc((size_t)B);
+  memset(hc.data(), 0, sizeof(PathCtl) * (size_t)B);
+  for (int l = 0; l < B; ++l) {
+    h_pts[(size_t)l].sa = o->points[3 * l]; h_pts[(size_t)l].sb = o->points[3 * l + 1]; h_pts[(size_t)l].sd = o->points[3 * l + 2];
+    h_pts[(size_t)l].extrap = 0.0;
+    PathCtl& c = hc[(size_t)l];
+    c.point = 0; c.n_points = 1; c.max_iter = 1; c.pt_off = l; c.pt_lo = 0; c.stride = 1; c.tail_pt = -1;
+    c.tol = o->tol[l]; c.mode = o->mode[l]; c.L = 1.0;
+    c.t = 7.0; c.have_base = 1; c.zzero = 1; c.zsup = -1; c.mu = -1.0;  // (what the solver is to write: slm_engine.h)
+  }
+  HIP_TRY(hipMemcpyAsync(ds->pts, h_pts.data(), sizeof(slm_path_point) * (size_t)B, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ds->ctl, hc.data(), sizeof(PathCtl) * (size_t)B, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ds->ws_idx, h_idx.data(), sizeof(int32_t) * WS_KCAP, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ds->ws_gs, h_gs.data(), sizeof(int32_t) * WS_KCAP, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ds->ws_gl, h_gl.data(), sizeof(int32_t) * WS_KCAP, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ds->ws_pos, h_pos.data(), sizeof(int32_t) * (size_t)ld, hipMemcpyHostToDevice, s));
+  std::unique_ptr<WsCtl> h(new WsCtl);
+  memset(h.get(), 0, sizeof(WsCtl));
+  h->valid = (o->flags & SLM_WMS_INVALID) ? 0 : 1;
+  h->building = (o->flags & SLM_WMS_BUILDING) ? 1 : 0;
+  h->disabled = (o->flags & SLM_WMS_DISABLED) ? 1 : 0;
+  h->stale = (o->flags & SLM_WMS_STALE) ? 1 : 0;
+  h->K = K;
+  h->Kreal = kreal;
+  h->k_new = kreal;
+  h->builds = 1;
+  h->max_builds = kWsMaxBuilds;
+  h->hard = (o->flags & SLM_WMS_HARD) ? 1 : 0;
+  for (int l = 0; l < SLM_MAX_LANES; ++l) {
+    h->last_point[l] = (l < B && o->last_point) ? o->last_point[l] : -1;
+    h->repeats[l] = (l < B && o->repeats) ? o->repeats[l] : 0;
+    h->last_cols[l] = (l < B && o->last_cols) ? o->last_cols[l] : 0;
+    h->hard_lane[l] = (l < B && (o->flags & SLM_WMS_HARD)) ? 1 : 0;
+    h->Lw[l] = (l < n_sets && o->Lw) ? o->Lw[l] : 0.0;
+  }
+  HIP_TRY(hipMemcpyAsync(ds->ws_ctl, h.get(), sizeof(WsCtl), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (the host buffers above are short-lived)
+  // ---- the launches of a pass's refinement
+  WsNames wn;
+  ws_enqueue_solvers(ds, ta, wa, B, s, &wn);
+  SLM_TRY(check_launch());
+  HIP_TRY(hipStreamSynchronize(s));
+  // ---- what they left
+  HIP_TRY(hipMemcpy2D(out->z, row, ds->z, sizeof(double) * ld, row, B, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy2D(out->beta, row, ds->beta, sizeof(double) * ld, row, B, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hc.data(), ds->ctl, sizeof(PathCtl) * (size_t)B, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.get(), ds->ws_ctl, sizeof(WsCtl), hipMemcpyDeviceToHost));
+  for (int l = 0; l < B; ++l) {
+    const PathCtl& c = hc[(size_t)l];
+    out->served[l] = h->served[l];
+    out->mu[l] = c.mu; out->zsup[l] = c.zsup; out->t[l] = c.t; out->have_base[l] = c.have_base; out->zzero[l] = c.zzero;
+    out->want_full[l] = h->want_full[l];
+    out->repeats[l] = h->repeats[l]; out->hard_lane[l] = h->hard_lane[l]; out->last_point[l] = h->last_point[l];
+  }
+  for (int st = 0; st < n_sets; ++st) out->Lw[st] = h->Lw[st];
+  const int32_t counters[8] = {h->refined, h->inner_iters, h->newton_steps, h->newton_fails,
+                               h->newton_nopd, h->newton_factors, h->newton_unknowns, h->hard_next};
+  memcpy(out->counters, counters, sizeof(counters));
+  if (out->kernels && out->kernels_len > 0) {
+    std::string names;
+    for (int u = 0; u < wn.n; ++u) {
+      if (u) names += ';';
+      names += wn.k[u];
+    }
+    snprintf(out->kernels, (size_t)out->kernels_len, "%s", names.c_str());
+  }
+  // (the control block describes a working set no solve built: the next solve selects afresh)
+  HIP_TRY(hipMemset(ds->ws_ctl, 0, sizeof(WsCtl)));
   return SLM_OK;
 }

@@ -46,7 +46,14 @@ constexpr int WS_MAX_REPEATS = 6;   // refinements of one path point before the 
 // on the free coordinates (Cholesky solve, see `direct_step`) replaces further iterations; one prox-gradient
 // step after it tests convergence, and the next direct step follows at once if that fails.
 constexpr int WS_NEWTON_AFTER = 16;
-constexpr int WS_NEWTON_MAX = 64;    // direct steps per refinement
+// Direct steps per refinement.  Where the projected trial points do not lower the model (ill-conditioned faces: the projection
+// destroys the cancellations the direction lives on) a step is the straight segment to the first sign change, i.e. ONE
+// coordinate changes sides per step, and a start that is not yet on the minimiser's face needs about as many steps as the
+// face has positions: 129 from a start with 80 of 120 coordinates non-zero to a minimiser with 30 (per-feature penalty,
+// condition 1e8, direct mode from the first iteration; tests/test_model_solver_gpu.py::test_start_hard).  Until this was 256 it
+// was 64: that solve ended unsettled, and so did the next five refinements of such a point -- the same steps in all, with a
+// pass over X between every 64 of them.  WS_INNER_MAX bounds the steps of a refinement as before.
+constexpr int WS_NEWTON_MAX = 256;
 constexpr int WS_AFTER_DIRECT = 40;  // iterations left to a refinement whose direct steps are used up: on a face that
                                      // needed them more would not converge either -- the next pass re-expands the model
                                      // at the point reached and the refinement resumes from there

@@ -45,7 +45,7 @@ FLAG_PROFILE_UNIT = 1024  # with FLAG_PROFILE: the event bracket spans residuals
 FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plain steps, no rounds on the model Gram (csrc/mg_kernels.hpp)
 
 COMM_ID_BYTES = 128
-ABI_VERSION = 22  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
+ABI_VERSION = 23  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -78,6 +78,7 @@ ABI_SYMBOLS = (
     "slm_gradient_ex",
     "slm_gradient_lanes",
     "slm_working_set_lanes",
+    "slm_working_set_model_solve",
     "slm_eval_sse",
     "slm_eval_sse_sparse",
     "slm_dense_spd_solve",
@@ -133,6 +134,27 @@ class _WsLanesOpts(C.Structure):
     _fields_ = [("route", C.c_int32), ("n_lanes", C.c_int32), ("Z", C.c_void_p), ("on_ws", C.c_void_p),
                 ("row_weights", C.c_void_p), ("n_eff", C.c_void_p), ("cov_index", C.c_void_p), ("cols", C.c_void_p),
                 ("k_end", C.c_void_p), ("n_builds", C.c_int32), ("flags", C.c_uint32)]
+
+
+# slm_working_set_model_solve flags
+WMS_DIRECT, WMS_HARD, WMS_INVALID, WMS_BUILDING, WMS_DISABLED, WMS_STALE, WMS_NONFINITE = 1, 2, 4, 8, 16, 32, 64
+WMS_COUNTERS = ("refined", "inner_iters", "newton_steps", "newton_fails", "newton_nopd", "newton_factors", "newton_unknowns",
+                "hard_next")
+
+
+class _WsModelOpts(C.Structure):
+    _fields_ = [("n_lanes", C.c_int32), ("kreal", C.c_int32), ("cols", C.c_void_p), ("n_sets", C.c_int32), ("flags", C.c_uint32),
+                ("gram", C.c_void_p), ("set_of", C.c_void_p), ("zprev", C.c_void_p), ("gprev", C.c_void_p), ("z", C.c_void_p),
+                ("a0", C.c_void_p), ("b0", C.c_void_p), ("d0", C.c_void_p), ("points", C.c_void_p), ("tol", C.c_void_p),
+                ("mode", C.c_void_p), ("Lw", C.c_void_p), ("repeats", C.c_void_p), ("last_point", C.c_void_p),
+                ("last_cols", C.c_void_p)]
+
+
+class _WsModelOut(C.Structure):
+    _fields_ = [("z", C.c_void_p), ("beta", C.c_void_p), ("served", C.c_void_p), ("mu", C.c_void_p), ("zsup", C.c_void_p),
+                ("t", C.c_void_p), ("have_base", C.c_void_p), ("zzero", C.c_void_p), ("want_full", C.c_void_p),
+                ("repeats", C.c_void_p), ("hard_lane", C.c_void_p), ("last_point", C.c_void_p), ("Lw", C.c_void_p),
+                ("counters", C.c_void_p), ("kernels", C.c_void_p), ("kernels_len", C.c_int32)]
 
 
 class _PathPoint(C.Structure):
@@ -299,6 +321,7 @@ def load_library():
             "slm_gradient_ex": [vp, vp, P(_GradientOpts), vp, P(dbl), i32, P(dbl)],
             "slm_gradient_lanes": [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, C.c_char_p, i32],
             "slm_working_set_lanes": [vp, P(_WsLanesOpts), vp, vp, vp, vp, vp, vp, vp, C.c_char_p, i32],
+            "slm_working_set_model_solve": [vp, P(_WsModelOpts), P(_WsModelOut)],
             "slm_reload_knobs": [],
             "slm_eval_sse": [vp, vp, i32, vp, vp],
             "slm_eval_sse_sparse": [vp, vp, i32, vp, i32, vp, vp],
@@ -859,6 +882,71 @@ class Dataset:
         return types.SimpleNamespace(G=G, loss=loss, gram=gram[:ns], set_of=set_of, n_sets=ns, K=K, XW=XW,
                                      xty=None if xt is None else xt[:kreal], yy=None if xt is None else float(xt[kreal]),
                                      kernels=names.value.decode())
+
+    def working_set_model_solve(self, cols, gram, zprev, gprev, z, a0, b0, d0, points, tol, mode, set_of=None, Lw=None,
+                                direct: bool = True, hard: bool = False, invalid: bool = False, building: bool = False,
+                                disabled: bool = False, stale: bool = False, allow_nonfinite: bool = False, repeats=None,
+                                last_point=None, last_cols=None, flags: int = 0):
+        """``slm_working_set_model_solve``: the working-set model solver alone, one launch (two with ``direct``) over
+        ``len(z)`` lanes, on the model ``gprev_W . (x - zprev)_W + (x - zprev)_W^T gram (x - zprev)_W / 2 + pen(x)`` with W =
+        ``cols``.  ``gram`` is (sets, K, K) with K = max(16, len(cols) rounded up to 16), zero on the padding.  Per lane:
+        ``zprev``, ``gprev``, ``z``, ``a0`` (lanes, p), ``b0``, ``d0`` (lanes, G), ``points`` (lanes, 3), ``tol``, ``mode``.
+        Returns a namespace with ``z``, ``beta`` (NaN where nothing was written), the per-lane ``served``, ``mu``, ``zsup``,
+        ``t``, ``have_base``, ``zzero`` (presets -1, -1, 7, 1, 1), ``want_full``, ``repeats``, ``hard_lane``, ``last_point``,
+        ``Lw`` per Gram, the ``WMS_COUNTERS`` by name, and ``kernels``."""
+        import types
+
+        _sync_knobs()
+        z = _f64(np.atleast_2d(z), "z")
+        B = z.shape[0]
+        if z.shape[1] != self.p:
+            raise ValueError(f"z must have {self.p} columns")
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        kreal = int(cols.size)
+        K = max(16, (kreal + 15) // 16 * 16)
+        gram = _f64(gram, "gram")
+        if gram.ndim == 2:
+            gram = gram[None]
+        if gram.ndim != 3 or gram.shape[1:] != (K, K):
+            raise ValueError(f"gram has shape {gram.shape}, expected (sets, {K}, {K})")
+        gram = np.ascontiguousarray(gram)
+        ns = gram.shape[0]
+        zprev = _f64(zprev, "zprev", (B, self.p))
+        gprev = _f64(gprev, "gprev", (B, self.p))
+        a0 = _f64(a0, "a0", (B, self.p))
+        b0 = _f64(np.atleast_2d(b0), "b0")
+        d0 = _f64(np.atleast_2d(d0), "d0")
+        if b0.shape != d0.shape or b0.shape[0] != B:
+            raise ValueError("b0 and d0 must have shape (lanes, groups)")
+        points = _f64(points, "points", (B, 3))
+        tol = _f64(np.broadcast_to(np.asarray(tol, dtype=np.float64), (B,)), "tol", (B,))
+
+        def ints(v, count):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.int32), (count,)))
+
+        mode = ints(mode, B)
+        so, rp, lp, lc = ints(set_of, B), ints(repeats, B), ints(last_point, B), ints(last_cols, B)
+        lw = None if Lw is None else _f64(np.broadcast_to(np.asarray(Lw, dtype=np.float64), (ns,)), "Lw", (ns,))
+        fl = int(flags) | (WMS_DIRECT if direct else 0) | (WMS_HARD if hard else 0) | (WMS_INVALID if invalid else 0) | \
+            (WMS_BUILDING if building else 0) | (WMS_DISABLED if disabled else 0) | (WMS_STALE if stale else 0) | \
+            (WMS_NONFINITE if allow_nonfinite else 0)
+        opts = _WsModelOpts(B, kreal, _ptr(cols), ns, fl, _ptr(gram), _ptr(so), _ptr(zprev), _ptr(gprev), _ptr(z), _ptr(a0),
+                            _ptr(b0), _ptr(d0), _ptr(points), _ptr(tol), _ptr(mode), _ptr(lw), _ptr(rp), _ptr(lp), _ptr(lc))
+        o = types.SimpleNamespace(z=np.empty((B, self.p)), beta=np.empty((B, self.p)))
+        for name in ("served", "zsup", "have_base", "zzero", "want_full", "repeats", "hard_lane", "last_point"):
+            setattr(o, name, np.zeros(B, dtype=np.int32))
+        o.mu, o.t, o.Lw = np.zeros(B), np.zeros(B), np.zeros(ns)
+        counters = np.zeros(8, dtype=np.int32)
+        names = C.create_string_buffer(256)
+        out = _WsModelOut(_ptr(o.z), _ptr(o.beta), _ptr(o.served), _ptr(o.mu), _ptr(o.zsup), _ptr(o.t), _ptr(o.have_base),
+                          _ptr(o.zzero), _ptr(o.want_full), _ptr(o.repeats), _ptr(o.hard_lane), _ptr(o.last_point), _ptr(o.Lw),
+                          _ptr(counters), C.cast(names, C.c_void_p), len(names))
+        _check(self._lib.slm_working_set_model_solve(self._h, C.byref(opts), C.byref(out)))
+        for name, v in zip(WMS_COUNTERS, counters):
+            setattr(o, name, int(v))
+        o.K = K
+        o.kernels = names.value.decode()
+        return o
 
     def eval_sse(self, Z, row_weight=None, sparse=None) -> np.ndarray:
         """sum_i w_i (x_i . Z[k] - y_i)^2 for every row Z[k] of ``Z`` (m, p); ``row_weight`` is e.g. the

@@ -40,6 +40,8 @@ _STRUCTS = {
     "slm_solve_stats": "_SolveStats",
     "slm_lane": "_Lane",
     "slm_ws_lanes_opts": "_WsLanesOpts",
+    "slm_ws_model_opts": "_WsModelOpts",
+    "slm_ws_model_out": "_WsModelOut",
 }
 
 
