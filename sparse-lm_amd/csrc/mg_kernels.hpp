@@ -529,27 +529,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void mg_step_kernel(TailArgs a, MgArg
     }
   });
   // ---- prox of the lane's penalty at its current path point, step 1 / Ls, in the image --------------------------
-  tail_for<E>(tid, p, [&](int j, bool ok) {
-    double uu = soft(us[j], inv_ls * pt.sa * a.a0[j]);
-    if (group_pen && a.singleton) {
-      const double nrm = fabs(uu);
-      const double sc = nrm > 0.0 ? fmax(0.0, 1.0 - inv_ls * pt.sb * a.b0[j] / nrm) : 0.0;
-      uu *= sc / (1.0 + inv_ls * pt.sd * a.d0[j]);
-    }
-    if (ok) us[j] = uu;
-  });
-  if (group_pen && !a.singleton) {
-    __syncthreads();
-    for_each_group_sumsq(us, a.order, a.gstart, G, a.team, [&](int g, double ss) {
-      const double nrm = sqrt(ss);
-      a.gscale[g] = (nrm > 0.0 ? fmax(0.0, 1.0 - inv_ls * pt.sb * a.b0[g] / nrm) : 0.0) / (1.0 + inv_ls * pt.sd * a.d0[g]);
-    });
-    __syncthreads();
-    tail_for<E>(tid, p, [&](int j, bool ok) {
-      const double val = us[j] * a.gscale[a.gid[j]];
-      if (ok) us[j] = val;
-    });
-  }
+  tail_prox_image<E>(us, a, pt, inv_ls, group_pen, nullptr);
   //  s[0] = ||u - v||^2  s[1] = ||u||^2  s[2] = (v - u).(u - x)  s[3] = #non-finite  s[7] = ||u - z0||^2
   tail_for<E>(tid, p, [&](int j, bool ok) {
     const double u = us[j], vj = v[j], xj = x[j], zo = z0[j];

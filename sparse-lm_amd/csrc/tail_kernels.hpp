@@ -20,6 +20,7 @@
 #include "../../include/slm_engine.h"
 #include "grad_kernel.hpp"  // DPP reductions
 #include "light_ctl.hpp"
+#include "tail_logic.hpp"  // the scalar state machine, shared with the CPU test
 
 namespace slm {
 
@@ -79,22 +80,16 @@ struct PathCtl {
   int32_t rounds;      // out: rounds run
 };
 
-constexpr int BB_HIST = 5;
-constexpr int BB_REJECT_LIMIT = 3;    // rejected candidates before a lane falls back to FISTA
-constexpr int BB_POINT_LIMIT = 60;    // spectral iterations on one point before falling back
-constexpr double BB_SIGMA = 1e-4;
-// (round 2: the floor also counts the noise of the gradient itself, kRoundFloor * curvature * ||beta|| -- near a
-// minimiser ||g|| is of the size of the penalty while the rounding error of X^T (X beta - y) / n scales with
-// lambda_max ||beta||; on weakly convex faces (p > n, tol 1e-12) the rule otherwise asks for a residual below that
-// noise and is met, or not, by the luck of the summation order)
 // Stopping rule floor: ||prox step|| <= kRoundFloor * ||g|| / curvature is the rounding noise of the
 // step itself (16 ulp of the gradient); below it `tol * ||beta||` cannot be met in fp64 when the
-// minimiser is itself a rounding-level number (alpha ~ alpha_max).
+// minimiser is itself a rounding-level number (alpha ~ alpha_max).  The floor also counts the noise of the gradient
+// itself, kRoundFloor * curvature * ||beta||: near a minimiser ||g|| is of the size of the penalty while the rounding
+// error of X^T (X beta - y) / n scales with lambda_max ||beta||; on weakly convex faces (p > n, tol 1e-12) the rule
+// otherwise asks for a residual below that noise and is met, or not, by the luck of the summation order.
+// (Defined HERE, not with the other constants of the rule in tail_logic.hpp: the working-set and on-chip solvers stop by
+// it too, and tests/_model_reference.py reads its value out of this file by name; the state machine receives it as
+// TailSnap::round_floor.)
 constexpr double kRoundFloor = 16.0 * 2.220446049250313e-16;
-// Strong-convexity estimates below kMuFloor * lambda_max are not trusted: p > n problems, duplicated
-// columns -- the objective is then flat along some direction of the face (mu = 0: the minimiser is not
-// unique and no residual bounds the distance to "it"); the rule then bounds the residual itself.
-constexpr double kMuFloor = 1e-6;
 
 // One workgroup per lane (blockIdx.x): vectors of lane l start at l * ld (g: l * (ld + 16)).
 struct TailArgs {
@@ -228,7 +223,207 @@ __device__ __forceinline__ void for_each_group_sumsq(const double* src, const in
   }
 }
 
-// E = elements per thread (p <= 1024 * E).  Everything a thread needs of its E features is loaded
+// ---------------------------------------------------------------------------------------------
+// What fista_tail_kernel and fista_tail_stream_kernel share around their vector phases: the view of the lane's arrays,
+// the snapshot of its control block, the write-back.  The decisions in between are tail_logic.hpp's.
+// ---------------------------------------------------------------------------------------------
+// every per-lane pointer of `a` moved to lane `lane`
+__device__ __forceinline__ void tail_rebase(TailArgs& a, const PathCtl* ctl, int lane) {
+  const int64_t off = (int64_t)lane * a.ld;
+  a.beta += off; a.z += off; a.zprev += off; a.gprev += off;
+  a.a0 += off; a.b0 += off; a.d0 += off;
+  a.g += (int64_t)lane * (a.ld + 16);
+  a.gscale += (int64_t)lane * a.G;
+  a.uscratch += off;
+  const int64_t po = ctl->pt_off;
+  a.pts += po;
+  a.betas_out += po * a.p;
+  a.infos += po;
+  if (a.gn_out != nullptr) a.gn_out += po * a.G;
+}
+
+// uniform snapshot of the control block (read-only until tail_commit); `a` is rebased
+__device__ __forceinline__ TailSnap tail_snapshot(const TailArgs& a, const PathCtl* ctl) {
+  TailSnap c;
+  c.point = ctl->point;
+  c.iter = ctl->iter;
+  c.L = ctl->L;
+  c.t = ctl->t;
+  c.tol = ctl->tol;
+  c.flags = ctl->flags;
+  c.total_iter = ctl->total_iter;
+  c.n_points = ctl->n_points;
+  c.pt_lo = ctl->pt_lo;
+  c.max_iter = ctl->max_iter;
+  c.mode = ctl->mode;
+  c.have_base = ctl->have_base;
+  c.rejects = ctl->rejects;
+  c.n_hist = ctl->n_hist;
+  c.ak = ctl->ak;
+  c.Lhat = ctl->Lhat;
+  c.pen_z = ctl->pen_z;
+  c.mu = ctl->mu;
+  c.mu_rq = ctl->mu_rq;
+#pragma unroll
+  for (int k = 0; k < BB_HIST; ++k) c.hist[k] = c.mode == 1 ? ctl->hist[k] : 0.0;
+  // (the ring is the spectral scheme's alone, and tail_commit writes it back in that mode only: ten scalar registers fewer
+  //  across every loop of a FISTA call -- with them fista_tail_stream_kernel<0> spilled 160 scalar registers instead of 99)
+  c.loss_base = ctl->loss_base;
+  c.stride = ctl->stride;
+  c.tail_pt = ctl->tail_pt;
+  tail_snap_call(c, a.g[a.ld], a.provisional != 0, kRoundFloor);
+  return c;
+}
+
+// The control block and the point's record after the call.  (One thread.)
+__device__ __forceinline__ void tail_commit(const TailArgs& a, PathCtl* ctl, int lane, const TailSnap& c, const TailNext& n,
+                                            const TailRoute& r) {
+  if (n.stored) light_commit(a, lane);
+  ctl->zzero = 0;  // (z was just rewritten)
+  ctl->total_iter = c.total_iter + 1;
+  ctl->L = n.L;
+  ctl->mode = n.mode;
+  ctl->rejects = n.rejects;
+  ctl->ak = n.ak;
+  ctl->Lhat = n.Lhat;
+  ctl->loss_base = n.loss_base;
+  if (n.l_bad) ctl->l_bumps += 1;
+  if (n.did_restart) ctl->restarts += 1;
+  if (n.finalize) {
+    slm_point_info info;
+    info.n_iter = c.iter + 1;
+    info.status = tail_status(n);
+    info.resid = n.resid;
+    info.beta_norm = n.bnorm;
+    info.loss = c.loss_z;
+    info.L = n.mode == 1 ? n.ak : n.L;
+    info.mode = n.mode;
+    info.rejects = n.rejects;
+    info.kkt = n.kkt;
+    info.mu = n.mu_eff;
+    a.infos[c.point] = info;
+    ctl->mu = 0.0;     // (the next point has its own face)
+    ctl->mu_rq = 0.0;
+    ctl->iter = 0;
+    ctl->t = 1.0;
+    ctl->have_base = 0;  // the next point's objective differs: start its history afresh
+    ctl->n_hist = 0;
+    ctl->pen_z = 0.0;
+    ctl->point = r.next_point;
+    if (n.nonfinite) {
+      ctl->nonfinite = 1;
+      ctl->done = 1;
+      a.gdone[a.done_slot] = 1;  // abort every lane
+    } else if (r.goes_idle) {
+      // End of this lane's range: in shared-path mode the lane goes idle and steal_kernel (launched
+      // right after this kernel, when every lane's state is at rest) hands it new work or retires it.
+      ctl->idle = 1;
+    } else if (r.range_end) {
+      ctl->done = 1;
+      if (atomicAdd(&a.gdone[1], 1) + 1 == a.n_lanes) a.gdone[a.done_slot] = 1;
+    }
+  } else {
+    ctl->iter = c.iter + 1;
+    atomicMax(&a.gdone[2], c.iter + 1);  // GlobalCtl::hard: lets the host give a hard problem the working set
+    ctl->t = n.t;
+    // (a call on an estimated gradient leaves no base behind: the first true gradient starts the history, and a
+    //  rejection can never fall back on the estimate)
+    ctl->have_base = a.provisional ? 0 : n.have_base;
+    ctl->n_hist = a.provisional ? 0 : n.n_hist;
+    ctl->pen_z = n.pen_z;
+    ctl->mu_rq = n.mu_rq;
+    if (c.mode == 1) {
+#pragma unroll
+      for (int k = 0; k < BB_HIST; ++k) ctl->hist[k] = n.hist[k];
+    }
+  }
+}
+
+// E > 0: p <= 1024 E, every walk over the features is E unrolled steps of straight-line code -- loads from a clamped index,
+// sums and stores predicated -- so that the loads of a phase are all in flight at once (as runtime loops a phase was ten
+// dependent round trips: 100 us per call at p = 10 000 against 25); E = 0: runtime loops, any p.
+template <int E, typename F>
+__device__ __forceinline__ void tail_for(int tid, int p, F f) {
+  if constexpr (E > 0) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int j = tid + e * TAIL_THREADS;
+      f(j < p ? j : 0, j < p);
+    }
+  } else {
+    for (int j = tid; j < p; j += TAIL_THREADS) f(j, true);
+  }
+}
+
+// The feature image us[] holds v; on return it holds prox_{step * penalty}(v) at path point `pt`.  pen (nullable):
+// thread-partial penalty value of the result, accumulated in the order of fista_tail_kernel's prox_inplace.  Of `a` it
+// reads p, G, singleton, team, order, gstart, gid and -- these four moved to the caller's lane -- a0, b0, d0, gscale
+// (scratch), and nothing else: mg_step_kernel rebases only those.
+template <int E>
+__device__ __forceinline__ void tail_prox_image(double* us, const TailArgs& a, const slm_path_point& pt, double step, bool group_pen,
+                                                double* pen) {
+  const int tid = threadIdx.x, p = a.p;
+  tail_for<E>(tid, p, [&](int j, bool ok) {
+    double uu = soft(us[j], step * pt.sa * a.a0[j]);
+    if (group_pen && a.singleton) {
+      const double nrm = fabs(uu);
+      const double sc = nrm > 0.0 ? fmax(0.0, 1.0 - step * pt.sb * a.b0[j] / nrm) : 0.0;
+      uu *= sc / (1.0 + step * pt.sd * a.d0[j]);
+      if (pen && ok) *pen += pt.sb * a.b0[j] * fabs(uu) + 0.5 * pt.sd * a.d0[j] * uu * uu;
+    }
+    if (ok) us[j] = uu;
+  });
+  if (group_pen && !a.singleton) {
+    __syncthreads();
+    for_each_group_sumsq(us, a.order, a.gstart, a.G, a.team, [&](int g, double ss) {
+      const double nrm = sqrt(ss);
+      const double sc = (nrm > 0.0 ? fmax(0.0, 1.0 - step * pt.sb * a.b0[g] / nrm) : 0.0) /
+                        (1.0 + step * pt.sd * a.d0[g]);
+      a.gscale[g] = sc;
+      if (pen) {
+        const double nc = nrm * sc;
+        *pen += pt.sb * a.b0[g] * nc + 0.5 * pt.sd * a.d0[g] * nc * nc;
+      }
+    });
+    __syncthreads();
+    tail_for<E>(tid, p, [&](int j, bool ok) {
+      const double v = us[j] * a.gscale[a.gid[j]];
+      if (ok) us[j] = v;
+    });
+  }
+  if (pen && pt.sa != 0.0) {
+    tail_for<E>(tid, p, [&](int j, bool ok) {
+      if (ok) *pen += pt.sa * a.a0[j] * fabs(us[j]);
+    });
+  }
+}
+
+// Thread-partial penalty value at the vector v (indexed by feature), added to pen; real groups gather v through the
+// image us[], which nobody may be reading.
+template <int E>
+__device__ __forceinline__ void tail_penalty_image(double* us, const TailArgs& a, const slm_path_point& pt, bool group_pen,
+                                                   const double* v, double& pen) {
+  const int tid = threadIdx.x, p = a.p;
+  tail_for<E>(tid, p, [&](int j, bool ok) {
+    const double az = fabs(v[j]);
+    if (ok) {
+      pen += pt.sa * a.a0[j] * az;
+      if (group_pen && a.singleton) pen += pt.sb * a.b0[j] * az + 0.5 * pt.sd * a.d0[j] * az * az;
+    }
+  });
+  if (group_pen && !a.singleton) {
+    tail_for<E>(tid, p, [&](int j, bool ok) {
+      const double z = v[j];
+      if (ok) us[j] = z;
+    });
+    __syncthreads();
+    for_each_group_sumsq(us, a.order, a.gstart, a.G, a.team, [&](int g, double ss) {
+      pen += pt.sb * a.b0[g] * sqrt(ss) + 0.5 * pt.sd * a.d0[g] * ss;
+    });
+  }
+}
+
+// E = elements per thread (p <= 1024 * E, E <= 6).  Everything a thread needs of its E features is loaded
 // once into registers (independent loads: one L2 round trip), the group phase goes through LDS, the
 // only other global round trips are the control block and -- for real group penalties -- the group
 // tables.
@@ -257,90 +452,35 @@ __device__ __forceinline__ void for_each_group_sumsq(const double* src, const in
 // the smallest Rayleigh quotient along its moves), capped by the curvatures this kernel measures itself:
 // the smallest Barzilai-Borwein quotient accepted on this point and Lhat (spectral mode), L (FISTA mode).
 // Without any of these the rule is the classical ||prox step|| <= tol ||beta|| with a step 1/L.
-// (the body, for lane `lane_id`; fista_tail_kernel runs it for lane blockIdx.x)
 template <int E>
-__device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
+__global__ __launch_bounds__(TAIL_THREADS) void fista_tail_kernel(TailArgs a) {
+  // (1024 threads => 128 VGPRs: a thread carries 6 E doubles -- z, g, base, its gradient, the new point, the new base --
+  //  through three sums; from E = 7 on what did not fit went to scratch memory)
+  static_assert(E >= 1 && E <= 6, "rows of more than 6 144 columns take fista_tail_stream_kernel");
   __shared__ double red[9][TAIL_WAVES];
-  // image of the thresholded vector for the group gathers: LDS up to 16K features, the per-lane
-  // global scratch beyond (long-row fallback; the tail is negligible next to a two-pass gradient)
-  constexpr bool US_IN_LDS = E <= 16;
-  __shared__ double us_lds[US_IN_LDS ? E * TAIL_THREADS : 1];
+  __shared__ double us[E * TAIL_THREADS];  // image of the thresholded vector for the group gathers
+  const int lane_id = blockIdx.x;
   PathCtl* ctl = a.ctl + lane_id;
   if (ctl->done != 0 || ctl->idle != 0 || a.gdone[0] != 0) return;
   const int tid = threadIdx.x;
   const int p = a.p, G = a.G;
-  {  // rebase every per-lane pointer
-    const int64_t off = (int64_t)lane_id * a.ld;
-    a.beta += off; a.z += off; a.zprev += off; a.gprev += off;
-    a.a0 += off; a.b0 += off; a.d0 += off;
-    a.g += (int64_t)lane_id * (a.ld + 16);
-    a.gscale += (int64_t)lane_id * G;
-    a.uscratch += off;
-    const int64_t po = ctl->pt_off;
-    a.pts += po;
-    a.betas_out += po * p;
-    a.infos += po;
-    if (a.gn_out != nullptr) a.gn_out += po * G;
-  }
-
-  double* us = US_IN_LDS ? us_lds : a.uscratch;
+  tail_rebase(a, ctl, lane_id);
 
   // ---- phase 0: per-feature loads (independent of the control block) ---------------------------
-  // (kept to the minimum that must live across the reductions: 1024 threads => 128 VGPRs.  Up to six features per
-  //  thread the base point and its gradient stay in registers too; beyond -- p > 6144, BASELINE config 5's 10 000 --
-  //  they are read where they are used, once more from the L2 in the branches that need them again: with all four
-  //  vectors and the two results in registers a thread of E = 10 needs 120 of its 128 for them alone, and what did
-  //  not fit went to scratch memory, 20 ... 544 bytes per thread, whose dirty lines are written back at the end of
-  //  every call of this kernel)
-  constexpr bool KEEP = E <= 6;
-  double zj[E], gj[E], bo[KEEP ? E : 1], gpv[KEEP ? E : 1];
+  double zj[E], gj[E], bo[E], gpv[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int j = tid + e * TAIL_THREADS;
     const int jj = j < p ? j : 0;
     zj[e] = a.z[jj];
     gj[e] = a.g[jj];
-    if (KEEP) {
-      bo[KEEP ? e : 0] = a.beta[jj];
-      gpv[KEEP ? e : 0] = a.gprev[jj];
-    }
+    bo[e] = a.beta[jj];
+    gpv[e] = a.gprev[jj];
   }
-  // base point / its gradient of feature slot e (jj: the slot's feature, clamped)
-  auto BO = [&](int e, int jj) -> double { return KEEP ? bo[KEEP ? e : 0] : a.beta[jj]; };
-  auto GPV = [&](int e, int jj) -> double { return KEEP ? gpv[KEEP ? e : 0] : a.gprev[jj]; };
 
-  // uniform snapshot of the control block (read-only until the final single-thread update)
-  const int point = ctl->point;
-  const int iter = ctl->iter;
-  const double L = ctl->L;
-  const double t_old = ctl->t;
-  const double tol = ctl->tol;
-  const uint32_t flags = ctl->flags;
-  const int64_t total_iter = ctl->total_iter;
-  const int n_points = ctl->n_points;
-  const int pt_lo = ctl->pt_lo;
-  const int max_iter = ctl->max_iter;
-  const int mode = ctl->mode;
-  const int have_base = ctl->have_base;
-  const int rejects = ctl->rejects;
-  const int n_hist = ctl->n_hist;
-  const double ak_old = ctl->ak;
-  const double Lhat_old = ctl->Lhat;
-  const double pen_z = ctl->pen_z;
-  const double mu_ws = ctl->mu;
-  const double mu_rq_old = ctl->mu_rq;
-  double hist[BB_HIST];
-#pragma unroll
-  for (int k = 0; k < BB_HIST; ++k) hist[k] = ctl->hist[k];
-  const slm_path_point pt = a.pts[point];
-  const double loss_z = a.g[a.ld];
+  const TailSnap c = tail_snapshot(a, ctl);
+  const slm_path_point pt = a.pts[c.point];
   const bool group_pen = (pt.sb != 0.0) || (pt.sd != 0.0);
-  const bool cold = (flags & SLM_FLAG_COLD_START) != 0;
-  const bool hit_max = (iter + 1 >= max_iter);
-  // ||beta|| in the stopping rule never drops below 1e-10 of the scale the data give a coefficient
-  // vector (rms residual / sqrt(L)): at alpha ~ alpha_max the minimiser is a rounding-level number
-  // (~1e-16) and "tol relative to it" would ask for more digits than fp64 has.
-  const double bnorm_floor = 1e-10 * sqrt(2.0 * fmax(loss_z, 0.0) / fmax(L, Lhat_old));
 
   // prox_{step * penalty} of the per-thread vector v[] (in place), optionally accumulating the
   // penalty value of the result into pen (thread-partial; the caller block-sums it).
@@ -395,31 +535,18 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
     }
   };
 
-  // outcome of this call, filled by either scheme
+  TailNext n = tail_next(c);  // outcome of this call, filled by either scheme
   double u[E];   // next point z (candidate / extrapolated point), or the reported solution when finalize
   double(&nb)[E] = zj;  // new beta when !finalize: takes over the registers of z once the sums over z are done
-  bool finalize = false, conv = false, nonfinite = false;
-  double resid = 0.0, bnorm = 0.0;
-  double kkt = 0.0, mu_eff = 0.0, new_mu_rq = mu_rq_old;
-  // control-block updates
-  int new_mode = mode, new_have_base = have_base, new_rejects = rejects, new_n_hist = n_hist;
-  double new_loss_base = ctl->loss_base;
-  double new_t = t_old, new_L = L, new_ak = ak_old, new_Lhat = Lhat_old, new_pen_z = pen_z;
-  bool did_restart = false, l_bad = false;
-  bool stored = true;  // gprev now holds this call's gradient (all but a rejected candidate)
 
-  if (mode == 1) {
-    // ================= spectral (BB) scheme =====================================================
-    //  s[0] = ||z - beta||^2   s[1] = <z - beta, g - gbase>   s[2] = ||g - gbase||^2   s[3] = #non-finite g
-    //  s[4] = penalty value at z (only computed at the start of a path point, when no candidate
-    //         carried it over)
-    //  s[5] = ||g||^2 (rounding floor of the stopping rule)
+  if (c.mode == 1) {
+    // ================= spectral (BB) scheme (sums: bb_decide) ===================================
     double s[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int j = tid + e * TAIL_THREADS;
       if (j < p) {
-        const double dz = zj[e] - BO(e, j), dg = gj[e] - GPV(e, j);
+        const double dz = zj[e] - bo[e], dg = gj[e] - gpv[e];
         s[0] = __builtin_fma(dz, dz, s[0]);
         s[1] = __builtin_fma(dz, dg, s[1]);
         s[2] = __builtin_fma(dg, dg, s[2]);
@@ -427,7 +554,7 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
         s[5] = __builtin_fma(gj[e], gj[e], s[5]);
       }
     }
-    if (!have_base) {
+    if (!c.have_base) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int j = tid + e * TAIL_THREADS;
@@ -450,50 +577,10 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
       }
     }
     block_sum<6>(s, red);
-    const double Fz = loss_z + (have_base ? pen_z : s[4]);
-    nonfinite = s[3] > 0.0 || !isfinite(Fz);
-    bool accept;
-    if (!have_base) {
-      accept = true;  // z is the start point of this path point: it becomes the base
-      new_n_hist = 0;
-    } else {
-      double fmax_hist = hist[0];
-#pragma unroll
-      for (int k = 1; k < BB_HIST; ++k)
-        if (k < n_hist) fmax_hist = fmax(fmax_hist, hist[k]);
-      accept = Fz <= fmax_hist - 0.5 * BB_SIGMA * ak_old * s[0];
-      if (accept) {
-        if (s[0] > 0.0) {
-          new_Lhat = fmax(Lhat_old, sqrt(s[2] / s[0]));
-          new_ak = s[1] > 0.0 ? s[1] / s[0] : new_Lhat;
-        }
-        new_ak = fmin(fmax(new_ak, 1e-6 * new_Lhat), 1e6 * new_Lhat);
-        // (a step at the rounding level of the iterate or of the gradient measures nothing)
-        if (s[1] > 0.0 && s[0] * new_Lhat * new_Lhat > 1e-20 * s[5] && s[2] > 1e-20 * s[5])
-          new_mu_rq = mu_rq_old > 0.0 ? fmin(mu_rq_old, new_ak) : new_ak;
-      } else {
-        new_ak = fmin(2.0 * ak_old, 1e6 * Lhat_old);
-        new_rejects = rejects + 1;
-      }
-    }
-    if (accept) {  // push F(z) into the ring of the last BB_HIST accepted values
-      if (new_n_hist < BB_HIST) {
-#pragma unroll
-        for (int k = 0; k < BB_HIST; ++k)
-          if (k == new_n_hist) hist[k] = Fz;
-        new_n_hist += 1;
-      } else {
-#pragma unroll
-        for (int k = 0; k + 1 < BB_HIST; ++k) hist[k] = hist[k + 1];
-        hist[BB_HIST - 1] = Fz;
-      }
-      new_have_base = 1;
-      new_loss_base = loss_z;
-    }
-    stored = accept;
+    const bool accept = bb_decide(c, n, s);
     // base point and its gradient after the decision; (zprev, gprev) = (base, its gradient) stays a
     // consistent pair for the FISTA curvature guard should this lane fall back
-    const double step = 1.0 / new_ak;
+    const double step = 1.0 / n.ak;
     // (two loops under one test rather than `accept ? zj[e] : bo[e]` in one: the compiler turns that into a choice
     // between the ADDRESSES of the arrays, which puts them in scratch memory -- sixteen stores, thirty loads and their
     // lines to write back at the end of every call.  nb IS zj from here on: an accepted candidate is the new base
@@ -512,34 +599,28 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int j = tid + e * TAIL_THREADS;
-        const int jj = j < p ? j : 0;
-        nb[e] = BO(e, jj);
+        nb[e] = bo[e];
         if (j < p) a.zprev[j] = nb[e];
-        u[e] = nb[e] - step * GPV(e, jj);
+        u[e] = nb[e] - step * gpv[e];
       }
     }
-    const bool fallback = !nonfinite && (new_rejects >= BB_REJECT_LIMIT || iter + 1 > BB_POINT_LIMIT);
-    if (fallback) {
-      new_mode = 0;
-      new_t = 1.0;
-      new_L = fmax(L, new_Lhat);
+    if (n.fallback) {
+      bb_fallback(c, n);
 #pragma unroll
       for (int e = 0; e < E; ++e) u[e] = nb[e];  // FISTA restarts from the base point
-      finalize = hit_max;
-      if (finalize) {
+      if (n.finalize) {
         double q[1] = {0.0};
 #pragma unroll
         for (int e = 0; e < E; ++e)
           if (tid + e * TAIL_THREADS < p) q[0] = __builtin_fma(u[e], u[e], q[0]);
         block_sum<1>(q, red);
-        bnorm = sqrt(q[0]);
-        resid = sqrt(s[0]);
+        n.bnorm = sqrt(q[0]);
+        n.resid = sqrt(s[0]);
       }
     } else {
       double pen_c = 0.0;
       prox_inplace(u, step, &pen_c);
-      //  q[0] = ||c - base||^2   q[1] = ||c||^2   q[2] = pen(c)   q[3] = #non-finite
-      double q[4] = {0, 0, pen_c, 0};
+      double q[4] = {0, 0, pen_c, 0};  // (sums: bb_stop)
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         if (tid + e * TAIL_THREADS < p) {
@@ -550,32 +631,17 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
         }
       }
       block_sum<4>(q, red);
-      nonfinite = nonfinite || q[3] > 0.0 || !isfinite(q[0]) || !isfinite(q[1]);
-      new_pen_z = q[2];
-      resid = sqrt(q[0]) * fmax(1.0, new_ak / new_Lhat);
-      bnorm = sqrt(q[1]);
-      kkt = sqrt(q[0]) * new_ak;  // ||G_s(base)||, s = 1 / ak
-      mu_eff = fmin(new_ak, new_Lhat);
-      if (new_mu_rq > 0.0) mu_eff = fmin(mu_eff, new_mu_rq);
-      if (mu_ws > 0.0) mu_eff = fmin(mu_eff, mu_ws);
-      mu_eff = fmax(mu_eff, kMuFloor * new_Lhat);
-      // (second term: a prox step at the rounding level of the gradient itself cannot be improved)
-      conv = !a.provisional && kkt <= fmax(tol * fmax(bnorm, bnorm_floor) * mu_eff, kRoundFloor * (sqrt(s[5]) + new_Lhat * bnorm));
-      finalize = nonfinite || conv || hit_max;
+      bb_stop(c, n, s, q);
     }
   } else {
-    // ================= FISTA scheme =================================================================
-    //  s[0] = ||b+ - z||^2   s[1] = ||b+||^2   s[2] = (z - b+).(b+ - b)   s[3] = ||g - gprev||^2
-    //  s[4] = ||z - zprev||^2   s[5] = ||z||^2   s[6] = #non-finite
-    //  s[7] = ||g||^2   s[8] = <g - gprev, z - zprev>
+    // ================= FISTA scheme (sums: fista_decide) ========================================
     double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const double step = 1.0 / L;
-    new_loss_base = loss_z;  // (zprev = z below)
+    const double step = 1.0 / c.L;
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int j = tid + e * TAIL_THREADS;
       if (j < p) {
-        const double dg = gj[e] - GPV(e, j), dzz = zj[e] - a.zprev[j];
+        const double dg = gj[e] - gpv[e], dzz = zj[e] - a.zprev[j];
         s[3] = __builtin_fma(dg, dg, s[3]);
         s[4] = __builtin_fma(dzz, dzz, s[4]);
         s[8] = __builtin_fma(dg, dzz, s[8]);
@@ -595,74 +661,38 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
         const double dz = bn - zj[e];
         s[0] = __builtin_fma(dz, dz, s[0]);
         s[1] = __builtin_fma(bn, bn, s[1]);
-        s[2] = __builtin_fma(-dz, bn - BO(e, j), s[2]);
+        s[2] = __builtin_fma(-dz, bn - bo[e], s[2]);
         if (!isfinite(bn)) s[6] += 1.0;
       }
     }
     block_sum<9>(s, red);
-    nonfinite = s[6] > 0.0 || !isfinite(s[0]) || !isfinite(s[1]) || !isfinite(loss_z);
-    // Curvature guard: ||A dz|| / ||dz|| is a lower bound on lambda_max(A), A = X^T W X / n.  If it
-    // exceeds L the step 1/L was too long: raise L, discard the step and restart from beta.
-    if (total_iter > 0 && s[4] > 1e-12 * s[5] && s[4] > 0.0) {
-      const double curv = sqrt(s[3] / s[4]);
-      if (curv > L * (1.0 + 1e-9)) {
-        l_bad = true;
-        new_L = 1.02 * curv;
-      }
-      // curvature along the move of the extrapolated point: a Rayleigh quotient of X^T W X / n, i.e. an upper
-      // estimate of the strong convexity on the face the iteration is on
-      if (s[8] > 0.0 && s[3] > 1e-20 * s[7]) new_mu_rq = mu_rq_old > 0.0 ? fmin(mu_rq_old, s[8] / s[4]) : s[8] / s[4];
-    }
-    did_restart = !(flags & SLM_FLAG_NO_RESTART) && s[2] > 0.0;
-    const double t_use = did_restart ? 1.0 : t_old;
-    const double t_new = 0.5 * (1.0 + sqrt(1.0 + 4.0 * t_use * t_use));
-    const double mom = (t_use - 1.0) / t_new;
-    resid = sqrt(s[0]);
-    bnorm = sqrt(s[1]);
-    kkt = resid * L;  // ||G_s(z)||, s = 1 / L
-    mu_eff = mu_ws > 0.0 ? fmin(mu_ws, L) : L;
-    if (new_mu_rq > 0.0) mu_eff = fmin(mu_eff, new_mu_rq);
-    mu_eff = fmax(mu_eff, kMuFloor * L);
-    conv = !a.provisional && !l_bad && (kkt <= fmax(tol * fmax(bnorm, bnorm_floor) * mu_eff, kRoundFloor * (sqrt(s[7]) + L * bnorm)));
-    finalize = nonfinite || conv || hit_max;
-    new_t = l_bad ? 1.0 : t_new;
+    fista_decide(c, n, s);
 #pragma unroll
     for (int e = 0; e < E; ++e) {  // (z is spent: nb takes its registers)
-      const int j = tid + e * TAIL_THREADS;
-      const double bn = u[e], bold = BO(e, j < p ? j : 0);
-      if (l_bad) {
+      const double bn = u[e], bold = bo[e];
+      if (n.l_bad) {
         nb[e] = bold;  // step rejected: beta unchanged, momentum dropped
         u[e] = bold;
       } else {
         nb[e] = bn;
-        if (!finalize) u[e] = bn + mom * (bn - bold);  // next extrapolated point
+        if (!n.finalize) u[e] = bn + n.mom * (bn - bold);  // next extrapolated point
       }
     }
   }
 
   // ---- state update --------------------------------------------------------------------------
+  const TailRoute r = tail_route(c, n, a.steal != 0);
   // secant prediction of the next point's start from the last two solutions (see slm_path_point)
-  double extrap = 0.0;
-  const int stride = ctl->stride > 1 ? ctl->stride : 1;
-  // (interleaved lanes: the neighbouring points belong to other lanes and finish in this same launch,
-  //  so there is no secant through them -- the next point starts from this lane's last solution)
-  if (finalize && !cold && !nonfinite && stride == 1 && point - pt_lo >= 1 && point + 1 < n_points)
-    extrap = a.pts[point + 1].extrap;
-  // End of this lane's range: in shared-path mode the lane goes idle and steal_kernel (launched
-  // right after this kernel, when every lane's state is at rest) hands it new work or retires it.
-  const int tail_pt = ctl->tail_pt;
-  const bool walk_end = point + stride >= n_points;  // (the tail point itself lies beyond n_points)
-  const bool range_end = finalize && !nonfinite && walk_end && (tail_pt < 0 || point == tail_pt);
-  const bool goes_idle = range_end && a.steal;
+  const double extrap = r.secant ? a.pts[c.point + 1].extrap : 0.0;
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const int j = tid + e * TAIL_THREADS;
     if (j < p) {
-      if (finalize) {
+      if (n.finalize) {
         const double out = u[e];
-        a.betas_out[(int64_t)point * p + j] = out;
-        double nxt = (cold || goes_idle) ? 0.0 : out;  // a taken-over range starts cold
-        if (extrap != 0.0) nxt = out + extrap * (out - a.betas_out[(int64_t)(point - 1) * p + j]);
+        a.betas_out[(int64_t)c.point * p + j] = out;
+        double nxt = (c.cold || r.goes_idle) ? 0.0 : out;  // a taken-over range starts cold
+        if (extrap != 0.0) nxt = out + extrap * (out - a.betas_out[(int64_t)(c.point - 1) * p + j]);
         a.beta[j] = nxt;
         a.z[j] = nxt;
       } else {
@@ -671,7 +701,7 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
       }
     }
   }
-  if (finalize && a.gn_out != nullptr) {
+  if (n.finalize && a.gn_out != nullptr) {
     // group norms of the reported solution (the reference's auxiliaries.group_norms.value,
     // model/_lasso.py:239-255, consumed by the adaptive re-weighting at _adaptive_lasso.py:364-374)
     __syncthreads();
@@ -681,73 +711,10 @@ __device__ __forceinline__ void fista_tail_body(TailArgs a, const int lane_id) {
       if (j < p) us[j] = u[e];
     }
     __syncthreads();
-    double* gn = a.gn_out + (int64_t)point * G;
+    double* gn = a.gn_out + (int64_t)c.point * G;
     for_each_group_sumsq(us, a.order, a.gstart, G, a.team, [&](int g, double ss) { gn[g] = sqrt(ss); });
   }
-
-  // ---- control block ----------------------------------------------------------------------------
-  if (tid == 0) {
-    if (stored) light_commit(a, lane_id);
-    ctl->zzero = 0;  // (z was just rewritten)
-    ctl->total_iter = total_iter + 1;
-    ctl->L = new_L;
-    ctl->mode = new_mode;
-    ctl->rejects = new_rejects;
-    ctl->ak = new_ak;
-    ctl->Lhat = new_Lhat;
-    ctl->loss_base = new_loss_base;
-    if (l_bad) ctl->l_bumps += 1;
-    if (did_restart) ctl->restarts += 1;
-    if (finalize) {
-      slm_point_info info;
-      info.n_iter = iter + 1;
-      info.status = (conv && !nonfinite) ? SLM_OK : (nonfinite ? SLM_ERR_NON_FINITE : SLM_ERR_NOT_CONVERGED);
-      info.resid = resid;
-      info.beta_norm = bnorm;
-      info.loss = loss_z;
-      info.L = new_mode == 1 ? new_ak : new_L;
-      info.mode = new_mode;
-      info.rejects = new_rejects;
-      info.kkt = kkt;
-      info.mu = mu_eff;
-      a.infos[point] = info;
-      ctl->mu = 0.0;     // (the next point has its own face)
-      ctl->mu_rq = 0.0;
-      ctl->iter = 0;
-      ctl->t = 1.0;
-      ctl->have_base = 0;  // the next point's objective differs: start its history afresh
-      ctl->n_hist = 0;
-      ctl->pen_z = 0.0;
-      ctl->point = (walk_end && tail_pt >= 0 && point != tail_pt) ? tail_pt : point + stride;
-      if (nonfinite) {
-        ctl->nonfinite = 1;
-        ctl->done = 1;
-        a.gdone[a.done_slot] = 1;  // abort every lane
-      } else if (goes_idle) {
-        ctl->idle = 1;
-      } else if (range_end) {
-        ctl->done = 1;
-        if (atomicAdd(&a.gdone[1], 1) + 1 == a.n_lanes) a.gdone[a.done_slot] = 1;
-      }
-    } else {
-      ctl->iter = iter + 1;
-      atomicMax(&a.gdone[2], iter + 1);  // GlobalCtl::hard: lets the host give a hard problem the working set
-      ctl->t = new_t;
-      // (a call on an estimated gradient leaves no base behind: the first true gradient starts the history, and a
-      //  rejection can never fall back on the estimate)
-      ctl->have_base = a.provisional ? 0 : new_have_base;
-      ctl->n_hist = a.provisional ? 0 : new_n_hist;
-      ctl->pen_z = new_pen_z;
-      ctl->mu_rq = new_mu_rq;
-#pragma unroll
-      for (int k = 0; k < BB_HIST; ++k) ctl->hist[k] = hist[k];
-    }
-  }
-}
-
-template <int E>
-__global__ __launch_bounds__(TAIL_THREADS) void fista_tail_kernel(TailArgs a) {
-  fista_tail_body<E>(a, (int)blockIdx.x);
+  if (tid == 0) tail_commit(a, ctl, lane_id, c, n, r);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -756,27 +723,11 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_kernel(TailArgs a) {
 // gradient, the new point, the new base) through three sums; from E = 7 on that is more than the 128 registers 1 024
 // threads leave each other, and what did not fit went to scratch memory -- 20 ... 544 bytes per thread from E = 7 to 10,
 // kilobytes beyond -- whose dirty lines the next kernel boundary has to write back ("Kernel
-// boundaries").  Here every phase walks the features (j = tid, tid + 1024, ...: the order, and therefore every sum, is
-// that of the register kernel), reads what it needs from the L2-resident vectors and leaves its result in the feature
-// image `us` (LDS up to 16 384 features, the per-lane global scratch beyond); the image is the candidate point, the
-// base point is zprev (which the decision phase writes anyway).  Same arithmetic, same state machine, any p.
+// boundaries").  Here every phase walks the features (tail_for: j = tid, tid + 1024, ..., the order, and therefore every
+// sum, is that of the register kernel), reads what it needs from the L2-resident vectors and leaves its result in the
+// feature image `us` (LDS up to 16 384 features, the per-lane global scratch beyond); the image is the candidate point,
+// the base point is zprev (which the decision phase writes anyway).  Same arithmetic, same state machine, any p.
 // ---------------------------------------------------------------------------------------------
-// E > 0: p <= 1024 E, every walk over the features is E unrolled steps of straight-line code -- loads from a clamped index,
-// sums and stores predicated -- so that the loads of a phase are all in flight at once (as runtime loops a phase was ten
-// dependent round trips: 100 us per call at p = 10 000 against 25); E = 0: runtime loops, any p.
-template <int E, typename F>
-__device__ __forceinline__ void tail_for(int tid, int p, F f) {
-  if constexpr (E > 0) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int j = tid + e * TAIL_THREADS;
-      f(j < p ? j : 0, j < p);
-    }
-  } else {
-    for (int j = tid; j < p; j += TAIL_THREADS) f(j, true);
-  }
-}
-
 template <int E>
 __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArgs a) {
   __shared__ double red[9][TAIL_WAVES];
@@ -787,102 +738,19 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
   if (ctl->done != 0 || ctl->idle != 0 || a.gdone[0] != 0) return;
   const int tid = threadIdx.x;
   const int p = a.p, G = a.G;
-  {  // rebase every per-lane pointer
-    const int64_t off = (int64_t)lane_id * a.ld;
-    a.beta += off; a.z += off; a.zprev += off; a.gprev += off;
-    a.a0 += off; a.b0 += off; a.d0 += off;
-    a.g += (int64_t)lane_id * (a.ld + 16);
-    a.gscale += (int64_t)lane_id * G;
-    a.uscratch += off;
-    const int64_t po = ctl->pt_off;
-    a.pts += po;
-    a.betas_out += po * p;
-    a.infos += po;
-    if (a.gn_out != nullptr) a.gn_out += po * G;
-  }
+  tail_rebase(a, ctl, lane_id);
   double* us = p <= US_LDS ? us_lds : a.uscratch;
 
-  const int point = ctl->point;
-  const int iter = ctl->iter;
-  const double L = ctl->L;
-  const double t_old = ctl->t;
-  const double tol = ctl->tol;
-  const uint32_t flags = ctl->flags;
-  const int64_t total_iter = ctl->total_iter;
-  const int n_points = ctl->n_points;
-  const int pt_lo = ctl->pt_lo;
-  const int max_iter = ctl->max_iter;
-  const int mode = ctl->mode;
-  const int have_base = ctl->have_base;
-  const int rejects = ctl->rejects;
-  const int n_hist = ctl->n_hist;
-  const double ak_old = ctl->ak;
-  const double Lhat_old = ctl->Lhat;
-  const double pen_z = ctl->pen_z;
-  const double mu_ws = ctl->mu;
-  const double mu_rq_old = ctl->mu_rq;
-  double hist[BB_HIST];
-#pragma unroll
-  for (int k = 0; k < BB_HIST; ++k) hist[k] = ctl->hist[k];
-  const slm_path_point pt = a.pts[point];
-  const double loss_z = a.g[a.ld];
+  const TailSnap c = tail_snapshot(a, ctl);
+  const slm_path_point pt = a.pts[c.point];
   const bool group_pen = (pt.sb != 0.0) || (pt.sd != 0.0);
-  const bool cold = (flags & SLM_FLAG_COLD_START) != 0;
-  const bool hit_max = (iter + 1 >= max_iter);
-  const double bnorm_floor = 1e-10 * sqrt(2.0 * fmax(loss_z, 0.0) / fmax(L, Lhat_old));
 
-  // the image us[] holds v; on return it holds prox_{step * penalty}(v).  pen (nullable): thread-partial penalty value
-  // of the result, accumulated in the order of fista_tail_kernel's prox_inplace
-  auto prox_image = [&](double step, double* pen) {
-    tail_for<E>(tid, p, [&](int j, bool ok) {
-      double uu = soft(us[j], step * pt.sa * a.a0[j]);
-      if (group_pen && a.singleton) {
-        const double nrm = fabs(uu);
-        const double sc = nrm > 0.0 ? fmax(0.0, 1.0 - step * pt.sb * a.b0[j] / nrm) : 0.0;
-        uu *= sc / (1.0 + step * pt.sd * a.d0[j]);
-        if (pen && ok) *pen += pt.sb * a.b0[j] * fabs(uu) + 0.5 * pt.sd * a.d0[j] * uu * uu;
-      }
-      if (ok) us[j] = uu;
-    });
-    if (group_pen && !a.singleton) {
-      __syncthreads();
-      for_each_group_sumsq(us, a.order, a.gstart, G, a.team, [&](int g, double ss) {
-        const double nrm = sqrt(ss);
-        const double sc = (nrm > 0.0 ? fmax(0.0, 1.0 - step * pt.sb * a.b0[g] / nrm) : 0.0) /
-                          (1.0 + step * pt.sd * a.d0[g]);
-        a.gscale[g] = sc;
-        if (pen) {
-          const double nc = nrm * sc;
-          *pen += pt.sb * a.b0[g] * nc + 0.5 * pt.sd * a.d0[g] * nc * nc;
-        }
-      });
-      __syncthreads();
-      tail_for<E>(tid, p, [&](int j, bool ok) {
-        const double v = us[j] * a.gscale[a.gid[j]];
-        if (ok) us[j] = v;
-      });
-    }
-    if (pen && pt.sa != 0.0) {
-      tail_for<E>(tid, p, [&](int j, bool ok) {
-        if (ok) *pen += pt.sa * a.a0[j] * fabs(us[j]);
-      });
-    }
-  };
-
-  bool finalize = false, conv = false, nonfinite = false;
-  double resid = 0.0, bnorm = 0.0;
-  double kkt = 0.0, mu_eff = 0.0, new_mu_rq = mu_rq_old;
-  int new_mode = mode, new_have_base = have_base, new_rejects = rejects, new_n_hist = n_hist;
-  double new_loss_base = ctl->loss_base;
-  double new_t = t_old, new_L = L, new_ak = ak_old, new_Lhat = Lhat_old, new_pen_z = pen_z;
-  bool did_restart = false, l_bad = false;
   // how the last phase finds the new base point and the next point of feature j:
   //   mode 1: base = zprev[j], next = us[j] (the candidate; the base itself on the switch to FISTA: us holds it then)
   //   mode 0: base / next from us[j] (the proximal point) and beta[j], see below
-  double mom = 0.0;
-  bool stored = true;  // gprev now holds this call's gradient (all but a rejected candidate)
+  TailNext n = tail_next(c);
 
-  if (mode == 1) {
+  if (c.mode == 1) {
     double s[6] = {0, 0, 0, 0, 0, 0};
     tail_for<E>(tid, p, [&](int j, bool ok) {
       const double z = a.z[j], g = a.g[j];
@@ -895,68 +763,10 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
         s[5] = __builtin_fma(g, g, s[5]);
       }
     });
-    if (!have_base) {
-      tail_for<E>(tid, p, [&](int j, bool ok) {
-        const double az = fabs(a.z[j]);
-        if (ok) {
-          s[4] += pt.sa * a.a0[j] * az;
-          if (group_pen && a.singleton) s[4] += pt.sb * a.b0[j] * az + 0.5 * pt.sd * a.d0[j] * az * az;
-        }
-      });
-      if (group_pen && !a.singleton) {
-        tail_for<E>(tid, p, [&](int j, bool ok) {
-          const double z = a.z[j];
-          if (ok) us[j] = z;
-        });
-        __syncthreads();
-        for_each_group_sumsq(us, a.order, a.gstart, G, a.team, [&](int g, double ss) {
-          s[4] += pt.sb * a.b0[g] * sqrt(ss) + 0.5 * pt.sd * a.d0[g] * ss;
-        });
-      }
-    }
+    if (!c.have_base) tail_penalty_image<E>(us, a, pt, group_pen, a.z, s[4]);
     block_sum<6>(s, red);
-    const double Fz = loss_z + (have_base ? pen_z : s[4]);
-    nonfinite = s[3] > 0.0 || !isfinite(Fz);
-    bool accept;
-    if (!have_base) {
-      accept = true;
-      new_n_hist = 0;
-    } else {
-      double fmax_hist = hist[0];
-#pragma unroll
-      for (int k = 1; k < BB_HIST; ++k)
-        if (k < n_hist) fmax_hist = fmax(fmax_hist, hist[k]);
-      accept = Fz <= fmax_hist - 0.5 * BB_SIGMA * ak_old * s[0];
-      if (accept) {
-        if (s[0] > 0.0) {
-          new_Lhat = fmax(Lhat_old, sqrt(s[2] / s[0]));
-          new_ak = s[1] > 0.0 ? s[1] / s[0] : new_Lhat;
-        }
-        new_ak = fmin(fmax(new_ak, 1e-6 * new_Lhat), 1e6 * new_Lhat);
-        if (s[1] > 0.0 && s[0] * new_Lhat * new_Lhat > 1e-20 * s[5] && s[2] > 1e-20 * s[5])
-          new_mu_rq = mu_rq_old > 0.0 ? fmin(mu_rq_old, new_ak) : new_ak;
-      } else {
-        new_ak = fmin(2.0 * ak_old, 1e6 * Lhat_old);
-        new_rejects = rejects + 1;
-      }
-    }
-    if (accept) {
-      if (new_n_hist < BB_HIST) {
-#pragma unroll
-        for (int k = 0; k < BB_HIST; ++k)
-          if (k == new_n_hist) hist[k] = Fz;
-        new_n_hist += 1;
-      } else {
-#pragma unroll
-        for (int k = 0; k + 1 < BB_HIST; ++k) hist[k] = hist[k + 1];
-        hist[BB_HIST - 1] = Fz;
-      }
-      new_have_base = 1;
-      new_loss_base = loss_z;
-    }
-    stored = accept;
-    const double step = 1.0 / new_ak;
-    const bool fallback = !nonfinite && (new_rejects >= BB_REJECT_LIMIT || iter + 1 > BB_POINT_LIMIT);
+    const bool accept = bb_decide(c, n, s);
+    const double step = 1.0 / n.ak;
     __syncthreads();  // (the image may still be read by the group sums above)
     // base point (-> zprev) and its gradient (-> gprev) after the decision; the image gets base - step * gradient,
     // or, on the switch to FISTA, the base itself
@@ -966,7 +776,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
         if (ok) {
           a.gprev[j] = g;
           a.zprev[j] = z;
-          us[j] = fallback ? z : z - step * g;
+          us[j] = n.fallback ? z : z - step * g;
         }
       });
     } else {
@@ -974,55 +784,40 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
         const double b = a.beta[j], gp = a.gprev[j];
         if (ok) {
           a.zprev[j] = b;
-          us[j] = fallback ? b : b - step * gp;
+          us[j] = n.fallback ? b : b - step * gp;
         }
       });
     }
-    if (fallback) {
-      new_mode = 0;
-      new_t = 1.0;
-      new_L = fmax(L, new_Lhat);
-      finalize = hit_max;
-      if (finalize) {
+    if (n.fallback) {
+      bb_fallback(c, n);
+      if (n.finalize) {
         double q[1] = {0.0};
         tail_for<E>(tid, p, [&](int j, bool ok) {
           if (ok) q[0] = __builtin_fma(us[j], us[j], q[0]);
         });
         block_sum<1>(q, red);
-        bnorm = sqrt(q[0]);
-        resid = sqrt(s[0]);
+        n.bnorm = sqrt(q[0]);
+        n.resid = sqrt(s[0]);
       }
     } else {
       double pen_c = 0.0;
-      prox_image(step, &pen_c);
+      tail_prox_image<E>(us, a, pt, step, group_pen, &pen_c);
       double q[4] = {0, 0, pen_c, 0};
       tail_for<E>(tid, p, [&](int j, bool ok) {
-        const double c = us[j];
-        const double dc = c - a.zprev[j];
+        const double cj = us[j];
+        const double dc = cj - a.zprev[j];
         if (ok) {
           q[0] = __builtin_fma(dc, dc, q[0]);
-          q[1] = __builtin_fma(c, c, q[1]);
-          if (!isfinite(c)) q[3] += 1.0;
+          q[1] = __builtin_fma(cj, cj, q[1]);
+          if (!isfinite(cj)) q[3] += 1.0;
         }
       });
       block_sum<4>(q, red);
-      nonfinite = nonfinite || q[3] > 0.0 || !isfinite(q[0]) || !isfinite(q[1]);
-      new_pen_z = q[2];
-      resid = sqrt(q[0]) * fmax(1.0, new_ak / new_Lhat);
-      bnorm = sqrt(q[1]);
-      kkt = sqrt(q[0]) * new_ak;
-      mu_eff = fmin(new_ak, new_Lhat);
-      if (new_mu_rq > 0.0) mu_eff = fmin(mu_eff, new_mu_rq);
-      if (mu_ws > 0.0) mu_eff = fmin(mu_eff, mu_ws);
-      mu_eff = fmax(mu_eff, kMuFloor * new_Lhat);
-      conv = !a.provisional && kkt <= fmax(tol * fmax(bnorm, bnorm_floor) * mu_eff, kRoundFloor * (sqrt(s[5]) + new_Lhat * bnorm));
-      finalize = nonfinite || conv || hit_max;
+      bb_stop(c, n, s, q);
     }
   } else {
-    // ================= FISTA scheme =================================================================
     double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const double step = 1.0 / L;
-    new_loss_base = loss_z;  // (zprev = z below)
+    const double step = 1.0 / c.L;
     tail_for<E>(tid, p, [&](int j, bool ok) {
       const double z = a.z[j], g = a.g[j];
       const double dg = g - a.gprev[j], dzz = z - a.zprev[j];
@@ -1037,7 +832,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
         us[j] = z - step * g;
       }
     });
-    prox_image(step, nullptr);
+    tail_prox_image<E>(us, a, pt, step, group_pen, nullptr);
     tail_for<E>(tid, p, [&](int j, bool ok) {
       const double bn = us[j];
       const double dz = bn - a.z[j], db = bn - a.beta[j];
@@ -1049,60 +844,33 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
       }
     });
     block_sum<9>(s, red);
-    nonfinite = s[6] > 0.0 || !isfinite(s[0]) || !isfinite(s[1]) || !isfinite(loss_z);
-    if (total_iter > 0 && s[4] > 1e-12 * s[5] && s[4] > 0.0) {
-      const double curv = sqrt(s[3] / s[4]);
-      if (curv > L * (1.0 + 1e-9)) {
-        l_bad = true;
-        new_L = 1.02 * curv;
-      }
-      if (s[8] > 0.0 && s[3] > 1e-20 * s[7]) new_mu_rq = mu_rq_old > 0.0 ? fmin(mu_rq_old, s[8] / s[4]) : s[8] / s[4];
-    }
-    did_restart = !(flags & SLM_FLAG_NO_RESTART) && s[2] > 0.0;
-    const double t_use = did_restart ? 1.0 : t_old;
-    const double t_new = 0.5 * (1.0 + sqrt(1.0 + 4.0 * t_use * t_use));
-    mom = (t_use - 1.0) / t_new;
-    resid = sqrt(s[0]);
-    bnorm = sqrt(s[1]);
-    kkt = resid * L;
-    mu_eff = mu_ws > 0.0 ? fmin(mu_ws, L) : L;
-    if (new_mu_rq > 0.0) mu_eff = fmin(mu_eff, new_mu_rq);
-    mu_eff = fmax(mu_eff, kMuFloor * L);
-    conv = !a.provisional && !l_bad && (kkt <= fmax(tol * fmax(bnorm, bnorm_floor) * mu_eff, kRoundFloor * (sqrt(s[7]) + L * bnorm)));
-    finalize = nonfinite || conv || hit_max;
-    new_t = l_bad ? 1.0 : t_new;
+    fista_decide(c, n, s);
   }
 
   // ---- state update --------------------------------------------------------------------------
-  double extrap = 0.0;
-  const int stride = ctl->stride > 1 ? ctl->stride : 1;
-  if (finalize && !cold && !nonfinite && stride == 1 && point - pt_lo >= 1 && point + 1 < n_points)
-    extrap = a.pts[point + 1].extrap;
-  const int tail_pt = ctl->tail_pt;
-  const bool walk_end = point + stride >= n_points;
-  const bool range_end = finalize && !nonfinite && walk_end && (tail_pt < 0 || point == tail_pt);
-  const bool goes_idle = range_end && a.steal;
+  const TailRoute r = tail_route(c, n, a.steal != 0);
+  const double extrap = r.secant ? a.pts[c.point + 1].extrap : 0.0;
   tail_for<E>(tid, p, [&](int j, bool ok) {
     double nbv, uu;  // new base, next point (or the reported solution)
     const double image = us[j];
-    if (mode == 1) {
+    if (c.mode == 1) {
       nbv = a.zprev[j];
       uu = image;
     } else {
       const double bold = a.beta[j];
-      if (l_bad) {
+      if (n.l_bad) {
         nbv = bold;
         uu = bold;
       } else {
         nbv = image;
-        uu = finalize ? image : image + mom * (image - bold);
+        uu = n.finalize ? image : image + n.mom * (image - bold);
       }
     }
     if (!ok) return;
-    if (finalize) {
-      a.betas_out[(int64_t)point * p + j] = uu;
-      double nxt = (cold || goes_idle) ? 0.0 : uu;
-      if (extrap != 0.0) nxt = uu + extrap * (uu - a.betas_out[(int64_t)(point - 1) * p + j]);
+    if (n.finalize) {
+      a.betas_out[(int64_t)c.point * p + j] = uu;
+      double nxt = (c.cold || r.goes_idle) ? 0.0 : uu;
+      if (extrap != 0.0) nxt = uu + extrap * (uu - a.betas_out[(int64_t)(c.point - 1) * p + j]);
       a.beta[j] = nxt;
       a.z[j] = nxt;
       us[j] = uu;  // (the group norms below read the reported solution)
@@ -1111,70 +879,12 @@ __global__ __launch_bounds__(TAIL_THREADS) void fista_tail_stream_kernel(TailArg
       a.z[j] = uu;
     }
   });
-  if (finalize && a.gn_out != nullptr) {
+  if (n.finalize && a.gn_out != nullptr) {
     __syncthreads();
-    double* gn = a.gn_out + (int64_t)point * G;
+    double* gn = a.gn_out + (int64_t)c.point * G;
     for_each_group_sumsq(us, a.order, a.gstart, G, a.team, [&](int g, double ss) { gn[g] = sqrt(ss); });
   }
-
-  // ---- control block (as in fista_tail_kernel) ---------------------------------------------------
-  if (tid == 0) {
-    if (stored) light_commit(a, lane_id);
-    ctl->zzero = 0;
-    ctl->total_iter = total_iter + 1;
-    ctl->L = new_L;
-    ctl->mode = new_mode;
-    ctl->rejects = new_rejects;
-    ctl->ak = new_ak;
-    ctl->Lhat = new_Lhat;
-    ctl->loss_base = new_loss_base;
-    if (l_bad) ctl->l_bumps += 1;
-    if (did_restart) ctl->restarts += 1;
-    if (finalize) {
-      slm_point_info info;
-      info.n_iter = iter + 1;
-      info.status = (conv && !nonfinite) ? SLM_OK : (nonfinite ? SLM_ERR_NON_FINITE : SLM_ERR_NOT_CONVERGED);
-      info.resid = resid;
-      info.beta_norm = bnorm;
-      info.loss = loss_z;
-      info.L = new_mode == 1 ? new_ak : new_L;
-      info.mode = new_mode;
-      info.rejects = new_rejects;
-      info.kkt = kkt;
-      info.mu = mu_eff;
-      a.infos[point] = info;
-      ctl->mu = 0.0;
-      ctl->mu_rq = 0.0;
-      ctl->iter = 0;
-      ctl->t = 1.0;
-      ctl->have_base = 0;
-      ctl->n_hist = 0;
-      ctl->pen_z = 0.0;
-      ctl->point = (walk_end && tail_pt >= 0 && point != tail_pt) ? tail_pt : point + stride;
-      if (nonfinite) {
-        ctl->nonfinite = 1;
-        ctl->done = 1;
-        a.gdone[a.done_slot] = 1;
-      } else if (goes_idle) {
-        ctl->idle = 1;
-      } else if (range_end) {
-        ctl->done = 1;
-        if (atomicAdd(&a.gdone[1], 1) + 1 == a.n_lanes) a.gdone[a.done_slot] = 1;
-      }
-    } else {
-      ctl->iter = iter + 1;
-      atomicMax(&a.gdone[2], iter + 1);
-      ctl->t = new_t;
-      // (a call on an estimated gradient leaves no base behind: the first true gradient starts the history, and a
-      //  rejection can never fall back on the estimate)
-      ctl->have_base = a.provisional ? 0 : new_have_base;
-      ctl->n_hist = a.provisional ? 0 : new_n_hist;
-      ctl->pen_z = new_pen_z;
-      ctl->mu_rq = new_mu_rq;
-#pragma unroll
-      for (int k = 0; k < BB_HIST; ++k) ctl->hist[k] = hist[k];
-    }
-  }
+  if (tid == 0) tail_commit(a, ctl, lane_id, c, n, r);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Audit of a path's certificates: every point the engine reports is checked against X itself.
 
-The tail kernel (csrc/tail_kernels.hpp, ``fista_tail_body``) reports ``u = prox_s(z - s g(z))`` for a base point z, with
+The tail kernel (csrc/tail_kernels.hpp, ``fista_tail_kernel`` / ``fista_tail_stream_kernel``; the rule itself:
+csrc/tail_logic.hpp) reports ``u = prox_s(z - s g(z))`` for a base point z, with
 ``info.kkt = ||G_s(z)||`` (G_s the proximal-gradient mapping) and ``info.L = 1 / s`` -- the inverse step that produced u, in
 both schemes (spectral: ``ak``; FISTA: ``L``).  From ``(z - u) / s - g(z) in dh(u)``:
 

@@ -1,4 +1,5 @@
-// CPU test of csrc/host_logic.hpp -- the engine's device-free bookkeeping -- meant to run under AddressSanitizer and
+// CPU test of csrc/host_logic.hpp -- the engine's device-free bookkeeping -- and of csrc/tail_logic.hpp -- the scalar state
+// machine of the tail kernels, the very functions the device runs -- meant to run under AddressSanitizer and
 // UndefinedBehaviorSanitizer (tools/sanitize.sh; tests/test_host_logic_cpu.py builds and runs it plainly in the CPU suite).
 // Every check is against an independent statement of what the function must do; a randomised pool run models the
 // allocator with malloc/free so that a double release or a leak is the sanitizers' to find.
@@ -11,8 +12,10 @@
 #include <string>
 
 #include "../sparse-lm_amd/csrc/host_logic.hpp"
+#include "../sparse-lm_amd/csrc/tail_logic.hpp"
 
 using namespace slm_host;
+using namespace slm;
 
 static int failures = 0;
 #define CHECK(cond)                                                           \
@@ -293,6 +296,330 @@ static void test_knobs() {
   CHECK(k.ws == 1 && k.mg == 0 && k.trace == 1 && k.ws_theta == 0.85 && k.split);
 }
 
+
+// ---- csrc/tail_logic.hpp --------------------------------------------------------------------------------------------
+// A lane in the middle of a point: L = 4, ak = 2, Lhat = 3, one accepted value (10) in the ring, pen_z = 0.5, loss_z = 1.
+// The numbers are small dyadic ones wherever a check is an equality, so that no rounding is involved.
+static const double kFloor = 16.0 * 2.220446049250313e-16;  // kRoundFloor: a copy, the HIP header that defines it (tail_kernels.hpp) cannot be
+                                                            // included here; the checks below need a floor, not this value
+static TailSnap tail_snap(int mode, double loss_z = 1.0, bool provisional = false) {
+  TailSnap c{};
+  c.point = 1; c.n_points = 4; c.pt_lo = 0; c.stride = 1; c.tail_pt = -1;
+  c.iter = 3; c.max_iter = 1000; c.total_iter = 10; c.flags = 0;
+  c.mode = mode; c.have_base = 1; c.rejects = 0; c.n_hist = 1;
+  c.t = 2.0; c.L = 4.0; c.tol = 1e-6; c.ak = 2.0; c.Lhat = 3.0; c.pen_z = 0.5; c.mu = 0.0; c.mu_rq = 0.0; c.loss_base = 7.0;
+  c.hist[0] = 10.0;
+  for (int k = 1; k < BB_HIST; ++k) c.hist[k] = 1000.0;  // (beyond n_hist: stale, never to be looked at)
+  tail_snap_call(c, loss_z, provisional, kFloor);
+  return c;
+}
+
+static void test_tail_snapshot() {
+  TailSnap c = tail_snap(1, 8.0);
+  CHECK(!c.hit_max && !c.cold && !c.provisional && c.loss_z == 8.0 && c.bnorm_floor == 1e-10 * sqrt(2.0 * 8.0 / 4.0));
+  c.Lhat = 16.0; c.flags = SLM_FLAG_COLD_START; c.max_iter = c.iter + 1;
+  tail_snap_call(c, -1.0, true, kFloor);  // (a loss below zero counts as zero; the larger of L and Lhat scales the floor)
+  CHECK(c.hit_max && c.cold && c.provisional && c.bnorm_floor == 0.0);
+  c.max_iter = c.iter + 2;
+  tail_snap_call(c, 8.0, false, kFloor);
+  CHECK(!c.hit_max && c.bnorm_floor == 1e-10 * sqrt(2.0 * 8.0 / 16.0));
+  const TailNext n = tail_next(c);
+  CHECK(n.mode == c.mode && n.have_base == c.have_base && n.rejects == c.rejects && n.n_hist == c.n_hist && n.t == c.t && n.L == c.L &&
+        n.ak == c.ak && n.Lhat == c.Lhat && n.pen_z == c.pen_z && n.mu_rq == c.mu_rq && n.loss_base == c.loss_base);
+  CHECK(n.stored && !n.finalize && !n.conv && !n.nonfinite && !n.did_restart && !n.l_bad && !n.fallback);
+}
+
+static void test_bb_decide() {
+  {  // first call of a point: the start point is the base whatever the ring held, its penalty is s[4]
+    TailSnap c = tail_snap(1);
+    c.have_base = 0; c.n_hist = 3;
+    TailNext n = tail_next(c);
+    const double s[6] = {1.0, 1.0, 1.0, 0.0, 0.25, 4.0};
+    CHECK(bb_decide(c, n, s));
+    CHECK(n.n_hist == 1 && n.hist[0] == 1.25 && n.have_base == 1 && n.loss_base == 1.0 && n.stored && !n.nonfinite && !n.fallback);
+    CHECK(n.ak == 2.0 && n.Lhat == 3.0 && n.rejects == 0 && n.mu_rq == 0.0);
+  }
+  // accept and reject against a ring of 1, BB_HIST - 1 and BB_HIST entries: the reference is the largest VALID entry
+  // (top), the candidate must lie below it by sigma/2 ak ||dz||^2 = 1e-4
+  for (int nh : {1, BB_HIST - 1, BB_HIST})
+    for (int accept_it = 0; accept_it < 2; ++accept_it)
+      for (int top_at = 0; top_at < nh; top_at += (nh > 1 ? nh - 1 : 1)) {  // the largest entry first, or last
+        const double top = 20.0;
+        TailSnap c = tail_snap(1, accept_it ? top - 1.5 : top - 0.5);  // F(z) = loss_z + pen_z = top - 1 | top
+        c.n_hist = nh; c.mu_rq = 1.5;
+        for (int k = 0; k < nh; ++k) c.hist[k] = 10.0 + k;
+        c.hist[top_at] = top;
+        TailNext n = tail_next(c);
+        const double s[6] = {1.0, 2.0, 9.0, 0.0, 99.0, 4.0};
+        const bool accept = bb_decide(c, n, s);
+        CHECK(accept == (accept_it != 0) && n.stored == accept && !n.nonfinite && !n.fallback);
+        if (accept) {
+          CHECK(n.Lhat == 3.0 && n.ak == 2.0 && n.mu_rq == 1.5 && n.rejects == 0 && n.have_base == 1 && n.loss_base == c.loss_z);
+          if (nh < BB_HIST) {
+            CHECK(n.n_hist == nh + 1 && n.hist[nh] == top - 1.0);
+            for (int k = 0; k < nh; ++k) CHECK(n.hist[k] == c.hist[k]);
+          } else {  // full: the oldest value leaves
+            CHECK(n.n_hist == BB_HIST && n.hist[BB_HIST - 1] == top - 1.0);
+            for (int k = 0; k + 1 < BB_HIST; ++k) CHECK(n.hist[k] == c.hist[k + 1]);
+          }
+        } else {
+          CHECK(n.ak == 4.0 && n.rejects == 1 && n.n_hist == nh && n.Lhat == 3.0 && n.mu_rq == 1.5 && n.loss_base == 7.0);
+          for (int k = 0; k < BB_HIST; ++k) CHECK(n.hist[k] == c.hist[k]);
+        }
+      }
+  {  // the margin itself: just below the reference is not enough
+    TailSnap c = tail_snap(1, 10.0 - 0.5 - 0.5e-4);
+    TailNext n = tail_next(c);
+    const double s[6] = {1.0, 2.0, 9.0, 0.0, 0.0, 4.0};
+    CHECK(!bb_decide(c, n, s));
+    c = tail_snap(1, 10.0 - 0.5 - 2e-4);
+    n = tail_next(c);
+    CHECK(bb_decide(c, n, s));
+  }
+  // ak: the quotient <dz,dg>/<dz,dz>, Lhat where that is not positive, unchanged for a zero step; clamped to
+  // [1e-6, 1e6] Lhat; a larger curvature ||dg||/||dz|| raises Lhat; the first quotient of a point starts mu_rq
+  struct { double s0, s1, s2, ak, Lhat, mu_rq; } cases[] = {
+      {1.0, 2.0, 9.0, 2.0, 3.0, 2.0},        {1.0, 2.0, 25.0, 2.0, 5.0, 2.0},           {1.0, 1e-9, 9.0, 1e-6 * 3.0, 3.0, 1e-6 * 3.0},
+      {1.0, 1e8, 9.0, 1e6 * 3.0, 3.0, 1e6 * 3.0}, {1.0, -1.0, 9.0, 3.0, 3.0, 0.0}, {0.0, 0.0, 0.0, 2.0, 3.0, 0.0}};
+  for (const auto& k : cases) {
+    const TailSnap c = tail_snap(1, 0.0);
+    TailNext n = tail_next(c);
+    const double s[6] = {k.s0, k.s1, k.s2, 0.0, 0.0, 4.0};
+    CHECK(bb_decide(c, n, s));
+    CHECK(n.ak == k.ak && n.Lhat == k.Lhat && n.mu_rq == k.mu_rq);
+  }
+  {  // a rejected step doubles ak, up to 1e6 Lhat
+    TailSnap c = tail_snap(1, 100.0);
+    c.ak = 2e6;
+    TailNext n = tail_next(c);
+    const double s[6] = {1.0, 2.0, 9.0, 0.0, 0.0, 4.0};
+    CHECK(!bb_decide(c, n, s) && n.ak == 1e6 * 3.0);
+  }
+  // mu_rq is left alone when the step is at the rounding level of the iterate (first) or of the gradient (second)
+  for (int which = 0; which < 2; ++which) {
+    TailSnap c = tail_snap(1, 0.0);
+    c.mu_rq = 0.75;
+    TailNext n = tail_next(c);
+    const double s[6] = {which ? 1.0 : 1e-30, which ? 1.0 : 1e-30, which ? 1e-10 : 1e-30, 0.0, 0.0, 1e12};
+    CHECK(bb_decide(c, n, s) && n.mu_rq == 0.75 && n.ak == 1.0);
+  }
+  // fallback: at exactly BB_REJECT_LIMIT rejects, and when the call is iteration BB_POINT_LIMIT + 1 of its point
+  for (int rej = 0; rej < BB_REJECT_LIMIT; ++rej)
+    for (int accept_it = 0; accept_it < 2; ++accept_it) {
+      TailSnap c = tail_snap(1, accept_it ? 0.0 : 100.0);
+      c.rejects = rej;
+      TailNext n = tail_next(c);
+      const double s[6] = {1.0, 2.0, 25.0, 0.0, 0.0, 4.0};
+      CHECK(bb_decide(c, n, s) == (accept_it != 0));
+      CHECK(n.fallback == (!accept_it && rej == BB_REJECT_LIMIT - 1));
+      if (n.fallback) {
+        bb_fallback(c, n);
+        CHECK(n.mode == 0 && n.t == 1.0 && n.L == 4.0 && !n.finalize && n.rejects == BB_REJECT_LIMIT);
+      }
+    }
+  for (int it : {BB_POINT_LIMIT - 1, BB_POINT_LIMIT}) {
+    TailSnap c = tail_snap(1, 0.0);
+    c.iter = it;
+    c.max_iter = BB_POINT_LIMIT + 1;
+    tail_snap_call(c, 0.0, false, kFloor);
+    TailNext n = tail_next(c);
+    const double s[6] = {1.0, 2.0, 25.0, 0.0, 0.0, 4.0};
+    CHECK(bb_decide(c, n, s) && n.fallback == (it == BB_POINT_LIMIT));
+    if (n.fallback) {  // FISTA takes the largest curvature seen; a point out of iterations is reported as it stands
+      bb_fallback(c, n);
+      CHECK(n.mode == 0 && n.t == 1.0 && n.L == 5.0 && c.hit_max && n.finalize && tail_status(n) == SLM_ERR_NOT_CONVERGED);
+    }
+  }
+  {  // a non-finite gradient or objective: no fallback, the point ends in bb_stop
+    TailSnap c = tail_snap(1, 100.0);
+    c.rejects = BB_REJECT_LIMIT - 1;
+    TailNext n = tail_next(c);
+    const double s[6] = {1.0, 2.0, 9.0, 1.0, 0.0, 4.0};
+    CHECK(!bb_decide(c, n, s) && n.nonfinite && !n.fallback);
+    c = tail_snap(1, INFINITY);
+    n = tail_next(c);
+    const double s2[6] = {1.0, 2.0, 9.0, 0.0, 0.0, 4.0};
+    bb_decide(c, n, s2);
+    CHECK(n.nonfinite && !n.fallback);
+  }
+}
+
+static void test_bb_stop() {
+  const double s[6] = {1.0, 2.0, 9.0, 0.0, 0.0, 4.0};
+  auto run = [&](TailSnap c, const double (&q)[4]) {
+    TailNext n = tail_next(c);
+    CHECK(bb_decide(c, n, s));
+    bb_stop(c, n, s, q);
+    return n;
+  };
+  const double far[4] = {1.0, 1.0, 0.125, 0.0}, there[4] = {0.0, 1.0, 0.125, 0.0};
+  TailNext n = run(tail_snap(1, 0.0), far);
+  CHECK(!n.conv && !n.finalize && !n.nonfinite && n.pen_z == 0.125 && n.resid == 1.0 && n.bnorm == 1.0 && n.kkt == 2.0 && n.mu_eff == 2.0);
+  {  // mu: the smallest of ak, Lhat, the point's quotients and the model solver's estimate, floored at kMuFloor Lhat
+    TailSnap c = tail_snap(1, 0.0);
+    c.mu_rq = 1.5;
+    CHECK(run(c, far).mu_eff == 1.5);
+    c.mu = 0.5;
+    CHECK(run(c, far).mu_eff == 0.5);
+    c.mu = 1e-9;
+    CHECK(run(c, far).mu_eff == kMuFloor * 3.0);
+    c = tail_snap(1, 0.0);
+    c.ak = 8.0;  // (a step shorter than 1 / Lhat: the residual is reported at the scale of Lhat)
+    const double s0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 4.0};
+    TailNext m = tail_next(c);
+    CHECK(bb_decide(c, m, s0) && m.ak == 8.0);
+    bb_stop(c, m, s0, far);
+    CHECK(m.resid == 8.0 / 3.0 && m.kkt == 8.0 && m.mu_eff == 3.0);
+  }
+  n = run(tail_snap(1, 0.0), there);
+  CHECK(n.conv && n.finalize && tail_status(n) == SLM_OK && n.kkt == 0.0);
+  n = run(tail_snap(1, 0.0, true), there);  // an estimated gradient accepts no point
+  CHECK(!n.conv && !n.finalize);
+  {  // the rule itself: kkt <= tol * ||c|| * mu, one ulp either side (q[1] = 1, mu = ak = 2: the bound is 2 tol)
+    TailSnap c = tail_snap(1, 0.0);
+    c.tol = 0.25;
+    const double in[4] = {0.0625, 1.0, 0.0, 0.0}, out[4] = {0.0625 * (1.0 + 1e-15), 1.0, 0.0, 0.0};
+    CHECK(run(c, in).conv && !run(c, out).conv);
+    const double tiny[4] = {0.0625, 1e-40, 0.0, 0.0};  // ||c|| below the floor: the floor stands in
+    CHECK(c.bnorm_floor == 0.0 && !run(c, tiny).conv);
+    c.hist[0] = 1e21;
+    tail_snap_call(c, 8e20, false, kFloor);  // (rms residual / sqrt(L) = sqrt(2 * 8e20 / 4): the floor is 1e-10 of it)
+    CHECK(c.bnorm_floor == 2.0 && run(c, tiny).conv);
+  }
+  {
+    TailSnap c = tail_snap(1, 0.0);
+    c.max_iter = c.iter + 1;
+    tail_snap_call(c, 0.0, false, kFloor);
+    n = run(c, far);
+    CHECK(!n.conv && n.finalize && tail_status(n) == SLM_ERR_NOT_CONVERGED);
+  }
+  const double bad1[4] = {1.0, 1.0, 0.0, 1.0}, bad2[4] = {INFINITY, 1.0, 0.0, 0.0}, bad3[4] = {0.0, NAN, 0.0, 0.0};
+  for (const auto* q : {&bad1, &bad2, &bad3}) {
+    n = run(tail_snap(1, 0.0), *q);
+    const TailRoute r = tail_route(tail_snap(1, 0.0), n, true);
+    CHECK(n.nonfinite && n.finalize && tail_status(n) == SLM_ERR_NON_FINITE && !r.range_end && !r.goes_idle && !r.secant);
+  }
+}
+
+static void test_fista_decide() {
+  //                 ||b+-z||^2 ||b+||^2 restart ||dg||^2 ||dz||^2 ||z||^2 bad ||g||^2 <dg,dz>
+  const double plain[9] = {1.0, 1.0, -1.0, 4.0, 1.0, 1.0, 0.0, 4.0, 2.0};
+  TailSnap c = tail_snap(0);
+  TailNext n = tail_next(c);
+  fista_decide(c, n, plain);
+  const double t17 = 0.5 * (1.0 + sqrt(17.0));
+  CHECK(!n.l_bad && !n.did_restart && !n.conv && !n.finalize && n.L == 4.0 && n.t == t17 && n.mom == 1.0 / t17);
+  CHECK(n.resid == 1.0 && n.bnorm == 1.0 && n.kkt == 4.0 && n.mu_rq == 2.0 && n.mu_eff == 2.0 && n.loss_base == 1.0 && n.stored);
+  c.mu = 0.5; c.mu_rq = 1.0;
+  n = tail_next(c);
+  fista_decide(c, n, plain);
+  CHECK(n.mu_rq == 1.0 && n.mu_eff == 0.5);
+  {  // the curvature guard: ||dg||/||dz|| = 10 > L raises L to 1.02 * 10, drops the momentum and forbids conv, even at a
+     // fixed point of the step; exactly L does not trip it, and neither does the first call of a solve or a move of z at the rounding level
+    const double bad[9] = {0.0, 1.0, -1.0, 100.0, 1.0, 1.0, 0.0, 4.0, 2.0};
+    c = tail_snap(0);
+    n = tail_next(c);
+    fista_decide(c, n, bad);
+    CHECK(n.l_bad && n.L == 1.02 * 10.0 && n.t == 1.0 && !n.conv && !n.finalize && n.kkt == 0.0);
+    const double edge[9] = {0.0, 1.0, -1.0, 16.0, 1.0, 1.0, 0.0, 4.0, 2.0};
+    n = tail_next(c);
+    fista_decide(c, n, edge);
+    CHECK(!n.l_bad && n.L == 4.0 && n.conv && n.finalize && tail_status(n) == SLM_OK);
+    c.total_iter = 0;
+    n = tail_next(c);
+    fista_decide(c, n, bad);
+    CHECK(!n.l_bad && n.L == 4.0 && n.mu_rq == 0.0);
+    c = tail_snap(0);
+    const double still[9] = {0.0, 1.0, -1.0, 100e-13, 1e-13, 1.0, 0.0, 4.0, 2.0};
+    n = tail_next(c);
+    fista_decide(c, n, still);
+    CHECK(!n.l_bad && n.L == 4.0);
+  }
+  {  // restart when the step turns against the last move, unless the caller forbids it
+    const double back[9] = {1.0, 1.0, 0.5, 4.0, 1.0, 1.0, 0.0, 4.0, 2.0};
+    c = tail_snap(0);
+    n = tail_next(c);
+    fista_decide(c, n, back);
+    CHECK(n.did_restart && n.mom == 0.0 && n.t == 0.5 * (1.0 + sqrt(5.0)));
+    c.flags = SLM_FLAG_NO_RESTART;
+    n = tail_next(c);
+    fista_decide(c, n, back);
+    CHECK(!n.did_restart && n.t == t17 && n.mom == 1.0 / t17);
+  }
+  const double there[9] = {0.0, 1.0, -1.0, 4.0, 1.0, 1.0, 0.0, 4.0, 2.0};
+  c = tail_snap(0, 1.0, true);
+  n = tail_next(c);
+  fista_decide(c, n, there);
+  CHECK(!n.conv && !n.finalize);
+  c = tail_snap(0);
+  c.max_iter = c.iter + 1;
+  tail_snap_call(c, 1.0, false, kFloor);
+  n = tail_next(c);
+  fista_decide(c, n, plain);
+  CHECK(!n.conv && n.finalize && tail_status(n) == SLM_ERR_NOT_CONVERGED);
+  for (int which = 0; which < 4; ++which) {  // a non-finite count, sum or loss ends the point and the path
+    double s[9];
+    for (int k = 0; k < 9; ++k) s[k] = plain[k];
+    if (which == 0) s[6] = 1.0;
+    if (which == 1) s[0] = NAN;
+    if (which == 2) s[1] = INFINITY;
+    c = tail_snap(0, which == 3 ? NAN : 1.0);
+    c.point = 3;  // (the last point of the range: it would otherwise end the range)
+    n = tail_next(c);
+    fista_decide(c, n, s);
+    const TailRoute r = tail_route(c, n, false);
+    CHECK(n.nonfinite && n.finalize && tail_status(n) == SLM_ERR_NON_FINITE && !r.range_end && !r.goes_idle);
+  }
+}
+
+static void test_tail_route() {
+  TailNext done = tail_next(tail_snap(1)), going = done;
+  done.finalize = true;
+  for (int steal = 0; steal < 2; ++steal) {
+    TailSnap c = tail_snap(1);  // points 0..3, the lane stands on 1
+    TailRoute r = tail_route(c, done, steal != 0);
+    CHECK(r.secant && !r.range_end && !r.goes_idle && r.next_point == 2);
+    r = tail_route(c, going, steal != 0);  // (an unfinished point moves nothing)
+    CHECK(!r.secant && !r.range_end && !r.goes_idle);
+    c.flags = SLM_FLAG_COLD_START;
+    tail_snap_call(c, 1.0, false, kFloor);
+    CHECK(!tail_route(c, done, steal != 0).secant);
+    c = tail_snap(1);
+    c.point = 0;  // the first point of the range has no predecessor for the secant ...
+    CHECK(!tail_route(c, done, steal != 0).secant && tail_route(c, done, steal != 0).next_point == 1);
+    c.point = 2; c.pt_lo = 2;  // ... nor has the first point of a range taken over
+    CHECK(!tail_route(c, done, steal != 0).secant);
+    c = tail_snap(1);
+    c.point = 3;  // the last point, no tail point: the range ends; on a shared path the lane waits for work
+    r = tail_route(c, done, steal != 0);
+    CHECK(!r.secant && r.range_end && r.goes_idle == (steal != 0) && r.next_point == 4);
+    r = tail_route(c, going, steal != 0);
+    CHECK(!r.range_end && !r.goes_idle);
+    c.tail_pt = 9;  // the last regular point with a tail point to visit: on to it
+    r = tail_route(c, done, steal != 0);
+    CHECK(!r.range_end && !r.goes_idle && r.next_point == 9);
+    c.point = 9;  // the tail point itself (it lies beyond n_points): the range ends
+    r = tail_route(c, done, steal != 0);
+    CHECK(r.range_end && r.goes_idle == (steal != 0) && r.next_point == 10 && !r.secant);
+    // interleaved lanes: every sixteenth point of 48, no secant through the neighbours' points
+    c = tail_snap(1);
+    c.n_points = 48; c.stride = 16; c.point = 21; c.pt_lo = 5; c.tail_pt = 49;
+    r = tail_route(c, done, steal != 0);
+    CHECK(!r.secant && !r.range_end && r.next_point == 37);
+    c.point = 37;
+    r = tail_route(c, done, steal != 0);
+    CHECK(!r.range_end && r.next_point == 49);
+    c.tail_pt = -1;
+    r = tail_route(c, done, steal != 0);
+    CHECK(r.range_end && r.next_point == 53);
+    c.n_points = 54;  // (one more regular point)
+    CHECK(!tail_route(c, done, steal != 0).range_end && tail_route(c, done, steal != 0).next_point == 53);
+    c = tail_snap(1);
+    c.stride = 0;  // (a control block that never set it walks point by point)
+    CHECK(tail_route(c, done, steal != 0).next_point == 2 && tail_route(c, done, steal != 0).secant);
+  }
+}
+
 int main() {
   test_pool();
   test_row_sets();
@@ -302,6 +629,11 @@ int main() {
   test_grid();
   test_find_and_tiles();
   test_knobs();
+  test_tail_snapshot();
+  test_bb_decide();
+  test_bb_stop();
+  test_fista_decide();
+  test_tail_route();
   if (failures) {
     fprintf(stderr, "host_logic_test: %d check(s) failed\n", failures);
     return 1;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # AddressSanitizer + UndefinedBehaviorSanitizer over the host code that runs without a GPU (GPU sanitizers are
 # not available on the pool, and this script is for the BUILD CONTAINER only -- never the GPU box):
-#   1. csrc/host_logic.hpp -- the engine's device-free bookkeeping, the file engine*.hip include -- through tests/host_logic_test.cpp;
+#   1. csrc/host_logic.hpp -- the engine's device-free bookkeeping, the file engine*.hip include -- and csrc/tail_logic.hpp -- the tail
+#      kernels' scalar state machine -- through tests/host_logic_test.cpp;
 #   2. csrc/binding.cpp -- the pybind11 module of the hot calls -- built with the sanitizers (sparse-lm_amd/build.py, SLM_SANITIZE=1)
 #      and driven by tests/test_binding_cpu.py and tests/test_abi.py with the runtimes preloaded into python.
 # usage: bash tools/sanitize.sh [log]      (default log: profiles/r06_sanitizers.log)
