@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SLM_ABI_VERSION 23
+#define SLM_ABI_VERSION 24
 
 typedef enum slm_status {
   SLM_OK = 0,
@@ -45,7 +45,8 @@ typedef enum slm_status {
   SLM_ERR_HIP = 3,          /* -> RuntimeError (HIP runtime / kernel failure) */
   SLM_ERR_NO_DEVICE = 4,    /* -> RuntimeError (no gfx950 device visible) */
   SLM_ERR_COMM = 5,         /* -> RuntimeError (RCCL failure) */
-  SLM_ERR_NOT_CONVERGED = 6,/* informational: reported per path point, never returned by solve */
+  SLM_ERR_NOT_CONVERGED = 6,/* informational: reported per path point, never returned by solve; slm_solve_l0 returns
+                               it (with valid outputs) when its node budget ran out */
   SLM_ERR_NON_FINITE = 7,   /* -> RuntimeError: non-finite value in the iterate (the reference's
                                counterpart is cvxpy's SolverError / "infeasible" RuntimeError,
                                model/_adaptive_lasso.py:216-220) */
@@ -579,6 +580,33 @@ int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, const double* b
 int slm_solve_constrained(slm_dataset* ds, const double* a, const double* A, int32_t m, const double* lo, const double* hi,
                           const slm_solve_opts* opts, double tol_inner, int32_t max_sweeps, const double* beta0, int32_t warm,
                           double* beta_out, double* lambda_out, slm_point_info* info);
+
+/*
+ * (ABI 24) The exact l0 estimators -- the reference's mixed-integer family BestSubsetSelection, RidgedBestSubsetSelection,
+ * RegularizedL0 and L2L0 (src/sparselm/model/_miqp/_best_subset.py:95-124, 215-248; _regularized_l0.py:115-144, 502-530),
+ * which it hands to Gurobi / SCIP through cvxpy -- by a depth-first search over supports on chip (csrc/l0_kernels.hpp).
+ * The reference's objectives divided by 2n (_miqp/_base.py:126-127, _regularized_l0.py:157-161, _base.py:544-546): with
+ * G = X^T W X / n and c = X^T W y / n of the dataset (its row weights, its centring),
+ *   minimise over supports S (sets of the dataset's GROUPS, slm_dataset_set_groups) and beta with supp beta in cols(S),
+ *   |beta_j| <= big_M:      1/2 beta^T (G + 2 eta T) beta - c^T beta + alpha |S|
+ *   subject to  |S| <= max_groups   and   i in S => need[i] subset of S.
+ * T: p x p, row-major (only its symmetric part acts), NULL: the identity.  need: one mask per group over the groups (bit h
+ * of need[i]: group i may only be active when group h is), NULL: no hierarchy.  max_nodes <= 0: the engine's default budget.
+ * Up to 64 columns and 64 groups (SLM_ERR_UNSUPPORTED beyond, and on row-sharded datasets).  Negative or non-finite alpha
+ * / eta, negative big_M, a need bit at or beyond the group count: SLM_ERR_BAD_ARG before anything is launched.  The
+ * dataset's Gram is the one slm_dataset_covariance keeps (built on first use).
+ * beta_out [p]: the winner's coefficients, recomputed once on the host from the Gram on its support (so they do not depend
+ * on which wavefront found it); support_out: bit i = group i active; *lower_bound_out: the proven lower bound of the
+ * objective, equal to it when the search finished; *nodes_out: group inclusions tried.  info->loss = 1/(2n)||X beta - y||_W^2,
+ * info->n_iter = launches, info->kkt = the objective above, info->mu = the objective of the greedy seed, info->L = the
+ * unconstrained quadratic value on all columns (the bound's q_all), info->mode = 4, info->status = SLM_OK or
+ * SLM_ERR_NOT_CONVERGED.  When the node budget runs out every wavefront drains, the outputs hold the incumbent and the call
+ * returns SLM_ERR_NOT_CONVERGED.
+ */
+int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T /* p*p or NULL */,
+                 double big_M, const uint64_t* need /* n_groups masks or NULL */, int64_t max_nodes /* <=0: default */,
+                 double* beta_out, uint64_t* support_out, double* lower_bound_out, int64_t* nodes_out,
+                 slm_point_info* info);
 
 /*
  * The Gram of a row set, for covariance passes (SLM_FLAG_COVARIANCE): G = X^T W X / n_eff, c = X^T W y / n_eff and

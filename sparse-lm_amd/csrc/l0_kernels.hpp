@@ -1,0 +1,315 @@
+// Exact l0 estimators (the reference's mixed-integer family: BestSubsetSelection, RidgedBestSubsetSelection, RegularizedL0,
+// L2L0 -- src/sparselm/model/_miqp/_best_subset.py, _regularized_l0.py) by a depth-first search over supports on chip.
+//
+//     minimise over supports S (sets of groups) and beta, supp beta in cols(S), |beta_j| <= big_M:
+//         1/2 beta^T H beta - c^T beta + alpha |S|        H = G + 2 eta T,  G = X^T X / n,  c = X^T y / n
+//     subject to |S| <= K and i in S => need[i] in S
+//
+// The host hands over H, c and the groups in SEARCH ORDER (a group's columns contiguous, groups by descending
+// ||c_g||^2 / tr G_gg).  One wavefront owns one subtree at a time: the subtrees are the 2^d include / exclude prefixes of
+// the first d = min(groups, 16) groups, handed out by a ticket counter.  Inside a wave lane r holds row r of the Cholesky
+// factor L of H on the included columns (in registers: every index into the row is a compile-time constant, the loops over
+// its entries are unrolled and guarded by the wave-uniform column count) and entry r of w = L^-1 c.  Including a group
+// appends its columns by a column-oriented forward substitution -- one cross-lane broadcast per step; excluding one costs
+// nothing; backtracking is lowering the column count.  The quadratic value of a support is -1/2 ||w||^2, so a node is
+// evaluated without a back-substitution.
+//
+// Pruning, all exact: cardinality; hierarchy (an included group needs an excluded one); and the bound
+// q_all + alpha (|S| + 1) >= incumbent for everything below a node, q_all the unconstrained value on all columns -- the
+// quadratic part is monotone in the support, so no descendant (which includes at least one more group) can be below it.
+// A column whose pivot is <= 1e-12 of its diagonal depends on the included ones and cannot lower the value: it is skipped
+// (its coefficient is 0) and the rest of its group goes on -- what makes n < p, duplicated columns and centred one-hot groups
+// safe.  A group that brings NO column leaves the value where it was and costs a slot (and alpha): its include branch is
+// dropped unless some other group needs it -- every support with it is matched by the same support without it.
+//
+// The incumbent is shared through a 64-bit atomic min on an order-preserving integer image of the double; every wave also
+// keeps its own best (value, support), and the host picks the winner from those in a fixed order, so the result does not
+// depend on which wave met it first.  Only a candidate that would beat the incumbent is back-substituted; if it leaves the
+// box its value comes from cyclic coordinate descent with clipping on its own block of H, stopped at a relative change of
+// L0_CD_TOL per sweep -- the host values its seed by the same descent, so boxed supports are compared like with like.  A global node counter is
+// bumped in batches; past max_nodes every wave drains and exits.  Every loop is bounded.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace slm {
+
+constexpr int L0_PMAX = 64;        // columns, and groups
+constexpr int L0_WAVES = 4;        // wavefronts per workgroup (they share H in LDS and nothing else)
+constexpr int L0_PREFIX = 16;      // groups decided by the ticket
+constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
+constexpr int L0_CD_SWEEPS = 10000;
+constexpr double L0_CD_TOL = 1e-12;
+constexpr double L0_PIVOT = 1e-12;
+// control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
+constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_CTL_WORDS = 8;
+
+struct L0Args {
+  const double* H;                  // [p][p] G + 2 eta T, search order
+  const double* c;                  // [p]
+  const long long* gstart;          // [ng + 1] first column of each group
+  const unsigned long long* need;   // [ng] groups (search order) each group depends on
+  unsigned long long* ctl;          // [L0_CTL_WORDS]
+  double* best_val;                 // [waves of the grid]
+  unsigned long long* best_mask;    // [waves of the grid]
+  int p, ng, d, K;
+  double alpha, big_M, q_all;
+  long long max_nodes;
+};
+
+// order-preserving image of a double in an unsigned 64-bit integer (and back)
+static __host__ __device__ inline unsigned long long l0_key(double v) {
+  unsigned long long b;
+  __builtin_memcpy(&b, &v, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+static __host__ __device__ inline double l0_unkey(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double v;
+  __builtin_memcpy(&v, &b, 8);
+  return v;
+}
+
+static __device__ __forceinline__ double l0_bcast(double v, int k) {  // lane k's value (k wave-uniform)
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), k);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), k);
+  return __hiloint2double(hi, lo);
+}
+static __device__ __forceinline__ double l0_wave_sum(double v) {  // the same bits in every lane
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+static __device__ __forceinline__ double l0_wave_max(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  return v;
+}
+
+static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
+  __shared__ double Hs[L0_PMAX * L0_PMAX];
+  __shared__ double cs[L0_PMAX];
+  __shared__ unsigned long long needs[L0_PMAX];
+  __shared__ int gs[L0_PMAX + 1];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int p = a.p, ng = a.ng, d = a.d, K = a.K;
+  for (int e = tid; e < p * p; e += 64 * L0_WAVES) Hs[e] = a.H[e];
+  for (int e = tid; e < p; e += 64 * L0_WAVES) cs[e] = a.c[e];
+  for (int e = tid; e < ng; e += 64 * L0_WAVES) needs[e] = a.need[e];
+  for (int e = tid; e <= ng; e += 64 * L0_WAVES) gs[e] = (int)a.gstart[e];
+  __syncthreads();  // (the only barrier: from here on the waves run on their own and leave when they are done)
+
+  const long long n_tickets = 1ll << d;
+  const double alpha = a.alpha, big_M = a.big_M, q_all = a.q_all;
+  // lane r: row r of L (entries below the diagonal), 1 / L[r][r], w[r], the column it stands for
+  double Lrow[L0_PMAX];
+#pragma unroll
+  for (int k = 0; k < L0_PMAX; ++k) Lrow[k] = 0.0;
+  double invd = 0.0, w = 0.0;
+  int mycol = 0;
+  // the state before group g was decided, held by lane g
+  int st_m = 0;
+  double st_ss = 0.0;
+  unsigned long long st_need = 0;
+
+  double best_v = __builtin_inf();
+  unsigned long long best_mask = ~0ull;
+  double inc = l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  long long nodes_local = 0;
+  int since_refresh = 0;
+  unsigned long long needed = 0;  // groups some other group depends on
+  for (int g = 0; g < ng; ++g) needed |= needs[g];
+  bool quit = false;
+
+  for (long long round = 0; round <= n_tickets && !quit; ++round) {
+    long long t = 0;
+    unsigned long long stop = 0;
+    if (lane == 0) {
+      t = (long long)atomicAdd(&a.ctl[L0_TICKET], 1ull);
+      stop = __hip_atomic_load(&a.ctl[L0_STOP], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    t = ((long long)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)t);
+    stop = (unsigned)__builtin_amdgcn_readfirstlane((int)stop);
+    if (t >= n_tickets) break;
+    if (stop) {  // (a ticket taken and not searched: the search is incomplete)
+      if (lane == 0) atomicOr(&a.ctl[L0_ABORTED], 1ull);
+      break;
+    }
+    inc = l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    int m = 0, cnt = 0, depth = 0;
+    double ss = 0.0;
+    unsigned long long incl = 0, needm = 0;
+    bool down = true;
+    // every pass of this loop either descends one level, or climbs one, or turns an include into an exclude: at most
+    // three passes per edge of a finite tree; the node budget ends it earlier
+    for (;;) {
+      int g;
+      bool try_exclude = false;
+      if (down) {
+        if (depth >= ng || cnt >= K || !(q_all + alpha * (double)(cnt + 1) < inc)) {
+          down = false;
+          continue;
+        }
+        g = depth;
+        const bool forced = g < d;
+        const bool want = forced ? ((t >> g) & 1) != 0 : true;
+        if (lane == g) {
+          st_m = m;
+          st_ss = ss;
+          st_need = needm;
+        }
+        bool ok = want;
+        if (ok) {
+          const unsigned long long low = g == 0 ? 0ull : (~0ull >> (64 - g));
+          ok = (needs[g] & low & ~incl) == 0;  // hierarchy: it needs a group that was excluded
+        }
+        if (ok) {
+          if (++nodes_local >= L0_BATCH) {  // the node budget
+            unsigned long long flag = 0;
+            if (lane == 0) {
+              const unsigned long long total = atomicAdd(&a.ctl[L0_NODES], (unsigned long long)nodes_local) + (unsigned long long)nodes_local;
+              if ((long long)total > a.max_nodes) atomicOr(&a.ctl[L0_STOP], 1ull);
+              flag = __hip_atomic_load(&a.ctl[L0_STOP], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | ((long long)total > a.max_nodes ? 1ull : 0ull);
+            }
+            nodes_local = 0;
+            if (__builtin_amdgcn_readfirstlane((int)flag)) {
+              if (lane == 0) atomicOr(&a.ctl[L0_ABORTED], 1ull);
+              quit = true;
+              break;
+            }
+          }
+          const int c0 = __builtin_amdgcn_readfirstlane(gs[g]), c1 = __builtin_amdgcn_readfirstlane(gs[g + 1]);
+          for (int j = c0; j < c1; ++j) {
+            // append column j: x = L^-1 H[cols, j] by columns, x_k broadcast from lane k at step k
+            const double hjj = Hs[j * p + j];
+            double b = lane < m ? Hs[j * p + mycol] : 0.0;  // (H is symmetric: the lanes read one row)
+            double s2 = 0.0, sw = 0.0;
+#pragma unroll
+            for (int k = 0; k < L0_PMAX; ++k) {
+              if (k < m) {
+                const double xk = l0_bcast(b * invd, k);
+                s2 = fma(xk, xk, s2);
+                sw = fma(xk, l0_bcast(w, k), sw);
+                b = fma(-Lrow[k], xk, b);
+                if (lane == m) Lrow[k] = xk;
+              }
+            }
+            const double piv = hjj - s2;
+            if (piv > L0_PIVOT * hjj) {  // (otherwise the column depends on the included ones: it is skipped, its beta is 0)
+              const double lmm = sqrt(piv), wm = (cs[j] - sw) / lmm;
+              if (lane == m) {
+                invd = 1.0 / lmm;
+                w = wm;
+                mycol = j;
+              }
+              ss = fma(wm, wm, ss);
+              ++m;
+            }
+          }
+          // a group that brought no column leaves the value where it was and costs a slot (and alpha): unless another
+          // group needs it, every support with it is matched by the same support without it
+          if (m == __builtin_amdgcn_readlane(st_m, g) && !((needed >> g) & 1)) ok = false;
+        }
+        if (ok) {
+          incl |= 1ull << g;
+          ++cnt;
+          needm |= needs[g];
+          depth = g + 1;
+          // every node is a candidate; inside the prefix the ticket whose remaining bits are zero evaluates it
+          const bool mine = depth >= d || (t >> depth) == 0;
+          double val = -0.5 * ss + alpha * (double)cnt;
+          if (mine && (needm & ~incl) == 0 && val <= inc && (val < best_v || (val == best_v && incl < best_mask))) {
+            // back-substitution beta = L^-T w, row by row from the last: lane r contributes L[r][k] beta_r to entry k
+            double beta = 0.0;
+#pragma unroll
+            for (int k = L0_PMAX - 1; k >= 0; --k) {
+              if (k < m) {
+                const double part = l0_wave_sum((lane > k && lane < m) ? Lrow[k] * beta : 0.0);
+                if (lane == k) beta = (w - part) * invd;
+              }
+            }
+            if (l0_wave_max(lane < m ? fabs(beta) : 0.0) > big_M) {
+              // the box binds: cyclic coordinate descent with clipping on the support's block of H; lane r keeps
+              // beta_r and the gradient entry (H beta - c)_r
+              beta = fmin(fmax(beta, -big_M), big_M);
+              double gr = lane < m ? -cs[mycol] : 0.0;
+              for (int k = 0; k < m; ++k) {
+                const int ck = __builtin_amdgcn_readlane(mycol, k);
+                gr = fma(lane < m ? Hs[ck * p + mycol] : 0.0, l0_bcast(beta, k), gr);
+              }
+              for (int sweep = 0; sweep < L0_CD_SWEEPS; ++sweep) {
+                double maxd = 0.0, maxb = 0.0;
+                for (int k = 0; k < m; ++k) {
+                  const int ck = __builtin_amdgcn_readlane(mycol, k);
+                  const double bk = l0_bcast(beta, k), gk = l0_bcast(gr, k);
+                  const double nb = fmin(fmax(bk - gk / Hs[ck * p + ck], -big_M), big_M);
+                  const double dk = nb - bk;
+                  if (dk != 0.0) {
+                    gr = fma(lane < m ? Hs[ck * p + mycol] : 0.0, dk, gr);
+                    if (lane == k) beta = nb;
+                  }
+                  maxd = fmax(maxd, fabs(dk));
+                  maxb = fmax(maxb, fabs(nb));
+                }
+                if (maxd <= L0_CD_TOL * maxb || maxd == 0.0) break;
+              }
+              val = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0) + alpha * (double)cnt;
+            }
+            if (val <= inc && (val < best_v || (val == best_v && incl < best_mask))) {
+              unsigned long long old = 0;
+              if (lane == 0) old = atomicMin(&a.ctl[L0_INCUMBENT], l0_key(val));
+              const double seen = l0_unkey(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) |
+                                           (unsigned)__builtin_amdgcn_readfirstlane((int)old));
+              inc = fmin(seen, val);
+              if (val <= inc) {
+                best_v = val;
+                best_mask = incl;
+              }
+            }
+          }
+          // a fresh look at the incumbent now and then
+          if (++since_refresh >= 32) {
+            since_refresh = 0;
+            inc = fmin(inc, l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+          }
+          continue;  // (down, one level deeper)
+        }
+        if (forced && want) break;  // the ticket's own include is impossible: its subtree is empty
+        try_exclude = true;
+      } else {
+        g = depth - 1;
+        if (g < d) break;  // back at the prefix: the ticket is done
+        if ((incl >> g) & 1) {  // back from the include branch: undo it, take the exclude branch
+          incl &= ~(1ull << g);
+          --cnt;
+          try_exclude = true;
+        } else {
+          depth = g;  // back from the exclude branch: climb on
+          continue;
+        }
+      }
+      if (try_exclude) {
+        m = __builtin_amdgcn_readlane(st_m, g);
+        ss = l0_bcast(st_ss, g);
+        needm = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(st_need >> 32), g) << 32) |
+                (unsigned)__builtin_amdgcn_readlane((int)st_need, g);
+        if ((needm >> g) & 1) {  // an included group needs this one
+          if (g < d) break;
+          depth = g;
+          down = false;
+        } else {
+          depth = g + 1;
+          down = true;
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    if (nodes_local > 0) atomicAdd(&a.ctl[L0_NODES], (unsigned long long)nodes_local);
+    const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
+    a.best_val[wv] = best_v;
+    a.best_mask[wv] = best_mask;
+  }
+}
+
+}  // namespace slm

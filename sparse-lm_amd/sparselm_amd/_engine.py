@@ -45,7 +45,7 @@ FLAG_PROFILE_UNIT = 1024  # with FLAG_PROFILE: the event bracket spans residuals
 FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plain steps, no rounds on the model Gram (csrc/mg_kernels.hpp)
 
 COMM_ID_BYTES = 128
-ABI_VERSION = 23  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
+ABI_VERSION = 24  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -88,6 +88,7 @@ ABI_SYMBOLS = (
     "slm_solve_path_lanes",
     "slm_solve_standardized_sgl",
     "slm_solve_constrained",
+    "slm_solve_l0",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -345,6 +346,7 @@ def load_library():
             ],
             "slm_solve_standardized_sgl": [vp, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
             "slm_solve_constrained": [vp, vp, vp, i32, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
+            "slm_solve_l0": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1268,6 +1270,45 @@ class Dataset:
             )
         )
         return beta, lam, info[0]
+
+    def solve_l0(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0``: the exact search over supports of the dataset's groups (csrc/l0_kernels.hpp) for
+        ``1/2 b^T (G + 2 eta T) b - c^T b + alpha |S|`` with ``|S| <= max_groups``, ``|b_j| <= big_M`` and the hierarchy
+        ``need`` (one integer mask per group).  Returns ``(beta, support mask, info)`` where ``info`` is a dict with
+        ``objective``, ``lower_bound``, ``proven_optimal``, ``nodes``, ``status``, ``loss``, ``seed_objective``, ``q_all``,
+        ``launches``, ``box_tol``.  ``binding``: None = the compiled binding when it is there, False = ctypes, True = the binding or an
+        error (the two routes are compared by the tests)."""
+        _sync_knobs()
+        G = self.n_groups
+        K = G if max_groups is None else int(max_groups)
+        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
+        need_ = None
+        if need is not None:
+            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
+            if need_.shape != (G,):
+                raise ValueError(f"need must have {G} entries")
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        if b is not None:
+            beta, support, lower, nodes, rec, rc = b.solve_l0(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M),
+                                                              need_, int(max_nodes))
+            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
+        else:
+            beta = np.empty(self.p)
+            sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
+            infos = np.zeros(1, dtype=_INFO_DTYPE)
+            rc = self._lib.slm_solve_l0(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes),
+                                        _ptr(beta), C.byref(sup), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
+            if rc != SLM_ERR_NOT_CONVERGED:
+                _check(rc)
+            support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
+        return beta, int(support), {
+            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
+            "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
+            "box_tol": 1e-12,  # L0_CD_TOL: relative change per sweep at which boxed candidates' descents stop (DESIGN 4d)
+        }
 
 
 class _HostPool:

@@ -1,13 +1,25 @@
-"""Lasso-family estimators under the reference's public names.
+"""The reference's estimators under its public names.
 
-The reference exports 16 estimators from ``sparselm.model``; the ten below (plus OLS) are the ones a
-proximal-gradient engine can serve.  The mixed-integer ones (BestSubsetSelection, RegularizedL0,
-L1L0, L2L0, ...) need a branch-and-bound MIQP solver and are out of scope.
+The reference exports 16 estimators from ``sparselm.model``.  Served here:
+
+* the ten Lasso-family ones plus OLS (``__all__``: ``_lasso.py``, ``_adaptive_lasso.py``) -- convex problems, solved by the
+  proximal-gradient engine;
+* four of the mixed-integer ones (``MIQP_ESTIMATORS``: ``BestSubsetSelection``, ``RidgedBestSubsetSelection``,
+  ``RegularizedL0``, ``L2L0`` -- ``_miqp.py``) -- solved EXACTLY by a depth-first search over supports on the GPU
+  (``slm_solve_l0``) for up to 64 columns and 64 groups, where the reference needs Gurobi or SCIP behind cvxpy.
+
+``from sparselm_amd.model import L2L0`` works; the four are kept out of ``__all__`` because they share neither the
+penalty interface nor ``constraints=`` of the Lasso family, which is what ``__all__`` enumerates.  ``L1L0`` is not
+provided (a lasso solve per support; the reference's own tests leave it out).
 """
 
 from . import _adaptive_lasso as _adaptive
 from . import _lasso as _plain
+from . import _miqp
 
 __all__ = list(_plain.__all__) + list(_adaptive.__all__)
 globals().update({name: getattr(_plain, name) for name in _plain.__all__})
 globals().update({name: getattr(_adaptive, name) for name in _adaptive.__all__})
+
+MIQP_ESTIMATORS = tuple(_miqp.__all__)
+globals().update({name: getattr(_miqp, name) for name in _miqp.__all__})

@@ -1,0 +1,259 @@
+"""Exact l0 estimators under the reference's names: ``BestSubsetSelection``, ``RidgedBestSubsetSelection``,
+``RegularizedL0`` and ``L2L0`` (reference src/sparselm/model/_miqp/_best_subset.py:95-124, 215-248 and
+_regularized_l0.py:115-144, 502-530 for the constructors and parameter constraints).
+
+The reference writes these as mixed-integer quadratic programs in cvxpy and needs Gurobi or SCIP to solve them.  Here one
+launch of a depth-first search over supports on the GPU (``slm_solve_l0``, csrc/l0_kernels.hpp) returns the proven optimum
+for up to 64 columns and 64 groups.  The reference's objectives divided by ``2n`` (_miqp/_base.py:126-127,
+_regularized_l0.py:157-161, ``TikhonovMixin`` _base.py:544-546) are all
+
+    minimise over supports S (sets of GROUPS) and beta, supp beta in cols(S), |beta_j| <= big_M:
+        1/2 beta^T (G + 2 eta W^T W) beta - c^T beta + alpha |S|,      G = X^T X / n,  c = X^T y / n
+    subject to |S| <= sparse_bound  and  i in S => hierarchy[i] in S
+
+with ``alpha = 0`` for the two best-subset classes (the reference's missing ``1/(2n)`` there does not move the minimiser),
+``sparse_bound =`` the number of groups for the two regularised ones, and ``eta = 0`` without a ridge term.
+
+``L1L0`` is NOT provided: every support would need a lasso solve of its own, and the reference's own tests leave it out.
+There is no ``constraints=`` on these classes.
+"""
+
+from __future__ import annotations
+
+import warnings
+from numbers import Real
+
+import numpy as np
+from sklearn.base import BaseEstimator, RegressorMixin
+from sklearn.exceptions import ConvergenceWarning
+from sklearn.utils._param_validation import Interval, validate_parameter_constraints
+from sklearn.utils.validation import _check_sample_weight, check_is_fitted, validate_data
+
+from .._utils.validation import check_groups, dense_group_index
+
+__all__ = ["BestSubsetSelection", "RidgedBestSubsetSelection", "RegularizedL0", "L2L0"]
+
+_KNOWN_OPTIONS = {"max_nodes", "device"}
+
+
+def _hierarchy_masks(hierarchy, groups, n_features):
+    """``need[i]``: the dense indices (as one integer mask) of the groups the i-th sorted label depends on -- entry i of
+    ``hierarchy`` lists LABELS (reference _miqp/_base.py:160-166).  ValueError for a wrong length or an unknown label."""
+    labels = np.arange(n_features) if groups is None else np.unique(np.asarray(groups))
+    if hierarchy is None:
+        return None
+    if len(hierarchy) != len(labels):
+        raise ValueError(f"hierarchy must have one entry per group: {len(hierarchy)} != {len(labels)}")
+    index = {lab.item() if hasattr(lab, "item") else lab: i for i, lab in enumerate(labels)}
+    need = []
+    for i, subs in enumerate(hierarchy):
+        mask = 0
+        for lab in subs:
+            key = lab.item() if hasattr(lab, "item") else lab
+            if key not in index:
+                raise ValueError(f"hierarchy[{i}] names {lab!r}, which is not a group label")
+            mask |= 1 << index[key]
+        need.append(mask)
+    return need
+
+
+class _ExactL0(RegressorMixin, BaseEstimator):
+    """Common part of the four estimators (the reference's ``MIQPl0``, _miqp/_base.py:22-167).
+
+    Fitted attributes: ``coef_``, ``intercept_``, ``active_groups_`` (bool per sorted group label: the counterpart of the
+    reference's ``canonicals_.auxiliaries.z0.value``) and ``solver_info_`` with ``objective`` (in the units above),
+    ``lower_bound`` (proven; equal to the objective when the search finished), ``proven_optimal``, ``nodes`` (group
+    inclusions tried: it may differ between two fits of one problem, because pruning depends on when the wavefronts see
+    each other's incumbents -- the result does not), ``status``, ``loss``, ``seed_objective``, ``launches``, ``box_tol``
+    (supports that leave the ``big_M`` box are compared by a coordinate descent stopped at this relative change per sweep).
+    A column that depends on the other active columns keeps a zero coefficient: an inactive group is all zero, an active
+    group need not be all non-zero (a group {a, 2a}, a centred one-hot group).
+
+    ``solver`` is accepted for the reference's signature and ignored; ``ignore_psd_check`` likewise (there is no cvxpy
+    check to skip); ``solver_options`` understands ``max_nodes`` (the node budget: when it runs out a
+    ``ConvergenceWarning`` is raised and the incumbent kept) and ``device``.
+    """
+
+    _parameter_constraints: dict = {
+        "ignore_psd_check": ["boolean"],
+        "fit_intercept": ["boolean"],
+        "copy_X": ["boolean"],
+        "warm_start": ["boolean"],
+        "solver": [str, None],
+        "solver_options": [dict, None],
+    }
+    _hyper_parameter_constraints: dict = {"big_M": [Interval(type=Real, left=0.0, right=None, closed="left")]}
+
+    def _validate_params(self, X, y) -> None:
+        constraints = dict(self._parameter_constraints)
+        constraints.update(self._hyper_parameter_constraints)
+        params = self.get_params(deep=False)
+        validate_parameter_constraints(constraints, {k: params[k] for k in constraints}, caller_name=self.__class__.__name__)
+        check_groups(self.groups, X.shape[1])
+
+    # what the sub-classes say about the problem
+    def _l0_problem(self, n_groups):
+        """(alpha, max_groups, eta)"""
+        raise NotImplementedError
+
+    def _tikhonov(self, n_features):
+        return None
+
+    def fit(self, X, y, sample_weight=None):
+        X, y = validate_data(self, X, y, accept_sparse=False, y_numeric=True, multi_output=False)
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        # everything is validated before a device is touched
+        self._validate_params(X, y)
+        options = {} if self.solver_options is None else dict(self.solver_options)
+        unknown = set(options) - _KNOWN_OPTIONS
+        if unknown:
+            raise ValueError(f"unknown solver_options {sorted(unknown)}: the exact l0 search takes {sorted(_KNOWN_OPTIONS)}")
+        p = X.shape[1]
+        gidx, n_groups = dense_group_index(self.groups, p)
+        need = _hierarchy_masks(self.hierarchy, self.groups, p)
+        alpha, max_groups, eta = self._l0_problem(n_groups)
+        T = self._tikhonov(p)
+        w = None
+        if sample_weight is not None:
+            w = _check_sample_weight(sample_weight, X, dtype=X.dtype)
+            w = w * (X.shape[0] / np.sum(w))
+
+        from .. import _engine
+
+        eng = _engine.get_engine(options.get("device"))
+        with eng.dataset(X, y, row_weight=w) as ds:
+            x_mean, y_mean = ds.center() if self.fit_intercept else (np.zeros(p), 0.0)
+            ds.set_groups(gidx, n_groups)
+            if need is not None and n_groups > 64:
+                need = None  # (the engine refuses the size itself; masks of more than 64 groups have no 64-bit form)
+            beta, support, info = ds.solve_l0(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
+                                              need=need, max_nodes=int(options.get("max_nodes", 0) or 0))
+        if not info["proven_optimal"]:
+            warnings.warn(
+                f"the node budget ran out after {info['nodes']} nodes: the incumbent (objective {info['objective']:.6g}, proven "
+                f"lower bound {info['lower_bound']:.6g}) is kept; raise solver_options['max_nodes']",
+                ConvergenceWarning,
+            )
+        self.coef_ = beta
+        self.active_groups_ = np.array([(support >> i) & 1 for i in range(n_groups)], dtype=bool)
+        self.solver_info_ = info
+        self.intercept_ = float(y_mean - np.dot(x_mean, beta)) if self.fit_intercept else 0.0
+        return self
+
+    def predict(self, X):
+        check_is_fitted(self)
+        X = validate_data(self, X, accept_sparse=False, reset=False)
+        return X @ self.coef_ + self.intercept_
+
+    def __sklearn_tags__(self):
+        tags = super().__sklearn_tags__()
+        tags.target_tags.single_output = True
+        return tags
+
+
+class _TikhonovMixin:
+    """``eta ||W beta||^2`` (reference ``TikhonovMixin``, _base.py:522-548); ``W = I`` when ``tikhonov_w`` is None."""
+
+    def _tikhonov(self, n_features):
+        if self.tikhonov_w is None:
+            return None
+        W = np.asarray(self.tikhonov_w, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != n_features:
+            raise ValueError(f"tikhonov_w must have {n_features} columns")
+        return W.T @ W
+
+
+class BestSubsetSelection(_ExactL0):
+    """Best subset selection: at most ``sparse_bound`` active groups (reference _best_subset.py:24-139), solved exactly.
+
+    Args as in the reference: ``groups`` (None: every feature its own group), ``sparse_bound``, ``big_M`` (bound on every
+    ``|coef_j|``), ``hierarchy`` (entry i lists the group labels the i-th sorted label depends on), ``ignore_psd_check``,
+    ``fit_intercept``, ``copy_X``, ``warm_start``, ``solver``, ``solver_options``.
+    """
+
+    _hyper_parameter_constraints: dict = {
+        "sparse_bound": [Interval(type=Real, left=0, right=None, closed="left")],
+        **_ExactL0._hyper_parameter_constraints,
+    }
+
+    def __init__(self, groups=None, sparse_bound=100, big_M=100, hierarchy=None, ignore_psd_check=True, fit_intercept=False,
+                 copy_X=True, warm_start=False, solver=None, solver_options=None):
+        self.groups = groups
+        self.sparse_bound = sparse_bound
+        self.big_M = big_M
+        self.hierarchy = hierarchy
+        self.ignore_psd_check = ignore_psd_check
+        self.fit_intercept = fit_intercept
+        self.copy_X = copy_X
+        self.warm_start = warm_start
+        self.solver = solver
+        self.solver_options = solver_options
+
+    def _l0_problem(self, n_groups):
+        return 0.0, int(min(np.floor(self.sparse_bound), n_groups)), 0.0
+
+
+class RidgedBestSubsetSelection(_TikhonovMixin, BestSubsetSelection):
+    """Best subset selection with a ridge / Tikhonov term ``eta ||W beta||^2`` (reference _best_subset.py:142-248)."""
+
+    _hyper_parameter_constraints: dict = {
+        "eta": [Interval(type=Real, left=0.0, right=None, closed="left")],
+        **BestSubsetSelection._hyper_parameter_constraints,
+    }
+
+    def __init__(self, groups=None, sparse_bound=100, eta=1.0, big_M=100, hierarchy=None, tikhonov_w=None,
+                 ignore_psd_check=True, fit_intercept=False, copy_X=True, warm_start=False, solver=None, solver_options=None):
+        super().__init__(groups=groups, sparse_bound=sparse_bound, big_M=big_M, hierarchy=hierarchy,
+                         ignore_psd_check=ignore_psd_check, fit_intercept=fit_intercept, copy_X=copy_X, warm_start=warm_start,
+                         solver=solver, solver_options=solver_options)
+        self.tikhonov_w = tikhonov_w
+        self.eta = eta
+
+    def _l0_problem(self, n_groups):
+        return 0.0, int(min(np.floor(self.sparse_bound), n_groups)), float(self.eta)
+
+
+class RegularizedL0(_ExactL0):
+    """``1/(2n)||X beta - y||^2 + alpha |S|`` over active groups S (reference _regularized_l0.py:39-161), solved exactly."""
+
+    _hyper_parameter_constraints: dict = {
+        "alpha": [Interval(type=Real, left=0.0, right=None, closed="left")],
+        **_ExactL0._hyper_parameter_constraints,
+    }
+
+    def __init__(self, groups=None, alpha=1.0, big_M=100, hierarchy=None, ignore_psd_check=True, fit_intercept=False,
+                 copy_X=True, warm_start=False, solver=None, solver_options=None):
+        self.groups = groups
+        self.alpha = alpha
+        self.big_M = big_M
+        self.hierarchy = hierarchy
+        self.ignore_psd_check = ignore_psd_check
+        self.fit_intercept = fit_intercept
+        self.copy_X = copy_X
+        self.warm_start = warm_start
+        self.solver = solver
+        self.solver_options = solver_options
+
+    def _l0_problem(self, n_groups):
+        return float(self.alpha), n_groups, 0.0
+
+
+class L2L0(_TikhonovMixin, RegularizedL0):
+    """``RegularizedL0`` with a ridge / Tikhonov term ``eta ||W beta||^2`` (reference _regularized_l0.py:413-530)."""
+
+    _hyper_parameter_constraints: dict = {
+        "eta": [Interval(type=Real, left=0.0, right=None, closed="left")],
+        **RegularizedL0._hyper_parameter_constraints,
+    }
+
+    def __init__(self, groups=None, alpha=1.0, eta=1.0, big_M=100, hierarchy=None, tikhonov_w=None, ignore_psd_check=True,
+                 fit_intercept=False, copy_X=True, warm_start=False, solver=None, solver_options=None):
+        super().__init__(groups=groups, alpha=alpha, big_M=big_M, hierarchy=hierarchy, ignore_psd_check=ignore_psd_check,
+                         fit_intercept=fit_intercept, copy_X=copy_X, warm_start=warm_start, solver=solver,
+                         solver_options=solver_options)
+        self.tikhonov_w = tikhonov_w
+        self.eta = eta
+
+    def _l0_problem(self, n_groups):
+        return float(self.alpha), n_groups, float(self.eta)
