@@ -32,15 +32,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "l0_host.hpp"  // L0_PMAX, L0_CD_SWEEPS, L0_CD_TOL, L0_PIVOT: shared with the host side
+
 namespace slm {
 
-constexpr int L0_PMAX = 64;        // columns, and groups
 constexpr int L0_WAVES = 4;        // wavefronts per workgroup (they share H in LDS and nothing else)
 constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
-constexpr int L0_CD_SWEEPS = 10000;
-constexpr double L0_CD_TOL = 1e-12;
-constexpr double L0_PIVOT = 1e-12;
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
 constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_CTL_WORDS = 8;
 

@@ -1,8 +1,10 @@
-// CPU test of csrc/host_logic.hpp -- the engine's device-free bookkeeping -- and of csrc/tail_logic.hpp -- the scalar state
-// machine of the tail kernels, the very functions the device runs -- meant to run under AddressSanitizer and
+// CPU test of csrc/host_logic.hpp -- the engine's device-free bookkeeping --, of csrc/tail_logic.hpp -- the scalar state
+// machine of the tail kernels, the very functions the device runs -- and of csrc/l0_host.hpp -- the host side of the exact
+// l0 search: the growing factor, the boxed descent, a support's value and coefficients -- meant to run under AddressSanitizer and
 // UndefinedBehaviorSanitizer (tools/sanitize.sh; tests/test_host_logic_cpu.py builds and runs it plainly in the CPU suite).
 // Every check is against an independent statement of what the function must do; a randomised pool run models the
 // allocator with malloc/free so that a double release or a leak is the sanitizers' to find.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -13,6 +15,7 @@
 
 #include "../sparse-lm_amd/csrc/host_logic.hpp"
 #include "../sparse-lm_amd/csrc/tail_logic.hpp"
+#include "../sparse-lm_amd/csrc/l0_host.hpp"
 
 using namespace slm_host;
 using namespace slm;
@@ -620,6 +623,212 @@ static void test_tail_route() {
   }
 }
 
+// ---- csrc/l0_host.hpp -----------------------------------------------------------------------------------------------
+// A 6 x 6 symmetric positive definite matrix with no structure to hide behind (entries from a fixed recurrence), and c.
+static void l0_spd6(double* H /* [36] */, double* c /* [6] */) {
+  double A[8][6];
+  unsigned v = 12345u;
+  for (int i = 0; i < 8; ++i)
+    for (int j = 0; j < 6; ++j) {
+      v = v * 1103515245u + 12345u;
+      A[i][j] = (double)((v >> 16) & 0x3ff) / 512.0 - 1.0;
+    }
+  for (int i = 0; i < 6; ++i) {
+    for (int j = 0; j < 6; ++j) {
+      double t = i == j ? 0.25 : 0.0;
+      for (int k = 0; k < 8; ++k) t += A[k][i] * A[k][j];
+      H[i * 6 + j] = t;
+    }
+    c[i] = 0.5 * (double)(i + 1) * ((i & 1) ? -1.0 : 1.0);
+  }
+}
+
+// Reference in long double: the Cholesky factor of H on `cols`, w = L^-1 c, beta = L^-T w.
+static void l0_reference(const double* H, const double* c, int p, const int* cols, int m, long double L[6][6], long double* w, long double* beta) {
+  for (int i = 0; i < m; ++i) {
+    for (int j = 0; j <= i; ++j) {
+      long double t = H[cols[i] * p + cols[j]];
+      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+      L[i][j] = i == j ? sqrtl(t) : t / L[j][j];
+    }
+    long double t = c[cols[i]];
+    for (int k = 0; k < i; ++k) t -= L[i][k] * w[k];
+    w[i] = t / L[i][i];
+  }
+  for (int k = m - 1; k >= 0; --k) {
+    long double t = w[k];
+    for (int r = k + 1; r < m; ++r) t -= L[r][k] * beta[r];
+    beta[k] = t / L[k][k];
+  }
+}
+
+static bool l0_near(double got, long double want, double rtol) { return fabsl((long double)got - want) <= rtol * fmaxl(1.0L, fabsl(want)); }
+
+static void l0_check_factor(const L0Factor& f, const double* H, const double* c, const int* cols, int m) {
+  long double L[6][6], w[6], beta[6], ss = 0.0L;
+  l0_reference(H, c, 6, cols, m, L, w, beta);
+  CHECK(f.m == m);
+  double b[L0_PMAX];
+  f.solve(b);
+  for (int r = 0; r < m; ++r) {
+    CHECK(f.col[r] == cols[r]);
+    for (int k = 0; k <= r; ++k) CHECK(l0_near(f.L[r][k], L[r][k], 1e-13));
+    CHECK(l0_near(f.w[r], w[r], 1e-13));
+    CHECK(l0_near(b[r], beta[r], 1e-12));
+    ss += w[r] * w[r];
+  }
+  CHECK(l0_near(f.ss, ss, 1e-13));
+  // ... and the solution solves the normal equations of the block
+  for (int r = 0; r < m; ++r) {
+    long double t = -(long double)c[cols[r]];
+    for (int k = 0; k < m; ++k) t += (long double)H[cols[r] * 6 + cols[k]] * b[k];
+    CHECK(fabsl(t) <= 1e-12);
+  }
+}
+
+static void test_l0_factor() {
+  double H[36], c[6];
+  l0_spd6(H, c);
+  const int all[6] = {0, 1, 2, 3, 4, 5}, some[4] = {4, 1, 5, 2}, after_pop[4] = {0, 1, 2, 5};
+  {
+    L0Factor f(H, c, 6);
+    double ss_at_3 = 0.0;
+    for (int j = 0; j < 6; ++j) {
+      CHECK(f.push(j));
+      l0_check_factor(f, H, c, all, j + 1);  // every prefix of the columns
+      if (j == 2) ss_at_3 = f.ss;
+    }
+    // backtracking: the column count goes down, ss is that of the remaining columns, and the factor grows again from there
+    f.pop_to(3);
+    CHECK(f.m == 3 && fabs(f.ss - ss_at_3) <= 4e-16 * ss_at_3);
+    l0_check_factor(f, H, c, all, 3);
+    CHECK(f.push(5));
+    l0_check_factor(f, H, c, after_pop, 4);
+    f.pop_to(0);
+    CHECK(f.m == 0 && f.ss == 0.0);
+  }
+  {
+    L0Factor f(H, c, 6);  // columns out of order: col[] carries the map
+    for (int k = 0; k < 4; ++k) CHECK(f.push(some[k]));
+    l0_check_factor(f, H, c, some, 4);
+  }
+  {
+    // a dependent column is refused and leaves the factor as it was: x2 = x0 + x1 (the Gram of integer vectors, exact)
+    const double X[4][3] = {{1, 2, 3}, {2, -1, 1}, {0, 3, 3}, {-1, 1, 0}};
+    double G[9], g[3];
+    for (int i = 0; i < 3; ++i) {
+      g[i] = (double)(i + 1);
+      for (int j = 0; j < 3; ++j) {
+        G[i * 3 + j] = 0.0;
+        for (int k = 0; k < 4; ++k) G[i * 3 + j] += X[k][i] * X[k][j];
+      }
+    }
+    L0Factor f(G, g, 3);
+    CHECK(f.push(0) && f.push(1));
+    const double ss = f.ss, l10 = f.L[1][0], w1 = f.w[1];
+    CHECK(!f.push(2));
+    CHECK(f.m == 2 && f.ss == ss && f.L[1][0] == l10 && f.w[1] == w1 && f.col[0] == 0 && f.col[1] == 1);
+    CHECK(!f.push(1));  // (so is a column that is already there)
+    CHECK(f.m == 2 && f.ss == ss);
+    // a zero column has nothing to bring either
+    const double Z[4] = {1.0, 0.0, 0.0, 0.0}, z[2] = {1.0, 0.0};
+    L0Factor fz(Z, z, 2);
+    CHECK(!fz.push(1) && fz.m == 0 && fz.push(0) && !fz.push(1) && fz.m == 1);
+  }
+}
+
+// min 1/2 b^T H b - c^T b over |b_j| <= 1 with H = tridiag(1, 2, 1) and c = (3.5, 1.75, 0): the minimiser is
+// b = (1, 1/2, -1/4).  There H b - c = (-1, 0, 0): the first coordinate sits at its bound with the gradient pushing outwards,
+// the other two are free with a zero gradient -- the KKT conditions of a strictly convex problem, so the point is THE
+// minimiser; its value is 1/2 * 3.375 - 4.375 = -2.6875.  (The unconstrained minimiser is (1.75, 0, 0) with the value -3.0625: the box binds.)
+static void test_l0_boxed() {
+  const double H3[9] = {2, 1, 0, 1, 2, 1, 0, 1, 2}, c3[3] = {3.5, 1.75, 0.0};
+  const double want[3] = {1.0, 0.5, -0.25}, value = -2.6875;
+  const int cols3[3] = {0, 1, 2};
+  for (int polish = 0; polish < 2; ++polish) {
+    const double tol = polish ? 1e-14 : 1e-10;  // (the descent stops at a relative change of 1e-12 per sweep; the polish is exact)
+    for (int start = 0; start < 2; ++start) {
+      double b[3] = {0.0, 0.0, 0.0};
+      if (start) {  // from the unconstrained minimiser, as l0_support calls it
+        L0Factor f(H3, c3, 3);
+        for (int j = 0; j < 3; ++j) CHECK(f.push(j));
+        f.solve(b);
+        CHECK(fabs(b[0] - 1.75) <= 1e-14 && fabs(b[1]) <= 1e-14 && fabs(b[2]) <= 1e-14);
+      }
+      const double v = l0_boxed(H3, c3, 3, cols3, 3, 1.0, polish != 0, b);
+      CHECK(b[0] == 1.0);
+      for (int k = 0; k < 3; ++k) CHECK(fabs(b[k] - want[k]) <= tol);
+      CHECK(fabs(v - value) <= tol);
+    }
+    // the same block scattered over a 5 x 5 matrix whose other entries must not be read
+    double H5[25], c5[5] = {1.75, 1e6, 0.0, -1e6, 3.5};
+    const int cols5[3] = {4, 0, 2};
+    for (int e = 0; e < 25; ++e) H5[e] = 1e6;
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) H5[cols5[i] * 5 + cols5[j]] = H3[i * 3 + j];
+    double b[3] = {0.0, 0.0, 0.0};
+    const double v = l0_boxed(H5, c5, 5, cols5, 3, 1.0, polish != 0, b);
+    for (int k = 0; k < 3; ++k) CHECK(fabs(b[k] - want[k]) <= tol);
+    CHECK(fabs(v - value) <= tol);
+    // a box nothing touches leaves the unconstrained minimiser; a box of zero leaves nothing
+    double wide[3] = {0.0, 0.0, 0.0}, none[3] = {0.3, -0.2, 0.1};
+    CHECK(fabs(l0_boxed(H3, c3, 3, cols3, 3, 100.0, polish != 0, wide) + 3.0625) <= 1e-9);
+    CHECK(fabs(wide[0] - 1.75) <= 1e-9 && fabs(wide[1]) <= 1e-9 && fabs(wide[2]) <= 1e-9);
+    CHECK(l0_boxed(H3, c3, 3, cols3, 3, 0.0, polish != 0, none) == 0.0 && none[0] == 0.0 && none[1] == 0.0 && none[2] == 0.0);
+  }
+  // through l0_support: three groups of one column, all included, big_M = 1
+  double beta[3];
+  const std::vector<int> gstart = {0, 1, 2, 3};
+  CHECK(fabs(l0_support(H3, c3, 3, gstart, 7ull, 1.0, true, beta) - value) <= 1e-14);
+  for (int k = 0; k < 3; ++k) CHECK(fabs(beta[k] - want[k]) <= 1e-14);
+  // two of the three: b_1 is out of the support and stays at zero; min over (b_0, b_2) separates: b_0 = 1 (1.75 clipped), b_2 = 0
+  CHECK(fabs(l0_support(H3, c3, 3, gstart, 5ull, 1.0, true, beta) - (1.0 - 3.5)) <= 1e-14);
+  CHECK(beta[0] == 1.0 && beta[1] == 0.0 && beta[2] == 0.0);
+}
+
+static void test_l0_support_skips_dependent_columns() {
+  // columns x0, x1 = 2 x0, x2, x3 in two groups {0, 1}, {2, 3}: the Gram of integer vectors, exact
+  const double X[5][4] = {{1, 2, 0, 1}, {-1, -2, 2, 0}, {2, 4, 1, 1}, {0, 0, -1, 3}, {1, 2, 1, -1}};
+  const double y[5] = {1.0, -2.0, 0.5, 3.0, -1.0};
+  double G[16], g[4];
+  for (int i = 0; i < 4; ++i) {
+    g[i] = 0.0;
+    for (int k = 0; k < 5; ++k) g[i] += X[k][i] * y[k];
+    for (int j = 0; j < 4; ++j) {
+      G[i * 4 + j] = 0.0;
+      for (int k = 0; k < 5; ++k) G[i * 4 + j] += X[k][i] * X[k][j];
+    }
+  }
+  const std::vector<int> gstart = {0, 2, 4};
+  const double inf = HUGE_VAL;
+  double beta[4];
+  for (int polish = 0; polish < 2; ++polish) {
+    // the first group alone: one column counts, the dependent one keeps a zero, the other group is all zero
+    double v = l0_support(G, g, 4, gstart, 1ull, inf, polish != 0, beta);
+    CHECK(fabs(beta[0] - g[0] / G[0]) <= 1e-15 && beta[1] == 0.0 && beta[2] == 0.0 && beta[3] == 0.0);
+    CHECK(fabs(v + 0.5 * g[0] * g[0] / G[0]) <= 1e-14);
+    // both groups: the solution on columns {0, 2, 3}, with the skipped column still at zero
+    v = l0_support(G, g, 4, gstart, 3ull, inf, polish != 0, beta);
+    const int cols[3] = {0, 2, 3};
+    long double L[6][6], w[6], b[6], ss = 0.0L;
+    l0_reference(G, g, 4, cols, 3, L, w, b);
+    for (int k = 0; k < 3; ++k) ss += w[k] * w[k];
+    CHECK(beta[1] == 0.0);
+    for (int k = 0; k < 3; ++k) CHECK(l0_near(beta[cols[k]], b[k], 1e-13));
+    CHECK(l0_near(v, -0.5L * ss, 1e-13));
+    // ... also when the box binds on the kept columns
+    double top = 0.0;
+    for (int k = 0; k < 4; ++k) top = fmax(top, fabs(beta[k]));
+    const double free_v = v;
+    v = l0_support(G, g, 4, gstart, 3ull, 0.5 * top, polish != 0, beta);
+    CHECK(beta[1] == 0.0 && v > free_v);
+    for (int k = 0; k < 4; ++k) CHECK(fabs(beta[k]) <= 0.5 * top);
+    // the empty support
+    CHECK(l0_support(G, g, 4, gstart, 0ull, inf, polish != 0, beta) == 0.0);
+    for (int k = 0; k < 4; ++k) CHECK(beta[k] == 0.0);
+  }
+}
+
 int main() {
   test_pool();
   test_row_sets();
@@ -634,6 +843,9 @@ int main() {
   test_bb_stop();
   test_fista_decide();
   test_tail_route();
+  test_l0_factor();
+  test_l0_boxed();
+  test_l0_support_skips_dependent_columns();
   if (failures) {
     fprintf(stderr, "host_logic_test: %d check(s) failed\n", failures);
     return 1;

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 from sklearn.datasets import make_regression, make_sparse_coded_signal
 
-from _l0_reference import brute_force, forward_stepwise, objective_of
+from _l0_reference import brute_force, forward_stepwise, objective_of, search_rank
 
 REFERENCE_SRC = "/root/reference/src/sparselm/model/_miqp"
 
@@ -52,6 +52,48 @@ def test_brute_force_box_ridge_and_hierarchy_are_consistent():
     assert not brute_force(X, y, K=4, hierarchy=chained)["active"].any()
     cols, rss = forward_stepwise(X, y, 3)
     assert rss >= (2 * 40) * free["objective"] + y @ y - 1e-9 * (y @ y)  # greedy is never better than the optimum
+
+
+def test_search_rank_on_a_hand_made_case():
+    """Four columns that touch one row each: c_j = x_j y_j / 4 and G_jj = x_j^2 / 4, so a column's score is y_j^2 / 4 whatever
+    its scale -- 1, 2.25, 2.25 (an exact tie: the lower label goes first) and 0.25."""
+    X = np.diag([2.0, 1.0, 1.0, 3.0])
+    y = np.array([2.0, 3.0, -3.0, 1.0])
+    assert search_rank(X, y).tolist() == [2, 0, 1, 3]
+    assert search_rank(X, y, eta=0.1, W=np.eye(4)).tolist() == [2, 0, 1, 3]
+    # groups by sorted label: 3 -> {column 2}: 2.25; 5 -> {column 3}: 0.25; 7 -> {columns 0, 1}: (1 + 0.5625) / (1 + 0.25) = 1.25
+    assert search_rank(X, y, groups=[7, 7, 3, 5]).tolist() == [0, 2, 1]
+    # a column of zeros scores zero and goes last; equal scores keep the order of the labels
+    assert search_rank(np.diag([1.0, 0.0, 1.0]), np.array([1.0, 5.0, 1.0])).tolist() == [0, 2, 1]
+
+
+def test_max_size_closes_a_penalised_problem_like_the_full_enumeration():
+    X, y = make_regression(40, 10, n_informative=3, noise=1.0, random_state=4)
+    alpha = 0.02 * float(y @ y) / (2 * 40)
+    full = brute_force(X, y, alpha=alpha)
+    assert full["closed"] and full["n_supports"] == 2**10 and 0 < full["active"].sum() <= 4
+    part = brute_force(X, y, alpha=alpha, max_size=4)
+    assert part["closed"] and part["n_supports"] == 1 + 10 + 45 + 120 + 210
+    np.testing.assert_array_equal(part["active"], full["active"])
+    assert part["objective"] == full["objective"] and part["coef"].tobytes() == full["coef"].tobytes()
+    assert 0 < part["gap"] <= full["gap"] and part["kappa"] == full["kappa"]
+    # a bound K at or below max_size: everything admissible was enumerated
+    assert brute_force(X, y, alpha=alpha, K=3, max_size=4)["closed"]
+    assert brute_force(X, y, K=3, max_size=3)["n_supports"] == brute_force(X, y, K=3)["n_supports"]
+
+
+def test_max_size_one_too_small_is_not_closed():
+    """Orthogonal columns of norm sqrt n and y = 2 x_0 - 2 x_1 + 2 x_2: a column's gain is 1/2 * 2^2 = 2, so for alpha = 0.5 the
+    optimum is exactly those three.  Two are not enough (-4 + 3 alpha is below the best pair's -4 + 2 alpha + ... nothing the
+    reference can rule out: q_all + 3 alpha = -4.5 < -3), three are (q_all + 4 alpha = -4 > -4.5)."""
+    Q = np.linalg.qr(np.random.default_rng(0).standard_normal((12, 6)))[0] * np.sqrt(12)
+    y = 2 * Q[:, 0] - 2 * Q[:, 1] + 2 * Q[:, 2]
+    short = brute_force(Q, y, alpha=0.5, max_size=2)
+    assert not short["closed"] and short["active"].sum() == 2 and abs(short["objective"] + 3.0) < 1e-12
+    enough = brute_force(Q, y, alpha=0.5, max_size=3)
+    assert enough["closed"] and enough["active"].tolist() == [True, True, True, False, False, False]
+    assert abs(enough["objective"] + 4.5) < 1e-12
+    np.testing.assert_array_equal(enough["active"], brute_force(Q, y, alpha=0.5)["active"])
 
 
 @pytest.mark.parametrize("name", sorted(SIGNATURES))
