@@ -609,6 +609,27 @@ int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, 
                  slm_point_info* info);
 
 /*
+ * (added under ABI 24: a new symbol beside slm_solve_l0, no existing entry, structure or constant changes, so the version
+ * stays 24 -- a caller that needs it looks the symbol up.)  The reference's L1L0 (_regularized_l0.py:258-410, objective
+ * :395-410, divided by 2n) by the same search in its l1 mode (csrc/l0_kernels.hpp, template parameter L1):
+ *   minimise over supports S (sets of the dataset's GROUPS) and beta with supp beta in cols(S), |beta_j| <= big_M:
+ *       1/2 beta^T G beta - c^T beta + eta_l1 ||beta||_1 + alpha |S|     subject to  i in S => need[i] subset of S
+ * -- no cardinality bound and no ridge term.  A support's value is a lasso inside the box: the register Cholesky value
+ * q(S) <= f(S) is an exact lower-bound filter in front of a cyclic coordinate descent with a soft-threshold over ALL
+ * columns of the support (a dependent column can lower the value under an l1 term).  eta_l1 == 0 runs the very code of
+ * slm_solve_l0(ds, alpha, n_groups, 0, NULL, ...).  The contract is slm_solve_l0's: up to 64 columns and 64 groups
+ * (SLM_ERR_UNSUPPORTED beyond, and on row-sharded datasets); negative or non-finite alpha / eta_l1, negative big_M, a need
+ * bit at or beyond the group count: SLM_ERR_BAD_ARG before anything is launched; SLM_ERR_NOT_CONVERGED with the incumbent
+ * in the outputs when the node budget ran out.  beta_out: the winner's coefficients, recomputed once on the host by the
+ * same descent and polished (the free non-zero coordinates solved exactly on their sign pattern, kept when signs and box
+ * hold).  info as for slm_solve_l0, with info->L = the proven lower bound on the value of all columns that the subtree
+ * bound used (the lasso dual value at a feasible point where that is above q_all) and info->rejects = descents run.
+ */
+int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, double big_M, const uint64_t* need /* n_groups masks or NULL */,
+                    int64_t max_nodes /* <=0: default */, double* beta_out, uint64_t* support_out, double* lower_bound_out,
+                    int64_t* nodes_out, slm_point_info* info);
+
+/*
  * The Gram of a row set, for covariance passes (SLM_FLAG_COVARIANCE): G = X^T W X / n_eff, c = X^T W y / n_eff and
  * y^T W y / n_eff, kept with the dataset (8 ld^2 bytes each) and found again by a fingerprint of the row weights and
  * n_eff -- what a lane of slm_solve_lanes brings as (row_weight, n_eff).  row_weight: length n on the host, NULL = the

@@ -328,6 +328,31 @@ py::tuple solve_l0(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, do
   return py::make_tuple(beta, support, lower, nodes, info, rc);
 }
 
+// slm_solve_l0_l1: the same search in l1 mode (the reference's L1L0); the tuple of solve_l0.
+py::tuple solve_l0_l1(uintptr_t ds, int64_t p, double alpha, double eta_l1, double big_M, const py::object& need, int64_t max_nodes) {
+  const uint64_t* needp = nullptr;
+  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
+  if (!need.is_none()) {
+    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
+    if (!need_arr) throw py::value_error("need is not convertible to uint64");
+    needp = need_arr.data();
+  }
+  py::array_t<double> beta((py::ssize_t)p);
+  py::array info = info_bytes(1);
+  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
+  uint64_t support = 0;
+  double lower = 0.0;
+  int64_t nodes = 0;
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_l1(reinterpret_cast<slm_dataset*>(ds), alpha, eta_l1, big_M, needp, max_nodes, beta.mutable_data(), &support, &lower,
+                         &nodes, static_cast<slm_point_info*>(info.mutable_data()));
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, support, lower, nodes, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -343,6 +368,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_path_lanes", &solve_path_lanes);
   m.def("dataset_create", &dataset_create);
   m.def("solve_l0", &solve_l0);
+  m.def("solve_l0_l1", &solve_l0_l1);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

@@ -3,6 +3,8 @@
 // Gurobi or SCIP through cvxpy.  Here: the dataset's own Gram (engine_cov.hip), the search order, the greedy seed and the
 // unconstrained bound on the host (p <= 64: microseconds), ONE launch of the search, and the winner's coefficients
 // recomputed in one place from the Gram on its support.
+// slm_solve_l0_l1 (the reference's L1L0, _regularized_l0.py:258-410) is the same call in l1 mode: the kernel's L1 instantiation,
+// the l0_l1_* functions of l0_host.hpp for seed, winner and the dual bound on all columns.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -12,15 +14,17 @@ namespace {
 constexpr long long kL0DefaultNodes = 1ll << 30;  // the budget of a call that names none: at the 6.2e8 nodes/s measured at 25 x 30
                                                   // (profiles/l0_search.txt) a call that exhausts it stays under two seconds
 
-}  // namespace
-
-extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
-                            const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
-                            double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
+// Both entries.  eta_l1 > 0 is l1 mode (the kernel's L1 instantiation, the l0_l1_* functions of l0_host.hpp); eta_l1 == 0 is the
+// search without an l1 term, instruction for instruction what it was before there was one.
+int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double eta_l1, double big_M,
+                  const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* lower_bound_out,
+                  int64_t* nodes_out, slm_point_info* info) {
   if (!ds || !beta_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   // the arguments are checked before anything touches the device
   if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(SLM_ERR_BAD_ARG, "alpha must be finite and >= 0");
   if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(SLM_ERR_BAD_ARG, "eta must be finite and >= 0");
+  if (!(eta_l1 >= 0.0) || !std::isfinite(eta_l1)) return fail(SLM_ERR_BAD_ARG, "eta_l1 must be finite and >= 0");
+  const bool l1 = eta_l1 > 0.0;
   if (!(big_M >= 0.0)) return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
   const int64_t p64 = ds->p;
   const int ng = ds->singleton ? (int)std::min<int64_t>(p64, L0_PMAX + 1) : ds->G;
@@ -36,6 +40,12 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
   if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "the exact l0 search is not built for row-sharded datasets");
   const int p = (int)p64;
   const int K = max_groups < 0 ? 0 : std::min<int>(max_groups, ng);
+  // the value (without alpha |S|) and coefficients of one support, as the kernel values a node
+  auto value_of = [&](const std::vector<double>& H, const std::vector<double>& c, const std::vector<int>& gstart, unsigned long long mask,
+                      bool polish, double* beta) {
+    return l1 ? l0_l1_support(H.data(), c.data(), p, gstart, mask, eta_l1, big_M, polish, beta)
+              : l0_support(H.data(), c.data(), p, gstart, mask, big_M, polish, beta);
+  };
   slm_engine* eng = ds->eng;
   HIP_TRY(hipSetDevice(eng->device));
   hipStream_t s = eng->stream;
@@ -101,6 +111,8 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
     for (int j = 0; j < p; ++j) (void)f.push(j);
     q_all = -0.5 * f.ss;
   }
+  // the subtree bound's lower bound on the value of all columns: in l1 mode the lasso dual value where it is above q_all
+  const double bound = l1 ? l0_l1_lower_bound(H.data(), c.data(), p, ds->cov[(size_t)entry].yy, eta_l1, q_all) : q_all;
   const unsigned long long all_mask = ng == 64 ? ~0ull : ((1ull << ng) - 1);
   double seed_val = 0.0;  // the empty support
   unsigned long long seed_mask = 0;
@@ -123,7 +135,7 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
       if (pick < 0) break;
       cur |= 1ull << pick;
       // (the factor keeps search order inside the kernel; the seed's value is taken the same way)
-      const double v = l0_support(H.data(), c.data(), p, gstart, cur, big_M, false, beta_s.data()) + alpha * (double)(step + 1);
+      const double v = value_of(H, c, gstart, cur, false, beta_s.data()) + alpha * (double)(step + 1);
       if (v < seed_val) {
         seed_val = v;
         seed_mask = cur;
@@ -131,7 +143,7 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
       for (int j = gstart[(size_t)pick]; j < gstart[(size_t)pick + 1]; ++j) (void)f.push(j);
     }
     if (K >= ng && ng > 0) {  // every group: the one support whose value can meet the bound exactly
-      const double v = l0_support(H.data(), c.data(), p, gstart, all_mask, big_M, false, beta_s.data()) + alpha * (double)ng;
+      const double v = value_of(H, c, gstart, all_mask, false, beta_s.data()) + alpha * (double)ng;
       if (v < seed_val) {
         seed_val = v;
         seed_mask = all_mask;
@@ -174,9 +186,13 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
   k.need = dev + off_need;
   k.gstart = reinterpret_cast<const long long*>(dev + off_gs);
   k.p = p; k.ng = ng; k.d = d; k.K = K;
-  k.alpha = alpha; k.big_M = big_M; k.q_all = q_all;
+  k.alpha = alpha; k.big_M = big_M; k.q_all = bound;
+  k.eta_l1 = eta_l1;
   k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
-  hipLaunchKernelGGL(l0_search_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  if (l1)
+    hipLaunchKernelGGL(l0_search_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  else
+    hipLaunchKernelGGL(l0_search_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
   SLM_TRY(check_launch());
   HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(unsigned long long) * off_H, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -195,7 +211,7 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
   }
   const bool finished = h[L0_ABORTED] == 0;
   // its coefficients, recomputed here whichever wave found it
-  const double quad = l0_support(H.data(), c.data(), p, gstart, win_mask, big_M, true, beta_s.data());
+  const double quad = value_of(H, c, gstart, win_mask, true, beta_s.data());
   int n_active = 0;
   unsigned long long support = 0;
   for (int g = 0; g < ng; ++g)
@@ -206,7 +222,7 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
   const double objective = quad + alpha * (double)n_active;
   for (int i = 0; i < p; ++i) beta_out[cols[(size_t)i]] = beta_s[(size_t)i];
   if (support_out) *support_out = support;
-  if (lower_bound_out) *lower_bound_out = finished ? objective : std::min(objective, q_all);
+  if (lower_bound_out) *lower_bound_out = finished ? objective : std::min(objective, bound);
   if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
   if (info) {
     // 1/(2n)||X beta - y||_W^2 = 1/2 beta^T G beta - c^T beta + 1/2 y^T W y / n from the Gram already on the host: no second launch
@@ -224,7 +240,8 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
     info->mode = 4;
     info->kkt = objective;
     info->mu = seed_val;
-    info->L = q_all;
+    info->L = bound;
+    info->rejects = (int32_t)std::min<unsigned long long>(h[L0_DESCENTS], 0x7fffffffull);  // (l1 mode: descents run)
     double bn = 0.0;
     for (int j = 0; j < p; ++j) bn += beta_out[j] * beta_out[j];
     info->beta_norm = std::sqrt(bn);
@@ -232,4 +249,20 @@ extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, d
   if (!finished) return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld) ran out before the search finished: the incumbent is returned",
                              (long long)k.max_nodes);
   return SLM_OK;
+}
+
+}  // namespace
+
+extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
+                            const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
+                            double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_impl(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out, info);
+}
+
+// The reference's L1L0 (_regularized_l0.py:258-410): no cardinality bound, no ridge term, eta_l1 ||beta||_1.
+extern "C" int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, double big_M, const uint64_t* need, int64_t max_nodes,
+                               double* beta_out, uint64_t* support_out, double* lower_bound_out, int64_t* nodes_out,
+                               slm_point_info* info) {
+  return solve_l0_impl(ds, alpha, L0_PMAX, 0.0, nullptr, eta_l1, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out,
+                       info);
 }

@@ -1,7 +1,8 @@
 // Host side of the exact l0 search (l0_kernels.hpp, engine_l0.hip): the limits and tolerances the kernel and the host share,
 // the factor of H on a growing list of columns as the kernel keeps it, the boxed descent candidates are compared by, and the
-// value and coefficients of one support.  Like host_logic.hpp and tail_logic.hpp it is free of HIP types so that g++
-// compiles it alone: tests/host_logic_test.cpp runs these functions on the CPU under the sanitizers, and slm_solve_l0 calls
+// value and coefficients of one support, and the same for l1 mode (a lasso per support: the descent, its polish, the dual
+// bound on all columns).  Like host_logic.hpp and tail_logic.hpp it is free of HIP types so that g++
+// compiles it alone: tests/host_logic_test.cpp and tests/l1l0_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 call
 // THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.
 #pragma once
 #include <stddef.h>
@@ -161,6 +162,174 @@ inline double l0_support(const double* H, const double* c, int p, const std::vec
   if (outside) val = l0_boxed(H, c, p, f.col, f.m, big_M, polish, b);
   for (int k = 0; k < f.m; ++k) beta[f.col[k]] = b[k];
   return val;
+}
+
+// ---- l1 mode (slm_solve_l0_l1, the reference's L1L0): eta ||beta||_1 joins the objective ------------------------------------
+//
+// One coordinate step of the descent, the kernel's own: clip(soft(b - g / h, eta / h), +-big_M).  A column of zeros (h = 0)
+// keeps a zero coefficient.  (constexpr: the device code calls this very function.)
+constexpr double l0_l1_step(double b, double g, double h, double eta, double big_M) {
+  if (!(h > 0.0)) return 0.0;
+  const double u = b - g / h, th = eta / h;
+  const double s = u > th ? u - th : (u < -th ? u + th : 0.0);
+  return s < -big_M ? -big_M : (s > big_M ? big_M : s);
+}
+
+// 1/2 b^T H_S b - c_S^T b + eta ||b||_1 on the columns `cols`
+inline double l0_l1_value(const double* H, const double* c, int p, const int* cols, int m, double eta, const double* b) {
+  double val = 0.0;
+  for (int r = 0; r < m; ++r) {
+    double t = 0.0;
+    for (int k = 0; k < m; ++k) t += H[(size_t)cols[r] * p + cols[k]] * b[k];
+    val += b[r] * (0.5 * t - c[cols[r]]) + eta * std::fabs(b[r]);
+  }
+  return val;
+}
+
+// min 1/2 b^T H_S b - c_S^T b + eta ||b||_1 over |b_j| <= big_M on the columns `cols` -- ANY columns of a support, dependent
+// ones included (with an l1 term a dependent column can lower the value).  The kernel's descent with the kernel's stopping
+// rule; b: in the start, out the point reached.  Returns the value the kernel computes, 1/2 sum b_r (g_r - c_r) + eta ||b||_1.
+inline double l0_l1_descent(const double* H, const double* c, int p, const int* cols, int m, double eta, double big_M, double* b) {
+  std::vector<double> g((size_t)m);
+  for (int r = 0; r < m; ++r) b[r] = std::min(std::max(b[r], -big_M), big_M);
+  for (int r = 0; r < m; ++r) {
+    double t = -c[cols[r]];
+    for (int k = 0; k < m; ++k) t += H[(size_t)cols[r] * p + cols[k]] * b[k];
+    g[(size_t)r] = t;
+  }
+  for (int sweep = 0; sweep < L0_CD_SWEEPS; ++sweep) {
+    double maxd = 0.0, maxb = 0.0;
+    for (int k = 0; k < m; ++k) {
+      const double nb = l0_l1_step(b[k], g[(size_t)k], H[(size_t)cols[k] * p + cols[k]], eta, big_M);
+      const double dk = nb - b[k];
+      if (dk != 0.0) {
+        for (int r = 0; r < m; ++r) g[(size_t)r] += H[(size_t)cols[r] * p + cols[k]] * dk;
+        b[k] = nb;
+      }
+      maxd = std::max(maxd, std::fabs(dk));
+      maxb = std::max(maxb, std::fabs(nb));
+    }
+    if (maxd <= L0_CD_TOL * maxb || maxd == 0.0) break;
+  }
+  double val = 0.0;
+  for (int r = 0; r < m; ++r) val += 0.5 * b[r] * (g[(size_t)r] - c[cols[r]]) + eta * std::fabs(b[r]);
+  return val;
+}
+
+// Polish of a descent's point: the free, non-zero coordinates are solved exactly on their sign pattern,
+//     H_FF x = c_F - eta sign(b_F) - H_FB b_B,
+// with the bound ones (B) where they are and the zero ones at zero.  x is taken only when every sign and the box hold: it is
+// then the minimiser over the face the descent's point lies in, so its value is not above that point's (to rounding).
+// Returns the value of the point kept, computed from that point.
+inline double l0_l1_polish(const double* H, const double* c, int p, const int* cols, int m, double eta, double big_M, double* b) {
+  const double v0 = l0_l1_value(H, c, p, cols, m, eta, b);  // (what is returned whenever the point stays as it is)
+  std::vector<int> fr;
+  for (int k = 0; k < m; ++k)
+    if (b[k] != 0.0 && std::fabs(b[k]) < big_M) fr.push_back(k);
+  const int f = (int)fr.size();
+  if (f == 0) return v0;
+  std::vector<double> A((size_t)f * f), x((size_t)f);
+  for (int i = 0; i < f; ++i) {
+    const int ci = cols[fr[(size_t)i]];
+    double t = c[ci] - (b[fr[(size_t)i]] > 0.0 ? eta : -eta);
+    for (int k = 0; k < m; ++k)
+      if (b[k] != 0.0 && std::fabs(b[k]) >= big_M) t -= H[(size_t)ci * p + cols[k]] * b[k];
+    x[(size_t)i] = t;
+    for (int j = 0; j < f; ++j) A[(size_t)i * f + j] = H[(size_t)ci * p + cols[fr[(size_t)j]]];
+  }
+  for (int i = 0; i < f; ++i)  // Cholesky of the free block, in place; a block that is not definite keeps the descent's point
+    for (int j = 0; j <= i; ++j) {
+      double t = A[(size_t)i * f + j];
+      for (int k = 0; k < j; ++k) t -= A[(size_t)i * f + k] * A[(size_t)j * f + k];
+      if (i == j) {
+        if (!(t > L0_PIVOT * A[(size_t)i * f + i])) return v0;
+        A[(size_t)i * f + i] = std::sqrt(t);
+      } else {
+        A[(size_t)i * f + j] = t / A[(size_t)j * f + j];
+      }
+    }
+  for (int i = 0; i < f; ++i) {
+    double t = x[(size_t)i];
+    for (int k = 0; k < i; ++k) t -= A[(size_t)i * f + k] * x[(size_t)k];
+    x[(size_t)i] = t / A[(size_t)i * f + i];
+  }
+  for (int i = f - 1; i >= 0; --i) {
+    double t = x[(size_t)i];
+    for (int k = i + 1; k < f; ++k) t -= A[(size_t)k * f + i] * x[(size_t)k];
+    x[(size_t)i] = t / A[(size_t)i * f + i];
+  }
+  std::vector<double> nb(b, b + m);
+  for (int i = 0; i < f; ++i) {
+    const double xi = x[(size_t)i], bi = b[fr[(size_t)i]];
+    if (!((bi > 0.0 ? xi > 0.0 : xi < 0.0) && std::fabs(xi) <= big_M)) return v0;
+    nb[(size_t)fr[(size_t)i]] = xi;
+  }
+  for (int k = 0; k < m; ++k) b[k] = nb[(size_t)k];
+  return l0_l1_value(H, c, p, cols, m, eta, b);
+}
+
+// f(S) of the support `mask` (groups in search order) in l1 mode, and its coefficients: the descent over ALL its columns from
+// the back-substituted beta of the independent ones (clipped; zero on the columns the pivot rule skipped), as the kernel
+// values a node.  beta: [p] in search order.
+inline double l0_l1_support(const double* H, const double* c, int p, const std::vector<int>& gstart, unsigned long long mask, double eta,
+                            double big_M, bool polish, double* beta) {
+  L0Factor f(H, c, p);
+  const int ng = (int)gstart.size() - 1;
+  int cols[L0_PMAX];
+  int na = 0;
+  for (int g = 0; g < ng; ++g)
+    if ((mask >> g) & 1)
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) {
+        (void)f.push(j);
+        cols[na++] = j;
+      }
+  for (int j = 0; j < p; ++j) beta[j] = 0.0;
+  double bs[L0_PMAX], b[L0_PMAX];
+  f.solve(bs);
+  for (int r = 0; r < na; ++r) {
+    b[r] = 0.0;
+    for (int k = 0; k < f.m; ++k)
+      if (f.col[k] == cols[r]) b[r] = bs[k];
+  }
+  double val = l0_l1_descent(H, c, p, cols, na, eta, big_M, b);
+  if (polish) val = l0_l1_polish(H, c, p, cols, na, eta, big_M, b);
+  for (int r = 0; r < na; ++r) beta[cols[r]] = b[r];
+  return val;
+}
+
+// A proven lower bound on f(all columns) = min_b 1/2 b^T G b - c^T b + eta ||b||_1 (the box can only raise it): the larger of
+// q_all and the lasso dual value at a feasible point.  With the primal 1/(2n)||y - X b||^2 + eta ||b||_1 = f + yy / 2
+// (yy = y^T W y / n), the dual is  max D(nu) = yy/2 - n/2 ||nu - y/n||^2  over ||X^T nu||_inf <= eta.  For any b,
+// nu = s (y - X b) / n has X^T nu = -s (G b - c), feasible for s = min(1, eta / ||G b - c||_inf), and
+//     D(nu) - yy/2 = -1/2 s^2 rr + s ry - 1/2 yy,    rr = yy - 2 c^T b + b^T G b,  ry = yy - c^T b
+// (at eta -> 0, s = 1 and b the least-squares solution this is -1/2 c^T b = q_all).  b comes from the descent on all
+// columns without the box; only its quality, never its validity, depends on how far that descent got.  The value is
+// lowered by a margin that covers the rounding of the sums and of a Gram that is itself a rounded product.
+inline double l0_l1_lower_bound(const double* G, const double* c, int p, double yy, double eta, double q_all) {
+  if (p <= 0 || p > L0_PMAX || !(eta > 0.0)) return q_all;
+  int cols[L0_PMAX];
+  double b[L0_PMAX];
+  for (int j = 0; j < p; ++j) {
+    cols[j] = j;
+    b[j] = 0.0;
+  }
+  (void)l0_l1_descent(G, c, p, cols, p, eta, HUGE_VAL, b);
+  double cb = 0.0, bGb = 0.0, ginf = 0.0, scale = std::fabs(yy);
+  for (int i = 0; i < p; ++i) {
+    double t = 0.0, ta = 0.0;
+    for (int j = 0; j < p; ++j) {
+      t += G[(size_t)i * p + j] * b[j];
+      ta += std::fabs(G[(size_t)i * p + j] * b[j]);
+    }
+    ginf = std::max(ginf, std::fabs(t - c[i]));
+    cb += c[i] * b[i];
+    bGb += b[i] * t;
+    scale += 2.0 * std::fabs(c[i] * b[i]) + std::fabs(b[i]) * ta;
+  }
+  const double s = ginf > eta ? eta / ginf : 1.0;
+  const double rr = yy - 2.0 * cb + bGb, ry = yy - cb;
+  const double dual = -0.5 * s * s * rr + s * ry - 0.5 * yy - 1e-10 * scale;
+  return dual > q_all && std::isfinite(dual) ? dual : q_all;
 }
 
 }  // namespace slm

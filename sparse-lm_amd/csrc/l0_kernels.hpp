@@ -28,6 +28,15 @@
 // box its value comes from cyclic coordinate descent with clipping on its own block of H, stopped at a relative change of
 // L0_CD_TOL per sweep -- the host values its seed by the same descent, so boxed supports are compared like with like.  A global node counter is
 // bumped in batches; past max_nodes every wave drains and exits.  Every loop is bounded.
+//
+// l1 mode (template parameter L1, slm_solve_l0_l1: the reference's L1L0): eta_l1 ||beta||_1 joins the objective, so a support's
+// value f(S) is a lasso inside the box.  f is monotone in the support and f(S) >= q(S) = -1/2 ||w||^2, so the register
+// Cholesky stays as an exact lower-bound FILTER: only a node whose q(S) + alpha |S| is <= the incumbent and better than the
+// wave's own best runs the descent -- the cyclic one of the boxed case with a soft-threshold in the update -- and its value
+// is what the descent reaches.  The descent runs over ALL columns of the support, the ones the pivot rule skipped
+// included: with an l1 term a column equal to a + b replaces two coefficients by one, so a dependent column CAN lower the
+// value, and the cut of a group that brought no independent column is off.  The subtree bound takes a proven lower bound
+// on f(all columns) from the host in q_all (the lasso dual value at a feasible point, or q_all itself).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,7 +49,7 @@ constexpr int L0_WAVES = 4;        // wavefronts per workgroup (they share H in 
 constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
-constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_CTL_WORDS = 8;
+constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CTL_WORDS = 8;
 
 struct L0Args {
   const double* H;                  // [p][p] G + 2 eta T, search order
@@ -51,8 +60,9 @@ struct L0Args {
   double* best_val;                 // [waves of the grid]
   unsigned long long* best_mask;    // [waves of the grid]
   int p, ng, d, K;
-  double alpha, big_M, q_all;
+  double alpha, big_M, q_all;       // (q_all: the proven lower bound on the value of ALL columns the subtree bound uses)
   long long max_nodes;
+  double eta_l1;                    // l1 mode only: the weight of ||beta||_1
 };
 
 // order-preserving image of a double in an unsigned 64-bit integer (and back)
@@ -84,6 +94,8 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
   return v;
 }
 
+// L1 = false: the search above.  L1 = true: eta_l1 ||beta||_1 joins the objective (see the head of the file).
+template <bool L1>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
   __shared__ double Hs[L0_PMAX * L0_PMAX];
   __shared__ double cs[L0_PMAX];
@@ -105,6 +117,9 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   for (int k = 0; k < L0_PMAX; ++k) Lrow[k] = 0.0;
   double invd = 0.0, w = 0.0;
   int mycol = 0;
+  // l1 mode: lane r also stands for the r-th column of the SUPPORT (dependent ones included), na of them
+  int acol = 0, na = 0, st_na = 0;
+  long long descents_local = 0;
   // the state before group g was decided, held by lane g
   int st_m = 0;
   double st_ss = 0.0;
@@ -135,6 +150,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     }
     inc = l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     int m = 0, cnt = 0, depth = 0;
+    na = 0;
     double ss = 0.0;
     unsigned long long incl = 0, needm = 0;
     bool down = true;
@@ -155,6 +171,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           st_m = m;
           st_ss = ss;
           st_need = needm;
+          if constexpr (L1) st_na = na;
         }
         bool ok = want;
         if (ok) {
@@ -177,6 +194,10 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
             }
           }
           const int c0 = __builtin_amdgcn_readfirstlane(gs[g]), c1 = __builtin_amdgcn_readfirstlane(gs[g + 1]);
+          if constexpr (L1) {  // the support's own column list grows by the whole group
+            if (lane >= na && lane < na + (c1 - c0)) acol = c0 + (lane - na);
+            na += c1 - c0;
+          }
           for (int j = c0; j < c1; ++j) {
             // append column j: x = L^-1 H[cols, j] by columns, x_k broadcast from lane k at step k
             const double hjj = Hs[j * p + j];
@@ -206,7 +227,9 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           }
           // a group that brought no column leaves the value where it was and costs a slot (and alpha): unless another
           // group needs it, every support with it is matched by the same support without it
-          if (m == __builtin_amdgcn_readlane(st_m, g) && !((needed >> g) & 1)) ok = false;
+          // (not with an l1 term: a column equal to a + b replaces two coefficients by one, and the value falls)
+          if constexpr (!L1)
+            if (m == __builtin_amdgcn_readlane(st_m, g) && !((needed >> g) & 1)) ok = false;
         }
         if (ok) {
           incl |= 1ull << g;
@@ -226,7 +249,42 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
                 if (lane == k) beta = (w - part) * invd;
               }
             }
-            if (l0_wave_max(lane < m ? fabs(beta) : 0.0) > big_M) {
+            if constexpr (L1) {
+              // the node's value is a lasso inside the box on ALL columns of the support: the same cyclic descent with a
+              // soft-threshold, from the back-substituted beta (clipped; zero on the columns the pivot rule skipped).
+              // Lane r keeps beta_r and the gradient entry (H beta - c)_r of the support's r-th column.
+              ++descents_local;
+              const double eta1 = a.eta_l1;
+              double b1 = 0.0;
+              for (int k = 0; k < m; ++k) {
+                const int ck = __builtin_amdgcn_readlane(mycol, k);
+                const double bk = l0_bcast(beta, k);
+                if (lane < na && acol == ck) b1 = fmin(fmax(bk, -big_M), big_M);
+              }
+              double gr = lane < na ? -cs[acol] : 0.0;
+              for (int k = 0; k < na; ++k) {
+                const int ck = __builtin_amdgcn_readlane(acol, k);
+                gr = fma(lane < na ? Hs[ck * p + acol] : 0.0, l0_bcast(b1, k), gr);
+              }
+              for (int sweep = 0; sweep < L0_CD_SWEEPS; ++sweep) {
+                double maxd = 0.0, maxb = 0.0;
+                for (int k = 0; k < na; ++k) {
+                  const int ck = __builtin_amdgcn_readlane(acol, k);
+                  const double bk = l0_bcast(b1, k), gk = l0_bcast(gr, k);
+                  const double nb = l0_l1_step(bk, gk, Hs[ck * p + ck], eta1, big_M);
+                  const double dk = nb - bk;
+                  if (dk != 0.0) {
+                    gr = fma(lane < na ? Hs[ck * p + acol] : 0.0, dk, gr);
+                    if (lane == k) b1 = nb;
+                  }
+                  maxd = fmax(maxd, fabs(dk));
+                  maxb = fmax(maxb, fabs(nb));
+                }
+                if (maxd <= L0_CD_TOL * maxb || maxd == 0.0) break;
+              }
+              val = 0.5 * l0_wave_sum(lane < na ? b1 * (gr - cs[acol]) : 0.0) + eta1 * l0_wave_sum(lane < na ? fabs(b1) : 0.0) +
+                    alpha * (double)cnt;
+            } else if (l0_wave_max(lane < m ? fabs(beta) : 0.0) > big_M) {
               // the box binds: cyclic coordinate descent with clipping on the support's block of H; lane r keeps
               // beta_r and the gradient entry (H beta - c)_r
               beta = fmin(fmax(beta, -big_M), big_M);
@@ -289,6 +347,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
       if (try_exclude) {
         m = __builtin_amdgcn_readlane(st_m, g);
         ss = l0_bcast(st_ss, g);
+        if constexpr (L1) na = __builtin_amdgcn_readlane(st_na, g);
         needm = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(st_need >> 32), g) << 32) |
                 (unsigned)__builtin_amdgcn_readlane((int)st_need, g);
         if ((needm >> g) & 1) {  // an included group needs this one
@@ -304,6 +363,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   }
   if (lane == 0) {
     if (nodes_local > 0) atomicAdd(&a.ctl[L0_NODES], (unsigned long long)nodes_local);
+    if constexpr (L1)
+      if (descents_local > 0) atomicAdd(&a.ctl[L0_DESCENTS], (unsigned long long)descents_local);
     const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
     a.best_val[wv] = best_v;
     a.best_mask[wv] = best_mask;

@@ -89,6 +89,7 @@ ABI_SYMBOLS = (
     "slm_solve_standardized_sgl",
     "slm_solve_constrained",
     "slm_solve_l0",
+    "slm_solve_l0_l1",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -347,6 +348,7 @@ def load_library():
             "slm_solve_standardized_sgl": [vp, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
             "slm_solve_constrained": [vp, vp, vp, i32, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
             "slm_solve_l0": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
+            "slm_solve_l0_l1": [vp, dbl, dbl, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1308,6 +1310,42 @@ class Dataset:
             "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
             "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
             "box_tol": 1e-12,  # L0_CD_TOL: relative change per sweep at which boxed candidates' descents stop
+        }
+
+    def solve_l0_l1(self, alpha=0.0, eta_l1=0.0, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_l1``: the exact search in its l1 mode (the reference's ``L1L0``) for
+        ``1/2 b^T G b - c^T b + eta_l1 ||b||_1 + alpha |S|`` with ``|b_j| <= big_M`` and the hierarchy ``need``; no bound on
+        ``|S|``.  ``eta_l1 == 0`` runs the code of ``solve_l0``.  Returns what ``solve_l0`` returns; ``info`` also holds
+        ``descents`` (candidates that passed the lower-bound filter and were valued by the descent) and ``q_all`` is the
+        proven lower bound on the value of all columns that the subtree bound used."""
+        _sync_knobs()
+        G = self.n_groups
+        need_ = None
+        if need is not None:
+            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
+            if need_.shape != (G,):
+                raise ValueError(f"need must have {G} entries")
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        if b is not None:
+            beta, support, lower, nodes, rec, rc = b.solve_l0_l1(self._h.value, self.p, float(alpha), float(eta_l1), float(big_M), need_,
+                                                                 int(max_nodes))
+            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
+        else:
+            beta = np.empty(self.p)
+            sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
+            infos = np.zeros(1, dtype=_INFO_DTYPE)
+            rc = self._lib.slm_solve_l0_l1(self._h, float(alpha), float(eta_l1), float(big_M), _ptr(need_), int(max_nodes), _ptr(beta),
+                                           C.byref(sup), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
+            if rc != SLM_ERR_NOT_CONVERGED:
+                _check(rc)
+            support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
+        return beta, int(support), {
+            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
+            "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
+            "descents": int(info["rejects"]), "box_tol": 1e-12,
         }
 
 

@@ -1,0 +1,12 @@
+"""The reference's five mixed-integer estimators (``sparselm.model``'s ``BestSubsetSelection``,
+``RidgedBestSubsetSelection``, ``RegularizedL0``, ``L1L0``, ``L2L0``) in one place, all solved exactly by the depth-first
+search over supports on the GPU.
+
+``from sparselm_amd.miqp import L1L0`` is the import path of ``L1L0``.  ``sparselm_amd.model`` exports the other four
+(``model.MIQP_ESTIMATORS``), as before.
+"""
+
+from .model._l1l0 import L1L0
+from .model._miqp import L2L0, BestSubsetSelection, RegularizedL0, RidgedBestSubsetSelection
+
+__all__ = ["BestSubsetSelection", "RidgedBestSubsetSelection", "RegularizedL0", "L1L0", "L2L0"]

@@ -1,0 +1,54 @@
+"""``L1L0`` under the reference's name (reference src/sparselm/model/_miqp/_regularized_l0.py:258-410; constructor and
+parameter constraints :343-369, objective :395-410).
+
+The reference's objective divided by ``2n``:
+
+    minimise over supports S (sets of GROUPS) and beta, supp beta in cols(S), |beta_j| <= big_M:
+        1/2 beta^T G beta - c^T beta + eta ||beta||_1 + alpha |S|,      G = X^T X / n,  c = X^T y / n
+    subject to  i in S => hierarchy[i] in S
+
+-- no bound on ``|S|`` and no ridge term.  A support's value is a lasso inside the box.  The depth-first search of the other
+four estimators (``_miqp.py``) solves it exactly in its l1 mode (``slm_solve_l0_l1``, csrc/l0_kernels.hpp): the quadratic
+value from the Cholesky factor in registers is a lower bound on a support's value, so it filters the candidates, and the
+ones that pass are valued by a cyclic coordinate descent with a soft-threshold over ALL columns of the support.  Unlike
+without an l1 term, a column that depends on the other active columns may carry the coefficient (a column equal to
+``a + b`` replaces two coefficients by one).  ``eta = 0`` is ``RegularizedL0``, bit for bit.
+
+The import path is ``sparselm_amd.miqp.L1L0``; ``sparselm_amd.model`` keeps the four names it had.
+"""
+
+from __future__ import annotations
+
+from numbers import Real
+
+from sklearn.utils._param_validation import Interval
+
+from ._miqp import RegularizedL0
+
+__all__ = ["L1L0"]
+
+
+class L1L0(RegularizedL0):
+    """``1/(2n)||X beta - y||^2 + eta ||beta||_1 + alpha |S|`` over active groups S (reference _regularized_l0.py:258-410),
+    solved exactly.
+
+    Args as in the reference: ``groups``, ``alpha`` (l0 weight), ``eta`` (l1 weight), ``big_M``, ``hierarchy``,
+    ``ignore_psd_check``, ``fit_intercept``, ``copy_X``, ``warm_start``, ``solver``, ``solver_options``.  Fitted attributes as
+    for the other exact l0 estimators; ``solver_info_`` also holds ``descents``, the candidates that passed the lower-bound
+    filter and were valued by the descent.
+    """
+
+    _hyper_parameter_constraints: dict = {
+        "eta": [Interval(type=Real, left=0.0, right=None, closed="left")],
+        **RegularizedL0._hyper_parameter_constraints,
+    }
+
+    def __init__(self, groups=None, alpha=1.0, eta=1.0, big_M=100, hierarchy=None, ignore_psd_check=True, fit_intercept=False,
+                 copy_X=True, warm_start=False, solver=None, solver_options=None):
+        super().__init__(groups=groups, alpha=alpha, big_M=big_M, hierarchy=hierarchy, ignore_psd_check=ignore_psd_check,
+                         fit_intercept=fit_intercept, copy_X=copy_X, warm_start=warm_start, solver=solver,
+                         solver_options=solver_options)
+        self.eta = eta
+
+    def _l1_weight(self):
+        return float(self.eta)

@@ -14,8 +14,9 @@ _regularized_l0.py:157-161, ``TikhonovMixin`` _base.py:544-546) are all
 with ``alpha = 0`` for the two best-subset classes (the reference's missing ``1/(2n)`` there does not move the minimiser),
 ``sparse_bound =`` the number of groups for the two regularised ones, and ``eta = 0`` without a ridge term.
 
-``L1L0`` is NOT provided: every support would need a lasso solve of its own, and the reference's own tests leave it out.
-There is no ``constraints=`` on these classes.
+The fifth, ``L1L0`` (an l1 term beside the l0 one: a lasso per support), is served by the same search in its l1 mode
+(``slm_solve_l0_l1``); it lives in ``_l1l0.py`` and its import path is ``sparselm_amd.miqp.L1L0`` -- this module's ``__all__``
+and ``sparselm_amd.model`` keep the four names above.  There is no ``constraints=`` on these classes.
 """
 
 from __future__ import annotations
@@ -99,6 +100,10 @@ class _ExactL0(RegressorMixin, BaseEstimator):
     def _tikhonov(self, n_features):
         return None
 
+    def _l1_weight(self):
+        """The weight of ``||beta||_1`` in the objective (``L1L0``); 0: none, the search without an l1 term."""
+        return 0.0
+
     def fit(self, X, y, sample_weight=None):
         X, y = validate_data(self, X, y, accept_sparse=False, y_numeric=True, multi_output=False)
         X = np.asarray(X, dtype=np.float64)
@@ -114,6 +119,7 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         need = _hierarchy_masks(self.hierarchy, self.groups, p)
         alpha, max_groups, eta = self._l0_problem(n_groups)
         T = self._tikhonov(p)
+        eta_l1 = float(self._l1_weight())
         w = None
         if sample_weight is not None:
             w = _check_sample_weight(sample_weight, X, dtype=X.dtype)
@@ -127,8 +133,12 @@ class _ExactL0(RegressorMixin, BaseEstimator):
             ds.set_groups(gidx, n_groups)
             if need is not None and n_groups > 64:
                 need = None  # (the engine refuses the size itself; masks of more than 64 groups have no 64-bit form)
-            beta, support, info = ds.solve_l0(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
-                                              need=need, max_nodes=int(options.get("max_nodes", 0) or 0))
+            max_nodes = int(options.get("max_nodes", 0) or 0)
+            if eta_l1 > 0.0:
+                beta, support, info = ds.solve_l0_l1(alpha=alpha, eta_l1=eta_l1, big_M=float(self.big_M), need=need, max_nodes=max_nodes)
+            else:
+                beta, support, info = ds.solve_l0(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
+                                                  need=need, max_nodes=max_nodes)
         if not info["proven_optimal"]:
             warnings.warn(
                 f"the node budget ran out after {info['nodes']} nodes: the incumbent (objective {info['objective']:.6g}, proven "

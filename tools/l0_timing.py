@@ -5,7 +5,11 @@ estimators on 25 x 20 and 25 x 30 ``make_regression`` draws with ``sparse_bound 
 
 The engine's default budget (``kL0DefaultNodes``, csrc/engine_l0.hip) is the largest power of two for which a call that
 exhausts it at 25 x 30 stays under two seconds at the rate measured here; both numbers are in the file's last lines,
-followed by one timed call under the default budget itself."""
+followed by one timed call under the default budget itself.
+
+Then the l1 mode (``L1L0``, ``slm_solve_l0_l1``) at the same two sizes beside ``RegularizedL0`` on the same data and
+``alpha``, for ``eta`` = 1e-3, 0.05 and 0.5 of ``||X^T y / n||_inf``: nodes, descents run (candidates that passed the
+lower-bound filter), wall time.  No figure is promised for these: how many candidates pass the filter depends on ``eta``."""
 
 import argparse
 import math
@@ -28,6 +32,7 @@ def main():
     from sklearn.datasets import make_regression
 
     from sparselm_amd import _engine
+    from sparselm_amd.miqp import L1L0
     from sparselm_amd.model import L2L0, BestSubsetSelection, RegularizedL0, RidgedBestSubsetSelection
 
     dev = _engine.get_engine().device_info()
@@ -76,6 +81,27 @@ def main():
     info = est.solver_info_
     lines.append(f"BestSubsetSelection 25x30 under the default budget: {info['nodes']} nodes in {wall:.3f} s, "
                  f"proven optimal: {info['proven_optimal']}, objective {info['objective']:.8e}")
+    # the l1 mode beside RegularizedL0: same data, same alpha
+    lines += ["", f"l1 mode (L1L0) beside RegularizedL0, alpha = 3, big_M = 1000, budget {args.max_nodes} nodes per call; eta relative to ||X^T y / n||_inf", ""]
+    lines.append(f"{'estimator':28s} {'n x p':8s} {'eta rel':>8s} {'nodes':>12s} {'descents':>10s} {'wall s':>9s} {'proven':>7s} {'bound used':>16s} "
+                 f"{'objective':>16s}")
+    for p in (20, 30):
+        X, y = make_regression(25, p, n_informative=10, noise=1.0, random_state=0)
+        cinf = float(np.max(np.abs(X.T @ y / X.shape[0])))
+        makers = [(None, lambda: RegularizedL0(alpha=3.0, big_M=1000, solver_options=opts))]
+        makers += [(rel, lambda rel=rel: L1L0(alpha=3.0, eta=rel * cinf, big_M=1000, solver_options=opts)) for rel in (1e-3, 0.05, 0.5)]
+        for rel, make in makers:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                make().fit(X, y)
+                est = make()
+                t0 = time.perf_counter()
+                est.fit(X, y)
+                wall = time.perf_counter() - t0
+            info = est.solver_info_
+            lines.append(f"{type(est).__name__:28s} {'25x%d' % p:8s} {'-' if rel is None else '%g' % rel:>8s} {info['nodes']:12d} "
+                         f"{info.get('descents', 0):10d} {wall:9.4f} {str(info['proven_optimal']):>7s} {info['q_all']:16.8e} {info['objective']:16.8e}")
+            print(lines[-1], flush=True)
     text = "\n".join(lines) + "\n"
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
