@@ -980,6 +980,28 @@ int allow_big_lds(const void* fn, int device) {
   return SLM_OK;
 }
 
+// What the two one-launch splittings share on the host: the defaults of their options, and the LDS left beside what the
+// kernel keeps there (`fixed_bytes`) -- the stage of the rows of the build, then the partial products of three wavefronts
+// and the head of the b-step's direct solves (small_bstep.hpp).  `stage` comes back 0 where that is less than
+// 3 p + min_head doubles or than four padded rows.
+struct SplitLaunch {
+  double tol, tol_inner;
+  int max_sweeps, max_iters;
+  int64_t stage;  // doubles
+};
+static SplitLaunch split_launch(const slm_solve_opts* opts, double tol_inner, int32_t max_sweeps, int p, size_t fixed_bytes, int min_head) {
+  SplitLaunch o;
+  o.tol = opts && opts->tol > 0 ? opts->tol : 1e-8;
+  o.tol_inner = tol_inner > 0 ? tol_inner : std::min(o.tol, 1e-10);
+  o.max_sweeps = max_sweeps > 0 ? max_sweeps : 500;
+  o.max_iters = opts && opts->max_iter > 0 ? (int)std::min<int64_t>(opts->max_iter, 4000) : 4000;
+  const size_t lds = (size_t)SM_LDS_BYTES;
+  o.stage = fixed_bytes + 64 < lds ? (int64_t)((lds - fixed_bytes - 64) / sizeof(double)) : 0;
+  const int ps = 4 * ((p + 4) / 4);
+  if (o.stage < 3 * (int64_t)p + min_head || o.stage < 4 * (int64_t)ps) o.stage = 0;
+  return o;
+}
+
 // ------------------------------------------------------------------------------------------------
 // SparseGroupLasso(standardize=True): the operator splitting on chip (small_split_kernels.hpp)
 // ------------------------------------------------------------------------------------------------
@@ -1000,10 +1022,8 @@ extern "C" int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, cons
   // LDS: Gram matrix, three vectors, the groups' Cholesky factors; what is left stages the rows of the build and
   // then holds the partial products of three wavefronts
   const size_t fixed = sizeof(double) * ((size_t)p * p + 3 * (size_t)p + (size_t)p * gm);
-  const size_t lds = (size_t)SM_LDS_BYTES;
-  const int64_t stage = fixed + 64 < lds ? (int64_t)((lds - fixed - 64) / sizeof(double)) : 0;
-  const int ps = 4 * ((p + 4) / 4);
-  if (stage < 3 * (int64_t)p + 512 || stage < 4 * (int64_t)ps)  // (512: the head of the b-step's direct solves)
+  const SplitLaunch sl = split_launch(opts, tol_inner, max_sweeps, p, fixed, 512);  // (512: the head of the b-step's direct solves)
+  if (sl.stage == 0)
     return fail(SLM_ERR_UNSUPPORTED, "groups of up to %d columns at p = %d leave no room in LDS", gm, p);
   const size_t rec_off = 3 * (size_t)ld + 4;  // state: gamma [ld], u [ld], rho, valid, direct b-steps, factorisations; then beta_out [ld]; then the record
   const size_t n_state = rec_off + (sizeof(slm_point_info) + 7) / 8 + (size_t)ld;  // (+ group norms [ld])
@@ -1035,15 +1055,12 @@ extern "C" int slm_solve_standardized_sgl(slm_dataset* ds, const double* a, cons
   k.info = reinterpret_cast<slm_point_info*>(ds->split_state + rec_off);
   k.gn_out = ds->split_state + rec_off + (sizeof(slm_point_info) + 7) / 8;
   k.warm = warm ? 1 : 0;
-  k.tol = opts && opts->tol > 0 ? opts->tol : 1e-8;
-  k.tol_inner = tol_inner > 0 ? tol_inner : std::min(k.tol, 1e-10);
+  k.tol = sl.tol; k.tol_inner = sl.tol_inner; k.max_sweeps = sl.max_sweeps; k.max_iters = sl.max_iters;
   k.inv_n = 1.0 / (double)ds->n_global;
-  k.max_sweeps = max_sweeps > 0 ? max_sweeps : 500;
-  k.max_iters = opts && opts->max_iter > 0 ? (int)std::min<int64_t>(opts->max_iter, 4000) : 4000;
   k.gmax = gm;
-  k.stage_doubles = (int)stage;
+  k.stage_doubles = (int)sl.stage;
   SLM_TRY(allow_big_lds((const void*)small_stdsgl_kernel, eng->device));
-  hipLaunchKernelGGL(small_stdsgl_kernel, dim3(1), dim3(SM_THREADS), lds, s, k);
+  hipLaunchKernelGGL(small_stdsgl_kernel, dim3(1), dim3(SM_THREADS), (size_t)SM_LDS_BYTES, s, k);
   SLM_TRY(check_launch());
   double* h_out = h + 3 * ld;  // a copy of everything behind gamma and u
   const size_t out_off = 2 * (size_t)ld;
@@ -1088,10 +1105,8 @@ extern "C" int slm_solve_constrained(slm_dataset* ds, const double* a, const dou
   // LDS: Gram matrix, three vectors, the staged constraint vector; what is left stages the rows of the build and then
   // holds the partial products of three wavefronts and the head of the b-step's direct solves
   const size_t fixed = sizeof(double) * ((size_t)p * p + 3 * (size_t)p + (size_t)SC_MMAX);
-  const size_t lds = (size_t)SM_LDS_BYTES;
-  const int64_t stage = fixed + 64 < lds ? (int64_t)((lds - fixed - 64) / sizeof(double)) : 0;
-  const int ps = 4 * ((p + 4) / 4);
-  if (stage < 3 * (int64_t)p + 640 || stage < 4 * (int64_t)ps)
+  const SplitLaunch sl = split_launch(opts, tol_inner, max_sweeps, p, fixed, 640);
+  if (sl.stage == 0)
     return fail(SLM_ERR_UNSUPPORTED, "no room in LDS at p = %d", p);
   slm_engine* eng = ds->eng;
   HIP_TRY(hipSetDevice(eng->device));
@@ -1146,14 +1161,11 @@ extern "C" int slm_solve_constrained(slm_dataset* ds, const double* a, const dou
   k.info = reinterpret_cast<slm_point_info*>(k.lambda_out + m);
   k.state = ds->cons_state;
   k.warm = warm ? 1 : 0;
-  k.tol = opts && opts->tol > 0 ? opts->tol : 1e-8;
-  k.tol_inner = tol_inner > 0 ? tol_inner : std::min(k.tol, 1e-10);
+  k.tol = sl.tol; k.tol_inner = sl.tol_inner; k.max_sweeps = sl.max_sweeps; k.max_iters = sl.max_iters;
   k.inv_n = 1.0 / (double)ds->n_global;
-  k.max_sweeps = max_sweeps > 0 ? max_sweeps : 500;
-  k.max_iters = opts && opts->max_iter > 0 ? (int)std::min<int64_t>(opts->max_iter, 4000) : 4000;
-  k.stage_doubles = (int)stage;
+  k.stage_doubles = (int)sl.stage;
   SLM_TRY(allow_big_lds((const void*)small_constrained_kernel, eng->device));
-  hipLaunchKernelGGL(small_constrained_kernel, dim3(1), dim3(SM_THREADS), lds, s, k);
+  hipLaunchKernelGGL(small_constrained_kernel, dim3(1), dim3(SM_THREADS), (size_t)SM_LDS_BYTES, s, k);
   SLM_TRY(check_launch());
   double* h_out = h.data() + n_in;
   HIP_TRY(hipMemcpyAsync(h_out, d + n_in, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));

@@ -109,6 +109,41 @@ def test_on_chip_and_host_routes_agree():
     assert _rel(ols_chip.coef_, ols_host.coef_) < 1e-6
 
 
+def _feasible_problem(n, p, m):
+    """Dense-ish Lasso data with m rows A b <= hi that half the least-squares fit satisfies -- a quarter of them with no
+    slack -- and row 0 an equality."""
+    rng = np.random.default_rng(1000 * n + 10 * p + m)
+    X = rng.standard_normal((n, p))
+    beta = np.where(rng.random(p) < 0.3, rng.standard_normal(p), 0.0)
+    y = X @ beta + 0.1 * rng.standard_normal(n)
+    A = rng.standard_normal((m, p)) / np.sqrt(p)
+    b_feas = 0.5 * np.linalg.lstsq(X, y, rcond=None)[0]
+    slack = np.where(rng.random(m) < 0.25, 0.0, rng.uniform(0.05, 1.0, m))
+    slack[0] = 0.0  # (the equality goes through the feasible point)
+    hi = A @ b_feas + slack
+    lo = np.full(m, -np.inf)
+    lo[0] = hi[0]
+    alpha = 0.02 * np.max(np.abs(X.T @ y)) / n
+    return X, y, [LinearConstraint(A, lo, hi)], alpha
+
+
+# p = 64 fills a lane's first position, 65 is the first with a second, 128 the widest; m = 64 / 65 is the step to a second
+# constraint row per lane, 512 the most
+@pytest.mark.parametrize("n,p,m", [(40, 5, 1), (160, 64, 64), (160, 65, 65), (300, 128, 512), (160, 65, 1), (40, 5, 65)])
+def test_on_chip_lasso_where_the_kernel_changes_path(n, p, m):
+    from sparselm_amd.model import Lasso
+
+    X, y, cons, alpha = _feasible_problem(n, p, m)
+    chip = Lasso(alpha=alpha, constraints=cons).fit(X, y)
+    assert chip.solver_info_["route"] == "on_chip"
+    assert chip.solver_info_["launches"] == 1
+    _certify(chip, X, y, cons, (alpha * np.ones(p), None, None, None, p))
+    host = Lasso(alpha=alpha, constraints=cons, solver_options={"on_chip": False}).fit(X, y)
+    assert host.solver_info_["route"] == "host"
+    print(f"({n}, {p}, {m}): chip vs host {_rel(chip.coef_, host.coef_):.3e}")
+    assert _rel(chip.coef_, host.coef_) < 1e-6
+
+
 def _abi_call(ds, A, lo, hi, a=None):
     from sparselm_amd import _engine
 

@@ -164,7 +164,8 @@ def test_standardized_sparse_group_splitting_in_one_launch(eng):
     original problem; a rank-deficient group, groups in scattered order, an empty group, and the continuation of the
     splitting variables the adaptive loop uses."""
     rng = np.random.default_rng(5)
-    for n, p, G in ((100, 80, 10), (25, 30, 6), (400, 100, 25), (60, 128, 16)):
+    # (64 / 65 columns: the last width with one position per lane and the first with two)
+    for n, p, G in ((100, 80, 10), (25, 30, 6), (400, 100, 25), (60, 128, 16), (90, 64, 8), (90, 65, 5)):
         X = rng.standard_normal((n, p)) + 0.5 * rng.standard_normal((n, 1))
         groups = rng.permutation(np.arange(p) % G)
         cols = np.flatnonzero(groups == 0)
