@@ -172,6 +172,12 @@ int slm_gradient(slm_dataset* ds, const double* z, double* g_out, double* loss_o
  *            gradient of lane `lane_out` is returned: a lane of the second half is xtr32's second plane, or the vector
  *            units' share of xtr18 / xtr20.  More than one lane needs the column-major copy (built on first use).
  *            Where the dataset has no split pass the call falls back to route 0.
+ *   route 2: the opening's sample product -- what a cold shared path hands to its first, provisional tail step: rows
+ *            [0, n / SLM_SAMPLE_DIV), z ignored (zero), g_out = -X_s^T y / n_s, loss_out = y_s^T y_s / (2 n_s).  Through the
+ *            dataset's fp32 image of those rows (built on first use; csrc/sample_kernels.hpp) where it has one, through the
+ *            fp64 rows otherwise: SLM_SAMPLE_F64=1, row weights, no memory, or an entry of X that a float cannot hold.  One
+ *            lane, no timed launches (ms_out = 0).  (Added under ABI 24: a new value of `route`, which older libraries refuse
+ *            with SLM_ERR_BAD_ARG; no entry, structure or constant changes.)
  *   probe_lanes: lanes of the timed launches behind `reps` / ms_out (<= 0: one); xtr_only: time X^T R alone (route 1).
  * Reference counterpart: the gradient of the smooth term of /root/reference/src/sparselm/model/_lasso.py:109-121.
  */

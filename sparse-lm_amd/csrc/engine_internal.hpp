@@ -28,6 +28,7 @@
 #include "tail_kernels.hpp"
 #include "ws_kernels.hpp"
 #include "split_kernels.hpp"
+#include "sample_kernels.hpp"
 #include "light_kernels.hpp"
 #include "small_kernels.hpp"
 #include "small_split_kernels.hpp"
@@ -267,6 +268,13 @@ struct slm_dataset {
   double* stop_words = nullptr;  // [STOP_WORDS] row-sharded mode: the vector the ranks all-reduce after every pass
   double* XT = nullptr;  // column-major copy of X in tiles of 32 rows (tile_columns_kernel), built on first use
   bool XT_ready = false, XT_failed = false;
+  // fp32 image of the first rows32 rows of X, row-major with its own leading dimension ld32 (a multiple of four floats), for
+  // the opening's sample product (sample_kernels.hpp): built on first use by ensure_x32s, rebuilt when a call's sample is
+  // larger, dropped with anything that rewrites X (x32_drop).  x32_failed: no memory for it; x32_lossy: X holds entries a
+  // float cannot stand in for -- either way the dataset keeps the fp64 sample.  4 * ld32 * rows32 bytes.
+  float* X32s = nullptr;
+  int64_t rows32 = 0, ld32 = 0;
+  bool x32_failed = false, x32_lossy = false;
   // certified partial passes (light_kernels.hpp): the column norms ||X_j|| / sqrt(n_global), built with the copy; the moves'
   // residual changes, their block sums, the borderline columns and their partial products -- allocated on first use
   double* colnorm = nullptr;
@@ -372,6 +380,12 @@ int enqueue_gradient_split(const slm_host::Knobs& kn, slm_dataset* ds, const Lan
                            GradNames* names = nullptr);
 bool split_usable(const slm_host::Knobs& kn, slm_dataset* ds);
 int ensure_xt(const slm_host::Knobs& kn, slm_dataset* ds);
+// the fp32 image of the first n_rows rows (optional: *usable says whether the dataset has one that covers them)
+int ensure_x32s(slm_dataset* ds, int64_t n_rows, bool* usable);
+void x32_drop(slm_dataset* ds);  // X changed
+// the opening's sample product on the image: g = -X32s^T y / n_eff over the first n_rows rows into the g slot of n_lanes lanes,
+// the loss at zero into g[ld].  *queued = false (nothing launched): the partial sums do not fit the dataset's buffer.
+int enqueue_sample_f32(slm_dataset* ds, int64_t n_rows, double n_eff, int n_lanes, const int* done, bool* queued);
 int check_launch();
 // (engine_solve.hip, used by the solve loop of engine_path.hip)
 void launch_rowdot(const slm_host::Knobs& kn, slm_dataset* ds, const SplitKernel* sk, int nblk, int B, SplitArgs& a, hipStream_t s,

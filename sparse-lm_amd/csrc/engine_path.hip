@@ -155,6 +155,7 @@ struct PathCall {
   int ws_comm_rc = 0;        // first RCCL error of the per-pass Gram all-reduce (checked after each chunk)
   bool mg_handover = false;  // the rounds on the model Gram are on: tail points change hands (tail_handover_kernel)
   bool fix_start = false;    // the refinement being queued follows the pass on the row sample (sample start)
+  bool sample_f32 = false;   // the sample's product reads the dataset's fp32 image of its rows (sample_kernels.hpp)
   // ---- queue
   int chunk = 0;
   int64_t max_total = 0, enq = 0, expected = 0, n_sample = 0, prof_off = 0;
@@ -233,6 +234,8 @@ int PathCall::run() {
   if (small) return run_on_chip();
   SLM_TRY(prepare_working_set());
   plan_queue();
+  // (the fp32 image of the sample rows: a one-off of the dataset like the column-major copy, and as optional)
+  if (n_sample > 0 && !kn.sample_f64) SLM_TRY(ensure_x32s(ds, n_sample, &sample_f32));
   SLM_TRY(pass_loop());
   return finish();
 }
@@ -1383,7 +1386,13 @@ int PathCall::queue_chunk() {
     if (sample_pass) {
       LaneSetup part = ls;
       for (int l = 0; l < kMaxLanes; ++l) part.n_eff[l] = (double)ds->n_global * (double)n_sample / (double)n;
-      SLM_TRY(enqueue_gradient_split(kn, ds, part, ds->y, done_flag, ds->ctl, &wa, nullptr, nullptr, n_sample));
+      // Every lane stands at z = 0 and there are no row weights (plan_queue's conditions): the product is ONE vector, -X_s^T y /
+      // n_eff, and the residual launches would only build R = -y for it.  On the fp32 image it is half the bytes; the ranking
+      // it is used for stands far above a float's rounding (sample_kernels.hpp).  SLM_SAMPLE_F64=1, a dataset without the
+      // image: the split pass on the fp64 rows.
+      bool on_image = false;
+      if (sample_f32) SLM_TRY(enqueue_sample_f32(ds, n_sample, part.n_eff[0], B, done_flag, &on_image));
+      if (!on_image) SLM_TRY(enqueue_gradient_split(kn, ds, part, ds->y, done_flag, ds->ctl, &wa, nullptr, nullptr, n_sample));
       TailArgs first = ta;
       first.provisional = 1;
       launch_tail(first, s);

@@ -550,6 +550,7 @@ extern "C" int slm_dataset_center(slm_dataset* ds, double* x_mean_out, double* y
   ds->sketch_valid = false;
   ds->carry_valid = false;
   ds->XT_ready = false;  // X changed in place: the column-major copy is rebuilt on next use
+  x32_drop(ds);          // ... and the fp32 image of the sample rows
   mg_invalidate(ds);     // ... and so is the model Gram
   return SLM_OK;
 }
@@ -583,12 +584,34 @@ extern "C" int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradi
   slm_gradient_opts o;
   memset(&o, 0, sizeof(o));
   if (opts) o = *opts;
-  if (o.route < 0 || o.route > 1) return fail(SLM_ERR_BAD_ARG, "route must be 0 (fused) or 1 (split pass), got %d", o.route);
+  if (o.route < 0 || o.route > 2)
+    return fail(SLM_ERR_BAD_ARG, "route must be 0 (fused), 1 (split pass) or 2 (the opening's sample product), got %d", o.route);
   if (o.n_lanes > kMaxLanes || o.probe_lanes > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "at most %d lanes", kMaxLanes);
   const slm_host::Knobs kn = knobs();
   HIP_TRY(hipSetDevice(ds->eng->device));
   hipStream_t s = ds->eng->stream;
   HIP_TRY(hipMemsetAsync(ds->z, 0, sizeof(double) * ds->ld, s));
+  if (o.route == 2) {
+    // What a cold shared path opens on (PathCall::queue_chunk): rows [0, n / SLM_SAMPLE_DIV), z = 0, scaled by the sample's
+    // share of n_global -- on the fp32 image where the dataset has one, on the fp64 rows otherwise (and with row weights, which
+    // the image's kernel does not know).  One lane; no timed launches.
+    const int64_t n_s = std::max<int64_t>(1, ds->n / kn.sample_div);
+    LaneSetup part = default_lanes(ds, 1);
+    for (int l = 0; l < kMaxLanes; ++l) part.n_eff[l] = (double)ds->n_global * (double)n_s / (double)ds->n;
+    bool usable = false, on_image = false;
+    if (!kn.sample_f64 && !ds->rw) SLM_TRY(ensure_x32s(ds, n_s, &usable));
+    if (usable) SLM_TRY(enqueue_sample_f32(ds, n_s, part.n_eff[0], 1, nullptr, &on_image));
+    if (!on_image) {
+      if (split_usable(kn, ds)) SLM_TRY(enqueue_gradient_split(kn, ds, part, ds->y, nullptr, nullptr, nullptr, nullptr, nullptr, n_s));
+      else SLM_TRY(enqueue_gradient(ds, part, ds->y, nullptr, nullptr, nullptr, n_s));
+    }
+    SLM_TRY(check_launch());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (g_out) HIP_TRY(hipMemcpy(g_out, ds->g, sizeof(double) * ds->p, hipMemcpyDeviceToHost));
+    if (loss_out) HIP_TRY(hipMemcpy(loss_out, ds->g + ds->ld, sizeof(double), hipMemcpyDeviceToHost));
+    if (ms_out) *ms_out = 0.0;
+    return SLM_OK;
+  }
   if (z) HIP_TRY(hipMemcpyAsync(ds->z, z, sizeof(double) * ds->p, hipMemcpyHostToDevice, s));
   const bool use_split = o.route == 1 && split_usable(kn, ds);
   if (use_split) SLM_TRY(ensure_xt(kn, ds));  // (so that tests and probes reach rowdot_mfma_kernel; optional copy)
@@ -897,6 +920,79 @@ int ensure_xt(const slm_host::Knobs& kn, slm_dataset* ds) {
       ds->colnorm_ready = true;
     }
   }
+  return SLM_OK;
+}
+
+// fp32 image of the sample rows (sample_kernels.hpp); optional like the column-major copy: no memory, or entries of X a float
+// cannot hold, leave the dataset on the fp64 sample for good
+void x32_drop(slm_dataset* ds) {
+  dfree(ds->X32s);
+  ds->rows32 = 0;
+  ds->ld32 = 0;
+  ds->x32_lossy = false;  // (the new X is looked at afresh)
+}
+int ensure_x32s(slm_dataset* ds, int64_t n_rows, bool* usable) {
+  *usable = false;
+  if (ds->x32_failed || ds->x32_lossy || n_rows < 1 || n_rows > ds->n) return SLM_OK;
+  if (ds->X32s && ds->rows32 >= n_rows) {
+    *usable = true;
+    return SLM_OK;
+  }
+  hipStream_t s = ds->eng->stream;
+  HIP_TRY(hipStreamSynchronize(s));  // (a smaller image may still be read by a queued launch)
+  x32_drop(ds);
+  const int64_t ld32 = slm_host::sample_ld32(ds->p);
+  unsigned int* lost = nullptr;
+  if (pool_malloc((void**)&ds->X32s, sizeof(float) * (size_t)ld32 * (size_t)n_rows) != hipSuccess ||
+      pool_malloc((void**)&lost, sizeof(unsigned int)) != hipSuccess) {
+    (void)hipGetLastError();
+    if (lost) pool_free(lost);
+    lost = nullptr;
+    dfree(ds->X32s);
+    ds->x32_failed = true;
+    return SLM_OK;
+  }
+  unsigned int host = 0;
+  hipError_t e = hipMemsetAsync(lost, 0, sizeof(unsigned int), s);
+  if (e == hipSuccess) {
+    const int64_t work = n_rows * (ld32 / 4);
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)ds->eng->cus * 8, (work + 255) / 256));
+    hipLaunchKernelGGL(x32_convert_kernel, dim3(blocks), dim3(256), 0, s, (const double*)ds->X, n_rows, ds->ld, ld32, ds->X32s, lost);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, lost, sizeof(unsigned int), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  pool_free(lost);
+  if (e != hipSuccess) {
+    dfree(ds->X32s);
+    return fail(SLM_ERR_HIP, "fp32 image of the sample rows: %s", hipGetErrorString(e));
+  }
+  if (host != 0) {  // (a finite entry became inf, or a non-zero one zero: the image cannot stand in for these rows)
+    dfree(ds->X32s);
+    ds->x32_lossy = true;
+    return SLM_OK;
+  }
+  ds->rows32 = n_rows;
+  ds->ld32 = ld32;
+  *usable = true;
+  return SLM_OK;
+}
+
+int enqueue_sample_f32(slm_dataset* ds, int64_t n_rows, double n_eff, int n_lanes, const int* done, bool* queued) {
+  *queued = false;
+  if (!ds->X32s || n_rows < 1 || n_rows > ds->rows32 || n_lanes < 1 || n_lanes > ds->lane_cap) return SLM_OK;
+  const slm_host::SamplePlan g = slm_host::sample_plan(n_rows, ds->p, ds->ld32, ds->eng->cus);
+  // (partial sums: [yb][ld] and the row blocks' sums of y^2 behind them, in the gradient's own buffer)
+  if ((size_t)g.yb * (size_t)ds->ld + (size_t)g.yb > ds->partial_elems) return SLM_OK;
+  SampleArgs a;
+  a.X32 = ds->X32s; a.y = ds->y; a.partial = ds->partial; a.g = ds->g; a.done = done;
+  a.n_s = n_rows; a.ld32 = ds->ld32; a.ld = ds->ld; a.rows = g.rows; a.pstride = ds->ld;
+  a.p = (int)ds->p; a.yb = g.yb; a.n_lanes = n_lanes;
+  a.scale = 1.0 / n_eff;
+  hipStream_t s = ds->eng->stream;
+  hipLaunchKernelGGL(sample_xty_kernel<8>, dim3((unsigned)g.xb, (unsigned)g.yb), dim3(slm_host::kSampleThreads), 0, s, a);
+  hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)(ds->ld / 16 + 1)), dim3(256), 0, s, a);
+  *queued = true;
   return SLM_OK;
 }
 

@@ -232,6 +232,37 @@ inline XtrGrid xtr_grid(int64_t n, int64_t ld, int col_block, int64_t want) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Grid of the opening's sample product on the fp32 image of the first rows (sample_kernels.hpp): g = -X32s^T y / n_s over
+// the first n_s rows.  A thread owns four columns (one 16-byte load per row), a workgroup of kSampleThreads threads a
+// column block of 4 * kSampleThreads columns and ALL rows of its row block, so no sum crosses a thread before the finishing
+// launch.  Row blocks: as many as give every CU kSampleWgsPerCu workgroups (they are all resident at once: the tile
+// quantisation of one workgroup per CU -- 240 of 256 at 20 000 columns -- does not arise), but at least kSampleMinRows
+// rows each, so that the partial sums (8 bytes per column and row block) stay small beside the rows read (4 bytes per
+// column and row).  No row block is empty: yb = ceil(n_s / rows).
+// ---------------------------------------------------------------------------------------------
+constexpr int kSampleThreads = 256;
+constexpr int kSampleWgsPerCu = 4;
+constexpr int kSampleMinRows = 16;
+struct SamplePlan {
+  int xb, yb;       // column blocks, row blocks
+  int64_t rows;     // rows per row block (the last one may hold fewer, never none)
+  int64_t ld32;     // floats per row of the image: a multiple of four, every row starts on 16 bytes
+};
+inline int64_t sample_ld32(int64_t p) { return (p + 3) / 4 * 4; }
+inline SamplePlan sample_plan(int64_t n_s, int64_t p, int64_t ld32, int cus) {
+  SamplePlan g;
+  g.ld32 = ld32;
+  (void)p;  // (the columns [p, ld32) of the image are zero: the grid covers whole groups of four)
+  const int64_t quads = ld32 / 4;
+  g.xb = (int)std::max<int64_t>(1, (quads + kSampleThreads - 1) / kSampleThreads);
+  if (n_s < 1) n_s = 1;
+  const int64_t want = std::max<int64_t>(1, (int64_t)kSampleWgsPerCu * std::max(1, cus) / g.xb);
+  g.rows = std::max<int64_t>(kSampleMinRows, (n_s + want - 1) / want);
+  g.yb = (int)((n_s + g.rows - 1) / g.rows);
+  return g;
+}
+
+// ---------------------------------------------------------------------------------------------
 // A row set's Gram among those a dataset keeps: by the two fingerprint sums of its row weights and its scaling.
 // ---------------------------------------------------------------------------------------------
 template <typename Entry>
@@ -316,6 +347,7 @@ struct Knobs {
   bool sample_start = true;      // SLM_NO_SAMPLE_START
   int64_t sample_min_rows = 65536;  // SLM_SAMPLE_START_MIN_ROWS (>= 64)
   int sample_div = 4;            // SLM_SAMPLE_DIV (1..64)
+  bool sample_f64 = false;       // SLM_SAMPLE_F64=1: the opening's sample reads the fp64 rows (no fp32 image; tests, A/B runs)
   // model Gram
   int mg = -1;                   // SLM_MG: 0 off, 2 forced from the first snapshot (tests), -1 by capacity
   bool handover = true;          // SLM_NO_HANDOVER
@@ -374,6 +406,7 @@ struct Knobs {
     k.sample_start = !is_set("SLM_NO_SAMPLE_START");
     if (const char* e = text("SLM_SAMPLE_START_MIN_ROWS")) k.sample_min_rows = std::max<int64_t>(64, atoll(e));
     as_int("SLM_SAMPLE_DIV", 1, 64, &k.sample_div);
+    k.sample_f64 = first("SLM_SAMPLE_F64") == '1';
     if (const char c = first("SLM_MG")) k.mg = c == '0' ? 0 : (c == '2' ? 2 : -1);
     k.handover = !is_set("SLM_NO_HANDOVER");
     k.light_pass = !is_set("SLM_NO_LIGHT_PASS");

@@ -822,6 +822,17 @@ class Dataset:
                                              C.byref(ms) if reps > 0 else None))
         return (g, loss.value, ms.value) if reps > 0 else (g, loss.value)
 
+    def sample_product(self):
+        """``slm_gradient_ex`` route 2: what a cold shared path opens on -- ``g = -X_s^T y / n_s`` and the loss at zero over the
+        first ``n // SLM_SAMPLE_DIV`` rows, through the dataset's fp32 image of those rows where it has one (the fp64 rows with
+        ``SLM_SAMPLE_F64=1`` or where a float cannot hold X).  Returns ``(g, loss)``."""
+        _sync_knobs()
+        g = np.empty(self.p)
+        loss = C.c_double()
+        o = _GradientOpts(2, 1, 0, 1, 0)
+        _check(self._lib.slm_gradient_ex(self._h, None, C.byref(o), _ptr(g), C.byref(loss), 0, None))
+        return g, loss.value
+
     def gradient_lanes(self, Z, row_weights=None, n_eff=None, route: int = 0, cov_index=None, n_rows: int = 0):
         """``slm_gradient_lanes``: one gradient pass of ``len(Z)`` lanes through route 0 (fused), 1 (split pass) or 2
         (covariance entries ``cov_index``), each lane with its own point ``Z[l]``, row weights ``row_weights[l]`` and
