@@ -4,6 +4,7 @@
 // slm_solve_lanes_reweighted, slm_solve_path_lanes).  Kernel tables, the launches of a pass and the step-size seeds are
 // engine_solve.hip's.
 #include "engine_internal.hpp"
+#include "ws_solve_kernels.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // path solves

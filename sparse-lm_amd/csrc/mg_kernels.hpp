@@ -474,7 +474,7 @@ static __global__ __launch_bounds__(TAIL_THREADS) void mg_begin_kernel(TailArgs 
 }
 
 // One inner iteration of every active lane, a workgroup per lane: the model gradient at v from the product's partial
-// sums, the proximal step, and the bookkeeping of ws_refine_lane's loop (ws_kernels.hpp) -- spectral steps first, then
+// sums, the proximal step, and the bookkeeping of ws_iterate's loop (ws_solve_kernels.hpp) -- spectral steps first, then
 // accelerated steps with restart, the curvature guard on L -- on all p coordinates.  Streaming like
 // fista_tail_stream_kernel: nothing per feature lives in registers across a workgroup sum; the candidate sits in an LDS image.
 template <int E>

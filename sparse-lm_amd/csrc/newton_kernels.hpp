@@ -1,5 +1,5 @@
 // Dense symmetric positive definite solves inside ONE workgroup: the direct step of the working-set model
-// solver (ws_kernels.hpp).
+// solver (ws_solve_kernels.hpp).
 //
 // When the penalised quadratic model restricted to the face of the current iterate (its non-zero
 // coordinates with their signs) is ill-conditioned, proximal-gradient iterations on it crawl (rate
@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "host_logic.hpp"
 #include "tail_kernels.hpp"
 
 namespace slm {
@@ -139,10 +140,8 @@ __device__ __forceinline__ bool nt_factor(double* F, double* Dinv, int T, double
     const int rem = T - J - 1;
     const int npairs = rem * (rem + 1) / 2;
     for (int q = wave; q < npairs; q += TAIL_WAVES) {
-      int a_ = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);  // q = a (a + 1) / 2 + b, 0 <= b <= a
-      while (a_ * (a_ + 1) / 2 > q) --a_;
-      while ((a_ + 1) * (a_ + 2) / 2 <= q) ++a_;
-      const int b_ = q - a_ * (a_ + 1) / 2;
+      int a_, b_;  // q = a (a + 1) / 2 + b, 0 <= b <= a
+      slm_host::triangle_tile_fast(q, &a_, &b_);
       const int I = J + 1 + a_, Kp = J + 1 + b_;
       const double* li = F + nt_tile_off(I, J);
       const double* lk = F + nt_tile_off(Kp, J);
@@ -262,10 +261,8 @@ static __global__ __launch_bounds__(TAIL_THREADS) void dense_spd_solve_kernel(De
   for (int i = 0; i < m; ++i) dmax = fmax(dmax, a.H[(int64_t)i * m + i]);
   for (int e = tid; e < ntl * 256; e += TAIL_THREADS) {
     const int t = e >> 8, w = e & 255;
-    int I = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while (I * (I + 1) / 2 > t) --I;
-    while ((I + 1) * (I + 2) / 2 <= t) ++I;
-    const int J = t - I * (I + 1) / 2;
+    int I, J;
+    slm_host::triangle_tile_fast(t, &I, &J);
     const int l = w & 63, s = w >> 6;
     const int ii = 16 * I + (l & 15), jj = 16 * J + (l >> 4) + 4 * s;
     F[e] = (ii < m && jj < m) ? a.H[(int64_t)jj * m + ii] : (ii == jj ? 1.0 : 0.0);

@@ -43,7 +43,7 @@ constexpr int WS_MAX_REPEATS = 6;   // refinements of one path point before the 
 // Direct step of the model solver (newton_kernels.hpp): when the proximal-gradient iteration on the model has
 // not converged after WS_NEWTON_AFTER iterations -- or the curvature it measures along its own moves says
 // the face is ill-conditioned (Rayleigh quotient below WS_NEWTON_RQ of lambda_max) -- a projected Newton step
-// on the free coordinates (Cholesky solve, see `direct_step`) replaces further iterations; one prox-gradient
+// on the free coordinates (Cholesky solve, ws_solve_kernels.hpp `ws_direct_step`) replaces further iterations; one prox-gradient
 // step after it tests convergence, and the next direct step follows at once if that fails.
 constexpr int WS_NEWTON_AFTER = 16;
 // Direct steps per refinement.  Where the projected trial points do not lower the model (ill-conditioned faces: the projection
@@ -1212,1068 +1212,6 @@ static __global__ __launch_bounds__(256) void ws_publish_kernel(WsArgs w) {
       __threadfence();
       ws->building = 0;
     }
-  }
-}
-
-// Workgroup sums of the model solver: only the threads of the first `nwc` wavefronts (4 or 8: the ones with q == 0, a
-// position each) bring a value, every thread gets bit-identical totals.  block_sum makes all sixteen wavefronts scan
-// their zeros and fold sixteen partial sums each: 1.8 us per iteration for seven values, issue-bound on the fp64 DPP adds
-// of four wavefronts per SIMD (in-kernel clock marks).  Here the scan runs where the values are, and a lane reads ONE
-// partial sum per value and folds it with its quad (or half-row) by commutative pairings.
-template <int NV>
-__device__ __forceinline__ void ws_sum(double (&v)[NV], double (*lds)[TAIL_WAVES], int nwc) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (wave < nwc) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = wave_sum_lane63(v[k]);
-  }
-  __syncthreads();  // protect lds from the previous use
-  if (wave < nwc && lane == 63) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) lds[k][wave] = v[k];
-  }
-  __syncthreads();
-  if (nwc == 4) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = group_sum_all<4>(lds[k][lane & 3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = group_sum_all<8>(lds[k][lane & 7]);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// (iv) refinement: one workgroup per lane minimises the penalised quadratic model over W.
-// Threads q KP + k work on working-set position k (q splits the matrix-vector product; TPC = 4 parts, or 2
-// beyond 256 positions).  Up to
-// WS_KLDS columns the Gram is copied into LDS first, so an inner iteration never leaves the CU.
-// ---------------------------------------------------------------------------------------------
-// GROUPED: the dataset has real groups (compiled apart from the per-feature variant: each instance carries one
-// direct step, and the registers of the other's never weigh on its iteration loop).
-// DIRECT = false: the iteration alone.  A lane whose solve would take a direct step is left, untouched, to the
-// DIRECT instance launched right behind (WsCtl::want_full; returns false).  Most solves never take one, and the
-// kernel without the factorisation is a fifth of the code, keeps its registers (the full one spills 250 of them
-// at 128 per thread) and leaves no scratch lines for the end of the kernel to write back.
-// LDS of the model solver: one block per workgroup, handed to ws_refine_lane by the kernel
-struct WsSolveLds {
-  double delta[WS_KCAP];
-  double uim[WS_KCAP];
-  double part[WS_THREADS];
-  double Gl[WS_KLDS * WS_KLDS];
-  // direct step (newton_kernels.hpp)
-  NtShared nts;
-  double nv[WS_KCAP];   // right-hand side / solution, indexed by rank in the face
-  double xsl[WS_KCAP];  // direct step with group norms: the base point,
-  double rgl[WS_KCAP];  // the norm of each position's group there,
-  double pbl[WS_KCAP];  // and its group weight
-  double scale2;        // the length scale of the problem on W (see the iteration)
-  int nz[WS_KCAP];
-  int act[WS_KCAP];      // position of the ii-th face coordinate
-  int rank_of[WS_KCAP];  // rank of a position in the face, or -1
-  int nnz, m;
-};
-
-template <bool GROUPED, bool DIRECT>
-__device__ __forceinline__ bool ws_refine_lane(TailArgs a, const WsArgs& w, double (*red)[TAIL_WAVES], WsSolveLds& sh) {
-  double (&delta)[WS_KCAP] = sh.delta;
-  double (&uim)[WS_KCAP] = sh.uim;
-  int (&nz)[WS_KCAP] = sh.nz;
-  int& nnz_s = sh.nnz;
-  double (&part)[WS_THREADS] = sh.part;
-  double (&Gl)[WS_KLDS * WS_KLDS] = sh.Gl;
-  NtShared& nts = sh.nts;
-  double (&nv)[WS_KCAP] = sh.nv;
-  int (&act)[WS_KCAP] = sh.act;
-  int (&rank_of)[WS_KCAP] = sh.rank_of;
-  int& m_s = sh.m;
-  double (&xsl)[WS_KCAP] = sh.xsl;
-  double (&rgl)[WS_KCAP] = sh.rgl;
-  double (&pbl)[WS_KCAP] = sh.pbl;
-  double& scale2_s = sh.scale2;
-  const int lane_id = blockIdx.x;
-  PathCtl* ctl = a.ctl + lane_id;
-  WsCtl* ws = w.ws;
-  if (!ws->valid || ws->building || ws->disabled) return true;
-  const int tid = threadIdx.x;
-  const int p = a.p;
-  const int K = __builtin_amdgcn_readfirstlane(ws->K);
-  const int set = w.set_of[lane_id];
-  const double* Gm = w.Gm + (int64_t)set * (WS_KCAP * WS_KCAP);
-  {
-    const int64_t off = (int64_t)lane_id * a.ld;
-    a.beta += off; a.z += off; a.zprev += off; a.gprev += off;
-    a.a0 += off; a.b0 += off; a.d0 += off;
-    a.pts += ctl->pt_off;
-  }
-  // A lane whose plain step left W (and W could not be extended) is not refined: resetting those
-  // coordinates below would undo its progress.  Neither is a lane that keeps being sent back to the
-  // same path point (the model solve did not reach the tolerance, e.g. a near-singular Gram): it
-  // finishes the point with plain steps.
-  if (ws->stale) {
-    double out[1] = {0.0};
-    for (int j = tid; j < p; j += WS_THREADS)
-      if (w.pos[j] < 0 && a.z[j] != a.zprev[j]) out[0] += 1.0;
-    block_sum<1>(out, red);
-    if (out[0] != 0.0) return true;
-  }
-  const int point_now = ctl->point + ctl->pt_off;
-  // (a point whose refinements keep being sent back because W had to grow -- strongly correlated designs
-  // discover their support in waves -- is a different matter from one the model cannot settle)
-  const int reps = (ws->last_point[lane_id] == point_now && ws->last_cols[lane_id] == ws->Kreal) ? ws->repeats[lane_id] : 0;
-  if (reps >= WS_MAX_REPEATS) return true;
-  const int hard_now = w.hard_call ? ws->hard : ws->hard_lane[lane_id];
-  if (!DIRECT && w.nt != nullptr && hard_now != 0) {  // a refinement of this lane needed direct steps: so may this one
-    if (tid == 0) ws->want_full[lane_id] = 1;
-    return false;
-  }
-
-  unsigned long long tk_s = wall_clock64();
-  auto mark = [&](int slot) {
-    if (tid == 0 && lane_id == 0) {
-      const unsigned long long now = wall_clock64();
-      ws->solve_ticks[slot] += now - tk_s;
-      tk_s = now;
-    }
-  };
-  const slm_path_point pt = a.pts[ctl->point];
-  const int mode = ctl->mode;
-  const double tol = ctl->tol;
-  const bool group_pen = (pt.sb != 0.0) || (pt.sd != 0.0);
-  const bool g_lds = K <= WS_KLDS;
-  if (g_lds) {
-    for (int e = tid; e < K * K; e += WS_THREADS) {
-      const int r = e / K, c = e - r * K;
-      Gl[e] = Gm[r * WS_KCAP + c];
-    }
-  }
-
-  // 4 threads per position up to 256 positions, 2 beyond (1024 threads, WS_KCAP = 512)
-  // Thread q KP + k works on position k, KP = WS_THREADS / TPC: the lanes of a wavefront hold CONSECUTIVE
-  // positions and one q, so a Gram row segment is one coalesced 512-byte load.  (With the TPC threads of a
-  // position next to each other the lanes alternated between TPC rows 4 KiB apart and every lane became
-  // its own memory request: 28 us per product at K = 272, in-kernel clock marks.)
-  const int tsh = K <= 256 ? 2 : 1;
-  const int TPC = 1 << tsh;
-  const int KP = WS_THREADS >> tsh;
-  const int k = tid & (KP - 1), q = tid >> (10 - tsh);
-  static_assert(WS_THREADS == 1024, "q = tid >> (10 - tsh)");
-  const int nwc = KP >> 6;  // wavefronts whose threads account for a position (q == 0): 4 or 8 -- ws_sum
-  const int j = k < K ? w.idx[k] : -1;
-  const bool live = j >= 0;
-  const bool mine = live && q == 0;  // the thread that accounts for position k in reductions
-  const int jj = live ? j : 0;
-  const double z0 = live ? a.zprev[jj] : 0.0;
-  const double g0 = live ? a.gprev[jj] : 0.0;
-  const double x_start = live ? a.z[jj] : 0.0;
-  const double pa = live ? pt.sa * a.a0[jj] : 0.0;
-  const int gsk = live ? w.gs[k] : 0, glk = live ? w.gl[k] : 1;
-  const int gix = a.singleton ? jj : a.gid[jj];
-  const double pb = live ? pt.sb * a.b0[gix] : 0.0;
-  const double pd = live ? pt.sd * a.d0[gix] : 0.0;
-  __syncthreads();  // Gl complete
-
-  // G (val - z0) for the vector held as `val` at every position.  Every call is followed by a
-  // block_sum before the next one, so delta is never overwritten while it is being read.
-  auto matvec = [&](double val, bool dense) -> double {
-    if (q == 0) delta[k] = (k < K) ? val - z0 : 0.0;
-    __syncthreads();
-    double acc = 0.0;
-    if (g_lds) {
-      if (k < K) {
-#pragma unroll 4
-        for (int c = q; c < K; c += TPC) acc = __builtin_fma(Gl[c * K + k], delta[c], acc);
-      }
-    } else if (dense) {
-      // Gram through L2 (K > WS_KLDS): the loads of a batch are issued together, then consumed in the same
-      // order as before (one FMA chain).  Left to the compiler the loop ran one load at a time: 28 us per
-      // product at K = 272 (in-kernel clock marks), i.e. 0.3 ms of power iteration per selection.
-      // (the last batch is a full one too, its entries past the end read the batch's first row again and count with a
-      //  factor of zero: left to a loop of its own the tail ran one load at a time, 0.2 us each -- twelve of them per
-      //  product at K = 176, half the power iteration)
-      if (k < K) {
-        for (int c = __builtin_amdgcn_readfirstlane(q); c < K; c += 16 * TPC) {
-          double gv[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) gv[u] = Gm[(c + u * TPC < K ? c + u * TPC : c) * WS_KCAP + k];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) acc = __builtin_fma(gv[u], c + u * TPC < K ? delta[c + u * TPC] : 0.0, acc);
-        }
-      }
-    } else {
-      if (tid < 64) {  // compact list of the non-zero entries (wave 0, ballots)
-        int basep = 0;
-        for (int c0 = 0; c0 < K; c0 += 64) {
-          const int kk = c0 + tid;
-          const bool nzq = kk < K && delta[kk] != 0.0;
-          const uint64_t m = __ballot(nzq);
-          if (nzq) nz[basep + __popcll(m & ((1ull << tid) - 1ull))] = kk;
-          basep += __popcll(m);
-        }
-        if (tid == 0) nnz_s = basep;
-      }
-      __syncthreads();
-      // (q, the list and its length are the same for all lanes of a wavefront: told to the compiler, the sixteen row
-      //  numbers and the in-range tests live in scalar registers)
-      const int nnz = __builtin_amdgcn_readfirstlane(nnz_s);
-      const int qs = __builtin_amdgcn_readfirstlane(q);
-      // (full batches to the end, as above: the headline's solves have 10-60 non-zeros, FEWER than the 16 TPC a batch
-      //  used to need -- every one of their products ran in the one-load-at-a-time tail, 2.4 us of a 5.6 us iteration.
-      //  Twelve per batch: sixteen cost the kernel without direct steps 28 bytes of scratch.)
-      if (k < K) {
-        for (int m = qs; m < nnz; m += 12 * TPC) {
-          int cc[12];
-          double gv[12];
-#pragma unroll
-          for (int u = 0; u < 12; ++u) cc[u] = __builtin_amdgcn_readfirstlane(nz[m + u * TPC < nnz ? m + u * TPC : m]);
-#pragma unroll
-          for (int u = 0; u < 12; ++u) gv[u] = Gm[cc[u] * WS_KCAP + k];
-#pragma unroll
-          for (int u = 0; u < 12; ++u) acc = __builtin_fma(gv[u], m + u * TPC < nnz ? delta[cc[u]] : 0.0, acc);
-        }
-      }
-    }
-    // the TPC parts of a position sit in different wavefronts: fold them through LDS, in a fixed order
-    part[tid] = acc;
-    __syncthreads();
-    double tot = part[k];
-    for (int qq = 1; qq < TPC; ++qq) tot += part[qq * KP + k];
-    return tot;
-  };
-  // prox of the lane's penalty at the current path point, step s, on the W coordinates
-  auto prox_w = [&](double v, double s) -> double {
-    double u = live ? soft(v, s * pa) : 0.0;
-    if (group_pen) {
-      if (a.singleton) {
-        const double nrm = fabs(u);
-        const double sc = nrm > 0.0 ? fmax(0.0, 1.0 - s * pb / nrm) : 0.0;
-        u *= sc / (1.0 + s * pd);
-      } else {
-        __syncthreads();
-        if (q == 0) uim[k] = u;
-        __syncthreads();
-        double ss = 0.0;
-        for (int m = 0; m < glk; ++m) {
-          const double t = uim[gsk + m];
-          ss = __builtin_fma(t, t, ss);
-        }
-        const double nrm = sqrt(ss);
-        const double sc = (nrm > 0.0 ? fmax(0.0, 1.0 - s * pb / nrm) : 0.0) / (1.0 + s * pd);
-        u *= sc;
-      }
-    }
-    return u;
-  };
-  // penalty value of the vector held as `val` (thread-partial: counted once per position / group)
-  auto pen_part = [&](double val) -> double {
-    double pv = 0.0;
-    if (mine) {
-      pv = pa * fabs(val);
-      if (group_pen && a.singleton) pv += pb * fabs(val) + 0.5 * pd * val * val;
-    }
-    if (group_pen && !a.singleton) {
-      __syncthreads();
-      if (q == 0) uim[k] = live ? val : 0.0;
-      __syncthreads();
-      if (mine && gsk == k) {  // first member of the group
-        double ss = 0.0;
-        for (int m = 0; m < glk; ++m) ss = __builtin_fma(uim[k + m], uim[k + m], ss);
-        pv += pb * sqrt(ss) + 0.5 * pd * ss;
-      }
-    }
-    return pv;
-  };
-
-  mark(0);
-  // ---- lambda_max of this Gram (once per selection): power iteration from a fixed start ---------
-  double Lw = ws->Lw[set];
-  if (!(Lw > 0.0)) {
-    double vec = (k < K) ? 1.0 + 0.37 * (double)(((k * 2654435761u) >> 24) & 0xffu) / 255.0 : 0.0;
-    double lam = 0.0;
-    for (int itp = 0; itp < w.power_iters; ++itp) {
-      const double y = matvec(vec + z0, true);  // matvec works on (val - z0)
-      double s[1] = {q == 0 && k < K ? y * y : 0.0};
-      ws_sum<1>(s, red, nwc);
-      lam = sqrt(s[0]);
-      vec = lam > 0.0 ? y / lam : 0.0;
-    }
-    Lw = lam * 1.1;  // from below; the curvature guard in the loop covers the rest
-    if (!(Lw > 0.0)) return true;  // empty / zero Gram: nothing to refine
-  }
-
-  // ---- direct step: projected Newton on the free coordinates ---------------------------------------
-  // Free set F: the non-zero coordinates of x plus the zero ones whose model gradient exceeds their
-  // threshold (they want to leave zero); orthant: sign(x), or the side such a coordinate wants to move to.
-  // Inside the orthant the model + penalty is a smooth quadratic: d = H_FF^-1 (pseudo-gradient) by a Cholesky
-  // solve, then x - t d projected back onto the orthant (a coordinate that would change sign stops at zero),
-  // t = 1, 1/2, ... until the model value falls (two-metric projection: F holds no coordinate that the
-  // gradient pins at zero, so the projected arc is a descent arc).  When nothing is projected at t = 1 the
-  // result IS the minimiser over that face.  Returns 1 when x moved, 0 when there was nothing to do, -1 when
-  // H_FF is not positive definite or no trial lowered the model (the iteration simply carries on).  mu_out:
-  // estimate of the smallest eigenvalue of the face Hessian (0 = not computed).  This is the variant for
-  // per-feature penalties (and singleton "groups"); real group norms: direct_step_group further down.
-  constexpr bool group_face = GROUPED;  // real groups: direct_step_group below (it also serves a lane of such a
-                                        // dataset whose current point has no group term: b = 0 adds no curvature)
-  const bool newton_capable = w.nt != nullptr;
-  double* ntF = newton_capable ? w.nt + (int64_t)lane_id * NT_SCRATCH : nullptr;
-  double* ntD = newton_capable ? ntF + (int64_t)NT_TILES * 256 : nullptr;
-  auto block_min = [&](double val) -> double {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) val = fmin(val, __shfl_xor(val, off, 64));
-    __syncthreads();
-    if ((tid & 63) == 0) red[0][tid >> 6] = val;
-    __syncthreads();
-    double mm = red[0][0];
-#pragma unroll
-    for (int wv = 1; wv < TAIL_WAVES; ++wv) mm = fmin(mm, red[0][wv]);
-    return mm;
-  };
-  int resolve_cap = WS_NEWTON_RESOLVE;
-  auto direct_step = [&](double& x, double Lmax, double* mu_out, bool want_mu) -> int {
-   if constexpr (GROUPED) {
-    return 0;  // (this instance uses direct_step_group)
-   } else {
-    *mu_out = 0.0;
-    const double thr = pa + pb;  // (singleton groups: b acts as a second l1 weight)
-    // On an ill-conditioned face the Newton direction lives on cancellations between near-collinear columns:
-    // projecting some of its coordinates away leaves a step that is no descent step at any useful length.
-    // So the free set is made consistent first, active-set fashion: a zero coordinate stays in F only if the
-    // solve moves it to the side it wants to go, a non-zero one only if the solve does not carry it across
-    // zero -- the others are set to / kept at zero (and stay out of F for the rest of this call), the
-    // pseudo-gradient is re-evaluated there and the system is solved again (WS_NEWTON_RESOLVE times at most:
-    // then the projected arc has to do).
-    double xb = x;          // base point of the solve: x with the coordinates dropped so far at zero
-    bool banned = false;    // this position was dropped: it stays at zero and out of F
-    double m_old = 0.0;     // model value at x (relative to the expansion point)
-    double d_first = 0.0, t_first = 2.0;  // first solve: direction and the step to the first sign change from x
-    bool ok_first = true, tiny_first = false;
-    double pg_first = 0.0;
-    int m = 0, T = 0, mp = 0, my_rank = -1;
-    double dk = 0.0, xi = 1.0;
-    unsigned long long tk = wall_clock64();
-    auto lap = [&](int slot) {
-      if (tid == 0) {
-        const unsigned long long now = wall_clock64();
-        ws->nt_ticks[lane_id][slot] += now - tk;
-        tk = now;
-      }
-    };
-    for (int resolve = 0; resolve < resolve_cap; ++resolve) {
-      lap(4);
-      const double gdb = matvec(xb, false);  // G (xb - z0)
-      const double gx = g0 + gdb;            // model gradient at xb
-      if (resolve == 0) {
-        double sv[2] = {mine ? (x - z0) * (g0 + 0.5 * gdb) : 0.0, 0.0};
-        sv[1] = pen_part(x);
-        block_sum<2>(sv, red);
-        m_old = sv[0] + sv[1];
-      }
-      double pg;  // pseudo-gradient of this position at xb; xi: the orthant it may move in
-      if (xb != 0.0) {
-        xi = xb > 0.0 ? 1.0 : -1.0;
-        pg = gx + thr * xi + pd * xb;
-      } else {
-        pg = fabs(gx) > thr * (1.0 + 1e-12) ? gx - copysign(thr, gx) : 0.0;
-        xi = pg > 0.0 ? -1.0 : 1.0;
-      }
-      // of the zero coordinates that want to leave zero only the strongest enter now (within WS_NEWTON_ENTER of
-      // the largest violation): on correlated designs most violators stop violating once a few of them have
-      // moved, and a free set full of them solves for a direction that means nothing
-      const double viol = (live && !banned && xb == 0.0) ? fabs(pg) : 0.0;
-      const double viol_max = -block_min(-viol);
-      const bool is_free = live && !banned && (xb != 0.0 || (viol > 0.0 && viol >= WS_NEWTON_ENTER * viol_max));
-      // free positions in position order
-      __syncthreads();
-      if (q == 0 && k < WS_KCAP) {
-        nv[k] = is_free ? 1.0 : 0.0;
-        rank_of[k] = -1;
-      }
-      __syncthreads();
-      if (tid < 64) {
-        int basep = 0;
-        for (int c0 = 0; c0 < K; c0 += 64) {
-          const int kk = c0 + tid;
-          const bool on = kk < K && nv[kk] != 0.0;
-          const uint64_t mk = __ballot(on);
-          if (on) {
-            const int ii = basep + __popcll(mk & ((1ull << tid) - 1ull));
-            act[ii] = kk;
-            rank_of[kk] = ii;
-          }
-          basep += __popcll(mk);
-        }
-        if (tid == 0) m_s = basep;
-      }
-      __syncthreads();
-      m = m_s;
-      if (m == 0) {
-        if (resolve == 0) return 0;
-        dk = 0.0;
-        my_rank = -1;
-        break;  // everything was dropped: the base point itself is the candidate
-      }
-      T = (m + 15) >> 4;
-      mp = 16 * T;
-      my_rank = (k < K) ? rank_of[k] : -1;
-      __syncthreads();
-      if (tid < mp) nv[tid] = 0.0;
-      if (q == 0 && k < WS_KCAP) delta[k] = pd;  // (matvec is done with delta: it now carries the ridge diagonal)
-      __syncthreads();
-      if (q == 0 && my_rank >= 0) nv[my_rank] = pg;
-      lap(0);
-      // H_FF, tile by tile (G is symmetric: read along rows)
-      const int ntl = T * (T + 1) / 2;
-      for (int e = tid; e < ntl * 256; e += WS_THREADS) {
-        const int tl = e >> 8, wi = e & 255;
-        int I = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-        while (I * (I + 1) / 2 > tl) --I;
-        while ((I + 1) * (I + 2) / 2 <= tl) ++I;
-        const int J = tl - I * (I + 1) / 2;
-        const int l6 = wi & 63, st = wi >> 6;
-        const int ii = 16 * I + (l6 & 15), jj = 16 * J + (l6 >> 4) + 4 * st;
-        double hv;
-        if (ii < m && jj < m) {
-          const int pi = act[ii], pj = act[jj];
-          hv = Gm[pj * WS_KCAP + pi];
-          if (ii == jj) hv += delta[pi];
-        } else {
-          hv = ii == jj ? 1.0 : 0.0;
-        }
-        ntF[e] = hv;
-      }
-      __syncthreads();
-      lap(1);
-      if (!nt_factor(ntF, ntD, T, 1e-12 * Lmax, nts)) {
-        if (tid == 0) atomicAdd(&ws->newton_nopd, 1);
-        return -1;
-      }
-      lap(2);
-      nt_solve(ntF, ntD, T, nv);  // nv = H_FF^-1 pg
-      lap(3);
-      if (tid == 0) {
-        atomicAdd(&ws->newton_factors, 1);
-        ws->nt_factors[lane_id] += 1;
-        atomicAdd(&ws->newton_unknowns, m);
-      }
-      dk = my_rank >= 0 ? nv[my_rank] : 0.0;
-      if (resolve == 0) {
-        ok_first = my_rank >= 0 && (x != 0.0 || dk * pg > 0.0);
-        d_first = ok_first ? dk : 0.0;  // (a zero coordinate the first solve sent the wrong way stays where it is)
-        pg_first = pg;
-        // a coordinate the solve carries across zero ends the straight segment -- unless it sits so close to
-        // zero (the dust a prox-gradient step leaves on every violator) that the segment would have no
-        // length: those go to zero outright and take no part in the direction
-        tiny_first = my_rank >= 0 && x != 0.0 && x * dk > 0.0 && fabs(x) < 1e-6 * fabs(dk);
-        if (tiny_first) d_first = 0.0;
-        else if (my_rank >= 0 && x != 0.0 && x * dk > 0.0 && fabs(dk) >= fabs(x)) t_first = x / dk;
-      }
-      // zero coordinates the solve would move to the wrong side (or not at all), non-zero ones it would carry
-      // across zero
-      const bool wrong = my_rank >= 0 && (xb == 0.0 ? !(dk * pg > 0.0) : (xb - dk) * xi <= 0.0);
-      double cnt[1] = {mine && wrong ? 1.0 : 0.0};
-      block_sum<1>(cnt, red);
-      if (cnt[0] == 0.0 || resolve == resolve_cap - 1) break;
-      if (wrong) {
-        banned = true;
-        xb = 0.0;
-      }
-    }
-    t_first = fmin(1.0, block_min(t_first));
-    {
-      // the model along x - t d_first, 0 <= t <= t_first (no coordinate changes sign there), is the parabola
-      // m_old - t <pg, d> + t^2/2 <d, H d>: with the wrong-way coordinates held back d is not the Newton direction
-      // of what moves, so the full segment need not descend -- its minimiser does
-      const double gd = matvec(z0 + d_first, false);  // G d_first
-      double sv[2] = {0.0, 0.0};
-      if (mine) {
-        sv[0] = pg_first * d_first;
-        sv[1] = d_first * (gd + pd * d_first);
-      }
-      block_sum<2>(sv, red);
-      if (tid == 0) {
-        if (!(t_first > 1e-14)) atomicAdd(&ws->newton_ref[0], 1);
-        else if (!(sv[0] > 0.0)) atomicAdd(&ws->newton_ref[1], 1);
-        else if (!(sv[1] > 0.0)) atomicAdd(&ws->newton_ref[2], 1);
-      }
-      t_first = (sv[0] > 0.0 && sv[1] > 0.0) ? fmin(t_first, sv[0] / sv[1]) : 0.0;
-    }
-    // trial points: the base point minus the (projected) step at t = 1, 1/2, 1/4, then -- from x itself, along
-    // the first solve -- the straight segment up to the first sign change (a guaranteed descent step: nothing
-    // is projected on it)
-    double xn = x;
-    bool moved = false, projected = false, full = false;
-    for (int trial = 0; trial < 4 && !moved; ++trial) {
-      if (trial == 3 && !(t_first > 1e-14)) break;
-      double xc, cut = 0.0;
-      if (trial < 3) {
-        const double tt = trial == 0 ? 1.0 : (trial == 1 ? 0.5 : 0.25);
-        xc = xb;
-        if (my_rank >= 0) {
-          xc = xb - tt * dk;
-          if (xc * xi <= 0.0) {  // left the orthant (or landed on its boundary): stops at zero
-            if (xb != 0.0 || xc != 0.0) cut = 1.0;
-            xc = 0.0;
-          }
-        }
-      } else {
-        xc = x - t_first * d_first;
-        if (tiny_first || (x != 0.0 && xc * x <= 0.0)) xc = 0.0;  // the coordinate that reaches zero there
-        cut = 1.0;
-      }
-      const double gdn = matvec(xc, false);
-      double sv[4] = {0.0, 0.0, 0.0, 0.0};
-      if (mine) {
-        sv[0] = (xc - z0) * (g0 + 0.5 * gdn);
-        sv[2] = cut;
-        if (!isfinite(xc)) sv[3] = 1.0;
-      }
-      sv[1] = pen_part(xc);
-      block_sum<4>(sv, red);
-      if (sv[3] == 0.0 && sv[0] + sv[1] < m_old) {
-        moved = true;
-        projected = sv[2] > 0.0;
-        full = trial == 0;
-        xn = xc;
-        if (tid == 0) atomicAdd(&ws->newton_trial[trial], 1);
-        // dropping every inconsistent coordinate at once did not settle the free set and the step fell back
-        // to the segment: on this face (strong cancellations) the following steps go there directly
-        if (trial == 3) resolve_cap = 1;
-      }
-    }
-    lap(4);
-    if (!moved && tid == 0 && t_first > 1e-14) atomicAdd(&ws->newton_ref[3], 1);
-    if (!moved) return -1;
-    if (want_mu && full && !projected && m > 0) {  // H_FF is the Hessian on the face of the new point: its
-      __syncthreads();                                      // smallest eigenvalue, two inverse-iteration steps
-      *mu_out = nt_lambda_min(ntF, ntD, T, mp, nv, red, 2); // from the step itself
-      lap(5);
-    }
-    x = xn;
-    return 1;
-   }
-  };
-
-  // ---- direct step with group norms (GroupLasso, SparseGroupLasso, ridged; round 2) ----------------------
-  // On the face of the iterate -- its active groups, inside them the non-zero coordinates with their signs when
-  // there is an l1 term -- the objective is smooth but no longer quadratic: the norm of an active group adds the
-  // curvature (b_g / r_g)(I - u u^T), r_g = ||x_g||, u = x_g / r_g.  One call is one damped Newton step there:
-  // H = G_FF + d + those blocks, d = H^-1 (gradient of the smooth face objective), trial points x - t d for
-  // t = 1, 1/2, 1/4, 1/8 with the same projections as above (a coordinate with an l1 kink stops at zero; a group the
-  // step would carry through the origin goes to zero as a whole), the first that lowers model + penalty wins.
-  // Groups that are zero but want in (||soft(g_g, a)|| > b_g, the strongest violators only) first receive their
-  // prox-gradient value -- the penalty has no gradient at a zero group -- and join the face.  The free set is made
-  // consistent by dropping what the solve sends the wrong way, as in the l1 case.
-  auto group_sum = [&](double val) -> double {  // sum of `val` over the members of this position's group
-    __syncthreads();
-    if (q == 0 && k < WS_KCAP) uim[k] = (k < K && live) ? val : 0.0;
-    __syncthreads();
-    double ss = 0.0;
-    if (live)
-      for (int m2 = 0; m2 < glk; ++m2) ss += uim[gsk + m2];
-    return ss;
-  };
-  auto direct_step_group = [&](double& x, double Lmax, double* mu_out, bool want_mu) -> int {
-   if constexpr (!GROUPED) {
-    return 0;  // (this instance uses direct_step)
-   } else {
-    *mu_out = 0.0;
-    const bool kink = pa > 0.0;  // this coordinate has an l1 term: its sign is part of the face
-    double xb = x;
-    bool banned = false;
-    double m_old = 0.0;
-    int m = 0, T = 0, mp = 0, my_rank = -1;
-    double dk = 0.0, xi = 0.0;
-    for (int resolve = 0; resolve < resolve_cap; ++resolve) {
-      double gx = g0 + matvec(xb, false);
-      if (resolve == 0) {
-        double sv[2] = {mine ? (x - z0) * (g0 + 0.5 * (gx - g0)) : 0.0, 0.0};
-        sv[1] = pen_part(x);
-        block_sum<2>(sv, red);
-        m_old = sv[0] + sv[1];
-      }
-      double r2 = group_sum(xb * xb);
-      bool g_active = r2 > 0.0;
-      const double sk = (live && !banned && !g_active) ? soft(gx, pa) : 0.0;
-      const double S = sqrt(group_sum(sk * sk));
-      double viol = 0.0;
-      if (live && !banned) {
-        if (!g_active) viol = fmax(0.0, S - pb);
-        else if (xb == 0.0 && kink) viol = fmax(0.0, fabs(gx) - pa);
-      }
-      const double viol_max = -block_min(-viol);
-      if (resolve == 0 && viol_max > 0.0) {
-        const bool enter = live && !banned && !g_active && viol > 0.0 && viol >= WS_NEWTON_ENTER * viol_max;
-        double cnt[1] = {mine && enter ? 1.0 : 0.0};
-        block_sum<1>(cnt, red);
-        if (cnt[0] > 0.0) {  // (uniform: every thread takes the same branch)
-          if (enter) {
-            const double st = 1.0 / Lmax;
-            xb = -st * sk * (1.0 - pb / S) / (1.0 + st * pd);
-          }
-          gx = g0 + matvec(xb, false);
-          r2 = group_sum(xb * xb);
-          g_active = r2 > 0.0;
-        }
-      }
-      const double rg = sqrt(r2);
-      double pg = 0.0;
-      bool is_free = false;
-      xi = 0.0;
-      if (live && !banned && g_active) {
-        if (xb != 0.0) {
-          xi = kink ? (xb > 0.0 ? 1.0 : -1.0) : 0.0;
-          pg = gx + pa * (xb > 0.0 ? 1.0 : -1.0) + (pb / rg + pd) * xb;
-          is_free = true;
-        } else if (!kink) {
-          pg = gx;  // no l1 term: the objective is smooth in this coordinate at zero
-          is_free = gx != 0.0;
-        } else {
-          const double e = fabs(gx) - pa;
-          if (e > 0.0 && e >= WS_NEWTON_ENTER * viol_max) {
-            pg = gx - copysign(pa, gx);
-            xi = pg > 0.0 ? -1.0 : 1.0;
-            is_free = true;
-          }
-        }
-      }
-      // free positions in position order
-      __syncthreads();
-      if (q == 0 && k < WS_KCAP) {
-        nv[k] = is_free ? 1.0 : 0.0;
-        rank_of[k] = -1;
-      }
-      __syncthreads();
-      if (tid < 64) {
-        int basep = 0;
-        for (int c0 = 0; c0 < K; c0 += 64) {
-          const int kk = c0 + tid;
-          const bool on = kk < K && nv[kk] != 0.0;
-          const uint64_t mk = __ballot(on);
-          if (on) {
-            const int ii = basep + __popcll(mk & ((1ull << tid) - 1ull));
-            act[ii] = kk;
-            rank_of[kk] = ii;
-          }
-          basep += __popcll(mk);
-        }
-        if (tid == 0) m_s = basep;
-      }
-      __syncthreads();
-      m = m_s;
-      if (m == 0) {
-        if (resolve == 0) return 0;
-        dk = 0.0;
-        my_rank = -1;
-        break;
-      }
-      T = (m + 15) >> 4;
-      mp = 16 * T;
-      my_rank = (k < K) ? rank_of[k] : -1;
-      __syncthreads();
-      if (tid < mp) nv[tid] = 0.0;
-      if (q == 0 && k < WS_KCAP) {
-        delta[k] = pd;
-        xsl[k] = (k < K && live) ? xb : 0.0;
-        rgl[k] = rg;
-        pbl[k] = pb;
-        nz[k] = gsk;  // (group id; the mat-vec rebuilds its own list when it next runs)
-      }
-      __syncthreads();
-      if (q == 0 && my_rank >= 0) nv[my_rank] = pg;
-      const int ntl = T * (T + 1) / 2;
-      for (int e = tid; e < ntl * 256; e += WS_THREADS) {
-        const int tl = e >> 8, wi = e & 255;
-        int I = (int)((sqrtf(8.0f * (float)tl + 1.0f) - 1.0f) * 0.5f);
-        while (I * (I + 1) / 2 > tl) --I;
-        while ((I + 1) * (I + 2) / 2 <= tl) ++I;
-        const int J = tl - I * (I + 1) / 2;
-        const int l6 = wi & 63, st = wi >> 6;
-        const int ii = 16 * I + (l6 & 15), jj2 = 16 * J + (l6 >> 4) + 4 * st;
-        double hv;
-        if (ii < m && jj2 < m) {
-          const int pi = act[ii], pj = act[jj2];
-          hv = Gm[pj * WS_KCAP + pi];
-          if (ii == jj2) hv += delta[pi];
-          if (nz[pi] == nz[pj]) {  // same group: curvature of its norm
-            const double rr = rgl[pi];
-            hv += (pbl[pi] / rr) * ((ii == jj2 ? 1.0 : 0.0) - xsl[pi] * xsl[pj] / (rr * rr));
-          }
-        } else {
-          hv = ii == jj2 ? 1.0 : 0.0;
-        }
-        ntF[e] = hv;
-      }
-      __syncthreads();
-      if (!nt_factor(ntF, ntD, T, 1e-12 * Lmax, nts)) {
-        if (tid == 0) atomicAdd(&ws->newton_nopd, 1);
-        return -1;
-      }
-      nt_solve(ntF, ntD, T, nv);
-      if (tid == 0) {
-        atomicAdd(&ws->newton_factors, 1);
-        atomicAdd(&ws->newton_unknowns, m);
-        ws->nt_factors[lane_id] += 1;
-      }
-      dk = my_rank >= 0 ? nv[my_rank] : 0.0;
-      // what the solve sends the wrong way: a kinked coordinate across (or to the wrong side of) zero, a whole
-      // group through the origin
-      bool wrong = false;
-      if (my_rank >= 0 && kink) wrong = xb == 0.0 ? !(dk * pg > 0.0) : (xb - dk) * xi <= 0.0;
-      const double radial = group_sum(live && !banned ? (xb - dk) * xb : 0.0);
-      const bool g_wrong = live && !banned && g_active && !(radial > 0.0);
-      double cnt[1] = {mine && (wrong || g_wrong) ? 1.0 : 0.0};
-      block_sum<1>(cnt, red);
-      if (cnt[0] == 0.0 || resolve == resolve_cap - 1) break;
-      if (wrong || g_wrong) {
-        banned = true;
-        xb = 0.0;
-      }
-    }
-    double xn = x;
-    bool moved = false, projected = false, full = false;
-    double tt = 1.0;
-    for (int trial = 0; trial < 4 && !moved; ++trial, tt *= 0.5) {
-      double xc = xb, cut = 0.0;
-      if (my_rank >= 0) {
-        xc = xb - tt * dk;
-        if (kink && xc * xi <= 0.0) {
-          if (xb != 0.0 || xc != 0.0) cut = 1.0;
-          xc = 0.0;
-        }
-      }
-      const double radial = group_sum(live ? xc * xb : 0.0);
-      const double r2b = group_sum(xb * xb);
-      if (live && r2b > 0.0 && !(radial > 0.0)) {  // the group would pass through the origin: it goes to zero
-        if (xc != 0.0) cut = 1.0;
-        xc = 0.0;
-      }
-      const double gdn = matvec(xc, false);
-      double sv[4] = {0.0, 0.0, 0.0, 0.0};
-      if (mine) {
-        sv[0] = (xc - z0) * (g0 + 0.5 * gdn);
-        sv[2] = cut;
-        if (!isfinite(xc)) sv[3] = 1.0;
-      }
-      sv[1] = pen_part(xc);
-      block_sum<4>(sv, red);
-      if (sv[3] == 0.0 && sv[0] + sv[1] < m_old) {
-        moved = true;
-        projected = sv[2] > 0.0;
-        full = trial == 0;
-        xn = xc;
-        if (tid == 0) atomicAdd(&ws->newton_trial[trial < 3 ? trial : 2], 1);
-      }
-    }
-    if (!moved) return -1;
-    if (want_mu && full && !projected && m > 0) {
-      __syncthreads();
-      *mu_out = nt_lambda_min(ntF, ntD, T, mp, nv, red, 2);
-    }
-    x = xn;
-    return 1;
-   }
-  };
-
-  mark(1);
-  // ---- FISTA on the model ------------------------------------------------------------------------
-  double L = Lw;
-  double Ls = L;  // curvature the next step is taken with (L, or less while the steps are spectral)
-  double x = x_start, v = x_start, t = 1.0;
-  double v_prev = 0.0, gv_prev = 0.0;
-  bool have_prev = false;
-  mark(2);
-  bool ok = true;
-  bool settled = false;  // the iteration met its own tolerance: its point minimises the model
-  int n_inner = 0;
-  // smallest Rayleigh quotient <dv, G dv> / <dv, dv> along the moves of the iteration: an upper estimate
-  // of the smallest eigenvalue on the face that closes in as the slow modes come to dominate the moves
-  double rq_min = 0.0;
-  int rq_n = 0;
-  double mu_face = 0.0;       // from the factor of a direct step (0: none taken)
-  int since_direct = 0, n_direct = 0, n_direct_bad = 0;
-  bool direct_on = newton_capable;
-  // direct mode: the iterate only moves by direct steps; the prox-gradient step of every round is just the
-  // convergence test (taken when it passes).  Taking it regardless would wreck the next direct step: from a
-  // face minimiser one prox-gradient step gives EVERY violator a tiny non-zero value, and a free set full of
-  // those solves for a direction that means nothing.  A solve starts in this mode when an earlier refinement of ITS LANE
-  // of this call needed direct steps (WsCtl::hard_lane).
-  bool direct_mode = direct_on && hard_now != 0;
-  // the length scale of the problem on W: a gradient step from the expansion point, ||g0_W|| / L (what "rounding level" is
-  // measured against where the iterate itself is zero or dust)
-  // (kept in LDS, not in a register across the loop: the kernel sits at the 128 registers of a 1 024-thread workgroup, and a
-  //  value more across the iteration was 12 bytes of scratch per thread)
-  {
-    double sg[1] = {mine ? g0 * g0 : 0.0};
-    ws_sum<1>(sg, red, nwc);
-    if (tid == 0) scale2_s = sg[0] / (Lw * Lw);
-    __syncthreads();
-  }
-#define scale2 scale2_s
-  // The first WS_BB_ITERS steps carry no momentum and take their length from the curvature along the move
-  // before: on the well-conditioned faces of an easy path that is there in half the steps of the accelerated
-  // iteration, which takes over if it is not.
-  bool spectral = !direct_mode && w.bb_steps != 0;
-  int it_end = WS_INNER_MAX;
-  for (int it = 0; it < it_end; ++it) {
-    ++n_inner;
-    const double gv = g0 + matvec(v, false);
-    const double u = prox_w(v - gv / Ls, 1.0 / Ls);
-    //  s[0] = ||u - v||^2  s[1] = ||u||^2  s[2] = (v - u).(u - x)  s[3] = #non-finite
-    //  s[4] = ||v - v_prev||^2  s[5] = ||gv - gv_prev||^2   (curvature along the last move of v)
-    //  s[6] = <v - v_prev, gv - gv_prev>
-    double s[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (mine) {
-      const double r = u - v;
-      s[0] = r * r;
-      s[1] = u * u;
-      s[2] = -r * (u - x);
-      if (!isfinite(u)) s[3] = 1.0;
-      if (have_prev) {
-        const double dv = v - v_prev, dg = gv - gv_prev;
-        s[4] = dv * dv;
-        s[5] = dg * dg;
-        s[6] = dv * dg;
-      }
-    }
-    ws_sum<7>(s, red, nwc);
-    if (s[3] > 0.0 || !isfinite(s[0])) {
-      ok = false;
-      break;
-    }
-    v_prev = v;
-    gv_prev = gv;
-    have_prev = true;
-    if (s[4] > 1e-20 * fmax(s[1], scale2) && s[4] > 0.0) {  // (a move at the rounding level measures nothing)
-      const double rq = s[6] / s[4];
-      if (rq > 0.0 && (rq_n == 0 || rq < rq_min)) rq_min = rq;
-      rq_n += 1;
-    }
-    // (a move at the rounding level measures no curvature either -- and "rounding level" has to be told on the scale of
-    //  the PROBLEM, not of the iterate: the point at alpha_max solves to rounding dust (|g_j| - alpha = 1e-16 for the
-    //  first feature), its moves are dust against dust, ||dg|| / ||dv|| of one of them sent L from 1.7 to 44 -- through
-    //  WsCtl::Lw for every later refinement of the call, whose Rayleigh quotients then all "said" ill-conditioned: 170
-    //  direct steps of 200 unknowns on an iid design, 26 ms for an 8-pass path, soak seed 29)
-    const bool real_move = s[4] > 1e-20 * fmax(s[1], scale2) && s[4] > 0.0;
-    if (real_move && sqrt(s[5] / s[4]) > L) {  // the bound was too low
-      L = 1.05 * sqrt(s[5] / s[4]);
-      if (!spectral) {  // an accelerated step of 1/L was too long: redo it from x (a spectral step claims nothing of L)
-        Ls = L;
-        v = x;
-        t = 1.0;
-        continue;
-      }
-    }
-    if (spectral) {
-      // the next step is as long as the curvature along this move allows (Barzilai-Borwein, first form),
-      // never longer than WS_BB_MAX_STEP steps of 1/L
-      const double rq = s[4] > 1e-20 * s[1] ? s[6] / s[4] : L;
-      Ls = fmin(L, fmax(rq, L / WS_BB_MAX_STEP));
-      if (it + 1 >= WS_BB_ITERS) {  // not there in the steps such a face takes: momentum from here
-        spectral = false;
-        Ls = L;
-      }
-    }
-    // (a spectral step is longer than 1/L and moves at least as far from the same point: the test is the stricter for it)
-    // (... or the step is rounding noise on the problem's scale, the floor of fista_tail_kernel's stopping rule: a solution
-    //  that IS dust -- the path's first point -- has converged, it does not iterate thirty times and take a direct step)
-    const bool inner_conv = sqrt(s[0]) <= fmax(WS_INNER_TOL * tol * sqrt(s[1]), kRoundFloor * (sqrt(scale2) + sqrt(s[1])));
-    if (DIRECT && direct_mode && !inner_conv) {
-      bool stepped = false;
-      if (n_direct < WS_NEWTON_MAX) {
-        double mu_new = 0.0;
-        const int rc = group_face ? direct_step_group(x, L, &mu_new, mu_face == 0.0) : direct_step(x, L, &mu_new, mu_face == 0.0);
-        n_direct += 1;
-        if (rc > 0) {
-          if (mu_new > 0.0) mu_face = mu_new;
-          stepped = true;
-        } else if (rc < 0) {
-          n_direct_bad += 1;
-        }
-      }
-      if (stepped) {
-        v = x;
-        t = 1.0;
-        continue;
-      }
-      // no usable step from this point (e.g. the coordinates it had to hold back carried the descent): one
-      // prox-gradient step moves the iterate somewhere else and the next round tries again; after
-      // WS_NEWTON_REFUSALS of those, or at the cap, the iteration finishes the job
-      if (n_direct_bad >= WS_NEWTON_REFUSALS || n_direct >= WS_NEWTON_MAX) {
-        direct_mode = false;
-        direct_on = false;
-        since_direct = 0;
-        it_end = min(it_end, it + WS_AFTER_DIRECT);
-      }
-    }
-    const bool restart = s[2] > 0.0;
-    const double t_use = restart ? 1.0 : t;
-    const double t_new = 0.5 * (1.0 + sqrt(1.0 + 4.0 * t_use * t_use));
-    const double mom = spectral ? 0.0 : (t_use - 1.0) / t_new;
-    v = u + mom * (u - x);
-    x = u;
-    t = t_new;
-    if (inner_conv) {
-      settled = true;
-      break;
-    }
-    since_direct += 1;
-    if (direct_on && n_direct < WS_NEWTON_MAX &&
-        (since_direct >= WS_NEWTON_AFTER || (rq_n >= 5 && rq_min < WS_NEWTON_RQ * L))) {
-      if (!DIRECT) {  // (nothing of this solve has been written yet)
-        if (tid == 0) ws->want_full[lane_id] = 1;
-        return false;
-      }
-      double mu_new = 0.0;
-      const int rc = group_face ? direct_step_group(x, L, &mu_new, mu_face == 0.0) : direct_step(x, L, &mu_new, mu_face == 0.0);
-      since_direct = 0;
-      n_direct += 1;
-      if (rc > 0) {
-        if (mu_new > 0.0) mu_face = mu_new;
-        v = x;
-        t = 1.0;
-        direct_mode = true;
-      } else if (rc < 0) {
-        n_direct_bad += 1;
-        if (n_direct_bad >= WS_NEWTON_REFUSALS) {  // singular face / useless steps: the iteration finishes the job
-          direct_on = false;
-          if (n_direct > n_direct_bad) it_end = min(it_end, it + WS_AFTER_DIRECT);
-        }
-      }
-    }
-  }
-#undef scale2
-  mark(3);
-  if (!ok) return true;
-  // An iteration that ran out of steps is accepted only if the model says its point is no worse than the start (two
-  // products with the Gram, 14 us per call).  Not spent on a point that met the tolerance -- a minimiser of the model is
-  // no worse than anything -- unless the START already met it (one iteration): that point is one proximal step from
-  // where the lane stood, now and then a hair worse, and taking it resets the lane's step history for nothing.  On
-  // paths whose ends outgrow the working set such solves are common (a fifth to a half of all) and accepting them
-  // unseen cost 4-6 passes of 24-58 (tools/headline_soak.py); the headline path has none.
-  if (!settled || n_inner == 1) {
-    double m_start;  // model values relative to the expansion point
-    {
-      const double gd = matvec(x_start, false);
-      const double d = x_start - z0;
-      double s[2] = {mine ? d * (g0 + 0.5 * gd) : 0.0, 0.0};
-      s[1] = pen_part(x_start);
-      ws_sum<2>(s, red, nwc);
-      m_start = s[0] + s[1];
-    }
-    const double gd = matvec(x, false);
-    const double d = x - z0;
-    double s[3] = {mine ? d * (g0 + 0.5 * gd) : 0.0, 0.0, mine && !isfinite(x) ? 1.0 : 0.0};
-    s[1] = pen_part(x);
-    ws_sum<3>(s, red, nwc);
-    const double m_end = s[0] + s[1];
-    if (s[2] > 0.0 || !(m_end <= m_start)) return true;
-  }
-  // the refined point: model minimiser on W, the expansion point elsewhere (eight features per round: their loads
-  // go out together -- one feature at a time every load waited for the one before it, 11 us per call)
-  for (int f0 = tid; f0 < p; f0 += 8 * WS_THREADS) {
-    int ps[8];
-    double zo[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int f = f0 + u * WS_THREADS;
-      const int ff = f < p ? f : 0;
-      ps[u] = f < p ? w.pos[ff] : 0;
-      zo[u] = a.zprev[ff];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int f = f0 + u * WS_THREADS;
-      if (f < p && ps[u] < 0) {
-        a.z[f] = zo[u];
-        if (mode == 0) a.beta[f] = zo[u];
-      }
-    }
-  }
-  if (mine) {
-    a.z[jj] = x;
-    if (mode == 0) a.beta[jj] = x;
-  }
-  if (tid == 0) {
-    if (mode == 1) ctl->have_base = 0;  // the refined point becomes the base of the spectral scheme
-    else ctl->t = 1.0;
-    ctl->zzero = 0;
-    ws->last_point[lane_id] = point_now;
-    ws->served[lane_id] = 1;
-    ws->repeats[lane_id] = reps + 1;
-    ws->last_cols[lane_id] = ws->Kreal;
-    // (the lanes of a set end within microseconds of each other: read-compare-write let the smaller of two bounds
-    // land last now and then, and the next pass started from a different L -- positive doubles order as integers)
-    if (L > 0.0) atomicMax(reinterpret_cast<unsigned long long*>(&ws->Lw[set]), (unsigned long long)__double_as_longlong(L));
-    atomicAdd(&ws->refined, 1);
-    atomicAdd(&ws->inner_iters, n_inner);
-    atomicAdd(&ws->iters_hist[n_inner < 31 ? n_inner : 31], 1);
-    if (n_direct) atomicAdd(&ws->newton_steps, n_direct - n_direct_bad);
-    if (n_direct > n_direct_bad) {
-      ws->hard_next = 1;  // (same value from every lane: the order of the stores is immaterial)
-      ws->hard_lane[lane_id] = 1;
-    }
-    if (n_direct_bad) atomicAdd(&ws->newton_fails, n_direct_bad);
-    // strong convexity on the face of the refined point, for the stopping rule of the pass that verifies it
-    // (fista_tail_kernel): from the factor when a direct step stood, else from the iteration's own moves
-    // (halved: both are estimates from above); 0 = unknown.
-    ctl->mu = mu_face > 0.0 ? 0.5 * mu_face : (rq_n >= 3 ? 0.5 * rq_min : 0.0);
-  }
-  mark(4);
-  return true;
-}
-
-// MODE 0: the iteration alone (lanes that would take a direct step are left, untouched, with WsCtl::want_full set);
-// MODE 1: the solver with direct steps, for the lanes MODE 0 left -- a launch of its own behind it.  (Round 6 tried both in
-// one launch: the idle second launch is 4.8 us of the chain between two passes, but the light instance compiled into one
-// kernel with the factorisation was no faster for per-feature penalties and 0.35 ms per pass slower for grouped ones --
-// its registers went to scratch memory; tools/ab_knobs.py, profiles/r06_fusion_ab.txt.)
-template <bool GROUPED, int MODE>
-__global__ __launch_bounds__(WS_THREADS) void ws_solve_kernel(TailArgs a, WsArgs w) {
-  __shared__ double red[8][TAIL_WAVES];
-  __shared__ WsSolveLds sh;
-  const int lane_id = blockIdx.x;
-  PathCtl* ctl = a.ctl + lane_id;
-  if (ctl->done != 0 || ctl->idle != 0 || a.gdone[0] != 0) return;
-  const unsigned long long tk_in = wall_clock64();
-  if (MODE == 1) {  // only the lanes the light kernel left
-    const int mine = w.ws->want_full[lane_id] | w.one_solver;
-    __syncthreads();
-    if (!mine) return;
-    if (threadIdx.x == 0) w.ws->want_full[lane_id] = 0;
-  }
-  // (every return inside is taken by the whole workgroup)
-  if (MODE == 0) {
-    if (!ws_refine_lane<GROUPED, false>(a, w, red, sh)) return;
-  } else {
-    (void)ws_refine_lane<GROUPED, true>(a, w, red, sh);
-  }
-  __syncthreads();
-  // Is the point the next pass evaluates zero outside W?  Then its residual needs only the gathered
-  // columns (resid_ws_kernel) and the pass over X is the accumulate-only xtr_ring_kernel.
-  const WsCtl* ws = w.ws;
-  const bool w_ok = ws->valid && !ws->building && !ws->disabled;
-  double out[1] = {0.0};
-  if (w_ok) {
-    const double* z = a.z + (int64_t)lane_id * a.ld;
-    for (int j0 = threadIdx.x; j0 < a.p; j0 += 8 * WS_THREADS) {
-      int ps[8];
-      double zj[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int j = j0 + u * WS_THREADS;
-        const int jj = j < a.p ? j : 0;
-        ps[u] = j < a.p ? w.pos[jj] : 0;
-        zj[u] = z[jj];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (ps[u] < 0 && zj[u] != 0.0) out[0] += 1.0;
-    }
-  }
-  block_sum<1>(out, red);
-  if (threadIdx.x == 0) {
-    ctl->zsup = (w_ok && out[0] == 0.0) ? 1 : 0;
-    w.ws->lane_ticks[lane_id] += wall_clock64() - tk_in;
   }
 }
 

@@ -1,5 +1,5 @@
 """The direct (Cholesky) step of the working-set model solver and the KKT-based stopping rule
-(sparse-lm_amd/csrc/newton_kernels.hpp, ws_kernels.hpp `direct_step`, tail_kernels.hpp stopping rule).
+(sparse-lm_amd/csrc/newton_kernels.hpp, ws_solve_kernels.hpp `ws_direct_step`, tail_kernels.hpp stopping rule).
 
 The minimiser the reference returns (cvxpy's interior-point solve, src/sparselm/model/_base.py:512-519) does
 not depend on the conditioning of X; a proximal-gradient stop on the step length does.  These tests pin the
@@ -207,7 +207,7 @@ def test_group_penalties_on_correlated_designs_take_newton_steps(eng, design, ki
 
 def test_lanes_left_to_the_solver_with_direct_steps_give_what_one_kernel_gives(eng, monkeypatch):
     """The model solver is two launches: the iteration alone, then -- for the lanes that would take a direct step --
-    the instance that carries them, which starts those solves over (ws_kernels.hpp, `ws_refine_lane<GROUPED, DIRECT>`).
+    the instance that carries them, which starts those solves over (ws_solve_kernels.hpp, `ws_refine_lane<GROUPED, DIRECT>`).
     Nothing of an abandoned solve may leak: every lane on the second instance (SLM_WS_ONE_SOLVER=1) gives the same bits,
     and so does a second run."""
     rng = np.random.default_rng(11)

@@ -263,6 +263,52 @@ def test_start_hard(eng, kind, cond):
     _check_one(c, oh, tag=f"hard {kind} {cond}")
 
 
+# kind, positions, preset direct mode -- each the smallest case of one regime of a direct step (faces of 5, 32, 105, 51 and
+# 148 non-zeros at the minimiser):
+REGIMES = [("lasso", 16, True),           # a face of one 16-tile; hard presets direct mode, so a direct step is certain
+           ("lasso", 100, False),         # K = 112, the largest Gram held in LDS; two tiles
+           ("lasso", 300, False),         # K = 304: two threads per position, Gram through L2
+           ("sparse_group", 84, False),   # the l1 kink inside active groups
+           ("sparse_group", 300, False)]  # the same with two threads per position and the 200-member group
+REGIMES_UNSETTLED = REGIMES[4:]  # (measured: 4 direct steps, 39 factorisations, 57 iterations, model_kkt 1.5e-3 against a bound
+                                 #  of 1.6e-8 -- the solve uses up its refusals and ends unsettled; test_regime_that_does_not_settle)
+
+
+def _regime_case(kind, k):
+    sizes = None if kind == "lasso" else GROUP_SIZES[:5] + [40] if k == 84 else GROUP_SIZES[:6] + [56]
+    return make_case(k, 700, 500, cond=1e6, tol=1e-8, strength=0.05, least_squares=True, penalty=kind, group_sizes=sizes)
+
+
+def _regime_solve(eng, kind, k, hard, monkeypatch):
+    """The solve of one regime, with what holds whether or not it settles: direct steps were taken, and the two launches and
+    the one solver give the same bits."""
+    c = _regime_case(kind, k)
+    if kind == "sparse_group":
+        assert c.point[0] > 0.0 and c.point[1] > 0.0  # (an l1 term AND a group term)
+    o = _solve(eng, [c], direct=True, hard=hard)
+    print(f"regime {kind} {k}: inner {o.inner_iters} newton {o.newton_steps} factors {o.newton_factors} unknowns {o.newton_unknowns} "
+          f"nnz {np.count_nonzero(o.z[0][c.cols])}")
+    if hard:  # (test_start_hard's)
+        assert o.want_full[0] == 0 and o.newton_factors > 0
+    else:  # (test_direct_steps')
+        assert o.newton_steps > 0 and o.hard_lane[0] == 1
+        monkeypatch.setenv("SLM_WS_ONE_SOLVER", "1")
+        o1 = _solve(eng, [c], direct=True)
+        assert o1.kernels in ("ws_solve_kernel<false,1>", "ws_solve_kernel<true,1>")
+        assert np.array_equal(o1.z, o.z) and np.array_equal(o1.beta, o.beta, equal_nan=True) and o1.mu[0] == o.mu[0]
+        monkeypatch.delenv("SLM_WS_ONE_SOLVER")
+    return c, o
+
+
+@pytest.mark.parametrize("kind,k,hard", REGIMES[:4])
+def test_direct_steps_by_regime(eng, kind, k, hard, monkeypatch):
+    c, o = _regime_solve(eng, kind, k, hard, monkeypatch)
+    fig = _check_one(c, o, tag=f"regime {kind} {k}")
+    if not hard:
+        assert o.mu[0] > 0.0
+        assert 0.5 * fig["lam_min"] * (1.0 - 1e-9) <= o.mu[0] <= 0.5 * fig["lam_max"]
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # may not settle: the monotone rule and the write-back contract only
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -270,6 +316,16 @@ def _check_monotone(c, o, tag):
     bad = judge_monotone(c.mdl, c.cols, c.zprev, c.z_start, c.mode, o.z[0], o.beta[0], int(o.served[0]))
     print(f"{tag}: served {o.served[0]} inner {o.inner_iters} newton {o.newton_steps} nopd {o.newton_nopd}")
     assert bad == [], bad
+
+
+@pytest.mark.parametrize("kind,k,hard", REGIMES_UNSETTLED)
+def test_regime_that_does_not_settle(eng, kind, k, hard, monkeypatch):
+    """The l1 kink inside active groups with two threads per position and the 200-member group: the solve takes direct steps
+    and ends unsettled (REGIMES_UNSETTLED), so what it returns is judged by the monotone rule, as _hard_case describes for the
+    freely drawn gradient."""
+    c, o = _regime_solve(eng, kind, k, hard, monkeypatch)
+    assert o.refined == 1
+    _check_monotone(c, o, f"regime {kind} {k}")
 
 
 @pytest.mark.parametrize("cond", [1e6, 1e8])
