@@ -636,6 +636,35 @@ int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, double big_M, 
                     int64_t* nodes_out, slm_point_info* info);
 
 /*
+ * (added under ABI 24: a new symbol beside slm_solve_l0, no existing entry, structure or constant changes, so the version
+ * stays 24 -- a caller that needs it looks the symbol up.)  The exact l0 PROFILE: one search (csrc/l0_kernels.hpp, template
+ * parameter PROFILE) returns, for every size k = 0 .. max_groups, the best admissible support of exactly k groups for
+ *       q(S) = min over beta, supp beta in cols(S), |beta_j| <= big_M, of  1/2 beta^T (G + 2 eta T) beta - c^T beta
+ * (G, c, T, need as for slm_solve_l0).  q(S) depends on neither alpha nor the bound, so with Q_k = value_out[k] the table
+ * answers best subset for every bound K' <= max_groups (min over k <= K' of Q_k) and RegularizedL0 / L2L0 for every
+ * alpha >= alpha_min (min over k of Q_k + alpha k).  alpha_min > 0 prunes: below a node of cnt groups nothing is searched when
+ * q_all + alpha_min (cnt + 1) >= min(0, min over k <= cnt of Q_k + alpha_min k), which no support strictly better at any
+ * alpha >= alpha_min can lie behind -- the table then serves those alphas only, and its entries need not be the best of
+ * their size.  The table is complete only for alpha_min = 0; the search then visits about as many nodes as there are
+ * admissible supports of at most max_groups groups (meant for up to ~30 groups, or a small max_groups).
+ * Outputs, max_groups + 1 entries each (a negative max_groups counts as 0): beta_out [(max_groups + 1) * p], row k the
+ * coefficients of size k, recomputed once on the host from the Gram on its support; support_out[k]: bit i = group i active;
+ * value_out[k] = Q_k.  Entry 0 is the empty support (value 0).  An entry nobody filled -- a size above the group count, one the
+ * hierarchy admits no support of, one the pruning never reached -- holds +inf, an all-ones mask and zero coefficients.
+ * *nodes_out: group inclusions tried.  info->n_iter = launches (1), info->L = q_all, info->mode = 4, info->kkt = the
+ * regularised optimum at alpha_min, info->mu = the best-subset optimum at max_groups, info->status = SLM_OK or
+ * SLM_ERR_NOT_CONVERGED; info->loss is not set.  Limits and argument errors are slm_solve_l0's: up to 64 columns and 64 groups
+ * (SLM_ERR_UNSUPPORTED beyond, and on row-sharded datasets); negative or non-finite alpha_min / eta, negative big_M, a need
+ * bit at or beyond the group count: SLM_ERR_BAD_ARG before anything is launched; SLM_ERR_NOT_CONVERGED with the table of
+ * incumbents when the node budget ran out.  There is no l1 term here (L1L0's support value depends on its own eta) and no
+ * linear constraints.
+ */
+int slm_solve_l0_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T /* p*p or NULL */,
+                         double big_M, const uint64_t* need /* n_groups masks or NULL */, int64_t max_nodes /* <=0: default */,
+                         double* beta_out /* [(max_groups+1)*p] */, uint64_t* support_out /* [max_groups+1] */,
+                         double* value_out /* [max_groups+1] */, int64_t* nodes_out, slm_point_info* info);
+
+/*
  * The Gram of a row set, for covariance passes (SLM_FLAG_COVARIANCE): G = X^T W X / n_eff, c = X^T W y / n_eff and
  * y^T W y / n_eff, kept with the dataset (8 ld^2 bytes each) and found again by a fingerprint of the row weights and
  * n_eff -- what a lane of slm_solve_lanes brings as (row_weight, n_eff).  row_weight: length n on the host, NULL = the

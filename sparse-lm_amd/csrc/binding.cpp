@@ -353,6 +353,37 @@ py::tuple solve_l0_l1(uintptr_t ds, int64_t p, double alpha, double eta_l1, doub
   return py::make_tuple(beta, support, lower, nodes, info, rc);
 }
 
+// slm_solve_l0_profile: the best support of every size up to max_groups from one search.  Returns (coefficients
+// [max_groups + 1][p], support masks, values, nodes, record as bytes, status) -- status as for solve_l0.
+py::tuple solve_l0_profile(uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta, const py::object& T, double big_M,
+                           const py::object& need, int64_t max_nodes) {
+  if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
+  Keep keep;
+  const double* Tp = vector_arg(T, p * p, "T", keep);
+  const uint64_t* needp = nullptr;
+  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
+  if (!need.is_none()) {
+    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
+    if (!need_arr) throw py::value_error("need is not convertible to uint64");
+    needp = need_arr.data();
+  }
+  const py::ssize_t rows = (py::ssize_t)max_groups + 1;
+  py::array_t<double> beta({rows, (py::ssize_t)p});
+  py::array_t<uint64_t> support(rows);
+  py::array_t<double> value(rows);
+  py::array info = info_bytes(1);
+  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
+  int64_t nodes = 0;
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_profile(reinterpret_cast<slm_dataset*>(ds), alpha_min, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
+                              support.mutable_data(), value.mutable_data(), &nodes, static_cast<slm_point_info*>(info.mutable_data()));
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, support, value, nodes, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -369,6 +400,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("dataset_create", &dataset_create);
   m.def("solve_l0", &solve_l0);
   m.def("solve_l0_l1", &solve_l0_l1);
+  m.def("solve_l0_profile", &solve_l0_profile);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

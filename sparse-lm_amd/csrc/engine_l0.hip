@@ -5,6 +5,8 @@
 // recomputed in one place from the Gram on its support.
 // slm_solve_l0_l1 (the reference's L1L0, _regularized_l0.py:258-410) is the same call in l1 mode: the kernel's L1 instantiation,
 // the l0_l1_* functions of l0_host.hpp for seed, winner and the dual bound on all columns.
+// slm_solve_l0_profile is the same search in profile mode (the kernel's PROFILE instantiation): the best support of every size
+// up to max_groups from one launch, seeded per size by the same greedy selection, each size's coefficients recomputed here.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -14,17 +16,14 @@ namespace {
 constexpr long long kL0DefaultNodes = 1ll << 30;  // the budget of a call that names none: at the 6.2e8 nodes/s measured at 25 x 30
                                                   // (profiles/l0_search.txt) a call that exhausts it stays under two seconds
 
-// Both entries.  eta_l1 > 0 is l1 mode (the kernel's L1 instantiation, the l0_l1_* functions of l0_host.hpp); eta_l1 == 0 is the
-// search without an l1 term, instruction for instruction what it was before there was one.
-int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double eta_l1, double big_M,
-                  const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* lower_bound_out,
-                  int64_t* nodes_out, slm_point_info* info) {
-  if (!ds || !beta_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  // the arguments are checked before anything touches the device
-  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(SLM_ERR_BAD_ARG, "alpha must be finite and >= 0");
+// The argument checks both searches share, before anything touches the device.  alpha_name: what the l0 weight is called in
+// the entry's own signature.  Leaves p and the group count.
+int l0_check_args(slm_dataset* ds, const void* out, double alpha, const char* alpha_name, double eta, double eta_l1, double big_M,
+                  const double* T, const uint64_t* need, int* p_out, int* ng_out) {
+  if (!ds || !out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(SLM_ERR_BAD_ARG, "%s must be finite and >= 0", alpha_name);
   if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(SLM_ERR_BAD_ARG, "eta must be finite and >= 0");
   if (!(eta_l1 >= 0.0) || !std::isfinite(eta_l1)) return fail(SLM_ERR_BAD_ARG, "eta_l1 must be finite and >= 0");
-  const bool l1 = eta_l1 > 0.0;
   if (!(big_M >= 0.0)) return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
   const int64_t p64 = ds->p;
   const int ng = ds->singleton ? (int)std::min<int64_t>(p64, L0_PMAX + 1) : ds->G;
@@ -38,14 +37,21 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
     return fail(SLM_ERR_UNSUPPORTED, "the exact l0 search takes up to %d columns and %d groups (got %lld, %d)", L0_PMAX, L0_PMAX,
                 (long long)p64, ng);
   if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "the exact l0 search is not built for row-sharded datasets");
-  const int p = (int)p64;
-  const int K = max_groups < 0 ? 0 : std::min<int>(max_groups, ng);
-  // the value (without alpha |S|) and coefficients of one support, as the kernel values a node
-  auto value_of = [&](const std::vector<double>& H, const std::vector<double>& c, const std::vector<int>& gstart, unsigned long long mask,
-                      bool polish, double* beta) {
-    return l1 ? l0_l1_support(H.data(), c.data(), p, gstart, mask, eta_l1, big_M, polish, beta)
-              : l0_support(H.data(), c.data(), p, gstart, mask, big_M, polish, beta);
-  };
+  *p_out = (int)p64;
+  *ng_out = ng;
+  return SLM_OK;
+}
+
+// What both searches work on: the dataset's Gram on the host, the search order, H = G + 2 eta T and c in that order, the
+// hierarchy in that order, and the unconstrained value on all columns.
+struct L0Problem {
+  std::vector<double> G, cvec, H, c;  // G, cvec: the dataset's order; H, c: search order
+  std::vector<int> cols, gstart, gorder;
+  std::vector<unsigned long long> needo;
+  double q_all = 0.0, yy = 0.0;
+};
+
+int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, const uint64_t* need, L0Problem& P) {
   slm_engine* eng = ds->eng;
   HIP_TRY(hipSetDevice(eng->device));
   hipStream_t s = eng->stream;
@@ -57,7 +63,9 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   SLM_TRY(cov_fingerprints(ds, &wdev, 1, fp));
   const int entry = cov_find(ds, fp[0], fp[1], (double)ds->n_global);
   if (entry < 0) return fail(SLM_ERR_HIP, "the dataset's Gram was not filed");
-  std::vector<double> G((size_t)p * p), cvec((size_t)p);
+  std::vector<double>&G = P.G, &cvec = P.cvec;
+  G.assign((size_t)p * p, 0.0);
+  cvec.assign((size_t)p, 0.0);
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipMemcpy2D(G.data(), sizeof(double) * p, ds->cov[(size_t)entry].G, sizeof(double) * ds->ld, sizeof(double) * p, (size_t)p,
                       hipMemcpyDeviceToHost));
@@ -75,19 +83,25 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
     num[(size_t)gid[(size_t)j]] += cvec[(size_t)j] * cvec[(size_t)j];
     den[(size_t)gid[(size_t)j]] += G[(size_t)j * p + j];
   }
-  std::vector<int> gorder((size_t)ng), gpos((size_t)ng);
+  std::vector<int>& gorder = P.gorder;
+  gorder.assign((size_t)ng, 0);
+  std::vector<int> gpos((size_t)ng);
   std::iota(gorder.begin(), gorder.end(), 0);
   auto score = [&](int g) { return den[(size_t)g] > 0.0 ? num[(size_t)g] / den[(size_t)g] : 0.0; };
   std::stable_sort(gorder.begin(), gorder.end(), [&](int x, int y) { return score(x) > score(y); });
   for (int k = 0; k < ng; ++k) gpos[(size_t)gorder[(size_t)k]] = k;
-  std::vector<int> cols;  // search position -> column of X
-  std::vector<int> gstart((size_t)ng + 1, 0);
+  std::vector<int>& cols = P.cols;  // search position -> column of X
+  std::vector<int>& gstart = P.gstart;
+  cols.clear();
+  gstart.assign((size_t)ng + 1, 0);
   for (int k = 0; k < ng; ++k) {
     for (int j = 0; j < p; ++j)
       if (gid[(size_t)j] == gorder[(size_t)k]) cols.push_back(j);
     gstart[(size_t)k + 1] = (int)cols.size();
   }
-  std::vector<double> H((size_t)p * p), c((size_t)p);
+  std::vector<double>&H = P.H, &c = P.c;
+  H.assign((size_t)p * p, 0.0);
+  c.assign((size_t)p, 0.0);
   for (int i = 0; i < p; ++i) {
     c[(size_t)i] = cvec[(size_t)cols[(size_t)i]];
     for (int j = 0; j < p; ++j) {
@@ -97,59 +111,105 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
       H[(size_t)i * p + j] = G[(size_t)ci * p + cj] + 2.0 * eta * t;
     }
   }
-  std::vector<unsigned long long> needo((size_t)ng, 0ull);
+  std::vector<unsigned long long>& needo = P.needo;
+  needo.assign((size_t)ng, 0ull);
   if (need)
     for (int g = 0; g < ng; ++g)
       for (int h = 0; h < ng; ++h)
         if (h != g && ((need[g] >> h) & 1)) needo[(size_t)gpos[(size_t)g]] |= 1ull << gpos[(size_t)h];
 
-  // ---- the unconstrained value on all columns, and the greedy seed of the incumbent -----------------------------------------
-  std::vector<double> beta_s((size_t)p);
-  double q_all;
+  // ---- the unconstrained value on all columns ------------------------------------------------------------------------------
   {
     L0Factor f(H.data(), c.data(), p);
     for (int j = 0; j < p; ++j) (void)f.push(j);
-    q_all = -0.5 * f.ss;
+    P.q_all = -0.5 * f.ss;
   }
+  P.yy = ds->cov[(size_t)entry].yy;
+  return SLM_OK;
+}
+
+// The search's one device block: the stream is drained and the block freed however the call ends.
+struct L0DevGuard {
+  unsigned long long*& p;
+  hipStream_t s;
+  ~L0DevGuard() {
+    (void)hipStreamSynchronize(s);
+    dfree(p);
+  }
+};
+
+// Greedy forward selection over the groups, up to K of them: one admissible support per size, handed to visit(size, support,
+// value) with the value value_of(support) gives it (the kernel's own valuation, no alpha term); and, when K reaches the group
+// count, the support of every group -- the one whose value can meet the bound q_all exactly.
+template <class ValueOf, class Visit>
+void l0_greedy(const L0Problem& P, int p, int ng, int K, ValueOf value_of, Visit visit) {
+  const std::vector<int>& gstart = P.gstart;
+  const std::vector<unsigned long long>& needo = P.needo;
+  L0Factor f(P.H.data(), P.c.data(), p);
+  unsigned long long cur = 0;
+  for (int step = 0; step < K; ++step) {
+    int pick = -1;
+    double pick_ss = f.ss;
+    const int m0 = f.m;
+    for (int g = 0; g < ng; ++g) {
+      if (((cur >> g) & 1) || (needo[(size_t)g] & ~cur)) continue;
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) (void)f.push(j);  // (dependent columns are skipped, as in the kernel)
+      if (f.ss > pick_ss) {
+        pick_ss = f.ss;
+        pick = g;
+      }
+      f.pop_to(m0);
+    }
+    if (pick < 0) break;
+    cur |= 1ull << pick;
+    // (the factor keeps search order inside the kernel; the seed's value is taken the same way)
+    visit(step + 1, cur, value_of(cur));
+    for (int j = gstart[(size_t)pick]; j < gstart[(size_t)pick + 1]; ++j) (void)f.push(j);
+  }
+  if (K >= ng && ng > 0) {
+    const unsigned long long all_mask = ng == 64 ? ~0ull : ((1ull << ng) - 1);
+    visit(ng, all_mask, value_of(all_mask));
+  }
+}
+
+// Both entries.  eta_l1 > 0 is l1 mode (the kernel's L1 instantiation, the l0_l1_* functions of l0_host.hpp); eta_l1 == 0 is the
+// search without an l1 term, instruction for instruction what it was before there was one.
+int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double eta_l1, double big_M,
+                  const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* lower_bound_out,
+                  int64_t* nodes_out, slm_point_info* info) {
+  int p = 0, ng = 0;
+  SLM_TRY(l0_check_args(ds, beta_out, alpha, "alpha", eta, eta_l1, big_M, T, need, &p, &ng));
+  const bool l1 = eta_l1 > 0.0;
+  const int K = max_groups < 0 ? 0 : std::min<int>(max_groups, ng);
+  // the value (without alpha |S|) and coefficients of one support, as the kernel values a node
+  auto value_of = [&](const std::vector<double>& H, const std::vector<double>& c, const std::vector<int>& gstart, unsigned long long mask,
+                      bool polish, double* beta) {
+    return l1 ? l0_l1_support(H.data(), c.data(), p, gstart, mask, eta_l1, big_M, polish, beta)
+              : l0_support(H.data(), c.data(), p, gstart, mask, big_M, polish, beta);
+  };
+  L0Problem P;
+  SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, P));
+  slm_engine* eng = ds->eng;
+  hipStream_t s = eng->stream;
+  const std::vector<double>&G = P.G, &cvec = P.cvec, &H = P.H, &c = P.c;
+  const std::vector<int>&cols = P.cols, &gstart = P.gstart, &gorder = P.gorder;
+  const std::vector<unsigned long long>& needo = P.needo;
+  const double q_all = P.q_all;
+
+  // ---- the greedy seed of the incumbent ------------------------------------------------------------------------------------
+  std::vector<double> beta_s((size_t)p);
   // the subtree bound's lower bound on the value of all columns: in l1 mode the lasso dual value where it is above q_all
-  const double bound = l1 ? l0_l1_lower_bound(H.data(), c.data(), p, ds->cov[(size_t)entry].yy, eta_l1, q_all) : q_all;
-  const unsigned long long all_mask = ng == 64 ? ~0ull : ((1ull << ng) - 1);
+  const double bound = l1 ? l0_l1_lower_bound(H.data(), c.data(), p, P.yy, eta_l1, q_all) : q_all;
   double seed_val = 0.0;  // the empty support
   unsigned long long seed_mask = 0;
-  {
-    L0Factor f(H.data(), c.data(), p);
-    unsigned long long cur = 0;
-    for (int step = 0; step < K; ++step) {
-      int pick = -1;
-      double pick_ss = f.ss;
-      const int m0 = f.m;
-      for (int g = 0; g < ng; ++g) {
-        if (((cur >> g) & 1) || (needo[(size_t)g] & ~cur)) continue;
-        for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) (void)f.push(j);  // (dependent columns are skipped, as in the kernel)
-        if (f.ss > pick_ss) {
-          pick_ss = f.ss;
-          pick = g;
-        }
-        f.pop_to(m0);
-      }
-      if (pick < 0) break;
-      cur |= 1ull << pick;
-      // (the factor keeps search order inside the kernel; the seed's value is taken the same way)
-      const double v = value_of(H, c, gstart, cur, false, beta_s.data()) + alpha * (double)(step + 1);
-      if (v < seed_val) {
-        seed_val = v;
-        seed_mask = cur;
-      }
-      for (int j = gstart[(size_t)pick]; j < gstart[(size_t)pick + 1]; ++j) (void)f.push(j);
-    }
-    if (K >= ng && ng > 0) {  // every group: the one support whose value can meet the bound exactly
-      const double v = value_of(H, c, gstart, all_mask, false, beta_s.data()) + alpha * (double)ng;
-      if (v < seed_val) {
-        seed_val = v;
-        seed_mask = all_mask;
-      }
-    }
-  }
+  l0_greedy(P, p, ng, K, [&](unsigned long long mask) { return value_of(H, c, gstart, mask, false, beta_s.data()); },
+            [&](int size, unsigned long long mask, double quad) {
+              const double v = quad + alpha * (double)size;
+              if (v < seed_val) {
+                seed_val = v;
+                seed_mask = mask;
+              }
+            });
 
   // ---- the search: one launch --------------------------------------------------------------------------------------------
   const int d = std::min(ng, L0_PREFIX);
@@ -167,14 +227,7 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   for (int g = 0; g <= ng; ++g) h[off_gs + (size_t)g] = (unsigned long long)gstart[(size_t)g];
   unsigned long long* dev = nullptr;
   SLM_TRY(dalloc(&dev, words));
-  struct Guard {
-    unsigned long long*& p;
-    hipStream_t s;
-    ~Guard() {
-      (void)hipStreamSynchronize(s);
-      dfree(p);
-    }
-  } guard{dev, s};
+  L0DevGuard guard{dev, s};
   HIP_TRY(hipMemcpyAsync(dev, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, s));
   L0Args k;
   memset(&k, 0, sizeof(k));
@@ -226,7 +279,7 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
   if (info) {
     // 1/(2n)||X beta - y||_W^2 = 1/2 beta^T G beta - c^T beta + 1/2 y^T W y / n from the Gram already on the host: no second launch
-    double loss = 0.5 * ds->cov[(size_t)entry].yy;
+    double loss = 0.5 * P.yy;
     for (int i = 0; i < p; ++i) {
       if (beta_out[i] == 0.0) continue;
       double t = 0.0;
@@ -251,6 +304,114 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   return SLM_OK;
 }
 
+// slm_solve_l0_profile: the kernel's PROFILE instantiation.  Seeds per size from the greedy selection, one launch, then per size
+// the minimum over the waves' bests and the seed in a fixed order and the coefficients recomputed from H on that support.
+int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
+                          const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
+                          int64_t* nodes_out, slm_point_info* info) {
+  int p = 0, ng = 0;
+  if (!support_out || !value_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  SLM_TRY(l0_check_args(ds, beta_out, alpha_min, "alpha_min", eta, 0.0, big_M, T, need, &p, &ng));
+  const int rows = max_groups < 0 ? 0 : (int)max_groups;  // the outputs have rows + 1 entries; sizes above the group count stay unfilled
+  const int K = std::min(rows, ng);
+  L0Problem P;
+  SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, P));
+  slm_engine* eng = ds->eng;
+  hipStream_t s = eng->stream;
+  const std::vector<double>&H = P.H, &c = P.c;
+
+  // ---- the seed of every size: the supports the greedy selection passes through, valued as the kernel values a node ---------
+  std::vector<double> beta_s((size_t)p);
+  std::vector<double> win_val((size_t)L0_PMAX + 1, HUGE_VAL);
+  std::vector<unsigned long long> win_mask((size_t)L0_PMAX + 1, ~0ull);
+  win_val[0] = 0.0;  // the empty support
+  win_mask[0] = 0ull;
+  l0_greedy(P, p, ng, K, [&](unsigned long long mask) { return l0_support(H.data(), c.data(), p, P.gstart, mask, big_M, false, beta_s.data()); },
+            [&](int size, unsigned long long mask, double quad) {
+              if (quad < win_val[(size_t)size] || (quad == win_val[(size_t)size] && mask < win_mask[(size_t)size])) {
+                win_val[(size_t)size] = quad;
+                win_mask[(size_t)size] = mask;
+              }
+            });
+
+  // ---- the search: one launch --------------------------------------------------------------------------------------------
+  const int d = std::min(ng, L0_PREFIX);
+  const long long n_tickets = 1ll << d;
+  const int blocks = (int)std::max<long long>(1, std::min<long long>(2ll * eng->cus, (n_tickets + L0_WAVES - 1) / L0_WAVES));
+  const int waves = blocks * L0_WAVES;
+  // one block of 8-byte words: control | incumbents per size | best values [waves][64] | best supports [waves][64] | H | c | need | group starts
+  const size_t off_bv = L0_PROFILE_WORDS, off_bm = off_bv + (size_t)waves * 64, off_H = off_bm + (size_t)waves * 64,
+               off_c = off_H + (size_t)p * p, off_need = off_c + (size_t)p, off_gs = off_need + (size_t)ng, words = off_gs + (size_t)ng + 1;
+  std::vector<unsigned long long> h(words, 0ull);
+  for (int k = 1; k <= L0_PMAX; ++k) h[(size_t)L0_PROFILE_INC + (size_t)k - 1] = l0_key(win_val[(size_t)k]);
+  memcpy(&h[off_H], H.data(), sizeof(double) * (size_t)p * p);
+  memcpy(&h[off_c], c.data(), sizeof(double) * (size_t)p);
+  for (int g = 0; g < ng; ++g) h[off_need + (size_t)g] = P.needo[(size_t)g];
+  for (int g = 0; g <= ng; ++g) h[off_gs + (size_t)g] = (unsigned long long)P.gstart[(size_t)g];
+  unsigned long long* dev = nullptr;
+  SLM_TRY(dalloc(&dev, words));
+  L0DevGuard guard{dev, s};
+  HIP_TRY(hipMemcpyAsync(dev, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, s));
+  L0Args k;
+  memset(&k, 0, sizeof(k));
+  k.ctl = dev;
+  k.best_val = reinterpret_cast<double*>(dev + off_bv);
+  k.best_mask = dev + off_bm;
+  k.H = reinterpret_cast<const double*>(dev + off_H);
+  k.c = reinterpret_cast<const double*>(dev + off_c);
+  k.need = dev + off_need;
+  k.gstart = reinterpret_cast<const long long*>(dev + off_gs);
+  k.p = p; k.ng = ng; k.d = d; k.K = K;
+  k.alpha = alpha_min; k.big_M = big_M; k.q_all = P.q_all;
+  k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
+  hipLaunchKernelGGL((l0_search_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  SLM_TRY(check_launch());
+  HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(unsigned long long) * off_H, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+
+  // ---- per size: the waves' bests and the seed in a fixed order, the lower support on a bitwise tie ---------------------------
+  for (int size = 1; size <= K; ++size)
+    for (int wv = 0; wv < waves; ++wv) {
+      double v;
+      memcpy(&v, &h[off_bv + (size_t)wv * 64 + (size_t)size - 1], 8);
+      const unsigned long long mk = h[off_bm + (size_t)wv * 64 + (size_t)size - 1];
+      if (v < win_val[(size_t)size] || (v == win_val[(size_t)size] && mk < win_mask[(size_t)size])) {
+        win_val[(size_t)size] = v;
+        win_mask[(size_t)size] = mk;
+      }
+    }
+  const bool finished = h[L0_ABORTED] == 0;
+  // the coefficients of every size, recomputed here whichever wave found its support; a size nobody filled: +inf, all ones, zeros
+  for (int size = 0; size <= rows; ++size) {
+    double* beta = beta_out + (size_t)size * p;
+    for (int i = 0; i < p; ++i) beta[i] = 0.0;
+    const bool filled = size <= K && std::isfinite(win_val[(size_t)size]);
+    value_out[size] = HUGE_VAL;
+    support_out[size] = ~0ull;
+    if (!filled) continue;
+    value_out[size] = l0_support(H.data(), c.data(), p, P.gstart, win_mask[(size_t)size], big_M, true, beta_s.data());
+    unsigned long long support = 0;
+    for (int g = 0; g < ng; ++g)
+      if ((win_mask[(size_t)size] >> g) & 1) support |= 1ull << P.gorder[(size_t)g];
+    support_out[size] = support;
+    for (int i = 0; i < p; ++i) beta[P.cols[(size_t)i]] = beta_s[(size_t)i];
+  }
+  if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
+  if (info) {
+    memset(info, 0, sizeof(*info));
+    info->n_iter = 1;
+    info->status = finished ? SLM_OK : SLM_ERR_NOT_CONVERGED;
+    info->mode = 4;
+    const int at = l0_profile_regularized(value_out, K, alpha_min), sub = l0_profile_best_subset(value_out, K);
+    info->kkt = value_out[at] + alpha_min * (double)at;  // the regularised optimum at alpha_min, the smallest alpha the table serves
+    info->mu = value_out[sub];                           // the best-subset optimum at the bound max_groups
+    info->L = P.q_all;
+  }
+  if (!finished) return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld) ran out before the search finished: the table of incumbents is returned",
+                             (long long)k.max_nodes);
+  return SLM_OK;
+}
+
 }  // namespace
 
 extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
@@ -265,4 +426,11 @@ extern "C" int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, dou
                                slm_point_info* info) {
   return solve_l0_impl(ds, alpha, L0_PMAX, 0.0, nullptr, eta_l1, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out,
                        info);
+}
+
+// The table of the best supports of every size up to max_groups, from one search (the kernel's profile mode).
+extern "C" int slm_solve_l0_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
+                                    const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
+                                    int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_profile_impl(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
 }

@@ -1,8 +1,8 @@
 // Host side of the exact l0 search (l0_kernels.hpp, engine_l0.hip): the limits and tolerances the kernel and the host share,
 // the factor of H on a growing list of columns as the kernel keeps it, the boxed descent candidates are compared by, and the
-// value and coefficients of one support, and the same for l1 mode (a lasso per support: the descent, its polish, the dual
-// bound on all columns).  Like host_logic.hpp and tail_logic.hpp it is free of HIP types so that g++
-// compiles it alone: tests/host_logic_test.cpp and tests/l1l0_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 call
+// value and coefficients of one support, the same for l1 mode (a lasso per support: the descent, its polish, the dual
+// bound on all columns), and for profile mode the pruning rule and the two questions its table answers.  Like host_logic.hpp and tail_logic.hpp it is free of HIP types so that g++
+// compiles it alone: tests/host_logic_test.cpp, tests/l1l0_host_test.cpp and tests/l0_profile_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 / slm_solve_l0_profile call
 // THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.
 #pragma once
 #include <stddef.h>
@@ -163,6 +163,37 @@ inline double l0_support(const double* H, const double* c, int p, const std::vec
   for (int k = 0; k < f.m; ++k) beta[f.col[k]] = b[k];
   return val;
 }
+
+// ---- profile mode (slm_solve_l0_profile): the best support of every size from one search ------------------------------------
+//
+// values[k], k = 0 .. K: the best quadratic value over admissible supports of exactly k groups (values[0] = 0, +inf where no
+// support of that size was held).  The two questions the table answers; ties go to the smaller k, and an all-+inf range
+// answers 0 (the empty support is always there).
+inline int l0_profile_best_subset(const double* values, int K_prime) {  // argmin_{k <= K'} values[k]
+  int best = 0;
+  for (int k = 1; k <= K_prime; ++k)
+    if (values[k] < values[best]) best = k;
+  return best;
+}
+inline int l0_profile_regularized(const double* values, int K, double alpha) {  // argmin_k values[k] + alpha k
+  int best = 0;
+  for (int k = 1; k <= K; ++k)
+    if (values[k] + alpha * (double)k < values[best] + alpha * (double)best) best = k;
+  return best;
+}
+
+// The pruning rule of the profile search, one set of functions for host and device (constexpr, as l0_l1_step is):
+//     E(c) = min(0, min_{1 <= k <= c} q_k + alpha_min k),      cut below a node of cnt groups when q_all + alpha_min (cnt + 1) >= E(cnt).
+// The kernel folds l0_profile_term with l0_profile_join across the lanes (a prefix-min); l0_profile_envelope is the same
+// fold in a loop.  q: the incumbents of the sizes 1 .. c (q[k - 1] for size k).
+constexpr double l0_profile_term(double qk, int k, double alpha_min) { return qk + alpha_min * (double)k; }
+constexpr double l0_profile_join(double a, double b) { return b < a ? b : a; }
+constexpr double l0_profile_envelope(const double* q, int c, double alpha_min) {
+  double e = 0.0;
+  for (int k = 1; k <= c; ++k) e = l0_profile_join(e, l0_profile_term(q[k - 1], k, alpha_min));
+  return e;
+}
+constexpr bool l0_profile_cut(double q_all, double alpha_min, int cnt, double e_cnt) { return !(q_all + alpha_min * (double)(cnt + 1) < e_cnt); }
 
 // ---- l1 mode (slm_solve_l0_l1, the reference's L1L0): eta ||beta||_1 joins the objective ------------------------------------
 //

@@ -37,6 +37,19 @@
 // included: with an l1 term a column equal to a + b replaces two coefficients by one, so a dependent column CAN lower the
 // value, and the cut of a group that brought no independent column is off.  The subtree bound takes a proven lower bound
 // on f(all columns) from the host in q_all (the lasso dual value at a feasible point, or q_all itself).
+//
+// profile mode (template parameter PROFILE, slm_solve_l0_profile; never together with L1): ONE search returns, for every
+// size k = 1 .. K, the best admissible support of exactly k groups -- the table Q_k that answers best subset for every bound
+// K' <= K (min_{k <= K'} Q_k) and RegularizedL0 / L2L0 for every alpha (min_k Q_k + alpha k).  Lane k - 1 of a wave keeps the
+// wave's best (value, support) of size k and the shared incumbent of that size, read from an array of 64 keys behind the
+// control words (one coalesced load per refresh, one atomic min per improvement).  A node of cnt groups is a candidate for
+// entry cnt alone, valued without an alpha term; the tie rule is the one above, per size.  a.alpha holds alpha_min, and the
+// subtree bound becomes  q_all + alpha_min (cnt + 1) >= E(cnt),  E(c) = min(0, min_{1 <= k <= c} Qinc_k + alpha_min k)
+// (l0_profile_term / l0_profile_join of l0_host.hpp, a prefix-min over the lanes at every refresh): every support S' below
+// the node has k' >= cnt + 1 groups and q(S') >= q_all, so for the minimising k* <= cnt and any alpha >= alpha_min
+//     Qinc_k* + alpha k* <= q_all + alpha_min (cnt + 1) + (alpha - alpha_min) k* <= q(S') + alpha k'
+// -- S' is never strictly better than a support already held.  With alpha_min = 0 the cut fires only where a held support
+// has reached q_all, and the table is the full one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,17 +63,20 @@ constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
 constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CTL_WORDS = 8;
+// profile mode: the incumbents of the sizes 1 .. 64 (keys, seeded by the host) follow the control words
+constexpr int L0_PROFILE_INC = L0_CTL_WORDS, L0_PROFILE_WORDS = L0_CTL_WORDS + L0_PMAX;
 
 struct L0Args {
   const double* H;                  // [p][p] G + 2 eta T, search order
   const double* c;                  // [p]
   const long long* gstart;          // [ng + 1] first column of each group
   const unsigned long long* need;   // [ng] groups (search order) each group depends on
-  unsigned long long* ctl;          // [L0_CTL_WORDS]
-  double* best_val;                 // [waves of the grid]
-  unsigned long long* best_mask;    // [waves of the grid]
+  unsigned long long* ctl;          // [L0_CTL_WORDS]; profile mode: [L0_PROFILE_WORDS]
+  double* best_val;                 // [waves of the grid]; profile mode: [waves][64], entry k - 1 for size k
+  unsigned long long* best_mask;    // [waves of the grid]; profile mode: [waves][64]
   int p, ng, d, K;
-  double alpha, big_M, q_all;       // (q_all: the proven lower bound on the value of ALL columns the subtree bound uses)
+  double alpha, big_M, q_all;       // (q_all: the proven lower bound on the value of ALL columns the subtree bound uses;
+                                    //  profile mode: alpha is alpha_min)
   long long max_nodes;
   double eta_l1;                    // l1 mode only: the weight of ||beta||_1
 };
@@ -88,6 +104,9 @@ static __device__ __forceinline__ double l0_wave_sum(double v) {  // the same bi
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
   return v;
 }
+static __device__ __forceinline__ unsigned long long l0_bcast(unsigned long long v, int k) {
+  return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), k) << 32) | (unsigned)__builtin_amdgcn_readlane((int)v, k);
+}
 static __device__ __forceinline__ double l0_wave_max(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
@@ -95,8 +114,10 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
 }
 
 // L1 = false: the search above.  L1 = true: eta_l1 ||beta||_1 joins the objective (see the head of the file).
-template <bool L1>
+// PROFILE = true: the best support of every size (see the head of the file); everything it adds sits under if constexpr.
+template <bool L1, bool PROFILE = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
+  static_assert(!(L1 && PROFILE), "the profile mode has no l1 term");
   __shared__ double Hs[L0_PMAX * L0_PMAX];
   __shared__ double cs[L0_PMAX];
   __shared__ unsigned long long needs[L0_PMAX];
@@ -125,9 +146,26 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   double st_ss = 0.0;
   unsigned long long st_need = 0;
 
+  // (profile mode: these two and inc are per lane -- lane k - 1 holds size k -- and env is E(k) of the head of the file)
   double best_v = __builtin_inf();
   unsigned long long best_mask = ~0ull;
-  double inc = l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  auto read_incumbent = [&]() {
+    if constexpr (PROFILE)
+      return l0_unkey(__hip_atomic_load(&a.ctl[L0_PROFILE_INC + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    else
+      return l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  };
+  double inc = read_incumbent();
+  double env = 0.0;
+  auto envelope = [&]() {  // an inclusive prefix-min of Qinc_k + alpha_min k over the lanes, capped by 0 (the empty support)
+    double v = l0_profile_term(inc, lane + 1, alpha);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const double t = __shfl_up(v, off);
+      if (lane >= off) v = l0_profile_join(v, t);
+    }
+    env = l0_profile_join(0.0, v);
+  };
   long long nodes_local = 0;
   int since_refresh = 0;
   unsigned long long needed = 0;  // groups some other group depends on
@@ -148,7 +186,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
       if (lane == 0) atomicOr(&a.ctl[L0_ABORTED], 1ull);
       break;
     }
-    inc = l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    inc = read_incumbent();
+    if constexpr (PROFILE) envelope();
     int m = 0, cnt = 0, depth = 0;
     na = 0;
     double ss = 0.0;
@@ -160,7 +199,12 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
       int g;
       bool try_exclude = false;
       if (down) {
-        if (depth >= ng || cnt >= K || !(q_all + alpha * (double)(cnt + 1) < inc)) {
+        bool stop_here;
+        if constexpr (PROFILE)  // the subtree bound against E(cnt)
+          stop_here = depth >= ng || cnt >= K || l0_profile_cut(q_all, alpha, cnt, cnt == 0 ? 0.0 : l0_bcast(env, cnt - 1));
+        else
+          stop_here = depth >= ng || cnt >= K || !(q_all + alpha * (double)(cnt + 1) < inc);
+        if (stop_here) {
           down = false;
           continue;
         }
@@ -239,7 +283,16 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           // every node is a candidate; inside the prefix the ticket whose remaining bits are zero evaluates it
           const bool mine = depth >= d || (t >> depth) == 0;
           double val = -0.5 * ss + alpha * (double)cnt;
-          if (mine && (needm & ~incl) == 0 && val <= inc && (val < best_v || (val == best_v && incl < best_mask))) {
+          // what the candidate has to beat: the incumbent and the wave's best -- in profile mode those of its size
+          double inc_k = inc, best_k = best_v;
+          unsigned long long mask_k = best_mask;
+          if constexpr (PROFILE) {
+            val = -0.5 * ss;
+            inc_k = l0_bcast(inc, cnt - 1);
+            best_k = l0_bcast(best_v, cnt - 1);
+            mask_k = l0_bcast(best_mask, cnt - 1);
+          }
+          if (mine && (needm & ~incl) == 0 && val <= inc_k && (val < best_k || (val == best_k && incl < mask_k))) {
             // back-substitution beta = L^-T w, row by row from the last: lane r contributes L[r][k] beta_r to entry k
             double beta = 0.0;
 #pragma unroll
@@ -309,24 +362,39 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
                 }
                 if (maxd <= L0_CD_TOL * maxb || maxd == 0.0) break;
               }
-              val = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0) + alpha * (double)cnt;
+              if constexpr (PROFILE)
+                val = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0);
+              else
+                val = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0) + alpha * (double)cnt;
             }
-            if (val <= inc && (val < best_v || (val == best_v && incl < best_mask))) {
+            if (val <= inc_k && (val < best_k || (val == best_k && incl < mask_k))) {
               unsigned long long old = 0;
-              if (lane == 0) old = atomicMin(&a.ctl[L0_INCUMBENT], l0_key(val));
+              if (lane == 0) old = atomicMin(PROFILE ? &a.ctl[L0_PROFILE_INC + cnt - 1] : &a.ctl[L0_INCUMBENT], l0_key(val));
               const double seen = l0_unkey(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) |
                                            (unsigned)__builtin_amdgcn_readfirstlane((int)old));
-              inc = fmin(seen, val);
-              if (val <= inc) {
-                best_v = val;
-                best_mask = incl;
+              if constexpr (PROFILE) {
+                const double now = fmin(seen, val);
+                if (lane == cnt - 1) {
+                  inc = now;
+                  if (val <= now) {
+                    best_v = val;
+                    best_mask = incl;
+                  }
+                }
+              } else {
+                inc = fmin(seen, val);
+                if (val <= inc) {
+                  best_v = val;
+                  best_mask = incl;
+                }
               }
             }
           }
           // a fresh look at the incumbent now and then
           if (++since_refresh >= 32) {
             since_refresh = 0;
-            inc = fmin(inc, l0_unkey(__hip_atomic_load(&a.ctl[L0_INCUMBENT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+            inc = fmin(inc, read_incumbent());
+            if constexpr (PROFILE) envelope();
           }
           continue;  // (down, one level deeper)
         }
@@ -361,13 +429,20 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
       }
     }
   }
+  if constexpr (PROFILE) {  // every lane its size: 64 values and 64 supports per wave
+    const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
+    a.best_val[(size_t)wv * 64 + lane] = best_v;
+    a.best_mask[(size_t)wv * 64 + lane] = best_mask;
+  }
   if (lane == 0) {
     if (nodes_local > 0) atomicAdd(&a.ctl[L0_NODES], (unsigned long long)nodes_local);
     if constexpr (L1)
       if (descents_local > 0) atomicAdd(&a.ctl[L0_DESCENTS], (unsigned long long)descents_local);
-    const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
-    a.best_val[wv] = best_v;
-    a.best_mask[wv] = best_mask;
+    if constexpr (!PROFILE) {
+      const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
+      a.best_val[wv] = best_v;
+      a.best_mask[wv] = best_mask;
+    }
   }
 }
 

@@ -90,6 +90,7 @@ ABI_SYMBOLS = (
     "slm_solve_constrained",
     "slm_solve_l0",
     "slm_solve_l0_l1",
+    "slm_solve_l0_profile",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -349,6 +350,7 @@ def load_library():
             "slm_solve_constrained": [vp, vp, vp, i32, vp, vp, P(_SolveOpts), dbl, i32, vp, i32, vp, vp, P(_PointInfo)],
             "slm_solve_l0": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_l1": [vp, dbl, dbl, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
+            "slm_solve_l0_profile": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1357,6 +1359,46 @@ class Dataset:
             "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
             "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
             "descents": int(info["rejects"]), "box_tol": 1e-12,
+        }
+
+    def solve_l0_profile(self, alpha_min=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_profile``: one search that returns the best support of EVERY size ``k = 0 .. max_groups`` for
+        ``1/2 b^T (G + 2 eta T) b - c^T b`` inside the box and under the hierarchy (the arguments of ``solve_l0``), pruned
+        only by what no ``alpha >= alpha_min`` can use.  Returns ``(betas [K + 1, p], support masks [K + 1], values [K + 1],
+        info)``; an entry nobody filled holds ``+inf``, an all-ones mask and zeros.  ``info``: ``nodes``, ``launches``,
+        ``q_all``, ``status``, ``proven_optimal``, ``box_tol``."""
+        _sync_knobs()
+        G = self.n_groups
+        K = G if max_groups is None else int(max_groups)
+        if K < 0:
+            raise ValueError("max_groups must be >= 0")
+        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
+        need_ = None
+        if need is not None:
+            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
+            if need_.shape != (G,):
+                raise ValueError(f"need must have {G} entries")
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        if b is not None:
+            betas, supports, values, nodes, rec, rc = b.solve_l0_profile(self._h.value, self.p, float(alpha_min), K, float(eta), T_,
+                                                                         float(big_M), need_, int(max_nodes))
+            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
+        else:
+            betas = np.empty((K + 1, self.p))
+            supports = np.empty(K + 1, dtype=np.uint64)
+            values = np.empty(K + 1)
+            nd = C.c_int64()
+            infos = np.zeros(1, dtype=_INFO_DTYPE)
+            rc = self._lib.slm_solve_l0_profile(self._h, float(alpha_min), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes),
+                                                _ptr(betas), _ptr(supports), _ptr(values), C.byref(nd), _as(infos, _PointInfo))
+            if rc != SLM_ERR_NOT_CONVERGED:
+                _check(rc)
+            nodes, info = int(nd.value), infos[0]
+        return betas, supports, values, {
+            "nodes": int(nodes), "launches": int(info["n_iter"]), "q_all": float(info["L"]),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "proven_optimal": rc == SLM_OK, "box_tol": 1e-12,
         }
 
 

@@ -4,8 +4,13 @@ search over supports on the GPU.
 
 ``from sparselm_amd.miqp import L1L0`` is the import path of ``L1L0``.  ``sparselm_amd.model`` exports the other four
 (``model.MIQP_ESTIMATORS``), as before.
+
+``l0_profile`` / ``L0Profile`` (``model/_l0_profile.py``) are here too, beside ``__all__``'s five estimator names: one search
+that returns the best support of every size, from which best subset at every bound and the regularised optimum at every
+``alpha`` are read off.
 """
 
+from .model._l0_profile import L0Profile, l0_profile  # noqa: F401  (not estimators: outside __all__, which tests pin)
 from .model._l1l0 import L1L0
 from .model._miqp import L2L0, BestSubsetSelection, RegularizedL0, RidgedBestSubsetSelection
 

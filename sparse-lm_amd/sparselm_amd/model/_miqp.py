@@ -17,10 +17,14 @@ with ``alpha = 0`` for the two best-subset classes (the reference's missing ``1/
 The fifth, ``L1L0`` (an l1 term beside the l0 one: a lasso per support), is served by the same search in its l1 mode
 (``slm_solve_l0_l1``); it lives in ``_l1l0.py`` and its import path is ``sparselm_amd.miqp.L1L0`` -- this module's ``__all__``
 and ``sparselm_amd.model`` keep the four names above.  There is no ``constraints=`` on these classes.
+
+``sparselm_amd.miqp.l0_profile`` (``_l0_profile.py``) answers a whole scan over ``sparse_bound`` or ``alpha`` of the four
+classes here from one search; it shares ``_ExactL0._l0_setup`` and ``_ExactL0._l0_dataset`` with ``fit``.
 """
 
 from __future__ import annotations
 
+import contextlib
 import warnings
 from numbers import Real
 
@@ -104,11 +108,12 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         """The weight of ``||beta||_1`` in the objective (``L1L0``); 0: none, the search without an l1 term."""
         return 0.0
 
-    def fit(self, X, y, sample_weight=None):
+    def _l0_setup(self, X, y, sample_weight):
+        """Everything a search needs, validated before a device is touched (shared with ``l0_profile``, _l0_profile.py):
+        ``(X, y, options, gidx, n_groups, need, T, w)`` with the hierarchy as masks and the sample weights normalised to sum n."""
         X, y = validate_data(self, X, y, accept_sparse=False, y_numeric=True, multi_output=False)
         X = np.asarray(X, dtype=np.float64)
         y = np.asarray(y, dtype=np.float64)
-        # everything is validated before a device is touched
         self._validate_params(X, y)
         options = {} if self.solver_options is None else dict(self.solver_options)
         unknown = set(options) - _KNOWN_OPTIONS
@@ -117,23 +122,33 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         p = X.shape[1]
         gidx, n_groups = dense_group_index(self.groups, p)
         need = _hierarchy_masks(self.hierarchy, self.groups, p)
-        alpha, max_groups, eta = self._l0_problem(n_groups)
         T = self._tikhonov(p)
-        eta_l1 = float(self._l1_weight())
         w = None
         if sample_weight is not None:
             w = _check_sample_weight(sample_weight, X, dtype=X.dtype)
             w = w * (X.shape[0] / np.sum(w))
+        return X, y, options, gidx, n_groups, need, T, w
 
+    @contextlib.contextmanager
+    def _l0_dataset(self, X, y, w, gidx, n_groups, need, options):
+        """The dataset of a search on its device, centred when an intercept is fitted: yields ``(ds, x_mean, y_mean, need,
+        max_nodes)``."""
         from .. import _engine
 
         eng = _engine.get_engine(options.get("device"))
         with eng.dataset(X, y, row_weight=w) as ds:
-            x_mean, y_mean = ds.center() if self.fit_intercept else (np.zeros(p), 0.0)
+            x_mean, y_mean = ds.center() if self.fit_intercept else (np.zeros(X.shape[1]), 0.0)
             ds.set_groups(gidx, n_groups)
             if need is not None and n_groups > 64:
                 need = None  # (the engine refuses the size itself; masks of more than 64 groups have no 64-bit form)
-            max_nodes = int(options.get("max_nodes", 0) or 0)
+            yield ds, x_mean, y_mean, need, int(options.get("max_nodes", 0) or 0)
+
+    def fit(self, X, y, sample_weight=None):
+        # everything is validated before a device is touched
+        X, y, options, gidx, n_groups, need, T, w = self._l0_setup(X, y, sample_weight)
+        alpha, max_groups, eta = self._l0_problem(n_groups)
+        eta_l1 = float(self._l1_weight())
+        with self._l0_dataset(X, y, w, gidx, n_groups, need, options) as (ds, x_mean, y_mean, need, max_nodes):
             if eta_l1 > 0.0:
                 beta, support, info = ds.solve_l0_l1(alpha=alpha, eta_l1=eta_l1, big_M=float(self.big_M), need=need, max_nodes=max_nodes)
             else:
