@@ -665,6 +665,39 @@ int slm_solve_l0_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, 
                          double* value_out /* [max_groups+1] */, int64_t* nodes_out, slm_point_info* info);
 
 /*
+ * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_profile, no existing entry, structure or constant
+ * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The WIDE exact l0 search: the problems,
+ * arguments, outputs and argument errors of slm_solve_l0 and slm_solve_l0_profile for up to 128 columns and 128 groups
+ * (SLM_ERR_UNSUPPORTED beyond, with a message that names 128, and on row-sharded datasets), on the kernel's wide
+ * instantiations (csrc/l0_kernels.hpp, template parameter WIDE).  Both run the wide kernel at ANY admissible size, narrow ones
+ * included; a problem within slm_solve_l0's limits gives the same coefficients, support and objective, bit for bit, on either.
+ * Every mask is two 64-bit words, the low one first (bit g of the 128-bit integer): need holds 2 words per group,
+ * support_out 2 words (the profile: 2 per size, all ones in both on an entry nobody filled).  There is no wide l1 mode.
+ * Capacity: the Cholesky factor keeps 64 rows, so a support holds at most 64 INDEPENDENT columns (columns that depend on
+ * the included ones are skipped as always and do not count).  An include that would bring a 65th is refused and its subtree
+ * is not searched.  With c_min the smallest number of groups held where that happened, every support left out has at least
+ * c_min + 1 groups and a quadratic value >= q_all, so its objective is at least q_all + alpha (c_min + 1).
+ * slm_solve_l0_wide: when no include was refused nothing differs from slm_solve_l0.  Otherwise *lower_bound_out =
+ * min(objective, q_all + alpha (c_min + 1)) -- and q_all when the node budget ran out, as before -- and the call is proven
+ * optimal (SLM_OK) iff the search finished and objective <= q_all + alpha (c_min + 1); if not it returns
+ * SLM_ERR_NOT_CONVERGED with valid outputs, like an exhausted budget.  info->rejects = c_min + 1, or 0 when no include was
+ * refused; info->resid = 1 when the node budget ran out, else 0; the other fields as for slm_solve_l0.  The greedy seed only
+ * takes groups that fit the 64 rows.
+ * slm_solve_l0_profile_wide: lane k - 1 keeps size k, so max_groups <= 64; and there is no dynamic rule -- the call is
+ * refused with SLM_ERR_UNSUPPORTED (the message names 64) when the max_groups largest groups together hold more than 64
+ * columns, so that no include can be refused and the table keeps its meaning.
+ */
+int slm_solve_l0_wide(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T /* p*p or NULL */,
+                      double big_M, const uint64_t* need /* 2 words per group, low word first, or NULL */,
+                      int64_t max_nodes /* <=0: default */, double* beta_out, uint64_t* support_out /* [2] */,
+                      double* lower_bound_out, int64_t* nodes_out, slm_point_info* info);
+int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T /* p*p or NULL */,
+                              double big_M, const uint64_t* need /* 2 words per group, low word first, or NULL */,
+                              int64_t max_nodes /* <=0: default */, double* beta_out /* [(max_groups+1)*p] */,
+                              uint64_t* support_out /* [(max_groups+1)*2] */, double* value_out /* [max_groups+1] */,
+                              int64_t* nodes_out, slm_point_info* info);
+
+/*
  * The Gram of a row set, for covariance passes (SLM_FLAG_COVARIANCE): G = X^T W X / n_eff, c = X^T W y / n_eff and
  * y^T W y / n_eff, kept with the dataset (8 ld^2 bytes each) and found again by a fingerprint of the row weights and
  * n_eff -- what a lane of slm_solve_lanes brings as (row_weight, n_eff).  row_weight: length n on the host, NULL = the

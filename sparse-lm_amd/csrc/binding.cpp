@@ -384,6 +384,64 @@ py::tuple solve_l0_profile(uintptr_t ds, int64_t p, double alpha_min, int32_t ma
   return py::make_tuple(beta, support, value, nodes, info, rc);
 }
 
+// The need masks of the wide entries: n_groups x 2 words (the low one first), or None.
+const uint64_t* need_words(const py::object& need, py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& hold) {
+  if (need.is_none()) return nullptr;
+  hold = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
+  if (!hold) throw py::value_error("need is not convertible to uint64");
+  return hold.data();
+}
+
+// slm_solve_l0_wide: the tuple of solve_l0 with the support as an array of two words (the low one first).
+py::tuple solve_l0_wide(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
+                        const py::object& need, int64_t max_nodes) {
+  Keep keep;
+  const double* Tp = vector_arg(T, p * p, "T", keep);
+  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
+  py::array_t<double> beta((py::ssize_t)p);
+  py::array_t<uint64_t> support(2);
+  support.mutable_data()[0] = support.mutable_data()[1] = 0;
+  py::array info = info_bytes(1);
+  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
+  double lower = 0.0;
+  int64_t nodes = 0;
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_wide(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
+                           support.mutable_data(), &lower, &nodes, static_cast<slm_point_info*>(info.mutable_data()));
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, support, lower, nodes, info, rc);
+}
+
+// slm_solve_l0_profile_wide: the tuple of solve_l0_profile with the supports as [max_groups + 1][2] words.
+py::tuple solve_l0_profile_wide(uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta, const py::object& T,
+                                double big_M, const py::object& need, int64_t max_nodes) {
+  if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
+  Keep keep;
+  const double* Tp = vector_arg(T, p * p, "T", keep);
+  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
+  const py::ssize_t rows = (py::ssize_t)max_groups + 1;
+  py::array_t<double> beta({rows, (py::ssize_t)p});
+  py::array_t<uint64_t> support({rows, (py::ssize_t)2});
+  py::array_t<double> value(rows);
+  py::array info = info_bytes(1);
+  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
+  int64_t nodes = 0;
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_profile_wide(reinterpret_cast<slm_dataset*>(ds), alpha_min, max_groups, eta, Tp, big_M, needp, max_nodes,
+                                   beta.mutable_data(), support.mutable_data(), value.mutable_data(), &nodes,
+                                   static_cast<slm_point_info*>(info.mutable_data()));
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, support, value, nodes, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -401,6 +459,8 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0", &solve_l0);
   m.def("solve_l0_l1", &solve_l0_l1);
   m.def("solve_l0_profile", &solve_l0_profile);
+  m.def("solve_l0_wide", &solve_l0_wide);
+  m.def("solve_l0_profile_wide", &solve_l0_profile_wide);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

@@ -1,12 +1,15 @@
 // Host side of the MI355X fit engine, sixth unit: the exact l0 estimators (csrc/l0_kernels.hpp) -- the reference's
 // mixed-integer family (reference src/sparselm/model/_miqp/_best_subset.py, _regularized_l0.py), which it hands to
 // Gurobi or SCIP through cvxpy.  Here: the dataset's own Gram (engine_cov.hip), the search order, the greedy seed and the
-// unconstrained bound on the host (p <= 64: microseconds), ONE launch of the search, and the winner's coefficients
+// unconstrained bound on the host (p <= 128: microseconds), ONE launch of the search, and the winner's coefficients
 // recomputed in one place from the Gram on its support.
 // slm_solve_l0_l1 (the reference's L1L0, _regularized_l0.py:258-410) is the same call in l1 mode: the kernel's L1 instantiation,
 // the l0_l1_* functions of l0_host.hpp for seed, winner and the dual bound on all columns.
 // slm_solve_l0_profile is the same search in profile mode (the kernel's PROFILE instantiation): the best support of every size
 // up to max_groups from one launch, seeded per size by the same greedy selection, each size's coefficients recomputed here.
+// slm_solve_l0_wide and slm_solve_l0_profile_wide are the same two calls on the kernel's WIDE instantiations: up to 128 columns
+// and groups, masks of two words, a support of at most 64 independent columns (the capacity rule of l0_host.hpp).  One
+// template over WIDE serves both widths; with WIDE = false it is the code there was before.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -17,25 +20,35 @@ constexpr long long kL0DefaultNodes = 1ll << 30;  // the budget of a call that n
                                                   // (profiles/l0_search.txt) a call that exhausts it stays under two seconds
 
 // The argument checks both searches share, before anything touches the device.  alpha_name: what the l0 weight is called in
-// the entry's own signature.  Leaves p and the group count.
+// the entry's own signature.  Leaves p and the group count.  pmax: L0_PMAX, or L0_WIDE_PMAX for the wide entries (need then
+// holds two words per group, the low one first).
 int l0_check_args(slm_dataset* ds, const void* out, double alpha, const char* alpha_name, double eta, double eta_l1, double big_M,
-                  const double* T, const uint64_t* need, int* p_out, int* ng_out) {
+                  const double* T, const uint64_t* need, int* p_out, int* ng_out, int pmax = L0_PMAX) {
   if (!ds || !out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(SLM_ERR_BAD_ARG, "%s must be finite and >= 0", alpha_name);
   if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(SLM_ERR_BAD_ARG, "eta must be finite and >= 0");
   if (!(eta_l1 >= 0.0) || !std::isfinite(eta_l1)) return fail(SLM_ERR_BAD_ARG, "eta_l1 must be finite and >= 0");
   if (!(big_M >= 0.0)) return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
   const int64_t p64 = ds->p;
-  const int ng = ds->singleton ? (int)std::min<int64_t>(p64, L0_PMAX + 1) : ds->G;
-  if (need && ng <= L0_PMAX)
+  const int ng = ds->singleton ? (int)std::min<int64_t>(p64, pmax + 1) : ds->G;
+  if (need && ng <= pmax && pmax == L0_PMAX)
     for (int g = 0; g < ng; ++g)
       if (ng < 64 && (need[g] >> ng) != 0) return fail(SLM_ERR_BAD_ARG, "need[%d] names a group at or beyond n_groups = %d", g, ng);
+  if (need && ng <= pmax && pmax != L0_PMAX)
+    for (int g = 0; g < ng; ++g) {
+      const L0Mask128 mk{need[2 * g], need[2 * g + 1]}, below = l0m_below<L0Mask128>(ng);
+      if (l0m_any_outside(mk, below)) return fail(SLM_ERR_BAD_ARG, "need[%d] names a group at or beyond n_groups = %d", g, ng);
+    }
   if (T)
-    for (int64_t e = 0; e < p64 * p64 && p64 <= L0_PMAX; ++e)
+    for (int64_t e = 0; e < p64 * p64 && p64 <= pmax; ++e)
       if (!std::isfinite(T[e])) return fail(SLM_ERR_BAD_ARG, "T contains a non-finite value");
-  if (p64 > L0_PMAX || ng > L0_PMAX)
+  if (p64 > pmax || ng > pmax) {
+    if (pmax != L0_PMAX)
+      return fail(SLM_ERR_UNSUPPORTED, "the wide exact l0 search takes up to %d columns and %d groups (got %lld, %d)", pmax, pmax,
+                  (long long)p64, ng);
     return fail(SLM_ERR_UNSUPPORTED, "the exact l0 search takes up to %d columns and %d groups (got %lld, %d)", L0_PMAX, L0_PMAX,
                 (long long)p64, ng);
+  }
   if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "the exact l0 search is not built for row-sharded datasets");
   *p_out = (int)p64;
   *ng_out = ng;
@@ -44,14 +57,22 @@ int l0_check_args(slm_dataset* ds, const void* out, double alpha, const char* al
 
 // What both searches work on: the dataset's Gram on the host, the search order, H = G + 2 eta T and c in that order, the
 // hierarchy in that order, and the unconstrained value on all columns.
-struct L0Problem {
+// (Mask: one word, or the wide mode's two.)
+template <class Mask>
+struct L0ProblemT {
   std::vector<double> G, cvec, H, c;  // G, cvec: the dataset's order; H, c: search order
   std::vector<int> cols, gstart, gorder;
-  std::vector<unsigned long long> needo;
+  std::vector<Mask> needo;
   double q_all = 0.0, yy = 0.0;
 };
+using L0Problem = L0ProblemT<unsigned long long>;
 
-int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, const uint64_t* need, L0Problem& P) {
+// need[g] of the caller (the dataset's group order) as a mask
+inline unsigned long long l0_need_of(const uint64_t* need, int g, unsigned long long) { return need[g]; }
+inline L0Mask128 l0_need_of(const uint64_t* need, int g, L0Mask128) { return L0Mask128{need[2 * g], need[2 * g + 1]}; }
+
+template <class Mask>
+int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, const uint64_t* need, L0ProblemT<Mask>& P) {
   slm_engine* eng = ds->eng;
   HIP_TRY(hipSetDevice(eng->device));
   hipStream_t s = eng->stream;
@@ -111,19 +132,15 @@ int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, cons
       H[(size_t)i * p + j] = G[(size_t)ci * p + cj] + 2.0 * eta * t;
     }
   }
-  std::vector<unsigned long long>& needo = P.needo;
-  needo.assign((size_t)ng, 0ull);
+  std::vector<Mask>& needo = P.needo;
+  needo.assign((size_t)ng, l0m_none<Mask>());
   if (need)
     for (int g = 0; g < ng; ++g)
       for (int h = 0; h < ng; ++h)
-        if (h != g && ((need[g] >> h) & 1)) needo[(size_t)gpos[(size_t)g]] |= 1ull << gpos[(size_t)h];
+        if (h != g && l0m_test(l0_need_of(need, g, Mask{}), h)) l0m_set(needo[(size_t)gpos[(size_t)g]], gpos[(size_t)h]);
 
   // ---- the unconstrained value on all columns ------------------------------------------------------------------------------
-  {
-    L0Factor f(H.data(), c.data(), p);
-    for (int j = 0; j < p; ++j) (void)f.push(j);
-    P.q_all = -0.5 * f.ss;
-  }
+  P.q_all = l0_q_all(H.data(), c.data(), p);
   P.yy = ds->cov[(size_t)entry].yy;
   return SLM_OK;
 }
@@ -138,62 +155,35 @@ struct L0DevGuard {
   }
 };
 
-// Greedy forward selection over the groups, up to K of them: one admissible support per size, handed to visit(size, support,
-// value) with the value value_of(support) gives it (the kernel's own valuation, no alpha term); and, when K reaches the group
-// count, the support of every group -- the one whose value can meet the bound q_all exactly.
-template <class ValueOf, class Visit>
-void l0_greedy(const L0Problem& P, int p, int ng, int K, ValueOf value_of, Visit visit) {
-  const std::vector<int>& gstart = P.gstart;
-  const std::vector<unsigned long long>& needo = P.needo;
-  L0Factor f(P.H.data(), P.c.data(), p);
-  unsigned long long cur = 0;
-  for (int step = 0; step < K; ++step) {
-    int pick = -1;
-    double pick_ss = f.ss;
-    const int m0 = f.m;
-    for (int g = 0; g < ng; ++g) {
-      if (((cur >> g) & 1) || (needo[(size_t)g] & ~cur)) continue;
-      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) (void)f.push(j);  // (dependent columns are skipped, as in the kernel)
-      if (f.ss > pick_ss) {
-        pick_ss = f.ss;
-        pick = g;
-      }
-      f.pop_to(m0);
-    }
-    if (pick < 0) break;
-    cur |= 1ull << pick;
-    // (the factor keeps search order inside the kernel; the seed's value is taken the same way)
-    visit(step + 1, cur, value_of(cur));
-    for (int j = gstart[(size_t)pick]; j < gstart[(size_t)pick + 1]; ++j) (void)f.push(j);
-  }
-  if (K >= ng && ng > 0) {
-    const unsigned long long all_mask = ng == 64 ? ~0ull : ((1ull << ng) - 1);
-    visit(ng, all_mask, value_of(all_mask));
-  }
-}
-
 // Both entries.  eta_l1 > 0 is l1 mode (the kernel's L1 instantiation, the l0_l1_* functions of l0_host.hpp); eta_l1 == 0 is the
 // search without an l1 term, instruction for instruction what it was before there was one.
+// WIDE: the kernel's wide instantiation (no l1 mode there), masks of two words in need, support_out and on the device.
+template <bool WIDE>
 int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double eta_l1, double big_M,
                   const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* lower_bound_out,
                   int64_t* nodes_out, slm_point_info* info) {
+  using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
+  constexpr size_t MW = WIDE ? 2 : 1;  // words per mask
   int p = 0, ng = 0;
-  SLM_TRY(l0_check_args(ds, beta_out, alpha, "alpha", eta, eta_l1, big_M, T, need, &p, &ng));
-  const bool l1 = eta_l1 > 0.0;
+  SLM_TRY(l0_check_args(ds, beta_out, alpha, "alpha", eta, eta_l1, big_M, T, need, &p, &ng, WIDE ? L0_WIDE_PMAX : L0_PMAX));
+  const bool l1 = !WIDE && eta_l1 > 0.0;
   const int K = max_groups < 0 ? 0 : std::min<int>(max_groups, ng);
   // the value (without alpha |S|) and coefficients of one support, as the kernel values a node
-  auto value_of = [&](const std::vector<double>& H, const std::vector<double>& c, const std::vector<int>& gstart, unsigned long long mask,
-                      bool polish, double* beta) {
-    return l1 ? l0_l1_support(H.data(), c.data(), p, gstart, mask, eta_l1, big_M, polish, beta)
-              : l0_support(H.data(), c.data(), p, gstart, mask, big_M, polish, beta);
+  auto value_of = [&](const std::vector<double>& H, const std::vector<double>& c, const std::vector<int>& gstart, Mask mask, bool polish,
+                      double* beta) {
+    if constexpr (WIDE)
+      return l0_support_of(H.data(), c.data(), p, gstart, mask, big_M, polish, beta);
+    else
+      return l1 ? l0_l1_support(H.data(), c.data(), p, gstart, mask, eta_l1, big_M, polish, beta)
+                : l0_support(H.data(), c.data(), p, gstart, mask, big_M, polish, beta);
   };
-  L0Problem P;
+  L0ProblemT<Mask> P;
   SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, P));
   slm_engine* eng = ds->eng;
   hipStream_t s = eng->stream;
   const std::vector<double>&G = P.G, &cvec = P.cvec, &H = P.H, &c = P.c;
   const std::vector<int>&cols = P.cols, &gstart = P.gstart, &gorder = P.gorder;
-  const std::vector<unsigned long long>& needo = P.needo;
+  const std::vector<Mask>& needo = P.needo;
   const double q_all = P.q_all;
 
   // ---- the greedy seed of the incumbent ------------------------------------------------------------------------------------
@@ -201,9 +191,9 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   // the subtree bound's lower bound on the value of all columns: in l1 mode the lasso dual value where it is above q_all
   const double bound = l1 ? l0_l1_lower_bound(H.data(), c.data(), p, P.yy, eta_l1, q_all) : q_all;
   double seed_val = 0.0;  // the empty support
-  unsigned long long seed_mask = 0;
-  l0_greedy(P, p, ng, K, [&](unsigned long long mask) { return value_of(H, c, gstart, mask, false, beta_s.data()); },
-            [&](int size, unsigned long long mask, double quad) {
+  Mask seed_mask = l0m_none<Mask>();
+  l0_greedy(H.data(), c.data(), p, gstart, needo, K, [&](Mask mask) { return value_of(H, c, gstart, mask, false, beta_s.data()); },
+            [&](int size, Mask mask, double quad) {
               const double v = quad + alpha * (double)size;
               if (v < seed_val) {
                 seed_val = v;
@@ -216,14 +206,16 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   const long long n_tickets = 1ll << d;
   const int blocks = (int)std::max<long long>(1, std::min<long long>(2ll * eng->cus, (n_tickets + L0_WAVES - 1) / L0_WAVES));
   const int waves = blocks * L0_WAVES;
-  // one block of 8-byte words: control | best values | best supports | H | c | need | group starts
-  const size_t off_bv = L0_CTL_WORDS, off_bm = off_bv + (size_t)waves, off_H = off_bm + (size_t)waves, off_c = off_H + (size_t)p * p,
-               off_need = off_c + (size_t)p, off_gs = off_need + (size_t)ng, words = off_gs + (size_t)ng + 1;
+  // one block of 8-byte words: control | best values | best supports | H | c | need | group starts (a mask: MW words)
+  const size_t off_bv = L0_CTL_WORDS, off_bm = off_bv + (size_t)waves, off_H = off_bm + MW * (size_t)waves, off_c = off_H + (size_t)p * p,
+               off_need = off_c + (size_t)p, off_gs = off_need + MW * (size_t)ng, words = off_gs + (size_t)ng + 1;
   std::vector<unsigned long long> h(words, 0ull);
   h[L0_INCUMBENT] = l0_key(seed_val);
+  if constexpr (WIDE) h[L0_CAPACITY] = ~0ull;  // (lowered by a wave that refused an include for capacity)
   memcpy(&h[off_H], H.data(), sizeof(double) * (size_t)p * p);
   memcpy(&h[off_c], c.data(), sizeof(double) * (size_t)p);
-  for (int g = 0; g < ng; ++g) h[off_need + (size_t)g] = needo[(size_t)g];
+  static_assert(sizeof(Mask) == MW * sizeof(unsigned long long), "a mask is MW words, the low one first");
+  if (ng > 0) memcpy(&h[off_need], needo.data(), sizeof(Mask) * (size_t)ng);
   for (int g = 0; g <= ng; ++g) h[off_gs + (size_t)g] = (unsigned long long)gstart[(size_t)g];
   unsigned long long* dev = nullptr;
   SLM_TRY(dalloc(&dev, words));
@@ -242,7 +234,9 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   k.alpha = alpha; k.big_M = big_M; k.q_all = bound;
   k.eta_l1 = eta_l1;
   k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
-  if (l1)
+  if constexpr (WIDE)
+    hipLaunchKernelGGL((l0_search_kernel<false, false, true>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  else if (l1)
     hipLaunchKernelGGL(l0_search_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
   else
     hipLaunchKernelGGL(l0_search_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
@@ -252,12 +246,13 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
 
   // ---- the winner: the waves' bests and the seed in a fixed order, the lower support on a bitwise tie -------------------------
   double win_val = seed_val;
-  unsigned long long win_mask = seed_mask;
+  Mask win_mask = seed_mask;
   for (int wv = 0; wv < waves; ++wv) {
     double v;
     memcpy(&v, &h[off_bv + (size_t)wv], 8);
-    const unsigned long long mk = h[off_bm + (size_t)wv];
-    if (v < win_val || (v == win_val && mk < win_mask)) {
+    Mask mk;
+    memcpy(&mk, &h[off_bm + MW * (size_t)wv], sizeof(Mask));
+    if (v < win_val || (v == win_val && l0m_less(mk, win_mask))) {
       win_val = v;
       win_mask = mk;
     }
@@ -266,16 +261,21 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   // its coefficients, recomputed here whichever wave found it
   const double quad = value_of(H, c, gstart, win_mask, true, beta_s.data());
   int n_active = 0;
-  unsigned long long support = 0;
+  Mask support = l0m_none<Mask>();
   for (int g = 0; g < ng; ++g)
-    if ((win_mask >> g) & 1) {
+    if (l0m_test(win_mask, g)) {
       ++n_active;
-      support |= 1ull << gorder[(size_t)g];
+      l0m_set(support, gorder[(size_t)g]);
     }
   const double objective = quad + alpha * (double)n_active;
   for (int i = 0; i < p; ++i) beta_out[cols[(size_t)i]] = beta_s[(size_t)i];
-  if (support_out) *support_out = support;
-  if (lower_bound_out) *lower_bound_out = finished ? objective : std::min(objective, bound);
+  if (support_out) memcpy(support_out, &support, sizeof(Mask));
+  // wide: c_min + 1 of the capacity rule (l0_host.hpp), 0 when no include was refused because the factor was full
+  const int cut = WIDE && h[L0_CAPACITY] != ~0ull ? (int)h[L0_CAPACITY] : 0;
+  const bool proven = finished && l0_capacity_proven(objective, q_all, alpha, cut);
+  double lower = finished ? objective : std::min(objective, bound);
+  if (cut) lower = std::min(lower, l0_capacity_bound(q_all, alpha, cut));
+  if (lower_bound_out) *lower_bound_out = lower;
   if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
   if (info) {
     // 1/(2n)||X beta - y||_W^2 = 1/2 beta^T G beta - c^T beta + 1/2 y^T W y / n from the Gram already on the host: no second launch
@@ -288,33 +288,57 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
     }
     memset(info, 0, sizeof(*info));
     info->n_iter = 1;
-    info->status = finished ? SLM_OK : SLM_ERR_NOT_CONVERGED;
+    info->status = proven ? SLM_OK : SLM_ERR_NOT_CONVERGED;
     info->loss = loss;
     info->mode = 4;
     info->kkt = objective;
     info->mu = seed_val;
     info->L = bound;
     info->rejects = (int32_t)std::min<unsigned long long>(h[L0_DESCENTS], 0x7fffffffull);  // (l1 mode: descents run)
+    if constexpr (WIDE) {
+      info->rejects = cut;                   // (c_min + 1, or 0)
+      info->resid = finished ? 0.0 : 1.0;  // (1: the node budget ran out -- what tells it from a result unproven for capacity alone)
+    }
     double bn = 0.0;
     for (int j = 0; j < p; ++j) bn += beta_out[j] * beta_out[j];
     info->beta_norm = std::sqrt(bn);
   }
   if (!finished) return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld) ran out before the search finished: the incumbent is returned",
                              (long long)k.max_nodes);
+  if (!proven)
+    return fail(SLM_ERR_NOT_CONVERGED, "a support holds at most %d independent columns: includes were refused from %d groups on, and the "
+                "incumbent is above the bound %.17g on what lies behind them", L0_PMAX, cut - 1, l0_capacity_bound(q_all, alpha, cut));
   return SLM_OK;
 }
 
 // slm_solve_l0_profile: the kernel's PROFILE instantiation.  Seeds per size from the greedy selection, one launch, then per size
 // the minimum over the waves' bests and the seed in a fixed order and the coefficients recomputed from H on that support.
+// WIDE: the kernel's wide profile instantiation; lane k - 1 still holds size k, and no include may be refused for capacity, so
+// a call whose max_groups largest groups could hold more than L0_PMAX columns is refused before anything is launched.
+template <bool WIDE>
 int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
                           const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
                           int64_t* nodes_out, slm_point_info* info) {
+  using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
+  constexpr size_t MW = WIDE ? 2 : 1;  // words per mask
   int p = 0, ng = 0;
   if (!support_out || !value_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  SLM_TRY(l0_check_args(ds, beta_out, alpha_min, "alpha_min", eta, 0.0, big_M, T, need, &p, &ng));
+  SLM_TRY(l0_check_args(ds, beta_out, alpha_min, "alpha_min", eta, 0.0, big_M, T, need, &p, &ng, WIDE ? L0_WIDE_PMAX : L0_PMAX));
   const int rows = max_groups < 0 ? 0 : (int)max_groups;  // the outputs have rows + 1 entries; sizes above the group count stay unfilled
   const int K = std::min(rows, ng);
-  L0Problem P;
+  if constexpr (WIDE) {
+    if (K > L0_PMAX)
+      return fail(SLM_ERR_UNSUPPORTED, "the wide l0 profile keeps one size per lane: max_groups up to %d (got %d)", L0_PMAX, K);
+    std::vector<int> width((size_t)ng, 0);
+    for (int j = 0; j < p; ++j) ++width[(size_t)(ds->h_gid.empty() ? j : ds->h_gid[(size_t)j])];
+    std::sort(width.begin(), width.end(), [](int x, int y) { return x > y; });
+    int most = 0;
+    for (int k = 0; k < K; ++k) most += width[(size_t)k];
+    if (most > L0_PMAX)
+      return fail(SLM_ERR_UNSUPPORTED, "the wide l0 profile needs every support to fit the factor: the %d largest groups hold %d columns, "
+                  "more than %d", K, most, L0_PMAX);
+  }
+  L0ProblemT<Mask> P;
   SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, P));
   slm_engine* eng = ds->eng;
   hipStream_t s = eng->stream;
@@ -323,12 +347,13 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
   // ---- the seed of every size: the supports the greedy selection passes through, valued as the kernel values a node ---------
   std::vector<double> beta_s((size_t)p);
   std::vector<double> win_val((size_t)L0_PMAX + 1, HUGE_VAL);
-  std::vector<unsigned long long> win_mask((size_t)L0_PMAX + 1, ~0ull);
+  std::vector<Mask> win_mask((size_t)L0_PMAX + 1, l0m_ones<Mask>());
   win_val[0] = 0.0;  // the empty support
-  win_mask[0] = 0ull;
-  l0_greedy(P, p, ng, K, [&](unsigned long long mask) { return l0_support(H.data(), c.data(), p, P.gstart, mask, big_M, false, beta_s.data()); },
-            [&](int size, unsigned long long mask, double quad) {
-              if (quad < win_val[(size_t)size] || (quad == win_val[(size_t)size] && mask < win_mask[(size_t)size])) {
+  win_mask[0] = l0m_none<Mask>();
+  l0_greedy(H.data(), c.data(), p, P.gstart, P.needo, K,
+            [&](Mask mask) { return l0_support_of(H.data(), c.data(), p, P.gstart, mask, big_M, false, beta_s.data()); },
+            [&](int size, Mask mask, double quad) {
+              if (quad < win_val[(size_t)size] || (quad == win_val[(size_t)size] && l0m_less(mask, win_mask[(size_t)size]))) {
                 win_val[(size_t)size] = quad;
                 win_mask[(size_t)size] = mask;
               }
@@ -340,13 +365,16 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
   const int blocks = (int)std::max<long long>(1, std::min<long long>(2ll * eng->cus, (n_tickets + L0_WAVES - 1) / L0_WAVES));
   const int waves = blocks * L0_WAVES;
   // one block of 8-byte words: control | incumbents per size | best values [waves][64] | best supports [waves][64] | H | c | need | group starts
-  const size_t off_bv = L0_PROFILE_WORDS, off_bm = off_bv + (size_t)waves * 64, off_H = off_bm + (size_t)waves * 64,
-               off_c = off_H + (size_t)p * p, off_need = off_c + (size_t)p, off_gs = off_need + (size_t)ng, words = off_gs + (size_t)ng + 1;
+  // (a mask: MW words)
+  const size_t off_bv = L0_PROFILE_WORDS, off_bm = off_bv + (size_t)waves * 64, off_H = off_bm + MW * (size_t)waves * 64,
+               off_c = off_H + (size_t)p * p, off_need = off_c + (size_t)p, off_gs = off_need + MW * (size_t)ng, words = off_gs + (size_t)ng + 1;
   std::vector<unsigned long long> h(words, 0ull);
   for (int k = 1; k <= L0_PMAX; ++k) h[(size_t)L0_PROFILE_INC + (size_t)k - 1] = l0_key(win_val[(size_t)k]);
   memcpy(&h[off_H], H.data(), sizeof(double) * (size_t)p * p);
   memcpy(&h[off_c], c.data(), sizeof(double) * (size_t)p);
-  for (int g = 0; g < ng; ++g) h[off_need + (size_t)g] = P.needo[(size_t)g];
+  if constexpr (WIDE) h[L0_CAPACITY] = ~0ull;
+  static_assert(sizeof(Mask) == MW * sizeof(unsigned long long), "a mask is MW words, the low one first");
+  if (ng > 0) memcpy(&h[off_need], P.needo.data(), sizeof(Mask) * (size_t)ng);
   for (int g = 0; g <= ng; ++g) h[off_gs + (size_t)g] = (unsigned long long)P.gstart[(size_t)g];
   unsigned long long* dev = nullptr;
   SLM_TRY(dalloc(&dev, words));
@@ -364,7 +392,7 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
   k.p = p; k.ng = ng; k.d = d; k.K = K;
   k.alpha = alpha_min; k.big_M = big_M; k.q_all = P.q_all;
   k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
-  hipLaunchKernelGGL((l0_search_kernel<false, true>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  hipLaunchKernelGGL((l0_search_kernel<false, true, WIDE>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
   SLM_TRY(check_launch());
   HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(unsigned long long) * off_H, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -374,26 +402,29 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
     for (int wv = 0; wv < waves; ++wv) {
       double v;
       memcpy(&v, &h[off_bv + (size_t)wv * 64 + (size_t)size - 1], 8);
-      const unsigned long long mk = h[off_bm + (size_t)wv * 64 + (size_t)size - 1];
-      if (v < win_val[(size_t)size] || (v == win_val[(size_t)size] && mk < win_mask[(size_t)size])) {
+      Mask mk;
+      memcpy(&mk, &h[off_bm + MW * ((size_t)wv * 64 + (size_t)size - 1)], sizeof(Mask));
+      if (v < win_val[(size_t)size] || (v == win_val[(size_t)size] && l0m_less(mk, win_mask[(size_t)size]))) {
         win_val[(size_t)size] = v;
         win_mask[(size_t)size] = mk;
       }
     }
   const bool finished = h[L0_ABORTED] == 0;
+  if (WIDE && h[L0_CAPACITY] != ~0ull) return fail(SLM_ERR_HIP, "the wide l0 profile refused an include for capacity (internal error)");
   // the coefficients of every size, recomputed here whichever wave found its support; a size nobody filled: +inf, all ones, zeros
   for (int size = 0; size <= rows; ++size) {
     double* beta = beta_out + (size_t)size * p;
     for (int i = 0; i < p; ++i) beta[i] = 0.0;
     const bool filled = size <= K && std::isfinite(win_val[(size_t)size]);
     value_out[size] = HUGE_VAL;
-    support_out[size] = ~0ull;
+    Mask support = l0m_ones<Mask>();
+    memcpy(support_out + MW * (size_t)size, &support, sizeof(Mask));
     if (!filled) continue;
-    value_out[size] = l0_support(H.data(), c.data(), p, P.gstart, win_mask[(size_t)size], big_M, true, beta_s.data());
-    unsigned long long support = 0;
+    value_out[size] = l0_support_of(H.data(), c.data(), p, P.gstart, win_mask[(size_t)size], big_M, true, beta_s.data());
+    support = l0m_none<Mask>();
     for (int g = 0; g < ng; ++g)
-      if ((win_mask[(size_t)size] >> g) & 1) support |= 1ull << P.gorder[(size_t)g];
-    support_out[size] = support;
+      if (l0m_test(win_mask[(size_t)size], g)) l0m_set(support, P.gorder[(size_t)g]);
+    memcpy(support_out + MW * (size_t)size, &support, sizeof(Mask));
     for (int i = 0; i < p; ++i) beta[P.cols[(size_t)i]] = beta_s[(size_t)i];
   }
   if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
@@ -417,14 +448,21 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
 extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
                             const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
                             double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
-  return solve_l0_impl(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out, info);
+  return solve_l0_impl<false>(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out, info);
+}
+
+// The same search on the kernel's wide instantiation: up to 128 columns and groups, masks of two words (the low one first).
+extern "C" int slm_solve_l0_wide(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
+                                 const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
+                                 double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_impl<true>(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out, info);
 }
 
 // The reference's L1L0 (_regularized_l0.py:258-410): no cardinality bound, no ridge term, eta_l1 ||beta||_1.
 extern "C" int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, double big_M, const uint64_t* need, int64_t max_nodes,
                                double* beta_out, uint64_t* support_out, double* lower_bound_out, int64_t* nodes_out,
                                slm_point_info* info) {
-  return solve_l0_impl(ds, alpha, L0_PMAX, 0.0, nullptr, eta_l1, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out,
+  return solve_l0_impl<false>(ds, alpha, L0_PMAX, 0.0, nullptr, eta_l1, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out,
                        info);
 }
 
@@ -432,5 +470,12 @@ extern "C" int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, dou
 extern "C" int slm_solve_l0_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
                                     const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
                                     int64_t* nodes_out, slm_point_info* info) {
-  return solve_l0_profile_impl(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
+  return solve_l0_profile_impl<false>(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
+}
+
+// The profile on the kernel's wide instantiation: masks of two words in need and support_out, max_groups up to 64.
+extern "C" int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
+                                         const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
+                                         double* value_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_profile_impl<true>(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
 }

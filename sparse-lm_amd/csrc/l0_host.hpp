@@ -3,34 +3,84 @@
 // value and coefficients of one support, the same for l1 mode (a lasso per support: the descent, its polish, the dual
 // bound on all columns), and for profile mode the pruning rule and the two questions its table answers.  Like host_logic.hpp and tail_logic.hpp it is free of HIP types so that g++
 // compiles it alone: tests/host_logic_test.cpp, tests/l1l0_host_test.cpp and tests/l0_profile_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 / slm_solve_l0_profile call
-// THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.
+// THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.  The wide mode
+// (slm_solve_l0_wide, slm_solve_l0_profile_wide; tests/l0_wide_host_test.cpp) adds masks of two words, a factor with a capacity
+// parameter and the capacity rule.
 #pragma once
 #include <stddef.h>
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 namespace slm {
 
-constexpr int L0_PMAX = 64;        // columns, and groups
+constexpr int L0_PMAX = 64;        // columns, and groups; in wide mode the rows of the factor (independent columns of a support)
+constexpr int L0_WIDE_PMAX = 128;  // columns, and groups, of the wide mode (slm_solve_l0_wide, slm_solve_l0_profile_wide)
 constexpr int L0_CD_SWEEPS = 10000;
 constexpr double L0_CD_TOL = 1e-12;
 constexpr double L0_PIVOT = 1e-12;
 
+// ---- supports as masks over the groups ----------------------------------------------------------------------------------------
+//
+// One 64-bit word up to 64 groups; the wide mode's two words, bit g of the 128-bit integer hi:lo.  One set of functions for
+// both (and for host and device: constexpr), so that the search, the seed and the winner are written once.  The order of
+// l0m_less is that of the 128-bit integer -- the high word first, then the low one: "the lower support wins a bitwise tie".
+struct L0Mask128 {
+  unsigned long long lo, hi;
+};
+constexpr unsigned long long l0m_low_word(int g) { return g <= 0 ? 0ull : (g >= 64 ? ~0ull : (~0ull >> (64 - g))); }
+template <class M> constexpr M l0m_none();
+template <> constexpr unsigned long long l0m_none<unsigned long long>() { return 0ull; }
+template <> constexpr L0Mask128 l0m_none<L0Mask128>() { return L0Mask128{0ull, 0ull}; }
+template <class M> constexpr M l0m_ones();
+template <> constexpr unsigned long long l0m_ones<unsigned long long>() { return ~0ull; }
+template <> constexpr L0Mask128 l0m_ones<L0Mask128>() { return L0Mask128{~0ull, ~0ull}; }
+template <class M> constexpr M l0m_below(int g);  // the bits 0 .. g - 1
+template <> constexpr unsigned long long l0m_below<unsigned long long>(int g) { return g == 0 ? 0ull : (~0ull >> (64 - g)); }
+template <> constexpr L0Mask128 l0m_below<L0Mask128>(int g) { return L0Mask128{l0m_low_word(g), l0m_low_word(g - 64)}; }
+constexpr bool l0m_test(unsigned long long a, int g) { return ((a >> g) & 1) != 0; }
+constexpr bool l0m_test(L0Mask128 a, int g) { return g < 64 ? ((a.lo >> g) & 1) != 0 : ((a.hi >> (g - 64)) & 1) != 0; }
+constexpr void l0m_set(unsigned long long& a, int g) { a |= 1ull << g; }
+constexpr void l0m_set(L0Mask128& a, int g) {
+  if (g < 64) a.lo |= 1ull << g;
+  else a.hi |= 1ull << (g - 64);
+}
+constexpr void l0m_clear(unsigned long long& a, int g) { a &= ~(1ull << g); }
+constexpr void l0m_clear(L0Mask128& a, int g) {
+  if (g < 64) a.lo &= ~(1ull << g);
+  else a.hi &= ~(1ull << (g - 64));
+}
+constexpr void l0m_or(unsigned long long& a, unsigned long long b) { a |= b; }
+constexpr void l0m_or(L0Mask128& a, L0Mask128 b) {
+  a.lo |= b.lo;
+  a.hi |= b.hi;
+}
+constexpr unsigned long long l0m_and(unsigned long long a, unsigned long long b) { return a & b; }
+constexpr L0Mask128 l0m_and(L0Mask128 a, L0Mask128 b) { return L0Mask128{a.lo & b.lo, a.hi & b.hi}; }
+constexpr bool l0m_any_outside(unsigned long long a, unsigned long long b) { return (a & ~b) != 0; }  // a holds a bit that b lacks
+constexpr bool l0m_any_outside(L0Mask128 a, L0Mask128 b) { return ((a.lo & ~b.lo) | (a.hi & ~b.hi)) != 0; }
+constexpr bool l0m_less(unsigned long long a, unsigned long long b) { return a < b; }
+constexpr bool l0m_less(L0Mask128 a, L0Mask128 b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+
 // The factor of H on a growing list of columns, as the kernel keeps it: L row by row, w = L^-1 c, value = -1/2 ||w||^2.
-struct L0Factor {
+// CAP rows.  An INDEPENDENT column that arrives when all CAP rows are taken is refused like a dependent one and sets
+// `overflow` (the wide mode's capacity rule; at p <= CAP it cannot happen).
+template <int CAP>
+struct L0FactorT {
   const double* H;
   const double* c;
   int p;
-  double L[L0_PMAX][L0_PMAX];
-  double w[L0_PMAX];
-  int col[L0_PMAX];
+  double L[CAP][CAP];
+  double w[CAP];
+  int col[CAP];
   int m = 0;
   double ss = 0.0;
-  L0Factor(const double* H_, const double* c_, int p_) : H(H_), c(c_), p(p_) {}
+  bool overflow = false;
+  L0FactorT(const double* H_, const double* c_, int p_) : H(H_), c(c_), p(p_) {}
   bool push(int j) {  // false: the column depends on the included ones (the kernel's pivot rule)
-    double x[L0_PMAX];
+    double x[CAP];
     double s2 = 0.0, sw = 0.0;
     for (int k = 0; k < m; ++k) {
       double b = H[(size_t)j * p + col[k]];
@@ -41,6 +91,10 @@ struct L0Factor {
     }
     const double hjj = H[(size_t)j * p + j], piv = hjj - s2;
     if (!(piv > L0_PIVOT * hjj)) return false;
+    if (m == CAP) {
+      overflow = true;
+      return false;
+    }
     for (int k = 0; k < m; ++k) L[m][k] = x[k];
     L[m][m] = std::sqrt(piv);
     w[m] = (c[j] - sw) / L[m][m];
@@ -51,6 +105,7 @@ struct L0Factor {
   }
   void pop_to(int m0) {
     m = m0;
+    overflow = false;
     ss = 0.0;
     for (int k = 0; k < m; ++k) ss += w[k] * w[k];
   }
@@ -62,6 +117,7 @@ struct L0Factor {
     }
   }
 };
+using L0Factor = L0FactorT<L0_PMAX>;
 
 // min 1/2 b^T H_S b - c_S^T b over |b_j| <= big_M on the columns `cols` (independent: they passed the pivot rule).
 // Cyclic coordinate descent with clipping, the kernel's own (same stopping rule): what candidates are COMPARED by, on both
@@ -146,13 +202,21 @@ inline double l0_boxed(const double* H, const double* c, int p, const int* cols,
 
 // The quadratic value and coefficients of the support `mask` (groups in search order), inside the box.  Columns that depend
 // on earlier ones of the support stay at zero.  beta: [p] in search order.
-inline double l0_support(const double* H, const double* c, int p, const std::vector<int>& gstart, unsigned long long mask, double big_M,
-                  bool polish, double* beta) {
+// (A template over the mask: the wide mode's supports draw their at most L0_PMAX independent columns from up to
+// L0_WIDE_PMAX; *overflow, when asked for, says that the support holds more independent columns than the factor has rows.)
+template <class Mask>
+inline double l0_support_of(const double* H, const double* c, int p, const std::vector<int>& gstart, Mask mask, double big_M, bool polish,
+                            double* beta, bool* overflow = nullptr) {
   L0Factor f(H, c, p);
   const int ng = (int)gstart.size() - 1;
+  bool over = false;
   for (int g = 0; g < ng; ++g)
-    if ((mask >> g) & 1)
-      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) (void)f.push(j);
+    if (l0m_test(mask, g))
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) {
+        (void)f.push(j);
+        over = over || f.overflow;
+      }
+  if (overflow) *overflow = over;
   for (int j = 0; j < p; ++j) beta[j] = 0.0;
   double b[L0_PMAX];
   f.solve(b);
@@ -162,6 +226,78 @@ inline double l0_support(const double* H, const double* c, int p, const std::vec
   if (outside) val = l0_boxed(H, c, p, f.col, f.m, big_M, polish, b);
   for (int k = 0; k < f.m; ++k) beta[f.col[k]] = b[k];
   return val;
+}
+inline double l0_support(const double* H, const double* c, int p, const std::vector<int>& gstart, unsigned long long mask, double big_M,
+                  bool polish, double* beta) {
+  return l0_support_of(H, c, p, gstart, mask, big_M, polish, beta);
+}
+
+// The unconstrained value on ALL columns, q_all of the subtree bound: a factor of up to L0_WIDE_PMAX rows, dependent columns
+// skipped by the pivot rule.  (On the heap: 128 KiB of factor.)
+inline double l0_q_all(const double* H, const double* c, int p) {
+  if (p <= L0_PMAX) {
+    L0Factor f(H, c, p);
+    for (int j = 0; j < p; ++j) (void)f.push(j);
+    return -0.5 * f.ss;
+  }
+  auto f = std::make_unique<L0FactorT<L0_WIDE_PMAX>>(H, c, p);
+  for (int j = 0; j < p; ++j) (void)f->push(j);
+  return -0.5 * f->ss;
+}
+
+// The wide mode's capacity rule (section "Capacity" of DESIGN 4d).  cut = c_min + 1, c_min the smallest number of groups
+// held where an include was refused because the factor was full; 0: none was.  Every support below such a refusal has at
+// least c_min + 1 groups and a quadratic value of at least q_all, so nothing unsearched is below q_all + alpha cut.
+constexpr double l0_capacity_bound(double q_all, double alpha, int cut) { return q_all + alpha * (double)cut; }
+constexpr bool l0_capacity_proven(double objective, double q_all, double alpha, int cut) {
+  return cut == 0 || objective <= l0_capacity_bound(q_all, alpha, cut);
+}
+
+// Greedy forward selection over the groups (H, c, gstart and the hierarchy needo in search order), up to K of them: one
+// admissible support per size, handed to visit(size, support, value) with the value value_of(support) gives it (the kernel's
+// own valuation, no alpha term); and, when K reaches the group count, the support of every group -- the one whose value can
+// meet the bound q_all exactly.
+// Wide mode: a group whose columns would not fit in the factor's L0_PMAX rows is no candidate, and the support of every group
+// is visited only when it fits.
+template <class Mask, class ValueOf, class Visit>
+void l0_greedy(const double* H, const double* c, int p, const std::vector<int>& gstart, const std::vector<Mask>& needo, int K,
+               ValueOf value_of, Visit visit) {
+  const int ng = (int)gstart.size() - 1;
+  L0Factor f(H, c, p);
+  Mask cur = l0m_none<Mask>();
+  for (int step = 0; step < K; ++step) {
+    int pick = -1;
+    double pick_ss = f.ss;
+    const int m0 = f.m;
+    for (int g = 0; g < ng; ++g) {
+      if (l0m_test(cur, g) || l0m_any_outside(needo[(size_t)g], cur)) continue;
+      bool fits = true;
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) {  // (dependent columns are skipped, as in the kernel)
+        (void)f.push(j);
+        fits = fits && !f.overflow;
+      }
+      if (fits && f.ss > pick_ss) {
+        pick_ss = f.ss;
+        pick = g;
+      }
+      f.pop_to(m0);
+    }
+    if (pick < 0) break;
+    l0m_set(cur, pick);
+    // (the factor keeps search order inside the kernel; the seed's value is taken the same way)
+    visit(step + 1, cur, value_of(cur));
+    for (int j = gstart[(size_t)pick]; j < gstart[(size_t)pick + 1]; ++j) (void)f.push(j);
+  }
+  if (K >= ng && ng > 0) {
+    const Mask all_mask = l0m_below<Mask>(ng);
+    f.pop_to(0);
+    bool fits = true;
+    for (int j = 0; j < p; ++j) {
+      (void)f.push(j);
+      fits = fits && !f.overflow;
+    }
+    if (fits) visit(ng, all_mask, value_of(all_mask));
+  }
 }
 
 // ---- profile mode (slm_solve_l0_profile): the best support of every size from one search ------------------------------------

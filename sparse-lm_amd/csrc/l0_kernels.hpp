@@ -50,9 +50,22 @@
 //     Qinc_k* + alpha k* <= q_all + alpha_min (cnt + 1) + (alpha - alpha_min) k* <= q(S') + alpha k'
 // -- S' is never strictly better than a support already held.  With alpha_min = 0 the cut fires only where a held support
 // has reached q_all, and the table is the full one.
+//
+// wide mode (template parameter WIDE, slm_solve_l0_wide / slm_solve_l0_profile_wide; never together with L1): up to
+// L0_WIDE_PMAX = 128 columns and groups.  The factor is indexed by inclusion position, not by column, so it keeps its 64 rows
+// and a support draws its at most 64 INDEPENDENT columns from any of the 128.  What differs, all under if constexpr (WIDE) or
+// behind the mask type: H sits in LDS as a packed lower triangle (row i at i (i + 1) / 2: 66 048 B at 128 columns, so two
+// workgroups still share a CU); every mask is two 64-bit words (L0Mask128 of l0_host.hpp, ordered as a 128-bit integer); lane
+// g & 63 holds the state before group g was decided in slot g >> 6, the slot picked by a wave-uniform branch.  Capacity: an
+// independent column that arrives when the factor holds 64 rows REFUSES its group's include -- the state is restored as for
+// any refused include and the exclude branch is taken.  The wave keeps the smallest cnt at which it refused one and lowers
+// the control word L0_CAPACITY with cnt + 1 on exit: every support below such a refusal has at least cnt + 1 groups and
+// q >= q_all, so nothing unsearched is below q_all + alpha (c_min + 1) -- the host proves optimality against that.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "l0_host.hpp"  // L0_PMAX, L0_CD_SWEEPS, L0_CD_TOL, L0_PIVOT: shared with the host side
 
@@ -62,7 +75,8 @@ constexpr int L0_WAVES = 4;        // wavefronts per workgroup (they share H in 
 constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
-constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CTL_WORDS = 8;
+constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CAPACITY = 6, L0_CTL_WORDS = 8;
+// (L0_CAPACITY, wide mode only: seeded with all ones, lowered to c_min + 1 by a wave that refused an include for capacity)
 // profile mode: the incumbents of the sizes 1 .. 64 (keys, seeded by the host) follow the control words
 constexpr int L0_PROFILE_INC = L0_CTL_WORDS, L0_PROFILE_WORDS = L0_CTL_WORDS + L0_PMAX;
 
@@ -70,10 +84,10 @@ struct L0Args {
   const double* H;                  // [p][p] G + 2 eta T, search order
   const double* c;                  // [p]
   const long long* gstart;          // [ng + 1] first column of each group
-  const unsigned long long* need;   // [ng] groups (search order) each group depends on
+  const unsigned long long* need;   // [ng] groups (search order) each group depends on; wide mode: [ng][2], low word first
   unsigned long long* ctl;          // [L0_CTL_WORDS]; profile mode: [L0_PROFILE_WORDS]
   double* best_val;                 // [waves of the grid]; profile mode: [waves][64], entry k - 1 for size k
-  unsigned long long* best_mask;    // [waves of the grid]; profile mode: [waves][64]
+  unsigned long long* best_mask;    // [waves of the grid]; profile mode: [waves][64]; wide mode: two words each, low word first
   int p, ng, d, K;
   double alpha, big_M, q_all;       // (q_all: the proven lower bound on the value of ALL columns the subtree bound uses;
                                     //  profile mode: alpha is alpha_min)
@@ -107,6 +121,7 @@ static __device__ __forceinline__ double l0_wave_sum(double v) {  // the same bi
 static __device__ __forceinline__ unsigned long long l0_bcast(unsigned long long v, int k) {
   return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), k) << 32) | (unsigned)__builtin_amdgcn_readlane((int)v, k);
 }
+static __device__ __forceinline__ L0Mask128 l0_bcast(L0Mask128 v, int k) { return L0Mask128{l0_bcast(v.lo, k), l0_bcast(v.hi, k)}; }
 static __device__ __forceinline__ double l0_wave_max(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
@@ -115,20 +130,44 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
 
 // L1 = false: the search above.  L1 = true: eta_l1 ||beta||_1 joins the objective (see the head of the file).
 // PROFILE = true: the best support of every size (see the head of the file); everything it adds sits under if constexpr.
-template <bool L1, bool PROFILE = false>
+// WIDE = true: up to 128 columns and groups (see the head of the file); what it adds sits under if constexpr or behind Mask.
+template <bool L1, bool PROFILE = false, bool WIDE = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
   static_assert(!(L1 && PROFILE), "the profile mode has no l1 term");
-  __shared__ double Hs[L0_PMAX * L0_PMAX];
-  __shared__ double cs[L0_PMAX];
-  __shared__ unsigned long long needs[L0_PMAX];
-  __shared__ int gs[L0_PMAX + 1];
+  static_assert(!(L1 && WIDE), "there is no wide l1 mode");
+  using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
+  constexpr int PM = WIDE ? L0_WIDE_PMAX : L0_PMAX;
+  __shared__ double Hs[WIDE ? PM * (PM + 1) / 2 : PM * PM];  // (wide: the lower triangle, row i at i (i + 1) / 2)
+  __shared__ double cs[PM];
+  __shared__ Mask needs[PM];
+  __shared__ int gs[PM + 1];
   const int tid = threadIdx.x, lane = tid & 63;
   const int p = a.p, ng = a.ng, d = a.d, K = a.K;
-  for (int e = tid; e < p * p; e += 64 * L0_WAVES) Hs[e] = a.H[e];
+  if constexpr (WIDE) {
+    for (int e = tid; e < p * p; e += 64 * L0_WAVES) {
+      const int i = e / p, j = e - i * p;
+      if (j <= i) Hs[i * (i + 1) / 2 + j] = a.H[e];
+    }
+  } else {
+    for (int e = tid; e < p * p; e += 64 * L0_WAVES) Hs[e] = a.H[e];
+  }
   for (int e = tid; e < p; e += 64 * L0_WAVES) cs[e] = a.c[e];
-  for (int e = tid; e < ng; e += 64 * L0_WAVES) needs[e] = a.need[e];
+  if constexpr (WIDE) {
+    for (int e = tid; e < ng; e += 64 * L0_WAVES) needs[e] = L0Mask128{a.need[2 * e], a.need[2 * e + 1]};
+  } else {
+    for (int e = tid; e < ng; e += 64 * L0_WAVES) needs[e] = a.need[e];
+  }
   for (int e = tid; e <= ng; e += 64 * L0_WAVES) gs[e] = (int)a.gstart[e];
   __syncthreads();  // (the only barrier: from here on the waves run on their own and leave when they are done)
+  // H[i][j] (symmetric) from LDS
+  auto Hat = [&](int i, int j) -> double {
+    if constexpr (WIDE) {
+      const int hi = i > j ? i : j, lo = i > j ? j : i;
+      return Hs[hi * (hi + 1) / 2 + lo];
+    } else {
+      return Hs[i * p + j];
+    }
+  };
 
   const long long n_tickets = 1ll << d;
   const double alpha = a.alpha, big_M = a.big_M, q_all = a.q_all;
@@ -141,14 +180,23 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   // l1 mode: lane r also stands for the r-th column of the SUPPORT (dependent ones included), na of them
   int acol = 0, na = 0, st_na = 0;
   long long descents_local = 0;
-  // the state before group g was decided, held by lane g
+  // the state before group g was decided, held by lane g (wide: by lane g & 63, in slot g >> 6)
   int st_m = 0;
   double st_ss = 0.0;
-  unsigned long long st_need = 0;
+  Mask st_need = l0m_none<Mask>();
+  [[maybe_unused]] int st_m1 = 0;  // (the second slot: wide only)
+  [[maybe_unused]] double st_ss1 = 0.0;
+  [[maybe_unused]] Mask st_need1 = l0m_none<Mask>();
+  [[maybe_unused]] int cap_min = 0x7fffffff;  // wide: the smallest cnt at which an include was refused because the factor was full
+  auto saved_m = [&](int g) -> int {
+    if constexpr (WIDE)
+      if (g >= 64) return __builtin_amdgcn_readlane(st_m1, g - 64);
+    return __builtin_amdgcn_readlane(st_m, g);
+  };
 
   // (profile mode: these two and inc are per lane -- lane k - 1 holds size k -- and env is E(k) of the head of the file)
   double best_v = __builtin_inf();
-  unsigned long long best_mask = ~0ull;
+  Mask best_mask = l0m_ones<Mask>();
   auto read_incumbent = [&]() {
     if constexpr (PROFILE)
       return l0_unkey(__hip_atomic_load(&a.ctl[L0_PROFILE_INC + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -168,8 +216,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   };
   long long nodes_local = 0;
   int since_refresh = 0;
-  unsigned long long needed = 0;  // groups some other group depends on
-  for (int g = 0; g < ng; ++g) needed |= needs[g];
+  Mask needed = l0m_none<Mask>();  // groups some other group depends on
+  for (int g = 0; g < ng; ++g) l0m_or(needed, needs[g]);
   bool quit = false;
 
   for (long long round = 0; round <= n_tickets && !quit; ++round) {
@@ -191,7 +239,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     int m = 0, cnt = 0, depth = 0;
     na = 0;
     double ss = 0.0;
-    unsigned long long incl = 0, needm = 0;
+    Mask incl = l0m_none<Mask>(), needm = l0m_none<Mask>();
     bool down = true;
     // every pass of this loop either descends one level, or climbs one, or turns an include into an exclude: at most
     // three passes per edge of a finite tree; the node budget ends it earlier
@@ -211,17 +259,26 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
         g = depth;
         const bool forced = g < d;
         const bool want = forced ? ((t >> g) & 1) != 0 : true;
-        if (lane == g) {
+        if constexpr (WIDE) {
+          if (g < 64) {
+            if (lane == g) {
+              st_m = m;
+              st_ss = ss;
+              st_need = needm;
+            }
+          } else if (lane == g - 64) {
+            st_m1 = m;
+            st_ss1 = ss;
+            st_need1 = needm;
+          }
+        } else if (lane == g) {
           st_m = m;
           st_ss = ss;
           st_need = needm;
           if constexpr (L1) st_na = na;
         }
         bool ok = want;
-        if (ok) {
-          const unsigned long long low = g == 0 ? 0ull : (~0ull >> (64 - g));
-          ok = (needs[g] & low & ~incl) == 0;  // hierarchy: it needs a group that was excluded
-        }
+        if (ok) ok = !l0m_any_outside(l0m_and(needs[g], l0m_below<Mask>(g)), incl);  // hierarchy: it needs a group that was excluded
         if (ok) {
           if (++nodes_local >= L0_BATCH) {  // the node budget
             unsigned long long flag = 0;
@@ -244,8 +301,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           }
           for (int j = c0; j < c1; ++j) {
             // append column j: x = L^-1 H[cols, j] by columns, x_k broadcast from lane k at step k
-            const double hjj = Hs[j * p + j];
-            double b = lane < m ? Hs[j * p + mycol] : 0.0;  // (H is symmetric: the lanes read one row)
+            const double hjj = Hat(j, j);
+            double b = lane < m ? Hat(j, mycol) : 0.0;  // (H is symmetric: the lanes read one row)
             double s2 = 0.0, sw = 0.0;
 #pragma unroll
             for (int k = 0; k < L0_PMAX; ++k) {
@@ -259,6 +316,12 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
             }
             const double piv = hjj - s2;
             if (piv > L0_PIVOT * hjj) {  // (otherwise the column depends on the included ones: it is skipped, its beta is 0)
+              if constexpr (WIDE)
+                if (m == L0_PMAX) {  // capacity: the factor is full, the include is refused (the exclude branch restores the state)
+                  ok = false;
+                  cap_min = cnt < cap_min ? cnt : cap_min;
+                  break;
+                }
               const double lmm = sqrt(piv), wm = (cs[j] - sw) / lmm;
               if (lane == m) {
                 invd = 1.0 / lmm;
@@ -273,26 +336,26 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           // group needs it, every support with it is matched by the same support without it
           // (not with an l1 term: a column equal to a + b replaces two coefficients by one, and the value falls)
           if constexpr (!L1)
-            if (m == __builtin_amdgcn_readlane(st_m, g) && !((needed >> g) & 1)) ok = false;
+            if (m == saved_m(g) && !l0m_test(needed, g)) ok = false;
         }
         if (ok) {
-          incl |= 1ull << g;
+          l0m_set(incl, g);
           ++cnt;
-          needm |= needs[g];
+          l0m_or(needm, needs[g]);
           depth = g + 1;
           // every node is a candidate; inside the prefix the ticket whose remaining bits are zero evaluates it
           const bool mine = depth >= d || (t >> depth) == 0;
           double val = -0.5 * ss + alpha * (double)cnt;
           // what the candidate has to beat: the incumbent and the wave's best -- in profile mode those of its size
           double inc_k = inc, best_k = best_v;
-          unsigned long long mask_k = best_mask;
+          Mask mask_k = best_mask;
           if constexpr (PROFILE) {
             val = -0.5 * ss;
             inc_k = l0_bcast(inc, cnt - 1);
             best_k = l0_bcast(best_v, cnt - 1);
             mask_k = l0_bcast(best_mask, cnt - 1);
           }
-          if (mine && (needm & ~incl) == 0 && val <= inc_k && (val < best_k || (val == best_k && incl < mask_k))) {
+          if (mine && !l0m_any_outside(needm, incl) && val <= inc_k && (val < best_k || (val == best_k && l0m_less(incl, mask_k)))) {
             // back-substitution beta = L^-T w, row by row from the last: lane r contributes L[r][k] beta_r to entry k
             double beta = 0.0;
 #pragma unroll
@@ -344,17 +407,17 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               double gr = lane < m ? -cs[mycol] : 0.0;
               for (int k = 0; k < m; ++k) {
                 const int ck = __builtin_amdgcn_readlane(mycol, k);
-                gr = fma(lane < m ? Hs[ck * p + mycol] : 0.0, l0_bcast(beta, k), gr);
+                gr = fma(lane < m ? Hat(ck, mycol) : 0.0, l0_bcast(beta, k), gr);
               }
               for (int sweep = 0; sweep < L0_CD_SWEEPS; ++sweep) {
                 double maxd = 0.0, maxb = 0.0;
                 for (int k = 0; k < m; ++k) {
                   const int ck = __builtin_amdgcn_readlane(mycol, k);
                   const double bk = l0_bcast(beta, k), gk = l0_bcast(gr, k);
-                  const double nb = fmin(fmax(bk - gk / Hs[ck * p + ck], -big_M), big_M);
+                  const double nb = fmin(fmax(bk - gk / Hat(ck, ck), -big_M), big_M);
                   const double dk = nb - bk;
                   if (dk != 0.0) {
-                    gr = fma(lane < m ? Hs[ck * p + mycol] : 0.0, dk, gr);
+                    gr = fma(lane < m ? Hat(ck, mycol) : 0.0, dk, gr);
                     if (lane == k) beta = nb;
                   }
                   maxd = fmax(maxd, fabs(dk));
@@ -367,7 +430,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               else
                 val = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0) + alpha * (double)cnt;
             }
-            if (val <= inc_k && (val < best_k || (val == best_k && incl < mask_k))) {
+            if (val <= inc_k && (val < best_k || (val == best_k && l0m_less(incl, mask_k)))) {
               unsigned long long old = 0;
               if (lane == 0) old = atomicMin(PROFILE ? &a.ctl[L0_PROFILE_INC + cnt - 1] : &a.ctl[L0_INCUMBENT], l0_key(val));
               const double seen = l0_unkey(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) |
@@ -403,8 +466,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
       } else {
         g = depth - 1;
         if (g < d) break;  // back at the prefix: the ticket is done
-        if ((incl >> g) & 1) {  // back from the include branch: undo it, take the exclude branch
-          incl &= ~(1ull << g);
+        if (l0m_test(incl, g)) {  // back from the include branch: undo it, take the exclude branch
+          l0m_clear(incl, g);
           --cnt;
           try_exclude = true;
         } else {
@@ -413,12 +476,22 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
         }
       }
       if (try_exclude) {
-        m = __builtin_amdgcn_readlane(st_m, g);
-        ss = l0_bcast(st_ss, g);
-        if constexpr (L1) na = __builtin_amdgcn_readlane(st_na, g);
-        needm = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(st_need >> 32), g) << 32) |
-                (unsigned)__builtin_amdgcn_readlane((int)st_need, g);
-        if ((needm >> g) & 1) {  // an included group needs this one
+        m = saved_m(g);
+        if constexpr (WIDE) {
+          if (g < 64) {
+            ss = l0_bcast(st_ss, g);
+            needm = l0_bcast(st_need, g);
+          } else {
+            ss = l0_bcast(st_ss1, g - 64);
+            needm = l0_bcast(st_need1, g - 64);
+          }
+        } else {
+          ss = l0_bcast(st_ss, g);
+          if constexpr (L1) na = __builtin_amdgcn_readlane(st_na, g);
+          needm = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(st_need >> 32), g) << 32) |
+                  (unsigned)__builtin_amdgcn_readlane((int)st_need, g);
+        }
+        if (l0m_test(needm, g)) {  // an included group needs this one
           if (g < d) break;
           depth = g;
           down = false;
@@ -432,7 +505,12 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   if constexpr (PROFILE) {  // every lane its size: 64 values and 64 supports per wave
     const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
     a.best_val[(size_t)wv * 64 + lane] = best_v;
-    a.best_mask[(size_t)wv * 64 + lane] = best_mask;
+    if constexpr (WIDE) {
+      a.best_mask[((size_t)wv * 64 + lane) * 2] = best_mask.lo;
+      a.best_mask[((size_t)wv * 64 + lane) * 2 + 1] = best_mask.hi;
+    } else {
+      a.best_mask[(size_t)wv * 64 + lane] = best_mask;
+    }
   }
   if (lane == 0) {
     if (nodes_local > 0) atomicAdd(&a.ctl[L0_NODES], (unsigned long long)nodes_local);
@@ -441,8 +519,15 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     if constexpr (!PROFILE) {
       const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
       a.best_val[wv] = best_v;
-      a.best_mask[wv] = best_mask;
+      if constexpr (WIDE) {
+        a.best_mask[(size_t)wv * 2] = best_mask.lo;
+        a.best_mask[(size_t)wv * 2 + 1] = best_mask.hi;
+      } else {
+        a.best_mask[wv] = best_mask;
+      }
     }
+    if constexpr (WIDE)
+      if (cap_min != 0x7fffffff) atomicMin(&a.ctl[L0_CAPACITY], (unsigned long long)cap_min + 1ull);
   }
 }
 

@@ -91,6 +91,8 @@ ABI_SYMBOLS = (
     "slm_solve_l0",
     "slm_solve_l0_l1",
     "slm_solve_l0_profile",
+    "slm_solve_l0_wide",
+    "slm_solve_l0_profile_wide",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -351,6 +353,8 @@ def load_library():
             "slm_solve_l0": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_l1": [vp, dbl, dbl, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_profile": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
+            "slm_solve_l0_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
+            "slm_solve_l0_profile_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1359,6 +1363,95 @@ class Dataset:
             "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
             "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
             "descents": int(info["rejects"]), "box_tol": 1e-12,
+        }
+
+    def _need_words(self, need):
+        """``need`` (one Python integer of up to 128 bits per group) as the wide entries take it: two 64-bit words per group,
+        the low one first."""
+        if need is None:
+            return None
+        G = self.n_groups
+        vals = [int(v) for v in need]
+        if len(vals) != G:
+            raise ValueError(f"need must have {G} entries")
+        if any(v < 0 or v >> 128 for v in vals):
+            raise ValueError("need masks must be non-negative integers of at most 128 bits")
+        mask = (1 << 64) - 1
+        return np.ascontiguousarray([[v & mask, v >> 64] for v in vals], dtype=np.uint64).reshape(G, 2)
+
+    def solve_l0_wide(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_wide``: ``solve_l0`` on the kernel's wide instantiation -- up to 128 columns and 128 groups, at any
+        admissible size (a problem within ``solve_l0``'s limits gives the same bits on either).  ``need`` holds Python
+        integers of up to 128 bits and the support comes back as one.  A support holds at most 64 independent columns: an
+        include that would bring a 65th is refused, and ``info`` then holds ``capacity_cut`` = the smallest number of groups
+        held where that happened (``None``: never) and ``lower_bound <= q_all + alpha (capacity_cut + 1)``.  ``status`` is
+        ``"capacity"`` when that alone is why the result is unproven, ``"node_budget"`` when the budget ran out."""
+        _sync_knobs()
+        G = self.n_groups
+        K = G if max_groups is None else int(max_groups)
+        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
+        need_ = self._need_words(need)
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        if b is not None:
+            beta, words, lower, nodes, rec, rc = b.solve_l0_wide(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M),
+                                                                 need_, int(max_nodes))
+            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
+        else:
+            beta = np.empty(self.p)
+            words = np.zeros(2, dtype=np.uint64)
+            lb, nd = C.c_double(), C.c_int64()
+            infos = np.zeros(1, dtype=_INFO_DTYPE)
+            rc = self._lib.slm_solve_l0_wide(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes),
+                                             _ptr(beta), _ptr(words), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
+            if rc != SLM_ERR_NOT_CONVERGED:
+                _check(rc)
+            lower, nodes, info = float(lb.value), int(nd.value), infos[0]
+        support = int(words[0]) | (int(words[1]) << 64)
+        cut = int(info["rejects"])
+        status = "optimal" if rc == SLM_OK else "node_budget" if float(info["resid"]) != 0.0 else "capacity"
+        return beta, support, {
+            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
+            "status": status, "loss": float(info["loss"]), "seed_objective": float(info["mu"]), "q_all": float(info["L"]),
+            "launches": int(info["n_iter"]), "box_tol": 1e-12, "capacity_cut": cut - 1 if cut else None,
+        }
+
+    def solve_l0_profile_wide(self, alpha_min=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_profile_wide``: ``solve_l0_profile`` on the kernel's wide instantiation -- up to 128 columns and
+        groups, ``max_groups <= 64``, refused (``NotImplementedError``) when the ``max_groups`` largest groups together hold
+        more than 64 columns.  ``need`` holds Python integers of up to 128 bits; the support masks come back as a list of
+        Python integers (all ones on an entry nobody filled)."""
+        _sync_knobs()
+        G = self.n_groups
+        K = G if max_groups is None else int(max_groups)
+        if K < 0:
+            raise ValueError("max_groups must be >= 0")
+        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
+        need_ = self._need_words(need)
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        if b is not None:
+            betas, words, values, nodes, rec, rc = b.solve_l0_profile_wide(self._h.value, self.p, float(alpha_min), K, float(eta), T_,
+                                                                           float(big_M), need_, int(max_nodes))
+            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
+        else:
+            betas = np.empty((K + 1, self.p))
+            words = np.empty((K + 1, 2), dtype=np.uint64)
+            values = np.empty(K + 1)
+            nd = C.c_int64()
+            infos = np.zeros(1, dtype=_INFO_DTYPE)
+            rc = self._lib.slm_solve_l0_profile_wide(self._h, float(alpha_min), K, float(eta), _ptr(T_), float(big_M), _ptr(need_),
+                                                     int(max_nodes), _ptr(betas), _ptr(words), _ptr(values), C.byref(nd),
+                                                     _as(infos, _PointInfo))
+            if rc != SLM_ERR_NOT_CONVERGED:
+                _check(rc)
+            nodes, info = int(nd.value), infos[0]
+        supports = [int(lo) | (int(hi) << 64) for lo, hi in np.asarray(words).reshape(K + 1, 2)]
+        return betas, supports, values, {
+            "nodes": int(nodes), "launches": int(info["n_iter"]), "q_all": float(info["L"]),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "proven_optimal": rc == SLM_OK, "box_tol": 1e-12,
         }
 
     def solve_l0_profile(self, alpha_min=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):

@@ -14,8 +14,9 @@ fits one estimator per value walks the same include / exclude tree once per valu
 With ``alpha_min = 0`` nothing is pruned but what cannot matter to any question, and the search visits about as many nodes
 as there are admissible supports of at most ``max_groups`` groups: it is meant for up to ~30 groups, or a small
 ``max_groups``.  ``alpha_min > 0`` prunes what no ``alpha >= alpha_min`` can use; the table is then no longer the best of
-every size and serves ``regularized`` only.  Limits are the estimators': 64 columns and 64 groups, no row-sharded
-datasets, no ``constraints=``.  ``L1L0`` is not served: the value of a support there depends on its own ``eta``.
+every size and serves ``regularized`` only.  Limits are the estimators': 64 columns and 64 groups -- 128 of each with
+``solver_options={"wide": True}``, when ``max_groups <= 64`` and the ``max_groups`` largest groups together hold at most 64
+columns (so that every support fits the factor) --, no row-sharded datasets, no ``constraints=``.  ``L1L0`` is not served: the value of a support there depends on its own ``eta``.
 
 Import path: ``sparselm_amd.miqp`` (``l0_profile``, ``L0Profile``); ``sparselm_amd.model`` keeps the names it had.
 """
@@ -137,7 +138,7 @@ def l0_profile(X, y, *, groups=None, max_groups=None, alpha_min=0.0, eta=0.0, ti
     """The best support of every size ``0 .. max_groups`` (None: the number of groups) from one search on the GPU.
 
     ``groups``, ``big_M``, ``hierarchy``, ``fit_intercept``, ``sample_weight`` and ``solver_options`` (``max_nodes``,
-    ``device``) are the estimators'; ``eta`` and ``tikhonov_w`` are the ridge term of ``RidgedBestSubsetSelection`` / ``L2L0``
+    ``device``, ``wide``) are the estimators'; ``eta`` and ``tikhonov_w`` are the ridge term of ``RidgedBestSubsetSelection`` / ``L2L0``
     (``eta = 0``: none).  ``alpha_min``: the smallest ``alpha`` that ``regularized`` will be asked; 0 keeps the full table.
     A ``ConvergenceWarning`` is raised when the node budget ran out: the table then holds the incumbents."""
     spec = _ProfileProblem(groups=groups, max_groups=max_groups, alpha_min=alpha_min, eta=eta, tikhonov_w=tikhonov_w, big_M=big_M,
@@ -149,9 +150,10 @@ def l0_profile(X, y, *, groups=None, max_groups=None, alpha_min=0.0, eta=0.0, ti
     K = n_groups if max_groups is None else int(max_groups)
     if K > n_groups:
         raise ValueError(f"max_groups = {max_groups} is above the number of groups, {n_groups}")
+    wide = bool(options.get("wide")) and (X.shape[1] > 64 or n_groups > 64)  # (within the narrow limits: the narrow search)
     with spec._l0_dataset(X, y, w, gidx, n_groups, need, options) as (ds, x_mean, y_mean, need, max_nodes):
-        coefs, masks, values, info = ds.solve_l0_profile(alpha_min=float(alpha_min), max_groups=K, eta=float(eta), T=T, big_M=float(big_M),
-                                                         need=need, max_nodes=max_nodes)
+        solve = ds.solve_l0_profile_wide if wide else ds.solve_l0_profile
+        coefs, masks, values, info = solve(alpha_min=float(alpha_min), max_groups=K, eta=float(eta), T=T, big_M=float(big_M), need=need, max_nodes=max_nodes)
     if not info["proven_optimal"]:
         warnings.warn(f"the node budget ran out after {info['nodes']} nodes: the table holds the incumbents of every size; raise "
                       "solver_options['max_nodes']", ConvergenceWarning)

@@ -4,7 +4,8 @@ _regularized_l0.py:115-144, 502-530 for the constructors and parameter constrain
 
 The reference writes these as mixed-integer quadratic programs in cvxpy and needs Gurobi or SCIP to solve them.  Here one
 launch of a depth-first search over supports on the GPU (``slm_solve_l0``, csrc/l0_kernels.hpp) returns the proven optimum
-for up to 64 columns and 64 groups.  The reference's objectives divided by ``2n`` (_miqp/_base.py:126-127,
+for up to 64 columns and 64 groups -- with ``solver_options={"wide": True}`` up to 128 of each (``slm_solve_l0_wide``), where a
+support may hold at most 64 independent columns.  The reference's objectives divided by ``2n`` (_miqp/_base.py:126-127,
 _regularized_l0.py:157-161, ``TikhonovMixin`` _base.py:544-546) are all
 
     minimise over supports S (sets of GROUPS) and beta, supp beta in cols(S), |beta_j| <= big_M:
@@ -38,7 +39,8 @@ from .._utils.validation import check_groups, dense_group_index
 
 __all__ = ["BestSubsetSelection", "RidgedBestSubsetSelection", "RegularizedL0", "L2L0"]
 
-_KNOWN_OPTIONS = {"max_nodes", "device"}
+_KNOWN_OPTIONS = {"max_nodes", "device", "wide"}
+_NARROW = 64  # L0_PMAX: columns and groups of the narrow search, independent columns of a support in the wide one
 
 
 def _hierarchy_masks(hierarchy, groups, n_features):
@@ -76,8 +78,14 @@ class _ExactL0(RegressorMixin, BaseEstimator):
 
     ``solver`` is accepted for the reference's signature and ignored; ``ignore_psd_check`` likewise (there is no cvxpy
     check to skip); ``solver_options`` understands ``max_nodes`` (the node budget: when it runs out a
-    ``ConvergenceWarning`` is raised and the incumbent kept) and ``device``.
+    ``ConvergenceWarning`` is raised and the incumbent kept), ``device`` and ``wide``.  ``wide=True`` admits up to 128 columns
+    and 128 groups: a problem within the narrow limits still takes the narrow search (the same bits), a wider one the wide
+    search, in which a support holds at most 64 independent columns.  Where that cap cut the search and the result is not
+    proven all the same, ``solver_info_["status"]`` is ``"capacity"``, ``solver_info_["capacity_cut"]`` the number of groups
+    from which includes were refused, and a ``ConvergenceWarning`` names the bound.
     """
+
+    _wide_mode = True  # (L1L0: there is no wide l1 mode)
 
     _parameter_constraints: dict = {
         "ignore_psd_check": ["boolean"],
@@ -119,6 +127,10 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         unknown = set(options) - _KNOWN_OPTIONS
         if unknown:
             raise ValueError(f"unknown solver_options {sorted(unknown)}: the exact l0 search takes {sorted(_KNOWN_OPTIONS)}")
+        if not isinstance(options.get("wide", False), (bool, np.bool_)):
+            raise ValueError("solver_options['wide'] must be a bool")
+        if options.get("wide") and not self._wide_mode:
+            raise ValueError(f"{self.__class__.__name__} has no wide mode: the l1 search takes up to {_NARROW} columns and groups")
         p = X.shape[1]
         gidx, n_groups = dense_group_index(self.groups, p)
         need = _hierarchy_masks(self.hierarchy, self.groups, p)
@@ -139,7 +151,7 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         with eng.dataset(X, y, row_weight=w) as ds:
             x_mean, y_mean = ds.center() if self.fit_intercept else (np.zeros(X.shape[1]), 0.0)
             ds.set_groups(gidx, n_groups)
-            if need is not None and n_groups > 64:
+            if need is not None and n_groups > _NARROW and not options.get("wide"):
                 need = None  # (the engine refuses the size itself; masks of more than 64 groups have no 64-bit form)
             yield ds, x_mean, y_mean, need, int(options.get("max_nodes", 0) or 0)
 
@@ -148,13 +160,30 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         X, y, options, gidx, n_groups, need, T, w = self._l0_setup(X, y, sample_weight)
         alpha, max_groups, eta = self._l0_problem(n_groups)
         eta_l1 = float(self._l1_weight())
+        # (wide: only a problem beyond the narrow limits takes the wide search -- within them the bits stay what they were)
+        wide = bool(options.get("wide")) and (X.shape[1] > _NARROW or n_groups > _NARROW)
         with self._l0_dataset(X, y, w, gidx, n_groups, need, options) as (ds, x_mean, y_mean, need, max_nodes):
             if eta_l1 > 0.0:
                 beta, support, info = ds.solve_l0_l1(alpha=alpha, eta_l1=eta_l1, big_M=float(self.big_M), need=need, max_nodes=max_nodes)
+            elif wide:
+                beta, support, info = ds.solve_l0_wide(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
+                                                       need=need, max_nodes=max_nodes)
             else:
-                beta, support, info = ds.solve_l0(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
-                                                  need=need, max_nodes=max_nodes)
-        if not info["proven_optimal"]:
+                try:
+                    beta, support, info = ds.solve_l0(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
+                                                      need=need, max_nodes=max_nodes)
+                except NotImplementedError as exc:
+                    if options.get("wide") or max(X.shape[1], n_groups) <= _NARROW:
+                        raise
+                    raise NotImplementedError(f"{exc}; solver_options={{'wide': True}} takes up to 128 of each") from None
+        if info["status"] == "capacity":
+            warnings.warn(
+                f"a support holds at most {_NARROW} independent columns: includes were refused from {info['capacity_cut']} groups on, "
+                f"and the incumbent (objective {info['objective']:.6g}) is above the bound {info['lower_bound']:.6g} on what lies "
+                "behind them; it is kept, unproven",
+                ConvergenceWarning,
+            )
+        elif not info["proven_optimal"]:
             warnings.warn(
                 f"the node budget ran out after {info['nodes']} nodes: the incumbent (objective {info['objective']:.6g}, proven "
                 f"lower bound {info['lower_bound']:.6g}) is kept; raise solver_options['max_nodes']",

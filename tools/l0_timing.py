@@ -18,7 +18,13 @@ process, same device -- 25 x 20 and 25 x 30 with ``max_groups = 8`` against ``Be
 while ``alpha`` is scanned) and ``alpha_min`` = the smallest of its five alphas, against ``L2L0`` at the five; one call at
 ``alpha_min = 0`` beside one at that ``alpha_min``; and the nodes of a single ``RegularizedL0(alpha_min)`` search beside the
 profile's at the same ``alpha_min`` (the profile's bound uses only sizes <= the node's own, so it prunes less).  Nothing is
-promised: the file states what was found.  ``--only search`` / ``--only profile`` runs one of the two parts."""
+promised: the file states what was found.
+
+Then the wide mode (``solver_options={"wide": True}``, ``slm_solve_l0_wide``), written to ``profiles/l0_wide.txt``: the wide
+kernel forced (through the dataset call) on the 25 x 20 and 25 x 30 problems above beside the narrow kernel on the same
+dataset in the same run -- the price of ``WIDE`` per node; ``BestSubsetSelection(sparse_bound=K)`` at 150 x 100 with K = 3
+and at 200 x 128 with K = 4; and ``L2L0(fit_intercept=True, alpha=3.16e-7, eta=1.66e-6)`` on the reference's 290 x 66
+cluster-expansion data under the default budget.  ``--only search`` / ``--only profile`` / ``--only wide`` runs one part."""
 
 import argparse
 import math
@@ -118,16 +124,75 @@ def profile_section(out_path):
     print(text)
 
 
+def wide_section(out_path, max_nodes):
+    from sklearn.datasets import make_regression
+
+    from sparselm_amd import _engine
+    from sparselm_amd.model import L2L0, BestSubsetSelection
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    lines = [f"wide exact l0 search on {name}, {dev['compute_units']} compute units", "(wall time of the whole call, second of two calls each)", ""]
+
+    def say(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    # ---- the price of WIDE per node: both kernels on the same dataset ------------------------------------------------------------
+    say(f"the wide kernel forced on narrow problems beside the narrow kernel (dataset calls, big_M = 1000, budget {max_nodes} nodes per call)")
+    say(f"{'problem':34s} {'n x p':8s} {'kernel':7s} {'nodes':>12s} {'wall s':>9s} {'nodes/s':>12s} {'proven':>7s} {'objective':>16s}")
+    for p in (20, 30):
+        X, y = make_regression(25, p, n_informative=10, noise=1.0, random_state=0)
+        with _engine.get_engine().dataset(X, y) as ds:
+            for what, kw in (("best subset, K = p / 2", dict(max_groups=p // 2)), ("ridged best subset, eta = 1", dict(max_groups=p // 2, eta=1.0)),
+                             ("RegularizedL0, alpha = 3", dict(alpha=3.0)), ("L2L0, alpha = 3, eta = 1", dict(alpha=3.0, eta=1.0))):
+                rates = {}
+                for kernel, call in (("narrow", ds.solve_l0), ("wide", ds.solve_l0_wide)):
+                    (_, _, info), wall = timed(lambda: call(big_M=1000.0, max_nodes=max_nodes, **kw))
+                    rates[kernel] = info["nodes"] / wall
+                    say(f"{what:34s} {'25x%d' % p:8s} {kernel:7s} {info['nodes']:12d} {wall:9.4f} {rates[kernel]:12.3e} "
+                        f"{str(info['proven_optimal']):>7s} {info['objective']:16.8e}")
+                say(f"    wide / narrow nodes per second: {rates['wide'] / rates['narrow']:.3f}")
+    # ---- a small bound over a wide dictionary ------------------------------------------------------------------------------------
+    say("")
+    say("BestSubsetSelection(sparse_bound=K, big_M=1000, solver_options={'wide': True}), default budget")
+    say(f"{'n x p':10s} {'K':>3s} {'nodes':>12s} {'wall s':>9s} {'nodes/s':>12s} {'proven':>7s} {'capacity_cut':>13s} {'objective':>16s}")
+    for n, p, K in ((150, 100, 3), (200, 128, 4)):
+        X, y = make_regression(n, p, n_informative=10, noise=1.0, random_state=0)
+        est, wall = timed(lambda: BestSubsetSelection(sparse_bound=K, big_M=1000, solver_options={"wide": True}).fit(X, y))
+        info = est.solver_info_
+        say(f"{'%dx%d' % (n, p):10s} {K:3d} {info['nodes']:12d} {wall:9.4f} {info['nodes'] / wall:12.3e} {str(info['proven_optimal']):>7s} "
+            f"{str(info['capacity_cut']):>13s} {info['objective']:16.8e}")
+    # ---- the reference's cluster-expansion data ----------------------------------------------------------------------------------
+    d = os.path.join(ROOT, "tests", "golden", "reference_examples")
+    X, y = np.load(os.path.join(d, "corr.npy")), np.load(os.path.join(d, "energy.npy"))
+    say("")
+    say(f"L2L0(fit_intercept=True, alpha=3.16e-7, eta=1.66e-6, solver_options={{'wide': True}}) on the reference's {X.shape[0]} x {X.shape[1]} data, "
+        "default budget")
+    est, wall = timed(lambda: L2L0(fit_intercept=True, alpha=3.16e-7, eta=1.66e-6, solver_options={"wide": True}).fit(X, y))
+    info = est.solver_info_
+    say(f"    finished: {info['proven_optimal']} (status {info['status']}), {info['nodes']} nodes in {wall:.3f} s ({info['nodes'] / wall:.3e} nodes/s)")
+    say(f"    objective {info['objective']:.10e}, lower bound {info['lower_bound']:.10e}, seed {info['seed_objective']:.10e}, q_all {info['q_all']:.10e}")
+    say(f"    active columns {int(est.active_groups_.sum())} of {X.shape[1]}, capacity_cut {info['capacity_cut']}")
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-nodes", type=int, default=1 << 24)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "l0_search.txt"))
     ap.add_argument("--profile-out", default=os.path.join(ROOT, "profiles", "l0_profile.txt"))
-    ap.add_argument("--only", choices=["search", "profile"], default=None)
+    ap.add_argument("--wide-out", default=os.path.join(ROOT, "profiles", "l0_wide.txt"))
+    ap.add_argument("--only", choices=["search", "profile", "wide"], default=None)
     args = ap.parse_args()
-    if args.only != "search":
+    if args.only in (None, "wide"):
+        wide_section(args.wide_out, args.max_nodes)
+    if args.only in (None, "profile"):
         profile_section(args.profile_out)
-    if args.only == "profile":
+    if args.only not in (None, "search"):
         return
     from sklearn.datasets import make_regression
 
