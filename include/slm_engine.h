@@ -698,6 +698,42 @@ int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_gro
                               int64_t* nodes_out, slm_point_info* info);
 
 /*
+ * (added under ABI 24: a new symbol beside slm_solve_l0, no existing entry, structure or constant changes, so the version
+ * stays 24 -- a caller that needs it looks the symbol up.)  The exact l0 search under LINEAR CONSTRAINTS on the coefficients
+ * (csrc/l0_kernels.hpp, template parameter CON; the reference's add_constraints on its mixed-integer estimators,
+ * examples/plot_chull.py:157-183): slm_solve_l0's problem and arguments with, in addition,
+ *       lo <= A beta <= hi   (A: m x p row-major, m <= 64; an infinite lo_i or hi_i leaves that side open)   and
+ *       box_lo_j <= beta_j <= box_hi_j   (each NULL: -big_M / +big_M; intersected with +-big_M; box_lo_j <= 0 <= box_hi_j).
+ * A column whose interval excludes 0 is forced active -- that is a row e_j of A, not a box.  A support's value f(S) is a
+ * quadratic programme (+inf where no beta on S is feasible); f(S) >= q(S) keeps the register Cholesky as an exact lower-bound
+ * filter, and a node that passes it is valued on chip by a splitting (augmented Lagrangian of the rows, clipped coordinate
+ * sweeps) that ends every sweep with a dual value D <= f(S), lowered by a rounding margin.  A candidate is VALUED (rows within
+ * 1e-9 of their scale, value within 1e-9 of D: L0_CON_TOL), REJECTED (D above what it has to beat; infeasible supports end so)
+ * or UNSETTLED (max_qp_sweeps sweeps ran out, <= 0: 20000; D + alpha |S| is then a lower bound on that one support).
+ * G + 2 eta T must be positive definite on all columns (with constraints a dependent column can lower the value):
+ * SLM_ERR_UNSUPPORTED otherwise, with a message that names the cure (eta > 0, or a design of full column rank) -- as for
+ * m > 64, more than 64 columns or groups, and row-sharded datasets.  SLM_ERR_BAD_ARG before anything is launched: m < 0, a NaN
+ * or an infinity in A, a NaN bound, lo_i > hi_i, box_lo_j > 0 or box_hi_j < 0, and slm_solve_l0's own.
+ * beta_out, support_out, nodes_out as for slm_solve_l0; the winner's coefficients come from the same splitting on the host
+ * followed by an exact solve on the face it identifies (active rows and clipped coordinates fixed), kept when feasibility and
+ * the multipliers' signs hold.  lambda_out [m] (may be NULL): the rows' multipliers, 0 = H beta - c + A^T lambda + mu on the
+ * support, > 0 only where hi binds, < 0 only where lo binds (mu: the box's).  *lower_bound_out = min(objective, the lowest
+ * bound of an unsettled candidate), and the bound on all columns as well when the node budget ran out.  SLM_OK iff the search
+ * finished and the objective is <= every unsettled bound; otherwise SLM_ERR_NOT_CONVERGED with valid outputs.  When the search
+ * finished, nothing is unsettled and no feasible admissible support exists: SLM_ERR_BAD_ARG ("no admissible support").
+ * info as for slm_solve_l0 with info->L = F_lb, the proven lower bound on f(all columns) the subtree bound used;
+ * info->rejects = candidates valued on chip; info->resid = candidates left unsettled; info->beta_norm = the lowest of their
+ * bounds (+inf: none).
+ */
+int slm_solve_l0_constrained(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T /* p*p or NULL */,
+                             double big_M, const uint64_t* need /* n_groups masks or NULL */, int64_t max_nodes /* <=0: default */,
+                             const double* A /* m*p */, int32_t m, const double* lo /* m */, const double* hi /* m */,
+                             const double* box_lo /* p or NULL */, const double* box_hi /* p or NULL */,
+                             int32_t max_qp_sweeps /* <=0: default */, double* beta_out, uint64_t* support_out,
+                             double* lower_bound_out, int64_t* nodes_out, double* lambda_out /* m or NULL */,
+                             slm_point_info* info);
+
+/*
  * The Gram of a row set, for covariance passes (SLM_FLAG_COVARIANCE): G = X^T W X / n_eff, c = X^T W y / n_eff and
  * y^T W y / n_eff, kept with the dataset (8 ld^2 bytes each) and found again by a fingerprint of the row weights and
  * n_eff -- what a lane of slm_solve_lanes brings as (row_weight, n_eff).  row_weight: length n on the host, NULL = the

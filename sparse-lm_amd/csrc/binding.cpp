@@ -328,6 +328,43 @@ py::tuple solve_l0(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, do
   return py::make_tuple(beta, support, lower, nodes, info, rc);
 }
 
+// slm_solve_l0_constrained: the search under lo <= A beta <= hi and a per-column box.  Returns the tuple of solve_l0 with the
+// rows' multipliers after the support.
+py::tuple solve_l0_constrained(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
+                               const py::object& need, int64_t max_nodes, const py::object& A, int32_t m, const py::object& lo,
+                               const py::object& hi, const py::object& box_lo, const py::object& box_hi, int32_t max_qp_sweeps) {
+  Keep keep;
+  const double* Tp = vector_arg(T, p * p, "T", keep);
+  const int64_t rows = m > 0 ? m : 0;
+  const double* Ap = vector_arg(A, rows * p, "A", keep);
+  const double* lop = vector_arg(lo, rows, "lo", keep);
+  const double* hip = vector_arg(hi, rows, "hi", keep);
+  const double* blop = vector_arg(box_lo, p, "box_lo", keep);
+  const double* bhip = vector_arg(box_hi, p, "box_hi", keep);
+  const uint64_t* needp = nullptr;
+  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
+  if (!need.is_none()) {
+    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
+    if (!need_arr) throw py::value_error("need is not convertible to uint64");
+    needp = need_arr.data();
+  }
+  py::array_t<double> beta((py::ssize_t)p), lam((py::ssize_t)rows);
+  py::array info = info_bytes(1);
+  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
+  uint64_t support = 0;
+  double lower = 0.0;
+  int64_t nodes = 0;
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_constrained(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, Ap, m, lop, hip,
+                                  blop, bhip, max_qp_sweeps, beta.mutable_data(), &support, &lower, &nodes, lam.mutable_data(),
+                                  static_cast<slm_point_info*>(info.mutable_data()));
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, support, lam, lower, nodes, info, rc);
+}
+
 // slm_solve_l0_l1: the same search in l1 mode (the reference's L1L0); the tuple of solve_l0.
 py::tuple solve_l0_l1(uintptr_t ds, int64_t p, double alpha, double eta_l1, double big_M, const py::object& need, int64_t max_nodes) {
   const uint64_t* needp = nullptr;
@@ -458,6 +495,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("dataset_create", &dataset_create);
   m.def("solve_l0", &solve_l0);
   m.def("solve_l0_l1", &solve_l0_l1);
+  m.def("solve_l0_constrained", &solve_l0_constrained);
   m.def("solve_l0_profile", &solve_l0_profile);
   m.def("solve_l0_wide", &solve_l0_wide);
   m.def("solve_l0_profile_wide", &solve_l0_profile_wide);

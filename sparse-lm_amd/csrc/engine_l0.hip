@@ -10,6 +10,8 @@
 // slm_solve_l0_wide and slm_solve_l0_profile_wide are the same two calls on the kernel's WIDE instantiations: up to 128 columns
 // and groups, masks of two words, a support of at most 64 independent columns (the capacity rule of l0_host.hpp).  One
 // template over WIDE serves both widths; with WIDE = false it is the code there was before.
+// slm_solve_l0_constrained is the search on the kernel's CON instantiation: rows lo <= A beta <= hi and a per-column box, the
+// l0_con_* functions of l0_host.hpp for the seed, the bound on all columns and the winner (solve_l0_con_impl).
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -443,6 +445,238 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
   return SLM_OK;
 }
 
+// slm_solve_l0_constrained: the kernel's CON instantiation (DESIGN 4d "Constrained mode").  The arguments are checked before
+// anything is launched; H must be positive definite on all columns; the rows are scaled to unit norm and everything is put in
+// search order; the seed, the bound F_lb on all columns and the winner come from l0_con_solve / l0_con_polish of l0_host.hpp,
+// the very splitting the kernel runs.
+int solve_l0_con_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M, const uint64_t* need,
+                      int64_t max_nodes, const double* A, int32_t m, const double* lo, const double* hi, const double* box_lo,
+                      const double* box_hi, int32_t max_qp_sweeps, double* beta_out, uint64_t* support_out, double* lower_bound_out,
+                      int64_t* nodes_out, double* lambda_out, slm_point_info* info) {
+  using Mask = unsigned long long;
+  int p = 0, ng = 0;
+  SLM_TRY(l0_check_args(ds, beta_out, alpha, "alpha", eta, 0.0, big_M, T, need, &p, &ng, L0_PMAX));
+  if (m < 0) return fail(SLM_ERR_BAD_ARG, "m must be >= 0");
+  if (m > 0 && (!A || !lo || !hi)) return fail(SLM_ERR_BAD_ARG, "NULL argument (A, lo, hi with m > 0)");
+  for (int64_t e = 0; e < (int64_t)m * p; ++e)
+    if (!std::isfinite(A[e])) return fail(SLM_ERR_BAD_ARG, "A contains a NaN or an infinity");
+  for (int i = 0; i < m; ++i) {
+    if (std::isnan(lo[i]) || std::isnan(hi[i])) return fail(SLM_ERR_BAD_ARG, "a bound of row %d is NaN", i);
+    if (lo[i] > hi[i]) return fail(SLM_ERR_BAD_ARG, "lo > hi in row %d", i);
+  }
+  for (int j = 0; j < p; ++j) {
+    if (box_lo && !(box_lo[j] <= 0.0))
+      return fail(SLM_ERR_BAD_ARG, "box_lo[%d] must be <= 0 (a column whose interval excludes 0 is forced active: that is a row of A)", j);
+    if (box_hi && !(box_hi[j] >= 0.0))
+      return fail(SLM_ERR_BAD_ARG, "box_hi[%d] must be >= 0 (a column whose interval excludes 0 is forced active: that is a row of A)", j);
+  }
+  if (m > L0_CON_MMAX) return fail(SLM_ERR_UNSUPPORTED, "the constrained exact l0 search takes up to %d rows of A (got %d)", L0_CON_MMAX, m);
+  const int K = max_groups < 0 ? 0 : std::min<int>(max_groups, ng);
+  L0Problem P;
+  SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, P));
+  slm_engine* eng = ds->eng;
+  hipStream_t s = eng->stream;
+  const std::vector<double>&H = P.H, &c = P.c;
+  const std::vector<int>&cols = P.cols, &gstart = P.gstart, &gorder = P.gorder;
+  if (!l0_con_pd(H.data(), c.data(), p))
+    return fail(SLM_ERR_UNSUPPORTED, "constraints need a positive definite G + 2 eta T: a column depends on the others -- use eta > 0 (L2L0, "
+                "RidgedBestSubsetSelection) or a design of full column rank");
+
+  // ---- the constraints in search order: rows of unit norm, the box inside +-big_M ---------------------------------------------
+  std::vector<double> As((size_t)m * p), At((size_t)m * p), los((size_t)m), his((size_t)m), rnorm((size_t)m, 1.0), blo((size_t)p), bhi((size_t)p);
+  for (int i = 0; i < m; ++i) {
+    double nn = 0.0;
+    for (int j = 0; j < p; ++j) nn += A[(size_t)i * p + j] * A[(size_t)i * p + j];
+    if (nn > 0.0) rnorm[(size_t)i] = std::sqrt(nn);
+    for (int k = 0; k < p; ++k) {
+      As[(size_t)i * p + k] = A[(size_t)i * p + cols[(size_t)k]] / rnorm[(size_t)i];
+      At[(size_t)k * m + i] = As[(size_t)i * p + k];
+    }
+    los[(size_t)i] = lo[i] / rnorm[(size_t)i];
+    his[(size_t)i] = hi[i] / rnorm[(size_t)i];
+  }
+  for (int k = 0; k < p; ++k) {
+    blo[(size_t)k] = box_lo ? std::max(box_lo[cols[(size_t)k]], -big_M) : -big_M;
+    bhi[(size_t)k] = box_hi ? std::min(box_hi[cols[(size_t)k]], big_M) : big_M;
+  }
+  L0ConProblem CP;
+  CP.H = H.data(); CP.c = c.data(); CP.p = p;
+  CP.A = As.data(); CP.m = m; CP.lo = los.data(); CP.hi = his.data();
+  CP.blo = blo.data(); CP.bhi = bhi.data();
+  CP.rho = l0_con_rho(H.data(), p, As.data(), m);
+  CP.max_sweeps = L0_CON_SWEEPS;  // (the host's own solves -- seed, bound, winner -- always get the full cap: max_qp_sweeps starves the candidates on chip)
+
+  // ---- F_lb, the subtree bound's proven lower bound on f(all columns); and what no feasible support's objective exceeds ------------
+  L0ConPoint all;
+  const double bound = l0_con_lower_bound(CP, P.q_all, &all);
+  double cap = l0_con_value_cap(H.data(), c.data(), p, blo.data(), bhi.data());
+  cap = cap + alpha * (double)K + 1e-9 * (cap + alpha * (double)K) + 1e-300;
+
+  // ---- the seed: the empty support, the greedy supports, and supports of the largest groups of the all-columns solution ----------
+  int scols[L0_PMAX];
+  auto value_of = [&](Mask mask) {
+    const int ms = l0_con_columns(gstart, mask, scols);
+    const L0ConPoint R = l0_con_solve(CP, scols, ms, HUGE_VAL);
+    return R.outcome == 0 ? R.primal : HUGE_VAL;
+  };
+  bool zero_ok = true;
+  for (int i = 0; i < m; ++i) zero_ok = zero_ok && lo[i] <= 0.0 && hi[i] >= 0.0;
+  double seed_val = zero_ok ? 0.0 : HUGE_VAL;
+  Mask seed_mask = zero_ok ? 0ull : ~0ull;
+  auto offer = [&](int size, Mask mask, double quad) {
+    const double v = quad + alpha * (double)size;
+    if (v < seed_val || (v == seed_val && v < HUGE_VAL && mask < seed_mask)) {
+      seed_val = v;
+      seed_mask = mask;
+    }
+  };
+  l0_greedy(H.data(), c.data(), p, gstart, P.needo, K, value_of, offer);
+  {
+    std::vector<double> gnorm((size_t)ng, 0.0);
+    for (int g = 0; g < ng; ++g)
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1] && (size_t)j < all.beta.size(); ++j) gnorm[(size_t)g] += all.beta[(size_t)j] * all.beta[(size_t)j];
+    std::vector<int> by((size_t)ng);
+    std::iota(by.begin(), by.end(), 0);
+    std::stable_sort(by.begin(), by.end(), [&](int x, int y) { return gnorm[(size_t)x] > gnorm[(size_t)y]; });
+    Mask cur = 0ull, last = 0ull;
+    for (int k = 0; k < ng; ++k) {
+      cur |= 1ull << by[(size_t)k];
+      for (bool grew = true; grew;) {  // closed under the hierarchy
+        grew = false;
+        for (int g = 0; g < ng; ++g)
+          if (((cur >> g) & 1) && (P.needo[(size_t)g] & ~cur)) {
+            cur |= P.needo[(size_t)g];
+            grew = true;
+          }
+      }
+      const int size = __builtin_popcountll(cur);
+      if (size > K) break;
+      if (cur != last) offer(size, cur, value_of(cur));
+      last = cur;
+    }
+  }
+
+  // ---- the search: one launch --------------------------------------------------------------------------------------------
+  const int d = std::min(ng, L0_PREFIX);
+  const long long n_tickets = 1ll << d;
+  const int blocks = (int)std::max<long long>(1, std::min<long long>(2ll * eng->cus, (n_tickets + L0_WAVES - 1) / L0_WAVES));
+  const int waves = blocks * L0_WAVES;
+  // one block of 8-byte words: control | best values | best supports | H | c | need | group starts | A by columns | lo | hi | box
+  const size_t off_bv = L0_CTL_WORDS, off_bm = off_bv + (size_t)waves, off_H = off_bm + (size_t)waves, off_c = off_H + (size_t)p * p,
+               off_need = off_c + (size_t)p, off_gs = off_need + (size_t)ng, off_A = off_gs + (size_t)ng + 1, off_lo = off_A + (size_t)m * p,
+               off_hi = off_lo + (size_t)m, off_blo = off_hi + (size_t)m, off_bhi = off_blo + (size_t)p, words = off_bhi + (size_t)p;
+  std::vector<unsigned long long> h(words, 0ull);
+  h[L0_INCUMBENT] = l0_key(std::min(seed_val, cap));
+  h[L0_UNSETTLED] = ~0ull;  // (lowered by a wave whose candidate ran out of sweeps)
+  memcpy(&h[off_H], H.data(), sizeof(double) * (size_t)p * p);
+  memcpy(&h[off_c], c.data(), sizeof(double) * (size_t)p);
+  if (ng > 0) memcpy(&h[off_need], P.needo.data(), sizeof(Mask) * (size_t)ng);
+  for (int g = 0; g <= ng; ++g) h[off_gs + (size_t)g] = (unsigned long long)gstart[(size_t)g];
+  if (m > 0) {
+    memcpy(&h[off_A], At.data(), sizeof(double) * (size_t)m * p);
+    memcpy(&h[off_lo], los.data(), sizeof(double) * (size_t)m);
+    memcpy(&h[off_hi], his.data(), sizeof(double) * (size_t)m);
+  }
+  memcpy(&h[off_blo], blo.data(), sizeof(double) * (size_t)p);
+  memcpy(&h[off_bhi], bhi.data(), sizeof(double) * (size_t)p);
+  unsigned long long* dev = nullptr;
+  SLM_TRY(dalloc(&dev, words));
+  L0DevGuard guard{dev, s};
+  HIP_TRY(hipMemcpyAsync(dev, h.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, s));
+  L0Args k;
+  memset(&k, 0, sizeof(k));
+  k.ctl = dev;
+  k.best_val = reinterpret_cast<double*>(dev + off_bv);
+  k.best_mask = dev + off_bm;
+  k.H = reinterpret_cast<const double*>(dev + off_H);
+  k.c = reinterpret_cast<const double*>(dev + off_c);
+  k.need = dev + off_need;
+  k.gstart = reinterpret_cast<const long long*>(dev + off_gs);
+  k.A = reinterpret_cast<const double*>(dev + off_A);
+  k.lo = reinterpret_cast<const double*>(dev + off_lo);
+  k.hi = reinterpret_cast<const double*>(dev + off_hi);
+  k.blo = reinterpret_cast<const double*>(dev + off_blo);
+  k.bhi = reinterpret_cast<const double*>(dev + off_bhi);
+  k.rows = m; k.con_sweeps = max_qp_sweeps > 0 ? max_qp_sweeps : L0_CON_SWEEPS; k.rho = CP.rho;
+  k.p = p; k.ng = ng; k.d = d; k.K = K;
+  k.alpha = alpha; k.big_M = big_M; k.q_all = bound;
+  k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
+  hipLaunchKernelGGL((l0_search_kernel<false, false, false, true>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  SLM_TRY(check_launch());
+  HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(unsigned long long) * off_H, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+
+  // ---- the winner: the waves' bests and the seed in a fixed order, the lower support on a bitwise tie -------------------------
+  double win_val = seed_val;
+  Mask win_mask = seed_mask;
+  for (int wv = 0; wv < waves; ++wv) {
+    double v;
+    memcpy(&v, &h[off_bv + (size_t)wv], 8);
+    const Mask mk = h[off_bm + (size_t)wv];
+    if (v < win_val || (v == win_val && v < HUGE_VAL && mk < win_mask)) {
+      win_val = v;
+      win_mask = mk;
+    }
+  }
+  const bool finished = h[L0_ABORTED] == 0;
+  const long long n_unsettled = (long long)h[L0_UNSETTLED_COUNT];
+  const double unsettled_bound = h[L0_UNSETTLED] == ~0ull ? HUGE_VAL : l0_unkey(h[L0_UNSETTLED]);
+  if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
+  for (int i = 0; i < p; ++i) beta_out[i] = 0.0;
+  for (int i = 0; i < m && lambda_out; ++i) lambda_out[i] = 0.0;
+  if (support_out) *support_out = 0;
+  if (!(win_val < HUGE_VAL) && finished && n_unsettled == 0)
+    return fail(SLM_ERR_BAD_ARG, "no admissible support satisfies the constraints (%d groups at most, the hierarchy, %d rows and the box)", K, m);
+  // its coefficients and multipliers, recomputed here whichever wave found it: the splitting, then the exact face solve
+  double objective = HUGE_VAL;
+  int n_active = 0;
+  if (win_val < HUGE_VAL) {
+    const int ms = l0_con_columns(gstart, win_mask, scols);
+    L0ConPoint R = l0_con_solve(CP, scols, ms, HUGE_VAL);
+    (void)l0_con_polish(CP, scols, ms, R);
+    Mask support = 0ull;
+    for (int g = 0; g < ng; ++g)
+      if ((win_mask >> g) & 1) {
+        ++n_active;
+        support |= 1ull << gorder[(size_t)g];
+      }
+    objective = R.primal + alpha * (double)n_active;
+    for (int r = 0; r < ms; ++r) beta_out[cols[(size_t)scols[r]]] = R.beta[(size_t)r];
+    for (int i = 0; i < m && lambda_out; ++i) lambda_out[i] = R.y[(size_t)i] / rnorm[(size_t)i];
+    if (support_out) *support_out = support;
+  }
+  const bool proven = finished && objective <= unsettled_bound && objective < HUGE_VAL;
+  double lower = std::min(objective, unsettled_bound);
+  if (!finished) lower = std::min(lower, bound);
+  if (lower_bound_out) *lower_bound_out = lower;
+  if (info) {
+    double loss = 0.5 * P.yy;
+    for (int i = 0; i < p; ++i) {
+      if (beta_out[i] == 0.0) continue;
+      double t = 0.0;
+      for (int j = 0; j < p; ++j) t += P.G[(size_t)i * p + j] * beta_out[j];
+      loss += beta_out[i] * (0.5 * t - P.cvec[(size_t)i]);
+    }
+    memset(info, 0, sizeof(*info));
+    info->n_iter = 1;
+    info->status = proven ? SLM_OK : SLM_ERR_NOT_CONVERGED;
+    info->loss = loss;
+    info->mode = 4;
+    info->kkt = objective;
+    info->mu = seed_val;
+    info->L = bound;
+    info->rejects = (int32_t)std::min<unsigned long long>(h[L0_DESCENTS], 0x7fffffffull);  // candidates valued
+    info->resid = (double)n_unsettled;                                                    // candidates that ran out of sweeps
+    info->beta_norm = unsettled_bound;                                                    // the lowest of their bounds, +inf: none
+  }
+  if (!finished) return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld) ran out before the search finished: the incumbent is returned",
+                             (long long)k.max_nodes);
+  if (!proven)
+    return fail(SLM_ERR_NOT_CONVERGED, "%lld candidate(s) ran out of sweeps (%d each): the incumbent is above the bound %.17g on them",
+                n_unsettled, k.con_sweeps, unsettled_bound);
+  return SLM_OK;
+}
+
 }  // namespace
 
 extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
@@ -478,4 +712,14 @@ extern "C" int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int3
                                          const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
                                          double* value_out, int64_t* nodes_out, slm_point_info* info) {
   return solve_l0_profile_impl<true>(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
+}
+
+// The same search under linear constraints lo <= A beta <= hi and a per-column box (the kernel's constrained instantiation).
+extern "C" int slm_solve_l0_constrained(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
+                                        const uint64_t* need, int64_t max_nodes, const double* A, int32_t m, const double* lo,
+                                        const double* hi, const double* box_lo, const double* box_hi, int32_t max_qp_sweeps,
+                                        double* beta_out, uint64_t* support_out, double* lower_bound_out, int64_t* nodes_out,
+                                        double* lambda_out, slm_point_info* info) {
+  return solve_l0_con_impl(ds, alpha, max_groups, eta, T, big_M, need, max_nodes, A, m, lo, hi, box_lo, box_hi, max_qp_sweeps, beta_out,
+                           support_out, lower_bound_out, nodes_out, lambda_out, info);
 }

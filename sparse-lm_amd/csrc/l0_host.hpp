@@ -5,7 +5,9 @@
 // compiles it alone: tests/host_logic_test.cpp, tests/l1l0_host_test.cpp and tests/l0_profile_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 / slm_solve_l0_profile call
 // THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.  The wide mode
 // (slm_solve_l0_wide, slm_solve_l0_profile_wide; tests/l0_wide_host_test.cpp) adds masks of two words, a factor with a capacity
-// parameter and the capacity rule.
+// parameter and the capacity rule.  The constrained mode (slm_solve_l0_constrained; tests/l0_con_host_test.cpp) adds the splitting
+// that values a support under linear constraints, the dual value host and device share, its face polish, the positive-definite
+// check and the lower bound on all columns.
 #pragma once
 #include <stddef.h>
 
@@ -497,6 +499,381 @@ inline double l0_l1_lower_bound(const double* G, const double* c, int p, double 
   const double rr = yy - 2.0 * cb + bGb, ry = yy - cb;
   const double dual = -0.5 * s * s * rr + s * ry - 0.5 * yy - 1e-10 * scale;
   return dual > q_all && std::isfinite(dual) ? dual : q_all;
+}
+
+// ---- constrained mode (slm_solve_l0_constrained): linear constraints on the coefficients -------------------------------------
+//
+//     f(S) = min 1/2 b^T H_S b - c_S^T b   over   blo_j <= b_j <= bhi_j  (a box that contains 0),   lo <= A_S b <= hi  (m rows)
+//
+// and +inf when no b on S is feasible.  H is positive definite on ALL columns (l0_con_pd: the call is refused otherwise), so
+// no column is ever skipped.  q(S) = -1/2 ||w||^2 <= f(S) stays the kernel's filter; a node that passes it is valued by the
+// splitting below (the augmented Lagrangian of the rows, one clipped coordinate sweep per multiplier step), the same on the
+// host (l0_con_solve: the seed, the bound on all columns, the winner) and in the kernel.  Every sweep ends with the dual value
+//     D_S(y, mu) = -1/2 ||L_S^-1 (c_S - A_S^T y - mu)||^2 - sum_i (hi_i y_i^+ - lo_i y_i^-) - sum_j (bhi_j mu_j^+ - blo_j mu_j^-)  <=  f(S)
+// at y = rho u (signs admissible by construction) and mu = the multipliers of the clipped coordinates: weak duality, for ANY
+// admissible (y, mu), so how far the sweeps got decides only how tight it is.  A candidate ends VALUED (rows within
+// L0_CON_TOL of their scale, primal value within L0_CON_TOL of D), REJECTED (D - margin above what it has to beat) or
+// UNSETTLED (the sweep cap ran out: D - margin is a lower bound on that one support).
+constexpr int L0_CON_MMAX = 64;        // rows of A
+constexpr double L0_CON_TOL = 1e-9;    // feasibility and duality gap of a valued candidate, relative
+constexpr int L0_CON_SWEEPS = 20000;   // sweep cap of one candidate (max_qp_sweeps <= 0)
+
+// The pieces host and device share (constexpr, as l0_l1_step is: the device code calls these very functions).
+constexpr double l0_con_abs(double v) { return v < 0.0 ? -v : v; }
+constexpr double l0_con_clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// one row's term of the support function, hi y^+ - lo y^-; +inf for a multiplier whose sign the row does not admit
+constexpr double l0_con_sigma(double y, double lo, double hi) {
+  return y > 0.0 ? (hi < __builtin_inf() ? hi * y : __builtin_inf()) : (y < 0.0 ? (lo > -__builtin_inf() ? lo * y : __builtin_inf()) : 0.0);
+}
+// the multiplier of a clipped coordinate: gl = (H b - c + A^T y)_j, taken where the bound and the sign agree
+constexpr double l0_con_box_mu(double b, double gl, double blo, double bhi) {
+  return (b >= bhi && gl < 0.0) || (b <= blo && gl > 0.0) ? -gl : 0.0;
+}
+// a coordinate step on the augmented Lagrangian: g the entry of H b - c plus rho A_k^T (A b - s + u), curv = H_kk + rho ||A_k||^2
+constexpr double l0_con_step(double b, double g, double curv, double blo, double bhi) { return l0_con_clip(b - g / curv, blo, bhi); }
+// a row's violation relative to its scale (the rows of A have unit norm; maxb = the larger of ||b||_inf and the unconstrained minimiser's)
+constexpr double l0_con_violation(double t, double lo, double hi, double maxb) {
+  const double v = lo - t > t - hi ? lo - t : t - hi;
+  if (!(v > 0.0)) return 0.0;
+  double sc = maxb;
+  if (lo > -__builtin_inf() && l0_con_abs(lo) > sc) sc = l0_con_abs(lo);
+  if (hi < __builtin_inf() && l0_con_abs(hi) > sc) sc = l0_con_abs(hi);
+  return sc > 0.0 ? v / sc : __builtin_inf();
+}
+// The dual value from zz = ||L^-1 (c - A^T y - mu)||^2, sigma = the sum of the support-function terms and asum = the sum of
+// their magnitudes: raw, and lowered by the rounding margin (1e-10 of the sum of its terms' magnitudes, as
+// l0_l1_lower_bound does it) -- `bound` is what is compared.
+struct L0ConDual {
+  double raw, bound, mag;
+};
+constexpr L0ConDual l0_con_dual(double zz, double sigma, double asum) {
+  const double mag = 0.5 * zz + asum;
+  return L0ConDual{-0.5 * zz - sigma, -0.5 * zz - sigma - 1e-10 * mag, mag};
+}
+// valued: the rows within L0_CON_TOL of their scale, the gap (either way: a point that undercuts D is not feasible enough) within L0_CON_TOL of the dual's terms and of qmag = 1/2 ||w||^2, the
+// size of the support's unconstrained value (a support whose optimum is b = 0 has no other scale)
+constexpr bool l0_con_valued(double primal, const L0ConDual& d, double viol, double qmag) {
+  return viol <= L0_CON_TOL && l0_con_abs(primal - d.raw) <= L0_CON_TOL * (d.mag + qmag);
+}
+
+struct L0ConProblem {
+  const double* H;  // [p][p], search order
+  const double* c;  // [p]
+  int p;
+  const double* A;  // [m][p] row-major, search order, every non-zero row scaled to unit norm
+  int m;
+  const double *lo, *hi;    // [m] (scaled with their rows)
+  const double *blo, *bhi;  // [p]: blo_j <= 0 <= bhi_j
+  double rho;
+  int max_sweeps;  // <= 0: L0_CON_SWEEPS
+};
+struct L0ConPoint {
+  int outcome = 2;  // 0 valued, 1 rejected (infeasible supports included), 2 unsettled
+  double primal = HUGE_VAL, bound = -HUGE_VAL;  // the point's value; D - margin at exit, a lower bound on f(S) however it ended
+  int sweeps = 0;
+  bool polished = false;
+  std::vector<double> beta, mu, y;  // [ms], [ms], [m]
+};
+
+// H positive definite on all columns, under the kernel's pivot rule in search order (fact 4 of DESIGN 4d "Constrained mode")
+inline bool l0_con_pd(const double* H, const double* c, int p) {
+  auto f = std::make_unique<L0Factor>(H, c, p);
+  for (int j = 0; j < p; ++j)
+    if (!f->push(j)) return false;
+  return true;
+}
+// the augmented Lagrangian's weight: rho ||A||_F^2 = tr H
+inline double l0_con_rho(const double* H, int p, const double* A, int m) {
+  double trH = 0.0, trK = 0.0;
+  for (int j = 0; j < p; ++j) trH += H[(size_t)j * p + j];
+  for (size_t e = 0; e < (size_t)m * p; ++e) trK += A[e] * A[e];
+  return trH > 0.0 && trK > 0.0 ? trH / trK : 1.0;
+}
+// no feasible b has a larger value: sum |c_j| B_j + 1/2 sum |H_ij| B_i B_j, B_j = max(-blo_j, bhi_j) (+inf with an open box)
+inline double l0_con_value_cap(const double* H, const double* c, int p, const double* blo, const double* bhi) {
+  double v = 0.0;
+  for (int i = 0; i < p; ++i) {
+    const double Bi = std::max(-blo[i], bhi[i]);
+    if (Bi == 0.0) continue;
+    v += std::fabs(c[i]) * Bi;
+    for (int j = 0; j < p; ++j) {
+      const double Bj = std::max(-blo[j], bhi[j]);
+      if (Bj != 0.0) v += 0.5 * std::fabs(H[(size_t)i * p + j]) * Bi * Bj;
+    }
+  }
+  return v;
+}
+
+// f(S) on the columns `cols` by the splitting, as the kernel values a node.  reject_above: the solve stops as REJECTED once
+// D - margin is above it (+inf: never).
+inline L0ConPoint l0_con_solve(const L0ConProblem& P, const int* cols, int ms, double reject_above) {
+  L0ConPoint R;
+  const int m = P.m, p = P.p;
+  R.beta.assign((size_t)ms, 0.0);
+  R.mu.assign((size_t)ms, 0.0);
+  R.y.assign((size_t)m, 0.0);
+  for (int i = 0; i < m; ++i) {  // a row that is zero on the support and excludes 0: infeasible without a solve
+    bool zero = true;
+    for (int r = 0; r < ms; ++r) zero = zero && P.A[(size_t)i * p + cols[r]] == 0.0;
+    if (zero && (P.lo[i] > 0.0 || P.hi[i] < 0.0)) {
+      R.outcome = 1;
+      R.bound = HUGE_VAL;
+      return R;
+    }
+  }
+  auto f = std::make_unique<L0Factor>(P.H, P.c, p);
+  for (int r = 0; r < ms; ++r)
+    if (!f->push(cols[r])) return R;  // (cannot happen once l0_con_pd passed)
+  std::vector<double> b((size_t)ms), g((size_t)ms), curv((size_t)ms), t((size_t)m, 0.0), s((size_t)m), u((size_t)m, 0.0), z((size_t)ms);
+  if (ms > 0) f->solve(b.data());
+  double bref = 0.0;  // the size of the unconstrained minimiser: the scale of a row that binds at b = 0
+  for (int r = 0; r < ms; ++r) bref = std::max(bref, std::fabs(b[(size_t)r]));
+  for (int r = 0; r < ms; ++r) b[(size_t)r] = l0_con_clip(b[(size_t)r], P.blo[cols[r]], P.bhi[cols[r]]);
+  for (int r = 0; r < ms; ++r) {
+    double tt = -P.c[cols[r]], a2 = 0.0;
+    for (int k = 0; k < ms; ++k) tt += P.H[(size_t)cols[r] * p + cols[k]] * b[(size_t)k];
+    for (int i = 0; i < m; ++i) a2 += P.A[(size_t)i * p + cols[r]] * P.A[(size_t)i * p + cols[r]];
+    g[(size_t)r] = tt;
+    curv[(size_t)r] = P.H[(size_t)cols[r] * p + cols[r]] + P.rho * a2;
+  }
+  for (int i = 0; i < m; ++i) {
+    for (int k = 0; k < ms; ++k) t[(size_t)i] += P.A[(size_t)i * p + cols[k]] * b[(size_t)k];
+    s[(size_t)i] = l0_con_clip(t[(size_t)i], P.lo[i], P.hi[i]);
+  }
+  const int cap = P.max_sweeps > 0 ? P.max_sweeps : L0_CON_SWEEPS;
+  for (int sweep = 1; sweep <= cap; ++sweep) {
+    R.sweeps = sweep;
+    double maxb = bref;
+    for (int k = 0; k < ms; ++k) {
+      double pen = 0.0;
+      for (int i = 0; i < m; ++i) pen += P.A[(size_t)i * p + cols[k]] * (t[(size_t)i] - s[(size_t)i] + u[(size_t)i]);
+      const double nb = l0_con_step(b[(size_t)k], g[(size_t)k] + P.rho * pen, curv[(size_t)k], P.blo[cols[k]], P.bhi[cols[k]]);
+      const double dk = nb - b[(size_t)k];
+      if (dk != 0.0) {
+        for (int r = 0; r < ms; ++r) g[(size_t)r] += P.H[(size_t)cols[r] * p + cols[k]] * dk;
+        for (int i = 0; i < m; ++i) t[(size_t)i] += P.A[(size_t)i * p + cols[k]] * dk;
+        b[(size_t)k] = nb;
+      }
+      maxb = std::max(maxb, std::fabs(nb));
+    }
+    double sigma = 0.0, asum = 0.0, viol = 0.0;
+    for (int i = 0; i < m; ++i) {  // the multiplier step: s <- clip(A b + u), u <- A b + u - s, y = rho u
+      const double v = t[(size_t)i] + u[(size_t)i];
+      s[(size_t)i] = l0_con_clip(v, P.lo[i], P.hi[i]);
+      u[(size_t)i] = v - s[(size_t)i];
+      R.y[(size_t)i] = P.rho * u[(size_t)i];
+      const double st = l0_con_sigma(R.y[(size_t)i], P.lo[i], P.hi[i]);
+      sigma += st;
+      asum += std::fabs(st);
+      viol = std::max(viol, l0_con_violation(t[(size_t)i], P.lo[i], P.hi[i], maxb));
+    }
+    double primal = 0.0, zz = 0.0;
+    for (int r = 0; r < ms; ++r) {  // z = L^-1 (c - A^T y - mu), row by row
+      double aty = 0.0;
+      for (int i = 0; i < m; ++i) aty += P.A[(size_t)i * p + cols[r]] * R.y[(size_t)i];
+      R.mu[(size_t)r] = l0_con_box_mu(b[(size_t)r], g[(size_t)r] + aty, P.blo[cols[r]], P.bhi[cols[r]]);
+      const double st = l0_con_sigma(R.mu[(size_t)r], P.blo[cols[r]], P.bhi[cols[r]]);
+      sigma += st;
+      asum += std::fabs(st);
+      double v = P.c[cols[r]] - aty - R.mu[(size_t)r];
+      for (int k = 0; k < r; ++k) v -= f->L[r][k] * z[(size_t)k];
+      z[(size_t)r] = v / f->L[r][r];
+      zz += z[(size_t)r] * z[(size_t)r];
+      primal += 0.5 * b[(size_t)r] * (g[(size_t)r] - P.c[cols[r]]);
+    }
+    const L0ConDual d = l0_con_dual(zz, sigma, asum);
+    R.bound = d.bound;
+    R.primal = primal;
+    if (d.bound > reject_above) {
+      R.outcome = 1;
+      break;
+    }
+    if (l0_con_valued(primal, d, viol, 0.5 * f->ss)) {
+      R.outcome = 0;
+      break;
+    }
+  }
+  R.beta = b;
+  return R;
+}
+
+// D_S(y, mu) at ANY multipliers (the kernel and l0_con_solve evaluate it at their own): -inf where a sign is not admissible
+inline L0ConDual l0_con_dual_at(const L0ConProblem& P, const int* cols, int ms, const double* y /* [m] */, const double* mu /* [ms] */) {
+  auto f = std::make_unique<L0Factor>(P.H, P.c, P.p);
+  for (int r = 0; r < ms; ++r) (void)f->push(cols[r]);
+  double sigma = 0.0, asum = 0.0, zz = 0.0;
+  for (int i = 0; i < P.m; ++i) {
+    const double st = l0_con_sigma(y[i], P.lo[i], P.hi[i]);
+    sigma += st;
+    asum += std::fabs(st);
+  }
+  std::vector<double> z((size_t)ms);
+  for (int r = 0; r < ms && r < f->m; ++r) {
+    const double st = l0_con_sigma(mu[r], P.blo[cols[r]], P.bhi[cols[r]]);
+    sigma += st;
+    asum += std::fabs(st);
+    double v = P.c[cols[r]] - mu[r];
+    for (int i = 0; i < P.m; ++i) v -= P.A[(size_t)i * P.p + cols[r]] * y[i];
+    for (int k = 0; k < r; ++k) v -= f->L[r][k] * z[(size_t)k];
+    z[(size_t)r] = v / f->L[r][r];
+    zz += z[(size_t)r] * z[(size_t)r];
+  }
+  return l0_con_dual(zz, sigma, asum);
+}
+
+// Cholesky of a dense n x n matrix in place (lower triangle), pivots under the rule L0_PIVOT; and the two substitutions
+inline bool l0_dense_chol(std::vector<double>& M, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double t = M[(size_t)i * n + j];
+      for (int k = 0; k < j; ++k) t -= M[(size_t)i * n + k] * M[(size_t)j * n + k];
+      if (i == j) {
+        if (!(t > L0_PIVOT * M[(size_t)i * n + i])) return false;
+        M[(size_t)i * n + i] = std::sqrt(t);
+      } else {
+        M[(size_t)i * n + j] = t / M[(size_t)j * n + j];
+      }
+    }
+  return true;
+}
+inline void l0_dense_fwd(const std::vector<double>& M, int n, double* x) {  // x <- L^-1 x
+  for (int i = 0; i < n; ++i) {
+    double t = x[i];
+    for (int k = 0; k < i; ++k) t -= M[(size_t)i * n + k] * x[k];
+    x[i] = t / M[(size_t)i * n + i];
+  }
+}
+inline void l0_dense_bwd(const std::vector<double>& M, int n, double* x) {  // x <- L^-T x
+  for (int i = n - 1; i >= 0; --i) {
+    double t = x[i];
+    for (int k = i + 1; k < n; ++k) t -= M[(size_t)k * n + i] * x[k];
+    x[i] = t / M[(size_t)i * n + i];
+  }
+}
+
+// Polish of a valued point (the pattern of l0_l1_polish): the face it lies in -- the rows with a non-zero multiplier and the
+// equality rows held at their bound, the clipped coordinates where they are -- is solved exactly,
+//     [H_FF  A_WF^T] [b_F   ]   [c_F - H_FB b_B ]
+//     [A_WF  0     ] [lambda] = [d_W - A_WB b_B ],
+// and that point is taken only when every row and the box hold and every multiplier has the sign of its side.  It is then
+// the minimiser on S (the KKT conditions hold to rounding), whatever the splitting's last digits were.  Returns whether
+// the point was taken; R.beta, R.y (the rows' multipliers) and R.mu (the box multipliers) then describe it.
+inline bool l0_con_polish(const L0ConProblem& P, const int* cols, int ms, L0ConPoint& R) {
+  const int m = P.m, p = P.p;
+  std::vector<int> W, F, B;
+  std::vector<double> d;
+  for (int i = 0; i < m; ++i) {
+    if (P.lo[i] == P.hi[i]) {
+      bool zero = true;
+      for (int r = 0; r < ms; ++r) zero = zero && P.A[(size_t)i * p + cols[r]] == 0.0;
+      if (zero) continue;
+      W.push_back(i);
+      d.push_back(P.lo[i]);
+    } else if (R.y[(size_t)i] != 0.0) {
+      W.push_back(i);
+      d.push_back(R.y[(size_t)i] > 0.0 ? P.hi[i] : P.lo[i]);
+    }
+  }
+  for (int r = 0; r < ms; ++r) (R.beta[(size_t)r] <= P.blo[cols[r]] || R.beta[(size_t)r] >= P.bhi[cols[r]] ? B : F).push_back(r);
+  const int nf = (int)F.size(), nw = (int)W.size();
+  std::vector<double> b(R.beta), lam((size_t)nw, 0.0);
+  if (nf > 0) {
+    std::vector<double> HF((size_t)nf * nf), rhs((size_t)nf);
+    for (int i = 0; i < nf; ++i) {
+      const int ci = cols[F[(size_t)i]];
+      double t = P.c[ci];
+      for (int r : B) t -= P.H[(size_t)ci * p + cols[r]] * b[(size_t)r];
+      rhs[(size_t)i] = t;
+      for (int j = 0; j < nf; ++j) HF[(size_t)i * nf + j] = P.H[(size_t)ci * p + cols[F[(size_t)j]]];
+    }
+    if (!l0_dense_chol(HF, nf)) return false;
+    l0_dense_fwd(HF, nf, rhs.data());  // w0 = L^-1 rhs
+    if (nw > 0) {
+      if (nw > nf) return false;
+      std::vector<double> Y((size_t)nw * nf), S((size_t)nw * nw);  // Y row i = L^-1 A_{W_i, F}^T
+      for (int i = 0; i < nw; ++i) {
+        for (int j = 0; j < nf; ++j) Y[(size_t)i * nf + j] = P.A[(size_t)W[(size_t)i] * p + cols[F[(size_t)j]]];
+        l0_dense_fwd(HF, nf, &Y[(size_t)i * nf]);
+        double t = d[(size_t)i];
+        for (int r : B) t -= P.A[(size_t)W[(size_t)i] * p + cols[r]] * b[(size_t)r];
+        double yw = 0.0;
+        for (int j = 0; j < nf; ++j) yw += Y[(size_t)i * nf + j] * rhs[(size_t)j];
+        lam[(size_t)i] = yw - t;
+      }
+      for (int i = 0; i < nw; ++i)
+        for (int j = 0; j < nw; ++j) {
+          double t = 0.0;
+          for (int k = 0; k < nf; ++k) t += Y[(size_t)i * nf + k] * Y[(size_t)j * nf + k];
+          S[(size_t)i * nw + j] = t;
+        }
+      if (!l0_dense_chol(S, nw)) return false;
+      l0_dense_fwd(S, nw, lam.data());
+      l0_dense_bwd(S, nw, lam.data());
+      for (int i = 0; i < nw; ++i)
+        for (int j = 0; j < nf; ++j) rhs[(size_t)j] -= Y[(size_t)i * nf + j] * lam[(size_t)i];
+    }
+    l0_dense_bwd(HF, nf, rhs.data());
+    for (int i = 0; i < nf; ++i) b[(size_t)F[(size_t)i]] = rhs[(size_t)i];
+  } else if (nw > 0) {
+    return false;  // (every coordinate clipped and rows active: the multipliers of the splitting stay)
+  }
+  // the conditions that make the face point the minimiser
+  double maxb = 0.0;
+  for (int r = 0; r < ms; ++r) maxb = std::max(maxb, std::fabs(b[(size_t)r]));
+  for (int i : F)
+    if (!(b[(size_t)i] >= P.blo[cols[i]] && b[(size_t)i] <= P.bhi[cols[i]])) return false;
+  for (int i = 0; i < m; ++i) {
+    double t = 0.0;
+    for (int r = 0; r < ms; ++r) t += P.A[(size_t)i * p + cols[r]] * b[(size_t)r];
+    if (l0_con_violation(t, P.lo[i], P.hi[i], maxb) > 1e-12) return false;
+  }
+  std::vector<double> y((size_t)m, 0.0), mu((size_t)ms, 0.0);
+  for (int i = 0; i < nw; ++i) {
+    const int row = W[(size_t)i];
+    if (P.lo[row] != P.hi[row] && (R.y[(size_t)row] > 0.0 ? lam[(size_t)i] < 0.0 : lam[(size_t)i] > 0.0)) return false;
+    y[(size_t)row] = lam[(size_t)i];
+  }
+  for (int r : B) {
+    double gl = -P.c[cols[r]];
+    for (int k = 0; k < ms; ++k) gl += P.H[(size_t)cols[r] * p + cols[k]] * b[(size_t)k];
+    for (int i = 0; i < m; ++i) gl += P.A[(size_t)i * p + cols[r]] * y[(size_t)i];
+    const bool at_lo = b[(size_t)r] <= P.blo[cols[r]], at_hi = b[(size_t)r] >= P.bhi[cols[r]];
+    if ((at_hi && !at_lo && gl > 0.0) || (at_lo && !at_hi && gl < 0.0)) return false;
+    mu[(size_t)r] = -gl;
+  }
+  double val = 0.0;
+  for (int r = 0; r < ms; ++r) {
+    double t = 0.0;
+    for (int k = 0; k < ms; ++k) t += P.H[(size_t)cols[r] * p + cols[k]] * b[(size_t)k];
+    val += b[(size_t)r] * (0.5 * t - P.c[cols[r]]);
+  }
+  R.beta = b;
+  R.y = y;
+  R.mu = mu;
+  R.primal = val;
+  R.polished = true;
+  return true;
+}
+
+// The columns of the support `mask` (groups in search order), in search order
+inline int l0_con_columns(const std::vector<int>& gstart, unsigned long long mask, int* cols) {
+  int ms = 0;
+  for (int g = 0; g + 1 < (int)gstart.size(); ++g)
+    if ((mask >> g) & 1)
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) cols[ms++] = j;
+  return ms;
+}
+
+// A proven lower bound on f(all columns), the subtree bound's F_lb: the larger of q_all and the dual value at the multipliers
+// of a solve on all columns (whose quality decides how tight it is, never whether it holds; +inf when all columns together
+// are infeasible -- every support then is).  all: that solve, for the seed's repair.
+inline double l0_con_lower_bound(const L0ConProblem& P, double q_all, L0ConPoint* all = nullptr) {
+  int cols[L0_PMAX];
+  for (int j = 0; j < P.p; ++j) cols[j] = j;
+  L0ConPoint R = l0_con_solve(P, cols, P.p, HUGE_VAL);
+  const double lb = R.bound > q_all ? R.bound : q_all;  // (a NaN bound keeps q_all)
+  if (all) *all = std::move(R);
+  return lb;
 }
 
 }  // namespace slm

@@ -61,6 +61,20 @@
 // any refused include and the exclude branch is taken.  The wave keeps the smallest cnt at which it refused one and lowers
 // the control word L0_CAPACITY with cnt + 1 on exit: every support below such a refusal has at least cnt + 1 groups and
 // q >= q_all, so nothing unsearched is below q_all + alpha (c_min + 1) -- the host proves optimality against that.
+//
+// constrained mode (template parameter CON, slm_solve_l0_constrained; alone): rows lo <= A beta <= hi and a per-column box
+// blo_j <= beta_j <= bhi_j join the problem, so f(S) is a quadratic programme, +inf on an infeasible support.  f is monotone in
+// the support and f(S) >= q(S), so the register Cholesky stays an exact lower-bound FILTER as in l1 mode, and a node that
+// passes it is valued by the splitting of l0_host.hpp (l0_con_solve is this code on the host): lane r < m keeps beta_r and
+// (H beta - c)_r, lane i < rows keeps (A beta)_i, s_i and u_i; a sweep is the clipped coordinate descent with the row term
+// rho A_k^T (A beta - s + u) from one wave sum per coordinate, then s <- clip(A beta + u), u <- A beta + u - s.  Every sweep ends
+// with the dual value D_S(rho u, mu) <= f(S) -- one forward substitution with the factor the wave holds -- lowered by its
+// rounding margin: the candidate is VALUED when its rows hold and its value meets D to L0_CON_TOL, REJECTED when D is above
+// what it has to beat (the incumbent, or the wave's best under the tie rule; an infeasible support's D grows past every
+// feasible value), and UNSETTLED when the sweep cap runs out -- D + alpha |S| then goes into the control word L0_UNSETTLED by
+// one atomic min, a lower bound on that one support, and the search below goes on.  H is positive definite on all columns
+// (the host refuses the call otherwise), so no column is skipped and the cut of a group that brought none is off; q_all is
+// the host's proven lower bound on f(all columns).  A lives in LDS beside H, column by column with a padded stride.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,8 +89,12 @@ constexpr int L0_WAVES = 4;        // wavefronts per workgroup (they share H in 
 constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
-constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CAPACITY = 6, L0_CTL_WORDS = 8;
+constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CAPACITY = 6, L0_UNSETTLED = 7,
+              L0_UNSETTLED_COUNT = 8, L0_CTL_WORDS = 10;
 // (L0_CAPACITY, wide mode only: seeded with all ones, lowered to c_min + 1 by a wave that refused an include for capacity)
+// (L0_UNSETTLED, constrained mode only: seeded with all ones, lowered to the key of D + alpha |S| by a wave whose candidate ran
+//  out of sweeps; L0_UNSETTLED_COUNT counts them.  L0_DESCENTS counts the candidates valued in l1 and constrained mode.)
+constexpr int L0_CON_LD = L0_CON_MMAX + 1;  // the stride of a column of A in LDS (odd: lanes that read different columns spread over the banks)
 // profile mode: the incumbents of the sizes 1 .. 64 (keys, seeded by the host) follow the control words
 constexpr int L0_PROFILE_INC = L0_CTL_WORDS, L0_PROFILE_WORDS = L0_CTL_WORDS + L0_PMAX;
 
@@ -93,6 +111,14 @@ struct L0Args {
                                     //  profile mode: alpha is alpha_min)
   long long max_nodes;
   double eta_l1;                    // l1 mode only: the weight of ||beta||_1
+  // constrained mode only
+  const double* A;                  // [p][rows] column by column: A[j * rows + i], rows of unit norm, search order
+  const double* lo;                 // [rows]
+  const double* hi;                 // [rows]
+  const double* blo;                // [p] the box, blo_j <= 0 <= bhi_j
+  const double* bhi;                // [p]
+  int rows, con_sweeps;
+  double rho;
 };
 
 // order-preserving image of a double in an unsigned 64-bit integer (and back)
@@ -131,18 +157,42 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
 // L1 = false: the search above.  L1 = true: eta_l1 ||beta||_1 joins the objective (see the head of the file).
 // PROFILE = true: the best support of every size (see the head of the file); everything it adds sits under if constexpr.
 // WIDE = true: up to 128 columns and groups (see the head of the file); what it adds sits under if constexpr or behind Mask.
-template <bool L1, bool PROFILE = false, bool WIDE = false>
+// CON = true: linear constraints and a per-column box (see the head of the file); everything it adds sits under if constexpr.
+template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
   static_assert(!(L1 && PROFILE), "the profile mode has no l1 term");
   static_assert(!(L1 && WIDE), "there is no wide l1 mode");
+  static_assert(!(CON && (L1 || PROFILE || WIDE)), "the constrained mode stands alone");
   using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
   constexpr int PM = WIDE ? L0_WIDE_PMAX : L0_PMAX;
   __shared__ double Hs[WIDE ? PM * (PM + 1) / 2 : PM * PM];  // (wide: the lower triangle, row i at i (i + 1) / 2)
   __shared__ double cs[PM];
   __shared__ Mask needs[PM];
   __shared__ int gs[PM + 1];
+  // constrained mode: A by columns (column j at j * L0_CON_LD), the rows' bounds, the box, the curvature H_jj + rho ||A_j||^2
+  [[maybe_unused]] __shared__ double As[CON ? L0_PMAX * L0_CON_LD : 1];
+  [[maybe_unused]] __shared__ double los[CON ? L0_CON_MMAX : 1], his[CON ? L0_CON_MMAX : 1];
+  [[maybe_unused]] __shared__ double blos[CON ? L0_PMAX : 1], bhis[CON ? L0_PMAX : 1], curvs[CON ? L0_PMAX : 1];
   const int tid = threadIdx.x, lane = tid & 63;
   const int p = a.p, ng = a.ng, d = a.d, K = a.K;
+  [[maybe_unused]] const int rows = CON ? a.rows : 0;
+  if constexpr (CON) {
+    for (int e = tid; e < p * rows; e += 64 * L0_WAVES) {
+      const int j = e / rows, i = e - j * rows;
+      As[j * L0_CON_LD + i] = a.A[e];
+    }
+    for (int e = tid; e < rows; e += 64 * L0_WAVES) {
+      los[e] = a.lo[e];
+      his[e] = a.hi[e];
+    }
+    for (int e = tid; e < p; e += 64 * L0_WAVES) {
+      double a2 = 0.0;
+      for (int i = 0; i < rows; ++i) a2 = fma(a.A[e * rows + i], a.A[e * rows + i], a2);
+      blos[e] = a.blo[e];
+      bhis[e] = a.bhi[e];
+      curvs[e] = a.H[e * p + e] + a.rho * a2;
+    }
+  }
   if constexpr (WIDE) {
     for (int e = tid; e < p * p; e += 64 * L0_WAVES) {
       const int i = e / p, j = e - i * p;
@@ -180,6 +230,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   // l1 mode: lane r also stands for the r-th column of the SUPPORT (dependent ones included), na of them
   int acol = 0, na = 0, st_na = 0;
   long long descents_local = 0;
+  [[maybe_unused]] long long unsettled_local = 0;
   // the state before group g was decided, held by lane g (wide: by lane g & 63, in slot g >> 6)
   int st_m = 0;
   double st_ss = 0.0;
@@ -335,7 +386,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           // a group that brought no column leaves the value where it was and costs a slot (and alpha): unless another
           // group needs it, every support with it is matched by the same support without it
           // (not with an l1 term: a column equal to a + b replaces two coefficients by one, and the value falls)
-          if constexpr (!L1)
+          // (nor with constraints: a dependent column moves A beta -- and H is positive definite there, none is skipped)
+          if constexpr (!L1 && !CON)
             if (m == saved_m(g) && !l0m_test(needed, g)) ok = false;
         }
         if (ok) {
@@ -358,6 +410,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           if (mine && !l0m_any_outside(needm, incl) && val <= inc_k && (val < best_k || (val == best_k && l0m_less(incl, mask_k)))) {
             // back-substitution beta = L^-T w, row by row from the last: lane r contributes L[r][k] beta_r to entry k
             double beta = 0.0;
+            [[maybe_unused]] bool settled = true;  // (constrained mode: the candidate was valued)
 #pragma unroll
             for (int k = L0_PMAX - 1; k >= 0; --k) {
               if (k < m) {
@@ -400,6 +453,84 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               }
               val = 0.5 * l0_wave_sum(lane < na ? b1 * (gr - cs[acol]) : 0.0) + eta1 * l0_wave_sum(lane < na ? fabs(b1) : 0.0) +
                     alpha * (double)cnt;
+            } else if constexpr (CON) {
+              // the node's value is a quadratic programme: the splitting of l0_host.hpp (l0_con_solve, step for step) from the
+              // back-substituted beta, clipped.  Lane r < m: beta_r and (H beta - c)_r; lane i < rows: (A beta)_i, s_i, u_i.
+              ++descents_local;
+              settled = false;
+              const double rho = a.rho, half_ss = 0.5 * ss;
+              const double bref = l0_wave_max(lane < m ? fabs(beta) : 0.0);
+              const double blo = lane < m ? blos[mycol] : 0.0, bhi = lane < m ? bhis[mycol] : 0.0;
+              const double rlo = lane < rows ? los[lane] : 0.0, rhi = lane < rows ? his[lane] : 0.0;
+              beta = l0_con_clip(beta, blo, bhi);
+              double gr = lane < m ? -cs[mycol] : 0.0, tt = 0.0, amax = 0.0;
+              for (int k = 0; k < m; ++k) {
+                const int ck = __builtin_amdgcn_readlane(mycol, k);
+                const double bk = l0_bcast(beta, k), ak = lane < rows ? As[ck * L0_CON_LD + lane] : 0.0;
+                gr = fma(lane < m ? Hat(ck, mycol) : 0.0, bk, gr);
+                tt = fma(ak, bk, tt);
+                amax = fmax(amax, fabs(ak));
+              }
+              val = __builtin_inf();
+              // a row that is zero on the support and excludes 0: infeasible without a solve
+              if (l0_wave_max(lane < rows && amax == 0.0 && (rlo > 0.0 || rhi < 0.0) ? 1.0 : 0.0) == 0.0) {
+                double sv = l0_con_clip(tt, rlo, rhi), u = 0.0, bound = -__builtin_inf();
+                bool rejected = false;
+                for (int sweep = 0; sweep < a.con_sweeps; ++sweep) {
+                  double maxb = bref;
+                  for (int k = 0; k < m; ++k) {
+                    const int ck = __builtin_amdgcn_readlane(mycol, k);
+                    const double ak = lane < rows ? As[ck * L0_CON_LD + lane] : 0.0;
+                    const double pen = l0_wave_sum(ak * (tt - sv + u));
+                    const double bk = l0_bcast(beta, k), gk = l0_bcast(gr, k);
+                    const double nb = l0_con_step(bk, gk + rho * pen, curvs[ck], blos[ck], bhis[ck]);
+                    const double dk = nb - bk;
+                    if (dk != 0.0) {
+                      gr = fma(lane < m ? Hat(ck, mycol) : 0.0, dk, gr);
+                      tt = fma(ak, dk, tt);
+                      if (lane == k) beta = nb;
+                    }
+                    maxb = fmax(maxb, fabs(nb));
+                  }
+                  // the multiplier step, y = rho u; then D_S(y, mu): A^T y and mu per column, one forward substitution
+                  const double v = tt + u;
+                  sv = l0_con_clip(v, rlo, rhi);
+                  u = v - sv;
+                  const double y = lane < rows ? rho * u : 0.0;
+                  double aty = 0.0;
+                  for (int i = 0; i < rows; ++i) aty = fma(lane < m ? As[mycol * L0_CON_LD + i] : 0.0, l0_bcast(y, i), aty);
+                  const double mu = lane < m ? l0_con_box_mu(beta, gr + aty, blo, bhi) : 0.0;
+                  double b = lane < m ? cs[mycol] - aty - mu : 0.0, zz = 0.0;
+#pragma unroll
+                  for (int k = 0; k < L0_PMAX; ++k) {
+                    if (k < m) {
+                      const double zk = l0_bcast(b * invd, k);
+                      zz = fma(zk, zk, zz);
+                      b = fma(-Lrow[k], zk, b);
+                    }
+                  }
+                  const double st = (lane < rows ? l0_con_sigma(y, rlo, rhi) : 0.0) + (lane < m ? l0_con_sigma(mu, blo, bhi) : 0.0);
+                  const double sa = (lane < rows ? fabs(l0_con_sigma(y, rlo, rhi)) : 0.0) + (lane < m ? fabs(l0_con_sigma(mu, blo, bhi)) : 0.0);
+                  const L0ConDual dual = l0_con_dual(zz, l0_wave_sum(st), l0_wave_sum(sa));
+                  const double primal = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0);
+                  const double viol = l0_wave_max(lane < rows ? l0_con_violation(tt, rlo, rhi, maxb) : 0.0);
+                  bound = dual.bound + alpha * (double)cnt;
+                  // rejected: it cannot beat the incumbent, or the wave's best under the tie rule
+                  if (bound > inc_k || bound > best_k || (bound == best_k && !l0m_less(incl, mask_k))) {
+                    rejected = true;
+                    break;
+                  }
+                  if (l0_con_valued(primal, dual, viol, half_ss)) {
+                    settled = true;
+                    val = primal + alpha * (double)cnt;
+                    break;
+                  }
+                }
+                if (!settled && !rejected) {  // the sweep cap ran out: a lower bound on this one support
+                  ++unsettled_local;
+                  if (lane == 0) atomicMin(&a.ctl[L0_UNSETTLED], l0_key(bound));
+                }
+              }
             } else if (l0_wave_max(lane < m ? fabs(beta) : 0.0) > big_M) {
               // the box binds: cyclic coordinate descent with clipping on the support's block of H; lane r keeps
               // beta_r and the gradient entry (H beta - c)_r
@@ -430,7 +561,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               else
                 val = 0.5 * l0_wave_sum(lane < m ? beta * (gr - cs[mycol]) : 0.0) + alpha * (double)cnt;
             }
-            if (val <= inc_k && (val < best_k || (val == best_k && l0m_less(incl, mask_k)))) {
+            if (settled && val <= inc_k && (val < best_k || (val == best_k && l0m_less(incl, mask_k)))) {
               unsigned long long old = 0;
               if (lane == 0) old = atomicMin(PROFILE ? &a.ctl[L0_PROFILE_INC + cnt - 1] : &a.ctl[L0_INCUMBENT], l0_key(val));
               const double seen = l0_unkey(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(old >> 32)) << 32) |
@@ -514,8 +645,10 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   }
   if (lane == 0) {
     if (nodes_local > 0) atomicAdd(&a.ctl[L0_NODES], (unsigned long long)nodes_local);
-    if constexpr (L1)
+    if constexpr (L1 || CON)
       if (descents_local > 0) atomicAdd(&a.ctl[L0_DESCENTS], (unsigned long long)descents_local);
+    if constexpr (CON)
+      if (unsettled_local > 0) atomicAdd(&a.ctl[L0_UNSETTLED_COUNT], (unsigned long long)unsettled_local);
     if constexpr (!PROFILE) {
       const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
       a.best_val[wv] = best_v;

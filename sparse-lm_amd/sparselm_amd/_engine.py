@@ -93,6 +93,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_profile",
     "slm_solve_l0_wide",
     "slm_solve_l0_profile_wide",
+    "slm_solve_l0_constrained",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -355,6 +356,8 @@ def load_library():
             "slm_solve_l0_profile": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_profile_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
+            "slm_solve_l0_constrained": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, i32, vp, vp, vp, vp, i32, vp, P(C.c_uint64), P(dbl), P(i64),
+                                         vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1327,6 +1330,63 @@ class Dataset:
             "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
             "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
             "box_tol": 1e-12,  # L0_CD_TOL: relative change per sweep at which boxed candidates' descents stop
+        }
+
+    def solve_l0_constrained(self, A, lo, hi, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0,
+                             box_lo=None, box_hi=None, max_qp_sweeps=0, m=None, binding=None):
+        """``slm_solve_l0_constrained``: ``solve_l0`` subject to ``lo <= A b <= hi`` (``A``: m x p, m <= 64) and the per-column
+        box ``box_lo_j <= b_j <= box_hi_j`` (None: ``-big_M`` / ``+big_M``; each interval must contain 0).  ``G + 2 eta T`` must
+        be positive definite (``NotImplementedError`` otherwise).  Returns ``(beta, support mask, multipliers, info)``: the
+        rows' multipliers (> 0 where ``hi`` binds, < 0 where ``lo`` binds) and ``solve_l0``'s ``info`` with ``qp_solves``
+        (candidates valued on chip), ``unsettled`` (candidates whose ``max_qp_sweeps`` sweeps ran out), ``unsettled_bound``
+        (the lowest bound on those, ``inf``: none), ``con_tol`` and ``status`` ``"optimal"`` / ``"node_budget"`` /
+        ``"unsettled"``; ``q_all`` is the proven lower bound on the value of all columns that the subtree bound used.
+        ``m``: the row count handed to the engine (None: ``A``'s)."""
+        _sync_knobs()
+        G = self.n_groups
+        K = G if max_groups is None else int(max_groups)
+        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
+        A_ = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, self.p) if np.size(A) else np.zeros((0, self.p))
+        rows = A_.shape[0]
+        lo_ = _f64(np.broadcast_to(lo, (rows,)), "lo")
+        hi_ = _f64(np.broadcast_to(hi, (rows,)), "hi")
+        blo_ = None if box_lo is None else _f64(np.broadcast_to(box_lo, (self.p,)), "box_lo")
+        bhi_ = None if box_hi is None else _f64(np.broadcast_to(box_hi, (self.p,)), "box_hi")
+        m_ = rows if m is None else int(m)
+        need_ = None
+        if need is not None:
+            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
+            if need_.shape != (G,):
+                raise ValueError(f"need must have {G} entries")
+        if rows == 0:
+            A_ = lo_ = hi_ = None
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        if b is not None:
+            beta, support, lam, lower, nodes, rec, rc = b.solve_l0_constrained(
+                self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M), need_, int(max_nodes), A_, m_, lo_, hi_, blo_, bhi_,
+                int(max_qp_sweeps))
+            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
+        else:
+            beta, lam = np.empty(self.p), np.zeros(rows)
+            sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
+            infos = np.zeros(1, dtype=_INFO_DTYPE)
+            rc = self._lib.slm_solve_l0_constrained(
+                self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes), _ptr(A_), m_, _ptr(lo_),
+                _ptr(hi_), _ptr(blo_), _ptr(bhi_), int(max_qp_sweeps), _ptr(beta), C.byref(sup), C.byref(lb), C.byref(nd),
+                _ptr(lam) if rows else None, _as(infos, _PointInfo))
+            if rc != SLM_ERR_NOT_CONVERGED:
+                _check(rc)
+            support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
+        objective, unsettled, ubound = float(info["kkt"]), int(info["resid"]), float(info["beta_norm"])
+        status = "optimal" if rc == SLM_OK else ("unsettled" if unsettled and not objective <= ubound else "node_budget")
+        return beta, int(support), np.asarray(lam, dtype=np.float64), {
+            "objective": objective, "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
+            "status": status, "loss": float(info["loss"]), "seed_objective": float(info["mu"]), "q_all": float(info["L"]),
+            "launches": int(info["n_iter"]), "box_tol": 1e-12, "constrained": True, "qp_solves": int(info["rejects"]),
+            "unsettled": unsettled, "unsettled_bound": ubound,
+            "con_tol": 1e-9,  # L0_CON_TOL: rows and duality gap of a candidate valued on chip, relative (DESIGN 4d)
         }
 
     def solve_l0_l1(self, alpha=0.0, eta_l1=0.0, big_M=100.0, need=None, max_nodes=0, binding=None):

@@ -9,7 +9,8 @@ The reference exports 16 estimators from ``sparselm.model``.  Served here:
   (``slm_solve_l0``) for up to 64 columns and 64 groups, where the reference needs Gurobi or SCIP behind cvxpy.
 
 ``from sparselm_amd.model import L2L0`` works; the four are kept out of ``__all__`` because they share neither the
-penalty interface nor ``constraints=`` of the Lasso family, which is what ``__all__`` enumerates.  The fifth, ``L1L0``,
+penalty interface of the Lasso family, which is what ``__all__`` enumerates (they take linear constraints too, through ``add_constraints`` alone,
+solved inside the search: ``slm_solve_l0_constrained``).  The fifth, ``L1L0``,
 is served by the same search in its l1 mode; its import path is ``sparselm_amd.miqp.L1L0`` (``sparselm_amd.miqp`` exports
 all five), and it is not a name of this module.
 """

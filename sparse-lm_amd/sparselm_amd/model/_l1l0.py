@@ -35,10 +35,12 @@ class L1L0(RegularizedL0):
     Args as in the reference: ``groups``, ``alpha`` (l0 weight), ``eta`` (l1 weight), ``big_M``, ``hierarchy``,
     ``ignore_psd_check``, ``fit_intercept``, ``copy_X``, ``warm_start``, ``solver``, ``solver_options``.  Fitted attributes as
     for the other exact l0 estimators; ``solver_info_`` also holds ``descents``, the candidates that passed the lower-bound
-    filter and were valued by the descent.  There is no wide l1 mode: ``solver_options={"wide": True}`` is a ``ValueError``.
+    filter and were valued by the descent.  There is no wide l1 mode: ``solver_options={"wide": True}`` is a ``ValueError``; nor
+    a constrained one: constraints (``add_constraints``) are a ``ValueError`` at fit.
     """
 
     _wide_mode = False
+    _constrained_mode = False  # (constraints set through ``add_constraints`` are a ``ValueError`` at fit)
 
     _hyper_parameter_constraints: dict = {
         "eta": [Interval(type=Real, left=0.0, right=None, closed="left")],

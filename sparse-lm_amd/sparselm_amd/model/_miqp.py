@@ -17,7 +17,17 @@ with ``alpha = 0`` for the two best-subset classes (the reference's missing ``1/
 
 The fifth, ``L1L0`` (an l1 term beside the l0 one: a lasso per support), is served by the same search in its l1 mode
 (``slm_solve_l0_l1``); it lives in ``_l1l0.py`` and its import path is ``sparselm_amd.miqp.L1L0`` -- this module's ``__all__``
-and ``sparselm_amd.model`` keep the four names above.  There is no ``constraints=`` on these classes.
+and ``sparselm_amd.model`` keep the four names above.
+
+``add_constraints`` (``scipy.optimize.LinearConstraint`` / ``Bounds`` objects, as on the Lasso family; the reference's method
+of that name, examples/plot_chull.py:157-183 -- there is no ``constraints=`` constructor argument, the constructors stay
+the reference's) adds ``lo <= A beta <= hi`` to the problem of the four classes here:
+the search then runs in its constrained mode (``slm_solve_l0_constrained``), in which a support's value is a quadratic
+programme valued on chip and bounded from below by a dual value (DESIGN 4d "Constrained mode").  A ``Bounds`` interval that
+contains 0 narrows the ``big_M`` box of its column; one that excludes 0 forces the column active and becomes a row ``e_j``
+of ``A``.  The mode takes up to 64 rows and needs ``G + 2 eta W^T W`` positive definite (``eta > 0``, or a design of full
+column rank).  Refused: ``L1L0`` with constraints, constraints with ``wide``, more than 64 rows.  ``l0_profile`` has no
+constraints.
 
 ``sparselm_amd.miqp.l0_profile`` (``_l0_profile.py``) answers a whole scan over ``sparse_bound`` or ``alpha`` of the four
 classes here from one search; it shares ``_ExactL0._l0_setup`` and ``_ExactL0._l0_dataset`` with ``fit``.
@@ -30,16 +40,17 @@ import warnings
 from numbers import Real
 
 import numpy as np
-from sklearn.base import BaseEstimator, RegressorMixin
+from sklearn.base import BaseEstimator, RegressorMixin, _clone_parametrized
 from sklearn.exceptions import ConvergenceWarning
 from sklearn.utils._param_validation import Interval, validate_parameter_constraints
 from sklearn.utils.validation import _check_sample_weight, check_is_fitted, validate_data
 
 from .._utils.validation import check_groups, dense_group_index
+from ._constrained import _as_list, check_feasible, stack_constraints
 
 __all__ = ["BestSubsetSelection", "RidgedBestSubsetSelection", "RegularizedL0", "L2L0"]
 
-_KNOWN_OPTIONS = {"max_nodes", "device", "wide"}
+_KNOWN_OPTIONS = {"max_nodes", "device", "wide", "max_qp_sweeps"}
 _NARROW = 64  # L0_PMAX: columns and groups of the narrow search, independent columns of a support in the wide one
 
 
@@ -64,6 +75,50 @@ def _hierarchy_masks(hierarchy, groups, n_features):
     return need
 
 
+class _FoldedConstraints:
+    """``constraints`` as the constrained search takes them: the rows ``lo <= A b <= hi`` and the per-column box.
+
+    Every object is stacked by ``stack_constraints`` (``self.cs``: validation, the feasibility check, ``split``).  A stacked
+    row that comes from a ``Bounds`` entry whose interval contains 0 is FOLDED into the box of its column
+    (``box_lo`` / ``box_hi``); every other stacked row -- ``LinearConstraint`` rows, and ``Bounds`` entries that exclude 0
+    (the column is forced active) -- is a row of ``A``.  ``route[r]``: ``("row", i)`` the i-th row of ``A``, or
+    ``("box", j, lb, ub)``."""
+
+    def __init__(self, constraints, n_features):
+        from scipy.optimize import Bounds
+
+        p = int(n_features)
+        self.cs = cs = stack_constraints(constraints, p)
+        self.box_lo, self.box_hi = np.full(p, -np.inf), np.full(p, np.inf)
+        self.route, rows, r = [], [], 0
+        for obj, kept in zip(_as_list(constraints), cs.kept):
+            for j in kept:
+                lb, ub = cs.lo[r], cs.hi[r]
+                if isinstance(obj, Bounds) and lb <= 0.0 <= ub:
+                    self.box_lo[j], self.box_hi[j] = max(self.box_lo[j], lb), min(self.box_hi[j], ub)
+                    self.route.append(("box", int(j), float(lb), float(ub)))
+                else:
+                    self.route.append(("row", len(rows)))
+                    rows.append(r)
+                r += 1
+        self.A = np.ascontiguousarray(cs.A[rows]).reshape(len(rows), p)
+        self.lo, self.hi = cs.lo[rows].copy(), cs.hi[rows].copy()
+
+    def split(self, lam_rows, coef, mu, active_cols):
+        """One array of multipliers per constraint object: the engine's for the rows of ``A``; for a folded ``Bounds`` entry
+        the box multiplier ``mu_j`` where the coefficient of an active column sits at that entry's own bound
+        (> 0: ``ub`` binds, < 0: ``lb`` binds)."""
+        lam = np.zeros(self.cs.m)
+        for r, how in enumerate(self.route):
+            if how[0] == "row":
+                lam[r] = lam_rows[how[1]]
+            else:
+                _, j, lb, ub = how
+                if active_cols[j] and ((coef[j] == ub and mu[j] > 0.0) or (coef[j] == lb and mu[j] < 0.0)):
+                    lam[r] = mu[j]
+        return self.cs.split(lam)
+
+
 class _ExactL0(RegressorMixin, BaseEstimator):
     """Common part of the four estimators (the reference's ``MIQPl0``, _miqp/_base.py:22-167).
 
@@ -83,9 +138,52 @@ class _ExactL0(RegressorMixin, BaseEstimator):
     search, in which a support holds at most 64 independent columns.  Where that cap cut the search and the result is not
     proven all the same, ``solver_info_["status"]`` is ``"capacity"``, ``solver_info_["capacity_cut"]`` the number of groups
     from which includes were refused, and a ``ConvergenceWarning`` names the bound.
+
+    ``constraints`` (None, or the list that ``add_constraints`` built from ``scipy.optimize.LinearConstraint`` / ``Bounds``
+    objects) is an attribute, not a constructor argument -- the constructors are the reference's, which attaches constraints
+    through ``add_constraints`` too -- so ``get_params`` / ``set_params`` do not know it; ``clone`` carries it over.  The
+    constraints act on ``coef_``, never on the intercept.  The fit then also sets ``constraint_multipliers_`` (one array per object; > 0: ``ub`` binds, < 0: ``lb`` binds;
+    a ``Bounds`` entry folded into the box reports the box multiplier) and ``solver_info_`` holds ``constrained`` (True),
+    ``qp_solves`` (candidates that passed the lower-bound filter and were valued on chip), ``unsettled`` (candidates whose
+    sweeps ran out: ``solver_options["max_qp_sweeps"]``, default 20000), ``con_tol`` (rows and duality gap of a valued
+    candidate, relative) and ``max_violation`` (of ``coef_``, over every constraint).  ``status`` may be ``"unsettled"``: some
+    candidate's lower bound is below the incumbent, which is kept unproven under a ``ConvergenceWarning`` that names the bound.
+    A ``ValueError`` says so when no admissible support satisfies the constraints.
     """
 
     _wide_mode = True  # (L1L0: there is no wide l1 mode)
+    _constrained_mode = True  # (L1L0: nor a constrained one)
+
+    constraints = None  # (set by ``add_constraints`` alone: the constructors stay the reference's)
+
+    def add_constraints(self, constraints):
+        """Append linear constraints (a ``LinearConstraint`` / ``Bounds`` or a list of them) to ``self.constraints`` -- the
+        semantics of ``ProxRegressor.add_constraints``: a new list is built, the caller's list is never changed.  Returns the
+        estimator."""
+        old = [] if self.constraints is None else _as_list(self.constraints)
+        self.constraints = old + _as_list(constraints)
+        return self
+
+    def __sklearn_clone__(self):
+        """``constraints`` is no constructor parameter, so ``clone`` (``GridSearchCV``, ``cross_val_score``) would drop it:
+        the copy gets a list of its own with the same constraint objects."""
+        new = _clone_parametrized(self)
+        if self.constraints is not None:
+            new.constraints = list(self.constraints)
+        return new
+
+    def _l0_constraints(self, n_features, options):
+        """``constraints`` validated and folded, before a device is touched; None without constraints."""
+        if self.constraints is None:
+            return None
+        if not self._constrained_mode:
+            raise ValueError(f"{self.__class__.__name__} takes no constraints: the constrained search has no l1 term")
+        if options.get("wide"):
+            raise ValueError("constraints and solver_options['wide'] do not go together: the constrained search takes up to "
+                             f"{_NARROW} columns and groups")
+        folded = _FoldedConstraints(self.constraints, n_features)
+        check_feasible(folded.cs)
+        return folded
 
     _parameter_constraints: dict = {
         "ignore_psd_check": ["boolean"],
@@ -162,8 +260,15 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         eta_l1 = float(self._l1_weight())
         # (wide: only a problem beyond the narrow limits takes the wide search -- within them the bits stay what they were)
         wide = bool(options.get("wide")) and (X.shape[1] > _NARROW or n_groups > _NARROW)
+        folded = self._l0_constraints(X.shape[1], options)
+        lam = None
         with self._l0_dataset(X, y, w, gidx, n_groups, need, options) as (ds, x_mean, y_mean, need, max_nodes):
-            if eta_l1 > 0.0:
+            if folded is not None:
+                beta, support, lam, info = ds.solve_l0_constrained(
+                    folded.A, folded.lo, folded.hi, alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
+                    need=need, max_nodes=max_nodes, box_lo=folded.box_lo, box_hi=folded.box_hi,
+                    max_qp_sweeps=int(options.get("max_qp_sweeps", 0) or 0))
+            elif eta_l1 > 0.0:
                 beta, support, info = ds.solve_l0_l1(alpha=alpha, eta_l1=eta_l1, big_M=float(self.big_M), need=need, max_nodes=max_nodes)
             elif wide:
                 beta, support, info = ds.solve_l0_wide(alpha=alpha, max_groups=max_groups, eta=eta, T=T, big_M=float(self.big_M),
@@ -183,6 +288,13 @@ class _ExactL0(RegressorMixin, BaseEstimator):
                 "behind them; it is kept, unproven",
                 ConvergenceWarning,
             )
+        elif info["status"] == "unsettled":
+            warnings.warn(
+                f"{info['unsettled']} candidate support(s) ran out of sweeps: the incumbent (objective {info['objective']:.6g}) is "
+                f"above the proven lower bound {info['lower_bound']:.6g} on them; it is kept, unproven -- raise "
+                "solver_options['max_qp_sweeps']",
+                ConvergenceWarning,
+            )
         elif not info["proven_optimal"]:
             warnings.warn(
                 f"the node budget ran out after {info['nodes']} nodes: the incumbent (objective {info['objective']:.6g}, proven "
@@ -193,6 +305,17 @@ class _ExactL0(RegressorMixin, BaseEstimator):
         self.active_groups_ = np.array([(support >> i) & 1 for i in range(n_groups)], dtype=bool)
         self.solver_info_ = info
         self.intercept_ = float(y_mean - np.dot(x_mean, beta)) if self.fit_intercept else 0.0
+        if folded is not None:
+            # the box multipliers from X: mu = -(H beta - c + A^T lambda), H beta - c the gradient of the smooth part
+            Xc, yc = X - x_mean, y - y_mean
+            r = Xc @ beta - yc
+            g = Xc.T @ (r if w is None else w * r) / X.shape[0]
+            if eta > 0.0:
+                g = g + 2.0 * eta * (beta if T is None else 0.5 * (T + T.T) @ beta)
+            mu = -(g + folded.A.T @ lam)
+            gidx_ = np.arange(X.shape[1]) if gidx is None else np.asarray(gidx)
+            self.constraint_multipliers_ = folded.split(lam, beta, mu, self.active_groups_[gidx_])
+            info["max_violation"] = folded.cs.violation(beta)
         return self
 
     def predict(self, X):

@@ -24,7 +24,15 @@ Then the wide mode (``solver_options={"wide": True}``, ``slm_solve_l0_wide``), w
 kernel forced (through the dataset call) on the 25 x 20 and 25 x 30 problems above beside the narrow kernel on the same
 dataset in the same run -- the price of ``WIDE`` per node; ``BestSubsetSelection(sparse_bound=K)`` at 150 x 100 with K = 3
 and at 200 x 128 with K = 4; and ``L2L0(fit_intercept=True, alpha=3.16e-7, eta=1.66e-6)`` on the reference's 290 x 66
-cluster-expansion data under the default budget.  ``--only search`` / ``--only profile`` / ``--only wide`` runs one part."""
+cluster-expansion data under the default budget.
+
+Then the constrained mode (``add_constraints``, ``slm_solve_l0_constrained``), written to ``profiles/l0_constrained.txt``: the four
+estimators at the two sizes above under non-negativity and four random rows, beside the same estimator without constraints --
+nodes, ``qp_solves`` (candidates valued on chip), ``unsettled`` and the wall time of the whole call -- and one problem of 64
+columns under 64 rows.  An estimator without a ridge term at 25 x 30 is refused (its Gram is singular) and recorded so.  No
+rate is promised: how many candidates pass the filter depends on the constraints.
+
+``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` runs one part."""
 
 import argparse
 import math
@@ -180,14 +188,74 @@ def wide_section(out_path, max_nodes):
         fh.write(text)
 
 
+def constrained_section(out_path, max_nodes):
+    from scipy.optimize import Bounds, LinearConstraint
+    from sklearn.datasets import make_regression
+
+    from sparselm_amd import _engine
+    from sparselm_amd.model import L2L0, BestSubsetSelection, RegularizedL0, RidgedBestSubsetSelection
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    lines = [f"constrained exact l0 search on {name}, {dev['compute_units']} compute units: budget {max_nodes} nodes per call",
+             "(wall time of the whole Python call, second of two calls each; big_M = 1000; constraints: coefficients >= 0 and four random",
+             " rows r^T b <= 0.5 |r^T b_ols| + 1, beside the same estimator without constraints)", ""]
+    head = (f"{'estimator':28s} {'n x p':8s} {'constraints':>11s} {'nodes':>12s} {'qp_solves':>10s} {'unsettled':>9s} {'wall s':>9s} {'status':>11s} "
+            f"{'objective':>16s}")
+
+    def say(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    def run(make, X, y, shape, what):
+        try:
+            est, wall = timed(lambda: make().fit(X, y))
+        except NotImplementedError as exc:
+            say(f"{type(make()).__name__:28s} {shape:8s} {what:>11s} refused: {str(exc)[:110]}")
+            return
+        info = est.solver_info_
+        say(f"{type(est).__name__:28s} {shape:8s} {what:>11s} {info['nodes']:12d} {info.get('qp_solves', 0):10d} {info.get('unsettled', 0):9d} "
+            f"{wall:9.4f} {info['status']:>11s} {info['objective']:16.8e}")
+
+    say(head)
+    for p in (20, 30):
+        X, y = make_regression(25, p, n_informative=10, noise=1.0, random_state=0)
+        R = np.random.default_rng(p).standard_normal((4, p))
+        b_ols = np.linalg.lstsq(X, y, rcond=None)[0]
+        cons = [Bounds(0.0, np.inf), LinearConstraint(R, -np.inf, 0.5 * np.abs(R @ b_ols) + 1.0)]
+        for c, what in ((None, "none"), (cons, "nonneg + 4")):
+            opts = {"max_nodes": max_nodes}
+            for make in (lambda: BestSubsetSelection(sparse_bound=p // 2, big_M=1000, solver_options=opts).add_constraints(c),
+                         lambda: RidgedBestSubsetSelection(sparse_bound=p // 2, eta=1.0, big_M=1000, solver_options=opts).add_constraints(c),
+                         lambda: RegularizedL0(alpha=3.0, big_M=1000, solver_options=opts).add_constraints(c),
+                         lambda: L2L0(alpha=3.0, eta=1.0, big_M=1000, solver_options=opts).add_constraints(c)):
+                run(make, X, y, "25x%d" % p, what)
+    say("")
+    say("64 columns under 64 rows: L2L0(alpha = 3, eta = 1), rows r^T b <= 0.5 |r^T b_ols| + 1")
+    say(head)
+    X, y = make_regression(100, 64, n_informative=10, noise=1.0, random_state=0)
+    R = np.random.default_rng(64).standard_normal((64, 64))
+    b_ols = np.linalg.lstsq(X, y, rcond=None)[0]
+    cons = LinearConstraint(R, -np.inf, 0.5 * np.abs(R @ b_ols) + 1.0)
+    for c, what in ((None, "none"), (cons, "64 rows")):
+        run(lambda: L2L0(alpha=3.0, eta=1.0, big_M=1000, solver_options={"max_nodes": max_nodes}).add_constraints(c), X, y, "100x64", what)
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-nodes", type=int, default=1 << 24)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "l0_search.txt"))
     ap.add_argument("--profile-out", default=os.path.join(ROOT, "profiles", "l0_profile.txt"))
     ap.add_argument("--wide-out", default=os.path.join(ROOT, "profiles", "l0_wide.txt"))
-    ap.add_argument("--only", choices=["search", "profile", "wide"], default=None)
+    ap.add_argument("--constrained-out", default=os.path.join(ROOT, "profiles", "l0_constrained.txt"))
+    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained"], default=None)
     args = ap.parse_args()
+    if args.only in (None, "constrained"):
+        constrained_section(args.constrained_out, args.max_nodes)
     if args.only in (None, "wide"):
         wide_section(args.wide_out, args.max_nodes)
     if args.only in (None, "profile"):
