@@ -698,6 +698,29 @@ int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_gro
                               int64_t* nodes_out, slm_point_info* info);
 
 /*
+ * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant
+ * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The exact l0 search with the
+ * EXCLUSION BOUND (csrc/l0_kernels.hpp, template parameter XB): the arguments, outputs, argument errors and contract of
+ * slm_solve_l0 and slm_solve_l0_wide, and on any problem with a unique optimum that both searches finish the same
+ * coefficients, support and objective bit for bit (the winner is recomputed on the host by the same function).  What differs
+ * is the subtree bound: q_all + alpha (|S| + 1) becomes q(all \ E) + alpha (|S| + 1), E the columns of the groups the path has
+ * excluded, from P = H^-1 and P c by a second register Cholesky (of P on E) that grows with every exclude; the increment is
+ * lowered by the relative margin delta = 256 kappa_1 2^-53, kappa_1 = ||H||_1 ||P||_1 (csrc/l0_host.hpp, l0_excl_bound).  The
+ * search visits fewer nodes and each costs more; nothing else changes -- *lower_bound_out on a spent budget stays
+ * min(objective, q_all).  FALLBACK, not refusal: when H is not positive definite on all columns under the pivot rule (n < p
+ * with eta = 0, duplicated columns), or delta >= 1/2, the call runs the kernel and bound of slm_solve_l0 / slm_solve_l0_wide.
+ * info->mode says which ran: 5 the exclusion bound, 6 q_all because H is not positive definite, 7 q_all because delta >= 1/2;
+ * info->beta_norm holds delta (0 under mode 6) instead of ||beta||_2; the other fields as for the plain entries.
+ */
+int slm_solve_l0_xb(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T /* p*p or NULL */, double big_M,
+                    const uint64_t* need /* n_groups masks or NULL */, int64_t max_nodes /* <=0: default */, double* beta_out,
+                    uint64_t* support_out, double* lower_bound_out, int64_t* nodes_out, slm_point_info* info);
+int slm_solve_l0_xb_wide(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T /* p*p or NULL */,
+                         double big_M, const uint64_t* need /* 2 words per group, low word first, or NULL */,
+                         int64_t max_nodes /* <=0: default */, double* beta_out, uint64_t* support_out /* [2] */,
+                         double* lower_bound_out, int64_t* nodes_out, slm_point_info* info);
+
+/*
  * (added under ABI 24: a new symbol beside slm_solve_l0, no existing entry, structure or constant changes, so the version
  * stays 24 -- a caller that needs it looks the symbol up.)  The exact l0 search under LINEAR CONSTRAINTS on the coefficients
  * (csrc/l0_kernels.hpp, template parameter CON; the reference's add_constraints on its mixed-integer estimators,

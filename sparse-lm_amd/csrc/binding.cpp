@@ -301,6 +301,8 @@ uintptr_t dataset_create(uintptr_t eng, const py::array& X_in, const py::object&
 
 // slm_solve_l0: the exact search over supports.  Returns (beta, support mask, lower bound, nodes, record as bytes, status) --
 // status is SLM_OK or SLM_ERR_NOT_CONVERGED (the node budget ran out: the outputs hold the incumbent); anything else raises.
+// (XB: slm_solve_l0_xb -- the same search with the exclusion bound, the same signature and tuple.)
+template <bool XB>
 py::tuple solve_l0(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
                    const py::object& need, int64_t max_nodes) {
   Keep keep;
@@ -321,8 +323,11 @@ py::tuple solve_l0(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, do
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = slm_solve_l0(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(), &support,
-                      &lower, &nodes, static_cast<slm_point_info*>(info.mutable_data()));
+    slm_point_info* rec = static_cast<slm_point_info*>(info.mutable_data());
+    rc = XB ? slm_solve_l0_xb(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
+                              &support, &lower, &nodes, rec)
+            : slm_solve_l0(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(), &support,
+                           &lower, &nodes, rec);
   }
   if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
   return py::make_tuple(beta, support, lower, nodes, info, rc);
@@ -430,6 +435,8 @@ const uint64_t* need_words(const py::object& need, py::array_t<uint64_t, py::arr
 }
 
 // slm_solve_l0_wide: the tuple of solve_l0 with the support as an array of two words (the low one first).
+// (XB: slm_solve_l0_xb_wide.)
+template <bool XB>
 py::tuple solve_l0_wide(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
                         const py::object& need, int64_t max_nodes) {
   Keep keep;
@@ -446,8 +453,11 @@ py::tuple solve_l0_wide(uintptr_t ds, int64_t p, double alpha, int32_t max_group
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = slm_solve_l0_wide(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
-                           support.mutable_data(), &lower, &nodes, static_cast<slm_point_info*>(info.mutable_data()));
+    slm_point_info* rec = static_cast<slm_point_info*>(info.mutable_data());
+    rc = XB ? slm_solve_l0_xb_wide(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
+                                   support.mutable_data(), &lower, &nodes, rec)
+            : slm_solve_l0_wide(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
+                                support.mutable_data(), &lower, &nodes, rec);
   }
   if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
   return py::make_tuple(beta, support, lower, nodes, info, rc);
@@ -493,11 +503,13 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_lanes_reweighted", &solve_lanes_reweighted);
   m.def("solve_path_lanes", &solve_path_lanes);
   m.def("dataset_create", &dataset_create);
-  m.def("solve_l0", &solve_l0);
+  m.def("solve_l0", &solve_l0<false>);
+  m.def("solve_l0_xb", &solve_l0<true>);
   m.def("solve_l0_l1", &solve_l0_l1);
   m.def("solve_l0_constrained", &solve_l0_constrained);
   m.def("solve_l0_profile", &solve_l0_profile);
-  m.def("solve_l0_wide", &solve_l0_wide);
+  m.def("solve_l0_wide", &solve_l0_wide<false>);
+  m.def("solve_l0_xb_wide", &solve_l0_wide<true>);
   m.def("solve_l0_profile_wide", &solve_l0_profile_wide);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");

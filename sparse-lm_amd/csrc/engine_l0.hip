@@ -12,6 +12,9 @@
 // template over WIDE serves both widths; with WIDE = false it is the code there was before.
 // slm_solve_l0_constrained is the search on the kernel's CON instantiation: rows lo <= A beta <= hi and a per-column box, the
 // l0_con_* functions of l0_host.hpp for the seed, the bound on all columns and the winner (solve_l0_con_impl).
+// slm_solve_l0_xb and slm_solve_l0_xb_wide are slm_solve_l0 and slm_solve_l0_wide on the kernel's XB instantiations: the subtree
+// bound on everything not yet excluded (l0_excl_plan of l0_host.hpp hands over P = H^-1, P c and the margin delta); where H is
+// not positive definite on all columns, or delta >= 1/2, they run the plain kernel and say so in info->mode.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -160,7 +163,10 @@ struct L0DevGuard {
 // Both entries.  eta_l1 > 0 is l1 mode (the kernel's L1 instantiation, the l0_l1_* functions of l0_host.hpp); eta_l1 == 0 is the
 // search without an l1 term, instruction for instruction what it was before there was one.
 // WIDE: the kernel's wide instantiation (no l1 mode there), masks of two words in need, support_out and on the device.
-template <bool WIDE>
+// XB: the exclusion bound (never with an l1 term); XB = false is the code there was.  info->mode then says which bound ran:
+// 5 the exclusion bound (info->beta_norm = delta), 6 q_all because H is not positive definite on all columns, 7 q_all because
+// delta >= 1/2 (info->beta_norm = delta).
+template <bool WIDE, bool XB = false>
 int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double eta_l1, double big_M,
                   const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* lower_bound_out,
                   int64_t* nodes_out, slm_point_info* info) {
@@ -187,6 +193,9 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   const std::vector<int>&cols = P.cols, &gstart = P.gstart, &gorder = P.gorder;
   const std::vector<Mask>& needo = P.needo;
   const double q_all = P.q_all;
+  [[maybe_unused]] L0ExclPlan plan;
+  if constexpr (XB) plan = l0_excl_plan(H.data(), c.data(), p);
+  const bool xb = XB && plan.reason == 0;
 
   // ---- the greedy seed of the incumbent ------------------------------------------------------------------------------------
   std::vector<double> beta_s((size_t)p);
@@ -209,9 +218,15 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   const int blocks = (int)std::max<long long>(1, std::min<long long>(2ll * eng->cus, (n_tickets + L0_WAVES - 1) / L0_WAVES));
   const int waves = blocks * L0_WAVES;
   // one block of 8-byte words: control | best values | best supports | H | c | need | group starts (a mask: MW words)
+  // | exclusion bound: P | P c
   const size_t off_bv = L0_CTL_WORDS, off_bm = off_bv + (size_t)waves, off_H = off_bm + MW * (size_t)waves, off_c = off_H + (size_t)p * p,
-               off_need = off_c + (size_t)p, off_gs = off_need + MW * (size_t)ng, words = off_gs + (size_t)ng + 1;
+               off_need = off_c + (size_t)p, off_gs = off_need + MW * (size_t)ng, off_P = off_gs + (size_t)ng + 1,
+               off_bh = off_P + (xb ? (size_t)p * p : 0), words = off_bh + (xb ? (size_t)p : 0);
   std::vector<unsigned long long> h(words, 0ull);
+  if (xb) {
+    memcpy(&h[off_P], plan.P.data(), sizeof(double) * (size_t)p * p);
+    memcpy(&h[off_bh], plan.bhat.data(), sizeof(double) * (size_t)p);
+  }
   h[L0_INCUMBENT] = l0_key(seed_val);
   if constexpr (WIDE) h[L0_CAPACITY] = ~0ull;  // (lowered by a wave that refused an include for capacity)
   memcpy(&h[off_H], H.data(), sizeof(double) * (size_t)p * p);
@@ -236,7 +251,14 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   k.alpha = alpha; k.big_M = big_M; k.q_all = bound;
   k.eta_l1 = eta_l1;
   k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
-  if constexpr (WIDE)
+  if (xb) {
+    if constexpr (XB) {
+      k.P = reinterpret_cast<const double*>(dev + off_P);
+      k.bhat = reinterpret_cast<const double*>(dev + off_bh);
+      k.xb_delta = plan.delta;
+      hipLaunchKernelGGL((l0_search_kernel<false, false, WIDE, false, true>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    }
+  } else if constexpr (WIDE)
     hipLaunchKernelGGL((l0_search_kernel<false, false, true>), dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
   else if (l1)
     hipLaunchKernelGGL(l0_search_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
@@ -304,6 +326,10 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
     double bn = 0.0;
     for (int j = 0; j < p; ++j) bn += beta_out[j] * beta_out[j];
     info->beta_norm = std::sqrt(bn);
+    if constexpr (XB) {  // which bound ran, and its margin
+      info->mode = plan.reason == 0 ? 5 : (plan.reason == 1 ? 6 : 7);
+      info->beta_norm = plan.delta;
+    }
   }
   if (!finished) return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld) ran out before the search finished: the incumbent is returned",
                              (long long)k.max_nodes);
@@ -690,6 +716,22 @@ extern "C" int slm_solve_l0_wide(slm_dataset* ds, double alpha, int32_t max_grou
                                  const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
                                  double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
   return solve_l0_impl<true>(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out, info);
+}
+
+// slm_solve_l0 and slm_solve_l0_wide with the exclusion bound (the kernel's XB instantiations): the same signature, contract and
+// result; info->mode tells which bound ran (5: exclusion, 6 / 7: q_all) and info->beta_norm holds the margin delta.
+extern "C" int slm_solve_l0_xb(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
+                               const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
+                               double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_impl<false, true>(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out,
+                                    info);
+}
+
+extern "C" int slm_solve_l0_xb_wide(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,
+                                    const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
+                                    double* lower_bound_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_impl<true, true>(ds, alpha, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, lower_bound_out, nodes_out,
+                                   info);
 }
 
 // The reference's L1L0 (_regularized_l0.py:258-410): no cardinality bound, no ridge term, eta_l1 ||beta||_1.

@@ -7,7 +7,8 @@
 // (slm_solve_l0_wide, slm_solve_l0_profile_wide; tests/l0_wide_host_test.cpp) adds masks of two words, a factor with a capacity
 // parameter and the capacity rule.  The constrained mode (slm_solve_l0_constrained; tests/l0_con_host_test.cpp) adds the splitting
 // that values a support under linear constraints, the dual value host and device share, its face polish, the positive-definite
-// check and the lower bound on all columns.
+// check and the lower bound on all columns.  The exclusion bound (slm_solve_l0_xb, slm_solve_l0_xb_wide;
+// tests/l0_bound_host_test.cpp) adds P = H^-1, P c, the margin delta and the guarded bound host and device share.
 #pragma once
 #include <stddef.h>
 
@@ -254,6 +255,76 @@ constexpr double l0_capacity_bound(double q_all, double alpha, int cut) { return
 constexpr bool l0_capacity_proven(double objective, double q_all, double alpha, int cut) {
   return cut == 0 || objective <= l0_capacity_bound(q_all, alpha, cut);
 }
+
+// ---- exclusion bound (slm_solve_l0_xb, slm_solve_l0_xb_wide; DESIGN 4d "Exclusion bound") ------------------------------------
+//
+// With P = H^-1 and bhat = P c (q_all = -1/2 c^T bhat), every support S that avoids the excluded columns E has
+//     q(S) >= q(all \ E) = q_all + 1/2 bhat_E^T (P_EE)^-1 bhat_E = q_all + 1/2 ||w'||^2,   w' = L'^-1 bhat_E,  L' L'^T = P_EE
+// (q is monotone in the support; the block inverse of H).  Along a depth-first path E grows in the order of the decisions, so
+// L' grows by the append of L0FactorT on (P, bhat) instead of (H, c) -- the kernel keeps it in a second register row of
+// L0_XCAP entries per lane.  ANY sub-collection of E gives a valid, weaker bound: a column whose pivot fails the pivot rule
+// and every column that arrives when the factor holds L0_XCAP rows are left out of it.
+// The increment comes from a P that is itself a rounded inverse, so it is trusted only up to the relative margin
+//     delta = L0_XB_C kappa_1 2^-53,   kappa_1 = ||H||_1 ||P||_1;
+// L0_XB_C is 16 times the worst overshoot of the unguarded fp64 increment over a long-double Cholesky of H on all \ E that
+// tests/l0_bound_host_test.cpp measures (12.2 units of kappa_1 2^-53 1/2 ssx).  delta >= 1/2, or
+// an H that is not positive definite on all columns under the pivot rule, runs the search with the plain bound q_all.
+constexpr int L0_XCAP = 64;          // rows of the exclusion factor (columns of E the bound can use along one path)
+constexpr double L0_XB_C = 256.0;     // >= 16 x 12.2, the worst overshoot measured
+// what the kernel compares: the guarded q(all \ E).  One function for host and device (constexpr, as l0_l1_step is).
+constexpr double l0_excl_bound(double q_all, double ssx, double delta) {
+  return q_all + 0.5 * ssx * (1.0 - delta) - 1e-10 * ((q_all < 0.0 ? -q_all : q_all) + 0.5 * ssx);
+}
+struct L0ExclPlan {
+  int reason = 0;  // 0: the exclusion bound runs; 1: H is not positive definite on all columns; 2: delta >= 1/2
+  double kappa1 = 0.0, delta = 0.0;
+  std::vector<double> P, bhat;  // [p][p], [p]: search order
+};
+inline double l0_excl_delta(double kappa1) { return L0_XB_C * kappa1 * 0x1p-53; }
+// P, bhat, kappa_1 and delta from the factor of H on all columns in search order
+inline L0ExclPlan l0_excl_plan(const double* H, const double* c, int p) {
+  L0ExclPlan R;
+  auto f = std::make_unique<L0FactorT<L0_WIDE_PMAX>>(H, c, p);
+  for (int j = 0; j < p; ++j)
+    if (!f->push(j)) {
+      R.reason = 1;
+      return R;
+    }
+  // X = L^-1 (lower triangle, column by column), P = X^T X
+  std::vector<double> X((size_t)p * p, 0.0);
+  for (int j = 0; j < p; ++j)
+    for (int i = j; i < p; ++i) {
+      double t = i == j ? 1.0 : 0.0;
+      for (int k = j; k < i; ++k) t -= f->L[i][k] * X[(size_t)k * p + j];
+      X[(size_t)i * p + j] = t / f->L[i][i];
+    }
+  R.P.assign((size_t)p * p, 0.0);
+  for (int i = 0; i < p; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double t = 0.0;
+      for (int k = i; k < p; ++k) t += X[(size_t)k * p + i] * X[(size_t)k * p + j];
+      R.P[(size_t)i * p + j] = R.P[(size_t)j * p + i] = t;
+    }
+  R.bhat.assign((size_t)p, 0.0);
+  if (p > 0) f->solve(R.bhat.data());
+  double h1 = 0.0, p1 = 0.0;
+  for (int j = 0; j < p; ++j) {
+    double sh = 0.0, sp = 0.0;
+    for (int i = 0; i < p; ++i) {
+      sh += std::fabs(H[(size_t)i * p + j]);
+      sp += std::fabs(R.P[(size_t)i * p + j]);
+    }
+    h1 = std::max(h1, sh);
+    p1 = std::max(p1, sp);
+  }
+  R.kappa1 = h1 * p1;
+  R.delta = l0_excl_delta(R.kappa1);
+  if (!(R.delta < 0.5)) R.reason = 2;
+  return R;
+}
+// The exclusion factor as the kernel keeps it: L0FactorT on (P, bhat) with L0_XCAP rows; push() refuses a column the pivot
+// rule skips and every column once the rows are full, and ss is ssx = ||w'||^2.
+using L0ExclFactor = L0FactorT<L0_XCAP>;
 
 // Greedy forward selection over the groups (H, c, gstart and the hierarchy needo in search order), up to K of them: one
 // admissible support per size, handed to visit(size, support, value) with the value value_of(support) gives it (the kernel's

@@ -75,6 +75,21 @@
 // one atomic min, a lower bound on that one support, and the search below goes on.  H is positive definite on all columns
 // (the host refuses the call otherwise), so no column is skipped and the cut of a group that brought none is off; q_all is
 // the host's proven lower bound on f(all columns).  A lives in LDS beside H, column by column with a padded stride.
+//
+// exclusion bound (template parameter XB, slm_solve_l0_xb / slm_solve_l0_xb_wide; with WIDE or alone): the subtree bound becomes
+// q(all \ E) + alpha (|S| + 1) >= incumbent, E the columns of the groups the path has excluded -- every support below the node
+// avoids them and q is monotone.  With P = H^-1 and bhat = P c from the host (l0_excl_plan of l0_host.hpp),
+//     q(all \ E) = q_all + 1/2 ||w'||^2,   w' = L'^-1 bhat_E,   L' L'^T = P_EE,
+// and E grows in the order of the decisions, so L' grows by the SAME append as L (L0_APPEND below), on P and bhat in LDS in
+// H's layout: lane r keeps row r of L' in a second register row of L0_XCAP entries with 1 / L'[r][r] and w'_r, the wave keeps
+// the column count mx and ssx = ||w'||^2, lane g (wide: slot g >> 6) saves both from before group g was decided beside st_m and
+// st_ss, and every exclude -- back from an include, a forced 0 bit of the ticket, a refused include, a group that brought no
+// column -- restores them and appends the group's columns.  A column whose pivot is <= L0_PIVOT P_jj is left out, and so is every
+// column once mx == L0_XCAP: a sub-collection of E gives a valid, weaker bound.  Includes do not touch L'.  What is compared
+// is l0_excl_bound (l0_host.hpp): the increment lowered by the margin delta the host derived from the conditioning of H.
+// LDS: 67 336 B narrow, 136 712 B wide (one workgroup per CU); 256 VGPRs + 80 / 103 AGPRs at L0_XCAP = 64, no scratch, 1 wave/SIMD.
+// Measured in profiles/l0_bound.txt, L0_XCAP = 32 beside it (256 + 19 / 41 registers, also 1 wave/SIMD: the same time on the 25-row
+// problems, more nodes and more time on the reference's 290 x 66 data).  Not measured: the time one wavefront walks alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -119,6 +134,10 @@ struct L0Args {
   const double* bhi;                // [p]
   int rows, con_sweeps;
   double rho;
+  // exclusion bound only
+  const double* P;                  // [p][p] H^-1, search order
+  const double* bhat;               // [p] P c
+  double xb_delta;                  // the relative margin of the increment (l0_excl_bound)
 };
 
 // order-preserving image of a double in an unsigned 64-bit integer (and back)
@@ -154,19 +173,39 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
   return v;
 }
 
+// The append both factors run: x = L^-1 b by columns (b: lane r holds the new column's entry against the column lane r stands
+// for), x_k broadcast from lane k at step k and written into lane m's row; s2 = ||x||^2 and sw = x^T w come back.  Every index
+// into the register row is a compile-time constant; the steps are guarded by the wave-uniform column count m.  (A macro, not
+// a function: a register row handed to a function by reference left the six older instantiations with other register
+// counts; expanded in place they keep theirs.)
+#define L0_APPEND(CAP, row, invd, w, m, b, s2, sw)    \
+  _Pragma("unroll") for (int k = 0; k < (CAP); ++k) { \
+    if (k < (m)) {                                    \
+      const double xk = l0_bcast((b) * (invd), k);    \
+      s2 = fma(xk, xk, s2);                           \
+      sw = fma(xk, l0_bcast(w, k), sw);               \
+      b = fma(-row[k], xk, b);                        \
+      if (lane == (m)) row[k] = xk;                   \
+    }                                                 \
+  }
+
 // L1 = false: the search above.  L1 = true: eta_l1 ||beta||_1 joins the objective (see the head of the file).
 // PROFILE = true: the best support of every size (see the head of the file); everything it adds sits under if constexpr.
 // WIDE = true: up to 128 columns and groups (see the head of the file); what it adds sits under if constexpr or behind Mask.
 // CON = true: linear constraints and a per-column box (see the head of the file); everything it adds sits under if constexpr.
-template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false>
+// XB = true: the exclusion bound (see the head of the file); everything it adds sits under if constexpr.
+template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false, bool XB = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
   static_assert(!(L1 && PROFILE), "the profile mode has no l1 term");
   static_assert(!(L1 && WIDE), "there is no wide l1 mode");
   static_assert(!(CON && (L1 || PROFILE || WIDE)), "the constrained mode stands alone");
+  static_assert(!(XB && (L1 || PROFILE || CON)), "the exclusion bound serves the plain search, narrow and wide");
   using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
   constexpr int PM = WIDE ? L0_WIDE_PMAX : L0_PMAX;
   __shared__ double Hs[WIDE ? PM * (PM + 1) / 2 : PM * PM];  // (wide: the lower triangle, row i at i (i + 1) / 2)
   __shared__ double cs[PM];
+  [[maybe_unused]] __shared__ double Ps[XB ? (WIDE ? PM * (PM + 1) / 2 : PM * PM) : 1];  // exclusion bound: P in H's layout, and bhat
+  [[maybe_unused]] __shared__ double bhs[XB ? PM : 1];
   __shared__ Mask needs[PM];
   __shared__ int gs[PM + 1];
   // constrained mode: A by columns (column j at j * L0_CON_LD), the rows' bounds, the box, the curvature H_jj + rho ||A_j||^2
@@ -202,6 +241,17 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     for (int e = tid; e < p * p; e += 64 * L0_WAVES) Hs[e] = a.H[e];
   }
   for (int e = tid; e < p; e += 64 * L0_WAVES) cs[e] = a.c[e];
+  if constexpr (XB) {
+    if constexpr (WIDE) {
+      for (int e = tid; e < p * p; e += 64 * L0_WAVES) {
+        const int i = e / p, j = e - i * p;
+        if (j <= i) Ps[i * (i + 1) / 2 + j] = a.P[e];
+      }
+    } else {
+      for (int e = tid; e < p * p; e += 64 * L0_WAVES) Ps[e] = a.P[e];
+    }
+    for (int e = tid; e < p; e += 64 * L0_WAVES) bhs[e] = a.bhat[e];
+  }
   if constexpr (WIDE) {
     for (int e = tid; e < ng; e += 64 * L0_WAVES) needs[e] = L0Mask128{a.need[2 * e], a.need[2 * e + 1]};
   } else {
@@ -219,6 +269,15 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     }
   };
 
+  [[maybe_unused]] auto Pat = [&](int i, int j) -> double {  // P[i][j] (symmetric) from LDS
+    if constexpr (WIDE) {
+      const int hi = i > j ? i : j, lo = i > j ? j : i;
+      return Ps[hi * (hi + 1) / 2 + lo];
+    } else {
+      return Ps[i * p + j];
+    }
+  };
+
   const long long n_tickets = 1ll << d;
   const double alpha = a.alpha, big_M = a.big_M, q_all = a.q_all;
   // lane r: row r of L (entries below the diagonal), 1 / L[r][r], w[r], the column it stands for
@@ -227,6 +286,16 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   for (int k = 0; k < L0_PMAX; ++k) Lrow[k] = 0.0;
   double invd = 0.0, w = 0.0;
   int mycol = 0;
+  // exclusion bound: lane r holds row r of L' (P on the excluded columns), 1 / L'[r][r], w'[r] and the column it stands for;
+  // mx columns, ssx = ||w'||^2 (wave-uniform), and what they were before group g was decided (lane g; wide: slot g >> 6)
+  [[maybe_unused]] double Xrow[XB ? L0_XCAP : 1];
+  [[maybe_unused]] double xinvd = 0.0, xw = 0.0, ssx = 0.0, st_ssx = 0.0, st_ssx1 = 0.0;
+  [[maybe_unused]] int xcol = 0, mx = 0, st_mx = 0, st_mx1 = 0;
+  [[maybe_unused]] const double xb_delta = XB ? a.xb_delta : 0.0;
+  if constexpr (XB) {
+#pragma unroll
+    for (int k = 0; k < L0_XCAP; ++k) Xrow[k] = 0.0;
+  }
   // l1 mode: lane r also stands for the r-th column of the SUPPORT (dependent ones included), na of them
   int acol = 0, na = 0, st_na = 0;
   long long descents_local = 0;
@@ -290,6 +359,10 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     int m = 0, cnt = 0, depth = 0;
     na = 0;
     double ss = 0.0;
+    if constexpr (XB) {
+      mx = 0;
+      ssx = 0.0;
+    }
     Mask incl = l0m_none<Mask>(), needm = l0m_none<Mask>();
     bool down = true;
     // every pass of this loop either descends one level, or climbs one, or turns an include into an exclude: at most
@@ -301,6 +374,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
         bool stop_here;
         if constexpr (PROFILE)  // the subtree bound against E(cnt)
           stop_here = depth >= ng || cnt >= K || l0_profile_cut(q_all, alpha, cnt, cnt == 0 ? 0.0 : l0_bcast(env, cnt - 1));
+        else if constexpr (XB)  // the subtree bound on everything not yet excluded
+          stop_here = depth >= ng || cnt >= K || !(l0_excl_bound(q_all, ssx, xb_delta) + alpha * (double)(cnt + 1) < inc);
         else
           stop_here = depth >= ng || cnt >= K || !(q_all + alpha * (double)(cnt + 1) < inc);
         if (stop_here) {
@@ -316,17 +391,29 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               st_m = m;
               st_ss = ss;
               st_need = needm;
+              if constexpr (XB) {
+                st_mx = mx;
+                st_ssx = ssx;
+              }
             }
           } else if (lane == g - 64) {
             st_m1 = m;
             st_ss1 = ss;
             st_need1 = needm;
+            if constexpr (XB) {
+              st_mx1 = mx;
+              st_ssx1 = ssx;
+            }
           }
         } else if (lane == g) {
           st_m = m;
           st_ss = ss;
           st_need = needm;
           if constexpr (L1) st_na = na;
+          if constexpr (XB) {
+            st_mx = mx;
+            st_ssx = ssx;
+          }
         }
         bool ok = want;
         if (ok) ok = !l0m_any_outside(l0m_and(needs[g], l0m_below<Mask>(g)), incl);  // hierarchy: it needs a group that was excluded
@@ -355,16 +442,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
             const double hjj = Hat(j, j);
             double b = lane < m ? Hat(j, mycol) : 0.0;  // (H is symmetric: the lanes read one row)
             double s2 = 0.0, sw = 0.0;
-#pragma unroll
-            for (int k = 0; k < L0_PMAX; ++k) {
-              if (k < m) {
-                const double xk = l0_bcast(b * invd, k);
-                s2 = fma(xk, xk, s2);
-                sw = fma(xk, l0_bcast(w, k), sw);
-                b = fma(-Lrow[k], xk, b);
-                if (lane == m) Lrow[k] = xk;
-              }
-            }
+            L0_APPEND(L0_PMAX, Lrow, invd, w, m, b, s2, sw)
             const double piv = hjj - s2;
             if (piv > L0_PIVOT * hjj) {  // (otherwise the column depends on the included ones: it is skipped, its beta is 0)
               if constexpr (WIDE)
@@ -627,6 +705,40 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           depth = g;
           down = false;
         } else {
+          if constexpr (XB) {
+            // the group joins E: the exclusion factor as it was before the group was decided, then its columns appended
+            // (a dependent column and every column beyond L0_XCAP rows are left out: a sub-collection of E bounds too)
+            if constexpr (WIDE) {
+              if (g < 64) {
+                mx = __builtin_amdgcn_readlane(st_mx, g);
+                ssx = l0_bcast(st_ssx, g);
+              } else {
+                mx = __builtin_amdgcn_readlane(st_mx1, g - 64);
+                ssx = l0_bcast(st_ssx1, g - 64);
+              }
+            } else {
+              mx = __builtin_amdgcn_readlane(st_mx, g);
+              ssx = l0_bcast(st_ssx, g);
+            }
+            const int x0 = __builtin_amdgcn_readfirstlane(gs[g]), x1 = __builtin_amdgcn_readfirstlane(gs[g + 1]);
+            for (int j = x0; j < x1 && mx < L0_XCAP; ++j) {
+              const double pjj = Pat(j, j);
+              double b = lane < mx ? Pat(j, xcol) : 0.0;
+              double s2 = 0.0, sw = 0.0;
+              L0_APPEND(L0_XCAP, Xrow, xinvd, xw, mx, b, s2, sw)
+              const double piv = pjj - s2;
+              if (piv > L0_PIVOT * pjj) {
+                const double lmm = sqrt(piv), wm = (bhs[j] - sw) / lmm;
+                if (lane == mx) {
+                  xinvd = 1.0 / lmm;
+                  xw = wm;
+                  xcol = j;
+                }
+                ssx = fma(wm, wm, ssx);
+                ++mx;
+              }
+            }
+          }
           depth = g + 1;
           down = true;
         }
@@ -663,5 +775,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
       if (cap_min != 0x7fffffff) atomicMin(&a.ctl[L0_CAPACITY], (unsigned long long)cap_min + 1ull);
   }
 }
+
+#undef L0_APPEND
 
 }  // namespace slm

@@ -94,6 +94,8 @@ ABI_SYMBOLS = (
     "slm_solve_l0_wide",
     "slm_solve_l0_profile_wide",
     "slm_solve_l0_constrained",
+    "slm_solve_l0_xb",
+    "slm_solve_l0_xb_wide",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -356,6 +358,8 @@ def load_library():
             "slm_solve_l0_profile": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_profile_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
+            "slm_solve_l0_xb": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
+            "slm_solve_l0_xb_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_constrained": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, i32, vp, vp, vp, vp, i32, vp, P(C.c_uint64), P(dbl), P(i64),
                                          vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
@@ -1293,7 +1297,30 @@ class Dataset:
         )
         return beta, lam, info[0]
 
-    def solve_l0(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+    @staticmethod
+    def _l0_bound_keys(info):
+        """What the exclusion-bound entries add to ``info``: which bound ran (``info->mode``: 5 the exclusion bound, 6 / 7 the
+        plain one) and the margin delta (``info->beta_norm``)."""
+        mode = int(info["mode"])
+        if mode == 5:
+            return {"bound": "exclusion", "bound_margin": float(info["beta_norm"])}
+        reason = ("G + 2 eta T is not positive definite on all columns" if mode == 6 else
+                  f"the margin delta = {float(info['beta_norm']):.3g} of the exclusion bound is >= 1/2 (ill-conditioned G + 2 eta T)")
+        return {"bound": "q_all", "bound_reason": reason}
+
+    def solve_l0_xb(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_xb``: ``solve_l0`` with the exclusion bound -- a subtree is cut against the value on every column the
+        path has not excluded, not against the value on all columns (DESIGN 4d "Exclusion bound").  The same arguments and
+        result; ``info`` also holds ``bound`` (``"exclusion"``, with ``bound_margin`` = the relative safety margin delta; or
+        ``"q_all"`` with ``bound_reason`` when the call fell back to the plain bound: a Gram that is not positive definite on
+        all columns, or delta >= 1/2)."""
+        return self.solve_l0(alpha, max_groups, eta, T, big_M, need, max_nodes, binding, _xb=True)
+
+    def solve_l0_xb_wide(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_xb_wide``: ``solve_l0_wide`` with the exclusion bound (see ``solve_l0_xb``)."""
+        return self.solve_l0_wide(alpha, max_groups, eta, T, big_M, need, max_nodes, binding, _xb=True)
+
+    def solve_l0(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None, _xb=False):
         """``slm_solve_l0``: the exact search over supports of the dataset's groups (csrc/l0_kernels.hpp) for
         ``1/2 b^T (G + 2 eta T) b - c^T b + alpha |S|`` with ``|S| <= max_groups``, ``|b_j| <= big_M`` and the hierarchy
         ``need`` (one integer mask per group).  Returns ``(beta, support mask, info)`` where ``info`` is a dict with
@@ -1313,15 +1340,17 @@ class Dataset:
         if binding is True and b is None:
             raise EngineError("the compiled binding is not available")
         if b is not None:
-            beta, support, lower, nodes, rec, rc = b.solve_l0(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M),
-                                                              need_, int(max_nodes))
+            call = b.solve_l0_xb if _xb else b.solve_l0
+            beta, support, lower, nodes, rec, rc = call(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M), need_,
+                                                        int(max_nodes))
             info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
         else:
             beta = np.empty(self.p)
             sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
             infos = np.zeros(1, dtype=_INFO_DTYPE)
-            rc = self._lib.slm_solve_l0(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes),
-                                        _ptr(beta), C.byref(sup), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
+            call = self._lib.slm_solve_l0_xb if _xb else self._lib.slm_solve_l0
+            rc = call(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes), _ptr(beta),
+                      C.byref(sup), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
             if rc != SLM_ERR_NOT_CONVERGED:
                 _check(rc)
             support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
@@ -1330,6 +1359,7 @@ class Dataset:
             "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
             "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
             "box_tol": 1e-12,  # L0_CD_TOL: relative change per sweep at which boxed candidates' descents stop
+            **(self._l0_bound_keys(info) if _xb else {}),
         }
 
     def solve_l0_constrained(self, A, lo, hi, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0,
@@ -1439,7 +1469,7 @@ class Dataset:
         mask = (1 << 64) - 1
         return np.ascontiguousarray([[v & mask, v >> 64] for v in vals], dtype=np.uint64).reshape(G, 2)
 
-    def solve_l0_wide(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
+    def solve_l0_wide(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None, _xb=False):
         """``slm_solve_l0_wide``: ``solve_l0`` on the kernel's wide instantiation -- up to 128 columns and 128 groups, at any
         admissible size (a problem within ``solve_l0``'s limits gives the same bits on either).  ``need`` holds Python
         integers of up to 128 bits and the support comes back as one.  A support holds at most 64 independent columns: an
@@ -1455,16 +1485,18 @@ class Dataset:
         if binding is True and b is None:
             raise EngineError("the compiled binding is not available")
         if b is not None:
-            beta, words, lower, nodes, rec, rc = b.solve_l0_wide(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M),
-                                                                 need_, int(max_nodes))
+            call = b.solve_l0_xb_wide if _xb else b.solve_l0_wide
+            beta, words, lower, nodes, rec, rc = call(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M), need_,
+                                                      int(max_nodes))
             info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
         else:
             beta = np.empty(self.p)
             words = np.zeros(2, dtype=np.uint64)
             lb, nd = C.c_double(), C.c_int64()
             infos = np.zeros(1, dtype=_INFO_DTYPE)
-            rc = self._lib.slm_solve_l0_wide(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes),
-                                             _ptr(beta), _ptr(words), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
+            call = self._lib.slm_solve_l0_xb_wide if _xb else self._lib.slm_solve_l0_wide
+            rc = call(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes), _ptr(beta), _ptr(words),
+                      C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
             if rc != SLM_ERR_NOT_CONVERGED:
                 _check(rc)
             lower, nodes, info = float(lb.value), int(nd.value), infos[0]
@@ -1475,6 +1507,7 @@ class Dataset:
             "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
             "status": status, "loss": float(info["loss"]), "seed_objective": float(info["mu"]), "q_all": float(info["L"]),
             "launches": int(info["n_iter"]), "box_tol": 1e-12, "capacity_cut": cut - 1 if cut else None,
+            **(self._l0_bound_keys(info) if _xb else {}),
         }
 
     def solve_l0_profile_wide(self, alpha_min=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):

@@ -144,6 +144,9 @@ def l0_profile(X, y, *, groups=None, max_groups=None, alpha_min=0.0, eta=0.0, ti
     spec = _ProfileProblem(groups=groups, max_groups=max_groups, alpha_min=alpha_min, eta=eta, tikhonov_w=tikhonov_w, big_M=big_M,
                            hierarchy=hierarchy, fit_intercept=fit_intercept, solver_options=solver_options)
     # everything is validated before a device is touched
+    if isinstance(solver_options, dict) and "bound" in solver_options:
+        raise ValueError("l0_profile takes no solver_options['bound']: the profile search prunes against the table of incumbents "
+                         "per size, and the exclusion bound is not built into it")
     X, y, options, gidx, n_groups, need, T, w = spec._l0_setup(X, y, sample_weight)
     if not np.isfinite(alpha_min) or not np.isfinite(eta):
         raise ValueError("alpha_min and eta must be finite")

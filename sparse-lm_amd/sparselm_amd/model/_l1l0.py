@@ -41,6 +41,7 @@ class L1L0(RegularizedL0):
 
     _wide_mode = False
     _constrained_mode = False  # (constraints set through ``add_constraints`` are a ``ValueError`` at fit)
+    _bound_mode = False  # (``solver_options={"bound": ...}`` likewise: the exclusion bound bounds q, not a lasso's value)
 
     _hyper_parameter_constraints: dict = {
         "eta": [Interval(type=Real, left=0.0, right=None, closed="left")],

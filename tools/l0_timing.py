@@ -32,7 +32,14 @@ nodes, ``qp_solves`` (candidates valued on chip), ``unsettled`` and the wall tim
 columns under 64 rows.  An estimator without a ridge term at 25 x 30 is refused (its Gram is singular) and recorded so.  No
 rate is promised: how many candidates pass the filter depends on the constraints.
 
-``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` runs one part."""
+Then the exclusion bound (``solver_options={"bound": "exclusion"}``, ``slm_solve_l0_xb`` / ``slm_solve_l0_xb_wide``), written to
+``profiles/l0_bound.txt``: every row beside the plain search of the same build on the same device, the calls alternating --
+the four estimators at the two sizes above under the default budget (nodes and the wall time of the whole call: the bounded
+kernel costs more per node, so a problem the plain search finishes in milliseconds may get slower); best subset K = 15 at
+25 x 30 with a ridge term; and ``L2L0`` on the reference's 290 x 66 data at alpha = 3.16e-7, 1e-6 and 1e-5.  No time is
+promised.
+
+``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` / ``--only bound`` runs one part."""
 
 import argparse
 import math
@@ -188,6 +195,79 @@ def wide_section(out_path, max_nodes):
         fh.write(text)
 
 
+def bound_section(out_path):
+    from sklearn.datasets import make_regression
+
+    from sparselm_amd import _engine
+    from sparselm_amd.model import L2L0, BestSubsetSelection, RegularizedL0, RidgedBestSubsetSelection
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    with open(os.path.join(ROOT, "sparse-lm_amd", "csrc", "l0_host.hpp")) as fh:
+        xcap = next(line.split("=")[1].split(";")[0].strip() for line in fh if line.startswith("constexpr int L0_XCAP"))
+    lines = [f"exact l0 search with the exclusion bound on {name}, {dev['compute_units']} compute units; L0_XCAP = {xcap}",
+             "(wall time of the whole Python call; plain and bounded calls alternate, the second of two calls each is reported; default node",
+             " budget; big_M = 1000)", ""]
+    head = (f"{'estimator':46s} {'n x p':8s} {'bound':>9s} {'nodes':>12s} {'wall s':>9s} {'proven':>7s} {'objective':>18s} {'margin':>10s}")
+
+    def say(line):
+        lines.append(line)
+        print(line, flush=True)
+
+    def pair(what, shape, make, X, y):
+        """``make(options)`` -> estimator; plain, bounded, plain, bounded"""
+        res = {}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            for _ in range(2):
+                for kind, extra in (("q_all", {}), ("exclusion", {"bound": "exclusion"})):
+                    est = make(extra)
+                    t0 = time.perf_counter()
+                    est.fit(X, y)
+                    res[kind] = (est, time.perf_counter() - t0)
+        for kind in ("q_all", "exclusion"):
+            est, wall = res[kind]
+            info = est.solver_info_
+            ran = info.get("bound", "q_all")
+            say(f"{what:46s} {shape:8s} {ran if kind == 'exclusion' else 'q_all':>9s} {info['nodes']:12d} {wall:9.4f} {str(info['proven_optimal']):>7s} "
+                f"{info['objective']:18.10e} {info.get('bound_margin', float('nan')):10.2e}")
+        a, b = res["q_all"], res["exclusion"]
+        same = np.array_equal(a[0].coef_, b[0].coef_)
+        say(f"    exclusion / q_all: {b[0].solver_info_['nodes'] / max(a[0].solver_info_['nodes'], 1):.3g} of the nodes, {b[1] / a[1]:.3g} of the wall "
+            f"time; same coefficients: {same}" + ("" if "bound_reason" not in b[0].solver_info_ else f"; fell back: {b[0].solver_info_['bound_reason']}"))
+
+    say(head)
+    for p in (20, 30):
+        X, y = make_regression(25, p, n_informative=10, noise=1.0, random_state=0)
+        shape = "25x%d" % p
+        pair("BestSubsetSelection(K = p / 2)", shape, lambda o: BestSubsetSelection(sparse_bound=p // 2, big_M=1000, solver_options=o), X, y)
+        pair("RidgedBestSubsetSelection(K = p / 2, eta = 1)", shape,
+             lambda o: RidgedBestSubsetSelection(sparse_bound=p // 2, eta=1.0, big_M=1000, solver_options=o), X, y)
+        pair("RegularizedL0(alpha = 3)", shape, lambda o: RegularizedL0(alpha=3.0, big_M=1000, solver_options=o), X, y)
+        pair("L2L0(alpha = 3, eta = 1)", shape, lambda o: L2L0(alpha=3.0, eta=1.0, big_M=1000, solver_options=o), X, y)
+    say("")
+    say("best subset K = 15 at 25 x 30 with a ridge term (without one n < p: the Gram is singular and the call falls back)")
+    say(head)
+    X, y = make_regression(25, 30, n_informative=10, noise=1.0, random_state=0)
+    for eta in (1.0, 1e-3):
+        pair(f"RidgedBestSubsetSelection(K = 15, eta = {eta:g})", "25x30",
+             lambda o: RidgedBestSubsetSelection(sparse_bound=15, eta=eta, big_M=1000, solver_options=o), X, y)
+    d = os.path.join(ROOT, "tests", "golden", "reference_examples")
+    X, y = np.load(os.path.join(d, "corr.npy")), np.load(os.path.join(d, "energy.npy"))
+    say("")
+    say(f"L2L0(fit_intercept=True, eta=1.66e-6, solver_options={{'wide': True}}) on the reference's {X.shape[0]} x {X.shape[1]} data")
+    say(head)
+    for alpha in (1e-5, 1e-6, 3.16e-7):
+        pair(f"L2L0(alpha = {alpha:g})", "%dx%d" % X.shape,
+             lambda o: L2L0(fit_intercept=True, alpha=alpha, eta=1.66e-6, solver_options=dict(o, wide=True)), X, y)
+    say("")
+    say("not measured: the share of the wall time in which one wavefront walked the last ticket alone (the engine keeps no such count).")
+    text = "\n".join(lines) + "\n"
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write(text)
+
+
 def constrained_section(out_path, max_nodes):
     from scipy.optimize import Bounds, LinearConstraint
     from sklearn.datasets import make_regression
@@ -252,8 +332,11 @@ def main():
     ap.add_argument("--profile-out", default=os.path.join(ROOT, "profiles", "l0_profile.txt"))
     ap.add_argument("--wide-out", default=os.path.join(ROOT, "profiles", "l0_wide.txt"))
     ap.add_argument("--constrained-out", default=os.path.join(ROOT, "profiles", "l0_constrained.txt"))
-    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained"], default=None)
+    ap.add_argument("--bound-out", default=os.path.join(ROOT, "profiles", "l0_bound.txt"))
+    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound"], default=None)
     args = ap.parse_args()
+    if args.only in (None, "bound"):
+        bound_section(args.bound_out)
     if args.only in (None, "constrained"):
         constrained_section(args.constrained_out, args.max_nodes)
     if args.only in (None, "wide"):
