@@ -299,37 +299,82 @@ uintptr_t dataset_create(uintptr_t eng, const py::array& X_in, const py::object&
   return reinterpret_cast<uintptr_t>(out);
 }
 
-// slm_solve_l0: the exact search over supports.  Returns (beta, support mask, lower bound, nodes, record as bytes, status) --
-// status is SLM_OK or SLM_ERR_NOT_CONVERGED (the node budget ran out: the outputs hold the incumbent); anything else raises.
-// (XB: slm_solve_l0_xb -- the same search with the exclusion bound, the same signature and tuple.)
-template <bool XB>
-py::tuple solve_l0(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
-                   const py::object& need, int64_t max_nodes) {
-  Keep keep;
-  const double* Tp = vector_arg(T, p * p, "T", keep);
-  const uint64_t* needp = nullptr;
-  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
-  if (!need.is_none()) {
-    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
-    if (!need_arr) throw py::value_error("need is not convertible to uint64");
-    needp = need_arr.data();
-  }
-  py::array_t<double> beta((py::ssize_t)p);
+// ---- the exact search over supports: slm_solve_l0 and its seven relatives -------------------------------------------------
+//
+// Every wrapper's tuple ends with (record as bytes, status).  status is SLM_OK or SLM_ERR_NOT_CONVERGED (the result is not
+// proven -- the node budget ran out, say: the outputs hold the incumbent); anything else raises.
+using arr_u64 = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>;
+
+// The need masks: one word per group (the wide entries: n_groups x 2 words, the low one first), or None.
+const uint64_t* need_words(const py::object& need, arr_u64& hold) {
+  if (need.is_none()) return nullptr;
+  hold = arr_u64::ensure(need);
+  if (!hold) throw py::value_error("need is not convertible to uint64");
+  return hold.data();
+}
+
+// One call: a zeroed record, the GIL released while call(record) runs, and the status checked as above.
+template <class Call>
+std::pair<py::array, int> l0_call(Call call) {
   py::array info = info_bytes(1);
-  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
-  uint64_t support = 0;
-  double lower = 0.0;
-  int64_t nodes = 0;
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec));
   int rc;
   {
     py::gil_scoped_release nogil;
-    slm_point_info* rec = static_cast<slm_point_info*>(info.mutable_data());
-    rc = XB ? slm_solve_l0_xb(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
-                              &support, &lower, &nodes, rec)
-            : slm_solve_l0(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(), &support,
-                           &lower, &nodes, rec);
+    rc = call(rec);
   }
   if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return {info, rc};
+}
+
+// The four entries with slm_solve_l0's signature.  Returns (beta, support, lower bound, nodes, record, status); the support is
+// an integer, wide: an array of two words (the low one first).
+template <class Entry>
+py::tuple l0_search(bool wide, Entry entry, uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T,
+                    double big_M, const py::object& need, int64_t max_nodes) {
+  Keep keep;
+  const double* Tp = vector_arg(T, p * p, "T", keep);
+  arr_u64 need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
+  py::array_t<double> beta((py::ssize_t)p);
+  py::array_t<uint64_t> support(2);
+  double* bp = beta.mutable_data();
+  uint64_t* sup = support.mutable_data();
+  sup[0] = sup[1] = 0;
+  double lower = 0.0;
+  int64_t nodes = 0;
+  const auto [info, rc] = l0_call([&](slm_point_info* rec) {
+    return entry(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, bp, sup, &lower, &nodes, rec);
+  });
+  if (wide) return py::make_tuple(beta, support, lower, nodes, info, rc);
+  return py::make_tuple(beta, sup[0], lower, nodes, info, rc);
+}
+template <bool XB>  // slm_solve_l0; XB: the same search with the exclusion bound
+py::tuple solve_l0(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
+                   const py::object& need, int64_t max_nodes) {
+  return l0_search(false, [](auto... a) { return XB ? slm_solve_l0_xb(a...) : slm_solve_l0(a...); }, ds, p, alpha, max_groups, eta, T, big_M,
+                   need, max_nodes);
+}
+template <bool XB>
+py::tuple solve_l0_wide(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
+                        const py::object& need, int64_t max_nodes) {
+  return l0_search(true, [](auto... a) { return XB ? slm_solve_l0_xb_wide(a...) : slm_solve_l0_wide(a...); }, ds, p, alpha, max_groups, eta, T,
+                   big_M, need, max_nodes);
+}
+
+// slm_solve_l0_l1: the same search in l1 mode (the reference's L1L0); the tuple of solve_l0.
+py::tuple solve_l0_l1(uintptr_t ds, int64_t p, double alpha, double eta_l1, double big_M, const py::object& need, int64_t max_nodes) {
+  arr_u64 need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
+  py::array_t<double> beta((py::ssize_t)p);
+  double* bp = beta.mutable_data();
+  uint64_t support = 0;
+  double lower = 0.0;
+  int64_t nodes = 0;
+  const auto [info, rc] = l0_call([&](slm_point_info* rec) {
+    return slm_solve_l0_l1(reinterpret_cast<slm_dataset*>(ds), alpha, eta_l1, big_M, needp, max_nodes, bp, &support, &lower, &nodes, rec);
+  });
   return py::make_tuple(beta, support, lower, nodes, info, rc);
 }
 
@@ -346,147 +391,49 @@ py::tuple solve_l0_constrained(uintptr_t ds, int64_t p, double alpha, int32_t ma
   const double* hip = vector_arg(hi, rows, "hi", keep);
   const double* blop = vector_arg(box_lo, p, "box_lo", keep);
   const double* bhip = vector_arg(box_hi, p, "box_hi", keep);
-  const uint64_t* needp = nullptr;
-  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
-  if (!need.is_none()) {
-    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
-    if (!need_arr) throw py::value_error("need is not convertible to uint64");
-    needp = need_arr.data();
-  }
+  arr_u64 need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
   py::array_t<double> beta((py::ssize_t)p), lam((py::ssize_t)rows);
-  py::array info = info_bytes(1);
-  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
+  double *bp = beta.mutable_data(), *lp = lam.mutable_data();
   uint64_t support = 0;
   double lower = 0.0;
   int64_t nodes = 0;
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = slm_solve_l0_constrained(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, Ap, m, lop, hip,
-                                  blop, bhip, max_qp_sweeps, beta.mutable_data(), &support, &lower, &nodes, lam.mutable_data(),
-                                  static_cast<slm_point_info*>(info.mutable_data()));
-  }
-  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  const auto [info, rc] = l0_call([&](slm_point_info* rec) {
+    return slm_solve_l0_constrained(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, Ap, m, lop, hip,
+                                    blop, bhip, max_qp_sweeps, bp, &support, &lower, &nodes, lp, rec);
+  });
   return py::make_tuple(beta, support, lam, lower, nodes, info, rc);
 }
 
-// slm_solve_l0_l1: the same search in l1 mode (the reference's L1L0); the tuple of solve_l0.
-py::tuple solve_l0_l1(uintptr_t ds, int64_t p, double alpha, double eta_l1, double big_M, const py::object& need, int64_t max_nodes) {
-  const uint64_t* needp = nullptr;
-  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
-  if (!need.is_none()) {
-    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
-    if (!need_arr) throw py::value_error("need is not convertible to uint64");
-    needp = need_arr.data();
-  }
-  py::array_t<double> beta((py::ssize_t)p);
-  py::array info = info_bytes(1);
-  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
-  uint64_t support = 0;
-  double lower = 0.0;
+// The two profile entries: the best support of every size up to max_groups from one search.  Returns (coefficients
+// [max_groups + 1][p], support masks [max_groups + 1] (wide: [max_groups + 1][2] words), values, nodes, record, status).
+template <class Entry>
+py::tuple l0_profile(bool wide, Entry entry, uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta, const py::object& T,
+                     double big_M, const py::object& need, int64_t max_nodes) {
+  if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
+  Keep keep;
+  const double* Tp = vector_arg(T, p * p, "T", keep);
+  arr_u64 need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
+  const py::ssize_t rows = (py::ssize_t)max_groups + 1;
+  py::array_t<double> beta({rows, (py::ssize_t)p}), value(rows);
+  py::array_t<uint64_t> support = wide ? py::array_t<uint64_t>({rows, (py::ssize_t)2}) : py::array_t<uint64_t>(rows);
+  double *bp = beta.mutable_data(), *vp = value.mutable_data();
+  uint64_t* sup = support.mutable_data();
   int64_t nodes = 0;
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = slm_solve_l0_l1(reinterpret_cast<slm_dataset*>(ds), alpha, eta_l1, big_M, needp, max_nodes, beta.mutable_data(), &support, &lower,
-                         &nodes, static_cast<slm_point_info*>(info.mutable_data()));
-  }
-  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
-  return py::make_tuple(beta, support, lower, nodes, info, rc);
+  const auto [info, rc] = l0_call([&](slm_point_info* rec) {
+    return entry(reinterpret_cast<slm_dataset*>(ds), alpha_min, max_groups, eta, Tp, big_M, needp, max_nodes, bp, sup, vp, &nodes, rec);
+  });
+  return py::make_tuple(beta, support, value, nodes, info, rc);
 }
-
-// slm_solve_l0_profile: the best support of every size up to max_groups from one search.  Returns (coefficients
-// [max_groups + 1][p], support masks, values, nodes, record as bytes, status) -- status as for solve_l0.
 py::tuple solve_l0_profile(uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta, const py::object& T, double big_M,
                            const py::object& need, int64_t max_nodes) {
-  if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
-  Keep keep;
-  const double* Tp = vector_arg(T, p * p, "T", keep);
-  const uint64_t* needp = nullptr;
-  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
-  if (!need.is_none()) {
-    need_arr = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
-    if (!need_arr) throw py::value_error("need is not convertible to uint64");
-    needp = need_arr.data();
-  }
-  const py::ssize_t rows = (py::ssize_t)max_groups + 1;
-  py::array_t<double> beta({rows, (py::ssize_t)p});
-  py::array_t<uint64_t> support(rows);
-  py::array_t<double> value(rows);
-  py::array info = info_bytes(1);
-  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
-  int64_t nodes = 0;
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = slm_solve_l0_profile(reinterpret_cast<slm_dataset*>(ds), alpha_min, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
-                              support.mutable_data(), value.mutable_data(), &nodes, static_cast<slm_point_info*>(info.mutable_data()));
-  }
-  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
-  return py::make_tuple(beta, support, value, nodes, info, rc);
+  return l0_profile(false, [](auto... a) { return slm_solve_l0_profile(a...); }, ds, p, alpha_min, max_groups, eta, T, big_M, need, max_nodes);
 }
-
-// The need masks of the wide entries: n_groups x 2 words (the low one first), or None.
-const uint64_t* need_words(const py::object& need, py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& hold) {
-  if (need.is_none()) return nullptr;
-  hold = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>::ensure(need);
-  if (!hold) throw py::value_error("need is not convertible to uint64");
-  return hold.data();
-}
-
-// slm_solve_l0_wide: the tuple of solve_l0 with the support as an array of two words (the low one first).
-// (XB: slm_solve_l0_xb_wide.)
-template <bool XB>
-py::tuple solve_l0_wide(uintptr_t ds, int64_t p, double alpha, int32_t max_groups, double eta, const py::object& T, double big_M,
-                        const py::object& need, int64_t max_nodes) {
-  Keep keep;
-  const double* Tp = vector_arg(T, p * p, "T", keep);
-  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
-  const uint64_t* needp = need_words(need, need_arr);
-  py::array_t<double> beta((py::ssize_t)p);
-  py::array_t<uint64_t> support(2);
-  support.mutable_data()[0] = support.mutable_data()[1] = 0;
-  py::array info = info_bytes(1);
-  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
-  double lower = 0.0;
-  int64_t nodes = 0;
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    slm_point_info* rec = static_cast<slm_point_info*>(info.mutable_data());
-    rc = XB ? slm_solve_l0_xb_wide(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
-                                   support.mutable_data(), &lower, &nodes, rec)
-            : slm_solve_l0_wide(reinterpret_cast<slm_dataset*>(ds), alpha, max_groups, eta, Tp, big_M, needp, max_nodes, beta.mutable_data(),
-                                support.mutable_data(), &lower, &nodes, rec);
-  }
-  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
-  return py::make_tuple(beta, support, lower, nodes, info, rc);
-}
-
-// slm_solve_l0_profile_wide: the tuple of solve_l0_profile with the supports as [max_groups + 1][2] words.
 py::tuple solve_l0_profile_wide(uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta, const py::object& T,
                                 double big_M, const py::object& need, int64_t max_nodes) {
-  if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
-  Keep keep;
-  const double* Tp = vector_arg(T, p * p, "T", keep);
-  py::array_t<uint64_t, py::array::c_style | py::array::forcecast> need_arr;
-  const uint64_t* needp = need_words(need, need_arr);
-  const py::ssize_t rows = (py::ssize_t)max_groups + 1;
-  py::array_t<double> beta({rows, (py::ssize_t)p});
-  py::array_t<uint64_t> support({rows, (py::ssize_t)2});
-  py::array_t<double> value(rows);
-  py::array info = info_bytes(1);
-  std::memset(info.mutable_data(), 0, sizeof(slm_point_info));
-  int64_t nodes = 0;
-  int rc;
-  {
-    py::gil_scoped_release nogil;
-    rc = slm_solve_l0_profile_wide(reinterpret_cast<slm_dataset*>(ds), alpha_min, max_groups, eta, Tp, big_M, needp, max_nodes,
-                                   beta.mutable_data(), support.mutable_data(), value.mutable_data(), &nodes,
-                                   static_cast<slm_point_info*>(info.mutable_data()));
-  }
-  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
-  return py::make_tuple(beta, support, value, nodes, info, rc);
+  return l0_profile(true, [](auto... a) { return slm_solve_l0_profile_wide(a...); }, ds, p, alpha_min, max_groups, eta, T, big_M, need,
+                    max_nodes);
 }
 
 }  // namespace

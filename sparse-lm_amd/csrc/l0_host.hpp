@@ -8,9 +8,12 @@
 // parameter and the capacity rule.  The constrained mode (slm_solve_l0_constrained; tests/l0_con_host_test.cpp) adds the splitting
 // that values a support under linear constraints, the dual value host and device share, its face polish, the positive-definite
 // check and the lower bound on all columns.  The exclusion bound (slm_solve_l0_xb, slm_solve_l0_xb_wide;
-// tests/l0_bound_host_test.cpp) adds P = H^-1, P c, the margin delta and the guarded bound host and device share.
+// tests/l0_bound_host_test.cpp) adds P = H^-1, P c, the margin delta and the guarded bound host and device share.  The end of
+// the file holds what every entry's launch shares (tests/l0_launch_host_test.cpp): the layout of the device block, the
+// winner among the waves' results, the way back to the caller's groups and columns, and the loss from the Gram.
 #pragma once
 #include <stddef.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -945,6 +948,97 @@ inline double l0_con_lower_bound(const L0ConProblem& P, double q_all, L0ConPoint
   const double lb = R.bound > q_all ? R.bound : q_all;  // (a NaN bound keeps q_all)
   if (all) *all = std::move(R);
   return lb;
+}
+
+// ---- the launch plan and what is read back (every entry of engine_l0.hip; tests/l0_launch_host_test.cpp) ---------------------
+//
+// The search's one block of 8-byte words, in this order:
+//     control | best values | best supports | H | c | need | group starts | what a mode appends
+// A wave owns `slots` results (1; profile mode 64, entry k - 1 for size k); a mask is `mask_words` words, the low one first.
+// The host reads back the part before H.  The kernel's constants (control words, ticket prefix, waves per workgroup) are
+// arguments: this header knows nothing of l0_kernels.hpp.
+struct L0Layout {
+  int d = 0, blocks = 0, waves = 0, slots = 1, mask_words = 1;
+  size_t off_bv = 0, off_bm = 0, off_H = 0, off_c = 0, off_need = 0, off_gs = 0, words = 0;
+  size_t append(size_t n) { return (words += n) - n; }  // a section of n words behind what is there; its offset
+};
+inline L0Layout l0_layout(int p, int ng, int cus, int mask_words, int slots, int ctl_words, int prefix, int block_waves) {
+  L0Layout y;
+  y.d = std::min(ng, prefix);  // 2^d tickets, one per wave while they last: at least one workgroup, at most two per CU
+  y.blocks = (int)std::max<long long>(1, std::min<long long>(2ll * cus, ((1ll << y.d) + block_waves - 1) / block_waves));
+  y.waves = y.blocks * block_waves;
+  y.slots = slots;
+  y.mask_words = mask_words;
+  (void)y.append((size_t)ctl_words);
+  y.off_bv = y.append((size_t)y.waves * slots);
+  y.off_bm = y.append((size_t)mask_words * y.waves * slots);
+  y.off_H = y.append((size_t)p * p);
+  y.off_c = y.append((size_t)p);
+  y.off_need = y.append((size_t)mask_words * ng);
+  y.off_gs = y.append((size_t)ng + 1);
+  return y;
+}
+// the common sections of the host image h[y.words] (control, results and whatever is appended stay as they are)
+template <class Mask>
+inline void l0_fill_image(const L0Layout& y, const double* H, const double* c, int p, const std::vector<Mask>& needo,
+                          const std::vector<int>& gstart, unsigned long long* h) {
+  static_assert(sizeof(Mask) % sizeof(unsigned long long) == 0, "a mask is whole words, the low one first");
+  memcpy(h + y.off_H, H, sizeof(double) * (size_t)p * p);
+  memcpy(h + y.off_c, c, sizeof(double) * (size_t)p);
+  if (!needo.empty()) memcpy(h + y.off_need, needo.data(), sizeof(Mask) * needo.size());
+  for (size_t g = 0; g < gstart.size(); ++g) h[y.off_gs + g] = (unsigned long long)gstart[g];
+}
+
+// The tie rule of every comparison of two candidates: the lower value, then the lower support.  Two candidates at +inf are
+// no tie: +inf says "nothing held" (a wave that found nothing stores +inf with an all-ones mask, the seed of an infeasible
+// empty support is +inf with all ones), and whoever holds +inf keeps the mask it has -- which nobody reads.
+template <class Mask>
+inline bool l0_better(double v, Mask mk, double than_v, Mask than_mk) {
+  return v < than_v || (v == than_v && v < HUGE_VAL && l0m_less(mk, than_mk));
+}
+// The winner among the seed (in val, mask) and result `slot` of every wave's `stride`, in a fixed order; h: the block as read back.
+template <class Mask>
+inline void l0_winner(const unsigned long long* h, size_t off_bv, size_t off_bm, int waves, int stride, int slot, double& val, Mask& mask) {
+  for (int wv = 0; wv < waves; ++wv) {
+    const size_t at = (size_t)wv * stride + slot;
+    double v;
+    Mask mk;
+    memcpy(&v, h + off_bv + at, sizeof(double));
+    memcpy(&mk, h + off_bm + at * (sizeof(Mask) / sizeof(unsigned long long)), sizeof(Mask));
+    if (l0_better(v, mk, val, mask)) {
+      val = v;
+      mask = mk;
+    }
+  }
+}
+
+// A support in search order as the caller sees it: group gorder[k] for bit k.  count: the groups it holds.
+template <class Mask>
+inline Mask l0_caller_mask(Mask mask, const std::vector<int>& gorder, int* count = nullptr) {
+  Mask out = l0m_none<Mask>();
+  int n = 0;
+  for (int k = 0; k < (int)gorder.size(); ++k)
+    if (l0m_test(mask, k)) {
+      ++n;
+      l0m_set(out, gorder[(size_t)k]);
+    }
+  if (count) *count = n;
+  return out;
+}
+// coefficients in search order to the caller's columns: cols[i] is the column at search position i
+inline void l0_scatter(const double* beta_s, const std::vector<int>& cols, double* beta) {
+  for (size_t i = 0; i < cols.size(); ++i) beta[cols[i]] = beta_s[i];
+}
+// 1/(2n)||X beta - y||_W^2 = 1/2 beta^T G beta - c^T beta + 1/2 yy (yy = y^T W y / n) from the Gram: no pass over X
+inline double l0_gram_loss(const double* G, const double* c, int p, double yy, const double* beta) {
+  double loss = 0.5 * yy;
+  for (int i = 0; i < p; ++i) {
+    if (beta[i] == 0.0) continue;
+    double t = 0.0;
+    for (int j = 0; j < p; ++j) t += G[(size_t)i * p + j] * beta[j];
+    loss += beta[i] * (0.5 * t - c[i]);
+  }
+  return loss;
 }
 
 }  // namespace slm

@@ -1297,16 +1297,100 @@ class Dataset:
         )
         return beta, lam, info[0]
 
+    # ---- the exact l0 search: what its eight entries share ------------------------------------------------------------------
+    def _need_narrow(self, need):
+        """``need`` (one integer mask per group) as the narrow entries take it: one 64-bit word per group."""
+        if need is None:
+            return None
+        need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
+        if need_.shape != (self.n_groups,):
+            raise ValueError(f"need must have {self.n_groups} entries")
+        return need_
+
+    def _need_words(self, need):
+        """``need`` (one Python integer of up to 128 bits per group) as the wide entries take it: two 64-bit words per group,
+        the low one first."""
+        if need is None:
+            return None
+        G = self.n_groups
+        vals = [int(v) for v in need]
+        if len(vals) != G:
+            raise ValueError(f"need must have {G} entries")
+        if any(v < 0 or v >> 128 for v in vals):
+            raise ValueError("need masks must be non-negative integers of at most 128 bits")
+        mask = (1 << 64) - 1
+        return np.ascontiguousarray([[v & mask, v >> 64] for v in vals], dtype=np.uint64).reshape(G, 2)
+
     @staticmethod
-    def _l0_bound_keys(info):
-        """What the exclusion-bound entries add to ``info``: which bound ran (``info->mode``: 5 the exclusion bound, 6 / 7 the
-        plain one) and the margin delta (``info->beta_norm``)."""
-        mode = int(info["mode"])
-        if mode == 5:
-            return {"bound": "exclusion", "bound_margin": float(info["beta_norm"])}
-        reason = ("G + 2 eta T is not positive definite on all columns" if mode == 6 else
-                  f"the margin delta = {float(info['beta_norm']):.3g} of the exclusion bound is >= 1/2 (ill-conditioned G + 2 eta T)")
-        return {"bound": "q_all", "bound_reason": reason}
+    def _l0_route(binding):
+        """``binding`` of the l0 methods: None = the compiled binding when it is there, False = ctypes (None is returned),
+        True = the binding or an error."""
+        b = load_binding() if binding is not False else None
+        if binding is True and b is None:
+            raise EngineError("the compiled binding is not available")
+        return b
+
+    def _l0_call(self, name, binding, args, outs, c_order=None):
+        """One call of ``slm_<name>`` by the route ``binding`` names.  ``args``: the entry's arguments between the dataset and
+        its outputs, arrays as arrays.  ``outs``: the outputs the ctypes route fills -- arrays, ctypes cells, None -- in the
+        order of the binding's tuple (``c_order``: their positions in the C signature, where that order differs).  Returns
+        ``(outputs, record, rc)``; ``rc`` is ``SLM_OK`` or ``SLM_ERR_NOT_CONVERGED`` (the result is not proven: the outputs
+        hold the incumbent), anything else raises."""
+        _sync_knobs()
+        b = self._l0_route(binding)
+        if b is not None:
+            *res, rec, rc = getattr(b, name)(self._h.value, self.p, *args)
+            return res, np.frombuffer(rec, dtype=_INFO_DTYPE)[0], rc
+        infos = np.zeros(1, dtype=_INFO_DTYPE)
+        c_outs = [_ptr(o) if o is None or isinstance(o, np.ndarray) else C.byref(o) for o in outs]
+        rc = getattr(self._lib, "slm_" + name)(
+            self._h, *[_ptr(a) if a is None or isinstance(a, np.ndarray) else a for a in args],
+            *[c_outs[i] for i in c_order or range(len(outs))], _as(infos, _PointInfo))
+        if rc != SLM_ERR_NOT_CONVERGED:
+            _check(rc)
+        return [o if o is None or isinstance(o, np.ndarray) else o.value for o in outs], infos[0], rc
+
+    @staticmethod
+    def _l0_info(info, rc, lower, nodes, *modes):
+        """``info`` of a search for one support: the keys every entry reports, from the record's common fields, then what the
+        record's other fields mean in each of ``modes`` (the table at ``l0_report``, csrc/engine_l0.hip):
+        ``rejects`` counts the descents (``"l1"``) or the qp solves (``"constrained"``), or is the capacity rule's c_min + 1
+        (``"wide"``, 0: no include was refused); ``resid`` is 1 where the node budget ran out (``"wide"``) or counts the
+        unsettled candidates (``"constrained"``); ``beta_norm`` is the lowest bound on those (``"constrained"``) or the margin
+        delta (``"xb"``, where ``mode`` says which bound ran: 5 the exclusion bound, 6 / 7 the plain one)."""
+        out = {
+            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
+            "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
+            "box_tol": 1e-12,  # L0_CD_TOL: relative change per sweep at which boxed candidates' descents stop (DESIGN 4d)
+        }
+        if "l1" in modes:
+            out["descents"] = int(info["rejects"])
+        if "wide" in modes:
+            cut = int(info["rejects"])
+            out["capacity_cut"] = cut - 1 if cut else None
+            if rc != SLM_OK and float(info["resid"]) == 0.0:
+                out["status"] = "capacity"
+        if "constrained" in modes:
+            unsettled, ubound = int(info["resid"]), float(info["beta_norm"])
+            if rc != SLM_OK and unsettled and not out["objective"] <= ubound:
+                out["status"] = "unsettled"
+            out.update(constrained=True, qp_solves=int(info["rejects"]), unsettled=unsettled, unsettled_bound=ubound,
+                       con_tol=1e-9)  # L0_CON_TOL: rows and duality gap of a candidate valued on chip, relative (DESIGN 4d)
+        if "xb" in modes and int(info["mode"]) == 5:
+            out.update(bound="exclusion", bound_margin=float(info["beta_norm"]))
+        elif "xb" in modes:
+            reason = ("G + 2 eta T is not positive definite on all columns" if int(info["mode"]) == 6 else
+                      f"the margin delta = {float(info['beta_norm']):.3g} of the exclusion bound is >= 1/2 (ill-conditioned G + 2 eta T)")
+            out.update(bound="q_all", bound_reason=reason)
+        return out
+
+    def _l0_search_args(self, wide, alpha, max_groups, eta, T, big_M, need, max_nodes):
+        """The arguments ``slm_solve_l0`` and its relatives share, converted."""
+        K = self.n_groups if max_groups is None else int(max_groups)
+        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
+        need_ = self._need_words(need) if wide else self._need_narrow(need)
+        return float(alpha), K, float(eta), T_, float(big_M), need_, int(max_nodes)
 
     def solve_l0_xb(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
         """``slm_solve_l0_xb``: ``solve_l0`` with the exclusion bound -- a subtree is cut against the value on every column the
@@ -1327,40 +1411,10 @@ class Dataset:
         ``objective``, ``lower_bound``, ``proven_optimal``, ``nodes``, ``status``, ``loss``, ``seed_objective``, ``q_all``,
         ``launches``, ``box_tol``.  ``binding``: None = the compiled binding when it is there, False = ctypes, True = the binding or an
         error (the two routes are compared by the tests)."""
-        _sync_knobs()
-        G = self.n_groups
-        K = G if max_groups is None else int(max_groups)
-        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
-        need_ = None
-        if need is not None:
-            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
-            if need_.shape != (G,):
-                raise ValueError(f"need must have {G} entries")
-        b = load_binding() if binding is not False else None
-        if binding is True and b is None:
-            raise EngineError("the compiled binding is not available")
-        if b is not None:
-            call = b.solve_l0_xb if _xb else b.solve_l0
-            beta, support, lower, nodes, rec, rc = call(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M), need_,
-                                                        int(max_nodes))
-            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
-        else:
-            beta = np.empty(self.p)
-            sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
-            infos = np.zeros(1, dtype=_INFO_DTYPE)
-            call = self._lib.slm_solve_l0_xb if _xb else self._lib.slm_solve_l0
-            rc = call(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes), _ptr(beta),
-                      C.byref(sup), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
-            if rc != SLM_ERR_NOT_CONVERGED:
-                _check(rc)
-            support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
-        return beta, int(support), {
-            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
-            "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
-            "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
-            "box_tol": 1e-12,  # L0_CD_TOL: relative change per sweep at which boxed candidates' descents stop (DESIGN 4d)
-            **(self._l0_bound_keys(info) if _xb else {}),
-        }
+        args = self._l0_search_args(False, alpha, max_groups, eta, T, big_M, need, max_nodes)
+        (beta, support, lower, nodes), info, rc = self._l0_call(
+            "solve_l0_xb" if _xb else "solve_l0", binding, args, [np.empty(self.p), C.c_uint64(), C.c_double(), C.c_int64()])
+        return beta, int(support), self._l0_info(info, rc, lower, nodes, *(("xb",) if _xb else ()))
 
     def solve_l0_constrained(self, A, lo, hi, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0,
                              box_lo=None, box_hi=None, max_qp_sweeps=0, m=None, binding=None):
@@ -1372,52 +1426,21 @@ class Dataset:
         (the lowest bound on those, ``inf``: none), ``con_tol`` and ``status`` ``"optimal"`` / ``"node_budget"`` /
         ``"unsettled"``; ``q_all`` is the proven lower bound on the value of all columns that the subtree bound used.
         ``m``: the row count handed to the engine (None: ``A``'s)."""
-        _sync_knobs()
-        G = self.n_groups
-        K = G if max_groups is None else int(max_groups)
-        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
         A_ = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, self.p) if np.size(A) else np.zeros((0, self.p))
         rows = A_.shape[0]
         lo_ = _f64(np.broadcast_to(lo, (rows,)), "lo")
         hi_ = _f64(np.broadcast_to(hi, (rows,)), "hi")
         blo_ = None if box_lo is None else _f64(np.broadcast_to(box_lo, (self.p,)), "box_lo")
         bhi_ = None if box_hi is None else _f64(np.broadcast_to(box_hi, (self.p,)), "box_hi")
-        m_ = rows if m is None else int(m)
-        need_ = None
-        if need is not None:
-            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
-            if need_.shape != (G,):
-                raise ValueError(f"need must have {G} entries")
         if rows == 0:
             A_ = lo_ = hi_ = None
-        b = load_binding() if binding is not False else None
-        if binding is True and b is None:
-            raise EngineError("the compiled binding is not available")
-        if b is not None:
-            beta, support, lam, lower, nodes, rec, rc = b.solve_l0_constrained(
-                self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M), need_, int(max_nodes), A_, m_, lo_, hi_, blo_, bhi_,
-                int(max_qp_sweeps))
-            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
-        else:
-            beta, lam = np.empty(self.p), np.zeros(rows)
-            sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
-            infos = np.zeros(1, dtype=_INFO_DTYPE)
-            rc = self._lib.slm_solve_l0_constrained(
-                self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes), _ptr(A_), m_, _ptr(lo_),
-                _ptr(hi_), _ptr(blo_), _ptr(bhi_), int(max_qp_sweeps), _ptr(beta), C.byref(sup), C.byref(lb), C.byref(nd),
-                _ptr(lam) if rows else None, _as(infos, _PointInfo))
-            if rc != SLM_ERR_NOT_CONVERGED:
-                _check(rc)
-            support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
-        objective, unsettled, ubound = float(info["kkt"]), int(info["resid"]), float(info["beta_norm"])
-        status = "optimal" if rc == SLM_OK else ("unsettled" if unsettled and not objective <= ubound else "node_budget")
-        return beta, int(support), np.asarray(lam, dtype=np.float64), {
-            "objective": objective, "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
-            "status": status, "loss": float(info["loss"]), "seed_objective": float(info["mu"]), "q_all": float(info["L"]),
-            "launches": int(info["n_iter"]), "box_tol": 1e-12, "constrained": True, "qp_solves": int(info["rejects"]),
-            "unsettled": unsettled, "unsettled_bound": ubound,
-            "con_tol": 1e-9,  # L0_CON_TOL: rows and duality gap of a candidate valued on chip, relative (DESIGN 4d)
-        }
+        args = self._l0_search_args(False, alpha, max_groups, eta, T, big_M, need, max_nodes)
+        args += (A_, rows if m is None else int(m), lo_, hi_, blo_, bhi_, int(max_qp_sweeps))
+        (beta, support, lam, lower, nodes), info, rc = self._l0_call(
+            "solve_l0_constrained", binding, args,
+            [np.empty(self.p), C.c_uint64(), np.zeros(rows) if rows else None, C.c_double(), C.c_int64()], c_order=(0, 1, 3, 4, 2))
+        lam = np.zeros(0) if lam is None else np.asarray(lam, dtype=np.float64)
+        return beta, int(support), lam, self._l0_info(info, rc, lower, nodes, "constrained")
 
     def solve_l0_l1(self, alpha=0.0, eta_l1=0.0, big_M=100.0, need=None, max_nodes=0, binding=None):
         """``slm_solve_l0_l1``: the exact search in its l1 mode (the reference's ``L1L0``) for
@@ -1425,49 +1448,10 @@ class Dataset:
         ``|S|``.  ``eta_l1 == 0`` runs the code of ``solve_l0``.  Returns what ``solve_l0`` returns; ``info`` also holds
         ``descents`` (candidates that passed the lower-bound filter and were valued by the descent) and ``q_all`` is the
         proven lower bound on the value of all columns that the subtree bound used."""
-        _sync_knobs()
-        G = self.n_groups
-        need_ = None
-        if need is not None:
-            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
-            if need_.shape != (G,):
-                raise ValueError(f"need must have {G} entries")
-        b = load_binding() if binding is not False else None
-        if binding is True and b is None:
-            raise EngineError("the compiled binding is not available")
-        if b is not None:
-            beta, support, lower, nodes, rec, rc = b.solve_l0_l1(self._h.value, self.p, float(alpha), float(eta_l1), float(big_M), need_,
-                                                                 int(max_nodes))
-            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
-        else:
-            beta = np.empty(self.p)
-            sup, lb, nd = C.c_uint64(), C.c_double(), C.c_int64()
-            infos = np.zeros(1, dtype=_INFO_DTYPE)
-            rc = self._lib.slm_solve_l0_l1(self._h, float(alpha), float(eta_l1), float(big_M), _ptr(need_), int(max_nodes), _ptr(beta),
-                                           C.byref(sup), C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
-            if rc != SLM_ERR_NOT_CONVERGED:
-                _check(rc)
-            support, lower, nodes, info = int(sup.value), float(lb.value), int(nd.value), infos[0]
-        return beta, int(support), {
-            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
-            "status": "optimal" if rc == SLM_OK else "node_budget", "loss": float(info["loss"]),
-            "seed_objective": float(info["mu"]), "q_all": float(info["L"]), "launches": int(info["n_iter"]),
-            "descents": int(info["rejects"]), "box_tol": 1e-12,
-        }
-
-    def _need_words(self, need):
-        """``need`` (one Python integer of up to 128 bits per group) as the wide entries take it: two 64-bit words per group,
-        the low one first."""
-        if need is None:
-            return None
-        G = self.n_groups
-        vals = [int(v) for v in need]
-        if len(vals) != G:
-            raise ValueError(f"need must have {G} entries")
-        if any(v < 0 or v >> 128 for v in vals):
-            raise ValueError("need masks must be non-negative integers of at most 128 bits")
-        mask = (1 << 64) - 1
-        return np.ascontiguousarray([[v & mask, v >> 64] for v in vals], dtype=np.uint64).reshape(G, 2)
+        args = (float(alpha), float(eta_l1), float(big_M), self._need_narrow(need), int(max_nodes))
+        (beta, support, lower, nodes), info, rc = self._l0_call(
+            "solve_l0_l1", binding, args, [np.empty(self.p), C.c_uint64(), C.c_double(), C.c_int64()])
+        return beta, int(support), self._l0_info(info, rc, lower, nodes, "l1")
 
     def solve_l0_wide(self, alpha=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None, _xb=False):
         """``slm_solve_l0_wide``: ``solve_l0`` on the kernel's wide instantiation -- up to 128 columns and 128 groups, at any
@@ -1476,38 +1460,25 @@ class Dataset:
         include that would bring a 65th is refused, and ``info`` then holds ``capacity_cut`` = the smallest number of groups
         held where that happened (``None``: never) and ``lower_bound <= q_all + alpha (capacity_cut + 1)``.  ``status`` is
         ``"capacity"`` when that alone is why the result is unproven, ``"node_budget"`` when the budget ran out."""
-        _sync_knobs()
-        G = self.n_groups
-        K = G if max_groups is None else int(max_groups)
-        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
-        need_ = self._need_words(need)
-        b = load_binding() if binding is not False else None
-        if binding is True and b is None:
-            raise EngineError("the compiled binding is not available")
-        if b is not None:
-            call = b.solve_l0_xb_wide if _xb else b.solve_l0_wide
-            beta, words, lower, nodes, rec, rc = call(self._h.value, self.p, float(alpha), K, float(eta), T_, float(big_M), need_,
-                                                      int(max_nodes))
-            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
-        else:
-            beta = np.empty(self.p)
-            words = np.zeros(2, dtype=np.uint64)
-            lb, nd = C.c_double(), C.c_int64()
-            infos = np.zeros(1, dtype=_INFO_DTYPE)
-            call = self._lib.slm_solve_l0_xb_wide if _xb else self._lib.slm_solve_l0_wide
-            rc = call(self._h, float(alpha), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes), _ptr(beta), _ptr(words),
-                      C.byref(lb), C.byref(nd), _as(infos, _PointInfo))
-            if rc != SLM_ERR_NOT_CONVERGED:
-                _check(rc)
-            lower, nodes, info = float(lb.value), int(nd.value), infos[0]
+        args = self._l0_search_args(True, alpha, max_groups, eta, T, big_M, need, max_nodes)
+        (beta, words, lower, nodes), info, rc = self._l0_call(
+            "solve_l0_xb_wide" if _xb else "solve_l0_wide", binding, args,
+            [np.empty(self.p), np.zeros(2, dtype=np.uint64), C.c_double(), C.c_int64()])
         support = int(words[0]) | (int(words[1]) << 64)
-        cut = int(info["rejects"])
-        status = "optimal" if rc == SLM_OK else "node_budget" if float(info["resid"]) != 0.0 else "capacity"
-        return beta, support, {
-            "objective": float(info["kkt"]), "lower_bound": float(lower), "proven_optimal": rc == SLM_OK, "nodes": int(nodes),
-            "status": status, "loss": float(info["loss"]), "seed_objective": float(info["mu"]), "q_all": float(info["L"]),
-            "launches": int(info["n_iter"]), "box_tol": 1e-12, "capacity_cut": cut - 1 if cut else None,
-            **(self._l0_bound_keys(info) if _xb else {}),
+        return beta, support, self._l0_info(info, rc, lower, nodes, "wide", *(("xb",) if _xb else ()))
+
+    def _l0_profile(self, wide, alpha_min, max_groups, eta, T, big_M, need, max_nodes, binding):
+        """Both profile entries: ``(betas, support words, values, info)``."""
+        K = self.n_groups if max_groups is None else int(max_groups)
+        if K < 0:
+            raise ValueError("max_groups must be >= 0")
+        args = self._l0_search_args(wide, alpha_min, K, eta, T, big_M, need, max_nodes)
+        (betas, supports, values, nodes), info, rc = self._l0_call(
+            "solve_l0_profile_wide" if wide else "solve_l0_profile", binding, args,
+            [np.empty((K + 1, self.p)), np.empty((K + 1, 2) if wide else K + 1, dtype=np.uint64), np.empty(K + 1), C.c_int64()])
+        return betas, supports, values, {
+            "nodes": int(nodes), "launches": int(info["n_iter"]), "q_all": float(info["L"]),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "proven_optimal": rc == SLM_OK, "box_tol": 1e-12,
         }
 
     def solve_l0_profile_wide(self, alpha_min=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
@@ -1515,37 +1486,8 @@ class Dataset:
         groups, ``max_groups <= 64``, refused (``NotImplementedError``) when the ``max_groups`` largest groups together hold
         more than 64 columns.  ``need`` holds Python integers of up to 128 bits; the support masks come back as a list of
         Python integers (all ones on an entry nobody filled)."""
-        _sync_knobs()
-        G = self.n_groups
-        K = G if max_groups is None else int(max_groups)
-        if K < 0:
-            raise ValueError("max_groups must be >= 0")
-        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
-        need_ = self._need_words(need)
-        b = load_binding() if binding is not False else None
-        if binding is True and b is None:
-            raise EngineError("the compiled binding is not available")
-        if b is not None:
-            betas, words, values, nodes, rec, rc = b.solve_l0_profile_wide(self._h.value, self.p, float(alpha_min), K, float(eta), T_,
-                                                                           float(big_M), need_, int(max_nodes))
-            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
-        else:
-            betas = np.empty((K + 1, self.p))
-            words = np.empty((K + 1, 2), dtype=np.uint64)
-            values = np.empty(K + 1)
-            nd = C.c_int64()
-            infos = np.zeros(1, dtype=_INFO_DTYPE)
-            rc = self._lib.slm_solve_l0_profile_wide(self._h, float(alpha_min), K, float(eta), _ptr(T_), float(big_M), _ptr(need_),
-                                                     int(max_nodes), _ptr(betas), _ptr(words), _ptr(values), C.byref(nd),
-                                                     _as(infos, _PointInfo))
-            if rc != SLM_ERR_NOT_CONVERGED:
-                _check(rc)
-            nodes, info = int(nd.value), infos[0]
-        supports = [int(lo) | (int(hi) << 64) for lo, hi in np.asarray(words).reshape(K + 1, 2)]
-        return betas, supports, values, {
-            "nodes": int(nodes), "launches": int(info["n_iter"]), "q_all": float(info["L"]),
-            "status": "optimal" if rc == SLM_OK else "node_budget", "proven_optimal": rc == SLM_OK, "box_tol": 1e-12,
-        }
+        betas, words, values, info = self._l0_profile(True, alpha_min, max_groups, eta, T, big_M, need, max_nodes, binding)
+        return betas, [int(lo) | (int(hi) << 64) for lo, hi in np.asarray(words).reshape(-1, 2)], values, info
 
     def solve_l0_profile(self, alpha_min=0.0, max_groups=None, eta=0.0, T=None, big_M=100.0, need=None, max_nodes=0, binding=None):
         """``slm_solve_l0_profile``: one search that returns the best support of EVERY size ``k = 0 .. max_groups`` for
@@ -1553,39 +1495,7 @@ class Dataset:
         only by what no ``alpha >= alpha_min`` can use.  Returns ``(betas [K + 1, p], support masks [K + 1], values [K + 1],
         info)``; an entry nobody filled holds ``+inf``, an all-ones mask and zeros.  ``info``: ``nodes``, ``launches``,
         ``q_all``, ``status``, ``proven_optimal``, ``box_tol``."""
-        _sync_knobs()
-        G = self.n_groups
-        K = G if max_groups is None else int(max_groups)
-        if K < 0:
-            raise ValueError("max_groups must be >= 0")
-        T_ = None if T is None else _f64(T, "T", (self.p, self.p))
-        need_ = None
-        if need is not None:
-            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
-            if need_.shape != (G,):
-                raise ValueError(f"need must have {G} entries")
-        b = load_binding() if binding is not False else None
-        if binding is True and b is None:
-            raise EngineError("the compiled binding is not available")
-        if b is not None:
-            betas, supports, values, nodes, rec, rc = b.solve_l0_profile(self._h.value, self.p, float(alpha_min), K, float(eta), T_,
-                                                                         float(big_M), need_, int(max_nodes))
-            info = np.frombuffer(rec, dtype=_INFO_DTYPE)[0]
-        else:
-            betas = np.empty((K + 1, self.p))
-            supports = np.empty(K + 1, dtype=np.uint64)
-            values = np.empty(K + 1)
-            nd = C.c_int64()
-            infos = np.zeros(1, dtype=_INFO_DTYPE)
-            rc = self._lib.slm_solve_l0_profile(self._h, float(alpha_min), K, float(eta), _ptr(T_), float(big_M), _ptr(need_), int(max_nodes),
-                                                _ptr(betas), _ptr(supports), _ptr(values), C.byref(nd), _as(infos, _PointInfo))
-            if rc != SLM_ERR_NOT_CONVERGED:
-                _check(rc)
-            nodes, info = int(nd.value), infos[0]
-        return betas, supports, values, {
-            "nodes": int(nodes), "launches": int(info["n_iter"]), "q_all": float(info["L"]),
-            "status": "optimal" if rc == SLM_OK else "node_budget", "proven_optimal": rc == SLM_OK, "box_tol": 1e-12,
-        }
+        return self._l0_profile(False, alpha_min, max_groups, eta, T, big_M, need, max_nodes, binding)
 
 
 class _HostPool:
