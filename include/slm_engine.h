@@ -698,6 +698,38 @@ int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_gro
                               int64_t* nodes_out, slm_point_info* info);
 
 /*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_profile, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs it looks the symbol up.)  The BATCHED l0 profile: the tables of slm_solve_l0_profile
+ * for `count` row sets of one dataset -- the training sets of a cross-validation and all rows, say -- from ONE launch
+ * (csrc/l0_kernels.hpp, template parameter BATCH), one upload and one read-back.  1 <= count <= 16, what the dataset's Gram
+ * store holds.  Row set b is (row_weights[b], n_effs[b]) as a lane of slm_solve_lanes brings them: n weights >= 0 and the
+ * divisor of its Gram (<= 0: the dataset's row count); a NULL entry is the dataset's own rows and weights.  When every entry
+ * is non-NULL the Grams come from one slm_dataset_covariance_folds call, otherwise from slm_dataset_covariance one by one.
+ * intercept != 0: the dataset's LAST column is a column of ones, alone in the LAST group (SLM_ERR_BAD_ARG otherwise); it is
+ * not searched but eliminated from every row set's Gram (G <- G - g1 g1^T / G11, c <- c - g1 c1 / G11), which is weighted
+ * centring of X and y by that row set's own weighted means, and intercept_out[b][k] = ymean_b - xmean_b^T beta.  (The
+ * elimination cancels where a column's |mean| is far above its spread: relative error about 2^-53 (1 + mean^2 / variance).)
+ * ps, the number of search columns, is p, or p - 1 with an intercept; the search groups are the dataset's without the last
+ * one then.  T (ps * ps), need (one mask per search group), alpha_min, max_groups, eta, big_M as for slm_solve_l0_profile
+ * and shared by the problems; max_nodes is the budget of EACH problem.  Problems differ in their Gram alone, hence in search
+ * order, q_all and seeds; each has its own tickets, node counter, stop word and incumbents, and a problem whose budget runs
+ * out stops alone.  Outputs per problem b as slm_solve_l0_profile's: beta_out [count][max_groups + 1][ps], intercept_out
+ * [count][max_groups + 1] (may be NULL; zeros without an intercept), support_out and value_out [count][max_groups + 1],
+ * nodes_out [count] (may be NULL), info [count] (may be NULL), info[b].status = SLM_OK or SLM_ERR_NOT_CONVERGED.  Returns
+ * SLM_OK iff every problem finished; SLM_ERR_NOT_CONVERGED with ALL outputs valid when any budget ran out.  Limits and
+ * argument errors, all before a device is touched: count outside 1 .. 16, a negative or non-finite weight and those of
+ * slm_solve_l0_profile (SLM_ERR_BAD_ARG); ps or the search groups above 64, a row-sharded dataset (SLM_ERR_UNSUPPORTED).
+ * Not here: wide, l1, constrained or exclusion-bound problems; batches over eta or T.
+ */
+int slm_solve_l0_profile_batch(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
+                               const int64_t* n_effs /* [count] */, int32_t intercept, double alpha_min, int32_t max_groups,
+                               double eta, const double* T /* ps*ps or NULL */, double big_M,
+                               const uint64_t* need /* search-group masks or NULL */, int64_t max_nodes /* per problem; <=0: default */,
+                               double* beta_out /* [count][max_groups+1][ps] */, double* intercept_out /* [count][max_groups+1] or NULL */,
+                               uint64_t* support_out /* [count][max_groups+1] */, double* value_out /* [count][max_groups+1] */,
+                               int64_t* nodes_out /* [count] or NULL */, slm_point_info* info /* [count] or NULL */);
+
+/*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant
  * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The exact l0 search with the
  * EXCLUSION BOUND (csrc/l0_kernels.hpp, template parameter XB): the arguments, outputs, argument errors and contract of

@@ -299,7 +299,7 @@ uintptr_t dataset_create(uintptr_t eng, const py::array& X_in, const py::object&
   return reinterpret_cast<uintptr_t>(out);
 }
 
-// ---- the exact search over supports: slm_solve_l0 and its seven relatives -------------------------------------------------
+// ---- the exact search over supports: slm_solve_l0 and its eight relatives -------------------------------------------------
 //
 // Every wrapper's tuple ends with (record as bytes, status).  status is SLM_OK or SLM_ERR_NOT_CONVERGED (the result is not
 // proven -- the node budget ran out, say: the outputs hold the incumbent); anything else raises.
@@ -436,6 +436,46 @@ py::tuple solve_l0_profile_wide(uintptr_t ds, int64_t p, double alpha_min, int32
                     max_nodes);
 }
 
+// slm_solve_l0_profile_batch: the profiles of several row sets of one dataset from one launch.  row_weights: a sequence of
+// arrays of n weights or None; n_effs: as many integers.  Returns (coefficients [count][max_groups + 1][ps], intercepts
+// [count][max_groups + 1], support masks, values, nodes [count], records as bytes, status); ps = p - 1 with an intercept.
+py::tuple solve_l0_profile_batch(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs,
+                                 bool intercept, double alpha_min, int32_t max_groups, double eta, const py::object& T, double big_M,
+                                 const py::object& need, int64_t max_nodes) {
+  if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
+  const py::ssize_t count = (py::ssize_t)py::len(row_weights);
+  if ((py::ssize_t)py::len(n_effs) != count) throw py::value_error("row_weights and n_effs differ in length");
+  const int64_t ps = intercept && p > 0 ? p - 1 : p;
+  Keep keep;
+  const double* Tp = vector_arg(T, ps * ps, "T", keep);
+  arr_u64 need_arr;
+  const uint64_t* needp = need_words(need, need_arr);
+  std::vector<const double*> wp((size_t)count);
+  std::vector<int64_t> ne((size_t)count);
+  for (py::ssize_t b = 0; b < count; ++b) {
+    wp[(size_t)b] = vector_arg(row_weights[b], n, "row_weights", keep);
+    ne[(size_t)b] = n_effs[b].cast<int64_t>();
+  }
+  const py::ssize_t rows = (py::ssize_t)max_groups + 1, cnt = count > 0 ? count : 1;  // (count 0: the engine refuses it)
+  py::array_t<double> beta({cnt, rows, (py::ssize_t)ps}), icpt({cnt, rows}), value({cnt, rows});
+  py::array_t<uint64_t> support({cnt, rows});
+  py::array_t<int64_t> nodes(cnt);
+  double *bp = beta.mutable_data(), *ip = icpt.mutable_data(), *vp = value.mutable_data();
+  uint64_t* sup = support.mutable_data();
+  int64_t* np_ = nodes.mutable_data();
+  py::array info = info_bytes(cnt);
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_profile_batch(reinterpret_cast<slm_dataset*>(ds), (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, alpha_min,
+                                    max_groups, eta, Tp, big_M, needp, max_nodes, bp, ip, sup, vp, np_, rec);
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, icpt, support, value, nodes, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -458,6 +498,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_wide", &solve_l0_wide<false>);
   m.def("solve_l0_xb_wide", &solve_l0_wide<true>);
   m.def("solve_l0_profile_wide", &solve_l0_profile_wide);
+  m.def("solve_l0_profile_batch", &solve_l0_profile_batch);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

@@ -1,10 +1,11 @@
 // Host side of the MI355X fit engine, sixth unit: the exact l0 estimators (csrc/l0_kernels.hpp) -- the reference's
 // mixed-integer family (reference src/sparselm/model/_miqp/_best_subset.py, _regularized_l0.py), which it hands to
-// Gurobi or SCIP through cvxpy.  Eight entries, three functions (solve_l0_impl, solve_l0_profile_impl, solve_l0_con_impl), ONE
+// Gurobi or SCIP through cvxpy.  Nine entries, four functions (solve_l0_impl, solve_l0_profile_impl, solve_l0_con_impl,
+// solve_l0_profile_batch_impl), ONE
 // pipeline, everything around the launch on the host (p <= 128: microseconds):
 //   check    l0_check_args, and what a mode adds: whatever can be refused is refused before a device is touched
-//   prepare  l0_prepare: the dataset's own Gram (engine_cov.hip), the search order, H = G + 2 eta T, c and the hierarchy in that
-//            order, the unconstrained value q_all on all columns
+//   prepare  l0_prepare: the dataset's own Gram (engine_cov.hip; l0_fetch_gram), then l0_order: the search order, H = G + 2 eta T, c
+//            and the hierarchy in that order, the unconstrained value q_all on all columns
 //   seed     l0_greedy of l0_host.hpp, every support valued as the kernel values a node
 //   plan     l0_plan: the grid, the layout of the one device block (l0_layout), its host image, the kernel's common arguments;
 //            a mode appends its sections (L0Plan::append) and seeds its control words
@@ -24,6 +25,9 @@
 //   slm_solve_l0_xb, slm_solve_l0_xb_wide  the XB instantiations: the subtree bound on everything not yet excluded.
 //       l0_excl_plan of l0_host.hpp hands over P = H^-1, P c (appended to the block) and the margin delta; where H is not
 //       positive definite on all columns, or delta >= 1/2, the plain kernel runs on the plain block and info->mode says so.
+//   slm_solve_l0_profile_batch  the BATCH instantiation: the profiles of up to 16 row sets of the dataset (CV folds, all rows) from
+//       one launch.  Per problem the profile's own pieces (l0_fetch_gram, l0_order, l0_profile_seed, l0_profile_collect) on its copy
+//       of the block (l0_batch_layout of l0_host.hpp); an intercept column is eliminated per row set (l0_eliminate_last).
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -38,19 +42,19 @@ inline unsigned long long l0_need_of(const uint64_t* need, int g, unsigned long 
 inline L0Mask128 l0_need_of(const uint64_t* need, int g, L0Mask128) { return L0Mask128{need[2 * g], need[2 * g + 1]}; }
 
 // The argument checks every entry shares, before anything touches the device.  alpha_name: what the l0 weight is called in
-// the entry's own signature.  Leaves p and the group count.  Mask: one word, or the two of the wide entries (need then holds
+// the entry's own signature.  Leaves p and the group count (without the last `drop` columns and groups).  Mask: one word, or the two of the wide entries (need then holds
 // two words per group, the low one first; the limits are L0_WIDE_PMAX).
 template <class Mask>
 int l0_check_args(slm_dataset* ds, const void* out, double alpha, const char* alpha_name, double eta, double eta_l1, double big_M,
-                  const double* T, const uint64_t* need, int* p_out, int* ng_out) {
+                  const double* T, const uint64_t* need, int* p_out, int* ng_out, int drop = 0) {
   constexpr int pmax = std::is_same_v<Mask, L0Mask128> ? L0_WIDE_PMAX : L0_PMAX;
   if (!ds || !out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(SLM_ERR_BAD_ARG, "%s must be finite and >= 0", alpha_name);
   if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(SLM_ERR_BAD_ARG, "eta must be finite and >= 0");
   if (!(eta_l1 >= 0.0) || !std::isfinite(eta_l1)) return fail(SLM_ERR_BAD_ARG, "eta_l1 must be finite and >= 0");
   if (!(big_M >= 0.0)) return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
-  const int64_t p64 = ds->p;
-  const int ng = ds->singleton ? (int)std::min<int64_t>(p64, pmax + 1) : ds->G;
+  const int64_t p64 = ds->p - drop;  // (drop: the batched profile's intercept column, last and alone in the last group, is not searched)
+  const int ng = ds->singleton ? (int)std::min<int64_t>(p64, pmax + 1) : ds->G - drop;
   if (need && ng <= pmax)
     for (int g = 0; g < ng; ++g)
       if (l0m_any_outside(l0_need_of(need, g, Mask{}), l0m_below<Mask>(ng)))
@@ -78,20 +82,10 @@ struct L0ProblemT {
   double q_all = 0.0, yy = 0.0;
 };
 
-template <class Mask>
-int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, const uint64_t* need, L0ProblemT<Mask>& P) {
-  slm_engine* eng = ds->eng;
-  HIP_TRY(hipSetDevice(eng->device));
-  hipStream_t s = eng->stream;
-
-  // ---- the dataset's own Gram: G = X^T W X / n, c = X^T W y / n (built by the covariance code when it is not there) ------
-  SLM_TRY(slm_dataset_covariance(ds, nullptr, 0));
-  const double* wdev = ds->rw;
-  double fp[2];
-  SLM_TRY(cov_fingerprints(ds, &wdev, 1, fp));
-  const int entry = cov_find(ds, fp[0], fp[1], (double)ds->n_global);
+// Entry `entry` of the dataset's Gram store to the host: G = X^T W X / n_eff, c = X^T W y / n_eff, yy = y^T W y / n_eff.
+int l0_fetch_gram(slm_dataset* ds, int p, int entry, std::vector<double>& G, std::vector<double>& cvec, double* yy) {
+  hipStream_t s = ds->eng->stream;
   if (entry < 0) return fail(SLM_ERR_HIP, "the dataset's Gram was not filed");
-  std::vector<double>&G = P.G, &cvec = P.cvec;
   G.assign((size_t)p * p, 0.0);
   cvec.assign((size_t)p, 0.0);
   HIP_TRY(hipStreamSynchronize(s));
@@ -102,6 +96,14 @@ int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, cons
     if (!std::isfinite(v)) return fail(SLM_ERR_NON_FINITE, "the Gram holds a non-finite value (non-finite data)");
   for (double v : cvec)
     if (!std::isfinite(v)) return fail(SLM_ERR_NON_FINITE, "X^T y holds a non-finite value (non-finite data)");
+  *yy = ds->cov[(size_t)entry].yy;
+  return SLM_OK;
+}
+
+// From P.G, P.cvec (the first p columns of the dataset, in its order) to the search's own order; host code only.
+template <class Mask>
+void l0_order(const slm_dataset* ds, int p, int ng, double eta, const double* T, const uint64_t* need, L0ProblemT<Mask>& P) {
+  const std::vector<double>&G = P.G, &cvec = P.cvec;
 
   // ---- search order: groups by descending ||c_g||^2 / tr G_gg (ties: the lower index), a group's columns contiguous --------
   std::vector<int> gid((size_t)p);
@@ -148,7 +150,18 @@ int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, cons
 
   // ---- the unconstrained value on all columns ------------------------------------------------------------------------------
   P.q_all = l0_q_all(H.data(), c.data(), p);
-  P.yy = ds->cov[(size_t)entry].yy;
+}
+
+template <class Mask>
+int l0_prepare(slm_dataset* ds, int p, int ng, double eta, const double* T, const uint64_t* need, L0ProblemT<Mask>& P) {
+  HIP_TRY(hipSetDevice(ds->eng->device));
+  // ---- the dataset's own Gram ---------------------------------------------------------------------------------------------
+  SLM_TRY(slm_dataset_covariance(ds, nullptr, 0));
+  const double* wdev = ds->rw;
+  double fp[2];
+  SLM_TRY(cov_fingerprints(ds, &wdev, 1, fp));
+  SLM_TRY(l0_fetch_gram(ds, p, cov_find(ds, fp[0], fp[1], (double)ds->n_global), P.G, P.cvec, &P.yy));
+  l0_order(ds, p, ng, eta, T, need, P);
   return SLM_OK;
 }
 
@@ -353,6 +366,67 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
   return SLM_OK;
 }
 
+// The profile's pieces around its launch, shared by the single entries and the batched one.
+constexpr int kL0BatchMax = 16;  // problems of one batched launch: what the dataset's Gram store holds
+template <class Mask>
+struct L0ProfileWork {
+  L0ProblemT<Mask> P;
+  std::vector<double> win_val;  // [L0_PMAX + 1] per size: the seed, then the winner
+  std::vector<Mask> win_mask;
+};
+// the seed of every size: the supports the greedy selection passes through, valued as the kernel values a node
+template <class Mask>
+void l0_profile_seed(L0ProfileWork<Mask>& W, int p, int K, double big_M) {
+  const L0ProblemT<Mask>& P = W.P;
+  const double *H = P.H.data(), *c = P.c.data();
+  std::vector<double> beta_s((size_t)p);
+  W.win_val.assign((size_t)L0_PMAX + 1, HUGE_VAL);
+  W.win_mask.assign((size_t)L0_PMAX + 1, l0m_ones<Mask>());
+  W.win_val[0] = 0.0;  // the empty support
+  W.win_mask[0] = l0m_none<Mask>();
+  l0_greedy(H, c, p, P.gstart, P.needo, K, [&](Mask mask) { return l0_support_of(H, c, p, P.gstart, mask, big_M, false, beta_s.data()); },
+            [&](int size, Mask mask, double quad) {
+              if (l0_better(quad, mask, W.win_val[(size_t)size], W.win_mask[(size_t)size])) {
+                W.win_val[(size_t)size] = quad;
+                W.win_mask[(size_t)size] = mask;
+              }
+            });
+}
+// the incumbents of the sizes 1 .. 64 behind the control words of one problem's image
+template <class Mask>
+void l0_profile_seed_image(const L0ProfileWork<Mask>& W, unsigned long long* h) {
+  for (int k = 1; k <= L0_PMAX; ++k) h[(size_t)L0_PROFILE_INC + (size_t)k - 1] = l0_key(W.win_val[(size_t)k]);
+}
+// per size: the winner among the seed and the waves' results, its coefficients recomputed here; a size nobody filled: +inf, all
+// ones, zeros.  h: one problem's part of the block as read back.  Then the node count and the record.
+template <class Mask>
+void l0_profile_collect(L0ProfileWork<Mask>& W, const unsigned long long* h, const L0Layout& y, int p, int rows, int K, double alpha_min,
+                        double big_M, bool finished, double* beta_out, uint64_t* support_out, double* value_out, int64_t* nodes_out,
+                        slm_point_info* info) {
+  const L0ProblemT<Mask>& P = W.P;
+  const double *H = P.H.data(), *c = P.c.data();
+  std::vector<double> beta_s((size_t)p);
+  for (int size = 1; size <= K; ++size) l0_winner(h, y.off_bv, y.off_bm, y.waves, 64, size - 1, W.win_val[(size_t)size], W.win_mask[(size_t)size]);
+  for (int size = 0; size <= rows; ++size) {
+    double* beta = beta_out + (size_t)size * p;
+    for (int i = 0; i < p; ++i) beta[i] = 0.0;
+    const bool filled = size <= K && std::isfinite(W.win_val[(size_t)size]);
+    value_out[size] = HUGE_VAL;
+    Mask support = l0m_ones<Mask>();
+    if (filled) {
+      value_out[size] = l0_support_of(H, c, p, P.gstart, W.win_mask[(size_t)size], big_M, true, beta_s.data());
+      support = l0_caller_mask(W.win_mask[(size_t)size], P.gorder);
+      l0_scatter(beta_s.data(), P.cols, beta);
+    }
+    memcpy(support_out + (sizeof(Mask) / sizeof(uint64_t)) * (size_t)size, &support, sizeof(Mask));  // (a mask: one word, wide two)
+  }
+  if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
+  if (info) {
+    const int at = l0_profile_regularized(value_out, K, alpha_min), sub = l0_profile_best_subset(value_out, K);
+    l0_report(info, finished, 0.0, value_out[at] + alpha_min * (double)at, value_out[sub], P.q_all);
+  }
+}
+
 // slm_solve_l0_profile, _profile_wide: a seed and a winner per size.  Wide: lane k - 1 still holds size k, and no include may be
 // refused for capacity, so a call whose max_groups largest groups could hold more than L0_PMAX columns is refused before anything
 // is launched.
@@ -378,55 +452,160 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
       return fail(SLM_ERR_UNSUPPORTED, "the wide l0 profile needs every support to fit the factor: the %d largest groups hold %d columns, "
                   "more than %d", K, most, L0_PMAX);
   }
-  L0ProblemT<Mask> P;
-  SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, P));
-  const double *H = P.H.data(), *c = P.c.data();
-
-  // ---- the seed of every size: the supports the greedy selection passes through, valued as the kernel values a node ---------
-  std::vector<double> beta_s((size_t)p);
-  std::vector<double> win_val((size_t)L0_PMAX + 1, HUGE_VAL);
-  std::vector<Mask> win_mask((size_t)L0_PMAX + 1, l0m_ones<Mask>());
-  win_val[0] = 0.0;  // the empty support
-  win_mask[0] = l0m_none<Mask>();
-  l0_greedy(H, c, p, P.gstart, P.needo, K, [&](Mask mask) { return l0_support_of(H, c, p, P.gstart, mask, big_M, false, beta_s.data()); },
-            [&](int size, Mask mask, double quad) {
-              if (l0_better(quad, mask, win_val[(size_t)size], win_mask[(size_t)size])) {
-                win_val[(size_t)size] = quad;
-                win_mask[(size_t)size] = mask;
-              }
-            });
+  L0ProfileWork<Mask> W;
+  SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, W.P));
+  l0_profile_seed(W, p, K, big_M);
 
   // ---- the search: one launch, 64 results per wave, the incumbents of the sizes 1 .. 64 behind the control words ----------------
-  L0Plan plan = l0_plan(ds->eng, P, p, ng, K, 64, L0_PROFILE_WORDS, alpha_min, big_M, P.q_all, max_nodes);
-  for (int k = 1; k <= L0_PMAX; ++k) plan.h[(size_t)L0_PROFILE_INC + (size_t)k - 1] = l0_key(win_val[(size_t)k]);
+  L0Plan plan = l0_plan(ds->eng, W.P, p, ng, K, 64, L0_PROFILE_WORDS, alpha_min, big_M, W.P.q_all, max_nodes);
+  l0_profile_seed_image(W, plan.h.data());
   if constexpr (WIDE) plan.h[L0_CAPACITY] = ~0ull;
   SLM_TRY(l0_run(ds->eng, plan, l0_search_kernel<false, true, WIDE>));
   const std::vector<unsigned long long>& h = plan.h;
 
-  // ---- per size: the winner, its coefficients recomputed here; a size nobody filled: +inf, all ones, zeros --------------------
-  for (int size = 1; size <= K; ++size)
-    l0_winner(h.data(), plan.y.off_bv, plan.y.off_bm, plan.y.waves, 64, size - 1, win_val[(size_t)size], win_mask[(size_t)size]);
   const bool finished = h[L0_ABORTED] == 0;
   if (WIDE && h[L0_CAPACITY] != ~0ull) return fail(SLM_ERR_HIP, "the wide l0 profile refused an include for capacity (internal error)");
-  for (int size = 0; size <= rows; ++size) {
-    double* beta = beta_out + (size_t)size * p;
-    for (int i = 0; i < p; ++i) beta[i] = 0.0;
-    const bool filled = size <= K && std::isfinite(win_val[(size_t)size]);
-    value_out[size] = HUGE_VAL;
-    Mask support = l0m_ones<Mask>();
-    if (filled) {
-      value_out[size] = l0_support_of(H, c, p, P.gstart, win_mask[(size_t)size], big_M, true, beta_s.data());
-      support = l0_caller_mask(win_mask[(size_t)size], P.gorder);
-      l0_scatter(beta_s.data(), P.cols, beta);
-    }
-    memcpy(support_out + (WIDE ? 2 : 1) * (size_t)size, &support, sizeof(Mask));  // (a mask: one word, wide two)
-  }
-  if (nodes_out) *nodes_out = (int64_t)h[L0_NODES];
-  if (info) {
-    const int at = l0_profile_regularized(value_out, K, alpha_min), sub = l0_profile_best_subset(value_out, K);
-    l0_report(info, finished, 0.0, value_out[at] + alpha_min * (double)at, value_out[sub], P.q_all);
-  }
+  l0_profile_collect(W, h.data(), plan.y, p, rows, K, alpha_min, big_M, finished, beta_out, support_out, value_out, nodes_out, info);
   if (!finished) return l0_budget_ran_out(plan, "table of incumbents");
+  return SLM_OK;
+}
+
+// slm_solve_l0_profile_batch: the profiles of `count` row sets of one dataset from ONE launch of the kernel's BATCH instantiation.
+// Per problem today's pipeline, piece by piece: its Gram (fetched before anything else: l0_fetch_gram), the intercept column
+// eliminated (l0_eliminate_last), l0_order, l0_profile_seed, its copy of the block (l0_batch_layout, l0_fill_image,
+// l0_profile_seed_image, q_all in L0_BATCH_QALL); then one upload, one launch, one read-back of the block, and
+// l0_profile_collect per problem.
+int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs, int32_t intercept,
+                                double alpha_min, int32_t max_groups, double eta, const double* T, double big_M, const uint64_t* need,
+                                int64_t max_nodes, double* beta_out, double* intercept_out, uint64_t* support_out, double* value_out,
+                                int64_t* nodes_out, slm_point_info* info) {
+  using Mask = unsigned long long;
+  int ps = 0, ng = 0;
+  if (count < 1 || count > kL0BatchMax) return fail(SLM_ERR_BAD_ARG, "count must be 1 .. %d, the Gram store's capacity (got %d)", kL0BatchMax, count);
+  if (!support_out || !value_out || !row_weights || !n_effs) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  const int drop = intercept != 0 ? 1 : 0;
+  if (ds && drop) {  // the ones column: last, alone in the last group
+    const int64_t p = ds->p;
+    const int G = ds->singleton ? (int)std::min<int64_t>(p, 1 << 30) : ds->G;
+    bool alone = p >= 1 && G >= 1;
+    for (int64_t j = 0; j < p && alone && !ds->h_gid.empty(); ++j) alone = (ds->h_gid[(size_t)j] == G - 1) == (j == p - 1);
+    if (!alone) return fail(SLM_ERR_BAD_ARG, "intercept: the last column must be alone in the last group");
+  }
+  SLM_TRY(l0_check_args<Mask>(ds, beta_out, alpha_min, "alpha_min", eta, 0.0, big_M, T, need, &ps, &ng, drop));
+  const int p = ps + drop;
+  const int rows = max_groups < 0 ? 0 : (int)max_groups;
+  const int K = std::min(rows, ng);
+  const int64_t n = ds->n;
+  for (int b = 0; b < count; ++b)
+    for (int64_t i = 0; i < n && row_weights[b]; ++i)
+      if (!(row_weights[b][i] >= 0.0) || !std::isfinite(row_weights[b][i]))
+        return fail(SLM_ERR_BAD_ARG, "row_weights[%d][%lld] must be finite and >= 0", b, (long long)i);
+  slm_engine* eng = ds->eng;
+  HIP_TRY(hipSetDevice(eng->device));
+  hipStream_t s = eng->stream;
+
+  // ---- the Grams: the folds' in one call when every row set brings its weights, else one by one; each fetched at once ---------
+  bool all_given = true;
+  for (int b = 0; b < count; ++b) all_given = all_given && row_weights[b] != nullptr;
+  struct Weights {
+    double* dev = nullptr;
+    hipStream_t s;
+    ~Weights() {
+      (void)hipStreamSynchronize(s);
+      dfree(dev);
+    }
+  } wts;
+  wts.s = s;
+  SLM_TRY(dalloc(&wts.dev, (size_t)count * (size_t)n));
+  std::vector<const double*> wdev((size_t)count);
+  std::vector<double> neff((size_t)count);
+  for (int b = 0; b < count; ++b) {
+    neff[(size_t)b] = row_weights[b] && n_effs[b] > 0 ? (double)n_effs[b] : (double)ds->n_global;
+    wdev[(size_t)b] = ds->rw;
+    if (!row_weights[b]) continue;
+    wdev[(size_t)b] = wts.dev + (size_t)b * (size_t)n;
+    HIP_TRY(hipMemcpyAsync(wts.dev + (size_t)b * (size_t)n, row_weights[b], sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  if (all_given) SLM_TRY(slm_dataset_covariance_folds(ds, row_weights, n_effs, count));
+  std::vector<double> fp(2 * (size_t)count);
+  SLM_TRY(cov_fingerprints(ds, wdev.data(), count, fp.data()));
+  std::vector<L0ProfileWork<Mask>> W((size_t)count);
+  std::vector<double> xmean((size_t)count * (size_t)ps, 0.0), ymean((size_t)count, 0.0);
+  for (int b = 0; b < count; ++b) {
+    L0ProblemT<Mask>& P = W[(size_t)b].P;
+    int entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
+    if (entry < 0) {  // not from the folds' call (or pushed out of the store by a later one): built here, fetched at once
+      SLM_TRY(slm_dataset_covariance(ds, row_weights[b], row_weights[b] ? n_effs[b] : 0));
+      entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
+    }
+    SLM_TRY(l0_fetch_gram(ds, p, entry, P.G, P.cvec, &P.yy));
+    if (drop) {
+      std::vector<double> Gs((size_t)ps * ps), cs((size_t)ps);
+      if (!l0_eliminate_last(P.G.data(), P.cvec.data(), p, P.yy, Gs.data(), cs.data(), &P.yy, xmean.data() + (size_t)b * ps, &ymean[(size_t)b]))
+        return fail(SLM_ERR_BAD_ARG, "intercept: row set %d gives the last column no weight", b);
+      P.G.swap(Gs);
+      P.cvec.swap(cs);
+    }
+    l0_order(ds, ps, ng, eta, T, need, P);
+    l0_profile_seed(W[(size_t)b], ps, K, big_M);
+  }
+
+  // ---- the block: `count` copies of the profile layout; one upload, ONE launch, one read-back ------------------------------------
+  const L0BatchLayout B = l0_batch_layout(count, ps, ng, eng->cus, 1, 64, L0_PROFILE_WORDS, L0_PREFIX, L0_WAVES);
+  const L0Layout& y = B.one;
+  std::vector<unsigned long long> h(B.words, 0ull);
+  for (int b = 0; b < count; ++b) {
+    const L0ProblemT<Mask>& P = W[(size_t)b].P;
+    unsigned long long* hb = h.data() + B.at(b);
+    l0_fill_image(y, P.H.data(), P.c.data(), ps, P.needo, P.gstart, hb);
+    l0_profile_seed_image(W[(size_t)b], hb);
+    memcpy(hb + L0_BATCH_QALL, &P.q_all, sizeof(double));
+  }
+  L0Args k;
+  memset(&k, 0, sizeof(k));
+  k.p = ps; k.ng = ng; k.d = y.d; k.K = K;
+  k.alpha = alpha_min; k.big_M = big_M;
+  k.max_nodes = max_nodes > 0 ? max_nodes : kL0DefaultNodes;
+  k.batch_stride = (long long)B.stride;
+  k.batch_blocks = y.blocks;
+  {
+    unsigned long long* dev = nullptr;
+    SLM_TRY(dalloc(&dev, B.words));
+    L0DevGuard guard{dev, s};
+    HIP_TRY(hipMemcpyAsync(dev, h.data(), sizeof(unsigned long long) * B.words, hipMemcpyHostToDevice, s));
+    k.ctl = dev;
+    k.best_val = reinterpret_cast<double*>(dev + y.off_bv);
+    k.best_mask = dev + y.off_bm;
+    k.H = reinterpret_cast<const double*>(dev + y.off_H);
+    k.c = reinterpret_cast<const double*>(dev + y.off_c);
+    k.need = dev + y.off_need;
+    k.gstart = reinterpret_cast<const long long*>(dev + y.off_gs);
+    hipLaunchKernelGGL((l0_search_kernel<false, true, false, false, false, true>), dim3((unsigned)B.grid()), dim3(64 * L0_WAVES), 0, s, k);
+    SLM_TRY(check_launch());
+    // one read-back: the whole block (the results are most of every copy; H, c, need and the group starts come back as they went)
+    HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(unsigned long long) * B.words, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+
+  // ---- per problem: the winners, the table, the record -------------------------------------------------------------------------------
+  const size_t tab = (size_t)rows + 1;
+  int unfinished = 0, first = -1;
+  for (int b = 0; b < count; ++b) {
+    const unsigned long long* hb = h.data() + B.at(b);
+    const bool finished = hb[L0_ABORTED] == 0;
+    if (!finished && unfinished++ == 0) first = b;
+    double* beta_b = beta_out + (size_t)b * tab * ps;
+    l0_profile_collect(W[(size_t)b], hb, y, ps, rows, K, alpha_min, big_M, finished, beta_b, support_out + (size_t)b * tab, value_out + (size_t)b * tab,
+                       nodes_out ? nodes_out + b : nullptr, info ? info + b : nullptr);
+    for (size_t size = 0; size < tab && intercept_out; ++size) {
+      double t = drop ? ymean[(size_t)b] : 0.0;
+      for (int j = 0; j < ps && drop; ++j) t -= xmean[(size_t)b * ps + j] * beta_b[size * ps + j];
+      intercept_out[(size_t)b * tab + size] = t;
+    }
+  }
+  if (unfinished)
+    return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld per problem) ran out in %d of %d problems (the first: %d): their tables of "
+                "incumbents are returned", k.max_nodes, unfinished, count, first);
   return SLM_OK;
 }
 
@@ -659,4 +838,13 @@ extern "C" int slm_solve_l0_constrained(slm_dataset* ds, double alpha, int32_t m
                                         double* lambda_out, slm_point_info* info) {
   return solve_l0_con_impl(ds, alpha, max_groups, eta, T, big_M, need, max_nodes, A, m, lo, hi, box_lo, box_hi, max_qp_sweeps, beta_out,
                            support_out, lower_bound_out, nodes_out, lambda_out, info);
+}
+
+// The profiles of `count` row sets of one dataset (CV folds and all rows) from one launch of the kernel's batched instantiation.
+extern "C" int slm_solve_l0_profile_batch(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                                          int32_t intercept, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
+                                          const uint64_t* need, int64_t max_nodes, double* beta_out, double* intercept_out,
+                                          uint64_t* support_out, double* value_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_profile_batch_impl(ds, count, row_weights, n_effs, intercept, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out,
+                                     intercept_out, support_out, value_out, nodes_out, info);
 }

@@ -10,7 +10,9 @@
 // check and the lower bound on all columns.  The exclusion bound (slm_solve_l0_xb, slm_solve_l0_xb_wide;
 // tests/l0_bound_host_test.cpp) adds P = H^-1, P c, the margin delta and the guarded bound host and device share.  The end of
 // the file holds what every entry's launch shares (tests/l0_launch_host_test.cpp): the layout of the device block, the
-// winner among the waves' results, the way back to the caller's groups and columns, and the loss from the Gram.
+// winner among the waves' results, the way back to the caller's groups and columns, and the loss from the Gram.  The batched
+// profile (slm_solve_l0_profile_batch; tests/l0_batch_host_test.cpp) adds the layout of several problems in one block and the
+// elimination of an intercept column from a Gram.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -962,10 +964,11 @@ struct L0Layout {
   size_t off_bv = 0, off_bm = 0, off_H = 0, off_c = 0, off_need = 0, off_gs = 0, words = 0;
   size_t append(size_t n) { return (words += n) - n; }  // a section of n words behind what is there; its offset
 };
-inline L0Layout l0_layout(int p, int ng, int cus, int mask_words, int slots, int ctl_words, int prefix, int block_waves) {
+// (max_blocks: the most workgroups one problem may have -- two per CU for a problem that has the device to itself)
+inline L0Layout l0_layout_capped(int p, int ng, long long max_blocks, int mask_words, int slots, int ctl_words, int prefix, int block_waves) {
   L0Layout y;
   y.d = std::min(ng, prefix);  // 2^d tickets, one per wave while they last: at least one workgroup, at most two per CU
-  y.blocks = (int)std::max<long long>(1, std::min<long long>(2ll * cus, ((1ll << y.d) + block_waves - 1) / block_waves));
+  y.blocks = (int)std::max<long long>(1, std::min<long long>(max_blocks, ((1ll << y.d) + block_waves - 1) / block_waves));
   y.waves = y.blocks * block_waves;
   y.slots = slots;
   y.mask_words = mask_words;
@@ -977,6 +980,55 @@ inline L0Layout l0_layout(int p, int ng, int cus, int mask_words, int slots, int
   y.off_need = y.append((size_t)mask_words * ng);
   y.off_gs = y.append((size_t)ng + 1);
   return y;
+}
+inline L0Layout l0_layout(int p, int ng, int cus, int mask_words, int slots, int ctl_words, int prefix, int block_waves) {
+  return l0_layout_capped(p, ng, 2ll * cus, mask_words, slots, ctl_words, prefix, block_waves);
+}
+// The batched profile (slm_solve_l0_profile_batch): `count` problems of one shape in one block, each a whole copy of the
+// layout above, back to back.  `one` is a single problem's layout with its offsets relative to the copy; problem b's copy
+// starts at word at(b) = b * stride.  The problems share the device: blocks_b = clamp(ceil(2^d / block_waves), 1,
+// max(1, floor(2 cus / count))) workgroups each (one.blocks), so that the grid of count * blocks_b workgroups is resident
+// at once like a single problem's.  count = 1 is l0_layout.
+struct L0BatchLayout {
+  L0Layout one;
+  int count = 1;
+  size_t stride = 0, words = 0;
+  size_t at(int b) const { return (size_t)b * stride; }
+  int grid() const { return count * one.blocks; }
+};
+inline L0BatchLayout l0_batch_layout(int count, int p, int ng, int cus, int mask_words, int slots, int ctl_words, int prefix, int block_waves) {
+  L0BatchLayout B;
+  B.count = count;
+  B.one = l0_layout_capped(p, ng, 2ll * cus / count, mask_words, slots, ctl_words, prefix, block_waves);
+  B.stride = B.one.words;
+  B.words = B.stride * (size_t)count;
+  return B;
+}
+
+// Elimination of an intercept column from the Gram of [X | 1] on one row set (weights w, sum w = n_eff):
+//     G <- G - g1 g1^T / G11,   c <- c - g1 c1 / G11,   yy <- yy - c1^2 / G11,      g1 = G[:, last], c1 = c[last], G11 = G[last][last]
+// -- the Schur complement of the ones column, which is exactly weighted centring of X and y by that row set's own weighted
+// means xmean = g1 / G11 and ymean = c1 / G11, so one Gram build per row set gives the centred problem of each.  The
+// intercept that goes with coefficients beta is ymean - xmean^T beta.
+// Cancellation: G_ij holds mean_i mean_j + cov_ij and the subtraction removes the first term, so the centred entry keeps a
+// relative error of about 2^-53 (1 + mean_i mean_j / cov_ij): a column whose |mean| is 1e4 times its spread loses eight to
+// nine of sixteen digits (tests/l0_batch_host_test.cpp measures 3.8e-7; centring X before the product does not).  Data far
+// from the origin should be shifted by the caller.
+// In: G [p][p], c [p] with the ones column LAST.  Out: Gs [(p - 1)][(p - 1)], cs, xmean [p - 1].  false: G11 is not positive.
+inline bool l0_eliminate_last(const double* G, const double* c, int p, double yy, double* Gs, double* cs, double* yys, double* xmean,
+                              double* ymean) {
+  const int q = p - 1;
+  const double g11 = G[(size_t)q * p + q], c1 = c[q];
+  if (!(g11 > 0.0) || !std::isfinite(g11)) return false;
+  for (int i = 0; i < q; ++i) {
+    const double gi = G[(size_t)i * p + q];
+    xmean[i] = gi / g11;
+    cs[i] = c[i] - gi * c1 / g11;
+    for (int j = 0; j < q; ++j) Gs[(size_t)i * q + j] = G[(size_t)i * p + j] - gi * G[(size_t)j * p + q] / g11;  // (symmetric when G is)
+  }
+  *ymean = c1 / g11;
+  *yys = yy - c1 * c1 / g11;
+  return true;
 }
 // the common sections of the host image h[y.words] (control, results and whatever is appended stay as they are)
 template <class Mask>

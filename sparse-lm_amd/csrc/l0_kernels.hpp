@@ -105,7 +105,8 @@ constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
 constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CAPACITY = 6, L0_UNSETTLED = 7,
-              L0_UNSETTLED_COUNT = 8, L0_CTL_WORDS = 10;
+              L0_UNSETTLED_COUNT = 8, L0_BATCH_QALL = 9, L0_CTL_WORDS = 10;
+// (L0_BATCH_QALL, batched profile only: the bits of the problem's own q_all, written by the host and only read on the device)
 // (L0_CAPACITY, wide mode only: seeded with all ones, lowered to c_min + 1 by a wave that refused an include for capacity)
 // (L0_UNSETTLED, constrained mode only: seeded with all ones, lowered to the key of D + alpha |S| by a wave whose candidate ran
 //  out of sweeps; L0_UNSETTLED_COUNT counts them.  L0_DESCENTS counts the candidates valued in l1 and constrained mode.)
@@ -138,6 +139,9 @@ struct L0Args {
   const double* P;                  // [p][p] H^-1, search order
   const double* bhat;               // [p] P c
   double xb_delta;                  // the relative margin of the increment (l0_excl_bound)
+  // batched profile only: the pointers above are problem 0's, problem b's lie b * batch_stride words further on
+  long long batch_stride;           // 8-byte words from one problem's copy of the block to the next
+  int batch_blocks;                 // workgroups per problem: problem b owns the workgroups b * batch_blocks .. (b + 1) * batch_blocks - 1
 };
 
 // order-preserving image of a double in an unsigned 64-bit integer (and back)
@@ -194,12 +198,30 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
 // WIDE = true: up to 128 columns and groups (see the head of the file); what it adds sits under if constexpr or behind Mask.
 // CON = true: linear constraints and a per-column box (see the head of the file); everything it adds sits under if constexpr.
 // XB = true: the exclusion bound (see the head of the file); everything it adds sits under if constexpr.
-template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false, bool XB = false>
+// BATCH = true (slm_solve_l0_profile_batch; narrow profile only): up to 16 problems of one shape in one launch.  The block is
+// `count` copies of the single-problem profile layout at a constant stride (l0_batch_layout of l0_host.hpp); a workgroup
+// belongs to problem blockIdx.x / batch_blocks, moves every base pointer to that copy and numbers its waves within the
+// problem.  Ticket counter, node counter, stop and aborted words, the 64 incumbents and q_all (L0_BATCH_QALL) are the copy's
+// own, so a problem that runs out of its budget stops its own workgroups alone, and waves of different problems share no
+// word: no new barrier, no new loop.  A workgroup whose problem has no ticket left exits (it is not moved to another
+// problem: that would re-stage H behind a barrier).  Everything it adds sits under if constexpr.
+template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false, bool XB = false, bool BATCH = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
   static_assert(!(L1 && PROFILE), "the profile mode has no l1 term");
   static_assert(!(L1 && WIDE), "there is no wide l1 mode");
   static_assert(!(CON && (L1 || PROFILE || WIDE)), "the constrained mode stands alone");
   static_assert(!(XB && (L1 || PROFILE || CON)), "the exclusion bound serves the plain search, narrow and wide");
+  static_assert(!(BATCH && (!PROFILE || L1 || WIDE || CON || XB)), "a batch holds narrow profile searches and nothing else");
+  if constexpr (BATCH) {  // the workgroup's problem (wave-uniform): every base pointer moves to that problem's copy of the block
+    const size_t at = (size_t)(blockIdx.x / (unsigned)a.batch_blocks) * (size_t)a.batch_stride;
+    a.ctl += at;
+    a.best_val += at;
+    a.best_mask += at;
+    a.H += at;
+    a.c += at;
+    a.need += at;
+    a.gstart += at;
+  }
   using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
   constexpr int PM = WIDE ? L0_WIDE_PMAX : L0_PMAX;
   __shared__ double Hs[WIDE ? PM * (PM + 1) / 2 : PM * PM];  // (wide: the lower triangle, row i at i (i + 1) / 2)
@@ -279,7 +301,9 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   };
 
   const long long n_tickets = 1ll << d;
-  const double alpha = a.alpha, big_M = a.big_M, q_all = a.q_all;
+  const double alpha = a.alpha, big_M = a.big_M;
+  double q_all = a.q_all;
+  if constexpr (BATCH) q_all = __longlong_as_double((long long)a.ctl[L0_BATCH_QALL]);  // (the folds' c differ: so does the bound)
   // lane r: row r of L (entries below the diagonal), 1 / L[r][r], w[r], the column it stands for
   double Lrow[L0_PMAX];
 #pragma unroll
@@ -746,7 +770,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
     }
   }
   if constexpr (PROFILE) {  // every lane its size: 64 values and 64 supports per wave
-    const int wv = blockIdx.x * L0_WAVES + (tid >> 6);
+    int wv = blockIdx.x * L0_WAVES + (tid >> 6);
+    if constexpr (BATCH) wv = (int)(blockIdx.x % (unsigned)a.batch_blocks) * L0_WAVES + (tid >> 6);  // (its number within the problem)
     a.best_val[(size_t)wv * 64 + lane] = best_v;
     if constexpr (WIDE) {
       a.best_mask[((size_t)wv * 64 + lane) * 2] = best_mask.lo;

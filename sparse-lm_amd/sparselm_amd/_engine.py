@@ -93,6 +93,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_profile",
     "slm_solve_l0_wide",
     "slm_solve_l0_profile_wide",
+    "slm_solve_l0_profile_batch",
     "slm_solve_l0_constrained",
     "slm_solve_l0_xb",
     "slm_solve_l0_xb_wide",
@@ -358,6 +359,7 @@ def load_library():
             "slm_solve_l0_profile": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_profile_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
+            "slm_solve_l0_profile_batch": [vp, i32, vp, vp, i32, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_xb": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_xb_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_constrained": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, i32, vp, vp, vp, vp, i32, vp, P(C.c_uint64), P(dbl), P(i64),
@@ -1297,7 +1299,7 @@ class Dataset:
         )
         return beta, lam, info[0]
 
-    # ---- the exact l0 search: what its eight entries share ------------------------------------------------------------------
+    # ---- the exact l0 search: what its nine entries share -------------------------------------------------------------------
     def _need_narrow(self, need):
         """``need`` (one integer mask per group) as the narrow entries take it: one 64-bit word per group."""
         if need is None:
@@ -1330,25 +1332,28 @@ class Dataset:
             raise EngineError("the compiled binding is not available")
         return b
 
-    def _l0_call(self, name, binding, args, outs, c_order=None):
+    def _l0_call(self, name, binding, args, outs, c_order=None, records=None, binding_args=None):
         """One call of ``slm_<name>`` by the route ``binding`` names.  ``args``: the entry's arguments between the dataset and
         its outputs, arrays as arrays.  ``outs``: the outputs the ctypes route fills -- arrays, ctypes cells, None -- in the
         order of the binding's tuple (``c_order``: their positions in the C signature, where that order differs).  Returns
         ``(outputs, record, rc)``; ``rc`` is ``SLM_OK`` or ``SLM_ERR_NOT_CONVERGED`` (the result is not proven: the outputs
-        hold the incumbent), anything else raises."""
+        hold the incumbent), anything else raises.  ``records``: an entry that fills that many records gets them all back
+        as an array (None: the one record).  ``binding_args``: the binding's arguments where they differ from ``args`` (an
+        entry that takes a list of arrays there and a table of pointers here)."""
         _sync_knobs()
         b = self._l0_route(binding)
         if b is not None:
-            *res, rec, rc = getattr(b, name)(self._h.value, self.p, *args)
-            return res, np.frombuffer(rec, dtype=_INFO_DTYPE)[0], rc
-        infos = np.zeros(1, dtype=_INFO_DTYPE)
+            *res, rec, rc = getattr(b, name)(self._h.value, self.p, *(args if binding_args is None else binding_args))
+            recs = np.frombuffer(rec, dtype=_INFO_DTYPE)
+            return res, recs[0] if records is None else recs, rc
+        infos = np.zeros(1 if records is None else max(1, records), dtype=_INFO_DTYPE)
         c_outs = [_ptr(o) if o is None or isinstance(o, np.ndarray) else C.byref(o) for o in outs]
         rc = getattr(self._lib, "slm_" + name)(
             self._h, *[_ptr(a) if a is None or isinstance(a, np.ndarray) else a for a in args],
             *[c_outs[i] for i in c_order or range(len(outs))], _as(infos, _PointInfo))
         if rc != SLM_ERR_NOT_CONVERGED:
             _check(rc)
-        return [o if o is None or isinstance(o, np.ndarray) else o.value for o in outs], infos[0], rc
+        return [o if o is None or isinstance(o, np.ndarray) else o.value for o in outs], infos[0] if records is None else infos, rc
 
     @staticmethod
     def _l0_info(info, rc, lower, nodes, *modes):
@@ -1496,6 +1501,48 @@ class Dataset:
         info)``; an entry nobody filled holds ``+inf``, an all-ones mask and zeros.  ``info``: ``nodes``, ``launches``,
         ``q_all``, ``status``, ``proven_optimal``, ``box_tol``."""
         return self._l0_profile(False, alpha_min, max_groups, eta, T, big_M, need, max_nodes, binding)
+
+    def solve_l0_profile_batch(self, row_weights, n_effs, intercept=False, alpha_min=0.0, max_groups=None, eta=0.0, T=None,
+                               big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_profile_batch``: the tables of ``solve_l0_profile`` for several row sets of this dataset -- the
+        training sets of a cross-validation and all rows -- from ONE launch.  ``row_weights``: up to 16 arrays of ``n``
+        weights, or None for the dataset's own rows; ``n_effs``: the divisor of each set's Gram (<= 0: the row count).
+        ``intercept``: the dataset's last column is a column of ones, alone in the last group; it is not searched but
+        eliminated from every set's Gram (weighted centring by the set's own means), so ``T`` is ``ps x ps`` and ``need``
+        has one mask per search group, ``ps = p - 1`` columns in ``n_groups - 1`` groups.  ``max_nodes`` is each problem's
+        budget.  Returns ``(betas [count, K + 1, ps], intercepts [count, K + 1], support masks [count, K + 1], values
+        [count, K + 1], infos)``; ``infos`` is one dict per problem as ``solve_l0_profile`` gives it."""
+        drop = 1 if intercept else 0
+        ps, gs = self.p - drop, self.n_groups - drop
+        K = gs if max_groups is None else int(max_groups)
+        if K < 0:
+            raise ValueError("max_groups must be >= 0")
+        rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
+        nes = [int(v) for v in n_effs]
+        if len(nes) != len(rws):
+            raise ValueError("row_weights and n_effs differ in length")
+        count = len(rws)
+        T_ = None if T is None else _f64(T, "T", (ps, ps))
+        need_ = None
+        if need is not None:
+            need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
+            if need_.shape != (gs,):
+                raise ValueError(f"need must have {gs} entries")
+        tail = (bool(intercept), float(alpha_min), K, float(eta), T_, float(big_M), need_, int(max_nodes))
+        ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
+        ne = np.array(nes or [0], dtype=np.int64)
+        cnt = max(1, count)
+        (betas, icpts, supports, values, nodes), infos, rc = self._l0_call(
+            "solve_l0_profile_batch", binding, (count, ptrs, ne, int(tail[0])) + tail[1:],
+            [np.empty((cnt, K + 1, ps)), np.empty((cnt, K + 1)), np.empty((cnt, K + 1), dtype=np.uint64), np.empty((cnt, K + 1)),
+             np.zeros(cnt, dtype=np.int64)],
+            records=count, binding_args=(self.n, rws, nes) + tail)
+        out = [{
+            "nodes": int(nodes[b]), "launches": int(infos[b]["n_iter"]), "q_all": float(infos[b]["L"]),
+            "status": "optimal" if int(infos[b]["status"]) == SLM_OK else "node_budget",
+            "proven_optimal": int(infos[b]["status"]) == SLM_OK, "box_tol": 1e-12,
+        } for b in range(count)]
+        return betas, icpts, supports, values, out
 
 
 class _HostPool:

@@ -89,24 +89,34 @@ class L0Profile:
     def _row(self, k):
         return self.coefs_[k].copy(), float(self.intercepts_[k]), self.supports_[k].copy()
 
-    def best_subset(self, sparse_bound):
-        """``(coef, intercept, active_groups)`` of best subset selection with at most ``sparse_bound`` groups:
-        ``argmin_{k <= sparse_bound} values_[k]``, ties to the smaller k (``l0_profile_best_subset``, csrc/l0_host.hpp)."""
+    def best_subset_size(self, sparse_bound):
+        """The row ``best_subset(sparse_bound)`` reads: ``argmin_{k <= sparse_bound} values_[k]``, ties to the smaller k
+        (``l0_profile_best_subset``, csrc/l0_host.hpp)."""
         if self.alpha_min_ > 0.0:
             raise ValueError(f"this table was pruned for regularised use (alpha_min = {self.alpha_min_:g}): its entries need not be the "
                              "best of their size; build it with alpha_min = 0 for best_subset")
         bound = int(np.floor(sparse_bound))
         if bound < 0 or bound > self.max_groups_:
             raise ValueError(f"sparse_bound = {sparse_bound} is outside the table's 0 .. max_groups = {self.max_groups_}")
-        return self._row(int(np.argmin(self.values_[: bound + 1])))  # (argmin: the first of equal minima)
+        return int(np.argmin(self.values_[: bound + 1]))  # (argmin: the first of equal minima)
 
-    def regularized(self, alpha):
-        """``(coef, intercept, active_groups)`` of ``RegularizedL0`` / ``L2L0`` at ``alpha >= alpha_min_``:
-        ``argmin_k values_[k] + alpha k``, ties to the smaller k (``l0_profile_regularized``, csrc/l0_host.hpp)."""
+    def regularized_size(self, alpha):
+        """The row ``regularized(alpha)`` reads: ``argmin_k values_[k] + alpha k``, ties to the smaller k
+        (``l0_profile_regularized``, csrc/l0_host.hpp)."""
         alpha = float(alpha)
         if not np.isfinite(alpha) or alpha < self.alpha_min_:
             raise ValueError(f"alpha = {alpha:g} is below the table's alpha_min = {self.alpha_min_:g} (or not finite)")
-        return self._row(int(np.argmin(self.values_ + alpha * np.arange(len(self.values_)))))
+        return int(np.argmin(self.values_ + alpha * np.arange(len(self.values_))))
+
+    def best_subset(self, sparse_bound):
+        """``(coef, intercept, active_groups)`` of best subset selection with at most ``sparse_bound`` groups (the row
+        ``best_subset_size`` names)."""
+        return self._row(self.best_subset_size(sparse_bound))
+
+    def regularized(self, alpha):
+        """``(coef, intercept, active_groups)`` of ``RegularizedL0`` / ``L2L0`` at ``alpha >= alpha_min_`` (the row
+        ``regularized_size`` names)."""
+        return self._row(self.regularized_size(alpha))
 
     def alpha_breakpoints(self):
         """The exact regularisation path: ``(alphas, sizes)`` with ``alphas`` decreasing and ``len(sizes) == len(alphas) + 1``.
