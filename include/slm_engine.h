@@ -698,6 +698,41 @@ int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_gro
                               int64_t* nodes_out, slm_point_info* info);
 
 /*
+ * (added under ABI 24: two new symbols beside slm_solve_l0_l1 and slm_solve_l0_profile, no existing entry, structure or constant
+ * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The L1 PROFILE: the reference's L1L0 at
+ * EVERY alpha from one search (csrc/l0_kernels.hpp, template parameters L1 and PROFILE together).  For one fixed eta_l1 the
+ * value of a support,
+ *       f(S) = min over beta, supp beta in cols(S), |beta_j| <= big_M, of  1/2 beta^T G beta - c^T beta + eta_l1 ||beta||_1,
+ * depends on neither alpha nor the size, so with F_k = value_out[k] = min over admissible S of exactly k groups of f(S) the
+ * table answers slm_solve_l0_l1(alpha, eta_l1) for every alpha >= alpha_min (min over k of F_k + alpha k) and, at
+ * alpha_min = 0, the cardinality-bounded lasso for every bound K' <= max_groups.  There is no ridge term and no T, as in
+ * slm_solve_l0_l1.  The search is the profile's: q(S) <= f(S) filters the candidates of each size, a candidate is valued by
+ * the descent of slm_solve_l0_l1 over all columns of its support, and the subtree cut of slm_solve_l0_profile runs with the
+ * proven lower bound on f(all columns) of slm_solve_l0_l1 in place of q_all (f is monotone in the support).  The lasso sets
+ * coefficients to zero by itself, so the table saturates: from the size that holds every column the lasso on all columns
+ * uses, larger sizes tie with it in value and the smaller mask is returned.  Outputs as slm_solve_l0_profile's (row k
+ * recomputed on the host by the same descent and polished, as slm_solve_l0_l1 recomputes its winner); info as
+ * slm_solve_l0_profile's with info->L = the l1 lower bound used and info->rejects = descents run.  eta_l1 == 0 runs the very
+ * code of slm_solve_l0_profile(ds, alpha_min, max_groups, 0, NULL, ...).  Argument errors are those of slm_solve_l0_l1 and
+ * slm_solve_l0_profile (SLM_ERR_BAD_ARG before anything is launched; SLM_ERR_UNSUPPORTED beyond the limits and on row-sharded
+ * datasets; SLM_ERR_NOT_CONVERGED with the table of incumbents when the node budget ran out).
+ * slm_solve_l0_l1_profile: up to 64 columns and 64 groups.  slm_solve_l0_l1_profile_wide: up to 128 columns and 128 groups,
+ * masks of two words as in slm_solve_l0_profile_wide, and its two refusals: max_groups <= 64, and the max_groups largest
+ * groups together hold at most 64 columns (the messages name 64) -- a support's columns, dependent ones included, then fit
+ * the 64 lanes that hold them.  A problem within the narrow limits gives the same bytes on either.  Not here: a ridge term,
+ * linear constraints, the exclusion bound, batches over row sets.
+ */
+int slm_solve_l0_l1_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
+                            const uint64_t* need /* n_groups masks or NULL */, int64_t max_nodes /* <=0: default */,
+                            double* beta_out /* [(max_groups+1)*p] */, uint64_t* support_out /* [max_groups+1] */,
+                            double* value_out /* [max_groups+1] */, int64_t* nodes_out, slm_point_info* info);
+int slm_solve_l0_l1_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
+                                 const uint64_t* need /* 2 words per group, low word first, or NULL */,
+                                 int64_t max_nodes /* <=0: default */, double* beta_out /* [(max_groups+1)*p] */,
+                                 uint64_t* support_out /* [(max_groups+1)*2] */, double* value_out /* [max_groups+1] */,
+                                 int64_t* nodes_out, slm_point_info* info);
+
+/*
  * (added under ABI 24: a new symbol beside slm_solve_l0_profile, no existing entry, structure or constant changes, so the
  * version stays 24 -- a caller that needs it looks the symbol up.)  The BATCHED l0 profile: the tables of slm_solve_l0_profile
  * for `count` row sets of one dataset -- the training sets of a cross-validation and all rows, say -- from ONE launch

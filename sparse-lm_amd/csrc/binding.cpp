@@ -435,6 +435,20 @@ py::tuple solve_l0_profile_wide(uintptr_t ds, int64_t p, double alpha_min, int32
   return l0_profile(true, [](auto... a) { return slm_solve_l0_profile_wide(a...); }, ds, p, alpha_min, max_groups, eta, T, big_M, need,
                     max_nodes);
 }
+// The two l1 profile entries (L1L0 at every alpha from one search): no ridge term and no T, so the helper's eta carries eta_l1 and
+// its T stays None.  The tuple of solve_l0_profile / solve_l0_profile_wide.
+py::tuple solve_l0_l1_profile(uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
+                              const py::object& need, int64_t max_nodes) {
+  return l0_profile(false, [](slm_dataset* d, double am, int32_t K, double e1, const double*, auto... a) {
+    return slm_solve_l0_l1_profile(d, am, K, e1, a...);
+  }, ds, p, alpha_min, max_groups, eta_l1, py::none(), big_M, need, max_nodes);
+}
+py::tuple solve_l0_l1_profile_wide(uintptr_t ds, int64_t p, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
+                                   const py::object& need, int64_t max_nodes) {
+  return l0_profile(true, [](slm_dataset* d, double am, int32_t K, double e1, const double*, auto... a) {
+    return slm_solve_l0_l1_profile_wide(d, am, K, e1, a...);
+  }, ds, p, alpha_min, max_groups, eta_l1, py::none(), big_M, need, max_nodes);
+}
 
 // slm_solve_l0_profile_batch: the profiles of several row sets of one dataset from one launch.  row_weights: a sequence of
 // arrays of n weights or None; n_effs: as many integers.  Returns (coefficients [count][max_groups + 1][ps], intercepts
@@ -499,6 +513,8 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_xb_wide", &solve_l0_wide<true>);
   m.def("solve_l0_profile_wide", &solve_l0_profile_wide);
   m.def("solve_l0_profile_batch", &solve_l0_profile_batch);
+  m.def("solve_l0_l1_profile", &solve_l0_l1_profile);
+  m.def("solve_l0_l1_profile_wide", &solve_l0_l1_profile_wide);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

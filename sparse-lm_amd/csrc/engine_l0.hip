@@ -1,6 +1,6 @@
 // Host side of the MI355X fit engine, sixth unit: the exact l0 estimators (csrc/l0_kernels.hpp) -- the reference's
 // mixed-integer family (reference src/sparselm/model/_miqp/_best_subset.py, _regularized_l0.py), which it hands to
-// Gurobi or SCIP through cvxpy.  Nine entries, four functions (solve_l0_impl, solve_l0_profile_impl, solve_l0_con_impl,
+// Gurobi or SCIP through cvxpy.  Eleven entries, four functions (solve_l0_impl, solve_l0_profile_impl, solve_l0_con_impl,
 // solve_l0_profile_batch_impl), ONE
 // pipeline, everything around the launch on the host (p <= 128: microseconds):
 //   check    l0_check_args, and what a mode adds: whatever can be refused is refused before a device is touched
@@ -18,6 +18,8 @@
 //       l0_host.hpp value the seed and the winner; the subtree bound uses the lasso dual value on all columns.
 //   slm_solve_l0_profile  the PROFILE instantiation: the best support of every size up to max_groups.  A seed and a winner per
 //       size, 64 results per wave, the incumbents per size behind the control words.
+//   slm_solve_l0_l1_profile, slm_solve_l0_l1_profile_wide  the L1 + PROFILE instantiations: L1L0 at every alpha from one search, narrow and
+//       wide.  The profile's pipeline with l0_l1_support_of for the seed and the winners and l0_l1_lower_bound for the cut.
 //   slm_solve_l0_wide, slm_solve_l0_profile_wide  the WIDE instantiations: up to 128 columns and groups, masks of two words, a
 //       support of at most 64 independent columns (the capacity rule of l0_host.hpp).  One template over WIDE serves both widths.
 //   slm_solve_l0_constrained  the CON instantiation: rows lo <= A beta <= hi and a per-column box.  The l0_con_* functions of
@@ -375,16 +377,21 @@ struct L0ProfileWork {
   std::vector<Mask> win_mask;
 };
 // the seed of every size: the supports the greedy selection passes through, valued as the kernel values a node
+// (eta_l1 > 0, here and in l0_profile_collect: the l1 profile -- a support's value is its lasso, l0_l1_support_of)
 template <class Mask>
-void l0_profile_seed(L0ProfileWork<Mask>& W, int p, int K, double big_M) {
+void l0_profile_seed(L0ProfileWork<Mask>& W, int p, int K, double big_M, double eta_l1 = 0.0) {
   const L0ProblemT<Mask>& P = W.P;
   const double *H = P.H.data(), *c = P.c.data();
   std::vector<double> beta_s((size_t)p);
+  auto value_of = [&](Mask mask) {
+    return eta_l1 > 0.0 ? l0_l1_support_of(H, c, p, P.gstart, mask, eta_l1, big_M, false, beta_s.data())
+                        : l0_support_of(H, c, p, P.gstart, mask, big_M, false, beta_s.data());
+  };
   W.win_val.assign((size_t)L0_PMAX + 1, HUGE_VAL);
   W.win_mask.assign((size_t)L0_PMAX + 1, l0m_ones<Mask>());
   W.win_val[0] = 0.0;  // the empty support
   W.win_mask[0] = l0m_none<Mask>();
-  l0_greedy(H, c, p, P.gstart, P.needo, K, [&](Mask mask) { return l0_support_of(H, c, p, P.gstart, mask, big_M, false, beta_s.data()); },
+  l0_greedy(H, c, p, P.gstart, P.needo, K, value_of,
             [&](int size, Mask mask, double quad) {
               if (l0_better(quad, mask, W.win_val[(size_t)size], W.win_mask[(size_t)size])) {
                 W.win_val[(size_t)size] = quad;
@@ -402,7 +409,7 @@ void l0_profile_seed_image(const L0ProfileWork<Mask>& W, unsigned long long* h) 
 template <class Mask>
 void l0_profile_collect(L0ProfileWork<Mask>& W, const unsigned long long* h, const L0Layout& y, int p, int rows, int K, double alpha_min,
                         double big_M, bool finished, double* beta_out, uint64_t* support_out, double* value_out, int64_t* nodes_out,
-                        slm_point_info* info) {
+                        slm_point_info* info, double eta_l1 = 0.0) {
   const L0ProblemT<Mask>& P = W.P;
   const double *H = P.H.data(), *c = P.c.data();
   std::vector<double> beta_s((size_t)p);
@@ -414,7 +421,8 @@ void l0_profile_collect(L0ProfileWork<Mask>& W, const unsigned long long* h, con
     value_out[size] = HUGE_VAL;
     Mask support = l0m_ones<Mask>();
     if (filled) {
-      value_out[size] = l0_support_of(H, c, p, P.gstart, W.win_mask[(size_t)size], big_M, true, beta_s.data());
+      value_out[size] = eta_l1 > 0.0 ? l0_l1_support_of(H, c, p, P.gstart, W.win_mask[(size_t)size], eta_l1, big_M, true, beta_s.data())
+                                     : l0_support_of(H, c, p, P.gstart, W.win_mask[(size_t)size], big_M, true, beta_s.data());
       support = l0_caller_mask(W.win_mask[(size_t)size], P.gorder);
       l0_scatter(beta_s.data(), P.cols, beta);
     }
@@ -430,14 +438,18 @@ void l0_profile_collect(L0ProfileWork<Mask>& W, const unsigned long long* h, con
 // slm_solve_l0_profile, _profile_wide: a seed and a winner per size.  Wide: lane k - 1 still holds size k, and no include may be
 // refused for capacity, so a call whose max_groups largest groups could hold more than L0_PMAX columns is refused before anything
 // is launched.
+// slm_solve_l0_l1_profile, _l1_profile_wide (eta_l1 > 0): the kernel's L1 + PROFILE instantiations.  Seed and winners are valued by
+// l0_l1_support_of, the subtree cut takes l0_l1_lower_bound on all columns for q_all, info->L is that bound and info->rejects the
+// descents run.  The wide refusals above also keep every support's column list within the 64 lanes.  eta_l1 == 0 is the profile itself.
 template <bool WIDE>
-int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
+int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double eta_l1, double big_M,
                           const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
                           int64_t* nodes_out, slm_point_info* info) {
   using Mask = std::conditional_t<WIDE, L0Mask128, unsigned long long>;
   int p = 0, ng = 0;
   if (!support_out || !value_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  SLM_TRY(l0_check_args<Mask>(ds, beta_out, alpha_min, "alpha_min", eta, 0.0, big_M, T, need, &p, &ng));
+  SLM_TRY(l0_check_args<Mask>(ds, beta_out, alpha_min, "alpha_min", eta, eta_l1, big_M, T, need, &p, &ng));
+  const bool l1 = eta_l1 > 0.0;
   const int rows = max_groups < 0 ? 0 : (int)max_groups;  // the outputs have rows + 1 entries; sizes above the group count stay unfilled
   const int K = std::min(rows, ng);
   if constexpr (WIDE) {
@@ -454,18 +466,25 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
   }
   L0ProfileWork<Mask> W;
   SLM_TRY(l0_prepare(ds, p, ng, eta, T, need, W.P));
-  l0_profile_seed(W, p, K, big_M);
+  l0_profile_seed(W, p, K, big_M, eta_l1);
+  // the subtree cut's lower bound on the value of all columns: with an l1 term the lasso dual value where it is above q_all
+  const double bound = l1 ? l0_l1_lower_bound(W.P.H.data(), W.P.c.data(), p, W.P.yy, eta_l1, W.P.q_all) : W.P.q_all;
 
   // ---- the search: one launch, 64 results per wave, the incumbents of the sizes 1 .. 64 behind the control words ----------------
-  L0Plan plan = l0_plan(ds->eng, W.P, p, ng, K, 64, L0_PROFILE_WORDS, alpha_min, big_M, W.P.q_all, max_nodes);
+  L0Plan plan = l0_plan(ds->eng, W.P, p, ng, K, 64, L0_PROFILE_WORDS, alpha_min, big_M, bound, max_nodes);
   l0_profile_seed_image(W, plan.h.data());
   if constexpr (WIDE) plan.h[L0_CAPACITY] = ~0ull;
-  SLM_TRY(l0_run(ds->eng, plan, l0_search_kernel<false, true, WIDE>));
+  plan.k.eta_l1 = eta_l1;
+  SLM_TRY(l0_run(ds->eng, plan, l1 ? l0_search_kernel<true, true, WIDE> : l0_search_kernel<false, true, WIDE>));
   const std::vector<unsigned long long>& h = plan.h;
 
   const bool finished = h[L0_ABORTED] == 0;
   if (WIDE && h[L0_CAPACITY] != ~0ull) return fail(SLM_ERR_HIP, "the wide l0 profile refused an include for capacity (internal error)");
-  l0_profile_collect(W, h.data(), plan.y, p, rows, K, alpha_min, big_M, finished, beta_out, support_out, value_out, nodes_out, info);
+  l0_profile_collect(W, h.data(), plan.y, p, rows, K, alpha_min, big_M, finished, beta_out, support_out, value_out, nodes_out, info, eta_l1);
+  if (info && l1) {
+    info->L = bound;
+    info->rejects = l0_count32(h[L0_DESCENTS]);
+  }
   if (!finished) return l0_budget_ran_out(plan, "table of incumbents");
   return SLM_OK;
 }
@@ -820,14 +839,31 @@ extern "C" int slm_solve_l0_l1(slm_dataset* ds, double alpha, double eta_l1, dou
 extern "C" int slm_solve_l0_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
                                     const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
                                     int64_t* nodes_out, slm_point_info* info) {
-  return solve_l0_profile_impl<false>(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
+  return solve_l0_profile_impl<false>(ds, alpha_min, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
 }
 
 // The profile on the kernel's wide instantiation: masks of two words in need and support_out, max_groups up to 64.
 extern "C" int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
                                          const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
                                          double* value_out, int64_t* nodes_out, slm_point_info* info) {
-  return solve_l0_profile_impl<true>(ds, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
+  return solve_l0_profile_impl<true>(ds, alpha_min, max_groups, eta, T, 0.0, big_M, need, max_nodes, beta_out, support_out, value_out, nodes_out, info);
+}
+
+// The l1 profile (the reference's L1L0 at every alpha from one search): the table F_k = min over supports of exactly k groups of the
+// lasso value of the support; no ridge term, no T.  eta_l1 == 0 is slm_solve_l0_profile with eta = 0.
+extern "C" int slm_solve_l0_l1_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
+                                       const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out, double* value_out,
+                                       int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_profile_impl<false>(ds, alpha_min, max_groups, 0.0, nullptr, eta_l1, big_M, need, max_nodes, beta_out, support_out, value_out,
+                                      nodes_out, info);
+}
+
+// The l1 profile on the kernel's wide instantiation: masks of two words, max_groups up to 64, every support within 64 columns.
+extern "C" int slm_solve_l0_l1_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
+                                            const uint64_t* need, int64_t max_nodes, double* beta_out, uint64_t* support_out,
+                                            double* value_out, int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_profile_impl<true>(ds, alpha_min, max_groups, 0.0, nullptr, eta_l1, big_M, need, max_nodes, beta_out, support_out, value_out,
+                                     nodes_out, info);
 }
 
 // The same search under linear constraints lo <= A beta <= hi and a per-column box (the kernel's constrained instantiation).

@@ -2,8 +2,10 @@
 // the factor of H on a growing list of columns as the kernel keeps it, the boxed descent candidates are compared by, and the
 // value and coefficients of one support, the same for l1 mode (a lasso per support: the descent, its polish, the dual
 // bound on all columns), and for profile mode the pruning rule and the two questions its table answers.  Like host_logic.hpp and tail_logic.hpp it is free of HIP types so that g++
-// compiles it alone: tests/host_logic_test.cpp, tests/l1l0_host_test.cpp and tests/l0_profile_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 / slm_solve_l0_profile call
-// THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.  The wide mode
+// compiles it alone: tests/host_logic_test.cpp, tests/l1l0_host_test.cpp, tests/l0_profile_host_test.cpp and tests/l1l0_profile_host_test.cpp run these functions on the CPU under the sanitizers, and slm_solve_l0 / slm_solve_l0_l1 / slm_solve_l0_profile call
+// THESE functions for the seed, the bound q_all and the winner's coefficients -- what is tested is what runs.  The l1 profile
+// (slm_solve_l0_l1_profile, slm_solve_l0_l1_profile_wide) values the seed and the winner of every size by l0_l1_support_of, the
+// lasso of a support for a mask of either width, and cuts with l0_l1_lower_bound on up to 128 columns.  The wide mode
 // (slm_solve_l0_wide, slm_solve_l0_profile_wide; tests/l0_wide_host_test.cpp) adds masks of two words, a factor with a capacity
 // parameter and the capacity rule.  The constrained mode (slm_solve_l0_constrained; tests/l0_con_host_test.cpp) adds the splitting
 // that values a support under linear constraints, the dual value host and device share, its face polish, the positive-definite
@@ -542,6 +544,42 @@ inline double l0_l1_support(const double* H, const double* c, int p, const std::
   return val;
 }
 
+// The same for a mask of either width (slm_solve_l0_l1_profile, _profile_wide): the support's at most L0_PMAX columns are drawn
+// from up to L0_WIDE_PMAX.  A column that arrives when the list holds L0_PMAX is left out and sets *overflow (the entries refuse
+// such a call before anything runs; at p <= L0_PMAX it cannot happen, and the result is the narrow function's bit for bit).
+template <class Mask>
+inline double l0_l1_support_of(const double* H, const double* c, int p, const std::vector<int>& gstart, Mask mask, double eta, double big_M,
+                               bool polish, double* beta, bool* overflow = nullptr) {
+  L0Factor f(H, c, p);
+  const int ng = (int)gstart.size() - 1;
+  int cols[L0_PMAX];
+  int na = 0;
+  bool over = false;
+  for (int g = 0; g < ng; ++g)
+    if (l0m_test(mask, g))
+      for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1]; ++j) {
+        if (na == L0_PMAX) {
+          over = true;
+          continue;
+        }
+        (void)f.push(j);
+        cols[na++] = j;
+      }
+  if (overflow) *overflow = over;
+  for (int j = 0; j < p; ++j) beta[j] = 0.0;
+  double bs[L0_PMAX], b[L0_PMAX];
+  f.solve(bs);
+  for (int r = 0; r < na; ++r) {
+    b[r] = 0.0;
+    for (int k = 0; k < f.m; ++k)
+      if (f.col[k] == cols[r]) b[r] = bs[k];
+  }
+  double val = l0_l1_descent(H, c, p, cols, na, eta, big_M, b);
+  if (polish) val = l0_l1_polish(H, c, p, cols, na, eta, big_M, b);
+  for (int r = 0; r < na; ++r) beta[cols[r]] = b[r];
+  return val;
+}
+
 // A proven lower bound on f(all columns) = min_b 1/2 b^T G b - c^T b + eta ||b||_1 (the box can only raise it): the larger of
 // q_all and the lasso dual value at a feasible point.  With the primal 1/(2n)||y - X b||^2 + eta ||b||_1 = f + yy / 2
 // (yy = y^T W y / n), the dual is  max D(nu) = yy/2 - n/2 ||nu - y/n||^2  over ||X^T nu||_inf <= eta.  For any b,
@@ -549,11 +587,12 @@ inline double l0_l1_support(const double* H, const double* c, int p, const std::
 //     D(nu) - yy/2 = -1/2 s^2 rr + s ry - 1/2 yy,    rr = yy - 2 c^T b + b^T G b,  ry = yy - c^T b
 // (at eta -> 0, s = 1 and b the least-squares solution this is -1/2 c^T b = q_all).  b comes from the descent on all
 // columns without the box; only its quality, never its validity, depends on how far that descent got.  The value is
-// lowered by a margin that covers the rounding of the sums and of a Gram that is itself a rounded product.
+// lowered by a margin that covers the rounding of the sums and of a Gram that is itself a rounded product.  Up to
+// L0_WIDE_PMAX columns (the wide l1 profile).
 inline double l0_l1_lower_bound(const double* G, const double* c, int p, double yy, double eta, double q_all) {
-  if (p <= 0 || p > L0_PMAX || !(eta > 0.0)) return q_all;
-  int cols[L0_PMAX];
-  double b[L0_PMAX];
+  if (p <= 0 || p > L0_WIDE_PMAX || !(eta > 0.0)) return q_all;
+  int cols[L0_WIDE_PMAX];
+  double b[L0_WIDE_PMAX];
   for (int j = 0; j < p; ++j) {
     cols[j] = j;
     b[j] = 0.0;

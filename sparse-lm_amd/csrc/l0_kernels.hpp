@@ -38,7 +38,7 @@
 // value, and the cut of a group that brought no independent column is off.  The subtree bound takes a proven lower bound
 // on f(all columns) from the host in q_all (the lasso dual value at a feasible point, or q_all itself).
 //
-// profile mode (template parameter PROFILE, slm_solve_l0_profile; never together with L1): ONE search returns, for every
+// profile mode (template parameter PROFILE, slm_solve_l0_profile; with L1: see "l1 profile" below): ONE search returns, for every
 // size k = 1 .. K, the best admissible support of exactly k groups -- the table Q_k that answers best subset for every bound
 // K' <= K (min_{k <= K'} Q_k) and RegularizedL0 / L2L0 for every alpha (min_k Q_k + alpha k).  Lane k - 1 of a wave keeps the
 // wave's best (value, support) of size k and the shared incumbent of that size, read from an array of 64 keys behind the
@@ -51,7 +51,7 @@
 // -- S' is never strictly better than a support already held.  With alpha_min = 0 the cut fires only where a held support
 // has reached q_all, and the table is the full one.
 //
-// wide mode (template parameter WIDE, slm_solve_l0_wide / slm_solve_l0_profile_wide; never together with L1): up to
+// wide mode (template parameter WIDE, slm_solve_l0_wide / slm_solve_l0_profile_wide; with L1 only as the l1 profile below): up to
 // L0_WIDE_PMAX = 128 columns and groups.  The factor is indexed by inclusion position, not by column, so it keeps its 64 rows
 // and a support draws its at most 64 INDEPENDENT columns from any of the 128.  What differs, all under if constexpr (WIDE) or
 // behind the mask type: H sits in LDS as a packed lower triangle (row i at i (i + 1) / 2: 66 048 B at 128 columns, so two
@@ -61,6 +61,22 @@
 // any refused include and the exclude branch is taken.  The wave keeps the smallest cnt at which it refused one and lowers
 // the control word L0_CAPACITY with cnt + 1 on exit: every support below such a refusal has at least cnt + 1 groups and
 // q >= q_all, so nothing unsearched is below q_all + alpha (c_min + 1) -- the host proves optimality against that.
+//
+// l1 profile (template parameters L1 and PROFILE together, slm_solve_l0_l1_profile; with WIDE slm_solve_l0_l1_profile_wide): for one
+// fixed eta_l1 the value f(S) of a support depends on neither alpha nor the size, so the table F_k = min_{|S| = k} f(S) answers L1L0 at
+// EVERY alpha (min_k F_k + alpha k).  The two modes compose as they stand.  A node of cnt groups is a candidate for row cnt alone: the
+// filter compares q(S) = -1/2 ||w||^2 <= f(S) with that size's incumbent and the wave's best of that size, the descent's value goes
+// into the table without an alpha term, and the subtree cut is the profile's with bound_all, the host's proven lower bound on
+// f(all columns), in q_all:  bound_all + alpha_min (cnt + 1) >= E(cnt).  The argument of profile mode carries over word for word
+// with f for q: f is monotone in the support, so every S' below the node has f(S') >= f(all) >= bound_all and k' >= cnt + 1 groups.
+// The lasso zeroes coefficients by itself, so the table saturates: from the size that holds every column the lasso on all
+// columns uses, larger sizes tie in value and the tie rule (the smaller mask) picks their supports.  WIDE: the descent reads H
+// through Hat (the packed triangle), st_na gets its second slot beside st_m1 / st_ss1, and lane r still stands for the r-th
+// column of the support -- the host refuses a call whose max_groups largest groups hold more than 64 columns, so a support's
+// column list (dependent columns included) fits the lanes; an include that would take it past 64 is refused all the same and
+// lowers L0_CAPACITY, which the host reports as an internal error.  There is no plain wide l1 search: it would need a dynamic
+// capacity rule on the column list.  230 (narrow) / 250 (wide) VGPRs, no AGPRs, no scratch, 34 056 / 69 640 B of LDS, 2 waves/SIMD;
+// measured in profiles/l1l0_profile.txt.
 //
 // constrained mode (template parameter CON, slm_solve_l0_constrained; alone): rows lo <= A beta <= hi and a per-column box
 // blo_j <= beta_j <= bhi_j join the problem, so f(S) is a quadratic programme, +inf on an infeasible support.  f is monotone in
@@ -193,6 +209,10 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
     }                                                 \
   }
 
+// H[i][j] as the l1 descent reads it: the narrow instantiations keep the expression they had (and with it their code), the wide
+// one goes through Hat's packed triangle.  (WIDE is a template parameter: the branch not taken is not compiled into the kernel.)
+#define L0_HL1(i, j) (WIDE ? Hat((i), (j)) : Hs[(i) * p + (j)])
+
 // L1 = false: the search above.  L1 = true: eta_l1 ||beta||_1 joins the objective (see the head of the file).
 // PROFILE = true: the best support of every size (see the head of the file); everything it adds sits under if constexpr.
 // WIDE = true: up to 128 columns and groups (see the head of the file); what it adds sits under if constexpr or behind Mask.
@@ -207,8 +227,7 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
 // problem: that would re-stage H behind a barrier).  Everything it adds sits under if constexpr.
 template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false, bool XB = false, bool BATCH = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
-  static_assert(!(L1 && PROFILE), "the profile mode has no l1 term");
-  static_assert(!(L1 && WIDE), "there is no wide l1 mode");
+  static_assert(!(L1 && WIDE) || PROFILE, "a wide l1 search exists only as a profile (a plain one needs a dynamic capacity rule on the support's column list)");
   static_assert(!(CON && (L1 || PROFILE || WIDE)), "the constrained mode stands alone");
   static_assert(!(XB && (L1 || PROFILE || CON)), "the exclusion bound serves the plain search, narrow and wide");
   static_assert(!(BATCH && (!PROFILE || L1 || WIDE || CON || XB)), "a batch holds narrow profile searches and nothing else");
@@ -322,6 +341,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   }
   // l1 mode: lane r also stands for the r-th column of the SUPPORT (dependent ones included), na of them
   int acol = 0, na = 0, st_na = 0;
+  [[maybe_unused]] int st_na1 = 0;  // (the second slot: wide only)
   long long descents_local = 0;
   [[maybe_unused]] long long unsettled_local = 0;
   // the state before group g was decided, held by lane g (wide: by lane g & 63, in slot g >> 6)
@@ -415,6 +435,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               st_m = m;
               st_ss = ss;
               st_need = needm;
+              if constexpr (L1) st_na = na;
               if constexpr (XB) {
                 st_mx = mx;
                 st_ssx = ssx;
@@ -424,6 +445,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
             st_m1 = m;
             st_ss1 = ss;
             st_need1 = needm;
+            if constexpr (L1) st_na1 = na;
             if constexpr (XB) {
               st_mx1 = mx;
               st_ssx1 = ssx;
@@ -457,11 +479,21 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
             }
           }
           const int c0 = __builtin_amdgcn_readfirstlane(gs[g]), c1 = __builtin_amdgcn_readfirstlane(gs[g + 1]);
+          if constexpr (L1 && WIDE) {
+            // lane r stands for the support's r-th column: a group that would take the list past 64 is refused like an include
+            // the factor has no row for (the host refuses such a call before the launch: this only guards the lanes)
+            if (na + (c1 - c0) > L0_PMAX) {
+              ok = false;
+              cap_min = cnt < cap_min ? cnt : cap_min;
+            }
+          }
           if constexpr (L1) {  // the support's own column list grows by the whole group
             if (lane >= na && lane < na + (c1 - c0)) acol = c0 + (lane - na);
             na += c1 - c0;
           }
           for (int j = c0; j < c1; ++j) {
+            if constexpr (L1 && WIDE)
+              if (!ok) break;
             // append column j: x = L^-1 H[cols, j] by columns, x_k broadcast from lane k at step k
             const double hjj = Hat(j, j);
             double b = lane < m ? Hat(j, mycol) : 0.0;  // (H is symmetric: the lanes read one row)
@@ -535,17 +567,17 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               double gr = lane < na ? -cs[acol] : 0.0;
               for (int k = 0; k < na; ++k) {
                 const int ck = __builtin_amdgcn_readlane(acol, k);
-                gr = fma(lane < na ? Hs[ck * p + acol] : 0.0, l0_bcast(b1, k), gr);
+                gr = fma(lane < na ? L0_HL1(ck, acol) : 0.0, l0_bcast(b1, k), gr);
               }
               for (int sweep = 0; sweep < L0_CD_SWEEPS; ++sweep) {
                 double maxd = 0.0, maxb = 0.0;
                 for (int k = 0; k < na; ++k) {
                   const int ck = __builtin_amdgcn_readlane(acol, k);
                   const double bk = l0_bcast(b1, k), gk = l0_bcast(gr, k);
-                  const double nb = l0_l1_step(bk, gk, Hs[ck * p + ck], eta1, big_M);
+                  const double nb = l0_l1_step(bk, gk, L0_HL1(ck, ck), eta1, big_M);
                   const double dk = nb - bk;
                   if (dk != 0.0) {
-                    gr = fma(lane < na ? Hs[ck * p + acol] : 0.0, dk, gr);
+                    gr = fma(lane < na ? L0_HL1(ck, acol) : 0.0, dk, gr);
                     if (lane == k) b1 = nb;
                   }
                   maxd = fmax(maxd, fabs(dk));
@@ -553,8 +585,11 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
                 }
                 if (maxd <= L0_CD_TOL * maxb || maxd == 0.0) break;
               }
-              val = 0.5 * l0_wave_sum(lane < na ? b1 * (gr - cs[acol]) : 0.0) + eta1 * l0_wave_sum(lane < na ? fabs(b1) : 0.0) +
-                    alpha * (double)cnt;
+              if constexpr (PROFILE)  // (the table holds f(S) itself: no alpha term)
+                val = 0.5 * l0_wave_sum(lane < na ? b1 * (gr - cs[acol]) : 0.0) + eta1 * l0_wave_sum(lane < na ? fabs(b1) : 0.0);
+              else
+                val = 0.5 * l0_wave_sum(lane < na ? b1 * (gr - cs[acol]) : 0.0) + eta1 * l0_wave_sum(lane < na ? fabs(b1) : 0.0) +
+                      alpha * (double)cnt;
             } else if constexpr (CON) {
               // the node's value is a quadratic programme: the splitting of l0_host.hpp (l0_con_solve, step for step) from the
               // back-substituted beta, clipped.  Lane r < m: beta_r and (H beta - c)_r; lane i < rows: (A beta)_i, s_i, u_i.
@@ -714,9 +749,11 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
           if (g < 64) {
             ss = l0_bcast(st_ss, g);
             needm = l0_bcast(st_need, g);
+            if constexpr (L1) na = __builtin_amdgcn_readlane(st_na, g);
           } else {
             ss = l0_bcast(st_ss1, g - 64);
             needm = l0_bcast(st_need1, g - 64);
+            if constexpr (L1) na = __builtin_amdgcn_readlane(st_na1, g - 64);
           }
         } else {
           ss = l0_bcast(st_ss, g);
@@ -802,5 +839,6 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
 }
 
 #undef L0_APPEND
+#undef L0_HL1
 
 }  // namespace slm

@@ -94,6 +94,8 @@ ABI_SYMBOLS = (
     "slm_solve_l0_wide",
     "slm_solve_l0_profile_wide",
     "slm_solve_l0_profile_batch",
+    "slm_solve_l0_l1_profile",
+    "slm_solve_l0_l1_profile_wide",
     "slm_solve_l0_constrained",
     "slm_solve_l0_xb",
     "slm_solve_l0_xb_wide",
@@ -359,6 +361,8 @@ def load_library():
             "slm_solve_l0_profile": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_profile_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
+            "slm_solve_l0_l1_profile": [vp, dbl, i32, dbl, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
+            "slm_solve_l0_l1_profile_wide": [vp, dbl, i32, dbl, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_profile_batch": [vp, i32, vp, vp, i32, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_xb": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_xb_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
@@ -1299,7 +1303,7 @@ class Dataset:
         )
         return beta, lam, info[0]
 
-    # ---- the exact l0 search: what its nine entries share -------------------------------------------------------------------
+    # ---- the exact l0 search: what its eleven entries share -------------------------------------------------------------------
     def _need_narrow(self, need):
         """``need`` (one integer mask per group) as the narrow entries take it: one 64-bit word per group."""
         if need is None:
@@ -1501,6 +1505,36 @@ class Dataset:
         info)``; an entry nobody filled holds ``+inf``, an all-ones mask and zeros.  ``info``: ``nodes``, ``launches``,
         ``q_all``, ``status``, ``proven_optimal``, ``box_tol``."""
         return self._l0_profile(False, alpha_min, max_groups, eta, T, big_M, need, max_nodes, binding)
+
+    def _l0_l1_profile(self, wide, alpha_min, max_groups, eta_l1, big_M, need, max_nodes, binding):
+        """Both l1 profile entries: ``(betas, support words, values, info)``."""
+        K = self.n_groups if max_groups is None else int(max_groups)
+        if K < 0:
+            raise ValueError("max_groups must be >= 0")
+        need_ = self._need_words(need) if wide else self._need_narrow(need)
+        args = (float(alpha_min), K, float(eta_l1), float(big_M), need_, int(max_nodes))
+        (betas, supports, values, nodes), info, rc = self._l0_call(
+            "solve_l0_l1_profile_wide" if wide else "solve_l0_l1_profile", binding, args,
+            [np.empty((K + 1, self.p)), np.empty((K + 1, 2) if wide else K + 1, dtype=np.uint64), np.empty(K + 1), C.c_int64()])
+        return betas, supports, values, {
+            "nodes": int(nodes), "launches": int(info["n_iter"]), "q_all": float(info["L"]), "descents": int(info["rejects"]),
+            "status": "optimal" if rc == SLM_OK else "node_budget", "proven_optimal": rc == SLM_OK, "box_tol": 1e-12,
+        }
+
+    def solve_l0_l1_profile(self, alpha_min=0.0, max_groups=None, eta_l1=0.0, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_l1_profile``: ``solve_l0_profile`` with an l1 term -- the best support of every size for
+        ``min_b 1/2 b^T G b - c^T b + eta_l1 ||b||_1`` inside the box, the table that answers ``solve_l0_l1`` at every
+        ``alpha >= alpha_min``.  No ridge term, no ``T``.  Returns what ``solve_l0_profile`` returns; ``info`` also holds
+        ``descents`` and ``q_all`` is the proven lower bound on the value of all columns that the subtree cut used.
+        ``eta_l1 == 0`` runs the code of ``solve_l0_profile``."""
+        return self._l0_l1_profile(False, alpha_min, max_groups, eta_l1, big_M, need, max_nodes, binding)
+
+    def solve_l0_l1_profile_wide(self, alpha_min=0.0, max_groups=None, eta_l1=0.0, big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_l1_profile_wide``: ``solve_l0_l1_profile`` on the kernel's wide instantiation -- up to 128 columns
+        and groups, ``max_groups <= 64``, refused (``NotImplementedError``) when the ``max_groups`` largest groups together
+        hold more than 64 columns.  Masks as in ``solve_l0_profile_wide``."""
+        betas, words, values, info = self._l0_l1_profile(True, alpha_min, max_groups, eta_l1, big_M, need, max_nodes, binding)
+        return betas, [int(lo) | (int(hi) << 64) for lo, hi in np.asarray(words).reshape(-1, 2)], values, info
 
     def solve_l0_profile_batch(self, row_weights, n_effs, intercept=False, alpha_min=0.0, max_groups=None, eta=0.0, T=None,
                                big_M=100.0, need=None, max_nodes=0, binding=None):

@@ -16,7 +16,9 @@ as there are admissible supports of at most ``max_groups`` groups: it is meant f
 ``max_groups``.  ``alpha_min > 0`` prunes what no ``alpha >= alpha_min`` can use; the table is then no longer the best of
 every size and serves ``regularized`` only.  Limits are the estimators': 64 columns and 64 groups -- 128 of each with
 ``solver_options={"wide": True}``, when ``max_groups <= 64`` and the ``max_groups`` largest groups together hold at most 64
-columns (so that every support fits the factor) --, no row-sharded datasets, no ``constraints=``.  ``L1L0`` is not served: the value of a support there depends on its own ``eta``.
+columns (so that every support fits the factor) --, no row-sharded datasets, no ``constraints=``.  ``L1L0`` is not served
+HERE: the value of a support there depends on its own l1 weight.  For one fixed l1 weight it depends on nothing else, and
+``l1l0_profile`` (``_l1l0_profile.py``) is this table under an l1 term: ``L1L0`` at every ``alpha`` from one search per ``eta``.
 
 Import path: ``sparselm_amd.miqp`` (``l0_profile``, ``L0Profile``); ``sparselm_amd.model`` keeps the names it had.
 """

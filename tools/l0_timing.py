@@ -49,7 +49,15 @@ they lose is not lost to idle workgroups of finished problems).  Whole calls, ea
 in a synchronise, after a warm-up of every shape; ``--repeats`` (default 5) repeats with the variants alternating; median and
 spread.  Nothing is promised but what the file states.
 
-``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` / ``--only bound`` / ``--only cv`` runs one part."""
+Then the l1 profile (``sparselm_amd.miqp.l1l0_profile``, ``slm_solve_l0_l1_profile`` / ``_wide``), written to
+``profiles/l1l0_profile.txt`` by ``--only l1profile`` (it is not part of a run without ``--only``): at 25 x 20 and 25 x 30 one profile
+call at one ``eta`` with ``alpha_min`` the smallest of ten alphas beside the ten ``L1L0`` fits it replaces, in the same run --
+nodes, descents and ms per call, warm, the median of ``--repeats`` (default 5) with the variants alternating; and one call on
+the reference's 290 x 66 data (status, nodes, descents, time).  Every call runs under ``--max-nodes`` (a descent costs far more
+than a node, so the default budget of 2^30 nodes would take minutes per call at 25 x 30).  Nothing is promised but what the file states.
+
+``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` / ``--only bound`` / ``--only cv`` / ``--only l1profile`` runs one
+part."""
 
 import argparse
 import math
@@ -440,6 +448,83 @@ def cv_section(out_path, repeats):
         fh.write(text)
 
 
+def l1_profile_section(out_path, repeats, max_nodes):
+    from sklearn.datasets import make_regression
+
+    from sparselm_amd import _engine
+    from sparselm_amd.miqp import L1L0, l1l0_profile
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    lines = [f"l1 profile (l1l0_profile) on {name}, {dev['compute_units']} compute units: one profile call beside the L1L0 fits it replaces",
+             f"(wall time of whole Python calls, each ending in a synchronise; every shape warmed first; {repeats} repeats with the variants "
+             f"alternating, medians with the spread min .. max; budget {max_nodes} nodes per call; big_M = 1000)", ""]
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    opts = {"max_nodes": max_nodes}
+
+    def say(line):  # (the file grows line by line: a run that is cut short leaves what it measured)
+        lines.append(line)
+        print(line, flush=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    def clock(fn):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t0 = time.perf_counter()
+            out = fn()
+            return out, (time.perf_counter() - t0) * 1e3
+
+    def fmt(ms):
+        return f"{np.median(ms):9.3f} ({min(ms):.3f} .. {max(ms):.3f})"
+
+    for p in (20, 30):
+        X, y = make_regression(25, p, n_informative=10, noise=1.0, random_state=0)
+        var, cinf = float(np.var(y)), float(np.max(np.abs(X.T @ y / X.shape[0])))
+        eta = 0.05 * cinf
+        alphas = np.logspace(-4, 0, 10) * var
+        profile = lambda: l1l0_profile(X, y, eta=eta, alpha_min=alphas[0], big_M=1000, solver_options=opts)  # noqa: E731
+        fits = lambda: [L1L0(alpha=a, eta=eta, big_M=1000, solver_options=opts).fit(X, y) for a in alphas]  # noqa: E731
+        clock(profile), clock(fits)  # (warm: the first call of a shape loads the code objects)
+        t_prof, t_fits, prof, ests = [], [], None, None
+        for _ in range(repeats):
+            (prof, ms) = clock(profile)
+            t_prof.append(ms)
+            (ests, ms) = clock(fits)
+            t_fits.append(ms)
+        same = all(np.array_equal(e.coef_, prof.regularized(a)[0]) for e, a in zip(ests, alphas))
+        proven = prof.proven_optimal_ and all(e.solver_info_["proven_optimal"] for e in ests)
+        unproven = [f"{a / var:.1e}" for e, a in zip(ests, alphas) if not e.solver_info_["proven_optimal"]]
+        say(f"25 x {p}, eta = 0.05 ||X^T y / n||_inf, alphas = logspace(-4, 0, 10) var y, alpha_min = the smallest")
+        say(f"{'what':42s} {'nodes':>12s} {'descents':>10s} {'ms per call: median (min .. max)':>36s}")
+        say(f"{'l1l0_profile(alpha_min=1e-4 var y)':42s} {prof.solver_info_['nodes']:12d} {prof.solver_info_['descents']:10d} {fmt(t_prof):>36s}")
+        say(f"{'the ten L1L0 fits together':42s} {sum(e.solver_info_['nodes'] for e in ests):12d} "
+            f"{sum(e.solver_info_['descents'] for e in ests):10d} {fmt(t_fits):>36s}")
+        say(f"    sizes along the alphas {[int(e.active_groups_.sum()) for e in ests]}; every call proven: {proven}; coefficients identical at "
+            f"every alpha: {same}")
+        if not proven:
+            say(f"    the budget ran out in: the profile {not prof.proven_optimal_}; the fits at alpha / var y = {unproven} -- such rows compare "
+                "incumbents, not optima")
+        say(f"    one profile call / ten fits: {np.median(t_prof) / np.median(t_fits):.3f} of the wall time")
+        say("")
+    d = os.path.join(ROOT, "tests", "golden", "reference_examples")
+    X, y = np.load(os.path.join(d, "corr.npy")), np.load(os.path.join(d, "energy.npy"))
+    alpha_min, eta = 3.16e-7, 1.66e-6
+    call = lambda: l1l0_profile(X, y, eta=eta, alpha_min=alpha_min, max_groups=64, fit_intercept=True,  # noqa: E731
+                                solver_options={"wide": True, "max_nodes": max_nodes})
+    clock(call)
+    prof, ms = clock(call)
+    info = prof.solver_info_
+    say(f"the reference's {X.shape[0]} x {X.shape[1]} data: l1l0_profile(eta=1.66e-6, alpha_min=3.16e-7, max_groups=64, fit_intercept=True, "
+        f"solver_options={{'wide': True}}), budget {max_nodes} nodes, the second of two calls")
+    say(f"    status {info['status']} (proven: {info['proven_optimal']}), {info['nodes']} nodes, {info['descents']} descents, {ms / 1e3:.3f} s "
+        f"({info['nodes'] / (ms / 1e3):.3e} nodes/s)")
+    k = prof.regularized_size(alpha_min)
+    say(f"    bound on all columns {info['q_all']:.10e}; filled rows {int(np.isfinite(prof.values_).sum())} of {len(prof.values_)}; at alpha_min the "
+        f"table reads size {k}, objective {prof.values_[k] + alpha_min * k:.10e}")
+    say("    (nothing replaces this row: L1L0 itself stops at 64 columns)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-nodes", type=int, default=1 << 24)
@@ -449,9 +534,13 @@ def main():
     ap.add_argument("--constrained-out", default=os.path.join(ROOT, "profiles", "l0_constrained.txt"))
     ap.add_argument("--bound-out", default=os.path.join(ROOT, "profiles", "l0_bound.txt"))
     ap.add_argument("--cv-out", default=os.path.join(ROOT, "profiles", "l0_cv.txt"))
+    ap.add_argument("--l1-profile-out", default=os.path.join(ROOT, "profiles", "l1l0_profile.txt"))
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv"], default=None)
+    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile"], default=None)
     args = ap.parse_args()
+    if args.only == "l1profile":
+        l1_profile_section(args.l1_profile_out, max(1, args.repeats), args.max_nodes)
+        return
     if args.only == "cv":
         cv_section(args.cv_out, max(5, args.repeats))
         return
