@@ -215,18 +215,23 @@ int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lanes, const do
  *   k_end increasing, at most 512 in all).  Each build sets W's control block as the device's selection does (Kreal, K =
  *   max(16, Kreal rounded up to 16), k_new = the previous Kreal, idx = -1 on the padding) and queues what a solve queues after
  *   a selection: ws_gather_kernel (from the column-major copy of X, or from X with SLM_WSL_GATHER_X), the ws_xty kernels
- *   (SLM_WSL_XTY), ws_gram_kernel, ws_gram_reduce_kernel -- or ws_gram_cov_kernel under route 2.
+ *   (SLM_WSL_XTY: ws_xty_partial_kernel and ws_xty_apply_kernel, what a dataset without the column-major copy runs;
+ *   SLM_WSL_XTY_BUILD: what a solve queues on this dataset -- ws_gather_xty_kernel, which sums X_W^T y while it gathers, and
+ *   ws_xty_apply_kernel; with SLM_WSL_GATHER_X the same as SLM_WSL_XTY), ws_gram_kernel, ws_gram_reduce_kernel -- or
+ *   ws_gram_cov_kernel under route 2.
  *   Lanes with the same row weights and n_eff share a Gram (a row set); set_of_out[l] is lane l's, n_sets_out their number.
  *   Then one pass: route 1 the split pass (residuals from W for the lanes with on_ws[l] != 0, from X for the others, then X^T R),
  *   route 2 the covariance route (cov_index[l]: the lane's entry of slm_dataset_covariance*; no row weights, no n_eff).  A lane
  *   with on_ws must be zero outside W (SLM_ERR_BAD_ARG otherwise).  G_out[l], loss_out[l] as for slm_gradient_lanes.
- * gram_out: [n_sets][K][K] (nullable); xw_out: [n][K] (nullable; route 1); xty_out: [Kreal + 1] (SLM_WSL_XTY):
- * -X_W^T y / n, then y^T y / 2n.  kernels_out (nullable): every kernel launched, ';'-separated, in order; the covariance
+ * gram_out: [n_sets][K][K] (nullable); xw_out: [n][K] (nullable; route 1); xty_out: [Kreal + 1] (SLM_WSL_XTY, SLM_WSL_XTY_BUILD):
+ * -X_W^T y / n, then y^T y / 2n; with SLM_WSL_XTY_BUILD [Kreal + 2], last the number of entries of lane 0's gradient vector
+ * outside W that the builds wrote to (0: they left everything but W's entries and the loss alone).  kernels_out (nullable): every kernel launched, ';'-separated, in order; the covariance
  * product is named "+listed" when every row set reads only W's rows of its Gram.  SLM_ERR_UNSUPPORTED where no kernel serves
  * the call, and for row-sharded datasets.  No reference counterpart (tests only).
  */
 #define SLM_WSL_GATHER_X 1u  /* gather from the row-major X, not the column-major copy */
 #define SLM_WSL_XTY 2u       /* queue the ws_xty kernels with every build (the refinement after a row-sample pass) */
+#define SLM_WSL_XTY_BUILD 4u /* X_W^T y with every build the way a solve gets it: out of the gather where it reads the column-major copy */
 typedef struct slm_ws_lanes_opts {
   int32_t route;             /* 1: split pass, 2: covariance entries */
   int32_t n_lanes;           /* 1 .. SLM_MAX_LANES */

@@ -394,7 +394,8 @@ int enqueue_gradient_cov(slm_dataset* ds, int B, const int* entry_of, const int*
                          const PathCtl* ctl = nullptr, const WsArgs* wa = nullptr, GradNames* names = nullptr);
 void launch_tail(const TailArgs& ta, hipStream_t s);
 int64_t sketch_rows(int64_t n);
-int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows = 0);
+int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows = 0,
+                    double* keep = nullptr);
 int estimate_lipschitz(const slm_host::Knobs& kn, slm_dataset* ds, double* L_out, int iters);
 int allow_big_lds(const void* fn, int device);
 static const int kProfStride = 3;  // SLM_FLAG_PROFILE times every 3rd gradient launch (a working-set path has ~5: two of them;

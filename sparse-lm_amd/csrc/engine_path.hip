@@ -417,8 +417,8 @@ int PathCall::find_covariance() {
 // the sketch's estimate for the dataset's own rows and weights, computed once and kept on the device
 int PathCall::kept_sketch() {
   if (ds->sketch_valid && !(o.flags & SLM_FLAG_FRESH_L)) return SLM_OK;
-  SLM_TRY(power_iteration(kn, ds, default_lanes(ds, 1), nullptr, slm_host::kSketchPowerIters, sketch_rows(ds->n)));
-  HIP_TRY(hipMemcpyAsync(ds->lambda + ds->lane_cap, ds->lambda, sizeof(double), hipMemcpyDeviceToDevice, eng->stream));
+  // (the last power step stores the estimate in lane 0's slot and in the kept one)
+  SLM_TRY(power_iteration(kn, ds, default_lanes(ds, 1), nullptr, slm_host::kSketchPowerIters, sketch_rows(ds->n), ds->lambda + ds->lane_cap));
   ds->sketch_valid = true;
   return SLM_OK;
 }
@@ -1060,12 +1060,17 @@ void PathCall::enqueue_tail() {
 // gradient at zero on W (`xty`: the refinement after the pass on a row sample), the partial Grams and their fixed-order sum --
 // or, under covariance passes (`cs` != nullptr), the sub-matrix of the row sets' Grams.  Every kernel returns at once unless
 // a build is under way.  PathCall::enqueue_refinement and slm_working_set_lanes; `names` (nullable): the kernels launched.
+// xty: WS_XTY_BUILD is what a solve asks for -- the partial sums of X_W^T y come out of the gather where it reads the
+// column-major copy, and from a launch of their own behind it (ws_xty_partial_kernel) where it reads X;
+// WS_XTY_SEPARATE (the diagnostic call's SLM_WSL_XTY) takes that launch on any dataset.
+enum WsXty { WS_XTY_NONE = 0, WS_XTY_BUILD = 1, WS_XTY_SEPARATE = 2 };
+static_assert(slm_host::kXtyPartStride == WS_KCAP + 1, "a row of partial sums: every position, then y^2");
 struct WsNames {
   const char* k[8];
   int n = 0;
   void add(const char* name) { if (n < 8) k[n++] = name; }
 };
-static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* cs, bool xty, const int* done, int n_lanes, hipStream_t s,
+static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* cs, WsXty xty, const int* done, int n_lanes, hipStream_t s,
                              WsNames* names = nullptr) {
   const int64_t n = ds->n;
   if (cs) {
@@ -1075,19 +1080,27 @@ static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* c
     if (names) names->add("ws_gram_cov_kernel");
     return;
   }
-  hipLaunchKernelGGL(ws_gather_kernel, dim3((unsigned)std::min<int64_t>((n + 31) / 32, 1024), WS_KCAP / 32), dim3(256), 0, s, wa);
-  if (names) names->add("ws_gather_kernel");
-  if (xty) {  // the exact gradient at zero on W, from the gathered columns (ws_kernels.hpp (ii-b))
+  // (the partial sums of X_W^T y, up to 1 024 x 513 doubles, go where the Gram kernel's go next: that block holds 512 x 512 doubles
+  //  per row block of the Gram kernel and row set.  The gradient's `partial` is sized by the gradient kernels' grids alone --
+  //  8192 ld doubles from X^T R, less than 512 x 513 for rows of up to 32 columns)
+  const bool fused = xty == WS_XTY_BUILD && wa.XT != nullptr;
+  const int64_t part_doubles = (int64_t)ws_row_blocks(ds, false, 1).most * std::max(1, ds->ws_sets) * WS_KCAP * WS_KCAP;
+  const int gather_rows = fused ? slm_host::xty_part_rows(n, part_doubles) : slm_host::gather_row_blocks(n);
+  if (fused) hipLaunchKernelGGL(ws_gather_xty_kernel, dim3((unsigned)gather_rows, WS_KCAP / 32), dim3(256), 0, s, wa, ds->y, wa.part);
+  else hipLaunchKernelGGL(ws_gather_kernel, dim3((unsigned)gather_rows, WS_KCAP / 32), dim3(256), 0, s, wa);
+  if (names) names->add(fused ? "ws_gather_xty_kernel" : "ws_gather_kernel");
+  if (xty != WS_XTY_NONE) {  // the exact gradient at zero on W (ws_kernels.hpp (ii-b))
     XtyArgs xa;
-    // (its partial sums, up to 2 CUs x 513 doubles, go where the Gram kernel's go next: that block holds 512 x 512 doubles per row
-    //  block of the Gram kernel, at least half as many blocks as these.  The gradient's `partial` is sized by the gradient
-    //  kernels' grids alone -- 8192 ld doubles from X^T R, less than 512 x 513 for rows of up to 32 columns)
     xa.ws = wa.ws; xa.idx = wa.idx; xa.XW = wa.XW; xa.y = ds->y; xa.part = wa.part; xa.g = ds->g; xa.gprev = ds->gprev; xa.z = ds->z;
     xa.ctl = ds->ctl; xa.done = done; xa.n = n; xa.ld = ds->ld; xa.inv_n = 1.0 / (double)ds->n_global; xa.n_lanes = n_lanes;
-    xa.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(2 * ds->eng->cus, n / 64));
-    hipLaunchKernelGGL(ws_xty_partial_kernel, dim3((unsigned)xa.nblk), dim3(512), 0, s, xa);
-    hipLaunchKernelGGL(ws_xty_apply_kernel, dim3(WS_KCAP / 128), dim3(512), 0, s, xa);
-    if (names) { names->add("ws_xty_partial_kernel"); names->add("ws_xty_apply_kernel"); }
+    xa.nblk = gather_rows;
+    if (!fused) {
+      xa.nblk = (int)std::max<int64_t>(1, std::min<int64_t>(2 * ds->eng->cus, n / 64));
+      hipLaunchKernelGGL(ws_xty_partial_kernel, dim3((unsigned)xa.nblk), dim3(512), 0, s, xa);
+      if (names) names->add("ws_xty_partial_kernel");
+    }
+    hipLaunchKernelGGL(ws_xty_apply_kernel, dim3(WS_KCAP / 16), dim3(512), 0, s, xa);
+    if (names) names->add("ws_xty_apply_kernel");
   }
   hipLaunchKernelGGL(ws_gram_kernel, dim3((unsigned)wa.nblk, (unsigned)wa.n_sets, 1), dim3(WS_GRAM_THREADS), 0, s,
                      wa);
@@ -1127,9 +1140,9 @@ void PathCall::enqueue_refinement() {
     if (cov_on) {
       CovSets cs;
       for (int st = 0; st < kMaxLanes; ++st) cs.G[st] = st < wa.n_sets ? ds->cov[(size_t)cov_entry[wa.set_lane[st]]].G : nullptr;
-      ws_enqueue_build(ds, wa, &cs, false, done_flag, B, s);
+      ws_enqueue_build(ds, wa, &cs, WS_XTY_NONE, done_flag, B, s);
     } else {
-      ws_enqueue_build(ds, wa, nullptr, fix_start, done_flag, B, s);
+      ws_enqueue_build(ds, wa, nullptr, fix_start ? WS_XTY_BUILD : WS_XTY_NONE, done_flag, B, s);
     }
     if (wa.Gx) {
       // one collective per pass on every rank whether or not a build is under way: the ranks run the
@@ -1725,11 +1738,13 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
                                      int32_t kernels_len) {
   if (!ds || !o || !o->Z || !o->cols || !o->k_end || !G_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   const int route = o->route, B = o->n_lanes, nb = o->n_builds;
-  const bool gather_x = (o->flags & SLM_WSL_GATHER_X) != 0, xty = (o->flags & SLM_WSL_XTY) != 0;
+  const bool gather_x = (o->flags & SLM_WSL_GATHER_X) != 0, xty = (o->flags & (SLM_WSL_XTY | SLM_WSL_XTY_BUILD)) != 0;
+  const WsXty xty_mode = (o->flags & SLM_WSL_XTY_BUILD) ? WS_XTY_BUILD : xty ? WS_XTY_SEPARATE : WS_XTY_NONE;
   if (route != 1 && route != 2) return fail(SLM_ERR_BAD_ARG, "route must be 1 (split pass) or 2 (covariance), got %d", route);
   if (B < 1 || B > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "between 1 and %d lanes, got %d", kMaxLanes, B);
-  if (o->flags & ~(SLM_WSL_GATHER_X | SLM_WSL_XTY)) return fail(SLM_ERR_BAD_ARG, "unknown flags %#x", o->flags);
-  if (xty != (xty_out != nullptr)) return fail(SLM_ERR_BAD_ARG, "xty_out goes with SLM_WSL_XTY");
+  if (o->flags & ~(SLM_WSL_GATHER_X | SLM_WSL_XTY | SLM_WSL_XTY_BUILD)) return fail(SLM_ERR_BAD_ARG, "unknown flags %#x", o->flags);
+  if ((o->flags & SLM_WSL_XTY) && (o->flags & SLM_WSL_XTY_BUILD)) return fail(SLM_ERR_BAD_ARG, "SLM_WSL_XTY or SLM_WSL_XTY_BUILD, not both");
+  if (xty != (xty_out != nullptr)) return fail(SLM_ERR_BAD_ARG, "xty_out goes with SLM_WSL_XTY / SLM_WSL_XTY_BUILD");
   if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "slm_working_set_lanes: row-sharded datasets");
   if (B > ds->lane_cap) return fail(SLM_ERR_UNSUPPORTED, "%d lanes: the dataset holds %d", B, ds->lane_cap);
   const int64_t n = ds->n, p = ds->p, ld = ds->ld;
@@ -1873,7 +1888,7 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
     SLM_TRY(put(ds->ws_pos, h_pos.data(), sizeof(int32_t) * (size_t)ld));
     SLM_TRY(put(ds->ws_ctl, h, sizeof(WsCtl)));
     WsNames wn;
-    ws_enqueue_build(ds, wa, route == 2 ? &cs : nullptr, xty, &ds->gctl->done, B, s, &wn);
+    ws_enqueue_build(ds, wa, route == 2 ? &cs : nullptr, xty_mode, &ds->gctl->done, B, s, &wn);
     for (int u = 0; u < wn.n; ++u) named(wn.k[u]);
     SLM_TRY(check_launch());
     SLM_TRY(get(h, ds->ws_ctl, sizeof(WsCtl)));
@@ -1894,6 +1909,17 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
     SLM_TRY(get(g0.data(), ds->g, sizeof(double) * (size_t)(ld + 16)));
     for (int k = 0; k < kreal; ++k) xty_out[k] = g0[(size_t)o->cols[k]];
     xty_out[kreal] = g0[(size_t)ld];
+    if (o->flags & SLM_WSL_XTY_BUILD) {
+      // entries of lane 0's vector outside W (and outside the loss slot) that no longer hold the fill written above: a build
+      // writes W's entries and nothing else -- what a pad position or a position past K would hit shows here
+      int64_t touched = 0;
+      for (int64_t j = 0; j < ld + 16; ++j) {
+        uint64_t bits;
+        memcpy(&bits, &g0[(size_t)j], sizeof(bits));
+        if (j != ld && !(j < ld && pos[(size_t)j] >= 0) && bits != ~0ull) ++touched;
+      }
+      xty_out[kreal + 1] = (double)touched;
+    }
   }
   HIP_TRY(hipStreamSynchronize(s));
   // ---- one pass on W: the lanes' control blocks (live; on W where asked -- PathCtl::zsup; at zero where they are --

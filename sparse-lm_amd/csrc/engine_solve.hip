@@ -446,7 +446,9 @@ int64_t sketch_rows(int64_t n) {
 // eigenvalue is, in expectation, no smaller than that of the full operator (Jensen: lambda_max is
 // convex and E G_S = G for exchangeable rows), so it serves as a cheap step-size bound where the
 // iteration does not depend on a tight one (working-set solves); the curvature guards cover the rest.
-int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows) {
+// keep (nullable, device): the last step stores lane 0's estimate there as well -- the dataset's kept slot (PathCall::kept_sketch).
+int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup& ls_in, double* L_out /*[B]*/, int iters, int64_t n_rows,
+                    double* keep) {
   LaneSetup ls = ls_in;
   if (n_rows > 0) {
     for (int l = 0; l < kMaxLanes; ++l) {
@@ -468,6 +470,7 @@ int power_iteration(const slm_host::Knobs& kn, slm_dataset* ds, const LaneSetup&
     pa.g = ds->g;
     pa.v = ds->z;
     pa.lambda = ds->lambda;
+    pa.keep = k + 1 == iters ? keep : nullptr;
     pa.p = (int)ds->p;
     pa.ld = ds->ld;
     hipLaunchKernelGGL(power_step_kernel, dim3(ls.B), dim3(TAIL_THREADS), 0, s, pa);

@@ -263,6 +263,23 @@ inline SamplePlan sample_plan(int64_t n_s, int64_t p, int64_t ld32, int cus) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Row blocks of the working set's gather (ws_kernels.hpp, ws_gather_kernel): one per tile of 32 rows up to kGatherRowBlocks,
+// from there on the kernel's grid-stride loop wraps.  The gather that also sums X_W^T y writes one row of kXtyPartStride
+// partial sums per row block into a buffer of part_doubles doubles (the Gram's partial block): it takes the same grid
+// unless the buffer holds fewer rows -- never fewer than one, which the smallest buffer (512 x 512) holds.
+// ---------------------------------------------------------------------------------------------
+constexpr int kGatherRowBlocks = 1024;
+constexpr int kXtyPartStride = 512 + 1;  // (WS_KCAP positions and the sum of y^2)
+inline int gather_row_blocks(int64_t n) {
+  const int64_t tiles = (std::max<int64_t>(n, 1) + 31) / 32;
+  return (int)std::min<int64_t>(tiles, kGatherRowBlocks);
+}
+inline int xty_part_rows(int64_t n, int64_t part_doubles) {
+  const int64_t fit = std::max<int64_t>(1, part_doubles / kXtyPartStride);
+  return (int)std::min<int64_t>(gather_row_blocks(n), fit);
+}
+
+// ---------------------------------------------------------------------------------------------
 // A row set's Gram among those a dataset keeps: by the two fingerprint sums of its row weights and its scaling.
 // ---------------------------------------------------------------------------------------------
 template <typename Entry>

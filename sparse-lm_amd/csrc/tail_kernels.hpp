@@ -1113,6 +1113,7 @@ struct PowerArgs {
   const double* g;  // [n_lanes][ld + 16]
   double* v;        // [n_lanes][ld]
   double* lambda;   // [n_lanes]
+  double* keep;     // nullable: lane 0's lambda goes there too (it was a device-to-device copy of one double behind the launch)
   int p;
   int64_t ld;
 };
@@ -1129,7 +1130,10 @@ static __global__ __launch_bounds__(TAIL_THREADS) void power_step_kernel(PowerAr
   const double nrm = sqrt(s[0]);
   const double inv = nrm > 0.0 ? 1.0 / nrm : 0.0;
   for (int j = threadIdx.x; j < a.p; j += TAIL_THREADS) a.v[j] = a.g[j] * inv;
-  if (threadIdx.x == 0) a.lambda[0] = nrm;
+  if (threadIdx.x == 0) {
+    a.lambda[0] = nrm;
+    if (a.keep != nullptr && blockIdx.x == 0) a.keep[0] = nrm;
+  }
 }
 
 // Step-size seed of a solve straight from the power iteration's result (one estimate for all lanes): L with the

@@ -724,11 +724,22 @@ static __global__ __launch_bounds__(WS_THREADS) void ws_select_kernel(TailArgs a
 // tile, so reads and writes both move 256-byte segments.  (Gathering from the row-major X touches one 64-byte
 // sector per element: 0.2 ms for 112 columns, 0.5 ms per 50-alpha path.)  grid (row tiles, 16 column
 // tiles of 32 starting at k_new); tiles beyond K return at once.
+//
+// XTY (the build behind the pass on a row sample, (ii-b) below): the pass that moves a value also holds it in a register
+// next to its row, so the linear term of the model comes out of it -- every thread sums x * y[i] for its four columns over
+// the row tiles it walks, in the order of its grid-stride loop; the 32 row lanes of a column are folded by shuffles (xor
+// 16, 8, 4, 2, 1: a fixed tree), and row lane 0 writes part[blockIdx.x][k], one partial per (row block, position).  The
+// column tile blockIdx.y == 0 does the same for y[i]^2 into part[blockIdx.x][WS_KCAP].  No LDS beyond the tile, no
+// atomics.  A pad position (idx < 0) and a row past n read nothing and add zeros.  The tiles start at position 0 whatever
+// k_new is (the selection behind a sample pass is a fresh one; the diagnostic call may ask at an append, and then the old
+// columns are written again with the values they hold), so every position below K has its partial in every row block.
+// The plain gather (XTY = false, ws_gather_kernel) is the kernel as it was: the extra code is compiled out.
 // ---------------------------------------------------------------------------------------------
-static __global__ __launch_bounds__(256) void ws_gather_kernel(WsArgs w) {
+template <bool XTY>
+__device__ __forceinline__ void ws_gather_body(const WsArgs& w, const double* __restrict__ y, double* __restrict__ part) {
   if (!w.ws->building) return;
   const int K = w.ws->K;
-  const int k0 = w.ws->k_new + 32 * (int)blockIdx.y;
+  const int k0 = (XTY ? 0 : w.ws->k_new) + 32 * (int)blockIdx.y;
   if (k0 >= K) return;
   __shared__ double tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
@@ -741,15 +752,25 @@ static __global__ __launch_bounds__(256) void ws_gather_kernel(WsArgs w) {
     const int k = k0 + ty + 8 * u;
     jcol[u] = k < K ? w.idx[k] : -1;
   }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  double yy = 0.0;
+  const bool yy_tile = XTY && blockIdx.y == 0;
   for (int64_t rt = blockIdx.x; rt < row_tiles; rt += gridDim.x) {
     const int64_t i0 = rt * 32;
     const int64_t i = i0 + tx;
     double v[4];
+    double yi = 0.0;
+    if (XTY) yi = i < w.n ? y[i] : 0.0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {  // read: lanes walk rows i (contiguous in XT)
       const int j = jcol[u];
       // (XT == nullptr: no memory for the column-major copy -- same tile, sector-granular reads from X)
       v[u] = (j >= 0 && i < w.n) ? (w.XT ? w.XT[((rt * w.ld + j) << 5) + tx] : w.X[i * w.ld + j]) : 0.0;
+    }
+    if (XTY) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc[u] = __builtin_fma(v[u], yi, acc[u]);
+      if (yy_tile) yy = __builtin_fma(yi, yi, yy);
     }
     __syncthreads();  // the tile of the previous round has been written out
 #pragma unroll
@@ -761,14 +782,37 @@ static __global__ __launch_bounds__(256) void ws_gather_kernel(WsArgs w) {
       if (i < w.n && k < K) w.XW[i * WS_KCAP + k] = tile[tx][ii];
     }
   }
+  if (XTY) {
+    // (a wavefront holds two values of ty, 32 row lanes each: the xor offsets below 32 stay inside a half)
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc[u] += __shfl_xor(acc[u], off, 64);
+      if (yy_tile) yy += __shfl_xor(yy, off, 64);  // (uniform for the workgroup)
+    }
+    double* out = part + (int64_t)blockIdx.x * (WS_KCAP + 1);
+    if (tx == 0) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int k = k0 + ty + 8 * u;
+        if (k < K) out[k] = acc[u];
+      }
+      if (yy_tile && ty == 0) out[WS_KCAP] = yy;
+    }
+  }
 }
+static __global__ __launch_bounds__(256) void ws_gather_kernel(WsArgs w) { ws_gather_body<false>(w, nullptr, nullptr); }
+static __global__ __launch_bounds__(256) void ws_gather_xty_kernel(WsArgs w, const double* y, double* part) { ws_gather_body<true>(w, y, part); }
 
 // ---------------------------------------------------------------------------------------------
 // (ii-b) A path that opened on a row sample (solve_core, "sample start"): the gradient at zero the first call worked
-// with is an estimate -- good enough to choose W, not to build the model on.  On W the exact one costs one read of
-// the gathered columns, not of X: c_k = -X_k^T y / n, and the loss at zero is y^T y / 2n.  Two launches: partial
-// sums over row blocks, then the sums go into g and gprev of every lane (all lanes stand at zero), the loss
-// into g[ld], the first entry of the objective history and PathCtl::loss_base.  No row weights (the caller checks).
+// with is an estimate -- good enough to choose W, not to build the model on.  On W the exact one is c_k = -X_k^T y / n, and
+// the loss at zero is y^T y / 2n.  The partial sums over row blocks are a by-product of the gather (ws_gather_xty_kernel);
+// ws_xty_apply_kernel folds them and the sums go into g and gprev of every lane (all lanes stand at zero), the loss into
+// g[ld], the first entry of the objective history and PathCtl::loss_base.  No row weights (the caller checks).
+// A dataset without the column-major copy (XT == nullptr) keeps the launch of its own for the partial sums,
+// ws_xty_partial_kernel, one more read of the gathered columns: its gather is bound by the sector-granular reads of X, ten
+// times the time of the other, and is left as it is.  The partials of both have one layout, and the apply is the same.
 // ---------------------------------------------------------------------------------------------
 struct XtyArgs {
   const WsCtl* ws;
@@ -855,32 +899,41 @@ static __global__ __launch_bounds__(512) void ws_xty_partial_kernel(XtyArgs a) {
     out[WS_KCAP] = sum;
   }
 }
-// grid: WS_KCAP / 128 workgroups of 512 threads -- 128 positions each, four threads per position that take every
-// fourth row block (eight loads in flight each: one thread per position walked the 512 blocks one load at a time, 122 us)
+// grid: WS_KCAP / 16 workgroups of 512 threads -- 16 positions each (128 bytes of a row of partials), 32 threads per position
+// that take every thirty-second row block, eight loads in flight each: at most 1 024 row blocks (slm_host::xty_part_rows) are
+// four rounds of loads per thread.  (Four workgroups of 128 positions x 4 threads walked 512 blocks in sixteen rounds: 16 us.)
+// The 32 slices of a position are added in order; so are the blocks' sums of y^2, by workgroup 0.
 static __global__ __launch_bounds__(512) void ws_xty_apply_kernel(XtyArgs a) {
-  if (*a.done) return;
-  __shared__ double red[4][128];
+  if (*a.done || !a.ws->building) return;  // (no build under way: the gather has left no partial sums)
+  __shared__ double red[32][17];
   __shared__ double ry[512];
   const int K = a.ws->K;
-  const int kl = threadIdx.x & 127, q = threadIdx.x >> 7;
-  const int k = (int)blockIdx.x * 128 + kl;
-  if ((int)blockIdx.x * 128 >= K) return;  // (uniform for the workgroup)
+  const int kl = threadIdx.x & 15, q = threadIdx.x >> 4;
+  const int k = (int)blockIdx.x * 16 + kl;
+  if ((int)blockIdx.x * 16 >= K) return;  // (uniform for the workgroup)
   double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (k < K) {
     int b = q;
-    for (; b + 28 < a.nblk; b += 32) {
+    for (; b + 224 < a.nblk; b += 256) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) s[u] += a.part[(int64_t)(b + 4 * u) * (WS_KCAP + 1) + k];
+      for (int u = 0; u < 8; ++u) s[u] += a.part[(int64_t)(b + 32 * u) * (WS_KCAP + 1) + k];
     }
-    for (; b < a.nblk; b += 4) s[0] += a.part[(int64_t)b * (WS_KCAP + 1) + k];
+    for (; b < a.nblk; b += 32) s[0] += a.part[(int64_t)b * (WS_KCAP + 1) + k];
   }
   red[q][kl] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-  if (blockIdx.x == 0) ry[threadIdx.x] = (int)threadIdx.x < a.nblk ? a.part[(int64_t)threadIdx.x * (WS_KCAP + 1) + WS_KCAP] : 0.0;
+  if (blockIdx.x == 0) {
+    double t = 0.0;
+    for (int b = threadIdx.x; b < a.nblk; b += 512) t += a.part[(int64_t)b * (WS_KCAP + 1) + WS_KCAP];
+    ry[threadIdx.x] = t;
+  }
   __syncthreads();
   if (q == 0 && k < K) {
     const int j = a.idx[k];
     if (j >= 0) {
-      const double c = -((red[0][kl] + red[1][kl]) + (red[2][kl] + red[3][kl])) * a.inv_n;
+      double t = 0.0;
+#pragma unroll
+      for (int w = 0; w < 32; ++w) t += red[w][kl];
+      const double c = -t * a.inv_n;
       for (int l = 0; l < a.n_lanes; ++l) {
         a.g[(int64_t)l * (a.ld + 16) + j] = c;
         a.gprev[(int64_t)l * a.ld + j] = c;
@@ -888,7 +941,7 @@ static __global__ __launch_bounds__(512) void ws_xty_apply_kernel(XtyArgs a) {
       }
     }
   }
-  if (blockIdx.x == 0) {  // the loss at zero: the row blocks' sums of y^2, folded in a fixed order (nblk <= 512)
+  if (blockIdx.x == 0) {  // the loss at zero: the row blocks' sums of y^2, folded in a fixed order
     for (int off = 256; off >= 1; off >>= 1) {
       if ((int)threadIdx.x < off) ry[threadIdx.x] += ry[threadIdx.x + off];
       __syncthreads();

@@ -139,6 +139,7 @@ class _GradientOpts(C.Structure):
 
 WSL_GATHER_X = 1  # slm_working_set_lanes: gather from the row-major X, not the column-major copy
 WSL_XTY = 2       # ... and queue the ws_xty kernels with every build
+WSL_XTY_BUILD = 4  # ... X_W^T y with every build the way a solve gets it (out of the gather where it reads the column-major copy)
 
 
 class _WsLanesOpts(C.Structure):
@@ -875,12 +876,13 @@ class Dataset:
         return G, loss, names.value.decode()
 
     def working_set_lanes(self, Z, cols, k_end, on_ws=None, row_weights=None, n_eff=None, route: int = 1, cov_index=None,
-                          gather_from_x: bool = False, xty: bool = False, want_xw: bool = False):
+                          gather_from_x: bool = False, xty: bool = False, want_xw: bool = False, xty_build: bool = False):
         """``slm_working_set_lanes``: W built in stages -- ``cols[:k_end[0]]``, then each ``cols[k_end[b-1]:k_end[b]]``
         appended -- and one gradient pass of ``len(Z)`` lanes on it through route 1 (split pass; residuals from W for the
         lanes with ``on_ws``) or 2 (covariance entries ``cov_index``).  Returns a namespace: ``G`` (lanes, p), ``loss``,
         ``gram`` (row sets, K, K), ``set_of``, ``n_sets``, ``K``, ``XW`` (n, K) with ``want_xw``, ``xty`` (-X_W^T y / n) and
-        ``yy`` (y^T y / 2n) with ``xty``, and ``kernels``.  A call no kernel serves raises NotImplementedError."""
+        ``yy`` (y^T y / 2n) with ``xty`` (the two ws_xty kernels behind the gather) or ``xty_build`` (the way a solve
+        gets them on this dataset: out of the gather), and ``kernels``.  A call no kernel serves raises NotImplementedError."""
         import types
 
         _sync_knobs()
@@ -901,21 +903,32 @@ class Dataset:
         if ci is not None and ci.shape != (B,):
             raise ValueError(f"cov_index has shape {ci.shape}, expected {(B,)}")
         opts = _WsLanesOpts(int(route), B, _ptr(Z), _ptr(ow), _ptr(rw), _ptr(ne), _ptr(ci), _ptr(cols), _ptr(k_end),
-                            int(k_end.size), (WSL_GATHER_X if gather_from_x else 0) | (WSL_XTY if xty else 0))
+                            int(k_end.size), (WSL_GATHER_X if gather_from_x else 0) | (WSL_XTY if xty else 0) |
+                            (WSL_XTY_BUILD if xty_build else 0))
         G = np.empty((B, self.p))
         loss = np.empty(B)
         set_of = np.empty(B, dtype=np.int32)
         n_sets = C.c_int32(0)
         gram = np.empty((B, K, K))
         XW = np.empty((self.n, K)) if want_xw else None
-        xt = np.empty(kreal + 1) if xty else None
+        xt = np.empty(kreal + 2) if (xty or xty_build) else None
         names = C.create_string_buffer(4096)
         _check(self._lib.slm_working_set_lanes(self._h, C.byref(opts), _ptr(G), _ptr(loss), _ptr(set_of), C.byref(n_sets),
                                                _ptr(gram), _ptr(XW), _ptr(xt), names, len(names)))
         ns = n_sets.value
         return types.SimpleNamespace(G=G, loss=loss, gram=gram[:ns], set_of=set_of, n_sets=ns, K=K, XW=XW,
                                      xty=None if xt is None else xt[:kreal], yy=None if xt is None else float(xt[kreal]),
-                                     kernels=names.value.decode())
+                                     touched_outside=int(xt[kreal + 1]) if xty_build else None, kernels=names.value.decode())
+
+    def ws_build(self, cols, k_end=None, xty: bool = False, gather_from_x: bool = False, want_xw: bool = False):
+        """The builds of a working set alone, as a solve queues them: ``working_set_lanes`` with one lane at zero.  ``xty``:
+        the exact linear term of the build behind a row-sample pass (``xty`` = -X_W^T y / n per position, ``yy`` = y^T y / 2n),
+        with the kernels a solve takes for it on this dataset; ``touched_outside`` counts the entries of the gradient vector
+        outside W that the builds wrote to (a pad position must write nothing: 0)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        r = self.working_set_lanes(np.zeros((1, self.p)), cols, [cols.size] if k_end is None else k_end, on_ws=[0],
+                                   gather_from_x=gather_from_x, want_xw=want_xw, xty_build=xty)
+        return r
 
     def working_set_model_solve(self, cols, gram, zprev, gprev, z, a0, b0, d0, points, tol, mode, set_of=None, Lw=None,
                                 direct: bool = True, hard: bool = False, invalid: bool = False, building: bool = False,
