@@ -725,7 +725,7 @@ int slm_solve_l0_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_gro
  * masks of two words as in slm_solve_l0_profile_wide, and its two refusals: max_groups <= 64, and the max_groups largest
  * groups together hold at most 64 columns (the messages name 64) -- a support's columns, dependent ones included, then fit
  * the 64 lanes that hold them.  A problem within the narrow limits gives the same bytes on either.  Not here: a ridge term,
- * linear constraints, the exclusion bound, batches over row sets.
+ * linear constraints, the exclusion bound.  Batches over row sets and l1 weights: slm_solve_l0_profile_grid (eta_kind 1).
  */
 int slm_solve_l0_l1_profile(slm_dataset* ds, double alpha_min, int32_t max_groups, double eta_l1, double big_M,
                             const uint64_t* need /* n_groups masks or NULL */, int64_t max_nodes /* <=0: default */,
@@ -759,7 +759,8 @@ int slm_solve_l0_l1_profile_wide(slm_dataset* ds, double alpha_min, int32_t max_
  * SLM_OK iff every problem finished; SLM_ERR_NOT_CONVERGED with ALL outputs valid when any budget ran out.  Limits and
  * argument errors, all before a device is touched: count outside 1 .. 16, a negative or non-finite weight and those of
  * slm_solve_l0_profile (SLM_ERR_BAD_ARG); ps or the search groups above 64, a row-sharded dataset (SLM_ERR_UNSUPPORTED).
- * Not here: wide, l1, constrained or exclusion-bound problems; batches over eta or T.
+ * Not here: wide, constrained or exclusion-bound problems; batches over T.  An l1 term and several eta per call:
+ * slm_solve_l0_profile_grid below, of which this entry is the call n_eta = 1, eta_kind = 0.
  */
 int slm_solve_l0_profile_batch(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                                const int64_t* n_effs /* [count] */, int32_t intercept, double alpha_min, int32_t max_groups,
@@ -768,6 +769,39 @@ int slm_solve_l0_profile_batch(slm_dataset* ds, int32_t count, const double* con
                                double* beta_out /* [count][max_groups+1][ps] */, double* intercept_out /* [count][max_groups+1] or NULL */,
                                uint64_t* support_out /* [count][max_groups+1] */, double* value_out /* [count][max_groups+1] */,
                                int64_t* nodes_out /* [count] or NULL */, slm_point_info* info /* [count] or NULL */);
+
+/*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_profile_batch, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs it looks the symbol up.)  The l0 profile GRID: the tables of slm_solve_l0_profile
+ * (eta_kind 0) or of slm_solve_l0_l1_profile (eta_kind 1) for `count` row sets of one dataset at n_eta weights each -- a
+ * cross-validation of L2L0 or L1L0 over (alpha, eta) -- from ONE launch (csrc/l0_kernels.hpp, template parameter BATCH, with
+ * L1 for eta_kind 1), one upload, one Gram per row set and one read-back.  Row sets (row_weights, n_effs, NULL entries,
+ * 1 <= count <= 16) and intercept exactly as for slm_solve_l0_profile_batch.  Problem b = r * n_eta + e is row set r with
+ * etas[e]:  eta_kind 0: H = G_r + 2 etas[e] T, the problem of slm_solve_l0_profile;  eta_kind 1: H = G_r and etas[e] weighs
+ * ||beta||_1, the problem of slm_solve_l0_l1_profile, T must be NULL (an l1 weight of exactly 0 is searched by the l1 kernel
+ * with weight 0 and valued on the host as slm_solve_l0_profile values it).  Every output has the leading dimension
+ * count * n_eta in that order and holds per problem what the entry it replaces gives: with eta_kind 1 the rows are recomputed
+ * by the descent and polished, info[b].L is the l1 lower bound the cut used and info[b].rejects the number of descents.
+ * alpha_min, max_groups, T, big_M and need are shared; max_nodes is the budget of EACH problem, a starved problem stops alone.
+ * Returns SLM_OK iff every problem finished, SLM_ERR_NOT_CONVERGED with ALL outputs valid otherwise.
+ * Size: count * n_eta <= SLM_L0_GRID_MAX = 128 problems.  Each problem gets max(1, 2 CUs / problems) workgroups, so on a device
+ * of at least 64 CUs the grid is resident at once.  On a smaller device the call still RUNS: every problem keeps one workgroup,
+ * the grid exceeds what the device holds and the surplus workgroups start as others leave -- no workgroup waits on another.
+ * Refusals, all before a device is touched: those of slm_solve_l0_profile_batch and of the entry the kind generalises;
+ * n_eta < 1, a negative or non-finite etas[e], eta_kind outside {0, 1}, T with eta_kind 1, count * n_eta above the cap (the
+ * message names it) (SLM_ERR_BAD_ARG); more than 64 search columns or groups, a row-sharded dataset (SLM_ERR_UNSUPPORTED).
+ * Not here: wide, constrained or exclusion-bound problems, a ridge term beside the l1 term, several T.
+ */
+#define SLM_L0_GRID_MAX 128
+int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
+                              const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_eta, const double* etas /* [n_eta] */,
+                              int32_t eta_kind /* 0 ridge, 1 l1 */, double alpha_min, int32_t max_groups,
+                              const double* T /* ps*ps or NULL; NULL with eta_kind 1 */, double big_M,
+                              const uint64_t* need /* search-group masks or NULL */, int64_t max_nodes /* per problem; <=0: default */,
+                              double* beta_out /* [count*n_eta][max_groups+1][ps] */,
+                              double* intercept_out /* [count*n_eta][max_groups+1] or NULL */,
+                              uint64_t* support_out /* [count*n_eta][max_groups+1] */, double* value_out /* [count*n_eta][max_groups+1] */,
+                              int64_t* nodes_out /* [count*n_eta] or NULL */, slm_point_info* info /* [count*n_eta] or NULL */);
 
 /*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant

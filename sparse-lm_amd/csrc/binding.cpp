@@ -453,11 +453,14 @@ py::tuple solve_l0_l1_profile_wide(uintptr_t ds, int64_t p, double alpha_min, in
 // slm_solve_l0_profile_batch: the profiles of several row sets of one dataset from one launch.  row_weights: a sequence of
 // arrays of n weights or None; n_effs: as many integers.  Returns (coefficients [count][max_groups + 1][ps], intercepts
 // [count][max_groups + 1], support masks, values, nodes [count], records as bytes, status); ps = p - 1 with an intercept.
-py::tuple solve_l0_profile_batch(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs,
-                                 bool intercept, double alpha_min, int32_t max_groups, double eta, const py::object& T, double big_M,
-                                 const py::object& need, int64_t max_nodes) {
+// etas == nullptr: that entry, with its one ridge eta.  Otherwise slm_solve_l0_profile_grid: n_eta weights of kind eta_kind per row
+// set, every output's leading dimension count * n_eta (problem r * n_eta + e: row set r with etas[e]).
+py::tuple l0_profile_rows(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
+                          const arr_d* etas, int32_t eta_kind, double alpha_min, int32_t max_groups, double eta, const py::object& T,
+                          double big_M, const py::object& need, int64_t max_nodes) {
   if (max_groups < 0) throw py::value_error("max_groups must be >= 0");
   const py::ssize_t count = (py::ssize_t)py::len(row_weights);
+  const py::ssize_t n_eta = etas ? (py::ssize_t)etas->size() : 1;
   if ((py::ssize_t)py::len(n_effs) != count) throw py::value_error("row_weights and n_effs differ in length");
   const int64_t ps = intercept && p > 0 ? p - 1 : p;
   Keep keep;
@@ -470,7 +473,9 @@ py::tuple solve_l0_profile_batch(uintptr_t ds, int64_t p, int64_t n, const py::s
     wp[(size_t)b] = vector_arg(row_weights[b], n, "row_weights", keep);
     ne[(size_t)b] = n_effs[b].cast<int64_t>();
   }
-  const py::ssize_t rows = (py::ssize_t)max_groups + 1, cnt = count > 0 ? count : 1;  // (count 0: the engine refuses it)
+  // (count 0, no eta, more problems than any call takes: the engine refuses them, the outputs only have to exist)
+  const py::ssize_t rows = (py::ssize_t)max_groups + 1;
+  const py::ssize_t cnt = count > 0 && n_eta > 0 && count * n_eta <= 4 * SLM_L0_GRID_MAX ? count * n_eta : 1;
   py::array_t<double> beta({cnt, rows, (py::ssize_t)ps}), icpt({cnt, rows}), value({cnt, rows});
   py::array_t<uint64_t> support({cnt, rows});
   py::array_t<int64_t> nodes(cnt);
@@ -483,11 +488,26 @@ py::tuple solve_l0_profile_batch(uintptr_t ds, int64_t p, int64_t n, const py::s
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = slm_solve_l0_profile_batch(reinterpret_cast<slm_dataset*>(ds), (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, alpha_min,
-                                    max_groups, eta, Tp, big_M, needp, max_nodes, bp, ip, sup, vp, np_, rec);
+    if (etas)
+      rc = slm_solve_l0_profile_grid(reinterpret_cast<slm_dataset*>(ds), (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, (int32_t)n_eta,
+                                     etas->data(), eta_kind, alpha_min, max_groups, Tp, big_M, needp, max_nodes, bp, ip, sup, vp, np_, rec);
+    else
+      rc = slm_solve_l0_profile_batch(reinterpret_cast<slm_dataset*>(ds), (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, alpha_min,
+                                      max_groups, eta, Tp, big_M, needp, max_nodes, bp, ip, sup, vp, np_, rec);
   }
   if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
   return py::make_tuple(beta, icpt, support, value, nodes, info, rc);
+}
+py::tuple solve_l0_profile_batch(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs,
+                                 bool intercept, double alpha_min, int32_t max_groups, double eta, const py::object& T, double big_M,
+                                 const py::object& need, int64_t max_nodes) {
+  return l0_profile_rows(ds, p, n, row_weights, n_effs, intercept, nullptr, 0, alpha_min, max_groups, eta, T, big_M, need, max_nodes);
+}
+// slm_solve_l0_profile_grid: the tuple of solve_l0_profile_batch with count * n_eta problems.
+py::tuple solve_l0_profile_grid(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs,
+                                bool intercept, const arr_d& etas, int32_t eta_kind, double alpha_min, int32_t max_groups,
+                                const py::object& T, double big_M, const py::object& need, int64_t max_nodes) {
+  return l0_profile_rows(ds, p, n, row_weights, n_effs, intercept, &etas, eta_kind, alpha_min, max_groups, 0.0, T, big_M, need, max_nodes);
 }
 
 }  // namespace
@@ -513,6 +533,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_xb_wide", &solve_l0_wide<true>);
   m.def("solve_l0_profile_wide", &solve_l0_profile_wide);
   m.def("solve_l0_profile_batch", &solve_l0_profile_batch);
+  m.def("solve_l0_profile_grid", &solve_l0_profile_grid);
   m.def("solve_l0_l1_profile", &solve_l0_l1_profile);
   m.def("solve_l0_l1_profile_wide", &solve_l0_l1_profile_wide);
   m.def("path_extrapolation", [](const arr_d& pts) {

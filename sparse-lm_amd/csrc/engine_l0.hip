@@ -1,7 +1,7 @@
 // Host side of the MI355X fit engine, sixth unit: the exact l0 estimators (csrc/l0_kernels.hpp) -- the reference's
 // mixed-integer family (reference src/sparselm/model/_miqp/_best_subset.py, _regularized_l0.py), which it hands to
-// Gurobi or SCIP through cvxpy.  Eleven entries, four functions (solve_l0_impl, solve_l0_profile_impl, solve_l0_con_impl,
-// solve_l0_profile_batch_impl), ONE
+// Gurobi or SCIP through cvxpy.  Twelve entries, four functions (solve_l0_impl, solve_l0_profile_impl, solve_l0_con_impl,
+// solve_l0_profile_grid_impl), ONE
 // pipeline, everything around the launch on the host (p <= 128: microseconds):
 //   check    l0_check_args, and what a mode adds: whatever can be refused is refused before a device is touched
 //   prepare  l0_prepare: the dataset's own Gram (engine_cov.hip; l0_fetch_gram), then l0_order: the search order, H = G + 2 eta T, c
@@ -30,6 +30,9 @@
 //   slm_solve_l0_profile_batch  the BATCH instantiation: the profiles of up to 16 row sets of the dataset (CV folds, all rows) from
 //       one launch.  Per problem the profile's own pieces (l0_fetch_gram, l0_order, l0_profile_seed, l0_profile_collect) on its copy
 //       of the block (l0_batch_layout of l0_host.hpp); an intercept column is eliminated per row set (l0_eliminate_last).
+//   slm_solve_l0_profile_grid  the BATCH instantiations, with or without L1: one problem per (row set, eta), up to L0_GRID_MAX, from
+//       one launch.  Gram and elimination once per row set; order, seed, (l1: the bound) and the copy of the block per problem.
+//       slm_solve_l0_profile_batch is its call with one ridge eta.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -369,7 +372,8 @@ int solve_l0_impl(slm_dataset* ds, double alpha, int32_t max_groups, double eta,
 }
 
 // The profile's pieces around its launch, shared by the single entries and the batched one.
-constexpr int kL0BatchMax = 16;  // problems of one batched launch: what the dataset's Gram store holds
+constexpr int kL0BatchMax = 16;  // row sets of one batched launch: what the dataset's Gram store holds
+static_assert(kL0BatchMax == L0_GRID_ROW_SETS && SLM_L0_GRID_MAX == L0_GRID_MAX, "the header, the host logic and this unit name one set of limits");
 template <class Mask>
 struct L0ProfileWork {
   L0ProblemT<Mask> P;
@@ -489,18 +493,37 @@ int solve_l0_profile_impl(slm_dataset* ds, double alpha_min, int32_t max_groups,
   return SLM_OK;
 }
 
-// slm_solve_l0_profile_batch: the profiles of `count` row sets of one dataset from ONE launch of the kernel's BATCH instantiation.
-// Per problem today's pipeline, piece by piece: its Gram (fetched before anything else: l0_fetch_gram), the intercept column
-// eliminated (l0_eliminate_last), l0_order, l0_profile_seed, its copy of the block (l0_batch_layout, l0_fill_image,
-// l0_profile_seed_image, q_all in L0_BATCH_QALL); then one upload, one launch, one read-back of the block, and
-// l0_profile_collect per problem.
-int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs, int32_t intercept,
-                                double alpha_min, int32_t max_groups, double eta, const double* T, double big_M, const uint64_t* need,
-                                int64_t max_nodes, double* beta_out, double* intercept_out, uint64_t* support_out, double* value_out,
-                                int64_t* nodes_out, slm_point_info* info) {
+// slm_solve_l0_profile_grid, slm_solve_l0_profile_batch: the profiles of `count` row sets of one dataset at n_eta weights each from
+// ONE launch of the kernel's BATCH instantiation (l1: the L1 one).  Problem b = r * n_eta + e (l0_grid_index) is row set r with etas[e]:
+// a ridge weight (H = G_r + 2 eta T) or an l1 weight (H = G_r).  Per row set, once: its Gram (fetched before anything else:
+// l0_fetch_gram), the intercept column eliminated (l0_eliminate_last).  Per problem today's pipeline, piece by piece: l0_order,
+// l0_profile_seed, its copy of the block (l0_batch_layout, l0_fill_image, l0_profile_seed_image, the subtree cut's bound in
+// L0_BATCH_QALL, the l1 weight in L0_BATCH_ETA); then one upload, one launch, one read-back of the block, and l0_profile_collect
+// per problem.  grid = false is slm_solve_l0_profile_batch: one ridge eta, checked and reported in that entry's own words.
+int solve_l0_profile_grid_impl(bool grid, slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                               int32_t intercept, int32_t n_eta, const double* etas, int32_t eta_kind, double alpha_min, int32_t max_groups,
+                               const double* T, double big_M, const uint64_t* need, int64_t max_nodes, double* beta_out,
+                               double* intercept_out, uint64_t* support_out, double* value_out, int64_t* nodes_out, slm_point_info* info) {
   using Mask = unsigned long long;
   int ps = 0, ng = 0;
   if (count < 1 || count > kL0BatchMax) return fail(SLM_ERR_BAD_ARG, "count must be 1 .. %d, the Gram store's capacity (got %d)", kL0BatchMax, count);
+  if (grid) {
+    int which = 0;
+    switch (l0_grid_check(count, n_eta, etas, eta_kind, T != nullptr, &which)) {
+      case L0_GRID_OK: break;
+      case L0_GRID_N_ETA: return fail(SLM_ERR_BAD_ARG, "n_eta must be >= 1 (got %d)", n_eta);
+      case L0_GRID_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+      case L0_GRID_KIND: return fail(SLM_ERR_BAD_ARG, "eta_kind must be 0 (ridge) or 1 (l1) (got %d)", eta_kind);
+      case L0_GRID_T_WITH_L1: return fail(SLM_ERR_BAD_ARG, "T goes with the ridge weights (eta_kind 0): the l1 profile has no ridge term");
+      case L0_GRID_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%d] must be finite and >= 0", which);
+      case L0_GRID_PROBLEMS:
+        return fail(SLM_ERR_BAD_ARG, "count * n_eta must be at most %d problems (got %d x %d = %lld)", L0_GRID_MAX, count, n_eta,
+                    (long long)count * n_eta);
+      default: return fail(SLM_ERR_BAD_ARG, "count must be 1 .. %d, the Gram store's capacity (got %d)", kL0BatchMax, count);
+    }
+  }
+  const bool l1 = eta_kind == 1;
+  const int problems = count * n_eta;
   if (!support_out || !value_out || !row_weights || !n_effs) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   const int drop = intercept != 0 ? 1 : 0;
   if (ds && drop) {  // the ones column: last, alone in the last group
@@ -510,7 +533,7 @@ int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* co
     for (int64_t j = 0; j < p && alone && !ds->h_gid.empty(); ++j) alone = (ds->h_gid[(size_t)j] == G - 1) == (j == p - 1);
     if (!alone) return fail(SLM_ERR_BAD_ARG, "intercept: the last column must be alone in the last group");
   }
-  SLM_TRY(l0_check_args<Mask>(ds, beta_out, alpha_min, "alpha_min", eta, 0.0, big_M, T, need, &ps, &ng, drop));
+  SLM_TRY(l0_check_args<Mask>(ds, beta_out, alpha_min, "alpha_min", grid ? 0.0 : etas[0], 0.0, big_M, T, need, &ps, &ng, drop));
   const int p = ps + drop;
   const int rows = max_groups < 0 ? 0 : (int)max_groups;
   const int K = std::min(rows, ng);
@@ -548,10 +571,11 @@ int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* co
   if (all_given) SLM_TRY(slm_dataset_covariance_folds(ds, row_weights, n_effs, count));
   std::vector<double> fp(2 * (size_t)count);
   SLM_TRY(cov_fingerprints(ds, wdev.data(), count, fp.data()));
-  std::vector<L0ProfileWork<Mask>> W((size_t)count);
+  std::vector<L0ProfileWork<Mask>> W((size_t)problems);
   std::vector<double> xmean((size_t)count * (size_t)ps, 0.0), ymean((size_t)count, 0.0);
+  std::vector<double> bound((size_t)problems, 0.0);  // what the subtree cut takes for the value of all columns: q_all, or the l1 bound
   for (int b = 0; b < count; ++b) {
-    L0ProblemT<Mask>& P = W[(size_t)b].P;
+    L0ProblemT<Mask>& P = W[(size_t)l0_grid_index(b, 0, n_eta)].P;  // (the row set's Gram lands in its first problem and is copied on)
     int entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
     if (entry < 0) {  // not from the folds' call (or pushed out of the store by a later one): built here, fetched at once
       SLM_TRY(slm_dataset_covariance(ds, row_weights[b], row_weights[b] ? n_effs[b] : 0));
@@ -565,20 +589,31 @@ int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* co
       P.G.swap(Gs);
       P.cvec.swap(cs);
     }
-    l0_order(ds, ps, ng, eta, T, need, P);
-    l0_profile_seed(W[(size_t)b], ps, K, big_M);
+    for (int e = 0; e < n_eta; ++e) {
+      const int at = l0_grid_index(b, e, n_eta);
+      L0ProblemT<Mask>& Q = W[(size_t)at].P;
+      if (e > 0) {
+        Q.G = P.G;
+        Q.cvec = P.cvec;
+        Q.yy = P.yy;
+      }
+      l0_order(ds, ps, ng, l1 ? 0.0 : etas[e], T, need, Q);
+      l0_profile_seed(W[(size_t)at], ps, K, big_M, l1 ? etas[e] : 0.0);
+      bound[(size_t)at] = l1 && etas[e] > 0.0 ? l0_l1_lower_bound(Q.H.data(), Q.c.data(), ps, Q.yy, etas[e], Q.q_all) : Q.q_all;
+    }
   }
 
-  // ---- the block: `count` copies of the profile layout; one upload, ONE launch, one read-back ------------------------------------
-  const L0BatchLayout B = l0_batch_layout(count, ps, ng, eng->cus, 1, 64, L0_PROFILE_WORDS, L0_PREFIX, L0_WAVES);
+  // ---- the block: one copy of the profile layout per problem; one upload, ONE launch, one read-back -------------------------------
+  const L0BatchLayout B = l0_grid_layout(count, n_eta, ps, ng, eng->cus, 64, L0_PROFILE_WORDS, L0_PREFIX, L0_WAVES);
   const L0Layout& y = B.one;
   std::vector<unsigned long long> h(B.words, 0ull);
-  for (int b = 0; b < count; ++b) {
+  for (int b = 0; b < problems; ++b) {
     const L0ProblemT<Mask>& P = W[(size_t)b].P;
     unsigned long long* hb = h.data() + B.at(b);
     l0_fill_image(y, P.H.data(), P.c.data(), ps, P.needo, P.gstart, hb);
     l0_profile_seed_image(W[(size_t)b], hb);
-    memcpy(hb + L0_BATCH_QALL, &P.q_all, sizeof(double));
+    memcpy(hb + L0_BATCH_QALL, &bound[(size_t)b], sizeof(double));
+    if (l1) memcpy(hb + L0_BATCH_ETA, &etas[l0_grid_eta(b, n_eta)], sizeof(double));
   }
   L0Args k;
   memset(&k, 0, sizeof(k));
@@ -599,7 +634,8 @@ int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* co
     k.c = reinterpret_cast<const double*>(dev + y.off_c);
     k.need = dev + y.off_need;
     k.gstart = reinterpret_cast<const long long*>(dev + y.off_gs);
-    hipLaunchKernelGGL((l0_search_kernel<false, true, false, false, false, true>), dim3((unsigned)B.grid()), dim3(64 * L0_WAVES), 0, s, k);
+    const L0Kernel kernel = l1 ? l0_search_kernel<true, true, false, false, false, true> : l0_search_kernel<false, true, false, false, false, true>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B.grid()), dim3(64 * L0_WAVES), 0, s, k);
     SLM_TRY(check_launch());
     // one read-back: the whole block (the results are most of every copy; H, c, need and the group starts come back as they went)
     HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(unsigned long long) * B.words, hipMemcpyDeviceToHost, s));
@@ -609,22 +645,28 @@ int solve_l0_profile_batch_impl(slm_dataset* ds, int32_t count, const double* co
   // ---- per problem: the winners, the table, the record -------------------------------------------------------------------------------
   const size_t tab = (size_t)rows + 1;
   int unfinished = 0, first = -1;
-  for (int b = 0; b < count; ++b) {
+  for (int b = 0; b < problems; ++b) {
     const unsigned long long* hb = h.data() + B.at(b);
+    const int r = l0_grid_row_set(b, n_eta);
+    const double eta_l1 = l1 ? etas[l0_grid_eta(b, n_eta)] : 0.0;
     const bool finished = hb[L0_ABORTED] == 0;
     if (!finished && unfinished++ == 0) first = b;
     double* beta_b = beta_out + (size_t)b * tab * ps;
     l0_profile_collect(W[(size_t)b], hb, y, ps, rows, K, alpha_min, big_M, finished, beta_b, support_out + (size_t)b * tab, value_out + (size_t)b * tab,
-                       nodes_out ? nodes_out + b : nullptr, info ? info + b : nullptr);
+                       nodes_out ? nodes_out + b : nullptr, info ? info + b : nullptr, eta_l1);
+    if (info && l1) {
+      info[b].L = bound[(size_t)b];
+      info[b].rejects = l0_count32(hb[L0_DESCENTS]);
+    }
     for (size_t size = 0; size < tab && intercept_out; ++size) {
-      double t = drop ? ymean[(size_t)b] : 0.0;
-      for (int j = 0; j < ps && drop; ++j) t -= xmean[(size_t)b * ps + j] * beta_b[size * ps + j];
+      double t = drop ? ymean[(size_t)r] : 0.0;
+      for (int j = 0; j < ps && drop; ++j) t -= xmean[(size_t)r * ps + j] * beta_b[size * ps + j];
       intercept_out[(size_t)b * tab + size] = t;
     }
   }
   if (unfinished)
     return fail(SLM_ERR_NOT_CONVERGED, "the node budget (%lld per problem) ran out in %d of %d problems (the first: %d): their tables of "
-                "incumbents are returned", k.max_nodes, unfinished, count, first);
+                "incumbents are returned", k.max_nodes, unfinished, problems, first);
   return SLM_OK;
 }
 
@@ -881,6 +923,17 @@ extern "C" int slm_solve_l0_profile_batch(slm_dataset* ds, int32_t count, const 
                                           int32_t intercept, double alpha_min, int32_t max_groups, double eta, const double* T, double big_M,
                                           const uint64_t* need, int64_t max_nodes, double* beta_out, double* intercept_out,
                                           uint64_t* support_out, double* value_out, int64_t* nodes_out, slm_point_info* info) {
-  return solve_l0_profile_batch_impl(ds, count, row_weights, n_effs, intercept, alpha_min, max_groups, eta, T, big_M, need, max_nodes, beta_out,
-                                     intercept_out, support_out, value_out, nodes_out, info);
+  return solve_l0_profile_grid_impl(false, ds, count, row_weights, n_effs, intercept, 1, &eta, 0, alpha_min, max_groups, T, big_M, need, max_nodes,
+                                    beta_out, intercept_out, support_out, value_out, nodes_out, info);
+}
+
+// The profiles of `count` row sets at n_eta weights each -- ridge (eta_kind 0) or l1 (eta_kind 1) -- from one launch: problem
+// r * n_eta + e is row set r with etas[e].
+extern "C" int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                                         int32_t intercept, int32_t n_eta, const double* etas, int32_t eta_kind, double alpha_min,
+                                         int32_t max_groups, const double* T, double big_M, const uint64_t* need, int64_t max_nodes,
+                                         double* beta_out, double* intercept_out, uint64_t* support_out, double* value_out,
+                                         int64_t* nodes_out, slm_point_info* info) {
+  return solve_l0_profile_grid_impl(true, ds, count, row_weights, n_effs, intercept, n_eta, etas, eta_kind, alpha_min, max_groups, T, big_M, need,
+                                    max_nodes, beta_out, intercept_out, support_out, value_out, nodes_out, info);
 }

@@ -14,7 +14,8 @@
 // the file holds what every entry's launch shares (tests/l0_launch_host_test.cpp): the layout of the device block, the
 // winner among the waves' results, the way back to the caller's groups and columns, and the loss from the Gram.  The batched
 // profile (slm_solve_l0_profile_batch; tests/l0_batch_host_test.cpp) adds the layout of several problems in one block and the
-// elimination of an intercept column from a Gram.
+// elimination of an intercept column from a Gram.  The profile grid (slm_solve_l0_profile_grid; tests/l0_grid_host_test.cpp) adds
+// the problem index over (row set, eta), its argument checks and the layout at up to L0_GRID_MAX problems.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -1042,6 +1043,36 @@ inline L0BatchLayout l0_batch_layout(int count, int p, int ng, int cus, int mask
   B.stride = B.one.words;
   B.words = B.stride * (size_t)count;
   return B;
+}
+
+// The profile grid (slm_solve_l0_profile_grid): one problem per (row set, eta), problem b = r * n_eta + e the row set r with
+// etas[e] -- the row sets outermost, so that a row set's problems (one Gram, n_eta orders and seeds) lie side by side and every
+// output's leading dimension is count * n_eta in that order.  At most L0_GRID_MAX problems: l0_batch_layout gives each
+// max(1, 2 cus / problems) workgroups, so on a device of at least 64 CUs the whole grid is resident at once; below that every
+// problem keeps its one workgroup, the grid exceeds 2 cus and runs in waves -- nothing in the kernel waits on another workgroup.
+constexpr int L0_GRID_MAX = 128;      // problems of one grid launch
+constexpr int L0_GRID_ROW_SETS = 16;  // row sets of one call: what the dataset's Gram store holds
+constexpr int l0_grid_index(int r, int e, int n_eta) { return r * n_eta + e; }
+constexpr int l0_grid_row_set(int b, int n_eta) { return b / n_eta; }
+constexpr int l0_grid_eta(int b, int n_eta) { return b % n_eta; }
+// What the grid entry refuses on top of the entries it generalises, in this order (0: nothing); *which: the offending eta.
+enum L0GridRefusal { L0_GRID_OK = 0, L0_GRID_COUNT, L0_GRID_N_ETA, L0_GRID_NULL, L0_GRID_KIND, L0_GRID_T_WITH_L1, L0_GRID_ETA, L0_GRID_PROBLEMS };
+inline L0GridRefusal l0_grid_check(long long count, long long n_eta, const double* etas, int eta_kind, bool has_T, int* which = nullptr) {
+  if (count < 1 || count > L0_GRID_ROW_SETS) return L0_GRID_COUNT;
+  if (n_eta < 1) return L0_GRID_N_ETA;
+  if (!etas) return L0_GRID_NULL;
+  if (eta_kind != 0 && eta_kind != 1) return L0_GRID_KIND;
+  if (eta_kind == 1 && has_T) return L0_GRID_T_WITH_L1;
+  if (count * n_eta > L0_GRID_MAX) return L0_GRID_PROBLEMS;  // (before etas is read: n_eta is then within bounds the caller meant)
+  for (long long e = 0; e < n_eta; ++e)
+    if (!(etas[e] >= 0.0) || !std::isfinite(etas[e])) {
+      if (which) *which = (int)e;
+      return L0_GRID_ETA;
+    }
+  return L0_GRID_OK;
+}
+inline L0BatchLayout l0_grid_layout(int count, int n_eta, int p, int ng, int cus, int slots, int ctl_words, int prefix, int block_waves) {
+  return l0_batch_layout(count * n_eta, p, ng, cus, 1, slots, ctl_words, prefix, block_waves);
 }
 
 // Elimination of an intercept column from the Gram of [X | 1] on one row set (weights w, sum w = n_eff):

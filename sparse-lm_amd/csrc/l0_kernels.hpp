@@ -121,8 +121,9 @@ constexpr int L0_PREFIX = 16;      // groups decided by the ticket
 constexpr int L0_BATCH = 256;      // nodes between two bumps of the global counter
 // control words (unsigned 64-bit each), zeroed / seeded by the host before the launch
 constexpr int L0_TICKET = 0, L0_INCUMBENT = 1, L0_NODES = 2, L0_STOP = 3, L0_ABORTED = 4, L0_DESCENTS = 5, L0_CAPACITY = 6, L0_UNSETTLED = 7,
-              L0_UNSETTLED_COUNT = 8, L0_BATCH_QALL = 9, L0_CTL_WORDS = 10;
+              L0_UNSETTLED_COUNT = 8, L0_BATCH_QALL = 9, L0_BATCH_ETA = 10, L0_CTL_WORDS = 11;
 // (L0_BATCH_QALL, batched profile only: the bits of the problem's own q_all, written by the host and only read on the device)
+// (L0_BATCH_ETA, batched l1 profile only: the bits of the problem's own l1 weight, written by the host and only read on the device)
 // (L0_CAPACITY, wide mode only: seeded with all ones, lowered to c_min + 1 by a wave that refused an include for capacity)
 // (L0_UNSETTLED, constrained mode only: seeded with all ones, lowered to the key of D + alpha |S| by a wave whose candidate ran
 //  out of sweeps; L0_UNSETTLED_COUNT counts them.  L0_DESCENTS counts the candidates valued in l1 and constrained mode.)
@@ -218,19 +219,23 @@ static __device__ __forceinline__ double l0_wave_max(double v) {
 // WIDE = true: up to 128 columns and groups (see the head of the file); what it adds sits under if constexpr or behind Mask.
 // CON = true: linear constraints and a per-column box (see the head of the file); everything it adds sits under if constexpr.
 // XB = true: the exclusion bound (see the head of the file); everything it adds sits under if constexpr.
-// BATCH = true (slm_solve_l0_profile_batch; narrow profile only): up to 16 problems of one shape in one launch.  The block is
+// BATCH = true (slm_solve_l0_profile_batch, slm_solve_l0_profile_grid; narrow profile only, with or without L1): up to 16 problems
+// (the grid entry: up to L0_GRID_MAX = 128, one per (row set, eta)) of one shape in one launch.  The block is
 // `count` copies of the single-problem profile layout at a constant stride (l0_batch_layout of l0_host.hpp); a workgroup
 // belongs to problem blockIdx.x / batch_blocks, moves every base pointer to that copy and numbers its waves within the
 // problem.  Ticket counter, node counter, stop and aborted words, the 64 incumbents and q_all (L0_BATCH_QALL) are the copy's
 // own, so a problem that runs out of its budget stops its own workgroups alone, and waves of different problems share no
 // word: no new barrier, no new loop.  A workgroup whose problem has no ticket left exits (it is not moved to another
-// problem: that would re-stage H behind a barrier).  Everything it adds sits under if constexpr.
+// problem: that would re-stage H behind a barrier).  With L1 the l1 weight is the copy's own too (L0_BATCH_ETA, read once per
+// workgroup; a.eta_l1 stays what the other instantiations read), as L0_DESCENTS already is; q_all then holds the problem's l1
+// bound.  Nothing waits on another workgroup, so a grid of more workgroups than the device holds at once runs in waves.
+// Everything it adds sits under if constexpr.  L1 + PROFILE + BATCH: 231 VGPRs, no AGPRs, no scratch, 34 056 B of LDS, 2 waves/SIMD.
 template <bool L1, bool PROFILE = false, bool WIDE = false, bool CON = false, bool XB = false, bool BATCH = false>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args a) {
   static_assert(!(L1 && WIDE) || PROFILE, "a wide l1 search exists only as a profile (a plain one needs a dynamic capacity rule on the support's column list)");
   static_assert(!(CON && (L1 || PROFILE || WIDE)), "the constrained mode stands alone");
   static_assert(!(XB && (L1 || PROFILE || CON)), "the exclusion bound serves the plain search, narrow and wide");
-  static_assert(!(BATCH && (!PROFILE || L1 || WIDE || CON || XB)), "a batch holds narrow profile searches and nothing else");
+  static_assert(!(BATCH && (!PROFILE || WIDE || CON || XB)), "a batch holds narrow profile searches, with or without an l1 term, and nothing else");
   if constexpr (BATCH) {  // the workgroup's problem (wave-uniform): every base pointer moves to that problem's copy of the block
     const size_t at = (size_t)(blockIdx.x / (unsigned)a.batch_blocks) * (size_t)a.batch_stride;
     a.ctl += at;
@@ -323,6 +328,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
   const double alpha = a.alpha, big_M = a.big_M;
   double q_all = a.q_all;
   if constexpr (BATCH) q_all = __longlong_as_double((long long)a.ctl[L0_BATCH_QALL]);  // (the folds' c differ: so does the bound)
+  [[maybe_unused]] double eta_own = 0.0;  // batched l1 profile: the problem's own l1 weight
+  if constexpr (BATCH && L1) eta_own = __longlong_as_double((long long)a.ctl[L0_BATCH_ETA]);
   // lane r: row r of L (entries below the diagonal), 1 / L[r][r], w[r], the column it stands for
   double Lrow[L0_PMAX];
 #pragma unroll
@@ -557,7 +564,8 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_search_kernel(L0Args 
               // soft-threshold, from the back-substituted beta (clipped; zero on the columns the pivot rule skipped).
               // Lane r keeps beta_r and the gradient entry (H beta - c)_r of the support's r-th column.
               ++descents_local;
-              const double eta1 = a.eta_l1;
+              double eta1 = a.eta_l1;
+              if constexpr (BATCH) eta1 = eta_own;
               double b1 = 0.0;
               for (int k = 0; k < m; ++k) {
                 const int ck = __builtin_amdgcn_readlane(mycol, k);

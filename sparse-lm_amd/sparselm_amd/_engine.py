@@ -46,6 +46,7 @@ FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plai
 
 COMM_ID_BYTES = 128
 ABI_VERSION = 24  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
+L0_GRID_MAX = 128  # SLM_L0_GRID_MAX: the problems of one slm_solve_l0_profile_grid call
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -94,6 +95,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_wide",
     "slm_solve_l0_profile_wide",
     "slm_solve_l0_profile_batch",
+    "slm_solve_l0_profile_grid",
     "slm_solve_l0_l1_profile",
     "slm_solve_l0_l1_profile_wide",
     "slm_solve_l0_constrained",
@@ -365,6 +367,7 @@ def load_library():
             "slm_solve_l0_l1_profile": [vp, dbl, i32, dbl, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_l1_profile_wide": [vp, dbl, i32, dbl, dbl, vp, i64, vp, vp, vp, P(i64), P(_PointInfo)],
             "slm_solve_l0_profile_batch": [vp, i32, vp, vp, i32, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_profile_grid": [vp, i32, vp, vp, i32, i32, vp, i32, dbl, i32, vp, dbl, vp, i64, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_xb": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, P(C.c_uint64), P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_xb_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_constrained": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, i32, vp, vp, vp, vp, i32, vp, P(C.c_uint64), P(dbl), P(i64),
@@ -1559,6 +1562,23 @@ class Dataset:
         has one mask per search group, ``ps = p - 1`` columns in ``n_groups - 1`` groups.  ``max_nodes`` is each problem's
         budget.  Returns ``(betas [count, K + 1, ps], intercepts [count, K + 1], support masks [count, K + 1], values
         [count, K + 1], infos)``; ``infos`` is one dict per problem as ``solve_l0_profile`` gives it."""
+        return self._l0_profile_rows(row_weights, n_effs, intercept, None, 0, alpha_min, max_groups, eta, T, big_M, need, max_nodes, binding)
+
+    def solve_l0_profile_grid(self, row_weights, n_effs, etas, eta_kind=0, intercept=False, alpha_min=0.0, max_groups=None, T=None,
+                              big_M=100.0, need=None, max_nodes=0, binding=None):
+        """``slm_solve_l0_profile_grid``: ``solve_l0_profile_batch`` at several weights ``etas`` per row set, from ONE launch.
+        ``eta_kind`` 0: ridge weights, every problem is ``solve_l0_profile``'s; 1: l1 weights, every problem is
+        ``solve_l0_l1_profile``'s (``T`` must be None).  Problem ``r * len(etas) + e`` is row set ``r`` with ``etas[e]``; at most
+        ``L0_GRID_MAX`` = 128 problems.  Returns what ``solve_l0_profile_batch`` returns with the leading dimension
+        ``count * len(etas)``; with l1 weights every ``info`` also holds ``descents`` and its ``q_all`` is the l1 lower bound the
+        cut used."""
+        etas_ = np.ascontiguousarray(etas, dtype=np.float64).reshape(-1)
+        return self._l0_profile_rows(row_weights, n_effs, intercept, etas_, int(eta_kind), alpha_min, max_groups, 0.0, T, big_M, need,
+                                     max_nodes, binding)
+
+    def _l0_profile_rows(self, row_weights, n_effs, intercept, etas, eta_kind, alpha_min, max_groups, eta, T, big_M, need, max_nodes,
+                         binding):
+        """Both entries over row sets: ``etas`` None is the batched profile with its one ridge ``eta``, an array the grid."""
         drop = 1 if intercept else 0
         ps, gs = self.p - drop, self.n_groups - drop
         K = gs if max_groups is None else int(max_groups)
@@ -1575,20 +1595,33 @@ class Dataset:
             need_ = np.ascontiguousarray([int(v) for v in need], dtype=np.uint64)
             if need_.shape != (gs,):
                 raise ValueError(f"need must have {gs} entries")
-        tail = (bool(intercept), float(alpha_min), K, float(eta), T_, float(big_M), need_, int(max_nodes))
         ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
         ne = np.array(nes or [0], dtype=np.int64)
-        cnt = max(1, count)
+        if etas is None:
+            name, problems = "solve_l0_profile_batch", count
+            tail = (bool(intercept), float(alpha_min), K, float(eta), T_, float(big_M), need_, int(max_nodes))
+            args = (count, ptrs, ne, int(tail[0])) + tail[1:]
+        else:
+            name, problems = "solve_l0_profile_grid", count * len(etas)
+            if problems > 4 * L0_GRID_MAX:  # (the engine refuses anything above L0_GRID_MAX: the outputs only have to exist)
+                problems = 0
+            tail = (bool(intercept), etas, eta_kind, float(alpha_min), K, T_, float(big_M), need_, int(max_nodes))
+            eta_arr = etas if len(etas) else np.zeros(1)  # (an empty array has no address worth handing over)
+            args = (count, ptrs, ne, int(tail[0]), len(etas), eta_arr, eta_kind) + tail[3:]
+        cnt = max(1, problems)
         (betas, icpts, supports, values, nodes), infos, rc = self._l0_call(
-            "solve_l0_profile_batch", binding, (count, ptrs, ne, int(tail[0])) + tail[1:],
+            name, binding, args,
             [np.empty((cnt, K + 1, ps)), np.empty((cnt, K + 1)), np.empty((cnt, K + 1), dtype=np.uint64), np.empty((cnt, K + 1)),
              np.zeros(cnt, dtype=np.int64)],
-            records=count, binding_args=(self.n, rws, nes) + tail)
+            records=problems, binding_args=(self.n, rws, nes) + tail)
         out = [{
             "nodes": int(nodes[b]), "launches": int(infos[b]["n_iter"]), "q_all": float(infos[b]["L"]),
             "status": "optimal" if int(infos[b]["status"]) == SLM_OK else "node_budget",
             "proven_optimal": int(infos[b]["status"]) == SLM_OK, "box_tol": 1e-12,
-        } for b in range(count)]
+        } for b in range(problems)]
+        if etas is not None and eta_kind == 1:
+            for b in range(problems):
+                out[b]["descents"] = int(infos[b]["rejects"])
         return betas, icpts, supports, values, out
 
 

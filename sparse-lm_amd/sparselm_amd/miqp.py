@@ -10,10 +10,12 @@ that returns the best support of every size, from which best subset at every bou
 ``alpha`` are read off.  ``l0_profile_cv`` / ``L0ProfileCV`` (``model/_l0_cv.py``) do that for every fold of a cross-validation and for
 all rows from one launch, and read a whole grid off the tables.  ``l1l0_profile`` / ``L1L0Profile`` (``model/_l1l0_profile.py``) are the
 profile under an l1 term: ``L1L0`` at every ``alpha`` from one search per ``eta``, up to 128 columns with
-``solver_options={"wide": True}``.
+``solver_options={"wide": True}``.  ``l1l0_profile_cv`` / ``l2l0_profile_cv`` / ``L0ProfileGridCV`` (``model/_l0_grid_cv.py``) cross-validate
+``L1L0`` and ``L2L0`` over (alpha, eta): every (fold, eta) profile from one launch, the grid read off the tables.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
+from .model._l0_grid_cv import L0ProfileGridCV, l1l0_profile_cv, l2l0_profile_cv  # noqa: F401  (CV over (alpha, eta) from one launch; outside __all__)
 from .model._l0_profile import L0Profile, l0_profile  # noqa: F401  (not estimators: outside __all__, which tests pin)
 from .model._l1l0 import L1L0
 from .model._l1l0_profile import L1L0Profile, l1l0_profile  # noqa: F401  (L1L0 at every alpha from one search; outside __all__)

@@ -19,7 +19,8 @@ it is the first of its value.
 Limits: 64 columns and 64 groups -- 128 of each with ``solver_options={"wide": True}``, when ``max_groups <= 64`` and the
 ``max_groups`` largest groups together hold at most 64 columns (a support holds at most 64 columns).  This is the way
 ``L1L0`` reaches more than 64 columns: the estimator itself has no wide mode.  No ridge term, no ``constraints=``, no
-``solver_options["bound"]``, no row-sharded datasets, and not batched over cross-validation folds.
+``solver_options["bound"]``, no row-sharded datasets.  One call is one row set at one ``eta``; every fold of a
+cross-validation at a list of ``eta`` from one launch is ``l1l0_profile_cv`` (``_l0_grid_cv.py``, narrow problems only).
 
 Import path: ``sparselm_amd.miqp`` (``l1l0_profile``, ``L1L0Profile``).
 """

@@ -56,8 +56,15 @@ nodes, descents and ms per call, warm, the median of ``--repeats`` (default 5) w
 the reference's 290 x 66 data (status, nodes, descents, time).  Every call runs under ``--max-nodes`` (a descent costs far more
 than a node, so the default budget of 2^30 nodes would take minutes per call at 25 x 30).  Nothing is promised but what the file states.
 
-``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` / ``--only bound`` / ``--only cv`` / ``--only l1profile`` runs one
-part."""
+Then the profile grid (``sparselm_amd.miqp.l1l0_profile_cv`` / ``l2l0_profile_cv``, ``slm_solve_l0_profile_grid``), written to
+``profiles/l0_grid_cv.txt`` by ``--only gridcv`` (it is not part of a run without ``--only``): at 25 x 20 with five folds and eight
+``eta`` values one ``l1l0_profile_cv`` call (48 problems, one launch) beside the 48 ``l1l0_profile`` calls it replaces, and one
+``l2l0_profile_cv`` call beside the 8 ``l0_profile_cv`` calls it replaces; and the node-bound 45 x 30 split of ``--only cv`` for
+the ridge kind, every problem under ``--max-nodes``.  Whole calls, warm, the variants alternating, medians of ``--repeats``
+(default 5).  Nothing is promised but what the file states; a row where the one launch is slower is written down like any other.
+
+``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` / ``--only bound`` / ``--only cv`` / ``--only l1profile`` /
+``--only gridcv`` runs one part."""
 
 import argparse
 import math
@@ -525,6 +532,136 @@ def l1_profile_section(out_path, repeats, max_nodes):
     say("    (nothing replaces this row: L1L0 itself stops at 64 columns)")
 
 
+def grid_cv_section(out_path, repeats, max_nodes):
+    from sklearn.datasets import make_regression
+    from sklearn.model_selection import KFold, train_test_split
+
+    from sparselm_amd import _engine
+    from sparselm_amd.miqp import l0_profile_cv, l1l0_profile, l1l0_profile_cv, l2l0_profile_cv
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    lines = [f"exact l0 profile grid on {name}, {dev['compute_units']} compute units: (five folds + all rows) x eight eta in one launch",
+             f"(wall time of whole Python calls, each ending in a synchronise; every variant warmed up once, then {repeats} repeats with the",
+             f" variants alternating; median [min .. max]; budget {max_nodes} nodes per problem; big_M = 1000; KFold(5, shuffle=True, random_state=0))", ""]
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    opts = {"max_nodes": max_nodes}
+    cv = KFold(5, shuffle=True, random_state=0)
+
+    def say(line):  # (the file grows line by line: a run that is cut short leaves what it measured)
+        lines.append(line)
+        print(line, flush=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    def measure(variants):
+        walls, last = {k: [] for k in variants}, {}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            for rnd in range(repeats + 1):
+                for k, fn in variants.items():
+                    t0 = time.perf_counter()
+                    last[k] = fn()
+                    if rnd:
+                        walls[k].append(time.perf_counter() - t0)
+        return {k: sorted(v) for k, v in walls.items()}, last
+
+    def fmt(v):
+        return f"{float(np.median(v)):9.4f} [{v[0]:.4f} .. {v[-1]:.4f}]"
+
+    def tables(grid):  # row sets outermost, etas innermost: the engine's order
+        return [(c.profiles_ + [c.full_]) for c in grid.cvs_]
+
+    def report(what_one, what_many, count, walls, same, grid, many_infos):
+        ratio = float(np.median(walls["one"]) / np.median(walls["many"]))
+        spread = max((w[-1] - w[0]) / float(np.median(w)) for w in walls.values())
+        probs = grid.solver_info_["problems"]
+        say(f"    one {what_one} call (1 launch, {len(probs)} problems){'':8s} {fmt(walls['one'])} s")
+        say(f"    the {count} {what_many} calls it replaces{'':18s} {fmt(walls['many'])} s")
+        say(f"    one call / {count} calls: {ratio:.3f} of the median wall time; the run's spread (max - min over the median): {spread:.3f}; same supports "
+            f"and values (1e-9) in all {len(probs)} tables: {same}")
+        say(f"    nodes: one call {sum(p['nodes'] for p in probs)}, the {count} calls {sum(i['nodes'] for i in many_infos)}; finished: one call "
+            f"{sum(p['proven_optimal'] for p in probs)} of {len(probs)}, the {count} calls {sum(i['proven_optimal'] for i in many_infos)} of {len(many_infos)}")
+        if "descents" in probs[0]:
+            say(f"    descents: one call {sum(p['descents'] for p in probs)}, the {count} calls {sum(i['descents'] for i in many_infos)}")
+        if ratio > 1.0 + spread:
+            say(f"    the one call is SLOWER by {100.0 * (ratio - 1.0):.1f} % of the {count} calls' median, more than the run's spread")
+
+    def agree(a, b, alphas=None):
+        """The same table; with ``alphas`` (a table pruned by alpha_min > 0, whose rows need not be the best of their size, or one that
+        saturates under an l1 term): the same answer at each of them, which is what such tables promise."""
+        if alphas is None:
+            return bool(np.array_equal(a.supports_, b.supports_) and np.allclose(a.values_, b.values_, rtol=1e-9, atol=0))
+        rows = [(a.regularized_size(al), b.regularized_size(al)) for al in alphas]
+        return all(np.array_equal(a.supports_[i], b.supports_[j]) and np.isclose(a.values_[i], b.values_[j], rtol=1e-9, atol=0) for i, j in rows)
+
+    # ---- (a), (b) launch-bound: 25 x 20, five folds, eight etas ----------------------------------------------------------------------
+    X, y = make_regression(25, 20, n_informative=10, noise=1.0, random_state=0)
+    var, cinf = float(np.var(y)), float(np.max(np.abs(X.T @ y / X.shape[0])))
+    rels = np.logspace(-2, -0.3, 8)
+    etas = rels * cinf
+    kw = dict(alpha_min=1e-4 * var, big_M=1000, solver_options=opts)
+    sets = [tr for tr, _ in cv.split(X)] + [np.arange(len(y))]
+    walls, last = measure({
+        "one": lambda: l1l0_profile_cv(X, y, etas=etas, cv=cv, **kw),
+        "many": lambda: [[l1l0_profile(X[rows], y[rows], eta=eta, **kw) for rows in sets] for eta in etas],
+    })
+    grid, many = last["one"], last["many"]
+    alphas = np.logspace(-4, 0, 10) * var
+    same = all(agree(a, b, alphas) for ta, tb in zip(tables(grid), many) for a, b in zip(ta, tb))
+    say("(a) l1 kind: 25 x 20, no intercept, etas = logspace(-2, -0.3, 8) ||X^T y / n||_inf, alpha_min = 1e-4 var y")
+    say("    (pruned tables under an l1 term: 'same' compares what they promise, the support and value read at alphas = logspace(-4, 0, 10) var y)")
+    report("l1l0_profile_cv", "l1l0_profile", 48, walls, same, grid, [t.solver_info_ for tb in many for t in tb])
+    per_eta = [sum(t.solver_info_["descents"] for t in ta) for ta in tables(grid)]
+    say(f"    descents per eta, six row sets together, smallest eta first: {per_eta}")
+    say(f"    (every problem has the same {grid.solver_info_['problems'][0]['launches']} launch and an equal share of the workgroups: a problem with few "
+        "descents leaves its share idle while the others run)")
+    say("")
+    kw4 = dict(kw, max_groups=4)
+    walls, last = measure({
+        "one": lambda: l1l0_profile_cv(X, y, etas=etas, cv=cv, **kw4),
+        "many": lambda: [[l1l0_profile(X[rows], y[rows], eta=eta, **kw4) for rows in sets] for eta in etas],
+    })
+    grid, many = last["one"], last["many"]
+    same = all(agree(a, b, alphas) for ta, tb in zip(tables(grid), many) for a, b in zip(ta, tb))
+    say("(a') l1 kind, small: the same with max_groups = 4")
+    report("l1l0_profile_cv", "l1l0_profile", 48, walls, same, grid, [t.solver_info_ for tb in many for t in tb])
+    say("")
+    retas = np.logspace(-2, 1, 8)
+    kw = dict(max_groups=8, big_M=1000, solver_options=opts)
+    walls, last = measure({
+        "one": lambda: l2l0_profile_cv(X, y, etas=retas, cv=cv, **kw),
+        "many": lambda: [l0_profile_cv(X, y, cv=cv, eta=eta, **kw) for eta in retas],
+    })
+    grid, many = last["one"], last["many"]
+    same = all(agree(a, b) for ta, c in zip(tables(grid), many) for a, b in zip(ta, c.profiles_ + [c.full_]))
+    say("(b) ridge kind: 25 x 20, no intercept, etas = logspace(-2, 1, 8), max_groups = 8")
+    report("l2l0_profile_cv", "l0_profile_cv", 8, walls, same, grid, [i for c in many for i in c.solver_info_["problems"]])
+    # ---- (c) node-bound: the 45 x 30 split of profiles/l0_cv.txt, every problem under the budget --------------------------------------------
+    X, y = make_regression(n_samples=60, n_features=30, n_informative=8, noise=40.0, bias=-15.0, random_state=0)
+    X, _, y, _ = train_test_split(X, y, test_size=0.25, random_state=0)
+    retas = np.logspace(-1, 1, 8)
+    kw = dict(alpha_min=1e-3 * float(np.var(y)), big_M=1000, fit_intercept=True, solver_options=opts)
+    walls, last = measure({
+        "one": lambda: l2l0_profile_cv(X, y, etas=retas, cv=cv, **kw),
+        "many": lambda: [l0_profile_cv(X, y, cv=cv, eta=eta, **kw) for eta in retas],
+    })
+    grid, many = last["one"], last["many"]
+    same = all(agree(a, b) for ta, c in zip(tables(grid), many) for a, b in zip(ta, c.profiles_ + [c.full_]))
+    say("")
+    say(f"(c) ridge kind, node-bound: the line-search example's 45 x 30 split, fit_intercept, etas = logspace(-1, 1, 8), alpha_min = 1e-3 var y;")
+    say(f"    a problem that does not finish within {max_nodes} nodes stops with its incumbents (two sets of incumbents need not agree)")
+    report("l2l0_profile_cv", "l0_profile_cv", 8, walls, same, grid, [i for c in many for i in c.solver_info_["problems"]])
+    nb = sum(p["nodes"] for p in grid.solver_info_["problems"])
+    ns = sum(i["nodes"] for c in many for i in c.solver_info_["problems"])
+    say(f"    nodes/s: one call {nb / float(np.median(walls['one'])):.3e}, the 8 calls {ns / float(np.median(walls['many'])):.3e}")
+    say("")
+    say("not measured: the default budget of 2^30 nodes per problem (48 node-bound problems under it take minutes per call); the l1 kind at")
+    say("25 x 30 or on the 45 x 30 split; a device of fewer than 64 compute units, where the 48 problems exceed two workgroups per CU and run in")
+    say("waves; the time workgroups of finished problems idle while other problems run (the engine keeps no such count, so the reading of (a) --")
+    say("the call lasts as long as its heaviest problem on a 48th of the device -- rests on the descent counts alone); GridSearchCV fit by fit.")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-nodes", type=int, default=1 << 24)
@@ -536,8 +673,12 @@ def main():
     ap.add_argument("--cv-out", default=os.path.join(ROOT, "profiles", "l0_cv.txt"))
     ap.add_argument("--l1-profile-out", default=os.path.join(ROOT, "profiles", "l1l0_profile.txt"))
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile"], default=None)
+    ap.add_argument("--grid-cv-out", default=os.path.join(ROOT, "profiles", "l0_grid_cv.txt"))
+    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile", "gridcv"], default=None)
     args = ap.parse_args()
+    if args.only == "gridcv":
+        grid_cv_section(args.grid_cv_out, max(1, args.repeats), args.max_nodes)
+        return
     if args.only == "l1profile":
         l1_profile_section(args.l1_profile_out, max(1, args.repeats), args.max_nodes)
         return
