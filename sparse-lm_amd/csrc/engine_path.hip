@@ -1102,8 +1102,9 @@ static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* c
     hipLaunchKernelGGL(ws_xty_apply_kernel, dim3(WS_KCAP / 16), dim3(512), 0, s, xa);
     if (names) names->add("ws_xty_apply_kernel");
   }
-  hipLaunchKernelGGL(ws_gram_kernel, dim3((unsigned)wa.nblk, (unsigned)wa.n_sets, 1), dim3(WS_GRAM_THREADS), 0, s,
-                     wa);
+  // (no row weights -- the headline and most calls: the instantiation without the weight's load and select)
+  if (wa.rw) hipLaunchKernelGGL(ws_gram_kernel<true>, dim3((unsigned)wa.nblk, (unsigned)wa.n_sets, 1), dim3(WS_GRAM_THREADS), 0, s, wa);
+  else hipLaunchKernelGGL(ws_gram_kernel<false>, dim3((unsigned)wa.nblk, (unsigned)wa.n_sets, 1), dim3(WS_GRAM_THREADS), 0, s, wa);
   if (wa.Gx)  // (zero where this pass builds nothing, so the unconditional all-reduce below is harmless)
     (void)hipMemsetAsync(wa.Gx, 0, sizeof(double) * (size_t)wa.n_sets * WS_KCAP * WS_KCAP, s);
   hipLaunchKernelGGL(ws_gram_reduce_kernel, dim3(WS_TILES * WS_TILES, (unsigned)wa.n_sets), dim3(256),

@@ -1020,6 +1020,69 @@ typedef double ws_d4 __attribute__((ext_vector_type(4)));
 constexpr int WS_GRAM_THREADS = 512;
 constexpr int WS_GRAM_ZCHUNKS = 4;  // slices of a row block: 4 column quarters x this many chunks of tile rows
 
+// The products of one wavefront in one slice: rows [s_begin, s_end) of the block at row r0, NTI x NTJ output tiles from
+// tile row `ibase` and tile column 4 wj.  HAS_RW and the tile counts are template parameters so that the loop body is
+// ONE basic block -- loads, then MFMAs, no condition anywhere -- in which the compiler counts the loads exactly.
+//
+// Four register sets; the loads of three steps (twelve rows) stay in flight behind the MFMAs of a step.  A set is the
+// NTI + NTJ operand loads the products need (eight for 4 x 4 tiles; the runtime tile pattern used to read eight whatever
+// it needed, three of them from column blocks past K on a one-tile-row append), with the row weight as one more and LAST
+// load where there are weights: the weight scales A, so the first MFMA of a step waits for its whole set at once.  Every
+// wait in the compiled loop is exact: it leaves the three younger sets outstanding -- 3 (NTI + NTJ [+ 1]) loads, vmcnt(24)
+// to vmcnt(31) for 4 x 4 tiles -- and none reaches into a younger set (profiles/gram_pipeline/isa_waits.txt).  A step
+// beyond the wavefront's rows reads row 0 of the block with weight zero, so the prologue and the last iteration need no
+// conditions either; the prologue sits under the same test as the do-while, in its preheader, so that it issues its sets in
+// the order the back edge leaves them in (under a `for` its loads were sunk past the loop's entry test and reordered, and
+// the loop head took the stricter count: vmcnt(11), (19)).  The sched_barriers keep the loads that open a step above its
+// MFMAs and the select of a set's weight next to them: in one loop with the tile pattern as branches the compiler had
+// moved the first step's MFMAs above the fourth set's loads and sunk the selects of all in-flight weights to the back
+// edge, which drained the pipeline once per sixteen rows (vmcnt 3, 2, 10, 9).  The products are accumulated in row order
+// whatever the depth.
+template <bool HAS_RW, int NTI, int NTJ>
+static __device__ __forceinline__ void ws_gram_rows(const double* __restrict__ XW, const double* __restrict__ rw, int64_t r0, int64_t s_begin,
+                                                    int64_t s_end, int ibase, int wj, int kk, int c, ws_d4 (&acc)[4][4]) {
+  auto load = [&](int64_t s, double(&av)[4], double(&bv)[4], double& wv) {
+    const int64_t i = s + kk;
+    const int64_t row = r0 + (i < s_end ? i : 0);
+    const double* xr = XW + row * WS_KCAP + c;
+#pragma unroll
+    for (int t = 0; t < NTI; ++t) av[t] = xr[16 * (ibase + t)];
+#pragma unroll
+    for (int t = 0; t < NTJ; ++t) bv[t] = xr[16 * (4 * wj + t)];
+    if constexpr (HAS_RW) wv = rw[row];
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto mma = [&](int64_t s, const double(&av)[4], const double(&bv)[4], double wv) {
+    const bool ok = s + kk < s_end;
+    const double wgt = ok ? (HAS_RW ? wv : 1.0) : 0.0;
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti) {
+      const double a = av[ti] * wgt;
+#pragma unroll
+      for (int tj = 0; tj < NTJ; ++tj) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[tj], acc[ti][tj], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  double a0[4], b0[4], a1[4], b1[4], a2[4], b2[4], a3[4], b3[4], w0 = 1.0, w1 = 1.0, w2 = 1.0, w3 = 1.0;
+  if (s_begin >= s_end) return;  // (a row part without rows)
+  load(s_begin, a0, b0, w0);
+  load(s_begin + 4, a1, b1, w1);
+  load(s_begin + 8, a2, b2, w2);
+  int64_t s = s_begin;
+  do {
+    load(s + 12, a3, b3, w3);
+    mma(s, a0, b0, w0);
+    load(s + 16, a0, b0, w0);
+    mma(s + 4, a1, b1, w1);
+    load(s + 20, a1, b1, w1);
+    mma(s + 8, a2, b2, w2);
+    load(s + 24, a2, b2, w2);
+    mma(s + 12, a3, b3, w3);
+    s += 16;
+  } while (s < s_end);
+}
+
+template <bool HAS_RW>
 static __global__ __launch_bounds__(WS_GRAM_THREADS) void ws_gram_kernel(WsArgs w) {
   if (!w.ws->building) return;
   __shared__ ws_d4 comb[2][16][64];  // 64 KiB: row-split appends fold their four parts through here
@@ -1045,7 +1108,7 @@ static __global__ __launch_bounds__(WS_GRAM_THREADS) void ws_gram_kernel(WsArgs 
   const int64_t base = w.n / w.nblk, rem = w.n % w.nblk;
   const int64_t r0 = b * base + (b < rem ? b : rem);
   const int64_t nrows = base + (b < rem ? 1 : 0);
-  const double* rw = w.rw ? w.rw + (int64_t)w.set_lane[set] * w.rw_stride : nullptr;
+  const double* rw = HAS_RW ? w.rw + (int64_t)w.set_lane[set] * w.rw_stride : nullptr;
   // rows of this wavefront: everything, or the part-th quarter (in steps of four rows)
   const int part = row_split ? (wave >> 1) : 0;
   const int64_t steps = (nrows + 3) >> 2;
@@ -1062,10 +1125,10 @@ static __global__ __launch_bounds__(WS_GRAM_THREADS) void ws_gram_kernel(WsArgs 
   if (row_split ? (tile_lo + 4 * zhi >= tiles) : (zhi >= 2)) continue;
   const int wj = 2 * (slice & 3) + (wave & 1);
   const int ntj = min(4, max(0, tiles - 4 * wj));
-  const int ibase = row_split ? tile_lo + 4 * zhi : 4 * (4 * zhi + (wave >> 1));
-  const int ti_lo = row_split ? 0 : max(0, tile_lo - ibase);  // first tile row of this wave to do
-  const int nti = min(4, max(0, tiles - ibase));
-  const bool active = ti_lo < nti && ntj > 0;
+  const int irow = row_split ? tile_lo + 4 * zhi : 4 * (4 * zhi + (wave >> 1));  // the four tile rows of this wavefront
+  const int ibase = max(tile_lo, irow);  // (the first of them to do: tile_lo where the plain mapping straddles it on an append)
+  const int nti = max(0, min(tiles, irow + 4) - ibase);
+  const bool active = nti > 0 && ntj > 0;
   if (!row_split && !active) continue;  // (per wavefront: this mode has no barrier)
   ws_d4 acc[4][4];
 #pragma unroll
@@ -1075,55 +1138,15 @@ static __global__ __launch_bounds__(WS_GRAM_THREADS) void ws_gram_kernel(WsArgs 
 
   const int kk = lane >> 4, c = lane & 15;
   if (active) {
-    // (the row weight is applied in mma(), not at the load, so nothing waits on a load before the MFMAs)
-    // (every load of a step is issued whatever the tile pattern: a tile this wavefront does not need is read from
-    //  a column block that exists and never used.  With the loads under conditions the compiler could not count
-    //  them and waited for ALL of them -- the ones of the steps ahead included -- before the first MFMA of a step)
-    const int ta_max = WS_TILES - 1;
-    const double* rwp = rw ? rw : w.XW;  // (no row weights: any readable address, the value is replaced by 1)
-    const bool has_rw = rw != nullptr;
-    auto load = [&](int64_t s, double(&av)[4], double(&bv)[4], double& wgt) {
-      const int64_t i = s + kk;
-      const bool ok = i < s_end;
-      const int64_t row = r0 + (ok ? i : 0);
-      const double wv = rwp[has_rw ? row : 0];
-      const double* xr = w.XW + row * WS_KCAP + c;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        av[t] = xr[16 * min(ibase + t, ta_max)];
-        bv[t] = xr[16 * min(4 * wj + t, ta_max)];
-      }
-      wgt = ok ? (has_rw ? wv : 1.0) : 0.0;
-    };
-    auto mma = [&](const double(&av)[4], const double(&bv)[4], double wgt) {
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti) {
-        if (ti >= ti_lo && ti < nti) {
-          const double a = av[ti] * wgt;
-#pragma unroll
-          for (int tj = 0; tj < 4; ++tj)
-            if (tj < ntj) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[tj], acc[ti][tj], 0, 0, 0);
-        }
-      }
-    };
-    // Four register sets, three steps (twelve rows) of loads ahead of the MFMAs of a step, and no conditions around
-    // the loads or the products: a step beyond the wavefront's rows reads row 0 of the block with weight zero.  (With
-    // `if (s + 4 < s_end) load(...)` the waits became vmcnt(0): a memory round trip per step.)  The products are
-    // accumulated in row order whatever the depth.
-    double a0[4], b0[4], a1[4], b1[4], a2[4], b2[4], a3[4], b3[4], w0, w1, w2, w3;
-    load(s_begin, a0, b0, w0);
-    load(s_begin + 4, a1, b1, w1);
-    load(s_begin + 8, a2, b2, w2);
-    for (int64_t s = s_begin; s < s_end; s += 16) {
-      load(s + 12, a3, b3, w3);
-      mma(a0, b0, w0);
-      load(s + 16, a0, b0, w0);
-      mma(a1, b1, w1);
-      load(s + 20, a1, b1, w1);
-      mma(a2, b2, w2);
-      load(s + 24, a2, b2, w2);
-      mma(a3, b3, w3);
+#define WS_GRAM_ROWS(I, J) \
+  case 4 * (I - 1) + (J - 1): ws_gram_rows<HAS_RW, I, J>(w.XW, rw, r0, s_begin, s_end, ibase, wj, kk, c, acc); break;
+    switch (4 * (nti - 1) + (ntj - 1)) {  // (uniform for the wavefront)
+      WS_GRAM_ROWS(1, 1) WS_GRAM_ROWS(1, 2) WS_GRAM_ROWS(1, 3) WS_GRAM_ROWS(1, 4)
+      WS_GRAM_ROWS(2, 1) WS_GRAM_ROWS(2, 2) WS_GRAM_ROWS(2, 3) WS_GRAM_ROWS(2, 4)
+      WS_GRAM_ROWS(3, 1) WS_GRAM_ROWS(3, 2) WS_GRAM_ROWS(3, 3) WS_GRAM_ROWS(3, 4)
+      WS_GRAM_ROWS(4, 1) WS_GRAM_ROWS(4, 2) WS_GRAM_ROWS(4, 3) WS_GRAM_ROWS(4, 4)
     }
+#undef WS_GRAM_ROWS
   }
   if (row_split) {  // parts 0..3 in order: store, add + store, add + store, add (and write below)
     for (int round = 0; round < 4; ++round) {
@@ -1146,7 +1169,7 @@ static __global__ __launch_bounds__(WS_GRAM_THREADS) void ws_gram_kernel(WsArgs 
   // part[set][tile (I, J)][b][16 x 16] -- the reduce kernel then walks 2 KiB strides, not 2 MiB ones
 #pragma unroll
   for (int ti = 0; ti < 4; ++ti) {
-    if (ti < ti_lo || ti >= nti) continue;
+    if (ti >= nti) continue;
 #pragma unroll
     for (int tj = 0; tj < 4; ++tj) {
       if (tj >= ntj) continue;
