@@ -804,6 +804,48 @@ int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* cons
                               int64_t* nodes_out /* [count*n_eta] or NULL */, slm_point_info* info /* [count*n_eta] or NULL */);
 
 /*
+ * (added under ABI 24: two new symbols beside the exact l0 entries, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs them looks the symbols up.)  The l0 LOCAL SEARCH (csrc/l0_local_kernels.hpp): an
+ * APPROXIMATE answer to the regularised l0 problem for up to SLM_L0_LOCAL_PMAX = 1024 columns, where every entry above
+ * stops at 128.  It proves nothing: no lower bound comes back, and SLM_OK means "reached its fixed point", never "optimal".
+ * For cell e, with G = X^T W X / n_eff, c = X^T W y / n_eff and H = G + 2 etas[e] I,
+ *       minimise over beta, |beta_j| <= big_M:   F(beta) = 1/2 beta^T H beta - c^T beta + alphas[e] ||beta||_0
+ * -- the units of slm_solve_l0's objective with singleton groups and T = I.  The rule (Hazimeh and Mazumder 2020, "Fast best
+ * subset selection: coordinate descent and local combinatorial optimization"): with r = c - H beta and d_j = H_jj, coordinate
+ * j given the others has u = r_j + d_j beta_j, b = clip(u / d_j, +-big_M), gain = u b - 1/2 d_j b^2.
+ *   1. Descent: j = 0 .. p-1 cyclically, beta_j <- b if gain > alphas[e] (strictly), else 0; a column with
+ *      d_j <= 1e-12 max_k d_k stays 0.  A sweep ends the descent when no coordinate entered or left the support and
+ *      max_j |delta_j| sqrt(d_j) <= 1e-12 sqrt(yy); 10000 sweeps end it unconverged.
+ *   2. Swap scan: for i in the support, ascending, with i removed: g_i = gain(i) and g_j the best gain over j outside the
+ *      support (ties: the lowest j); if g_j > g_i + 1e-10 max(|g_i|, alphas[e]), i leaves, j enters at its b, and the rule
+ *      returns to 1.  When no i swaps the problem is done; 10000 swaps end it unconverged.
+ * Every accepted step lowers F.  slm_solve_l0_local_descent is the same call without step 2: every problem ends at its
+ * descent's fixed point, whose F is never below the full rule's from the same start.
+ * One launch runs n_cells * n_starts problems, one wavefront each: cell e from starts[(e * n_starts + s) * p ..] (each inside
+ * the box; NULL with n_starts = 1: the zero start).  The kernel reads the Gram that slm_dataset_covariance files with the
+ * dataset, in place.  Per cell the start with the lowest F wins (ties: the lowest index; start_out, may be NULL), and the
+ * host re-solves the winner's support exactly inside the box: beta_out[e] is the minimiser on its support and
+ * objective_out[e] its F.  info[e] (may be NULL): status = SLM_OK or SLM_ERR_NOT_CONVERGED (a cap ended the winner), n_iter =
+ * its sweeps, rejects = its accepted swaps, resid = its status word (1: a descent ran out of sweeps, 2: the swap cap), mu =
+ * its objective before the polish, kkt = the objective after it, loss, beta_norm = ||beta||_2, L = -inf (no bound), mode = 8.
+ * Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when some cell's winner reached a cap.
+ * Refusals, all before a device is touched, each with its own message: p > 1024, groups that are not singletons, a
+ * row-sharded dataset (SLM_ERR_UNSUPPORTED); a negative or non-finite alphas[e] or etas[e], big_M < 0, n_cells < 1,
+ * n_starts < 1, n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS = 8192, a start outside the box (SLM_ERR_BAD_ARG).
+ * Not here: groups and a hierarchy, a bound on the cardinality, an l1 term, a Tikhonov matrix, constraints, row sets (CV
+ * folds) in the launch.
+ */
+#define SLM_L0_LOCAL_PMAX 1024
+#define SLM_L0_LOCAL_MAX_PROBLEMS 8192
+int slm_solve_l0_local(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
+                       double big_M, int32_t n_starts, const double* starts /* n_cells * n_starts * p, or NULL: one zero start */,
+                       double* beta_out /* n_cells * p */, double* objective_out /* n_cells */, int32_t* start_out /* winning start */,
+                       slm_point_info* info /* n_cells */);
+int slm_solve_l0_local_descent(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                               int32_t n_starts, const double* starts, double* beta_out, double* objective_out, int32_t* start_out,
+                               slm_point_info* info);
+
+/*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant
  * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The exact l0 search with the
  * EXCLUSION BOUND (csrc/l0_kernels.hpp, template parameter XB): the arguments, outputs, argument errors and contract of

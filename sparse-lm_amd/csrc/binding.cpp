@@ -510,6 +510,38 @@ py::tuple solve_l0_profile_grid(uintptr_t ds, int64_t p, int64_t n, const py::se
   return l0_profile_rows(ds, p, n, row_weights, n_effs, intercept, &etas, eta_kind, alpha_min, max_groups, 0.0, T, big_M, need, max_nodes);
 }
 
+// slm_solve_l0_local / slm_solve_l0_local_descent: the local search over n_cells cells from n_starts starts each.  starts: None
+// (the zero start) or n_cells * n_starts * p doubles.  Returns (coefficients [n_cells][p], objectives [n_cells], winning starts
+// [n_cells], records as bytes, status).
+template <bool SWAPS>
+py::tuple solve_l0_local(uintptr_t ds, int64_t p, int32_t n_cells, const arr_d& alphas, const arr_d& etas, double big_M, int32_t n_starts,
+                         const py::object& starts) {
+  const int64_t cells = n_cells > 0 ? n_cells : 0;
+  if ((int64_t)alphas.size() < cells || (int64_t)etas.size() < cells) throw py::value_error("alphas and etas must have n_cells entries");
+  // (no cell, more problems than any call takes: the engine refuses them, the outputs only have to exist)
+  const bool sized = n_cells >= 1 && n_starts >= 1 && (int64_t)n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS;
+  Keep keep;
+  const double* sp = sized ? vector_arg(starts, (int64_t)n_cells * n_starts * p, "starts", keep) : nullptr;
+  const py::ssize_t cnt = sized ? n_cells : 1;
+  py::array_t<double> beta({cnt, (py::ssize_t)p}), objective(cnt);
+  py::array_t<int32_t> winner(cnt);
+  py::array info = info_bytes(cnt);
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
+  double *bp = beta.mutable_data(), *op = objective.mutable_data();
+  int32_t* wp = winner.mutable_data();
+  std::memset(wp, 0, sizeof(int32_t) * (size_t)cnt);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    auto* d = reinterpret_cast<slm_dataset*>(ds);
+    rc = SWAPS ? slm_solve_l0_local(d, n_cells, alphas.data(), etas.data(), big_M, n_starts, sp, bp, op, wp, rec)
+               : slm_solve_l0_local_descent(d, n_cells, alphas.data(), etas.data(), big_M, n_starts, sp, bp, op, wp, rec);
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, objective, winner, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -536,6 +568,8 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_profile_grid", &solve_l0_profile_grid);
   m.def("solve_l0_l1_profile", &solve_l0_l1_profile);
   m.def("solve_l0_l1_profile_wide", &solve_l0_l1_profile_wide);
+  m.def("solve_l0_local", &solve_l0_local<true>);
+  m.def("solve_l0_local_descent", &solve_l0_local<false>);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

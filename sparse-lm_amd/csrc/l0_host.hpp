@@ -15,7 +15,10 @@
 // winner among the waves' results, the way back to the caller's groups and columns, and the loss from the Gram.  The batched
 // profile (slm_solve_l0_profile_batch; tests/l0_batch_host_test.cpp) adds the layout of several problems in one block and the
 // elimination of an intercept column from a Gram.  The profile grid (slm_solve_l0_profile_grid; tests/l0_grid_host_test.cpp) adds
-// the problem index over (row set, eta), its argument checks and the layout at up to L0_GRID_MAX problems.
+// the problem index over (row set, eta), its argument checks and the layout at up to L0_GRID_MAX problems.  The local search
+// (slm_solve_l0_local; tests/l0_local_host_test.cpp) adds, at the very end, the two decisions host and device share, the rule
+// itself without a device (l0_ls_solve), the polish of its winner and its argument checks; it uses nothing of the exact search
+// but l0_boxed and the dense Cholesky.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -1161,6 +1164,204 @@ inline double l0_gram_loss(const double* G, const double* c, int p, double yy, c
     loss += beta[i] * (0.5 * t - c[i]);
   }
   return loss;
+}
+
+// ---- local search (slm_solve_l0_local; csrc/l0_local_kernels.hpp; tests/l0_local_host_test.cpp) ------------------------------
+//
+// The one part of the family that proves nothing: for a cell (alpha, eta), H = G + 2 eta I,
+//     F(beta) = 1/2 beta^T H beta - c^T beta + alpha ||beta||_0   over |beta_j| <= big_M,
+// cyclic coordinate descent with hard thresholding, then one-for-one swaps until none helps (DESIGN 4d "Local search").  The
+// state is beta, r = c - H beta and d_j = H_jj.  l0_ls_coord and l0_ls_swap_better are the two decisions, shared with the
+// kernel; l0_ls_solve is the whole rule without a device (the kernel's twin: the same sequence of changes, the same
+// arithmetic up to the order of the final sums and the contraction of a multiply-add), l0_ls_polish the exact re-solve of a
+// support inside the box that the entry runs on the winner.
+constexpr int L0_LS_PMAX = 1024;             // columns: 16 slots of 64 lanes
+constexpr int L0_LS_SLOTS = L0_LS_PMAX / 64;
+constexpr int L0_LS_SWAPS = 10000;           // accepted swaps of one problem; reaching it marks the problem unconverged
+constexpr double L0_LS_SWAP_TOL = 1e-10;     // a swap must gain this much, relative to max(|g_i|, alpha)
+constexpr int L0_LS_MAX_PROBLEMS = 8192;     // (cell, start) problems of one call
+constexpr int L0_LS_SWEEPS_OUT = 1, L0_LS_SWAPS_OUT = 2;  // bits of a problem's status word: which cap it reached
+
+// coordinate j given the others: u = r_j + d_j beta_j, b = clip(u / d_j), gain = u b - 1/2 d_j b^2 (what F without the alpha
+// term falls by when beta_j goes from 0 to b)
+struct L0LsCoord {
+  double b, gain;
+};
+constexpr L0LsCoord l0_ls_coord(double u, double d, double big_M) {
+  double b = u / d;
+  b = b < -big_M ? -big_M : (b > big_M ? big_M : b);
+  return L0LsCoord{b, u * b - 0.5 * d * b * b};
+}
+// the descent's rule: the new value of a coordinate
+constexpr double l0_ls_threshold(const L0LsCoord& co, double alpha) { return co.gain > alpha ? co.b : 0.0; }
+// the swap rule: column j (gain gj with i removed) replaces column i (gain gi with i removed)
+constexpr bool l0_ls_swap_better(double gj, double gi, double alpha) {
+  const double a = gi < 0.0 ? -gi : gi;
+  return gj > gi + L0_LS_SWAP_TOL * (a > alpha ? a : alpha);
+}
+
+struct L0LsResult {
+  double F = 0.0;  // the objective at the returned beta
+  int sweeps = 0, swaps = 0, status = 0, nnz = 0;
+  long long changes = 0;  // columns of H applied to r after the start (one per coordinate change, two per swap): what the time goes to
+};
+
+// The rule on one problem.  G: [p][ld] the Gram (symmetric; row j is read for column j), c: [p]; 2 eta goes on the diagonal
+// here.  start: [p] inside the box, or NULL for zero.  beta: [p] out.  A column whose d_j <= L0_PIVOT max d stays zero.
+inline L0LsResult l0_ls_solve(const double* G, size_t ld, const double* c, int p, double alpha, double eta, double big_M, double yy,
+                              bool swaps, const double* start, double* beta) {
+  L0LsResult R;
+  std::vector<double> r(c, c + p), d((size_t)p);
+  const double eta2 = 2.0 * eta;
+  double dmax = 0.0;
+  for (int j = 0; j < p; ++j) {
+    d[(size_t)j] = G[(size_t)j * ld + j] + eta2;
+    dmax = std::max(dmax, d[(size_t)j]);
+  }
+  for (int j = 0; j < p; ++j) {
+    if (!(d[(size_t)j] > L0_PIVOT * dmax)) d[(size_t)j] = 0.0;  // (0 marks a column that stays out)
+    beta[j] = start && d[(size_t)j] > 0.0 ? start[j] : 0.0;
+  }
+  auto axpy = [&](int j, double w) {  // r += w H[:, j]
+    const double* row = G + (size_t)j * ld;
+    for (int k = 0; k < p; ++k) r[(size_t)k] += w * (k == j ? row[k] + eta2 : row[k]);
+  };
+  for (int j = 0; j < p; ++j)
+    if (beta[j] != 0.0) axpy(j, -beta[j]);
+  const double tol = L0_CD_TOL * std::sqrt(yy);
+  for (;;) {
+    // ---- 1. the descent to its fixed point --------------------------------------------------------------------------------
+    for (int sw = 0;; ++sw) {
+      if (sw == L0_CD_SWEEPS) {
+        R.status |= L0_LS_SWEEPS_OUT;
+        break;
+      }
+      bool moved = false;
+      double maxd = 0.0;
+      for (int j = 0; j < p; ++j) {
+        const double dj = d[(size_t)j];
+        if (!(dj > 0.0)) continue;
+        const double nb = l0_ls_threshold(l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M), alpha);
+        if (nb == beta[j]) continue;
+        const double delta = nb - beta[j];
+        moved = moved || ((nb != 0.0) != (beta[j] != 0.0));
+        maxd = std::max(maxd, std::fabs(delta) * std::sqrt(dj));
+        beta[j] = nb;
+        axpy(j, -delta);
+        ++R.changes;
+      }
+      ++R.sweeps;
+      if (!moved && maxd <= tol) break;
+    }
+    if (!swaps || R.status) break;
+    // ---- 2. the swap scan: the first i of the support that a column outside replaces with a gain ----------------------------
+    bool swapped = false;
+    for (int i = 0; i < p && !swapped; ++i) {
+      const double bi = beta[i];
+      if (bi == 0.0) continue;
+      const double* row = G + (size_t)i * ld;
+      const double gi = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * bi, d[(size_t)i], big_M).gain;
+      double gb = -1.0, bb = 0.0;
+      int jb = -1;
+      for (int j = 0; j < p; ++j) {
+        if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
+        const L0LsCoord co = l0_ls_coord(r[(size_t)j] + row[j] * bi, d[(size_t)j], big_M);
+        if (co.gain > gb) {  // (ties: the lowest j)
+          gb = co.gain;
+          bb = co.b;
+          jb = j;
+        }
+      }
+      if (jb < 0 || !l0_ls_swap_better(gb, gi, alpha)) continue;
+      beta[i] = 0.0;
+      axpy(i, bi);
+      beta[jb] = bb;
+      axpy(jb, -bb);
+      ++R.swaps;
+      R.changes += 2;
+      swapped = true;
+    }
+    if (!swapped) break;
+    if (R.swaps == L0_LS_SWAPS) {
+      R.status |= L0_LS_SWAPS_OUT;
+      break;
+    }
+  }
+  // F = 1/2 beta^T H beta - c^T beta + alpha nnz with H beta = c - r
+  double acc = 0.0;
+  for (int j = 0; j < p; ++j) {
+    acc += beta[j] * (c[j] + r[(size_t)j]);
+    R.nnz += beta[j] != 0.0;
+  }
+  R.F = -0.5 * acc + alpha * (double)R.nnz;
+  return R;
+}
+
+// The winner's support re-solved exactly inside the box (what l0_boxed(..., polish = true) does for the exact search): the
+// descent of l0_boxed from beta, its face solve where the box binds, and where it does not the Cholesky solve of the whole
+// support, taken when the factor exists under the pivot rule and the point is inside the box.  beta: [p] in, out (the support
+// is kept: zeros stay zero).  Returns 1/2 beta^T H beta - c^T beta, without the alpha term.
+inline double l0_ls_polish(const double* G, size_t ld, const double* c, int p, double eta, double big_M, double* beta) {
+  std::vector<int> cols;
+  for (int j = 0; j < p; ++j)
+    if (beta[j] != 0.0) cols.push_back(j);
+  const int m = (int)cols.size();
+  if (m == 0) return 0.0;
+  std::vector<double> Hs((size_t)m * m), cs((size_t)m), b((size_t)m);
+  std::vector<int> id((size_t)m);
+  for (int a = 0; a < m; ++a) {
+    id[(size_t)a] = a;
+    cs[(size_t)a] = c[cols[(size_t)a]];
+    b[(size_t)a] = beta[cols[(size_t)a]];
+    for (int k = 0; k < m; ++k) Hs[(size_t)a * m + k] = G[(size_t)cols[(size_t)a] * ld + cols[(size_t)k]] + (a == k ? 2.0 * eta : 0.0);
+  }
+  double val = l0_boxed(Hs.data(), cs.data(), m, id.data(), m, big_M, true, b.data());
+  bool all_free = true;
+  for (int a = 0; a < m; ++a) all_free = all_free && std::fabs(b[(size_t)a]) < big_M;
+  if (all_free) {
+    std::vector<double> M = Hs, x = cs;
+    if (l0_dense_chol(M, m)) {
+      l0_dense_fwd(M, m, x.data());
+      l0_dense_bwd(M, m, x.data());
+      bool inside = true;
+      for (int a = 0; a < m; ++a) inside = inside && std::fabs(x[(size_t)a]) <= big_M && x[(size_t)a] != 0.0;
+      if (inside) {
+        b = x;
+        val = 0.0;
+        for (int a = 0; a < m; ++a) {
+          double t = 0.0;
+          for (int k = 0; k < m; ++k) t += Hs[(size_t)a * m + k] * b[(size_t)k];
+          val += b[(size_t)a] * (0.5 * t - cs[(size_t)a]);
+        }
+      }
+    }
+  }
+  for (int a = 0; a < m; ++a) beta[cols[(size_t)a]] = b[(size_t)a];
+  return val;
+}
+
+// What slm_solve_l0_local refuses before anything is launched, in this order (0: nothing); *which: the offending index.
+enum L0LsRefusal { L0_LS_OK = 0, L0_LS_NULL, L0_LS_CELLS, L0_LS_STARTS, L0_LS_PROBLEMS, L0_LS_BIG_M, L0_LS_ALPHA, L0_LS_ETA, L0_LS_WIDTH,
+                   L0_LS_START_BOX };
+inline L0LsRefusal l0_ls_check(long long n_cells, const double* alphas, const double* etas, double big_M, long long n_starts,
+                               const double* starts, long long p, long long* which = nullptr) {
+  if (!alphas || !etas) return L0_LS_NULL;
+  if (n_cells < 1) return L0_LS_CELLS;
+  if (n_starts < 1) return L0_LS_STARTS;
+  if (n_cells > L0_LS_MAX_PROBLEMS || n_starts > L0_LS_MAX_PROBLEMS || n_cells * n_starts > L0_LS_MAX_PROBLEMS) return L0_LS_PROBLEMS;
+  if (!(big_M >= 0.0)) return L0_LS_BIG_M;
+  for (long long e = 0; e < n_cells; ++e) {
+    if (which) *which = e;
+    if (!(alphas[e] >= 0.0) || !std::isfinite(alphas[e])) return L0_LS_ALPHA;
+    if (!(etas[e] >= 0.0) || !std::isfinite(etas[e])) return L0_LS_ETA;
+  }
+  if (p > L0_LS_PMAX) return L0_LS_WIDTH;
+  for (long long e = 0; starts && e < n_cells * n_starts * p; ++e)
+    if (!(std::fabs(starts[e]) <= big_M)) {  // (a NaN fails too)
+      if (which) *which = e;
+      return L0_LS_START_BOX;
+    }
+  return L0_LS_OK;
 }
 
 }  // namespace slm

@@ -1,0 +1,227 @@
+// The l0 LOCAL SEARCH on chip (slm_solve_l0_local, engine_l0.hip; the rule and its host twin l0_ls_solve: l0_host.hpp, "local
+// search"; DESIGN 4d "Local search").  Where the exact search (l0_kernels.hpp) stops at 128 columns, this kernel takes
+// L0_LS_PMAX = 1024 and proves nothing: cyclic coordinate descent with hard thresholding on
+//     F(beta) = 1/2 beta^T H beta - c^T beta + alpha ||beta||_0,   H = G + 2 eta I,   |beta_j| <= big_M,
+// then one-for-one swaps until none helps.
+//
+// One WAVEFRONT per (cell, start) problem; the L0_WAVES wavefronts of a workgroup share nothing, there is no LDS and no barrier,
+// and a grid-stride loop over the problems lets a launch hold more problems than the grid has waves.  Coordinate j lives in
+// lane j & 63, slot j >> 6: beta, r = c - H beta and d = diag H take 16 doubles each per lane.  Every loop over the slots is
+// unrolled and every index into them a compile-time constant; the one entry a step updates is selected by comparing the lane
+// (and, for a swap's incoming column, the slot) -- nothing is indexed at run time, so nothing goes to scratch.
+//
+// The sequential rule does not cost p steps per sweep.  Until a coordinate changes, r is unchanged, so all lanes evaluate their
+// coordinates at once; because j = 64 slot + lane, the first j >= the cursor whose value would change is in the first slot with
+// a changing lane, and there it is the lowest such lane: one ballot per slot, no arg-min.  That change is applied -- ONE read of
+// row j of G (symmetric: column j), 64 consecutive doubles per slot, all slots' loads in flight together -- and the cursor moves
+// to j + 1.  This is exactly the sequence of changes of the sequential rule.  The swap scan does the same per i of the support:
+// one read of row i, every lane's best gain over its outside columns, a wave arg-max with the lowest index on ties.
+//
+// G and c are read IN PLACE from the dataset's Gram store with its leading dimension; 2 eta goes on the diagonal here.  Each
+// problem owns row q of every output, so nothing is shared and there is no atomic.  Every applied change is one dependent read
+// of 8 p bytes (from L2 / Infinity Cache: the Gram is at most 8 MB), so a problem is latency-bound and the chip fills only
+// through the number of problems.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "l0_host.hpp"     // L0_LS_*, l0_ls_coord, l0_ls_threshold, l0_ls_swap_better: shared with the host twin
+#include "l0_kernels.hpp"  // L0_WAVES, l0_bcast, l0_wave_max, l0_wave_sum
+
+namespace slm {
+
+struct L0LsArgs {
+  const double* G;       // [p][ld] the dataset's Gram, in place
+  const double* c;       // [p]
+  const double* alphas;  // [n_cells]
+  const double* etas;    // [n_cells]
+  const double* starts;  // [n_problems][p] inside the box, or NULL: zero
+  double* beta_out;      // [n_problems][p]
+  double* F_out;         // [n_problems]
+  int* stat_out;         // [n_problems][4]: sweeps, swaps, status word (L0_LS_SWEEPS_OUT | L0_LS_SWAPS_OUT), non-zeros
+  long long ld;
+  int p, n_problems, n_starts, swaps;  // problem q is cell q / n_starts; swaps == 0: the descent alone
+  double big_M, yy;
+};
+
+static __device__ __forceinline__ int l0_ls_wave_min(int v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
+  return v;
+}
+
+// r += w H[:, j] (row j of G, 2 eta on the diagonal): one coalesced read, the slots' loads independent of each other
+static __device__ __forceinline__ void l0_ls_axpy(double (&r)[L0_LS_SLOTS], const double* __restrict__ G, long long ld, int p, int ns, int lane,
+                                                  double eta2, int j, double w) {
+  const double* row = G + (long long)j * ld;
+#pragma unroll
+  for (int t = 0; t < L0_LS_SLOTS; ++t)
+    if (t < ns) {
+      const int k = t * 64 + lane;
+      if (k < p) {
+        double h = row[k];
+        if (k == j) h += eta2;
+        r[t] += w * h;
+      }
+    }
+}
+
+static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int p = a.p, ns = (p + 63) >> 6;
+  const long long ld = a.ld;
+  const double* __restrict__ G = a.G;
+  const double big_M = a.big_M, tol = L0_CD_TOL * sqrt(a.yy);
+  const int stride = (int)gridDim.x * L0_WAVES;
+  for (int q = (int)blockIdx.x * L0_WAVES + (int)(threadIdx.x >> 6); q < a.n_problems; q += stride) {
+    const int cell = q / a.n_starts;
+    const double alpha = a.alphas[cell], eta2 = 2.0 * a.etas[cell];
+    double beta[L0_LS_SLOTS], r[L0_LS_SLOTS], d[L0_LS_SLOTS];
+    double dmax = 0.0;
+#pragma unroll
+    for (int s = 0; s < L0_LS_SLOTS; ++s) {
+      const int j = s * 64 + lane;
+      beta[s] = 0.0;
+      r[s] = 0.0;
+      d[s] = 0.0;
+      if (s < ns && j < p) {
+        d[s] = G[(long long)j * ld + j] + eta2;
+        r[s] = a.c[j];
+        if (a.starts) beta[s] = a.starts[(long long)q * p + j];
+      }
+      dmax = fmax(dmax, d[s]);
+    }
+    dmax = l0_wave_max(dmax);
+#pragma unroll
+    for (int s = 0; s < L0_LS_SLOTS; ++s)
+      if (!(d[s] > L0_PIVOT * dmax)) {  // d = 0 marks a column that stays out (and the lanes beyond p)
+        d[s] = 0.0;
+        beta[s] = 0.0;
+      }
+    // r = c - H beta of the start, column by column in ascending order
+#pragma unroll
+    for (int s = 0; s < L0_LS_SLOTS; ++s)
+      if (s < ns) {
+        unsigned long long act = __ballot(beta[s] != 0.0);
+        while (act) {
+          const int k = __builtin_ctzll(act);
+          act &= act - 1;
+          l0_ls_axpy(r, G, ld, p, ns, lane, eta2, s * 64 + k, -l0_bcast(beta[s], k));
+        }
+      }
+
+    int sweeps = 0, swaps = 0, status = 0;
+    for (;;) {
+      // ---- 1. the descent to its fixed point --------------------------------------------------------------------------------
+      for (int sw = 0;; ++sw) {
+        if (sw == L0_CD_SWEEPS) {
+          status |= L0_LS_SWEEPS_OUT;
+          break;
+        }
+        bool moved = false;
+        double maxd = 0.0;
+        int cursor = 0;
+        for (;;) {  // the next change at or after the cursor
+          const int s0 = cursor >> 6;
+          bool found = false;
+          int jf = 0;
+          double delta = 0.0;
+#pragma unroll
+          for (int s = 0; s < L0_LS_SLOTS; ++s)
+            if (!found && s >= s0 && s < ns) {
+              const double nb = l0_ls_threshold(l0_ls_coord(r[s] + d[s] * beta[s], d[s], big_M), alpha);
+              const unsigned long long bal = __ballot(d[s] > 0.0 && s * 64 + lane >= cursor && nb != beta[s]);
+              if (bal) {
+                const int k = __builtin_ctzll(bal);
+                const double nbk = l0_bcast(nb, k), old = l0_bcast(beta[s], k), dk = l0_bcast(d[s], k);
+                if (lane == k) beta[s] = nbk;
+                found = true;
+                jf = s * 64 + k;
+                delta = nbk - old;
+                moved = moved || ((nbk != 0.0) != (old != 0.0));
+                maxd = fmax(maxd, fabs(delta) * sqrt(dk));
+              }
+            }
+          if (!found) break;
+          l0_ls_axpy(r, G, ld, p, ns, lane, eta2, jf, -delta);
+          cursor = jf + 1;
+        }
+        ++sweeps;
+        if (!moved && maxd <= tol) break;
+      }
+      if (!a.swaps || status) break;
+      // ---- 2. the swap scan: the first i of the support that a column outside replaces with a gain ----------------------------
+      bool swapped = false;
+#pragma unroll
+      for (int si = 0; si < L0_LS_SLOTS; ++si)
+        if (!swapped && si < ns) {
+          unsigned long long act = __ballot(beta[si] != 0.0);
+          while (act && !swapped) {
+            const int k = __builtin_ctzll(act);
+            act &= act - 1;
+            const int i = si * 64 + k;
+            const double bi = l0_bcast(beta[si], k), di = l0_bcast(d[si], k), ri = l0_bcast(r[si], k);
+            const double gi = l0_ls_coord(ri + di * bi, di, big_M).gain;
+            const double* row = G + (long long)i * ld;
+            double gb = -1.0, bb = 0.0;
+            int jb = 0x7fffffff;
+#pragma unroll
+            for (int t = 0; t < L0_LS_SLOTS; ++t)
+              if (t < ns) {
+                const int j = t * 64 + lane;
+                const double h = j < p ? row[j] : 0.0;
+                const L0LsCoord co = l0_ls_coord(r[t] + h * bi, d[t], big_M);
+                if (d[t] > 0.0 && beta[t] == 0.0 && co.gain > gb) {  // (ascending slots: the lane keeps its lowest j on ties)
+                  gb = co.gain;
+                  bb = co.b;
+                  jb = j;
+                }
+              }
+            const double gmax = l0_wave_max(gb);
+            const int jmin = l0_ls_wave_min(gb == gmax ? jb : 0x7fffffff);
+            if (jmin != 0x7fffffff && l0_ls_swap_better(gmax, gi, alpha)) {
+              const double bj = l0_bcast(bb, jmin & 63);  // (that lane's best IS jmin)
+              if (lane == k) beta[si] = 0.0;
+              l0_ls_axpy(r, G, ld, p, ns, lane, eta2, i, bi);
+#pragma unroll
+              for (int t = 0; t < L0_LS_SLOTS; ++t)
+                if (t == (jmin >> 6) && lane == (jmin & 63)) beta[t] = bj;
+              l0_ls_axpy(r, G, ld, p, ns, lane, eta2, jmin, -bj);
+              ++swaps;
+              swapped = true;
+            }
+          }
+        }
+      if (!swapped) break;
+      if (swaps == L0_LS_SWAPS) {
+        status |= L0_LS_SWAPS_OUT;
+        break;
+      }
+    }
+
+    // F = 1/2 beta^T H beta - c^T beta + alpha nnz with H beta = c - r; the problem's own row of every output
+    double acc = 0.0;
+    int nnz = 0;
+#pragma unroll
+    for (int s = 0; s < L0_LS_SLOTS; ++s)
+      if (s < ns) {
+        const int j = s * 64 + lane;
+        if (j < p) {
+          acc += beta[s] * (a.c[j] + r[s]);
+          nnz += beta[s] != 0.0;
+          a.beta_out[(long long)q * p + j] = beta[s];
+        }
+      }
+    acc = l0_wave_sum(acc);
+    nnz = (int)l0_wave_sum((double)nnz);
+    if (lane == 0) {
+      a.F_out[q] = -0.5 * acc + alpha * (double)nnz;
+      a.stat_out[4 * q + 0] = sweeps;
+      a.stat_out[4 * q + 1] = swaps;
+      a.stat_out[4 * q + 2] = status;
+      a.stat_out[4 * q + 3] = nnz;
+    }
+  }
+}
+
+}  // namespace slm

@@ -47,6 +47,8 @@ FLAG_NO_MODEL_GRAM = 512  # lanes beyond the working set's 512 columns take plai
 COMM_ID_BYTES = 128
 ABI_VERSION = 24  # SLM_ABI_VERSION of include/slm_engine.h this binding was written against
 L0_GRID_MAX = 128  # SLM_L0_GRID_MAX: the problems of one slm_solve_l0_profile_grid call
+L0_LOCAL_PMAX = 1024  # SLM_L0_LOCAL_PMAX: the columns of slm_solve_l0_local
+L0_LOCAL_MAX_PROBLEMS = 8192  # SLM_L0_LOCAL_MAX_PROBLEMS: the (cell, start) problems of one slm_solve_l0_local call
 
 # every symbol include/slm_engine.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -101,6 +103,8 @@ ABI_SYMBOLS = (
     "slm_solve_l0_constrained",
     "slm_solve_l0_xb",
     "slm_solve_l0_xb_wide",
+    "slm_solve_l0_local",
+    "slm_solve_l0_local_descent",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -372,6 +376,8 @@ def load_library():
             "slm_solve_l0_xb_wide": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, vp, P(dbl), P(i64), P(_PointInfo)],
             "slm_solve_l0_constrained": [vp, dbl, i32, dbl, vp, dbl, vp, i64, vp, i32, vp, vp, vp, vp, i32, vp, P(C.c_uint64), P(dbl), P(i64),
                                          vp, P(_PointInfo)],
+            "slm_solve_l0_local": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_descent": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1319,7 +1325,7 @@ class Dataset:
         )
         return beta, lam, info[0]
 
-    # ---- the exact l0 search: what its eleven entries share -------------------------------------------------------------------
+    # ---- the exact l0 search: what its entries share -------------------------------------------------------------------
     def _need_narrow(self, need):
         """``need`` (one integer mask per group) as the narrow entries take it: one 64-bit word per group."""
         if need is None:
@@ -1623,6 +1629,47 @@ class Dataset:
             for b in range(problems):
                 out[b]["descents"] = int(infos[b]["rejects"])
         return betas, icpts, supports, values, out
+
+    def solve_l0_local(self, alphas, etas=0.0, big_M=100.0, starts=None, swaps=True, n_cells=None, n_starts=None, binding=None):
+        """``slm_solve_l0_local`` (``swaps=False``: ``slm_solve_l0_local_descent``): the l0 LOCAL SEARCH -- coordinate descent with
+        hard thresholding, then one-for-one swaps until none helps (csrc/l0_local_kernels.hpp) -- for
+        ``1/2 b^T (G + 2 eta I) b - c^T b + alpha ||b||_0`` with ``|b_j| <= big_M`` at every cell ``(alphas[e], etas[e])``, up
+        to 1024 columns, singleton groups.  ``starts``: None (the zero start), or ``[cells, n_starts, p]`` points inside the box;
+        every (cell, start) is one problem of ONE launch, and per cell the start with the lowest objective wins.  Nothing is
+        proven.  Returns ``(betas [cells, p], objectives [cells], winning starts [cells], infos)``; ``infos`` is one dict per
+        cell with ``objective``, ``descent_objective`` (before the host re-solved the winner's support exactly), ``loss``,
+        ``sweeps``, ``swaps``, ``converged``, ``status`` (``"fixed_point"``, ``"sweep_cap"``, ``"swap_cap"``) and
+        ``proven_optimal`` (False).  ``n_cells`` / ``n_starts``: the counts handed to the engine (None: the arrays')."""
+        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        et = np.ascontiguousarray(np.broadcast_to(np.asarray(etas, dtype=np.float64), al.shape), dtype=np.float64).reshape(-1)
+        cells = len(al) if n_cells is None else int(n_cells)
+        if len(al) < cells or len(et) < cells:
+            raise ValueError("alphas and etas must have n_cells entries")
+        st = None
+        ns = 1 if n_starts is None else int(n_starts)
+        if starts is not None:
+            st = np.ascontiguousarray(starts, dtype=np.float64)
+            if n_starts is None:
+                if st.ndim != 3 or st.shape[0] != cells or st.shape[2] != self.p:
+                    raise ValueError(f"starts must have the shape (cells, n_starts, {self.p})")
+                ns = st.shape[1]
+            st = st.reshape(-1)
+        sized = cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS  # (else the engine refuses: the outputs only have to exist)
+        if st is not None and sized and st.size != cells * ns * self.p:
+            raise ValueError(f"starts has {st.size} entries, expected {cells * ns * self.p}")
+        cnt = cells if sized else 1
+        pad = np.zeros(1)  # (an empty array has no address worth handing over)
+        args = (cells, al if len(al) else pad, et if len(et) else pad, float(big_M), ns, st if sized else None)
+        (betas, objectives, winners), infos, rc = self._l0_call(
+            "solve_l0_local" if swaps else "solve_l0_local_descent", binding, args,
+            [np.zeros((cnt, self.p)), np.zeros(cnt), np.zeros(cnt, dtype=np.int32)], records=cnt)
+        names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
+        out = [{
+            "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
+            "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
+            "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
+        } for e in range(cnt)]
+        return betas, objectives, winners, out
 
 
 class _HostPool:

@@ -63,8 +63,15 @@ Then the profile grid (``sparselm_amd.miqp.l1l0_profile_cv`` / ``l2l0_profile_cv
 the ridge kind, every problem under ``--max-nodes``.  Whole calls, warm, the variants alternating, medians of ``--repeats``
 (default 5).  Nothing is promised but what the file states; a row where the one launch is slower is written down like any other.
 
+Then the local search (``sparselm_amd.miqp.l0_local_search``, ``slm_solve_l0_local``), written to ``profiles/l0_local.txt`` by
+``--only local`` (it is not part of a run without ``--only``): beside ``RegularizedL0`` on the reference's 290 x 66 data and at 25 x 30
+(time, and the objective's gap to the proven or incumbent value); at 200 x 512 and 400 x 1024 one launch of 1, 16, 64 and 256 cells
+against the host twin ``l0_ls_solve`` on one core (``tools/l0_local_host_bench.cpp``, compiled here with g++); the time per applied
+coordinate change at 1024 columns.  No ratio is promised: the file names the number of cells from which the launch wins, or says that it
+did not, and what was not measured.
+
 ``--only search`` / ``--only profile`` / ``--only wide`` / ``--only constrained`` / ``--only bound`` / ``--only cv`` / ``--only l1profile`` /
-``--only gridcv`` runs one part."""
+``--only gridcv`` / ``--only local`` runs one part."""
 
 import argparse
 import math
@@ -661,6 +668,164 @@ def grid_cv_section(out_path, repeats, max_nodes):
     say("waves; the time workgroups of finished problems idle while other problems run (the engine keeps no such count, so the reading of (a) --")
     say("the call lasts as long as its heaviest problem on a 48th of the device -- rests on the descent counts alone); GridSearchCV fit by fit.")
 
+# the resource line of l0_local_kernel (hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage -c csrc/engine_l0.hip):
+# the build does not report it, so it is kept here and checked whenever the kernel changes
+LOCAL_KERNEL_RESOURCES = ("l0_local_kernel on gfx950: 255 VGPRs, 78 AGPRs, scratch 0 bytes/lane, LDS 0 bytes, 104 SGPRs (156 SGPR spills to "
+                          "VGPR lanes, no VGPR spill), 1 wave/SIMD")
+
+LOCAL_OTHER_KERNELS = ("the twelve instantiations of l0_search_kernel compile to the resource lines of the parent commit (compared line by line; "
+                       "l0_local_kernels.hpp includes l0_kernels.hpp and changes nothing in it)")
+# measured on a CPU with the committed restatement (tests/_l0_local_reference.py) against tests/_l0_reference.brute_force; the
+# test tests/test_l0_local_cpu.py asserts what these lines say, case by case
+LOCAL_HIT_COUNTS = (
+    "how often the rule finds the optimum (CPU, the numpy restatement against brute force; tests/test_l0_local_cpu.py): the law n = 30,",
+    "p = 14, AR(1) correlation 0.9, 4 true columns, SNR 2 (_l0_local_reference.hard_law), seeds 0 - 23, alpha in {0.02, 0.05, 0.1} var y, 72 cases:",
+    "    the descent alone at the exact optimum in 13 of 72, with swaps in 32 of 72; swaps strictly better in 39, never worse; never below the optimum",
+    "    (the prototype of the issue, on its own draw of that law: 11 and 41 of 72, strictly better in 55)",
+    "    so on this law the search MISSES the optimum in 40 of 72 cases: it is a local search, and the exact estimators are the yardstick to 128 columns",
+)
+
+
+def local_section(out_path, repeats, max_nodes):
+    import subprocess
+    import tempfile
+
+    from sklearn.datasets import make_regression
+
+    from sparselm_amd import _engine
+    from sparselm_amd.miqp import RegularizedL0, l0_local_search
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    lines = [f"l0 local search (l0_local_search, slm_solve_l0_local) on {name}, {dev['compute_units']} compute units",
+             f"(wall time of whole calls, each ending in a synchronise; every shape warmed first; {repeats} repeats with the variants alternating, "
+             "medians with the spread min .. max)", LOCAL_KERNEL_RESOURCES, LOCAL_OTHER_KERNELS, "", *LOCAL_HIT_COUNTS, ""]
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+
+    def say(line):  # (the file grows line by line: a run that is cut short leaves what it measured)
+        lines.append(line)
+        print(line, flush=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    def clock(fn):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t0 = time.perf_counter()
+            out = fn()
+            return out, (time.perf_counter() - t0) * 1e3
+
+    def fmt(ms):
+        return f"{np.median(ms):9.3f} ({min(ms):.3f} .. {max(ms):.3f})"
+
+    # ---- 1. beside the exact search: the reference's 290 x 66 data and 25 x 30 ----------------------------------------------------------
+    d = os.path.join(ROOT, "tests", "golden", "reference_examples")
+    Xr, yr = np.load(os.path.join(d, "corr.npy")), np.load(os.path.join(d, "energy.npy"))
+    Xs, ys = make_regression(25, 30, n_informative=10, noise=1.0, random_state=0)
+    for X, y, icpt, big_M, rels, exact_opts in ((Xr, yr, True, 100, np.logspace(-4, -1, 4), {"wide": True, "max_nodes": max_nodes}),
+                                                (Xs, ys, False, 1000, np.logspace(-4, 0, 5), {"max_nodes": max_nodes})):
+        alphas = rels * float(np.var(y))
+        local = lambda: l0_local_search(X, y, alphas=alphas, big_M=big_M, fit_intercept=icpt)  # noqa: E731
+        exact = lambda: [RegularizedL0(alpha=a, big_M=big_M, fit_intercept=icpt, solver_options=exact_opts).fit(X, y) for a in alphas]  # noqa: E731
+        clock(local), clock(exact)
+        t_loc, t_ex, path, ests = [], [], None, None
+        for _ in range(repeats):
+            (path, ms) = clock(local)
+            t_loc.append(ms)
+            (ests, ms) = clock(exact)
+            t_ex.append(ms)
+        say(f"{X.shape[0]} x {X.shape[1]}, fit_intercept = {icpt}, big_M = {big_M}, alphas / var y = {[float(f'{r:.1e}') for r in rels]}; the exact search under "
+            f"{max_nodes} nodes per fit")
+        say(f"{'what':46s} {'ms per call: median (min .. max)':>36s}")
+        say(f"{'l0_local_search, all alphas, max_rounds = 2':46s} {fmt(t_loc):>36s}   rounds {path.rounds_}, swaps {path.swaps_[:, 0].tolist()}, "
+            f"sweeps {path.sweeps_[:, 0].tolist()}, converged {path.converged_[:, 0].tolist()}")
+        say(f"{'the RegularizedL0 fits together':46s} {fmt(t_ex):>36s}")
+        for a, est in enumerate(ests):
+            info = est.solver_info_
+            kind = "proven optimum" if info["proven_optimal"] else "incumbent (budget ran out)"
+            gap = (path.objectives_[a, 0] - info["objective"]) / max(abs(info["objective"]), alphas[a])
+            say(f"    alpha / var y = {rels[a]:.1e}: local {path.objectives_[a, 0]:.10e} ({int(path.supports_[a, 0].sum())} columns), exact "
+                f"{info['objective']:.10e} ({int(est.active_groups_.sum())} columns, {kind}); relative gap {gap:+.3e}")
+        say("    (a call lasts as long as its slowest problem: the sweeps above are the winners'; a start that loses may run up to the cap of 10 000")
+        say("    sweeps -- with fewer rows than columns and a small alpha a neighbour's start can hold a singular set of columns -- and the entry")
+        say("    reports the winner's counts only, so where a call's time goes beyond them was not measured)")
+        say("")
+
+    # ---- 2. wide synthetic problems: the one launch against the host twin on one core ------------------------------------------------------
+    exe = os.path.join(tempfile.mkdtemp(), "l0_local_host_bench")
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", os.path.join(ROOT, "tools", "l0_local_host_bench.cpp"), "-o", exe], check=True)
+
+    def host(G, c, yy, alphas, etas, big_M, swaps=True):
+        p = len(c)
+        with tempfile.NamedTemporaryFile(suffix=".bin", delete=False) as fh:
+            np.array([p, p, len(alphas), int(swaps)], dtype=np.int64).tofile(fh)
+            np.array([yy, big_M], dtype=np.float64).tofile(fh)
+            for arr in (G, c, alphas, etas):
+                np.ascontiguousarray(arr, dtype=np.float64).tofile(fh)
+        try:
+            out = subprocess.run([exe, fh.name], check=True, capture_output=True, text=True).stdout.splitlines()
+        finally:
+            os.remove(fh.name)
+        words = out[0].split()
+        return {"ms": float(words[3]), "changes": int(words[5]), "sweeps": int(words[7]), "swaps": int(words[9]),
+                "F": np.array(out[1].split()[1:], dtype=float)}
+
+    say("synthetic: rows of independent standard normal columns, 20 true columns at random places with coefficients +-1, noise 0.5; eta = 0;")
+    say("alphas = geomspace(0.003, 0.3, cells) var y; big_M = 100; zero starts.  GPU: Dataset.solve_l0_local on a dataset that holds its Gram")
+    say("(the whole call: upload of the cells, ONE launch, read-back, the Gram to the host, the polish of every winner).  Host: l0_ls_solve of")
+    say("csrc/l0_host.hpp, g++ -O2, one core, the cells one after the other, the rule alone (no polish) on numpy's Gram.")
+    say(f"{'n x p':>10s} {'cells':>6s} {'GPU ms: median (min .. max)':>34s} {'host ms: median (min .. max)':>36s} {'GPU / host':>11s} {'changes':>9s} {'same F':>7s}")
+    wins = {}
+    per_change = []
+    for n, p in ((200, 512), (400, 1024)):
+        rng = np.random.default_rng(p)
+        X = rng.standard_normal((n, p))
+        beta = np.zeros(p)
+        beta[rng.choice(p, 20, replace=False)] = (-1.0) ** np.arange(20)
+        y = X @ beta + 0.5 * rng.standard_normal(n)
+        G, c, yy = X.T @ X / n, X.T @ y / n, float(y @ y) / n
+        with _engine.get_engine().dataset(X, y) as ds:
+            for cells in (1, 16, 64, 256):
+                alphas = (np.geomspace(0.003, 0.3, cells) if cells > 1 else np.array([0.03])) * float(np.var(y))
+                etas = np.zeros(cells)
+                gpu = lambda: ds.solve_l0_local(alphas, etas, big_M=100.0)  # noqa: E731
+                clock(gpu), host(G, c, yy, alphas, etas, 100.0)
+                t_gpu, t_host, res, ref = [], [], None, None
+                for _ in range(repeats):
+                    (res, ms) = clock(gpu)
+                    t_gpu.append(ms)
+                    ref = host(G, c, yy, alphas, etas, 100.0)
+                    t_host.append(ref["ms"])
+                before = np.array([info["descent_objective"] for info in res[3]])
+                same = int(np.sum(np.abs(before - ref["F"]) <= 1e-9 * np.maximum(np.abs(ref["F"]), alphas)))
+                ratio = np.median(t_gpu) / np.median(t_host)
+                wins.setdefault((n, p), []).append((cells, ratio))
+                say(f"{f'{n} x {p}':>10s} {cells:6d} {fmt(t_gpu):>34s} {fmt(t_host):>36s} {ratio:11.3f} {ref['changes']:9d} {same:4d}/{cells}")
+            if p == 1024:  # ---- 3. the time of one applied change: single cells that differ in their number of changes ----------------
+                for rel in (0.3, 0.01, 0.003):
+                    alphas = np.array([rel * float(np.var(y))])
+                    gpu = lambda: ds.solve_l0_local(alphas, np.zeros(1), big_M=100.0)  # noqa: E731
+                    clock(gpu)
+                    ts = [clock(gpu)[1] for _ in range(repeats)]
+                    ref = host(G, c, yy, alphas, np.zeros(1), 100.0)
+                    per_change.append((rel, float(np.median(ts)), ref["changes"], ref["ms"]))
+    say("")
+    for (n, p), rows in wins.items():
+        won = [cells for cells, ratio in rows if ratio < 1.0]
+        say(f"{n} x {p}: the launch " + (f"wins from {min(won)} cells on (of 1, 16, 64, 256)" if won else "did not win at any of 1, 16, 64, 256 cells"))
+    say("")
+    say("time per applied coordinate change at 400 x 1024, single cells (one wavefront), whole calls:")
+    for rel, ms, changes, host_ms in per_change:
+        say(f"    alpha = {rel:g} var y: {changes:7d} changes, GPU call {ms:9.3f} ms, host rule {host_ms:9.3f} ms")
+    (_, t0, c0, h0), (_, t1, c1, h1) = per_change[0], per_change[-1]
+    if c1 > c0:
+        say(f"    slope between the first and the last: GPU {(t1 - t0) / (c1 - c0) * 1e3:.2f} us per change (one dependent 8 KB row read, the next scan), "
+            f"host {(h1 - h0) / (c1 - c0) * 1e3:.2f} us per change")
+    say("")
+    say("NOT measured: the kernel alone (no event bracket: the whole call is what a caller pays, and it carries the 8 p^2-byte copy of the Gram to")
+    say("the host for the polish); more than one start per cell; eta > 0; correlated designs, where sweeps and swaps multiply; devices with")
+    say("fewer compute units; the host twin on several cores (the cells are independent: a 16-core host divides its column by up to 16).")
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -674,8 +839,12 @@ def main():
     ap.add_argument("--l1-profile-out", default=os.path.join(ROOT, "profiles", "l1l0_profile.txt"))
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--grid-cv-out", default=os.path.join(ROOT, "profiles", "l0_grid_cv.txt"))
-    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile", "gridcv"], default=None)
+    ap.add_argument("--local-out", default=os.path.join(ROOT, "profiles", "l0_local.txt"))
+    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile", "gridcv", "local"], default=None)
     args = ap.parse_args()
+    if args.only == "local":
+        local_section(args.local_out, max(1, args.repeats), args.max_nodes)
+        return
     if args.only == "gridcv":
         grid_cv_section(args.grid_cv_out, max(1, args.repeats), args.max_nodes)
         return
