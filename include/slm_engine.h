@@ -832,8 +832,8 @@ int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* cons
  * Refusals, all before a device is touched, each with its own message: p > 1024, groups that are not singletons, a
  * row-sharded dataset (SLM_ERR_UNSUPPORTED); a negative or non-finite alphas[e] or etas[e], big_M < 0, n_cells < 1,
  * n_starts < 1, n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS = 8192, a start outside the box (SLM_ERR_BAD_ARG).
- * Not here: groups and a hierarchy, a bound on the cardinality, an l1 term, a Tikhonov matrix, constraints, row sets (CV
- * folds) in the launch.
+ * Not here: groups and a hierarchy, a bound on the cardinality, an l1 term, a Tikhonov matrix, constraints.  Row sets (CV
+ * folds) in the launch: slm_solve_l0_local_folds, below.
  */
 #define SLM_L0_LOCAL_PMAX 1024
 #define SLM_L0_LOCAL_MAX_PROBLEMS 8192
@@ -844,6 +844,39 @@ int slm_solve_l0_local(slm_dataset* ds, int32_t n_cells, const double* alphas, c
 int slm_solve_l0_local_descent(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
                                int32_t n_starts, const double* starts, double* beta_out, double* objective_out, int32_t* start_out,
                                slm_point_info* info);
+
+/*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_local, no existing entry, structure or constant changes, so the version
+ * stays 24 -- a caller that needs it looks the symbol up.)  The l0 local search on `count` ROW SETS of one dataset -- the
+ * training rows of a cross-validation's folds and all rows -- from ONE launch.  Row sets (row_weights, n_effs, NULL entries,
+ * 1 <= count <= 16) and intercept exactly as for slm_solve_l0_profile_batch: with intercept != 0 the dataset is [X | 1], the
+ * ones column last and alone in the last group; it is not searched but eliminated from every row set's Gram (the Schur
+ * complement: weighted centring of X and y by the row set's own means), so ps = p - 1 columns are searched and the dataset may
+ * hold SLM_L0_LOCAL_PMAX + 1 = 1025; else ps = p.  The Grams come from one slm_dataset_covariance_folds call when every entry
+ * of row_weights is given, else from one slm_dataset_covariance call per row set; they are found again by fingerprint and
+ * never modified (the eliminated copies live in a workspace of the call, count * ps * ld doubles; without an intercept the
+ * kernel reads the store in place).  Problem (r * n_cells + e) * n_starts + s is row set r, cell e (alphas[e], etas[e]:
+ * shared by the row sets), start s; starts and stat_out are in that order, every other output is [r * n_cells + e].
+ * swaps == 0: without the swap scan, as slm_solve_l0_local_descent.  Per (row set, cell) the winner among the starts, its
+ * polish (on the eliminated Gram when there is an intercept) and info follow slm_solve_l0_local;
+ * intercept_out = ymean_r - xmean_r^T beta (0 without an intercept).  stat_out (may be NULL): sweeps, accepted swaps, status
+ * word and non-zeros of EVERY problem, the losing starts included.  With count = 1, row_weights[0] = NULL and no intercept
+ * every output equals slm_solve_l0_local's (swaps == 0: _descent's) byte for byte.
+ * Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when some winner reached a cap.
+ * Refusals, all before a device is touched, each with its own message: those of slm_solve_l0_local (the width counts ps);
+ * count outside 1 .. 16, a negative or non-finite weight, an intercept column that is not last and alone (SLM_ERR_BAD_ARG);
+ * count * n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS (the message names the three factors).  A row set that gives the
+ * ones column no weight is refused once its Gram is there.
+ * Not here: groups, a bound on the cardinality, an l1 term, more than 16 row sets.
+ */
+int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
+                             const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
+                             const double* etas /* [n_cells] each */, double big_M, int32_t n_starts,
+                             const double* starts /* count * n_cells * n_starts * ps, or NULL: one zero start */, int32_t swaps,
+                             double* beta_out /* count * n_cells * ps */, double* intercept_out /* count * n_cells, or NULL */,
+                             double* objective_out /* count * n_cells */, int32_t* start_out /* or NULL */,
+                             int32_t* stat_out /* count * n_cells * n_starts * 4: sweeps, swaps, status word, non-zeros of EVERY problem; or NULL */,
+                             slm_point_info* info /* count * n_cells, or NULL */);
 
 /*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant

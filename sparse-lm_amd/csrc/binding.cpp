@@ -542,6 +542,49 @@ py::tuple solve_l0_local(uintptr_t ds, int64_t p, int32_t n_cells, const arr_d& 
   return py::make_tuple(beta, objective, winner, info, rc);
 }
 
+// slm_solve_l0_local_folds: the local search on several row sets of one dataset from one launch.  row_weights: a sequence of
+// arrays of n weights or None; n_effs: as many integers.  starts: None or count * n_cells * n_starts * ps doubles.  Returns
+// (coefficients [count * n_cells][ps], intercepts, objectives, winning starts [count * n_cells], the four status words of every
+// problem [count * n_cells * n_starts][4], records as bytes, status); ps = p - 1 with an intercept.
+py::tuple solve_l0_local_folds(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
+                               int32_t n_cells, const arr_d& alphas, const arr_d& etas, double big_M, int32_t n_starts,
+                               const py::object& starts, bool swaps) {
+  const py::ssize_t count = (py::ssize_t)py::len(row_weights);
+  if ((py::ssize_t)py::len(n_effs) != count) throw py::value_error("row_weights and n_effs differ in length");
+  const int64_t cells = n_cells > 0 ? n_cells : 0;
+  if ((int64_t)alphas.size() < cells || (int64_t)etas.size() < cells) throw py::value_error("alphas and etas must have n_cells entries");
+  const int64_t ps = intercept && p > 0 ? p - 1 : p;
+  // (no row set, no cell, more problems than any call takes: the engine refuses them, the outputs only have to exist)
+  const bool sized = count >= 1 && count <= 16 && n_cells >= 1 && n_starts >= 1 && (int64_t)n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS &&
+                     (int64_t)count * n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS;
+  Keep keep;
+  const double* sp = sized ? vector_arg(starts, (int64_t)count * n_cells * n_starts * ps, "starts", keep) : nullptr;
+  std::vector<const double*> wp((size_t)count);
+  std::vector<int64_t> ne((size_t)count);
+  for (py::ssize_t b = 0; b < count; ++b) {
+    wp[(size_t)b] = vector_arg(row_weights[b], n, "row_weights", keep);
+    ne[(size_t)b] = n_effs[b].cast<int64_t>();
+  }
+  const py::ssize_t cnt = sized ? count * n_cells : 1, problems = sized ? cnt * n_starts : 1;
+  py::array_t<double> beta({cnt, (py::ssize_t)ps}), icpt(cnt), objective(cnt);
+  py::array_t<int32_t> winner(cnt), stats({problems, (py::ssize_t)4});
+  py::array info = info_bytes(cnt);
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
+  double *bp = beta.mutable_data(), *ip = icpt.mutable_data(), *op = objective.mutable_data();
+  int32_t *wn = winner.mutable_data(), *tp = stats.mutable_data();
+  std::memset(wn, 0, sizeof(int32_t) * (size_t)cnt);
+  std::memset(tp, 0, sizeof(int32_t) * 4 * (size_t)problems);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_local_folds(reinterpret_cast<slm_dataset*>(ds), (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, n_cells,
+                                  alphas.data(), etas.data(), big_M, n_starts, sp, swaps ? 1 : 0, bp, ip, op, wn, tp, rec);
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, icpt, objective, winner, stats, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -570,6 +613,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_l1_profile_wide", &solve_l0_l1_profile_wide);
   m.def("solve_l0_local", &solve_l0_local<true>);
   m.def("solve_l0_local_descent", &solve_l0_local<false>);
+  m.def("solve_l0_local_folds", &solve_l0_local_folds);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

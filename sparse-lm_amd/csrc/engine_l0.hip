@@ -34,7 +34,8 @@
 //       one launch.  Gram and elimination once per row set; order, seed, (l1: the bound) and the copy of the block per problem.
 //       slm_solve_l0_profile_batch is its call with one ridge eta.
 // Beside them, and none of the above: slm_solve_l0_local, slm_solve_l0_local_descent (solve_l0_local_impl, at the end of the
-// unit; csrc/l0_local_kernels.hpp) -- the local search beyond 128 columns, which proves nothing.
+// unit; csrc/l0_local_kernels.hpp) -- the local search beyond 128 columns, which proves nothing -- and
+// slm_solve_l0_local_folds (solve_l0_local_folds_impl), the same search on up to 16 row sets of the dataset in one launch.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -906,8 +907,10 @@ int solve_l0_local_impl(bool swaps, slm_dataset* ds, int32_t n_cells, const doub
     HIP_TRY(hipMemcpyAsync(dd, h.data(), sizeof(double) * off_F, hipMemcpyHostToDevice, s));
     L0LsArgs k;
     memset(&k, 0, sizeof(k));
-    k.G = ds->cov[(size_t)entry].G;
-    k.c = ds->cov[(size_t)entry].c;
+    k.G[0] = ds->cov[(size_t)entry].G;  // (one row set: problem q is cell q / n_starts)
+    k.c[0] = ds->cov[(size_t)entry].c;
+    k.yy[0] = ds->cov[(size_t)entry].yy;
+    k.n_cells = n_cells;
     k.ld = (long long)ds->ld;
     k.alphas = dd;
     k.etas = dd + off_eta;
@@ -917,7 +920,6 @@ int solve_l0_local_impl(bool swaps, slm_dataset* ds, int32_t n_cells, const doub
     k.beta_out = dd + off_beta;
     k.p = p; k.n_problems = problems; k.n_starts = n_starts; k.swaps = swaps ? 1 : 0;
     k.big_M = big_M;
-    k.yy = ds->cov[(size_t)entry].yy;
     // (a problem is one wave.  The kernel's registers leave one workgroup of L0_WAVES waves resident per CU; twice that many are
     // launched so that a CU whose problems end early takes up another workgroup, and the problems beyond 2 cus workgroups are reached
     // by the kernel's grid-stride loop)
@@ -967,7 +969,287 @@ int solve_l0_local_impl(bool swaps, slm_dataset* ds, int32_t n_cells, const doub
   return SLM_OK;
 }
 
+// Rows `rows` (ascending) of a device Gram [.][ld], their first `width` entries, to the host: out[k * width + j].  A few rows
+// go one copy each; many go as one strided copy of the stretch that holds them.
+int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const std::vector<int>& rows, std::vector<double>& out) {
+  out.assign(rows.size() * (size_t)width, 0.0);
+  if (rows.empty()) return SLM_OK;
+  if (rows.size() <= 64) {
+    for (size_t k = 0; k < rows.size(); ++k)
+      HIP_TRY(hipMemcpyAsync(out.data() + k * (size_t)width, G + (size_t)rows[k] * ld, sizeof(double) * (size_t)width, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SLM_OK;
+  }
+  const int lo = rows.front(), span = rows.back() - lo + 1;
+  std::vector<double> all((size_t)span * (size_t)width);
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy2D(all.data(), sizeof(double) * (size_t)width, G + (size_t)lo * ld, sizeof(double) * ld, sizeof(double) * (size_t)width,
+                      (size_t)span, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < rows.size(); ++k)
+    memcpy(out.data() + k * (size_t)width, all.data() + (size_t)(rows[k] - lo) * (size_t)width, sizeof(double) * (size_t)width);
+  return SLM_OK;
+}
+
+// slm_solve_l0_local_folds (DESIGN 4d "Local search over folds"): solve_l0_local_impl on `count` row sets of one dataset -- the
+// training rows of a cross-validation's folds, then all rows -- from ONE launch of l0_local_kernel.  check (l0_lsf_check and
+// the dataset's shape, before a device is touched); the Grams as in solve_l0_profile_grid_impl (one slm_dataset_covariance_folds
+// call when every row set brings its weights, else one by one; found again by fingerprint), each HELD for the call, so that a
+// later build cannot push it out from under the kernel; with an intercept the ones column (last, alone in its group) is
+// eliminated per row set: the vectors on the host (l0_eliminate_vectors, from the last row of each Gram), the matrices by one
+// launch of l0_eliminate_kernel into a workspace of count * ps * ld doubles -- without an intercept nothing is copied and
+// the kernel reads the store in place; ONE launch over every (row set, cell, start) problem; per (row set, cell) the best
+// start by (F, then the lowest index), polished on host copies of ONLY the rows of its Gram that the winners of that row set
+// hold (l0_fetch_rows: the polish and the loss read nothing else); the record of solve_l0_local_impl's table per (row set,
+// cell); stat_out: the four status words of EVERY problem.
+int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs, int32_t intercept,
+                              int32_t n_cells, const double* alphas, const double* etas, double big_M, int32_t n_starts,
+                              const double* starts, int32_t swaps, double* beta_out, double* intercept_out, double* objective_out,
+                              int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
+  if (!ds || !beta_out || !objective_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  const int drop = intercept != 0 ? 1 : 0;
+  bool alone = ds->p >= 1;  // the ones column: last, alone in the last group
+  if (drop && !ds->singleton) {
+    const int G = ds->G;
+    alone = alone && G >= 1;
+    for (int64_t j = 0; j < ds->p && alone && !ds->h_gid.empty(); ++j) alone = (ds->h_gid[(size_t)j] == G - 1) == (j == ds->p - 1);
+  }
+  static_assert(sizeof(long long) == sizeof(int64_t), "n_effs goes to the host logic as it is");
+  const L0LsfRefusal R = l0_lsf_check(count, row_weights, reinterpret_cast<const long long*>(n_effs), ds->n, drop != 0, alone, n_cells, alphas,
+                                      etas, big_M, n_starts, starts, ds->p);
+  switch (R.kind) {
+    case L0_LSF_OK: break;
+    case L0_LSF_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    case L0_LSF_COUNT: return fail(SLM_ERR_BAD_ARG, "count must be 1 .. %d, the Gram store's capacity (got %d)", L0_LS_ROW_SETS, count);
+    case L0_LSF_PRODUCT:
+      return fail(SLM_ERR_BAD_ARG, "count * n_cells * n_starts must be at most %d problems (got %d x %d x %d)", L0_LS_MAX_PROBLEMS, count,
+                  n_cells, n_starts);
+    case L0_LSF_INTERCEPT: return fail(SLM_ERR_BAD_ARG, "intercept: the last column must be alone in the last group");
+    case L0_LSF_WEIGHT: return fail(SLM_ERR_BAD_ARG, "row_weights[%d][%lld] must be finite and >= 0", R.row_set, R.which);
+    case L0_LSF_LS:
+      switch (R.ls) {
+        case L0_LS_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
+        case L0_LS_STARTS: return fail(SLM_ERR_BAD_ARG, "n_starts must be >= 1 (got %d)", n_starts);
+        case L0_LS_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
+        case L0_LS_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", R.which);
+        case L0_LS_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", R.which);
+        case L0_LS_WIDTH:
+          return fail(SLM_ERR_UNSUPPORTED, "the l0 local search takes up to %d columns%s (got %lld)", L0_LS_PMAX,
+                      drop ? " beside the intercept's" : "", (long long)ds->p - drop);
+        case L0_LS_START_BOX:
+          return fail(SLM_ERR_BAD_ARG, "starts[%lld] lies outside the box |beta_j| <= big_M = %g (or is not a number)", R.which, big_M);
+        default: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+      }
+  }
+  if (!ds->singleton) return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for groups: every column must be its own group");
+  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for row-sharded datasets");
+  const int p = (int)ds->p, ps = p - drop, per_set = n_cells * n_starts, problems = count * per_set;
+  const int64_t n = ds->n;
+  const size_t ld = (size_t)ds->ld;
+  slm_engine* eng = ds->eng;
+  HIP_TRY(hipSetDevice(eng->device));
+  hipStream_t s = eng->stream;
+
+  // ---- the Grams: the folds' in one call when every row set brings its weights, else one by one; each held for the call ----------
+  bool all_given = true;
+  for (int b = 0; b < count; ++b) all_given = all_given && row_weights[b] != nullptr;
+  struct Weights {
+    double* dev = nullptr;
+    hipStream_t s;
+    ~Weights() {
+      (void)hipStreamSynchronize(s);
+      dfree(dev);
+    }
+  } wts;
+  wts.s = s;
+  SLM_TRY(dalloc(&wts.dev, (size_t)count * (size_t)n));
+  std::vector<const double*> wdev((size_t)count);
+  std::vector<double> neff((size_t)count);
+  for (int b = 0; b < count; ++b) {
+    neff[(size_t)b] = row_weights[b] && n_effs[b] > 0 ? (double)n_effs[b] : (double)ds->n_global;
+    wdev[(size_t)b] = ds->rw;
+    if (!row_weights[b]) continue;
+    wdev[(size_t)b] = wts.dev + (size_t)b * (size_t)n;
+    HIP_TRY(hipMemcpyAsync(wts.dev + (size_t)b * (size_t)n, row_weights[b], sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  if (all_given) SLM_TRY(slm_dataset_covariance_folds(ds, row_weights, n_effs, count));
+  std::vector<double> fp(2 * (size_t)count);
+  SLM_TRY(cov_fingerprints(ds, wdev.data(), count, fp.data()));
+  std::vector<slm_dataset::CovEntry> held((size_t)count);  // (a copy holds the entry's blocks: the store may drop it, the memory stays)
+  for (int b = 0; b < count; ++b) {
+    int entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
+    if (entry < 0) {  // not from the folds' call (or pushed out of the store by a later one): built here
+      SLM_TRY(slm_dataset_covariance(ds, row_weights[b], row_weights[b] ? n_effs[b] : 0));
+      entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
+    }
+    if (entry < 0) return fail(SLM_ERR_HIP, "the Gram of row set %d was not filed", b);
+    held[(size_t)b] = ds->cov[(size_t)entry];
+  }
+
+  // ---- per row set: c on the host (the polish reads it); with an intercept the last row of G too, and the eliminated vectors ---------
+  std::vector<double> ch((size_t)count * p), last((size_t)count * p), cs((size_t)count * ld, 0.0), xmean((size_t)count * ps, 0.0);
+  std::vector<double> ymean((size_t)count, 0.0), yy((size_t)count, 0.0);
+  for (int b = 0; b < count; ++b) {
+    HIP_TRY(hipMemcpyAsync(ch.data() + (size_t)b * p, held[(size_t)b].c, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
+    if (drop)
+      HIP_TRY(hipMemcpyAsync(last.data() + (size_t)b * p, held[(size_t)b].G + (size_t)ps * ld, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  for (double v : ch)
+    if (!std::isfinite(v)) return fail(SLM_ERR_NON_FINITE, "X^T y holds a non-finite value (non-finite data)");
+  for (int b = 0; b < count; ++b) {
+    yy[(size_t)b] = held[(size_t)b].yy;
+    if (!drop) continue;
+    const double* g1 = last.data() + (size_t)b * p;
+    for (int j = 0; j < p; ++j)
+      if (!std::isfinite(g1[j])) return fail(SLM_ERR_NON_FINITE, "the Gram holds a non-finite value (non-finite data)");
+    if (!l0_eliminate_vectors(g1, g1[ps], ch.data() + (size_t)b * p, ps, held[(size_t)b].yy, cs.data() + (size_t)b * ld, &yy[(size_t)b],
+                              xmean.data() + (size_t)b * ps, &ymean[(size_t)b]))
+      return fail(SLM_ERR_BAD_ARG, "intercept: row set %d gives the last column no weight", b);
+  }
+  // (what the kernel and the polish take for row set b's c: the eliminated vector, or the store's)
+  auto c_host = [&](int b) { return drop ? cs.data() + (size_t)b * ld : ch.data() + (size_t)b * p; };
+
+  // ---- one block: alphas | etas | starts | the eliminated c, then what comes back: F | the four status words | beta; the workspace --------
+  const size_t n_start_words = starts ? (size_t)problems * ps : 0, n_c_words = drop ? (size_t)count * ld : 0;
+  const size_t off_eta = (size_t)n_cells, off_st = 2 * (size_t)n_cells, off_c = off_st + n_start_words, off_F = off_c + n_c_words,
+               off_stat = off_F + (size_t)problems, off_beta = off_stat + 2 * (size_t)problems, words = off_beta + (size_t)problems * ps;
+  const size_t ws_stride = (size_t)ps * ld;
+  std::vector<double> h(words, 0.0);
+  memcpy(h.data(), alphas, sizeof(double) * (size_t)n_cells);
+  memcpy(h.data() + off_eta, etas, sizeof(double) * (size_t)n_cells);
+  if (starts) memcpy(h.data() + off_st, starts, sizeof(double) * n_start_words);
+  if (drop) memcpy(h.data() + off_c, cs.data(), sizeof(double) * n_c_words);
+  unsigned long long *dev = nullptr, *ws = nullptr;
+  L0DevGuard guard{dev, s}, ws_guard{ws, s};
+  SLM_TRY(dalloc(&dev, words));
+  if (drop) SLM_TRY(dalloc(&ws, (size_t)count * ws_stride));
+  double *dd = reinterpret_cast<double*>(dev), *wd = reinterpret_cast<double*>(ws);
+  std::vector<const double*> Gdev((size_t)count);
+  {
+    HIP_TRY(hipMemcpyAsync(dd, h.data(), sizeof(double) * off_F, hipMemcpyHostToDevice, s));
+    L0LsArgs k;
+    memset(&k, 0, sizeof(k));
+    if (drop) {
+      L0ElimArgs e;
+      memset(&e, 0, sizeof(e));
+      for (int b = 0; b < count; ++b) e.G[b] = held[(size_t)b].G;
+      e.out = wd;
+      e.ld = (long long)ld;
+      e.stride = (long long)ws_stride;
+      e.ps = ps;
+      if (ps > 0) {
+        const unsigned bx = (unsigned)std::min<size_t>(4, (ld + 255) / 256);
+        hipLaunchKernelGGL(l0_eliminate_kernel, dim3(bx, (unsigned)ps, (unsigned)count), dim3(256), 0, s, e);
+        SLM_TRY(check_launch());
+      }
+    }
+    for (int b = 0; b < count; ++b) {
+      Gdev[(size_t)b] = drop ? wd + (size_t)b * ws_stride : held[(size_t)b].G;
+      k.G[b] = Gdev[(size_t)b];
+      k.c[b] = drop ? dd + off_c + (size_t)b * ld : held[(size_t)b].c;
+      k.yy[b] = yy[(size_t)b];
+    }
+    k.ld = (long long)ld;
+    k.alphas = dd;
+    k.etas = dd + off_eta;
+    k.starts = starts ? dd + off_st : nullptr;
+    k.F_out = dd + off_F;
+    k.stat_out = reinterpret_cast<int*>(dd + off_stat);
+    k.beta_out = dd + off_beta;
+    k.p = ps; k.n_problems = problems; k.n_starts = n_starts; k.swaps = swaps ? 1 : 0; k.n_cells = n_cells;
+    k.big_M = big_M;
+    // (the grid of solve_l0_local_impl: two workgroups per CU, the rest by the kernel's grid-stride loop)
+    const int blocks = std::min((problems + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
+    hipLaunchKernelGGL(l0_local_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    SLM_TRY(check_launch());
+    HIP_TRY(hipMemcpyAsync(h.data() + off_F, dd + off_F, sizeof(double) * (words - off_F), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  const int* stat = reinterpret_cast<const int*>(h.data() + off_stat);
+  if (stat_out) memcpy(stat_out, stat, sizeof(int32_t) * 4 * (size_t)problems);
+
+  // ---- per (row set, cell): the best start; per row set the rows its winners hold, and on them the polish and the record -----------
+  int unconverged = 0, first_set = -1, first_cell = -1;
+  std::vector<int> win((size_t)n_cells), rows, at((size_t)std::max(ps, 1));
+  std::vector<double> Grows, Gc, cc, bc;
+  for (int b = 0; b < count; ++b) {
+    std::vector<char> used((size_t)std::max(ps, 1), 0);
+    for (int cell = 0; cell < n_cells; ++cell) {
+      const size_t q0 = (size_t)l0_lsf_index(b, cell, 0, n_cells, n_starts);
+      int w = 0;
+      for (int st = 1; st < n_starts; ++st)
+        if (h[off_F + q0 + st] < h[off_F + q0 + w]) w = st;  // (ties: the lowest index)
+      win[(size_t)cell] = w;
+      const double* beta = h.data() + off_beta + (q0 + w) * ps;
+      for (int j = 0; j < ps; ++j) used[(size_t)j] = used[(size_t)j] || beta[j] != 0.0;
+    }
+    rows.clear();
+    for (int j = 0; j < ps; ++j)
+      if (used[(size_t)j]) {
+        at[(size_t)j] = (int)rows.size();
+        rows.push_back(j);
+      }
+    const int m = (int)rows.size();
+    SLM_TRY(l0_fetch_rows(s, Gdev[(size_t)b], ld, ps, rows, Grows));
+    for (double v : Grows)
+      if (!std::isfinite(v)) return fail(SLM_ERR_NON_FINITE, "the Gram holds a non-finite value (non-finite data)");
+    // the Gram on those columns alone, in their order: the polish and the loss read entries between non-zeros only
+    Gc.assign((size_t)m * m, 0.0);
+    cc.assign((size_t)m, 0.0);
+    bc.assign((size_t)m, 0.0);
+    for (int a = 0; a < m; ++a) {
+      cc[(size_t)a] = c_host(b)[rows[(size_t)a]];
+      for (int k2 = 0; k2 < m; ++k2) Gc[(size_t)a * m + k2] = Grows[(size_t)a * ps + rows[(size_t)k2]];
+    }
+    for (int cell = 0; cell < n_cells; ++cell) {
+      const size_t rc = (size_t)b * n_cells + cell, q = (size_t)l0_lsf_index(b, cell, win[(size_t)cell], n_cells, n_starts);
+      double* beta = beta_out + rc * ps;
+      memcpy(beta, h.data() + off_beta + q * ps, sizeof(double) * (size_t)ps);
+      for (int a = 0; a < m; ++a) bc[(size_t)a] = beta[rows[(size_t)a]];
+      const double quad = l0_ls_polish(Gc.data(), (size_t)m, cc.data(), m, etas[cell], big_M, bc.data());
+      int nnz = 0;
+      double bn = 0.0, dot = 0.0;
+      for (int a = 0; a < m; ++a) beta[rows[(size_t)a]] = bc[(size_t)a];
+      for (int j = 0; j < ps; ++j) {
+        nnz += beta[j] != 0.0;
+        bn += beta[j] * beta[j];
+        if (drop) dot += xmean[(size_t)b * ps + j] * beta[j];
+      }
+      objective_out[rc] = quad + alphas[cell] * (double)nnz;
+      if (intercept_out) intercept_out[rc] = drop ? ymean[(size_t)b] - dot : 0.0;
+      if (start_out) start_out[rc] = win[(size_t)cell];
+      const bool done = stat[4 * q + 2] == 0;
+      if (!done && unconverged++ == 0) {
+        first_set = b;
+        first_cell = cell;
+      }
+      if (info) {
+        l0_report(info + rc, done, l0_gram_loss(Gc.data(), cc.data(), m, yy[(size_t)b], bc.data()), objective_out[rc], h[off_F + q], -HUGE_VAL);
+        info[rc].n_iter = stat[4 * q + 0];
+        info[rc].rejects = stat[4 * q + 1];
+        info[rc].resid = (double)stat[4 * q + 2];
+        info[rc].beta_norm = std::sqrt(bn);
+        info[rc].mode = 8;
+      }
+    }
+  }
+  if (unconverged)
+    return fail(SLM_ERR_NOT_CONVERGED, "the local search reached a cap (%d sweeps per descent, %d swaps) in %d of %d (row set, cell) pairs "
+                "(the first: row set %d, cell %d): their last points are returned", L0_CD_SWEEPS, L0_LS_SWAPS, unconverged, count * n_cells,
+                first_set, first_cell);
+  return SLM_OK;
+}
+
 }  // namespace
+
+// The l0 local search on up to 16 row sets of one dataset: every (row set, cell, start) problem from one launch.
+extern "C" int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                                        int32_t intercept, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                        int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
+                                        double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
+  return solve_l0_local_folds_impl(ds, count, row_weights, n_effs, intercept, n_cells, alphas, etas, big_M, n_starts, starts, swaps, beta_out,
+                                   intercept_out, objective_out, start_out, stat_out, info);
+}
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.
 extern "C" int slm_solve_l0_local(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,

@@ -1181,6 +1181,7 @@ constexpr int L0_LS_SWAPS = 10000;           // accepted swaps of one problem; r
 constexpr double L0_LS_SWAP_TOL = 1e-10;     // a swap must gain this much, relative to max(|g_i|, alpha)
 constexpr int L0_LS_MAX_PROBLEMS = 8192;     // (cell, start) problems of one call
 constexpr int L0_LS_SWEEPS_OUT = 1, L0_LS_SWAPS_OUT = 2;  // bits of a problem's status word: which cap it reached
+constexpr int L0_LS_ROW_SETS = 16;           // row sets of one slm_solve_l0_local_folds call: what the dataset's Gram store holds
 
 // coordinate j given the others: u = r_j + d_j beta_j, b = clip(u / d_j), gain = u b - 1/2 d_j b^2 (what F without the alpha
 // term falls by when beta_j goes from 0 to b)
@@ -1362,6 +1363,95 @@ inline L0LsRefusal l0_ls_check(long long n_cells, const double* alphas, const do
       return L0_LS_START_BOX;
     }
   return L0_LS_OK;
+}
+
+// ---- local search over row sets (slm_solve_l0_local_folds; tests/l0_local_folds_host_test.cpp) ---------------------------------
+//
+// The same problems on `count` row sets of one dataset -- a cross-validation's training rows, then all rows -- in one launch.
+// Problem q = (r * n_cells + e) * n_starts + s is row set r, cell e, start s; l0_lsf_split is the inverse.
+constexpr int l0_lsf_index(int r, int e, int s, int n_cells, int n_starts) { return (r * n_cells + e) * n_starts + s; }
+struct L0LsfProblem {
+  int r, e, s;
+};
+constexpr L0LsfProblem l0_lsf_split(int q, int n_cells, int n_starts) {
+  return L0LsfProblem{q / n_starts / n_cells, q / n_starts % n_cells, q % n_starts};
+}
+
+// What slm_solve_l0_local_folds refuses before a device is touched, in this order.  L0_LSF_LS: what slm_solve_l0_local
+// refuses too -- `ls` says which; its limit on the problems is reported as L0_LSF_PRODUCT, the cap on all three factors.
+// which: the offending index (a cell, a row of row set `row_set`, an entry of starts).
+enum L0LsfKind { L0_LSF_OK = 0, L0_LSF_COUNT, L0_LSF_NULL, L0_LSF_LS, L0_LSF_PRODUCT, L0_LSF_INTERCEPT, L0_LSF_WEIGHT };
+struct L0LsfRefusal {
+  L0LsfKind kind = L0_LSF_OK;
+  L0LsRefusal ls = L0_LS_OK;
+  long long which = 0;
+  int row_set = 0;
+};
+// p: the dataset's columns, the ones column included when `intercept`; last_alone: that column is last and alone in its group;
+// n: the rows (the length of every given row_weights[r]).
+inline L0LsfRefusal l0_lsf_check(long long count, const double* const* row_weights, const long long* n_effs, long long n, bool intercept,
+                                 bool last_alone, long long n_cells, const double* alphas, const double* etas, double big_M,
+                                 long long n_starts, const double* starts, long long p) {
+  L0LsfRefusal R;
+  auto refuse = [&](L0LsfKind kind, L0LsRefusal ls = L0_LS_OK) {
+    R.kind = kind;
+    R.ls = ls;
+    return R;
+  };
+  if (count < 1 || count > L0_LS_ROW_SETS) return refuse(L0_LSF_COUNT);  // (first, as in the batch entry: no row set, no table of them)
+  if (!row_weights || !n_effs || !alphas || !etas) return refuse(L0_LSF_NULL);
+  const long long ps = p - (intercept ? 1 : 0);
+  // (the product where l0_ls_check has its own of two factors: behind n_cells and n_starts, before big_M and the cells)
+  if (n_cells >= 1 && n_starts >= 1 &&
+      (n_cells > L0_LS_MAX_PROBLEMS || n_starts > L0_LS_MAX_PROBLEMS || count * n_cells * n_starts > L0_LS_MAX_PROBLEMS))
+    return refuse(L0_LSF_PRODUCT);
+  const L0LsRefusal ls = l0_ls_check(n_cells, alphas, etas, big_M, n_starts, nullptr, 0, &R.which);  // (the width and the box: below)
+  if (ls != L0_LS_OK) return refuse(L0_LSF_LS, ls);
+  R.which = 0;
+  if (ps > L0_LS_PMAX) return refuse(L0_LSF_LS, L0_LS_WIDTH);
+  if (intercept && (p < 1 || !last_alone)) return refuse(L0_LSF_INTERCEPT);
+  for (int r = 0; r < (int)count; ++r)
+    for (long long i = 0; i < n && row_weights[r]; ++i)
+      if (!(row_weights[r][i] >= 0.0) || !std::isfinite(row_weights[r][i])) {
+        R.row_set = r;
+        R.which = i;
+        return refuse(L0_LSF_WEIGHT);
+      }
+  for (long long e = 0; starts && e < count * n_cells * n_starts * ps; ++e)
+    if (!(std::fabs(starts[e]) <= big_M)) {  // (a NaN fails too)
+      R.which = e;
+      return refuse(L0_LSF_LS, L0_LS_START_BOX);
+    }
+  return R;
+}
+
+// l0_eliminate_last at a leading dimension, in two parts (the note on cancellation above it applies unchanged).
+// The vectors and scalars, from the ones column g1 [ps] (row or column `last` of G: symmetric), G11 and c [ps + 1]:
+//     c' = c - g1 c1 / G11,  yy' = yy - c1^2 / G11,  xmean = g1 / G11,  ymean = c1 / G11.     false: G11 is not positive.
+inline bool l0_eliminate_vectors(const double* g1, double g11, const double* c, int ps, double yy, double* cs, double* yys, double* xmean,
+                                 double* ymean) {
+  const double c1 = c[ps];
+  if (!(g11 > 0.0) || !std::isfinite(g11)) return false;
+  for (int i = 0; i < ps; ++i) {
+    xmean[i] = g1[i] / g11;
+    cs[i] = c[i] - g1[i] * c1 / g11;
+  }
+  *ymean = c1 / g11;
+  *yys = yy - c1 * c1 / g11;
+  return true;
+}
+// In: G [p][ld] with the ones column LAST, c [p].  Out: Gs [(p - 1)][lds] (the padding of a row is left alone), cs, xmean
+// [p - 1].  The device's l0_eliminate_kernel writes the same Gs.
+inline bool l0_eliminate_last_ld(const double* G, size_t ld, const double* c, int p, double yy, double* Gs, size_t lds, double* cs,
+                                 double* yys, double* xmean, double* ymean) {
+  const int q = p - 1;
+  std::vector<double> g1((size_t)q);
+  for (int i = 0; i < q; ++i) g1[(size_t)i] = G[(size_t)i * ld + q];
+  const double g11 = G[(size_t)q * ld + q];
+  if (!l0_eliminate_vectors(g1.data(), g11, c, q, yy, cs, yys, xmean, ymean)) return false;
+  for (int i = 0; i < q; ++i)
+    for (int j = 0; j < q; ++j) Gs[(size_t)i * lds + j] = G[(size_t)i * ld + j] - g1[(size_t)i] * g1[(size_t)j] / g11;
+  return true;
 }
 
 }  // namespace slm

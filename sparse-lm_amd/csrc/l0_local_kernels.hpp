@@ -21,6 +21,21 @@
 // problem owns row q of every output, so nothing is shared and there is no atomic.  Every applied change is one dependent read
 // of 8 p bytes (from L2 / Infinity Cache: the Gram is at most 8 MB), so a problem is latency-bound and the chip fills only
 // through the number of problems.
+//
+// ROW SETS (slm_solve_l0_local_folds: the training rows of a cross-validation's folds, then all rows).  Problem
+// q = (r * n_cells + e) * n_starts + s is row set r, cell e, start s: it reads G_r, c_r and yy_r (which feeds tol); alphas and
+// etas stay per cell and are shared by the row sets.  Up to L0_LS_ROW_SETS = 16 pointers and scalars ride in the kernel
+// argument; r is made a scalar (readfirstlane: a wave is one problem), so the choice is three scalar loads per problem and
+// nothing per lane.  With one row set r = 0 and e = q / n_starts: the parent's problem, change by change.
+//
+// l0_eliminate_kernel is the intercept of those row sets: the dataset is [X | 1] with the ones column last, and for each row
+// set the Schur complement of that column,  G' = G - g1 g1^T / G11  (g1 = G[:, last], G11 = G[last][last]), is written into a
+// workspace of the call with the dataset's leading dimension -- exactly weighted centring of X by the row set's own means --
+// and the search reads G' as it reads a filed Gram.  The filed Grams are not modified.  (The vectors c', xmean and the
+// scalars yy', ymean are the host's: l0_eliminate_vectors, l0_host.hpp.)  Cancellation, as for l0_eliminate_last: G_ij holds
+// mean_i mean_j + cov_ij and the subtraction removes the first term, so the centred entry keeps a relative error of about
+// 2^-53 (1 + mean_i mean_j / cov_ij): a column whose |mean| is 1e4 times its spread loses eight to nine of sixteen digits.
+// Data far from the origin should be shifted by the caller.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,8 +46,9 @@
 namespace slm {
 
 struct L0LsArgs {
-  const double* G;       // [p][ld] the dataset's Gram, in place
-  const double* c;       // [p]
+  const double* G[L0_LS_ROW_SETS];  // [p][ld] per row set: a filed Gram in place, or the call's eliminated copy
+  const double* c[L0_LS_ROW_SETS];  // [p] per row set
+  double yy[L0_LS_ROW_SETS];        // per row set
   const double* alphas;  // [n_cells]
   const double* etas;    // [n_cells]
   const double* starts;  // [n_problems][p] inside the box, or NULL: zero
@@ -40,9 +56,33 @@ struct L0LsArgs {
   double* F_out;         // [n_problems]
   int* stat_out;         // [n_problems][4]: sweeps, swaps, status word (L0_LS_SWEEPS_OUT | L0_LS_SWAPS_OUT), non-zeros
   long long ld;
-  int p, n_problems, n_starts, swaps;  // problem q is cell q / n_starts; swaps == 0: the descent alone
-  double big_M, yy;
+  int p, n_problems, n_starts, swaps;  // swaps == 0: the descent alone
+  int n_cells;                         // problem q = (r * n_cells + e) * n_starts + s: row set r, cell e, start s
+  double big_M;
 };
+
+struct L0ElimArgs {
+  const double* G[L0_LS_ROW_SETS];  // [ps + 1][ld] per row set: the filed Gram of [X | 1]
+  double* out;                      // row set r: [ps][ld] at out + r * stride
+  long long ld, stride;
+  int ps;
+};
+
+// G'[i][j] = G[i][j] - g1[i] g1[j] / G11 for i, j < ps (the padding j >= ps of a row: 0).  Grid (column blocks, ps rows, row
+// sets); g1 is read from the LAST ROW (the store holds both triangles, mirrored from one value), so every read is coalesced.
+// (a - (b c) / d: the division stands between the product and the difference, so nothing contracts and the host twin
+// l0_eliminate_last_ld gives the same bits.)
+static __global__ __launch_bounds__(256) void l0_eliminate_kernel(L0ElimArgs a) {
+  const int i = (int)blockIdx.y, ps = a.ps;
+  const long long ld = a.ld;
+  const double* __restrict__ G = a.G[blockIdx.z];
+  const double* __restrict__ last = G + (long long)ps * ld;
+  const double g11 = last[ps], gi = last[i];
+  const double* __restrict__ row = G + (long long)i * ld;
+  double* __restrict__ out = a.out + (long long)blockIdx.z * a.stride + (long long)i * ld;
+  for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < ld; j += (long long)gridDim.x * 256)
+    out[j] = j < ps ? row[j] - gi * last[j] / g11 : 0.0;
+}
 
 static __device__ __forceinline__ int l0_ls_wave_min(int v) {
 #pragma unroll
@@ -70,11 +110,15 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
   const int lane = threadIdx.x & 63;
   const int p = a.p, ns = (p + 63) >> 6;
   const long long ld = a.ld;
-  const double* __restrict__ G = a.G;
-  const double big_M = a.big_M, tol = L0_CD_TOL * sqrt(a.yy);
+  const double big_M = a.big_M;
   const int stride = (int)gridDim.x * L0_WAVES;
   for (int q = (int)blockIdx.x * L0_WAVES + (int)(threadIdx.x >> 6); q < a.n_problems; q += stride) {
-    const int cell = q / a.n_starts;
+    const int rc = q / a.n_starts;                                  // r * n_cells + e
+    const int rs = __builtin_amdgcn_readfirstlane(rc / a.n_cells);  // the row set: one per wave, so a scalar
+    const int cell = rc - rs * a.n_cells;
+    const double* __restrict__ G = a.G[rs];
+    const double* __restrict__ cv = a.c[rs];
+    const double tol = L0_CD_TOL * sqrt(a.yy[rs]);
     const double alpha = a.alphas[cell], eta2 = 2.0 * a.etas[cell];
     double beta[L0_LS_SLOTS], r[L0_LS_SLOTS], d[L0_LS_SLOTS];
     double dmax = 0.0;
@@ -86,7 +130,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
       d[s] = 0.0;
       if (s < ns && j < p) {
         d[s] = G[(long long)j * ld + j] + eta2;
-        r[s] = a.c[j];
+        r[s] = cv[j];
         if (a.starts) beta[s] = a.starts[(long long)q * p + j];
       }
       dmax = fmax(dmax, d[s]);
@@ -207,7 +251,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
       if (s < ns) {
         const int j = s * 64 + lane;
         if (j < p) {
-          acc += beta[s] * (a.c[j] + r[s]);
+          acc += beta[s] * (cv[j] + r[s]);
           nnz += beta[s] != 0.0;
           a.beta_out[(long long)q * p + j] = beta[s];
         }

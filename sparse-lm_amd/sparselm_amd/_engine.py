@@ -105,6 +105,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_xb_wide",
     "slm_solve_l0_local",
     "slm_solve_l0_local_descent",
+    "slm_solve_l0_local_folds",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -378,6 +379,7 @@ def load_library():
                                          vp, P(_PointInfo)],
             "slm_solve_l0_local": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_descent": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_folds": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1670,6 +1672,64 @@ class Dataset:
             "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
         } for e in range(cnt)]
         return betas, objectives, winners, out
+
+    def solve_l0_local_folds(self, row_weights, n_effs, alphas, etas=0.0, intercept=False, big_M=100.0, starts=None, swaps=True,
+                             n_cells=None, n_starts=None, binding=None):
+        """``slm_solve_l0_local_folds``: ``solve_l0_local`` on several row sets of this dataset -- the training sets of a
+        cross-validation and all rows -- from ONE launch.  ``row_weights``: up to 16 arrays of ``n`` weights, or None for the
+        dataset's own rows; ``n_effs``: the divisor of each set's Gram (<= 0: the row count).  ``intercept``: the dataset's last
+        column is a column of ones, alone in the last group; it is not searched but eliminated from every set's Gram (weighted
+        centring by the set's own means), so ``ps = p - 1`` columns are searched.  The cells ``(alphas[e], etas[e])`` are shared
+        by the row sets; ``starts``: None, or ``[count, cells, n_starts, ps]``.  Returns ``(betas [count, cells, ps], intercepts
+        [count, cells], objectives [count, cells], winning starts [count, cells], stats [count, cells, n_starts, 4], infos)``:
+        ``stats`` holds sweeps, accepted swaps, status word and non-zeros of EVERY problem; ``infos`` is one list per row set of
+        the dicts ``solve_l0_local`` gives per cell.  With one row set of None and no intercept the result equals
+        ``solve_l0_local``'s byte for byte."""
+        ps = self.p - (1 if intercept else 0)
+        rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
+        nes = [int(v) for v in n_effs]
+        if len(nes) != len(rws):
+            raise ValueError("row_weights and n_effs differ in length")
+        count = len(rws)
+        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        et = np.ascontiguousarray(np.broadcast_to(np.asarray(etas, dtype=np.float64), al.shape), dtype=np.float64).reshape(-1)
+        cells = len(al) if n_cells is None else int(n_cells)
+        if len(al) < cells or len(et) < cells:
+            raise ValueError("alphas and etas must have n_cells entries")
+        st = None
+        ns = 1 if n_starts is None else int(n_starts)
+        if starts is not None:
+            st = np.ascontiguousarray(starts, dtype=np.float64)
+            if n_starts is None:
+                if st.ndim != 4 or st.shape[:2] != (count, cells) or st.shape[3] != ps:
+                    raise ValueError(f"starts must have the shape ({count}, {cells}, n_starts, {ps})")
+                ns = st.shape[2]
+            st = st.reshape(-1)
+        # (else the engine refuses: the outputs only have to exist)
+        sized = 1 <= count <= 16 and cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS and count * cells * ns <= L0_LOCAL_MAX_PROBLEMS
+        if st is not None and sized and st.size != count * cells * ns * ps:
+            raise ValueError(f"starts has {st.size} entries, expected {count * cells * ns * ps}")
+        cnt = count * cells if sized else 1
+        problems = cnt * ns if sized else 1
+        pad = np.zeros(1)  # (an empty array has no address worth handing over)
+        ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
+        ne = np.array(nes or [0], dtype=np.int64)
+        tail = (int(bool(intercept)), cells, al if len(al) else pad, et if len(et) else pad, float(big_M), ns, st if sized else None,
+                int(bool(swaps)))
+        (betas, icpts, objectives, winners, stats), infos, rc = self._l0_call(
+            "solve_l0_local_folds", binding, (count, ptrs, ne) + tail,
+            [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros((problems, 4), dtype=np.int32)],
+            records=cnt, binding_args=(self.n, rws, nes, bool(intercept)) + tail[1:-1] + (bool(swaps),))
+        names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
+        out = [{
+            "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
+            "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
+            "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
+        } for e in range(cnt)]
+        if not sized:
+            return betas, icpts, objectives, winners, stats, [out]
+        return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
+                stats.reshape(count, cells, ns, 4), [out[r * cells:(r + 1) * cells] for r in range(count)])
 
 
 class _HostPool:

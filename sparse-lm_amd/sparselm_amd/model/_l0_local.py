@@ -19,7 +19,8 @@ One launch runs every (cell, start) problem, one wavefront each.  Round 0 starts
 rounding is no improvement); the rounds end early when no cell improved.
 
 Not built: groups and a hierarchy, a bound on the cardinality (best-subset form), an l1 term, a general Tikhonov matrix,
-constraints, cross-validation folds in the launch, handing the result to the exact search as its seed.
+constraints, handing the result to the exact search as its seed.  (Cross-validation folds in the launch: ``l0_local_cv``,
+``model/_l0_local_cv.py``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_search``, ``L0LocalPath``).
 """

@@ -1,0 +1,212 @@
+"""The l0 local search, cross-validated: every fold's (alpha, eta) grid and the grid of all rows from ONE launch per round
+(``slm_solve_l0_local_folds``, csrc/l0_local_kernels.hpp).
+
+``l0_local_search`` returns a local minimum at every cell of a grid and says nothing about which cell to use.  A
+cross-validation asks the same grid of every fold's training rows, and a refit asks it of all rows: ``l0_local_cv`` builds ONE
+dataset (of ``[X | 1]`` when an intercept is fitted -- the engine eliminates that column per row set, which is centring by the
+set's own weighted means), hands the folds' training masks and the all-rows set to one call per round, and scores every cell of
+every fold on its held-out rows with numpy.  Round 0 and each neighbour round of ``l0_local_search`` run over all row sets at
+once; each row set's cells start from THAT row set's neighbours' winners, and a result is kept under the same 1e-12 rule.  A
+whole cross-validation is therefore 1 + rounds launches, whatever the number of folds.  ``L0LocalCV.search`` then reads the
+grid off the scores: scikit-learn-shaped ``cv_results_``, the selection rules of ``model_selection.py``, and the selected model
+from the grid of all rows.
+
+Against ``l0_local_search`` on a fold's rows alone the supports and objectives agree (objectives to 1e-10 where no decision of
+the rule is closer than that to a tie); the coefficients are NOT the same bytes: a fold's Gram is built from the complement of
+its held-out rows, and centring is by elimination of the ones column instead of on the rows.  Nothing is proven optimal.
+
+Limits: the local search's 1024 columns, at most 15 splits (folds plus all rows fill the Gram store's 16 entries),
+``(splits + 1) x cells x starts <= 8192`` problems per launch; held-out scores are unweighted.  Not built: groups, a bound on
+the cardinality, an l1 term, rerouting ``GridSearchCV``.
+
+Import path: ``sparselm_amd.miqp`` (``l0_local_cv``, ``L0LocalCV``).
+"""
+
+from __future__ import annotations
+
+import warnings
+from numbers import Integral
+
+import numpy as np
+from sklearn.exceptions import ConvergenceWarning
+from sklearn.model_selection import check_cv
+
+from ._l0_cv import _SCORINGS, _SELECTIONS, MAX_SPLITS, _score
+from ._l0_local import _IMPROVE, _MAX_PROBLEMS, _OPTIONS, _PMAX, L0LocalPath, _grid, _LocalProblem
+
+__all__ = ["l0_local_cv", "L0LocalCV"]
+
+
+class L0LocalSearch:
+    """What ``L0LocalCV.search`` returns: ``cv_results_`` in scikit-learn's layout (``params``, ``split{f}_test_score``,
+    ``mean_test_score``, ``std_test_score``, ``rank_test_score``), ``best_index_``, ``best_params_``, ``best_score_``,
+    ``best_score_std_``, and the selected model from the grid of all rows: ``coef_``, ``intercept_``, ``predict``.
+    ``proven_optimal_`` is False: the model is a local minimum."""
+
+    proven_optimal_ = False
+
+    def __init__(self, cv_results, best_index, coef, intercept):
+        self.cv_results_ = cv_results
+        self.best_index_ = int(best_index)
+        self.best_params_ = cv_results["params"][self.best_index_]
+        self.best_score_ = cv_results["mean_test_score"][self.best_index_]
+        self.best_score_std_ = cv_results["std_test_score"][self.best_index_]
+        self.coef_, self.intercept_ = coef, intercept
+
+    def predict(self, X):
+        return np.asarray(X, dtype=np.float64) @ self.coef_ + self.intercept_
+
+
+class L0LocalCV:
+    """What ``l0_local_cv`` returns: ``paths_`` (one ``L0LocalPath`` per fold, on its training rows), ``full_`` (the
+    ``L0LocalPath`` of all rows), ``splits_`` (``(train, test)`` index pairs), ``cell_scores_`` (folds x A x E: the unweighted
+    held-out score of each cell's fit), ``alphas_``, ``etas_``, ``scoring_``, ``solver_info_`` (``launches``; ``rounds``;
+    ``problems``: the problems of one launch at most; ``max_sweeps`` and ``max_swaps``: the largest counts of ANY problem of the
+    call, a losing start included, beside ``winner_max_sweeps`` / ``winner_max_swaps`` of the kept results;
+    ``proven_optimal``: False) and ``proven_optimal_ = False``."""
+
+    proven_optimal_ = False
+
+    def __init__(self, paths, full, splits, cell_scores, scoring, solver_info):
+        self.paths_ = paths
+        self.full_ = full
+        self.splits_ = splits
+        self.cell_scores_ = cell_scores
+        self.alphas_, self.etas_ = full.alphas_, full.etas_
+        self.scoring_ = scoring
+        self.solver_info_ = solver_info
+
+    def search(self, opt_selection_method="max_score"):
+        """The grid ``alphas_ x etas_`` read off ``cell_scores_``: an ``L0LocalSearch`` whose ``cv_results_["params"]`` are
+        ``{"alpha", "eta"}`` dicts in the order of ``ParameterGrid({"alpha": alphas_, "eta": etas_})`` -- ``alpha`` outermost --
+        under either selection rule of ``model_selection.py``; the selected model is ``full_``'s at the chosen cell."""
+        from ..model_selection import _format_results, select_best_index_onestd
+
+        if opt_selection_method not in _SELECTIONS:
+            raise ValueError(f"opt_selection_method must be one of {list(_SELECTIONS)} (got {opt_selection_method!r})")
+        A, E = len(self.alphas_), len(self.etas_)
+        params = [{"alpha": float(a), "eta": float(e)} for a in self.alphas_ for e in self.etas_]
+        scores = np.asarray(self.cell_scores_, dtype=float).reshape(len(self.paths_), A * E).T
+        results = _format_results(params, scores, np.zeros_like(scores))
+        if opt_selection_method == "one_std_score":
+            best = select_best_index_onestd(results)
+        else:
+            best = int(results["rank_test_score"].argmin())
+        a, e = divmod(int(best), E)
+        return L0LocalSearch(results, best, self.full_.coefs_[a, e].copy(), float(self.full_.intercepts_[a, e]))
+
+
+def l0_local_cv(X, y, *, alphas, etas=(0.0,), cv=5, big_M=100, fit_intercept=False, sample_weight=None, starts=None, max_rounds=2,
+                scoring="neg_root_mean_squared_error", solver_options=None) -> L0LocalCV:
+    """``l0_local_search`` on every cross-validation fold's training rows and on all rows, one launch per round on the GPU.
+
+    The arguments of ``l0_local_search``, and ``cv`` (anything ``sklearn.model_selection.check_cv`` takes; at most 15 splits)
+    and ``scoring`` (``"neg_root_mean_squared_error"`` or ``"neg_mean_squared_error"``, unweighted on the held-out rows).
+    ``sample_weight`` weighs the training rows of every problem; ``starts`` are shared by the row sets.  One
+    ``ConvergenceWarning`` names the (row set, cell) pairs whose kept result ran into a sweep or swap cap.  The coefficients of
+    a fold are not byte for byte those of ``l0_local_search`` on its rows (see the module's text); nothing is proven optimal."""
+    options = {} if solver_options is None else solver_options
+    if not isinstance(options, dict):
+        raise ValueError("solver_options must be a dict or None")
+    unknown = set(options) - _OPTIONS
+    if unknown:
+        raise ValueError(f"unknown solver_options {sorted(unknown)}: the l0 local search takes {sorted(_OPTIONS)}")
+    swaps = options.get("swaps", True)
+    if not isinstance(swaps, (bool, np.bool_)):
+        raise ValueError("solver_options['swaps'] must be a bool")
+    if not isinstance(max_rounds, Integral) or isinstance(max_rounds, bool) or max_rounds < 0:
+        raise ValueError("max_rounds must be an integer >= 0")
+    if scoring not in _SCORINGS:
+        raise ValueError(f"scoring must be one of {list(_SCORINGS)} (got {scoring!r})")
+    spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options={k: v for k, v in options.items() if k == "device"} or None)
+    # everything is validated before a device is touched
+    X, y, dev_options, _, _, _, _, w = spec._l0_setup(X, y, sample_weight)
+    al, et = _grid(alphas, "alphas"), _grid(etas, "etas")
+    A, E = len(al), len(et)
+    n, p = X.shape
+    if p > _PMAX:
+        raise NotImplementedError(f"the l0 local search takes up to {_PMAX} columns (got {p})")
+    big_M = float(big_M)
+    first = np.zeros((A, E, 1, p))
+    if starts is not None:
+        st = np.asarray(starts, dtype=float)
+        if st.ndim == 2 and st.shape[1] == p:
+            st = np.broadcast_to(st, (A, E) + st.shape)
+        if st.ndim != 4 or st.shape[:2] != (A, E) or st.shape[3] != p:
+            raise ValueError(f"starts must have the shape (S, {p}) or ({A}, {E}, S, {p})")
+        if not np.all(np.abs(st) <= big_M):  # (a NaN fails too)
+            raise ValueError(f"starts must lie inside the box |beta_j| <= big_M = {big_M:g}")
+        first = np.concatenate([first, st], axis=2)
+    splitter = check_cv(cv, y, classifier=False)
+    n_splits = int(splitter.get_n_splits(X, y))
+    if not 1 <= n_splits <= MAX_SPLITS:
+        raise ValueError(f"l0_local_cv takes 1 .. {MAX_SPLITS} splits (got {n_splits}): the folds and all rows share one launch of "
+                         f"at most {MAX_SPLITS + 1} row sets")
+    splits = [(np.asarray(tr), np.asarray(te)) for tr, te in splitter.split(X, y)]
+    R = len(splits) + 1
+    most = max(first.shape[2], (2 * (A > 1) + 2 * (E > 1)) if max_rounds else 0)  # (a round starts a cell from its neighbours in the grid)
+    if R * A * E * most > _MAX_PROBLEMS:
+        raise ValueError(f"{R} row sets x {A * E} cells x up to {most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
+    base = np.ones(n) if w is None else np.asarray(w, dtype=np.float64)
+    row_weights, n_effs = [], []
+    for rows in [tr for tr, _ in splits] + [np.arange(n)]:  # the folds' training rows, then all rows
+        m = np.zeros(n)
+        m[rows] = base[rows]
+        total = float(m.sum())
+        if not total > 0.0:
+            raise ValueError("a training set has no weight")
+        row_weights.append(m * (len(rows) / total))
+        n_effs.append(len(rows))
+    cell_alpha, cell_eta = np.repeat(al, E), np.tile(et, A)
+
+    from .. import _engine
+
+    eng = _engine.get_engine(dev_options.get("device"))
+    Xd = np.hstack([X, np.ones((n, 1))]) if fit_intercept else X
+    launches, max_sweeps, max_swaps, problems = 0, 0, 0, 0
+    with eng.dataset(Xd, y) as ds:
+
+        def launch(points):  # points: R x A x E x S x p
+            nonlocal launches, max_sweeps, max_swaps, problems
+            b, i, o, _, stats, info = ds.solve_l0_local_folds(row_weights, n_effs, cell_alpha, cell_eta, intercept=fit_intercept, big_M=big_M,
+                                                              starts=points.reshape(R, A * E, -1, p), swaps=bool(swaps))
+            launches += 1
+            problems = max(problems, stats.shape[0] * stats.shape[1] * stats.shape[2])
+            max_sweeps, max_swaps = max(max_sweeps, int(stats[..., 0].max())), max(max_swaps, int(stats[..., 1].max()))
+            return (np.array(b).reshape(R, A, E, p), np.array(i).reshape(R, A, E), np.array(o).reshape(R, A, E),
+                    np.array(info, dtype=object).reshape(R, A, E))
+
+        coefs, icpts, objectives, infos = launch(np.broadcast_to(first, (R,) + first.shape))
+        history = [objectives.copy()]
+        moves = [(da, de) for da, de in ((-1, 0), (1, 0), (0, -1), (0, 1)) if (A > 1 and da) or (E > 1 and de)]
+        for _ in range(int(max_rounds) if moves else 0):
+            # every cell from its neighbours' winners IN ITS OWN ROW SET; beyond the grid's edge the cell's own winner stands in
+            points = np.stack([coefs[:, np.clip(np.arange(A) + da, 0, A - 1)][:, :, np.clip(np.arange(E) + de, 0, E - 1)] for da, de in moves],
+                              axis=3)
+            c2, i2, o2, f2 = launch(points)
+            better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[None, :, None])
+            coefs[better], icpts[better], objectives[better], infos[better] = c2[better], i2[better], o2[better], f2[better]
+            history.append(objectives.copy())
+            if not better.any():
+                break
+    history = np.array(history)  # rounds x R x A x E
+    names = [f"fold {f}" for f in range(len(splits))] + ["all rows"]
+    capped = [(names[r], a, e) for r in range(R) for a in range(A) for e in range(E) if not infos[r, a, e]["converged"]]
+    if capped:
+        shown = ", ".join(f"{nm}: alpha index {a}, eta index {e}" for nm, a, e in capped[:8]) + (", ..." if len(capped) > 8 else "")
+        warnings.warn(f"the local search ran into a cap in {len(capped)} of {R * A * E} (row set, cell) pairs ({shown}): their last points "
+                      "are returned", ConvergenceWarning)
+    take = np.vectorize(lambda d, k: d[k])
+    tables = [L0LocalPath(al, et, coefs[r], icpts[r], objectives[r], take(infos[r], "loss").astype(float), len(history), history[:, r],
+                          take(infos[r], "swaps").astype(int), take(infos[r], "sweeps").astype(int), take(infos[r], "converged").astype(bool))
+              for r in range(R)]
+    paths, full = tables[:-1], tables[-1]
+    cell_scores = np.empty((len(splits), A, E))
+    for f, (_, te) in enumerate(splits):
+        for a in range(A):
+            for e in range(E):
+                cell_scores[f, a, e] = _score(scoring, y[te] - (X[te] @ paths[f].coefs_[a, e] + paths[f].intercepts_[a, e]))
+    solver_info = {"launches": launches, "rounds": len(history), "problems": problems, "max_sweeps": max_sweeps, "max_swaps": max_swaps,
+                   "winner_max_sweeps": int(max(t.sweeps_.max() for t in tables)), "winner_max_swaps": int(max(t.swaps_.max() for t in tables)),
+                   "proven_optimal": False}
+    return L0LocalCV(paths, full, splits, cell_scores, scoring, solver_info)

@@ -827,6 +827,139 @@ def local_section(out_path, repeats, max_nodes):
     say("fewer compute units; the host twin on several cores (the cells are independent: a 16-core host divides its column by up to 16).")
 
 
+# the resource lines of the two kernels of csrc/l0_local_kernels.hpp after row sets went in (same command as above), beside the parent's
+LOCAL_CV_RESOURCES = (
+    "l0_local_kernel on gfx950: 256 VGPRs, 74 AGPRs, scratch 0 bytes/lane, LDS 0 bytes, 104 SGPRs (163 SGPR spills to VGPR lanes), 1 wave/SIMD",
+    "    (the parent, one Gram for all problems: 255 VGPRs, 78 AGPRs, scratch 0, 104 SGPRs, 156 SGPR spills, 1 wave/SIMD)",
+    "l0_eliminate_kernel on gfx950: 16 VGPRs, 0 AGPRs, scratch 0 bytes/lane, LDS 0 bytes, 34 SGPRs, no spills, 8 waves/SIMD",
+    "the other 101 kernels of engine_l0.hip, the twelve instantiations of the exact search among them: resource lines unchanged, compared line by line",
+)
+
+
+def _single_table(repeats):
+    """The 200 x 512 and 400 x 1024 table of local_section, the GPU column alone: {"n x p cells": [ms, ...]}."""
+    from sparselm_amd import _engine
+
+    out = {}
+    for n, p in ((200, 512), (400, 1024)):
+        rng = np.random.default_rng(p)
+        X = rng.standard_normal((n, p))
+        beta = np.zeros(p)
+        beta[rng.choice(p, 20, replace=False)] = (-1.0) ** np.arange(20)
+        y = X @ beta + 0.5 * rng.standard_normal(n)
+        with _engine.get_engine().dataset(X, y) as ds:
+            for cells in (1, 16, 64, 256):
+                alphas = (np.geomspace(0.003, 0.3, cells) if cells > 1 else np.array([0.03])) * float(np.var(y))
+                ds.solve_l0_local(alphas, np.zeros(cells), big_M=100.0)
+                ts = []
+                for _ in range(repeats):
+                    t0 = time.perf_counter()
+                    ds.solve_l0_local(alphas, np.zeros(cells), big_M=100.0)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                out[f"{n} x {p} {cells}"] = ts
+    return out
+
+
+def local_cv_section(out_path, repeats, parent_tree):
+    """profiles/l0_local_cv.txt: l0_local_cv against the loop it replaces, and the single-row-set path against the parent's."""
+    import json
+    import subprocess
+
+    from sklearn.model_selection import KFold
+
+    from sparselm_amd import _engine
+    from sparselm_amd.miqp import l0_local_cv, l0_local_search
+
+    dev = _engine.get_engine().device_info()
+    name = dev["name"].strip() or "device"
+    lines = [f"l0 local search over folds (l0_local_cv, slm_solve_l0_local_folds) on {name}, {dev['compute_units']} compute units",
+             f"(wall time of whole calls, each ending in a synchronise; every shape warmed first; {repeats} repeats with the variants alternating, "
+             "medians with the spread min .. max)", *LOCAL_CV_RESOURCES, ""]
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+
+    def say(line):  # (the file grows line by line: a run that is cut short leaves what it measured)
+        lines.append(line)
+        print(line, flush=True)
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    def clock(fn):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            t0 = time.perf_counter()
+            out = fn()
+            return out, (time.perf_counter() - t0) * 1e3
+
+    def fmt(ms):
+        return f"{np.median(ms):9.3f} ({min(ms):.3f} .. {max(ms):.3f})"
+
+    # ---- 1. what l0_local_cv replaces: cv + 1 calls of l0_local_search on the row subsets, each with its own upload and Gram ---------------
+    d = os.path.join(ROOT, "tests", "golden", "reference_examples")
+    Xr, yr = np.load(os.path.join(d, "corr.npy")), np.load(os.path.join(d, "energy.npy"))
+    rng = np.random.default_rng(1024)
+    Xw = rng.standard_normal((400, 1024))
+    bw = np.zeros(1024)
+    bw[rng.choice(1024, 20, replace=False)] = (-1.0) ** np.arange(20)
+    yw = Xw @ bw + 0.5 * rng.standard_normal(400)
+    say("five folds (KFold without shuffle) and all rows; max_rounds = 2; big_M = 100.  one launch per round: l0_local_cv.  the loop: 6 calls of")
+    say("l0_local_search on X[rows], y[rows], each with its own dataset, upload and Gram -- what a user had to write before.")
+    for X, y, icpt, rels, what in ((Xr, yr, True, np.logspace(-4, -1, 4), "the reference's 290 x 66 data, fit_intercept, alphas / var y = 1e-4 .. 1e-1 (4)"),
+                                   (Xw, yw, False, np.geomspace(0.003, 0.3, 16), "synthetic 400 x 1024 (the law of profiles/l0_local.txt), 16 alphas")):
+        alphas = rels * float(np.var(y))
+        rows = [tr for tr, _ in KFold(5).split(X)] + [np.arange(X.shape[0])]
+        one = lambda: l0_local_cv(X, y, alphas=alphas, cv=KFold(5), fit_intercept=icpt)  # noqa: E731
+        loop = lambda: [l0_local_search(X[r], y[r], alphas=alphas, fit_intercept=icpt) for r in rows]  # noqa: E731
+        clock(one), clock(loop)
+        t_one, t_loop, cv, paths = [], [], None, None
+        for _ in range(repeats):
+            (cv, ms) = clock(one)
+            t_one.append(ms)
+            (paths, ms) = clock(loop)
+            t_loop.append(ms)
+        info = cv.solver_info_
+        same = sum(int(np.array_equal(a.supports_, b.supports_)) for a, b in zip(cv.paths_ + [cv.full_], paths))
+        say(what)
+        say(f"{'what':46s} {'ms per call: median (min .. max)':>36s}")
+        say(f"{'l0_local_cv, 6 row sets in each launch':46s} {fmt(t_one):>36s}   launches {info['launches']}, at most {info['problems']} problems each")
+        say(f"{'6 calls of l0_local_search':46s} {fmt(t_loop):>36s}   launches {sum(p_.rounds_ for p_ in paths)}")
+        ratio = np.median(t_one) / np.median(t_loop)
+        say(f"    one-launch / loop = {ratio:.3f}" + ("  -- the one-launch call LOSES here" if ratio >= 1.0 else ""))
+        say(f"    sweeps: the largest of ANY problem {info['max_sweeps']}, of the kept winners {info['winner_max_sweeps']}; accepted swaps: any problem "
+            f"{info['max_swaps']}, winners {info['winner_max_swaps']}; row sets with the loop's supports: {same} of 6")
+        say("")
+
+    # ---- 2. the single-row-set path against the parent commit's, alternating processes on this box ----------------------------------------------
+    if parent_tree:
+        say("slm_solve_l0_local (one row set) on the parent commit and on this one: the GPU column of profiles/l0_local.txt's table, whole calls.")
+        say(f"Fresh processes alternate parent, change, {repeats} times; each warms a shape and times it 3 times; below the median of all its times")
+        say("and their min .. max.  Expected: every median of the change inside the parent's own min .. max.")
+        runs = {"parent": {}, "change": {}}
+        for _ in range(repeats):
+            for which, tree in (("parent", parent_tree), ("change", ROOT)):
+                env = dict(os.environ, PYTHONPATH=os.path.join(tree, "sparse-lm_amd"))
+                got = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", "local-single", "--tree", tree], env=env, check=True,
+                                     capture_output=True, text=True, timeout=600).stdout
+                for key, ts in json.loads(got.strip().splitlines()[-1]).items():
+                    runs[which].setdefault(key, []).extend(ts)
+        say(f"{'n x p':>10s} {'cells':>6s} {'parent ms: median (min .. max)':>36s} {'change ms: median (min .. max)':>36s} {'inside':>7s}")
+        outside = []
+        for key in runs["parent"]:
+            n_, _, p_, cells = key.split()
+            a, b = runs["parent"][key], runs["change"][key]
+            inside = min(a) <= np.median(b) <= max(a)
+            if not inside:
+                outside.append((key, float(np.median(b)), min(a), max(a)))
+            say(f"{f'{n_} x {p_}':>10s} {cells:>6s} {fmt(a):>36s} {fmt(b):>36s} {'yes' if inside else 'NO':>7s}")
+        for key, med, lo, hi in outside:
+            say(f"    OUTSIDE the parent's range ({'below' if med < lo else 'above'} it): {key} cells, change median {med:.3f} ms against {lo:.3f} .. {hi:.3f}")
+        say("")
+    say("Host copies for the polish: per row set only the rows of its Gram that its winners hold are fetched (8 ps bytes each; beyond 64 rows one")
+    say("strided copy of the stretch that holds them), not the 8 ld^2 bytes of every Gram; what a full fetch would cost was not measured.")
+    say("NOT measured: the kernels alone (no event bracket: the whole call is what a caller pays); the cost of the elimination launch by itself;")
+    say("more than five folds; starts beside zero in round 0; eta > 0; sample weights (their Grams are built row set by row set, not from the")
+    say("folds' complements); correlated designs, where sweeps and swaps multiply; devices with fewer compute units.")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-nodes", type=int, default=1 << 24)
@@ -840,8 +973,22 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--grid-cv-out", default=os.path.join(ROOT, "profiles", "l0_grid_cv.txt"))
     ap.add_argument("--local-out", default=os.path.join(ROOT, "profiles", "l0_local.txt"))
-    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile", "gridcv", "local"], default=None)
+    ap.add_argument("--local-cv-out", default=os.path.join(ROOT, "profiles", "l0_local_cv.txt"))
+    ap.add_argument("--parent-tree", default=None, help="localcv: a built checkout of the parent commit, for the single-row-set comparison")
+    ap.add_argument("--tree", default=None, help="local-single: the checkout whose package this process imports")
+    ap.add_argument("--only", choices=["search", "profile", "wide", "constrained", "bound", "cv", "l1profile", "gridcv", "local", "localcv",
+                                       "local-single"], default=None)
     args = ap.parse_args()
+    if args.only == "local-single":  # (a child of localcv: the table as one JSON line)
+        import json
+
+        if args.tree:
+            sys.path.insert(0, os.path.join(args.tree, "sparse-lm_amd"))
+        print(json.dumps(_single_table(3)))
+        return
+    if args.only == "localcv":
+        local_cv_section(args.local_cv_out, max(1, args.repeats), args.parent_tree)
+        return
     if args.only == "local":
         local_section(args.local_out, max(1, args.repeats), args.max_nodes)
         return
