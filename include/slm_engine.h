@@ -832,8 +832,8 @@ int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* cons
  * Refusals, all before a device is touched, each with its own message: p > 1024, groups that are not singletons, a
  * row-sharded dataset (SLM_ERR_UNSUPPORTED); a negative or non-finite alphas[e] or etas[e], big_M < 0, n_cells < 1,
  * n_starts < 1, n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS = 8192, a start outside the box (SLM_ERR_BAD_ARG).
- * Not here: groups and a hierarchy, a bound on the cardinality, an l1 term, a Tikhonov matrix, constraints.  Row sets (CV
- * folds) in the launch: slm_solve_l0_local_folds, below.
+ * Not here: groups and a hierarchy, an l1 term, a Tikhonov matrix, constraints.  Row sets (CV folds) in the launch:
+ * slm_solve_l0_local_folds, below; a bound on the cardinality: slm_solve_l0_local_subsets, below.
  */
 #define SLM_L0_LOCAL_PMAX 1024
 #define SLM_L0_LOCAL_MAX_PROBLEMS 8192
@@ -867,7 +867,7 @@ int slm_solve_l0_local_descent(slm_dataset* ds, int32_t n_cells, const double* a
  * count outside 1 .. 16, a negative or non-finite weight, an intercept column that is not last and alone (SLM_ERR_BAD_ARG);
  * count * n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS (the message names the three factors).  A row set that gives the
  * ones column no weight is refused once its Gram is there.
- * Not here: groups, a bound on the cardinality, an l1 term, more than 16 row sets.
+ * Not here: groups, an l1 term, more than 16 row sets.  (A bound on the cardinality: slm_solve_l0_local_subsets.)
  */
 int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                              const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
@@ -877,6 +877,42 @@ int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const
                              double* objective_out /* count * n_cells */, int32_t* start_out /* or NULL */,
                              int32_t* stat_out /* count * n_cells * n_starts * 4: sweeps, swaps, status word, non-zeros of EVERY problem; or NULL */,
                              slm_point_info* info /* count * n_cells, or NULL */);
+
+/*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_local_folds, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs it looks the symbol up.)  LOCAL SUBSETS: the l0 local search in its CARDINALITY form,
+ * the approximate twin of slm_solve_l0_profile beyond 128 columns (up to SLM_L0_LOCAL_PMAX = 1024).  Cell e is
+ * (sizes[e], etas[e]); with G, c as above and H = G + 2 etas[e] I,
+ *       minimise over beta, |beta_j| <= big_M, ||beta||_0 <= sizes[e]:   Q(beta) = 1/2 beta^T H beta - c^T beta
+ * -- the units of slm_solve_l0's objective with alpha = 0, singleton groups and T = I.  Nothing is proven.  The rule, with
+ * r, d, u, b and gain as for slm_solve_l0_local and tol = 1e-12 sqrt(yy), from a start of ANY support size inside the box:
+ *   1. Shrink: while nnz > k, the support column with the smallest g_i = gain(r_i + d_i beta_i, d_i) leaves (ties: the lowest
+ *      index).
+ *   2. Descent on the support: j over the support cyclically, beta_j <- b; no threshold, no column enters, a coordinate whose
+ *      b is exactly 0 leaves.  A sweep ends it when the support stood still and max |delta_j| sqrt(d_j) <= tol; 10000 sweeps
+ *      end it unconverged.  A column with d_j <= 1e-12 max d stays out throughout.
+ *   3. Grow: if nnz < k, the outside column with the largest gain(r_j, d_j) (ties: the lowest j) enters at its b when
+ *      |b| sqrt(d_j) > tol; back to 2.
+ *   4. Swap scan, once 3 adds nothing: step 2 of slm_solve_l0_local with alpha = 0; a swap goes back to 2, no swap ends the
+ *      problem, 10000 accepted swaps end it unconverged.  swaps == 0 stops after 3: greedy forward selection with re-fitting.
+ * Every accepted move lowers Q, apart from 1, which is forced.  A size above ps is legal: the problem ends when nothing more
+ * enters.  Row sets, intercept, starts, problem order, the winner per (row set, cell) by (Q, then the lowest start), its polish
+ * and info exactly as for slm_solve_l0_local_folds (info: mu = Q before the polish, kkt = objective_out = Q after it);
+ * count = 1 with row_weights[0] = NULL and no intercept is the plain single-dataset call.  stat_out (may be NULL): SIX ints per
+ * problem -- sweeps, accepted swaps, status word, non-zeros, grows (entries in 3), drops (exits in 1 and 2).
+ * Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when some winner reached a cap.
+ * Refusals, all before a device is touched, in this order: NULL sizes or etas; a size < 1; a negative or non-finite eta; then
+ * those of slm_solve_l0_local_folds for the row sets, the problem counts, big_M, the width, the intercept column, the weights
+ * and the box of the starts.
+ * Not here: groups, hierarchy, Tikhonov matrix, l1 term, constraints.
+ */
+int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
+                               const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const int32_t* sizes,
+                               const double* etas /* [n_cells] each */, double big_M, int32_t n_starts,
+                               const double* starts /* count * n_cells * n_starts * ps, or NULL: one zero start */, int32_t swaps,
+                               double* beta_out /* count * n_cells * ps */, double* intercept_out /* count * n_cells, or NULL */,
+                               double* objective_out /* count * n_cells */, int32_t* start_out /* or NULL */,
+                               int32_t* stat_out /* count * n_cells * n_starts * 6, or NULL */, slm_point_info* info /* count * n_cells, or NULL */);
 
 /*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant

@@ -546,13 +546,17 @@ py::tuple solve_l0_local(uintptr_t ds, int64_t p, int32_t n_cells, const arr_d& 
 // arrays of n weights or None; n_effs: as many integers.  starts: None or count * n_cells * n_starts * ps doubles.  Returns
 // (coefficients [count * n_cells][ps], intercepts, objectives, winning starts [count * n_cells], the four status words of every
 // problem [count * n_cells * n_starts][4], records as bytes, status); ps = p - 1 with an intercept.
-py::tuple solve_l0_local_folds(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
-                               int32_t n_cells, const arr_d& alphas, const arr_d& etas, double big_M, int32_t n_starts,
-                               const py::object& starts, bool swaps) {
+//
+// slm_solve_l0_local_subsets: the same tuple from the cardinality rule -- `sizes` (int32) where the alphas are, six status
+// words per problem.  One body serves both: `sizes` NULL is the penalised entry.
+py::tuple l0_local_rows(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
+                        int32_t n_cells, const double* alphas, const int32_t* sizes, const arr_d& etas, double big_M, int32_t n_starts,
+                        const py::object& starts, bool swaps) {
   const py::ssize_t count = (py::ssize_t)py::len(row_weights);
   if ((py::ssize_t)py::len(n_effs) != count) throw py::value_error("row_weights and n_effs differ in length");
   const int64_t cells = n_cells > 0 ? n_cells : 0;
-  if ((int64_t)alphas.size() < cells || (int64_t)etas.size() < cells) throw py::value_error("alphas and etas must have n_cells entries");
+  if ((int64_t)etas.size() < cells) throw py::value_error("etas must have n_cells entries");
+  const py::ssize_t nstat = sizes ? 6 : 4;
   const int64_t ps = intercept && p > 0 ? p - 1 : p;
   // (no row set, no cell, more problems than any call takes: the engine refuses them, the outputs only have to exist)
   const bool sized = count >= 1 && count <= 16 && n_cells >= 1 && n_starts >= 1 && (int64_t)n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS &&
@@ -567,22 +571,37 @@ py::tuple solve_l0_local_folds(uintptr_t ds, int64_t p, int64_t n, const py::seq
   }
   const py::ssize_t cnt = sized ? count * n_cells : 1, problems = sized ? cnt * n_starts : 1;
   py::array_t<double> beta({cnt, (py::ssize_t)ps}), icpt(cnt), objective(cnt);
-  py::array_t<int32_t> winner(cnt), stats({problems, (py::ssize_t)4});
+  py::array_t<int32_t> winner(cnt), stats({problems, nstat});
   py::array info = info_bytes(cnt);
   auto* rec = static_cast<slm_point_info*>(info.mutable_data());
   std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
   double *bp = beta.mutable_data(), *ip = icpt.mutable_data(), *op = objective.mutable_data();
   int32_t *wn = winner.mutable_data(), *tp = stats.mutable_data();
   std::memset(wn, 0, sizeof(int32_t) * (size_t)cnt);
-  std::memset(tp, 0, sizeof(int32_t) * 4 * (size_t)problems);
+  std::memset(tp, 0, sizeof(int32_t) * (size_t)nstat * (size_t)problems);
   int rc;
   {
     py::gil_scoped_release nogil;
-    rc = slm_solve_l0_local_folds(reinterpret_cast<slm_dataset*>(ds), (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, n_cells,
-                                  alphas.data(), etas.data(), big_M, n_starts, sp, swaps ? 1 : 0, bp, ip, op, wn, tp, rec);
+    auto* d = reinterpret_cast<slm_dataset*>(ds);
+    rc = sizes ? slm_solve_l0_local_subsets(d, (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, n_cells, sizes, etas.data(), big_M,
+                                            n_starts, sp, swaps ? 1 : 0, bp, ip, op, wn, tp, rec)
+               : slm_solve_l0_local_folds(d, (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, n_cells, alphas, etas.data(), big_M,
+                                          n_starts, sp, swaps ? 1 : 0, bp, ip, op, wn, tp, rec);
   }
   if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
   return py::make_tuple(beta, icpt, objective, winner, stats, info, rc);
+}
+py::tuple solve_l0_local_folds(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
+                               int32_t n_cells, const arr_d& alphas, const arr_d& etas, double big_M, int32_t n_starts,
+                               const py::object& starts, bool swaps) {
+  if ((int64_t)alphas.size() < (n_cells > 0 ? n_cells : 0)) throw py::value_error("alphas and etas must have n_cells entries");
+  return l0_local_rows(ds, p, n, row_weights, n_effs, intercept, n_cells, alphas.data(), nullptr, etas, big_M, n_starts, starts, swaps);
+}
+py::tuple solve_l0_local_subsets(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
+                                 int32_t n_cells, const py::array_t<int32_t, py::array::c_style | py::array::forcecast>& sizes,
+                                 const arr_d& etas, double big_M, int32_t n_starts, const py::object& starts, bool swaps) {
+  if ((int64_t)sizes.size() < (n_cells > 0 ? n_cells : 0)) throw py::value_error("sizes and etas must have n_cells entries");
+  return l0_local_rows(ds, p, n, row_weights, n_effs, intercept, n_cells, nullptr, sizes.data(), etas, big_M, n_starts, starts, swaps);
 }
 
 }  // namespace
@@ -614,6 +633,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_local", &solve_l0_local<true>);
   m.def("solve_l0_local_descent", &solve_l0_local<false>);
   m.def("solve_l0_local_folds", &solve_l0_local_folds);
+  m.def("solve_l0_local_subsets", &solve_l0_local_subsets);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

@@ -35,7 +35,8 @@
 //       slm_solve_l0_profile_batch is its call with one ridge eta.
 // Beside them, and none of the above: slm_solve_l0_local, slm_solve_l0_local_descent (solve_l0_local_impl, at the end of the
 // unit; csrc/l0_local_kernels.hpp) -- the local search beyond 128 columns, which proves nothing -- and
-// slm_solve_l0_local_folds (solve_l0_local_folds_impl), the same search on up to 16 row sets of the dataset in one launch.
+// slm_solve_l0_local_folds (solve_l0_local_folds_impl), the same search on up to 16 row sets of the dataset in one launch;
+// slm_solve_l0_local_subsets is that body with the kernel's cardinality rule: sizes where the alphas are.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -918,13 +919,13 @@ int solve_l0_local_impl(bool swaps, slm_dataset* ds, int32_t n_cells, const doub
     k.F_out = dd + off_F;
     k.stat_out = reinterpret_cast<int*>(dd + off_stat);
     k.beta_out = dd + off_beta;
-    k.p = p; k.n_problems = problems; k.n_starts = n_starts; k.swaps = swaps ? 1 : 0;
+    k.p = p; k.n_problems = problems; k.n_starts = n_starts; k.swaps = swaps ? 1 : 0; k.stat_stride = 4;
     k.big_M = big_M;
     // (a problem is one wave.  The kernel's registers leave one workgroup of L0_WAVES waves resident per CU; twice that many are
     // launched so that a CU whose problems end early takes up another workgroup, and the problems beyond 2 cus workgroups are reached
     // by the kernel's grid-stride loop)
     const int blocks = std::min((problems + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
-    hipLaunchKernelGGL(l0_local_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    hipLaunchKernelGGL(l0_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
     SLM_TRY(check_launch());
     HIP_TRY(hipMemcpyAsync(h.data() + off_F, dd + off_F, sizeof(double) * (words - off_F), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1001,10 +1002,14 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
 // start by (F, then the lowest index), polished on host copies of ONLY the rows of its Gram that the winners of that row set
 // hold (l0_fetch_rows: the polish and the loss read nothing else); the record of solve_l0_local_impl's table per (row set,
 // cell); stat_out: the four status words of EVERY problem.
+//
+// slm_solve_l0_local_subsets (DESIGN 4d "Local subsets") is the same call with `sizes` in the place of `alphas`: the check is
+// l0_lc_check, the launch l0_local_kernel<true> (the cardinality rule), the sizes travel as ints where the alphas did, the
+// objective has no alpha term (Q after the polish), and stat_out holds six words per problem: grows and drops behind the four.
 int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs, int32_t intercept,
-                              int32_t n_cells, const double* alphas, const double* etas, double big_M, int32_t n_starts,
-                              const double* starts, int32_t swaps, double* beta_out, double* intercept_out, double* objective_out,
-                              int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
+                              int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
+                              int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
+                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info, bool card) {
   if (!ds || !beta_out || !objective_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   const int drop = intercept != 0 ? 1 : 0;
   bool alone = ds->p >= 1;  // the ones column: last, alone in the last group
@@ -1014,8 +1019,23 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
     for (int64_t j = 0; j < ds->p && alone && !ds->h_gid.empty(); ++j) alone = (ds->h_gid[(size_t)j] == G - 1) == (j == ds->p - 1);
   }
   static_assert(sizeof(long long) == sizeof(int64_t), "n_effs goes to the host logic as it is");
-  const L0LsfRefusal R = l0_lsf_check(count, row_weights, reinterpret_cast<const long long*>(n_effs), ds->n, drop != 0, alone, n_cells, alphas,
+  static_assert(sizeof(int) == sizeof(int32_t), "sizes goes to the host logic and to the kernel as it is");
+  L0LsfRefusal R;
+  if (card) {
+    const L0LcRefusal C = l0_lc_check(count, row_weights, reinterpret_cast<const long long*>(n_effs), ds->n, drop != 0, alone, n_cells, sizes,
                                       etas, big_M, n_starts, starts, ds->p);
+    switch (C.kind) {
+      case L0_LC_OK: break;
+      case L0_LC_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+      case L0_LC_SIZE: return fail(SLM_ERR_BAD_ARG, "sizes[%lld] must be >= 1 (got %d)", C.which, sizes[C.which]);
+      case L0_LC_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", C.which);
+      case L0_LC_LSF: break;
+    }
+    R = C.lsf;
+  } else {
+    R = l0_lsf_check(count, row_weights, reinterpret_cast<const long long*>(n_effs), ds->n, drop != 0, alone, n_cells, alphas, etas, big_M,
+                     n_starts, starts, ds->p);
+  }
   switch (R.kind) {
     case L0_LSF_OK: break;
     case L0_LSF_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
@@ -1110,12 +1130,17 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
   auto c_host = [&](int b) { return drop ? cs.data() + (size_t)b * ld : ch.data() + (size_t)b * p; };
 
   // ---- one block: alphas | etas | starts | the eliminated c, then what comes back: F | the four status words | beta; the workspace --------
+  // (the cardinality rule: the sizes, as ints, lie where the alphas did; six status words)
+  const int nstat = card ? 6 : 4;
   const size_t n_start_words = starts ? (size_t)problems * ps : 0, n_c_words = drop ? (size_t)count * ld : 0;
   const size_t off_eta = (size_t)n_cells, off_st = 2 * (size_t)n_cells, off_c = off_st + n_start_words, off_F = off_c + n_c_words,
-               off_stat = off_F + (size_t)problems, off_beta = off_stat + 2 * (size_t)problems, words = off_beta + (size_t)problems * ps;
+               off_stat = off_F + (size_t)problems, off_beta = off_stat + ((size_t)nstat * problems + 1) / 2, words = off_beta + (size_t)problems * ps;
   const size_t ws_stride = (size_t)ps * ld;
   std::vector<double> h(words, 0.0);
-  memcpy(h.data(), alphas, sizeof(double) * (size_t)n_cells);
+  if (card)
+    memcpy(h.data(), sizes, sizeof(int32_t) * (size_t)n_cells);
+  else
+    memcpy(h.data(), alphas, sizeof(double) * (size_t)n_cells);
   memcpy(h.data() + off_eta, etas, sizeof(double) * (size_t)n_cells);
   if (starts) memcpy(h.data() + off_st, starts, sizeof(double) * n_start_words);
   if (drop) memcpy(h.data() + off_c, cs.data(), sizeof(double) * n_c_words);
@@ -1150,7 +1175,9 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
       k.yy[b] = yy[(size_t)b];
     }
     k.ld = (long long)ld;
-    k.alphas = dd;
+    k.alphas = card ? nullptr : dd;
+    k.sizes = card ? reinterpret_cast<const int*>(dd) : nullptr;
+    k.stat_stride = nstat;
     k.etas = dd + off_eta;
     k.starts = starts ? dd + off_st : nullptr;
     k.F_out = dd + off_F;
@@ -1160,13 +1187,16 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
     k.big_M = big_M;
     // (the grid of solve_l0_local_impl: two workgroups per CU, the rest by the kernel's grid-stride loop)
     const int blocks = std::min((problems + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
-    hipLaunchKernelGGL(l0_local_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    if (card)
+      hipLaunchKernelGGL(l0_local_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    else
+      hipLaunchKernelGGL(l0_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
     SLM_TRY(check_launch());
     HIP_TRY(hipMemcpyAsync(h.data() + off_F, dd + off_F, sizeof(double) * (words - off_F), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   const int* stat = reinterpret_cast<const int*>(h.data() + off_stat);
-  if (stat_out) memcpy(stat_out, stat, sizeof(int32_t) * 4 * (size_t)problems);
+  if (stat_out) memcpy(stat_out, stat, sizeof(int32_t) * (size_t)nstat * (size_t)problems);
 
   // ---- per (row set, cell): the best start; per row set the rows its winners hold, and on them the polish and the record -----------
   int unconverged = 0, first_set = -1, first_cell = -1;
@@ -1215,19 +1245,19 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
         bn += beta[j] * beta[j];
         if (drop) dot += xmean[(size_t)b * ps + j] * beta[j];
       }
-      objective_out[rc] = quad + alphas[cell] * (double)nnz;
+      objective_out[rc] = card ? quad : quad + alphas[cell] * (double)nnz;
       if (intercept_out) intercept_out[rc] = drop ? ymean[(size_t)b] - dot : 0.0;
       if (start_out) start_out[rc] = win[(size_t)cell];
-      const bool done = stat[4 * q + 2] == 0;
+      const bool done = stat[nstat * q + 2] == 0;
       if (!done && unconverged++ == 0) {
         first_set = b;
         first_cell = cell;
       }
       if (info) {
         l0_report(info + rc, done, l0_gram_loss(Gc.data(), cc.data(), m, yy[(size_t)b], bc.data()), objective_out[rc], h[off_F + q], -HUGE_VAL);
-        info[rc].n_iter = stat[4 * q + 0];
-        info[rc].rejects = stat[4 * q + 1];
-        info[rc].resid = (double)stat[4 * q + 2];
+        info[rc].n_iter = stat[nstat * q + 0];
+        info[rc].rejects = stat[nstat * q + 1];
+        info[rc].resid = (double)stat[nstat * q + 2];
         info[rc].beta_norm = std::sqrt(bn);
         info[rc].mode = 8;
       }
@@ -1247,8 +1277,18 @@ extern "C" int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const do
                                         int32_t intercept, int32_t n_cells, const double* alphas, const double* etas, double big_M,
                                         int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
                                         double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
-  return solve_l0_local_folds_impl(ds, count, row_weights, n_effs, intercept, n_cells, alphas, etas, big_M, n_starts, starts, swaps, beta_out,
-                                   intercept_out, objective_out, start_out, stat_out, info);
+  return solve_l0_local_folds_impl(ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, etas, big_M, n_starts, starts, swaps,
+                                   beta_out, intercept_out, objective_out, start_out, stat_out, info, false);
+}
+
+// The cardinality form of the l0 local search: every (row set, (size, eta) cell, start) problem from one launch of
+// l0_local_kernel<true>: at most sizes[e] non-zeros, nothing proven.
+extern "C" int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                                          int32_t intercept, int32_t n_cells, const int32_t* sizes, const double* etas, double big_M,
+                                          int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
+                                          double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
+  return solve_l0_local_folds_impl(ds, count, row_weights, n_effs, intercept, n_cells, nullptr, sizes, etas, big_M, n_starts, starts, swaps,
+                                   beta_out, intercept_out, objective_out, start_out, stat_out, info, true);
 }
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.

@@ -1425,6 +1425,199 @@ inline L0LsfRefusal l0_lsf_check(long long count, const double* const* row_weigh
   return R;
 }
 
+// ---- local subsets: the cardinality form (slm_solve_l0_local_subsets; tests/l0_local_subsets_host_test.cpp) -------------------
+//
+// For a cell (k, eta), H = G + 2 eta I:   minimise Q(beta) = 1/2 beta^T H beta - c^T beta   over |beta_j| <= big_M, ||beta||_0 <= k
+// (DESIGN 4d "Local subsets").  The state and the two decisions are the local search's; the rule, from a start of ANY support
+// size inside the box:
+//   1. Shrink: while nnz > k the support column with the smallest g_i = l0_ls_coord(r_i + d_i beta_i, d_i).gain leaves (ties:
+//      the lowest index).
+//   2. Descent on the support: j over the support cyclically, beta_j <- b, no threshold, no column enters; b == 0 leaves.  It
+//      ends as the local search's descent does.
+//   3. Grow: if nnz < k the outside column with the largest l0_ls_coord(r_j, d_j).gain (ties: the lowest j) enters at b_j when
+//      |b_j| sqrt(d_j) > tol; then 2.
+//   4. Swap scan, once 3 adds nothing: the local search's with alpha = 0; a swap goes to 2, none ends the problem.
+// `drops` counts the columns that left in 1 or 2, `grows` those that entered in 3.
+struct L0LcResult {
+  double Q = 0.0;  // the objective at the returned beta
+  int sweeps = 0, swaps = 0, status = 0, nnz = 0, grows = 0, drops = 0;
+  long long changes = 0;  // columns of H applied to r after the start
+};
+
+// The rule on one problem: the arguments of l0_ls_solve with the size k in alpha's place.  k >= p is legal.
+inline L0LcResult l0_lc_solve(const double* G, size_t ld, const double* c, int p, int k, double eta, double big_M, double yy, bool swaps,
+                              const double* start, double* beta) {
+  L0LcResult R;
+  std::vector<double> r(c, c + p), d((size_t)p);
+  const double eta2 = 2.0 * eta;
+  double dmax = 0.0;
+  for (int j = 0; j < p; ++j) {
+    d[(size_t)j] = G[(size_t)j * ld + j] + eta2;
+    dmax = std::max(dmax, d[(size_t)j]);
+  }
+  for (int j = 0; j < p; ++j) {
+    if (!(d[(size_t)j] > L0_PIVOT * dmax)) d[(size_t)j] = 0.0;  // (0 marks a column that stays out)
+    beta[j] = start && d[(size_t)j] > 0.0 ? start[j] : 0.0;
+  }
+  auto axpy = [&](int j, double w) {  // r += w H[:, j]
+    const double* row = G + (size_t)j * ld;
+    for (int i = 0; i < p; ++i) r[(size_t)i] += w * (i == j ? row[i] + eta2 : row[i]);
+    ++R.changes;
+  };
+  int nnz = 0;
+  for (int j = 0; j < p; ++j)
+    if (beta[j] != 0.0) {
+      axpy(j, -beta[j]);
+      ++nnz;
+    }
+  R.changes = 0;
+  const double tol = L0_CD_TOL * std::sqrt(yy);
+  for (;;) {
+    // ---- 1. shrink: the weakest column of the support leaves ---------------------------------------------------------------------
+    while (nnz > k) {
+      double gb = HUGE_VAL;
+      int ib = -1;
+      for (int i = 0; i < p; ++i) {
+        if (beta[i] == 0.0) continue;
+        const double g = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * beta[i], d[(size_t)i], big_M).gain;
+        if (g < gb) {  // (ties: the lowest i)
+          gb = g;
+          ib = i;
+        }
+      }
+      if (ib < 0) break;
+      const double bi = beta[ib];
+      beta[ib] = 0.0;
+      axpy(ib, bi);
+      --nnz;
+      ++R.drops;
+    }
+    // ---- 2. the descent on the support --------------------------------------------------------------------------------------------
+    for (int sw = 0;; ++sw) {
+      if (sw == L0_CD_SWEEPS) {
+        R.status |= L0_LS_SWEEPS_OUT;
+        break;
+      }
+      bool moved = false;
+      double maxd = 0.0;
+      for (int j = 0; j < p; ++j) {
+        if (beta[j] == 0.0) continue;
+        const double dj = d[(size_t)j];
+        const double nb = l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M).b;
+        if (nb == beta[j]) continue;
+        const double delta = nb - beta[j];
+        if (nb == 0.0) {
+          moved = true;
+          --nnz;
+          ++R.drops;
+        }
+        maxd = std::max(maxd, std::fabs(delta) * std::sqrt(dj));
+        beta[j] = nb;
+        axpy(j, -delta);
+      }
+      ++R.sweeps;
+      if (!moved && maxd <= tol) break;
+    }
+    if (R.status) break;
+    // ---- 3. grow: the best column outside enters, if it moves at all --------------------------------------------------------------
+    if (nnz < k) {
+      double gb = -1.0, bb = 0.0;
+      int jb = -1;
+      for (int j = 0; j < p; ++j) {
+        if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
+        const L0LsCoord co = l0_ls_coord(r[(size_t)j], d[(size_t)j], big_M);
+        if (co.gain > gb) {  // (ties: the lowest j)
+          gb = co.gain;
+          bb = co.b;
+          jb = j;
+        }
+      }
+      if (jb >= 0 && std::fabs(bb) * std::sqrt(d[(size_t)jb]) > tol) {
+        beta[jb] = bb;
+        axpy(jb, -bb);
+        ++nnz;
+        ++R.grows;
+        continue;
+      }
+    }
+    if (!swaps) break;
+    // ---- 4. the swap scan of l0_ls_solve with alpha = 0 ----------------------------------------------------------------------------
+    bool swapped = false;
+    for (int i = 0; i < p && !swapped; ++i) {
+      const double bi = beta[i];
+      if (bi == 0.0) continue;
+      const double* row = G + (size_t)i * ld;
+      const double gi = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * bi, d[(size_t)i], big_M).gain;
+      double gb = -1.0, bb = 0.0;
+      int jb = -1;
+      for (int j = 0; j < p; ++j) {
+        if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
+        const L0LsCoord co = l0_ls_coord(r[(size_t)j] + row[j] * bi, d[(size_t)j], big_M);
+        if (co.gain > gb) {  // (ties: the lowest j)
+          gb = co.gain;
+          bb = co.b;
+          jb = j;
+        }
+      }
+      if (jb < 0 || !l0_ls_swap_better(gb, gi, 0.0)) continue;
+      beta[i] = 0.0;
+      axpy(i, bi);
+      beta[jb] = bb;
+      axpy(jb, -bb);
+      ++R.swaps;
+      swapped = true;
+    }
+    if (!swapped) break;
+    if (R.swaps == L0_LS_SWAPS) {
+      R.status |= L0_LS_SWAPS_OUT;
+      break;
+    }
+  }
+  // Q = 1/2 beta^T H beta - c^T beta with H beta = c - r
+  double acc = 0.0;
+  for (int j = 0; j < p; ++j) {
+    acc += beta[j] * (c[j] + r[(size_t)j]);
+    R.nnz += beta[j] != 0.0;
+  }
+  R.Q = -0.5 * acc;
+  return R;
+}
+
+// What slm_solve_l0_local_subsets refuses before a device is touched, in this order: a NULL sizes or etas; the first size < 1;
+// the first eta that is negative or not finite; then everything l0_lsf_check refuses that is not about a cell's values (`lsf`:
+// the row sets, the problem counts, big_M, the width, the intercept, the weights, the box of the starts).  which: the cell.
+enum L0LcKind { L0_LC_OK = 0, L0_LC_NULL, L0_LC_SIZE, L0_LC_ETA, L0_LC_LSF };
+struct L0LcRefusal {
+  L0LcKind kind = L0_LC_OK;
+  L0LsfRefusal lsf;
+  long long which = 0;
+};
+inline L0LcRefusal l0_lc_check(long long count, const double* const* row_weights, const long long* n_effs, long long n, bool intercept,
+                               bool last_alone, long long n_cells, const int* sizes, const double* etas, double big_M, long long n_starts,
+                               const double* starts, long long p) {
+  L0LcRefusal R;
+  if (!sizes || !etas) {
+    R.kind = L0_LC_NULL;
+    return R;
+  }
+  for (long long e = 0; e < n_cells; ++e)
+    if (sizes[e] < 1) {
+      R.kind = L0_LC_SIZE;
+      R.which = e;
+      return R;
+    }
+  for (long long e = 0; e < n_cells; ++e)
+    if (!(etas[e] >= 0.0) || !std::isfinite(etas[e])) {
+      R.kind = L0_LC_ETA;
+      R.which = e;
+      return R;
+    }
+  // (the etas stand in for the alphas: they have just passed the test both get)
+  R.lsf = l0_lsf_check(count, row_weights, n_effs, n, intercept, last_alone, n_cells, etas, etas, big_M, n_starts, starts, p);
+  if (R.lsf.kind != L0_LSF_OK) R.kind = L0_LC_LSF;
+  return R;
+}
+
 // l0_eliminate_last at a leading dimension, in two parts (the note on cancellation above it applies unchanged).
 // The vectors and scalars, from the ones column g1 [ps] (row or column `last` of G: symmetric), G11 and c [ps + 1]:
 //     c' = c - g1 c1 / G11,  yy' = yy - c1^2 / G11,  xmean = g1 / G11,  ymean = c1 / G11.     false: G11 is not positive.

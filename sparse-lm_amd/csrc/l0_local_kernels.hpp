@@ -28,6 +28,15 @@
 // argument; r is made a scalar (readfirstlane: a wave is one problem), so the choice is three scalar loads per problem and
 // nothing per lane.  With one row set r = 0 and e = q / n_starts: the parent's problem, change by change.
 //
+// THE CARDINALITY RULE (l0_local_kernel<true>; slm_solve_l0_local_subsets; the host twin l0_lc_solve, l0_host.hpp "local
+// subsets").  Cell e is (sizes[e], etas[e]):  minimise Q = 1/2 beta^T H beta - c^T beta over the box with ||beta||_0 <= k.  The same
+// wave, state, Gram reads and outputs; three moves more, each a scan of the registers with no row read of its own: SHRINK (a
+// start larger than k loses its column of the smallest one-coordinate gain, an arg-min over the support, until k are left),
+// the descent restricted to beta != 0 with no threshold (a coordinate whose b is exactly 0 leaves), and GROW (below k, the
+// arg-max of the gains over the columns outside enters when it would move by more than the descent's stopping tolerance; the
+// descent runs again).  The swap scan follows once nothing grows, with alpha = 0.  stat_out gets two words more per problem:
+// grows and drops.  The penalised instantiation l0_local_kernel<false> is the code it was.
+//
 // l0_eliminate_kernel is the intercept of those row sets: the dataset is [X | 1] with the ones column last, and for each row
 // set the Schur complement of that column,  G' = G - g1 g1^T / G11  (g1 = G[:, last], G11 = G[last][last]), is written into a
 // workspace of the call with the dataset's leading dimension -- exactly weighted centring of X by the row set's own means --
@@ -54,10 +63,13 @@ struct L0LsArgs {
   const double* starts;  // [n_problems][p] inside the box, or NULL: zero
   double* beta_out;      // [n_problems][p]
   double* F_out;         // [n_problems]
-  int* stat_out;         // [n_problems][4]: sweeps, swaps, status word (L0_LS_SWEEPS_OUT | L0_LS_SWAPS_OUT), non-zeros
+  int* stat_out;         // [n_problems][stat_stride]: sweeps, swaps, status word (L0_LS_SWEEPS_OUT | L0_LS_SWAPS_OUT), non-zeros;
+                         // the cardinality rule: then grows, drops
+  const int* sizes;      // [n_cells]: the cardinality rule's k per cell (l0_local_kernel<true>; alphas is not read there)
   long long ld;
   int p, n_problems, n_starts, swaps;  // swaps == 0: the descent alone
   int n_cells;                         // problem q = (r * n_cells + e) * n_starts + s: row set r, cell e, start s
+  int stat_stride;                     // 4, the cardinality rule 6
   double big_M;
 };
 
@@ -106,6 +118,8 @@ static __device__ __forceinline__ void l0_ls_axpy(double (&r)[L0_LS_SLOTS], cons
     }
 }
 
+// CARD: the cardinality rule (below, at the loop); else the penalised rule of the unit's head.
+template <bool CARD>
 static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs a) {
   const int lane = threadIdx.x & 63;
   const int p = a.p, ns = (p + 63) >> 6;
@@ -119,7 +133,7 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
     const double* __restrict__ G = a.G[rs];
     const double* __restrict__ cv = a.c[rs];
     const double tol = L0_CD_TOL * sqrt(a.yy[rs]);
-    const double alpha = a.alphas[cell], eta2 = 2.0 * a.etas[cell];
+    const double alpha = CARD ? 0.0 : a.alphas[cell], eta2 = 2.0 * a.etas[cell];
     double beta[L0_LS_SLOTS], r[L0_LS_SLOTS], d[L0_LS_SLOTS];
     double dmax = 0.0;
 #pragma unroll
@@ -155,8 +169,42 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
       }
 
     int sweeps = 0, swaps = 0, status = 0;
+    int kmax = 0, nact = 0, grows = 0, drops = 0;  // (the cardinality rule's: the cell's size, the support's, the two counts)
+    if constexpr (CARD) {
+      kmax = a.sizes[cell];
+#pragma unroll
+      for (int s = 0; s < L0_LS_SLOTS; ++s)
+        if (s < ns) nact += __popcll(__ballot(beta[s] != 0.0));
+      // ---- shrink: while the support is larger than k its weakest column leaves (only a start can be: nothing below adds beyond k)
+      while (nact > kmax) {
+        double gb = HUGE_VAL;
+        int ib = 0x7fffffff;
+#pragma unroll
+        for (int t = 0; t < L0_LS_SLOTS; ++t)
+          if (t < ns) {
+            const double g = l0_ls_coord(r[t] + d[t] * beta[t], d[t], big_M).gain;
+            if (beta[t] != 0.0 && g < gb) {  // (ascending slots: the lane keeps its lowest i on ties)
+              gb = g;
+              ib = t * 64 + lane;
+            }
+          }
+        const double gmin = -l0_wave_max(-gb);
+        const int imin = l0_ls_wave_min(gb == gmin ? ib : 0x7fffffff);
+        if (imin == 0x7fffffff) break;
+        double mine = 0.0;
+#pragma unroll
+        for (int t = 0; t < L0_LS_SLOTS; ++t)
+          if (t == (imin >> 6)) {
+            mine = beta[t];
+            if (lane == (imin & 63)) beta[t] = 0.0;
+          }
+        l0_ls_axpy(r, G, ld, p, ns, lane, eta2, imin, l0_bcast(mine, imin & 63));
+        --nact;
+        ++drops;
+      }
+    }
     for (;;) {
-      // ---- 1. the descent to its fixed point --------------------------------------------------------------------------------
+      // ---- 1. the descent to its fixed point (the cardinality rule: on the support alone, no threshold, b == 0 leaves) ---------
       for (int sw = 0;; ++sw) {
         if (sw == L0_CD_SWEEPS) {
           status |= L0_LS_SWEEPS_OUT;
@@ -173,8 +221,9 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
 #pragma unroll
           for (int s = 0; s < L0_LS_SLOTS; ++s)
             if (!found && s >= s0 && s < ns) {
-              const double nb = l0_ls_threshold(l0_ls_coord(r[s] + d[s] * beta[s], d[s], big_M), alpha);
-              const unsigned long long bal = __ballot(d[s] > 0.0 && s * 64 + lane >= cursor && nb != beta[s]);
+              const L0LsCoord cd = l0_ls_coord(r[s] + d[s] * beta[s], d[s], big_M);
+              const double nb = CARD ? cd.b : l0_ls_threshold(cd, alpha);
+              const unsigned long long bal = __ballot((CARD ? beta[s] != 0.0 : d[s] > 0.0) && s * 64 + lane >= cursor && nb != beta[s]);
               if (bal) {
                 const int k = __builtin_ctzll(bal);
                 const double nbk = l0_bcast(nb, k), old = l0_bcast(beta[s], k), dk = l0_bcast(d[s], k);
@@ -183,6 +232,11 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
                 jf = s * 64 + k;
                 delta = nbk - old;
                 moved = moved || ((nbk != 0.0) != (old != 0.0));
+                if constexpr (CARD)
+                  if (nbk == 0.0) {
+                    --nact;
+                    ++drops;
+                  }
                 maxd = fmax(maxd, fabs(delta) * sqrt(dk));
               }
             }
@@ -192,6 +246,37 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
         }
         ++sweeps;
         if (!moved && maxd <= tol) break;
+      }
+      if constexpr (CARD) {
+        // ---- grow: below k, the outside column with the largest gain enters -- if it would move by more than the descent's own
+        // stopping tolerance -- and the descent runs again.  The swap scan's arg-max without a removed column and without a row read.
+        if (status) break;
+        if (nact < kmax) {
+          double gb = -1.0, bb = 0.0;
+          int jb = 0x7fffffff;
+#pragma unroll
+          for (int t = 0; t < L0_LS_SLOTS; ++t)
+            if (t < ns) {
+              const L0LsCoord co = l0_ls_coord(r[t], d[t], big_M);
+              if (d[t] > 0.0 && beta[t] == 0.0 && co.gain > gb) {  // (ascending slots: the lane keeps its lowest j on ties)
+                gb = co.gain;
+                bb = fabs(co.b) * sqrt(d[t]) > tol ? co.b : 0.0;  // (0: it would not move)
+                jb = t * 64 + lane;
+              }
+            }
+          const double gmax = l0_wave_max(gb);
+          const int jmin = l0_ls_wave_min(gb == gmax ? jb : 0x7fffffff);
+          const double bj = jmin != 0x7fffffff ? l0_bcast(bb, jmin & 63) : 0.0;  // (that lane's best IS jmin)
+          if (bj != 0.0) {
+#pragma unroll
+            for (int t = 0; t < L0_LS_SLOTS; ++t)
+              if (t == (jmin >> 6) && lane == (jmin & 63)) beta[t] = bj;
+            l0_ls_axpy(r, G, ld, p, ns, lane, eta2, jmin, -bj);
+            ++nact;
+            ++grows;
+            continue;
+          }
+        }
       }
       if (!a.swaps || status) break;
       // ---- 2. the swap scan: the first i of the support that a column outside replaces with a gain ----------------------------
@@ -260,10 +345,15 @@ static __global__ __launch_bounds__(64 * L0_WAVES) void l0_local_kernel(L0LsArgs
     nnz = (int)l0_wave_sum((double)nnz);
     if (lane == 0) {
       a.F_out[q] = -0.5 * acc + alpha * (double)nnz;
-      a.stat_out[4 * q + 0] = sweeps;
-      a.stat_out[4 * q + 1] = swaps;
-      a.stat_out[4 * q + 2] = status;
-      a.stat_out[4 * q + 3] = nnz;
+      int* stat = a.stat_out + (long long)q * a.stat_stride;
+      stat[0] = sweeps;
+      stat[1] = swaps;
+      stat[2] = status;
+      stat[3] = nnz;
+      if constexpr (CARD) {
+        stat[4] = grows;
+        stat[5] = drops;
+      }
     }
   }
 }

@@ -106,6 +106,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_local",
     "slm_solve_l0_local_descent",
     "slm_solve_l0_local_folds",
+    "slm_solve_l0_local_subsets",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -380,6 +381,7 @@ def load_library():
             "slm_solve_l0_local": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_descent": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_folds": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_subsets": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1730,6 +1732,81 @@ class Dataset:
             return betas, icpts, objectives, winners, stats, [out]
         return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
                 stats.reshape(count, cells, ns, 4), [out[r * cells:(r + 1) * cells] for r in range(count)])
+
+    def solve_l0_local_subsets(self, row_weights, n_effs, sizes, etas=0.0, intercept=False, big_M=100.0, starts=None, swaps=True,
+                               n_cells=None, n_starts=None, binding=None):
+        """``slm_solve_l0_local_subsets``: LOCAL SUBSETS, the l0 local search in its cardinality form -- for every row set and
+        every cell ``(sizes[e], etas[e])`` an approximate minimiser of ``Q = 1/2 b^T (G + 2 eta I) b - c^T b`` over
+        ``|b_j| <= big_M`` with at most ``sizes[e]`` non-zeros (shrink, descent on the support, grow, swap scan:
+        csrc/l0_local_kernels.hpp), up to 1024 columns, from ONE launch.  Row sets, ``intercept``, ``starts`` (of any support
+        size) and the layout of the result as for ``solve_l0_local_folds``; ``[None], [0]`` is the dataset's own rows.
+        ``swaps=False`` stops once nothing grows: greedy forward selection with re-fitting.  Returns ``(betas [count, cells,
+        ps], intercepts, objectives [count, cells] (Q after the polish), winning starts, stats [count, cells, n_starts, 6],
+        infos)``: ``stats`` holds sweeps, accepted swaps, status word, non-zeros, grows and drops of EVERY problem; ``infos``
+        the dicts of ``solve_l0_local`` with ``grows`` and ``drops`` of the winner beside them.  Nothing is proven."""
+        ps = self.p - (1 if intercept else 0)
+        rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
+        nes = [int(v) for v in n_effs]
+        if len(nes) != len(rws):
+            raise ValueError("row_weights and n_effs differ in length")
+        count = len(rws)
+        sz = None
+        if sizes is not None:  # (None reaches the engine as NULL, by the ctypes route: its first refusal)
+            raw = np.asarray(sizes).reshape(-1)
+            if raw.size and not np.all(np.isfinite(raw.astype(np.float64)) & (raw == np.floor(raw)) & (np.abs(raw) < 2 ** 31)):
+                raise ValueError("sizes must be integers")
+            sz = np.ascontiguousarray(raw, dtype=np.int32)
+        if etas is None or sz is None:
+            et = None if etas is None else np.ascontiguousarray(np.atleast_1d(etas), dtype=np.float64).reshape(-1)
+        else:
+            et = np.ascontiguousarray(np.broadcast_to(np.asarray(etas, dtype=np.float64), sz.shape), dtype=np.float64).reshape(-1)
+        given = [len(v) for v in (sz, et) if v is not None]
+        cells = (min(given) if given else 1) if n_cells is None else int(n_cells)
+        if any(g < cells for g in given):
+            raise ValueError("sizes and etas must have n_cells entries")
+        st = None
+        ns = 1 if n_starts is None else int(n_starts)
+        if starts is not None:
+            st = np.ascontiguousarray(starts, dtype=np.float64)
+            if n_starts is None:
+                if st.ndim != 4 or st.shape[:2] != (count, cells) or st.shape[3] != ps:
+                    raise ValueError(f"starts must have the shape ({count}, {cells}, n_starts, {ps})")
+                ns = st.shape[2]
+            st = st.reshape(-1)
+        # (else the engine refuses: the outputs only have to exist)
+        sized = 1 <= count <= 16 and cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS and count * cells * ns <= L0_LOCAL_MAX_PROBLEMS
+        if st is not None and sized and st.size != count * cells * ns * ps:
+            raise ValueError(f"starts has {st.size} entries, expected {count * cells * ns * ps}")
+        cnt = count * cells if sized else 1
+        problems = cnt * ns if sized else 1
+        pad = np.zeros(1)  # (an empty array has no address worth handing over)
+        ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
+        ne = np.array(nes or [0], dtype=np.int64)
+        if sz is not None and not len(sz):
+            sz = np.zeros(1, dtype=np.int32)
+        if et is not None and not len(et):
+            et = pad
+        tail = (int(bool(intercept)), cells, sz, et, float(big_M), ns, st if sized else None, int(bool(swaps)))
+        if sz is None or et is None:
+            binding = False  # (the compiled route takes arrays: a NULL goes by ctypes)
+        (betas, icpts, objectives, winners, stats), infos, rc = self._l0_call(
+            "solve_l0_local_subsets", binding, (count, ptrs, ne) + tail,
+            [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros((problems, 6), dtype=np.int32)],
+            records=cnt, binding_args=(self.n, rws, nes, bool(intercept)) + tail[1:-1] + (bool(swaps),))
+        names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
+        out = [{
+            "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
+            "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
+            "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
+        } for e in range(cnt)]
+        if not sized:
+            return betas, icpts, objectives, winners, stats, [out]
+        stats = stats.reshape(count, cells, ns, 6)
+        for e in range(cnt):
+            won = stats[e // cells, e % cells, int(winners[e])]
+            out[e]["grows"], out[e]["drops"] = int(won[4]), int(won[5])
+        return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
+                stats, [out[r * cells:(r + 1) * cells] for r in range(count)])
 
 
 class _HostPool:

@@ -17,13 +17,18 @@ profile under an l1 term: ``L1L0`` at every ``alpha`` from one search per ``eta`
 one-for-one swaps for the ``RegularizedL0`` / ``L2L0`` objective over a whole (alpha, eta) grid from one launch per round, for up
 to 1024 columns -- beyond the 128 at which every search above stops.  They prove nothing and say so (``proven_optimal_`` is False).
 ``l0_local_cv`` / ``L0LocalCV`` (``model/_l0_local_cv.py``) cross-validate that search: every fold's grid and the grid of all rows from
-one launch per round.
+one launch per round.  ``l0_local_subsets`` / ``L0LocalSubsets`` (``model/_l0_local_subsets.py``) are that search in the
+CARDINALITY form -- an incumbent for ``BestSubsetSelection`` / ``RidgedBestSubsetSelection`` at every ``sparse_bound`` of a list,
+the approximate twin of ``l0_profile`` up to 1024 columns -- and ``l0_local_subsets_cv`` / ``L0LocalSubsetsCV``
+(``model/_l0_local_subsets_cv.py``) cross-validate the size.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
 from .model._l0_grid_cv import L0ProfileGridCV, l1l0_profile_cv, l2l0_profile_cv  # noqa: F401  (CV over (alpha, eta) from one launch; outside __all__)
 from .model._l0_local import L0LocalPath, l0_local_search  # noqa: F401  (approximate, up to 1024 columns; outside __all__)
 from .model._l0_local_cv import L0LocalCV, l0_local_cv  # noqa: F401  (the local search of every CV fold from one launch per round; outside __all__)
+from .model._l0_local_subsets import L0LocalSubsets, l0_local_subsets  # noqa: F401  (approximate best subsets of every size; outside __all__)
+from .model._l0_local_subsets_cv import L0LocalSubsetsCV, l0_local_subsets_cv  # noqa: F401  (their cross-validation, one launch per round; outside __all__)
 from .model._l0_profile import L0Profile, l0_profile  # noqa: F401  (not estimators: outside __all__, which tests pin)
 from .model._l1l0 import L1L0
 from .model._l1l0_profile import L1L0Profile, l1l0_profile  # noqa: F401  (L1L0 at every alpha from one search; outside __all__)

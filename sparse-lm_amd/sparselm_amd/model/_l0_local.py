@@ -18,9 +18,9 @@ One launch runs every (cell, start) problem, one wavefront each.  Round 0 starts
 ``alpha`` and in ``eta`` and keeps a cell's new result only where the objective improves (by more than 1e-12 relative:
 rounding is no improvement); the rounds end early when no cell improved.
 
-Not built: groups and a hierarchy, a bound on the cardinality (best-subset form), an l1 term, a general Tikhonov matrix,
-constraints, handing the result to the exact search as its seed.  (Cross-validation folds in the launch: ``l0_local_cv``,
-``model/_l0_local_cv.py``.)
+Not built: groups and a hierarchy, an l1 term, a general Tikhonov matrix, constraints, handing the result to the exact search
+as its seed.  (Cross-validation folds in the launch: ``l0_local_cv``, ``model/_l0_local_cv.py``; a bound on the cardinality, the
+best-subset form: ``l0_local_subsets``, ``model/_l0_local_subsets.py``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_search``, ``L0LocalPath``).
 """

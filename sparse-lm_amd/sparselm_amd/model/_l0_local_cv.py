@@ -16,8 +16,8 @@ the rule is closer than that to a tie); the coefficients are NOT the same bytes:
 its held-out rows, and centring is by elimination of the ones column instead of on the rows.  Nothing is proven optimal.
 
 Limits: the local search's 1024 columns, at most 15 splits (folds plus all rows fill the Gram store's 16 entries),
-``(splits + 1) x cells x starts <= 8192`` problems per launch; held-out scores are unweighted.  Not built: groups, a bound on
-the cardinality, an l1 term, rerouting ``GridSearchCV``.
+``(splits + 1) x cells x starts <= 8192`` problems per launch; held-out scores are unweighted.  Not built: groups, an l1 term,
+rerouting ``GridSearchCV``.  (A bound on the cardinality: ``l0_local_subsets_cv``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_cv``, ``L0LocalCV``).
 """
@@ -96,6 +96,43 @@ class L0LocalCV:
         return L0LocalSearch(results, best, self.full_.coefs_[a, e].copy(), float(self.full_.intercepts_[a, e]))
 
 
+def _fold_splits(cv, X, y, name):
+    """The ``(train, test)`` index pairs of ``cv`` (anything ``check_cv`` takes): 1 .. 15 of them."""
+    splitter = check_cv(cv, y, classifier=False)
+    n_splits = int(splitter.get_n_splits(X, y))
+    if not 1 <= n_splits <= MAX_SPLITS:
+        raise ValueError(f"{name} takes 1 .. {MAX_SPLITS} splits (got {n_splits}): the folds and all rows share one launch of "
+                         f"at most {MAX_SPLITS + 1} row sets")
+    return [(np.asarray(tr), np.asarray(te)) for tr, te in splitter.split(X, y)]
+
+
+def _row_sets(splits, n, w):
+    """``(row_weights, n_effs)`` of the folds' training rows, then all rows: the sample weights on a set's rows, scaled to sum
+    to its row count."""
+    base = np.ones(n) if w is None else np.asarray(w, dtype=np.float64)
+    row_weights, n_effs = [], []
+    for rows in [tr for tr, _ in splits] + [np.arange(n)]:
+        m = np.zeros(n)
+        m[rows] = base[rows]
+        total = float(m.sum())
+        if not total > 0.0:
+            raise ValueError("a training set has no weight")
+        row_weights.append(m * (len(rows) / total))
+        n_effs.append(len(rows))
+    return row_weights, n_effs
+
+
+def _held_out_scores(scoring, X, y, splits, paths):
+    """folds x A x E: the unweighted score of every cell of ``paths[f]`` on fold f's held-out rows, by numpy."""
+    A, E = paths[0].coefs_.shape[:2]
+    scores = np.empty((len(splits), A, E))
+    for f, (_, te) in enumerate(splits):
+        for a in range(A):
+            for e in range(E):
+                scores[f, a, e] = _score(scoring, y[te] - (X[te] @ paths[f].coefs_[a, e] + paths[f].intercepts_[a, e]))
+    return scores
+
+
 def l0_local_cv(X, y, *, alphas, etas=(0.0,), cv=5, big_M=100, fit_intercept=False, sample_weight=None, starts=None, max_rounds=2,
                 scoring="neg_root_mean_squared_error", solver_options=None) -> L0LocalCV:
     """``l0_local_search`` on every cross-validation fold's training rows and on all rows, one launch per round on the GPU.
@@ -137,26 +174,12 @@ def l0_local_cv(X, y, *, alphas, etas=(0.0,), cv=5, big_M=100, fit_intercept=Fal
         if not np.all(np.abs(st) <= big_M):  # (a NaN fails too)
             raise ValueError(f"starts must lie inside the box |beta_j| <= big_M = {big_M:g}")
         first = np.concatenate([first, st], axis=2)
-    splitter = check_cv(cv, y, classifier=False)
-    n_splits = int(splitter.get_n_splits(X, y))
-    if not 1 <= n_splits <= MAX_SPLITS:
-        raise ValueError(f"l0_local_cv takes 1 .. {MAX_SPLITS} splits (got {n_splits}): the folds and all rows share one launch of "
-                         f"at most {MAX_SPLITS + 1} row sets")
-    splits = [(np.asarray(tr), np.asarray(te)) for tr, te in splitter.split(X, y)]
+    splits = _fold_splits(cv, X, y, "l0_local_cv")
     R = len(splits) + 1
     most = max(first.shape[2], (2 * (A > 1) + 2 * (E > 1)) if max_rounds else 0)  # (a round starts a cell from its neighbours in the grid)
     if R * A * E * most > _MAX_PROBLEMS:
         raise ValueError(f"{R} row sets x {A * E} cells x up to {most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
-    base = np.ones(n) if w is None else np.asarray(w, dtype=np.float64)
-    row_weights, n_effs = [], []
-    for rows in [tr for tr, _ in splits] + [np.arange(n)]:  # the folds' training rows, then all rows
-        m = np.zeros(n)
-        m[rows] = base[rows]
-        total = float(m.sum())
-        if not total > 0.0:
-            raise ValueError("a training set has no weight")
-        row_weights.append(m * (len(rows) / total))
-        n_effs.append(len(rows))
+    row_weights, n_effs = _row_sets(splits, n, w)  # the folds' training rows, then all rows
     cell_alpha, cell_eta = np.repeat(al, E), np.tile(et, A)
 
     from .. import _engine
@@ -201,11 +224,7 @@ def l0_local_cv(X, y, *, alphas, etas=(0.0,), cv=5, big_M=100, fit_intercept=Fal
                           take(infos[r], "swaps").astype(int), take(infos[r], "sweeps").astype(int), take(infos[r], "converged").astype(bool))
               for r in range(R)]
     paths, full = tables[:-1], tables[-1]
-    cell_scores = np.empty((len(splits), A, E))
-    for f, (_, te) in enumerate(splits):
-        for a in range(A):
-            for e in range(E):
-                cell_scores[f, a, e] = _score(scoring, y[te] - (X[te] @ paths[f].coefs_[a, e] + paths[f].intercepts_[a, e]))
+    cell_scores = _held_out_scores(scoring, X, y, splits, paths)
     solver_info = {"launches": launches, "rounds": len(history), "problems": problems, "max_sweeps": max_sweeps, "max_swaps": max_swaps,
                    "winner_max_sweeps": int(max(t.sweeps_.max() for t in tables)), "winner_max_swaps": int(max(t.swaps_.max() for t in tables)),
                    "proven_optimal": False}
