@@ -33,10 +33,10 @@
 //   slm_solve_l0_profile_grid  the BATCH instantiations, with or without L1: one problem per (row set, eta), up to L0_GRID_MAX, from
 //       one launch.  Gram and elimination once per row set; order, seed, (l1: the bound) and the copy of the block per problem.
 //       slm_solve_l0_profile_batch is its call with one ridge eta.
-// Beside them, and none of the above: slm_solve_l0_local, slm_solve_l0_local_descent (solve_l0_local_impl, at the end of the
-// unit; csrc/l0_local_kernels.hpp) -- the local search beyond 128 columns, which proves nothing -- and
-// slm_solve_l0_local_folds (solve_l0_local_folds_impl), the same search on up to 16 row sets of the dataset in one launch;
-// slm_solve_l0_local_subsets is that body with the kernel's cardinality rule: sizes where the alphas are.
+// Beside them, and none of the above: the local search beyond 128 columns, which proves nothing (csrc/l0_local_kernels.hpp) --
+// four entries, ONE body at the end of the unit (solve_l0_local_folds_impl): slm_solve_l0_local_folds, the search on up to 16 row sets
+// of the dataset in one launch; slm_solve_l0_local and slm_solve_l0_local_descent, that call with one row set, the dataset's own
+// rows; slm_solve_l0_local_subsets, that call with the kernel's cardinality rule: sizes where the alphas are.
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -843,133 +843,6 @@ int solve_l0_con_impl(slm_dataset* ds, double alpha, int32_t max_groups, double 
   return SLM_OK;
 }
 
-// slm_solve_l0_local, slm_solve_l0_local_descent (DESIGN 4d "Local search"): NOT a search over supports and not this unit's
-// pipeline -- no order, no seed, no block image.  check (l0_ls_check and the dataset's shape, before a device is touched);
-// the dataset's own Gram FILED, not fetched: the kernel reads ds->cov[entry] in place with the dataset's leading dimension
-// and puts 2 eta on the diagonal itself; ONE launch of l0_local_kernel over every (cell, start) problem; per cell the best
-// start by (F, then the lowest index); the winner polished on a host copy of G (l0_fetch_gram, l0_ls_polish); the record:
-//
-//   entry                 n_iter    rejects   resid                       mu                    kkt             L       mode
-//   solve_l0_local[_descent]  sweeps  swaps   the winner's status word    the objective before  the objective   -inf    8
-//                         of the    accepted  (1: a descent ran out of    the polish (the       after it        (no
-//                         winner    (winner)  sweeps, 2: the swap cap)    kernel's F)                           bound)
-//
-// status is SLM_OK where the winner reached its fixed point and SLM_ERR_NOT_CONVERGED where a cap ended it; beta_norm and
-// loss as for solve_l0.  Nothing here is proven optimal, whatever the status.
-static_assert(SLM_L0_LOCAL_PMAX == L0_LS_PMAX && SLM_L0_LOCAL_MAX_PROBLEMS == L0_LS_MAX_PROBLEMS, "the header and the host logic name one set of limits");
-int solve_l0_local_impl(bool swaps, slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
-                        int32_t n_starts, const double* starts, double* beta_out, double* objective_out, int32_t* start_out,
-                        slm_point_info* info) {
-  if (!ds || !beta_out || !objective_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  long long which = 0;
-  switch (l0_ls_check(n_cells, alphas, etas, big_M, n_starts, starts, ds->p, &which)) {
-    case L0_LS_OK: break;
-    case L0_LS_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
-    case L0_LS_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
-    case L0_LS_STARTS: return fail(SLM_ERR_BAD_ARG, "n_starts must be >= 1 (got %d)", n_starts);
-    case L0_LS_PROBLEMS:
-      return fail(SLM_ERR_BAD_ARG, "n_cells * n_starts must be at most %d problems (got %d x %d)", L0_LS_MAX_PROBLEMS, n_cells, n_starts);
-    case L0_LS_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
-    case L0_LS_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", which);
-    case L0_LS_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", which);
-    case L0_LS_WIDTH:
-      return fail(SLM_ERR_UNSUPPORTED, "the l0 local search takes up to %d columns (got %lld)", L0_LS_PMAX, (long long)ds->p);
-    case L0_LS_START_BOX:
-      return fail(SLM_ERR_BAD_ARG, "starts[%lld] lies outside the box |beta_j| <= big_M = %g (or is not a number)", which, big_M);
-  }
-  if (!ds->singleton) return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for groups: every column must be its own group");
-  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for row-sharded datasets");
-  const int p = (int)ds->p, problems = n_cells * n_starts;
-  slm_engine* eng = ds->eng;
-  HIP_TRY(hipSetDevice(eng->device));
-  hipStream_t s = eng->stream;
-
-  // ---- the dataset's own Gram, filed; the kernel reads it where it lies ------------------------------------------------------------
-  SLM_TRY(slm_dataset_covariance(ds, nullptr, 0));
-  const double* wdev = ds->rw;
-  double fp[2];
-  SLM_TRY(cov_fingerprints(ds, &wdev, 1, fp));
-  const int entry = cov_find(ds, fp[0], fp[1], (double)ds->n_global);
-  if (entry < 0) return fail(SLM_ERR_HIP, "the dataset's Gram was not filed");
-
-  // ---- one block: alphas | etas | starts, then what comes back: F | the four status words | beta -------------------------------------
-  const size_t n_start_words = starts ? (size_t)problems * p : 0;
-  const size_t off_eta = (size_t)n_cells, off_st = 2 * (size_t)n_cells, off_F = off_st + n_start_words, off_stat = off_F + (size_t)problems,
-               off_beta = off_stat + 2 * (size_t)problems, words = off_beta + (size_t)problems * p;
-  std::vector<double> h(words, 0.0);
-  memcpy(h.data(), alphas, sizeof(double) * (size_t)n_cells);
-  memcpy(h.data() + off_eta, etas, sizeof(double) * (size_t)n_cells);
-  if (starts) memcpy(h.data() + off_st, starts, sizeof(double) * n_start_words);
-  {
-    unsigned long long* dev = nullptr;
-    SLM_TRY(dalloc(&dev, words));
-    L0DevGuard guard{dev, s};
-    double* dd = reinterpret_cast<double*>(dev);
-    HIP_TRY(hipMemcpyAsync(dd, h.data(), sizeof(double) * off_F, hipMemcpyHostToDevice, s));
-    L0LsArgs k;
-    memset(&k, 0, sizeof(k));
-    k.G[0] = ds->cov[(size_t)entry].G;  // (one row set: problem q is cell q / n_starts)
-    k.c[0] = ds->cov[(size_t)entry].c;
-    k.yy[0] = ds->cov[(size_t)entry].yy;
-    k.n_cells = n_cells;
-    k.ld = (long long)ds->ld;
-    k.alphas = dd;
-    k.etas = dd + off_eta;
-    k.starts = starts ? dd + off_st : nullptr;
-    k.F_out = dd + off_F;
-    k.stat_out = reinterpret_cast<int*>(dd + off_stat);
-    k.beta_out = dd + off_beta;
-    k.p = p; k.n_problems = problems; k.n_starts = n_starts; k.swaps = swaps ? 1 : 0; k.stat_stride = 4;
-    k.big_M = big_M;
-    // (a problem is one wave.  The kernel's registers leave one workgroup of L0_WAVES waves resident per CU; twice that many are
-    // launched so that a CU whose problems end early takes up another workgroup, and the problems beyond 2 cus workgroups are reached
-    // by the kernel's grid-stride loop)
-    const int blocks = std::min((problems + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
-    hipLaunchKernelGGL(l0_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
-    SLM_TRY(check_launch());
-    HIP_TRY(hipMemcpyAsync(h.data() + off_F, dd + off_F, sizeof(double) * (words - off_F), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-
-  // ---- per cell: the best start, polished on the host's copy of G; the record ------------------------------------------------------
-  std::vector<double> Gh, ch;
-  double yy = 0.0;
-  SLM_TRY(l0_fetch_gram(ds, p, entry, Gh, ch, &yy));
-  const int* stat = reinterpret_cast<const int*>(h.data() + off_stat);
-  int unconverged = 0, first = -1;
-  for (int cell = 0; cell < n_cells; ++cell) {
-    int win = 0;
-    for (int st = 1; st < n_starts; ++st)
-      if (h[off_F + (size_t)cell * n_starts + st] < h[off_F + (size_t)cell * n_starts + win]) win = st;  // (ties: the lowest index)
-    const size_t q = (size_t)cell * n_starts + win;
-    double* beta = beta_out + (size_t)cell * p;
-    memcpy(beta, h.data() + off_beta + q * p, sizeof(double) * (size_t)p);
-    const double quad = l0_ls_polish(Gh.data(), (size_t)p, ch.data(), p, etas[cell], big_M, beta);
-    int nnz = 0;
-    double bn = 0.0;
-    for (int j = 0; j < p; ++j) {
-      nnz += beta[j] != 0.0;
-      bn += beta[j] * beta[j];
-    }
-    objective_out[cell] = quad + alphas[cell] * (double)nnz;
-    if (start_out) start_out[cell] = win;
-    const bool done = stat[4 * q + 2] == 0;
-    if (!done && unconverged++ == 0) first = cell;
-    if (info) {
-      l0_report(info + cell, done, l0_gram_loss(Gh.data(), ch.data(), p, yy, beta), objective_out[cell], h[off_F + q], -HUGE_VAL);
-      info[cell].n_iter = stat[4 * q + 0];
-      info[cell].rejects = stat[4 * q + 1];
-      info[cell].resid = (double)stat[4 * q + 2];
-      info[cell].beta_norm = std::sqrt(bn);
-      info[cell].mode = 8;
-    }
-  }
-  if (unconverged)
-    return fail(SLM_ERR_NOT_CONVERGED, "the local search reached a cap (%d sweeps per descent, %d swaps) in %d of %d cells (the first: %d): "
-                "their last points are returned", L0_CD_SWEEPS, L0_LS_SWAPS, unconverged, n_cells, first);
-  return SLM_OK;
-}
-
 // Rows `rows` (ascending) of a device Gram [.][ld], their first `width` entries, to the host: out[k * width + j].  A few rows
 // go one copy each; many go as one strided copy of the stretch that holds them.
 int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const std::vector<int>& rows, std::vector<double>& out) {
@@ -991,26 +864,57 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
   return SLM_OK;
 }
 
-// slm_solve_l0_local_folds (DESIGN 4d "Local search over folds"): solve_l0_local_impl on `count` row sets of one dataset -- the
-// training rows of a cross-validation's folds, then all rows -- from ONE launch of l0_local_kernel.  check (l0_lsf_check and
-// the dataset's shape, before a device is touched); the Grams as in solve_l0_profile_grid_impl (one slm_dataset_covariance_folds
-// call when every row set brings its weights, else one by one; found again by fingerprint), each HELD for the call, so that a
-// later build cannot push it out from under the kernel; with an intercept the ones column (last, alone in its group) is
-// eliminated per row set: the vectors on the host (l0_eliminate_vectors, from the last row of each Gram), the matrices by one
-// launch of l0_eliminate_kernel into a workspace of count * ps * ld doubles -- without an intercept nothing is copied and
-// the kernel reads the store in place; ONE launch over every (row set, cell, start) problem; per (row set, cell) the best
-// start by (F, then the lowest index), polished on host copies of ONLY the rows of its Gram that the winners of that row set
-// hold (l0_fetch_rows: the polish and the loss read nothing else); the record of solve_l0_local_impl's table per (row set,
-// cell); stat_out: the four status words of EVERY problem.
+// The l0 local search (DESIGN 4d "Local search", "Local search over folds", "Local subsets"): NOT a search over supports and
+// not this unit's pipeline -- no order, no seed, no block image -- and ONE body, solve_l0_local_folds_impl, for its four entries:
+//   slm_solve_l0_local_folds    `count` row sets of one dataset -- the training rows of a cross-validation's folds, then all rows
+//   slm_solve_l0_local[_descent]  that call with ONE row set, the dataset's own rows (a NULL weight vector), no intercept and no
+//                               intercept_out / stat_out; only the wording of two messages is its own (L0_LOCAL_ONE)
+//   slm_solve_l0_local_subsets  that call with `sizes` in the place of `alphas`: the check is l0_lc_check, the launch
+//                               l0_local_kernel<true> (the cardinality rule), the sizes travel as ints where the alphas did, the
+//                               objective has no alpha term (Q after the polish), and stat_out holds six words per problem:
+//                               grows and drops behind the four
+// check (l0_lsf_check -- at one row set l0_ls_check's refusals in l0_ls_check's order -- and the dataset's shape, before a device
+// is touched); the Grams FILED, not fetched: as in solve_l0_profile_grid_impl (one slm_dataset_covariance_folds call when every
+// row set brings its weights, else one by one; found again by fingerprint), each HELD for the call, so that a later build
+// cannot push it out from under the kernel, which reads it in place with the dataset's leading dimension and puts 2 eta on the
+// diagonal itself; with an intercept the ones column (last, alone in its group) is eliminated per row set: the vectors on the
+// host (l0_eliminate_vectors, from the last row of each Gram), the matrices by one launch of l0_eliminate_kernel into a
+// workspace of count * ps * ld doubles; ONE launch of l0_local_kernel over every (row set, cell, start) problem; per (row set,
+// cell) the best start by (F, then the lowest index), polished (l0_ls_polish) on host copies of ONLY the rows of its Gram that
+// the winners of that row set hold (l0_fetch_rows: the polish and the loss read nothing else; the whole Gram, 8 MB at 1024
+// columns, never comes to the host); stat_out: the status words of EVERY problem; the record, per (row set, cell):
 //
-// slm_solve_l0_local_subsets (DESIGN 4d "Local subsets") is the same call with `sizes` in the place of `alphas`: the check is
-// l0_lc_check, the launch l0_local_kernel<true> (the cardinality rule), the sizes travel as ints where the alphas did, the
-// objective has no alpha term (Q after the polish), and stat_out holds six words per problem: grows and drops behind the four.
-int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs, int32_t intercept,
-                              int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
+//   n_iter    rejects   resid                       mu                    kkt             L       mode
+//   sweeps    swaps     the winner's status word    the objective before  the objective   -inf    8
+//   of the    accepted  (1: a descent ran out of    the polish (the       after it        (no
+//   winner    (winner)  sweeps, 2: the swap cap)    kernel's F)                           bound)
+//
+// status is SLM_OK where the winner reached its fixed point and SLM_ERR_NOT_CONVERGED where a cap ended it; beta_norm and
+// loss as for solve_l0.  Nothing here is proven optimal, whatever the status.  Non-finite data is refused where it shows:
+// X^T y before the launch, the winners' Gram rows after it.
+static_assert(SLM_L0_LOCAL_PMAX == L0_LS_PMAX && SLM_L0_LOCAL_MAX_PROBLEMS == L0_LS_MAX_PROBLEMS, "the header and the host logic name one set of limits");
+enum L0LocalKind { L0_LOCAL_ONE, L0_LOCAL_SETS, L0_LOCAL_SIZES };  // slm_solve_l0_local[_descent]; _folds; _subsets
+int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                              int32_t intercept, int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
                               int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
-                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info, bool card) {
+                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info);
+
+// slm_solve_l0_local, slm_solve_l0_local_descent: the body below on one row set, the dataset's own rows
+int solve_l0_local_impl(int32_t swaps, slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                        int32_t n_starts, const double* starts, double* beta_out, double* objective_out, int32_t* start_out,
+                        slm_point_info* info) {
+  const double* const own_rows[1] = {nullptr};
+  const int64_t n_eff[1] = {0};
+  return solve_l0_local_folds_impl(L0_LOCAL_ONE, ds, 1, own_rows, n_eff, 0, n_cells, alphas, nullptr, etas, big_M, n_starts, starts, swaps,
+                                   beta_out, nullptr, objective_out, start_out, nullptr, info);
+}
+
+int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                              int32_t intercept, int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
+                              int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
+                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
   if (!ds || !beta_out || !objective_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  const bool card = kind == L0_LOCAL_SIZES, one = kind == L0_LOCAL_ONE;
   const int drop = intercept != 0 ? 1 : 0;
   bool alone = ds->p >= 1;  // the ones column: last, alone in the last group
   if (drop && !ds->singleton) {
@@ -1041,6 +945,7 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
     case L0_LSF_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
     case L0_LSF_COUNT: return fail(SLM_ERR_BAD_ARG, "count must be 1 .. %d, the Gram store's capacity (got %d)", L0_LS_ROW_SETS, count);
     case L0_LSF_PRODUCT:
+      if (one) return fail(SLM_ERR_BAD_ARG, "n_cells * n_starts must be at most %d problems (got %d x %d)", L0_LS_MAX_PROBLEMS, n_cells, n_starts);
       return fail(SLM_ERR_BAD_ARG, "count * n_cells * n_starts must be at most %d problems (got %d x %d x %d)", L0_LS_MAX_PROBLEMS, count,
                   n_cells, n_starts);
     case L0_LSF_INTERCEPT: return fail(SLM_ERR_BAD_ARG, "intercept: the last column must be alone in the last group");
@@ -1070,18 +975,22 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
   hipStream_t s = eng->stream;
 
   // ---- the Grams: the folds' in one call when every row set brings its weights, else one by one; each held for the call ----------
-  bool all_given = true;
-  for (int b = 0; b < count; ++b) all_given = all_given && row_weights[b] != nullptr;
-  struct Weights {
+  bool all_given = true, any_given = false;
+  for (int b = 0; b < count; ++b) {
+    all_given = all_given && row_weights[b] != nullptr;
+    any_given = any_given || row_weights[b] != nullptr;
+  }
+  struct Weights {  // (the given weights on the device; nothing where no row set brings any)
     double* dev = nullptr;
     hipStream_t s;
     ~Weights() {
+      if (!dev) return;
       (void)hipStreamSynchronize(s);
       dfree(dev);
     }
   } wts;
   wts.s = s;
-  SLM_TRY(dalloc(&wts.dev, (size_t)count * (size_t)n));
+  if (any_given) SLM_TRY(dalloc(&wts.dev, (size_t)count * (size_t)n));
   std::vector<const double*> wdev((size_t)count);
   std::vector<double> neff((size_t)count);
   for (int b = 0; b < count; ++b) {
@@ -1185,12 +1094,14 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
     k.beta_out = dd + off_beta;
     k.p = ps; k.n_problems = problems; k.n_starts = n_starts; k.swaps = swaps ? 1 : 0; k.n_cells = n_cells;
     k.big_M = big_M;
-    // (the grid of solve_l0_local_impl: two workgroups per CU, the rest by the kernel's grid-stride loop)
+    // (a problem is one wave.  The kernel's registers leave one workgroup of L0_WAVES waves resident per CU; twice that many are
+    // launched so that a CU whose problems end early takes up another workgroup, and the problems beyond 2 cus workgroups are reached
+    // by the kernel's grid-stride loop)
     const int blocks = std::min((problems + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
-    if (card)
-      hipLaunchKernelGGL(l0_local_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
-    else
+    if (!card)
       hipLaunchKernelGGL(l0_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    else
+      hipLaunchKernelGGL(l0_local_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
     SLM_TRY(check_launch());
     HIP_TRY(hipMemcpyAsync(h.data() + off_F, dd + off_F, sizeof(double) * (words - off_F), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1263,6 +1174,9 @@ int solve_l0_local_folds_impl(slm_dataset* ds, int32_t count, const double* cons
       }
     }
   }
+  if (unconverged && one)
+    return fail(SLM_ERR_NOT_CONVERGED, "the local search reached a cap (%d sweeps per descent, %d swaps) in %d of %d cells (the first: %d): "
+                "their last points are returned", L0_CD_SWEEPS, L0_LS_SWAPS, unconverged, n_cells, first_cell);
   if (unconverged)
     return fail(SLM_ERR_NOT_CONVERGED, "the local search reached a cap (%d sweeps per descent, %d swaps) in %d of %d (row set, cell) pairs "
                 "(the first: row set %d, cell %d): their last points are returned", L0_CD_SWEEPS, L0_LS_SWAPS, unconverged, count * n_cells,
@@ -1277,8 +1191,8 @@ extern "C" int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const do
                                         int32_t intercept, int32_t n_cells, const double* alphas, const double* etas, double big_M,
                                         int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
                                         double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
-  return solve_l0_local_folds_impl(ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, etas, big_M, n_starts, starts, swaps,
-                                   beta_out, intercept_out, objective_out, start_out, stat_out, info, false);
+  return solve_l0_local_folds_impl(L0_LOCAL_SETS, ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, etas, big_M, n_starts,
+                                   starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info);
 }
 
 // The cardinality form of the l0 local search: every (row set, (size, eta) cell, start) problem from one launch of
@@ -1287,22 +1201,22 @@ extern "C" int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const 
                                           int32_t intercept, int32_t n_cells, const int32_t* sizes, const double* etas, double big_M,
                                           int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
                                           double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
-  return solve_l0_local_folds_impl(ds, count, row_weights, n_effs, intercept, n_cells, nullptr, sizes, etas, big_M, n_starts, starts, swaps,
-                                   beta_out, intercept_out, objective_out, start_out, stat_out, info, true);
+  return solve_l0_local_folds_impl(L0_LOCAL_SIZES, ds, count, row_weights, n_effs, intercept, n_cells, nullptr, sizes, etas, big_M, n_starts,
+                                   starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info);
 }
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.
 extern "C" int slm_solve_l0_local(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
                                   int32_t n_starts, const double* starts, double* beta_out, double* objective_out, int32_t* start_out,
                                   slm_point_info* info) {
-  return solve_l0_local_impl(true, ds, n_cells, alphas, etas, big_M, n_starts, starts, beta_out, objective_out, start_out, info);
+  return solve_l0_local_impl(1, ds, n_cells, alphas, etas, big_M, n_starts, starts, beta_out, objective_out, start_out, info);
 }
 
 // The same call without the swap scan: every problem ends at its descent's fixed point.
 extern "C" int slm_solve_l0_local_descent(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
                                           int32_t n_starts, const double* starts, double* beta_out, double* objective_out,
                                           int32_t* start_out, slm_point_info* info) {
-  return solve_l0_local_impl(false, ds, n_cells, alphas, etas, big_M, n_starts, starts, beta_out, objective_out, start_out, info);
+  return solve_l0_local_impl(0, ds, n_cells, alphas, etas, big_M, n_starts, starts, beta_out, objective_out, start_out, info);
 }
 
 extern "C" int slm_solve_l0(slm_dataset* ds, double alpha, int32_t max_groups, double eta, const double* T, double big_M,

@@ -17,8 +17,8 @@
 // elimination of an intercept column from a Gram.  The profile grid (slm_solve_l0_profile_grid; tests/l0_grid_host_test.cpp) adds
 // the problem index over (row set, eta), its argument checks and the layout at up to L0_GRID_MAX problems.  The local search
 // (slm_solve_l0_local; tests/l0_local_host_test.cpp) adds, at the very end, the two decisions host and device share, the rule
-// itself without a device (l0_ls_solve), the polish of its winner and its argument checks; it uses nothing of the exact search
-// but l0_boxed and the dense Cholesky.
+// itself without a device (l0_local_solve: ONE twin of the one kernel, both of its rules), the polish of its winner and its
+// argument checks; it uses nothing of the exact search but l0_boxed and the dense Cholesky.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 namespace slm {
@@ -1172,7 +1173,7 @@ inline double l0_gram_loss(const double* G, const double* c, int p, double yy, c
 //     F(beta) = 1/2 beta^T H beta - c^T beta + alpha ||beta||_0   over |beta_j| <= big_M,
 // cyclic coordinate descent with hard thresholding, then one-for-one swaps until none helps (DESIGN 4d "Local search").  The
 // state is beta, r = c - H beta and d_j = H_jj.  l0_ls_coord and l0_ls_swap_better are the two decisions, shared with the
-// kernel; l0_ls_solve is the whole rule without a device (the kernel's twin: the same sequence of changes, the same
+// kernel; l0_local_solve<false> is the whole rule without a device (the kernel's twin: the same sequence of changes, the same
 // arithmetic up to the order of the final sums and the contraction of a multiply-add), l0_ls_polish the exact re-solve of a
 // support inside the box that the entry runs on the winner.
 constexpr int L0_LS_PMAX = 1024;             // columns: 16 slots of 64 lanes
@@ -1202,18 +1203,23 @@ constexpr bool l0_ls_swap_better(double gj, double gi, double alpha) {
 }
 
 struct L0LsResult {
-  double F = 0.0;  // the objective at the returned beta
+  double F = 0.0;  // the objective at the returned beta (the cardinality rule: Q, which has no alpha term)
   int sweeps = 0, swaps = 0, status = 0, nnz = 0;
-  long long changes = 0;  // columns of H applied to r after the start (one per coordinate change, two per swap): what the time goes to
+  int grows = 0, drops = 0;  // the cardinality rule's: columns that entered in its grow step, that left in its shrink or descent
+  long long changes = 0;     // columns of H applied to r after the start (one per coordinate change, two per swap): what the time goes to
 };
 
-// The rule on one problem.  G: [p][ld] the Gram (symmetric; row j is read for column j), c: [p]; 2 eta goes on the diagonal
-// here.  start: [p] inside the box, or NULL for zero.  beta: [p] out.  A column whose d_j <= L0_PIVOT max d stays zero.
-inline L0LsResult l0_ls_solve(const double* G, size_t ld, const double* c, int p, double alpha, double eta, double big_M, double yy,
-                              bool swaps, const double* start, double* beta) {
+// The rule on one problem: the kernel's twin, l0_local_kernel<CARD> without a device, laid out as the kernel is.  CARD false is
+// the penalised rule of this section and `cell` the cell's alpha; CARD true the cardinality rule of "local subsets" below and
+// `cell` its size k (k >= p is legal).  G: [p][ld] the Gram (symmetric; row j is read for column j), c: [p]; 2 eta goes on the
+// diagonal here.  start: [p] inside the box, or NULL for zero.  beta: [p] out.  A column whose d_j <= L0_PIVOT max d stays zero.
+template <bool CARD>
+inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, int p, std::conditional_t<CARD, int, double> cell, double eta,
+                                 double big_M, double yy, bool swaps, const double* start, double* beta) {
   L0LsResult R;
   std::vector<double> r(c, c + p), d((size_t)p);
-  const double eta2 = 2.0 * eta;
+  const double alpha = CARD ? 0.0 : (double)cell, eta2 = 2.0 * eta;
+  const int kmax = CARD ? (int)cell : 0;
   double dmax = 0.0;
   for (int j = 0; j < p; ++j) {
     d[(size_t)j] = G[(size_t)j * ld + j] + eta2;
@@ -1226,12 +1232,39 @@ inline L0LsResult l0_ls_solve(const double* G, size_t ld, const double* c, int p
   auto axpy = [&](int j, double w) {  // r += w H[:, j]
     const double* row = G + (size_t)j * ld;
     for (int k = 0; k < p; ++k) r[(size_t)k] += w * (k == j ? row[k] + eta2 : row[k]);
+    ++R.changes;
   };
+  int nact = 0;  // (the cardinality rule's: the support's size)
   for (int j = 0; j < p; ++j)
-    if (beta[j] != 0.0) axpy(j, -beta[j]);
+    if (beta[j] != 0.0) {
+      axpy(j, -beta[j]);
+      ++nact;
+    }
+  R.changes = 0;  // (the start is not counted)
   const double tol = L0_CD_TOL * std::sqrt(yy);
+  if (CARD) {
+    // ---- shrink: while the support is larger than k its weakest column leaves (only a start can be: nothing below adds beyond k)
+    while (nact > kmax) {
+      double gb = HUGE_VAL;
+      int ib = -1;
+      for (int i = 0; i < p; ++i) {
+        if (beta[i] == 0.0) continue;
+        const double g = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * beta[i], d[(size_t)i], big_M).gain;
+        if (g < gb) {  // (ties: the lowest i)
+          gb = g;
+          ib = i;
+        }
+      }
+      if (ib < 0) break;
+      const double bi = beta[ib];
+      beta[ib] = 0.0;
+      axpy(ib, bi);
+      --nact;
+      ++R.drops;
+    }
+  }
   for (;;) {
-    // ---- 1. the descent to its fixed point --------------------------------------------------------------------------------
+    // ---- 1. the descent to its fixed point (the cardinality rule: on the support alone, no threshold, b == 0 leaves) ---------
     for (int sw = 0;; ++sw) {
       if (sw == L0_CD_SWEEPS) {
         R.status |= L0_LS_SWEEPS_OUT;
@@ -1241,21 +1274,50 @@ inline L0LsResult l0_ls_solve(const double* G, size_t ld, const double* c, int p
       double maxd = 0.0;
       for (int j = 0; j < p; ++j) {
         const double dj = d[(size_t)j];
-        if (!(dj > 0.0)) continue;
-        const double nb = l0_ls_threshold(l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M), alpha);
+        if (CARD ? beta[j] == 0.0 : !(dj > 0.0)) continue;
+        const L0LsCoord co = l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M);
+        const double nb = CARD ? co.b : l0_ls_threshold(co, alpha);
         if (nb == beta[j]) continue;
         const double delta = nb - beta[j];
-        moved = moved || ((nb != 0.0) != (beta[j] != 0.0));
+        moved = moved || ((nb != 0.0) != (beta[j] != 0.0));  // (on the support alone: only a column that leaves)
+        if (CARD && nb == 0.0) {
+          --nact;
+          ++R.drops;
+        }
         maxd = std::max(maxd, std::fabs(delta) * std::sqrt(dj));
         beta[j] = nb;
         axpy(j, -delta);
-        ++R.changes;
       }
       ++R.sweeps;
       if (!moved && maxd <= tol) break;
     }
+    if (CARD) {
+      // ---- grow: below k, the outside column with the largest gain enters -- if it would move by more than the descent's own
+      // stopping tolerance -- and the descent runs again
+      if (R.status) break;
+      if (nact < kmax) {
+        double gb = -1.0, bb = 0.0;
+        int jb = -1;
+        for (int j = 0; j < p; ++j) {
+          if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
+          const L0LsCoord co = l0_ls_coord(r[(size_t)j], d[(size_t)j], big_M);
+          if (co.gain > gb) {  // (ties: the lowest j)
+            gb = co.gain;
+            bb = co.b;
+            jb = j;
+          }
+        }
+        if (jb >= 0 && std::fabs(bb) * std::sqrt(d[(size_t)jb]) > tol) {
+          beta[jb] = bb;
+          axpy(jb, -bb);
+          ++nact;
+          ++R.grows;
+          continue;
+        }
+      }
+    }
     if (!swaps || R.status) break;
-    // ---- 2. the swap scan: the first i of the support that a column outside replaces with a gain ----------------------------
+    // ---- 2. the swap scan: the first i of the support that a column outside replaces with a gain (the cardinality rule: alpha = 0)
     bool swapped = false;
     for (int i = 0; i < p && !swapped; ++i) {
       const double bi = beta[i];
@@ -1279,7 +1341,6 @@ inline L0LsResult l0_ls_solve(const double* G, size_t ld, const double* c, int p
       beta[jb] = bb;
       axpy(jb, -bb);
       ++R.swaps;
-      R.changes += 2;
       swapped = true;
     }
     if (!swapped) break;
@@ -1288,13 +1349,13 @@ inline L0LsResult l0_ls_solve(const double* G, size_t ld, const double* c, int p
       break;
     }
   }
-  // F = 1/2 beta^T H beta - c^T beta + alpha nnz with H beta = c - r
+  // F = 1/2 beta^T H beta - c^T beta + alpha nnz with H beta = c - r (the cardinality rule: no alpha term is added)
   double acc = 0.0;
   for (int j = 0; j < p; ++j) {
     acc += beta[j] * (c[j] + r[(size_t)j]);
     R.nnz += beta[j] != 0.0;
   }
-  R.F = -0.5 * acc + alpha * (double)R.nnz;
+  R.F = CARD ? -0.5 * acc : -0.5 * acc + alpha * (double)R.nnz;
   return R;
 }
 
@@ -1437,151 +1498,9 @@ inline L0LsfRefusal l0_lsf_check(long long count, const double* const* row_weigh
 //   3. Grow: if nnz < k the outside column with the largest l0_ls_coord(r_j, d_j).gain (ties: the lowest j) enters at b_j when
 //      |b_j| sqrt(d_j) > tol; then 2.
 //   4. Swap scan, once 3 adds nothing: the local search's with alpha = 0; a swap goes to 2, none ends the problem.
-// `drops` counts the columns that left in 1 or 2, `grows` those that entered in 3.
-struct L0LcResult {
-  double Q = 0.0;  // the objective at the returned beta
-  int sweeps = 0, swaps = 0, status = 0, nnz = 0, grows = 0, drops = 0;
-  long long changes = 0;  // columns of H applied to r after the start
-};
-
-// The rule on one problem: the arguments of l0_ls_solve with the size k in alpha's place.  k >= p is legal.
-inline L0LcResult l0_lc_solve(const double* G, size_t ld, const double* c, int p, int k, double eta, double big_M, double yy, bool swaps,
-                              const double* start, double* beta) {
-  L0LcResult R;
-  std::vector<double> r(c, c + p), d((size_t)p);
-  const double eta2 = 2.0 * eta;
-  double dmax = 0.0;
-  for (int j = 0; j < p; ++j) {
-    d[(size_t)j] = G[(size_t)j * ld + j] + eta2;
-    dmax = std::max(dmax, d[(size_t)j]);
-  }
-  for (int j = 0; j < p; ++j) {
-    if (!(d[(size_t)j] > L0_PIVOT * dmax)) d[(size_t)j] = 0.0;  // (0 marks a column that stays out)
-    beta[j] = start && d[(size_t)j] > 0.0 ? start[j] : 0.0;
-  }
-  auto axpy = [&](int j, double w) {  // r += w H[:, j]
-    const double* row = G + (size_t)j * ld;
-    for (int i = 0; i < p; ++i) r[(size_t)i] += w * (i == j ? row[i] + eta2 : row[i]);
-    ++R.changes;
-  };
-  int nnz = 0;
-  for (int j = 0; j < p; ++j)
-    if (beta[j] != 0.0) {
-      axpy(j, -beta[j]);
-      ++nnz;
-    }
-  R.changes = 0;
-  const double tol = L0_CD_TOL * std::sqrt(yy);
-  for (;;) {
-    // ---- 1. shrink: the weakest column of the support leaves ---------------------------------------------------------------------
-    while (nnz > k) {
-      double gb = HUGE_VAL;
-      int ib = -1;
-      for (int i = 0; i < p; ++i) {
-        if (beta[i] == 0.0) continue;
-        const double g = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * beta[i], d[(size_t)i], big_M).gain;
-        if (g < gb) {  // (ties: the lowest i)
-          gb = g;
-          ib = i;
-        }
-      }
-      if (ib < 0) break;
-      const double bi = beta[ib];
-      beta[ib] = 0.0;
-      axpy(ib, bi);
-      --nnz;
-      ++R.drops;
-    }
-    // ---- 2. the descent on the support --------------------------------------------------------------------------------------------
-    for (int sw = 0;; ++sw) {
-      if (sw == L0_CD_SWEEPS) {
-        R.status |= L0_LS_SWEEPS_OUT;
-        break;
-      }
-      bool moved = false;
-      double maxd = 0.0;
-      for (int j = 0; j < p; ++j) {
-        if (beta[j] == 0.0) continue;
-        const double dj = d[(size_t)j];
-        const double nb = l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M).b;
-        if (nb == beta[j]) continue;
-        const double delta = nb - beta[j];
-        if (nb == 0.0) {
-          moved = true;
-          --nnz;
-          ++R.drops;
-        }
-        maxd = std::max(maxd, std::fabs(delta) * std::sqrt(dj));
-        beta[j] = nb;
-        axpy(j, -delta);
-      }
-      ++R.sweeps;
-      if (!moved && maxd <= tol) break;
-    }
-    if (R.status) break;
-    // ---- 3. grow: the best column outside enters, if it moves at all --------------------------------------------------------------
-    if (nnz < k) {
-      double gb = -1.0, bb = 0.0;
-      int jb = -1;
-      for (int j = 0; j < p; ++j) {
-        if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
-        const L0LsCoord co = l0_ls_coord(r[(size_t)j], d[(size_t)j], big_M);
-        if (co.gain > gb) {  // (ties: the lowest j)
-          gb = co.gain;
-          bb = co.b;
-          jb = j;
-        }
-      }
-      if (jb >= 0 && std::fabs(bb) * std::sqrt(d[(size_t)jb]) > tol) {
-        beta[jb] = bb;
-        axpy(jb, -bb);
-        ++nnz;
-        ++R.grows;
-        continue;
-      }
-    }
-    if (!swaps) break;
-    // ---- 4. the swap scan of l0_ls_solve with alpha = 0 ----------------------------------------------------------------------------
-    bool swapped = false;
-    for (int i = 0; i < p && !swapped; ++i) {
-      const double bi = beta[i];
-      if (bi == 0.0) continue;
-      const double* row = G + (size_t)i * ld;
-      const double gi = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * bi, d[(size_t)i], big_M).gain;
-      double gb = -1.0, bb = 0.0;
-      int jb = -1;
-      for (int j = 0; j < p; ++j) {
-        if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
-        const L0LsCoord co = l0_ls_coord(r[(size_t)j] + row[j] * bi, d[(size_t)j], big_M);
-        if (co.gain > gb) {  // (ties: the lowest j)
-          gb = co.gain;
-          bb = co.b;
-          jb = j;
-        }
-      }
-      if (jb < 0 || !l0_ls_swap_better(gb, gi, 0.0)) continue;
-      beta[i] = 0.0;
-      axpy(i, bi);
-      beta[jb] = bb;
-      axpy(jb, -bb);
-      ++R.swaps;
-      swapped = true;
-    }
-    if (!swapped) break;
-    if (R.swaps == L0_LS_SWAPS) {
-      R.status |= L0_LS_SWAPS_OUT;
-      break;
-    }
-  }
-  // Q = 1/2 beta^T H beta - c^T beta with H beta = c - r
-  double acc = 0.0;
-  for (int j = 0; j < p; ++j) {
-    acc += beta[j] * (c[j] + r[(size_t)j]);
-    R.nnz += beta[j] != 0.0;
-  }
-  R.Q = -0.5 * acc;
-  return R;
-}
+// `drops` counts the columns that left in 1 or 2, `grows` those that entered in 3.  The rule without a device is
+// l0_local_solve<true>, above: the penalised twin's body, with 1 before its loop and 3 between its descent and its swap scan,
+// where the kernel has them.
 
 // What slm_solve_l0_local_subsets refuses before a device is touched, in this order: a NULL sizes or etas; the first size < 1;
 // the first eta that is negative or not finite; then everything l0_lsf_check refuses that is not about a cell's values (`lsf`:

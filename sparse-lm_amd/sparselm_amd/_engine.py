@@ -1644,36 +1644,17 @@ class Dataset:
         cell with ``objective``, ``descent_objective`` (before the host re-solved the winner's support exactly), ``loss``,
         ``sweeps``, ``swaps``, ``converged``, ``status`` (``"fixed_point"``, ``"sweep_cap"``, ``"swap_cap"``) and
         ``proven_optimal`` (False).  ``n_cells`` / ``n_starts``: the counts handed to the engine (None: the arrays')."""
-        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
-        et = np.ascontiguousarray(np.broadcast_to(np.asarray(etas, dtype=np.float64), al.shape), dtype=np.float64).reshape(-1)
-        cells = len(al) if n_cells is None else int(n_cells)
-        if len(al) < cells or len(et) < cells:
-            raise ValueError("alphas and etas must have n_cells entries")
-        st = None
-        ns = 1 if n_starts is None else int(n_starts)
-        if starts is not None:
-            st = np.ascontiguousarray(starts, dtype=np.float64)
-            if n_starts is None:
-                if st.ndim != 3 or st.shape[0] != cells or st.shape[2] != self.p:
-                    raise ValueError(f"starts must have the shape (cells, n_starts, {self.p})")
-                ns = st.shape[1]
-            st = st.reshape(-1)
+        al, et, cells = _l0_local_cells(alphas, etas, n_cells)
+        st, ns = _l0_local_starts(starts, n_starts, (cells,), self.p, f"cells, n_starts, {self.p}")
         sized = cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS  # (else the engine refuses: the outputs only have to exist)
         if st is not None and sized and st.size != cells * ns * self.p:
             raise ValueError(f"starts has {st.size} entries, expected {cells * ns * self.p}")
         cnt = cells if sized else 1
-        pad = np.zeros(1)  # (an empty array has no address worth handing over)
-        args = (cells, al if len(al) else pad, et if len(et) else pad, float(big_M), ns, st if sized else None)
+        args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), ns, st if sized else None)
         (betas, objectives, winners), infos, rc = self._l0_call(
             "solve_l0_local" if swaps else "solve_l0_local_descent", binding, args,
             [np.zeros((cnt, self.p)), np.zeros(cnt), np.zeros(cnt, dtype=np.int32)], records=cnt)
-        names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
-        out = [{
-            "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
-            "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
-            "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
-        } for e in range(cnt)]
-        return betas, objectives, winners, out
+        return betas, objectives, winners, _l0_local_infos(infos, cnt)
 
     def solve_l0_local_folds(self, row_weights, n_effs, alphas, etas=0.0, intercept=False, big_M=100.0, starts=None, swaps=True,
                              n_cells=None, n_starts=None, binding=None):
@@ -1687,51 +1668,9 @@ class Dataset:
         ``stats`` holds sweeps, accepted swaps, status word and non-zeros of EVERY problem; ``infos`` is one list per row set of
         the dicts ``solve_l0_local`` gives per cell.  With one row set of None and no intercept the result equals
         ``solve_l0_local``'s byte for byte."""
-        ps = self.p - (1 if intercept else 0)
-        rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
-        nes = [int(v) for v in n_effs]
-        if len(nes) != len(rws):
-            raise ValueError("row_weights and n_effs differ in length")
-        count = len(rws)
-        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
-        et = np.ascontiguousarray(np.broadcast_to(np.asarray(etas, dtype=np.float64), al.shape), dtype=np.float64).reshape(-1)
-        cells = len(al) if n_cells is None else int(n_cells)
-        if len(al) < cells or len(et) < cells:
-            raise ValueError("alphas and etas must have n_cells entries")
-        st = None
-        ns = 1 if n_starts is None else int(n_starts)
-        if starts is not None:
-            st = np.ascontiguousarray(starts, dtype=np.float64)
-            if n_starts is None:
-                if st.ndim != 4 or st.shape[:2] != (count, cells) or st.shape[3] != ps:
-                    raise ValueError(f"starts must have the shape ({count}, {cells}, n_starts, {ps})")
-                ns = st.shape[2]
-            st = st.reshape(-1)
-        # (else the engine refuses: the outputs only have to exist)
-        sized = 1 <= count <= 16 and cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS and count * cells * ns <= L0_LOCAL_MAX_PROBLEMS
-        if st is not None and sized and st.size != count * cells * ns * ps:
-            raise ValueError(f"starts has {st.size} entries, expected {count * cells * ns * ps}")
-        cnt = count * cells if sized else 1
-        problems = cnt * ns if sized else 1
-        pad = np.zeros(1)  # (an empty array has no address worth handing over)
-        ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
-        ne = np.array(nes or [0], dtype=np.int64)
-        tail = (int(bool(intercept)), cells, al if len(al) else pad, et if len(et) else pad, float(big_M), ns, st if sized else None,
-                int(bool(swaps)))
-        (betas, icpts, objectives, winners, stats), infos, rc = self._l0_call(
-            "solve_l0_local_folds", binding, (count, ptrs, ne) + tail,
-            [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros((problems, 4), dtype=np.int32)],
-            records=cnt, binding_args=(self.n, rws, nes, bool(intercept)) + tail[1:-1] + (bool(swaps),))
-        names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
-        out = [{
-            "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
-            "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
-            "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
-        } for e in range(cnt)]
-        if not sized:
-            return betas, icpts, objectives, winners, stats, [out]
-        return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
-                stats.reshape(count, cells, ns, 4), [out[r * cells:(r + 1) * cells] for r in range(count)])
+        rws, nes = self._l0_local_row_sets(row_weights, n_effs)
+        al, et, cells = _l0_local_cells(alphas, etas, n_cells)
+        return self._l0_local_rows("solve_l0_local_folds", 4, rws, nes, al, et, cells, intercept, big_M, starts, swaps, n_starts, binding)
 
     def solve_l0_local_subsets(self, row_weights, n_effs, sizes, etas=0.0, intercept=False, big_M=100.0, starts=None, swaps=True,
                                n_cells=None, n_starts=None, binding=None):
@@ -1744,12 +1683,7 @@ class Dataset:
         ps], intercepts, objectives [count, cells] (Q after the polish), winning starts, stats [count, cells, n_starts, 6],
         infos)``: ``stats`` holds sweeps, accepted swaps, status word, non-zeros, grows and drops of EVERY problem; ``infos``
         the dicts of ``solve_l0_local`` with ``grows`` and ``drops`` of the winner beside them.  Nothing is proven."""
-        ps = self.p - (1 if intercept else 0)
-        rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
-        nes = [int(v) for v in n_effs]
-        if len(nes) != len(rws):
-            raise ValueError("row_weights and n_effs differ in length")
-        count = len(rws)
+        rws, nes = self._l0_local_row_sets(row_weights, n_effs)
         sz = None
         if sizes is not None:  # (None reaches the engine as NULL, by the ctypes route: its first refusal)
             raw = np.asarray(sizes).reshape(-1)
@@ -1764,49 +1698,82 @@ class Dataset:
         cells = (min(given) if given else 1) if n_cells is None else int(n_cells)
         if any(g < cells for g in given):
             raise ValueError("sizes and etas must have n_cells entries")
-        st = None
-        ns = 1 if n_starts is None else int(n_starts)
-        if starts is not None:
-            st = np.ascontiguousarray(starts, dtype=np.float64)
-            if n_starts is None:
-                if st.ndim != 4 or st.shape[:2] != (count, cells) or st.shape[3] != ps:
-                    raise ValueError(f"starts must have the shape ({count}, {cells}, n_starts, {ps})")
-                ns = st.shape[2]
-            st = st.reshape(-1)
+        return self._l0_local_rows("solve_l0_local_subsets", 6, rws, nes, sz, et, cells, intercept, big_M, starts, swaps, n_starts, binding)
+
+    def _l0_local_row_sets(self, row_weights, n_effs):
+        """The row sets of a local-search call: ``(the weight arrays or None, the divisors)``, one per set."""
+        rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
+        nes = [int(v) for v in n_effs]
+        if len(nes) != len(rws):
+            raise ValueError("row_weights and n_effs differ in length")
+        return rws, nes
+
+    def _l0_local_rows(self, name, nstat, rws, nes, first, et, cells, intercept, big_M, starts, swaps, n_starts, binding):
+        """Both entries over row sets.  ``first``: the cells' alphas (``nstat`` 4 status words per problem) or their sizes (6:
+        grows and drops behind the four), coerced by the caller; a None there or in ``et`` reaches the engine as NULL."""
+        ps, count = self.p - (1 if intercept else 0), len(rws)
+        st, ns = _l0_local_starts(starts, n_starts, (count, cells), ps, f"{count}, {cells}, n_starts, {ps}")
         # (else the engine refuses: the outputs only have to exist)
         sized = 1 <= count <= 16 and cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS and count * cells * ns <= L0_LOCAL_MAX_PROBLEMS
         if st is not None and sized and st.size != count * cells * ns * ps:
             raise ValueError(f"starts has {st.size} entries, expected {count * cells * ns * ps}")
         cnt = count * cells if sized else 1
         problems = cnt * ns if sized else 1
-        pad = np.zeros(1)  # (an empty array has no address worth handing over)
         ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
         ne = np.array(nes or [0], dtype=np.int64)
-        if sz is not None and not len(sz):
-            sz = np.zeros(1, dtype=np.int32)
-        if et is not None and not len(et):
-            et = pad
-        tail = (int(bool(intercept)), cells, sz, et, float(big_M), ns, st if sized else None, int(bool(swaps)))
-        if sz is None or et is None:
+        tail = (int(bool(intercept)), cells, _l0_local_pad(first), _l0_local_pad(et), float(big_M), ns, st if sized else None, int(bool(swaps)))
+        if first is None or et is None:
             binding = False  # (the compiled route takes arrays: a NULL goes by ctypes)
         (betas, icpts, objectives, winners, stats), infos, rc = self._l0_call(
-            "solve_l0_local_subsets", binding, (count, ptrs, ne) + tail,
-            [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros((problems, 6), dtype=np.int32)],
+            name, binding, (count, ptrs, ne) + tail,
+            [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros((problems, nstat), dtype=np.int32)],
             records=cnt, binding_args=(self.n, rws, nes, bool(intercept)) + tail[1:-1] + (bool(swaps),))
-        names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
-        out = [{
-            "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
-            "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
-            "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
-        } for e in range(cnt)]
+        out = _l0_local_infos(infos, cnt)
         if not sized:
             return betas, icpts, objectives, winners, stats, [out]
-        stats = stats.reshape(count, cells, ns, 6)
-        for e in range(cnt):
+        stats = stats.reshape(count, cells, ns, nstat)
+        for e in range(cnt if nstat == 6 else 0):
             won = stats[e // cells, e % cells, int(winners[e])]
             out[e]["grows"], out[e]["drops"] = int(won[4]), int(won[5])
         return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
                 stats, [out[r * cells:(r + 1) * cells] for r in range(count)])
+
+
+def _l0_local_cells(alphas, etas, n_cells):
+    """The cells of the penalised local search as the engine takes them: ``(alphas, etas, the count handed over)``."""
+    al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+    et = np.ascontiguousarray(np.broadcast_to(np.asarray(etas, dtype=np.float64), al.shape), dtype=np.float64).reshape(-1)
+    cells = len(al) if n_cells is None else int(n_cells)
+    if len(al) < cells or len(et) < cells:
+        raise ValueError("alphas and etas must have n_cells entries")
+    return al, et, cells
+
+
+def _l0_local_starts(starts, n_starts, lead, width, shape_text):
+    """``(starts flat or None, the start count)``.  Without ``n_starts`` the array must be ``lead + (n_starts, width)``."""
+    if starts is None:
+        return None, 1 if n_starts is None else int(n_starts)
+    st = np.ascontiguousarray(starts, dtype=np.float64)
+    if n_starts is not None:
+        return st.reshape(-1), int(n_starts)
+    if st.ndim != len(lead) + 2 or st.shape[:-2] != tuple(lead) or st.shape[-1] != width:
+        raise ValueError(f"starts must have the shape ({shape_text})")
+    return st.reshape(-1), st.shape[-2]
+
+
+def _l0_local_pad(v):
+    """An empty array has no address worth handing over: one zero of its type instead.  (None stays None: a NULL.)"""
+    return v if v is None or len(v) else np.zeros(1, dtype=v.dtype)
+
+
+def _l0_local_infos(infos, cnt):
+    """The dict per (row set,) cell of the local-search wrappers, from the engine's records."""
+    names = {0: "fixed_point", 1: "sweep_cap", 2: "swap_cap", 3: "sweep_cap"}
+    return [{
+        "objective": float(infos[e]["kkt"]), "descent_objective": float(infos[e]["mu"]), "loss": float(infos[e]["loss"]),
+        "sweeps": int(infos[e]["n_iter"]), "swaps": int(infos[e]["rejects"]), "converged": int(infos[e]["status"]) == SLM_OK,
+        "status": names.get(int(infos[e]["resid"]), "sweep_cap"), "proven_optimal": False, "launches": 1,
+    } for e in range(cnt)]
 
 
 class _HostPool:

@@ -41,6 +41,7 @@ _PMAX = 1024  # SLM_L0_LOCAL_PMAX
 _MAX_PROBLEMS = 8192  # SLM_L0_LOCAL_MAX_PROBLEMS: (cell, start) problems of one launch
 _OPTIONS = {"device", "swaps"}
 _IMPROVE = 1e-12  # a round's result replaces a cell's only when it is lower by more than this, relative to max(|objective|, alpha)
+_MOVES = ((-1, 0), (1, 0), (0, -1), (0, 1))  # a cell's neighbours: along the grid's first axis (alpha, or the size), in eta
 
 
 class _LocalProblem(_ExactL0):
@@ -99,6 +100,50 @@ def _grid(values, name):
     return arr
 
 
+def _options(solver_options, max_rounds, what="the l0 local search"):
+    """``(swaps, the device options or None)`` of a call, validated.  ``what``: the caller, as its messages name it."""
+    options = {} if solver_options is None else solver_options
+    if not isinstance(options, dict):
+        raise ValueError("solver_options must be a dict or None")
+    unknown = set(options) - _OPTIONS
+    if unknown:
+        raise ValueError(f"unknown solver_options {sorted(unknown)}: {what} takes {sorted(_OPTIONS)}")
+    swaps = options.get("swaps", True)
+    if not isinstance(swaps, (bool, np.bool_)):
+        raise ValueError("solver_options['swaps'] must be a bool")
+    if not isinstance(max_rounds, Integral) or isinstance(max_rounds, bool) or max_rounds < 0:
+        raise ValueError("max_rounds must be an integer >= 0")
+    return bool(swaps), {k: v for k, v in options.items() if k == "device"} or None
+
+
+def _first_starts(starts, A, E, p, big_M):
+    """Round 0's starts, [A, E, S, p]: the zero start, then the caller's -- ``(S, p)`` for every cell or ``(A, E, S, p)``."""
+    first = np.zeros((A, E, 1, p))
+    if starts is None:
+        return first
+    st = np.asarray(starts, dtype=float)
+    if st.ndim == 2 and st.shape[1] == p:
+        st = np.broadcast_to(st, (A, E) + st.shape)
+    if st.ndim != 4 or st.shape[:2] != (A, E) or st.shape[3] != p:
+        raise ValueError(f"starts must have the shape (S, {p}) or ({A}, {E}, S, {p})")
+    if not np.all(np.abs(st) <= big_M):  # (a NaN fails too)
+        raise ValueError(f"starts must lie inside the box |beta_j| <= big_M = {big_M:g}")
+    return np.concatenate([first, st], axis=2)
+
+
+def _round_moves(A, E, max_rounds):
+    """The neighbours a round starts every cell from: none without rounds, or along an axis of length one."""
+    return [(da, de) for da, de in _MOVES if (A > 1 and da) or (E > 1 and de)] if max_rounds else []
+
+
+def _neighbour_starts(coefs, moves):
+    """``coefs``: [..., A, E, p].  Every cell's starts of a round: its neighbours' winners, [..., A, E, len(moves), p]; beyond the
+    grid's edge the cell's own winner stands in."""
+    A, E = coefs.shape[-3], coefs.shape[-2]
+    return np.stack([np.take(np.take(coefs, np.clip(np.arange(A) + da, 0, A - 1), axis=-3), np.clip(np.arange(E) + de, 0, E - 1), axis=-2)
+                     for da, de in moves], axis=-2)
+
+
 def l0_local_search(X, y, *, alphas, etas=(0.0,), big_M=100, fit_intercept=False, sample_weight=None, starts=None, max_rounds=2,
                     solver_options=None) -> L0LocalPath:
     """A local minimum of the regularised l0 problem at every cell of ``alphas x etas``, for up to 1024 columns, on the GPU.
@@ -109,18 +154,8 @@ def l0_local_search(X, y, *, alphas, etas=(0.0,), big_M=100, fit_intercept=False
     from its grid neighbours' winners.  ``solver_options``: ``device``, ``swaps`` (default True; False stops every problem at
     its descent's fixed point).  A ``ConvergenceWarning`` is raised when a cell's result ran into a sweep or swap cap.  Nothing
     is proven optimal."""
-    options = {} if solver_options is None else solver_options
-    if not isinstance(options, dict):
-        raise ValueError("solver_options must be a dict or None")
-    unknown = set(options) - _OPTIONS
-    if unknown:
-        raise ValueError(f"unknown solver_options {sorted(unknown)}: the l0 local search takes {sorted(_OPTIONS)}")
-    swaps = options.get("swaps", True)
-    if not isinstance(swaps, (bool, np.bool_)):
-        raise ValueError("solver_options['swaps'] must be a bool")
-    if not isinstance(max_rounds, Integral) or isinstance(max_rounds, bool) or max_rounds < 0:
-        raise ValueError("max_rounds must be an integer >= 0")
-    spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options={k: v for k, v in options.items() if k == "device"} or None)
+    swaps, device = _options(solver_options, max_rounds)
+    spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options=device)
     # everything is validated before a device is touched
     X, y, dev_options, gidx, n_groups, need, _, w = spec._l0_setup(X, y, sample_weight)
     al, et = _grid(alphas, "alphas"), _grid(etas, "etas")
@@ -128,17 +163,8 @@ def l0_local_search(X, y, *, alphas, etas=(0.0,), big_M=100, fit_intercept=False
     if p > _PMAX:
         raise NotImplementedError(f"the l0 local search takes up to {_PMAX} columns (got {p})")
     big_M = float(big_M)
-    first = np.zeros((A, E, 1, p))
-    if starts is not None:
-        st = np.asarray(starts, dtype=float)
-        if st.ndim == 2 and st.shape[1] == p:
-            st = np.broadcast_to(st, (A, E) + st.shape)
-        if st.ndim != 4 or st.shape[:2] != (A, E) or st.shape[3] != p:
-            raise ValueError(f"starts must have the shape (S, {p}) or ({A}, {E}, S, {p})")
-        if not np.all(np.abs(st) <= big_M):  # (a NaN fails too)
-            raise ValueError(f"starts must lie inside the box |beta_j| <= big_M = {big_M:g}")
-        first = np.concatenate([first, st], axis=2)
-    most = max(first.shape[2], (2 * (A > 1) + 2 * (E > 1)) if max_rounds else 0)  # (a round starts a cell from its neighbours in the grid)
+    first, moves = _first_starts(starts, A, E, p, big_M), _round_moves(A, E, max_rounds)
+    most = max(first.shape[2], len(moves))  # (a round starts a cell from its neighbours in the grid)
     if A * E * most > _MAX_PROBLEMS:
         raise ValueError(f"the grid holds {A * E} cells with up to {most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
     cell_alpha, cell_eta = np.repeat(al, E), np.tile(et, A)
@@ -146,18 +172,15 @@ def l0_local_search(X, y, *, alphas, etas=(0.0,), big_M=100, fit_intercept=False
     with spec._l0_dataset(X, y, w, gidx, n_groups, need, dev_options) as (ds, x_mean, y_mean, _, _):
 
         def launch(points):
-            return ds.solve_l0_local(cell_alpha, cell_eta, big_M=big_M, starts=points.reshape(A * E, -1, p), swaps=bool(swaps))
+            return ds.solve_l0_local(cell_alpha, cell_eta, big_M=big_M, starts=points.reshape(A * E, -1, p), swaps=swaps)
 
         coefs, objectives, _, infos = launch(first)
         coefs = np.array(coefs).reshape(A, E, p)
         objectives = np.array(objectives).reshape(A, E)
         infos = np.array(infos, dtype=object).reshape(A, E)
         history = [objectives.copy()]
-        moves = [(da, de) for da, de in ((-1, 0), (1, 0), (0, -1), (0, 1)) if (A > 1 and da) or (E > 1 and de)]
         for _ in range(int(max_rounds) if moves else 0):
-            # every cell from its neighbours' winners; beyond the grid's edge the cell's own winner stands in
-            points = np.stack([coefs[np.clip(np.arange(A) + da, 0, A - 1)][:, np.clip(np.arange(E) + de, 0, E - 1)] for da, de in moves], axis=2)
-            c2, o2, _, i2 = launch(points)
+            c2, o2, _, i2 = launch(_neighbour_starts(coefs, moves))
             c2, o2 = np.array(c2).reshape(A, E, p), np.array(o2).reshape(A, E)
             better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[:, None])
             coefs[better], objectives[better] = c2[better], o2[better]

@@ -25,14 +25,13 @@ Import path: ``sparselm_amd.miqp`` (``l0_local_cv``, ``L0LocalCV``).
 from __future__ import annotations
 
 import warnings
-from numbers import Integral
 
 import numpy as np
 from sklearn.exceptions import ConvergenceWarning
 from sklearn.model_selection import check_cv
 
 from ._l0_cv import _SCORINGS, _SELECTIONS, MAX_SPLITS, _score
-from ._l0_local import _IMPROVE, _MAX_PROBLEMS, _OPTIONS, _PMAX, L0LocalPath, _grid, _LocalProblem
+from ._l0_local import _IMPROVE, _MAX_PROBLEMS, _PMAX, L0LocalPath, _first_starts, _grid, _LocalProblem, _neighbour_starts, _options, _round_moves
 
 __all__ = ["l0_local_cv", "L0LocalCV"]
 
@@ -133,6 +132,56 @@ def _held_out_scores(scoring, X, y, splits, paths):
     return scores
 
 
+def _cv_rounds(X, y, splits, w, fit_intercept, device, solve, first, moves, max_rounds, improved):
+    """The launches of a cross-validation, for both forms of the local search: ONE dataset (of ``[X | 1]`` with an intercept),
+    round 0 from ``first`` [A, E, S, p] on every row set -- the folds' training rows, then all rows -- and up to ``max_rounds``
+    rounds that start every cell from its neighbours' winners IN ITS OWN ROW SET and keep a result where ``improved(new, old)``.
+    ``solve(ds, row_weights, n_effs, starts [R, A * E, S, p])`` is the dataset's call.  Returns ``(coefs [R, A, E, p], intercepts,
+    objectives, infos [R, A, E], history [rounds, R, A, E], the launch counts of solver_info)``."""
+    from .. import _engine
+
+    n, R = len(X), len(splits) + 1
+    A, E, _, p = first.shape
+    row_weights, n_effs = _row_sets(splits, n, w)  # the folds' training rows, then all rows
+    eng = _engine.get_engine(device)
+    Xd = np.hstack([X, np.ones((n, 1))]) if fit_intercept else X
+    counts = {"launches": 0, "rounds": 0, "problems": 0, "max_sweeps": 0, "max_swaps": 0}
+    with eng.dataset(Xd, y) as ds:
+
+        def launch(points):  # points: R x A x E x S x p
+            b, i, o, _, stats, info = solve(ds, row_weights, n_effs, points.reshape(R, A * E, -1, p))
+            counts["launches"] += 1
+            counts["problems"] = max(counts["problems"], stats.shape[0] * stats.shape[1] * stats.shape[2])
+            counts["max_sweeps"] = max(counts["max_sweeps"], int(stats[..., 0].max()))
+            counts["max_swaps"] = max(counts["max_swaps"], int(stats[..., 1].max()))
+            return (np.array(b).reshape(R, A, E, p), np.array(i).reshape(R, A, E), np.array(o).reshape(R, A, E),
+                    np.array(info, dtype=object).reshape(R, A, E))
+
+        coefs, icpts, objectives, infos = launch(np.broadcast_to(first, (R,) + first.shape))
+        history = [objectives.copy()]
+        for _ in range(int(max_rounds) if moves else 0):
+            c2, i2, o2, f2 = launch(_neighbour_starts(coefs, moves))
+            better = improved(o2, objectives)
+            coefs[better], icpts[better], objectives[better], infos[better] = c2[better], i2[better], o2[better], f2[better]
+            history.append(objectives.copy())
+            if not better.any():
+                break
+    counts["rounds"] = len(history)
+    return coefs, icpts, objectives, infos, np.array(history), counts
+
+
+def _warn_capped(infos, what, axis):
+    """One ``ConvergenceWarning`` for the (row set, cell) pairs whose kept result ran into a cap.  ``what``: the caller, ``axis``:
+    its grid's first axis, as the message names them."""
+    R, A, E = infos.shape
+    names = [f"fold {f}" for f in range(R - 1)] + ["all rows"]
+    capped = [(names[r], a, e) for r in range(R) for a in range(A) for e in range(E) if not infos[r, a, e]["converged"]]
+    if capped:
+        shown = ", ".join(f"{nm}: {axis} index {a}, eta index {e}" for nm, a, e in capped[:8]) + (", ..." if len(capped) > 8 else "")
+        warnings.warn(f"{what} ran into a cap in {len(capped)} of {R * A * E} (row set, cell) pairs ({shown}): their last points "
+                      "are returned", ConvergenceWarning)
+
+
 def l0_local_cv(X, y, *, alphas, etas=(0.0,), cv=5, big_M=100, fit_intercept=False, sample_weight=None, starts=None, max_rounds=2,
                 scoring="neg_root_mean_squared_error", solver_options=None) -> L0LocalCV:
     """``l0_local_search`` on every cross-validation fold's training rows and on all rows, one launch per round on the GPU.
@@ -142,90 +191,40 @@ def l0_local_cv(X, y, *, alphas, etas=(0.0,), cv=5, big_M=100, fit_intercept=Fal
     ``sample_weight`` weighs the training rows of every problem; ``starts`` are shared by the row sets.  One
     ``ConvergenceWarning`` names the (row set, cell) pairs whose kept result ran into a sweep or swap cap.  The coefficients of
     a fold are not byte for byte those of ``l0_local_search`` on its rows (see the module's text); nothing is proven optimal."""
-    options = {} if solver_options is None else solver_options
-    if not isinstance(options, dict):
-        raise ValueError("solver_options must be a dict or None")
-    unknown = set(options) - _OPTIONS
-    if unknown:
-        raise ValueError(f"unknown solver_options {sorted(unknown)}: the l0 local search takes {sorted(_OPTIONS)}")
-    swaps = options.get("swaps", True)
-    if not isinstance(swaps, (bool, np.bool_)):
-        raise ValueError("solver_options['swaps'] must be a bool")
-    if not isinstance(max_rounds, Integral) or isinstance(max_rounds, bool) or max_rounds < 0:
-        raise ValueError("max_rounds must be an integer >= 0")
+    swaps, device = _options(solver_options, max_rounds)
     if scoring not in _SCORINGS:
         raise ValueError(f"scoring must be one of {list(_SCORINGS)} (got {scoring!r})")
-    spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options={k: v for k, v in options.items() if k == "device"} or None)
+    spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options=device)
     # everything is validated before a device is touched
     X, y, dev_options, _, _, _, _, w = spec._l0_setup(X, y, sample_weight)
     al, et = _grid(alphas, "alphas"), _grid(etas, "etas")
-    A, E = len(al), len(et)
-    n, p = X.shape
+    A, E, p = len(al), len(et), X.shape[1]
     if p > _PMAX:
         raise NotImplementedError(f"the l0 local search takes up to {_PMAX} columns (got {p})")
     big_M = float(big_M)
-    first = np.zeros((A, E, 1, p))
-    if starts is not None:
-        st = np.asarray(starts, dtype=float)
-        if st.ndim == 2 and st.shape[1] == p:
-            st = np.broadcast_to(st, (A, E) + st.shape)
-        if st.ndim != 4 or st.shape[:2] != (A, E) or st.shape[3] != p:
-            raise ValueError(f"starts must have the shape (S, {p}) or ({A}, {E}, S, {p})")
-        if not np.all(np.abs(st) <= big_M):  # (a NaN fails too)
-            raise ValueError(f"starts must lie inside the box |beta_j| <= big_M = {big_M:g}")
-        first = np.concatenate([first, st], axis=2)
+    first, moves = _first_starts(starts, A, E, p, big_M), _round_moves(A, E, max_rounds)
     splits = _fold_splits(cv, X, y, "l0_local_cv")
     R = len(splits) + 1
-    most = max(first.shape[2], (2 * (A > 1) + 2 * (E > 1)) if max_rounds else 0)  # (a round starts a cell from its neighbours in the grid)
+    most = max(first.shape[2], len(moves))  # (a round starts a cell from its neighbours in the grid)
     if R * A * E * most > _MAX_PROBLEMS:
         raise ValueError(f"{R} row sets x {A * E} cells x up to {most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
-    row_weights, n_effs = _row_sets(splits, n, w)  # the folds' training rows, then all rows
     cell_alpha, cell_eta = np.repeat(al, E), np.tile(et, A)
 
-    from .. import _engine
+    def solve(ds, row_weights, n_effs, points):
+        return ds.solve_l0_local_folds(row_weights, n_effs, cell_alpha, cell_eta, intercept=fit_intercept, big_M=big_M, starts=points, swaps=swaps)
 
-    eng = _engine.get_engine(dev_options.get("device"))
-    Xd = np.hstack([X, np.ones((n, 1))]) if fit_intercept else X
-    launches, max_sweeps, max_swaps, problems = 0, 0, 0, 0
-    with eng.dataset(Xd, y) as ds:
+    def improved(new, old):
+        return new < old - _IMPROVE * np.maximum(np.abs(old), al[None, :, None])
 
-        def launch(points):  # points: R x A x E x S x p
-            nonlocal launches, max_sweeps, max_swaps, problems
-            b, i, o, _, stats, info = ds.solve_l0_local_folds(row_weights, n_effs, cell_alpha, cell_eta, intercept=fit_intercept, big_M=big_M,
-                                                              starts=points.reshape(R, A * E, -1, p), swaps=bool(swaps))
-            launches += 1
-            problems = max(problems, stats.shape[0] * stats.shape[1] * stats.shape[2])
-            max_sweeps, max_swaps = max(max_sweeps, int(stats[..., 0].max())), max(max_swaps, int(stats[..., 1].max()))
-            return (np.array(b).reshape(R, A, E, p), np.array(i).reshape(R, A, E), np.array(o).reshape(R, A, E),
-                    np.array(info, dtype=object).reshape(R, A, E))
-
-        coefs, icpts, objectives, infos = launch(np.broadcast_to(first, (R,) + first.shape))
-        history = [objectives.copy()]
-        moves = [(da, de) for da, de in ((-1, 0), (1, 0), (0, -1), (0, 1)) if (A > 1 and da) or (E > 1 and de)]
-        for _ in range(int(max_rounds) if moves else 0):
-            # every cell from its neighbours' winners IN ITS OWN ROW SET; beyond the grid's edge the cell's own winner stands in
-            points = np.stack([coefs[:, np.clip(np.arange(A) + da, 0, A - 1)][:, :, np.clip(np.arange(E) + de, 0, E - 1)] for da, de in moves],
-                              axis=3)
-            c2, i2, o2, f2 = launch(points)
-            better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[None, :, None])
-            coefs[better], icpts[better], objectives[better], infos[better] = c2[better], i2[better], o2[better], f2[better]
-            history.append(objectives.copy())
-            if not better.any():
-                break
-    history = np.array(history)  # rounds x R x A x E
-    names = [f"fold {f}" for f in range(len(splits))] + ["all rows"]
-    capped = [(names[r], a, e) for r in range(R) for a in range(A) for e in range(E) if not infos[r, a, e]["converged"]]
-    if capped:
-        shown = ", ".join(f"{nm}: alpha index {a}, eta index {e}" for nm, a, e in capped[:8]) + (", ..." if len(capped) > 8 else "")
-        warnings.warn(f"the local search ran into a cap in {len(capped)} of {R * A * E} (row set, cell) pairs ({shown}): their last points "
-                      "are returned", ConvergenceWarning)
+    coefs, icpts, objectives, infos, history, counts = _cv_rounds(X, y, splits, w, fit_intercept, dev_options.get("device"), solve, first,
+                                                                 moves, max_rounds, improved)
+    _warn_capped(infos, "the local search", "alpha")
     take = np.vectorize(lambda d, k: d[k])
     tables = [L0LocalPath(al, et, coefs[r], icpts[r], objectives[r], take(infos[r], "loss").astype(float), len(history), history[:, r],
                           take(infos[r], "swaps").astype(int), take(infos[r], "sweeps").astype(int), take(infos[r], "converged").astype(bool))
               for r in range(R)]
     paths, full = tables[:-1], tables[-1]
     cell_scores = _held_out_scores(scoring, X, y, splits, paths)
-    solver_info = {"launches": launches, "rounds": len(history), "problems": problems, "max_sweeps": max_sweeps, "max_swaps": max_swaps,
-                   "winner_max_sweeps": int(max(t.sweeps_.max() for t in tables)), "winner_max_swaps": int(max(t.swaps_.max() for t in tables)),
-                   "proven_optimal": False}
+    solver_info = {**counts, "winner_max_sweeps": int(max(t.sweeps_.max() for t in tables)),
+                   "winner_max_swaps": int(max(t.swaps_.max() for t in tables)), "proven_optimal": False}
     return L0LocalCV(paths, full, splits, cell_scores, scoring, solver_info)

@@ -41,11 +41,9 @@ from numbers import Integral
 import numpy as np
 from sklearn.exceptions import ConvergenceWarning
 
-from ._l0_local import _IMPROVE, _MAX_PROBLEMS, _OPTIONS, _PMAX, _grid, _LocalProblem
+from ._l0_local import _IMPROVE, _MAX_PROBLEMS, _PMAX, _first_starts, _grid, _LocalProblem, _neighbour_starts, _options, _round_moves
 
 __all__ = ["l0_local_subsets", "L0LocalSubsets"]
-
-_MOVES = ((-1, 0), (1, 0), (0, -1), (0, 1))  # a cell's neighbours: in size, in eta
 
 
 class L0LocalSubsets:
@@ -92,52 +90,17 @@ def _sizes(values):
     return raw.astype(np.int64)
 
 
-def _subsets_options(solver_options, max_rounds):
-    """``(swaps, the device options or None)`` of a call, validated."""
-    options = {} if solver_options is None else solver_options
-    if not isinstance(options, dict):
-        raise ValueError("solver_options must be a dict or None")
-    unknown = set(options) - _OPTIONS
-    if unknown:
-        raise ValueError(f"unknown solver_options {sorted(unknown)}: local subsets takes {sorted(_OPTIONS)}")
-    swaps = options.get("swaps", True)
-    if not isinstance(swaps, (bool, np.bool_)):
-        raise ValueError("solver_options['swaps'] must be a bool")
-    if not isinstance(max_rounds, Integral) or isinstance(max_rounds, bool) or max_rounds < 0:
-        raise ValueError("max_rounds must be an integer >= 0")
-    return bool(swaps), {k: v for k, v in options.items() if k == "device"} or None
-
-
 def _subsets_grid(sizes, etas, big_M, starts, max_rounds, p, row_sets=1):
     """``(sizes, etas, round-0 starts [K, E, S, p], the moves of a round)``, validated against the launch's limits."""
     ks, et = _sizes(sizes), _grid(etas, "etas")
     K, E = len(ks), len(et)
     if p > _PMAX:
         raise NotImplementedError(f"local subsets takes up to {_PMAX} columns (got {p})")
-    big_M = float(big_M)
-    first = np.zeros((K, E, 1, p))
-    if starts is not None:
-        st = np.asarray(starts, dtype=float)
-        if st.ndim == 2 and st.shape[1] == p:
-            st = np.broadcast_to(st, (K, E) + st.shape)
-        if st.ndim != 4 or st.shape[:2] != (K, E) or st.shape[3] != p:
-            raise ValueError(f"starts must have the shape (S, {p}) or ({K}, {E}, S, {p})")
-        if not np.all(np.abs(st) <= big_M):  # (a NaN fails too)
-            raise ValueError(f"starts must lie inside the box |beta_j| <= big_M = {big_M:g}")
-        first = np.concatenate([first, st], axis=2)
-    moves = [(dk, de) for dk, de in _MOVES if (K > 1 and dk) or (E > 1 and de)] if max_rounds else []
+    first, moves = _first_starts(starts, K, E, p, float(big_M)), _round_moves(K, E, max_rounds)
     most = max(first.shape[2], len(moves))
     if row_sets * K * E * most > _MAX_PROBLEMS:
         raise ValueError(f"{row_sets} row set(s) x {K * E} cells x up to {most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
     return ks, et, first, moves
-
-
-def _neighbour_starts(coefs, moves):
-    """``coefs``: [..., K, E, p].  Every cell's starts of a round: its neighbours' winners, [..., K, E, len(moves), p]; beyond the
-    grid's edge the cell's own winner stands in."""
-    K, E = coefs.shape[-3], coefs.shape[-2]
-    return np.stack([np.take(np.take(coefs, np.clip(np.arange(K) + dk, 0, K - 1), axis=-3), np.clip(np.arange(E) + de, 0, E - 1), axis=-2)
-                     for dk, de in moves], axis=-2)
 
 
 def _improved(new, old):
@@ -157,7 +120,7 @@ def l0_local_subsets(X, y, *, sizes, etas=(0.0,), big_M=100, fit_intercept=False
     ascending and consecutive, ``objectives_`` is non-increasing in k for each eta.  A ``ConvergenceWarning`` is raised when a
     cell's result ran into a sweep or swap cap.  Nothing is proven optimal."""
     # everything is validated before a device is touched
-    swaps, device = _subsets_options(solver_options, max_rounds)
+    swaps, device = _options(solver_options, max_rounds, "local subsets")
     spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options=device)
     X, y, dev_options, gidx, n_groups, need, _, w = spec._l0_setup(X, y, sample_weight)
     p = X.shape[1]

@@ -21,15 +21,12 @@ Import path: ``sparselm_amd.miqp`` (``l0_local_subsets_cv``, ``L0LocalSubsetsCV`
 
 from __future__ import annotations
 
-import warnings
-
 import numpy as np
-from sklearn.exceptions import ConvergenceWarning
 
 from ._l0_cv import _SCORINGS, _SELECTIONS
-from ._l0_local import _LocalProblem
-from ._l0_local_cv import L0LocalSearch, _fold_splits, _held_out_scores, _row_sets
-from ._l0_local_subsets import L0LocalSubsets, _improved, _neighbour_starts, _subsets_grid, _subsets_options
+from ._l0_local import _LocalProblem, _options
+from ._l0_local_cv import L0LocalSearch, _cv_rounds, _fold_splits, _held_out_scores, _warn_capped
+from ._l0_local_subsets import L0LocalSubsets, _improved, _subsets_grid
 
 __all__ = ["l0_local_subsets_cv", "L0LocalSubsetsCV"]
 
@@ -83,53 +80,24 @@ def l0_local_subsets_cv(X, y, *, sizes, etas=(0.0,), cv=5, big_M=100, fit_interc
     ``ConvergenceWarning`` names the (row set, cell) pairs whose kept result ran into a sweep or swap cap.  Nothing is proven
     optimal."""
     # everything is validated before a device is touched
-    swaps, device = _subsets_options(solver_options, max_rounds)
+    swaps, device = _options(solver_options, max_rounds, "local subsets")
     if scoring not in _SCORINGS:
         raise ValueError(f"scoring must be one of {list(_SCORINGS)} (got {scoring!r})")
     spec = _LocalProblem(big_M=big_M, fit_intercept=fit_intercept, solver_options=device)
     X, y, dev_options, _, _, _, _, w = spec._l0_setup(X, y, sample_weight)
-    n, p = X.shape
     splits = _fold_splits(cv, X, y, "l0_local_subsets_cv")
     R = len(splits) + 1
-    ks, et, first, moves = _subsets_grid(sizes, etas, big_M, starts, max_rounds, p, row_sets=R)
+    ks, et, first, moves = _subsets_grid(sizes, etas, big_M, starts, max_rounds, X.shape[1], row_sets=R)
     K, E = len(ks), len(et)
     big_M = float(big_M)
-    row_weights, n_effs = _row_sets(splits, n, w)  # the folds' training rows, then all rows
     cell_size, cell_eta = np.repeat(ks, E), np.tile(et, K)
 
-    from .. import _engine
+    def solve(ds, row_weights, n_effs, points):
+        return ds.solve_l0_local_subsets(row_weights, n_effs, cell_size, cell_eta, intercept=fit_intercept, big_M=big_M, starts=points, swaps=swaps)
 
-    eng = _engine.get_engine(dev_options.get("device"))
-    Xd = np.hstack([X, np.ones((n, 1))]) if fit_intercept else X
-    launches, max_sweeps, max_swaps, problems = 0, 0, 0, 0
-    with eng.dataset(Xd, y) as ds:
-
-        def launch(points):  # points: R x K x E x S x p
-            nonlocal launches, max_sweeps, max_swaps, problems
-            b, i, o, _, stats, info = ds.solve_l0_local_subsets(row_weights, n_effs, cell_size, cell_eta, intercept=fit_intercept, big_M=big_M,
-                                                                starts=points.reshape(R, K * E, -1, p), swaps=swaps)
-            launches += 1
-            problems = max(problems, stats.shape[0] * stats.shape[1] * stats.shape[2])
-            max_sweeps, max_swaps = max(max_sweeps, int(stats[..., 0].max())), max(max_swaps, int(stats[..., 1].max()))
-            return (np.array(b).reshape(R, K, E, p), np.array(i).reshape(R, K, E), np.array(o).reshape(R, K, E),
-                    np.array(info, dtype=object).reshape(R, K, E))
-
-        coefs, icpts, objectives, infos = launch(np.broadcast_to(first, (R,) + first.shape))
-        history = [objectives.copy()]
-        for _ in range(int(max_rounds) if moves else 0):
-            c2, i2, o2, f2 = launch(_neighbour_starts(coefs, moves))  # every cell from its neighbours' winners IN ITS OWN ROW SET
-            better = _improved(o2, objectives)
-            coefs[better], icpts[better], objectives[better], infos[better] = c2[better], i2[better], o2[better], f2[better]
-            history.append(objectives.copy())
-            if not better.any():
-                break
-    history = np.array(history)  # rounds x R x K x E
-    names = [f"fold {f}" for f in range(len(splits))] + ["all rows"]
-    capped = [(names[r], a, e) for r in range(R) for a in range(K) for e in range(E) if not infos[r, a, e]["converged"]]
-    if capped:
-        shown = ", ".join(f"{nm}: size index {a}, eta index {e}" for nm, a, e in capped[:8]) + (", ..." if len(capped) > 8 else "")
-        warnings.warn(f"local subsets ran into a cap in {len(capped)} of {R * K * E} (row set, cell) pairs ({shown}): their last points "
-                      "are returned", ConvergenceWarning)
+    coefs, icpts, objectives, infos, history, counts = _cv_rounds(X, y, splits, w, fit_intercept, dev_options.get("device"), solve, first,
+                                                                 moves, max_rounds, _improved)
+    _warn_capped(infos, "local subsets", "size")
     take = np.vectorize(lambda d, k: d[k])
     tables = [L0LocalSubsets(ks, et, coefs[r], icpts[r], objectives[r], take(infos[r], "loss").astype(float), len(history), history[:, r],
                              take(infos[r], "swaps").astype(int), take(infos[r], "sweeps").astype(int), take(infos[r], "grows").astype(int),
@@ -137,6 +105,5 @@ def l0_local_subsets_cv(X, y, *, sizes, etas=(0.0,), cv=5, big_M=100, fit_interc
               for r in range(R)]
     paths, full = tables[:-1], tables[-1]
     cell_scores = _held_out_scores(scoring, X, y, splits, paths)
-    solver_info = {"launches": launches, "rounds": len(history), "problems": problems, "max_sweeps": max_sweeps, "max_swaps": max_swaps,
-                   "proven_optimal": False}
+    solver_info = {**counts, "proven_optimal": False}
     return L0LocalSubsetsCV(paths, full, splits, cell_scores, scoring, solver_info)

@@ -1,7 +1,7 @@
 // CPU test of the host side of the l0 local search over row sets (slm_solve_l0_local_folds) in csrc/l0_host.hpp: the argument
 // check l0_lsf_check with every refusal and their order, the index map l0_lsf_index / l0_lsf_split, the elimination of the ones
-// column at a leading dimension (l0_eliminate_last_ld, l0_eliminate_vectors) against l0_eliminate_last, and l0_ls_solve on an
-// eliminated Gram against l0_ls_solve on the Gram of explicitly centred columns -- meant to run under AddressSanitizer and
+// column at a leading dimension (l0_eliminate_last_ld, l0_eliminate_vectors) against l0_eliminate_last, and l0_local_solve<false> on an
+// eliminated Gram against l0_local_solve<false> on the Gram of explicitly centred columns -- meant to run under AddressSanitizer and
 // UndefinedBehaviorSanitizer (tests/test_l0_local_cv_cpu.py builds and runs it both plainly and sanitized).
 #include <math.h>
 #include <stdio.h>
@@ -253,8 +253,8 @@ static void test_solve_on_eliminated() {
       for (bool swaps : {false, true}) {
         const double alpha = rel * yyc;
         std::vector<double> be((size_t)q), bc((size_t)q);
-        const L0LsResult Re = l0_ls_solve(Ge.data(), lds, ce.data(), q, alpha, eta, 100.0, yye, swaps, nullptr, be.data());
-        const L0LsResult Rc = l0_ls_solve(Gc.data(), lds, cc.data(), q, alpha, eta, 100.0, yyc, swaps, nullptr, bc.data());
+        const L0LsResult Re = l0_local_solve<false>(Ge.data(), lds, ce.data(), q, alpha, eta, 100.0, yye, swaps, nullptr, be.data());
+        const L0LsResult Rc = l0_local_solve<false>(Gc.data(), lds, cc.data(), q, alpha, eta, 100.0, yyc, swaps, nullptr, bc.data());
         CHECK(Re.status == 0 && Rc.status == 0 && Re.swaps == Rc.swaps && Re.nnz == Rc.nnz);
         CHECK(fabs(Re.F - Rc.F) <= 1e-10 * fmax(fabs(Rc.F), alpha));
         for (int j = 0; j < q; ++j) {

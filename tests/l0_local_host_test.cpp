@@ -1,4 +1,4 @@
-// CPU test of the host side of the l0 local search (slm_solve_l0_local) in csrc/l0_host.hpp: l0_ls_solve, the rule without a
+// CPU test of the host side of the l0 local search (slm_solve_l0_local) in csrc/l0_host.hpp: l0_local_solve<false>, the rule without a
 // device and the kernel's twin, l0_ls_polish and the argument checks l0_ls_check -- meant to run under AddressSanitizer and
 // UndefinedBehaviorSanitizer (tests/test_l0_local_cpu.py builds and runs it both plainly and sanitized).  Checks are against
 // a dense enumeration of all supports, the optimality conditions, or a certificate recomputed from the coefficients alone;
@@ -156,8 +156,8 @@ static void test_against_enumeration() {
     for (double rel : {0.002, 0.01, 0.05}) {
       const double alpha = rel * P.yy, eta = trial == 5 ? 0.05 : 0.0, M = 100.0;
       std::vector<double> b0((size_t)p), b1((size_t)p);
-      const L0LsResult R0 = l0_ls_solve(P.G.data(), P.ld, P.c.data(), p, alpha, eta, M, P.yy, false, nullptr, b0.data());
-      const L0LsResult R1 = l0_ls_solve(P.G.data(), P.ld, P.c.data(), p, alpha, eta, M, P.yy, true, nullptr, b1.data());
+      const L0LsResult R0 = l0_local_solve<false>(P.G.data(), P.ld, P.c.data(), p, alpha, eta, M, P.yy, false, nullptr, b0.data());
+      const L0LsResult R1 = l0_local_solve<false>(P.G.data(), P.ld, P.c.data(), p, alpha, eta, M, P.yy, true, nullptr, b1.data());
       const double exact = enumerate(P, alpha, eta), tol = 1e-9 * fmax(fabs(exact), alpha);
       CHECK(R0.status == 0 && R1.status == 0 && R0.swaps == 0);
       CHECK(fabs(R0.F - objective(P, alpha, eta, b0.data())) <= tol && fabs(R1.F - objective(P, alpha, eta, b1.data())) <= tol);
@@ -192,7 +192,7 @@ static void test_box() {
   const Problem P = problem(24, p, 12, 0.6);
   const double alpha = 0.002 * P.yy, M = 0.4;
   std::vector<double> b((size_t)p);
-  const L0LsResult R = l0_ls_solve(P.G.data(), P.ld, P.c.data(), p, alpha, 0.0, M, P.yy, true, nullptr, b.data());
+  const L0LsResult R = l0_local_solve<false>(P.G.data(), P.ld, P.c.data(), p, alpha, 0.0, M, P.yy, true, nullptr, b.data());
   CHECK(R.status == 0);
   int bound = 0;
   for (int j = 0; j < p; ++j) {
@@ -219,17 +219,17 @@ static void test_zero_column_and_singular() {
   const int p = 10;
   const Problem Z = problem(24, p, 10, 0.5, 4);  // column 4 (a true one) is zero: d_4 = 0, it stays out and nothing divides by it
   std::vector<double> b((size_t)p);
-  L0LsResult R = l0_ls_solve(Z.G.data(), Z.ld, Z.c.data(), p, 0.0, 0.0, 100.0, Z.yy, true, nullptr, b.data());
+  L0LsResult R = l0_local_solve<false>(Z.G.data(), Z.ld, Z.c.data(), p, 0.0, 0.0, 100.0, Z.yy, true, nullptr, b.data());
   CHECK(R.status == 0 && b[4] == 0.0 && std::isfinite(R.F) && R.nnz == p - 1);  // (alpha = 0: every live column enters)
   for (int j = 0; j < p; ++j) CHECK(std::isfinite(b[(size_t)j]));
   std::vector<double> st((size_t)p, 0.0);
   st[4] = 1.0;  // a start ON the dead column is dropped
-  R = l0_ls_solve(Z.G.data(), Z.ld, Z.c.data(), p, 0.01 * Z.yy, 0.0, 100.0, Z.yy, true, st.data(), b.data());
+  R = l0_local_solve<false>(Z.G.data(), Z.ld, Z.c.data(), p, 0.01 * Z.yy, 0.0, 100.0, Z.yy, true, st.data(), b.data());
   CHECK(R.status == 0 && b[4] == 0.0 && inescapable(Z, 0.01 * Z.yy, 0.0, 100.0, b.data(), true, 1e-8));
   // n < p: G is singular, eta > 0 makes H definite
   const Problem S = problem(5, p, 11, 0.3);
   const double eta = 0.05, alpha = 0.01 * S.yy;
-  R = l0_ls_solve(S.G.data(), S.ld, S.c.data(), p, alpha, eta, 100.0, S.yy, true, nullptr, b.data());
+  R = l0_local_solve<false>(S.G.data(), S.ld, S.c.data(), p, alpha, eta, 100.0, S.yy, true, nullptr, b.data());
   CHECK(R.status == 0 && std::isfinite(R.F) && R.F < 0.0);
   CHECK(fabs(R.F - objective(S, alpha, eta, b.data())) <= 1e-10 * fabs(R.F));
   CHECK(inescapable(S, alpha, eta, 100.0, b.data(), true, 1e-8));
@@ -243,14 +243,14 @@ static void test_wrong_start() {
   std::vector<double> st((size_t)p, 0.0), b((size_t)p), b0((size_t)p);
   st[0] = 3.0; st[2] = -2.0; st[9] = 1.5;  // none of the true columns 1, 4, 7
   const double F_start = objective(P, alpha, 0.0, st.data());
-  const L0LsResult R = l0_ls_solve(P.G.data(), P.ld, P.c.data(), p, alpha, 0.0, 100.0, P.yy, true, st.data(), b.data());
+  const L0LsResult R = l0_local_solve<false>(P.G.data(), P.ld, P.c.data(), p, alpha, 0.0, 100.0, P.yy, true, st.data(), b.data());
   CHECK(R.status == 0 && R.F <= F_start && R.F < 0.0);
   CHECK(fabs(R.F - objective(P, alpha, 0.0, b.data())) <= 1e-10 * fabs(R.F));
   CHECK(inescapable(P, alpha, 0.0, 100.0, b.data(), true, 1e-8));
   CHECK(st[0] == 3.0 && st[2] == -2.0 && st[9] == 1.5);  // the start is read, not written
   CHECK(R.F >= enumerate(P, alpha, 0.0) - 1e-10 * fabs(R.F));
   // an alpha above every gain empties the support, from a start too
-  const L0LsResult E = l0_ls_solve(P.G.data(), P.ld, P.c.data(), p, 10.0 * P.yy, 0.0, 100.0, P.yy, true, st.data(), b0.data());
+  const L0LsResult E = l0_local_solve<false>(P.G.data(), P.ld, P.c.data(), p, 10.0 * P.yy, 0.0, 100.0, P.yy, true, st.data(), b0.data());
   CHECK(E.status == 0 && E.nnz == 0 && E.F == 0.0);
   for (int j = 0; j < p; ++j) CHECK(b0[(size_t)j] == 0.0);
 }

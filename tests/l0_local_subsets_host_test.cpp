@@ -1,6 +1,6 @@
 // CPU test of the host side of local subsets (slm_solve_l0_local_subsets) in csrc/l0_host.hpp: the argument check l0_lc_check
 // with every refusal and their order, the problem index and the six-word status rows, and the host twin of the kernel's
-// cardinality rule l0_lc_solve -- against enumeration of every support, against a certificate recomputed from beta alone, from
+// cardinality rule l0_local_solve<true> -- against enumeration of every support, against a certificate recomputed from beta alone, from
 // starts that are too large and too small, at k >= p with a dead column, in a binding box, at a leading dimension with NaN
 // padding -- and l0_ls_polish on its results.  Meant to run under AddressSanitizer and UndefinedBehaviorSanitizer
 // (tests/test_l0_local_subsets_cpu.py builds and runs it both plainly and sanitized).
@@ -235,34 +235,34 @@ static void test_rule() {
     std::vector<double> beta((size_t)p), greedy((size_t)p), prev((size_t)p, 0.0);
     for (int k = 1; k <= 6; ++k) {
       const double eta = (seed & 1) ? 0.0 : 0.05;
-      const L0LcResult g = l0_lc_solve(P.G.data(), P.ld, P.c.data(), p, k, eta, M, P.yy, false, nullptr, greedy.data());
-      const L0LcResult s = l0_lc_solve(P.G.data(), P.ld, P.c.data(), p, k, eta, M, P.yy, true, nullptr, beta.data());
+      const L0LsResult g = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), p, k, eta, M, P.yy, false, nullptr, greedy.data());
+      const L0LsResult s = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), p, k, eta, M, P.yy, true, nullptr, beta.data());
       CHECK(g.status == 0 && s.status == 0 && g.swaps == 0);
       CHECK(g.nnz == k && s.nnz == k && g.grows == k && g.drops == 0);
       CHECK(s.grows == k && s.drops == 0);  // (a swap is neither)
-      CHECK(fabs(s.Q - quadratic(P, eta, beta.data())) <= 1e-12 * fabs(s.Q));
-      CHECK(s.Q <= g.Q + 1e-12 * fabs(g.Q));  // the swaps start where greedy stops
+      CHECK(fabs(s.F - quadratic(P, eta, beta.data())) <= 1e-12 * fabs(s.F));
+      CHECK(s.F <= g.F + 1e-12 * fabs(g.F));  // the swaps start where greedy stops
       const double best = enumerate(P, k, eta);
-      CHECK(s.Q >= best - 1e-10 * fabs(best));  // never below the optimum
+      CHECK(s.F >= best - 1e-10 * fabs(best));  // never below the optimum
       CHECK(inescapable(P, k, eta, M, beta.data(), true, 1e-8));
       CHECK(inescapable(P, k, eta, M, greedy.data(), false, 1e-8));
       // the polish keeps the support and does not raise Q
       std::vector<double> pol = beta;
       const double qp = l0_ls_polish(P.G.data(), P.ld, P.c.data(), p, eta, M, pol.data());
-      CHECK(qp <= s.Q + 1e-12 * fabs(s.Q) && fabs(qp - quadratic(P, eta, pol.data())) <= 1e-12 * fabs(qp));
+      CHECK(qp <= s.F + 1e-12 * fabs(s.F) && fabs(qp - quadratic(P, eta, pol.data())) <= 1e-12 * fabs(qp));
       for (int j = 0; j < p; ++j) CHECK((pol[(size_t)j] != 0.0) == (beta[(size_t)j] != 0.0));
       // from the winner of k - 1 (grown) the result is a fixed point of the rule too, and no worse than that winner
       if (k > 1) {
         std::vector<double> chain((size_t)p);
-        const L0LcResult c = l0_lc_solve(P.G.data(), P.ld, P.c.data(), p, k, eta, M, P.yy, true, prev.data(), chain.data());
+        const L0LsResult c = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), p, k, eta, M, P.yy, true, prev.data(), chain.data());
         CHECK(c.status == 0 && c.nnz == k && c.grows == 1 && c.drops == 0);
-        CHECK(c.Q <= quadratic(P, eta, prev.data()) + 1e-12);
+        CHECK(c.F <= quadratic(P, eta, prev.data()) + 1e-12);
         CHECK(inescapable(P, k, eta, M, chain.data(), true, 1e-8));
       }
       // from the winner of k (shrunk to k - 1, then to 1): the surplus leaves, nothing grows beyond the size
       if (k > 1) {
         std::vector<double> down((size_t)p);
-        const L0LcResult c = l0_lc_solve(P.G.data(), P.ld, P.c.data(), p, 1, eta, M, P.yy, true, beta.data(), down.data());
+        const L0LsResult c = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), p, 1, eta, M, P.yy, true, beta.data(), down.data());
         CHECK(c.status == 0 && c.nnz == 1 && c.drops == k - 1 && c.grows == 0);
         CHECK(inescapable(P, 1, eta, M, down.data(), true, 1e-8));
       }
@@ -276,28 +276,28 @@ static void test_edges() {
   {
     const double G[1] = {2.0}, c[1] = {3.0};
     double beta[1];
-    L0LcResult R = l0_lc_solve(G, 1, c, 1, 1, 0.0, 100.0, 5.0, true, nullptr, beta);
-    CHECK(R.status == 0 && R.nnz == 1 && R.grows == 1 && R.swaps == 0 && beta[0] == 1.5 && fabs(R.Q + 2.25) < 1e-15);
-    R = l0_lc_solve(G, 1, c, 1, 7, 0.25, 1.0, 5.0, true, nullptr, beta);  // the box binds; eta on the diagonal
-    CHECK(R.nnz == 1 && beta[0] == 1.0 && fabs(R.Q - (0.5 * 2.5 - 3.0)) < 1e-15);
+    L0LsResult R = l0_local_solve<true>(G, 1, c, 1, 1, 0.0, 100.0, 5.0, true, nullptr, beta);
+    CHECK(R.status == 0 && R.nnz == 1 && R.grows == 1 && R.swaps == 0 && beta[0] == 1.5 && fabs(R.F + 2.25) < 1e-15);
+    R = l0_local_solve<true>(G, 1, c, 1, 7, 0.25, 1.0, 5.0, true, nullptr, beta);  // the box binds; eta on the diagonal
+    CHECK(R.nnz == 1 && beta[0] == 1.0 && fabs(R.F - (0.5 * 2.5 - 3.0)) < 1e-15);
   }
   // k >= p with a dead column: the grow stops at the live columns
   {
     const Problem P = problem(25, 7, 7, 3, 99u);
     std::vector<double> beta(7), start(7, 0.5);
-    L0LcResult R = l0_lc_solve(P.G.data(), P.ld, P.c.data(), 7, 7, 0.0, 100.0, P.yy, true, nullptr, beta.data());
+    L0LsResult R = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), 7, 7, 0.0, 100.0, P.yy, true, nullptr, beta.data());
     CHECK(R.status == 0 && R.nnz == 6 && R.grows == 6 && beta[3] == 0.0);
     CHECK(inescapable(P, 7, 0.0, 100.0, beta.data(), true, 1e-8));
-    R = l0_lc_solve(P.G.data(), P.ld, P.c.data(), 7, 20, 0.0, 100.0, P.yy, true, start.data(), beta.data());  // (a start on the dead column)
+    R = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), 7, 20, 0.0, 100.0, P.yy, true, start.data(), beta.data());  // (a start on the dead column)
     CHECK(R.status == 0 && R.nnz == 6 && R.grows == 0 && R.drops == 0 && beta[3] == 0.0);
     const double all = enumerate(P, 7, 0.0);
-    CHECK(fabs(R.Q - all) <= 1e-9 * fabs(all));
+    CHECK(fabs(R.F - all) <= 1e-9 * fabs(all));
   }
   // a binding box: every coordinate inside it, the certificate holds with the clip
   {
     const Problem P = problem(30, 9, 9, -1, 7u);
     std::vector<double> beta(9);
-    const L0LcResult R = l0_lc_solve(P.G.data(), P.ld, P.c.data(), 9, 3, 0.0, 0.3, P.yy, true, nullptr, beta.data());
+    const L0LsResult R = l0_local_solve<true>(P.G.data(), P.ld, P.c.data(), 9, 3, 0.0, 0.3, P.yy, true, nullptr, beta.data());
     int at_bound = 0;
     for (double b : beta) {
       CHECK(fabs(b) <= 0.3);

@@ -324,3 +324,46 @@ def test_rounds_never_raise_an_objective_and_improve_a_cell():
             ok, why = is_swap_inescapable(H, c, alphas[a], 100.0, path.coefs_[a, e], CERT_TOL)
             assert ok, (a, e, why)
 
+
+
+# ---- 7. the one body behind the single-set entry: an empty winner, a start across the slot boundary, non-finite data ---------------
+def empty_and_live(X, y, starts=None):
+    """Two cells, the second with an alpha no column's gain reaches: its winner is empty -- objective 0, loss yy / 2, beta 0."""
+    yy = gram(X, y)[2]
+    alphas = np.array([0.02, 10.0]) * var(y)
+    ref, (betas, objectives, _, infos) = compare(X, y, alphas, starts=starts)
+    assert ref[0]["beta"].any() and not ref[1]["beta"].any()
+    assert not betas[1].any() and objectives[1] == 0.0 and infos[1]["objective"] == 0.0
+    # (yy is a sum of n products on either side: they differ by rounding alone, n eps at the most)
+    assert abs(infos[1]["loss"] - 0.5 * yy) <= 1e-12 * yy
+    return alphas
+
+
+def test_an_empty_winner_fetches_no_row_of_the_gram():
+    X, y = draw(30, 6, 3, 11)
+    alphas = empty_and_live(X, y)
+    # the empty cell alone: no winner of the call holds a column
+    betas, objectives, winners, infos = engine_cells(X, y, alphas[1:], np.zeros(1))
+    assert not betas.any() and objectives[0] == 0.0 and winners[0] == 0 and infos[0]["converged"]
+    assert abs(infos[0]["loss"] - 0.5 * gram(X, y)[2]) <= 1e-12 * gram(X, y)[2]
+
+
+def test_an_empty_winner_from_a_start_across_the_slot_boundary():
+    X, y = draw(80, 65, 6, 65)
+    starts = np.zeros((2, 1, 65))
+    starts[:, 0, 62:65] = 0.25  # columns 62 and 63 of the first slot, column 64 of the second
+    empty_and_live(X, y, starts=starts)
+
+
+def test_non_finite_data_is_refused_by_both_entries():
+    """One NaN in X: the dataset is built (only y is checked there), X^T y is not finite, and both entries say so by ctypes."""
+    from sparselm_amd import _engine
+
+    X, y = draw(30, 6, 3, 11)
+    X = X.copy()
+    X[4, 2] = np.nan
+    with _engine.get_engine().dataset(X, y) as ds:
+        with pytest.raises(_engine.NonFiniteError, match="non-finite"):
+            ds.solve_l0_local([0.1], binding=False)
+        with pytest.raises(_engine.NonFiniteError, match="non-finite"):
+            ds.solve_l0_local_folds([None], [0], [0.1], binding=False)

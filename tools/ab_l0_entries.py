@@ -1,4 +1,4 @@
-"""A/B of two builds of the engine on the eight exact-l0 entries (csrc/engine_l0.hip): child processes that load the library
+"""A/B of two builds of the engine on the eight exact-l0 entries and the four local-search entries (csrc/engine_l0.hip): child processes that load the library
 named by SLM_HIP_LIBRARY (every call then goes through ctypes), in the order given, each under its own time limit; the run
 stops at the first child that does not exit cleanly.  Results only (timing: tools/l0_timing.py).
 
@@ -12,6 +12,13 @@ Compared bit for bit between the first library and the others: coefficients, sup
 status, and every field of the info record -- except ``nodes``, and ``rejects`` where it counts descents or qp solves: those
 depend on which wave found an incumbent first and are printed.  Of a call under a node budget of one batch only the return
 code and the status are compared: its incumbent depends on timing.
+
+The local search (slm_solve_l0_local, _descent, _folds, _subsets): p in {5, 64, 65, 130} at n = 40, 3 cells x 2 starts with
+explicit starts and with none, swaps on and off, one NULL row set and three (two weighted, one NULL), intercept on and off,
+sizes {1, 3, p}, one cell whose alpha leaves the winner empty, and one refused call per refusal kind of l0_ls_check,
+l0_lsf_check and l0_lc_check.  Every output array, every field of every record and every raised message is compared: one wave
+owns one problem, so nothing varies between two runs.  Of a call on data with a NaN the exception's type is compared and its
+message printed (the single-set entry names X^T y where it named the Gram).
 
 usage: ab_l0_entries.py libA.so libB.so [...] [--out FILE]     (name the first library twice to see that the comparison is stable)"""
 import os, subprocess, sys, tempfile
@@ -138,6 +145,113 @@ with eng.dataset(X, y) as ds:  # ten groups of eight columns: includes are refus
     ds.set_groups(np.asarray(groups, dtype=np.int64), 10)
     keep("capacity", lambda: ds.solve_l0_wide(alpha=1e-9 * float(np.var(y)), big_M=1000.0))
     assert "capacity" in str(out["capacity/status"])
+
+# ---- the local search: the four entries, by ctypes ---------------------------------------------------------------------------------
+from test_l0_local_gpu import draw as draw_local
+
+def keep_local(tag, fn, message=True):
+    """every output array and every field of every record of the call, or what it raised"""
+    del records[:]
+    try:
+        res = fn()
+    except Exception as exc:
+        if message:
+            out[tag + "/raised"] = np.array(f"{type(exc).__name__}: {exc}")
+        else:
+            out[tag + "/raised_type"] = np.array(type(exc).__name__)
+            out[tag + "/print/message"] = np.array(str(exc))
+        return
+    out[tag + "/status"] = np.array("returned")
+    for i, v in enumerate(res[:-1]):
+        out[f"{tag}/out{i}"] = np.asarray(v)
+    for name in records[-1].dtype.names:
+        out[f"{tag}/rec/{name}"] = np.array(records[-1][name])
+
+def refused_local(tag, fn):
+    keep_local(tag + "/refused", fn)
+    assert tag + "/refused/raised" in out, tag
+
+def raw(ds, name, args, cnt, ps, nstat=None):
+    """the C entry with exactly these arguments (None: NULL), past the wrapper's coercions"""
+    outs = [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt, dtype=np.int32)]
+    if nstat:
+        outs = [outs[0], np.zeros(cnt), outs[1], outs[2], np.zeros((cnt, nstat), dtype=np.int32)]
+    return ds._l0_call(name, False, args, outs, records=cnt)
+
+rng = np.random.default_rng(7)
+for p in (5, 64, 65, 130):
+    X, y = draw_local(40, p, 3, p)
+    var = float(np.var(y))
+    alphas, etas = np.array([0.01, 0.1, 10.0]) * var, np.array([0.0, 0.02, 0.0])  # (the last alpha: an empty winner)
+    sizes = np.array([1, 3, p])
+    mask = np.ones(40)
+    mask[rng.choice(40, 8, replace=False)] = 0.0
+    sets = [mask * (40 / 32), rng.uniform(0.5, 1.5, 40), None]
+    n_effs = [32, 40, 0]
+    given = np.zeros((3, 2, p))
+    given[:, 1, ::3] = 0.25
+    if p > 64:
+        given[:, 1, 62:66] = -0.25  # (a support across the slot boundary)
+    with eng.dataset(X, y) as ds, eng.dataset(np.hstack([X, np.ones((40, 1))]), y) as ds1:
+        for swaps in (True, False):
+            for how, st, ns in (("given", given, None), ("none", None, 2)):
+                tag = f"local_p{p}_{'swaps' if swaps else 'descent'}_{how}"
+                keep_local(tag + "/single", lambda: ds.solve_l0_local(alphas, etas, starts=st, swaps=swaps, n_starts=ns))
+                for count in (1, 3):
+                    rws, nes = (sets, n_effs) if count == 3 else ([None], [0])
+                    stc = None if st is None else np.broadcast_to(st, (count,) + st.shape)
+                    for icpt, d in ((False, ds), (True, ds1)):
+                        t = f"{tag}/count{count}_icpt{int(icpt)}"
+                        keep_local(t + "/folds", lambda: d.solve_l0_local_folds(rws, nes, alphas, etas, intercept=icpt, starts=stc, swaps=swaps, n_starts=ns))
+                        keep_local(t + "/subsets", lambda: d.solve_l0_local_subsets(rws, nes, sizes, etas, intercept=icpt, starts=stc, swaps=swaps, n_starts=ns))
+        assert not out[f"local_p{p}_swaps_none/single/out0"][2].any() and out[f"local_p{p}_swaps_none/single/out0"][0].any()
+X, y = draw_local(40, 5, 3, 5)
+one, box = np.array([0.1]), np.full((1, 1, 5), 0.25)
+wide = np.random.default_rng(0).standard_normal((8, 1025))
+with eng.dataset(X, y) as ds, eng.dataset(wide, np.ones(8)) as dw:
+    # l0_ls_check, by the single-set entry
+    refused_local("ls_null", lambda: raw(ds, "solve_l0_local", (1, None, one, 100.0, 1, None), 1, 5))
+    refused_local("ls_cells", lambda: ds.solve_l0_local(one, n_cells=0))
+    refused_local("ls_starts", lambda: ds.solve_l0_local(one, n_starts=0))
+    refused_local("ls_problems", lambda: ds.solve_l0_local(np.full(8193, 0.1)))
+    refused_local("ls_big_M", lambda: ds.solve_l0_local(one, big_M=-1.0))
+    refused_local("ls_alpha", lambda: ds.solve_l0_local([0.1, -1.0]))
+    refused_local("ls_eta", lambda: ds.solve_l0_local([0.1, 0.1], etas=[0.0, np.nan]))
+    refused_local("ls_width", lambda: dw.solve_l0_local(one))
+    refused_local("ls_width_descent", lambda: dw.solve_l0_local(one, swaps=False))
+    refused_local("ls_box", lambda: ds.solve_l0_local(one, big_M=0.1, starts=box))
+    # l0_lsf_check, by the row-set entry
+    ptr0, ne0 = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.int64)
+    refused_local("lsf_count0", lambda: ds.solve_l0_local_folds([], [], one))
+    refused_local("lsf_count17", lambda: ds.solve_l0_local_folds([None] * 17, [0] * 17, one))
+    refused_local("lsf_null", lambda: raw(ds, "solve_l0_local_folds", (1, ptr0, ne0, 0, 1, None, one, 100.0, 1, None, 1), 1, 5, 4))
+    refused_local("lsf_cells", lambda: ds.solve_l0_local_folds([None], [0], one, n_cells=0))
+    refused_local("lsf_starts", lambda: ds.solve_l0_local_folds([None], [0], one, n_starts=0))
+    refused_local("lsf_product", lambda: ds.solve_l0_local_folds([None] * 3, [0] * 3, np.full(4096, 0.1)))
+    refused_local("lsf_big_M", lambda: ds.solve_l0_local_folds([None], [0], one, big_M=-1.0))
+    refused_local("lsf_alpha", lambda: ds.solve_l0_local_folds([None], [0], [0.1, -1.0]))
+    refused_local("lsf_eta", lambda: ds.solve_l0_local_folds([None], [0], [0.1, 0.1], etas=[0.0, np.nan]))
+    refused_local("lsf_width", lambda: dw.solve_l0_local_folds([None], [0], one))
+    refused_local("lsf_weight", lambda: ds.solve_l0_local_folds([np.r_[np.ones(39), -1.0]], [40], one))
+    refused_local("lsf_box", lambda: ds.solve_l0_local_folds([None], [0], one, big_M=0.1, starts=box[None]))
+    # l0_lc_check, by the cardinality entry
+    refused_local("lc_null", lambda: ds.solve_l0_local_subsets([None], [0], None))
+    refused_local("lc_size", lambda: ds.solve_l0_local_subsets([None], [0], [2, 0]))
+    refused_local("lc_eta", lambda: ds.solve_l0_local_subsets([None], [0], [2, 2], etas=[0.0, -1.0]))
+    refused_local("lc_lsf_big_M", lambda: ds.solve_l0_local_subsets([None], [0], [2], big_M=-1.0))
+    refused_local("lc_lsf_count", lambda: ds.solve_l0_local_subsets([None] * 17, [0] * 17, [2]))
+    # the dataset's shape, behind the checks: the intercept's column not alone in its group, then groups at all
+    ds.set_groups(np.array([0, 1, 2, 3, 3]), 4)
+    refused_local("lsf_intercept", lambda: ds.solve_l0_local_folds([None], [0], one, intercept=True))
+    refused_local("groups_single", lambda: ds.solve_l0_local(one))
+    refused_local("groups_folds", lambda: ds.solve_l0_local_folds([None], [0], one))
+    refused_local("groups_subsets", lambda: ds.solve_l0_local_subsets([None], [0], [2]))
+Xn = X.copy()
+Xn[4, 2] = np.nan
+with eng.dataset(Xn, y) as ds:  # (the constructor checks y alone)
+    keep_local("nan_single", lambda: ds.solve_l0_local(one), message=False)
+    keep_local("nan_folds", lambda: ds.solve_l0_local_folds([None], [0], one), message=False)
+    keep_local("nan_subsets", lambda: ds.solve_l0_local_subsets([None], [0], [2]), message=False)
 np.savez(out_path, **out)
 '''
 
@@ -187,13 +301,16 @@ if __name__ == "__main__":
         res.append(np.load(path))
         keys = res[i].files
         if i == 0:
-            say(f"{sum(k.endswith('/status') for k in keys)} calls that returned, {sum(k.endswith('/raised') for k in keys)} that raised, per library")
+            say(f"{sum(k.endswith('/status') and '/rec/' not in k for k in keys)} calls that returned, {sum(k.endswith('/raised') for k in keys)} that raised, per library")
             for k in keys:
                 if k.endswith("/raised"):
                     say(f"  {k}: {res[0][k]}")
-        printed = sorted({k.split("/")[0] for k in keys if "/print/" in k})
+        printed = sorted({k.split("/")[0] for k in keys if "/print/nodes" in k})
         say(f"child {i} ({lib}), not compared -- nodes[, descents or qp solves]: " + " ".join(
             f"{t} {int(res[i][t + '/print/nodes'])}" + (f",{int(res[i][t + '/print/rejects'])}" if t + "/print/rejects" in keys else "") for t in printed))
+        for k in keys:
+            if k.endswith("/print/message"):
+                say(f"  child {i}, printed: {k.split('/')[0]} raised {res[i][k.replace('/print/message', '/raised_type')]}: {res[i][k]}")
         if i > 0:
             same = compare(res[0], res[i], say)
             all_same = all_same and same

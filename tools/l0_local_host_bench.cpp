@@ -1,4 +1,4 @@
-// The CPU baseline of `tools/l0_timing.py --only local`: l0_ls_solve of csrc/l0_host.hpp -- the kernel's twin -- on the cells of
+// The CPU baseline of `tools/l0_timing.py --only local`: l0_local_solve<false> of csrc/l0_host.hpp -- the kernel's twin -- on the cells of
 // one file, one after the other on one core.  The tool compiles this file with g++ -O2 and runs it.
 // In: a file of  int64 p, ld, n_cells, swaps;  double yy, big_M;  G [p][ld];  c [p];  alphas [n_cells];  etas [n_cells].
 // Out: one line "cells N ms T changes C sweeps S swaps W", then one line "F" with every cell's objective.
@@ -28,7 +28,7 @@ int main(int argc, char** argv) {
   long long changes = 0, sweeps = 0, swaps = 0;
   const auto t0 = std::chrono::steady_clock::now();
   for (int e = 0; e < cells; ++e) {
-    const slm::L0LsResult R = slm::l0_ls_solve(G.data(), ld, c.data(), p, alphas[(size_t)e], etas[(size_t)e], scal[1], scal[0], head[3] != 0,
+    const slm::L0LsResult R = slm::l0_local_solve<false>(G.data(), ld, c.data(), p, alphas[(size_t)e], etas[(size_t)e], scal[1], scal[0], head[3] != 0,
                                                nullptr, beta.data());
     F[(size_t)e] = R.F;
     changes += R.changes;

@@ -1,4 +1,4 @@
-// The CPU baseline of `tools/l0_local_subsets_timing.py`: l0_lc_solve of csrc/l0_host.hpp -- the twin of the kernel's cardinality
+// The CPU baseline of `tools/l0_local_subsets_timing.py`: l0_local_solve<true> of csrc/l0_host.hpp -- the twin of the kernel's cardinality
 // rule -- on the cells of one file, one after the other on one core.  The tool compiles this file with g++ -O2 and runs it.
 // In: a file of  int64 p, ld, n_cells, swaps;  double yy, big_M;  G [p][ld];  c [p];  sizes [n_cells] (as doubles);  etas [n_cells].
 // Out: one line "cells N ms T changes C sweeps S swaps W grows G drops D", then one line "Q" with every cell's objective.
@@ -28,9 +28,9 @@ int main(int argc, char** argv) {
   long long changes = 0, sweeps = 0, swaps = 0, grows = 0, drops = 0;
   const auto t0 = std::chrono::steady_clock::now();
   for (int e = 0; e < cells; ++e) {
-    const slm::L0LcResult R = slm::l0_lc_solve(G.data(), ld, c.data(), p, (int)sizes[(size_t)e], etas[(size_t)e], scal[1], scal[0], head[3] != 0,
+    const slm::L0LsResult R = slm::l0_local_solve<true>(G.data(), ld, c.data(), p, (int)sizes[(size_t)e], etas[(size_t)e], scal[1], scal[0], head[3] != 0,
                                                nullptr, beta.data());
-    Q[(size_t)e] = R.Q;
+    Q[(size_t)e] = R.F;
     changes += R.changes;
     sweeps += R.sweeps;
     swaps += R.swaps;

@@ -1,6 +1,6 @@
 """Measurements of local subsets (``slm_solve_l0_local_subsets``) for ``profiles/l0_local_subsets.txt``.
 
-1. A sizes grid in ONE call (round 0: the zero start, ``max_rounds=0``) against the host twin ``l0_lc_solve`` on one core
+1. A sizes grid in ONE call (round 0: the zero start, ``max_rounds=0``) against the host twin ``l0_local_solve<true>`` on one core
    (``tools/l0_local_subsets_host_bench.cpp``, compiled here with g++ -O2), on the reference's 290 x 66 data and on synthetic
    400 x 1024; where it fits, against the exact ``l0_profile`` with ``wide`` (time and the gap in Q).
 2. ``l0_local_subsets_cv`` with five folds against the six ``l0_local_subsets`` calls it replaces.
@@ -98,7 +98,7 @@ def main():
     yw = Xw @ bw + 0.5 * rng.standard_normal(400)
 
     # ---- 1. one call against the host twin, and against the exact profile where it fits ---------------------------------------------
-    say("1. a sizes grid in ONE call (round 0 alone: max_rounds = 0, the zero start, big_M = 100, eta = 0) against l0_lc_solve on one core")
+    say("1. a sizes grid in ONE call (round 0 alone: max_rounds = 0, the zero start, big_M = 100, eta = 0) against l0_local_solve<true> on one core")
     say("   (the host time is the rule alone on a Gram it is handed; the call's includes the upload, the Gram and the polish).")
     for X, y, icpt, grids, what in ((Xr, yr, True, ([3], list(range(1, 9)), list(range(1, 33))), "the reference's 290 x 66 data, fit_intercept"),
                                     (Xw, yw, False, ([20], list(range(1, 17)), list(range(1, 65)), list(range(1, 65)) * 4),

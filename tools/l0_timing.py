@@ -66,7 +66,7 @@ the ridge kind, every problem under ``--max-nodes``.  Whole calls, warm, the var
 Then the local search (``sparselm_amd.miqp.l0_local_search``, ``slm_solve_l0_local``), written to ``profiles/l0_local.txt`` by
 ``--only local`` (it is not part of a run without ``--only``): beside ``RegularizedL0`` on the reference's 290 x 66 data and at 25 x 30
 (time, and the objective's gap to the proven or incumbent value); at 200 x 512 and 400 x 1024 one launch of 1, 16, 64 and 256 cells
-against the host twin ``l0_ls_solve`` on one core (``tools/l0_local_host_bench.cpp``, compiled here with g++); the time per applied
+against the host twin ``l0_local_solve<false>`` on one core (``tools/l0_local_host_bench.cpp``, compiled here with g++); the time per applied
 coordinate change at 1024 columns.  No ratio is promised: the file names the number of cells from which the launch wins, or says that it
 did not, and what was not measured.
 
@@ -772,7 +772,7 @@ def local_section(out_path, repeats, max_nodes):
 
     say("synthetic: rows of independent standard normal columns, 20 true columns at random places with coefficients +-1, noise 0.5; eta = 0;")
     say("alphas = geomspace(0.003, 0.3, cells) var y; big_M = 100; zero starts.  GPU: Dataset.solve_l0_local on a dataset that holds its Gram")
-    say("(the whole call: upload of the cells, ONE launch, read-back, the Gram to the host, the polish of every winner).  Host: l0_ls_solve of")
+    say("(the whole call: upload of the cells, ONE launch, read-back, the winners' Gram rows to the host, the polish of every winner).  Host: l0_local_solve<false> of")
     say("csrc/l0_host.hpp, g++ -O2, one core, the cells one after the other, the rule alone (no polish) on numpy's Gram.")
     say(f"{'n x p':>10s} {'cells':>6s} {'GPU ms: median (min .. max)':>34s} {'host ms: median (min .. max)':>36s} {'GPU / host':>11s} {'changes':>9s} {'same F':>7s}")
     wins = {}
@@ -822,8 +822,8 @@ def local_section(out_path, repeats, max_nodes):
         say(f"    slope between the first and the last: GPU {(t1 - t0) / (c1 - c0) * 1e3:.2f} us per change (one dependent 8 KB row read, the next scan), "
             f"host {(h1 - h0) / (c1 - c0) * 1e3:.2f} us per change")
     say("")
-    say("NOT measured: the kernel alone (no event bracket: the whole call is what a caller pays, and it carries the 8 p^2-byte copy of the Gram to")
-    say("the host for the polish); more than one start per cell; eta > 0; correlated designs, where sweeps and swaps multiply; devices with")
+    say("NOT measured: the kernel alone (no event bracket: the whole call is what a caller pays, and it carries the copy of the winners' Gram rows")
+    say("to the host for the polish); more than one start per cell; eta > 0; correlated designs, where sweeps and swaps multiply; devices with")
     say("fewer compute units; the host twin on several cores (the cells are independent: a 16-core host divides its column by up to 16).")
 
 
