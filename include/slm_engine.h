@@ -202,7 +202,12 @@ int slm_gradient_ex(slm_dataset* ds, const double* z, const slm_gradient_opts* o
  * Z, G_out: [n_lanes][p] (C-order, host); row_weights: [n_lanes][n] (NULL: the dataset's for every lane); n_eff: [n_lanes]
  * (NULL: the dataset's n).  kernels_out (nullable): the residual and product kernels launched, ';'-separated, e.g.
  * "rowdot_ring_kernel<8,1,5,3>;xtr_mfma_kernel".  SLM_ERR_UNSUPPORTED where the route has no kernel for this call: there
- * is no fallback to another route.  No reference counterpart (tests only).
+ * is no fallback to another route.
+ * Row-sharded datasets (routes 0 and 1): every rank calls with the same lanes; row_weights are THIS rank's rows, n_eff is the
+ * job's (NULL: n_global), and the pass ends in the all-reduce a solve's passes end in -- every rank gets the gradient and loss
+ * over all rows, bit for bit the same (one collective per call).  Route 2 and n_rows > 0 are SLM_ERR_UNSUPPORTED there (solves
+ * take neither covariance passes nor a sample start on sharded rows), before any collective.  No reference counterpart
+ * (tests only).
  */
 int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lanes, const double* Z, const double* row_weights,
                        const double* n_eff, const int32_t* cov_index, int64_t n_rows, double* G_out, double* loss_out,
@@ -227,7 +232,15 @@ int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lanes, const do
  * -X_W^T y / n, then y^T y / 2n; with SLM_WSL_XTY_BUILD [Kreal + 2], last the number of entries of lane 0's gradient vector
  * outside W that the builds wrote to (0: they left everything but W's entries and the loss alone).  kernels_out (nullable): every kernel launched, ';'-separated, in order; the covariance
  * product is named "+listed" when every row set reads only W's rows of its Gram.  SLM_ERR_UNSUPPORTED where no kernel serves
- * the call, and for row-sharded datasets.  No reference counterpart (tests only).
+ * the call.
+ * Row-sharded datasets (route 1): every rank calls with the same lanes, columns and stages; row_weights are THIS rank's rows,
+ * n_eff is the job's (NULL: n_global).  Every build stages this rank's part of the Grams, and what a sharded solve queues
+ * behind a build follows: the all-reduce of the staging matrix and ws_publish_kernel (named in kernels_out) -- so gram_out is
+ * the Gram over all rows, bit for bit the same on every rank; xw_out holds this rank's rows; the pass ends in the gradients'
+ * all-reduce.  The row sets are agreed among the ranks (two lanes are one set where their weights agree on EVERY rank's rows:
+ * one small all-reduce), so set_of_out and n_sets_out are the same everywhere.  n_builds + 2 collectives per call.  Route 2,
+ * SLM_WSL_XTY and SLM_WSL_XTY_BUILD are SLM_ERR_UNSUPPORTED there (no covariance passes and no sample start on sharded rows),
+ * before any collective.  No reference counterpart (tests only).
  */
 #define SLM_WSL_GATHER_X 1u  /* gather from the row-major X, not the column-major copy */
 #define SLM_WSL_XTY 2u       /* queue the ws_xty kernels with every build (the refinement after a row-sample pass) */

@@ -18,7 +18,11 @@ static int ws_policy(const slm_host::Knobs& kn, const slm_dataset* ds, uint32_t 
   //  width of a wavefront, not a property of the kernels: the model solver's group sums walk a group's members through LDS
   //  whatever their number, the scores and the selection move groups as blocks -- and ONE larger group switched the working
   //  set off for the whole dataset.)
-  if (ds->max_group > WS_KCAP / 2 || ds->n < 4) return 0;
+  // (row-sharded: the policy decides which collectives a pass enters and how many lanes a solve runs, so the row guard is
+  //  taken from the job's rows, which the ranks share -- from its own, a rank holding fewer than four rows of a tall matrix
+  //  left the working set alone, and its peers waiting in their Gram exchange)
+  const int64_t rows = row_sharded(ds) ? ds->n_global : ds->n;
+  if (ds->max_group > WS_KCAP / 2 || rows < 4) return 0;
   if (kn.ws == 0 || (flags & SLM_FLAG_NO_WORKING_SET)) return 0;
   const bool big = (double)ds->n * (double)ds->ld >= 67108864.0;  // 2^26 doubles = 512 MiB
   return (big || (flags & SLM_FLAG_WORKING_SET) || kn.ws == 1) ? 2 : 1;
@@ -1112,6 +1116,18 @@ static void ws_enqueue_build(slm_dataset* ds, const WsArgs& wa, const CovSets* c
   if (names) { names->add("ws_gram_kernel"); names->add("ws_gram_reduce_kernel"); }
 }
 
+// Row-sharded mode, behind ws_enqueue_build: the staged Gram parts of this rank's rows (wa.Gx) are summed over the ranks --
+// with the STOP_WORDS behind them in the same collective (enqueue_tail packs them; a caller without a tail zeroes them, and
+// stop_apply_kernel then does nothing) -- and ws_publish_kernel moves the new rows and columns into the Gram.  One collective
+// per call on every rank whether or not a build is under way.  `comm_rc` keeps the first failure of a collective (later ones
+// are not entered).  PathCall::enqueue_refinement and slm_working_set_lanes.
+static void ws_enqueue_exchange(slm_engine* eng, const WsArgs& wa, int* gdone, int& comm_rc, hipStream_t s) {
+  const size_t gram_words = (size_t)wa.n_sets * WS_KCAP * WS_KCAP;
+  if (comm_rc == 0) comm_rc = all_reduce_sum(eng, wa.Gx, gram_words + STOP_WORDS);  // (on the engine's stream: s)
+  hipLaunchKernelGGL(ws_publish_kernel, dim3(WS_PUBLISH_BLOCKS, (unsigned)wa.n_sets), dim3(256), 0, s, wa);
+  hipLaunchKernelGGL(stop_apply_kernel, dim3(1), dim3(64), 0, s, gdone, wa.Gx + gram_words);
+}
+
 // The model solvers of a pass: the iteration alone, then -- for the lanes it left -- the solver with direct steps
 // (ws_refine_lane).  PathCall::enqueue_refinement and slm_working_set_model_solve; `names` (nullable): the kernels launched.
 static void ws_enqueue_solvers(const slm_dataset* ds, const TailArgs& ta, const WsArgs& wa, int B, hipStream_t s, WsNames* names = nullptr) {
@@ -1145,14 +1161,9 @@ void PathCall::enqueue_refinement() {
     } else {
       ws_enqueue_build(ds, wa, nullptr, fix_start ? WS_XTY_BUILD : WS_XTY_NONE, done_flag, B, s);
     }
-    if (wa.Gx) {
-      // one collective per pass on every rank whether or not a build is under way: the ranks run the
-      // same state machine on the same all-reduced gradients, so they agree on when that is
-      const size_t gram_words = (size_t)wa.n_sets * WS_KCAP * WS_KCAP;
-      if (ws_comm_rc == 0) ws_comm_rc = all_reduce_sum(eng, wa.Gx, gram_words + STOP_WORDS);  // (+ the stop words: enqueue_tail)
-      hipLaunchKernelGGL(ws_publish_kernel, dim3(WS_PUBLISH_BLOCKS, (unsigned)wa.n_sets), dim3(256), 0, s, wa);
-      hipLaunchKernelGGL(stop_apply_kernel, dim3(1), dim3(64), 0, s, ta.gdone, wa.Gx + gram_words);
-    }
+    // one collective per pass on every rank whether or not a build is under way: the ranks run the
+    // same state machine on the same all-reduced gradients, so they agree on when that is
+    if (wa.Gx) ws_enqueue_exchange(eng, wa, ta.gdone, ws_comm_rc, s);  // (+ the stop words: enqueue_tail)
     ws_enqueue_solvers(ds, ta, wa, B, s);
   }
 }
@@ -1731,8 +1742,9 @@ extern "C" int slm_solve_path(slm_dataset* ds, const slm_penalty* pen, const slm
 
 // ------------------------------------------------------------------------------------------------
 // Diagnostic: a working set built in stages and one gradient pass on it (slm_engine.h).  The buffers, row blocks and launches
-// are a solve's own (ws_row_blocks, ws_alloc, ws_bind, ws_enqueue_build, enqueue_gradient_split / _cov); only the selection is
-// the caller's.  No fallback: where no kernel serves the call the answer is SLM_ERR_UNSUPPORTED.
+// are a solve's own (ws_row_blocks, ws_alloc, ws_bind, ws_enqueue_build, on row-sharded datasets ws_enqueue_exchange,
+// enqueue_gradient_split / _cov); only the selection is the caller's.  No fallback: where no kernel serves the call the
+// answer is SLM_ERR_UNSUPPORTED.
 // ------------------------------------------------------------------------------------------------
 extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o, double* G_out, double* loss_out, int32_t* set_of_out,
                                      int32_t* n_sets_out, double* gram_out, double* xw_out, double* xty_out, char* kernels_out,
@@ -1746,7 +1758,15 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
   if (o->flags & ~(SLM_WSL_GATHER_X | SLM_WSL_XTY | SLM_WSL_XTY_BUILD)) return fail(SLM_ERR_BAD_ARG, "unknown flags %#x", o->flags);
   if ((o->flags & SLM_WSL_XTY) && (o->flags & SLM_WSL_XTY_BUILD)) return fail(SLM_ERR_BAD_ARG, "SLM_WSL_XTY or SLM_WSL_XTY_BUILD, not both");
   if (xty != (xty_out != nullptr)) return fail(SLM_ERR_BAD_ARG, "xty_out goes with SLM_WSL_XTY / SLM_WSL_XTY_BUILD");
-  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "slm_working_set_lanes: row-sharded datasets");
+  // Row-sharded datasets: route 1 builds W as a sharded solve does -- every rank's part of the Gram staged, summed over the
+  // ranks and published (ws_enqueue_exchange) -- and the pass ends in the gradients' all-reduce.  What is refused is refused
+  // here, before the first collective and on arguments the ranks share: a bad call fails on every rank, nobody waits.
+  const bool sharded = row_sharded(ds);
+  if (sharded && route == 2)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_working_set_lanes: route 2 on a row-sharded dataset (solves take no covariance passes there)");
+  if (sharded && xty)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_working_set_lanes: X_W^T y on a row-sharded dataset (the sample start that needs it is not "
+                                     "built for sharded rows: its partial sums are not all-reduced)");
   if (B > ds->lane_cap) return fail(SLM_ERR_UNSUPPORTED, "%d lanes: the dataset holds %d", B, ds->lane_cap);
   const int64_t n = ds->n, p = ds->p, ld = ds->ld;
   // ---- the stages of W
@@ -1822,16 +1842,34 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
   if (o->n_eff)
     for (int l = 0; l < B; ++l) ls.n_eff[l] = o->n_eff[l];
   // row sets: lanes with the same row weights and n_eff (route 2: the same covariance entry)
-  int set_of[kMaxLanes], set_lane[kMaxLanes], n_sets = 0;
-  for (int l = 0; l < B; ++l) {
-    int found = -1;
-    for (int m = 0; m < l && found < 0; ++m) {
+  // Row-sharded: `row_weights` are this rank's rows, and two lanes whose weights differ only on another rank's rows are one
+  // set here and two there -- other n_sets, other collective sizes, Grams filed under the wrong set.  So the ranks agree: the
+  // B x B table "the same on my rows" is summed over the ranks, and two lanes are one set where every rank said so.  One
+  // small collective per call, on every rank alike.  (Solves need none: they compare the lanes' host pointers, which the
+  // ranks share by construction -- PathCall::ws_setup.)
+  std::vector<double> same_tab((size_t)B * B, 0.0);
+  for (int l = 0; l < B; ++l)
+    for (int m = 0; m < l; ++m) {
       const bool same = route == 2 ? o->cov_index[m] == o->cov_index[l]
                                    : ls.n_eff[m] == ls.n_eff[l] &&
                                          (!o->row_weights || memcmp(o->row_weights + (size_t)m * n, o->row_weights + (size_t)l * n,
                                                                     sizeof(double) * (size_t)n) == 0);
-      if (same) found = set_of[m];
+      same_tab[(size_t)l * B + m] = same ? 1.0 : 0.0;
     }
+  double same_all = 1.0;
+  if (sharded) {
+    // (through the gradient block: lane_cap >= kMaxLanes vectors of ld + 16 >= 32 doubles; overwritten below)
+    static_assert(kMaxLanes * kMaxLanes <= kMaxLanes * (16 + 16), "the table fits the gradient block of the narrowest dataset");
+    SLM_TRY(put(ds->g, same_tab.data(), sizeof(double) * same_tab.size()));
+    SLM_TRY(all_reduce_sum(ds->eng, ds->g, same_tab.size()));
+    SLM_TRY(get(same_tab.data(), ds->g, sizeof(double) * same_tab.size()));
+    same_all = (double)ds->eng->n_ranks;
+  }
+  int set_of[kMaxLanes], set_lane[kMaxLanes], n_sets = 0;
+  for (int l = 0; l < B; ++l) {
+    int found = -1;
+    for (int m = 0; m < l && found < 0; ++m)
+      if (same_tab[(size_t)l * B + m] == same_all) found = set_of[m];
     if (found < 0) {
       found = n_sets;
       set_lane[n_sets++] = l;
@@ -1839,11 +1877,11 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
     set_of[l] = found;
   }
   // ---- buffers and arguments as a solve makes them
-  const WsBlocks wb = ws_row_blocks(ds, ls.rw != nullptr && n_sets > 1, n_sets);
-  SLM_TRY(ws_alloc(kn, ds, n_sets, wb.most, false));
+  const WsBlocks wb = ws_row_blocks(ds, ls.rw != nullptr && !sharded && n_sets > 1, n_sets);  // (PathCall::ws_setup's)
+  SLM_TRY(ws_alloc(kn, ds, n_sets, wb.most, sharded));
   WsArgs wa;
   memset(&wa, 0, sizeof(wa));
-  SLM_TRY(ws_bind(kn, ds, ls, set_of, set_lane, n_sets, wb.nblk, false, wa, s));
+  SLM_TRY(ws_bind(kn, ds, ls, set_of, set_lane, n_sets, wb.nblk, sharded, wa, s));
   if (gather_x) wa.XT = nullptr;  // (what a dataset without the memory for the copy gathers from)
   std::string names;
   auto named = [&](const char* k) {
@@ -1860,6 +1898,9 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
   HIP_TRY(hipMemsetAsync(ds->ws_G, 0xff, sizeof(double) * (size_t)n_sets * WS_KCAP * WS_KCAP, s));
   HIP_TRY(hipMemsetAsync(ds->g, 0xff, sizeof(double) * (size_t)(ld + 16) * B, s));
   HIP_TRY(hipMemsetAsync(&ds->gctl->done, 0, sizeof(int32_t), s));
+  // (row-sharded: no tail packs the stop words that ride behind the Gram parts -- zeros, which stop_apply_kernel leaves alone)
+  if (wa.Gx) HIP_TRY(hipMemsetAsync(wa.Gx + (size_t)n_sets * WS_KCAP * WS_KCAP, 0, sizeof(double) * STOP_WORDS, s));
+  int comm_rc = 0;
   // the state of a fresh solve (ws_ctl_init_kernel)
   WsCtl* h = new WsCtl;
   std::unique_ptr<WsCtl> h_hold(h);
@@ -1891,6 +1932,11 @@ extern "C" int slm_working_set_lanes(slm_dataset* ds, const slm_ws_lanes_opts* o
     WsNames wn;
     ws_enqueue_build(ds, wa, route == 2 ? &cs : nullptr, xty_mode, &ds->gctl->done, B, s, &wn);
     for (int u = 0; u < wn.n; ++u) named(wn.k[u]);
+    if (wa.Gx) {  // (what PathCall::enqueue_refinement queues behind the build)
+      ws_enqueue_exchange(ds->eng, wa, &ds->gctl->done, comm_rc, s);
+      named("ws_publish_kernel");
+      if (comm_rc != 0) return comm_rc;  // (all_reduce_sum has set the message)
+    }
     SLM_TRY(check_launch());
     SLM_TRY(get(h, ds->ws_ctl, sizeof(WsCtl)));
     if (h->valid != 1 || h->building != 0 || h->counter != 0)

@@ -689,7 +689,13 @@ extern "C" int slm_gradient_lanes(slm_dataset* ds, int32_t route, int32_t n_lane
   if (route < 0 || route > 2) return fail(SLM_ERR_BAD_ARG, "route must be 0 (fused), 1 (split pass) or 2 (covariance), got %d", route);
   if (n_lanes < 1 || n_lanes > kMaxLanes) return fail(SLM_ERR_BAD_ARG, "between 1 and %d lanes, got %d", kMaxLanes, n_lanes);
   if (n_rows < 0 || n_rows > ds->n) return fail(SLM_ERR_BAD_ARG, "n_rows = %lld outside [0, %lld]", (long long)n_rows, (long long)ds->n);
-  if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "slm_gradient_lanes: row-sharded datasets");
+  // Row-sharded datasets: routes 0 and 1 end in the all-reduce a solve's passes end in (enqueue_gradient / _split), so every
+  // rank calls alike and gets the gradient over all rows.  What is refused is refused here, before that collective and on
+  // arguments the ranks share -- a bad call fails on every rank and leaves nobody waiting.
+  if (row_sharded(ds) && route == 2)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_gradient_lanes: route 2 on a row-sharded dataset (solves take no covariance passes there)");
+  if (row_sharded(ds) && n_rows > 0)
+    return fail(SLM_ERR_UNSUPPORTED, "slm_gradient_lanes: n_rows on a row-sharded dataset (the sample start is not built for sharded rows)");
   if (n_lanes > ds->lane_cap) return fail(SLM_ERR_UNSUPPORTED, "%d lanes: the dataset holds %d", n_lanes, ds->lane_cap);
   const int B = n_lanes;
   const int64_t n = ds->n, p = ds->p, ld = ds->ld;

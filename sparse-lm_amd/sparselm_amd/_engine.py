@@ -870,7 +870,9 @@ class Dataset:
         """``slm_gradient_lanes``: one gradient pass of ``len(Z)`` lanes through route 0 (fused), 1 (split pass) or 2
         (covariance entries ``cov_index``), each lane with its own point ``Z[l]``, row weights ``row_weights[l]`` and
         ``n_eff[l]``; ``n_rows`` > 0: only the first rows.  Returns ``(G, loss, kernels)``: (lanes, p), (lanes,) and the
-        names of the kernels launched.  A route without a kernel for the call raises NotImplementedError."""
+        names of the kernels launched.  A route without a kernel for the call raises NotImplementedError.  On a row-sharded
+        dataset (routes 0 and 1, every rank calling alike): ``row_weights`` are this rank's rows, ``n_eff`` is the job's, and
+        every rank gets the all-reduced gradients and losses."""
         _sync_knobs()
         Z = _f64(np.atleast_2d(Z), "Z")
         B = Z.shape[0]
@@ -895,7 +897,9 @@ class Dataset:
         lanes with ``on_ws``) or 2 (covariance entries ``cov_index``).  Returns a namespace: ``G`` (lanes, p), ``loss``,
         ``gram`` (row sets, K, K), ``set_of``, ``n_sets``, ``K``, ``XW`` (n, K) with ``want_xw``, ``xty`` (-X_W^T y / n) and
         ``yy`` (y^T y / 2n) with ``xty`` (the two ws_xty kernels behind the gather) or ``xty_build`` (the way a solve
-        gets them on this dataset: out of the gather), and ``kernels``.  A call no kernel serves raises NotImplementedError."""
+        gets them on this dataset: out of the gather), and ``kernels``.  A call no kernel serves raises NotImplementedError.
+        On a row-sharded dataset (route 1, no ``xty``, every rank calling alike): ``row_weights`` and ``XW`` are this rank's
+        rows, ``n_eff`` is the job's, ``gram`` / ``G`` / ``loss`` are over all rows and ``set_of`` is agreed among the ranks."""
         import types
 
         _sync_knobs()

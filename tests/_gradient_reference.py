@@ -251,16 +251,17 @@ def assert_xty_within_bound(c, yy, ref, what=""):
 SPLIT_RING = [(C, 3 if C < 5 else 2) for C in (1, 2, 3, 4, 5)]  # rowdot_ring_kernel<8, C, 5, D>: rows of up to 512 C columns
 
 
-def ws_build_expected(k_end, route=1, xty=False, owner=False):
-    """The build kernels: ws_block_owner_kernel once (lanes with row weights, unless SLM_NO_GRAM_OWNER), then per build
-    gather (+ xty) + Gram + reduce -- or ws_gram_cov_kernel under covariance passes."""
-    names = ["ws_block_owner_kernel"] if owner and route == 1 else []
+def ws_build_expected(k_end, route=1, xty=False, owner=False, sharded=False):
+    """The build kernels: ws_block_owner_kernel once (lanes with row weights, unless SLM_NO_GRAM_OWNER; never on a
+    row-sharded dataset), then per build gather (+ xty) + Gram + reduce -- or ws_gram_cov_kernel under covariance passes.
+    Row-sharded: the reduce stages this rank's part, and ws_publish_kernel follows the all-reduce of the staging matrix."""
+    names = ["ws_block_owner_kernel"] if owner and route == 1 and not sharded else []
     for _ in k_end:
         if route == 2:
             names.append("ws_gram_cov_kernel")
         else:
             names += ["ws_gather_kernel"] + (["ws_xty_partial_kernel", "ws_xty_apply_kernel"] if xty else []) + \
-                     ["ws_gram_kernel", "ws_gram_reduce_kernel"]
+                     ["ws_gram_kernel", "ws_gram_reduce_kernel"] + (["ws_publish_kernel"] if sharded else [])
     return names
 
 

@@ -8,45 +8,15 @@ Reference semantics being reproduced: one `_solve` on the whole (X, y) (src/spar
 and `_preprocess_data` centring on the whole matrix (:216-222); the reference has no distributed code.
 """
 
-import threading
-
 import numpy as np
 import pytest
 
+from _certificate import assert_certified, lambda_max
+from _ranks import run_ranks as _run_ranks, split_bounds
 from sparselm_amd import _engine
 from sparselm_amd.distributed import row_range
 
 pytestmark = pytest.mark.gpu
-
-
-def _run_ranks(n_ranks, work, timeout_s=30.0):
-    """work(rank, engine) on n_ranks fresh engines joined by an in-process communicator; returns the results
-    and the collective counts; re-raises the first exception of any rank."""
-    engines = [_engine.Engine(0) for _ in range(n_ranks)]
-    _engine.init_local_comm(engines, timeout_s=timeout_s)
-    out = [None] * n_ranks
-    err = [None] * n_ranks
-
-    def body(r):
-        try:
-            out[r] = work(r, engines[r])
-        except BaseException as exc:  # noqa: BLE001 - reported below
-            err[r] = exc
-
-    threads = [threading.Thread(target=body, args=(r,)) for r in range(n_ranks)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    counts = [e.comm_collectives() for e in engines]
-    infos = [e.comm_info() for e in engines]
-    for e in engines:
-        e.comm_destroy()
-        e.close()
-    for exc in err:
-        if exc is not None:
-            raise exc
-    return out, counts, infos
 
 
 def _problem(n, p, seed, n_inf=10, noise=0.5):
@@ -271,3 +241,131 @@ def test_single_local_rank_is_the_plain_engine():
         ref = ds.solve_path(pts, tol=1e-10, flags=plain)
     assert np.array_equal(out[0].betas, ref.betas)
     assert np.array_equal(out[0].n_iter, ref.n_iter)
+
+
+# ---- sharded solves that actually append to the working set ------------------------------------------------------------------
+# The paths above are well conditioned: their working sets most likely never grow.  Here a small first selection and small
+# appends (SLM_WS_KINIT / SLM_WS_APPEND, as in test_certificate_gpu.py) on a path that ends at the noise floor force misses and
+# appends, so the staged Gram of an append -- all-reduce, publish of the new rows and their mirror images -- decides whether
+# the model the lanes iterate on is the right one.  A wrong entry costs passes, not correctness (every point is verified on
+# X), so the counters are asserted beside the coefficients, and every point is audited against the whole X.
+APPEND_N, APPEND_P, APPEND_K = 3000, 300, 16
+APPEND_SPLITS = [(1500, 1500), (2999, 1), (63, 1, 2936)]
+APPEND_LANES = (1, 3, 16)
+_APPEND_CACHE = {}
+
+
+def _append_problem(kind):
+    """(X, y, points, a, groups, lambda_max) of a path of `kind` from the top of its range to the noise floor."""
+    if kind not in _APPEND_CACHE:
+        seed = ("l1", "weighted", "group", "sparse-group").index(kind)
+        rng = np.random.default_rng(300 + seed)
+        n, p = APPEND_N, APPEND_P
+        X = rng.standard_normal((n, p))
+        beta = np.zeros(p)
+        beta[rng.choice(p, 25, replace=False)] = 30.0 * rng.uniform(0.1, 1.0, 25)
+        y = X @ beta + 3.0 * rng.standard_normal(n)
+        g0 = X.T @ y / n
+        a = groups = None
+        if kind in ("l1", "weighted"):
+            a = rng.uniform(0.5, 2.0, p) if kind == "weighted" else None
+            top = float(np.max(np.abs(g0) / (1.0 if a is None else a)))
+            pts = [(s, 0.0, 0.0) for s in np.geomspace(top, 1e-3 * top, APPEND_K)]
+        else:
+            G = p // 10
+            groups = rng.permutation(np.repeat(np.arange(G), 10)).astype(np.int32)
+            top = float(np.max(np.sqrt(np.bincount(groups, weights=g0 * g0, minlength=G))))
+            l1 = 0.0 if kind == "group" else 0.4
+            pts = [(l1 * s, (1.0 - l1) * s, 0.0) for s in np.geomspace(top, 1e-2 * top, APPEND_K)]
+        _APPEND_CACHE[kind] = (X, y, pts, a, groups, lambda_max(X))
+    return _APPEND_CACHE[kind]
+
+
+def _append_reference(kind, lanes):
+    """The single-rank run of the same solve, under the knobs the caller has set (one per kind and lane count)."""
+    key = (kind, lanes)
+    if key not in _APPEND_CACHE:
+        X, y, pts, a, groups, _ = _append_problem(kind)
+        with _engine.get_engine(0).dataset(X, y) as ds:
+            if groups is not None:
+                ds.set_groups(groups, int(groups.max()) + 1)
+            _APPEND_CACHE[key] = ds.solve_path(pts, a=a, tol=1e-10, flags=_engine.FLAG_WORKING_SET, lanes=lanes)
+    return _APPEND_CACHE[key]
+
+
+@pytest.mark.parametrize("kind", ["l1", "weighted", "group", "sparse-group"])
+@pytest.mark.parametrize("split", APPEND_SPLITS, ids=lambda s: "_".join(map(str, s)))
+def test_sharded_solves_that_append_match_the_single_rank_path(split, kind, monkeypatch):
+    monkeypatch.setenv("SLM_WS_KINIT", "16")  # (before the rank threads start: the knobs are read at every call)
+    monkeypatch.setenv("SLM_WS_APPEND", "4")
+    X, y, pts, a, groups, L_true = _append_problem(kind)
+    n = len(y)
+    assert sum(split) == n
+    bounds = split_bounds(split)
+
+    def work(r, eng):
+        lo, hi = bounds[r]
+        out = []
+        with eng.dataset(X[lo:hi], y[lo:hi]) as ds:
+            ds.set_global_rows(n)
+            if groups is not None:
+                ds.set_groups(groups, int(groups.max()) + 1)
+            for lanes in APPEND_LANES:
+                c0 = eng.comm_collectives()
+                res = ds.solve_path(pts, a=a, tol=1e-10, flags=_engine.FLAG_WORKING_SET, lanes=lanes)
+                out.append((res, eng.comm_collectives() - c0))
+        return out
+
+    out, counts, _ = _run_ranks(len(split), work)
+    assert len(set(counts)) == 1 and counts[0] > 0
+    for k, lanes in enumerate(APPEND_LANES):
+        ref = _append_reference(kind, lanes)
+        assert ref.converged
+        for r in range(len(split)):
+            res, used = out[r][k]
+            what = f"{kind}, {lanes} lanes, rank {r} of {split}"
+            assert res.converged, what
+            assert res.ws_appends > 0 and res.ws_misses > 0, (what, res.ws_appends, res.ws_misses)
+            assert_certified(res, pts, X=X, y=y, a=a, groups=groups, tol=1e-10, L_true=L_true)
+            assert np.max(np.abs(res.betas - ref.betas)) <= 1e-8 * np.max(np.abs(ref.betas)), what
+            assert np.array_equal(res.betas, out[0][k][0].betas), f"{what}: not rank 0's bits"
+            assert used == out[0][k][1] and used > 0, f"{what}: {used} collectives, rank 0 entered {out[0][k][1]}"
+
+
+@pytest.mark.parametrize("split", APPEND_SPLITS, ids=lambda s: "_".join(map(str, s)))
+def test_sharded_fold_lanes_that_append_match_the_single_rank_lanes(split, monkeypatch):
+    """Three fold masks as per-lane row weights, each rank passing its slices: more than one row set in sharded mode, i.e. a
+    staged Gram per set in the one all-reduce of a pass."""
+    monkeypatch.setenv("SLM_WS_KINIT", "16")
+    monkeypatch.setenv("SLM_WS_APPEND", "4")
+    X, y, pts, _, _, _ = _append_problem("l1")
+    n = len(y)
+    folds = np.random.default_rng(17).permutation(n) % 3
+    masks = [(folds != f).astype(np.float64) for f in range(3)]
+    nes = [int(m.sum()) for m in masks]
+    bounds = split_bounds(split)
+
+    def specs(lo, hi):
+        return [dict(points=np.asarray(pts), row_weight=masks[f][lo:hi].copy(), n_eff=nes[f]) for f in range(3)]
+
+    def work(r, eng):
+        lo, hi = bounds[r]
+        with eng.dataset(X[lo:hi], y[lo:hi]) as ds:
+            ds.set_global_rows(n)
+            return ds.solve_lanes(specs(lo, hi), tol=1e-10, flags=_engine.FLAG_WORKING_SET)
+
+    out, counts, _ = _run_ranks(len(split), work)
+    assert len(set(counts)) == 1 and counts[0] > 0
+    if "folds" not in _APPEND_CACHE:
+        with _engine.get_engine(0).dataset(X, y) as ds:
+            _APPEND_CACHE["folds"] = ds.solve_lanes(specs(0, n), tol=1e-10, flags=_engine.FLAG_WORKING_SET)
+    ref = _APPEND_CACHE["folds"]
+    for r in range(len(split)):
+        for f in range(3):
+            res = out[r][f]
+            what = f"fold {f}, rank {r} of {split}"
+            assert res.converged and ref[f].converged, what
+            assert res.ws_appends > 0 and res.ws_misses > 0, (what, res.ws_appends, res.ws_misses)
+            assert_certified(res, pts, X=X, y=y, tol=1e-10, row_weight=masks[f], n_eff=nes[f])
+            assert np.max(np.abs(res.betas - ref[f].betas)) <= 1e-8 * np.max(np.abs(ref[f].betas)), what
+            assert np.array_equal(res.betas, out[0][f].betas), f"{what}: not rank 0's bits"
