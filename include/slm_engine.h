@@ -846,7 +846,8 @@ int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* cons
  * row-sharded dataset (SLM_ERR_UNSUPPORTED); a negative or non-finite alphas[e] or etas[e], big_M < 0, n_cells < 1,
  * n_starts < 1, n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS = 8192, a start outside the box (SLM_ERR_BAD_ARG).
  * Not here: groups and a hierarchy, an l1 term, a Tikhonov matrix, constraints.  Row sets (CV folds) in the launch:
- * slm_solve_l0_local_folds, below; a bound on the cardinality: slm_solve_l0_local_subsets, below.
+ * slm_solve_l0_local_folds, below; a bound on the cardinality: slm_solve_l0_local_subsets, below.  (Groups and a hierarchy:
+ * slm_solve_l0_local_groups, below.)
  */
 #define SLM_L0_LOCAL_PMAX 1024
 #define SLM_L0_LOCAL_MAX_PROBLEMS 8192
@@ -881,6 +882,7 @@ int slm_solve_l0_local_descent(slm_dataset* ds, int32_t n_cells, const double* a
  * count * n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS (the message names the three factors).  A row set that gives the
  * ones column no weight is refused once its Gram is there.
  * Not here: groups, an l1 term, more than 16 row sets.  (A bound on the cardinality: slm_solve_l0_local_subsets.)
+ * (Groups and a hierarchy: slm_solve_l0_local_groups.)
  */
 int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                              const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
@@ -917,7 +919,8 @@ int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const
  * Refusals, all before a device is touched, in this order: NULL sizes or etas; a size < 1; a negative or non-finite eta; then
  * those of slm_solve_l0_local_folds for the row sets, the problem counts, big_M, the width, the intercept column, the weights
  * and the box of the starts.
- * Not here: groups, hierarchy, Tikhonov matrix, l1 term, constraints.
+ * Not here: groups, hierarchy, Tikhonov matrix, l1 term, constraints.  (Groups and a hierarchy in the penalised form:
+ * slm_solve_l0_local_groups, below.)
  */
 int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                                const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const int32_t* sizes,
@@ -926,6 +929,55 @@ int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const double* con
                                double* beta_out /* count * n_cells * ps */, double* intercept_out /* count * n_cells, or NULL */,
                                double* objective_out /* count * n_cells */, int32_t* start_out /* or NULL */,
                                int32_t* stat_out /* count * n_cells * n_starts * 6, or NULL */, slm_point_info* info /* count * n_cells, or NULL */);
+
+/*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_local_folds, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs it looks the symbol up.)  LOCAL SEARCH WITH GROUPS AND A HIERARCHY
+ * (csrc/l0_local_group_kernels.hpp): what the three entries above refuse.  The groups are the dataset's
+ * (slm_dataset_set_groups) and must be CONTIGUOUS and ASCENDING in column order -- the group index starts at 0 and rises by 0
+ * or 1 from a column to the next; the caller orders the columns.  need_ptr / need_idx: the hierarchy as a CSR list of the groups
+ * each search group needs directly (need_ptr NULL: none); the host closes it transitively, a group is never in its own closed
+ * list, so cycles are legal.  For cell e, with G, c as for slm_solve_l0_local and H = G + 2 etas[e] I,
+ *       minimise over beta, |beta_j| <= big_M:   F(beta) = 1/2 beta^T H beta - c^T beta + alphas[e] |cl(S(beta))|
+ * S(beta) the groups that hold a non-zero coefficient, cl its closure under the hierarchy: slm_solve_l0's objective with
+ * max_groups = n_groups and T = I; with singleton groups and no hierarchy slm_solve_l0_local's F, and its rule.  NOTHING IS
+ * PROVEN.  The rule, with r, d, b, gain and tol as for slm_solve_l0_local; per group nz_g (non-zero coefficients), held_g (the
+ * groups h != g with nz_h > 0 that need g), z_g = (nz_g > 0 or held_g > 0), and the price of a group that is empty or has just
+ * been emptied, m_g = [held_g == 0] (1 + #{h in need*(g): nz_h == 0 and held_h == 0}), what entering adds to |cl(S)|:
+ *   1. Group descent, g = 0 .. n_groups-1 cyclically.  A group with z_g = 1 gets a step, an inactive one only when it passes the
+ *      screen C_g = sum_{j in g, d_j > 0} gain(r_j, d_j) > alpha m_g / 4.  THE SCREEN IS A HEURISTIC: a block's gain has no bound
+ *      in terms of its coordinates' gains, so it can miss a group that would have paid.  The step: up to 8 passes beta_j <- b_j
+ *      over the group's columns (ascending, no threshold; d_j <= 1e-12 max d stays 0), ended by a pass with
+ *      max |delta| sqrt(d) <= tol; then v_g = 1/2 beta_g^T (r_g + r'_g), r' = r + sum_{j in g} H[:, j] beta_j; the group is kept iff
+ *      v_g > alpha m_g (strictly), else beta_g <- 0 and r <- r'.  A sweep ends the descent when no group entered or left and
+ *      max |delta| sqrt(d) <= tol over the kept steps; 10000 sweeps end it unconverged.
+ *   2. Group swap scan (swaps != 0): i ascending over the groups with nz_i > 0 and held_i == 0.  With i removed (v_i, m_i), the
+ *      candidate j is the empty group other than i with the largest C_j - alpha m_j (ties: the lowest j); it is fitted from zero
+ *      by the inner passes (v_j); if v_j - alpha m_j > v_i - alpha m_i + 1e-10 max(|v_i|, alpha) the swap stands and the rule
+ *      returns to 1, else beta and r are restored exactly.  No swap ends the problem; 10000 accepted swaps end it unconverged.
+ * A start may have any support, closed or not.  Every accepted move lowers F.  Row sets, intercept (the ones column last and
+ * alone in the last group: it and its group are not searched, so need_ptr has (groups - 1) + 1 entries), starts, problem order
+ * and the winner per (row set, cell) by (F, then the lowest start) as for slm_solve_l0_local_folds.  The winner is re-solved
+ * exactly inside the box on ALL columns of the groups in cl(S) (a group that is only held is free to use);
+ * objective_out = quad + alphas[e] |cl(S)| of the coefficients that go back; group_support_out (may be NULL): cl(S), one int per
+ * search group.  stat_out (may be NULL): SIX ints per problem -- sweeps, accepted swaps, status word, |cl(S)|, non-zero columns,
+ * group trials (fits of a group that was not in cl(S), and of swap candidates).  info as for slm_solve_l0_local_folds, mode = 9.
+ * Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when some winner reached a cap.
+ * Refusals, all before a device is touched, each with its own message: those of slm_solve_l0_local_folds except the one about
+ * groups; groups that are not contiguous or not ascending (SLM_ERR_UNSUPPORTED: the caller must order the columns); a need_ptr
+ * that does not start at 0 or falls, a need_idx outside the search groups (SLM_ERR_BAD_ARG); a row-sharded dataset.
+ * Not here: groups in the cardinality form, an l1 term, a Tikhonov matrix, constraints, seeding the exact search.
+ */
+int slm_solve_l0_local_groups(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
+                              const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
+                              const double* etas /* [n_cells] each */, double big_M,
+                              const int32_t* need_ptr /* search groups + 1, or NULL */, const int32_t* need_idx, int32_t n_starts,
+                              const double* starts /* count * n_cells * n_starts * ps, or NULL: one zero start */, int32_t swaps,
+                              double* beta_out /* count * n_cells * ps */, double* intercept_out /* count * n_cells, or NULL */,
+                              double* objective_out /* count * n_cells */, int32_t* start_out /* or NULL */,
+                              int32_t* group_support_out /* count * n_cells * search groups, or NULL: cl(S) */,
+                              int32_t* stat_out /* 6 per problem: sweeps, swaps, status word, |cl(S)|, non-zero columns, group trials; or NULL */,
+                              slm_point_info* info /* count * n_cells, or NULL */);
 
 /*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant

@@ -604,6 +604,67 @@ py::tuple solve_l0_local_subsets(uintptr_t ds, int64_t p, int64_t n, const py::s
   return l0_local_rows(ds, p, n, row_weights, n_effs, intercept, n_cells, nullptr, sizes.data(), etas, big_M, n_starts, starts, swaps);
 }
 
+// slm_solve_l0_local_groups: the local search with groups and a hierarchy.  need_ptr / need_idx: None or int32 arrays (need_ptr
+// with one entry per search group and one more: checked by the caller, sparselm_amd/_engine.py).  Returns (coefficients
+// [count * n_cells][ps], intercepts, objectives, winning starts, cl(S) [count * n_cells][search groups], the six status words
+// of every problem, records as bytes, status).
+py::tuple solve_l0_local_groups(uintptr_t ds, int64_t p, int64_t n, int64_t n_groups, const py::sequence& row_weights,
+                                const py::sequence& n_effs, bool intercept, int32_t n_cells, const arr_d& alphas, const arr_d& etas,
+                                double big_M, const py::object& need_ptr, const py::object& need_idx, int32_t n_starts,
+                                const py::object& starts, bool swaps) {
+  using arr_i = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+  const py::ssize_t count = (py::ssize_t)py::len(row_weights);
+  if ((py::ssize_t)py::len(n_effs) != count) throw py::value_error("row_weights and n_effs differ in length");
+  const int64_t cells = n_cells > 0 ? n_cells : 0;
+  if ((int64_t)alphas.size() < cells || (int64_t)etas.size() < cells) throw py::value_error("alphas and etas must have n_cells entries");
+  const int64_t drop = intercept ? 1 : 0, ps = p > drop ? p - drop : 0, gs = n_groups > drop ? n_groups - drop : 0;
+  arr_i ptr_a, idx_a;
+  const int32_t *pp = nullptr, *ip = nullptr;
+  if (!need_ptr.is_none()) {
+    ptr_a = arr_i::ensure(need_ptr);
+    if (!ptr_a || (int64_t)ptr_a.size() != gs + 1) throw py::value_error("need_ptr must have one entry per search group and one more");
+    pp = ptr_a.data();
+  }
+  if (!need_idx.is_none()) {
+    idx_a = arr_i::ensure(need_idx);
+    if (!idx_a) throw py::value_error("need_idx is not convertible to int32");
+    for (int64_t g = 0; pp && g <= gs; ++g)
+      if ((int64_t)pp[g] > (int64_t)idx_a.size()) throw py::value_error("need_idx is shorter than need_ptr says");
+    ip = idx_a.data();
+  }
+  // (no row set, no cell, more problems than any call takes: the engine refuses them, the outputs only have to exist)
+  const bool sized = count >= 1 && count <= 16 && n_cells >= 1 && n_starts >= 1 && (int64_t)n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS &&
+                     (int64_t)count * n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS;
+  Keep keep;
+  const double* sp = sized ? vector_arg(starts, (int64_t)count * n_cells * n_starts * ps, "starts", keep) : nullptr;
+  std::vector<const double*> wp((size_t)count);
+  std::vector<int64_t> ne((size_t)count);
+  for (py::ssize_t b = 0; b < count; ++b) {
+    wp[(size_t)b] = vector_arg(row_weights[b], n, "row_weights", keep);
+    ne[(size_t)b] = n_effs[b].cast<int64_t>();
+  }
+  const py::ssize_t cnt = sized ? count * n_cells : 1, problems = sized ? cnt * n_starts : 1, gw = gs > 0 ? (py::ssize_t)gs : 1;
+  py::array_t<double> beta({cnt, (py::ssize_t)ps}), icpt(cnt), objective(cnt);
+  py::array_t<int32_t> winner(cnt), gsup({cnt, gw}), stats({problems, (py::ssize_t)6});
+  py::array info = info_bytes(cnt);
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
+  double *bp = beta.mutable_data(), *cp = icpt.mutable_data(), *op = objective.mutable_data();
+  int32_t *wn = winner.mutable_data(), *gp = gsup.mutable_data(), *tp = stats.mutable_data();
+  std::memset(wn, 0, sizeof(int32_t) * (size_t)cnt);
+  std::memset(gp, 0, sizeof(int32_t) * (size_t)cnt * (size_t)gw);
+  std::memset(tp, 0, sizeof(int32_t) * 6 * (size_t)problems);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    auto* d = reinterpret_cast<slm_dataset*>(ds);
+    rc = slm_solve_l0_local_groups(d, (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, n_cells, alphas.data(), etas.data(), big_M, pp, ip,
+                                   n_starts, sp, swaps ? 1 : 0, bp, cp, op, wn, gp, tp, rec);
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, icpt, objective, winner, gsup, stats, info, rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_slm_binding, m) {
@@ -634,6 +695,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_local_descent", &solve_l0_local<false>);
   m.def("solve_l0_local_folds", &solve_l0_local_folds);
   m.def("solve_l0_local_subsets", &solve_l0_local_subsets);
+  m.def("solve_l0_local_groups", &solve_l0_local_groups);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

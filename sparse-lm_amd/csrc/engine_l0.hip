@@ -36,11 +36,13 @@
 // Beside them, and none of the above: the local search beyond 128 columns, which proves nothing (csrc/l0_local_kernels.hpp) --
 // four entries, ONE body at the end of the unit (solve_l0_local_folds_impl): slm_solve_l0_local_folds, the search on up to 16 row sets
 // of the dataset in one launch; slm_solve_l0_local and slm_solve_l0_local_descent, that call with one row set, the dataset's own
-// rows; slm_solve_l0_local_subsets, that call with the kernel's cardinality rule: sizes where the alphas are.
+// rows; slm_solve_l0_local_subsets, that call with the kernel's cardinality rule: sizes where the alphas are.  (A fifth entry on that
+// body, with its own kernel: slm_solve_l0_local_groups, the search with groups and a hierarchy -- csrc/l0_local_group_kernels.hpp.)
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
 #include "l0_local_kernels.hpp"
+#include "l0_local_group_kernels.hpp"
 
 namespace {
 
@@ -873,6 +875,11 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
 //                               l0_local_kernel<true> (the cardinality rule), the sizes travel as ints where the alphas did, the
 //                               objective has no alpha term (Q after the polish), and stat_out holds six words per problem:
 //                               grows and drops behind the four
+//   slm_solve_l0_local_groups   the FOURTH kind (L0_LOCAL_GROUPS), the only one that goes on with groups: after the shared check
+//                               l0_lg_check decides the group order and the need lists; gstart and the CLOSED lists (l0_lg_close) go up
+//                               in a block of their own; the launch is l0_local_group_kernel; a winner is polished on every column of
+//                               the groups in cl(S) (l0_ls_polish_on; l0_fetch_rows fetches those groups' rows only); the objective
+//                               is quad + alpha |cl(S)| of the coefficients that go back; six status words (L0_LG_STATS); mode 9
 // check (l0_lsf_check -- at one row set l0_ls_check's refusals in l0_ls_check's order -- and the dataset's shape, before a device
 // is touched); the Grams FILED, not fetched: as in solve_l0_profile_grid_impl (one slm_dataset_covariance_folds call when every
 // row set brings its weights, else one by one; found again by fingerprint), each HELD for the call, so that a later build
@@ -893,11 +900,16 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
 // loss as for solve_l0.  Nothing here is proven optimal, whatever the status.  Non-finite data is refused where it shows:
 // X^T y before the launch, the winners' Gram rows after it.
 static_assert(SLM_L0_LOCAL_PMAX == L0_LS_PMAX && SLM_L0_LOCAL_MAX_PROBLEMS == L0_LS_MAX_PROBLEMS, "the header and the host logic name one set of limits");
-enum L0LocalKind { L0_LOCAL_ONE, L0_LOCAL_SETS, L0_LOCAL_SIZES };  // slm_solve_l0_local[_descent]; _folds; _subsets
+enum L0LocalKind { L0_LOCAL_ONE, L0_LOCAL_SETS, L0_LOCAL_SIZES, L0_LOCAL_GROUPS };  // slm_solve_l0_local[_descent]; _folds; _subsets; _groups
+struct L0LocalGroups {  // what only slm_solve_l0_local_groups brings: the direct need lists (CSR over the search groups) and cl(S) out
+  const int32_t *need_ptr, *need_idx;
+  int32_t* group_support_out;
+};
 int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
                               int32_t intercept, int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
                               int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
-                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info);
+                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info,
+                              const L0LocalGroups* lg = nullptr);
 
 // slm_solve_l0_local, slm_solve_l0_local_descent: the body below on one row set, the dataset's own rows
 int solve_l0_local_impl(int32_t swaps, slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
@@ -912,9 +924,11 @@ int solve_l0_local_impl(int32_t swaps, slm_dataset* ds, int32_t n_cells, const d
 int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
                               int32_t intercept, int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
                               int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
-                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
+                              double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info,
+                              const L0LocalGroups* lg) {
   if (!ds || !beta_out || !objective_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  const bool card = kind == L0_LOCAL_SIZES, one = kind == L0_LOCAL_ONE;
+  const bool card = kind == L0_LOCAL_SIZES, one = kind == L0_LOCAL_ONE, grouped = kind == L0_LOCAL_GROUPS;
+  if (grouped && !lg) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   const int drop = intercept != 0 ? 1 : 0;
   bool alone = ds->p >= 1;  // the ones column: last, alone in the last group
   if (drop && !ds->singleton) {
@@ -965,8 +979,33 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
         default: return fail(SLM_ERR_BAD_ARG, "NULL argument");
       }
   }
-  if (!ds->singleton) return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for groups: every column must be its own group");
+  if (!grouped && !ds->singleton)
+    return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for groups: every column must be its own group");
+  // (the grouped kind alone goes on with groups: l0_lg_check repeats the check above, which has passed, and decides the rest)
+  int ngs = (int)ds->p - drop;  // the groups of the searched columns
+  std::vector<int> gstart, cptr, cidx;
+  if (grouped) {
+    const int* gid = ds->singleton || ds->h_gid.empty() ? nullptr : ds->h_gid.data();
+    const L0LgRefusal Q = l0_lg_check(count, row_weights, reinterpret_cast<const long long*>(n_effs), ds->n, drop != 0, alone, n_cells, alphas,
+                                      etas, big_M, n_starts, starts, ds->p, gid, lg->need_ptr, lg->need_idx, row_sharded(ds), &ngs);
+    switch (Q.kind) {
+      case L0_LG_OK: break;
+      case L0_LG_ORDER:
+        return fail(SLM_ERR_UNSUPPORTED, "the grouped l0 local search takes groups that are contiguous and ascending in column order "
+                    "(column %lld breaks it): the caller must order the columns by group", Q.which);
+      case L0_LG_NEED_PTR: return fail(SLM_ERR_BAD_ARG, "need_ptr must start at 0 and never fall (entry %lld)", Q.which);
+      case L0_LG_NEED_IDX: return fail(SLM_ERR_BAD_ARG, "need_idx[%lld] must name one of the %d search groups", Q.which, ngs);
+      case L0_LG_SHARDED: break;  // (in the family's words, below)
+      default: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    }
+  }
   if (row_sharded(ds)) return fail(SLM_ERR_UNSUPPORTED, "the l0 local search is not built for row-sharded datasets");
+  if (grouped) {
+    const int psearch = (int)ds->p - drop;
+    gstart.assign((size_t)ngs + 1, psearch);
+    for (int j = psearch - 1; j >= 0; --j) gstart[(size_t)(ds->singleton || ds->h_gid.empty() ? j : ds->h_gid[(size_t)j])] = j;
+    l0_lg_close(ngs, lg->need_ptr, lg->need_idx, cptr, cidx);
+  }
   const int p = (int)ds->p, ps = p - drop, per_set = n_cells * n_starts, problems = count * per_set;
   const int64_t n = ds->n;
   const size_t ld = (size_t)ds->ld;
@@ -1040,7 +1079,7 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
 
   // ---- one block: alphas | etas | starts | the eliminated c, then what comes back: F | the four status words | beta; the workspace --------
   // (the cardinality rule: the sizes, as ints, lie where the alphas did; six status words)
-  const int nstat = card ? 6 : 4;
+  const int nstat = card ? 6 : (grouped ? L0_LG_STATS : 4);
   const size_t n_start_words = starts ? (size_t)problems * ps : 0, n_c_words = drop ? (size_t)count * ld : 0;
   const size_t off_eta = (size_t)n_cells, off_st = 2 * (size_t)n_cells, off_c = off_st + n_start_words, off_F = off_c + n_c_words,
                off_stat = off_F + (size_t)problems, off_beta = off_stat + ((size_t)nstat * problems + 1) / 2, words = off_beta + (size_t)problems * ps;
@@ -1053,10 +1092,20 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
   memcpy(h.data() + off_eta, etas, sizeof(double) * (size_t)n_cells);
   if (starts) memcpy(h.data() + off_st, starts, sizeof(double) * n_start_words);
   if (drop) memcpy(h.data() + off_c, cs.data(), sizeof(double) * n_c_words);
-  unsigned long long *dev = nullptr, *ws = nullptr;
-  L0DevGuard guard{dev, s}, ws_guard{ws, s};
+  unsigned long long *dev = nullptr, *ws = nullptr, *gtab = nullptr;
+  L0DevGuard guard{dev, s}, ws_guard{ws, s}, gtab_guard{gtab, s};
   SLM_TRY(dalloc(&dev, words));
   if (drop) SLM_TRY(dalloc(&ws, (size_t)count * ws_stride));
+  // (the grouped kind: gstart | the closed lists' cptr | cidx, as ints in a block of their own)
+  std::vector<int> gh;
+  if (grouped) {
+    gh.insert(gh.end(), gstart.begin(), gstart.end());
+    gh.insert(gh.end(), cptr.begin(), cptr.end());
+    gh.insert(gh.end(), cidx.begin(), cidx.end());
+    gh.push_back(0);  // (cidx is never an empty pointer)
+    SLM_TRY(dalloc(&gtab, (gh.size() + 1) / 2));
+    HIP_TRY(hipMemcpyAsync(gtab, gh.data(), sizeof(int) * gh.size(), hipMemcpyHostToDevice, s));
+  }
   double *dd = reinterpret_cast<double*>(dev), *wd = reinterpret_cast<double*>(ws);
   std::vector<const double*> Gdev((size_t)count);
   {
@@ -1098,7 +1147,24 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
     // launched so that a CU whose problems end early takes up another workgroup, and the problems beyond 2 cus workgroups are reached
     // by the kernel's grid-stride loop)
     const int blocks = std::min((problems + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
-    if (!card)
+    if (grouped) {
+      L0LgArgs g;
+      memset(&g, 0, sizeof(g));
+      for (int b = 0; b < count; ++b) {
+        g.G[b] = k.G[b];
+        g.c[b] = k.c[b];
+        g.yy[b] = k.yy[b];
+      }
+      g.alphas = k.alphas; g.etas = k.etas; g.starts = k.starts;
+      g.gstart = reinterpret_cast<const int*>(gtab);
+      g.cptr = g.gstart + (ngs + 1);
+      g.cidx = g.cptr + (ngs + 1);
+      g.beta_out = k.beta_out; g.F_out = k.F_out; g.stat_out = k.stat_out;
+      g.ld = k.ld;
+      g.p = ps; g.ng = ngs; g.n_problems = problems; g.n_starts = n_starts; g.swaps = k.swaps; g.n_cells = n_cells;
+      g.big_M = big_M;
+      hipLaunchKernelGGL(l0_local_group_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, g);
+    } else if (!card)
       hipLaunchKernelGGL(l0_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
     else
       hipLaunchKernelGGL(l0_local_kernel<true>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
@@ -1113,6 +1179,7 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
   int unconverged = 0, first_set = -1, first_cell = -1;
   std::vector<int> win((size_t)n_cells), rows, at((size_t)std::max(ps, 1));
   std::vector<double> Grows, Gc, cc, bc;
+  std::vector<int> closed((size_t)std::max(ngs, 1), 0);  // (the grouped kind: cl(S) of a winner)
   for (int b = 0; b < count; ++b) {
     std::vector<char> used((size_t)std::max(ps, 1), 0);
     for (int cell = 0; cell < n_cells; ++cell) {
@@ -1122,7 +1189,12 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
         if (h[off_F + q0 + st] < h[off_F + q0 + w]) w = st;  // (ties: the lowest index)
       win[(size_t)cell] = w;
       const double* beta = h.data() + off_beta + (q0 + w) * ps;
-      for (int j = 0; j < ps; ++j) used[(size_t)j] = used[(size_t)j] || beta[j] != 0.0;
+      for (int j = 0; j < ps && !grouped; ++j) used[(size_t)j] = used[(size_t)j] || beta[j] != 0.0;
+      if (grouped) {  // every column of the groups in cl(S): the polish may use them all
+        l0_lg_closure(beta, ngs, gstart.data(), cptr.data(), cidx.data(), closed.data());
+        for (int g = 0; g < ngs; ++g)
+          for (int j = gstart[(size_t)g]; j < gstart[(size_t)g + 1] && closed[(size_t)g]; ++j) used[(size_t)j] = 1;
+      }
     }
     rows.clear();
     for (int j = 0; j < ps; ++j)
@@ -1147,7 +1219,22 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
       double* beta = beta_out + rc * ps;
       memcpy(beta, h.data() + off_beta + q * ps, sizeof(double) * (size_t)ps);
       for (int a = 0; a < m; ++a) bc[(size_t)a] = beta[rows[(size_t)a]];
-      const double quad = l0_ls_polish(Gc.data(), (size_t)m, cc.data(), m, etas[cell], big_M, bc.data());
+      double quad = 0.0;
+      if (!grouped) {
+        quad = l0_ls_polish(Gc.data(), (size_t)m, cc.data(), m, etas[cell], big_M, bc.data());
+      } else {
+        // on ALL columns of the groups in cl(S) -- a group that is only held is free to use -- but for those the rule leaves out
+        l0_lg_closure(beta, ngs, gstart.data(), cptr.data(), cidx.data(), closed.data());
+        double dmax = 0.0;
+        for (int a = 0; a < m; ++a) dmax = std::max(dmax, Gc[(size_t)a * m + a] + 2.0 * etas[cell]);
+        std::vector<int> on;
+        int g = 0;
+        for (int a = 0; a < m; ++a) {
+          while (gstart[(size_t)g + 1] <= rows[(size_t)a]) ++g;
+          if (closed[(size_t)g] && (bc[(size_t)a] != 0.0 || Gc[(size_t)a * m + a] + 2.0 * etas[cell] > L0_PIVOT * dmax)) on.push_back(a);
+        }
+        quad = l0_ls_polish_on(Gc.data(), (size_t)m, cc.data(), etas[cell], big_M, on, bc.data());
+      }
       int nnz = 0;
       double bn = 0.0, dot = 0.0;
       for (int a = 0; a < m; ++a) beta[rows[(size_t)a]] = bc[(size_t)a];
@@ -1157,6 +1244,11 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
         if (drop) dot += xmean[(size_t)b * ps + j] * beta[j];
       }
       objective_out[rc] = card ? quad : quad + alphas[cell] * (double)nnz;
+      if (grouped) {  // alpha |cl(S)| of the coefficients that go back
+        const int ncl = l0_lg_closure(beta, ngs, gstart.data(), cptr.data(), cidx.data(), closed.data());
+        objective_out[rc] = quad + alphas[cell] * (double)ncl;
+        if (lg->group_support_out) memcpy(lg->group_support_out + rc * (size_t)ngs, closed.data(), sizeof(int32_t) * (size_t)ngs);
+      }
       if (intercept_out) intercept_out[rc] = drop ? ymean[(size_t)b] - dot : 0.0;
       if (start_out) start_out[rc] = win[(size_t)cell];
       const bool done = stat[nstat * q + 2] == 0;
@@ -1170,7 +1262,7 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
         info[rc].rejects = stat[nstat * q + 1];
         info[rc].resid = (double)stat[nstat * q + 2];
         info[rc].beta_norm = std::sqrt(bn);
-        info[rc].mode = 8;
+        info[rc].mode = grouped ? 9 : 8;
       }
     }
   }
@@ -1203,6 +1295,19 @@ extern "C" int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const 
                                           double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info) {
   return solve_l0_local_folds_impl(L0_LOCAL_SIZES, ds, count, row_weights, n_effs, intercept, n_cells, nullptr, sizes, etas, big_M, n_starts,
                                    starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info);
+}
+
+// The l0 local search with groups and a hierarchy: every (row set, cell, start) problem from one launch of l0_local_group_kernel.
+// The groups are the dataset's (slm_dataset_set_groups), contiguous and ascending; the need lists are closed on the host
+// (l0_lg_close); the winner is polished on every column of the groups in cl(S); objective_out = quad + alpha |cl(S)|.
+extern "C" int slm_solve_l0_local_groups(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                                         int32_t intercept, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                         const int32_t* need_ptr, const int32_t* need_idx, int32_t n_starts, const double* starts,
+                                         int32_t swaps, double* beta_out, double* intercept_out, double* objective_out,
+                                         int32_t* start_out, int32_t* group_support_out, int32_t* stat_out, slm_point_info* info) {
+  const L0LocalGroups lg{need_ptr, need_idx, group_support_out};
+  return solve_l0_local_folds_impl(L0_LOCAL_GROUPS, ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, etas, big_M, n_starts,
+                                   starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info, &lg);
 }
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.

@@ -1363,10 +1363,16 @@ inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, in
 // descent of l0_boxed from beta, its face solve where the box binds, and where it does not the Cholesky solve of the whole
 // support, taken when the factor exists under the pivot rule and the point is inside the box.  beta: [p] in, out (the support
 // is kept: zeros stay zero).  Returns 1/2 beta^T H beta - c^T beta, without the alpha term.
+// (l0_ls_polish_on: the same on a given column list, whose zeros are free to move -- the grouped search polishes on every column
+// of the groups in cl(S), "local groups" below)
+inline double l0_ls_polish_on(const double* G, size_t ld, const double* c, double eta, double big_M, const std::vector<int>& cols, double* beta);
 inline double l0_ls_polish(const double* G, size_t ld, const double* c, int p, double eta, double big_M, double* beta) {
   std::vector<int> cols;
   for (int j = 0; j < p; ++j)
     if (beta[j] != 0.0) cols.push_back(j);
+  return l0_ls_polish_on(G, ld, c, eta, big_M, cols, beta);
+}
+inline double l0_ls_polish_on(const double* G, size_t ld, const double* c, double eta, double big_M, const std::vector<int>& cols, double* beta) {
   const int m = (int)cols.size();
   if (m == 0) return 0.0;
   std::vector<double> Hs((size_t)m * m), cs((size_t)m), b((size_t)m);
@@ -1564,6 +1570,313 @@ inline bool l0_eliminate_last_ld(const double* G, size_t ld, const double* c, in
   for (int i = 0; i < q; ++i)
     for (int j = 0; j < q; ++j) Gs[(size_t)i * lds + j] = G[(size_t)i * ld + j] - g1[(size_t)i] * g1[(size_t)j] / g11;
   return true;
+}
+
+// ---- local groups: the local search with groups and a hierarchy (slm_solve_l0_local_groups; csrc/l0_local_group_kernels.hpp;
+// tests/l0_local_groups_host_test.cpp) -----------------------------------------------------------------------------------------
+//
+// For a cell (alpha, eta), H = G + 2 eta I:
+//     F(beta) = 1/2 beta^T H beta - c^T beta + alpha |cl(S(beta))|   over |beta_j| <= big_M,
+// S(beta) the groups that hold a non-zero coefficient, cl its closure under the hierarchy (S and every group its members need,
+// transitively): slm_solve_l0's objective with max_groups = n_groups and T = I.  Nothing is proven (DESIGN 4d "Local search with
+// groups").  Groups are CONTIGUOUS and ASCENDING in column order: group g is the columns gstart[g] .. gstart[g + 1] - 1.  The
+// hierarchy is the CLOSED list need*(g) per group in CSR form (l0_lg_close; g itself is not in it, so cycles are legal).
+//
+// The state: beta, r = c - H beta, d = diag H as for the local search; per group nz_g (its non-zero coefficients) and held_g (the
+// groups h != g with nz_h > 0 that need g); z_g = (nz_g > 0 or held_g > 0) says whether g is in cl(S).  The PRICE of a group
+// that is empty -- or of a non-empty one as if it had just been emptied -- is what |cl(S)| changes by when it enters (leaves):
+//     m_g = [held_g == 0] (1 + #{h in need*(g): nz_h == 0 and held_h == 0 without g's own hold}).
+//   1. Group descent, g = 0 .. n_groups - 1 cyclically.  A group with z_g = 1 gets a step; an inactive one only when it passes
+//      the screen C_g = sum_{j in g, d_j > 0} gain(r_j, d_j) > alpha m_g / L0_LG_SCREEN.  The step: up to L0_LG_INNER passes of
+//      beta_j <- b_j over the group's columns in ascending order, no threshold (a column with d_j <= 1e-12 max d stays 0), ended by
+//      a pass whose max |delta| sqrt(d) <= tol; then the group's value v_g = 1/2 beta_g^T (r_g + r'_g) with
+//      r' = r + sum_{j in g} H[:, j] beta_j (exact for any beta_g); the group is kept iff v_g > alpha m_g (strictly), else
+//      beta_g <- 0 and r <- r'.  A sweep ends the descent when no group entered or left and the kept steps' max |delta| sqrt(d)
+//      <= tol; L0_CD_SWEEPS sweeps end it unconverged.
+//   2. Group swap scan (unless swaps == 0): i ascending over the groups with nz_i > 0 and held_i == 0.  i is removed (v_i, m_i,
+//      r'); the candidate j is the empty group other than i with the largest C_j(r') - alpha m_j (prices in the state without i;
+//      ties: the lowest j); j is fitted from zero by the inner passes (v_j); the swap is accepted iff
+//      v_j - alpha m_j > v_i - alpha m_i + L0_LS_SWAP_TOL max(|v_i|, alpha) and the rule returns to 1; else beta and r are
+//      restored from saved copies and the scan goes on.  No swap ends the problem; L0_LS_SWAPS accepted swaps end it unconverged.
+// A start may have any support, closed or not; F always counts |cl(S)|.  Every accepted move lowers F.  With singleton groups
+// and no hierarchy this is the local search's rule: v_g is the coordinate's gain, m_g = 1, the screen lets through every column
+// the threshold would.
+constexpr double L0_LG_SCREEN = 4.0;  // A HEURISTIC: the gain of a block has no bound in terms of its coordinates' gains at the
+                                      // current r (two columns that cancel each other's correlation with r can gain together what
+                                      // neither shows alone), so a group below the screen can be one that would have paid
+constexpr int L0_LG_INNER = 8;        // passes over a group's columns in one step
+constexpr int L0_LG_STATS = 6;        // ints per problem: sweeps, swaps, status word, |cl(S)|, non-zero columns, group trials
+
+// need*(g) for every group from the direct lists (CSR: need_ptr [ng + 1], need_idx; NULL: no hierarchy): everything reachable
+// from g, without g itself, ascending.  The indices must lie in 0 .. ng - 1 (l0_lg_check).
+inline void l0_lg_close(int ng, const int* need_ptr, const int* need_idx, std::vector<int>& cptr, std::vector<int>& cidx) {
+  cptr.assign((size_t)ng + 1, 0);
+  cidx.clear();
+  if (!need_ptr) return;
+  std::vector<char> seen((size_t)ng);
+  std::vector<int> stack;
+  for (int g = 0; g < ng; ++g) {
+    std::fill(seen.begin(), seen.end(), 0);
+    stack.assign(1, g);
+    while (!stack.empty()) {
+      const int h = stack.back();
+      stack.pop_back();
+      for (int k = need_ptr[h]; k < need_ptr[h + 1]; ++k) {
+        const int t = need_idx[k];
+        if (seen[(size_t)t]) continue;
+        seen[(size_t)t] = 1;
+        stack.push_back(t);
+      }
+    }
+    for (int h = 0; h < ng; ++h)
+      if (seen[(size_t)h] && h != g) cidx.push_back(h);
+    cptr[(size_t)g + 1] = (int)cidx.size();
+  }
+}
+
+// cl(S) of a coefficient vector: in[g] = 1 where group g holds a non-zero or is needed by one that does.  Returns |cl(S)|.
+inline int l0_lg_closure(const double* beta, int ng, const int* gstart, const int* cptr, const int* cidx, int* in) {
+  for (int g = 0; g < ng; ++g) in[g] = 0;
+  for (int g = 0; g < ng; ++g) {
+    bool any = false;
+    for (int j = gstart[g]; j < gstart[g + 1]; ++j) any = any || beta[j] != 0.0;
+    if (!any) continue;
+    in[g] = 1;
+    for (int k = cptr[g]; k < cptr[g + 1]; ++k) in[cidx[k]] = 1;
+  }
+  int count = 0;
+  for (int g = 0; g < ng; ++g) count += in[g];
+  return count;
+}
+
+struct L0LgResult {
+  double F = 0.0;  // the objective at the returned beta, with alpha |cl(S)|
+  int sweeps = 0, swaps = 0, status = 0, closed = 0, nnz = 0, trials = 0;  // (trials: fits of a group that was not in cl(S), or of a swap's candidate)
+  long long changes = 0;  // columns of H applied to r or r' after the start: what the time goes to
+};
+
+// The rule on one problem: the kernel's twin, l0_local_group_kernel without a device.  G: [p][ld] (symmetric), c: [p]; 2 eta goes
+// on the diagonal here.  gstart: [ng + 1]; cptr, cidx: the CLOSED lists (cptr may be NULL: no hierarchy).  start: [p] inside the
+// box or NULL; beta: [p] out.
+inline L0LgResult l0_lg_solve(const double* G, size_t ld, const double* c, int p, int ng, const int* gstart, const int* cptr, const int* cidx,
+                              double alpha, double eta, double big_M, double yy, bool swaps, const double* start, double* beta) {
+  L0LgResult R;
+  std::vector<double> r(c, c + p), d((size_t)p), rp((size_t)p), sb((size_t)p), sr((size_t)p);
+  std::vector<int> nz((size_t)ng, 0), held((size_t)ng, 0);
+  const double eta2 = 2.0 * eta;
+  double dmax = 0.0;
+  for (int j = 0; j < p; ++j) {
+    d[(size_t)j] = G[(size_t)j * ld + j] + eta2;
+    dmax = std::max(dmax, d[(size_t)j]);
+  }
+  for (int j = 0; j < p; ++j) {
+    if (!(d[(size_t)j] > L0_PIVOT * dmax)) d[(size_t)j] = 0.0;  // (0 marks a column that stays out)
+    beta[j] = start && d[(size_t)j] > 0.0 ? start[j] : 0.0;
+  }
+  auto axpy = [&](std::vector<double>& x, int j, double w) {  // x += w H[:, j]
+    const double* row = G + (size_t)j * ld;
+    for (int k = 0; k < p; ++k) x[(size_t)k] += w * (k == j ? row[k] + eta2 : row[k]);
+    ++R.changes;
+  };
+  for (int j = 0; j < p; ++j)
+    if (beta[j] != 0.0) axpy(r, j, -beta[j]);
+  R.changes = 0;  // (the start is not counted)
+  const double tol = L0_CD_TOL * std::sqrt(yy);
+  auto first = [&](int g) { return cptr ? cptr[g] : 0; };
+  auto last = [&](int g) { return cptr ? cptr[g + 1] : 0; };
+  auto count = [&](int g) {
+    int n = 0;
+    for (int j = gstart[g]; j < gstart[g + 1]; ++j) n += beta[j] != 0.0;
+    return n;
+  };
+  auto hold = [&](int g, int by) {
+    for (int k = first(g); k < last(g); ++k) held[(size_t)cidx[k]] += by;
+  };
+  auto price = [&](int g) {  // m_g: of an empty group, or of a non-empty one as if it had just been emptied
+    if (held[(size_t)g] > 0) return 0;
+    const int own = nz[(size_t)g] > 0 ? 1 : 0;  // (its own hold on the groups it needs)
+    int m = 1;
+    for (int k = first(g); k < last(g); ++k) m += nz[(size_t)cidx[k]] == 0 && held[(size_t)cidx[k]] == own;
+    return m;
+  };
+  auto gains = [&](int g) {  // C_g, summed in ascending column order
+    double C = 0.0;
+    for (int j = gstart[g]; j < gstart[g + 1]; ++j) C += d[(size_t)j] > 0.0 ? l0_ls_coord(r[(size_t)j], d[(size_t)j], big_M).gain : 0.0;
+    return C;
+  };
+  auto fit = [&](int g, bool& changed) {  // the inner passes; the largest |delta| sqrt(d) of any of them
+    double worst = 0.0;
+    for (int pass = 0; pass < L0_LG_INNER; ++pass) {
+      double mp = 0.0;
+      for (int j = gstart[g]; j < gstart[g + 1]; ++j) {
+        const double dj = d[(size_t)j];
+        if (!(dj > 0.0)) continue;
+        const double b = l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M).b, delta = b - beta[j];
+        if (delta == 0.0) continue;
+        beta[j] = b;
+        axpy(r, j, -delta);
+        changed = true;
+        mp = std::max(mp, std::fabs(delta) * std::sqrt(dj));
+      }
+      worst = std::max(worst, mp);
+      if (mp <= tol) break;
+    }
+    return worst;
+  };
+  auto value = [&](int g) {  // v_g; rp <- r'
+    rp = r;
+    for (int j = gstart[g]; j < gstart[g + 1]; ++j)
+      if (beta[j] != 0.0) axpy(rp, j, beta[j]);
+    double v = 0.0;
+    for (int j = gstart[g]; j < gstart[g + 1]; ++j) v += beta[j] * (r[(size_t)j] + rp[(size_t)j]);
+    return 0.5 * v;
+  };
+  auto empty = [&](int g) {  // beta_g <- 0, r <- r'
+    for (int j = gstart[g]; j < gstart[g + 1]; ++j) beta[j] = 0.0;
+    r = rp;
+  };
+  for (int g = 0; g < ng; ++g) nz[(size_t)g] = count(g);
+  for (int g = 0; g < ng; ++g)
+    if (nz[(size_t)g] > 0) hold(g, 1);
+  for (;;) {
+    // ---- 1. the group descent to its fixed point ------------------------------------------------------------------------------
+    for (int sw = 0;; ++sw) {
+      if (sw == L0_CD_SWEEPS) {
+        R.status |= L0_LS_SWEEPS_OUT;
+        break;
+      }
+      bool moved = false;
+      double maxd = 0.0;
+      for (int g = 0; g < ng; ++g) {
+        const bool was = nz[(size_t)g] > 0;
+        const int m = price(g);
+        if (!was && held[(size_t)g] == 0) {
+          if (!(gains(g) > alpha * (double)m / L0_LG_SCREEN)) continue;
+          ++R.trials;
+        }
+        bool changed = false;
+        const double w = fit(g, changed);
+        const double v = value(g);
+        if (v > alpha * (double)m) {
+          const int now = count(g);
+          if ((now > 0) != was) {
+            hold(g, now > 0 ? 1 : -1);
+            moved = true;
+          }
+          nz[(size_t)g] = now;
+          maxd = std::max(maxd, w);
+        } else {
+          empty(g);
+          nz[(size_t)g] = 0;
+          if (was) {
+            hold(g, -1);
+            moved = true;
+          }
+        }
+      }
+      ++R.sweeps;
+      if (!moved && maxd <= tol) break;
+    }
+    if (!swaps || R.status) break;
+    // ---- 2. the group swap scan: the first i that an empty group replaces with a gain --------------------------------------------
+    bool swapped = false;
+    for (int i = 0; i < ng && !swapped; ++i) {
+      if (nz[(size_t)i] == 0 || held[(size_t)i] > 0) continue;
+      std::copy(beta, beta + p, sb.begin());
+      sr = r;
+      const int nzi = nz[(size_t)i], mi = price(i);
+      const double vi = value(i);
+      empty(i);
+      nz[(size_t)i] = 0;
+      hold(i, -1);
+      int jb = -1;
+      double best = -HUGE_VAL;
+      for (int j = 0; j < ng; ++j) {
+        if (j == i || nz[(size_t)j] > 0) continue;
+        const double score = gains(j) - alpha * (double)price(j);
+        if (score > best) {  // (ties: the lowest j)
+          best = score;
+          jb = j;
+        }
+      }
+      bool ok = false;
+      if (jb >= 0) {
+        const int mj = price(jb);
+        bool changed = false;
+        ++R.trials;
+        fit(jb, changed);
+        const double vj = value(jb), a = std::fabs(vi);
+        ok = vj - alpha * (double)mj > vi - alpha * (double)mi + L0_LS_SWAP_TOL * (a > alpha ? a : alpha);
+      }
+      if (ok) {
+        nz[(size_t)jb] = count(jb);
+        if (nz[(size_t)jb] > 0) hold(jb, 1);
+        ++R.swaps;
+        swapped = true;
+      } else {
+        std::copy(sb.begin(), sb.end(), beta);
+        r = sr;
+        nz[(size_t)i] = nzi;
+        hold(i, 1);
+      }
+    }
+    if (!swapped) break;
+    if (R.swaps == L0_LS_SWAPS) {
+      R.status |= L0_LS_SWAPS_OUT;
+      break;
+    }
+  }
+  double acc = 0.0;
+  for (int j = 0; j < p; ++j) {
+    acc += beta[j] * (c[j] + r[(size_t)j]);
+    R.nnz += beta[j] != 0.0;
+  }
+  for (int g = 0; g < ng; ++g) R.closed += nz[(size_t)g] > 0 || held[(size_t)g] > 0;
+  R.F = -0.5 * acc + alpha * (double)R.closed;
+  return R;
+}
+
+// What slm_solve_l0_local_groups refuses before a device is touched, in this order: everything l0_lsf_check refuses (`lsf`);
+// a group index that is not 0 at column 0 or does not rise by 0 or 1 from a column to the next (groups not contiguous or not
+// ascending: the caller must order the columns; which: the column); a need_ptr that does not start at 0 or falls (which: the
+// group); a need_idx outside the search groups, or a NULL need_idx under a non-empty need_ptr (which: the entry); a row-sharded
+// dataset.  gid: [p] the dataset's group index, or NULL for singleton groups; *n_search: the groups of the searched columns.
+enum L0LgKind { L0_LG_OK = 0, L0_LG_LSF, L0_LG_ORDER, L0_LG_NEED_PTR, L0_LG_NEED_IDX, L0_LG_SHARDED };
+struct L0LgRefusal {
+  L0LgKind kind = L0_LG_OK;
+  L0LsfRefusal lsf;
+  long long which = 0;
+};
+inline L0LgRefusal l0_lg_check(long long count, const double* const* row_weights, const long long* n_effs, long long n, bool intercept,
+                               bool last_alone, long long n_cells, const double* alphas, const double* etas, double big_M,
+                               long long n_starts, const double* starts, long long p, const int* gid, const int* need_ptr,
+                               const int* need_idx, bool sharded, int* n_search = nullptr) {
+  L0LgRefusal R;
+  auto refuse = [&](L0LgKind kind, long long which) {
+    R.kind = kind;
+    R.which = which;
+    return R;
+  };
+  R.lsf = l0_lsf_check(count, row_weights, n_effs, n, intercept, last_alone, n_cells, alphas, etas, big_M, n_starts, starts, p);
+  if (R.lsf.kind != L0_LSF_OK) return refuse(L0_LG_LSF, R.lsf.which);
+  const long long ps = p - (intercept ? 1 : 0);
+  for (long long j = 0; gid && j < p; ++j) {
+    const int step = j == 0 ? gid[0] + 1 : gid[j] - gid[j - 1];
+    if (step != 0 && step != 1) return refuse(L0_LG_ORDER, j);
+    if (j == 0 && step != 1) return refuse(L0_LG_ORDER, j);
+  }
+  const long long ng = ps < 1 ? 0 : (gid ? (long long)gid[ps - 1] + 1 : ps);
+  if (n_search) *n_search = (int)ng;
+  if (need_ptr) {
+    if (need_ptr[0] != 0) return refuse(L0_LG_NEED_PTR, 0);
+    for (long long g = 0; g < ng; ++g)
+      if (need_ptr[g + 1] < need_ptr[g]) return refuse(L0_LG_NEED_PTR, g + 1);
+    if (need_ptr[ng] > 0 && !need_idx) return refuse(L0_LG_NEED_IDX, 0);
+    for (long long k = 0; k < need_ptr[ng]; ++k)
+      if (need_idx[k] < 0 || need_idx[k] >= ng) return refuse(L0_LG_NEED_IDX, k);
+  }
+  if (sharded) return refuse(L0_LG_SHARDED, 0);
+  return R;
 }
 
 }  // namespace slm

@@ -107,6 +107,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_local_descent",
     "slm_solve_l0_local_folds",
     "slm_solve_l0_local_subsets",
+    "slm_solve_l0_local_groups",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -382,6 +383,7 @@ def load_library():
             "slm_solve_l0_local_descent": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_folds": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_subsets": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_groups": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1703,6 +1705,64 @@ class Dataset:
         if any(g < cells for g in given):
             raise ValueError("sizes and etas must have n_cells entries")
         return self._l0_local_rows("solve_l0_local_subsets", 6, rws, nes, sz, et, cells, intercept, big_M, starts, swaps, n_starts, binding)
+
+    def solve_l0_local_groups(self, row_weights, n_effs, alphas, etas=0.0, need=None, intercept=False, big_M=100.0, starts=None,
+                              swaps=True, n_cells=None, n_starts=None, binding=None):
+        """``slm_solve_l0_local_groups``: the l0 local search WITH GROUPS AND A HIERARCHY (csrc/l0_local_group_kernels.hpp) --
+        ``1/2 b^T (G + 2 eta I) b - c^T b + alpha |cl(S(b))|`` with ``|b_j| <= big_M``, ``S`` the groups that hold a non-zero, ``cl``
+        the closure under the hierarchy -- on the dataset's groups (``set_groups``), which must be contiguous and ascending in
+        column order.  ``need``: None, one list per search group of the groups it needs directly (the engine closes them
+        transitively), or the CSR pair ``(need_ptr, need_idx)`` as it goes to the engine.  Row sets, ``intercept`` (the ones column
+        and its group are not searched), cells, ``starts`` and ``swaps`` as for ``solve_l0_local_folds``.  Returns ``(betas [count,
+        cells, ps], intercepts, objectives [count, cells], winning starts, group supports [count, cells, groups] (cl(S), int32),
+        stats [count, cells, n_starts, 6], infos)``: ``stats`` holds sweeps, accepted swaps, status word, |cl(S)|, non-zero
+        columns and group trials of EVERY problem; ``infos`` the dicts of ``solve_l0_local`` with ``n_active_groups`` and ``trials``
+        of the winner.  Nothing is proven, and the screen of the group descent is a heuristic."""
+        rws, nes = self._l0_local_row_sets(row_weights, n_effs)
+        al, et, cells = _l0_local_cells(alphas, etas, n_cells)
+        drop = 1 if intercept else 0
+        ps, gs, count = self.p - drop, max(self.n_groups - drop, 0), len(rws)
+        if need is None:
+            ptr = idx = None
+        elif isinstance(need, tuple):
+            ptr, idx = (None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in need)
+            if ptr is None or len(ptr) != gs + 1:
+                raise ValueError(f"need_ptr must have {gs + 1} entries")
+            if idx is not None and len(ptr) and len(idx) < max(int(ptr.max()), 0):
+                raise ValueError("need_idx is shorter than need_ptr says")
+        else:
+            lists = [np.asarray(v, dtype=np.int64).reshape(-1) for v in need]
+            if len(lists) != gs:
+                raise ValueError(f"need must have {gs} entries")
+            ptr = np.concatenate([[0], np.cumsum([len(v) for v in lists])]).astype(np.int32)
+            idx = np.ascontiguousarray(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]), dtype=np.int32)
+        if idx is not None and not len(idx):
+            idx = np.zeros(1, dtype=np.int32)  # (an empty array has no address worth handing over)
+        st, ns = _l0_local_starts(starts, n_starts, (count, cells), ps, f"{count}, {cells}, n_starts, {ps}")
+        # (else the engine refuses: the outputs only have to exist)
+        sized = 1 <= count <= 16 and cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS and count * cells * ns <= L0_LOCAL_MAX_PROBLEMS
+        if st is not None and sized and st.size != count * cells * ns * ps:
+            raise ValueError(f"starts has {st.size} entries, expected {count * cells * ns * ps}")
+        cnt = count * cells if sized else 1
+        problems = cnt * ns if sized else 1
+        ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
+        ne = np.array(nes or [0], dtype=np.int64)
+        tail = (int(bool(intercept)), cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), ptr, idx, ns, st if sized else None,
+                int(bool(swaps)))
+        (betas, icpts, objectives, winners, gsup, stats), infos, rc = self._l0_call(
+            "solve_l0_local_groups", binding, (count, ptrs, ne) + tail,
+            [np.zeros((cnt, ps)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros((cnt, max(gs, 1)), dtype=np.int32),
+             np.zeros((problems, 6), dtype=np.int32)],
+            records=cnt, binding_args=(self.n, self.n_groups, rws, nes, bool(intercept)) + tail[1:-1] + (bool(swaps),))
+        out = _l0_local_infos(infos, cnt)
+        if not sized:
+            return betas, icpts, objectives, winners, gsup, stats, [out]
+        stats = stats.reshape(count, cells, ns, 6)
+        for e in range(cnt):
+            won = stats[e // cells, e % cells, int(winners[e])]
+            out[e]["n_active_groups"], out[e]["trials"] = int(np.count_nonzero(gsup[e][:gs])), int(won[5])
+        return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
+                gsup[:, :gs].reshape(count, cells, gs), stats, [out[r * cells:(r + 1) * cells] for r in range(count)])
 
     def _l0_local_row_sets(self, row_weights, n_effs):
         """The row sets of a local-search call: ``(the weight arrays or None, the divisors)``, one per set."""

@@ -20,13 +20,19 @@ to 1024 columns -- beyond the 128 at which every search above stops.  They prove
 one launch per round.  ``l0_local_subsets`` / ``L0LocalSubsets`` (``model/_l0_local_subsets.py``) are that search in the
 CARDINALITY form -- an incumbent for ``BestSubsetSelection`` / ``RidgedBestSubsetSelection`` at every ``sparse_bound`` of a list,
 the approximate twin of ``l0_profile`` up to 1024 columns -- and ``l0_local_subsets_cv`` / ``L0LocalSubsetsCV``
-(``model/_l0_local_subsets_cv.py``) cross-validate the size.
+(``model/_l0_local_subsets_cv.py``) cross-validate the size.  ``l0_local_group_search`` / ``L0LocalGroupPath``
+(``model/_l0_local_groups.py``) are the local search WITH ``groups=`` AND ``hierarchy=`` -- the estimators' arguments, for the few hundred
+to a thousand grouped columns of a cluster expansion: a group descent and one-for-one group swaps on
+``1/2 b^T (G + 2 eta I) b - c^T b + alpha |cl(S)|``; they prove nothing, and the screen of the descent can miss a group.
+``l0_local_group_cv`` / ``L0LocalGroupCV`` (``model/_l0_local_groups_cv.py``) cross-validate it, one launch per round.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
 from .model._l0_grid_cv import L0ProfileGridCV, l1l0_profile_cv, l2l0_profile_cv  # noqa: F401  (CV over (alpha, eta) from one launch; outside __all__)
 from .model._l0_local import L0LocalPath, l0_local_search  # noqa: F401  (approximate, up to 1024 columns; outside __all__)
 from .model._l0_local_cv import L0LocalCV, l0_local_cv  # noqa: F401  (the local search of every CV fold from one launch per round; outside __all__)
+from .model._l0_local_groups import L0LocalGroupPath, l0_local_group_search  # noqa: F401  (the local search with groups and a hierarchy; outside __all__)
+from .model._l0_local_groups_cv import L0LocalGroupCV, l0_local_group_cv  # noqa: F401  (its cross-validation, one launch per round; outside __all__)
 from .model._l0_local_subsets import L0LocalSubsets, l0_local_subsets  # noqa: F401  (approximate best subsets of every size; outside __all__)
 from .model._l0_local_subsets_cv import L0LocalSubsetsCV, l0_local_subsets_cv  # noqa: F401  (their cross-validation, one launch per round; outside __all__)
 from .model._l0_profile import L0Profile, l0_profile  # noqa: F401  (not estimators: outside __all__, which tests pin)

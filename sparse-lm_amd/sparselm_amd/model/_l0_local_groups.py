@@ -1,0 +1,155 @@
+"""The l0 local search WITH GROUPS AND A HIERARCHY: approximate regularised-l0 fits of a cluster expansion -- a few hundred to a
+thousand columns, grouped, under a hierarchy -- over a whole (alpha, eta) grid (``slm_solve_l0_local_groups``,
+csrc/l0_local_group_kernels.hpp).
+
+The exact estimators honour ``groups=`` and ``hierarchy=`` and stop at 64 columns (128 with ``wide``); ``l0_local_search`` goes to
+1024 and refuses groups.  This is that search for grouped columns: for every cell ``(alpha, eta)``
+
+    minimise over beta, |beta_j| <= big_M:   1/2 beta^T (G + 2 eta I) beta - c^T beta + alpha |cl(S(beta))|
+
+where ``S(beta)`` is the set of groups that hold a non-zero coefficient and ``cl`` closes it under the hierarchy (a group is
+active only with every group it needs, transitively) -- ``solver_info_["objective"]`` of ``RegularizedL0`` / ``L2L0`` with the
+same ``groups`` and ``hierarchy``.  The rule is a GROUP descent (a step fits a whole group by a few passes of coordinate descent,
+values it exactly, and keeps it iff its value beats ``alpha`` times the groups it adds to the closure) followed by one-for-one
+GROUP swaps until none helps (csrc/l0_host.hpp, "local groups").  With singleton groups and no hierarchy it is
+``l0_local_search``'s rule.
+
+NOTHING IS PROVEN: ``proven_optimal_`` is False and there is no lower bound.  Two things can miss a better fit: the local
+minimum itself, and the SCREEN that spares an inactive group its trial fit (the sum of its columns' one-coordinate gains must
+exceed a quarter of its price) -- a heuristic, since a block can gain together what none of its columns shows alone.  Where the
+columns fit, the exact estimators say by how much.
+
+``groups`` and ``hierarchy`` carry the reference's semantics: labels per column, and entry ``i`` of ``hierarchy`` listing the
+labels that the i-th sorted label needs.  The columns are permuted so that every group is contiguous (the engine takes nothing
+else); starts and coefficients are mapped back.  Rounds as for ``l0_local_search``.
+
+Out of scope: groups in the cardinality form (``l0_local_subsets`` stays without groups), an l1 term, a Tikhonov matrix,
+constraints, seeding the exact search with the result.  (Cross-validation: ``l0_local_group_cv``, ``model/_l0_local_groups_cv.py``.)
+
+Import path: ``sparselm_amd.miqp`` (``l0_local_group_search``, ``L0LocalGroupPath``).
+"""
+
+from __future__ import annotations
+
+import warnings
+
+import numpy as np
+from sklearn.exceptions import ConvergenceWarning
+
+from ._l0_local import _IMPROVE, _MAX_PROBLEMS, _PMAX, L0LocalPath, _first_starts, _grid, _LocalProblem, _neighbour_starts, _options, _round_moves
+from ._miqp import _hierarchy_lists
+
+__all__ = ["l0_local_group_search", "L0LocalGroupPath"]
+
+_WHAT = "the grouped l0 local search"
+
+
+class L0LocalGroupPath(L0LocalPath):
+    """What ``l0_local_group_search`` returns: ``L0LocalPath``'s tables (``coefs_`` are the exact minimiser on ALL columns of the
+    groups in cl(S), inside the box) and ``group_supports_`` (A x E x n_groups, bool, in the order of the sorted labels: cl(S),
+    the closure included), ``n_active_groups_`` (A x E: what ``alpha`` multiplies), ``trials_`` (A x E: trial fits of groups outside
+    the closure and of swap candidates) and ``proven_optimal_ = False``."""
+
+    proven_optimal_ = False
+
+    def __init__(self, *tables, group_supports, trials):
+        super().__init__(*tables)
+        self.group_supports_ = np.asarray(group_supports, dtype=bool)
+        self.n_active_groups_ = self.group_supports_.sum(axis=-1)
+        self.trials_ = np.asarray(trials, dtype=int)
+
+
+class _GroupPlan:
+    """The arguments both grouped entries share, validated before a device is touched: the columns in group order (``perm``),
+    the dense group index of the permuted columns, the need lists, the grids and round 0's starts in the permuted order."""
+
+    def __init__(self, X, y, alphas, groups, hierarchy, etas, big_M, fit_intercept, sample_weight, starts, max_rounds, solver_options):
+        self.swaps, device = _options(solver_options, max_rounds, what=_WHAT)
+        self.spec = _LocalProblem(groups=groups, big_M=big_M, fit_intercept=fit_intercept, solver_options=device)
+        X, self.y, self.dev_options, gidx, self.n_groups, _, _, self.w = self.spec._l0_setup(X, y, sample_weight)
+        self.need = _hierarchy_lists(hierarchy, groups, X.shape[1])
+        self.al, self.et = _grid(alphas, "alphas"), _grid(etas, "etas")
+        self.A, self.E, self.p = len(self.al), len(self.et), X.shape[1]
+        if self.p > _PMAX:
+            raise NotImplementedError(f"{_WHAT} takes up to {_PMAX} columns (got {self.p})")
+        self.big_M = float(big_M)
+        if gidx is None:  # every column its own group: nothing to order, and the dataset keeps its singleton groups
+            self.perm, self.X, self.gidx, self.gstart = np.arange(self.p), X, None, np.arange(self.p + 1)
+        else:
+            gidx = np.asarray(gidx)
+            self.perm = np.argsort(gidx, kind="stable")  # (columns of one group together, the groups ascending)
+            self.X, self.gidx = np.ascontiguousarray(X[:, self.perm]), np.ascontiguousarray(gidx[self.perm], dtype=np.int32)
+            self.gstart = np.searchsorted(self.gidx, np.arange(self.n_groups + 1))
+        self.first = np.ascontiguousarray(_first_starts(starts, self.A, self.E, self.p, self.big_M)[..., self.perm])
+        self.moves = _round_moves(self.A, self.E, max_rounds)
+        self.most = max(self.first.shape[2], len(self.moves))  # (a round starts a cell from its neighbours in the grid)
+        self.cell_alpha, self.cell_eta = np.repeat(self.al, self.E), np.tile(self.et, self.A)
+
+    def unpermute(self, coefs):
+        out = np.empty_like(coefs)
+        out[..., self.perm] = coefs
+        return out
+
+    def group_supports(self, coefs_permuted):
+        """cl(S) of coefficient vectors in the permuted order, [..., n_groups]."""
+        held = np.add.reduceat((coefs_permuted != 0.0).astype(int), self.gstart[:-1], axis=-1) > 0  # (a dense index: no group is empty)
+        if self.need is None:
+            return held
+        reach = np.eye(self.n_groups, dtype=bool)  # reach[g, h]: g needs h (or is h), transitively
+        for g, subs in enumerate(self.need):
+            reach[g, subs] = True
+        for k in range(self.n_groups):  # (Warshall)
+            reach |= reach[:, k:k + 1] & reach[k:k + 1, :]
+        return (held[..., :, None] & reach).any(axis=-2)
+
+
+def _warn_cells(infos, A, E):
+    unconverged = [(a, e) for a in range(A) for e in range(E) if not infos[a, e]["converged"]]
+    if unconverged:
+        a, e = unconverged[0]
+        warnings.warn(f"{_WHAT} ran into a cap in {len(unconverged)} of {A * E} cells (the first: alpha index {a}, eta index {e}, "
+                      f"{infos[a, e]['status']}): their last points are returned", ConvergenceWarning)
+
+
+def l0_local_group_search(X, y, *, alphas, groups=None, hierarchy=None, etas=(0.0,), big_M=100, fit_intercept=False, sample_weight=None,
+                          starts=None, max_rounds=2, solver_options=None) -> L0LocalGroupPath:
+    """A local minimum of the regularised l0 problem WITH GROUPS AND A HIERARCHY at every cell of ``alphas x etas``, for up to
+    1024 columns, on the GPU.
+
+    ``groups``: a label per column (None: every column its own group); ``hierarchy``: one list per sorted label, of the labels it
+    needs (None: no hierarchy) -- the estimators' arguments, validated as theirs.  ``alphas``, ``etas``, ``big_M``, ``fit_intercept``,
+    ``sample_weight``, ``starts`` (of any support, closed under the hierarchy or not), ``max_rounds`` and ``solver_options``
+    (``device``, ``swaps``) as for ``l0_local_search``.  A ``ConvergenceWarning`` is raised when a cell's result ran into a sweep
+    or swap cap.  Nothing is proven optimal, and the screen of the group descent can miss a group (see the module's text).
+    Out of scope: groups in the cardinality form, an l1 term, a Tikhonov matrix, constraints, seeding the exact search."""
+    # everything is validated before a device is touched
+    plan = _GroupPlan(X, y, alphas, groups, hierarchy, etas, big_M, fit_intercept, sample_weight, starts, max_rounds, solver_options)
+    A, E, p = plan.A, plan.E, plan.p
+    if A * E * plan.most > _MAX_PROBLEMS:
+        raise ValueError(f"the grid holds {A * E} cells with up to {plan.most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
+    al = plan.al
+
+    with plan.spec._l0_dataset(plan.X, plan.y, plan.w, plan.gidx, plan.n_groups, None, plan.dev_options) as (ds, x_mean, y_mean, _, _):
+
+        def launch(points):
+            b, _, o, _, _, _, info = ds.solve_l0_local_groups([None], [0], plan.cell_alpha, plan.cell_eta, need=plan.need, big_M=plan.big_M,
+                                                              starts=points.reshape(1, A * E, -1, p), swaps=plan.swaps)
+            return np.array(b).reshape(A, E, p), np.array(o).reshape(A, E), np.array(info[0], dtype=object).reshape(A, E)
+
+        coefs, objectives, infos = launch(plan.first)
+        history = [objectives.copy()]
+        for _ in range(int(max_rounds) if plan.moves else 0):
+            c2, o2, i2 = launch(_neighbour_starts(coefs, plan.moves))
+            better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[:, None])
+            coefs[better], objectives[better], infos[better] = c2[better], o2[better], i2[better]
+            history.append(objectives.copy())
+            if not better.any():
+                break
+    _warn_cells(infos, A, E)
+    take = np.vectorize(lambda d, k: d[k])
+    # (with the estimators' own expression, so that an intercept equals a fitted estimator's on the same coefficients)
+    intercepts = np.array([[float(y_mean - np.dot(x_mean, coefs[a, e])) if fit_intercept else 0.0 for e in range(E)] for a in range(A)])
+    return L0LocalGroupPath(al, plan.et, plan.unpermute(coefs), intercepts, objectives, take(infos, "loss").astype(float), len(history),
+                            np.array(history), take(infos, "swaps").astype(int), take(infos, "sweeps").astype(int),
+                            take(infos, "converged").astype(bool), group_supports=plan.group_supports(coefs),
+                            trials=take(infos, "trials").astype(int))

@@ -28,7 +28,8 @@ consecutive, ``objectives_`` is non-increasing in k for each eta: a cell above i
 by that neighbour's winner, from which the rule only descends.
 
 Not built: groups and a hierarchy, a Tikhonov matrix, an l1 term, constraints, handing the result to the exact search as its
-seed.  (Cross-validation over the sizes: ``l0_local_subsets_cv``, ``model/_l0_local_subsets_cv.py``.)
+seed.  (Cross-validation over the sizes: ``l0_local_subsets_cv``, ``model/_l0_local_subsets_cv.py``; groups and a hierarchy in the
+penalised form: ``l0_local_group_search``, ``model/_l0_local_groups.py``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_subsets``, ``L0LocalSubsets``).
 """

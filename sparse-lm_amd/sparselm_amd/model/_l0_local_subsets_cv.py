@@ -14,7 +14,8 @@ the rule is closer than that to a tie; the coefficients are not the same bytes (
 its held-out rows, and centring is by elimination of the ones column).  Nothing is proven optimal.
 
 Limits: 1024 columns, at most 15 splits, ``(splits + 1) x cells x starts <= 8192`` problems per launch; held-out scores are
-unweighted.  Not built: groups, an l1 term, rerouting ``GridSearchCV``.
+unweighted.  Not built: groups, an l1 term, rerouting ``GridSearchCV``.  (Groups and a hierarchy in the penalised form:
+``l0_local_group_cv``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_subsets_cv``, ``L0LocalSubsetsCV``).
 """

@@ -76,6 +76,15 @@ def _hierarchy_masks(hierarchy, groups, n_features):
     return need
 
 
+def _hierarchy_lists(hierarchy, groups, n_features):
+    """``_hierarchy_masks`` in list form, for more groups than a mask has bits (the grouped local search, up to 1024):
+    ``need[i]`` is the sorted dense indices of the groups the i-th sorted label depends on.  The same two ``ValueError``s."""
+    masks = _hierarchy_masks(hierarchy, groups, n_features)
+    if masks is None:
+        return None
+    return [[g for g in range(len(masks)) if (mask >> g) & 1] for mask in masks]
+
+
 class _FoldedConstraints:
     """``constraints`` as the constrained search takes them: the rows ``lo <= A b <= hi`` and the per-column box.
 
