@@ -847,7 +847,7 @@ int slm_solve_l0_profile_grid(slm_dataset* ds, int32_t count, const double* cons
  * n_starts < 1, n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS = 8192, a start outside the box (SLM_ERR_BAD_ARG).
  * Not here: groups and a hierarchy, an l1 term, a Tikhonov matrix, constraints.  Row sets (CV folds) in the launch:
  * slm_solve_l0_local_folds, below; a bound on the cardinality: slm_solve_l0_local_subsets, below.  (Groups and a hierarchy:
- * slm_solve_l0_local_groups, below.)
+ * slm_solve_l0_local_groups, below.  An l1 term: slm_solve_l0_local_l1, below.)
  */
 #define SLM_L0_LOCAL_PMAX 1024
 #define SLM_L0_LOCAL_MAX_PROBLEMS 8192
@@ -882,7 +882,7 @@ int slm_solve_l0_local_descent(slm_dataset* ds, int32_t n_cells, const double* a
  * count * n_cells * n_starts > SLM_L0_LOCAL_MAX_PROBLEMS (the message names the three factors).  A row set that gives the
  * ones column no weight is refused once its Gram is there.
  * Not here: groups, an l1 term, more than 16 row sets.  (A bound on the cardinality: slm_solve_l0_local_subsets.)
- * (Groups and a hierarchy: slm_solve_l0_local_groups.)
+ * (Groups and a hierarchy: slm_solve_l0_local_groups.  An l1 term: slm_solve_l0_local_l1.)
  */
 int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                              const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
@@ -920,7 +920,7 @@ int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const
  * those of slm_solve_l0_local_folds for the row sets, the problem counts, big_M, the width, the intercept column, the weights
  * and the box of the starts.
  * Not here: groups, hierarchy, Tikhonov matrix, l1 term, constraints.  (Groups and a hierarchy in the penalised form:
- * slm_solve_l0_local_groups, below.)
+ * slm_solve_l0_local_groups, below; an l1 term in the penalised form: slm_solve_l0_local_l1, below.)
  */
 int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                                const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const int32_t* sizes,
@@ -966,7 +966,8 @@ int slm_solve_l0_local_subsets(slm_dataset* ds, int32_t count, const double* con
  * Refusals, all before a device is touched, each with its own message: those of slm_solve_l0_local_folds except the one about
  * groups; groups that are not contiguous or not ascending (SLM_ERR_UNSUPPORTED: the caller must order the columns); a need_ptr
  * that does not start at 0 or falls, a need_idx outside the search groups (SLM_ERR_BAD_ARG); a row-sharded dataset.
- * Not here: groups in the cardinality form, an l1 term, a Tikhonov matrix, constraints, seeding the exact search.
+ * Not here: groups in the cardinality form, an l1 term beside groups (without groups: slm_solve_l0_local_l1, below), a Tikhonov
+ * matrix, constraints, seeding the exact search.
  */
 int slm_solve_l0_local_groups(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
                               const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
@@ -978,6 +979,40 @@ int slm_solve_l0_local_groups(slm_dataset* ds, int32_t count, const double* cons
                               int32_t* group_support_out /* count * n_cells * search groups, or NULL: cl(S) */,
                               int32_t* stat_out /* 6 per problem: sweeps, swaps, status word, |cl(S)|, non-zero columns, group trials; or NULL */,
                               slm_point_info* info /* count * n_cells, or NULL */);
+
+/*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_local_folds, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs it looks the symbol up.)  LOCAL SEARCH WITH AN L1 TERM (l0_local_l1_kernel,
+ * csrc/l0_local_kernels.hpp): the approximate answer to slm_solve_l0_l1 (the reference's L1L0) beyond its 64 columns, up to
+ * SLM_L0_LOCAL_PMAX = 1024.  Cell e is (alphas[e], l1s[e], ridges[e]); with G, c as for slm_solve_l0_local and
+ * H = G + 2 ridges[e] I,
+ *       minimise over beta, |beta_j| <= big_M:   F(beta) = 1/2 beta^T H beta - c^T beta + l1s[e] ||beta||_1 + alphas[e] ||beta||_0
+ * -- with ridges[e] = 0 the units of slm_solve_l0_l1's objective (eta_l1 = l1s[e]) with singleton groups.  NOTHING IS PROVEN.
+ * The rule is slm_solve_l0_local's with ONE change, the coordinate: with lam = l1s[e], u = r_j + d_j beta_j,
+ *       s = sign(u) max(|u| - lam, 0),   b = clip(s / d_j, +-big_M),   gain = u b - 1/2 d_j b^2 - lam |b|
+ * (what F without the alpha term falls by when beta_j goes from 0 to b).  The descent keeps b iff gain > alphas[e]; the swap scan
+ * compares these gains by the same rule; dead columns, the stopping rules and both caps are unchanged.  With l1s[e] = 0 every
+ * decision is slm_solve_l0_local_folds's (the objectives agree to rounding, not byte for byte: a multiply-add may contract
+ * otherwise).  Row sets, intercept, starts, problem order, the winner per (row set, cell) by (F, then the lowest start), stat_out
+ * (FOUR ints per problem) and info exactly as for slm_solve_l0_local_folds, mode = 10.  The winner is polished on the rows of
+ * its support alone: the soft-threshold descent to its last digit, then the exact solve on its sign pattern
+ * (H_FF x = c_F - lam sign(b_F) - H_FB b_B: free F, bound B), taken only when every sign and the box hold; a coefficient the
+ * polish brings to zero goes back as zero, objective_out is F of the coefficients that go back (alpha on THEIR non-zeros), and
+ * the polish never raises F.
+ * Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when some winner reached a cap.
+ * Refusals, all before a device is touched, in this order: NULL alphas or l1s; a negative or non-finite l1s[e]; a negative or
+ * non-finite ridges[e] where ridges is given; then those of slm_solve_l0_local_folds, in its order.
+ * Not here: groups or a hierarchy with the l1 term, the cardinality form with it, a Tikhonov matrix, constraints, seeding the
+ * exact search, more than 16 row sets.
+ */
+int slm_solve_l0_local_l1(slm_dataset* ds, int32_t count, const double* const* row_weights /* [count], entries may be NULL */,
+                          const int64_t* n_effs /* [count] */, int32_t intercept, int32_t n_cells, const double* alphas,
+                          const double* l1s /* [n_cells] each */, const double* ridges /* [n_cells] or NULL: 0 */, double big_M,
+                          int32_t n_starts, const double* starts /* count * n_cells * n_starts * ps, or NULL: one zero start */,
+                          int32_t swaps, double* beta_out /* count * n_cells * ps */, double* intercept_out /* count * n_cells, or NULL */,
+                          double* objective_out /* count * n_cells */, int32_t* start_out /* or NULL */,
+                          int32_t* stat_out /* 4 words per problem: sweeps, swaps, status word, non-zeros (or NULL) */,
+                          slm_point_info* info /* count * n_cells, or NULL */);
 
 /*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant

@@ -604,6 +604,51 @@ py::tuple solve_l0_local_subsets(uintptr_t ds, int64_t p, int64_t n, const py::s
   return l0_local_rows(ds, p, n, row_weights, n_effs, intercept, n_cells, nullptr, sizes.data(), etas, big_M, n_starts, starts, swaps);
 }
 
+// slm_solve_l0_local_l1: the local search with an l1 term -- the tuple of solve_l0_local_folds; `l1s` beside the alphas, `ridges`
+// an array or None (NULL: no ridge).
+py::tuple solve_l0_local_l1(uintptr_t ds, int64_t p, int64_t n, const py::sequence& row_weights, const py::sequence& n_effs, bool intercept,
+                            int32_t n_cells, const arr_d& alphas, const arr_d& l1s, const py::object& ridges, double big_M, int32_t n_starts,
+                            const py::object& starts, bool swaps) {
+  const py::ssize_t count = (py::ssize_t)py::len(row_weights);
+  if ((py::ssize_t)py::len(n_effs) != count) throw py::value_error("row_weights and n_effs differ in length");
+  const int64_t cells = n_cells > 0 ? n_cells : 0;
+  if ((int64_t)alphas.size() < cells || (int64_t)l1s.size() < cells) throw py::value_error("alphas, l1s and ridges must have n_cells entries");
+  const int64_t ps = intercept && p > 0 ? p - 1 : p;
+  // (no row set, no cell, more problems than any call takes: the engine refuses them, the outputs only have to exist)
+  const bool sized = count >= 1 && count <= 16 && n_cells >= 1 && n_starts >= 1 && (int64_t)n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS &&
+                     (int64_t)count * n_cells * n_starts <= SLM_L0_LOCAL_MAX_PROBLEMS;
+  Keep keep;
+  const arr_d rd = ridges.is_none() ? arr_d() : arr_d::ensure(ridges);  // (at least n_cells entries, as the alphas: the engine reads that many)
+  if (!ridges.is_none() && (!rd || (int64_t)rd.size() < cells)) throw py::value_error("alphas, l1s and ridges must have n_cells entries");
+  const double* rp = ridges.is_none() ? nullptr : rd.data();
+  const double* sp = sized ? vector_arg(starts, (int64_t)count * n_cells * n_starts * ps, "starts", keep) : nullptr;
+  std::vector<const double*> wp((size_t)count);
+  std::vector<int64_t> ne((size_t)count);
+  for (py::ssize_t b = 0; b < count; ++b) {
+    wp[(size_t)b] = vector_arg(row_weights[b], n, "row_weights", keep);
+    ne[(size_t)b] = n_effs[b].cast<int64_t>();
+  }
+  const py::ssize_t cnt = sized ? count * n_cells : 1, problems = sized ? cnt * n_starts : 1;
+  py::array_t<double> beta({cnt, (py::ssize_t)ps}), icpt(cnt), objective(cnt);
+  py::array_t<int32_t> winner(cnt), stats({problems, (py::ssize_t)4});
+  py::array info = info_bytes(cnt);
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
+  double *bp = beta.mutable_data(), *ip = icpt.mutable_data(), *op = objective.mutable_data();
+  int32_t *wn = winner.mutable_data(), *tp = stats.mutable_data();
+  std::memset(wn, 0, sizeof(int32_t) * (size_t)cnt);
+  std::memset(tp, 0, sizeof(int32_t) * 4 * (size_t)problems);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    auto* d = reinterpret_cast<slm_dataset*>(ds);
+    rc = slm_solve_l0_local_l1(d, (int32_t)count, wp.data(), ne.data(), intercept ? 1 : 0, n_cells, alphas.data(), l1s.data(), rp, big_M,
+                               n_starts, sp, swaps ? 1 : 0, bp, ip, op, wn, tp, rec);
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(beta, icpt, objective, winner, stats, info, rc);
+}
+
 // slm_solve_l0_local_groups: the local search with groups and a hierarchy.  need_ptr / need_idx: None or int32 arrays (need_ptr
 // with one entry per search group and one more: checked by the caller, sparselm_amd/_engine.py).  Returns (coefficients
 // [count * n_cells][ps], intercepts, objectives, winning starts, cl(S) [count * n_cells][search groups], the six status words
@@ -696,6 +741,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_local_folds", &solve_l0_local_folds);
   m.def("solve_l0_local_subsets", &solve_l0_local_subsets);
   m.def("solve_l0_local_groups", &solve_l0_local_groups);
+  m.def("solve_l0_local_l1", &solve_l0_local_l1);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

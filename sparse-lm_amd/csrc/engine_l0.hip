@@ -37,7 +37,8 @@
 // four entries, ONE body at the end of the unit (solve_l0_local_folds_impl): slm_solve_l0_local_folds, the search on up to 16 row sets
 // of the dataset in one launch; slm_solve_l0_local and slm_solve_l0_local_descent, that call with one row set, the dataset's own
 // rows; slm_solve_l0_local_subsets, that call with the kernel's cardinality rule: sizes where the alphas are.  (A fifth entry on that
-// body, with its own kernel: slm_solve_l0_local_groups, the search with groups and a hierarchy -- csrc/l0_local_group_kernels.hpp.)
+// body, with its own kernel: slm_solve_l0_local_groups, the search with groups and a hierarchy -- csrc/l0_local_group_kernels.hpp.  A
+// sixth: slm_solve_l0_local_l1, the penalised rule with an l1 term -- l0_local_l1_kernel, the family's body compiled a third time.)
 #include "engine_internal.hpp"
 #include "l0_host.hpp"
 #include "l0_kernels.hpp"
@@ -880,6 +881,9 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
 //                               in a block of their own; the launch is l0_local_group_kernel; a winner is polished on every column of
 //                               the groups in cl(S) (l0_ls_polish_on; l0_fetch_rows fetches those groups' rows only); the objective
 //                               is quad + alpha |cl(S)| of the coefficients that go back; six status words (L0_LG_STATS); mode 9
+//   slm_solve_l0_local_l1       the FIFTH kind (L0_LOCAL_L1): cells (alpha, l1, ridge); the check is l0_l1l_check; the l1 weights go up
+//                               behind the eliminated c; the launch is l0_local_l1_kernel; a winner is polished by l0_l1l_polish on
+//                               its support's rows; the objective holds lam ||beta||_1; four status words; mode 10
 // check (l0_lsf_check -- at one row set l0_ls_check's refusals in l0_ls_check's order -- and the dataset's shape, before a device
 // is touched); the Grams FILED, not fetched: as in solve_l0_profile_grid_impl (one slm_dataset_covariance_folds call when every
 // row set brings its weights, else one by one; found again by fingerprint), each HELD for the call, so that a later build
@@ -900,7 +904,7 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
 // loss as for solve_l0.  Nothing here is proven optimal, whatever the status.  Non-finite data is refused where it shows:
 // X^T y before the launch, the winners' Gram rows after it.
 static_assert(SLM_L0_LOCAL_PMAX == L0_LS_PMAX && SLM_L0_LOCAL_MAX_PROBLEMS == L0_LS_MAX_PROBLEMS, "the header and the host logic name one set of limits");
-enum L0LocalKind { L0_LOCAL_ONE, L0_LOCAL_SETS, L0_LOCAL_SIZES, L0_LOCAL_GROUPS };  // slm_solve_l0_local[_descent]; _folds; _subsets; _groups
+enum L0LocalKind { L0_LOCAL_ONE, L0_LOCAL_SETS, L0_LOCAL_SIZES, L0_LOCAL_GROUPS, L0_LOCAL_L1 };  // slm_solve_l0_local[_descent]; _folds; _subsets; _groups; _l1
 struct L0LocalGroups {  // what only slm_solve_l0_local_groups brings: the direct need lists (CSR over the search groups) and cl(S) out
   const int32_t *need_ptr, *need_idx;
   int32_t* group_support_out;
@@ -909,7 +913,7 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
                               int32_t intercept, int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
                               int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
                               double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info,
-                              const L0LocalGroups* lg = nullptr);
+                              const L0LocalGroups* lg = nullptr, const double* l1s = nullptr);
 
 // slm_solve_l0_local, slm_solve_l0_local_descent: the body below on one row set, the dataset's own rows
 int solve_l0_local_impl(int32_t swaps, slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
@@ -925,9 +929,9 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
                               int32_t intercept, int32_t n_cells, const double* alphas, const int32_t* sizes, const double* etas, double big_M,
                               int32_t n_starts, const double* starts, int32_t swaps, double* beta_out, double* intercept_out,
                               double* objective_out, int32_t* start_out, int32_t* stat_out, slm_point_info* info,
-                              const L0LocalGroups* lg) {
+                              const L0LocalGroups* lg, const double* l1s) {
   if (!ds || !beta_out || !objective_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
-  const bool card = kind == L0_LOCAL_SIZES, one = kind == L0_LOCAL_ONE, grouped = kind == L0_LOCAL_GROUPS;
+  const bool card = kind == L0_LOCAL_SIZES, one = kind == L0_LOCAL_ONE, grouped = kind == L0_LOCAL_GROUPS, l1 = kind == L0_LOCAL_L1;
   if (grouped && !lg) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   const int drop = intercept != 0 ? 1 : 0;
   bool alone = ds->p >= 1;  // the ones column: last, alone in the last group
@@ -948,6 +952,17 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
       case L0_LC_SIZE: return fail(SLM_ERR_BAD_ARG, "sizes[%lld] must be >= 1 (got %d)", C.which, sizes[C.which]);
       case L0_LC_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", C.which);
       case L0_LC_LSF: break;
+    }
+    R = C.lsf;
+  } else if (l1) {
+    const L0L1lRefusal C = l0_l1l_check(count, row_weights, reinterpret_cast<const long long*>(n_effs), ds->n, drop != 0, alone, n_cells, alphas,
+                                        l1s, etas, big_M, n_starts, starts, ds->p);
+    switch (C.kind) {
+      case L0_L1L_OK: break;
+      case L0_L1L_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+      case L0_L1L_L1: return fail(SLM_ERR_BAD_ARG, "l1s[%lld] must be finite and >= 0", C.which);
+      case L0_L1L_RIDGE: return fail(SLM_ERR_BAD_ARG, "ridges[%lld] must be finite and >= 0", C.which);
+      case L0_L1L_LSF: break;
     }
     R = C.lsf;
   } else {
@@ -1007,6 +1022,8 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
     l0_lg_close(ngs, lg->need_ptr, lg->need_idx, cptr, cidx);
   }
   const int p = (int)ds->p, ps = p - drop, per_set = n_cells * n_starts, problems = count * per_set;
+  const std::vector<double> no_ridge(l1 && !etas ? (size_t)n_cells : 0, 0.0);  // (the l1 kind: ridges == NULL is no ridge)
+  if (l1 && !etas) etas = no_ridge.data();
   const int64_t n = ds->n;
   const size_t ld = (size_t)ds->ld;
   slm_engine* eng = ds->eng;
@@ -1081,7 +1098,10 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
   // (the cardinality rule: the sizes, as ints, lie where the alphas did; six status words)
   const int nstat = card ? 6 : (grouped ? L0_LG_STATS : 4);
   const size_t n_start_words = starts ? (size_t)problems * ps : 0, n_c_words = drop ? (size_t)count * ld : 0;
-  const size_t off_eta = (size_t)n_cells, off_st = 2 * (size_t)n_cells, off_c = off_st + n_start_words, off_F = off_c + n_c_words,
+  // (the l1 kind: its l1 weights last of what goes up, so that every other kind keeps its block)
+  const size_t n_l1_words = l1 ? (size_t)n_cells : 0;
+  const size_t off_eta = (size_t)n_cells, off_st = 2 * (size_t)n_cells, off_c = off_st + n_start_words, off_l1 = off_c + n_c_words,
+               off_F = off_l1 + n_l1_words,
                off_stat = off_F + (size_t)problems, off_beta = off_stat + ((size_t)nstat * problems + 1) / 2, words = off_beta + (size_t)problems * ps;
   const size_t ws_stride = (size_t)ps * ld;
   std::vector<double> h(words, 0.0);
@@ -1092,6 +1112,7 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
   memcpy(h.data() + off_eta, etas, sizeof(double) * (size_t)n_cells);
   if (starts) memcpy(h.data() + off_st, starts, sizeof(double) * n_start_words);
   if (drop) memcpy(h.data() + off_c, cs.data(), sizeof(double) * n_c_words);
+  if (l1) memcpy(h.data() + off_l1, l1s, sizeof(double) * n_l1_words);
   unsigned long long *dev = nullptr, *ws = nullptr, *gtab = nullptr;
   L0DevGuard guard{dev, s}, ws_guard{ws, s}, gtab_guard{gtab, s};
   SLM_TRY(dalloc(&dev, words));
@@ -1164,6 +1185,12 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
       g.p = ps; g.ng = ngs; g.n_problems = problems; g.n_starts = n_starts; g.swaps = k.swaps; g.n_cells = n_cells;
       g.big_M = big_M;
       hipLaunchKernelGGL(l0_local_group_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, g);
+    } else if (l1) {
+      L0LsL1Args kl;
+      memset(&kl, 0, sizeof(kl));
+      static_cast<L0LsArgs&>(kl) = k;
+      kl.l1s = dd + off_l1;
+      hipLaunchKernelGGL(l0_local_l1_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, kl);
     } else if (!card)
       hipLaunchKernelGGL(l0_local_kernel<false>, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
     else
@@ -1220,7 +1247,9 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
       memcpy(beta, h.data() + off_beta + q * ps, sizeof(double) * (size_t)ps);
       for (int a = 0; a < m; ++a) bc[(size_t)a] = beta[rows[(size_t)a]];
       double quad = 0.0;
-      if (!grouped) {
+      if (l1) {  // (quad holds the l1 term too: objective_out = quad + alpha nnz of the coefficients that go back, as below)
+        quad = l0_l1l_polish(Gc.data(), (size_t)m, cc.data(), m, etas[cell], l1s[cell], big_M, bc.data());
+      } else if (!grouped) {
         quad = l0_ls_polish(Gc.data(), (size_t)m, cc.data(), m, etas[cell], big_M, bc.data());
       } else {
         // on ALL columns of the groups in cl(S) -- a group that is only held is free to use -- but for those the rule leaves out
@@ -1262,7 +1291,7 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
         info[rc].rejects = stat[nstat * q + 1];
         info[rc].resid = (double)stat[nstat * q + 2];
         info[rc].beta_norm = std::sqrt(bn);
-        info[rc].mode = grouped ? 9 : 8;
+        info[rc].mode = grouped ? 9 : (l1 ? 10 : 8);
       }
     }
   }
@@ -1308,6 +1337,17 @@ extern "C" int slm_solve_l0_local_groups(slm_dataset* ds, int32_t count, const d
   const L0LocalGroups lg{need_ptr, need_idx, group_support_out};
   return solve_l0_local_folds_impl(L0_LOCAL_GROUPS, ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, etas, big_M, n_starts,
                                    starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info, &lg);
+}
+
+// The l0 local search with an l1 term: every (row set, (alpha, l1, ridge) cell, start) problem from one launch of
+// l0_local_l1_kernel; the winner is polished by the soft-threshold descent and the sign-face solve on its support (l0_l1l_polish).
+extern "C" int slm_solve_l0_local_l1(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,
+                                     int32_t intercept, int32_t n_cells, const double* alphas, const double* l1s, const double* ridges,
+                                     double big_M, int32_t n_starts, const double* starts, int32_t swaps, double* beta_out,
+                                     double* intercept_out, double* objective_out, int32_t* start_out, int32_t* stat_out,
+                                     slm_point_info* info) {
+  return solve_l0_local_folds_impl(L0_LOCAL_L1, ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, ridges, big_M, n_starts,
+                                   starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info, nullptr, l1s);
 }
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.

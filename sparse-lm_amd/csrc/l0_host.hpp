@@ -17,7 +17,7 @@
 // elimination of an intercept column from a Gram.  The profile grid (slm_solve_l0_profile_grid; tests/l0_grid_host_test.cpp) adds
 // the problem index over (row set, eta), its argument checks and the layout at up to L0_GRID_MAX problems.  The local search
 // (slm_solve_l0_local; tests/l0_local_host_test.cpp) adds, at the very end, the two decisions host and device share, the rule
-// itself without a device (l0_local_solve: ONE twin of the one kernel, both of its rules), the polish of its winner and its
+// itself without a device (l0_local_solve: ONE twin of the one kernel, all of its rules), the polish of its winner and its
 // argument checks; it uses nothing of the exact search but l0_boxed and the dense Cholesky.
 #pragma once
 #include <stddef.h>
@@ -1194,6 +1194,15 @@ constexpr L0LsCoord l0_ls_coord(double u, double d, double big_M) {
   b = b < -big_M ? -big_M : (b > big_M ? big_M : b);
   return L0LsCoord{b, u * b - 0.5 * d * b * b};
 }
+// the same coordinate with an l1 term lam |beta_j| in F ("local search with an l1 term", below; l0_local_solve<false, true>):
+// s = sign(u) max(|u| - lam, 0), b = clip(s / d_j), gain = u b - 1/2 d_j b^2 - lam |b|.  lam = 0 gives l0_ls_coord's b and gain.
+constexpr L0LsCoord l0_ls_coord_l1(double u, double d, double big_M, double lam) {
+  const double au = u < 0.0 ? -u : u;
+  const double s = au > lam ? (u < 0.0 ? lam - au : au - lam) : 0.0;
+  double b = s / d;
+  b = b < -big_M ? -big_M : (b > big_M ? big_M : b);
+  return L0LsCoord{b, u * b - 0.5 * d * b * b - lam * (b < 0.0 ? -b : b)};
+}
 // the descent's rule: the new value of a coordinate
 constexpr double l0_ls_threshold(const L0LsCoord& co, double alpha) { return co.gain > alpha ? co.b : 0.0; }
 // the swap rule: column j (gain gj with i removed) replaces column i (gain gi with i removed)
@@ -1213,10 +1222,18 @@ struct L0LsResult {
 // the penalised rule of this section and `cell` the cell's alpha; CARD true the cardinality rule of "local subsets" below and
 // `cell` its size k (k >= p is legal).  G: [p][ld] the Gram (symmetric; row j is read for column j), c: [p]; 2 eta goes on the
 // diagonal here.  start: [p] inside the box, or NULL for zero.  beta: [p] out.  A column whose d_j <= L0_PIVOT max d stays zero.
-template <bool CARD>
+// L1 (the penalised rule alone): lam ||beta||_1 joins F and every coordinate is l0_ls_coord_l1's -- nothing else changes.
+template <bool CARD, bool L1 = false>
 inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, int p, std::conditional_t<CARD, int, double> cell, double eta,
-                                 double big_M, double yy, bool swaps, const double* start, double* beta) {
+                                 double big_M, double yy, bool swaps, const double* start, double* beta, double lam = 0.0) {
+  static_assert(!(CARD && L1), "best subset with an l1 term is no estimator of the reference");
   L0LsResult R;
+  auto coord = [&](double u, double dj) {
+    if constexpr (L1)
+      return l0_ls_coord_l1(u, dj, big_M, lam);
+    else
+      return l0_ls_coord(u, dj, big_M);
+  };
   std::vector<double> r(c, c + p), d((size_t)p);
   const double alpha = CARD ? 0.0 : (double)cell, eta2 = 2.0 * eta;
   const int kmax = CARD ? (int)cell : 0;
@@ -1249,7 +1266,7 @@ inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, in
       int ib = -1;
       for (int i = 0; i < p; ++i) {
         if (beta[i] == 0.0) continue;
-        const double g = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * beta[i], d[(size_t)i], big_M).gain;
+        const double g = coord(r[(size_t)i] + d[(size_t)i] * beta[i], d[(size_t)i]).gain;
         if (g < gb) {  // (ties: the lowest i)
           gb = g;
           ib = i;
@@ -1275,7 +1292,7 @@ inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, in
       for (int j = 0; j < p; ++j) {
         const double dj = d[(size_t)j];
         if (CARD ? beta[j] == 0.0 : !(dj > 0.0)) continue;
-        const L0LsCoord co = l0_ls_coord(r[(size_t)j] + dj * beta[j], dj, big_M);
+        const L0LsCoord co = coord(r[(size_t)j] + dj * beta[j], dj);
         const double nb = CARD ? co.b : l0_ls_threshold(co, alpha);
         if (nb == beta[j]) continue;
         const double delta = nb - beta[j];
@@ -1300,7 +1317,7 @@ inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, in
         int jb = -1;
         for (int j = 0; j < p; ++j) {
           if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
-          const L0LsCoord co = l0_ls_coord(r[(size_t)j], d[(size_t)j], big_M);
+          const L0LsCoord co = coord(r[(size_t)j], d[(size_t)j]);
           if (co.gain > gb) {  // (ties: the lowest j)
             gb = co.gain;
             bb = co.b;
@@ -1323,12 +1340,12 @@ inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, in
       const double bi = beta[i];
       if (bi == 0.0) continue;
       const double* row = G + (size_t)i * ld;
-      const double gi = l0_ls_coord(r[(size_t)i] + d[(size_t)i] * bi, d[(size_t)i], big_M).gain;
+      const double gi = coord(r[(size_t)i] + d[(size_t)i] * bi, d[(size_t)i]).gain;
       double gb = -1.0, bb = 0.0;
       int jb = -1;
       for (int j = 0; j < p; ++j) {
         if (beta[j] != 0.0 || !(d[(size_t)j] > 0.0)) continue;
-        const L0LsCoord co = l0_ls_coord(r[(size_t)j] + row[j] * bi, d[(size_t)j], big_M);
+        const L0LsCoord co = coord(r[(size_t)j] + row[j] * bi, d[(size_t)j]);
         if (co.gain > gb) {  // (ties: the lowest j)
           gb = co.gain;
           bb = co.b;
@@ -1356,6 +1373,11 @@ inline L0LsResult l0_local_solve(const double* G, size_t ld, const double* c, in
     R.nnz += beta[j] != 0.0;
   }
   R.F = CARD ? -0.5 * acc : -0.5 * acc + alpha * (double)R.nnz;
+  if constexpr (L1) {  // + lam ||beta||_1
+    double l1 = 0.0;
+    for (int j = 0; j < p; ++j) l1 += std::fabs(beta[j]);
+    R.F = -0.5 * acc + lam * l1 + alpha * (double)R.nnz;
+  }
   return R;
 }
 
@@ -1541,6 +1563,82 @@ inline L0LcRefusal l0_lc_check(long long count, const double* const* row_weights
   R.lsf = l0_lsf_check(count, row_weights, n_effs, n, intercept, last_alone, n_cells, etas, etas, big_M, n_starts, starts, p);
   if (R.lsf.kind != L0_LSF_OK) R.kind = L0_LC_LSF;
   return R;
+}
+
+// ---- local search with an l1 term (slm_solve_l0_local_l1; l0_local_l1_kernel; tests/l1l0_local_host_test.cpp) -------------------
+//
+// A cell is (alpha, lam, eta); with H = G + 2 eta I,
+//     F(beta) = 1/2 beta^T H beta - c^T beta + lam ||beta||_1 + alpha ||beta||_0   over |beta_j| <= big_M
+// (eta = 0: the reference's L1L0 objective over 2n, singleton groups; DESIGN 4d "Local search with an l1 term").  The rule is the
+// local search's with ONE change, the coordinate (l0_ls_coord_l1, above): the descent keeps b iff gain > alpha, the swap scan
+// compares the same gains with l0_ls_swap_better, F gains lam ||beta||_1.  lam = 0 takes the decisions of the local search.  The
+// rule without a device is l0_local_solve<false, true>.  Nothing is proven.
+
+// What slm_solve_l0_local_l1 refuses before a device is touched, in this order: a NULL alphas or l1s; the first l1s[e] that is
+// negative or not finite; the first ridges[e] that is (ridges may be NULL: no ridge); then everything l0_lsf_check refuses, in
+// its order (`lsf`).  which: the cell.
+enum L0L1lKind { L0_L1L_OK = 0, L0_L1L_NULL, L0_L1L_L1, L0_L1L_RIDGE, L0_L1L_LSF };
+struct L0L1lRefusal {
+  L0L1lKind kind = L0_L1L_OK;
+  L0LsfRefusal lsf;
+  long long which = 0;
+};
+inline L0L1lRefusal l0_l1l_check(long long count, const double* const* row_weights, const long long* n_effs, long long n, bool intercept,
+                                 bool last_alone, long long n_cells, const double* alphas, const double* l1s, const double* ridges,
+                                 double big_M, long long n_starts, const double* starts, long long p) {
+  L0L1lRefusal R;
+  if (!alphas || !l1s) {
+    R.kind = L0_L1L_NULL;
+    return R;
+  }
+  for (long long e = 0; e < n_cells; ++e)
+    if (!(l1s[e] >= 0.0) || !std::isfinite(l1s[e])) {
+      R.kind = L0_L1L_L1;
+      R.which = e;
+      return R;
+    }
+  for (long long e = 0; ridges && e < n_cells; ++e)
+    if (!(ridges[e] >= 0.0) || !std::isfinite(ridges[e])) {
+      R.kind = L0_L1L_RIDGE;
+      R.which = e;
+      return R;
+    }
+  // (no ridges: l0_lsf_check gets the zeros they stand for -- as many as it reads, which is none beyond the problem cap)
+  const std::vector<double> none(ridges || n_cells < 1 || n_cells > L0_LS_MAX_PROBLEMS ? 1 : (size_t)n_cells, 0.0);
+  R.lsf = l0_lsf_check(count, row_weights, n_effs, n, intercept, last_alone, n_cells, alphas, ridges ? ridges : none.data(), big_M, n_starts,
+                       starts, p);
+  if (R.lsf.kind != L0_LSF_OK) R.kind = L0_L1L_LSF;
+  return R;
+}
+
+// The polish of a winner, on the rows of its support alone (as l0_ls_polish): the soft-threshold descent on the support to its
+// last digit (l0_l1_descent), then the exact sign-face solve of l0_l1_polish -- H_FF x = c_F - lam sign(b_F) - H_FB b_B, taken
+// only when every sign and the box hold.  A coefficient that comes to zero goes back as zero.  The point is kept only when its
+// value is not above the incoming point's, so the polish never raises F (the non-zeros can only get fewer).  beta: [p] in, out.
+// Returns 1/2 beta^T H beta - c^T beta + lam ||beta||_1 of what goes back, without the alpha term.
+inline double l0_l1l_polish(const double* G, size_t ld, const double* c, int p, double eta, double lam, double big_M, double* beta) {
+  std::vector<int> cols;
+  for (int j = 0; j < p; ++j)
+    if (beta[j] != 0.0) cols.push_back(j);
+  const int m = (int)cols.size();
+  if (m == 0) return 0.0;
+  std::vector<double> Hs((size_t)m * m), cs((size_t)m), b((size_t)m), b0((size_t)m);
+  std::vector<int> id((size_t)m);
+  for (int a = 0; a < m; ++a) {
+    id[(size_t)a] = a;
+    cs[(size_t)a] = c[cols[(size_t)a]];
+    b0[(size_t)a] = b[(size_t)a] = beta[cols[(size_t)a]];
+    for (int k = 0; k < m; ++k) Hs[(size_t)a * m + k] = G[(size_t)cols[(size_t)a] * ld + cols[(size_t)k]] + (a == k ? 2.0 * eta : 0.0);
+  }
+  const double v0 = l0_l1_value(Hs.data(), cs.data(), m, id.data(), m, lam, b0.data());
+  l0_l1_descent(Hs.data(), cs.data(), m, id.data(), m, lam, big_M, b.data());
+  double val = l0_l1_polish(Hs.data(), cs.data(), m, id.data(), m, lam, big_M, b.data());
+  if (!(val <= v0)) {
+    b = b0;
+    val = v0;
+  }
+  for (int a = 0; a < m; ++a) beta[cols[(size_t)a]] = b[(size_t)a];
+  return val;
 }
 
 // l0_eliminate_last at a leading dimension, in two parts (the note on cancellation above it applies unchanged).

@@ -108,6 +108,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_local_folds",
     "slm_solve_l0_local_subsets",
     "slm_solve_l0_local_groups",
+    "slm_solve_l0_local_l1",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -384,6 +385,7 @@ def load_library():
             "slm_solve_l0_local_folds": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_subsets": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_groups": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_l1": [vp, i32, vp, vp, i32, i32, vp, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1764,6 +1766,32 @@ class Dataset:
         return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
                 gsup[:, :gs].reshape(count, cells, gs), stats, [out[r * cells:(r + 1) * cells] for r in range(count)])
 
+    def solve_l0_local_l1(self, row_weights, n_effs, alphas, l1s, ridges=0.0, intercept=False, big_M=100.0, starts=None, swaps=True,
+                          n_cells=None, n_starts=None, binding=None):
+        """``slm_solve_l0_local_l1``: the l0 local search WITH AN L1 TERM (``l0_local_l1_kernel``, csrc/l0_local_kernels.hpp) --
+        ``1/2 b^T (G + 2 ridge I) b - c^T b + l1 ||b||_1 + alpha ||b||_0`` with ``|b_j| <= big_M`` at every cell ``(alphas[e],
+        l1s[e], ridges[e])``: with ``ridge = 0`` the objective of ``solve_l0_l1`` (the reference's ``L1L0``) with singleton groups,
+        for up to 1024 columns.  ``l1s``, ``ridges``: scalars or one value per cell; ``ridges=None`` reaches the engine as NULL
+        (no ridge).  Row sets, ``intercept``, ``starts``, ``swaps`` and the layout of the result as for ``solve_l0_local_folds``:
+        ``(betas [count, cells, ps], intercepts, objectives, winning starts, stats [count, cells, n_starts, 4], infos)``.  The
+        winner is polished on its support (soft-threshold descent, then the exact solve on its sign pattern); a coefficient the
+        polish brings to zero comes back as zero.  With every ``l1s[e] = 0`` the decisions are ``solve_l0_local_folds``'s.  Nothing
+        is proven."""
+        rws, nes = self._l0_local_row_sets(row_weights, n_effs)
+        al = None if alphas is None else np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        shape = (1,) if al is None else al.shape
+
+        def per_cell(v):  # (None reaches the engine as NULL, by the ctypes route)
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), shape), dtype=np.float64).reshape(-1)
+
+        l1, rd = per_cell(l1s), per_cell(ridges)
+        given = [len(v) for v in (al, l1, rd) if v is not None]
+        cells = (min(given) if given else 1) if n_cells is None else int(n_cells)
+        if any(g < cells for g in given):
+            raise ValueError("alphas, l1s and ridges must have n_cells entries")
+        return self._l0_local_rows("solve_l0_local_l1", 4, rws, nes, al, rd, cells, intercept, big_M, starts, swaps, n_starts, binding,
+                                   between=(l1,), optional_et=True)
+
     def _l0_local_row_sets(self, row_weights, n_effs):
         """The row sets of a local-search call: ``(the weight arrays or None, the divisors)``, one per set."""
         rws = [None if w is None else _f64(w, "row_weights", (self.n,)) for w in row_weights]
@@ -1772,9 +1800,12 @@ class Dataset:
             raise ValueError("row_weights and n_effs differ in length")
         return rws, nes
 
-    def _l0_local_rows(self, name, nstat, rws, nes, first, et, cells, intercept, big_M, starts, swaps, n_starts, binding):
-        """Both entries over row sets.  ``first``: the cells' alphas (``nstat`` 4 status words per problem) or their sizes (6:
-        grows and drops behind the four), coerced by the caller; a None there or in ``et`` reaches the engine as NULL."""
+    def _l0_local_rows(self, name, nstat, rws, nes, first, et, cells, intercept, big_M, starts, swaps, n_starts, binding, between=(),
+                       optional_et=False):
+        """The entries over row sets.  ``first``: the cells' alphas (``nstat`` 4 status words per problem) or their sizes (6:
+        grows and drops behind the four), coerced by the caller; a None there or in ``et`` reaches the engine as NULL.
+        ``between``: per-cell arrays the entry takes between ``first`` and ``et`` (the l1 entry's l1 weights); ``optional_et``: the
+        entry takes a NULL there by either route."""
         ps, count = self.p - (1 if intercept else 0), len(rws)
         st, ns = _l0_local_starts(starts, n_starts, (count, cells), ps, f"{count}, {cells}, n_starts, {ps}")
         # (else the engine refuses: the outputs only have to exist)
@@ -1785,8 +1816,9 @@ class Dataset:
         problems = cnt * ns if sized else 1
         ptrs = np.array([0 if w is None else w.ctypes.data for w in rws] or [0], dtype=np.uint64)  # (the table of row-weight pointers)
         ne = np.array(nes or [0], dtype=np.int64)
-        tail = (int(bool(intercept)), cells, _l0_local_pad(first), _l0_local_pad(et), float(big_M), ns, st if sized else None, int(bool(swaps)))
-        if first is None or et is None:
+        tail = ((int(bool(intercept)), cells, _l0_local_pad(first)) + tuple(_l0_local_pad(v) for v in between)
+                + (_l0_local_pad(et), float(big_M), ns, st if sized else None, int(bool(swaps))))
+        if first is None or (et is None and not optional_et) or any(v is None for v in between):
             binding = False  # (the compiled route takes arrays: a NULL goes by ctypes)
         (betas, icpts, objectives, winners, stats), infos, rc = self._l0_call(
             name, binding, (count, ptrs, ne) + tail,

@@ -25,6 +25,9 @@ the approximate twin of ``l0_profile`` up to 1024 columns -- and ``l0_local_subs
 to a thousand grouped columns of a cluster expansion: a group descent and one-for-one group swaps on
 ``1/2 b^T (G + 2 eta I) b - c^T b + alpha |cl(S)|``; they prove nothing, and the screen of the descent can miss a group.
 ``l0_local_group_cv`` / ``L0LocalGroupCV`` (``model/_l0_local_groups_cv.py``) cross-validate it, one launch per round.
+``l1l0_local_search`` / ``L1L0LocalPath`` (``model/_l1l0_local.py``) are the local search WITH AN L1 TERM, the approximate answer to
+``L1L0`` beyond its 64 columns: ``1/2 b^T (G + 2 ridge I) b - c^T b + eta ||b||_1 + alpha ||b||_0`` over an ``(alpha, eta)`` grid, ``eta``
+the l1 weight as in ``L1L0``; ``l1l0_local_cv`` / ``L1L0LocalCV`` (``model/_l1l0_local_cv.py``) cross-validate it.  Nothing is proven.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
@@ -37,6 +40,8 @@ from .model._l0_local_subsets import L0LocalSubsets, l0_local_subsets  # noqa: F
 from .model._l0_local_subsets_cv import L0LocalSubsetsCV, l0_local_subsets_cv  # noqa: F401  (their cross-validation, one launch per round; outside __all__)
 from .model._l0_profile import L0Profile, l0_profile  # noqa: F401  (not estimators: outside __all__, which tests pin)
 from .model._l1l0 import L1L0
+from .model._l1l0_local import L1L0LocalPath, l1l0_local_search  # noqa: F401  (the local search with an l1 term, up to 1024 columns; outside __all__)
+from .model._l1l0_local_cv import L1L0LocalCV, l1l0_local_cv  # noqa: F401  (its cross-validation, one launch per round; outside __all__)
 from .model._l1l0_profile import L1L0Profile, l1l0_profile  # noqa: F401  (L1L0 at every alpha from one search; outside __all__)
 from .model._miqp import L2L0, BestSubsetSelection, RegularizedL0, RidgedBestSubsetSelection
 

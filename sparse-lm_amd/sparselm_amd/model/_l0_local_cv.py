@@ -17,7 +17,8 @@ its held-out rows, and centring is by elimination of the ones column instead of 
 
 Limits: the local search's 1024 columns, at most 15 splits (folds plus all rows fill the Gram store's 16 entries),
 ``(splits + 1) x cells x starts <= 8192`` problems per launch; held-out scores are unweighted.  Not built: groups, an l1 term,
-rerouting ``GridSearchCV``.  (A bound on the cardinality: ``l0_local_subsets_cv``; groups and a hierarchy: ``l0_local_group_cv``.)
+rerouting ``GridSearchCV``.  (A bound on the cardinality: ``l0_local_subsets_cv``; groups and a hierarchy: ``l0_local_group_cv``; an l1
+term: ``l1l0_local_cv``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_cv``, ``L0LocalCV``).
 """
