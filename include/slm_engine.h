@@ -1015,6 +1015,41 @@ int slm_solve_l0_local_l1(slm_dataset* ds, int32_t count, const double* const* r
                           slm_point_info* info /* count * n_cells, or NULL */);
 
 /*
+ * (added under ABI 24: a new symbol beside slm_solve_l0_local, no existing entry, structure or constant changes, so the version
+ * stays 24 -- a caller that needs it looks the symbol up.)  LOCAL BOUND (l0_local_bound_kernel, csrc/l0_local_bound_kernels.hpp):
+ * the half slm_solve_l0_local lacks -- for every cell e = (alphas[e], etas[e]) a PROVEN LOWER BOUND on the objective that entry
+ * minimises, for up to SLM_L0_LOCAL_PMAX = 1024 columns, one wavefront per cell, one launch.  With G, c as for
+ * slm_solve_l0_local and the box |beta_j| <= big_M,
+ *       F(beta) = 1/2 beta^T (G + 2 etas[e] I) beta - c^T beta + alphas[e] ||beta||_0.
+ * The indicator is relaxed by the perspective of the ridge term with the big-M link; that leaves a separable convex penalty phi
+ * whose conjugate is phi*(t) = max(0, h(t) - alpha), h(t) = t^2 / (4 eta) for |t| <= 2 eta M, else |t| M - eta M^2 (eta = 0:
+ * |t| M).  For EVERY vector u, with t = c - G u (the plain G),
+ *       L(u) = -1/2 u^T G u - sum over all p columns of max(0, h(t_j) - alpha)   <=   min F:
+ * IT IS A BOUND FOR EVERY u.  The kernel looks for the u that makes it tightest, the minimiser of the relaxation
+ * P(b) = 1/2 b^T G b - c^T b + sum phi(b_j), by cyclic coordinate descent from starts[e] (clipped into the box; NULL: zero),
+ * stops a cell when P - L <= gap_tol max(|P|, alphas[e]) or after max_sweeps sweeps (<= 0: 10000), rebuilds t from u alone and
+ * writes lower_out[e] = max(L(u), L(0)), primal_out[e] = P(u), u_out[e] = u, stat_out[2e] = sweeps, stat_out[2e + 1] = the
+ * status word (1: the sweeps ran out before the gap closed).  The values are bounds WHATEVER the status: the status says only
+ * whether the relaxation was closed.  A column whose G_jj <= 1e-12 max G_kk keeps u_j = 0 and is still counted in the sum.
+ * WHERE IT IS WEAK: the bound is tight with a ridge (eta > 0) or a box that binds, and weak at eta = 0 under a loose big_M,
+ * where phi is (alpha / big_M) |b|, next to nothing (DESIGN 4d "Local bound" has the measured gaps).  big_M = 0: lower = 0
+ * without a launch.  info[e]: L = lower_out[e], mu = primal_out[e], kkt = mu - L, n_iter = sweeps, resid = the status word,
+ * mode = 11.
+ * Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when a cell ran out of sweeps.
+ * Refusals, all before a device is touched, each with its own message, in this order: NULL ds, alphas, etas or lower_out;
+ * n_cells < 1; n_cells > SLM_L0_LOCAL_MAX_PROBLEMS; big_M < 0; a negative or non-finite alphas[e] or etas[e]; gap_tol < 0
+ * (SLM_ERR_BAD_ARG); more than 1024 columns (SLM_ERR_UNSUPPORTED); a non-finite start (SLM_ERR_BAD_ARG); groups that are not
+ * singletons; a row-sharded dataset (SLM_ERR_UNSUPPORTED).
+ * Not here: groups and a hierarchy, the cardinality form, the l1 entry, row sets (folds), a Tikhonov matrix, strengthening
+ * eta = 0 by extracting a diagonal from G, using the bound to prune or to seed the exact search.
+ */
+int slm_solve_l0_local_bound(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
+                             double big_M, const double* starts /* n_cells * p, or NULL */, int32_t max_sweeps /* <=0: default */,
+                             double gap_tol /* <0: BAD_ARG; 0: run to max_sweeps */, double* lower_out /* n_cells */,
+                             double* primal_out /* n_cells, or NULL */, double* u_out /* n_cells * p, or NULL */,
+                             int32_t* stat_out /* n_cells * 2: sweeps, status word; or NULL */, slm_point_info* info /* n_cells or NULL */);
+
+/*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant
  * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The exact l0 search with the
  * EXCLUSION BOUND (csrc/l0_kernels.hpp, template parameter XB): the arguments, outputs, argument errors and contract of

@@ -542,6 +542,38 @@ py::tuple solve_l0_local(uintptr_t ds, int64_t p, int32_t n_cells, const arr_d& 
   return py::make_tuple(beta, objective, winner, info, rc);
 }
 
+// slm_solve_l0_local_bound: the proven lower bound of every cell.  starts: None (zero) or n_cells * p doubles.  Returns (bounds
+// [n_cells], relaxed objectives [n_cells], u [n_cells][p], (sweeps, status word) [n_cells][2], records as bytes, status).
+py::tuple solve_l0_local_bound(uintptr_t ds, int64_t p, int32_t n_cells, const arr_d& alphas, const arr_d& etas, double big_M,
+                               const py::object& starts, int32_t max_sweeps, double gap_tol) {
+  const int64_t cells = n_cells > 0 ? n_cells : 0;
+  if ((int64_t)alphas.size() < cells || (int64_t)etas.size() < cells) throw py::value_error("alphas and etas must have n_cells entries");
+  // (no cell, more cells than any call takes: the engine refuses them, the outputs only have to exist)
+  const bool sized = n_cells >= 1 && n_cells <= SLM_L0_LOCAL_MAX_PROBLEMS;
+  Keep keep;
+  const double* sp = sized ? vector_arg(starts, (int64_t)n_cells * p, "starts", keep) : nullptr;
+  const py::ssize_t cnt = sized ? n_cells : 1;
+  py::array_t<double> lower(cnt), primal(cnt), u({cnt, (py::ssize_t)p});
+  py::array_t<int32_t> stats({cnt, (py::ssize_t)2});
+  py::array info = info_bytes(cnt);
+  auto* rec = static_cast<slm_point_info*>(info.mutable_data());
+  std::memset(rec, 0, sizeof(*rec) * (size_t)cnt);
+  double *lp = lower.mutable_data(), *pp = primal.mutable_data(), *up = u.mutable_data();
+  int32_t* tp = stats.mutable_data();
+  std::memset(lp, 0, sizeof(double) * (size_t)cnt);
+  std::memset(pp, 0, sizeof(double) * (size_t)cnt);
+  std::memset(up, 0, sizeof(double) * (size_t)cnt * (size_t)p);
+  std::memset(tp, 0, sizeof(int32_t) * 2 * (size_t)cnt);
+  int rc;
+  {
+    py::gil_scoped_release nogil;
+    rc = slm_solve_l0_local_bound(reinterpret_cast<slm_dataset*>(ds), n_cells, alphas.data(), etas.data(), big_M, sp, max_sweeps, gap_tol, lp,
+                                  pp, up, tp, rec);
+  }
+  if (rc != SLM_ERR_NOT_CONVERGED) check(rc);
+  return py::make_tuple(lower, primal, u, stats, info, rc);
+}
+
 // slm_solve_l0_local_folds: the local search on several row sets of one dataset from one launch.  row_weights: a sequence of
 // arrays of n weights or None; n_effs: as many integers.  starts: None or count * n_cells * n_starts * ps doubles.  Returns
 // (coefficients [count * n_cells][ps], intercepts, objectives, winning starts [count * n_cells], the four status words of every
@@ -742,6 +774,7 @@ PYBIND11_MODULE(_slm_binding, m) {
   m.def("solve_l0_local_subsets", &solve_l0_local_subsets);
   m.def("solve_l0_local_groups", &solve_l0_local_groups);
   m.def("solve_l0_local_l1", &solve_l0_local_l1);
+  m.def("solve_l0_local_bound", &solve_l0_local_bound);
   m.def("path_extrapolation", [](const arr_d& pts) {
     if (pts.size() % 3 != 0) throw py::value_error("points must be (K, 3)");
     const int64_t K = pts.size() / 3;

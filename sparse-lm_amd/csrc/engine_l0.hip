@@ -44,6 +44,7 @@
 #include "l0_kernels.hpp"
 #include "l0_local_kernels.hpp"
 #include "l0_local_group_kernels.hpp"
+#include "l0_local_bound_kernels.hpp"
 
 namespace {
 
@@ -867,6 +868,25 @@ int l0_fetch_rows(hipStream_t s, const double* G, size_t ld, int width, const st
   return SLM_OK;
 }
 
+// The Gram lookup of the local family (solve_l0_local_folds_impl, solve_l0_local_bound_impl): row set b -- its weights on the
+// device wdev[b] (the dataset's own where the caller brings none), its divisor neff[b] -- is found in the dataset's store by
+// fingerprint or built and filed here; held[b] gets a copy of the entry, which holds its blocks for the call.
+int l0_local_hold_grams(slm_dataset* ds, int count, const double* const* row_weights, const int64_t* n_effs, const double* const* wdev,
+                        const double* neff, slm_dataset::CovEntry* held) {
+  std::vector<double> fp(2 * (size_t)count);
+  SLM_TRY(cov_fingerprints(ds, wdev, count, fp.data()));
+  for (int b = 0; b < count; ++b) {
+    int entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
+    if (entry < 0) {  // not from the folds' call (or pushed out of the store by a later one): built here
+      SLM_TRY(slm_dataset_covariance(ds, row_weights[b], row_weights[b] ? n_effs[b] : 0));
+      entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
+    }
+    if (entry < 0) return fail(SLM_ERR_HIP, "the Gram of row set %d was not filed", b);
+    held[b] = ds->cov[(size_t)entry];
+  }
+  return SLM_OK;
+}
+
 // The l0 local search (DESIGN 4d "Local search", "Local search over folds", "Local subsets"): NOT a search over supports and
 // not this unit's pipeline -- no order, no seed, no block image -- and ONE body, solve_l0_local_folds_impl, for its four entries:
 //   slm_solve_l0_local_folds    `count` row sets of one dataset -- the training rows of a cross-validation's folds, then all rows
@@ -1057,18 +1077,8 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
     HIP_TRY(hipMemcpyAsync(wts.dev + (size_t)b * (size_t)n, row_weights[b], sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
   }
   if (all_given) SLM_TRY(slm_dataset_covariance_folds(ds, row_weights, n_effs, count));
-  std::vector<double> fp(2 * (size_t)count);
-  SLM_TRY(cov_fingerprints(ds, wdev.data(), count, fp.data()));
   std::vector<slm_dataset::CovEntry> held((size_t)count);  // (a copy holds the entry's blocks: the store may drop it, the memory stays)
-  for (int b = 0; b < count; ++b) {
-    int entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
-    if (entry < 0) {  // not from the folds' call (or pushed out of the store by a later one): built here
-      SLM_TRY(slm_dataset_covariance(ds, row_weights[b], row_weights[b] ? n_effs[b] : 0));
-      entry = cov_find(ds, fp[2 * (size_t)b], fp[2 * (size_t)b + 1], neff[(size_t)b]);
-    }
-    if (entry < 0) return fail(SLM_ERR_HIP, "the Gram of row set %d was not filed", b);
-    held[(size_t)b] = ds->cov[(size_t)entry];
-  }
+  SLM_TRY(l0_local_hold_grams(ds, count, row_weights, n_effs, wdev.data(), neff.data(), held.data()));
 
   // ---- per row set: c on the host (the polish reads it); with an intercept the last row of G too, and the eliminated vectors ---------
   std::vector<double> ch((size_t)count * p), last((size_t)count * p), cs((size_t)count * ld, 0.0), xmean((size_t)count * ps, 0.0);
@@ -1305,6 +1315,126 @@ int solve_l0_local_folds_impl(L0LocalKind kind, slm_dataset* ds, int32_t count, 
   return SLM_OK;
 }
 
+// The local bound (DESIGN 4d "Local bound"; the mathematics: l0_host.hpp "local bound"): for every cell a PROVEN lower bound on the
+// objective slm_solve_l0_local minimises, from one launch of l0_local_bound_kernel (csrc/l0_local_bound_kernels.hpp), one
+// wavefront per cell.  The check (l0_bound_check, and the dataset's shape) comes before a device is touched; big_M = 0 leaves
+// beta = 0 alone, whose objective 0 is the bound, and launches nothing.  The dataset's own rows, their Gram filed and held as
+// for the local search (l0_local_hold_grams) and read in place; lam and tauc of every cell are the host's (l0_lb_cell) and go
+// up beside the alphas and etas.  What comes back is a bound whatever the status: the status says only whether the relaxation
+// was closed.  The record, per cell:
+//
+//   n_iter    resid                          mu        L           kkt    mode
+//   sweeps    the status word (1: the        P(u)      the bound   P - L  11
+//             sweeps ran out)
+int solve_l0_local_bound_impl(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M, const double* starts,
+                              int32_t max_sweeps, double gap_tol, double* lower_out, double* primal_out, double* u_out, int32_t* stat_out,
+                              slm_point_info* info) {
+  if (!ds || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  long long which = 0;
+  switch (l0_bound_check(n_cells, alphas, etas, big_M, starts, ds->p, gap_tol, ds->singleton, row_sharded(ds), &which)) {
+    case L0_LB_OK: break;
+    case L0_LB_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    case L0_LB_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
+    case L0_LB_PROBLEMS: return fail(SLM_ERR_BAD_ARG, "n_cells must be at most %d cells (got %d)", L0_LS_MAX_PROBLEMS, n_cells);
+    case L0_LB_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
+    case L0_LB_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", which);
+    case L0_LB_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", which);
+    case L0_LB_GAP_TOL: return fail(SLM_ERR_BAD_ARG, "gap_tol must be >= 0");
+    case L0_LB_WIDTH: return fail(SLM_ERR_UNSUPPORTED, "the l0 local bound takes up to %d columns (got %lld)", L0_LS_PMAX, (long long)ds->p);
+    case L0_LB_START: return fail(SLM_ERR_BAD_ARG, "starts[%lld] is not a finite number", which);
+    case L0_LB_GROUPS: return fail(SLM_ERR_UNSUPPORTED, "the l0 local bound is not built for groups: every column must be its own group");
+    case L0_LB_SHARDED: return fail(SLM_ERR_UNSUPPORTED, "the l0 local bound is not built for row-sharded datasets");
+  }
+  const int p = (int)ds->p, sweeps_cap = max_sweeps > 0 ? max_sweeps : L0_LB_SWEEPS;
+  auto record = [&](int e, double lower, double primal, int sweeps, int status) {
+    lower_out[e] = lower;
+    if (primal_out) primal_out[e] = primal;
+    if (stat_out) {
+      stat_out[2 * e] = sweeps;
+      stat_out[2 * e + 1] = status;
+    }
+    if (!info) return;
+    l0_report(info + e, status == 0, 0.0, primal - lower, primal, lower);
+    info[e].n_iter = sweeps;
+    info[e].resid = (double)status;
+    info[e].mode = L0_LB_MODE;
+  };
+  if (big_M == 0.0) {  // the box holds beta = 0 alone: F = 0 is the optimum and the bound
+    if (u_out) std::fill(u_out, u_out + (size_t)n_cells * p, 0.0);
+    for (int e = 0; e < n_cells; ++e) record(e, 0.0, 0.0, 0, 0);
+    return SLM_OK;
+  }
+  const size_t ld = (size_t)ds->ld;
+  slm_engine* eng = ds->eng;
+  HIP_TRY(hipSetDevice(eng->device));
+  hipStream_t s = eng->stream;
+
+  // ---- the Gram of the dataset's own rows: found or filed, held for the call ------------------------------------------------------
+  const double* const own_rows[1] = {nullptr};
+  const int64_t n_eff[1] = {0};
+  const double* const wdev[1] = {ds->rw};
+  const double neff[1] = {(double)ds->n_global};
+  slm_dataset::CovEntry held;
+  SLM_TRY(l0_local_hold_grams(ds, 1, own_rows, n_eff, wdev, neff, &held));
+  std::vector<double> ch((size_t)p);
+  HIP_TRY(hipMemcpyAsync(ch.data(), held.c, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (double v : ch)
+    if (!std::isfinite(v)) return fail(SLM_ERR_NON_FINITE, "X^T y holds a non-finite value (non-finite data)");
+
+  // ---- one block: alphas | etas | lams | taus | starts, then what comes back: lower | primal | the two status words | u -------------
+  const size_t nc = (size_t)n_cells, n_start_words = starts ? nc * p : 0;
+  const size_t off_eta = nc, off_lam = 2 * nc, off_tau = 3 * nc, off_st = 4 * nc, off_low = off_st + n_start_words, off_pri = off_low + nc,
+               off_stat = off_pri + nc, off_u = off_stat + nc, words = off_u + nc * p;
+  std::vector<double> h(words, 0.0);
+  memcpy(h.data(), alphas, sizeof(double) * nc);
+  memcpy(h.data() + off_eta, etas, sizeof(double) * nc);
+  for (size_t e = 0; e < nc; ++e) {
+    const L0LbCell cell = l0_lb_cell(alphas[e], etas[e], big_M);
+    h[off_lam + e] = cell.lam;
+    h[off_tau + e] = cell.tauc;
+  }
+  if (starts) memcpy(h.data() + off_st, starts, sizeof(double) * n_start_words);
+  unsigned long long* dev = nullptr;
+  L0DevGuard guard{dev, s};
+  SLM_TRY(dalloc(&dev, words));
+  double* dd = reinterpret_cast<double*>(dev);
+  HIP_TRY(hipMemcpyAsync(dd, h.data(), sizeof(double) * off_low, hipMemcpyHostToDevice, s));
+  L0LbArgs k;
+  memset(&k, 0, sizeof(k));
+  k.G = held.G;
+  k.c = held.c;
+  k.alphas = dd;
+  k.etas = dd + off_eta;
+  k.lams = dd + off_lam;
+  k.taus = dd + off_tau;
+  k.starts = starts ? dd + off_st : nullptr;
+  k.lower_out = dd + off_low;
+  k.primal_out = dd + off_pri;
+  k.stat_out = reinterpret_cast<int*>(dd + off_stat);
+  k.u_out = dd + off_u;
+  k.ld = (long long)ld;
+  k.p = p; k.n_cells = n_cells; k.max_sweeps = sweeps_cap;
+  k.big_M = big_M; k.gap_tol = gap_tol;
+  // (a cell is one wave; the grid as for the local search: up to two workgroups a CU, the cells beyond by the grid-stride loop)
+  const int blocks = std::min((n_cells + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * eng->cus));
+  hipLaunchKernelGGL(l0_local_bound_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+  SLM_TRY(check_launch());
+  HIP_TRY(hipMemcpyAsync(h.data() + off_low, dd + off_low, sizeof(double) * (words - off_low), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int* stat = reinterpret_cast<const int*>(h.data() + off_stat);
+  if (u_out) memcpy(u_out, h.data() + off_u, sizeof(double) * nc * (size_t)p);
+  int unclosed = 0, first = -1;
+  for (int e = 0; e < n_cells; ++e) {
+    record(e, h[off_low + (size_t)e], h[off_pri + (size_t)e], stat[2 * e], stat[2 * e + 1]);
+    if (stat[2 * e + 1] != 0 && unclosed++ == 0) first = e;
+  }
+  if (unclosed)
+    return fail(SLM_ERR_NOT_CONVERGED, "the local bound ran out of sweeps (%d) in %d of %d cells (the first: %d): the relaxation is not closed "
+                "there, the values are bounds all the same", sweeps_cap, unclosed, n_cells, first);
+  return SLM_OK;
+}
+
 }  // namespace
 
 // The l0 local search on up to 16 row sets of one dataset: every (row set, cell, start) problem from one launch.
@@ -1348,6 +1478,14 @@ extern "C" int slm_solve_l0_local_l1(slm_dataset* ds, int32_t count, const doubl
                                      slm_point_info* info) {
   return solve_l0_local_folds_impl(L0_LOCAL_L1, ds, count, row_weights, n_effs, intercept, n_cells, alphas, nullptr, ridges, big_M, n_starts,
                                    starts, swaps, beta_out, intercept_out, objective_out, start_out, stat_out, info, nullptr, l1s);
+}
+
+// The local bound: for every cell a proven lower bound on the objective of slm_solve_l0_local, from one launch of
+// l0_local_bound_kernel -- a bound whatever the status, tight with a ridge or a real box, weak at eta = 0 under a loose big_M.
+extern "C" int slm_solve_l0_local_bound(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                        const double* starts, int32_t max_sweeps, double gap_tol, double* lower_out, double* primal_out,
+                                        double* u_out, int32_t* stat_out, slm_point_info* info) {
+  return solve_l0_local_bound_impl(ds, n_cells, alphas, etas, big_M, starts, max_sweeps, gap_tol, lower_out, primal_out, u_out, stat_out, info);
 }
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.

@@ -1977,4 +1977,215 @@ inline L0LgRefusal l0_lg_check(long long count, const double* const* row_weights
   return R;
 }
 
+// ---- local bound (slm_solve_l0_local_bound; csrc/l0_local_bound_kernels.hpp; tests/l0_local_bound_host_test.cpp) ----------------
+//
+// The half the local search lacks: a PROVEN lower bound on the objective it minimises.  For a cell (alpha, eta) and the box
+// |beta_j| <= M,  F(beta) = 1/2 beta^T (G + 2 eta I) beta - c^T beta + alpha ||beta||_0.  The indicator is relaxed by the
+// perspective of the ridge term with the big-M link (z_j in [0, 1], |beta_j| <= M z_j, cost eta beta_j^2 / z_j + alpha z_j);
+// minimising over z leaves a separable convex penalty phi.  With tau = sqrt(alpha / eta) (infinite at eta = 0):
+//     M >= tau:  phi(b) = 2 sqrt(alpha eta) |b| on |b| <= tau,  eta b^2 + alpha on tau <= |b| <= M
+//     M <  tau:  phi(b) = (eta M + alpha / M) |b| on |b| <= M
+// and phi*(t) = max(0, h(t) - alpha) with h(t) = t^2 / (4 eta) on |t| <= 2 eta M, else |t| M - eta M^2 (eta = 0: |t| M).  g(b) =
+// 1/2 b^T G b - c^T b is convex, so by Fenchel duality, for EVERY vector u, with t = c - G u (the plain G: the ridge is in phi),
+//     L(u) = -1/2 u^T G u - sum over ALL p columns of max(0, h(t_j) - alpha)   <=   min F.
+// It is tightest at the minimiser of P(b) = g(b) + sum phi(b_j), where L = P; cyclic coordinate descent on P finds it
+// (l0_lb_coord is the exact coordinate minimiser).  A column whose G_jj <= L0_PIVOT max G_kk keeps u_j = 0 and is still counted
+// in the sum.  The bound is tight with a ridge or a real box and weak at eta = 0 under a loose M (DESIGN 4d "Local bound").
+//
+// The functions below hold every number kernel and twin compute, with contraction of a*b + c switched off where the compiler
+// would decide it, so that both give the same bits on any host (one with fused multiply-adds too); the one contracted step is
+// the rank-one update of t (l0_ls_axpy on the device, std::fma here).  Under clang -- the device pass and hipcc's host pass --
+// L0_LB_STRICT at the head of a body switches contraction off for that body; under GCC, which has no such pragma inside a
+// function, the whole section stands between push_options / optimize("fp-contract=off") / pop_options.  (The tests and tools
+// that compile this header pass -ffp-contract=off as well.)
+// l0_lb_coord, l0_lb_phi, l0_lb_conj, l0_lb_changed and l0_lb_closed are the ONE definition kernel and twin share: constexpr
+// functions, which HIP-clang treats as __host__ __device__ without the words (as it does l0_ls_coord and l0_ls_coord_l1 above),
+// so that a plain C++ compiler reads this header too.
+#if defined(__clang__)
+#define L0_LB_STRICT _Pragma("clang fp contract(off)")
+#define L0_LB_INLINE __attribute__((always_inline))  // (a call left in the kernel would cost it its registers)
+#else
+#define L0_LB_STRICT
+#define L0_LB_INLINE
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#endif
+constexpr int L0_LB_SWEEPS = 10000;       // sweeps of one cell where the caller names none
+constexpr double L0_LB_GAP_DEFAULT = 1e-9;  // the default of the callers above the ABI: P - L <= gap_tol max(|P|, alpha) ends a cell
+constexpr int L0_LB_MODE = 11;            // slm_point_info.mode of the entry
+
+// what a cell's phi needs beside (alpha, eta, M): lam, its slope at zero, and tauc = min(tau, M), where its linear piece ends.
+// Computed once per cell on the host (the one place with a square root) and handed to kernel and twin alike.  big_M > 0.
+struct L0LbCell {
+  double lam, tauc;
+};
+inline L0LbCell l0_lb_cell(double alpha, double eta, double big_M) {
+  L0_LB_STRICT
+  if (eta > 0.0) {
+    const double tau = std::sqrt(alpha / eta);
+    if (big_M >= tau) return L0LbCell{2.0 * std::sqrt(alpha * eta), tau};
+    return L0LbCell{eta * big_M + alpha / big_M, big_M};
+  }
+  return L0LbCell{alpha / big_M, big_M};
+}
+// the coordinate step: the minimiser over |b| <= M of 1/2 a b^2 - s b + phi(b), a = G_jj > 0, s = t_j + a u_j
+L0_LB_INLINE constexpr double l0_lb_coord(double s, double a, double eta, double lam, double tauc, double big_M) {
+  L0_LB_STRICT
+  const double as = s < 0.0 ? -s : s;
+  const double b1 = as > lam ? (as - lam) / a : 0.0;
+  if (b1 <= tauc) return s < 0.0 ? -b1 : b1;
+  double b2 = as / (a + 2.0 * eta);
+  b2 = b2 < tauc ? tauc : (b2 > big_M ? big_M : b2);
+  return s < 0.0 ? -b2 : b2;
+}
+L0_LB_INLINE constexpr double l0_lb_phi(double b, double alpha, double eta, double lam, double tauc) {
+  L0_LB_STRICT
+  const double ab = b < 0.0 ? -b : b;
+  return ab <= tauc ? lam * ab : eta * ab * ab + alpha;
+}
+// phi*(t) = max(0, h(t) - alpha)
+L0_LB_INLINE constexpr double l0_lb_conj(double t, double alpha, double eta, double big_M) {
+  L0_LB_STRICT
+  const double at = t < 0.0 ? -t : t;
+  double h = 0.0;
+  if (eta > 0.0)
+    h = at <= 2.0 * eta * big_M ? at * at / (4.0 * eta) : at * big_M - eta * big_M * big_M;
+  else if (at > 0.0)
+    h = at * big_M;
+  const double v = h - alpha;
+  return v > 0.0 ? v : 0.0;
+}
+// has the coordinate changed?  (A NaN -- non-finite data -- is no change: it must not keep a cell sweeping.)
+L0_LB_INLINE constexpr bool l0_lb_changed(double nb, double old) { return nb < old || nb > old; }
+// the stopping rule after a sweep
+L0_LB_INLINE constexpr bool l0_lb_closed(double P, double L, double alpha, double gap_tol) {
+  L0_LB_STRICT
+  const double ap = P < 0.0 ? -P : P;
+  return P - L <= gap_tol * (ap > alpha ? ap : alpha);
+}
+
+// The kernel's sum of one term per column, in its order: lane j & 63 adds its columns in ascending order from zero, then the
+// wave's butterfly (l0_wave_sum: v += v[lane ^ off], off = 32 .. 1), which leaves the same bits in every lane.
+inline double l0_lb_wave_sum(const double* lanes) {
+  L0_LB_STRICT
+  double v[64], w[64];
+  for (int i = 0; i < 64; ++i) v[i] = lanes[i];
+  for (int off = 32; off >= 1; off >>= 1) {
+    for (int i = 0; i < 64; ++i) w[i] = v[i] + v[i ^ off];
+    for (int i = 0; i < 64; ++i) v[i] = w[i];
+  }
+  return v[0];
+}
+// P(u) and L(u) from u and t = c - G u, with u^T G u = u^T (c - t):
+//     P = -1/2 sum u_j (c_j + t_j) + sum phi(u_j),     L = -1/2 sum u_j (c_j - t_j) - sum phi*(t_j)
+struct L0LbValues {
+  double P, L;
+};
+inline L0LbValues l0_lb_values(const double* u, const double* t, const double* c, int p, double alpha, double eta, double big_M,
+                               const L0LbCell& cell) {
+  L0_LB_STRICT
+  double qp[64] = {0.0}, ql[64] = {0.0}, sp[64] = {0.0}, sc[64] = {0.0};
+  for (int j = 0; j < p; ++j) {
+    const int l = j & 63;
+    qp[l] += u[j] * (c[j] + t[j]);
+    ql[l] += u[j] * (c[j] - t[j]);
+    sp[l] += l0_lb_phi(u[j], alpha, eta, cell.lam, cell.tauc);
+    sc[l] += l0_lb_conj(t[j], alpha, eta, big_M);
+  }
+  return L0LbValues{-0.5 * l0_lb_wave_sum(qp) + l0_lb_wave_sum(sp), -0.5 * l0_lb_wave_sum(ql) - l0_lb_wave_sum(sc)};
+}
+
+struct L0LbResult {
+  double lower = 0.0;   // max(L(u), L(0)): the bound
+  double primal = 0.0;  // P(u): the relaxation's value at u
+  int sweeps = 0, status = 0;  // status: L0_LS_SWEEPS_OUT when the sweeps ran out before the gap closed
+  long long changes = 0;       // columns of G applied to t in the sweeps: what the time goes to
+};
+// The kernel's twin without a device, change for change.  G: [p][ld] (row j is read for column j), c: [p], start: [p] or NULL
+// (clipped into the box), u: [p] out.  big_M > 0; max_sweeps >= 1; gap_tol >= 0 (0: every sweep is run).
+inline L0LbResult l0_bound_solve(const double* G, size_t ld, const double* c, int p, double alpha, double eta, double big_M,
+                                 const double* start, int max_sweeps, double gap_tol, double* u) {
+  L0_LB_STRICT
+  L0LbResult R;
+  const L0LbCell cell = l0_lb_cell(alpha, eta, big_M);
+  std::vector<double> t(c, c + p), a((size_t)p);
+  double amax = 0.0;
+  for (int j = 0; j < p; ++j) {
+    a[(size_t)j] = G[(size_t)j * ld + j];
+    u[j] = 0.0;
+    amax = std::fmax(amax, a[(size_t)j]);
+  }
+  for (int j = 0; j < p; ++j)
+    if (!(a[(size_t)j] > L0_PIVOT * amax)) a[(size_t)j] = 0.0;  // a = 0 marks a column that keeps u_j = 0
+  const double L0 = l0_lb_values(u, t.data(), c, p, alpha, eta, big_M, cell).L;
+  auto axpy = [&](int j, double w) {  // t += w G[:, j]: the device's contracted multiply-add
+    const double* row = G + (size_t)j * ld;
+    for (int k = 0; k < p; ++k) t[(size_t)k] = std::fma(w, row[k], t[(size_t)k]);
+  };
+  auto build = [&]() {  // t = c - G u, column by column in ascending order
+    for (int k = 0; k < p; ++k) t[(size_t)k] = c[k];
+    for (int j = 0; j < p; ++j)
+      if (u[j] != 0.0) axpy(j, -u[j]);
+  };
+  if (start)
+    for (int j = 0; j < p; ++j)
+      if (a[(size_t)j] > 0.0) u[j] = start[j] < -big_M ? -big_M : (start[j] > big_M ? big_M : start[j]);
+  build();
+  for (int sw = 0;; ++sw) {
+    if (sw == max_sweeps) {
+      R.status |= L0_LS_SWEEPS_OUT;
+      break;
+    }
+    for (int j = 0; j < p; ++j) {
+      const double aj = a[(size_t)j];
+      if (!(aj > 0.0)) continue;
+      const double nb = l0_lb_coord(t[(size_t)j] + aj * u[j], aj, eta, cell.lam, cell.tauc, big_M);
+      if (!l0_lb_changed(nb, u[j])) continue;
+      const double delta = nb - u[j];
+      u[j] = nb;
+      axpy(j, -delta);
+      ++R.changes;
+    }
+    ++R.sweeps;
+    const L0LbValues v = l0_lb_values(u, t.data(), c, p, alpha, eta, big_M, cell);
+    if (l0_lb_closed(v.P, v.L, alpha, gap_tol)) break;
+  }
+  build();  // no running residual feeds the certificate
+  const L0LbValues v = l0_lb_values(u, t.data(), c, p, alpha, eta, big_M, cell);
+  R.lower = v.L > L0 ? v.L : L0;
+  R.primal = v.P;
+  return R;
+}
+
+#if !defined(__clang__)
+#pragma GCC pop_options
+#endif
+
+// What slm_solve_l0_local_bound refuses before a device is touched, in this order (slm_solve_l0_local's where the checks
+// coincide); which: the offending cell, or entry of starts.
+enum L0LbRefusal { L0_LB_OK = 0, L0_LB_NULL, L0_LB_CELLS, L0_LB_PROBLEMS, L0_LB_BIG_M, L0_LB_ALPHA, L0_LB_ETA, L0_LB_GAP_TOL, L0_LB_WIDTH,
+                   L0_LB_START, L0_LB_GROUPS, L0_LB_SHARDED };
+inline L0LbRefusal l0_bound_check(long long n_cells, const double* alphas, const double* etas, double big_M, const double* starts,
+                                  long long p, double gap_tol, bool singleton, bool sharded, long long* which = nullptr) {
+  if (!alphas || !etas) return L0_LB_NULL;
+  if (n_cells < 1) return L0_LB_CELLS;
+  if (n_cells > L0_LS_MAX_PROBLEMS) return L0_LB_PROBLEMS;
+  if (!(big_M >= 0.0)) return L0_LB_BIG_M;
+  for (long long e = 0; e < n_cells; ++e) {
+    if (which) *which = e;
+    if (!(alphas[e] >= 0.0) || !std::isfinite(alphas[e])) return L0_LB_ALPHA;
+    if (!(etas[e] >= 0.0) || !std::isfinite(etas[e])) return L0_LB_ETA;
+  }
+  if (!(gap_tol >= 0.0)) return L0_LB_GAP_TOL;
+  if (p > L0_LS_PMAX) return L0_LB_WIDTH;
+  for (long long e = 0; starts && e < n_cells * p; ++e)
+    if (!std::isfinite(starts[e])) {
+      if (which) *which = e;
+      return L0_LB_START;
+    }
+  if (!singleton) return L0_LB_GROUPS;
+  if (sharded) return L0_LB_SHARDED;
+  return L0_LB_OK;
+}
+
 }  // namespace slm

@@ -109,6 +109,7 @@ ABI_SYMBOLS = (
     "slm_solve_l0_local_subsets",
     "slm_solve_l0_local_groups",
     "slm_solve_l0_local_l1",
+    "slm_solve_l0_local_bound",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -386,6 +387,7 @@ def load_library():
             "slm_solve_l0_local_subsets": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_groups": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_l1": [vp, i32, vp, vp, i32, i32, vp, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_bound": [vp, i32, vp, vp, dbl, vp, i32, dbl, vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1791,6 +1793,33 @@ class Dataset:
             raise ValueError("alphas, l1s and ridges must have n_cells entries")
         return self._l0_local_rows("solve_l0_local_l1", 4, rws, nes, al, rd, cells, intercept, big_M, starts, swaps, n_starts, binding,
                                    between=(l1,), optional_et=True)
+
+    def solve_l0_local_bound(self, alphas, etas=0.0, big_M=100.0, starts=None, max_sweeps=0, gap_tol=1e-9, n_cells=None, binding=None):
+        """``slm_solve_l0_local_bound``: the LOCAL BOUND (``l0_local_bound_kernel``, csrc/l0_local_bound_kernels.hpp) -- for every
+        cell ``(alphas[e], etas[e])`` a PROVEN lower bound on ``min 1/2 b^T (G + 2 eta I) b - c^T b + alpha ||b||_0`` over
+        ``|b_j| <= big_M``, the objective ``solve_l0_local`` minimises, up to 1024 columns, singleton groups, one launch.  The bound
+        is ``L(u) = -1/2 u^T G u - sum_j max(0, h(c_j - (G u)_j) - alpha)``, valid for every ``u``; the kernel looks for the
+        tightest one by coordinate descent on the convex relaxation from ``starts`` (None, or ``[cells, p]``, clipped into the
+        box) and stops a cell at a relative gap of ``gap_tol`` or after ``max_sweeps`` sweeps (<= 0: 10000).  Tight with a ridge
+        or a box that binds, weak at ``eta = 0`` under a loose ``big_M``.  Returns ``(bounds [cells], relaxed objectives [cells],
+        u [cells, p], stats [cells, 2] (sweeps, status word), infos)``; ``infos`` is one dict per cell with ``lower_bound``,
+        ``relaxed_objective``, ``sweeps``, ``converged``, ``status`` (``"closed"``, ``"sweep_cap"``) and ``call_status`` (what the
+        call returned: ``SLM_OK``, or ``SLM_ERR_NOT_CONVERGED`` when some cell ran out of sweeps).  The values are bounds whatever
+        the status."""
+        al, et, cells = _l0_local_cells(alphas, etas, n_cells)
+        sized = 1 <= cells <= L0_LOCAL_MAX_PROBLEMS  # (else the engine refuses: the outputs only have to exist)
+        st = None if starts is None else np.ascontiguousarray(starts, dtype=np.float64).reshape(-1)
+        if st is not None and sized and st.size != cells * self.p:
+            raise ValueError(f"starts has {st.size} entries, expected {cells * self.p}")
+        cnt = cells if sized else 1
+        args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), st if sized else None, int(max_sweeps), float(gap_tol))
+        (lower, primal, u, stats), infos, rc = self._l0_call(
+            "solve_l0_local_bound", binding, args,
+            [np.zeros(cnt), np.zeros(cnt), np.zeros((cnt, self.p)), np.zeros((cnt, 2), dtype=np.int32)], records=cnt)
+        out = [{"lower_bound": float(infos[e]["L"]), "relaxed_objective": float(infos[e]["mu"]), "sweeps": int(infos[e]["n_iter"]),
+                "converged": int(infos[e]["status"]) == SLM_OK, "status": "closed" if int(infos[e]["resid"]) == 0 else "sweep_cap",
+                "call_status": int(rc)} for e in range(cnt)]
+        return lower, primal, u, stats, out
 
     def _l0_local_row_sets(self, row_weights, n_effs):
         """The row sets of a local-search call: ``(the weight arrays or None, the divisors)``, one per set."""

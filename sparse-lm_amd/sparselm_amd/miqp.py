@@ -28,11 +28,16 @@ to a thousand grouped columns of a cluster expansion: a group descent and one-fo
 ``l1l0_local_search`` / ``L1L0LocalPath`` (``model/_l1l0_local.py``) are the local search WITH AN L1 TERM, the approximate answer to
 ``L1L0`` beyond its 64 columns: ``1/2 b^T (G + 2 ridge I) b - c^T b + eta ||b||_1 + alpha ||b||_0`` over an ``(alpha, eta)`` grid, ``eta``
 the l1 weight as in ``L1L0``; ``l1l0_local_cv`` / ``L1L0LocalCV`` (``model/_l1l0_local_cv.py``) cross-validate it.  Nothing is proven.
+``l0_local_bound`` / ``L0LocalBound`` (``model/_l0_local_bound.py``) are the LOCAL BOUND, the half the local search lacks: a PROVEN lower
+bound on the objective of ``l0_local_search`` at every cell of its ``(alpha, eta)`` grid, up to 1024 columns, from one launch;
+``L0LocalBound.gap(path)`` is the proven relative gap per cell.  Tight with a ridge or a box that binds, weak at ``eta = 0`` under a loose
+``big_M``.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
 from .model._l0_grid_cv import L0ProfileGridCV, l1l0_profile_cv, l2l0_profile_cv  # noqa: F401  (CV over (alpha, eta) from one launch; outside __all__)
 from .model._l0_local import L0LocalPath, l0_local_search  # noqa: F401  (approximate, up to 1024 columns; outside __all__)
+from .model._l0_local_bound import L0LocalBound, l0_local_bound  # noqa: F401  (a proven lower bound for the local search's grid; outside __all__)
 from .model._l0_local_cv import L0LocalCV, l0_local_cv  # noqa: F401  (the local search of every CV fold from one launch per round; outside __all__)
 from .model._l0_local_groups import L0LocalGroupPath, l0_local_group_search  # noqa: F401  (the local search with groups and a hierarchy; outside __all__)
 from .model._l0_local_groups_cv import L0LocalGroupCV, l0_local_group_cv  # noqa: F401  (its cross-validation, one launch per round; outside __all__)

@@ -21,7 +21,8 @@ rounding is no improvement); the rounds end early when no cell improved.
 Not built: groups and a hierarchy, an l1 term, a general Tikhonov matrix, constraints, handing the result to the exact search
 as its seed.  (Cross-validation folds in the launch: ``l0_local_cv``, ``model/_l0_local_cv.py``; a bound on the cardinality, the
 best-subset form: ``l0_local_subsets``, ``model/_l0_local_subsets.py``; groups and a hierarchy: ``l0_local_group_search``,
-``model/_l0_local_groups.py``; an l1 term: ``l1l0_local_search``, ``model/_l1l0_local.py``.)
+``model/_l0_local_groups.py``; an l1 term: ``l1l0_local_search``, ``model/_l1l0_local.py``.)  (The lower bound this search lacks,
+and with it a proven gap per cell: ``l0_local_bound``, ``model/_l0_local_bound.py``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_search``, ``L0LocalPath``).
 """
