@@ -1050,6 +1050,69 @@ int slm_solve_l0_local_bound(slm_dataset* ds, int32_t n_cells, const double* alp
                              int32_t* stat_out /* n_cells * 2: sweeps, status word; or NULL */, slm_point_info* info /* n_cells or NULL */);
 
 /*
+ * (added under ABI 24: two new symbols beside slm_solve_l0_local_bound, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs them looks the symbols up.)  LOCAL PROOF (l0_local_node_kernel,
+ * csrc/l0_local_node_kernels.hpp; the tree: l0_prove_tree, csrc/l0_host.hpp): branch and bound on the local bound, which turns
+ * "within 25 %" into PROVEN OPTIMAL where the tree closes.  A NODE gives every column one of three states -- FREE, IN (the column
+ * pays alphas[e] whether its coefficient is zero or not) or OUT (beta_j = 0) -- as two masks of 16 words of 64 bits each: bit
+ * (j & 63) of word (j >> 6) is column j.  With G, c, F and h as for slm_solve_l0_local_bound and t = c - G u, for EVERY vector u
+ *       L_node(u) = -1/2 u^T G u - sum over FREE of max(0, h(t_j) - alpha) - sum over IN of (h(t_j) - alpha)
+ *                <=  min { F(beta) : |beta_j| <= big_M, beta_OUT = 0, IN columns pay alpha whether zero or not }.
+ * slm_solve_l0_local_nodes bounds ONE BATCH of n_nodes <= 8192 nodes in one launch, one wavefront per node; node i belongs to
+ * cell cell[i] of the call's n_cells cells, starts from starts[i] (clipped into the box; NULL: zero) and writes
+ * lower_out[i] = max(L_node(u), L_node(0), parent_lower[i]) (parent_lower NULL: none), primal_out[i] = P_node(u), the relaxation's
+ * value, upper_out[i] = F(u) = 1/2 u^T (G + 2 eta I) u - c^T u + alpha nnz(u), an upper bound of the cell because u lies in the
+ * box, u_out[i] = u and stat_out[2i], stat_out[2i + 1] = sweeps and the status word (1: the sweeps ran out; the values are bounds
+ * all the same).  A node stops at P - L <= gap_tol max(|P|, alpha) or after max_sweeps sweeps (<= 0: 10000).  info[i]: L =
+ * lower, mu = primal, kkt = upper, n_iter = sweeps, resid = the status word, mode = 12.  Returns SLM_OK, or
+ * SLM_ERR_NOT_CONVERGED with ALL outputs valid when a node ran out of sweeps.  Refusals, all before a device is touched, each
+ * with its own message, in this order: NULL ds, alphas, etas, cell, a mask or lower_out; n_cells < 1; n_cells > 8192; n_nodes
+ * < 1; n_nodes > 8192; big_M < 0; a negative or non-finite alphas[e] or etas[e]; gap_tol < 0 (SLM_ERR_BAD_ARG); more than 1024
+ * columns (SLM_ERR_UNSUPPORTED); a cell[i] outside the call's cells; a column both IN and OUT; a parent_lower[i] that is a NaN or
+ * +infinity (-infinity is "none"); a non-finite start (SLM_ERR_BAD_ARG); groups that are not singletons; a row-sharded dataset (SLM_ERR_UNSUPPORTED).  big_M = 0: everything zero
+ * without a launch.
+ */
+int slm_solve_l0_local_nodes(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
+                             double big_M, int32_t n_nodes, const int32_t* cell /* n_nodes */, const uint64_t* in_mask /* n_nodes * 16 */,
+                             const uint64_t* out_mask /* n_nodes * 16 */, const double* parent_lower /* n_nodes, or NULL */,
+                             const double* starts /* n_nodes * p, or NULL */, int32_t max_sweeps /* <=0: default */,
+                             double gap_tol /* <0: BAD_ARG */, double* lower_out /* n_nodes */, double* primal_out /* n_nodes, or NULL */,
+                             double* upper_out /* n_nodes, or NULL */, double* u_out /* n_nodes * p, or NULL */,
+                             int32_t* stat_out /* n_nodes * 2, or NULL */, slm_point_info* info /* n_nodes or NULL */);
+
+/*
+ * (ABI 24, see above.)  slm_solve_l0_local_prove grows THE WHOLE TREE for every cell of a grid.  Per cell: the incumbent is
+ * incumbents[e] (NULL, or a value not below 0: the empty support at 0); the root has empty masks; a round pops the `width` open
+ * nodes of lowest bound and splits each into an IN child and an OUT child on the FREE column whose z_j = min(|u_j| / tauc, 1) is
+ * closest to 1/2 (ties: the lowest index; where every z_j is 0 or 1, the largest |u_j|, then the largest |t_j|), both started
+ * from the parent's u; the children of ALL cells of a round are ONE launch of at most 8192 nodes.  A child whose F(u) is below
+ * the incumbent replaces it, polished on its support where that is lower still.  A node is dropped when best - lower <= rel_gap
+ * max(|best|, alpha).  Node relaxations run at gap_tol = rel_gap / 100 and max_sweeps (<= 0: 10000).  A cell ends status_out[e]
+ * = 0, PROVEN OPTIMAL to rel_gap, when no node is open, and 1 at max_nodes bound evaluations; either way lower_out[e] = min(best,
+ * the lowest open bound) is proven.  beta_out[e], objective_out[e]: the incumbent; nodes_out[e], rounds_out[e]: bound
+ * evaluations and launches the cell took part in.  The certificate, where leaf_capacity > 0 and the five leaf arrays are given:
+ * every dropped node's cell, two masks, u and bound, the first leaf_capacity of them; *leaf_count counts them all.  info[e]: kkt
+ * = mu = the objective, L = the proven bound, n_iter = rounds, rejects = nodes, resid = the status, mode = 13.
+ * WHERE THE TREE CLOSES: with a ridge (eta > 0) or a box that binds; at eta = 0 with more columns than rows it does not, and the
+ * call returns the proven gap it reached.  Returns SLM_OK, or SLM_ERR_NOT_CONVERGED with ALL outputs valid when a cell hit
+ * max_nodes.  Refusals, all before a device is touched, each with its own message, in this order: NULL ds, alphas, etas, beta_out,
+ * objective_out or lower_out; n_cells < 1; n_cells > 8192; big_M < 0; a negative or non-finite alphas[e] or etas[e]; rel_gap
+ * outside [1e-10, 1]; max_nodes < 1; width < 1 (SLM_ERR_BAD_ARG); more than 1024 columns (SLM_ERR_UNSUPPORTED); an incumbent
+ * outside the box or non-finite (SLM_ERR_BAD_ARG); groups that are not singletons; a row-sharded dataset (SLM_ERR_UNSUPPORTED).
+ * big_M = 0: no launch, everything zero, proven.
+ * Not here: groups and a hierarchy, the cardinality form, the l1 entry, row sets (folds), a Tikhonov matrix, strengthening
+ * eta = 0 by extracting a diagonal from G, feeding the bound into the exact search over supports.
+ */
+int slm_solve_l0_local_prove(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
+                             double big_M, const double* incumbents /* n_cells * p, or NULL */, double rel_gap, int32_t max_nodes,
+                             int32_t width, int32_t max_sweeps /* <=0: default */, int64_t leaf_capacity /* 0: no certificate */,
+                             double* beta_out /* n_cells * p */, double* objective_out /* n_cells */, double* lower_out /* n_cells */,
+                             int32_t* nodes_out, int32_t* rounds_out, int32_t* status_out /* n_cells each, or NULL */,
+                             int32_t* leaf_cell /* leaf_capacity */, uint64_t* leaf_in, uint64_t* leaf_out /* leaf_capacity * 16 each */,
+                             double* leaf_u /* leaf_capacity * p */, double* leaf_lower /* leaf_capacity */,
+                             int64_t* leaf_count /* or NULL */, slm_point_info* info /* n_cells or NULL */);
+
+/*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant
  * changes, so the version stays 24 -- a caller that needs them looks the symbols up.)  The exact l0 search with the
  * EXCLUSION BOUND (csrc/l0_kernels.hpp, template parameter XB): the arguments, outputs, argument errors and contract of

@@ -45,6 +45,7 @@
 #include "l0_local_kernels.hpp"
 #include "l0_local_group_kernels.hpp"
 #include "l0_local_bound_kernels.hpp"
+#include "l0_local_node_kernels.hpp"
 
 namespace {
 
@@ -1435,6 +1436,256 @@ int solve_l0_local_bound_impl(slm_dataset* ds, int32_t n_cells, const double* al
   return SLM_OK;
 }
 
+// The local proof (DESIGN 4d "Local proof"; the mathematics, the twin and the tree: l0_host.hpp "local proof").  L0NodeRunner is
+// what both entries share: the Gram of the dataset's own rows found or filed and held as solve_l0_local_bound_impl does it
+// (l0_local_hold_grams), the cells' constants on the device once, and run(): ONE launch of l0_local_node_kernel
+// (csrc/l0_local_node_kernels.hpp) for a batch of nodes -- the batch up in one copy, the results back in one.  The device block
+// grows with the largest batch seen.
+struct L0NodeRunner {
+  slm_dataset* ds = nullptr;
+  hipStream_t s = nullptr;
+  slm_dataset::CovEntry held;
+  int p = 0, n_cells = 0, max_sweeps = 0;
+  double big_M = 0.0, gap_tol = 0.0;
+  unsigned long long* cells_dev = nullptr;
+  unsigned long long* dev = nullptr;
+  size_t dev_words = 0;
+  long long launches = 0, launched_nodes = 0;
+  std::vector<double> h;
+  ~L0NodeRunner() {
+    if (s) (void)hipStreamSynchronize(s);
+    dfree(dev);
+    dfree(cells_dev);
+  }
+  int open(slm_dataset* ds_, const L0NodeCell* cells, int n_cells_, int max_sweeps_, double gap_tol_, std::vector<double>* c_host) {
+    ds = ds_;
+    p = (int)ds->p; n_cells = n_cells_; max_sweeps = max_sweeps_; gap_tol = gap_tol_; big_M = cells[0].big_M;
+    slm_engine* eng = ds->eng;
+    HIP_TRY(hipSetDevice(eng->device));
+    s = eng->stream;
+    const double* const own_rows[1] = {nullptr};
+    const int64_t n_eff[1] = {0};
+    const double* const wdev[1] = {ds->rw};
+    const double neff[1] = {(double)ds->n_global};
+    SLM_TRY(l0_local_hold_grams(ds, 1, own_rows, n_eff, wdev, neff, &held));
+    std::vector<double> ch((size_t)p);
+    HIP_TRY(hipMemcpyAsync(ch.data(), held.c, sizeof(double) * (size_t)p, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (double v : ch)
+      if (!std::isfinite(v)) return fail(SLM_ERR_NON_FINITE, "X^T y holds a non-finite value (non-finite data)");
+    const size_t nc = (size_t)n_cells;
+    std::vector<double> cw(4 * nc);
+    for (size_t e = 0; e < nc; ++e) {
+      cw[e] = cells[e].alpha;
+      cw[nc + e] = cells[e].eta;
+      cw[2 * nc + e] = cells[e].lam;
+      cw[3 * nc + e] = cells[e].tauc;
+    }
+    SLM_TRY(dalloc(&cells_dev, 4 * nc));
+    HIP_TRY(hipMemcpyAsync(cells_dev, cw.data(), sizeof(double) * 4 * nc, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (cw leaves scope)
+    if (c_host) *c_host = ch;
+    return SLM_OK;
+  }
+  // one block: cell | in | out | parent | starts, then what comes back: lower | primal | upper | the two status words | u
+  int run(const L0NodeBatch& b) {
+    const size_t n = (size_t)b.n, W = (size_t)L0_ND_WORDS;
+    const size_t off_in = (n + 1) / 2, off_out = off_in + n * W, off_par = off_out + n * W, off_st = off_par + n, off_low = off_st + n * p,
+                 off_pri = off_low + n, off_up = off_pri + n, off_stat = off_up + n, off_u = off_stat + n, words = off_u + n * p;
+    if (words > dev_words) {
+      HIP_TRY(hipStreamSynchronize(s));
+      dfree(dev);
+      dev_words = 0;
+      SLM_TRY(dalloc(&dev, words + words / 2));
+      dev_words = words + words / 2;
+    }
+    h.assign(words, 0.0);
+    memcpy(h.data(), b.cell, sizeof(int) * n);
+    memcpy(h.data() + off_in, b.in_mask, sizeof(unsigned long long) * n * W);
+    memcpy(h.data() + off_out, b.out_mask, sizeof(unsigned long long) * n * W);
+    if (b.parent_lower) memcpy(h.data() + off_par, b.parent_lower, sizeof(double) * n);
+    if (b.starts) memcpy(h.data() + off_st, b.starts, sizeof(double) * n * p);
+    double* dd = reinterpret_cast<double*>(dev);
+    HIP_TRY(hipMemcpyAsync(dd, h.data(), sizeof(double) * off_low, hipMemcpyHostToDevice, s));
+    const double* cd = reinterpret_cast<const double*>(cells_dev);
+    L0NdArgs k;
+    memset(&k, 0, sizeof(k));
+    k.G = held.G;
+    k.c = held.c;
+    k.alphas = cd;
+    k.etas = cd + n_cells;
+    k.lams = cd + 2 * (size_t)n_cells;
+    k.taus = cd + 3 * (size_t)n_cells;
+    k.cell = reinterpret_cast<const int*>(dd);
+    k.in_mask = dev + off_in;
+    k.out_mask = dev + off_out;
+    k.parent_lower = b.parent_lower ? dd + off_par : nullptr;
+    k.starts = b.starts ? dd + off_st : nullptr;
+    k.lower_out = dd + off_low;
+    k.primal_out = dd + off_pri;
+    k.upper_out = dd + off_up;
+    k.stat_out = reinterpret_cast<int*>(dd + off_stat);
+    k.u_out = dd + off_u;
+    k.ld = (long long)ds->ld;
+    k.p = p; k.n_nodes = b.n; k.max_sweeps = max_sweeps;
+    k.big_M = big_M; k.gap_tol = gap_tol;
+    // (a node is one wave; the grid as for the bound: up to two workgroups a CU, the nodes beyond by the grid-stride loop)
+    const int blocks = std::min((b.n + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * ds->eng->cus));
+    hipLaunchKernelGGL(l0_local_node_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    SLM_TRY(check_launch());
+    HIP_TRY(hipMemcpyAsync(h.data() + off_low, dd + off_low, sizeof(double) * (words - off_low), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    memcpy(b.lower, h.data() + off_low, sizeof(double) * n);
+    memcpy(b.primal, h.data() + off_pri, sizeof(double) * n);
+    memcpy(b.upper, h.data() + off_up, sizeof(double) * n);
+    memcpy(b.stat, h.data() + off_stat, sizeof(int) * 2 * n);
+    memcpy(b.u, h.data() + off_u, sizeof(double) * n * p);
+    ++launches;
+    launched_nodes += b.n;
+    return SLM_OK;
+  }
+};
+
+// One batch of nodes: the kernel's entry, and what the tests compare with the twin.  The record, per node:
+//
+//   n_iter    resid              mu          L           kkt       loss    mode
+//   sweeps    the status word    P_node(u)   the bound   F(u)      0       12
+int solve_l0_local_nodes_impl(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M, int32_t n_nodes,
+                              const int32_t* cell, const unsigned long long* in_mask, const unsigned long long* out_mask,
+                              const double* parent_lower, const double* starts, int32_t max_sweeps, double gap_tol, double* lower_out,
+                              double* primal_out, double* upper_out, double* u_out, int32_t* stat_out, slm_point_info* info) {
+  if (!ds || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  long long which = 0;
+  switch (l0_nodes_check(n_cells, alphas, etas, big_M, n_nodes, cell, in_mask, out_mask, parent_lower, starts, ds->p, gap_tol, ds->singleton, row_sharded(ds),
+                         &which)) {
+    case L0_ND_OK: break;
+    case L0_ND_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    case L0_ND_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
+    case L0_ND_PROBLEMS: return fail(SLM_ERR_BAD_ARG, "n_cells must be at most %d cells (got %d)", L0_LS_MAX_PROBLEMS, n_cells);
+    case L0_ND_NODES: return fail(SLM_ERR_BAD_ARG, "n_nodes must be >= 1 (got %d)", n_nodes);
+    case L0_ND_BATCH: return fail(SLM_ERR_BAD_ARG, "n_nodes must be at most %d nodes (got %d)", L0_ND_MAX_BATCH, n_nodes);
+    case L0_ND_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
+    case L0_ND_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", which);
+    case L0_ND_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", which);
+    case L0_ND_GAP_TOL: return fail(SLM_ERR_BAD_ARG, "gap_tol must be >= 0");
+    case L0_ND_WIDTH: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof takes up to %d columns (got %lld)", L0_LS_PMAX, (long long)ds->p);
+    case L0_ND_CELL: return fail(SLM_ERR_BAD_ARG, "cell[%lld] is not a cell of the call", which);
+    case L0_ND_MASK: return fail(SLM_ERR_BAD_ARG, "node %lld holds a column that is both IN and OUT", which);
+    case L0_ND_PARENT: return fail(SLM_ERR_BAD_ARG, "parent_lower[%lld] is neither a number nor -infinity", which);
+    case L0_ND_START: return fail(SLM_ERR_BAD_ARG, "starts[%lld] is not a finite number", which);
+    case L0_ND_GROUPS: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof is not built for groups: every column must be its own group");
+    case L0_ND_SHARDED: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof is not built for row-sharded datasets");
+  }
+  const int p = (int)ds->p, sweeps_cap = max_sweeps > 0 ? max_sweeps : L0_LB_SWEEPS;
+  const size_t n = (size_t)n_nodes;
+  std::vector<double> lower(n, 0.0), primal(n, 0.0), upper(n, 0.0), u(n * (size_t)p, 0.0);
+  std::vector<int> stat(2 * n, 0);
+  if (big_M != 0.0) {  // (big_M = 0: the box holds beta = 0 alone, every value is 0 and nothing is launched)
+    std::vector<L0NodeCell> cells((size_t)n_cells);
+    for (int e = 0; e < n_cells; ++e) cells[(size_t)e] = l0_node_cell(alphas[e], etas[e], big_M);
+    L0NodeRunner run;
+    SLM_TRY(run.open(ds, cells.data(), n_cells, sweeps_cap, gap_tol, nullptr));
+    const L0NodeBatch b{n_nodes, cell, in_mask, out_mask, parent_lower, starts, lower.data(), primal.data(), upper.data(), u.data(), stat.data()};
+    SLM_TRY(run.run(b));
+  }
+  int unclosed = 0, first = -1;
+  for (int i = 0; i < n_nodes; ++i) {
+    lower_out[i] = lower[(size_t)i];
+    if (primal_out) primal_out[i] = primal[(size_t)i];
+    if (upper_out) upper_out[i] = upper[(size_t)i];
+    if (stat_out) {
+      stat_out[2 * i] = stat[2 * (size_t)i];
+      stat_out[2 * i + 1] = stat[2 * (size_t)i + 1];
+    }
+    if (stat[2 * (size_t)i + 1] != 0 && unclosed++ == 0) first = i;
+    if (!info) continue;
+    l0_report(info + i, stat[2 * (size_t)i + 1] == 0, 0.0, upper[(size_t)i], primal[(size_t)i], lower[(size_t)i]);
+    info[i].n_iter = stat[2 * (size_t)i];
+    info[i].resid = (double)stat[2 * (size_t)i + 1];
+    info[i].mode = L0_ND_MODE;
+  }
+  if (u_out) memcpy(u_out, u.data(), sizeof(double) * n * (size_t)p);
+  if (unclosed)
+    return fail(SLM_ERR_NOT_CONVERGED, "the node relaxation ran out of sweeps (%d) in %d of %d nodes (the first: %d): it is not closed there, the "
+                "values are bounds all the same", sweeps_cap, unclosed, n_nodes, first);
+  return SLM_OK;
+}
+
+// The whole tree for a grid of cells: l0_prove_tree (l0_host.hpp) with the launch as its callable, one launch a round for the
+// children of every cell.  The Gram comes to the host once (the tree's branching rule and the incumbent's polish read it).
+// The record, per cell:
+//
+//   n_iter    rejects   resid                           mu               L                 kkt             mode
+//   rounds    nodes     the status (1: node limit)      the incumbent    the proven bound  the objective   13
+int solve_l0_local_prove_impl(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M, const double* incumbents,
+                              double rel_gap, int32_t max_nodes, int32_t width, int32_t max_sweeps, int64_t leaf_capacity, double* beta_out,
+                              double* objective_out, double* lower_out, int32_t* nodes_out, int32_t* rounds_out, int32_t* status_out,
+                              int32_t* leaf_cell, unsigned long long* leaf_in, unsigned long long* leaf_out, double* leaf_u, double* leaf_lower,
+                              int64_t* leaf_count, slm_point_info* info) {
+  if (!ds || !beta_out || !objective_out || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  long long which = 0;
+  switch (l0_prove_check(n_cells, alphas, etas, big_M, incumbents, ds->p, rel_gap, max_nodes, width, ds->singleton, row_sharded(ds), &which)) {
+    case L0_PV_OK: break;
+    case L0_PV_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    case L0_PV_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
+    case L0_PV_PROBLEMS: return fail(SLM_ERR_BAD_ARG, "n_cells must be at most %d cells (got %d)", L0_LS_MAX_PROBLEMS, n_cells);
+    case L0_PV_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
+    case L0_PV_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", which);
+    case L0_PV_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", which);
+    case L0_PV_REL_GAP: return fail(SLM_ERR_BAD_ARG, "rel_gap must lie in [1e-10, 1]");
+    case L0_PV_MAX_NODES: return fail(SLM_ERR_BAD_ARG, "max_nodes must be >= 1 (got %d)", max_nodes);
+    case L0_PV_TREE_WIDTH: return fail(SLM_ERR_BAD_ARG, "width must be >= 1 (got %d)", width);
+    case L0_PV_WIDTH: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof takes up to %d columns (got %lld)", L0_LS_PMAX, (long long)ds->p);
+    case L0_PV_INCUMBENT: return fail(SLM_ERR_BAD_ARG, "incumbents[%lld] is outside the box [-big_M, big_M] or not a number", which);
+    case L0_PV_GROUPS: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof is not built for groups: every column must be its own group");
+    case L0_PV_SHARDED: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof is not built for row-sharded datasets");
+  }
+  const int p = (int)ds->p, sweeps_cap = max_sweeps > 0 ? max_sweeps : L0_LB_SWEEPS;
+  const bool want_leaves = leaf_capacity > 0 && leaf_cell && leaf_in && leaf_out && leaf_u && leaf_lower;
+  std::vector<int> nodes((size_t)n_cells, 0), rounds((size_t)n_cells, 0), status((size_t)n_cells, L0_PV_OPTIMAL);
+  L0ProveLeaves leaves;
+  if (big_M == 0.0) {  // the box holds beta = 0 alone: F = 0 is the optimum, proven without a launch
+    std::fill(beta_out, beta_out + (size_t)n_cells * p, 0.0);
+    std::fill(objective_out, objective_out + n_cells, 0.0);
+    std::fill(lower_out, lower_out + n_cells, 0.0);
+  } else {
+    std::vector<L0NodeCell> cells((size_t)n_cells);
+    for (int e = 0; e < n_cells; ++e) cells[(size_t)e] = l0_node_cell(alphas[e], etas[e], big_M);
+    L0NodeRunner run;
+    std::vector<double> ch;
+    SLM_TRY(run.open(ds, cells.data(), n_cells, sweeps_cap, rel_gap / 100.0, &ch));
+    const size_t ld = (size_t)ds->ld;
+    std::vector<double> Gh((size_t)p * ld);
+    HIP_TRY(hipMemcpyAsync(Gh.data(), run.held.G, sizeof(double) * (size_t)p * ld, hipMemcpyDeviceToHost, run.s));
+    HIP_TRY(hipStreamSynchronize(run.s));
+    if (want_leaves) {
+      leaves.capacity = leaf_capacity;
+      leaves.cell = leaf_cell; leaves.in_mask = leaf_in; leaves.out_mask = leaf_out; leaves.u = leaf_u; leaves.lower = leaf_lower;
+    }
+    SLM_TRY(l0_prove_tree(Gh.data(), ld, ch.data(), p, n_cells, cells.data(), incumbents, rel_gap, max_nodes, width,
+                          [&](const L0NodeBatch& b) { return run.run(b); }, beta_out, objective_out, lower_out, nodes.data(), rounds.data(),
+                          status.data(), want_leaves ? &leaves : nullptr));
+  }
+  if (leaf_count) *leaf_count = leaves.count;
+  int open_cells = 0, first = -1;
+  for (int e = 0; e < n_cells; ++e) {
+    if (nodes_out) nodes_out[e] = nodes[(size_t)e];
+    if (rounds_out) rounds_out[e] = rounds[(size_t)e];
+    if (status_out) status_out[e] = status[(size_t)e];
+    if (status[(size_t)e] != L0_PV_OPTIMAL && open_cells++ == 0) first = e;
+    if (!info) continue;
+    l0_report(info + e, status[(size_t)e] == L0_PV_OPTIMAL, 0.0, objective_out[e], objective_out[e], lower_out[e]);
+    info[e].n_iter = rounds[(size_t)e];
+    info[e].rejects = nodes[(size_t)e];
+    info[e].resid = (double)status[(size_t)e];
+    info[e].mode = L0_PV_MODE;
+  }
+  if (open_cells)
+    return fail(SLM_ERR_NOT_CONVERGED, "the node limit (%d) ran out in %d of %d cells (the first: %d): the incumbent and a proven lower bound are "
+                "returned there", max_nodes, open_cells, n_cells, first);
+  return SLM_OK;
+}
+
 }  // namespace
 
 // The l0 local search on up to 16 row sets of one dataset: every (row set, cell, start) problem from one launch.
@@ -1486,6 +1737,28 @@ extern "C" int slm_solve_l0_local_bound(slm_dataset* ds, int32_t n_cells, const 
                                         const double* starts, int32_t max_sweeps, double gap_tol, double* lower_out, double* primal_out,
                                         double* u_out, int32_t* stat_out, slm_point_info* info) {
   return solve_l0_local_bound_impl(ds, n_cells, alphas, etas, big_M, starts, max_sweeps, gap_tol, lower_out, primal_out, u_out, stat_out, info);
+}
+
+// One batch of node relaxations of the local proof, from one launch of l0_local_node_kernel: one wavefront per node.
+extern "C" int slm_solve_l0_local_nodes(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M, int32_t n_nodes,
+                                        const int32_t* cell, const uint64_t* in_mask, const uint64_t* out_mask, const double* parent_lower,
+                                        const double* starts, int32_t max_sweeps, double gap_tol, double* lower_out, double* primal_out,
+                                        double* upper_out, double* u_out, int32_t* stat_out, slm_point_info* info) {
+  return solve_l0_local_nodes_impl(ds, n_cells, alphas, etas, big_M, n_nodes, cell, reinterpret_cast<const unsigned long long*>(in_mask),
+                                   reinterpret_cast<const unsigned long long*>(out_mask), parent_lower, starts, max_sweeps, gap_tol, lower_out,
+                                   primal_out, upper_out, u_out, stat_out, info);
+}
+
+// The local proof: branch and bound on the local bound for every cell of a grid, one launch a round; `optimal` is proven.
+extern "C" int slm_solve_l0_local_prove(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                        const double* incumbents, double rel_gap, int32_t max_nodes, int32_t width, int32_t max_sweeps,
+                                        int64_t leaf_capacity, double* beta_out, double* objective_out, double* lower_out, int32_t* nodes_out,
+                                        int32_t* rounds_out, int32_t* status_out, int32_t* leaf_cell, uint64_t* leaf_in, uint64_t* leaf_out,
+                                        double* leaf_u, double* leaf_lower, int64_t* leaf_count, slm_point_info* info) {
+  return solve_l0_local_prove_impl(ds, n_cells, alphas, etas, big_M, incumbents, rel_gap, max_nodes, width, max_sweeps, leaf_capacity, beta_out,
+                                   objective_out, lower_out, nodes_out, rounds_out, status_out, leaf_cell,
+                                   reinterpret_cast<unsigned long long*>(leaf_in), reinterpret_cast<unsigned long long*>(leaf_out), leaf_u,
+                                   leaf_lower, leaf_count, info);
 }
 
 // The l0 local search: every (cell, start) problem from one launch of l0_local_kernel, up to 1024 columns, nothing proven.

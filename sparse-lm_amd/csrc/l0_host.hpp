@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <map>
 #include <memory>
 #include <type_traits>
 #include <vector>
@@ -2186,6 +2187,503 @@ inline L0LbRefusal l0_bound_check(long long n_cells, const double* alphas, const
   if (!singleton) return L0_LB_GROUPS;
   if (sharded) return L0_LB_SHARDED;
   return L0_LB_OK;
+}
+
+// ---- local proof (slm_solve_l0_local_nodes, slm_solve_l0_local_prove; csrc/l0_local_node_kernels.hpp; tests/l0_local_prove_host_test.cpp)
+//
+// Branch and bound on the local bound (the L0BnB scheme of Hazimeh, Mazumder and Saab).  A NODE gives every column one of
+// three states: FREE, IN (the column pays alpha whether its coefficient is zero or not) or OUT (beta_j = 0).  The bound's
+// relaxation on a node is the same separable convex problem with three kinds of coordinate: with t = c - G u, for EVERY u,
+//     L_node(u) = -1/2 u^T G u - sum over FREE of max(0, h(t_j) - alpha) - sum over IN of (h(t_j) - alpha)
+//              <=  min { F(beta) : |beta_j| <= M, beta_OUT = 0, IN columns pay alpha whether zero or not }
+// (h: l0_lb_conj without its max).  g(beta) >= -1/2 u^T G u - t^T beta by convexity; the conjugate of eta b^2 + alpha on the box
+// is h - alpha, that of the indicator of {0} is 0.  The coordinate step: FREE l0_lb_coord, IN clip(s / (a + 2 eta), +-M), OUT
+// u_j = 0; a column that fails the pivot test keeps u_j = 0 in any state and its conjugate term is still counted.  Beside L and
+// P_node(u) a node returns F(u) = 1/2 u^T (G + 2 eta I) u - c^T u + alpha nnz(u), an upper bound of the cell because u lies in
+// the box.  The tree (l0_prove_tree) is device-free and templated on the callable that bounds a batch of nodes: the engine
+// passes the launch of l0_local_node_kernel, the twin l0_node_solve -- one body, the same tree node for node.
+#if !defined(__clang__)
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+#endif
+constexpr int L0_ND_FREE = 0, L0_ND_IN = 1, L0_ND_OUT = 2;  // a column's state in a node
+constexpr int L0_ND_WORDS = L0_LS_SLOTS;  // 64-bit words of a node's IN mask, and of its OUT mask: bit `lane` of word `slot`
+constexpr int L0_ND_MAX_BATCH = 8192;     // nodes of one launch
+constexpr int L0_ND_MODE = 12, L0_PV_MODE = 13;  // slm_point_info.mode of the two entries
+constexpr int L0_PV_OPTIMAL = 0, L0_PV_NODE_LIMIT = 1;  // a cell's status
+
+// a cell as kernel and twin take it: (alpha, eta, M) and l0_lb_cell's two numbers
+struct L0NodeCell {
+  double alpha, eta, big_M, lam, tauc;
+};
+inline L0NodeCell l0_node_cell(double alpha, double eta, double big_M) {
+  const L0LbCell c = l0_lb_cell(alpha, eta, big_M);
+  return L0NodeCell{alpha, eta, big_M, c.lam, c.tauc};
+}
+L0_LB_INLINE constexpr int l0_node_state(const unsigned long long* in_mask, const unsigned long long* out_mask, int j) {
+  return (int)((in_mask[j >> 6] >> (j & 63)) & 1ull) | ((int)((out_mask[j >> 6] >> (j & 63)) & 1ull) << 1);
+}
+// h(t): the conjugate of eta b^2 on the box, l0_lb_conj's h in its own arithmetic
+L0_LB_INLINE constexpr double l0_node_h(double t, double eta, double big_M) {
+  L0_LB_STRICT
+  const double at = t < 0.0 ? -t : t;
+  double h = 0.0;
+  if (eta > 0.0)
+    h = at <= 2.0 * eta * big_M ? at * at / (4.0 * eta) : at * big_M - eta * big_M * big_M;
+  else if (at > 0.0)
+    h = at * big_M;
+  return h;
+}
+// the coordinate step by state (a > 0: an OUT column and one that fails the pivot test never get here)
+L0_LB_INLINE constexpr double l0_node_coord(double s, double a, double eta, double lam, double tauc, double big_M, int state) {
+  L0_LB_STRICT
+  if (state == L0_ND_FREE) return l0_lb_coord(s, a, eta, lam, tauc, big_M);
+  if (state != L0_ND_IN) return 0.0;
+  const double b = s / (a + 2.0 * eta);
+  return b < -big_M ? -big_M : (b > big_M ? big_M : b);
+}
+// a column's term of P_node: FREE phi(b), IN eta b^2 + alpha (paid at zero too), OUT nothing
+L0_LB_INLINE constexpr double l0_node_phi(double b, double alpha, double eta, double lam, double tauc, int state) {
+  L0_LB_STRICT
+  if (state == L0_ND_FREE) return l0_lb_phi(b, alpha, eta, lam, tauc);
+  if (state != L0_ND_IN) return 0.0;
+  return eta * b * b + alpha;
+}
+// a column's term of -L_node: FREE max(0, h - alpha), IN h - alpha, OUT nothing
+L0_LB_INLINE constexpr double l0_node_conj(double t, double alpha, double eta, double big_M, int state) {
+  L0_LB_STRICT
+  if (state == L0_ND_FREE) return l0_lb_conj(t, alpha, eta, big_M);
+  if (state != L0_ND_IN) return 0.0;
+  return l0_node_h(t, eta, big_M) - alpha;
+}
+// P_node, L_node and F from the six sums over the columns (each a wave sum: l0_lb_wave_sum's order)
+struct L0NodeValues {
+  double P, L, F;
+};
+L0_LB_INLINE constexpr L0NodeValues l0_node_combine(double qp, double ql, double sp, double sc, double s2, double nz, double alpha, double eta) {
+  L0_LB_STRICT
+  const double half = -0.5 * qp;
+  return L0NodeValues{half + sp, -0.5 * ql - sc, (half + eta * s2) + alpha * nz};
+}
+inline L0NodeValues l0_node_values(const double* u, const double* t, const double* c, int p, const L0NodeCell& cell, const unsigned char* state) {
+  L0_LB_STRICT
+  double qp[64] = {0.0}, ql[64] = {0.0}, sp[64] = {0.0}, sc[64] = {0.0}, s2[64] = {0.0}, nz[64] = {0.0};
+  for (int j = 0; j < p; ++j) {
+    const int l = j & 63;
+    qp[l] += u[j] * (c[j] + t[j]);
+    ql[l] += u[j] * (c[j] - t[j]);
+    sp[l] += l0_node_phi(u[j], cell.alpha, cell.eta, cell.lam, cell.tauc, state[j]);
+    sc[l] += l0_node_conj(t[j], cell.alpha, cell.eta, cell.big_M, state[j]);
+    s2[l] += u[j] * u[j];
+    nz[l] += u[j] != 0.0 ? 1.0 : 0.0;
+  }
+  return l0_node_combine(l0_lb_wave_sum(qp), l0_lb_wave_sum(ql), l0_lb_wave_sum(sp), l0_lb_wave_sum(sc), l0_lb_wave_sum(s2), l0_lb_wave_sum(nz),
+                         cell.alpha, cell.eta);
+}
+
+struct L0NodeResult {
+  double lower = 0.0;   // max(L_node(u), L_node(0)): a bound of the node
+  double primal = 0.0;  // P_node(u)
+  double upper = 0.0;   // F(u): an upper bound of the cell
+  int sweeps = 0, status = 0;
+  long long changes = 0;
+};
+// The node kernel's twin without a device, change for change: l0_bound_solve with three kinds of coordinate -- its stopping
+// rule, its sums, its rebuilt certificate.  With both masks empty it returns l0_bound_solve's bits.  in_mask, out_mask:
+// L0_ND_WORDS words each; start: [p] or NULL (clipped into the box; an OUT column starts at zero); u: [p] out.
+inline L0NodeResult l0_node_solve(const double* G, size_t ld, const double* c, int p, const L0NodeCell& cell, const unsigned long long* in_mask,
+                                  const unsigned long long* out_mask, const double* start, int max_sweeps, double gap_tol, double* u) {
+  L0_LB_STRICT
+  L0NodeResult R;
+  const double big_M = cell.big_M;
+  std::vector<double> t(c, c + p), a((size_t)p);
+  std::vector<unsigned char> state((size_t)p);
+  double amax = 0.0;
+  for (int j = 0; j < p; ++j) {
+    a[(size_t)j] = G[(size_t)j * ld + j];
+    u[j] = 0.0;
+    state[(size_t)j] = (unsigned char)l0_node_state(in_mask, out_mask, j);
+    amax = std::fmax(amax, a[(size_t)j]);
+  }
+  for (int j = 0; j < p; ++j)
+    if (!(a[(size_t)j] > L0_PIVOT * amax) || state[(size_t)j] == L0_ND_OUT) a[(size_t)j] = 0.0;  // a = 0 marks a column that keeps u_j = 0
+  const double L0 = l0_node_values(u, t.data(), c, p, cell, state.data()).L;
+  auto axpy = [&](int j, double w) {
+    const double* row = G + (size_t)j * ld;
+    for (int k = 0; k < p; ++k) t[(size_t)k] = std::fma(w, row[k], t[(size_t)k]);
+  };
+  auto build = [&]() {
+    for (int k = 0; k < p; ++k) t[(size_t)k] = c[k];
+    for (int j = 0; j < p; ++j)
+      if (u[j] != 0.0) axpy(j, -u[j]);
+  };
+  if (start)
+    for (int j = 0; j < p; ++j)
+      if (a[(size_t)j] > 0.0) u[j] = start[j] < -big_M ? -big_M : (start[j] > big_M ? big_M : start[j]);
+  build();
+  for (int sw = 0;; ++sw) {
+    if (sw == max_sweeps) {
+      R.status |= L0_LS_SWEEPS_OUT;
+      break;
+    }
+    for (int j = 0; j < p; ++j) {
+      const double aj = a[(size_t)j];
+      if (!(aj > 0.0)) continue;
+      const double nb = l0_node_coord(t[(size_t)j] + aj * u[j], aj, cell.eta, cell.lam, cell.tauc, big_M, state[(size_t)j]);
+      if (!l0_lb_changed(nb, u[j])) continue;
+      const double delta = nb - u[j];
+      u[j] = nb;
+      axpy(j, -delta);
+      ++R.changes;
+    }
+    ++R.sweeps;
+    const L0NodeValues v = l0_node_values(u, t.data(), c, p, cell, state.data());
+    if (l0_lb_closed(v.P, v.L, cell.alpha, gap_tol)) break;
+  }
+  build();  // no running residual feeds the certificate
+  const L0NodeValues v = l0_node_values(u, t.data(), c, p, cell, state.data());
+  R.lower = v.L > L0 ? v.L : L0;
+  R.primal = v.P;
+  R.upper = v.F;
+  return R;
+}
+
+// A batch of nodes as the tree hands it to its callable: n <= L0_ND_MAX_BATCH nodes, for each its cell, its two masks, its
+// parent's bound and its start; back come lower = max(the node's bound, parent_lower), primal, upper, u and (sweeps, status).
+struct L0NodeBatch {
+  int n;
+  const int* cell;                    // [n]
+  const unsigned long long* in_mask;  // [n][L0_ND_WORDS]
+  const unsigned long long* out_mask; // [n][L0_ND_WORDS]
+  const double* parent_lower;         // [n]
+  const double* starts;               // [n][p]
+  double *lower, *primal, *upper;     // [n] each
+  double* u;                          // [n][p]
+  int* stat;                          // [n][2]
+};
+// the batch on the host: the twin, node after node
+inline int l0_node_batch_host(const double* G, size_t ld, const double* c, int p, const L0NodeCell* cells, int max_sweeps, double gap_tol,
+                              const L0NodeBatch& b) {
+  for (int i = 0; i < b.n; ++i) {
+    const L0NodeResult r = l0_node_solve(G, ld, c, p, cells[b.cell[i]], b.in_mask + (size_t)i * L0_ND_WORDS, b.out_mask + (size_t)i * L0_ND_WORDS,
+                                         b.starts ? b.starts + (size_t)i * p : nullptr, max_sweeps, gap_tol, b.u + (size_t)i * p);
+    b.lower[i] = !b.parent_lower || r.lower > b.parent_lower[i] ? r.lower : b.parent_lower[i];  // (parent_lower NULL: none, as the kernel)
+    b.primal[i] = r.primal;
+    b.upper[i] = r.upper;
+    b.stat[2 * i] = r.sweeps;
+    b.stat[2 * i + 1] = r.status;
+  }
+  return 0;
+}
+
+// The column a node is split on: the FREE column whose z_j = min(|u_j| / tauc, 1) (tauc = 0: 1 where u_j != 0) is closest to
+// 1/2 among those strictly between 0 and 1, ties to the lowest index; where every FREE z_j is 0 or 1, the FREE column of largest
+// |u_j| > 0, and where all are zero that of largest |t_j|, t = c - G u.  -1: no column is FREE.
+inline int l0_prove_branch(const double* G, size_t ld, const double* c, int p, double tauc, const unsigned long long* in_mask,
+                           const unsigned long long* out_mask, const double* u) {
+  L0_LB_STRICT
+  int pick = -1;
+  double dist = 1.0, top = 0.0;
+  for (int j = 0; j < p; ++j) {
+    if (l0_node_state(in_mask, out_mask, j) != L0_ND_FREE) continue;
+    const double au = std::fabs(u[j]);
+    const double z = tauc > 0.0 ? (au / tauc < 1.0 ? au / tauc : 1.0) : (au > 0.0 ? 1.0 : 0.0);
+    if (!(z > 0.0 && z < 1.0)) continue;
+    const double d = std::fabs(z - 0.5);
+    if (d < dist) {
+      dist = d;
+      pick = j;
+    }
+  }
+  if (pick >= 0) return pick;
+  for (int j = 0; j < p; ++j)
+    if (l0_node_state(in_mask, out_mask, j) == L0_ND_FREE && std::fabs(u[j]) > top) {
+      top = std::fabs(u[j]);
+      pick = j;
+    }
+  if (pick >= 0) return pick;
+  std::vector<double> t(c, c + p);
+  for (int k = 0; k < p; ++k)
+    if (u[k] != 0.0)
+      for (int j = 0; j < p; ++j) t[(size_t)j] -= G[(size_t)k * ld + j] * u[k];
+  top = -1.0;
+  for (int j = 0; j < p; ++j)
+    if (l0_node_state(in_mask, out_mask, j) == L0_ND_FREE && std::fabs(t[(size_t)j]) > top) {
+      top = std::fabs(t[(size_t)j]);
+      pick = j;
+    }
+  return pick;
+}
+// F(beta) = 1/2 beta^T (G + 2 eta I) beta - c^T beta + alpha nnz(beta), summed over the support in l0_boxed's order
+inline double l0_prove_value(const double* G, size_t ld, const double* c, int p, double alpha, double eta, const double* beta) {
+  L0_LB_STRICT
+  double val = 0.0;
+  int nnz = 0;
+  for (int r = 0; r < p; ++r) {
+    if (beta[r] == 0.0) continue;
+    double t = 0.0;
+    for (int k = 0; k < p; ++k)
+      if (beta[k] != 0.0) t += (G[(size_t)r * ld + k] + (r == k ? 2.0 * eta : 0.0)) * beta[k];
+    val += beta[r] * (0.5 * t - c[r]);
+    ++nnz;
+  }
+  return val + alpha * (double)nnz;
+}
+// should a node of bound `lower` be dropped against the incumbent `best`?
+inline bool l0_prove_pruned(double best, double lower, double alpha, double rel_gap) {
+  L0_LB_STRICT
+  const double ab = std::fabs(best);
+  return best - lower <= rel_gap * (ab > alpha ? ab : alpha);
+}
+
+// the leaves a proof rests on: every node that was dropped (pruned against the incumbent, or with no FREE column left)
+struct L0ProveLeaves {
+  long long capacity = 0, count = 0;  // count goes on past capacity: what the caller's arrays would have had to hold
+  int* cell = nullptr;                // [capacity]
+  unsigned long long* in_mask = nullptr;   // [capacity][L0_ND_WORDS]
+  unsigned long long* out_mask = nullptr;  // [capacity][L0_ND_WORDS]
+  double* u = nullptr;                // [capacity][p]
+  double* lower = nullptr;            // [capacity]
+};
+
+// The tree, for every cell of a grid at once.  Per cell: the incumbent (the caller's where its value is below 0, else the empty
+// support at 0); the root; then rounds: the `width` open nodes of lowest bound are popped (ties: the older node), each is split
+// on l0_prove_branch's column into an IN child and an OUT child, both started from the parent's u; ALL children of ALL cells of a
+// round go into ONE call of `bound`, at most L0_ND_MAX_BATCH nodes (the width of a round is cut to fit, and cells the batch has
+// no room for wait for the next round).  A child whose F(u) is below the incumbent replaces it, and l0_ls_polish_on on its support
+// replaces that where it is lower still.  A node is dropped when best - lower <= rel_gap max(|best|, alpha).  A cell ends
+// L0_PV_OPTIMAL when no node is open, L0_PV_NODE_LIMIT when max_nodes bound evaluations leave no room for two more (or a node
+// with no FREE column left is still open: its relaxation ran out of sweeps); either way lower_bound = min(best, the lowest open
+// bound) is proven.  Deterministic: the same `bound` bits give the same tree.  Returns what `bound` returned when that is not 0.
+template <class Bound>
+inline int l0_prove_tree(const double* G, size_t ld, const double* c, int p, int n_cells, const L0NodeCell* cells, const double* incumbents,
+                         double rel_gap, int max_nodes, int width, Bound&& bound, double* beta_out, double* objective_out,
+                         double* lower_out, int* nodes_out, int* rounds_out, int* status_out, L0ProveLeaves* leaves = nullptr) {
+  struct Node {
+    unsigned long long in[L0_ND_WORDS], out[L0_ND_WORDS];
+    double lower;
+    std::vector<double> u;
+  };
+  struct Cell {
+    std::map<std::pair<double, long long>, Node> open;
+    std::vector<double> beta;
+    double best = 0.0, stuck = INFINITY;
+    int nodes = 0, rounds = 0;
+    bool done = false, limit = false;
+  };
+  std::vector<Cell> T((size_t)n_cells);
+  long long seq = 0;
+  auto leaf = [&](int e, const Node& nd) {
+    if (!leaves) return;
+    const long long at = leaves->count++;
+    if (at >= leaves->capacity) return;
+    leaves->cell[at] = e;
+    memcpy(leaves->in_mask + (size_t)at * L0_ND_WORDS, nd.in, sizeof(nd.in));
+    memcpy(leaves->out_mask + (size_t)at * L0_ND_WORDS, nd.out, sizeof(nd.out));
+    memcpy(leaves->u + (size_t)at * p, nd.u.data(), sizeof(double) * (size_t)p);
+    leaves->lower[at] = nd.lower;
+  };
+  for (int e = 0; e < n_cells; ++e) {
+    Cell& t = T[(size_t)e];
+    t.beta.assign((size_t)p, 0.0);
+    if (incumbents) {
+      const double F = l0_prove_value(G, ld, c, p, cells[e].alpha, cells[e].eta, incumbents + (size_t)e * p);
+      if (F < 0.0) {
+        t.best = F;
+        t.beta.assign(incumbents + (size_t)e * p, incumbents + (size_t)(e + 1) * p);
+      }
+    }
+  }
+  std::vector<int> b_cell;
+  std::vector<unsigned long long> b_in, b_out;
+  std::vector<double> b_parent, b_start, b_lower, b_primal, b_upper, b_u;
+  std::vector<int> b_stat;
+  for (int round = 0;; ++round) {
+    b_cell.clear(); b_in.clear(); b_out.clear(); b_parent.clear(); b_start.clear();
+    auto push = [&](int e, const unsigned long long* in, const unsigned long long* out, double parent, const double* start) {
+      b_cell.push_back(e);
+      b_in.insert(b_in.end(), in, in + L0_ND_WORDS);
+      b_out.insert(b_out.end(), out, out + L0_ND_WORDS);
+      b_parent.push_back(parent);
+      if (start) b_start.insert(b_start.end(), start, start + p);
+      else b_start.insert(b_start.end(), (size_t)p, 0.0);
+    };
+    if (round == 0) {
+      const unsigned long long none[L0_ND_WORDS] = {0};
+      for (int e = 0; e < n_cells; ++e) {
+        push(e, none, none, -INFINITY, nullptr);
+        ++T[(size_t)e].rounds;
+      }
+    } else {
+      int active = 0;
+      for (int e = 0; e < n_cells; ++e) active += !T[(size_t)e].done;
+      if (active == 0) break;
+      const int fit = std::max(1, std::min(width, L0_ND_MAX_BATCH / 2 / active));
+      for (int e = 0; e < n_cells; ++e) {
+        Cell& t = T[(size_t)e];
+        if (t.done) continue;
+        int popped = 0;
+        while (!t.open.empty() && popped < fit) {
+          if (t.nodes + 2 * (popped + 1) > max_nodes) {
+            t.limit = true;
+            break;
+          }
+          if ((int)b_cell.size() + 2 > L0_ND_MAX_BATCH) break;  // no room in this round: the cell waits
+          Node nd = std::move(t.open.begin()->second);
+          t.open.erase(t.open.begin());
+          const int j = l0_prove_branch(G, ld, c, p, cells[e].tauc, nd.in, nd.out, nd.u.data());
+          if (j < 0) {  // every column is fixed and the node is still open: its relaxation was not closed
+            t.stuck = std::min(t.stuck, nd.lower);
+            leaf(e, nd);
+            continue;
+          }
+          nd.in[j >> 6] |= 1ull << (j & 63);
+          push(e, nd.in, nd.out, nd.lower, nd.u.data());
+          nd.in[j >> 6] &= ~(1ull << (j & 63));
+          nd.out[j >> 6] |= 1ull << (j & 63);
+          push(e, nd.in, nd.out, nd.lower, nd.u.data());
+          ++popped;
+        }
+        if (popped) ++t.rounds;
+        if (t.open.empty() && popped == 0) t.done = true;
+        if (t.limit && popped == 0) t.done = true;
+      }
+    }
+    const int n = (int)b_cell.size();
+    if (n == 0) continue;  // (cells ended in this round: the next round sees none active)
+    b_lower.assign((size_t)n, 0.0); b_primal.assign((size_t)n, 0.0); b_upper.assign((size_t)n, 0.0);
+    b_u.assign((size_t)n * p, 0.0); b_stat.assign((size_t)n * 2, 0);
+    const L0NodeBatch batch{n, b_cell.data(), b_in.data(), b_out.data(), b_parent.data(), b_start.data(), b_lower.data(), b_primal.data(),
+                            b_upper.data(), b_u.data(), b_stat.data()};
+    const int rc = bound(batch);
+    if (rc != 0) return rc;
+    for (int i = 0; i < n; ++i) {  // the incumbents first, so that every child of the round meets the round's best
+      const int e = b_cell[(size_t)i];
+      Cell& t = T[(size_t)e];
+      ++t.nodes;
+      if (!(b_upper[(size_t)i] < t.best)) continue;
+      const double* u = b_u.data() + (size_t)i * p;
+      t.best = b_upper[(size_t)i];
+      t.beta.assign(u, u + p);
+      std::vector<double> pol(u, u + p);
+      std::vector<int> cols;
+      for (int j = 0; j < p; ++j)
+        if (pol[(size_t)j] != 0.0) cols.push_back(j);
+      const double quad = l0_ls_polish_on(G, ld, c, cells[e].eta, cells[e].big_M, cols, pol.data());
+      int nnz = 0;
+      for (int j = 0; j < p; ++j) nnz += pol[(size_t)j] != 0.0;
+      const double F = quad + cells[e].alpha * (double)nnz;
+      if (F < t.best) {
+        t.best = F;
+        t.beta = pol;
+      }
+    }
+    for (int i = 0; i < n; ++i) {
+      const int e = b_cell[(size_t)i];
+      Cell& t = T[(size_t)e];
+      Node nd;
+      memcpy(nd.in, b_in.data() + (size_t)i * L0_ND_WORDS, sizeof(nd.in));
+      memcpy(nd.out, b_out.data() + (size_t)i * L0_ND_WORDS, sizeof(nd.out));
+      nd.lower = b_lower[(size_t)i];
+      nd.u.assign(b_u.data() + (size_t)i * p, b_u.data() + (size_t)(i + 1) * p);
+      if (l0_prove_pruned(t.best, nd.lower, cells[e].alpha, rel_gap)) leaf(e, nd);
+      else t.open.emplace(std::make_pair(nd.lower, seq++), std::move(nd));
+    }
+    for (int e = 0; e < n_cells; ++e) {  // an incumbent that improved closes open nodes: from the highest bound down
+      Cell& t = T[(size_t)e];
+      while (!t.open.empty()) {
+        auto last = std::prev(t.open.end());
+        if (!l0_prove_pruned(t.best, last->second.lower, cells[e].alpha, rel_gap)) break;
+        leaf(e, last->second);
+        t.open.erase(last);
+      }
+    }
+  }
+  for (int e = 0; e < n_cells; ++e) {
+    const Cell& t = T[(size_t)e];
+    double low = std::min(t.best, t.stuck);
+    if (!t.open.empty()) low = std::min(low, t.open.begin()->first.first);
+    memcpy(beta_out + (size_t)e * p, t.beta.data(), sizeof(double) * (size_t)p);
+    objective_out[e] = t.best;
+    lower_out[e] = low;
+    nodes_out[e] = t.nodes;
+    rounds_out[e] = t.rounds;
+    status_out[e] = t.open.empty() && l0_prove_pruned(t.best, t.stuck, cells[e].alpha, rel_gap) ? L0_PV_OPTIMAL : L0_PV_NODE_LIMIT;
+  }
+  return 0;
+}
+#if !defined(__clang__)
+#pragma GCC pop_options
+#endif
+
+// What slm_solve_l0_local_nodes refuses before a device is touched, in this order; which: the offending cell, node or entry.
+enum L0NdRefusal { L0_ND_OK = 0, L0_ND_NULL, L0_ND_CELLS, L0_ND_PROBLEMS, L0_ND_NODES, L0_ND_BATCH, L0_ND_BIG_M, L0_ND_ALPHA, L0_ND_ETA,
+                   L0_ND_GAP_TOL, L0_ND_WIDTH, L0_ND_CELL, L0_ND_MASK, L0_ND_PARENT, L0_ND_START, L0_ND_GROUPS, L0_ND_SHARDED };
+inline L0NdRefusal l0_nodes_check(long long n_cells, const double* alphas, const double* etas, double big_M, long long n_nodes,
+                                  const int* cell, const unsigned long long* in_mask, const unsigned long long* out_mask,
+                                  const double* parent_lower, const double* starts, long long p, double gap_tol, bool singleton, bool sharded,
+                                  long long* which = nullptr) {
+  if (!alphas || !etas || !cell || !in_mask || !out_mask) return L0_ND_NULL;
+  if (n_cells < 1) return L0_ND_CELLS;
+  if (n_cells > L0_LS_MAX_PROBLEMS) return L0_ND_PROBLEMS;
+  if (n_nodes < 1) return L0_ND_NODES;
+  if (n_nodes > L0_ND_MAX_BATCH) return L0_ND_BATCH;
+  if (!(big_M >= 0.0)) return L0_ND_BIG_M;
+  for (long long e = 0; e < n_cells; ++e) {
+    if (which) *which = e;
+    if (!(alphas[e] >= 0.0) || !std::isfinite(alphas[e])) return L0_ND_ALPHA;
+    if (!(etas[e] >= 0.0) || !std::isfinite(etas[e])) return L0_ND_ETA;
+  }
+  if (!(gap_tol >= 0.0)) return L0_ND_GAP_TOL;
+  if (p > L0_LS_PMAX) return L0_ND_WIDTH;
+  for (long long i = 0; i < n_nodes; ++i) {
+    if (which) *which = i;
+    if (cell[i] < 0 || cell[i] >= n_cells) return L0_ND_CELL;
+    for (int w = 0; w < L0_ND_WORDS; ++w)  // a column is IN or OUT, not both
+      if (in_mask[i * L0_ND_WORDS + w] & out_mask[i * L0_ND_WORDS + w]) return L0_ND_MASK;
+  }
+  for (long long i = 0; parent_lower && i < n_nodes; ++i)  // a parent's bound is a number or -infinity: a NaN, or +infinity, is neither
+    if (!(parent_lower[i] < INFINITY)) {
+      if (which) *which = i;
+      return L0_ND_PARENT;
+    }
+  for (long long e = 0; starts && e < n_nodes * p; ++e)
+    if (!std::isfinite(starts[e])) {
+      if (which) *which = e;
+      return L0_ND_START;
+    }
+  if (!singleton) return L0_ND_GROUPS;
+  if (sharded) return L0_ND_SHARDED;
+  return L0_ND_OK;
+}
+
+// What slm_solve_l0_local_prove refuses before a device is touched, in this order: the bound's, and the tree's own.
+enum L0PvRefusal { L0_PV_OK = 0, L0_PV_NULL, L0_PV_CELLS, L0_PV_PROBLEMS, L0_PV_BIG_M, L0_PV_ALPHA, L0_PV_ETA, L0_PV_REL_GAP, L0_PV_MAX_NODES,
+                   L0_PV_TREE_WIDTH, L0_PV_WIDTH, L0_PV_INCUMBENT, L0_PV_GROUPS, L0_PV_SHARDED };
+inline L0PvRefusal l0_prove_check(long long n_cells, const double* alphas, const double* etas, double big_M, const double* incumbents,
+                                  long long p, double rel_gap, long long max_nodes, long long width, bool singleton, bool sharded,
+                                  long long* which = nullptr) {
+  if (!alphas || !etas) return L0_PV_NULL;
+  if (n_cells < 1) return L0_PV_CELLS;
+  if (n_cells > L0_LS_MAX_PROBLEMS) return L0_PV_PROBLEMS;
+  if (!(big_M >= 0.0)) return L0_PV_BIG_M;
+  for (long long e = 0; e < n_cells; ++e) {
+    if (which) *which = e;
+    if (!(alphas[e] >= 0.0) || !std::isfinite(alphas[e])) return L0_PV_ALPHA;
+    if (!(etas[e] >= 0.0) || !std::isfinite(etas[e])) return L0_PV_ETA;
+  }
+  if (!(rel_gap >= 1e-10 && rel_gap <= 1.0)) return L0_PV_REL_GAP;
+  if (max_nodes < 1) return L0_PV_MAX_NODES;
+  if (width < 1) return L0_PV_TREE_WIDTH;
+  if (p > L0_LS_PMAX) return L0_PV_WIDTH;
+  for (long long e = 0; incumbents && e < n_cells * p; ++e)
+    if (!(std::fabs(incumbents[e]) <= big_M)) {  // (a NaN fails too)
+      if (which) *which = e;
+      return L0_PV_INCUMBENT;
+    }
+  if (!singleton) return L0_PV_GROUPS;
+  if (sharded) return L0_PV_SHARDED;
+  return L0_PV_OK;
 }
 
 }  // namespace slm

@@ -110,6 +110,8 @@ ABI_SYMBOLS = (
     "slm_solve_l0_local_groups",
     "slm_solve_l0_local_l1",
     "slm_solve_l0_local_bound",
+    "slm_solve_l0_local_nodes",
+    "slm_solve_l0_local_prove",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -388,6 +390,9 @@ def load_library():
             "slm_solve_l0_local_groups": [vp, i32, vp, vp, i32, i32, vp, vp, dbl, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_l1": [vp, i32, vp, vp, i32, i32, vp, vp, vp, dbl, i32, vp, i32, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_bound": [vp, i32, vp, vp, dbl, vp, i32, dbl, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_nodes": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, vp, P(_PointInfo)],
+            "slm_solve_l0_local_prove": [vp, i32, vp, vp, dbl, vp, dbl, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1820,6 +1825,66 @@ class Dataset:
                 "converged": int(infos[e]["status"]) == SLM_OK, "status": "closed" if int(infos[e]["resid"]) == 0 else "sweep_cap",
                 "call_status": int(rc)} for e in range(cnt)]
         return lower, primal, u, stats, out
+
+    def solve_l0_local_nodes(self, alphas, etas, cell, in_mask, out_mask, big_M=100.0, parent_lower=None, starts=None, max_sweeps=0,
+                             gap_tol=1e-9, n_cells=None):
+        """``slm_solve_l0_local_nodes``: ONE BATCH of node relaxations of the local proof (``l0_local_node_kernel``,
+        csrc/l0_local_node_kernels.hpp), one wavefront per node, one launch.  Node ``i`` belongs to cell ``cell[i]`` of
+        ``(alphas, etas)``; ``in_mask[i]`` and ``out_mask[i]`` are 16 words of 64 bits each (bit ``j & 63`` of word ``j >> 6``:
+        column ``j`` is fixed IN, or OUT; neither: FREE).  ``parent_lower`` (None, or ``[nodes]``) is folded into the bound,
+        ``starts`` (None, or ``[nodes, p]``) is clipped into the box.  Returns ``(lower [nodes], primal [nodes], upper [nodes],
+        u [nodes, p], stats [nodes, 2] (sweeps, status word), call_status)``: ``lower`` is a proven bound of the node whatever the
+        status, ``upper = F(u)`` an upper bound of the cell."""
+        al, et, cells = _l0_local_cells(alphas, etas, n_cells)
+        ce = np.ascontiguousarray(cell, dtype=np.int32).reshape(-1)
+        nodes = len(ce)
+        im = np.ascontiguousarray(in_mask, dtype=np.uint64).reshape(-1)
+        om = np.ascontiguousarray(out_mask, dtype=np.uint64).reshape(-1)
+        if im.size != 16 * nodes or om.size != 16 * nodes:
+            raise ValueError(f"in_mask and out_mask must hold 16 words per node ({16 * nodes}), got {im.size} and {om.size}")
+        pl = None if parent_lower is None else np.ascontiguousarray(parent_lower, dtype=np.float64).reshape(-1)
+        if pl is not None and pl.size != nodes:
+            raise ValueError(f"parent_lower has {pl.size} entries, expected {nodes}")
+        st = None if starts is None else np.ascontiguousarray(starts, dtype=np.float64).reshape(-1)
+        if st is not None and st.size != nodes * self.p:
+            raise ValueError(f"starts has {st.size} entries, expected {nodes * self.p}")
+        cnt = max(1, nodes)
+        args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), nodes, _l0_local_pad(ce), _l0_local_pad(im), _l0_local_pad(om), pl, st,
+                int(max_sweeps), float(gap_tol))
+        (lower, primal, upper, u, stats), _, rc = self._l0_call(
+            "solve_l0_local_nodes", False, args,
+            [np.zeros(cnt), np.zeros(cnt), np.zeros(cnt), np.zeros((cnt, self.p)), np.zeros((cnt, 2), dtype=np.int32)], records=cnt)
+        return lower, primal, upper, u, stats, int(rc)
+
+    def solve_l0_local_prove(self, alphas, etas=0.0, big_M=100.0, incumbents=None, rel_gap=1e-6, max_nodes=20000, width=32, max_sweeps=0,
+                             leaf_capacity=0, n_cells=None):
+        """``slm_solve_l0_local_prove``: THE LOCAL PROOF -- branch and bound on the local bound for every cell ``(alphas[e], etas[e])``,
+        one launch of ``l0_local_node_kernel`` a round for the children of every cell.  ``incumbents``: None, or ``[cells, p]`` inside
+        the box.  ``leaf_capacity > 0`` asks for the certificate: every dropped node's cell, masks, u and bound.  Returns a dict:
+        ``beta [cells, p]``, ``objective``, ``lower_bound``, ``nodes``, ``rounds``, ``status`` (0: proven optimal to ``rel_gap``; 1:
+        the node limit), ``call_status`` and, with a capacity, ``leaves`` (``cell``, ``in_mask``, ``out_mask``, ``u``, ``lower``,
+        ``count``: all dropped nodes, of which the arrays hold the first ``leaf_capacity``).  The tree closes with a ridge or a box
+        that binds; at ``eta = 0`` with more columns than rows it does not, and ``lower_bound`` is what was proven."""
+        al, et, cells = _l0_local_cells(alphas, etas, n_cells)
+        sized = 1 <= cells <= L0_LOCAL_MAX_PROBLEMS
+        inc = None if incumbents is None else np.ascontiguousarray(incumbents, dtype=np.float64).reshape(-1)
+        if inc is not None and sized and inc.size != cells * self.p:
+            raise ValueError(f"incumbents has {inc.size} entries, expected {cells * self.p}")
+        cnt, cap = (cells if sized else 1), max(0, int(leaf_capacity))
+        lc = C.c_int64(0)
+        leaf = [np.zeros(max(1, cap), dtype=np.int32), np.zeros((max(1, cap), 16), dtype=np.uint64), np.zeros((max(1, cap), 16), dtype=np.uint64),
+                np.zeros((max(1, cap), self.p)), np.zeros(max(1, cap))]
+        args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), inc if sized else None, float(rel_gap), int(max_nodes), int(width),
+                int(max_sweeps), cap)
+        outs = [np.zeros((cnt, self.p)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32),
+                np.zeros(cnt, dtype=np.int32), *leaf, lc]
+        (beta, obj, low, nodes, rounds, status, *_), _, rc = self._l0_call("solve_l0_local_prove", False, args, outs, records=cnt)
+        out = {"beta": beta, "objective": obj, "lower_bound": low, "nodes": nodes, "rounds": rounds, "status": status, "call_status": int(rc)}
+        if cap:
+            k = min(cap, int(lc.value))
+            out["leaves"] = {"cell": leaf[0][:k], "in_mask": leaf[1][:k], "out_mask": leaf[2][:k], "u": leaf[3][:k], "lower": leaf[4][:k],
+                             "count": int(lc.value)}
+        return out
 
     def _l0_local_row_sets(self, row_weights, n_effs):
         """The row sets of a local-search call: ``(the weight arrays or None, the divisors)``, one per set."""

@@ -32,12 +32,16 @@ the l1 weight as in ``L1L0``; ``l1l0_local_cv`` / ``L1L0LocalCV`` (``model/_l1l0
 bound on the objective of ``l0_local_search`` at every cell of its ``(alpha, eta)`` grid, up to 1024 columns, from one launch;
 ``L0LocalBound.gap(path)`` is the proven relative gap per cell.  Tight with a ridge or a box that binds, weak at ``eta = 0`` under a loose
 ``big_M``.
+``l0_local_prove`` / ``L0LocalProof`` (``model/_l0_local_prove.py``) are the LOCAL PROOF: branch and bound on that bound, pruned against the
+local search's incumbent, one launch a round for the nodes of every cell; a cell whose tree closes is PROVEN OPTIMAL -- with a ridge or
+a box that binds it does, at ``eta = 0`` with more columns than rows it does not, and the proven gap reached is returned.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
 from .model._l0_grid_cv import L0ProfileGridCV, l1l0_profile_cv, l2l0_profile_cv  # noqa: F401  (CV over (alpha, eta) from one launch; outside __all__)
 from .model._l0_local import L0LocalPath, l0_local_search  # noqa: F401  (approximate, up to 1024 columns; outside __all__)
 from .model._l0_local_bound import L0LocalBound, l0_local_bound  # noqa: F401  (a proven lower bound for the local search's grid; outside __all__)
+from .model._l0_local_prove import L0LocalProof, l0_local_prove  # noqa: F401  (branch and bound on the local bound: proven optimal where the tree closes; outside __all__)
 from .model._l0_local_cv import L0LocalCV, l0_local_cv  # noqa: F401  (the local search of every CV fold from one launch per round; outside __all__)
 from .model._l0_local_groups import L0LocalGroupPath, l0_local_group_search  # noqa: F401  (the local search with groups and a hierarchy; outside __all__)
 from .model._l0_local_groups_cv import L0LocalGroupCV, l0_local_group_cv  # noqa: F401  (its cross-validation, one launch per round; outside __all__)

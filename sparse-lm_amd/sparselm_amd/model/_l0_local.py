@@ -22,7 +22,8 @@ Not built: groups and a hierarchy, an l1 term, a general Tikhonov matrix, constr
 as its seed.  (Cross-validation folds in the launch: ``l0_local_cv``, ``model/_l0_local_cv.py``; a bound on the cardinality, the
 best-subset form: ``l0_local_subsets``, ``model/_l0_local_subsets.py``; groups and a hierarchy: ``l0_local_group_search``,
 ``model/_l0_local_groups.py``; an l1 term: ``l1l0_local_search``, ``model/_l1l0_local.py``.)  (The lower bound this search lacks,
-and with it a proven gap per cell: ``l0_local_bound``, ``model/_l0_local_bound.py``.)
+and with it a proven gap per cell: ``l0_local_bound``, ``model/_l0_local_bound.py``; branch and bound on that bound, which
+proves a cell optimal where its tree closes: ``l0_local_prove``, ``model/_l0_local_prove.py``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_search``, ``L0LocalPath``).
 """
@@ -146,6 +147,32 @@ def _neighbour_starts(coefs, moves):
                      for da, de in moves], axis=-2)
 
 
+def _search_rounds(ds, al, et, big_M, first, moves, max_rounds, swaps):
+    """The rounds of ``l0_local_search`` on the open dataset ``ds`` (``l0_local_prove`` runs them on its own handle for its
+    incumbents): ``(coefs [A, E, p], objectives [A, E], infos [A, E], the objectives after every round)``."""
+    A, E, p = len(al), len(et), first.shape[-1]
+    cell_alpha, cell_eta = np.repeat(al, E), np.tile(et, A)
+
+    def launch(points):
+        return ds.solve_l0_local(cell_alpha, cell_eta, big_M=big_M, starts=points.reshape(A * E, -1, p), swaps=swaps)
+
+    coefs, objectives, _, infos = launch(first)
+    coefs = np.array(coefs).reshape(A, E, p)
+    objectives = np.array(objectives).reshape(A, E)
+    infos = np.array(infos, dtype=object).reshape(A, E)
+    history = [objectives.copy()]
+    for _ in range(int(max_rounds) if moves else 0):
+        c2, o2, _, i2 = launch(_neighbour_starts(coefs, moves))
+        c2, o2 = np.array(c2).reshape(A, E, p), np.array(o2).reshape(A, E)
+        better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[:, None])
+        coefs[better], objectives[better] = c2[better], o2[better]
+        infos[better] = np.array(i2, dtype=object).reshape(A, E)[better]
+        history.append(objectives.copy())
+        if not better.any():
+            break
+    return coefs, objectives, infos, history
+
+
 def l0_local_search(X, y, *, alphas, etas=(0.0,), big_M=100, fit_intercept=False, sample_weight=None, starts=None, max_rounds=2,
                     solver_options=None) -> L0LocalPath:
     """A local minimum of the regularised l0 problem at every cell of ``alphas x etas``, for up to 1024 columns, on the GPU.
@@ -169,27 +196,9 @@ def l0_local_search(X, y, *, alphas, etas=(0.0,), big_M=100, fit_intercept=False
     most = max(first.shape[2], len(moves))  # (a round starts a cell from its neighbours in the grid)
     if A * E * most > _MAX_PROBLEMS:
         raise ValueError(f"the grid holds {A * E} cells with up to {most} starts each: more than the {_MAX_PROBLEMS} problems of one launch")
-    cell_alpha, cell_eta = np.repeat(al, E), np.tile(et, A)
 
     with spec._l0_dataset(X, y, w, gidx, n_groups, need, dev_options) as (ds, x_mean, y_mean, _, _):
-
-        def launch(points):
-            return ds.solve_l0_local(cell_alpha, cell_eta, big_M=big_M, starts=points.reshape(A * E, -1, p), swaps=swaps)
-
-        coefs, objectives, _, infos = launch(first)
-        coefs = np.array(coefs).reshape(A, E, p)
-        objectives = np.array(objectives).reshape(A, E)
-        infos = np.array(infos, dtype=object).reshape(A, E)
-        history = [objectives.copy()]
-        for _ in range(int(max_rounds) if moves else 0):
-            c2, o2, _, i2 = launch(_neighbour_starts(coefs, moves))
-            c2, o2 = np.array(c2).reshape(A, E, p), np.array(o2).reshape(A, E)
-            better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[:, None])
-            coefs[better], objectives[better] = c2[better], o2[better]
-            infos[better] = np.array(i2, dtype=object).reshape(A, E)[better]
-            history.append(objectives.copy())
-            if not better.any():
-                break
+        coefs, objectives, infos, history = _search_rounds(ds, al, et, big_M, first, moves, max_rounds, swaps)
     unconverged = [(a, e) for a in range(A) for e in range(E) if not infos[a, e]["converged"]]
     if unconverged:
         a, e = unconverged[0]
