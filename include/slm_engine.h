@@ -1100,7 +1100,7 @@ int slm_solve_l0_local_nodes(slm_dataset* ds, int32_t n_cells, const double* alp
  * outside [1e-10, 1]; max_nodes < 1; width < 1 (SLM_ERR_BAD_ARG); more than 1024 columns (SLM_ERR_UNSUPPORTED); an incumbent
  * outside the box or non-finite (SLM_ERR_BAD_ARG); groups that are not singletons; a row-sharded dataset (SLM_ERR_UNSUPPORTED).
  * big_M = 0: no launch, everything zero, proven.
- * Not here: groups and a hierarchy, the cardinality form, the l1 entry, row sets (folds), a Tikhonov matrix, strengthening
+ * Not here: groups and a hierarchy (slm_solve_l0_local_group_prove, below), the cardinality form, the l1 entry, row sets (folds), a Tikhonov matrix, strengthening
  * eta = 0 by extracting a diagonal from G, feeding the bound into the exact search over supports.
  */
 int slm_solve_l0_local_prove(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
@@ -1111,6 +1111,61 @@ int slm_solve_l0_local_prove(slm_dataset* ds, int32_t n_cells, const double* alp
                              int32_t* leaf_cell /* leaf_capacity */, uint64_t* leaf_in, uint64_t* leaf_out /* leaf_capacity * 16 each */,
                              double* leaf_u /* leaf_capacity * p */, double* leaf_lower /* leaf_capacity */,
                              int64_t* leaf_count /* or NULL */, slm_point_info* info /* n_cells or NULL */);
+
+/*
+ * (added under ABI 24: two new symbols beside slm_solve_l0_local_prove, no existing entry, structure or constant changes, so the
+ * version stays 24 -- a caller that needs them looks the symbols up.)  LOCAL PROOF WITH GROUPS AND A HIERARCHY
+ * (l0_local_group_node_kernel, csrc/l0_local_group_node_kernels.hpp; the tree: l0_prove_tree with a group map, csrc/l0_host.hpp):
+ * branch and bound for slm_solve_l0_local_groups' objective F(beta) = 1/2 beta^T (G + 2 eta I) beta - c^T beta + alpha |cl(S(beta))|.
+ * The dataset's groups must be contiguous and ascending in column order; need_ptr / need_idx are the direct need lists in CSR form
+ * over the groups (NULL: no hierarchy).  A NODE gives every GROUP one state -- FREE, IN (it pays alpha whether zero or not) or
+ * OUT (beta_g = 0) -- as two masks of 16 words of 64 bits: bit (g & 63) of word (g >> 6) is group g.  With h as for
+ * slm_solve_l0_local_bound and t = c - G u, for EVERY vector u
+ *       L_node(u) = -1/2 u^T G u - sum over FREE g of max(0, sum_{j in g} h(t_j) - alpha) - sum over IN g of (sum_{j in g} h(t_j) - alpha)
+ *                <=  min of F over the node;
+ * the relaxation ignores the hierarchy (|cl(S)| >= |S|), which lives in the branching.  slm_solve_l0_local_group_nodes bounds ONE
+ * BATCH of n_nodes <= 8192 nodes in one launch, one wavefront per node, with the arguments, outputs, stopping rule and return
+ * values of slm_solve_l0_local_nodes; upper_out[i] = F(u) counts |cl(S(u))|; info[i].mode = 14.  A node's masks must be CLOSED:
+ * an IN group brings every group it needs (transitively) IN, an OUT group takes every group that needs it OUT.  An intercept is
+ * the caller's centring, as for the grouped local search's own rows.  Refusals, all before a device is touched, each with its
+ * own message, in this order: everything slm_solve_l0_local_nodes refuses up to and including a non-finite start; groups that are
+ * not contiguous and ascending (SLM_ERR_UNSUPPORTED); a need_ptr that does not start at 0 or falls; a need_idx outside the
+ * groups; a mask bit beyond the groups; masks that are not closed (SLM_ERR_BAD_ARG); a row-sharded dataset (SLM_ERR_UNSUPPORTED).
+ */
+int slm_solve_l0_local_group_nodes(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
+                                   double big_M, int32_t n_nodes, const int32_t* cell /* n_nodes */,
+                                   const uint64_t* in_mask /* n_nodes * 16, by group */, const uint64_t* out_mask /* n_nodes * 16 */,
+                                   const double* parent_lower /* n_nodes, or NULL */, const double* starts /* n_nodes * p, or NULL */,
+                                   const int32_t* need_ptr /* n_groups + 1, or NULL */, const int32_t* need_idx,
+                                   int32_t max_sweeps /* <=0: default */, double gap_tol /* <0: BAD_ARG */, double* lower_out /* n_nodes */,
+                                   double* primal_out /* n_nodes, or NULL */, double* upper_out /* n_nodes, or NULL */,
+                                   double* u_out /* n_nodes * p, or NULL */, int32_t* stat_out /* n_nodes * 2, or NULL */,
+                                   slm_point_info* info /* n_nodes or NULL */);
+
+/*
+ * (ABI 24, see above.)  slm_solve_l0_local_group_prove grows THE WHOLE TREE over group nodes for every cell of a grid, with the
+ * arguments, outputs, rounds, pruning rule and return values of slm_solve_l0_local_prove.  A node is split on the FREE group whose
+ * optimal z_g is closest to 1/2 among those strictly between 0 and 1 (ties: the lowest index; where every z_g is 0 or 1, the
+ * largest ||u_g||_inf, then the largest sum of h(t_j)); the IN child sets g and everything need*(g) reaches IN, the OUT child g
+ * and every group that transitively needs g OUT (cycles are legal).  An incumbent's value counts |cl(S)|; a child whose F(u) is
+ * below the incumbent replaces it, polished on ALL columns of cl(S(u)) inside the box where that is lower still.
+ * group_support_out[e] (n_groups ints, or NULL): cl(S) of cell e's incumbent.  The leaves' masks are GROUP masks; info[e].mode =
+ * 15.  WHERE THE TREE CLOSES: with a ridge or a box that binds; at eta = 0 under a loose box, and with deep hierarchies whose
+ * free groups are cheap, it does not, and the proven gap reached is returned.  Refusals, all before a device is touched, in this
+ * order: everything slm_solve_l0_local_prove refuses up to and including an incumbent outside the box; then the groups, need_ptr,
+ * need_idx and the row-sharded dataset as above.
+ */
+int slm_solve_l0_local_group_prove(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas /* [n_cells] each */,
+                                   double big_M, const double* incumbents /* n_cells * p, or NULL */,
+                                   const int32_t* need_ptr /* n_groups + 1, or NULL */, const int32_t* need_idx, double rel_gap,
+                                   int32_t max_nodes, int32_t width, int32_t max_sweeps /* <=0: default */,
+                                   int64_t leaf_capacity /* 0: no certificate */, double* beta_out /* n_cells * p */,
+                                   double* objective_out /* n_cells */, double* lower_out /* n_cells */, int32_t* nodes_out,
+                                   int32_t* rounds_out, int32_t* status_out /* n_cells each, or NULL */,
+                                   int32_t* group_support_out /* n_cells * n_groups, or NULL */, int32_t* leaf_cell /* leaf_capacity */,
+                                   uint64_t* leaf_in, uint64_t* leaf_out /* leaf_capacity * 16 each */, double* leaf_u /* leaf_capacity * p */,
+                                   double* leaf_lower /* leaf_capacity */, int64_t* leaf_count /* or NULL */,
+                                   slm_point_info* info /* n_cells or NULL */);
 
 /*
  * (added under ABI 24: two new symbols beside slm_solve_l0 and slm_solve_l0_wide, no existing entry, structure or constant

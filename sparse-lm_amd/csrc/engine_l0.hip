@@ -46,6 +46,7 @@
 #include "l0_local_group_kernels.hpp"
 #include "l0_local_bound_kernels.hpp"
 #include "l0_local_node_kernels.hpp"
+#include "l0_local_group_node_kernels.hpp"
 
 namespace {
 
@@ -1452,10 +1453,29 @@ struct L0NodeRunner {
   size_t dev_words = 0;
   long long launches = 0, launched_nodes = 0;
   std::vector<double> h;
+  int* groups_dev = nullptr;  // the grouped entries: gof [p] | gstart [ng + 1] | cptr [ng + 1] | cidx; NULL: the column kernel
+  int ng = 0;
+  size_t n_cidx = 0;
   ~L0NodeRunner() {
     if (s) (void)hipStreamSynchronize(s);
     dfree(dev);
     dfree(cells_dev);
+    dfree(groups_dev);
+  }
+  // after open(): the nodes are GROUP nodes from here on, bounded by l0_local_group_node_kernel
+  int set_groups(const L0GroupMap& gm) {
+    ng = gm.ng;
+    n_cidx = gm.cptr ? (size_t)gm.cptr[ng] : 0;
+    std::vector<int> w((size_t)p + 2 * ((size_t)ng + 1) + n_cidx, 0);
+    for (int g = 0; g < ng; ++g)
+      for (int j = gm.gstart[g]; j < gm.gstart[g + 1]; ++j) w[(size_t)j] = g;
+    memcpy(w.data() + p, gm.gstart, sizeof(int) * ((size_t)ng + 1));
+    if (gm.cptr) memcpy(w.data() + p + ng + 1, gm.cptr, sizeof(int) * ((size_t)ng + 1));
+    if (n_cidx) memcpy(w.data() + p + 2 * ((size_t)ng + 1), gm.cidx, sizeof(int) * n_cidx);
+    SLM_TRY(dalloc(&groups_dev, w.size()));
+    HIP_TRY(hipMemcpyAsync(groups_dev, w.data(), sizeof(int) * w.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // (w leaves scope)
+    return SLM_OK;
   }
   int open(slm_dataset* ds_, const L0NodeCell* cells, int n_cells_, int max_sweeps_, double gap_tol_, std::vector<double>* c_host) {
     ds = ds_;
@@ -1531,7 +1551,19 @@ struct L0NodeRunner {
     k.big_M = big_M; k.gap_tol = gap_tol;
     // (a node is one wave; the grid as for the bound: up to two workgroups a CU, the nodes beyond by the grid-stride loop)
     const int blocks = std::min((b.n + L0_WAVES - 1) / L0_WAVES, std::max(1, 2 * ds->eng->cus));
-    hipLaunchKernelGGL(l0_local_node_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    if (groups_dev) {
+      L0GnArgs gk;
+      memset(&gk, 0, sizeof(gk));
+      gk.nd = k;
+      gk.gof = groups_dev;
+      gk.gstart = groups_dev + p;
+      gk.cptr = groups_dev + p + ng + 1;
+      gk.cidx = groups_dev + p + 2 * ((size_t)ng + 1);
+      gk.ng = ng;
+      hipLaunchKernelGGL(l0_local_group_node_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, gk);
+    } else {
+      hipLaunchKernelGGL(l0_local_node_kernel, dim3((unsigned)blocks), dim3(64 * L0_WAVES), 0, s, k);
+    }
     SLM_TRY(check_launch());
     HIP_TRY(hipMemcpyAsync(h.data() + off_low, dd + off_low, sizeof(double) * (words - off_low), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1553,10 +1585,12 @@ struct L0NodeRunner {
 int solve_l0_local_nodes_impl(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M, int32_t n_nodes,
                               const int32_t* cell, const unsigned long long* in_mask, const unsigned long long* out_mask,
                               const double* parent_lower, const double* starts, int32_t max_sweeps, double gap_tol, double* lower_out,
-                              double* primal_out, double* upper_out, double* u_out, int32_t* stat_out, slm_point_info* info) {
+                              double* primal_out, double* upper_out, double* u_out, int32_t* stat_out, slm_point_info* info,
+                              const L0GroupMap* groups = nullptr) {
+  // (groups: the grouped entry, whose own check has passed; the nodes are GROUP nodes, l0_local_group_node_kernel bounds them, mode 14)
   if (!ds || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   long long which = 0;
-  switch (l0_nodes_check(n_cells, alphas, etas, big_M, n_nodes, cell, in_mask, out_mask, parent_lower, starts, ds->p, gap_tol, ds->singleton, row_sharded(ds),
+  switch (l0_nodes_check(n_cells, alphas, etas, big_M, n_nodes, cell, in_mask, out_mask, parent_lower, starts, ds->p, gap_tol, ds->singleton || groups, row_sharded(ds),
                          &which)) {
     case L0_ND_OK: break;
     case L0_ND_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
@@ -1585,6 +1619,7 @@ int solve_l0_local_nodes_impl(slm_dataset* ds, int32_t n_cells, const double* al
     for (int e = 0; e < n_cells; ++e) cells[(size_t)e] = l0_node_cell(alphas[e], etas[e], big_M);
     L0NodeRunner run;
     SLM_TRY(run.open(ds, cells.data(), n_cells, sweeps_cap, gap_tol, nullptr));
+    if (groups) SLM_TRY(run.set_groups(*groups));
     const L0NodeBatch b{n_nodes, cell, in_mask, out_mask, parent_lower, starts, lower.data(), primal.data(), upper.data(), u.data(), stat.data()};
     SLM_TRY(run.run(b));
   }
@@ -1602,7 +1637,7 @@ int solve_l0_local_nodes_impl(slm_dataset* ds, int32_t n_cells, const double* al
     l0_report(info + i, stat[2 * (size_t)i + 1] == 0, 0.0, upper[(size_t)i], primal[(size_t)i], lower[(size_t)i]);
     info[i].n_iter = stat[2 * (size_t)i];
     info[i].resid = (double)stat[2 * (size_t)i + 1];
-    info[i].mode = L0_ND_MODE;
+    info[i].mode = groups ? L0_GN_MODE : L0_ND_MODE;
   }
   if (u_out) memcpy(u_out, u.data(), sizeof(double) * n * (size_t)p);
   if (unclosed)
@@ -1621,10 +1656,11 @@ int solve_l0_local_prove_impl(slm_dataset* ds, int32_t n_cells, const double* al
                               double rel_gap, int32_t max_nodes, int32_t width, int32_t max_sweeps, int64_t leaf_capacity, double* beta_out,
                               double* objective_out, double* lower_out, int32_t* nodes_out, int32_t* rounds_out, int32_t* status_out,
                               int32_t* leaf_cell, unsigned long long* leaf_in, unsigned long long* leaf_out, double* leaf_u, double* leaf_lower,
-                              int64_t* leaf_count, slm_point_info* info) {
+                              int64_t* leaf_count, slm_point_info* info, const L0GroupMap* groups = nullptr) {
+  // (groups: the grouped entry, whose own check has passed; group nodes, the closure at a branch, mode 15)
   if (!ds || !beta_out || !objective_out || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
   long long which = 0;
-  switch (l0_prove_check(n_cells, alphas, etas, big_M, incumbents, ds->p, rel_gap, max_nodes, width, ds->singleton, row_sharded(ds), &which)) {
+  switch (l0_prove_check(n_cells, alphas, etas, big_M, incumbents, ds->p, rel_gap, max_nodes, width, ds->singleton || groups, row_sharded(ds), &which)) {
     case L0_PV_OK: break;
     case L0_PV_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
     case L0_PV_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
@@ -1654,6 +1690,7 @@ int solve_l0_local_prove_impl(slm_dataset* ds, int32_t n_cells, const double* al
     L0NodeRunner run;
     std::vector<double> ch;
     SLM_TRY(run.open(ds, cells.data(), n_cells, sweeps_cap, rel_gap / 100.0, &ch));
+    if (groups) SLM_TRY(run.set_groups(*groups));
     const size_t ld = (size_t)ds->ld;
     std::vector<double> Gh((size_t)p * ld);
     HIP_TRY(hipMemcpyAsync(Gh.data(), run.held.G, sizeof(double) * (size_t)p * ld, hipMemcpyDeviceToHost, run.s));
@@ -1664,7 +1701,7 @@ int solve_l0_local_prove_impl(slm_dataset* ds, int32_t n_cells, const double* al
     }
     SLM_TRY(l0_prove_tree(Gh.data(), ld, ch.data(), p, n_cells, cells.data(), incumbents, rel_gap, max_nodes, width,
                           [&](const L0NodeBatch& b) { return run.run(b); }, beta_out, objective_out, lower_out, nodes.data(), rounds.data(),
-                          status.data(), want_leaves ? &leaves : nullptr));
+                          status.data(), want_leaves ? &leaves : nullptr, groups));
   }
   if (leaf_count) *leaf_count = leaves.count;
   int open_cells = 0, first = -1;
@@ -1678,7 +1715,7 @@ int solve_l0_local_prove_impl(slm_dataset* ds, int32_t n_cells, const double* al
     info[e].n_iter = rounds[(size_t)e];
     info[e].rejects = nodes[(size_t)e];
     info[e].resid = (double)status[(size_t)e];
-    info[e].mode = L0_PV_MODE;
+    info[e].mode = groups ? L0_GP_MODE : L0_PV_MODE;
   }
   if (open_cells)
     return fail(SLM_ERR_NOT_CONVERGED, "the node limit (%d) ran out in %d of %d cells (the first: %d): the incumbent and a proven lower bound are "
@@ -1686,7 +1723,145 @@ int solve_l0_local_prove_impl(slm_dataset* ds, int32_t n_cells, const double* al
   return SLM_OK;
 }
 
+// The local proof WITH GROUPS (DESIGN 4d "Local proof with groups"; l0_host.hpp "local proof with groups").  The dataset's groups
+// (contiguous and ascending, as the grouped local search takes them) and the caller's direct need lists become the map both
+// entries hand on: gstart, the closed lists and their reverse.
+struct L0GroupMapOwner {
+  std::vector<int> gstart, cptr, cidx, rptr, ridx;
+  L0GroupMap map;
+  void build(const slm_dataset* ds, int ng, const int32_t* need_ptr, const int32_t* need_idx) {
+    const int p = (int)ds->p;
+    const bool single = ds->singleton || ds->h_gid.empty();
+    gstart.assign((size_t)ng + 1, p);
+    for (int j = p - 1; j >= 0; --j) gstart[(size_t)(single ? j : ds->h_gid[(size_t)j])] = j;
+    l0_lg_close(ng, need_ptr, need_idx, cptr, cidx);
+    l0_gp_reverse(ng, cptr, cidx, rptr, ridx);
+    map.ng = ng;
+    map.gstart = gstart.data();
+    map.cptr = cptr.data();
+    map.cidx = cidx.data();
+    map.rptr = rptr.data();
+    map.ridx = ridx.data();
+  }
+};
+// the refusals the two grouped entries share, in the words of the grouped local search
+int l0_gp_refuse(const L0GpRefusal& Q, int ng) {
+  switch (Q.kind) {
+    case L0_GP_ORDER:
+      return fail(SLM_ERR_UNSUPPORTED, "the grouped l0 local proof takes groups that are contiguous and ascending in column order "
+                  "(column %lld breaks it): the caller must order the columns by group", Q.which);
+    case L0_GP_NEED_PTR: return fail(SLM_ERR_BAD_ARG, "need_ptr must start at 0 and never fall (entry %lld)", Q.which);
+    case L0_GP_NEED_IDX: return fail(SLM_ERR_BAD_ARG, "need_idx[%lld] must name one of the %d groups", Q.which, ng);
+    case L0_GP_RANGE: return fail(SLM_ERR_BAD_ARG, "node %lld fixes a group beyond the %d groups of the dataset", Q.which, ng);
+    case L0_GP_UNCLOSED:
+      return fail(SLM_ERR_BAD_ARG, "node %lld is not closed under the hierarchy: an IN group brings every group it needs IN, an OUT group "
+                  "takes every group that needs it OUT", Q.which);
+    case L0_GP_SHARDED: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof is not built for row-sharded datasets");
+    default: return SLM_OK;
+  }
+}
+
+int solve_l0_local_group_nodes_impl(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M, int32_t n_nodes,
+                                    const int32_t* cell, const unsigned long long* in_mask, const unsigned long long* out_mask,
+                                    const double* parent_lower, const double* starts, const int32_t* need_ptr, const int32_t* need_idx,
+                                    int32_t max_sweeps, double gap_tol, double* lower_out, double* primal_out, double* upper_out, double* u_out,
+                                    int32_t* stat_out, slm_point_info* info) {
+  if (!ds || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  const int* gid = ds->singleton || ds->h_gid.empty() ? nullptr : ds->h_gid.data();
+  int ng = 0;
+  const L0GpRefusal Q = l0_group_nodes_check(n_cells, alphas, etas, big_M, n_nodes, cell, in_mask, out_mask, parent_lower, starts, ds->p, gap_tol,
+                                             gid, need_ptr, need_idx, row_sharded(ds), &ng);
+  if (Q.kind == L0_GP_FIRST) {
+    const long long which = Q.which;
+    switch (Q.nd) {
+      case L0_ND_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+      case L0_ND_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
+      case L0_ND_PROBLEMS: return fail(SLM_ERR_BAD_ARG, "n_cells must be at most %d cells (got %d)", L0_LS_MAX_PROBLEMS, n_cells);
+      case L0_ND_NODES: return fail(SLM_ERR_BAD_ARG, "n_nodes must be >= 1 (got %d)", n_nodes);
+      case L0_ND_BATCH: return fail(SLM_ERR_BAD_ARG, "n_nodes must be at most %d nodes (got %d)", L0_ND_MAX_BATCH, n_nodes);
+      case L0_ND_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
+      case L0_ND_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", which);
+      case L0_ND_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", which);
+      case L0_ND_GAP_TOL: return fail(SLM_ERR_BAD_ARG, "gap_tol must be >= 0");
+      case L0_ND_WIDTH: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof takes up to %d columns (got %lld)", L0_LS_PMAX, (long long)ds->p);
+      case L0_ND_CELL: return fail(SLM_ERR_BAD_ARG, "cell[%lld] is not a cell of the call", which);
+      case L0_ND_MASK: return fail(SLM_ERR_BAD_ARG, "node %lld holds a group that is both IN and OUT", which);
+      case L0_ND_PARENT: return fail(SLM_ERR_BAD_ARG, "parent_lower[%lld] is neither a number nor -infinity", which);
+      case L0_ND_START: return fail(SLM_ERR_BAD_ARG, "starts[%lld] is not a finite number", which);
+      default: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    }
+  }
+  if (Q.kind != L0_GP_OK) return l0_gp_refuse(Q, ng);
+  L0GroupMapOwner own;
+  own.build(ds, ng, need_ptr, need_idx);
+  return solve_l0_local_nodes_impl(ds, n_cells, alphas, etas, big_M, n_nodes, cell, in_mask, out_mask, parent_lower, starts, max_sweeps, gap_tol,
+                                   lower_out, primal_out, upper_out, u_out, stat_out, info, &own.map);
+}
+
+int solve_l0_local_group_prove_impl(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                    const double* incumbents, const int32_t* need_ptr, const int32_t* need_idx, double rel_gap, int32_t max_nodes,
+                                    int32_t width, int32_t max_sweeps, int64_t leaf_capacity, double* beta_out, double* objective_out,
+                                    double* lower_out, int32_t* nodes_out, int32_t* rounds_out, int32_t* status_out, int32_t* group_support_out,
+                                    int32_t* leaf_cell, unsigned long long* leaf_in, unsigned long long* leaf_out, double* leaf_u,
+                                    double* leaf_lower, int64_t* leaf_count, slm_point_info* info) {
+  if (!ds || !beta_out || !objective_out || !lower_out) return fail(SLM_ERR_BAD_ARG, "NULL argument");
+  const int* gid = ds->singleton || ds->h_gid.empty() ? nullptr : ds->h_gid.data();
+  int ng = 0;
+  const L0GpRefusal Q = l0_group_prove_check(n_cells, alphas, etas, big_M, incumbents, ds->p, rel_gap, max_nodes, width, gid, need_ptr, need_idx,
+                                             row_sharded(ds), &ng);
+  if (Q.kind == L0_GP_FIRST) {
+    const long long which = Q.which;
+    switch (Q.pv) {
+      case L0_PV_NULL: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+      case L0_PV_CELLS: return fail(SLM_ERR_BAD_ARG, "n_cells must be >= 1 (got %d)", n_cells);
+      case L0_PV_PROBLEMS: return fail(SLM_ERR_BAD_ARG, "n_cells must be at most %d cells (got %d)", L0_LS_MAX_PROBLEMS, n_cells);
+      case L0_PV_BIG_M: return fail(SLM_ERR_BAD_ARG, "big_M must be >= 0");
+      case L0_PV_ALPHA: return fail(SLM_ERR_BAD_ARG, "alphas[%lld] must be finite and >= 0", which);
+      case L0_PV_ETA: return fail(SLM_ERR_BAD_ARG, "etas[%lld] must be finite and >= 0", which);
+      case L0_PV_REL_GAP: return fail(SLM_ERR_BAD_ARG, "rel_gap must lie in [1e-10, 1]");
+      case L0_PV_MAX_NODES: return fail(SLM_ERR_BAD_ARG, "max_nodes must be >= 1 (got %d)", max_nodes);
+      case L0_PV_TREE_WIDTH: return fail(SLM_ERR_BAD_ARG, "width must be >= 1 (got %d)", width);
+      case L0_PV_WIDTH: return fail(SLM_ERR_UNSUPPORTED, "the l0 local proof takes up to %d columns (got %lld)", L0_LS_PMAX, (long long)ds->p);
+      case L0_PV_INCUMBENT: return fail(SLM_ERR_BAD_ARG, "incumbents[%lld] is outside the box [-big_M, big_M] or not a number", which);
+      default: return fail(SLM_ERR_BAD_ARG, "NULL argument");
+    }
+  }
+  if (Q.kind != L0_GP_OK) return l0_gp_refuse(Q, ng);
+  L0GroupMapOwner own;
+  own.build(ds, ng, need_ptr, need_idx);
+  const int rc = solve_l0_local_prove_impl(ds, n_cells, alphas, etas, big_M, incumbents, rel_gap, max_nodes, width, max_sweeps, leaf_capacity,
+                                           beta_out, objective_out, lower_out, nodes_out, rounds_out, status_out, leaf_cell, leaf_in, leaf_out,
+                                           leaf_u, leaf_lower, leaf_count, info, &own.map);
+  if (group_support_out && (rc == SLM_OK || rc == SLM_ERR_NOT_CONVERGED))  // cl(S) of every cell's incumbent
+    for (int e = 0; e < n_cells; ++e) l0_gp_closure(beta_out + (size_t)e * ds->p, own.map, group_support_out + (size_t)e * ng);
+  return rc;
+}
+
 }  // namespace
+
+// One batch of GROUP node relaxations of the local proof, from one launch of l0_local_group_node_kernel: one wavefront per node.
+extern "C" int slm_solve_l0_local_group_nodes(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                              int32_t n_nodes, const int32_t* cell, const uint64_t* in_mask, const uint64_t* out_mask,
+                                              const double* parent_lower, const double* starts, const int32_t* need_ptr, const int32_t* need_idx,
+                                              int32_t max_sweeps, double gap_tol, double* lower_out, double* primal_out, double* upper_out,
+                                              double* u_out, int32_t* stat_out, slm_point_info* info) {
+  return solve_l0_local_group_nodes_impl(ds, n_cells, alphas, etas, big_M, n_nodes, cell, reinterpret_cast<const unsigned long long*>(in_mask),
+                                         reinterpret_cast<const unsigned long long*>(out_mask), parent_lower, starts, need_ptr, need_idx,
+                                         max_sweeps, gap_tol, lower_out, primal_out, upper_out, u_out, stat_out, info);
+}
+
+// The local proof with groups and a hierarchy: branch and bound over GROUP nodes for every cell of a grid, one launch a round.
+extern "C" int slm_solve_l0_local_group_prove(slm_dataset* ds, int32_t n_cells, const double* alphas, const double* etas, double big_M,
+                                              const double* incumbents, const int32_t* need_ptr, const int32_t* need_idx, double rel_gap,
+                                              int32_t max_nodes, int32_t width, int32_t max_sweeps, int64_t leaf_capacity, double* beta_out,
+                                              double* objective_out, double* lower_out, int32_t* nodes_out, int32_t* rounds_out,
+                                              int32_t* status_out, int32_t* group_support_out, int32_t* leaf_cell, uint64_t* leaf_in,
+                                              uint64_t* leaf_out, double* leaf_u, double* leaf_lower, int64_t* leaf_count, slm_point_info* info) {
+  return solve_l0_local_group_prove_impl(ds, n_cells, alphas, etas, big_M, incumbents, need_ptr, need_idx, rel_gap, max_nodes, width, max_sweeps,
+                                         leaf_capacity, beta_out, objective_out, lower_out, nodes_out, rounds_out, status_out, group_support_out,
+                                         leaf_cell, reinterpret_cast<unsigned long long*>(leaf_in), reinterpret_cast<unsigned long long*>(leaf_out),
+                                         leaf_u, leaf_lower, leaf_count, info);
+}
 
 // The l0 local search on up to 16 row sets of one dataset: every (row set, cell, start) problem from one launch.
 extern "C" int slm_solve_l0_local_folds(slm_dataset* ds, int32_t count, const double* const* row_weights, const int64_t* n_effs,

@@ -2376,6 +2376,351 @@ inline int l0_node_batch_host(const double* G, size_t ld, const double* c, int p
   return 0;
 }
 
+// ---- local proof with groups (slm_solve_l0_local_group_nodes, slm_solve_l0_local_group_prove; csrc/l0_local_group_node_kernels.hpp;
+// tests/l0_local_group_prove_host_test.cpp; DESIGN 4d "Local proof with groups") ------------------------------------------------
+//
+// The objective is the group search's, F(beta) = 1/2 beta^T H beta - c^T beta + alpha |cl(S(beta))|.  Each GROUP's indicator is
+// relaxed to z_g in [0, 1] with |beta_j| <= M z_g for j in g and the cost eta ||beta_g||^2 / z_g + alpha z_g; minimising over z
+// leaves phi_g(b) = min over z in [||b||_inf / M, 1] of eta ||b||^2 / z + alpha z, whose conjugate is
+// phi_g*(t_g) = max(0, sum_{j in g} h(t_j) - alpha).  A node gives every GROUP one state, and for EVERY u, with t = c - G u,
+//     L_node(u) = -1/2 u^T G u - sum over FREE g of max(0, sum_{j in g} h(t_j) - alpha) - sum over IN g of (sum_{j in g} h(t_j) - alpha)
+// is at or below the minimum of F over the node: the relaxation ignores the hierarchy, and |cl(S)| >= |S|.  The hierarchy lives
+// in the branching (l0_prove_tree with a group map).
+//
+// THE DESCENT on P(b) = 1/2 b^T G b - c^T b + sum phi_g(b_g), column by column in ascending order:
+//   * an IN group's column steps clip(s / (a + 2 eta), +-M); an OUT group's and a failed pivot keep 0;
+//   * a FREE group of one column, and a column whose group is zero elsewhere, step l0_lb_coord: phi_g is the bound's phi there;
+//   * a FREE column whose group holds other non-zeros (R = their sum of squares, m = their largest modulus) gets the EXACT
+//     minimiser over x of 1/2 a x^2 - s x + phi_g, by bisection on the monotone derivative (l0_gn_coord; phi_g has the three
+//     regimes 2 sqrt(alpha eta) ||b||_2, eta ||b||^2 + alpha and eta M ||b||^2 / ||b||_inf + alpha ||b||_inf / M, told apart
+//     without a square root), never by alternating between b and z;
+//   * a FREE group of several columns that is ZERO moves iff S = sum_{j in g} h(t_j) > alpha, the exact test for zero; it then
+//     moves AS ONE to eps b*, b*_j = argmax t_j b - eta b^2 on the box, with eps = min(1, (S - alpha) / D), D an upper bound of
+//     |g| b*^T G b* (l0_gn_jump) -- a step that lowers P -- and the sweep goes on behind the group.
+// Sums over a group are walked in ascending column order by kernel, twin and restatement alike.  The group terms of P and L are
+// added in the lane of the group's FIRST column, so that singleton groups give l0_node_solve's bits.
+constexpr int L0_GN_BISECT = 48;                 // halvings of one coordinate's bracket [0, min(M, |s| / a)]
+constexpr int L0_GN_MODE = 14, L0_GP_MODE = 15;  // slm_point_info.mode of the two entries
+
+// groups as the node rule and the tree take them: contiguous ascending column ranges, the CLOSED need lists (l0_lg_close) and
+// their reverse (rptr, ridx: the groups that need g, transitively); cptr == NULL: no hierarchy
+struct L0GroupMap {
+  int ng = 0;
+  const int* gstart = nullptr;
+  const int* cptr = nullptr;
+  const int* cidx = nullptr;
+  const int* rptr = nullptr;
+  const int* ridx = nullptr;
+};
+// the reverse of closed lists: rptr / ridx list for every group the groups whose closed list holds it, ascending
+inline void l0_gp_reverse(int ng, const std::vector<int>& cptr, const std::vector<int>& cidx, std::vector<int>& rptr, std::vector<int>& ridx) {
+  rptr.assign((size_t)ng + 1, 0);
+  ridx.assign(cidx.size(), 0);
+  for (int v : cidx) ++rptr[(size_t)v + 1];
+  for (int g = 0; g < ng; ++g) rptr[(size_t)g + 1] += rptr[(size_t)g];
+  std::vector<int> at(rptr.begin(), rptr.end() - 1);
+  for (int g = 0; g < ng; ++g)
+    for (int k = cptr[(size_t)g]; k < cptr[(size_t)g + 1]; ++k) ridx[(size_t)at[(size_t)cidx[(size_t)k]]++] = g;
+}
+L0_LB_INLINE constexpr int l0_gn_bit(const unsigned long long* mask, int g) { return (int)((mask[g >> 6] >> (g & 63)) & 1ull); }
+// b*(t): the maximiser of t b - eta b^2 over the box
+L0_LB_INLINE constexpr double l0_gn_bstar(double t, double eta, double big_M) {
+  L0_LB_STRICT
+  if (eta > 0.0) {
+    const double b = t / (2.0 * eta);
+    return b < -big_M ? -big_M : (b > big_M ? big_M : b);
+  }
+  return t > 0.0 ? big_M : (t < 0.0 ? -big_M : 0.0);
+}
+// eps of a zero group's move (0: it stays): S its sum of h(t_j), n its columns, amax the largest pivot.  b*^T G b* <= n amax
+// ||b*||^2, and ||b*||^2 <= S / eta (eta > 0: eta b*^2 <= h) or <= n M^2 (eta = 0).
+L0_LB_INLINE constexpr double l0_gn_jump(double S, double alpha, double eta, double big_M, double amax, int n) {
+  L0_LB_STRICT
+  if (!(S > alpha)) return 0.0;
+  const double dn = (double)n;
+  const double den = eta > 0.0 ? dn * amax * S / eta : dn * dn * amax * big_M * big_M;
+  const double e = (S - alpha) / den;
+  return e < 1.0 ? e : 1.0;
+}
+// is the derivative of 1/2 a x^2 - as x + phi_g at x >= 0 at or below zero?  (R > 0, so m > 0.)
+L0_LB_INLINE constexpr bool l0_gn_below(double x, double as, double a, double R, double m, double alpha, double eta, double big_M) {
+  L0_LB_STRICT
+  const double w = as - a * x;
+  if (!(eta > 0.0)) return (x > m ? alpha / big_M : 0.0) <= w;
+  const double N2 = R + x * x, inf = x > m ? x : m;
+  if (eta * N2 >= alpha) return 2.0 * eta * x <= w;  // z = 1
+  if (eta * N2 * big_M * big_M <= alpha * inf * inf)  // the link binds: z = ||b||_inf / M
+    return (x > m ? eta * big_M * (1.0 - R / (x * x)) + alpha / big_M : 2.0 * eta * big_M * x / m) <= w;
+  return w >= 0.0 && 4.0 * alpha * eta * x * x <= w * w * N2;  // 2 sqrt(alpha eta) x / ||b||_2 <= w, squared
+}
+// the coordinate step of a FREE column whose group holds other non-zeros
+L0_LB_INLINE constexpr double l0_gn_coord(double s, double a, double R, double m, double alpha, double eta, double big_M) {
+  L0_LB_STRICT
+  const double as = s < 0.0 ? -s : s;
+  double hi = as / a, lo = 0.0;
+  if (hi > big_M) hi = big_M;
+  if (l0_gn_below(hi, as, a, R, m, alpha, eta, big_M)) {
+    lo = hi;
+  } else {
+    for (int i = 0; i < L0_GN_BISECT; ++i) {
+      const double mid = 0.5 * (lo + hi);
+      if (l0_gn_below(mid, as, a, R, m, alpha, eta, big_M)) lo = mid;
+      else hi = mid;
+    }
+  }
+  return s < 0.0 ? -lo : lo;
+}
+// phi_g of a group of several columns from N2 = ||b||^2 and inf = ||b||_inf
+L0_LB_INLINE constexpr double l0_gn_phi(double N2, double inf, double alpha, double eta, double big_M) {
+  L0_LB_STRICT
+  if (!(N2 > 0.0)) return 0.0;
+  if (!(eta > 0.0)) return alpha * inf / big_M;
+  if (eta * N2 >= alpha) return eta * N2 + alpha;
+  if (eta * N2 * big_M * big_M <= alpha * inf * inf) return eta * big_M * N2 / inf + alpha * inf / big_M;
+  return __builtin_sqrt(4.0 * alpha * eta * N2);
+}
+// a group's terms of P_node and of -L_node by state (several columns; S = sum of h(t_j))
+L0_LB_INLINE constexpr double l0_gn_group_phi(double N2, double inf, double alpha, double eta, double big_M, int state) {
+  L0_LB_STRICT
+  if (state == L0_ND_FREE) return l0_gn_phi(N2, inf, alpha, eta, big_M);
+  if (state != L0_ND_IN) return 0.0;
+  return eta * N2 + alpha;
+}
+L0_LB_INLINE constexpr double l0_gn_group_conj(double S, double alpha, int state) {
+  L0_LB_STRICT
+  const double v = S - alpha;
+  if (state == L0_ND_FREE) return v > 0.0 ? v : 0.0;
+  if (state != L0_ND_IN) return 0.0;
+  return v;
+}
+
+// cl(S(u)) by groups: in[g] = 1 where g holds a non-zero or is needed by a group that does.  Returns |cl(S)|.
+inline int l0_gp_closure(const double* u, const L0GroupMap& gm, int* in) {
+  for (int g = 0; g < gm.ng; ++g) in[g] = 0;
+  for (int g = 0; g < gm.ng; ++g) {
+    bool any = false;
+    for (int j = gm.gstart[g]; j < gm.gstart[g + 1]; ++j) any = any || u[j] != 0.0;
+    if (!any) continue;
+    in[g] = 1;
+    for (int k = gm.cptr ? gm.cptr[g] : 0; gm.cptr && k < gm.cptr[g + 1]; ++k) in[gm.cidx[k]] = 1;
+  }
+  int count = 0;
+  for (int g = 0; g < gm.ng; ++g) count += in[g];
+  return count;
+}
+inline L0NodeValues l0_gn_values(const double* u, const double* t, const double* c, int p, const L0NodeCell& cell, const L0GroupMap& gm,
+                                 const unsigned char* gstate, double ncl) {
+  L0_LB_STRICT
+  double qp[64] = {0.0}, ql[64] = {0.0}, sp[64] = {0.0}, sc[64] = {0.0}, s2[64] = {0.0};
+  for (int j = 0; j < p; ++j) {
+    const int l = j & 63;
+    qp[l] += u[j] * (c[j] + t[j]);
+    ql[l] += u[j] * (c[j] - t[j]);
+    s2[l] += u[j] * u[j];
+  }
+  for (int g = 0; g < gm.ng; ++g) {
+    const int lo = gm.gstart[g], hi = gm.gstart[g + 1], l = lo & 63, st = gstate[g];
+    if (hi - lo == 1) {
+      sp[l] += l0_node_phi(u[lo], cell.alpha, cell.eta, cell.lam, cell.tauc, st);
+      sc[l] += l0_node_conj(t[lo], cell.alpha, cell.eta, cell.big_M, st);
+      continue;
+    }
+    double N2 = 0.0, inf = 0.0, S = 0.0;
+    for (int k = lo; k < hi; ++k) {
+      const double x = u[k], ax = x < 0.0 ? -x : x;
+      N2 += x * x;
+      inf = ax > inf ? ax : inf;
+      S += l0_node_h(t[k], cell.eta, cell.big_M);
+    }
+    sp[l] += l0_gn_group_phi(N2, inf, cell.alpha, cell.eta, cell.big_M, st);
+    sc[l] += l0_gn_group_conj(S, cell.alpha, st);
+  }
+  return l0_node_combine(l0_lb_wave_sum(qp), l0_lb_wave_sum(ql), l0_lb_wave_sum(sp), l0_lb_wave_sum(sc), l0_lb_wave_sum(s2), ncl, cell.alpha,
+                         cell.eta);
+}
+
+// The group node kernel's twin without a device, change for change.  gin, gout: L0_ND_WORDS words each, bit g for group g.
+// With singleton groups and no hierarchy it returns l0_node_solve's bits.
+inline L0NodeResult l0_group_node_solve(const double* G, size_t ld, const double* c, int p, const L0NodeCell& cell, const L0GroupMap& gm,
+                                        const unsigned long long* gin, const unsigned long long* gout, const double* start, int max_sweeps,
+                                        double gap_tol, double* u) {
+  L0_LB_STRICT
+  L0NodeResult R;
+  const double big_M = cell.big_M, alpha = cell.alpha, eta = cell.eta;
+  std::vector<double> t(c, c + p), a((size_t)p);
+  std::vector<unsigned char> gstate((size_t)gm.ng);
+  std::vector<int> gof((size_t)p), closed((size_t)gm.ng);
+  for (int g = 0; g < gm.ng; ++g) {
+    gstate[(size_t)g] = (unsigned char)(l0_gn_bit(gin, g) | (l0_gn_bit(gout, g) << 1));
+    for (int j = gm.gstart[g]; j < gm.gstart[g + 1]; ++j) gof[(size_t)j] = g;
+  }
+  double amax = 0.0;
+  for (int j = 0; j < p; ++j) {
+    a[(size_t)j] = G[(size_t)j * ld + j];
+    u[j] = 0.0;
+    amax = std::fmax(amax, a[(size_t)j]);
+  }
+  for (int j = 0; j < p; ++j)
+    if (!(a[(size_t)j] > L0_PIVOT * amax) || gstate[(size_t)gof[(size_t)j]] == L0_ND_OUT) a[(size_t)j] = 0.0;
+  const double L0 = l0_gn_values(u, t.data(), c, p, cell, gm, gstate.data(), 0.0).L;
+  auto axpy = [&](int j, double w) {
+    const double* row = G + (size_t)j * ld;
+    for (int k = 0; k < p; ++k) t[(size_t)k] = std::fma(w, row[k], t[(size_t)k]);
+  };
+  auto build = [&]() {
+    for (int k = 0; k < p; ++k) t[(size_t)k] = c[k];
+    for (int j = 0; j < p; ++j)
+      if (u[j] != 0.0) axpy(j, -u[j]);
+  };
+  if (start)
+    for (int j = 0; j < p; ++j)
+      if (a[(size_t)j] > 0.0) u[j] = start[j] < -big_M ? -big_M : (start[j] > big_M ? big_M : start[j]);
+  build();
+  for (int sw = 0;; ++sw) {
+    if (sw == max_sweeps) {
+      R.status |= L0_LS_SWEEPS_OUT;
+      break;
+    }
+    for (int j = 0; j < p; ++j) {
+      const double aj = a[(size_t)j];
+      if (!(aj > 0.0)) continue;
+      const int g = gof[(size_t)j], lo = gm.gstart[g], hi = gm.gstart[g + 1], st = gstate[(size_t)g];
+      const double s = t[(size_t)j] + aj * u[j];
+      double nb = 0.0;
+      if (st != L0_ND_FREE || hi - lo == 1) {
+        nb = l0_node_coord(s, aj, eta, cell.lam, cell.tauc, big_M, st);
+      } else {
+        double Rr = 0.0, m = 0.0, S = 0.0;
+        for (int k = lo; k < hi; ++k) {
+          S += l0_node_h(t[(size_t)k], eta, big_M);
+          if (k == j) continue;
+          const double x = u[k], ax = x < 0.0 ? -x : x;
+          Rr += x * x;
+          m = ax > m ? ax : m;
+        }
+        if (!(Rr > 0.0) && u[j] == 0.0) {  // the group is zero: it moves as one, or not at all
+          const double eps = l0_gn_jump(S, alpha, eta, big_M, amax, hi - lo);
+          nb = eps * l0_gn_bstar(t[(size_t)j], eta, big_M);
+          if (!l0_lb_changed(nb, 0.0)) continue;
+          for (int k = lo; k < hi; ++k)
+            if (a[(size_t)k] > 0.0) u[k] = eps * l0_gn_bstar(t[(size_t)k], eta, big_M);
+          for (int k = lo; k < hi; ++k)
+            if (u[k] != 0.0) {
+              axpy(k, -u[k]);
+              ++R.changes;
+            }
+          j = hi - 1;
+          continue;
+        }
+        nb = !(Rr > 0.0) ? l0_lb_coord(s, aj, eta, cell.lam, cell.tauc, big_M) : l0_gn_coord(s, aj, Rr, m, alpha, eta, big_M);
+      }
+      if (!l0_lb_changed(nb, u[j])) continue;
+      const double delta = nb - u[j];
+      u[j] = nb;
+      axpy(j, -delta);
+      ++R.changes;
+    }
+    ++R.sweeps;
+    const L0NodeValues v = l0_gn_values(u, t.data(), c, p, cell, gm, gstate.data(), 0.0);
+    if (l0_lb_closed(v.P, v.L, alpha, gap_tol)) break;
+  }
+  build();
+  const L0NodeValues v = l0_gn_values(u, t.data(), c, p, cell, gm, gstate.data(), (double)l0_gp_closure(u, gm, closed.data()));
+  R.lower = v.L > L0 ? v.L : L0;
+  R.primal = v.P;
+  R.upper = v.F;
+  return R;
+}
+// the batch on the host: the group twin, node after node
+inline int l0_group_node_batch_host(const double* G, size_t ld, const double* c, int p, const L0NodeCell* cells, const L0GroupMap& gm,
+                                    int max_sweeps, double gap_tol, const L0NodeBatch& b) {
+  for (int i = 0; i < b.n; ++i) {
+    const L0NodeResult r = l0_group_node_solve(G, ld, c, p, cells[b.cell[i]], gm, b.in_mask + (size_t)i * L0_ND_WORDS,
+                                               b.out_mask + (size_t)i * L0_ND_WORDS, b.starts ? b.starts + (size_t)i * p : nullptr, max_sweeps,
+                                               gap_tol, b.u + (size_t)i * p);
+    b.lower[i] = !b.parent_lower || r.lower > b.parent_lower[i] ? r.lower : b.parent_lower[i];
+    b.primal[i] = r.primal;
+    b.upper[i] = r.upper;
+    b.stat[2 * i] = r.sweeps;
+    b.stat[2 * i + 1] = r.status;
+  }
+  return 0;
+}
+
+// The GROUP a node is split on: the FREE group whose optimal z_g is closest to 1/2 among those strictly between 0 and 1 (ties:
+// the lowest index); where every FREE z_g is 0 or 1, the FREE group of largest ||u_g||_inf > 0, and where all are zero that of
+// largest sum of h(t_j), t = c - G u.  z_g of one column is the column rule's min(|u| / tauc, 1); of several it is
+// sqrt(eta ||u_g||^2 / alpha) held in [||u_g||_inf / M, 1] (eta = 0: ||u_g||_inf / M).  -1: no group is FREE.
+inline int l0_gp_branch(const double* G, size_t ld, const double* c, int p, const L0NodeCell& cell, const L0GroupMap& gm,
+                        const unsigned long long* gin, const unsigned long long* gout, const double* u) {
+  L0_LB_STRICT
+  int pick = -1;
+  double dist = 1.0, top = 0.0;
+  for (int g = 0; g < gm.ng; ++g) {
+    if (l0_gn_bit(gin, g) || l0_gn_bit(gout, g)) continue;
+    const int lo = gm.gstart[g], hi = gm.gstart[g + 1];
+    double z = 0.0;
+    if (hi - lo == 1) {
+      const double au = std::fabs(u[lo]);
+      z = cell.tauc > 0.0 ? (au / cell.tauc < 1.0 ? au / cell.tauc : 1.0) : (au > 0.0 ? 1.0 : 0.0);
+    } else {
+      double N2 = 0.0, inf = 0.0;
+      for (int k = lo; k < hi; ++k) {
+        N2 += u[k] * u[k];
+        inf = std::fabs(u[k]) > inf ? std::fabs(u[k]) : inf;
+      }
+      if (N2 > 0.0) {
+        const double low = inf / cell.big_M;
+        if (!(cell.eta > 0.0)) {
+          z = low;
+        } else {
+          const double zs = cell.alpha > 0.0 ? std::sqrt(cell.eta * N2 / cell.alpha) : 1.0;
+          z = zs < low ? low : (zs > 1.0 ? 1.0 : zs);
+        }
+      }
+    }
+    if (!(z > 0.0 && z < 1.0)) continue;
+    const double d = std::fabs(z - 0.5);
+    if (d < dist) {
+      dist = d;
+      pick = g;
+    }
+  }
+  if (pick >= 0) return pick;
+  for (int g = 0; g < gm.ng; ++g) {
+    if (l0_gn_bit(gin, g) || l0_gn_bit(gout, g)) continue;
+    double inf = 0.0;
+    for (int k = gm.gstart[g]; k < gm.gstart[g + 1]; ++k) inf = std::fabs(u[k]) > inf ? std::fabs(u[k]) : inf;
+    if (inf > top) {
+      top = inf;
+      pick = g;
+    }
+  }
+  if (pick >= 0) return pick;
+  std::vector<double> t(c, c + p);
+  for (int k = 0; k < p; ++k)
+    if (u[k] != 0.0)
+      for (int j = 0; j < p; ++j) t[(size_t)j] -= G[(size_t)k * ld + j] * u[k];
+  top = -1.0;
+  for (int g = 0; g < gm.ng; ++g) {
+    if (l0_gn_bit(gin, g) || l0_gn_bit(gout, g)) continue;
+    double S = 0.0;
+    for (int k = gm.gstart[g]; k < gm.gstart[g + 1]; ++k) S += l0_node_h(t[(size_t)k], cell.eta, cell.big_M);
+    if (S > top) {
+      top = S;
+      pick = g;
+    }
+  }
+  return pick;
+}
+// the masks of the children of a split on group g: the IN child takes g and need*(g), the OUT child g and every group that needs g
+inline void l0_gp_child(const L0GroupMap& gm, int g, bool in_child, unsigned long long* mask) {
+  mask[g >> 6] |= 1ull << (g & 63);
+  const int* ptr = in_child ? gm.cptr : gm.rptr;
+  const int* idx = in_child ? gm.cidx : gm.ridx;
+  for (int k = ptr ? ptr[g] : 0; ptr && k < ptr[g + 1]; ++k) mask[idx[k] >> 6] |= 1ull << (idx[k] & 63);
+}
+
 // The column a node is split on: the FREE column whose z_j = min(|u_j| / tauc, 1) (tauc = 0: 1 where u_j != 0) is closest to
 // 1/2 among those strictly between 0 and 1, ties to the lowest index; where every FREE z_j is 0 or 1, the FREE column of largest
 // |u_j| > 0, and where all are zero that of largest |t_j|, t = c - G u.  -1: no column is FREE.
@@ -2458,7 +2803,8 @@ struct L0ProveLeaves {
 template <class Bound>
 inline int l0_prove_tree(const double* G, size_t ld, const double* c, int p, int n_cells, const L0NodeCell* cells, const double* incumbents,
                          double rel_gap, int max_nodes, int width, Bound&& bound, double* beta_out, double* objective_out,
-                         double* lower_out, int* nodes_out, int* rounds_out, int* status_out, L0ProveLeaves* leaves = nullptr) {
+                         double* lower_out, int* nodes_out, int* rounds_out, int* status_out, L0ProveLeaves* leaves = nullptr,
+                         const L0GroupMap* groups = nullptr) {
   struct Node {
     unsigned long long in[L0_ND_WORDS], out[L0_ND_WORDS];
     double lower;
@@ -2487,7 +2833,10 @@ inline int l0_prove_tree(const double* G, size_t ld, const double* c, int p, int
     Cell& t = T[(size_t)e];
     t.beta.assign((size_t)p, 0.0);
     if (incumbents) {
-      const double F = l0_prove_value(G, ld, c, p, cells[e].alpha, cells[e].eta, incumbents + (size_t)e * p);
+      std::vector<int> closed(groups ? (size_t)groups->ng : 0);
+      const double F = groups ? l0_prove_value(G, ld, c, p, 0.0, cells[e].eta, incumbents + (size_t)e * p) +
+                                    cells[e].alpha * (double)l0_gp_closure(incumbents + (size_t)e * p, *groups, closed.data())
+                              : l0_prove_value(G, ld, c, p, cells[e].alpha, cells[e].eta, incumbents + (size_t)e * p);
       if (F < 0.0) {
         t.best = F;
         t.beta.assign(incumbents + (size_t)e * p, incumbents + (size_t)(e + 1) * p);
@@ -2531,10 +2880,22 @@ inline int l0_prove_tree(const double* G, size_t ld, const double* c, int p, int
           if ((int)b_cell.size() + 2 > L0_ND_MAX_BATCH) break;  // no room in this round: the cell waits
           Node nd = std::move(t.open.begin()->second);
           t.open.erase(t.open.begin());
-          const int j = l0_prove_branch(G, ld, c, p, cells[e].tauc, nd.in, nd.out, nd.u.data());
+          const int j = groups ? l0_gp_branch(G, ld, c, p, cells[e], *groups, nd.in, nd.out, nd.u.data())
+                               : l0_prove_branch(G, ld, c, p, cells[e].tauc, nd.in, nd.out, nd.u.data());
           if (j < 0) {  // every column is fixed and the node is still open: its relaxation was not closed
             t.stuck = std::min(t.stuck, nd.lower);
             leaf(e, nd);
+            continue;
+          }
+          if (groups) {  // (a split on a GROUP: the IN child takes what the group needs, the OUT child what needs the group)
+            unsigned long long child[L0_ND_WORDS];
+            memcpy(child, nd.in, sizeof(child));
+            l0_gp_child(*groups, j, true, child);
+            push(e, child, nd.out, nd.lower, nd.u.data());
+            memcpy(child, nd.out, sizeof(child));
+            l0_gp_child(*groups, j, false, child);
+            push(e, nd.in, child, nd.lower, nd.u.data());
+            ++popped;
             continue;
           }
           nd.in[j >> 6] |= 1ull << (j & 63);
@@ -2567,11 +2928,23 @@ inline int l0_prove_tree(const double* G, size_t ld, const double* c, int p, int
       t.beta.assign(u, u + p);
       std::vector<double> pol(u, u + p);
       std::vector<int> cols;
-      for (int j = 0; j < p; ++j)
-        if (pol[(size_t)j] != 0.0) cols.push_back(j);
-      const double quad = l0_ls_polish_on(G, ld, c, cells[e].eta, cells[e].big_M, cols, pol.data());
       int nnz = 0;
-      for (int j = 0; j < p; ++j) nnz += pol[(size_t)j] != 0.0;
+      if (groups) {  // (the group search's polish: every column of the groups in cl(S), inside the box; alpha counts cl(S) after it)
+        std::vector<int> closed((size_t)groups->ng);
+        l0_gp_closure(u, *groups, closed.data());
+        for (int g = 0; g < groups->ng; ++g)
+          for (int j = groups->gstart[g]; closed[(size_t)g] && j < groups->gstart[g + 1]; ++j) cols.push_back(j);
+      } else {
+        for (int j = 0; j < p; ++j)
+          if (pol[(size_t)j] != 0.0) cols.push_back(j);
+      }
+      const double quad = l0_ls_polish_on(G, ld, c, cells[e].eta, cells[e].big_M, cols, pol.data());
+      if (groups) {
+        std::vector<int> closed((size_t)groups->ng);
+        nnz = l0_gp_closure(pol.data(), *groups, closed.data());
+      } else {
+        for (int j = 0; j < p; ++j) nnz += pol[(size_t)j] != 0.0;
+      }
       const double F = quad + cells[e].alpha * (double)nnz;
       if (F < t.best) {
         t.best = F;
@@ -2684,6 +3057,99 @@ inline L0PvRefusal l0_prove_check(long long n_cells, const double* alphas, const
   if (!singleton) return L0_PV_GROUPS;
   if (sharded) return L0_PV_SHARDED;
   return L0_PV_OK;
+}
+
+// What the two grouped entries refuse before a device is touched, in this order: everything slm_solve_l0_local_nodes
+// (slm_solve_l0_local_prove) refuses up to its groups (nd, pv); groups that are not contiguous and ascending (which: the
+// column); a need_ptr that does not start at 0 or falls (which: the group); a need_idx outside the groups, or a NULL need_idx
+// under a non-empty need_ptr (which: the entry); for the nodes entry a mask bit beyond the groups, then masks that are not
+// CLOSED -- an IN group whose need*(g) is not all IN, or an OUT group needed by one that is not OUT (which: the node); a
+// row-sharded dataset.  gid: [p] the dataset's group index, or NULL for singleton groups; *n_groups: the groups found.
+enum L0GpKind { L0_GP_OK = 0, L0_GP_FIRST, L0_GP_ORDER, L0_GP_NEED_PTR, L0_GP_NEED_IDX, L0_GP_RANGE, L0_GP_UNCLOSED, L0_GP_SHARDED };
+struct L0GpRefusal {
+  L0GpKind kind = L0_GP_OK;
+  L0NdRefusal nd = L0_ND_OK;
+  L0PvRefusal pv = L0_PV_OK;
+  long long which = 0;
+};
+inline L0GpKind l0_gp_groups_check(long long p, const int* gid, const int* need_ptr, const int* need_idx, long long* which, int* n_groups) {
+  for (long long j = 0; gid && j < p; ++j) {
+    const int step = j == 0 ? gid[0] + 1 : gid[j] - gid[j - 1];
+    if ((step != 0 && step != 1) || (j == 0 && step != 1)) {
+      *which = j;
+      return L0_GP_ORDER;
+    }
+  }
+  const long long ng = p < 1 ? 0 : (gid ? (long long)gid[p - 1] + 1 : p);
+  if (n_groups) *n_groups = (int)ng;
+  if (need_ptr) {
+    *which = 0;
+    if (need_ptr[0] != 0) return L0_GP_NEED_PTR;
+    for (long long g = 0; g < ng; ++g)
+      if (need_ptr[g + 1] < need_ptr[g]) {
+        *which = g + 1;
+        return L0_GP_NEED_PTR;
+      }
+    if (need_ptr[ng] > 0 && !need_idx) return L0_GP_NEED_IDX;
+    for (long long k = 0; k < need_ptr[ng]; ++k)
+      if (need_idx[k] < 0 || need_idx[k] >= ng) {
+        *which = k;
+        return L0_GP_NEED_IDX;
+      }
+  }
+  return L0_GP_OK;
+}
+inline L0GpRefusal l0_group_nodes_check(long long n_cells, const double* alphas, const double* etas, double big_M, long long n_nodes,
+                                        const int* cell, const unsigned long long* in_mask, const unsigned long long* out_mask,
+                                        const double* parent_lower, const double* starts, long long p, double gap_tol, const int* gid,
+                                        const int* need_ptr, const int* need_idx, bool sharded, int* n_groups = nullptr) {
+  L0GpRefusal R;
+  R.nd = l0_nodes_check(n_cells, alphas, etas, big_M, n_nodes, cell, in_mask, out_mask, parent_lower, starts, p, gap_tol, true, false, &R.which);
+  if (R.nd != L0_ND_OK) {
+    R.kind = L0_GP_FIRST;
+    return R;
+  }
+  int ng = 0;
+  R.kind = l0_gp_groups_check(p, gid, need_ptr, need_idx, &R.which, &ng);
+  if (n_groups) *n_groups = ng;
+  if (R.kind != L0_GP_OK) return R;
+  std::vector<int> cptr, cidx;
+  l0_lg_close(ng, need_ptr, need_idx, cptr, cidx);
+  for (long long i = 0; i < n_nodes; ++i) {
+    const unsigned long long *in = in_mask + i * L0_ND_WORDS, *out = out_mask + i * L0_ND_WORDS;
+    R.which = i;
+    for (int g = ng; g < 64 * L0_ND_WORDS; ++g)
+      if (l0_gn_bit(in, g) || l0_gn_bit(out, g)) {
+        R.kind = L0_GP_RANGE;
+        return R;
+      }
+    for (int g = 0; g < ng; ++g)
+      for (int k = cptr[(size_t)g]; k < cptr[(size_t)g + 1]; ++k) {
+        const int h = cidx[(size_t)k];  // g needs h
+        if ((l0_gn_bit(in, g) && !l0_gn_bit(in, h)) || (l0_gn_bit(out, h) && !l0_gn_bit(out, g))) {
+          R.kind = L0_GP_UNCLOSED;
+          return R;
+        }
+      }
+  }
+  R.which = 0;
+  if (sharded) R.kind = L0_GP_SHARDED;
+  return R;
+}
+inline L0GpRefusal l0_group_prove_check(long long n_cells, const double* alphas, const double* etas, double big_M, const double* incumbents,
+                                        long long p, double rel_gap, long long max_nodes, long long width, const int* gid, const int* need_ptr,
+                                        const int* need_idx, bool sharded, int* n_groups = nullptr) {
+  L0GpRefusal R;
+  R.pv = l0_prove_check(n_cells, alphas, etas, big_M, incumbents, p, rel_gap, max_nodes, width, true, false, &R.which);
+  if (R.pv != L0_PV_OK) {
+    R.kind = L0_GP_FIRST;
+    return R;
+  }
+  R.kind = l0_gp_groups_check(p, gid, need_ptr, need_idx, &R.which, n_groups);
+  if (R.kind != L0_GP_OK) return R;
+  R.which = 0;
+  if (sharded) R.kind = L0_GP_SHARDED;
+  return R;
 }
 
 }  // namespace slm

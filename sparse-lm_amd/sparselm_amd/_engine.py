@@ -112,6 +112,8 @@ ABI_SYMBOLS = (
     "slm_solve_l0_local_bound",
     "slm_solve_l0_local_nodes",
     "slm_solve_l0_local_prove",
+    "slm_solve_l0_local_group_nodes",
+    "slm_solve_l0_local_group_prove",
     "slm_dataset_covariance",
     "slm_dataset_covariance_folds",
     "slm_dataset_covariance_folds_begin",
@@ -393,6 +395,10 @@ def load_library():
             "slm_solve_l0_local_nodes": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, vp, P(_PointInfo)],
             "slm_solve_l0_local_prove": [vp, i32, vp, vp, dbl, vp, dbl, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                          P(_PointInfo)],
+            "slm_solve_l0_local_group_nodes": [vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, i32, dbl, vp, vp, vp, vp, vp,
+                                               P(_PointInfo)],
+            "slm_solve_l0_local_group_prove": [vp, i32, vp, vp, dbl, vp, vp, vp, dbl, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, P(_PointInfo)],
             "slm_dataset_covariance": [vp, vp, i64],
             "slm_dataset_covariance_folds": [vp, vp, vp, i32],
             "slm_dataset_covariance_folds_begin": [vp, vp, vp, i32, P(i32)],
@@ -1731,22 +1737,7 @@ class Dataset:
         al, et, cells = _l0_local_cells(alphas, etas, n_cells)
         drop = 1 if intercept else 0
         ps, gs, count = self.p - drop, max(self.n_groups - drop, 0), len(rws)
-        if need is None:
-            ptr = idx = None
-        elif isinstance(need, tuple):
-            ptr, idx = (None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in need)
-            if ptr is None or len(ptr) != gs + 1:
-                raise ValueError(f"need_ptr must have {gs + 1} entries")
-            if idx is not None and len(ptr) and len(idx) < max(int(ptr.max()), 0):
-                raise ValueError("need_idx is shorter than need_ptr says")
-        else:
-            lists = [np.asarray(v, dtype=np.int64).reshape(-1) for v in need]
-            if len(lists) != gs:
-                raise ValueError(f"need must have {gs} entries")
-            ptr = np.concatenate([[0], np.cumsum([len(v) for v in lists])]).astype(np.int32)
-            idx = np.ascontiguousarray(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]), dtype=np.int32)
-        if idx is not None and not len(idx):
-            idx = np.zeros(1, dtype=np.int32)  # (an empty array has no address worth handing over)
+        ptr, idx = _l0_need_csr(need, gs)
         st, ns = _l0_local_starts(starts, n_starts, (count, cells), ps, f"{count}, {cells}, n_starts, {ps}")
         # (else the engine refuses: the outputs only have to exist)
         sized = 1 <= count <= 16 and cells >= 1 and ns >= 1 and cells * ns <= L0_LOCAL_MAX_PROBLEMS and count * cells * ns <= L0_LOCAL_MAX_PROBLEMS
@@ -1826,8 +1817,26 @@ class Dataset:
                 "call_status": int(rc)} for e in range(cnt)]
         return lower, primal, u, stats, out
 
+    def solve_l0_local_group_nodes(self, alphas, etas, cell, in_mask, out_mask, need=None, big_M=100.0, parent_lower=None, starts=None,
+                                   max_sweeps=0, gap_tol=1e-9, n_cells=None):
+        """``slm_solve_l0_local_group_nodes``: ONE BATCH of GROUP node relaxations of the local proof with groups
+        (``l0_local_group_node_kernel``, csrc/l0_local_group_node_kernels.hpp).  As ``solve_l0_local_nodes``, with the masks BY
+        GROUP (bit ``g & 63`` of word ``g >> 6``: group ``g`` of the dataset's contiguous, ascending groups) and ``need`` as for
+        ``solve_l0_local_groups``; ``upper = F(u)`` counts ``|cl(S(u))|``.  Masks that are not closed under the hierarchy are
+        refused."""
+        return self.solve_l0_local_nodes(alphas, etas, cell, in_mask, out_mask, big_M, parent_lower, starts, max_sweeps, gap_tol, n_cells,
+                                         _need=_l0_need_csr(need, self.n_groups))
+
+    def solve_l0_local_group_prove(self, alphas, etas=0.0, need=None, big_M=100.0, incumbents=None, rel_gap=1e-6, max_nodes=20000, width=32,
+                                   max_sweeps=0, leaf_capacity=0, n_cells=None):
+        """``slm_solve_l0_local_group_prove``: THE LOCAL PROOF WITH GROUPS AND A HIERARCHY -- branch and bound over group nodes for
+        ``slm_solve_l0_local_groups``' objective.  As ``solve_l0_local_prove``, with ``need`` as for ``solve_l0_local_groups``; the
+        dict gains ``group_support`` (``[cells, groups]`` int32: cl(S) of the incumbents) and the leaves' masks are group masks."""
+        return self.solve_l0_local_prove(alphas, etas, big_M, incumbents, rel_gap, max_nodes, width, max_sweeps, leaf_capacity, n_cells,
+                                         _need=_l0_need_csr(need, self.n_groups))
+
     def solve_l0_local_nodes(self, alphas, etas, cell, in_mask, out_mask, big_M=100.0, parent_lower=None, starts=None, max_sweeps=0,
-                             gap_tol=1e-9, n_cells=None):
+                             gap_tol=1e-9, n_cells=None, _need=None):
         """``slm_solve_l0_local_nodes``: ONE BATCH of node relaxations of the local proof (``l0_local_node_kernel``,
         csrc/l0_local_node_kernels.hpp), one wavefront per node, one launch.  Node ``i`` belongs to cell ``cell[i]`` of
         ``(alphas, etas)``; ``in_mask[i]`` and ``out_mask[i]`` are 16 words of 64 bits each (bit ``j & 63`` of word ``j >> 6``:
@@ -1850,14 +1859,14 @@ class Dataset:
             raise ValueError(f"starts has {st.size} entries, expected {nodes * self.p}")
         cnt = max(1, nodes)
         args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), nodes, _l0_local_pad(ce), _l0_local_pad(im), _l0_local_pad(om), pl, st,
-                int(max_sweeps), float(gap_tol))
+                *(() if _need is None else _need), int(max_sweeps), float(gap_tol))  # (_need: the grouped entry, with its two lists)
         (lower, primal, upper, u, stats), _, rc = self._l0_call(
-            "solve_l0_local_nodes", False, args,
+            "solve_l0_local_nodes" if _need is None else "solve_l0_local_group_nodes", False, args,
             [np.zeros(cnt), np.zeros(cnt), np.zeros(cnt), np.zeros((cnt, self.p)), np.zeros((cnt, 2), dtype=np.int32)], records=cnt)
         return lower, primal, upper, u, stats, int(rc)
 
     def solve_l0_local_prove(self, alphas, etas=0.0, big_M=100.0, incumbents=None, rel_gap=1e-6, max_nodes=20000, width=32, max_sweeps=0,
-                             leaf_capacity=0, n_cells=None):
+                             leaf_capacity=0, n_cells=None, _need=None):
         """``slm_solve_l0_local_prove``: THE LOCAL PROOF -- branch and bound on the local bound for every cell ``(alphas[e], etas[e])``,
         one launch of ``l0_local_node_kernel`` a round for the children of every cell.  ``incumbents``: None, or ``[cells, p]`` inside
         the box.  ``leaf_capacity > 0`` asks for the certificate: every dropped node's cell, masks, u and bound.  Returns a dict:
@@ -1874,12 +1883,16 @@ class Dataset:
         lc = C.c_int64(0)
         leaf = [np.zeros(max(1, cap), dtype=np.int32), np.zeros((max(1, cap), 16), dtype=np.uint64), np.zeros((max(1, cap), 16), dtype=np.uint64),
                 np.zeros((max(1, cap), self.p)), np.zeros(max(1, cap))]
-        args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), inc if sized else None, float(rel_gap), int(max_nodes), int(width),
-                int(max_sweeps), cap)
+        args = (cells, _l0_local_pad(al), _l0_local_pad(et), float(big_M), inc if sized else None, *(() if _need is None else _need),
+                float(rel_gap), int(max_nodes), int(width), int(max_sweeps), cap)  # (_need: the grouped entry, with its two lists)
+        gsup = [] if _need is None else [np.zeros((cnt, max(self.n_groups, 1)), dtype=np.int32)]
         outs = [np.zeros((cnt, self.p)), np.zeros(cnt), np.zeros(cnt), np.zeros(cnt, dtype=np.int32), np.zeros(cnt, dtype=np.int32),
-                np.zeros(cnt, dtype=np.int32), *leaf, lc]
-        (beta, obj, low, nodes, rounds, status, *_), _, rc = self._l0_call("solve_l0_local_prove", False, args, outs, records=cnt)
+                np.zeros(cnt, dtype=np.int32), *gsup, *leaf, lc]
+        (beta, obj, low, nodes, rounds, status, *_), _, rc = self._l0_call(
+            "solve_l0_local_prove" if _need is None else "solve_l0_local_group_prove", False, args, outs, records=cnt)
         out = {"beta": beta, "objective": obj, "lower_bound": low, "nodes": nodes, "rounds": rounds, "status": status, "call_status": int(rc)}
+        if gsup:
+            out["group_support"] = gsup[0][:, :self.n_groups]
         if cap:
             k = min(cap, int(lc.value))
             out["leaves"] = {"cell": leaf[0][:k], "in_mask": leaf[1][:k], "out_mask": leaf[2][:k], "u": leaf[3][:k], "lower": leaf[4][:k],
@@ -1927,6 +1940,28 @@ class Dataset:
             out[e]["grows"], out[e]["drops"] = int(won[4]), int(won[5])
         return (betas.reshape(count, cells, ps), icpts.reshape(count, cells), objectives.reshape(count, cells), winners.reshape(count, cells),
                 stats, [out[r * cells:(r + 1) * cells] for r in range(count)])
+
+
+def _l0_need_csr(need, gs):
+    """The need lists of ``gs`` groups as the engine takes them, ``(need_ptr, need_idx)``: from None (no hierarchy: two NULLs), one
+    list per group, or the CSR pair itself."""
+    if need is None:
+        return None, None
+    if isinstance(need, tuple):
+        ptr, idx = (None if v is None else np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in need)
+        if ptr is None or len(ptr) != gs + 1:
+            raise ValueError(f"need_ptr must have {gs + 1} entries")
+        if idx is not None and len(ptr) and len(idx) < max(int(ptr.max()), 0):
+            raise ValueError("need_idx is shorter than need_ptr says")
+    else:
+        lists = [np.asarray(v, dtype=np.int64).reshape(-1) for v in need]
+        if len(lists) != gs:
+            raise ValueError(f"need must have {gs} entries")
+        ptr = np.concatenate([[0], np.cumsum([len(v) for v in lists])]).astype(np.int32)
+        idx = np.ascontiguousarray(np.concatenate(lists + [np.zeros(0, dtype=np.int64)]), dtype=np.int32)
+    if idx is not None and not len(idx):
+        idx = np.zeros(1, dtype=np.int32)  # (an empty array has no address worth handing over)
+    return ptr, idx
 
 
 def _l0_local_cells(alphas, etas, n_cells):

@@ -35,6 +35,9 @@ bound on the objective of ``l0_local_search`` at every cell of its ``(alpha, eta
 ``l0_local_prove`` / ``L0LocalProof`` (``model/_l0_local_prove.py``) are the LOCAL PROOF: branch and bound on that bound, pruned against the
 local search's incumbent, one launch a round for the nodes of every cell; a cell whose tree closes is PROVEN OPTIMAL -- with a ridge or
 a box that binds it does, at ``eta = 0`` with more columns than rows it does not, and the proven gap reached is returned.
+``l0_local_group_prove`` / ``L0LocalGroupProof`` (``model/_l0_local_group_prove.py``) are that proof WITH GROUPS AND A HIERARCHY: branch
+and bound over group nodes for ``l0_local_group_search``'s objective, the hierarchy in the branching; it closes with a ridge or a box
+that binds and not at ``eta = 0`` under a loose box or with deep hierarchies whose free groups are cheap.
 """
 
 from .model._l0_cv import L0ProfileCV, l0_profile_cv  # noqa: F401  (the profiles of every CV fold from one launch; outside __all__)
@@ -42,6 +45,7 @@ from .model._l0_grid_cv import L0ProfileGridCV, l1l0_profile_cv, l2l0_profile_cv
 from .model._l0_local import L0LocalPath, l0_local_search  # noqa: F401  (approximate, up to 1024 columns; outside __all__)
 from .model._l0_local_bound import L0LocalBound, l0_local_bound  # noqa: F401  (a proven lower bound for the local search's grid; outside __all__)
 from .model._l0_local_prove import L0LocalProof, l0_local_prove  # noqa: F401  (branch and bound on the local bound: proven optimal where the tree closes; outside __all__)
+from .model._l0_local_group_prove import L0LocalGroupProof, l0_local_group_prove  # noqa: F401  (the local proof with groups and a hierarchy; outside __all__)
 from .model._l0_local_cv import L0LocalCV, l0_local_cv  # noqa: F401  (the local search of every CV fold from one launch per round; outside __all__)
 from .model._l0_local_groups import L0LocalGroupPath, l0_local_group_search  # noqa: F401  (the local search with groups and a hierarchy; outside __all__)
 from .model._l0_local_groups_cv import L0LocalGroupCV, l0_local_group_cv  # noqa: F401  (its cross-validation, one launch per round; outside __all__)

@@ -17,7 +17,8 @@ GROUP swaps until none helps (csrc/l0_host.hpp, "local groups").  With singleton
 NOTHING IS PROVEN: ``proven_optimal_`` is False and there is no lower bound.  Two things can miss a better fit: the local
 minimum itself, and the SCREEN that spares an inactive group its trial fit (the sum of its columns' one-coordinate gains must
 exceed a quarter of its price) -- a heuristic, since a block can gain together what none of its columns shows alone.  Where the
-columns fit, the exact estimators say by how much.
+columns fit, the exact estimators say by how much; beyond them ``l0_local_group_prove`` (``model/_l0_local_group_prove.py``) proves a
+cell optimal where its tree closes, and returns a proven gap where it does not.
 
 ``groups`` and ``hierarchy`` carry the reference's semantics: labels per column, and entry ``i`` of ``hierarchy`` listing the
 labels that the i-th sorted label needs.  The columns are permuted so that every group is contiguous (the engine takes nothing
@@ -111,6 +112,28 @@ def _warn_cells(infos, A, E):
                       f"{infos[a, e]['status']}): their last points are returned", ConvergenceWarning)
 
 
+def _group_rounds(ds, plan, max_rounds):
+    """The rounds of ``l0_local_group_search`` on the open dataset ``ds`` (``l0_local_group_prove`` runs them on its own handle for
+    its incumbents): ``(coefs [A, E, p] in the permuted order, objectives [A, E], infos [A, E], the objectives after every round)``."""
+    A, E, p, al = plan.A, plan.E, plan.p, plan.al
+
+    def launch(points):
+        b, _, o, _, _, _, info = ds.solve_l0_local_groups([None], [0], plan.cell_alpha, plan.cell_eta, need=plan.need, big_M=plan.big_M,
+                                                          starts=points.reshape(1, A * E, -1, p), swaps=plan.swaps)
+        return np.array(b).reshape(A, E, p), np.array(o).reshape(A, E), np.array(info[0], dtype=object).reshape(A, E)
+
+    coefs, objectives, infos = launch(plan.first)
+    history = [objectives.copy()]
+    for _ in range(int(max_rounds) if plan.moves else 0):
+        c2, o2, i2 = launch(_neighbour_starts(coefs, plan.moves))
+        better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[:, None])
+        coefs[better], objectives[better], infos[better] = c2[better], o2[better], i2[better]
+        history.append(objectives.copy())
+        if not better.any():
+            break
+    return coefs, objectives, infos, history
+
+
 def l0_local_group_search(X, y, *, alphas, groups=None, hierarchy=None, etas=(0.0,), big_M=100, fit_intercept=False, sample_weight=None,
                           starts=None, max_rounds=2, solver_options=None) -> L0LocalGroupPath:
     """A local minimum of the regularised l0 problem WITH GROUPS AND A HIERARCHY at every cell of ``alphas x etas``, for up to
@@ -130,21 +153,7 @@ def l0_local_group_search(X, y, *, alphas, groups=None, hierarchy=None, etas=(0.
     al = plan.al
 
     with plan.spec._l0_dataset(plan.X, plan.y, plan.w, plan.gidx, plan.n_groups, None, plan.dev_options) as (ds, x_mean, y_mean, _, _):
-
-        def launch(points):
-            b, _, o, _, _, _, info = ds.solve_l0_local_groups([None], [0], plan.cell_alpha, plan.cell_eta, need=plan.need, big_M=plan.big_M,
-                                                              starts=points.reshape(1, A * E, -1, p), swaps=plan.swaps)
-            return np.array(b).reshape(A, E, p), np.array(o).reshape(A, E), np.array(info[0], dtype=object).reshape(A, E)
-
-        coefs, objectives, infos = launch(plan.first)
-        history = [objectives.copy()]
-        for _ in range(int(max_rounds) if plan.moves else 0):
-            c2, o2, i2 = launch(_neighbour_starts(coefs, plan.moves))
-            better = o2 < objectives - _IMPROVE * np.maximum(np.abs(objectives), al[:, None])
-            coefs[better], objectives[better], infos[better] = c2[better], o2[better], i2[better]
-            history.append(objectives.copy())
-            if not better.any():
-                break
+        coefs, objectives, infos, history = _group_rounds(ds, plan, max_rounds)
     _warn_cells(infos, A, E)
     take = np.vectorize(lambda d, k: d[k])
     # (with the estimators' own expression, so that an intercept equals a fitted estimator's on the same coefficients)

@@ -23,8 +23,9 @@ close and a few dozen to a few hundred nodes settle the rest.  At ``eta = 0`` wi
 node is then next to free in every FREE column, the bound rises only with depth, and the tree is the full enumeration; the
 call ends at ``max_nodes`` with an honest, smaller proven gap (DESIGN 4d "Local proof" has the measured counts).
 
-Not built: groups and a hierarchy, the cardinality form, the l1 entry, row sets (folds), a Tikhonov matrix, strengthening
-``eta = 0`` by extracting a diagonal from G, feeding the bound into the exact search over supports.
+Not built: the cardinality form, the l1 entry, row sets (folds), a Tikhonov matrix, strengthening
+``eta = 0`` by extracting a diagonal from G, feeding the bound into the exact search over supports.  (Groups and a hierarchy:
+``l0_local_group_prove``, ``model/_l0_local_group_prove.py``.)
 
 Import path: ``sparselm_amd.miqp`` (``l0_local_prove``, ``L0LocalProof``).
 """
